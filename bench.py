@@ -21,6 +21,8 @@ Separate phases, in this order, so that nothing perturbs the number it does not 
      `config4` -- BASELINE.json's config 4: ViT-B, GLOBAL batch 1024 split over the ranks with parallel.shard_bounds (strong
      scaling: 128 per rank at N = 8), all-gather of the top-1 per step;
   4. rank 0, N = 1 only: the CPU oracle on a bounded sample -> `cpu_baseline`.
+--dump-outputs DIR: right after phase 1, rank 0 writes what the last timed step returned (dump_outputs()).  Images and
+weights are seeded, so two builds run with the same arguments can be compared array for array.
 Each rank pins its host threads to the NUMA node of its GPU before anything touches the GPU (no exec, no re-launch).
 """
 import argparse
@@ -63,7 +65,13 @@ def parse_args(argv=None):
     ap.add_argument("--natural-scales", action="store_true",
                     help="the same model with its activation ranges AS CALIBRATED (fixture deit_base_natural) instead of "
                          "power-of-two snapped: the regime of a real checkpoint, phi tables active (DESIGN.md section 2)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy: top1 (every rank's, "
+                         "gathered) and rank 0's logits and logits_f (integers as float64, floats as float32; about 3 MB)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 # ---------------------------------------------------------------------------------------------- launcher
@@ -294,6 +302,35 @@ class _StubEngine:
         return self(images)
 
 
+class _KeepLast:
+    """--dump-outputs: hands the timed path's forwards to `engine` and keeps what the last one returned (DataParallelTop1
+    passes only the top-1 on)"""
+
+    def __init__(self, engine):
+        self.engine, self.last = engine, None
+
+    def __call__(self, images):
+        self.last = self.engine(images)
+        return self.last
+
+    def forward_graph(self, images, resident=False):
+        self.last = self.engine.forward_graph(images, resident=resident)
+        return self.last
+
+
+def dump_outputs(path, top1, local):
+    """DIR/<name>.npy of the last timed step: the gathered top-1 and this rank's (logits, logits_f).  float64 holds every int32
+    exactly; float32 arrays stay float32."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    logits, logits_f, _ = local
+    for name, t in (("top1", top1), ("logits", logits), ("logits_f", logits_f)):
+        if t is None:      # the launcher test's stub engine computes the top-1 only
+            continue
+        a = t.detach().cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float32 if a.dtype == np.float32 else np.float64))
+
+
 def worker(args):
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     pinned = pin_to_numa(local_rank)      # first thing in the rank's process: before torch is imported, before any GPU call
@@ -357,7 +394,8 @@ def worker(args):
             fs, ranges, cfg, meta, _ = load_synthetic_model(MODEL_TAG + ("_natural" if args.natural_scales else ""))
             eng = IntViTEngine(fs, ranges, cfg["embed_dim"], cfg["depth"], cfg["num_heads"], device=dev, max_batch=batch)
         images = torch.from_numpy(synth.make_images(batch, 5000 + rank)).to(dev)  # resident in HBM
-    dp = DataParallelTop1(eng, world, graph=not args.no_graph)
+    keep = _KeepLast(eng) if args.dump_outputs else None
+    dp = DataParallelTop1(eng if keep is None else keep, world, graph=not args.no_graph)
 
     def sync():
         if grouped:
@@ -377,13 +415,16 @@ def worker(args):
     os.close(saved_stdout)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        dp.step(images)
+        top1 = dp.step(images)
     sync()
     dt = time.perf_counter() - t0
     if grouped:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:      # before phase 2: its forwards write the same workspace
+        dump_outputs(args.dump_outputs, top1, keep.last)
+        progress(f"outputs of the last timed step written to {args.dump_outputs}")
 
     # ---- phase 2: dominant-kernel duration, outside the timed region
     progress(f"timed region done: {dt / args.steps * 1e3:.3f} ms per step; probing the dominant kernel")

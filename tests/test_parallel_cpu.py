@@ -141,3 +141,29 @@ def test_bench_launcher_propagates_failure():
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "0"],
                        env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode != 0
+
+
+def test_bench_dump_outputs_stub(tmp_path):
+    """--dump-outputs writes what the last timed step returned, as float64 / float32 .npy: the same seeded inputs give the
+    same arrays whatever --steps / --warmup, and rank 0's shard of a 2-rank run is the 1-rank run's batch"""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR")}
+    env["IVIT_BENCH_STUB"] = "1"
+
+    def run(gpus, steps, warmup, out):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(gpus), "--steps", str(steps),
+                            "--warmup", str(warmup), "--no-extras", "--dump-outputs", str(out)],
+                           env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+
+    run(1, 3, 1, tmp_path / "a")
+    run(1, 1, 0, tmp_path / "b")
+    run(2, 2, 1, tmp_path / "c")
+    a, b, c = (np.load(tmp_path / d / "top1.npy") for d in "abc")
+    assert sorted(os.listdir(tmp_path / "a")) == ["top1.npy"]        # the stub engine returns no logits
+    assert a.dtype == np.float64 and a.shape == (8,) and np.array_equal(a, b)
+    assert c.shape == (16,) and np.array_equal(c[:8], a) and not np.array_equal(c[8:], a)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "0"], env=env, capture_output=True, text=True)
+    assert r.returncode != 0 and "--steps" in r.stderr
