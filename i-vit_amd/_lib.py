@@ -66,6 +66,8 @@ SIGNATURES = {
     "ivit_embed_assemble_i8": [vp, vp, vp, u32, i32, vp, ci, ci, ci, vp],
     "ivit_embed_assemble_i16": [vp, vp, vp, u32, i32, vp, ci, ci, ci, vp],
     "ivit_head_argmax": [vp, vp, ci, ci, vp, vp, vp],
+    "ivit_head_topk": [vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp],
+    "ivit_logits_topk_f32": [vp, ci, ci, ci, ci, vp, vp, vp, vp],
     "ivit_bgemm_qk_i8": [vp, vp, vp, ci, ci, ci, ci, vp],
     "ivit_bgemm_pv_i8": [vp, vp, vp, ci, ci, ci, ci, vp],
     "ivit_f32_to_i32": [vp, i64, ci, vp, ci, ci, vp, vp],

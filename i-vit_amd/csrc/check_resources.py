@@ -61,6 +61,9 @@ def occupancy_rules(path, what):
                 if not m:
                     continue
                 occ, need_no_scratch = (3 if m.group(1) and int(m.group(3)) >= 2 else 4), True      # = their __launch_bounds__
+        elif "head_topk_kernel" in name:
+            # the per-lane top-k lists live in registers (constant indices only): no scratch, full occupancy for any k <= 8
+            occ, need_no_scratch = 8, True
         else:
             m = re.search(r"layernorm_i8_stream_kernelILi(\d+)ELi(\d+)ELi(\d+)ELb([01])ELi(\d+)E", name)
             if not m:

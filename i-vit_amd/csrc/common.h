@@ -117,6 +117,27 @@ IVIT_DEV int wave_allmax_i32(int v)
     const v2u_ q = __builtin_amdgcn_permlane32_swap((unsigned)v, (unsigned)v, false, false);
     return max((int)q.x, (int)q.y);
 }
+// the same butterfly on 64-bit unsigned keys (both halves move with the same DPP control / permlane swap)
+IVIT_DEV unsigned long long wave_allmax_u64(unsigned long long v)
+{
+    typedef unsigned v2u_ __attribute__((ext_vector_type(2)));
+#define IVIT_MAX64(CTRL) { const unsigned lo_ = IVIT_DPP_U32((unsigned)v, CTRL), hi_ = IVIT_DPP_U32((unsigned)(v >> 32), CTRL); \
+                           const unsigned long long o_ = ((unsigned long long)hi_ << 32) | lo_; v = o_ > v ? o_ : v; }
+    IVIT_MAX64(0xB1)
+    IVIT_MAX64(0x4E)
+    IVIT_MAX64(0x141)
+    IVIT_MAX64(0x140)
+#undef IVIT_MAX64
+    const v2u_ a = __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false);
+    const v2u_ b = __builtin_amdgcn_permlane16_swap((unsigned)(v >> 32), (unsigned)(v >> 32), false, false);
+    unsigned long long x = ((unsigned long long)b.x << 32) | a.x, y = ((unsigned long long)b.y << 32) | a.y;
+    v = x > y ? x : y;
+    const v2u_ c = __builtin_amdgcn_permlane32_swap((unsigned)v, (unsigned)v, false, false);
+    const v2u_ d = __builtin_amdgcn_permlane32_swap((unsigned)(v >> 32), (unsigned)(v >> 32), false, false);
+    x = ((unsigned long long)d.x << 32) | c.x;
+    y = ((unsigned long long)d.y << 32) | c.y;
+    return x > y ? x : y;
+}
 
 // The per-channel constants of the int8-output LayerNorm kernels, once per workgroup into LDS: bias_int and the float32 bracket
 // [lo, hi] of the output requantiser's multiplier (the certificate of layernorm_i8_kernel, rowops.hip).  ALL global loads of a pass

@@ -1351,6 +1351,71 @@ __global__ __launch_bounds__(NT) void head_argmax_kernel(const int32_t* acc, con
     }
 }
 
+// classifier top-k: one 64-bit key per logit, the order-preserving u32 of the float (+-0 as one value) above 0xFFFFFFFF - n, so
+// one unsigned compare is "value descending, then index ascending" and no two keys of a row are equal.  Every real key is > 0
+// (the high half of the most negative float is 0x007FFFFF), so 0 marks an empty slot.
+IVIT_DEV unsigned long long topk_key(float v, int n)
+{
+    unsigned u = __float_as_uint(v == 0.0f ? 0.0f : v);
+    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return ((unsigned long long)u << 32) | (0xFFFFFFFFu - (unsigned)n);
+}
+
+// insert into a lane's sorted list h[0] > h[1] > ... > h[K-1]: one reject against h[K-1], then a compare-swap chain (constant
+// register indices only)
+template <int K>
+IVIT_DEV void topk_insert(unsigned long long (&h)[K], unsigned long long key)
+{
+    if (key <= h[K - 1]) return;
+    h[K - 1] = key;
+#pragma unroll
+    for (int j = K - 1; j > 0; --j) {
+        const unsigned long long a = h[j - 1], b = h[j];
+        h[j - 1] = b > a ? b : a;
+        h[j] = b > a ? a : b;
+    }
+}
+
+// one wave per row.  F32 = false: logits = float(acc) * s_acc over the padded width ld (the values head_argmax_kernel writes;
+// -ffp-contract=off keeps the product a single rounding), only n < N enter the selection.  F32 = true: logits read as given.
+// The k heads are merged by k rounds of a wave-wide max of the lanes' first keys; the winning lane (unique: the index is part
+// of the key) drops its head.  hits[r] += 1 when the row's target is its rank-r class (at most one atomic per row).
+template <int K, bool F32>
+__global__ __launch_bounds__(NT) void head_topk_kernel(const int32_t* acc, const float* s_acc, const float* logits_in, int batch,
+                                                       int ld, int N, float* logits_out, int32_t* topk, const int32_t* targets,
+                                                       unsigned long long* hits)
+{
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // scalar: row addresses in SALU
+    for (int row = blockIdx.x * WPB + wave; row < batch; row += gridDim.x * WPB) {
+        unsigned long long h[K];
+#pragma unroll
+        for (int j = 0; j < K; ++j) h[j] = 0;
+        if constexpr (F32) {
+            for (int n = lane; n < N; n += 64) topk_insert<K>(h, topk_key(logits_in[(int64_t)row * ld + n], n));
+        } else {
+            for (int n = lane; n < ld; n += 64) {
+                const float v = (float)acc[(int64_t)row * ld + n] * s_acc[n];
+                if (logits_out) logits_out[(int64_t)row * ld + n] = v;
+                if (n < N) topk_insert<K>(h, topk_key(v, n));
+            }
+        }
+        const int t = targets ? targets[row] : -1;
+        int hit = -1;
+#pragma unroll
+        for (int r = 0; r < K; ++r) {
+            const unsigned long long m = wave_allmax_u64(h[0]);
+            const int n = (int)(0xFFFFFFFFu - (unsigned)m);
+            if (lane == 0) topk[(int64_t)row * K + r] = n;
+            if (n == t) hit = r;
+            const bool pop = h[0] == m;
+#pragma unroll
+            for (int j = 0; j < K - 1; ++j) h[j] = pop ? h[j + 1] : h[j];
+            h[K - 1] = pop ? 0ull : h[K - 1];
+        }
+        if (lane == 0 && hit >= 0) atomicAdd(hits + hit, 1ull);
+    }
+}
+
 // generic QuantAct on int32 (fixedpoint_mul), bit-faithful general form
 __global__ __launch_bounds__(NT) void requant_i32_kernel(const int32_t* z, int64_t rows, int C, const uint32_t* m,
                                                          const int32_t* e, int n_me, const int32_t* z2,
@@ -2058,6 +2123,44 @@ IVIT_EXPORT int ivit_head_argmax(const int32_t* acc, const float* s_acc, int bat
     hipLaunchKernelGGL(head_argmax_kernel, dim3(grid_for_rows(batch)), dim3(NT), 0, ivit_stream(stream), acc, s_acc,
                        batch, N, logits_f32, top1);
     IVIT_CHECK_LAUNCH("ivit_head_argmax");
+}
+
+namespace {
+template <bool F32>
+void launch_head_topk(int k, const int32_t* acc, const float* s_acc, const float* logits_in, int batch, int ld, int N,
+                      float* logits_out, int32_t* topk, const int32_t* targets, uint64_t* hits, hipStream_t s)
+{
+    unsigned long long* h = reinterpret_cast<unsigned long long*>(hits);
+    const dim3 grid(grid_for_rows(batch)), block(NT);
+#define IVIT_TOPK_CASE(K) \
+    case K: hipLaunchKernelGGL((head_topk_kernel<K, F32>), grid, block, 0, s, acc, s_acc, logits_in, batch, ld, N, logits_out, topk, targets, h); break;
+    switch (k) {
+        IVIT_TOPK_CASE(1) IVIT_TOPK_CASE(2) IVIT_TOPK_CASE(3) IVIT_TOPK_CASE(4)
+        IVIT_TOPK_CASE(5) IVIT_TOPK_CASE(6) IVIT_TOPK_CASE(7) IVIT_TOPK_CASE(8)
+    }
+#undef IVIT_TOPK_CASE
+}
+static_assert(IVIT_TOPK_MAX == 8, "launch_head_topk instantiates k = 1..8");
+}  // namespace
+
+IVIT_EXPORT int ivit_head_topk(const int32_t* acc, const float* s_acc, int batch, int ld, int N, int k, float* logits_f32,
+                               int32_t* topk, const int32_t* targets, uint64_t* hits, ivit_stream_t stream)
+{
+    IVIT_REQUIRE(acc && s_acc && topk && batch > 0, "ivit_head_topk: bad operand");
+    IVIT_REQUIRE(k >= 1 && k <= IVIT_TOPK_MAX && k <= N && N <= ld, "ivit_head_topk: bad k=%d / N=%d / ld=%d", k, N, ld);
+    IVIT_REQUIRE((targets == nullptr) == (hits == nullptr), "ivit_head_topk: targets and hits go together");
+    launch_head_topk<false>(k, acc, s_acc, nullptr, batch, ld, N, logits_f32, topk, targets, hits, ivit_stream(stream));
+    IVIT_CHECK_LAUNCH("ivit_head_topk");
+}
+
+IVIT_EXPORT int ivit_logits_topk_f32(const float* logits, int batch, int ld, int N, int k, int32_t* topk, const int32_t* targets,
+                                     uint64_t* hits, ivit_stream_t stream)
+{
+    IVIT_REQUIRE(logits && topk && batch > 0, "ivit_logits_topk_f32: bad operand");
+    IVIT_REQUIRE(k >= 1 && k <= IVIT_TOPK_MAX && k <= N && N <= ld, "ivit_logits_topk_f32: bad k=%d / N=%d / ld=%d", k, N, ld);
+    IVIT_REQUIRE((targets == nullptr) == (hits == nullptr), "ivit_logits_topk_f32: targets and hits go together");
+    launch_head_topk<true>(k, nullptr, nullptr, logits, batch, ld, N, nullptr, topk, targets, hits, ivit_stream(stream));
+    IVIT_CHECK_LAUNCH("ivit_logits_topk_f32");
 }
 
 IVIT_EXPORT int ivit_requant_i32(const int32_t* z, int64_t rows, int C, const uint32_t* m, const int32_t* e, int n_me,

@@ -26,6 +26,7 @@ from . import _lib
 from .graph import GraphReplay
 from .prepare import (IMAGENET_MEAN, IMAGENET_STD, LayerNormParams, dyadic, f32, input_lut_u8, markstein_division_ok, pad_head, phi_is_identity, phi_tables, quant_sym,
                       requant_host, shiftexp2d, shiftexp_band)
+from .topk import TOPK_MAX, HeadTopK
 
 
 def _np(v):
@@ -34,7 +35,7 @@ def _np(v):
     return np.asarray(v)
 
 
-class IntViTEngine(GraphReplay):
+class IntViTEngine(GraphReplay, HeadTopK):
     # fragment-packed weights in the 16x16x64 MFMA order (False / IVIT_FRAGS16=0: the 32x32x32 order everywhere; A/B, tests)
     frags16 = os.environ.get("IVIT_FRAGS16", "1") != "0"
 
@@ -296,6 +297,7 @@ class IntViTEngine(GraphReplay):
             logits=torch.empty(B, self.head["N"], dtype=torch.int32, device=self.dev),
             logits_f=torch.empty(B, self.head["N"], dtype=torch.float32, device=self.dev),
             top1=torch.empty(B, dtype=torch.int32, device=self.dev),
+            topk=torch.empty(B * TOPK_MAX, dtype=torch.int32, device=self.dev),
         )
 
     def _w(self, lin, blocks):
@@ -376,13 +378,17 @@ class IntViTEngine(GraphReplay):
         """images: float32 [B,3,224,224] on the engine's device.  Returns (logits_int32 [B,classes],
         logits_f32 [B,classes], top1 int32 [B]) -- views of the engine's workspace, valid until the
         next call.  `taps` (debug/tests) receives clones of intermediate int8 tensors."""
+        return self._forward(images, taps)
+
+    def _forward(self, images: torch.Tensor, taps: dict | None = None, topk=None):
+        """forward; topk = (k, targets, hits): the classifier launch is the top-k selection (forward_topk)"""
         assert images.is_cuda and images.dtype in (torch.float32, torch.uint8) and images.is_contiguous()
         B = images.shape[0]
         assert images.shape[1:] == (3, self.IMG, self.IMG) and 0 < B <= self.max_batch
         if self.stream_bits == 16:
             if taps is not None:
                 raise NotImplementedError("taps are not recorded on the 16-bit-stream path")
-            return self._forward16(images)
+            return self._forward16(images, topk)
         C, H, hd, T = self.C, self.H, self.hd, self.T
         M = B * T
         ws = self.ws
@@ -457,10 +463,7 @@ class IntViTEngine(GraphReplay):
         hd_ = self.head
         _lib.call("ivit_gemm_i8_i32", _lib.ptr(ws["cls"]), C, _lib.ptr(hd_["W"]), hd_["K"], _lib.ptr(hd_["b"]),
                   _lib.ptr(ws["logits"]), hd_["N"], B, hd_["N"], C, st)
-        _lib.call("ivit_head_argmax", _lib.ptr(ws["logits"]), _lib.ptr(self.head_scale), B, hd_["N"],
-                  _lib.ptr(ws["logits_f"]), _lib.ptr(ws["top1"]), st)
-        nc = self.num_classes
-        return ws["logits"][:B, :nc], ws["logits_f"][:B, :nc], ws["top1"][:B]
+        return self._classify(B, st, topk)
 
     # ------------------------------------------------------------------ 16-bit residual stream
     def _ln16(self, x16, rows, ln, out, st):
@@ -476,7 +479,7 @@ class IntViTEngine(GraphReplay):
             _lib.call("ivit_layernorm_i16_i8", _lib.ptr(x16), rows, C, _lib.ptr(ln["bias"]), _lib.ptr(ln["s"]), _lib.ptr(ln["m"]),
                       _lib.ptr(ln["e"]), _lib.ptr(out), C, 0, 0, 0, 0, st)
 
-    def _forward16(self, images: torch.Tensor):
+    def _forward16(self, images: torch.Tensor, topk=None):
         """stream_bits = 16: the same dataflow with an int16 residual stream.  LayerNorm reads int16 rows (csrc/swin.hip), the
         projection / fc2 GEMMs requantise their accumulators to 16 bits per channel (attn.qact3 / mlp.qact2 at 16 bits) and the
         residual QuantActs are the 16-bit two-operand kernel; qkv / fc1 / attention / GELU are the int8 kernels unchanged."""
@@ -547,9 +550,6 @@ class IntViTEngine(GraphReplay):
         hd_ = self.head
         _lib.call("ivit_gemm_i8_i32", _lib.ptr(ws["cls"]), C, _lib.ptr(hd_["W"]), hd_["K"], _lib.ptr(hd_["b"]),
                   _lib.ptr(ws["logits"]), hd_["N"], B, hd_["N"], C, st)
-        _lib.call("ivit_head_argmax", _lib.ptr(ws["logits"]), _lib.ptr(self.head_scale), B, hd_["N"],
-                  _lib.ptr(ws["logits_f"]), _lib.ptr(ws["top1"]), st)
-        nc = self.num_classes
-        return ws["logits"][:B, :nc], ws["logits_f"][:B, :nc], ws["top1"][:B]
+        return self._classify(B, st, topk)
 
     __call__ = forward

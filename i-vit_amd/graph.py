@@ -7,6 +7,8 @@ from __future__ import annotations
 
 import torch
 
+from .topk import check_request
+
 
 class GraphReplay:
     """Mixin for IntViTEngine / IntSwinEngine."""
@@ -15,9 +17,22 @@ class GraphReplay:
         """resident=False: `images` is copied into the graph's own input buffer before every replay.
         resident=True: the graph reads `images` itself (the caller keeps that tensor alive and refills it in place,
         e.g. a loader's device-side staging buffer) -- no copy per step."""
+        return self._replay(images, resident, (), lambda x, warm: self.forward(x))
+
+    def forward_topk_graph(self, images: torch.Tensor, k: int = 5, targets=None, hits=None, resident: bool = False):
+        """forward_topk as a graph replay.  `targets` / `hits` are read and accumulated in place like a resident image tensor:
+        one graph per (batch size, k, targets pointer, hits pointer); the caller refills `targets` between replays and reads
+        `hits` when it likes.  The warm-up forward outside the capture runs without them, so `hits` only counts replays."""
+        check_request(self.num_classes, images.shape[0], self.dev, k, targets, hits)
+        tag = ("topk", k, 0 if targets is None else targets.data_ptr(), 0 if hits is None else hits.data_ptr())
+        return self._replay(images, resident, tag, lambda x, warm: self.forward_topk(x, k, None if warm else targets,
+                                                                                    None if warm else hits))
+
+    def _replay(self, images, resident, tag, run):
+        """run(x, warm): the forward to capture (warm=True: the uncaptured warm-up call); tag: extends the cache key"""
         B = images.shape[0]
         cache = self.__dict__.setdefault("_graphs", {})
-        key = (B, images.dtype, images.data_ptr()) if resident else (B, images.dtype)
+        key = ((B, images.dtype, images.data_ptr()) if resident else (B, images.dtype)) + tag
         if key not in cache:
             if resident:
                 static_in = images
@@ -27,11 +42,11 @@ class GraphReplay:
             side = torch.cuda.Stream(device=self.dev)
             side.wait_stream(torch.cuda.current_stream(self.dev))
             with torch.cuda.stream(side):           # warm-up outside the capture (lazy module loads, first-use paths)
-                self.forward(static_in)
+                run(static_in, True)
             torch.cuda.current_stream(self.dev).wait_stream(side)
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
-                out = self.forward(static_in)
+                out = run(static_in, False)
             cache[key] = (graph, static_in, out)
         graph, static_in, out = cache[key]
         if not resident:

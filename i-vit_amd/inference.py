@@ -23,9 +23,11 @@ import time
 from typing import Iterable, Optional
 
 import torch
+import torch.distributed as dist
 
-from . import swin_quant, vit_quant
+from . import swin_quant, topk, vit_quant
 from .model_utils import freeze_model
+from .parallel import allreduce_hits, shard_bounds
 
 FACTORIES = {name: getattr(mod, name) for mod in (vit_quant, swin_quant) for name in mod.__all__ if name.endswith("_224")}
 _BW_KEYS = ("patch_embed_bw", "pos_encoding_bw", "block_input_bw", "attention_out_bw", "softmax_bw", "mlp_out_bw",
@@ -135,4 +137,47 @@ def evaluate_dataset(model, data_loader, device, *, print_batch_stats: bool = Tr
               f"avg/img={(total_time / tot if tot else 0.0) * 1000:.2f} ms")
     if tot == 0:
         return 0.0, 0.0, 0.0
+    return 100 * correct1 / tot, 100 * correct3 / tot, 100 * correct5 / tot
+
+
+def evaluate_dataset_parallel(model, data_loader, device, *, scorer=None, print_batch_stats: bool = True):
+    """evaluate_dataset data-parallel over the ranks of the default process group (world 1 without one) -> the same
+    (top-1, top-3, top-5) percentages on every rank.
+
+    Every rank iterates the SAME loader and keeps its parallel.shard_bounds slice of each global batch (images and
+    targets): the slices partition the batch exactly -- no sampler padding, so no image is counted twice.  The rank
+    forwards its slice (an empty slice skips the forward) and the scorer adds that slice's rank-r hits into an int64 [5]
+    device tensor, with no host synchronisation per batch; ONE parallel.allreduce_hits at the end sums hits and image
+    counts over the ranks.
+
+    scorer(logits, targets int32 [b], hits int64 [5], k=5): default topk.count_hits, the HIP selection over the float
+    logits (value descending, equal logits by ascending class -- where evaluate_dataset's torch.topk leaves the order of
+    tied logits unspecified)."""
+    if dist.is_available() and dist.is_initialized():
+        world, rank = dist.get_world_size(), dist.get_rank()
+    else:
+        world, rank = 1, 0
+    scorer = topk.count_hits if scorer is None else scorer
+    hits = torch.zeros(5, dtype=torch.int64, device=device)
+    local = 0
+    start_total = time.perf_counter()
+    model.eval()
+    with torch.no_grad():
+        for imgs, targets in data_loader:
+            lo, hi = shard_bounds(imgs.size(0), world, rank)
+            if hi == lo:
+                continue
+            x = imgs[lo:hi].to(device)
+            t = targets[lo:hi].to(device=device, dtype=torch.int32)
+            scorer(model(x), t, hits, 5)
+            local += hi - lo
+    hits, tot = allreduce_hits(hits, local)
+    total_time = time.perf_counter() - start_total
+    if print_batch_stats and rank == 0 and tot:
+        print(f"Finished evaluation ({world} rank{'s' if world > 1 else ''}): total={total_time:.1f}s | "
+              f"avg/img={total_time / tot * 1000:.2f} ms")
+    if tot == 0:
+        return 0.0, 0.0, 0.0
+    h = hits.tolist()
+    correct1, correct3, correct5 = h[0], sum(h[:3]), sum(h)
     return 100 * correct1 / tot, 100 * correct3 / tot, 100 * correct5 / tot

@@ -48,3 +48,64 @@ class DataParallelTop1:
         else:
             _, _, top1 = self.engine(local_images)
         return gather_top1(top1, self.world, self.counts)
+
+
+def gather_rows(local: torch.Tensor, world: int, counts=None) -> torch.Tensor:
+    """all-gather of per-rank row blocks [B_local, w] -> [sum of the shard sizes, w] in rank order: ONE
+    all_gather_into_tensor, uneven shards padded to the largest as in gather_top1 (`counts`: every rank's shard size)."""
+    assert local.dim() == 2
+    if world == 1 and not (dist.is_available() and dist.is_initialized()):
+        return local
+    w = local.shape[1]
+    if counts is not None and len(set(counts)) > 1:
+        assert len(counts) == world and local.shape[0] == counts[dist.get_rank()]
+        rows = max(counts)
+        padded = torch.zeros(rows, w, dtype=local.dtype, device=local.device)
+        padded[: local.shape[0]] = local
+        out = torch.empty(world * rows, w, dtype=local.dtype, device=local.device)
+        dist.all_gather_into_tensor(out, padded)
+        return torch.cat([out[r * rows: r * rows + c] for r, c in enumerate(counts)])
+    out = torch.empty(world * local.shape[0], w, dtype=local.dtype, device=local.device)
+    dist.all_gather_into_tensor(out, local.contiguous())
+    return out
+
+
+def gather_topk(local_topk: torch.Tensor, world: int, counts=None) -> torch.Tensor:
+    """per-rank top-k class indices (int32 [B_local, k]) -> [B_global, k] in rank order"""
+    return gather_rows(local_topk, world, counts)
+
+
+def gather_logits(local_logits: torch.Tensor, world: int, counts=None) -> torch.Tensor:
+    """per-rank INT32 logits [B_local, classes] -> [B_global, classes] in rank order (the float logits are the same
+    integers times the per-class scale: gather the integers, scale once)"""
+    if local_logits.dtype != torch.int32:
+        raise TypeError("gather_logits takes the int32 logits")
+    return gather_rows(local_logits, world, counts)
+
+
+def allreduce_hits(hits: torch.Tensor, total) -> tuple:
+    """ONE all_reduce(SUM) of [hits[0..k), total] -> (hits int64 [k] summed over ranks, total summed over ranks) on every
+    rank.  hits: the int64 rank-r hit counts of topk.count_hits / forward_topk; total: this rank's image count."""
+    buf = torch.empty(hits.numel() + 1, dtype=torch.int64, device=hits.device)
+    buf[:-1] = hits
+    buf[-1] = int(total)
+    if dist.is_available() and dist.is_initialized():
+        dist.all_reduce(buf, op=dist.ReduceOp.SUM)
+    return buf[:-1], int(buf[-1])
+
+
+class DataParallelTopK:
+    """DataParallelTop1 with the top-k classes of every image: each rank runs forward_topk (graph=True: its graph replay,
+    reading `local_images` -- and `targets` / `hits` -- in place) and ONE all-gather of the int32 [B_local, k] rows follows.
+    targets (int32 [B_local]) with hits (int64 [k]): the rank's hit counts accumulate on its device (allreduce_hits at the
+    end of an evaluation)."""
+
+    def __init__(self, engine, world: int, k: int = 5, graph: bool = False, counts=None):
+        self.engine, self.world, self.k, self.graph, self.counts = engine, world, k, graph, counts
+
+    def step(self, local_images: torch.Tensor, targets=None, hits=None) -> torch.Tensor:
+        if self.graph:
+            _, _, topk = self.engine.forward_topk_graph(local_images, self.k, targets, hits, resident=True)
+        else:
+            _, _, topk = self.engine.forward_topk(local_images, self.k, targets, hits)
+        return gather_topk(topk, self.world, self.counts)

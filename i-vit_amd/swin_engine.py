@@ -26,6 +26,7 @@ from .prepare import (IMAGENET_MEAN, IMAGENET_STD, LayerNormParams, LinearParams
                       phi_tables, quant_sym,
                       requant_host, sym_scale)
 from .synth import IMG_SIZE
+from .topk import TOPK_MAX, HeadTopK
 
 PATCH = 4
 HEAD_DIM = 32
@@ -69,7 +70,7 @@ def window_row_map(B: int, H: int, W: int, ws: int, shift: int) -> np.ndarray:
     return (np.arange(B)[:, None] * (H * W) + idx.reshape(-1)[None, :]).reshape(-1)
 
 
-class IntSwinEngine(GraphReplay):
+class IntSwinEngine(GraphReplay, HeadTopK):
     def __init__(self, float_state, ranges, embed_dim=96, depths=(2, 2, 6, 2), num_heads=(3, 6, 12, 24), window=7,
                  device="cuda:0", max_batch: int = 64):
         self.C0, self.depths, self.heads, self.window = embed_dim, tuple(depths), tuple(num_heads), window
@@ -292,6 +293,7 @@ class IntSwinEngine(GraphReplay):
             logits=torch.empty(B, self.head["N"], dtype=torch.int32, device=self.dev),
             logits_f=torch.empty(B, self.head["N"], dtype=torch.float32, device=self.dev),
             top1=torch.empty(B, dtype=torch.int32, device=self.dev),
+            topk=torch.empty(B * TOPK_MAX, dtype=torch.int32, device=self.dev),
         )
 
     def _compact(self, on=True):
@@ -343,6 +345,10 @@ class IntSwinEngine(GraphReplay):
         """images: float32 [B,3,224,224] on the engine's device.  Returns (logits_int32 [B,1000], logits_f32, top1)
         -- views of the engine's workspace, valid until the next call.  `taps` (tests) receives clones of the
         intermediate integer tensors in the reference's layouts."""
+        return self._forward(images, taps)
+
+    def _forward(self, images: torch.Tensor, taps: dict | None = None, topk=None):
+        """forward; topk = (k, targets, hits): the classifier launch is the top-k selection (forward_topk)"""
         assert images.is_cuda and images.dtype in (torch.float32, torch.uint8) and images.is_contiguous()
         B = images.shape[0]
         assert images.shape[1:] == (3, IMG_SIZE, IMG_SIZE) and 0 < B <= self.max_batch
@@ -487,9 +493,6 @@ class IntSwinEngine(GraphReplay):
         hd = self.head
         _lib.call("ivit_gemm_i8_i32", _lib.ptr(ws["pooled"]), C, _lib.ptr(hd["W"]), hd["K"], _lib.ptr(hd["b"]),
                   _lib.ptr(ws["logits"]), hd["N"], B, hd["N"], hd["K"], st)
-        _lib.call("ivit_head_argmax", _lib.ptr(ws["logits"]), _lib.ptr(self.head_scale), B, hd["N"],
-                  _lib.ptr(ws["logits_f"]), _lib.ptr(ws["top1"]), st)
-        nc = self.num_classes
-        return ws["logits"][:B, :nc], ws["logits_f"][:B, :nc], ws["top1"][:B]
+        return self._classify(B, st, topk)
 
     __call__ = forward

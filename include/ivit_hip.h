@@ -349,6 +349,22 @@ int ivit_embed_assemble_i16(const int16_t* patch, const int32_t* pos_add, const 
 int ivit_head_argmax(const int32_t* acc, const float* s_acc, int batch, int N, float* logits_f32,
                      int32_t* top1, ivit_stream_t stream);
 
+/* Top-k classes per row (scripts/inference.py:245-254 takes top-1/3/5).  acc [batch][ld] int32, s_acc [ld]:
+ *   logits_f32[b][n] = fl(float(acc[b*ld+n]) * s_acc[n]) for n < ld -- the values ivit_head_argmax writes (may be NULL);
+ *   topk [batch][k] int32 = the k largest of logits_f32[b][0..N), value descending, equal values by ascending index
+ *   (= torch.sort(logits[:, :N], descending=True, stable=True).indices[:, :k]; -0.0 == +0.0).  Column 0 is
+ *   ivit_head_argmax's top1.  Columns N..ld-1 (the padded classes of a head whose width is rounded up) are never selected.
+ * targets (int32 [batch], may be NULL) with hits (uint64 [k]): hits[r] += 1 for every row whose target is topk[b][r]; hits
+ * accumulates over calls (never zeroed here); a target outside [0, N) never hits.  Logits must be finite (NaN: unspecified).
+ * IVIT_ERR_INVALID, nothing launched: k outside [1, min(N, IVIT_TOPK_MAX)], N > ld, NULL topk, or exactly one of
+ * targets / hits given. */
+#define IVIT_TOPK_MAX 8
+int ivit_head_topk(const int32_t* acc, const float* s_acc, int batch, int ld, int N, int k, float* logits_f32,
+                   int32_t* topk, const int32_t* targets, uint64_t* hits, ivit_stream_t stream);
+/* the same selection and hit count on float32 logits rows [batch][ld] (module path: any caller's logits) */
+int ivit_logits_topk_f32(const float* logits, int batch, int ld, int N, int k, int32_t* topk, const int32_t* targets,
+                         uint64_t* hits, ivit_stream_t stream);
+
 /* ---- module-level QuantMatMul (quant_modules.py:404-409): batched int8 matmul -> int32 ----------
  * qk: S[b][i][j] = sum_d Q[b][i][d] * K[b][j][d];  pv: O[b][i][d] = sum_j P[b][i][j] * V[b][j][d].
  * All operands dense row-major per batch entry. */
