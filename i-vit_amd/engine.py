@@ -23,19 +23,12 @@ import numpy as np
 import torch
 
 from . import _lib
-from .graph import GraphReplay
-from .prepare import (IMAGENET_MEAN, IMAGENET_STD, LayerNormParams, dyadic, f32, input_lut_u8, markstein_division_ok, pad_head, phi_is_identity, phi_tables, quant_sym,
-                      requant_host, shiftexp2d, shiftexp_band)
-from .topk import TOPK_MAX, HeadTopK
+from .engine_common import EngineBase, _np, block_copy, frag_copy, layernorm
+from .prepare import dyadic, f32, pad_head, phi_tables, quant_sym, requant_host, shiftexp2d, shiftexp_band
+from .topk import TOPK_MAX
 
 
-def _np(v):
-    if isinstance(v, torch.Tensor):
-        return v.detach().cpu().numpy()
-    return np.asarray(v)
-
-
-class IntViTEngine(GraphReplay, HeadTopK):
+class IntViTEngine(EngineBase):
     # fragment-packed weights in the 16x16x64 MFMA order (False / IVIT_FRAGS16=0: the 32x32x32 order everywhere; A/B, tests)
     frags16 = os.environ.get("IVIT_FRAGS16", "1") != "0"
 
@@ -81,15 +74,11 @@ class IntViTEngine(GraphReplay, HeadTopK):
         T = self.T
         s = source.act_scale
 
-        def dev(a, dtype=None):
-            t = torch.from_numpy(np.ascontiguousarray(a))
-            if dtype is not None:
-                t = t.to(dtype)
-            return t.to(self.dev)
+        dev = self._upload
 
         def lin_dev(lp, s_out):
             m, e = lp.requant_to(s_out)
-            return dict(W=dev(lp.W8), b=dev(lp.b32), m=dev(m.view(np.int32)), e=dev(e), K=lp.K, N=lp.W8.shape[0], Wb=None)
+            return dict(W=dev(lp.W8), b=dev(lp.b32), m=dev(m.view(np.int32)), e=dev(e), K=lp.K, N=lp.W8.shape[0])
 
         def phi_dev(s_in):
             """natural (non power-of-two) scale of an operator's input: the reference's operator sees phi(q) = fl(fl(q*s)/s),
@@ -101,32 +90,13 @@ class IntViTEngine(GraphReplay, HeadTopK):
             return dev(t[0]), dev(t[1])
 
         def ln_dev(prefix, s_out, s_in):
-            lp = source.layernorm(prefix, s_out)
-            if sb == 16 and family == "ibert":
-                try:
-                    shift = float(np.asarray(source.tensor(prefix + ".shift")).reshape(-1)[0])
-                except KeyError:
-                    shift = 0.0
-                return dict(kind="ib16", bias=dev(lp.bias_int), s=dev(lp.s_ln), m=dev(lp.m.view(np.int32)), e=dev(lp.e),
-                            s_in=float(s_in), shift_pow2=float(2.0 ** shift), fast_div=int(markstein_division_ok(s_in, 16)))
-            if sb == 16:
-                # I-LayerNorm on the 16-bit stream (csrc/swin.hip); natural input scale: the literal / Markstein-quotient forms
-                d = dict(kind="i16", bias=dev(lp.bias_int), s=dev(lp.s_ln), m=dev(lp.m.view(np.int32)), e=dev(lp.e), s_in=None, fast_div=0)
-                if not phi_is_identity(s_in, 16):
-                    self.natural_sites += 1
-                    d.update(s_in=float(s_in), fast_div=int(markstein_division_ok(s_in, 16)))
-                return d
+            shift = None
             if family == "ibert":
-                # IBERTIntLayerNorm has the same per-channel constants (bias_int, s_out = sqrt(C) / 2^30 * gamma,
-                # ibert_modules.py:145-153) and an overflow shift buffer (:134-137); the kernel works on fl(q * s_in) literally
                 try:
                     shift = float(np.asarray(source.tensor(prefix + ".shift")).reshape(-1)[0])
                 except KeyError:
                     shift = 0.0
-                return dict(kind="ibert", bias=dev(lp.bias_int), s=dev(lp.s_ln), m=dev(lp.m.view(np.int32)), e=dev(lp.e),
-                            s_in=float(s_in), shift_pow2=float(2.0 ** shift), remap=None, phi=None)
-            remap, phi = phi_dev(s_in)
-            return dict(bias=dev(lp.bias_int), s=dev(lp.s_ln), m=dev(lp.m.view(np.int32)), e=dev(lp.e), remap=remap, phi=phi)
+            return self._ln_spec(source.layernorm(prefix, s_out), s_in, sb, shift)
 
         def scalar_me(pre, z):
             m, e = dyadic(pre, z)
@@ -239,27 +209,15 @@ class IntViTEngine(GraphReplay, HeadTopK):
         self.head_scale = dev(hs)
         self.int8_weight_bytes = sum(int(b[k]["W"].numel()) for b in self.blocks for k in ("qkv", "proj", "fc1", "fc2")) \
             + int(self.patch["W"].numel()) + int(self.head["W"].numel())
-        # block-layout copies of the GEMM weights (include/ivit_hip.h IVIT_LAYOUT_BLOCKS): the persistent GEMM then reads
-        # 1 KB contiguous per LDS-DMA instruction instead of 16 half cache lines
-        for lin in [self.patch] + [b[k] for b in self.blocks for k in ("qkv", "proj", "fc1", "fc2")]:
-            if lin["K"] % 64 == 0 and lin["N"] % 16 == 0:
-                lin["Wb"] = torch.empty_like(lin["W"])
-                _lib.call("ivit_tile_operand_i8", _lib.ptr(lin["W"]), lin["K"], lin["N"], lin["K"], _lib.ptr(lin["Wb"]),
-                          self._stream())
-        # MFMA-fragment copies: the weights-in-registers GEMM, 14-21 % faster than the LDS-DMA kernel on block-layout weights; needs
-        # K % 192 == 0, and its 256-channel tiles must not waste more than an eighth of their columns.  IVIT_W_FRAGS16 (the
-        # v_mfma_i32_16x16x64_i8 form: the chip holds a higher clock on that shape, fc1 -7 %, fc2 -5 %) wherever the epilogue writes
-        # int8; the 16-bit-stream epilogue of proj / fc2 exists for the 32x32x32 form (IVIT_W_FRAGS) only
+        # block-layout and MFMA-fragment copies of the GEMM weights (engine_common).  The 16x16x64 fragment order wherever the
+        # epilogue writes int8; the 16-bit-stream epilogue of proj / fc2 exists for the 32x32x32 order only
+        lins = [self.patch] + [b[k] for b in self.blocks for k in ("qkv", "proj", "fc1", "fc2")]
+        for lin in lins:
+            lin["Wb"] = block_copy(lin["W"], self._stream())
         wide = {id(b[k]) for b in self.blocks for k in ("proj", "fc2")} if self.stream_bits == 16 else set()
-        for lin in [self.patch] + [b[k] for b in self.blocks for k in ("qkv", "proj", "fc1", "fc2")]:
-            N, K = lin["N"], lin["K"]
-            lin["Wf"] = None
-            lin["Wf_bit"] = 8 if id(lin) in wide or not self.frags16 else 16
-            # (the 16x16x64 form has 128-channel work items for the widths 256-channel tiles fit badly, round 4: any N % 64 == 0)
-            if K % 192 == 0 and N % 64 == 0 and N >= 128 and (lin["Wf_bit"] == 16 or (N + 255) // 256 * 256 * 8 <= N * 9):
-                lin["Wf"] = torch.empty((N + 63) // 64 * 64 * K, dtype=torch.int8, device=self.dev)
-                _lib.call("ivit_pack_weight_frags_i8" if lin["Wf_bit"] == 8 else "ivit_pack_weight_frags16_i8", _lib.ptr(lin["W"]), K, N, K,
-                          _lib.ptr(lin["Wf"]), self._stream())
+        for lin in lins:
+            narrow = id(lin) not in wide
+            lin["Wf"], lin["Wf_bit"] = frag_copy(lin["W"], self._stream(), order16=self.frags16 and narrow, narrow=narrow)
         self.weight_frags = True      # False: block-layout weights through the LDS-DMA kernel (A/B timing)
         self.block_operands = True    # False: row-major activations / weights everywhere (tests, A/B timing)
         # which producers write their output (a GEMM A operand) in the block layout.  Measured per producer / consumer pair
@@ -274,9 +232,6 @@ class IntViTEngine(GraphReplay, HeadTopK):
         torch.cuda.synchronize(self.dev)
 
     # ------------------------------------------------------------------ plumbing
-    def _stream(self):
-        return _lib.stream_ptr()
-
     def _alloc(self, B):
         C, T = self.C, self.T
         M = B * T
@@ -330,38 +285,33 @@ class IntViTEngine(GraphReplay, HeadTopK):
                   lay | int(a_blocks) | (4 if out_blocks else 0), st)
 
     def _gemm_res(self, A, lda, lin, res, me4, out, M, st, blocks=False, a_blocks=False):
-        C = self.C
-        w, lay = self._w(lin, blocks)
-        lay |= int(a_blocks)
+        """projection / fc2 + its QuantAct + the block's residual QuantAct (in place when out is res).  On the 16-bit stream the
+        GEMM requantises to 16 bits per channel; without fuse_res16 that GEMM and the two-operand residual kernel are separate"""
+        C, r = self.C, me4
+        if self.stream_bits == 16 and not self.fuse_res16:
+            k16 = self.ws["k16"]
+            _lib.call("ivit_gemm_i8_requant_i16", _lib.ptr(A), lda, _lib.ptr(lin["W"]), lin["K"], _lib.ptr(lin["b"]),
+                      _lib.ptr(lin["m"]), _lib.ptr(lin["e"]), _lib.ptr(k16), C, M, C, lin["K"], st)
+            _lib.call("ivit_residual_requant_i16", _lib.ptr(k16), 16, None, None, r[0], r[1], _lib.ptr(res), r[2], r[3],
+                      _lib.ptr(out), M, C, 0, 0, 0, 0, st)
+            return
         probe = self.probe
         if probe is not None:
             # bench.py's separate instrumented pass (never inside its timed region): HIP events around the dominant kernel
             probe.begin("gemm_resid", st)
-        _lib.call("ivit_gemm_i8_requant_residual_ex", _lib.ptr(A), lda, w, lin["K"],
-                  _lib.ptr(lin["b"]), _lib.ptr(lin["m"]), _lib.ptr(lin["e"]), _lib.ptr(res), C,
-                  me4[0], me4[1], me4[2], me4[3], _lib.ptr(out), C, M, lin["N"], lin["K"], lay, st)
+        if self.stream_bits == 8:
+            w, lay = self._w(lin, blocks)
+            _lib.call("ivit_gemm_i8_requant_residual_ex", _lib.ptr(A), lda, w, lin["K"],
+                      _lib.ptr(lin["b"]), _lib.ptr(lin["m"]), _lib.ptr(lin["e"]), _lib.ptr(res), C,
+                      r[0], r[1], r[2], r[3], _lib.ptr(out), C, M, lin["N"], lin["K"], lay | int(a_blocks), st)
+        else:
+            # the weights-in-registers form where it applies, else the 128 x 128-tile kernel (any shape; no block layouts)
+            frags = blocks and self.weight_frags and lin["Wf"] is not None
+            _lib.call("ivit_gemm_i8_requant_i16_residual_i16_ex", _lib.ptr(A), lda, _lib.ptr(lin["Wf"] if frags else lin["W"]),
+                      lin["K"], _lib.ptr(lin["b"]), _lib.ptr(lin["m"]), _lib.ptr(lin["e"]), _lib.ptr(res), C, r[0], r[1], r[2], r[3],
+                      _lib.ptr(out), C, M, C, lin["K"], lin["Wf_bit"] if frags else 0, st)
         if probe is not None:
             probe.end("gemm_resid", st, (M, lin["N"], lin["K"]))
-
-    def _ln(self, x, ldx, rows, ln, out, st, blocks=False):
-        C = self.C
-        if ln.get("kind") == "ibert":
-            _lib.call("ivit_ibert_layernorm_i8", _lib.ptr(x), ldx, rows, C, ln["s_in"], _lib.ptr(ln["bias"]), _lib.ptr(ln["s"]),
-                      ln["shift_pow2"], _lib.ptr(ln["m"]), _lib.ptr(ln["e"]), _lib.ptr(out), C, int(blocks), st)
-            return
-        if ln["remap"] is not None:
-            _lib.call("ivit_layernorm_i8_compat", _lib.ptr(x), ldx, rows, C, _lib.ptr(ln["bias"]), _lib.ptr(ln["s"]),
-                      _lib.ptr(ln["m"]), _lib.ptr(ln["e"]), _lib.ptr(ln["remap"]), _lib.ptr(ln["phi"]), _lib.ptr(out), C,
-                      int(blocks), st)
-            return
-        _lib.call("ivit_layernorm_i8_ex", _lib.ptr(x), ldx, rows, C, _lib.ptr(ln["bias"]), _lib.ptr(ln["s"]),
-                  _lib.ptr(ln["m"]), _lib.ptr(ln["e"]), _lib.ptr(out), C, int(blocks), st)
-
-    def set_input_normalisation(self, mean=IMAGENET_MEAN, std=IMAGENET_STD):
-        """uint8 input: the (mean, std) of the Normalize transform in front of the model (default: ImageNet's).  forward() then
-        accepts uint8 [B,3,224,224] pixel tensors -- a quarter of the bytes of the float32 input -- and quantises them through a
-        3 x 256 table that holds the float pipeline's result per (channel, pixel value): same integers as the float path."""
-        self.input_lut = torch.from_numpy(input_lut_u8(self.s0, mean, std)).to(self.dev)
 
     def _patchify(self, images, B, st):
         ws = self.ws
@@ -381,14 +331,16 @@ class IntViTEngine(GraphReplay, HeadTopK):
         return self._forward(images, taps)
 
     def _forward(self, images: torch.Tensor, taps: dict | None = None, topk=None):
-        """forward; topk = (k, targets, hits): the classifier launch is the top-k selection (forward_topk)"""
+        """forward; topk = (k, targets, hits): the classifier launch is the top-k selection (forward_topk).
+        stream_bits = 16: the same dataflow with an int16 residual stream.  The patch GEMM, the embedding assembly and the
+        projection / fc2 GEMMs write 16 bits (csrc/swin.hip's kernels), LayerNorm reads int16 rows, attention is the "wide"
+        form (softmax_bits); qkv / fc1 / GELU are the int8 kernels unchanged, every operand in row-major order."""
         assert images.is_cuda and images.dtype in (torch.float32, torch.uint8) and images.is_contiguous()
         B = images.shape[0]
         assert images.shape[1:] == (3, self.IMG, self.IMG) and 0 < B <= self.max_batch
-        if self.stream_bits == 16:
-            if taps is not None:
-                raise NotImplementedError("taps are not recorded on the 16-bit-stream path")
-            return self._forward16(images, topk)
+        wide = self.stream_bits == 16
+        if wide and taps is not None:
+            raise NotImplementedError("taps are not recorded on the 16-bit-stream path")
         C, H, hd, T = self.C, self.H, self.hd, self.T
         M = B * T
         ws = self.ws
@@ -396,7 +348,7 @@ class IntViTEngine(GraphReplay, HeadTopK):
 
         # GEMM operands in the block layout whenever the calls go to the persistent kernel (M >= 2048; N >= 128 always)
         blk_l = bool(self.block_operands) and M >= 2048 and C % 64 == 0    # weights (always) and, per producer, activations
-        a_ln, a_at, a_ge = (blk_l and self.block_a[k] for k in ("ln", "attn", "gelu"))
+        a_ln, a_at, a_ge = (blk_l and not wide and self.block_a[k] for k in ("ln", "attn", "gelu"))
 
         def tap(name, t, shape, blocks=False):
             if taps is not None:
@@ -407,16 +359,23 @@ class IntViTEngine(GraphReplay, HeadTopK):
                 taps[name] = t.reshape(-1)[: int(np.prod(shape))].view(shape).clone()
 
         self._patchify(images, B, st)
-        self._gemm(ws["a0"], 3 * self.P * self.P, self.patch, ws["pe"], C, B * self.NP, st,
-                   blocks=bool(self.block_operands) and B * self.NP >= 2048 and C >= 128)
-        tap("patch_embed.qact", ws["pe"], (B, self.NP, C))
-        _lib.call("ivit_embed_assemble_i8", _lib.ptr(ws["pe"]), _lib.ptr(self.pos_add), _lib.ptr(self.cls_row),
-                  self.embed_me[0], self.embed_me[1], _lib.ptr(ws["x"]), B, T, C, st)
-        tap("qact1", ws["x"], (B, T, C))
-        x, x2 = ws["x"], ws["x2"]
+        if wide:
+            pt = self.patch
+            _lib.call("ivit_gemm_i8_requant_i16", _lib.ptr(ws["a0"]), 3 * self.P * self.P, _lib.ptr(pt["W"]), pt["K"], _lib.ptr(pt["b"]),
+                      _lib.ptr(pt["m"]), _lib.ptr(pt["e"]), _lib.ptr(ws["pe16"]), C, B * self.NP, C, pt["K"], st)
+            # the fused epilogue's thread reads a residual chunk and writes the same chunk: in place unless fuse_res16 is off
+            x, x2 = ws["x16"], (ws["x16"] if self.fuse_res16 else ws["y16"])
+        else:
+            self._gemm(ws["a0"], 3 * self.P * self.P, self.patch, ws["pe"], C, B * self.NP, st,
+                       blocks=bool(self.block_operands) and B * self.NP >= 2048 and C >= 128)
+            tap("patch_embed.qact", ws["pe"], (B, self.NP, C))
+            x, x2 = ws["x"], ws["x2"]
+        _lib.call("ivit_embed_assemble_i16" if wide else "ivit_embed_assemble_i8", _lib.ptr(ws["pe16" if wide else "pe"]),
+                  _lib.ptr(self.pos_add), _lib.ptr(self.cls_row), self.embed_me[0], self.embed_me[1], _lib.ptr(x), B, T, C, st)
+        tap("qact1", x, (B, T, C))
         for i, blk in enumerate(self.blocks):
             p = f"blocks.{i}."
-            self._ln(x, C, M, blk["ln1"], ws["h"], st, blocks=a_ln)
+            layernorm(blk["ln1"], x, C, M, C, ws["h"], C, st, blocks=a_ln)
             tap(p + "qact1", ws["h"], (B, T, C), a_ln)
             q = blk["qkv"]
             qw, qlay = self._w(q, blk_l)
@@ -424,24 +383,26 @@ class IntViTEngine(GraphReplay, HeadTopK):
                       _lib.ptr(q["m"]), _lib.ptr(q["e"]), _lib.ptr(ws["qkv"]), T, H, hd, M, 3 * C, C, qlay | int(a_ln), st)
             tap(p + "attn.qkv_headmajor", ws["qkv"], (3, B, H, T, hd))
             a = blk["attn"]
+            # the 16-bit stream's "wide" forms take softmax_bits before the layout flag
+            sm = (self.softmax_bits,) if wide else ()
             if self.family == "ibert":
-                _lib.call("ivit_attention_fused_i8_ibert", _lib.ptr(ws["qkv"]), _lib.ptr(ws["ao"]), B, H, T, hd,
-                          a["ms"][0], a["ms"][1], a["mo"][0], a["mo"][1], _lib.ptr(a["ib_table"]), _lib.ptr(a["band"]), a["band_w"],
-                          int(a_at), st)
+                _lib.call("ivit_attention_fused_i8_ibert_wide" if wide else "ivit_attention_fused_i8_ibert", _lib.ptr(ws["qkv"]),
+                          _lib.ptr(ws["ao"]), B, H, T, hd, a["ms"][0], a["ms"][1], a["mo"][0], a["mo"][1], _lib.ptr(a["ib_table"]),
+                          _lib.ptr(a["band"]), a["band_w"], *sm, int(a_at), st)
             else:
-                _lib.call("ivit_attention_fused_i8_compat_band", _lib.ptr(ws["qkv"]), _lib.ptr(ws["ao"]), B, H, T, hd,
-                          a["ms"][0], a["ms"][1], a["s_attn"], a["mo"][0], a["mo"][1], _lib.ptr(a["exp2d"]), _lib.ptr(a["band"]),
-                          a["band_w"], int(a_at), st)
+                _lib.call("ivit_attention_fused_i8_wide" if wide else "ivit_attention_fused_i8_compat_band", _lib.ptr(ws["qkv"]),
+                          _lib.ptr(ws["ao"]), B, H, T, hd, a["ms"][0], a["ms"][1], a["s_attn"], a["mo"][0], a["mo"][1],
+                          _lib.ptr(a["exp2d"]), _lib.ptr(a["band"]), a["band_w"], *sm, int(a_at), st)
             tap(p + "attn.qact2", ws["ao"], (B, T, C), a_at)
             self._gemm_res(ws["ao"], C, blk["proj"], x, blk["res1"], x2, M, st, blocks=blk_l, a_blocks=a_at)
             tap(p + "qact2", x2, (B, T, C))
-            self._ln(x2, C, M, blk["ln2"], ws["h"], st, blocks=a_ln)
+            layernorm(blk["ln2"], x2, C, M, C, ws["h"], C, st, blocks=a_ln)
             tap(p + "qact3", ws["h"], (B, T, C), a_ln)
             # mlp.fc1 writes the block layout and GELU works IN PLACE on it: the 155 MB intermediate exists once, so the pair
             # (GELU output, fc2 operand) stays inside the 256 MB Infinity Cache (separate buffers: 310 MB; -0.18 ms / forward)
             f1 = blk["fc1"]
             if (self.family == "ibert" and self.fuse_ibert_gelu and taps is None and blk_l and self.weight_frags
-                    and f1.get("Wf") is not None):
+                    and f1["Wf"] is not None):
                 # I-BERT GELU + mlp.qact1 is a map of the requantised byte alone (no row maximum): applied in the fc1 epilogue,
                 # the GELU kernel and its pass over the 4C-wide intermediate disappear
                 g_buf = ws["f1"]
@@ -451,102 +412,19 @@ class IntViTEngine(GraphReplay, HeadTopK):
             else:
                 self._gemm(ws["h"], C, f1, ws["f1"], 4 * C, M, st, a_blocks=a_ln, blocks=blk_l, out_blocks=a_ge)
                 tap(p + "mlp.qact_gelu", ws["f1"], (B, T, 4 * C), a_ge)
-                g_buf = ws["f1"] if self.gelu_in_place else ws["g"]
+                g_buf = ws["f1"] if self.gelu_in_place or wide else ws["g"]
                 _lib.call("ivit_shiftgelu_lut_i8_ex", _lib.ptr(ws["f1"]), 4 * C, M, 4 * C, _lib.ptr(blk["gelu_lut"]),
                           _lib.ptr(g_buf), 4 * C, 3 if a_ge else 0, st)
             tap(p + "mlp.qact1", g_buf, (B, T, 4 * C), a_ge)
             self._gemm_res(g_buf, 4 * C, blk["fc2"], x2, blk["res2"], x, M, st, blocks=blk_l, a_blocks=a_ge)
             tap(p + "qact4", x, (B, T, C))
-        # final LayerNorm is row-wise and only the cls row is consumed (vit_quant.py:302-304)
-        self._ln(x, T * C, B, self.ln_f, ws["cls"], st)
-        tap("qact2", ws["cls"], (B, C))
-        hd_ = self.head
-        _lib.call("ivit_gemm_i8_i32", _lib.ptr(ws["cls"]), C, _lib.ptr(hd_["W"]), hd_["K"], _lib.ptr(hd_["b"]),
-                  _lib.ptr(ws["logits"]), hd_["N"], B, hd_["N"], C, st)
-        return self._classify(B, st, topk)
-
-    # ------------------------------------------------------------------ 16-bit residual stream
-    def _ln16(self, x16, rows, ln, out, st):
-        C = self.C
-        if ln["kind"] == "ib16":
-            _lib.call("ivit_ibert_layernorm_i16_i8_ex", _lib.ptr(x16), C, rows, C, ln["s_in"], _lib.ptr(ln["bias"]), _lib.ptr(ln["s"]),
-                      ln["shift_pow2"], _lib.ptr(ln["m"]), _lib.ptr(ln["e"]), _lib.ptr(out), C, ln["fast_div"], st)
-            return
-        if ln["s_in"] is not None:
-            _lib.call("ivit_layernorm_i16_i8_compat", _lib.ptr(x16), rows, C, ln["s_in"], ln["fast_div"], _lib.ptr(ln["bias"]),
-                      _lib.ptr(ln["s"]), _lib.ptr(ln["m"]), _lib.ptr(ln["e"]), _lib.ptr(out), C, 0, 0, 0, 0, st)
+        # final LayerNorm is row-wise and only the cls row is consumed (vit_quant.py:302-304); the int16 kernels want dense rows
+        if wide:
+            ws["cls16"][:B].copy_(x.view(-1, T, C)[:B, 0])
+            layernorm(self.ln_f, ws["cls16"], C, B, C, ws["cls"], C, st, blocks=False)
         else:
-            _lib.call("ivit_layernorm_i16_i8", _lib.ptr(x16), rows, C, _lib.ptr(ln["bias"]), _lib.ptr(ln["s"]), _lib.ptr(ln["m"]),
-                      _lib.ptr(ln["e"]), _lib.ptr(out), C, 0, 0, 0, 0, st)
-
-    def _forward16(self, images: torch.Tensor, topk=None):
-        """stream_bits = 16: the same dataflow with an int16 residual stream.  LayerNorm reads int16 rows (csrc/swin.hip), the
-        projection / fc2 GEMMs requantise their accumulators to 16 bits per channel (attn.qact3 / mlp.qact2 at 16 bits) and the
-        residual QuantActs are the 16-bit two-operand kernel; qkv / fc1 / attention / GELU are the int8 kernels unchanged."""
-        B = images.shape[0]
-        ws, C, H, hd, T = self.ws, self.C, self.H, self.hd, self.T
-        M = B * T
-        st = self._stream()
-        big = bool(self.block_operands) and M >= 2048 and C % 64 == 0
-        self._patchify(images, B, st)
-        pt = self.patch
-        _lib.call("ivit_gemm_i8_requant_i16", _lib.ptr(ws["a0"]), 3 * self.P * self.P, _lib.ptr(pt["W"]), pt["K"], _lib.ptr(pt["b"]),
-                  _lib.ptr(pt["m"]), _lib.ptr(pt["e"]), _lib.ptr(ws["pe16"]), C, B * self.NP, C, pt["K"], st)
-        _lib.call("ivit_embed_assemble_i16", _lib.ptr(ws["pe16"]), _lib.ptr(self.pos_add), _lib.ptr(self.cls_row),
-                  self.embed_me[0], self.embed_me[1], _lib.ptr(ws["x16"]), B, T, C, st)
-        x = ws["x16"]
-        inplace = bool(self.fuse_res16)
-
-        def gemm_res16(A, lda, lin, r, res, out):
-            # projection / fc2 + its 16-bit QuantAct + the block's residual QuantAct: one kernel in the weights-in-registers form
-            if self.fuse_res16:
-                frags = big and self.weight_frags and lin.get("Wf") is not None      # else: the 128 x 128-tile kernel, any shape
-                probe = self.probe
-                if probe is not None:     # bench.py's instrumented pass, as in _gemm_res
-                    probe.begin("gemm_resid", st)
-                _lib.call("ivit_gemm_i8_requant_i16_residual_i16_ex", _lib.ptr(A), lda, _lib.ptr(lin["Wf"] if frags else lin["W"]), lin["K"],
-                          _lib.ptr(lin["b"]), _lib.ptr(lin["m"]), _lib.ptr(lin["e"]), _lib.ptr(res), C, r[0], r[1], r[2], r[3], _lib.ptr(out),
-                          C, M, C, lin["K"], lin["Wf_bit"] if frags else 0, st)
-                if probe is not None:
-                    probe.end("gemm_resid", st, (M, C, lin["K"]))
-                return
-            _lib.call("ivit_gemm_i8_requant_i16", _lib.ptr(A), lda, _lib.ptr(lin["W"]), lin["K"], _lib.ptr(lin["b"]),
-                      _lib.ptr(lin["m"]), _lib.ptr(lin["e"]), _lib.ptr(ws["k16"]), C, M, C, lin["K"], st)
-            _lib.call("ivit_residual_requant_i16", _lib.ptr(ws["k16"]), 16, None, None, r[0], r[1], _lib.ptr(res), r[2], r[3],
-                      _lib.ptr(out), M, C, 0, 0, 0, 0, st)
-
-        for blk in self.blocks:
-            self._ln16(x, M, blk["ln1"], ws["h"], st)
-            q = blk["qkv"]
-            qw, qlay = self._w(q, big)
-            _lib.call("ivit_gemm_i8_requant_qkv_ex", _lib.ptr(ws["h"]), C, qw, q["K"], _lib.ptr(q["b"]),
-                      _lib.ptr(q["m"]), _lib.ptr(q["e"]), _lib.ptr(ws["qkv"]), T, H, hd, M, 3 * C, C, qlay, st)
-            a = blk["attn"]
-            if self.family == "ibert":
-                _lib.call("ivit_attention_fused_i8_ibert_wide", _lib.ptr(ws["qkv"]), _lib.ptr(ws["ao"]), B, H, T, hd,
-                          a["ms"][0], a["ms"][1], a["mo"][0], a["mo"][1], _lib.ptr(a["ib_table"]), _lib.ptr(a["band"]), a["band_w"],
-                          self.softmax_bits, 0, st)
-            else:
-                _lib.call("ivit_attention_fused_i8_wide", _lib.ptr(ws["qkv"]), _lib.ptr(ws["ao"]), B, H, T, hd,
-                          a["ms"][0], a["ms"][1], a["s_attn"], a["mo"][0], a["mo"][1], _lib.ptr(a["exp2d"]), _lib.ptr(a["band"]),
-                          a["band_w"], self.softmax_bits, 0, st)
-            y = x if inplace else ws["y16"]     # the fused epilogue's thread reads a residual chunk and writes the same chunk
-            gemm_res16(ws["ao"], C, blk["proj"], blk["res1"], x, y)
-            self._ln16(y, M, blk["ln2"], ws["h"], st)
-            f1 = blk["fc1"]
-            if self.family == "ibert" and self.fuse_ibert_gelu and big and self.weight_frags and f1.get("Wf") is not None:
-                # I-BERT GELU + mlp.qact1 as a byte map in the fc1 epilogue (see forward)
-                _lib.call("ivit_gemm_i8_requant_lut_ex", _lib.ptr(ws["h"]), C, _lib.ptr(f1["Wf"]), f1["K"], _lib.ptr(f1["b"]),
-                          _lib.ptr(f1["m"]), _lib.ptr(f1["e"]), _lib.ptr(blk["gelu_lut"]), _lib.ptr(ws["f1"]), 4 * C, M, f1["N"], f1["K"],
-                          f1["Wf_bit"], st)
-            else:
-                self._gemm(ws["h"], C, f1, ws["f1"], 4 * C, M, st, a_blocks=False, blocks=big, out_blocks=False)
-                _lib.call("ivit_shiftgelu_lut_i8_ex", _lib.ptr(ws["f1"]), 4 * C, M, 4 * C, _lib.ptr(blk["gelu_lut"]),
-                          _lib.ptr(ws["f1"]), 4 * C, 0, st)
-            gemm_res16(ws["f1"], 4 * C, blk["fc2"], blk["res2"], y, x)
-        # final LayerNorm: only the cls rows are consumed (vit_quant.py:302-304); the int16 kernel wants dense rows
-        ws["cls16"][:B].copy_(x.view(-1, T, C)[:B, 0])
-        self._ln16(ws["cls16"], B, self.ln_f, ws["cls"], st)
+            layernorm(self.ln_f, x, T * C, B, C, ws["cls"], C, st, blocks=False)
+        tap("qact2", ws["cls"], (B, C))
         hd_ = self.head
         _lib.call("ivit_gemm_i8_i32", _lib.ptr(ws["cls"]), C, _lib.ptr(hd_["W"]), hd_["K"], _lib.ptr(hd_["b"]),
                   _lib.ptr(ws["logits"]), hd_["N"], B, hd_["N"], C, st)

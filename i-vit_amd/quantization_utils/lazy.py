@@ -34,6 +34,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from ..engine_common import frag_copy
 from ..prepare import (LayerNormParams, LinearParams, dyadic, f32, phi_tables, quant_sym, shiftexp2d, shiftexp_band,
                        sym_scale)
 
@@ -305,11 +306,6 @@ def _key(*hosts):
     return tuple(np.asarray(h, f32).tobytes() if h is not None else None for h in hosts)
 
 
-def _frag_ok(N, K):
-    """the weights-in-registers GEMM on v_mfma_i32_16x16x64_i8 (256- or 128-channel work items, chosen by the launcher)"""
-    return K % 192 == 0 and N % 64 == 0 and N >= 128
-
-
 def linear_consts(lin, s_in, device):
     """integer weights of a QuantLinear / QuantConv2d for input scale s_in (host float32): W8 row-major (+ the 16x16x64
     fragment copy where the weights-in-registers GEMM applies), b32, s_acc"""
@@ -317,11 +313,9 @@ def linear_consts(lin, s_in, device):
         lp = LinearParams(lin.weight.detach().cpu().numpy(), None if lin.bias is None else lin.bias.detach().cpu().numpy(), s_in)
         N, K = lp.W8.shape
         lin._publish(lp, device)           # the buffers the reference rewrites on every call
-        d = dict(lp=lp, N=N, K=K, W=_dev(lp.W8, device), b=None if lp.b32 is None else _dev(lp.b32, device), Wf=None,
+        d = dict(lp=lp, N=N, K=K, W=_dev(lp.W8, device), b=None if lp.b32 is None else _dev(lp.b32, device),
                  s_acc=QS.make(lp.s_acc, device))
-        if K % 64 == 0 and _frag_ok(N, K):
-            d["Wf"] = torch.empty((N + 63) // 64 * 64 * K, dtype=torch.int8, device=device)
-            _lib.call("ivit_pack_weight_frags16_i8", _lib.ptr(d["W"]), K, N, K, _lib.ptr(d["Wf"]), _st())
+        d["Wf"], _ = frag_copy(d["W"], _st())       # every consumer here has an int8 epilogue
         return d
     return _cache(lin, ("lin", lin.weight._version, None if lin.bias is None else lin.bias._version, _key(s_in), str(device)), build)
 

@@ -21,22 +21,15 @@ import numpy as np
 import torch
 
 from . import _lib
-from .graph import GraphReplay
-from .prepare import (IMAGENET_MEAN, IMAGENET_STD, LayerNormParams, LinearParams, dyadic, f32, input_lut_u8, markstein_division_ok, pad_head, phi_is_identity, phi_table, window_shiftexp_band,
-                      phi_tables, quant_sym,
-                      requant_host, sym_scale)
+from .engine_common import EngineBase, _np, block_copy, frag_copy, layernorm
+from .prepare import (LayerNormParams, LinearParams, dyadic, f32, pad_head, phi_is_identity, phi_table, phi_tables, quant_sym,
+                      requant_host, sym_scale, window_shiftexp_band)
 from .synth import IMG_SIZE
-from .topk import TOPK_MAX, HeadTopK
+from .topk import TOPK_MAX
 
 PATCH = 4
 HEAD_DIM = 32
 IDENT = (1 << 30, 30)  # dyadic 1.0
-
-
-def _np(v):
-    if isinstance(v, torch.Tensor):
-        return v.detach().cpu().numpy()
-    return np.asarray(v)
 
 
 def _pad64(k):
@@ -70,7 +63,7 @@ def window_row_map(B: int, H: int, W: int, ws: int, shift: int) -> np.ndarray:
     return (np.arange(B)[:, None] * (H * W) + idx.reshape(-1)[None, :]).reshape(-1)
 
 
-class IntSwinEngine(GraphReplay, HeadTopK):
+class IntSwinEngine(EngineBase):
     def __init__(self, float_state, ranges, embed_dim=96, depths=(2, 2, 6, 2), num_heads=(3, 6, 12, 24), window=7,
                  device="cuda:0", max_batch: int = 64):
         self.C0, self.depths, self.heads, self.window = embed_dim, tuple(depths), tuple(num_heads), window
@@ -84,34 +77,19 @@ class IntSwinEngine(GraphReplay, HeadTopK):
             lo, hi = R[name]
             return sym_scale(lo, hi, bits)
 
-        def dev(a, dtype=None):
-            t = torch.from_numpy(np.ascontiguousarray(a))
-            if dtype is not None:
-                t = t.to(dtype)
-            return t.to(self.dev)
+        dev = self._upload
 
         def lin_host(name, s_in):
             lp = LinearParams(P[name + ".weight"], P.get(name + ".bias"), s_in)
             Kp = _pad64(lp.K)
             W = np.zeros((lp.W8.shape[0], Kp), np.int8)   # zero K-padding: the operand's pad columns never contribute
             W[:, :lp.K] = lp.W8
-            d = dict(W=dev(W), b=None if lp.b32 is None else dev(lp.b32), K=Kp, N=W.shape[0], Wb=None)
-            if d["N"] >= 128 and d["N"] % 16 == 0:
-                # block-layout copy (include/ivit_hip.h IVIT_LAYOUT_BLOCKS) for the calls that reach the persistent GEMM
-                d["Wb"] = torch.empty_like(d["W"])
-                _lib.call("ivit_tile_operand_i8", _lib.ptr(d["W"]), Kp, d["N"], Kp, _lib.ptr(d["Wb"]), _lib.stream_ptr())
-            d["Wf"] = None
-            N = d["N"]
-            wf_bit = 8 if name.endswith("attn.proj") else 16
-            narrow_ok = name.endswith(("attn.qkv", "mlp.fc1"))      # int8 epilogues; mlp.fc2 (16-bit residual epilogue) has full tiles only
-            if Kp % 192 == 0 and N % 64 == 0 and N >= 128 and (narrow_ok or (N + 255) // 256 * 256 * 8 <= N * 9):
-                # MFMA-fragment copy: the weights-in-registers GEMM (qkv / fc1 of stages 1-3, all of stage 3).  The 16x16x64
-                # order (IVIT_W_FRAGS16; 128-channel work items where 256-channel tiles fit badly, round 4) except for attn.proj,
-                # whose fused 16-bit epilogue exists for the 32x32x32 form only
-                d["Wf_bit"] = wf_bit
-                d["Wf"] = torch.empty((N + 63) // 64 * 64 * Kp, dtype=torch.int8, device=self.dev)
-                _lib.call("ivit_pack_weight_frags_i8" if d["Wf_bit"] == 8 else "ivit_pack_weight_frags16_i8", _lib.ptr(d["W"]), Kp, N, Kp,
-                          _lib.ptr(d["Wf"]), _lib.stream_ptr())
+            d = dict(W=dev(W), b=None if lp.b32 is None else dev(lp.b32), K=Kp, N=W.shape[0])
+            d["Wb"] = block_copy(d["W"], self._stream())      # for the calls that reach the persistent GEMM
+            # MFMA-fragment copy (qkv / fc1 of stages 1-3, all of stage 3): the 16x16x64 order except for attn.proj, whose fused
+            # 16-bit epilogue exists for the 32x32x32 order only; 128-channel work items for the int8 epilogues of qkv / fc1
+            d["Wf"], d["Wf_bit"] = frag_copy(d["W"], self._stream(), order16=not name.endswith("attn.proj"),
+                                             narrow=name.endswith(("attn.qkv", "mlp.fc1")))
             return lp, d
 
         def lin_dev(name, s_in, s_out):
@@ -129,17 +107,7 @@ class IntSwinEngine(GraphReplay, HeadTopK):
             """s_in: scale of the LayerNorm's input.  If fl(fl(q*s_in)/s_in) != q for some q of that width, the reference's
             LayerNorm sees those neighbouring floats (ivit_modules.py:36-38): 16-bit inputs take the literal kernel, the 8-bit
             patch norm the table form of the DeiT engine."""
-            lp = LayerNormParams(P[prefix + ".weight"], P[prefix + ".bias"], s_out)
-            d = dict(bias=dev(lp.bias_int), s=dev(lp.s_ln), m=dev(lp.m.view(np.int32)), e=dev(lp.e), s_in=None, remap=None, phi=None,
-                     fast_div=0)
-            if not phi_is_identity(s_in, bits_in):
-                self.natural_sites += 1
-                d["s_in"] = float(s_in)
-                d["fast_div"] = int(bits_in == 16 and markstein_division_ok(s_in, 16))
-                if bits_in == 8:
-                    remap, phi = phi_tables(s_in)
-                    d.update(remap=dev(remap), phi=dev(phi))
-            return d
+            return self._ln_spec(LayerNormParams(P[prefix + ".weight"], P[prefix + ".bias"], s_out), s_in, bits_in)
 
         def sme(pre, z):
             m, e = dyadic(pre, z)
@@ -270,9 +238,6 @@ class IntSwinEngine(GraphReplay, HeadTopK):
         torch.cuda.synchronize(self.dev)
 
     # ------------------------------------------------------------------ plumbing
-    def _stream(self):
-        return _lib.stream_ptr()
-
     def _alloc(self, B):
         C0 = self.C0
         M0 = B * (IMG_SIZE // PATCH) ** 2
@@ -328,19 +293,7 @@ class IntSwinEngine(GraphReplay, HeadTopK):
         _lib.call("ivit_gemm_i8_requant_ex", _lib.ptr(A), lda, w, lin["K"], _lib.ptr(lin["b"]),
                   _lib.ptr(lin["m"]), _lib.ptr(lin["e"]), _lib.ptr(out), ldo, M, lin["N"], lin["K"], lay, st)
 
-    def _ln16(self, x, rows, C, ln, out, ldo, st, H=0, W=0, ws=0, shift=0, outer=0):
-        if ln["s_in"] is not None:       # natural input scale: the literal kernel (csrc/swin.hip)
-            _lib.call("ivit_layernorm_i16_i8_compat", _lib.ptr(x), rows, C, ln["s_in"], ln["fast_div"] | (outer << 8), _lib.ptr(ln["bias"]), _lib.ptr(ln["s"]),
-                      _lib.ptr(ln["m"]), _lib.ptr(ln["e"]), _lib.ptr(out), ldo, H, W, ws, shift, st)
-            return
-        _lib.call("ivit_layernorm_i16_i8", _lib.ptr(x), rows, C, _lib.ptr(ln["bias"]), _lib.ptr(ln["s"]),
-                  _lib.ptr(ln["m"]), _lib.ptr(ln["e"]), _lib.ptr(out), ldo, H, W, ws, shift, st)
-
     # ------------------------------------------------------------------ forward
-    def set_input_normalisation(self, mean=IMAGENET_MEAN, std=IMAGENET_STD):
-        """uint8 input (see IntViTEngine.set_input_normalisation): the Normalize transform folded into the input table"""
-        self.input_lut = torch.from_numpy(input_lut_u8(self.s0, mean, std)).to(self.dev)
-
     def forward(self, images: torch.Tensor, taps: dict | None = None):
         """images: float32 [B,3,224,224] on the engine's device.  Returns (logits_int32 [B,1000], logits_f32, top1)
         -- views of the engine's workspace, valid until the next call.  `taps` (tests) receives clones of the
@@ -377,14 +330,8 @@ class IntSwinEngine(GraphReplay, HeadTopK):
                       self.inv_s0, st)
         self._gemm(ws["a0"], 64, self.patch, ws["pe"], C0, M, st)
         tap("patch_embed.qact_before_norm", ws["pe"], M, C0)
-        ln = self.patch_ln
-        if ln["remap"] is not None:
-            _lib.call("ivit_layernorm_i8_compat", _lib.ptr(ws["pe"]), C0, M, C0, _lib.ptr(ln["bias"]), _lib.ptr(ln["s"]),
-                      _lib.ptr(ln["m"]), _lib.ptr(ln["e"]), _lib.ptr(ln["remap"]), _lib.ptr(ln["phi"]), _lib.ptr(ws["pn"]), C0,
-                      (M // B) << 8, st)   # IVIT_LN_OUTER_MEAN(L): the reference reduces over the transposed view of layers_quant.py:198
-        else:
-            _lib.call("ivit_layernorm_i8", _lib.ptr(ws["pe"]), C0, M, C0, _lib.ptr(ln["bias"]), _lib.ptr(ln["s"]),
-                      _lib.ptr(ln["m"]), _lib.ptr(ln["e"]), _lib.ptr(ws["pn"]), C0, st)
+        # outer: the reference reduces over the transposed view of layers_quant.py:198
+        layernorm(self.patch_ln, ws["pe"], C0, M, C0, ws["pn"], C0, st, outer=M // B)
         tap("patch_embed.qact", ws["pn"], M, C0)
         x, x2 = ws["x"], ws["x2"]
         _lib.call("ivit_requant_i8_i16", _lib.ptr(ws["pn"]), self.stem_me[0], self.stem_me[1], _lib.ptr(x), M * C0, st)
@@ -407,7 +354,7 @@ class IntSwinEngine(GraphReplay, HeadTopK):
                 # strided stream) as the first operand, whose layout torch then gives the sum; only the patch merging's cat makes the
                 # stream contiguous.  Their float32 means run in torch's outer-reduction order (IVIT_LN_OUTER_MEAN)
                 outer = H * W if li == 0 else 0
-                self._ln16(x, M, C, blk["ln1"], ws["h"], ld, st, H, W, win, shift, outer=outer)
+                layernorm(blk["ln1"], x, C, M, C, ws["h"], ld, st, H=H, W=W, ws=win, shift=shift, outer=outer)
                 tap(p + "qact1", ws["h"], M, C, ld, perm)
                 q = blk["qkv"]
                 qw, qlay = self._w(q, M)
@@ -455,7 +402,7 @@ class IntSwinEngine(GraphReplay, HeadTopK):
                     _lib.call("ivit_residual_requant_i16", _lib.ptr(ws["acc"]), 32, _lib.ptr(pj["m"]), _lib.ptr(pj["e"]),
                               r[0], r[1], _lib.ptr(x), r[2], r[3], _lib.ptr(x2), M, C, H, W, win, shift, st)
                 tap(p + "qact2", x2, M, C)
-                self._ln16(x2, M, C, blk["ln2"], ws["h"], ld, st, outer=outer)
+                layernorm(blk["ln2"], x2, C, M, C, ws["h"], ld, st, outer=outer)
                 tap(p + "qact3", ws["h"], M, C, ld)
                 self._gemm(ws["h"], ld, blk["fc1"], ws["f1"], 4 * C, M, st)
                 tap(p + "mlp.qact_gelu", ws["f1"], M, 4 * C)
@@ -478,14 +425,14 @@ class IntSwinEngine(GraphReplay, HeadTopK):
                 p = f"layers.{li}.downsample."
                 _lib.call("ivit_patch_merge_i16", _lib.ptr(x), _lib.ptr(ws["xm"]), B, H, W, C, st)
                 M4 = M // 4
-                self._ln16(ws["xm"], M4, 4 * C, dn["ln"], ws["hm"], 4 * C, st)
+                layernorm(dn["ln"], ws["xm"], 4 * C, M4, 4 * C, ws["hm"], 4 * C, st)
                 tap(p + "qact1", ws["hm"], M4, 4 * C)
                 self._gemm(ws["hm"], 4 * C, dn["red"], ws["red"], 2 * C, M4, st)
                 tap(p + "qact2", ws["red"], M4, 2 * C)
                 _lib.call("ivit_requant_i8_i16", _lib.ptr(ws["red"]), IDENT[0], IDENT[1], _lib.ptr(x), M4 * 2 * C, st)
 
         C, T = self.C_last, self.T_last
-        self._ln16(x, B * T, C, self.ln_f, ws["hN"], C, st)
+        layernorm(self.ln_f, x, C, B * T, C, ws["hN"], C, st)
         tap("qact2", ws["hN"], B * T, C)
         _lib.call("ivit_avgpool_requant_i8", _lib.ptr(ws["hN"]), _lib.ptr(ws["pooled"]), B, T, C, self.pool_me[0],
                   self.pool_me[1], st)
