@@ -603,6 +603,264 @@ int attention_parts(int batch_heads, int tokens, int slots)
     return best;
 }
 
+// ---- long rows: 208 <= T <= 1025 tokens (384 / 16 -> 577, 224 / 8 -> 785, 512 / 16 -> 1025)
+// The same arithmetic as attention_kernel MODE 0 / 1 / 2 with PB = 8, but a row no longer fits 13 x 4 int registers.  After the
+// requantisation a score is one byte: k + 128 in [0, 255], and a lane keeps its four keys of a key tile packed in ONE dword
+// (sc[kt], byte r = key 16 kt + 4 g + r): a 1025-key row is 65 dwords in each of its four lanes.  Three passes over those registers:
+//   1. S^T tile = K . Q^T (one 16x16x64 MFMA per key tile), requantised, packed; row max over the packed bytes' sources
+//   2. idx = max - k for four keys at once (the row max replicated into every byte: no byte borrows), exp_int from the
+//      table, exact row sum: 16 exponents (<= 16 * 2^27) in u32, then u64 (1025 * 255 * 2^15 exceeds 2^32)
+//   3. the exponents again from idx, 8-bit probabilities, P . V per key step of 64 (attention_kernel's operand orders)
+// K and V^T of one (image, head) sit whole in LDS (150 KiB at 1025 tokens) and are shared by the waves of one workgroup per
+// CU (16 waves up to 655 tokens, 12 above: registers), each wave walking query tiles of 16.  V^T rows are padded to a multiple of 256 bytes, so that
+// attention_kernel's chunk swizzle j ^ (d & 15) stays inside the row.  MODE 0: power-of-two input scale, exponent table in LDS;
+// MODE 1: natural scale, the host's table gathered from global memory (band form when band_w > 0, else the [256][256] exp2d):
+// the band rows of every wave do not fit next to K and V^T.
+constexpr int LONG_T_MIN = 208, LONG_T_MAX = 1025;
+constexpr int LONG_LUT_BYTES = 2 * 256 * 4;
+
+struct LongArgs {
+    const int8_t* qkv;
+    int8_t* out;
+    int batch, heads, tokens;
+    double Ms, Mo;
+    float Ms32;                // RQ32: Ms as float32 (a power of two)
+    int x0;                    // floor(-1/s_attn)
+    int out_blocks;            // output in the GEMM block layout (common.h: ivit_block_offset)
+    const unsigned* table;     // MODE 1: band[(qmax + 128) * band_w + j] (band_w > 0) or exp2d[(qmax + 128) * 256 + q + 128]
+    int band_w;
+    int parts;                 // workgroups per (image, head)
+    int vt_row;                // bytes per d row of V^T: ceil(key steps / 4) * 256
+};
+
+// NKT: full key tiles held in registers (T >> 4 <= NKT); NTH: threads per workgroup, one workgroup per CU (1024: 128 VGPRs, enough
+// for 40 tiles; 768: 168 VGPRs, 142-149 used, for 64 tiles)
+template <int MODE, bool RQ32, int NKT, int NTH>
+__global__ __launch_bounds__(NTH, 1) void attention_long_kernel(LongArgs a)
+{
+    static_assert(!RQ32 || MODE == 0, "RQ32: power-of-two input scale");
+    constexpr int NKS = NKT / 4 + 1;          // key steps of 64: NKT full key tiles and the partial one
+    constexpr int KOFF = RQ32 ? RQ_OFF : 0;    // RQ32: scores carry the magic constant's exponent bits (low byte = k + 128)
+    extern __shared__ __attribute__((aligned(16))) char lsm[];
+    const int T = a.tokens, nkt = (T + 15) >> 4, nks = (nkt + 3) >> 2;
+    const int bh = blockIdx.x / a.parts, part = blockIdx.x - bh * a.parts;
+    const int b = bh / a.heads, hh = bh - b * a.heads;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int g = lane >> 4, l15 = lane & 15;
+    const int64_t plane = (int64_t)a.batch * a.heads * T * HD;
+    const int8_t* qg = a.qkv + (int64_t)bh * T * HD;
+    const int8_t* kg = qg + plane;
+    const int8_t* vg = qg + 2 * plane;
+    unsigned* lut = reinterpret_cast<unsigned*>(lsm);                 // [256] u32 exponent, [256] the same as float32
+    char* ksm = lsm + LONG_LUT_BYTES;                                  // K image, nkt * 16 rows of 64 bytes (kswz)
+    char* vt = ksm + nkt * 16 * HD;                                    // V^T, 64 rows of vt_row bytes
+    const int vt_row = a.vt_row;
+
+    if (MODE == 0 && tid < 256) {
+        const unsigned e0 = shiftexp_int(-tid, a.x0, 15);
+        lut[tid] = e0;
+        reinterpret_cast<float*>(lut)[256 + tid] = (float)e0;
+    }
+    // ---- K: 4 T chunks of 16 bytes, all requested before the first is written (as attention_kernel)
+    constexpr int NW = NTH / 64;
+    constexpr int KI = (4 * LONG_T_MAX + NTH - 1) / NTH;
+    v4i kst[KI];
+#pragma unroll
+    for (int i = 0; i < KI; ++i) {
+        const int q = min(tid + NTH * i, 4 * T - 1);
+        kst[i] = *reinterpret_cast<const v4i*>(kg + (int64_t)(q >> 2) * HD + 16 * (q & 3));
+    }
+    // ---- V^T: work item = 4 consecutive keys x 16 d, transposed in registers, written as dwords (attention_kernel's layout:
+    //      chunk j = 4 s + g' of row d holds keys 64 s + 16 t + 4 g' + r at byte 4 t + r, stored at chunk position j ^ (d & 15))
+    constexpr int VI = (((LONG_T_MAX + 3) / 4) * 4 + NTH - 1) / NTH;
+    const int nvi = ((T + 3) >> 2) * 4;
+    v4i vst[VI][4];
+#pragma unroll
+    for (int i = 0; i < VI; ++i) {
+        const int q = min(tid + NTH * i, nvi - 1);
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            vst[i][r] = *reinterpret_cast<const v4i*>(vg + (int64_t)min(4 * (q >> 2) + r, T - 1) * HD + 16 * (q & 3));
+    }
+#pragma unroll
+    for (int i = 0; i < KI; ++i) {
+        const int q = tid + NTH * i;
+        if (q < 4 * T) *reinterpret_cast<v4i*>(ksm + kswz(q >> 2, q & 3)) = kst[i];
+    }
+#pragma unroll
+    for (int i = 0; i < VI; ++i) {
+        const int q = tid + NTH * i;
+        if (q >= nvi) continue;
+        const int key0 = 4 * (q >> 2), c = q & 3;
+        const int j = 4 * (key0 >> 6) + ((key0 >> 2) & 3);
+        const int boff = 4 * ((key0 >> 4) & 3);
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const unsigned a0 = (unsigned)vst[i][0][w], a1 = (unsigned)vst[i][1][w], a2 = (unsigned)vst[i][2][w], a3 = (unsigned)vst[i][3][w];
+            const unsigned lo01 = __builtin_amdgcn_perm(a1, a0, 0x05010400u), hi01 = __builtin_amdgcn_perm(a1, a0, 0x07030602u);
+            const unsigned lo23 = __builtin_amdgcn_perm(a3, a2, 0x05010400u), hi23 = __builtin_amdgcn_perm(a3, a2, 0x07030602u);
+            const unsigned t[4] = {__builtin_amdgcn_perm(lo23, lo01, 0x05040100u), __builtin_amdgcn_perm(lo23, lo01, 0x07060302u),
+                                   __builtin_amdgcn_perm(hi23, hi01, 0x05040100u), __builtin_amdgcn_perm(hi23, hi01, 0x07060302u)};
+#pragma unroll
+            for (int bb = 0; bb < 4; ++bb) {
+                const int d = 16 * c + 4 * w + bb;
+                *reinterpret_cast<unsigned*>(vt + d * vt_row + ((j ^ (d & 15)) << 4) + boff) = t[bb];
+            }
+        }
+    }
+    __syncthreads();
+
+    const float* lutf = reinterpret_cast<const float*>(lut) + 256;
+    // the full key tiles live in sc[]; the partial one (T % 16 != 0: tile nfull, the only one with padding keys) in its own register,
+    // so that no unrolled tile carries a padding test.  Its key 16 nfull + 4 g + r is real for r < vr.
+    const int nfull = T >> 4, vr = T - 16 * nfull - 4 * g;
+    const bool partial = (T & 15) != 0;
+    const int W = a.band_w;
+    for (int qt = part * NW + wave; qt < nkt; qt += NW * a.parts) {
+        const int qrow = qt * 16 + l15;
+        const v4i qf = *reinterpret_cast<const v4i*>(qg + (int64_t)min(qrow, T - 1) * HD + 16 * g);
+        int nf = nfull;
+        asm volatile("" : "+s"(nf));   // opaque per query tile: the per-tile tests are not hoisted out as live masks (SGPR spills)
+
+        // ---- pass 1: scores, requantised (qact_attn1) to u = k + 128 (+ KOFF), packed four to a dword
+        int umax = KOFF;
+        auto score_tile = [&](int kt, int nreal) -> unsigned {
+            const v4i kf = *reinterpret_cast<const v4i*>(ksm + kswz(16 * kt + l15, g));
+            v4i acc = {0, 0, 0, 0};
+            acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(kf, qf, acc, 0, 0, 0);
+            int u[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                if constexpr (RQ32)    // RNE(S * Ms) + 128 in the low byte: exact, one rounding (see attention_kernel RQ32)
+                    u[r] = clamp_i32(__float_as_int(__builtin_fmaf((float)acc[r], a.Ms32, 12583040.0f)), KOFF, KOFF + 255);
+                else
+                    u[r] = clamp_i32(requant_exact(acc[r], a.Ms), -128, 127) + 128;
+                u[r] = r < nreal ? u[r] : KOFF;    // padding keys: byte 0, never the maximum; their exponent is masked below
+            }
+            umax = max(umax, max(max(u[0], u[1]), max(u[2], u[3])));
+            return __builtin_amdgcn_perm((unsigned)u[1], (unsigned)u[0], 0x0c0c0400u) |
+                   __builtin_amdgcn_perm((unsigned)u[3], (unsigned)u[2], 0x04000c0cu);
+        };
+        unsigned sc[NKT];
+#pragma unroll
+        for (int kt = 0; kt < NKT; ++kt) {
+            if (kt < nf) sc[kt] = score_tile(kt, 4);    // uniform test; the loop stays unrolled (sc[] in registers)
+            if ((kt & 3) == 3) __builtin_amdgcn_sched_barrier(0);  // at most 4 K fragments in flight
+        }
+        const unsigned sl = partial ? score_tile(nf, vr) : 0u;
+        umax = rows_allmax_i32(umax) & 255;    // qmax + 128
+        const unsigned rep = (unsigned)umax * 0x01010101u;
+
+        // exp_int of a key from idx = qmax - k in [0, 255] (and k + 128 = umax - idx)
+        const unsigned* trow = MODE == 1 ? a.table + (W ? umax * W : umax * 257) : nullptr;
+        auto expo = [&](unsigned idx) -> unsigned {
+            if constexpr (MODE == 0) return lut[idx];
+            else return W ? trow[min((int)idx, W - 1)] : trow[-(int)idx];
+        };
+
+        // ---- pass 2: Shiftmax row sum (ivit_modules.py:171), exact, rounded once to float32
+        unsigned long long esum = 0;
+        unsigned sum16 = 0;
+#pragma unroll
+        for (int kt = 0; kt < NKT; ++kt) {
+            if (kt < nf) {
+                const unsigned dk = rep - sc[kt];  // bytes: idx of the four keys (every k <= qmax: no borrow)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) sum16 += expo((dk >> (8 * r)) & 255u);
+            }
+            if ((kt & 3) == 3) {
+                esum += sum16;
+                sum16 = 0;
+            }
+        }
+        if (partial) {
+            const unsigned dk = rep - sl;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) sum16 += r < vr ? expo((dk >> (8 * r)) & 255u) : 0u;
+        }
+        esum = rows_allsum_u64(esum + sum16);
+        float S = (float)esum;                                         // :171
+        S = fminf(S, 2147483648.0f);                                   // :173
+        const float factor = floorf((1.0f / S) * 2147483648.0f);       // :174
+
+        // ---- pass 3: p = floor(fl32(e * factor) / 2^24) (:175) as bytes, P . V per key step of 64
+        auto prob_word = [&](unsigned packed, int nreal) -> unsigned {
+            const unsigned dk = rep - packed;
+            unsigned p[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const unsigned idx = (dk >> (8 * r)) & 255u;
+                const float ev = MODE == 0 ? lutf[idx] : (float)expo(idx);
+                p[r] = r < nreal ? (unsigned)(ev * factor) : 0u;          // float32 product (:175), < 2^31
+            }
+            return __builtin_amdgcn_perm(p[1], p[0], 0x0c0c0703u) | __builtin_amdgcn_perm(p[3], p[2], 0x07030c0cu);
+        };
+        const unsigned wl = partial ? prob_word(sl, vr) : 0u;
+        v4i o[4];
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) o[dt] = v4i{0, 0, 0, 0};
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks) {
+            if (ks >= nks) continue;
+            v4i pk;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const int kt = 4 * ks + t;
+                unsigned w = kt == nf ? wl : 0u;
+                if (kt < NKT && kt < nf) w = prob_word(sc[kt < NKT ? kt : 0], 4);
+                pk[t] = (int)w;
+            }
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt) {
+                const int d = 16 * dt + l15;
+                const v4i vf = *reinterpret_cast<const v4i*>(vt + d * vt_row + (((4 * ks + g) ^ (d & 15)) << 4));
+                o[dt] = __builtin_amdgcn_mfma_i32_16x16x64_i8(vf, pk, o[dt], 0, 0, 0);
+            }
+        }
+
+        // ---- O^T requantised (qact2): |O| <= 1025 * 127 * 128 < 2^24, the float64 product is exact
+        unsigned wq[4];
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) {
+            int ob[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) ob[r] = clamp_i32(requant_exact(o[dt][r], a.Mo), -128, 127);
+            wq[dt] = __builtin_amdgcn_perm((unsigned)ob[1], (unsigned)ob[0], 0x0c0c0400u) | __builtin_amdgcn_perm((unsigned)ob[3], (unsigned)ob[2], 0x04000c0cu);
+        }
+        // 4 x 4 dword transpose over the four lanes of a query: lane g ends with bytes d = 16 g .. 16 g + 15 (as attention_kernel)
+        typedef unsigned v2u __attribute__((ext_vector_type(2)));
+        const v2u ab = __builtin_amdgcn_permlane32_swap(wq[0], wq[2], false, false);
+        const v2u cd = __builtin_amdgcn_permlane32_swap(wq[1], wq[3], false, false);
+        const v2u ac = __builtin_amdgcn_permlane16_swap(ab.x, cd.x, false, false);
+        const v2u bd = __builtin_amdgcn_permlane16_swap(ab.y, cd.y, false, false);
+        if (qrow < T) {
+            const v4i chunk = {(int)ac.x, (int)ac.y, (int)bd.x, (int)bd.y};
+            const int64_t orow_idx = (int64_t)b * T + qrow;
+            if (a.out_blocks) {
+                const BlockRow obrow = block_row((int)orow_idx, a.heads * HD);
+                *reinterpret_cast<v4i*>(a.out + obrow.base + (unsigned)hh * 1024u + (((unsigned)g ^ obrow.rs) << 4)) = chunk;
+            } else {
+                *reinterpret_cast<v4i*>(a.out + orow_idx * ((int64_t)a.heads * HD) + hh * HD + 16 * g) = chunk;
+            }
+        }
+    }
+}
+
+// Workgroups per (image, head) for the long kernel: one workgroup per CU (256 slots), nw waves walking nqt query tiles.  The same
+// cost model as attention_parts, staging and a query tile both growing with T alike.
+int attention_long_parts(int batch_heads, int nqt, int nw)
+{
+    int best = 1;
+    double best_t = 0.0;
+    for (int p = 1; p <= 4; p *= 2) {
+        if (p > 1 && nw * (p / 2) >= nqt) break;
+        const int rounds = (batch_heads * p + 255) / 256, tiles = (nqt + nw * p - 1) / (nw * p);
+        const double t = rounds * (3.0 + 3.45 * tiles);
+        if (p == 1 || t < 0.95 * best_t) { best = p; best_t = t; }
+    }
+    return best;
+}
+
 }  // namespace
 
 IVIT_EXPORT int ivit_attention_fused_i8_ex(const int8_t* qkv, int8_t* out, int batch, int heads, int tokens,
@@ -766,4 +1024,57 @@ IVIT_EXPORT int ivit_attention_fused_i8(const int8_t* qkv, int8_t* out, int batc
                                         int32_t e_o, ivit_stream_t stream)
 {
     return ivit_attention_fused_i8_ex(qkv, out, batch, heads, tokens, head_dim, m_s, e_s, s_attn, m_o, e_o, 0, stream);
+}
+
+IVIT_EXPORT int ivit_attention_fused_i8_long(const int8_t* qkv, int8_t* out, int batch, int heads, int tokens, int head_dim,
+                                             uint32_t m_s, int32_t e_s, float s_attn, uint32_t m_o, int32_t e_o,
+                                             const uint32_t* exp2d, const uint32_t* band, int band_w, int out_blocks,
+                                             ivit_stream_t stream)
+{
+    IVIT_REQUIRE(qkv && out, "ivit_attention_fused_i8_long: NULL operand");
+    IVIT_REQUIRE(batch > 0 && heads > 0, "ivit_attention_fused_i8_long: empty batch");
+    if (head_dim != HD || tokens < LONG_T_MIN || tokens > LONG_T_MAX) {
+        ivit_set_error("ivit_attention_fused_i8_long: unsupported geometry head_dim=%d tokens=%d (need 64, %d..%d)", head_dim, tokens,
+                       LONG_T_MIN, LONG_T_MAX);
+        return IVIT_ERR_UNSUPPORTED;
+    }
+    IVIT_REQUIRE(((uintptr_t)qkv % 16 == 0) && ((uintptr_t)out % 16 == 0), "ivit_attention_fused_i8_long: misaligned operand (16-byte rows)");
+    IVIT_REQUIRE(s_attn > 0.0f, "ivit_attention_fused_i8_long: scale must be positive");
+    IVIT_REQUIRE(out_blocks == 0 || (out_blocks == 1 && ((int64_t)batch * tokens + 15) * heads * head_dim < 2147483648ll),
+                 "ivit_attention_fused_i8_long: bad output layout (block-layout buffers stay below 2 GiB)");
+    IVIT_REQUIRE((int64_t)batch * heads * tokens * head_dim * 3 < ((int64_t)1 << 40), "ivit_attention_fused_i8_long: qkv too large");
+    IVIT_REQUIRE((uintptr_t)exp2d % 4 == 0, "ivit_attention_fused_i8_long: misaligned exponent table");
+    IVIT_REQUIRE(band_w == 0 || (band && band_w >= 16 && band_w <= 256 && band_w % 16 == 0 && (uintptr_t)band % 16 == 0),
+                 "ivit_attention_fused_i8_long: band table must be 16-byte aligned, width a multiple of 16 in [16, 256]");
+    LongArgs a{};
+    a.qkv = qkv; a.out = out; a.batch = batch; a.heads = heads; a.tokens = tokens;
+    a.out_blocks = out_blocks;
+    a.Ms = ivit_dyadic_to_double(m_s, e_s);
+    a.Mo = ivit_dyadic_to_double(m_o, e_o);
+    IVIT_REQUIRE(a.Ms < 2048.0 && a.Mo < 512.0, "ivit_attention_fused_i8_long: requant multiplier too large");
+    const bool ms_pow2 = m_s != 0 && (m_s & (m_s - 1)) == 0 && a.Ms >= 1e-30;
+    a.Ms32 = (float)a.Ms;
+    const float x0f = __builtin_floorf((1.0f / s_attn) * -1.0f);   // ivit_modules.py:154
+    IVIT_REQUIRE(x0f <= -1.0f && x0f >= -4096.0f, "ivit_attention_fused_i8_long: x0=%g outside [-4096,-1]", (double)x0f);
+    a.x0 = (int)x0f;    // exp_int <= 2 |x0| * 2^14 <= 2^27: 16 of them in u32, the row in u64 (common.h rows_allsum_u64)
+    a.table = band_w ? band : exp2d;
+    a.band_w = band_w;
+    const int nkt = (tokens + 15) >> 4, nks = (nkt + 3) >> 2;
+    a.vt_row = ((nks + 3) >> 2) * 256;
+    const size_t lds = (size_t)LONG_LUT_BYTES + (size_t)nkt * 16 * HD + (size_t)HD * a.vt_row;    // <= 150528 bytes at 1025 tokens
+    const bool natural = band_w || exp2d, wide = (tokens >> 4) > 40;
+    const int nth = wide ? 768 : 1024;
+    a.parts = attention_long_parts(batch * heads, nkt, nth / 64);
+    const dim3 grid(batch * heads * a.parts), blk(nth);
+    hipStream_t st = ivit_stream(stream);
+    if (!wide) {
+        if (natural) hipLaunchKernelGGL((attention_long_kernel<1, false, 40, 1024>), grid, blk, lds, st, a);
+        else if (ms_pow2) hipLaunchKernelGGL((attention_long_kernel<0, true, 40, 1024>), grid, blk, lds, st, a);
+        else hipLaunchKernelGGL((attention_long_kernel<0, false, 40, 1024>), grid, blk, lds, st, a);
+    } else {
+        if (natural) hipLaunchKernelGGL((attention_long_kernel<1, false, 64, 768>), grid, blk, lds, st, a);
+        else if (ms_pow2) hipLaunchKernelGGL((attention_long_kernel<0, true, 64, 768>), grid, blk, lds, st, a);
+        else hipLaunchKernelGGL((attention_long_kernel<0, false, 64, 768>), grid, blk, lds, st, a);
+    }
+    IVIT_CHECK_LAUNCH("ivit_attention_fused_i8_long");
 }

@@ -46,7 +46,12 @@ def occupancy_rules(path, what):
     kernels = parse(open(path, errors="replace").read())
     bad, seen = [], 0
     for name, r in sorted(kernels.items()):
-        if what == "attention":
+        if what == "attention" and "attention_long_kernel" in name:
+            # attention_long_kernel<MODE, RQ32, NKT, NTH>: one workgroup of NTH threads per CU (the launcher's 256 slots), i.e.
+            # NTH / 256 waves per SIMD; the packed score rows must stay in registers: no scratch
+            m = re.search(r"attention_long_kernelILi(\d+)ELb([01])ELi(\d+)ELi(\d+)E", name)
+            occ, need_no_scratch = int(m.group(4)) // 256, True
+        elif what == "attention":
             m = re.search(r"attention_kernelILi(\d+)ELi(\d+)ELi(\d+)ELb([01])E", name)
             if not m:
                 continue
@@ -73,7 +78,7 @@ def occupancy_rules(path, what):
             # the natural-scale C = 1024 form spills a few loop-invariant dwords into cold paths (ln_stream.h)
             need_no_scratch = m.group(4) == "0" or int(m.group(2)) == 3
         seen += 1
-        ok = r.get("Occupancy", 0) >= occ and (r.get("Scratch") == 0 or not need_no_scratch)
+        ok = r.get("Occupancy", 0) >= occ and (r.get("Scratch") == 0 and r.get("VGPRSpill", 0) == 0 or not need_no_scratch)
         print(("ok   " if ok else "FAIL ") + f"{name}: VGPR {r.get('VGPRs')}, scratch {r.get('Scratch')}, occupancy {r.get('Occupancy')} (launcher assumes {occ}"
               f"{', no scratch' if need_no_scratch else ''})")
         if not ok:

@@ -65,6 +65,17 @@ IVIT_DEV unsigned rows_allreduce_u32(unsigned v, Op op)
 IVIT_DEV int rows_allmin_i32(int v) { return (int)rows_allreduce_u32((unsigned)v, [](unsigned x, unsigned y) { return (unsigned)min((int)x, (int)y); }); }
 IVIT_DEV int rows_allmax_i32(int v) { return (int)rows_allreduce_u32((unsigned)v, [](unsigned x, unsigned y) { return (unsigned)max((int)x, (int)y); }); }
 IVIT_DEV unsigned rows_allsum_u32(unsigned v) { return rows_allreduce_u32(v, [](unsigned x, unsigned y) { return x + y; }); }
+// the same sum on 64-bit values (both halves move with the same swap)
+IVIT_DEV unsigned long long rows_allsum_u64(unsigned long long v)
+{
+    typedef unsigned v2u_ __attribute__((ext_vector_type(2)));
+    const v2u_ al = __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false);
+    const v2u_ ah = __builtin_amdgcn_permlane16_swap((unsigned)(v >> 32), (unsigned)(v >> 32), false, false);
+    v = (((unsigned long long)ah.x << 32) | al.x) + (((unsigned long long)ah.y << 32) | al.y);
+    const v2u_ bl = __builtin_amdgcn_permlane32_swap((unsigned)v, (unsigned)v, false, false);
+    const v2u_ bh = __builtin_amdgcn_permlane32_swap((unsigned)(v >> 32), (unsigned)(v >> 32), false, false);
+    return (((unsigned long long)bh.x << 32) | bl.x) + (((unsigned long long)bh.y << 32) | bl.y);
+}
 
 // All-reduce butterflies without LDS (a __shfl_xor with a constant offset compiles to ds_bpermute_b32: an LDS round trip per step).
 // Steps 1 / 2: DPP quad permutes; 4 / 8: row_half_mirror / row_mirror (the partner lies in the other half of the group, whose lanes

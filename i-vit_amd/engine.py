@@ -31,6 +31,7 @@ from .topk import TOPK_MAX
 class IntViTEngine(EngineBase):
     # fragment-packed weights in the 16x16x64 MFMA order (False / IVIT_FRAGS16=0: the 32x32x32 order everywhere; A/B, tests)
     frags16 = os.environ.get("IVIT_FRAGS16", "1") != "0"
+    LONG_TOKENS = 1025     # ivit_attention_fused_i8_long (208 .. 1025 tokens); the other attention entries stop at 207
 
     def __init__(self, float_state=None, ranges=None, embed_dim: int = 768, depth: int = 12, num_heads: int = 12,
                  device="cuda:0", max_batch: int = 256, source=None, family: str = "ivit", stream_bits: int = 8,
@@ -40,10 +41,13 @@ class IntViTEngine(EngineBase):
         FloatSource interface of export.py (e.g. export.ExportSource: integer parameters + scale table, no floats)."""
         self.C, self.D, self.H = embed_dim, depth, num_heads
         # geometry (vit_quant.py:158-166: img_size, patch_size): square images, non-overlapping patches.  The patch GEMM steps K in
-        # 64-byte slabs and the fused attention kernel holds a whole Shiftmax row of at most 207 keys in four lanes
+        # 64-byte slabs.  The fused attention kernels hold a whole Shiftmax row of at most 207 keys in four lanes; I-ViT with the
+        # 8-bit stream takes up to 1025 tokens (ivit_attention_fused_i8_long above 207: packed 8-bit scores)
         self.IMG, self.P = int(img_size), int(patch_size)
-        if self.IMG % self.P or (3 * self.P * self.P) % 64 or (self.IMG // self.P) ** 2 + 1 > 207:
-            raise ValueError(f"geometry {self.IMG} / {self.P}: needs img_size % patch_size == 0, 3 * patch_size^2 % 64 == 0 and at most 207 tokens")
+        tokens = (self.IMG // self.P) ** 2 + 1 if self.P > 0 else 0
+        if self.IMG % self.P or (3 * self.P * self.P) % 64 or tokens > self.LONG_TOKENS:
+            raise ValueError(f"geometry {self.IMG} / {self.P}: needs img_size % patch_size == 0, 3 * patch_size^2 % 64 == 0 and at most "
+                             f"{self.LONG_TOKENS} tokens")
         self.NP = (self.IMG // self.P) ** 2
         self.T = self.NP + 1
         # operator family of LayerNorm / Softmax / GELU: "ivit" (I-ViT: IVITIntLayerNorm, Shiftmax, ShiftGELU) or "ibert" (the
@@ -56,6 +60,9 @@ class IntViTEngine(EngineBase):
         # GEMM operands stay int8, the stream and the projection / fc2 outputs are int16 (the kernels of the Swin engine)
         if stream_bits not in (8, 16):
             raise ValueError("stream_bits must be 8 or 16")
+        if self.T > 207 and (family != "ivit" or stream_bits != 8):
+            raise ValueError(f"geometry {self.IMG} / {self.P}: {self.T} tokens; the I-BERT softmax and the 16-bit stream take at most "
+                             "207 tokens (more: family 'ivit' with stream_bits = 8)")
         self.stream_bits = sb = stream_bits
         # softmax_bw / pos_encoding_bw (vit_quant.py:181, 184) may be 16 on the 16-bit-stream path ('--bitwidth 16' sets all eight)
         if softmax_bits not in (8, 16) or pos_bits not in (8, 16) or (sb == 8 and (softmax_bits, pos_bits) != (8, 8)):
@@ -390,7 +397,9 @@ class IntViTEngine(EngineBase):
                           _lib.ptr(ws["ao"]), B, H, T, hd, a["ms"][0], a["ms"][1], a["mo"][0], a["mo"][1], _lib.ptr(a["ib_table"]),
                           _lib.ptr(a["band"]), a["band_w"], *sm, int(a_at), st)
             else:
-                _lib.call("ivit_attention_fused_i8_wide" if wide else "ivit_attention_fused_i8_compat_band", _lib.ptr(ws["qkv"]),
+                name = "ivit_attention_fused_i8_wide" if wide else ("ivit_attention_fused_i8_long" if T > 207 else
+                                                                     "ivit_attention_fused_i8_compat_band")
+                _lib.call(name, _lib.ptr(ws["qkv"]),
                           _lib.ptr(ws["ao"]), B, H, T, hd, a["ms"][0], a["ms"][1], a["s_attn"], a["mo"][0], a["mo"][1],
                           _lib.ptr(a["exp2d"]), _lib.ptr(a["band"]), a["band_w"], *sm, int(a_at), st)
             tap(p + "attn.qact2", ws["ao"], (B, T, C), a_at)

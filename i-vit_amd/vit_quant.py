@@ -160,9 +160,10 @@ class VisionTransformer(EngineDispatch, nn.Module):
             return "head_dim != 64"
         img, patch = self.geometry[0], self.geometry[1]
         if (self.geometry[2:] != (3, 4.0, True, None) or not isinstance(img, int) or not isinstance(patch, int) or img % patch
-                or (3 * patch * patch) % 64 or (img // patch) ** 2 + 1 > 207):
+                or (3 * patch * patch) % 64 or (img // patch) ** 2 + 1 > 1025):
             return (f"geometry {self.geometry} (fused engine: square images, 3 channels, img_size % patch_size == 0, "
-                    "3 * patch_size^2 % 64 == 0, at most 207 tokens, mlp_ratio 4, qkv bias)")
+                    "3 * patch_size^2 % 64 == 0, at most 1025 tokens, mlp_ratio 4, qkv bias)")
+        tokens = (img // patch) ** 2 + 1
         if self.num_classes <= 0:
             return "no classification head"
         # every QuantAct of the DeiT / ViT engine is 8 bit, except the 16-bit one inside IBERTIntSoftmax (ibert_modules.py:247) ...
@@ -184,6 +185,12 @@ class VisionTransformer(EngineDispatch, nn.Module):
             return bad
         if (sm_bits != 8 and self._engine_widths[0] == 8) or getattr(m, "output_bit", 8) != 8:
             return "Shiftmax / ShiftGELU output width != 8"
+        # the fused I-BERT attention covers 193 .. 207 tokens (csrc/attention.hip), the 16-bit stream's up to 207; only I-ViT on the
+        # 8-bit stream has the long-row kernel (208 .. 1025 tokens)
+        if self.op_types[0] == "ibert" and not 193 <= tokens <= 207:
+            return f"geometry {self.geometry}: {tokens} tokens (fused I-BERT attention: 193 .. 207 tokens)"
+        if tokens > 207 and self._engine_widths[0] != 8:
+            return f"geometry {self.geometry}: {tokens} tokens (16-bit residual stream: at most 207 tokens)"
         return None
 
     def _build_engine(self, device, max_batch):

@@ -230,6 +230,18 @@ int ivit_attention_fused_i8_wide(const int8_t* qkv, int8_t* out, int batch, int 
                                  int32_t e_s, float s_attn, uint32_t m_o, int32_t e_o, const uint32_t* exp2d,
                                  const uint32_t* band, int band_w, int softmax_bits, int out_blocks, ivit_stream_t stream);
 
+/* Long rows: the same Shiftmax attention (8-bit probabilities) for 208 <= tokens <= 1025 (e.g. 384 / 16 -> 577, 224 / 8 -> 785,
+ * 512 / 16 -> 1025 tokens), which ivit_attention_fused_i8_compat_band rejects.  Arguments as there.
+ * Preconditions: head_dim 64; qkv, out non-NULL and 16-byte aligned; x0 = floor(-1/s_attn) in [-4096, -1] (the row sum is exact
+ * in 64 bits for every such x0); multipliers m_s * 2^-e_s < 2048, m_o * 2^-e_o < 512; band_w = 0 or a band table as above
+ * (16-byte aligned, width a multiple of 16 in [16, 256], entry band_w - 1 saturated); band_w = 0 and exp2d non-NULL: the
+ * full [256][256] table; both absent: power-of-two scale.  out_blocks = 1: IVIT_LAYOUT_BLOCKS output below 2 GiB.
+ * Errors: IVIT_ERR_UNSUPPORTED ("unsupported geometry") outside the token range or for another head_dim, IVIT_ERR_INVALID
+ * ("NULL operand", ...) otherwise. */
+int ivit_attention_fused_i8_long(const int8_t* qkv, int8_t* out, int batch, int heads, int tokens, int head_dim, uint32_t m_s,
+                                 int32_t e_s, float s_attn, uint32_t m_o, int32_t e_o, const uint32_t* exp2d,
+                                 const uint32_t* band, int band_w, int out_blocks, ivit_stream_t stream);
+
 /* ---- I-LayerNorm + the QuantAct behind it ---------------------------------------------------
  * IVITIntLayerNorm.forward (ivit_modules.py:30-65) then QuantAct (fixedpoint_mul).
  *   x [rows, C] int8 (ldx), per channel: bias_int[c] = floor((beta/gamma)/(sqrt(C)/2^30)),

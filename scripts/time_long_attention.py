@@ -1,0 +1,115 @@
+"""Long-row attention: time per (query, key) score of ivit_attention_fused_i8_long against the 197-token kernel, and DeiT-B at 384 px
+(577 tokens), batch 64: the engine's forward against the module path's.  Torch events time each case here; the numbers to quote come
+from the kernel trace of one run:
+
+    rocprofv3 --kernel-trace --stats -d prof -o run -- python scripts/time_long_attention.py [kernels] [model]
+    python scripts/time_long_attention.py summary prof/run_results.db
+
+`summary` reads the trace database and prints, per attention kernel form and token count, the dispatch durations and the time
+per score (T is recovered from the launch's LDS size, B from the cases below; the model's launches are the natural-scale form)."""
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import ivit_amd  # noqa: E402,F401
+from ivit_amd import _lib, synth  # noqa: E402
+from ivit_amd.prepare import dyadic  # noqa: E402
+
+DEV = "cuda:0"
+H, hd = 12, 64
+rng = np.random.default_rng(0)
+st = _lib.stream_ptr
+
+
+def timeit(fn, n=20):
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(n):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / n * 1e3
+
+
+def attention(B, T):
+    """us per launch: power-of-two scales (the float32 score requantisation), row-major output"""
+    qkv = torch.from_numpy(np.clip(np.rint(rng.normal(0, 40, size=(3, B, H, T, hd))), -128, 127).astype(np.int8)).to(DEV)
+    out = torch.empty(B * T, H * hd, dtype=torch.int8, device=DEV)
+    ms, es = dyadic(np.float32(2.0 ** -11), np.float32(2.0 ** -2))
+    mo, eo = dyadic(np.float32(2.0 ** -11), np.float32(2.0 ** -3))
+    name = "ivit_attention_fused_i8_long" if T > 207 else "ivit_attention_fused_i8_compat_band"
+    return timeit(lambda: _lib.call(name, _lib.ptr(qkv), _lib.ptr(out), B, H, T, hd, int(ms[0]), int(es[0]), 0.25, int(mo[0]),
+                                    int(eo[0]), None, None, 0, 0, st()))
+
+
+CASES = [(256, 197), (64, 209), (64, 577), (64, 785)]
+
+
+def long_lds(T):
+    """dynamic LDS of ivit_attention_fused_i8_long (its launcher): exponent tables, K image, V^T rows padded to 256 bytes"""
+    nkt = (T + 15) // 16
+    return 2048 + nkt * 1024 + 64 * (((nkt + 3) // 4 + 3) // 4) * 256
+
+
+def summary(db):
+    import sqlite3
+    con = sqlite3.connect(db)
+    by_lds = {long_lds(T): T for _, T in CASES if T > 207}
+    rows = con.execute("select name, lds_size, count(*), avg(duration), min(duration) from kernels where name like '%attention%' "
+                       "group by name, lds_size order by min(start)").fetchall()
+    for name, lds, n, avg, mn in rows:
+        form = name.split("(anonymous namespace)::")[1].rsplit("(", 1)[0]
+        T = 197 if form.startswith("attention_kernel") else by_lds.get(lds)
+        B = {197: 256}.get(T, 64)
+        ps = mn * 1e3 / (B * H * T * T) if T else float("nan")
+        print(f"{form:52s} T={T} B={B}: {n:3d} dispatches, mean {avg / 1e3:8.1f} us, min {mn / 1e3:8.1f} us, {ps:.3f} ps/score (min)")
+
+
+which = sys.argv[1:] or ["kernels", "model"]
+if which[0] == "summary":
+    summary(which[1])
+    sys.exit(0)
+if "kernels" in which:
+    for B, T in CASES:
+        us = attention(B, T)
+        ps = us * 1e6 / (B * H * T * T)      # chip-wide: launch time over every (query, key) score of the batch
+        print(f"attention B={B:3d} T={T:4d}  {us:8.1f} us  {ps:.3f} ps/score")
+
+if "model" in which:
+    from ivit_amd.quantization_utils import lazy
+    fs = synth.make_float_state("deit_base_patch16_224", 31)
+    fs["pos_embed"] = np.random.default_rng(1).normal(0, 0.02, size=(1, 577, 768)).astype(np.float32)
+    model = ivit_amd.deit_base_patch16_224(img_size=384)
+    model.load_state_dict({k: torch.from_numpy(v) for k, v in fs.items()}, strict=False)
+    model.to(DEV).eval()
+    imgs = torch.from_numpy(np.concatenate([synth.make_images(32, 5 + i) for i in range(2)])).to(DEV)
+    imgs = torch.nn.functional.interpolate(imgs, size=(384, 384), mode="bilinear", align_corners=False).contiguous()
+    with torch.no_grad():
+        model(imgs[:8])
+        ivit_amd.freeze_model(model)
+        assert model.engine_unsupported_reason() is None, model.engine_unsupported_reason()
+        eng = model.engine(64)
+        x = imgs.float().contiguous()
+        t_eng = timeit(lambda: eng.forward(x), n=10)
+        model.use_engine = False
+        lazy.enable_everywhere(True)
+        try:
+            t_mod = timeit(lambda: model(x), n=3)
+        finally:
+            lazy.enable_everywhere(False)
+    print(f"DeiT-B 384 px b64: engine forward {t_eng / 1e3:.2f} ms, module path {t_mod / 1e3:.2f} ms ({t_mod / t_eng:.1f}x)")
+    # the engine's own attention launches (its exponent tables: natural scales here), on the workspace of the last forward
+    ws, t_att = eng.ws, 0.0
+    for blk in eng.blocks:
+        a = blk["attn"]
+        t_att += timeit(lambda: _lib.call("ivit_attention_fused_i8_long", _lib.ptr(ws["qkv"]), _lib.ptr(ws["ao"]), 64, eng.H, eng.T, 64,
+                                          a["ms"][0], a["ms"][1], a["s_attn"], a["mo"][0], a["mo"][1], _lib.ptr(a["exp2d"]),
+                                          _lib.ptr(a["band"]), a["band_w"], 1, st()), n=5)
+    print(f"attention share of the engine forward: {t_att:.1f} us over {len(eng.blocks)} blocks = {t_att / t_eng * 100:.1f} % "
+          f"(natural-scale launches: {sum(1 for b in eng.blocks if b['attn']['band_w'] or b['attn']['exp2d'] is not None)})")
