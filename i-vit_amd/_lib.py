@@ -85,6 +85,7 @@ SIGNATURES = {
     "ivit_layernorm_i16_i8_compat": [vp, ci, ci, f32, ci, vp, vp, vp, vp, vp, i64, ci, ci, ci, ci, vp],
     "ivit_patch_merge_i16": [vp, vp, ci, ci, ci, ci, vp],
     "ivit_avgpool_requant_i8": [vp, vp, ci, ci, ci, u32, i32, vp],
+    "ivit_avgpool_requant_i8_literal": [vp, vp, ci, ci, ci, f32, u32, i32, vp],
     # I-BERT operator family (include/ivit_hip.h, last section)
     "ivit_ibert_gelu_i32": [vp, i64, f32, f32, f32, vp, vp],
     "ivit_ibert_softmax_i32": [vp, i64, ci, ci, f32, f32, f32, f32, f32, u32, i32, ci, vp, i64, vp, vp],
@@ -104,6 +105,8 @@ SIGNATURES = {
     "ivit_window_attention_i8_band": [vp, vp, i64, vp, vp, ci, ci, ci, ci, ci, u32, i32, u32, i32, f32, u32, i32, vp, ci, ci, ci, ci, ci, ci, vp],
     "ivit_window_attention_i8_unwindow": [vp, vp, i64, vp, vp, ci, ci, ci, ci, ci, ci, u32, i32, u32, i32, f32, u32, i32, vp, vp,
                                           ci, ci, ci, ci, vp],
+    "ivit_window_attention_i8_long": [vp, vp, i64, vp, vp, ci, ci, ci, ci, ci, ci, u32, i32, u32, i32, f32, u32, i32, vp, vp, vp, ci,
+                                      ci, ci, ci, ci, ci, ci, vp],
 }
 
 

@@ -59,7 +59,10 @@ def occupancy_rules(path, what):
             # (other geometries, "not tuned") may keep a few dwords of the Q prefetch in scratch
             occ, need_no_scratch = int(m.group(3)), m.group(4) == "0"
         elif what == "swin":
-            if "window_attention_kernel" in name:
+            if "window_attention_long_kernel" in name:
+                # 65..144 tokens: = its __launch_bounds__ (two workgroups per CU); the 36 scores per lane stay in registers: no scratch
+                occ, need_no_scratch = 2, True
+            elif "window_attention_kernel" in name:
                 occ, need_no_scratch = 4, True
             else:
                 m = re.search(r"layernorm_i16_i8_tiled(_compat)?_kernelILi(\d+)ELi(\d+)E", name)

@@ -997,6 +997,269 @@ __global__ __launch_bounds__(NT, 4) void window_attention_kernel(WinAttnArgs a)
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Windowed attention for 65..144 tokens (windows of 9x9 .. 12x12, Swin at 384 px): the arithmetic of window_attention_kernel, every
+// Shiftmax form and both output orders, with a row of up to 9 key tiles of 16.  Still one wave per (window, head): a row of 144 scores
+// is 36 per lane (9 key tiles x 4), S^T on 16x16x32 per key tile, O^T = Vt . P^T in up to 3 key steps of 64 on 16x16x64 (slots past T
+// are zero probabilities).  Vt of the wave's pair in LDS (32 x 192 bytes, each 64-key segment in window_attention_kernel's layout).
+// The bias is [nH][T][kp] int16 and the region table [nW][kp], kp = 16 * ceil(T / 16): rows of whole key tiles.  The bias rows stay
+// in global memory (L2): per score they are 2 bytes against the 16 of the score's 16x16x32 operand rows, and staging them in LDS
+// would add a wave barrier per query tile for data each wave reads once.
+// ------------------------------------------------------------------------------------------------
+constexpr int WL_NKT = 9;                          // key tiles of 16: up to 144 tokens
+constexpr int WL_NKS = 3;                          // P.V key steps of 64
+constexpr int WL_VT_ROW = 64 * WL_NKS;             // Vt row: 192 key slots
+constexpr int WL_VT_BYTES = WHD * WL_VT_ROW;       // 6 KiB per wave
+constexpr int WL_LUT_OFF = WPB * WL_VT_BYTES;
+
+// two workgroups of four waves per CU (<= 256 VGPRs): the 36 scores per lane (and the literal form's 36 float views) stay in registers
+template <int SM, bool RQ32>
+__global__ __launch_bounds__(NT, 2) void window_attention_long_kernel(WinAttnArgs a, int kp)
+{
+    __shared__ __attribute__((aligned(16))) char smem[WL_LUT_OFF + 256 * 4];
+    __shared__ float s_phi[2][256];
+    extern __shared__ __attribute__((aligned(16))) unsigned band_lds[];     // [4 waves][16 queries][band_w + WBAND_PAD], band form only
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int g = lane >> 4, l15 = lane & 15;
+    const int T = a.T;
+    const int nkt = (T + 15) >> 4, nks = (nkt + 3) >> 2;     // 6..9 key tiles, 2..3 key steps
+    reinterpret_cast<unsigned*>(smem + WL_LUT_OFF)[tid] = a.band1 ? a.band1[min(tid, a.band_w - 1)] : shiftexp_int(-tid, a.x0, 15);
+    constexpr bool band = SM == 2, compat = SM == 1;
+    if constexpr (compat) {
+        s_phi[0][tid] = a.phi[tid];
+        s_phi[1][tid] = a.phim[tid];
+    }
+    __syncthreads();
+    const unsigned* lut = reinterpret_cast<const unsigned*>(smem + WL_LUT_OFF);
+    char* vt = smem + wave * WL_VT_BYTES;
+    const int64_t plane = (int64_t)a.nwin * a.heads * T * WHD;
+    const int npairs = a.nwin * a.heads;
+
+    for (int pair = blockIdx.x * WPB + wave; pair < npairs; pair += gridDim.x * WPB) {
+        const int win = pair / a.heads, hh = pair - win * a.heads;
+        int64_t img_base = 0;
+        int wy0 = 0, wx0 = 0;
+        if (a.omap.ws) {
+            const int nwx = a.omap.W / a.omap.ws;
+            const int bimg = win / a.nW, wrem = win - bimg * a.nW;
+            const int wy = wrem / nwx;
+            wy0 = wy * a.omap.ws + a.omap.shift;
+            wx0 = (wrem - wy * nwx) * a.omap.ws + a.omap.shift;
+            img_base = (int64_t)bimg * a.omap.H * a.omap.W;
+        }
+        const int8_t* qg = a.qkv + (int64_t)pair * T * WHD;
+        const int8_t* kg = qg + plane;
+        const int8_t* vg = qg + 2 * plane;
+        // ---- Vt[d][64 s + slot(chunk g') + 4t + r] = V[key 64 s + 16t + 4g' + r][d], every slot of the nks segments written (keys past
+        //      T repeat key T - 1: their probabilities are 0).  Work item = 4 keys x 16 d.
+        __builtin_amdgcn_wave_barrier();
+        for (int item = lane; item < nks * 32; item += 64) {
+            const int kg4 = item >> 1, c = item & 1;
+            v4i v[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) v[r] = *reinterpret_cast<const v4i*>(vg + (int64_t)min(4 * kg4 + r, T - 1) * WHD + 16 * c);
+            const int key0 = 4 * kg4, seg = key0 >> 6;
+            const int j = (key0 >> 2) & 3, boff = 4 * ((key0 >> 4) & 3);
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                const unsigned a0 = (unsigned)v[0][w], a1 = (unsigned)v[1][w], a2 = (unsigned)v[2][w], a3 = (unsigned)v[3][w];
+                const unsigned lo01 = __builtin_amdgcn_perm(a1, a0, 0x05010400u), hi01 = __builtin_amdgcn_perm(a1, a0, 0x07030602u);
+                const unsigned lo23 = __builtin_amdgcn_perm(a3, a2, 0x05010400u), hi23 = __builtin_amdgcn_perm(a3, a2, 0x07030602u);
+                const unsigned t4[4] = {__builtin_amdgcn_perm(lo23, lo01, 0x05040100u), __builtin_amdgcn_perm(lo23, lo01, 0x07060302u),
+                                        __builtin_amdgcn_perm(hi23, hi01, 0x05040100u), __builtin_amdgcn_perm(hi23, hi01, 0x07060302u)};
+#pragma unroll
+                for (int bb = 0; bb < 4; ++bb) {
+                    const int d = 16 * c + 4 * w + bb;
+                    *reinterpret_cast<unsigned*>(vt + d * WL_VT_ROW + 64 * seg + (((j + 2 * ((d >> 2) & 1)) & 3) << 4) + boff) = t4[bb];
+                }
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
+
+        long kf[WL_NKT];
+        unsigned kreg[WL_NKT];
+        const uint8_t* regrow = a.region ? a.region + (int64_t)(win % a.nW) * kp : nullptr;
+#pragma unroll
+        for (int kt = 0; kt < WL_NKT; ++kt) {
+            kf[kt] = 0;
+            kreg[kt] = 0u;
+            if (kt < nkt) {
+                kf[kt] = *reinterpret_cast<const long*>(kg + (int64_t)min(16 * kt + l15, T - 1) * WHD + 8 * g);
+                if (regrow) kreg[kt] = *reinterpret_cast<const unsigned*>(regrow + 16 * kt + 4 * g);
+            }
+        }
+        for (int qt = 0; qt < nkt; ++qt) {
+            const int qrow = 16 * qt + l15;
+            const int qld = min(qrow, T - 1);
+            const long qf = *reinterpret_cast<const long*>(qg + (int64_t)qld * WHD + 8 * g);
+            const int16_t* brow = a.bias + ((int64_t)hh * T + qld) * kp + 4 * g;
+            const unsigned qreg = regrow ? regrow[qld] : 0u;
+            int s[WL_NKT][4];
+            int rmax = -100000;
+            float xv[WL_NKT][4], xmax = -__builtin_inff();
+#pragma unroll
+            for (int kt = 0; kt < WL_NKT; ++kt) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) { s[kt][r] = -100000; xv[kt][r] = -__builtin_inff(); }
+                if (kt >= nkt) continue;     // uniform
+                v4i acc = {0, 0, 0, 0};
+                acc = __builtin_amdgcn_mfma_i32_16x16x32_i8(kf[kt], qf, acc, 0, 0, 0);
+                const int2 bw = *reinterpret_cast<const int2*>(brow + 16 * kt);
+                const int bv[4] = {(int)(int16_t)bw.x, bw.x >> 16, (int)(int16_t)bw.y, bw.y >> 16};
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int key = 16 * kt + 4 * g + r;
+                    if (key < T) {
+                        int ka;
+                        if constexpr (RQ32) {
+                            const int tb = clamp_i32(__float_as_int(__builtin_fmaf((float)acc[r], a.Ms32, 12582912.0f)), 0x4B400000 - 128, 0x4B400000 + 127);
+                            const float kSf = __int_as_float(tb) - 12582912.0f;
+                            ka = clamp_i32(__float_as_int(__builtin_fmaf(kSf, a.Mb32, 12582912.0f)) - 0x4B400000 + bv[r], -128, 127);
+                        } else {
+                            const int kS = clamp_i32(requant_exact(acc[r], a.Ms), -128, 127);        // qact_attn1
+                            ka = clamp_i32(requant_exact(kS, a.Mb) + bv[r], -128, 127);              // qact2 (two operands)
+                        }
+                        const bool masked = ((kreg[kt] >> (8 * r)) & 0xffu) != qreg;
+                        if constexpr (compat) xv[kt][r] = s_phi[masked ? 1 : 0][ka + 128];
+                        if (masked) ka = band ? -50000 : ka + a.mask_value;                      // shift mask, after the clamp
+                        s[kt][r] = ka;
+                    }
+                    rmax = max(rmax, s[kt][r]);
+                    xmax = fmaxf(xmax, xv[kt][r]);
+                }
+            }
+            rmax = rows_allmax_i32(rmax);
+            unsigned esum = 0;
+            if constexpr (compat) {
+                xmax = fmaxf(xmax, __shfl_xor(xmax, 16));
+                xmax = fmaxf(xmax, __shfl_xor(xmax, 32));
+                const float x0f = (float)a.x0;
+#pragma unroll
+                for (int kt = 0; kt < WL_NKT; ++kt)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        unsigned e = 0u;
+                        if (s[kt][r] != -100000) {
+                            const float d = xv[kt][r] - xmax;                                    // ivit_modules.py:168
+                            float x = (d + floorf(d / 2.0f)) - floorf(d / 16.0f);                // :151
+                            x = fmaxf(x, 15.0f * x0f);                                           // :155
+                            const float qq = floorf(x / x0f);                                    // :157
+                            const float rr = x - x0f * qq;                                       // :158
+                            const float ex = floorf((rr / 2.0f - x0f) * ldexpf(1.0f, 15 - (int)qq));   // :159-160
+                            e = (unsigned)fmaxf(ex, 0.0f);
+                        }
+                        s[kt][r] = (int)e;
+                        esum += e;
+                    }
+            } else if constexpr (band) {
+                const int W = a.band_w, W1 = W - 1, stride = W + WBAND_PAD;
+                const int rm = max(rmax, -128);
+                unsigned* slice = band_lds + (wave * 16 + l15) * stride;
+                __builtin_amdgcn_wave_barrier();      // the previous tile's gathers are done
+                {
+                    const uint4* src = reinterpret_cast<const uint4*>(a.band + (size_t)(rm + 128) * W);
+                    uint4* dst = reinterpret_cast<uint4*>(slice);
+                    for (int i = g; i < (W >> 2); i += 4) dst[i] = src[i];
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+                for (int kt = 0; kt < WL_NKT; ++kt)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const unsigned e = (s[kt][r] == -100000) ? 0u : slice[min(rm - max(s[kt][r], -50000), W1)];
+                        s[kt][r] = (int)e;
+                        esum += e;
+                    }
+            } else {
+                // a masked score lies |mask_value| - 255 or more below the maximum: beyond the table's 256 distances when Shiftmax has not
+                // saturated by distance 255 (|x0| above about 24), so those take the exact integer form (band1: the host's saturated entry)
+#pragma unroll
+                for (int kt = 0; kt < WL_NKT; ++kt)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int d = rmax - s[kt][r];
+                        unsigned e = 0u;
+                        if (s[kt][r] != -100000) e = (d <= a.ksat || a.band1) ? lut[min(d, a.ksat) & 255] : shiftexp_int(-d, a.x0, 15);
+                        s[kt][r] = (int)e;
+                        esum += e;
+                    }
+            }
+            esum = rows_allsum_u32(esum);
+            const float S = fminf((float)esum, 2147483648.0f);             // ivit_modules.py:171-173
+            const float factor = floorf((1.0f / S) * 2147483648.0f);       // :174
+            v4i pk[WL_NKS];
+#pragma unroll
+            for (int ks = 0; ks < WL_NKS; ++ks)
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    unsigned w = 0;
+                    if (4 * ks + t < WL_NKT) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const float pr = (float)(unsigned)s[4 * ks + t][r] * factor;     // :175
+                            w |= ((((unsigned)pr) >> 24) & 0xffu) << (8 * r);
+                        }
+                    }
+                    pk[ks][t] = (int)w;
+                }
+            int64_t orow_idx = (int64_t)win * T + qrow;
+            if (a.omap.ws) {      // window reverse + roll back: (iy, ix) of the query in its window -> (y, x) of the image
+                const int qr = min(qrow, T - 1);
+                const int iy = (qr * a.omap_inv) >> 16, ix = qr - iy * a.omap.ws;      // qr / ws for qr < T (checked by the launcher)
+                int y = wy0 + iy, x = wx0 + ix;
+                y = y >= a.omap.H ? y - a.omap.H : y;
+                x = x >= a.omap.W ? x - a.omap.W : x;
+                orow_idx = img_base + y * a.omap.W + x;
+            }
+            int8_t* orow = a.out + orow_idx * a.ldo + hh * WHD;
+            unsigned wq[2];
+#pragma unroll
+            for (int dt = 0; dt < 2; ++dt) {
+                const int d = 16 * dt + l15;
+                const char* vrow = vt + d * WL_VT_ROW + (((g + 2 * ((d >> 2) & 1)) & 3) << 4);
+                v4i acc = {0, 0, 0, 0};
+#pragma unroll
+                for (int ks = 0; ks < WL_NKS; ++ks)
+                    if (ks < nks) acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(*reinterpret_cast<const v4i*>(vrow + 64 * ks), pk[ks], acc, 0, 0, 0);
+                unsigned w = 0;
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    w |= ((unsigned)clamp_i32(requant_exact(acc[r], a.Mo), -128, 127) & 0xffu) << (8 * r);
+                wq[dt] = w;
+            }
+            {
+                typedef unsigned v2u __attribute__((ext_vector_type(2)));
+                const v2u ab = __builtin_amdgcn_permlane32_swap(wq[0], wq[1], false, false);
+                const v2u pr = __builtin_amdgcn_permlane16_swap(ab.x, ab.y, false, false);
+                if (qrow < T) *reinterpret_cast<int2*>(orow + 8 * g) = make_int2((int)pr.x, (int)pr.y);
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Token average pooling + QuantAct at a natural input scale, literally (swin_quant.py:554-555 on the float view): the reference's
+// avgpool(x.transpose(1, 2)) on y = fl(q * s) is torch's CPU mean over the transposed view, i.e. the outer-reduction sum of rowsum.h
+// (column c of the contiguous extent C, a tail column when c >= 32 * (C / 32)) divided by float32(T); then qact3's own steps:
+// z = rint(fl(mean / s)) and the requantisation to int8.  One thread per output (b, c).
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(NT) void avgpool_literal_kernel(const int8_t* x, int8_t* out, int B, int T, int C, float s, double Mq)
+{
+    const int64_t total = (int64_t)B * C;
+    const int cfull = C & ~31;
+    for (int64_t q = (int64_t)blockIdx.x * NT + threadIdx.x; q < total; q += (int64_t)gridDim.x * NT) {
+        const int b = (int)(q / C), c = (int)(q - (int64_t)b * C);
+        const int8_t* col = x + (int64_t)b * T * C + c;
+        const float sum = torch_outer_rowsum([&](int t) { return (float)col[(int64_t)t * C] * s; }, T, c >= cfull);
+        const float mean = sum / (float)T;
+        const float z = rintf(mean / s);
+        out[q] = (int8_t)clamp_i32(requant_exact((int)z, Mq), -128, 127);
+    }
+}
+
 }  // namespace
 
 // ================================================================================================
@@ -1167,7 +1430,7 @@ static int window_attention_launch(const int8_t* qkv, int8_t* out, int64_t ldo, 
                                    int heads, int tokens, int head_dim, uint32_t m_s, int32_t e_s, uint32_t m_b,
                                    int32_t e_b, float s_attn, uint32_t m_o, int32_t e_o, const float* phi,
                                    const float* phi_masked, WinMap omap, ivit_stream_t stream, const uint32_t* band = nullptr,
-                                   int band_w = 0, int band_rows = 256)
+                                   int band_w = 0, int band_rows = 256, bool long_rows = false)
 {
     IVIT_REQUIRE(qkv && out && bias_add, "ivit_window_attention_i8: NULL operand");
     // (16 band rows per wave in LDS: 4 x 16 x (192 + 4) dwords = 49 KB beside the kernel's 11 KB stay below the 64 KB of a default launch)
@@ -1175,8 +1438,12 @@ static int window_attention_launch(const int8_t* qkv, int8_t* out, int64_t ldo, 
                  "ivit_window_attention_i8_band: the band table must be 16-byte aligned, its width a multiple of 16 in [16, 192]");
     IVIT_REQUIRE(windows > 0 && heads > 0 && windows_per_image > 0 && windows % windows_per_image == 0,
                  "ivit_window_attention_i8: bad window counts");
-    if (head_dim != WHD || tokens < 2 || tokens > 64) {
+    if (!long_rows && (head_dim != WHD || tokens < 2 || tokens > 64)) {
         ivit_set_error("ivit_window_attention_i8: unsupported geometry head_dim=%d tokens=%d (need 32, 2..64)", head_dim, tokens);
+        return IVIT_ERR_UNSUPPORTED;
+    }
+    if (long_rows && (head_dim != WHD || tokens < 65 || tokens > 144)) {
+        ivit_set_error("ivit_window_attention_i8_long: unsupported geometry head_dim=%d tokens=%d (need 32, 65..144)", head_dim, tokens);
         return IVIT_ERR_UNSUPPORTED;
     }
     IVIT_REQUIRE(((uintptr_t)qkv % 16 == 0) && ((uintptr_t)out % 8 == 0) && ldo % 8 == 0 && ldo >= (int64_t)heads * head_dim,
@@ -1188,7 +1455,7 @@ static int window_attention_launch(const int8_t* qkv, int8_t* out, int64_t ldo, 
     WinAttnArgs a;
     a.omap = omap;
     a.omap_inv = omap.ws ? 65536 / omap.ws + 1 : 0;
-    for (int qv = 0; qv < 64 && omap.ws; ++qv)
+    for (int qv = 0; qv < (long_rows ? tokens : 64) && omap.ws; ++qv)
         IVIT_REQUIRE(((qv * a.omap_inv) >> 16) == qv / omap.ws, "ivit_window_attention_i8_unwindow: window size %d unsupported", omap.ws);
     a.phi = phi; a.phim = phi_masked;
     IVIT_REQUIRE(band_rows == 256 || band_rows == 1, "ivit_window_attention_i8_band: band_rows must be 256 or 1");
@@ -1226,6 +1493,20 @@ static int window_attention_launch(const int8_t* qkv, int8_t* out, int64_t ldo, 
     const size_t band_bytes = a.band ? (size_t)WPB * 16 * (band_w + WBAND_PAD) * sizeof(unsigned) : 0;
     const dim3 grd(grid < 8192 ? grid : 8192), blk(NT);
     hipStream_t st = ivit_stream(stream);
+    if (long_rows) {
+        const int kp = 16 * ((tokens + 15) >> 4);
+        if (a.band) {
+            if (a.rq32) hipLaunchKernelGGL((window_attention_long_kernel<2, true>), grd, blk, band_bytes, st, a, kp);
+            else hipLaunchKernelGGL((window_attention_long_kernel<2, false>), grd, blk, band_bytes, st, a, kp);
+        } else if (a.phi) {
+            if (a.rq32) hipLaunchKernelGGL((window_attention_long_kernel<1, true>), grd, blk, 0, st, a, kp);
+            else hipLaunchKernelGGL((window_attention_long_kernel<1, false>), grd, blk, 0, st, a, kp);
+        } else {
+            if (a.rq32) hipLaunchKernelGGL((window_attention_long_kernel<0, true>), grd, blk, 0, st, a, kp);
+            else hipLaunchKernelGGL((window_attention_long_kernel<0, false>), grd, blk, 0, st, a, kp);
+        }
+        IVIT_CHECK_LAUNCH("ivit_window_attention_i8_long");
+    }
     if (a.band) {
         if (a.rq32) hipLaunchKernelGGL((window_attention_kernel<2, true>), grd, blk, band_bytes, st, a);
         else hipLaunchKernelGGL((window_attention_kernel<2, false>), grd, blk, band_bytes, st, a);
@@ -1278,4 +1559,41 @@ IVIT_EXPORT int ivit_window_attention_i8_unwindow(const int8_t* qkv, int8_t* out
                  shift, windows_per_image, tokens);
     return window_attention_launch(qkv, out, ldo, bias_add, mask_region, mask_value, windows, windows_per_image, heads, tokens,
                                    head_dim, m_s, e_s, m_b, e_b, s_attn, m_o, e_o, phi, phi_masked, WinMap{H, W, ws, shift}, stream);
+}
+
+IVIT_EXPORT int ivit_window_attention_i8_long(const int8_t* qkv, int8_t* out, int64_t ldo, const int16_t* bias_add,
+                                              const uint8_t* mask_region, int mask_value, int windows, int windows_per_image, int heads,
+                                              int tokens, int head_dim, uint32_t m_s, int32_t e_s, uint32_t m_b, int32_t e_b, float s_attn,
+                                              uint32_t m_o, int32_t e_o, const float* phi, const float* phi_masked, const uint32_t* band,
+                                              int band_w, int band_rows, int H, int W, int ws, int shift, int image_order,
+                                              ivit_stream_t stream)
+{
+    if (!(ws > 0 && ws * ws == tokens && H > 0 && W > 0 && H % ws == 0 && W % ws == 0 && shift >= 0 && shift < ws &&
+          windows_per_image == (H / ws) * (W / ws))) {
+        ivit_set_error("ivit_window_attention_i8_long: H=%d W=%d ws=%d shift=%d do not describe %d windows of %d tokens per image", H, W,
+                       ws, shift, windows_per_image, tokens);
+        return IVIT_ERR_UNSUPPORTED;
+    }
+    if (band && (band_w < 16 || band_w > 192 || band_w % 16 != 0 || (uintptr_t)band % 16 != 0 || (band_rows != 256 && band_rows != 1) ||
+                 phi || phi_masked)) {
+        ivit_set_error("ivit_window_attention_i8_long: bad band table (16-byte aligned, width a multiple of 16 in [16, 192], 256 or 1 rows, "
+                       "no phi tables beside it)");
+        return IVIT_ERR_UNSUPPORTED;
+    }
+    IVIT_REQUIRE(image_order == 0 || image_order == 1, "ivit_window_attention_i8_long: image_order must be 0 or 1");
+    return window_attention_launch(qkv, out, ldo, bias_add, mask_region, band ? 0 : mask_value, windows, windows_per_image, heads, tokens,
+                                   head_dim, m_s, e_s, m_b, e_b, s_attn, m_o, e_o, phi, phi_masked,
+                                   image_order ? WinMap{H, W, ws, shift} : WinMap{0, 0, 0, 0}, stream, band, band ? band_w : 0,
+                                   band ? band_rows : 256, true);
+}
+
+IVIT_EXPORT int ivit_avgpool_requant_i8_literal(const int8_t* x, int8_t* out, int batch, int tokens, int C, float s_in, uint32_t m,
+                                                int32_t e, ivit_stream_t stream)
+{
+    IVIT_REQUIRE(x && out && batch > 0 && tokens > 0 && C > 0 && s_in > 0.0f, "ivit_avgpool_requant_i8_literal: bad operand");
+    const double Mq = ivit_dyadic_to_double(m, e);
+    IVIT_REQUIRE(Mq < 1048576.0, "ivit_avgpool_requant_i8_literal: multiplier too large");
+    hipLaunchKernelGGL(avgpool_literal_kernel, dim3(ew_grid((int64_t)batch * C)), dim3(NT), 0, ivit_stream(stream), x, out, batch,
+                       tokens, C, s_in, Mq);
+    IVIT_CHECK_LAUNCH("ivit_avgpool_requant_i8_literal");
 }

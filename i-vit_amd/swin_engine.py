@@ -24,12 +24,39 @@ from . import _lib
 from .engine_common import EngineBase, _np, block_copy, frag_copy, layernorm
 from .prepare import (LayerNormParams, LinearParams, dyadic, f32, pad_head, phi_is_identity, phi_table, phi_tables, quant_sym,
                       requant_host, sym_scale, window_shiftexp_band)
-from .synth import IMG_SIZE
 from .topk import TOPK_MAX
 
 PATCH = 4
 HEAD_DIM = 32
 IDENT = (1 << 30, 30)  # dyadic 1.0
+SHORT_WINDOW = 64      # tokens per window of the one-wave-per-window entries (ivit_window_attention_i8*); above: *_long
+LONG_WINDOW = 144      # ivit_window_attention_i8_long: 65..144 tokens (windows of 9x9 .. 12x12)
+
+
+def key_pad(N: int) -> int:
+    """key length of a row of the bias / region tables: 64 for the short entries, whole key tiles of 16 for the long one"""
+    return 64 if N <= SHORT_WINDOW else (N + 15) // 16 * 16
+
+
+def unsupported_geometry(img_size: int, patch: int, window: int, stages: int) -> str | None:
+    """None when IntSwinEngine can run this geometry: square images, patch 4, and at every stage either a map no larger than the
+    window (one window, no shift: SwinTransformerBlock's rule) or a window that divides the map, of at most 144 tokens"""
+    if patch != PATCH:
+        return f"geometry: patch {patch} (fused engine: {PATCH})"
+    if img_size % PATCH:
+        return f"geometry: image size {img_size} is not a multiple of the patch"
+    H = img_size // PATCH
+    for li in range(stages):
+        win = min(window, H)
+        if H > window and H % window:
+            return f"geometry: stage {li} map {H}x{H} is not a whole number of {window}x{window} windows"
+        if win * win > LONG_WINDOW:
+            return f"geometry: {win}x{win} windows ({win * win} tokens; fused window attention: <= {LONG_WINDOW})"
+        if li < stages - 1:
+            if H % 2:
+                return f"geometry: stage {li} map {H}x{H} cannot be merged"
+            H //= 2
+    return None
 
 
 def _pad64(k):
@@ -63,10 +90,54 @@ def window_row_map(B: int, H: int, W: int, ws: int, shift: int) -> np.ndarray:
     return (np.arange(B)[:, None] * (H * W) + idx.reshape(-1)[None, :]).reshape(-1)
 
 
+def pool_literal_host(q: np.ndarray, s: float) -> np.ndarray:
+    """Host restatement of ivit_avgpool_requant_i8_literal's float32 mean (csrc/swin.hip, rowsum.h torch_outer_rowsum): q int8
+    [B, T, C], s the input scale -> float32 [B, C], torch's CPU mean over the transposed view of y = fl(q * s) (serial order)."""
+    B, T, C = q.shape
+    y = (q.astype(f32) * f32(s)).astype(f32)
+
+    def cascade(v):          # v [n, ...]: rowsum.h torch_cascade_sum along axis 0
+        n = v.shape[0]
+        lg = max(0, int(np.ceil(np.log2(n)))) if n > 1 else 0
+        lp = max(4, lg // 4)
+        step, mask = 1 << lp, (1 << lp) - 1
+        a0 = np.zeros(v.shape[1:], f32)
+        a1, a2, a3 = a0.copy(), a0.copy(), a0.copy()
+        i = 0
+        while i + step <= n:
+            for _ in range(step):
+                a0 = (a0 + v[i]).astype(f32)
+                i += 1
+            a1, a0 = (a1 + a0).astype(f32), np.zeros_like(a0)
+            if (i & (mask << lp)) == 0:
+                a2, a1 = (a2 + a1).astype(f32), np.zeros_like(a1)
+                if (i & (mask << (2 * lp))) == 0:
+                    a3, a2 = (a3 + a2).astype(f32), np.zeros_like(a2)
+        for j in range(i, n):
+            a0 = (a0 + v[j]).astype(f32)
+        return (((a0 + a1).astype(f32) + a2).astype(f32) + a3).astype(f32)
+
+    v = y.transpose(1, 0, 2)                       # [T, B, C]
+    out = cascade(v)
+    cf = C & ~31
+    if cf < C:                                     # tail columns: four interleaved partials, the T % 4 last elements into the first
+        t = v[:, :, cf:]
+        n4 = T // 4
+        p = [cascade(t[k:4 * n4:4]) if n4 else np.zeros(t.shape[1:], f32) for k in range(4)]
+        for j in range(4 * n4, T):
+            p[0] = (p[0] + t[j]).astype(f32)
+        out[:, cf:] = (((p[0] + p[1]).astype(f32) + p[2]).astype(f32) + p[3]).astype(f32)
+    return (out / f32(T)).astype(f32)
+
+
 class IntSwinEngine(EngineBase):
     def __init__(self, float_state, ranges, embed_dim=96, depths=(2, 2, 6, 2), num_heads=(3, 6, 12, 24), window=7,
-                 device="cuda:0", max_batch: int = 64):
+                 device="cuda:0", max_batch: int = 64, img_size: int = 224):
         self.C0, self.depths, self.heads, self.window = embed_dim, tuple(depths), tuple(num_heads), window
+        why = unsupported_geometry(img_size, PATCH, window, len(self.depths))
+        if why is not None:
+            raise ValueError(why)
+        self.img_size = img_size
         self.dev = torch.device(device)
         self.max_batch = max_batch
         _lib.lib()  # fail loudly now if the HIP library is absent
@@ -127,7 +198,7 @@ class IntSwinEngine(EngineBase):
 
         # ---- stages
         self.stages = []
-        G = IMG_SIZE // PATCH
+        G = img_size // PATCH
         H = W = G
         C = embed_dim
         for li, (depth, nH) in enumerate(zip(self.depths, self.heads)):
@@ -153,7 +224,8 @@ class IntSwinEngine(EngineBase):
                 bias = ktab[rel_position_index(win).reshape(-1)].reshape(N, N, nH).transpose(2, 0, 1)
                 bias_add = requant_host(bias, m2[0], e2[0])                    # identity operand of qact2, :143-147
                 assert np.abs(bias_add).max() < 32768
-                bias_pad = np.zeros((nH, N, 64), np.int16)
+                kp = key_pad(N)
+                bias_pad = np.zeros((nH, N, kp), np.int16)
                 bias_pad[:, :, :N] = bias_add
                 region, mask_value = None, 0
                 # Shiftmax input: phi(q) = fl(fl(q*s)/s) for a plain score, fl(fl(fl(q*s) - 100)/s) for one under the shift
@@ -169,7 +241,7 @@ class IntSwinEngine(EngineBase):
                         mask_value = -1                                         # unused by the literal form
                     else:
                         mask_value = int(mval)
-                    region = np.zeros(((H // win) * (W // win), 64), np.uint8)
+                    region = np.zeros(((H // win) * (W // win), kp), np.uint8)
                     region[:, :N] = shift_mask_regions(H, W, win, shift)
                 band, band_w = (None, 0)
                 if att_nat:
@@ -184,7 +256,7 @@ class IntSwinEngine(EngineBase):
                                    bias=dev(bias_pad), region=None if region is None else dev(region),
                                    mask_value=mask_value, nW=(H // win) * (W // win),
                                    phi=dev(phi_table(s_A)) if att_nat else None, phim=dev(phi_m) if att_nat else None,
-                                   band=None if band is None else dev(band), band_w=band_w)
+                                   band=None if band is None else dev(band), band_w=band_w, long=N > SHORT_WINDOW)
                 lp, d = lin_host(p + "attn.proj", s_a3)
                 s_a4 = s(p + "attn.qact4", 16)
                 mp, ep = dyadic(lp.s_acc, s_a4)
@@ -229,6 +301,12 @@ class IntSwinEngine(EngineBase):
         self.ln_f = ln_dev("norm", s_q2, s_x)
         s_q3 = s("qact3")
         self.pool_me = sme(s_q2, s_q3)
+        # the tail's float mean over an even token count can land on an exact .5 tie; at a natural scale its float32 rounding then decides
+        # qact3: the literal pooling restates torch's CPU order (ivit_avgpool_requant_i8_literal).  224 px (49 tokens): the integer form
+        self.pool_literal = self.T_last % 2 == 0 and not phi_is_identity(s_q2)
+        self.s_pool = float(s_q2)
+        if self.pool_literal:
+            self.natural_sites += 1
         lp = LinearParams(P["head.weight"], P.get("head.bias"), s_q3)
         hW, hb, hs, self.num_classes = pad_head(lp.W8, lp.b32, lp.s_acc)      # any class count
         self.head = dict(W=dev(hW), b=dev(hb), K=lp.K, N=hW.shape[0])
@@ -240,7 +318,7 @@ class IntSwinEngine(EngineBase):
     # ------------------------------------------------------------------ plumbing
     def _alloc(self, B):
         C0 = self.C0
-        M0 = B * (IMG_SIZE // PATCH) ** 2
+        M0 = B * (self.img_size // PATCH) ** 2
         ld0 = _pad64(C0)
         i8 = dict(dtype=torch.int8, device=self.dev)
         i16 = dict(dtype=torch.int16, device=self.dev)
@@ -295,7 +373,7 @@ class IntSwinEngine(EngineBase):
 
     # ------------------------------------------------------------------ forward
     def forward(self, images: torch.Tensor, taps: dict | None = None):
-        """images: float32 [B,3,224,224] on the engine's device.  Returns (logits_int32 [B,1000], logits_f32, top1)
+        """images: float32 [B,3,img_size,img_size] on the engine's device.  Returns (logits_int32 [B,1000], logits_f32, top1)
         -- views of the engine's workspace, valid until the next call.  `taps` (tests) receives clones of the
         intermediate integer tensors in the reference's layouts."""
         return self._forward(images, taps)
@@ -304,10 +382,11 @@ class IntSwinEngine(EngineBase):
         """forward; topk = (k, targets, hits): the classifier launch is the top-k selection (forward_topk)"""
         assert images.is_cuda and images.dtype in (torch.float32, torch.uint8) and images.is_contiguous()
         B = images.shape[0]
-        assert images.shape[1:] == (3, IMG_SIZE, IMG_SIZE) and 0 < B <= self.max_batch
+        img = self.img_size
+        assert images.shape[1:] == (3, img, img) and 0 < B <= self.max_batch
         ws = self.ws
         st = self._stream()
-        G = IMG_SIZE // PATCH
+        G = img // PATCH
         C0 = self.C0
         M = B * G * G
 
@@ -323,10 +402,10 @@ class IntSwinEngine(EngineBase):
         if images.dtype == torch.uint8:      # uint8 pixels: ToTensor + Normalize + the input QuantAct as a 3 x 256 table (engine.py)
             if self.input_lut is None:
                 self.set_input_normalisation()
-            _lib.call("ivit_quantize_patchify_u8_i8", _lib.ptr(images), _lib.ptr(ws["a0"]), 64, B, 3, IMG_SIZE, PATCH,
+            _lib.call("ivit_quantize_patchify_u8_i8", _lib.ptr(images), _lib.ptr(ws["a0"]), 64, B, 3, img, PATCH,
                       _lib.ptr(self.input_lut), st)
         else:
-            _lib.call("ivit_quantize_patchify_ld_f32_i8", _lib.ptr(images), _lib.ptr(ws["a0"]), 64, B, 3, IMG_SIZE, PATCH,
+            _lib.call("ivit_quantize_patchify_ld_f32_i8", _lib.ptr(images), _lib.ptr(ws["a0"]), 64, B, 3, img, PATCH,
                       self.inv_s0, st)
         self._gemm(ws["a0"], 64, self.patch, ws["pe"], C0, M, st)
         tap("patch_embed.qact_before_norm", ws["pe"], M, C0)
@@ -365,7 +444,15 @@ class IntSwinEngine(EngineBase):
                     taps[p + "attn.qact1"] = hm.permute(1, 3, 0, 2, 4).reshape(nwin, N, 3 * C).clone()
                 a = blk["attn"]
                 fuse_proj = self.proj_fused and taps is None
-                if a["band"] is not None:
+                if a["long"]:
+                    # windows of 65..144 tokens: one entry for every Shiftmax form and both output orders
+                    band = a["band"]
+                    _lib.call("ivit_window_attention_i8_long", _lib.ptr(ws["qkv"]), _lib.ptr(ws["ao"]), ld, _lib.ptr(a["bias"]),
+                              _lib.ptr(a["region"]), a["mask_value"], nwin, a["nW"], nH, N, HEAD_DIM, a["ms"][0], a["ms"][1], a["mb"][0],
+                              a["mb"][1], a["s_attn"], a["mo"][0], a["mo"][1], _lib.ptr(None if band is not None else a["phi"]),
+                              _lib.ptr(None if band is not None else a["phim"]), _lib.ptr(band), a["band_w"],
+                              0 if band is None else int(band.shape[0]), H, W, win, shift, int(fuse_proj), st)
+                elif a["band"] is not None:
                     _lib.call("ivit_window_attention_i8_band", _lib.ptr(ws["qkv"]), _lib.ptr(ws["ao"]), ld, _lib.ptr(a["bias"]),
                               _lib.ptr(a["region"]), nwin, a["nW"], nH, N, HEAD_DIM, a["ms"][0], a["ms"][1], a["mb"][0], a["mb"][1],
                               a["s_attn"], a["mo"][0], a["mo"][1], _lib.ptr(a["band"]), a["band_w"], int(a["band"].shape[0]), H, W,
@@ -434,8 +521,12 @@ class IntSwinEngine(EngineBase):
         C, T = self.C_last, self.T_last
         layernorm(self.ln_f, x, C, B * T, C, ws["hN"], C, st)
         tap("qact2", ws["hN"], B * T, C)
-        _lib.call("ivit_avgpool_requant_i8", _lib.ptr(ws["hN"]), _lib.ptr(ws["pooled"]), B, T, C, self.pool_me[0],
-                  self.pool_me[1], st)
+        if self.pool_literal:
+            _lib.call("ivit_avgpool_requant_i8_literal", _lib.ptr(ws["hN"]), _lib.ptr(ws["pooled"]), B, T, C, self.s_pool,
+                      self.pool_me[0], self.pool_me[1], st)
+        else:
+            _lib.call("ivit_avgpool_requant_i8", _lib.ptr(ws["hN"]), _lib.ptr(ws["pooled"]), B, T, C, self.pool_me[0],
+                      self.pool_me[1], st)
         tap("qact3", ws["pooled"], B, C)
         hd = self.head
         _lib.call("ivit_gemm_i8_i32", _lib.ptr(ws["pooled"]), C, _lib.ptr(hd["W"]), hd["K"], _lib.ptr(hd["b"]),

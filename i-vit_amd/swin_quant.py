@@ -247,7 +247,6 @@ class SwinTransformer(EngineDispatch, nn.Module):
         # the widths the constructor (= the reference's, swin_quant.py:110, 214, 222, 475) gives every QuantAct are the ones
         # the Swin kernels hard-wire; a width edited afterwards sends the model down the module path
         self._reference_widths = {n: int(m.activation_bit) for n, m in self._quant_acts()}
-        self._phi_check = None
 
     @staticmethod
     def _init_weights(m):
@@ -298,35 +297,19 @@ class SwinTransformer(EngineDispatch, nn.Module):
         for n, m in self._quant_acts():
             if int(m.activation_bit) != self._reference_widths[n]:
                 return f"QuantAct {n} is {int(m.activation_bit)}-bit (fused engine: {self._reference_widths[n]})"
-        last = self.patch_grid[0] // 2 ** (self.num_layers - 1)
-        if (last * last) % 2 == 0:
-            # the token pooling of the tail (swin_quant.py:554) is a float mean over last^2 tokens: with an even count an exact
-            # .5 tie is possible and, at natural scales, decided by float fuzz the engine does not restate -> module path
-            return self._natural_scale_reason()
-        return None
-
-    def _natural_scale_reason(self):
-        """Non-None when some QuantAct scale is natural (fl(fl(q*s)/s) != q for some q of its width).  The Swin engine handles
-        natural scales (literal LayerNorm on the 16-bit stream, literal Shiftmax on phi tables, remapped ShiftGELU table,
-        swin_engine.py); this check is only consulted for geometries whose tail pooling could tie (see the caller)."""
-        from .prepare import phi_is_identity, sym_scale
-        fp = self._fingerprint()
-        if self._phi_check is None or self._phi_check[0] != fp:
-            bad = None
-            for n, m in self._quant_acts():
-                lo, hi = float(m.x_min.reshape(-1)[0]), float(m.x_max.reshape(-1)[0])
-                if lo == hi == 0.0:
-                    continue
-                if not phi_is_identity(sym_scale(lo, hi, int(m.activation_bit)), int(m.activation_bit)):
-                    bad = f"QuantAct {n} has a natural (non power-of-two) scale: Swin runs module by module there"
-                    break
-            self._phi_check = (fp, bad)
-        return self._phi_check[1]
+        from .swin_engine import unsupported_geometry
+        ih, iw = self.patch_embed.img_size
+        ph, pw = self.patch_embed.patch_size
+        if ih != iw or ph != pw:
+            return f"geometry: {ih}x{iw} images, {ph}x{pw} patches (fused engine: square)"
+        # an even token count of the tail pooling (swin_quant.py:554) can put its float mean on an exact .5 tie; at natural scales the
+        # engine then runs the literal pooling in torch's CPU order (ivit_avgpool_requant_i8_literal)
+        return unsupported_geometry(ih, ph, self.window_size, self.num_layers)
 
     def _build_engine(self, device, max_batch):
         from .swin_engine import IntSwinEngine
         return IntSwinEngine(dict(self.state_dict()), self.ranges(), self.embed_dim, self.depths, self.num_heads,
-                             self.window_size, device=device, max_batch=max_batch)
+                             self.window_size, device=device, max_batch=max_batch, img_size=self.patch_embed.img_size[0])
 
     def forward(self, x):
         if self.takes_engine(x):

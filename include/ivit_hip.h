@@ -455,6 +455,13 @@ int ivit_patch_merge_i16(const int16_t* x, int16_t* out, int batch, int H, int W
  *   out[b][c] = clamp8(RNE(round(fl32(sum_t x[b][t][c] / tokens)) * m / 2^e)) */
 int ivit_avgpool_requant_i8(const int8_t* x, int8_t* out, int batch, int tokens, int C, uint32_t m, int32_t e,
                             ivit_stream_t stream);
+/* The same at a natural input scale s_in, literally: y = fl(x * s_in), the float32 mean over the tokens in the order of torch's CPU
+ * reduction over the transposed view (per column c the outer-reduction cascade of csrc/rowsum.h, the four-partial form for the tail
+ * columns c >= 32 * (C / 32)) divided by float32(tokens), then qact3's steps: z = rint(fl(mean / s_in)), out = clamp8(RNE(z * m / 2^e)).
+ * That is the order torch's serial reduction takes; above 32768 input elements torch splits the work over its threads, along the batch
+ * when batch >= the thread count (same order), else along the columns (a different order for the tail columns). */
+int ivit_avgpool_requant_i8_literal(const int8_t* x, int8_t* out, int batch, int tokens, int C, float s_in, uint32_t m, int32_t e,
+                                    ivit_stream_t stream);
 
 /* WindowAttention core (swin_quant.py:137-161): matmul_1 -> qact_attn1 -> + relative position bias through the
  * two-operand qact2 -> + shift mask -> Shiftmax -> matmul_2 -> qact3, one wave per (window, head).
@@ -505,6 +512,20 @@ int ivit_window_attention_i8_unwindow(const int8_t* qkv, int8_t* out, int64_t ld
                                       int tokens, int head_dim, uint32_t m_s, int32_t e_s, uint32_t m_b, int32_t e_b,
                                       float s_attn, uint32_t m_o, int32_t e_o, const float* phi, const float* phi_masked,
                                       int H, int W, int ws, int shift, ivit_stream_t stream);
+/* Windows of 65..144 tokens (ws = 9..12, Swin at 384 px with 12 x 12 windows): the arithmetic of ivit_window_attention_i8 with every
+ * form of the entries above in one entry.  Layouts differ from the short entries in the key padding only: bias_add [heads][tokens][kp]
+ * int16 and mask_region [windows_per_image][kp] uint8 (or NULL), kp = 16 * ceil(tokens / 16).  Shiftmax form: band != NULL the table
+ * form of ivit_window_attention_i8_band (band_w, band_rows = 256 or 1; mask_value unused; phi tables NULL); else phi / phi_masked the
+ * literal form of ivit_window_attention_i8_compat; else the power-of-two form with the integer mask_value.  H, W, ws, shift describe
+ * the windows (tokens == ws * ws, windows_per_image == (H / ws) * (W / ws), 0 <= shift < ws) in both output orders; image_order = 1
+ * writes the rows at their image positions as ivit_window_attention_i8_unwindow does, 0 in window order.
+ * Errors: IVIT_ERR_UNSUPPORTED for tokens outside 65..144, head_dim != 32, a bad band table or a window description that does not
+ * match; IVIT_ERR_INVALID ("NULL operand", alignment, multipliers) otherwise. */
+int ivit_window_attention_i8_long(const int8_t* qkv, int8_t* out, int64_t ldo, const int16_t* bias_add, const uint8_t* mask_region,
+                                  int mask_value, int windows, int windows_per_image, int heads, int tokens, int head_dim, uint32_t m_s,
+                                  int32_t e_s, uint32_t m_b, int32_t e_b, float s_attn, uint32_t m_o, int32_t e_o, const float* phi,
+                                  const float* phi_masked, const uint32_t* band, int band_w, int band_rows, int H, int W, int ws,
+                                  int shift, int image_order, ivit_stream_t stream);
 
 /* =================================================================================================
  * I-BERT operator family (models/quantization_utils/ibert_modules.py; registry key 'ibert', the fork's default,
