@@ -107,6 +107,10 @@ SIGNATURES = {
                                           ci, ci, ci, ci, vp],
     "ivit_window_attention_i8_long": [vp, vp, i64, vp, vp, ci, ci, ci, ci, ci, ci, u32, i32, u32, i32, f32, u32, i32, vp, vp, vp, ci,
                                       ci, ci, ci, ci, ci, ci, vp],
+    # evaluation transform (include/ivit_hip.h, end): the first two are host functions
+    "ivit_eval_geometry": [ci, ci, ci, ci, vp],
+    "ivit_resize_crop_workspace": [vp, ci, ci, vp, vp],
+    "ivit_resize_crop_bicubic_u8": [vp, vp, vp, ci, ci, ci, ci, ci, vp, i64, vp, vp],
 }
 
 

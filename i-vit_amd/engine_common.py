@@ -117,3 +117,4 @@ class EngineBase(GraphReplay, HeadTopK):
         accepts uint8 [B,3,H,W] pixel tensors -- a quarter of the bytes of the float32 input -- and quantises them through a
         3 x 256 table that holds the float pipeline's result per (channel, pixel value): same integers as the float path."""
         self.input_lut = torch.from_numpy(input_lut_u8(self.s0, mean, std)).to(self.dev)
+        self.input_norm = (tuple(float(v) for v in mean), tuple(float(v) for v in std))   # what the table was built for

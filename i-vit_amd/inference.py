@@ -113,8 +113,26 @@ def save_checkpoint(model, path, model_config: Optional[dict] = None, **extra):
     torch.save(d, path)
 
 
-def evaluate_dataset(model, data_loader, device, *, print_batch_stats: bool = True):
-    """inference.py:231-267 -> (top-1, top-3, top-5) accuracy in percent over (images, targets) batches."""
+def _forward_transformed(model, transform, packed, lo, hi, device):
+    """logits of images [lo, hi) of a transforms.PackedImages batch: the device resize + crop, then the fused engine on the uint8
+    crops (its input table set to the transform's Normalize) or, for any other model, the float32 tensor ToTensor + Normalize give"""
+    u8 = transform(packed, lo, hi, device=device)
+    takes = getattr(model, "takes_engine", None)
+    if takes is not None and takes(u8):
+        eng = model.engine(u8.shape[0])
+        norm = (transform.mean, transform.std)
+        if getattr(eng, "input_lut", None) is None or getattr(eng, "input_norm", None) != norm:
+            eng.set_input_normalisation(*norm)
+        _, logits_f32, _ = eng(u8)
+        return logits_f32.clone()
+    return model(transform.to_float(u8))
+
+
+def evaluate_dataset(model, data_loader, device, *, print_batch_stats: bool = True, transform=None):
+    """inference.py:231-267 -> (top-1, top-3, top-5) accuracy in percent over (images, targets) batches.
+
+    transform: None (the loader yields image tensors, as the reference's does), or a transforms.EvalTransform -- the loader then
+    yields (transforms.PackedImages, targets) and the reference's Resize -> CenterCrop -> ToTensor -> Normalize runs on the device."""
     correct1 = correct3 = correct5 = tot = 0
     batch_times = []
     start_total = time.perf_counter()
@@ -122,8 +140,12 @@ def evaluate_dataset(model, data_loader, device, *, print_batch_stats: bool = Tr
     with torch.no_grad():
         for imgs, targets in data_loader:
             t0 = time.perf_counter()
-            imgs, targets = imgs.to(device), targets.to(device)
-            logits = model(imgs)
+            if transform is None:
+                imgs, targets = imgs.to(device), targets.to(device)
+                logits = model(imgs)
+            else:
+                logits = _forward_transformed(model, transform, imgs, 0, imgs.size(0), device)
+                targets = targets.to(device)
             pred5 = logits.topk(5, dim=1).indices
             hit = pred5 == targets.reshape(-1, 1)
             correct1 += int(hit[:, 0].sum())
@@ -140,7 +162,7 @@ def evaluate_dataset(model, data_loader, device, *, print_batch_stats: bool = Tr
     return 100 * correct1 / tot, 100 * correct3 / tot, 100 * correct5 / tot
 
 
-def evaluate_dataset_parallel(model, data_loader, device, *, scorer=None, print_batch_stats: bool = True):
+def evaluate_dataset_parallel(model, data_loader, device, *, scorer=None, print_batch_stats: bool = True, transform=None):
     """evaluate_dataset data-parallel over the ranks of the default process group (world 1 without one) -> the same
     (top-1, top-3, top-5) percentages on every rank.
 
@@ -152,7 +174,9 @@ def evaluate_dataset_parallel(model, data_loader, device, *, scorer=None, print_
 
     scorer(logits, targets int32 [b], hits int64 [5], k=5): default topk.count_hits, the HIP selection over the float
     logits (value descending, equal logits by ascending class -- where evaluate_dataset's torch.topk leaves the order of
-    tied logits unspecified)."""
+    tied logits unspecified).
+
+    transform: as for evaluate_dataset; a rank transforms only its shard_bounds slice of each packed batch."""
     if dist.is_available() and dist.is_initialized():
         world, rank = dist.get_world_size(), dist.get_rank()
     else:
@@ -167,9 +191,13 @@ def evaluate_dataset_parallel(model, data_loader, device, *, scorer=None, print_
             lo, hi = shard_bounds(imgs.size(0), world, rank)
             if hi == lo:
                 continue
-            x = imgs[lo:hi].to(device)
-            t = targets[lo:hi].to(device=device, dtype=torch.int32)
-            scorer(model(x), t, hits, 5)
+            if transform is None:
+                x = imgs[lo:hi].to(device)
+                t = targets[lo:hi].to(device=device, dtype=torch.int32)
+                scorer(model(x), t, hits, 5)
+            else:
+                t = targets[lo:hi].to(device=device, dtype=torch.int32)
+                scorer(_forward_transformed(model, transform, imgs, lo, hi, device), t, hits, 5)
             local += hi - lo
     hits, tot = allreduce_hits(hits, local)
     total_time = time.perf_counter() - start_total

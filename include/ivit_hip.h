@@ -606,6 +606,30 @@ int ivit_ibert_layernorm_i16_i8_ex(const int16_t* x, int64_t ldx, int rows, int 
                                    const float* s_out, float shift_pow2, const uint32_t* m, const int32_t* e, int8_t* out, int64_t ldo,
                                    int fast_division, ivit_stream_t stream);
 
+/* ---- evaluation transform (the reference's data pipeline in front of the model) ----------------------------------------
+ * torchvision Resize([resize_short], BICUBIC) on a PIL image, then CenterCrop(crop) (scripts/inference.py:63-66,
+ * utils/data_utils.py:82-91), byte for byte: Pillow's 8-bit bicubic resample (a = -0.5, 22-bit fixed-point taps, horizontal pass
+ * first, uint8 between the passes), of which only the crop's pixels are computed.  DESIGN.md "Eval transform".
+ *
+ * ivit_eval_geometry: HOST function, host out4 = (new_h, new_w, top, left) for an h x w source: short side -> resize_short, long
+ * side int(resize_short * long / short) in float64; top / left = round((new - crop) / 2), half to even.  IVIT_ERR_UNSUPPORTED
+ * ("unsupported geometry") for an empty image, crop <= 32 (input sizes without a resize) or crop > the resized short side
+ * (torchvision would pad); IVIT_ERR_INVALID for a NULL out4. */
+int ivit_eval_geometry(int h, int w, int resize_short, int crop, int32_t* out4);
+/* HOST function: geom = host int32 [batch][6] rows (h, w, new_h, new_w, top, left); plan3 (host) = (ksize_h, ksize_v, rows), the
+ * largest horizontal / vertical tap count and intermediate row count of the batch; *bytes = the workspace
+ * ivit_resize_crop_bicubic_u8 needs for that plan.  IVIT_ERR_UNSUPPORTED ("unsupported geometry") for a row with an empty image,
+ * a crop that does not fit inside the resized image, or crop <= 32. */
+int ivit_resize_crop_workspace(const int32_t* geom, int batch, int crop, int32_t* plan3, int64_t* bytes);
+/* src: packed uint8 HWC RGB images, image b at src + offsets[b] (device int64 [batch]); geom: the same rows as above on the device,
+ * validated by ivit_resize_crop_workspace (the kernels clamp every index to the plan, so a table that disagrees with the plan reads
+ * and writes nothing outside the images, workspace and out); (ksize_h, ksize_v, rows) and workspace_bytes from
+ * ivit_resize_crop_workspace.  out: uint8 [batch][3][crop][crop], planar (the engines' uint8 input).  Alignment: offsets 8,
+ * geom 4, workspace 16 bytes.  IVIT_ERR_INVALID for NULL or misaligned operands, batch outside 0..65535, a plan or workspace that
+ * is too small; IVIT_ERR_UNSUPPORTED for crop <= 32.  Three launches on `stream`. */
+int ivit_resize_crop_bicubic_u8(const uint8_t* src, const int64_t* offsets, const int32_t* geom, int batch, int crop, int ksize_h,
+                                int ksize_v, int rows, void* workspace, int64_t workspace_bytes, uint8_t* out, ivit_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
