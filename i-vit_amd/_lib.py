@@ -111,6 +111,12 @@ SIGNATURES = {
     "ivit_eval_geometry": [ci, ci, ci, ci, vp],
     "ivit_resize_crop_workspace": [vp, ci, ci, vp, vp],
     "ivit_resize_crop_bicubic_u8": [vp, vp, vp, ci, ci, ci, ci, ci, vp, i64, vp, vp],
+    # JPEG decoding (include/ivit_hip.h, end): the first four are host functions
+    "ivit_jpeg_probe": [vp, i64, vp],
+    "ivit_jpeg_plan_image": [vp, i64, vp, i64, vp],
+    "ivit_jpeg_workspace": [vp, i64, vp, vp, ci, vp, vp],
+    "ivit_jpeg_decode_host": [vp, i64, vp, i64],
+    "ivit_jpeg_decode_u8": [vp, vp, ci, i64, i64, i64, vp, i64, vp, vp, vp],
 }
 
 

@@ -1,13 +1,16 @@
 """The reference's evaluation transform on the device (scripts/inference.py:63-66, utils/data_utils.py:82-91):
 Resize(s, BICUBIC) -> CenterCrop(c) -> ToTensor -> Normalize, without torchvision.
 
-Decoding stays on the CPU (ImageFolderU8); the resize and crop run in ivit_resize_crop_bicubic_u8 and are byte-identical to
-Pillow's resize plus torchvision's CenterCrop.  The fused engines take the uint8 crops as they are (their input table folds
+ImageFolderU8 decodes on the CPU; ImageFolderJPEG hands the compressed bytes on, and EvalTransform decodes baseline JPEGs on the
+device (ivit_jpeg_decode_u8, byte-identical to Image.open(f).convert("RGB")), every other file in the loader worker with Pillow.
+The resize and crop run in ivit_resize_crop_bicubic_u8 and are byte-identical to Pillow's resize plus torchvision's CenterCrop.  The fused engines take the uint8 crops as they are (their input table folds
 ToTensor + Normalize + the input QuantAct); the module path takes EvalTransform.to_float(crops), the float32 tensor ToTensor +
 Normalize would give.
 
     loader = torch.utils.data.DataLoader(ImageFolderU8(root), batch_size=256, collate_fn=ImageFolderU8.collate)
     inference.evaluate_dataset_parallel(model, loader, "cuda", transform=EvalTransform.for_input_size(224))
+
+ImageFolderJPEG / ImageFolderJPEG.collate in place of ImageFolderU8 / ImageFolderU8.collate decode on the device instead.
 """
 from __future__ import annotations
 
@@ -123,10 +126,14 @@ class EvalTransform:
             ws = self._ws[device] = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=device)
         return ws
 
-    def __call__(self, packed: PackedImages, lo: int = 0, hi: int | None = None, device="cuda", out: torch.Tensor | None = None):
+    def __call__(self, packed, lo: int = 0, hi: int | None = None, device="cuda", out: torch.Tensor | None = None):
+        """packed: a PackedImages, or an EncodedImages whose images [lo, hi) are decoded on the device first"""
         hi = len(packed) if hi is None else hi
         if not 0 <= lo <= hi <= len(packed):
             raise IndexError(f"shard [{lo}, {hi}) of a batch of {len(packed)}")
+        if isinstance(packed, EncodedImages):
+            packed = decode_images(packed, lo, hi, device)
+            lo, hi = 0, len(packed)
         n, c = hi - lo, self.crop
         device = torch.device(device)
         if device.type == "cuda" and device.index is None:
@@ -214,3 +221,191 @@ class ImageFolderU8:
     def collate(batch, pin: bool | None = None):
         imgs, targets = zip(*batch)
         return pack_images(list(imgs), pin=pin), torch.tensor(targets, dtype=torch.int64)
+
+
+# ---- JPEG decoding on the device ------------------------------------------------------------------------------------------
+
+_INDEX_BYTES = 40          # ivit_jpeg_workspace's index row
+_JPEG_WS = {}              # device -> workspace
+
+
+def _pil_decode_bytes(data) -> np.ndarray:
+    """Image.open(f).convert("RGB") of an encoded file held in memory (the reference's loader)"""
+    try:
+        from PIL import Image
+    except ImportError as e:
+        raise ImportError("files the device decoder does not take are decoded with Pillow, which is not installed") from e
+    import io
+    with Image.open(io.BytesIO(bytes(data))) as img:
+        return np.asarray(img.convert("RGB"))
+
+
+def probe_jpeg(data) -> tuple:
+    """(supported, reason, info): supported is True for a file ivit_jpeg_decode_u8 decodes; reason says why not; info = (h, w,
+    components, sampling) as far as the header gives them (sampling 0 gray, 1 4:4:4, 2 4:2:2, 3 4:2:0, -1 unsupported)"""
+    buf = bytes(data)
+    info = (C.c_int32 * 4)()
+    L = _lib.lib()
+    rc = L.ivit_jpeg_probe(buf, len(buf), info)
+    if rc == 0:
+        return True, "", tuple(int(v) for v in info)
+    return False, L.ivit_last_error_string().decode(), tuple(int(v) for v in info)
+
+
+def decode_jpeg_host(data) -> np.ndarray:
+    """ivit_jpeg_decode_host: one file decoded serially on the host with the device's primitives (uint8 H x W x 3).
+    IvitError for a file the probe rejects or corrupt entropy data."""
+    buf = bytes(data)
+    ok, reason, info = probe_jpeg(buf)
+    if not ok:
+        raise _lib.IvitError(f"unsupported JPEG: {reason}")
+    out = np.empty((info[0], info[1], 3), np.uint8)
+    _lib.call("ivit_jpeg_decode_host", buf, len(buf), out.ctypes.data_as(C.c_void_p), out.size)
+    return out
+
+
+@dataclass
+class EncodedImages:
+    """A batch of compressed images with PackedImages' interface (len, size(0), geometry(resize, crop) from the header sizes).
+    The device images' plan sections (ivit_jpeg_plan_image) lie in one buffer, in image order; the other images carry Pillow's
+    pixels (fallback) and the probe's reason (reasons)."""
+    plan: torch.Tensor          # uint8 [plan bytes], pinned when a GPU is present
+    sec_offsets: np.ndarray     # int64 [B]: section of image b in plan, -1 for a fallback image
+    sec_bytes: np.ndarray       # int64 [B]: its size, 0 for a fallback image
+    offsets: np.ndarray         # int64 [B]: HWC offset of image b in the decoded batch (pack_images' offsets)
+    sizes: np.ndarray           # int32 [B, 2]: (h, w)
+    fallback: dict = field(default_factory=dict)   # b -> uint8 H x W x 3
+    reasons: dict = field(default_factory=dict)    # b -> why b is not decoded on the device
+    _geom: dict = field(default_factory=dict, repr=False)
+
+    def __len__(self):
+        return len(self.offsets)
+
+    def size(self, dim=0):
+        if dim != 0:
+            raise IndexError("EncodedImages has one dimension: images")
+        return len(self)
+
+    def geometry(self, resize: int, crop: int) -> np.ndarray:
+        """int32 [B, 6]: (h, w, new_h, new_w, top, left) per image"""
+        key = (int(resize), int(crop))
+        g = self._geom.get(key)
+        if g is None:
+            g = np.empty((len(self), 6), np.int32)
+            for b, (h, w) in enumerate(self.sizes):
+                g[b, :2] = (h, w)
+                g[b, 2:] = eval_geometry(h, w, resize, crop)
+            self._geom[key] = g
+        return g
+
+
+def encode_images(files, decode_fallback=None, pin: bool | None = None) -> EncodedImages:
+    """list of encoded files (bytes) -> EncodedImages: probe and plan every file; decode_fallback(b, data) -> uint8 H x W x 3
+    decodes the others (default: Pillow's convert("RGB")).  Host code only: loader workers call it without touching the GPU
+    (pass pin=False there)."""
+    L = _lib.lib()
+    n = len(files)
+    bufs = [bytes(f) for f in files]
+    sec_bytes = np.zeros(n, np.int64)
+    sec_offsets = np.full(n, -1, np.int64)
+    reasons = {}
+    total = 0
+    nb = C.c_int64()
+    for b, buf in enumerate(bufs):
+        if L.ivit_jpeg_plan_image(buf, len(buf), None, 0, C.byref(nb)) == 0:
+            sec_offsets[b], sec_bytes[b] = total, nb.value
+            total += nb.value
+        else:
+            reasons[b] = L.ivit_last_error_string().decode()
+    if pin is None:
+        pin = torch.cuda.is_available()
+    plan = torch.empty(max(total, 16), dtype=torch.uint8, pin_memory=bool(pin))
+    base = plan.data_ptr()
+    sizes = np.empty((n, 2), np.int32)
+    fallback = {}
+    decode_fallback = decode_fallback or (lambda b, data: _pil_decode_bytes(data))
+    for b, buf in enumerate(bufs):
+        if sec_offsets[b] >= 0:
+            rc = L.ivit_jpeg_plan_image(buf, len(buf), C.c_void_p(base + int(sec_offsets[b])), int(sec_bytes[b]), C.byref(nb))
+            if rc != 0:
+                raise _lib.IvitError(f"ivit_jpeg_plan_image failed ({rc}): {L.ivit_last_error_string().decode()}")
+            hw = np.frombuffer(C.string_at(base + int(sec_offsets[b]) + 8, 8), np.int32)   # Sec: int64 bytes, then h, w
+            sizes[b] = hw
+        else:
+            a = np.ascontiguousarray(decode_fallback(b, buf))
+            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
+                raise ValueError(f"image {b}: fallback decode gave {a.dtype} {a.shape}, expected uint8 H x W x 3")
+            fallback[b] = a
+            sizes[b] = a.shape[:2]
+    px = sizes[:, 0].astype(np.int64) * sizes[:, 1] * 3
+    offsets = np.concatenate([[0], np.cumsum(px)[:-1]]).astype(np.int64) if n else np.zeros(0, np.int64)
+    return EncodedImages(plan, sec_offsets, sec_bytes, offsets, sizes, fallback, reasons)
+
+
+def _jpeg_workspace(device, nbytes):
+    ws = _JPEG_WS.get(device)
+    if ws is None or ws.numel() < nbytes:
+        ws = _JPEG_WS[device] = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=device)
+    return ws
+
+
+def decode_images(encoded: EncodedImages, lo: int = 0, hi: int | None = None, device="cuda") -> PackedImages:
+    """Images [lo, hi) of an EncodedImages -> a device-resident PackedImages: the device images decoded by ivit_jpeg_decode_u8
+    (one copy of their plan sections), the fallback images' pixels copied in.  IvitError for corrupt entropy data."""
+    hi = len(encoded) if hi is None else hi
+    if not 0 <= lo <= hi <= len(encoded):
+        raise IndexError(f"shard [{lo}, {hi}) of a batch of {len(encoded)}")
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    n = hi - lo
+    start = int(encoded.offsets[lo]) if n else 0
+    sizes = encoded.sizes[lo:hi].copy()
+    offs = encoded.offsets[lo:hi] - start
+    total = int((sizes[:, 0].astype(np.int64) * sizes[:, 1] * 3).sum())
+    out = torch.empty(max(total, 1), dtype=torch.uint8, device=device)
+    sec = encoded.sec_offsets[lo:hi]
+    dev = np.nonzero(sec >= 0)[0]
+    errors = None
+    if len(dev):
+        p0 = int(sec[dev[0]])
+        p1 = int(sec[dev[-1]] + encoded.sec_bytes[lo + dev[-1]])
+        host_plan = encoded.plan[p0:p1]
+        rel = np.ascontiguousarray(np.where(sec >= 0, sec - p0, -1).astype(np.int64))
+        offs_c = np.ascontiguousarray(offs.astype(np.int64))
+        index = torch.empty(n * _INDEX_BYTES, dtype=torch.uint8, pin_memory=encoded.plan.is_pinned())
+        sizes4 = (C.c_int64 * 4)()
+        _lib.call("ivit_jpeg_workspace", C.c_void_p(host_plan.data_ptr()), p1 - p0, rel.ctypes.data_as(C.c_void_p),
+                  offs_c.ctypes.data_as(C.c_void_p), n, C.c_void_p(index.data_ptr()), sizes4)
+        plan_d = host_plan.to(device, non_blocking=True)
+        index_d = index.to(device, non_blocking=True)
+        errors = torch.empty(n, dtype=torch.int32, device=device)
+        with torch.cuda.device(device):
+            ws = _jpeg_workspace(device, int(sizes4[0]))
+            _lib.call("ivit_jpeg_decode_u8", _lib.ptr(plan_d), _lib.ptr(index_d), n, sizes4[1], sizes4[2], sizes4[3], _lib.ptr(ws),
+                      ws.numel(), _lib.ptr(out), _lib.ptr(errors), _lib.stream_ptr())
+    for b in range(lo, hi):
+        a = encoded.fallback.get(b)
+        if a is not None:
+            o = int(encoded.offsets[b]) - start
+            out[o:o + a.size].copy_(torch.from_numpy(a.reshape(-1)).to(device))
+    if errors is not None:
+        bad = np.nonzero(errors.cpu().numpy())[0]
+        if len(bad):
+            raise _lib.IvitError(f"corrupt JPEG data in image(s) {[int(lo + b) for b in bad]} of the batch")
+    return PackedImages(out, offs.astype(np.int64), sizes)
+
+
+class ImageFolderJPEG(ImageFolderU8):
+    """ImageFolderU8's indexing; items are the files' bytes, and collate -> (EncodedImages, int64 targets): it probes and plans
+    every file and decodes the ones the device does not take with Pillow, in the loader worker."""
+
+    def __getitem__(self, i):
+        path, target = self.samples[i]
+        with open(path, "rb") as f:
+            return f.read(), target
+
+    @staticmethod
+    def collate(batch, pin: bool | None = None):
+        files, targets = zip(*batch)
+        return encode_images(list(files), pin=pin), torch.tensor(targets, dtype=torch.int64)

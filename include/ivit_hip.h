@@ -630,6 +630,34 @@ int ivit_resize_crop_workspace(const int32_t* geom, int batch, int crop, int32_t
 int ivit_resize_crop_bicubic_u8(const uint8_t* src, const int64_t* offsets, const int32_t* geom, int batch, int crop, int ksize_h,
                                 int ksize_v, int rows, void* workspace, int64_t workspace_bytes, uint8_t* out, ivit_stream_t stream);
 
+/* ---- JPEG decoding (the reference's image loader, Image.open(f).convert("RGB")) -------------------------------------------
+ * Baseline JPEG byte for byte as libjpeg-turbo decodes it at its defaults (JDCT_ISLOW, fancy upsampling): sequential Huffman
+ * (SOF0 / SOF1), 8-bit samples, one scan of all components, restart intervals, 1 component (replicated to RGB) or 3 components
+ * libjpeg-turbo takes as YCbCr with sampling 4:4:4, 4:2:2 or 4:2:0.  DESIGN.md §11 "JPEG decoding".  The first four functions
+ * are HOST functions that make no HIP runtime call (loader worker processes may call them).
+ *
+ * ivit_jpeg_probe: info4 (host) = (h, w, components, sampling: 0 gray, 1 4:4:4, 2 4:2:2, 3 4:2:0; -1 when unsupported).
+ * IVIT_ERR_UNSUPPORTED for every other file, ivit_last_error_string() the reason (progressive, CMYK, truncated, ...). */
+int ivit_jpeg_probe(const uint8_t* data, int64_t nbytes, int32_t* info4);
+/* One image's plan section (16-byte aligned, relocatable): quantisation tables in natural order, derived Huffman tables,
+ * component geometry, restart segments, the de-stuffed entropy bytes.  section == NULL: *section_bytes only.  The errors of
+ * ivit_jpeg_probe; IVIT_ERR_INVALID for a capacity below *section_bytes. */
+int ivit_jpeg_plan_image(const uint8_t* data, int64_t nbytes, uint8_t* section, int64_t capacity, int64_t* section_bytes);
+/* Batch index over a plan (host buffer of plan_bytes holding sections): sec_offsets[b] = section of image b, -1 for an image not
+ * decoded on the device; out_offsets[b] = its HWC offset in the output.  index (host, 40 bytes per image) is the operand of
+ * ivit_jpeg_decode_u8 once copied to the device; sizes4 (host) = (workspace bytes, subsequences, blocks, largest pixel count). */
+int ivit_jpeg_workspace(const uint8_t* plan, int64_t plan_bytes, const int64_t* sec_offsets, const int64_t* out_offsets, int batch,
+                        void* index, int64_t* sizes4);
+/* Decodes one image serially with the device's primitives into out (host, h x w x 3).  IVIT_ERR_UNSUPPORTED as the probe;
+ * IVIT_ERR_INVALID for corrupt entropy data (a code no table holds, a segment that ends early) or a short output. */
+int ivit_jpeg_decode_host(const uint8_t* data, int64_t nbytes, uint8_t* out, int64_t out_bytes);
+/* Device decode of a batch: plan (the host plan's bytes, copied), index (ivit_jpeg_workspace's, copied), (nsub, nblocks,
+ * max_pixels) = sizes4[1..3], workspace of sizes4[0] bytes; writes HWC uint8 at out + out_offsets[b] for every device image and
+ * errors[b] (device int32 [batch]) = 0, or non-zero for corrupt entropy data.  Alignment: plan 16, index 8, workspace 256, errors 4
+ * bytes.  Seven launches and two memsets on `stream`. */
+int ivit_jpeg_decode_u8(const uint8_t* plan, const void* index, int batch, int64_t nsub, int64_t nblocks, int64_t max_pixels,
+                        void* workspace, int64_t workspace_bytes, uint8_t* out, int32_t* errors, ivit_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
