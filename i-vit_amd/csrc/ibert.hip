@@ -3,11 +3,11 @@
 //
 // The reference evaluates these operators in float32 tensors holding (mostly) integers.  Each kernel performs the same
 // IEEE float32 operations on the same operands in the same order (build flags -ffp-contract=off -fno-fast-math;
-// division and square root are the correctly rounded forms), so results are bit-identical to the reference wherever
-// the reference itself is deterministic: the three row sums are taken exactly (integers / float64) and rounded once,
-// which equals the reference's float32 reduction whenever that reduction is exact (sum < 2^24; oracle/ibert.py counts
-// the rows where it is not).  Scalar constants (b_int, c_int, x0_int, scales) are computed by the caller in float32
-// exactly as the reference computes them on the host side of every call.
+// division and square root are the correctly rounded forms).  That includes the three row sums: they are taken in the
+// order of torch's CPU reduction (rowsum.h), which decides the result once a sum passes 2^24 (16-bit LayerNorm inputs,
+// a softmax row whose internal QuantAct runs at full range) or a term is not an integer (oracle/ibert.py counts the
+// rows where the order matters).  Scalar constants (b_int, c_int, x0_int, scales) are computed by the caller in
+// float32 exactly as the reference computes them on the host side of every call.
 #include <limits.h>
 #include <type_traits>
 
@@ -89,31 +89,18 @@ __global__ __launch_bounds__(NT) void ibert_softmax_kernel(IbSoftmaxArgs a)
                 a.exp_out[(int64_t)row * a.L + i] = ib_exp_int((float)(kr[i] - kmax), a);
             continue;
         }
-        double sum = 0.0;
-        for (int i = lane; i < a.L; i += 64) {
+        auto ex = [&](int i) {
             const float e = ib_exp_int((float)(kr[i] - kmax), a);
             // internal QuantAct(16): fixedpoint_mul(exp_int, exp_sf, 16) (quant_utils.py:220-245)
             const float z_int = rintf(e / a.exp_sf);
             double q16 = __builtin_rint((double)z_int * a.M);
             q16 = fmin(fmax(q16, -32768.0), 32767.0);
-            const float exp_int = ((float)q16 * a.act_sf) / a.act_sf;        // :309-310
-            sum += (double)exp_int;
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const long long b = __double_as_longlong(sum);
-            const int lo = __shfl_xor((int)(b & 0xffffffffll), o), hi = __shfl_xor((int)(b >> 32), o);
-            sum += __longlong_as_double(((long long)hi << 32) | (unsigned)lo);   // integer-valued terms: exact in any order
-        }
-        const float ssum = (float)sum;                                        // :311
+            return ((float)q16 * a.act_sf) / a.act_sf;                        // :309-310
+        };
+        const float ssum = torch_rowsum(ex, a.L, lane);                       // :311, torch's CPU reduction order
         const float factor = floorf(4294967296.0f / ssum);                    // :313
         for (int i = lane; i < a.L; i += 64) {
-            const float e = ib_exp_int((float)(kr[i] - kmax), a);
-            const float z_int = rintf(e / a.exp_sf);
-            double q16 = __builtin_rint((double)z_int * a.M);
-            q16 = fmin(fmax(q16, -32768.0), 32767.0);
-            const float exp_int = ((float)q16 * a.act_sf) / a.act_sf;
-            const float o = floorf((exp_int * factor) / a.out_div);          // :314
+            const float o = floorf((ex(i) * factor) / a.out_div);            // :314
             a.out[(int64_t)row * a.ldo + i] = (int)o;   // in [0, 2^(output_bit-1)]: the upper end is reachable (a one-hot row)
         }
     }
@@ -137,28 +124,13 @@ __global__ __launch_bounds__(NT) void ibert_layernorm_kernel(IbLnArgs a)
     const int C = a.C;
     for (int row = blockIdx.x * WPB + wave; row < a.rows; row += gridDim.x * WPB) {
         const int32_t* kr = a.k + (int64_t)row * a.ldx;
-        long long sum = 0;
-        for (int c = lane; c < C; c += 64) sum += kr[c];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const int lo = __shfl_xor((int)(sum & 0xffffffffll), o), hi = __shfl_xor((int)(sum >> 32), o);
-            sum += ((long long)hi << 32) | (unsigned)lo;
-        }
-        const float mean_int = rintf((float)sum / (float)C);                  // :127
-        double var = 0.0;
-        for (int c = lane; c < C; c += 64) {
-            const float y = (float)kr[c] - mean_int;                          // :128
-            const float ys = floorf(y / a.shift_pow2);                        // :129
-            const float sq = ys * ys;                                         // :130 float32 square
-            var += (double)sq;                                                // :131 (sum of integer-valued terms)
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const long long b = __double_as_longlong(var);
-            const int lo = __shfl_xor((int)(b & 0xffffffffll), o), hi = __shfl_xor((int)(b >> 32), o);
-            var += __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
-        }
-        const float var_int = (float)var;
+        auto xint = [&](int c) { return (float)kr[c]; };
+        const float mean_int = rintf(torch_rowsum(xint, C, lane) / (float)C); // :127, torch's CPU reduction order
+        auto sq = [&](int c) {
+            const float ys = floorf((xint(c) - mean_int) / a.shift_pow2);     // :128-129
+            return ys * ys;                                                   // :130 float32 square
+        };
+        const float var_int = torch_rowsum(sq, C, lane);                      // :131
         const float std_int = floorf(sqrtf(var_int)) * a.shift_pow2;          // :142
         const float factor = floorf(2147483648.0f / std_int);                 // :143
         float* orow = a.out + (int64_t)row * a.ldo;

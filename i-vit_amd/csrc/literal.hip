@@ -140,7 +140,8 @@ IVIT_EXPORT int ivit_layernorm_f32_f32(const float* x, int64_t ldx, int rows, in
 IVIT_EXPORT int ivit_shiftmax_f32_i8(const float* x, int64_t ldx, int rows, int L, float s, int8_t* out, int64_t ldo,
                                      ivit_stream_t stream)
 {
-    IVIT_REQUIRE(x && out && rows > 0 && L > 0 && ldx >= L && ldo >= L, "ivit_shiftmax_f32_i8: bad operand");
+    // L = 1: the reference's only probability is 2^(output_bit - 1) (1.0), one past what the output type holds
+    IVIT_REQUIRE(x && out && rows > 0 && L > 1 && ldx >= L && ldo >= L, "ivit_shiftmax_f32_i8: bad operand (L must be > 1)");
     IVIT_REQUIRE(s > 0.0f, "ivit_shiftmax_f32_i8: scale must be positive");
     const float x0 = __builtin_floorf((1.0f / s) * -1.0f);      // ivit_modules.py:154
     IVIT_REQUIRE(x0 <= -1.0f && x0 >= -1048576.0f, "ivit_shiftmax_f32_i8: x0=%g out of range", (double)x0);
@@ -152,7 +153,8 @@ IVIT_EXPORT int ivit_shiftmax_f32_i8(const float* x, int64_t ldx, int rows, int 
 IVIT_EXPORT int ivit_shiftmax_f32_i16(const float* x, int64_t ldx, int rows, int L, float s, int output_bit, int16_t* out,
                                       int64_t ldo, ivit_stream_t stream)
 {
-    IVIT_REQUIRE(x && out && rows > 0 && L > 0 && ldx >= L && ldo >= L, "ivit_shiftmax_f32_i16: bad operand");
+    // L = 1: the reference's only probability is 2^(output_bit - 1) (1.0), one past what the output type holds
+    IVIT_REQUIRE(x && out && rows > 0 && L > 1 && ldx >= L && ldo >= L, "ivit_shiftmax_f32_i16: bad operand (L must be > 1)");
     IVIT_REQUIRE(s > 0.0f && output_bit >= 2 && output_bit <= 16, "ivit_shiftmax_f32_i16: scale / output_bit out of range");
     const float x0 = __builtin_floorf((1.0f / s) * -1.0f);      // ivit_modules.py:154
     IVIT_REQUIRE(x0 <= -1.0f && x0 >= -1048576.0f, "ivit_shiftmax_f32_i16: x0=%g out of range", (double)x0);

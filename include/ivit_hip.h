@@ -197,7 +197,8 @@ int ivit_gemm_i8_i32(const int8_t* A, int64_t lda, const int8_t* W, int64_t ldw,
  *   (m_s, e_s): requantiser of q.k^T into the Shiftmax input (8 bit)
  *   s_attn: float32 scale of the Shiftmax input (x0 = floor(-1/s_attn), n = 15)
  *   (m_o, e_o): requantiser of P.v into the 8-bit output.
- * Supported: head_dim 64, 193 <= tokens <= 208 (13 key tiles of 16). */
+ * Supported: head_dim 64, 1 <= tokens <= 208 (13 key tiles of 16; 193 .. 208 take the tuned form in which only the last key tile is
+ * partial, fewer tokens the general one); IVIT_ERR_UNSUPPORTED ("unsupported geometry") otherwise. */
 int ivit_attention_fused_i8(const int8_t* qkv, int8_t* out, int batch, int heads, int tokens, int head_dim,
                             uint32_t m_s, int32_t e_s, float s_attn, uint32_t m_o, int32_t e_o,
                             ivit_stream_t stream);
@@ -314,20 +315,22 @@ int ivit_shiftgelu_lut_i8_ex(const int8_t* x, int64_t ldx, int rows, int L, cons
                              int64_t ldo, int layouts, ivit_stream_t stream);
 
 /* ---- stand-alone Shiftmax (module-level IVITIntSoftmax, ivit_modules.py:164-179) -----------------
- * x [rows, L] int8 with scale s -> out [rows, L] int8 in [0, 127] (scale 2^-7). L <= 1024. */
+ * x [rows, L] int8 with scale s -> out [rows, L] int8 in [0, 127] (scale 2^-7).  L >= 2, no upper limit (a one-column row would
+ * give 128 = 1.0, which int8 cannot hold: refused, as by every form below); x0 = floor(-1 / s) in [-65535, -1] (the row sum is
+ * kept in 64 bits). */
 int ivit_shiftmax_i8(const int8_t* x, int64_t ldx, int rows, int L, float s, int8_t* out, int64_t ldo,
                      ivit_stream_t stream);
 /* module-level LITERAL form, any input scale: x is the float view the reference's module receives (q*s, plus Swin's float
  * mask); every float32 step of ivit_modules.py:150-176 on x/s as written (the reference discards its .to(int32), :166),
- * the row sum in torch's CPU reduction order. */
+ * the row sum in torch's CPU reduction order.  L >= 2 (see above), x0 = floor(-1 / s) in [-1048576, -1]. */
 int ivit_shiftmax_f32_i8(const float* x, int64_t ldx, int rows, int L, float s, int8_t* out, int64_t ldo,
                          ivit_stream_t stream);
 /* the same with a wider output (IVITIntSoftmax(output_bit), the reference's softmax_bw knob, vit_quant.py:184): int16 values in
- * [0, 2^(output_bit-1) - 1], scale 2^-(output_bit-1) */
+ * [0, 2^(output_bit-1) - 1], scale 2^-(output_bit-1); output_bit 2 .. 16, L >= 2 */
 int ivit_shiftmax_f32_i16(const float* x, int64_t ldx, int rows, int L, float s, int output_bit, int16_t* out, int64_t ldo,
                           ivit_stream_t stream);
 /* the same on int32 inputs, |x| < 2^28: Swin adds the shift mask (-100/s, beyond 8 bits) to the scores in front of
- * the softmax (swin_quant.py:151-156) */
+ * the softmax (swin_quant.py:151-156); L and s as for ivit_shiftmax_i8 */
 int ivit_shiftmax_i32_i8(const int32_t* x, int64_t ldx, int rows, int L, float s, int8_t* out, int64_t ldo,
                          ivit_stream_t stream);
 
@@ -532,7 +535,9 @@ int ivit_window_attention_i8_long(const int8_t* qkv, int8_t* out, int64_t ldo, c
  * vit_quant.py:188-190).  Module-level kernels: integer activations in, the module's output out.  The scalar
  * constants are the float32 values the reference computes on the host side of every call (floor(coef / scale) ...);
  * the caller passes them by value.  Each kernel performs the reference's float32 operations in the reference's
- * order (see csrc/ibert.hip).
+ * order (see csrc/ibert.hip), the row sums of the softmax and of the LayerNorm included: they are added in torch's CPU
+ * reduction order (csrc/rowsum.h), which matters as soon as a sum passes 2^24 (16-bit LayerNorm inputs, long near-flat
+ * softmax rows): the integer-input kernels equal the literal forms below on x = k * s for every power-of-two s.
  * ================================================================================================= */
 
 /* IBERTIntGELU.forward (:220-235) on integers k (= x / scaling_factor):
