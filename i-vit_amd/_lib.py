@@ -94,6 +94,7 @@ SIGNATURES = {
     "ivit_ibert_softmax_build_table": [f32, f32, f32, f32, f32, f32, u32, i32, vp, vp],
     "ivit_attention_fused_i8_ibert": [vp, vp, ci, ci, ci, ci, u32, i32, u32, i32, vp, vp, ci, ci, vp],
     "ivit_attention_fused_i8_ibert_wide": [vp, vp, ci, ci, ci, ci, u32, i32, u32, i32, vp, vp, ci, ci, ci, vp],
+    "ivit_attention_fused_i8_ibert_long": [vp, vp, ci, ci, ci, ci, u32, i32, u32, i32, vp, vp, ci, ci, vp],
     "ivit_ibert_layernorm_i8": [vp, i64, ci, ci, f32, vp, vp, f32, vp, vp, vp, i64, ci, vp],
     "ivit_ibert_layernorm_i16_i8": [vp, i64, ci, ci, f32, vp, vp, f32, vp, vp, vp, i64, vp],
     "ivit_ibert_layernorm_i16_i8_ex": [vp, i64, ci, ci, f32, vp, vp, f32, vp, vp, vp, i64, ci, vp],

@@ -616,6 +616,10 @@ int attention_parts(int batch_heads, int tokens, int slots)
 // attention_kernel's chunk swizzle j ^ (d & 15) stays inside the row.  MODE 0: power-of-two input scale, exponent table in LDS;
 // MODE 1: natural scale, the host's table gathered from global memory (band form when band_w > 0, else the [256][256] exp2d):
 // the band rows of every wave do not fit next to K and V^T.
+// MODE 2: the I-BERT softmax (attention_kernel MODE 3 / 4 on this row organisation): the float32 (row max, q) table of
+// ivit_ibert_softmax_build_table gathered from global memory like MODE 1 (band form when band_w > 0), the row sum in float32 in
+// torch's CPU reduction order (rowsum.h), p = floor(fl32(e * floor(2^32 / S)) / 2^25) in [0, 128]; 128 = 127 + 1, the 1 in a
+// second P . V operand that is issued only for a key step that holds one.
 constexpr int LONG_T_MIN = 208, LONG_T_MAX = 1025;
 constexpr int LONG_LUT_BYTES = 2 * 256 * 4;
 
@@ -628,6 +632,7 @@ struct LongArgs {
     int x0;                    // floor(-1/s_attn)
     int out_blocks;            // output in the GEMM block layout (common.h: ivit_block_offset)
     const unsigned* table;     // MODE 1: band[(qmax + 128) * band_w + j] (band_w > 0) or exp2d[(qmax + 128) * 256 + q + 128]
+                               // MODE 2: the same two forms of the I-BERT table, float32 bit patterns
     int band_w;
     int parts;                 // workgroups per (image, head)
     int vt_row;                // bytes per d row of V^T: ceil(key steps / 4) * 256
@@ -638,7 +643,7 @@ struct LongArgs {
 template <int MODE, bool RQ32, int NKT, int NTH>
 __global__ __launch_bounds__(NTH, 1) void attention_long_kernel(LongArgs a)
 {
-    static_assert(!RQ32 || MODE == 0, "RQ32: power-of-two input scale");
+    static_assert(!RQ32 || MODE != 1, "RQ32: a power-of-two score multiplier (Shiftmax: power-of-two input scale)");
     constexpr int NKS = NKT / 4 + 1;          // key steps of 64: NKT full key tiles and the partial one
     constexpr int KOFF = RQ32 ? RQ_OFF : 0;    // RQ32: scores carry the magic constant's exponent bits (low byte = k + 128)
     extern __shared__ __attribute__((aligned(16))) char lsm[];
@@ -752,45 +757,156 @@ __global__ __launch_bounds__(NTH, 1) void attention_long_kernel(LongArgs a)
         const unsigned rep = (unsigned)umax * 0x01010101u;
 
         // exp_int of a key from idx = qmax - k in [0, 255] (and k + 128 = umax - idx)
-        const unsigned* trow = MODE == 1 ? a.table + (W ? umax * W : umax * 257) : nullptr;
+        const unsigned* trow = MODE != 0 ? a.table + (W ? umax * W : umax * 257) : nullptr;
         auto expo = [&](unsigned idx) -> unsigned {
             if constexpr (MODE == 0) return lut[idx];
             else return W ? trow[min((int)idx, W - 1)] : trow[-(int)idx];
         };
 
-        // ---- pass 2: Shiftmax row sum (ivit_modules.py:171), exact, rounded once to float32
-        unsigned long long esum = 0;
-        unsigned sum16 = 0;
+        float factor;
+        if constexpr (MODE == 2) {
+            // ---- pass 2 (I-BERT): S = e.sum() in float32 in torch's order (rowsum.h torch_rowsum; attention_kernel MODE 3 is the same
+            // for T < 208).  V = T >> 3 vectors of 8, I = V >> 2 = T >> 5 interleaved steps of 32 keys: partial j = key % 32 takes keys
+            // j + 32 i, i < I, in groups of 16 steps (each group summed from zero, the group sums added up, the remainder's sum
+            // added last); I <= 32, so the cascade never passes its second level.  With key = 16 kt + 4 g + r a lane owns the whole
+            // sequence of its eight partials (hi = kt & 1, r), step kt >> 1: key tiles 0 .. 2 I - 1.  The at most 31 keys behind them
+            // (key tiles 2 I and 2 I + 1: up to three vectors of 8 that join partials 0 .. 7, then the scalar tail) are exchanged
+            // among the four lanes of the query together with the partials, and every lane finishes the sum alike.  Padding keys
+            // and absent tiles are +0.0f, which changes no sum of non-negative terms: the selections below are by value.
+            int I2 = (T >> 5) << 1;                    // key tiles of the interleaved part; nf is I2 or I2 + 1
+            asm volatile("" : "+s"(I2));               // opaque per query tile, as nf: no hoisted masks
+            float p0[2][4], p1[2][4], t0[4], t1[4];
 #pragma unroll
-        for (int kt = 0; kt < NKT; ++kt) {
-            if (kt < nf) {
-                const unsigned dk = rep - sc[kt];  // bytes: idx of the four keys (every k <= qmax: no borrow)
+            for (int r = 0; r < 4; ++r) p0[0][r] = p0[1][r] = p1[0][r] = p1[1][r] = t0[r] = t1[r] = 0.0f;
 #pragma unroll
-                for (int r = 0; r < 4; ++r) sum16 += expo((dk >> (8 * r)) & 255u);
+            for (int kt = 0; kt < NKT; ++kt) {
+                if (kt < nf) {
+                    const unsigned dk = rep - sc[kt];
+                    float e[4];
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) e[r] = __int_as_float((int)expo((dk >> (8 * r)) & 255u));
+                    if (kt < I2) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            p0[kt & 1][r] += e[r];
+                            if (((kt >> 1) & 15) == 15) {      // a full group of 16 steps ends here
+                                p1[kt & 1][r] += p0[kt & 1][r];
+                                p0[kt & 1][r] = 0.0f;
+                            }
+                        }
+                    } else if (kt == I2) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) t0[r] = e[r];
+                    } else {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) t1[r] = e[r];
+                    }
+                }
             }
-            if ((kt & 3) == 3) {
-                esum += sum16;
-                sum16 = 0;
-            }
-        }
-        if (partial) {
-            const unsigned dk = rep - sl;
+            if (partial) {
+                const unsigned dk = rep - sl;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) sum16 += r < vr ? expo((dk >> (8 * r)) & 255u) : 0u;
+                for (int r = 0; r < 4; ++r) {
+                    const float e = r < vr ? __int_as_float((int)expo((dk >> (8 * r)) & 255u)) : 0.0f;
+                    if (nf == I2) t0[r] = e;
+                    else t1[r] = e;
+                }
+            }
+            // all-gather over the four lanes of a query (attention_kernel MODE 3): out[g'] = the value lane 16 g' + l15 held
+            typedef unsigned v2u __attribute__((ext_vector_type(2)));
+            struct F4 { float g0, g1, g2, g3; };
+            auto gather4 = [&](float x) -> F4 {
+                const unsigned xb = (unsigned)__float_as_int(x);
+                const v2u h = __builtin_amdgcn_permlane32_swap(xb, xb, false, false);       // h.x: rows 0,1,0,1; h.y: rows 2,3,2,3
+                const v2u a01 = __builtin_amdgcn_permlane16_swap(h.x, h.x, false, false);   // .x: row 0 everywhere, .y: row 1
+                const v2u a23 = __builtin_amdgcn_permlane16_swap(h.y, h.y, false, false);   // .x: row 2, .y: row 3
+                return F4{__int_as_float((int)a01.x), __int_as_float((int)a01.y), __int_as_float((int)a23.x), __int_as_float((int)a23.y)};
+            };
+            // partials 0 .. 7 (hi = 0 of the lanes g = 0, 1) take the vectors behind the interleaved part: vector 0 = this lane's own
+            // keys of tile I2, vector 1 = those of lane g + 2, vector 2 = its own of tile I2 + 1; then
+            // v_l = ((P_l + P_{l+8}) + P_{l+16}) + P_{l+24}, l = 4 g + r: P_{l+8}, P_{l+24} are lane g + 2's.  v_permlane32_swap of a
+            // value with itself: .y = the value of lane + 32 in the lanes below 32 (the other lanes' results are not used)
+            auto upper = [&](float x) -> float {
+                const unsigned xb = (unsigned)__float_as_int(x);
+                const v2u h = __builtin_amdgcn_permlane32_swap(xb, xb, false, false);
+                return __int_as_float((int)h.y);
+            };
+            const int nx = (T >> 3) - 2 * I2;          // 0 .. 3 vectors of 8 behind the interleaved part
+            float vl[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                float P = p0[0][r] + p1[0][r];         // the remainder's sum plus the groups' total
+                P += nx > 0 ? t0[r] : 0.0f;
+                P += nx > 1 ? upper(t0[r]) : 0.0f;
+                P += nx > 2 ? t1[r] : 0.0f;
+                vl[r] = ((P + upper(p0[0][r] + p1[0][r])) + (p0[1][r] + p1[1][r])) + upper(p0[1][r] + p1[1][r]);
+            }
+            // scalar tail: keys 8 V .. T - 1 (at most 7, in the half tile behind the last vector) in order, first into the final
+            // accumulator; then v_0 .. v_7
+            float fin = 0.0f;
+            {
+                const bool odd = nx & 1, second = nx >= 2;
+                float lo[4], hi[4];                    // the tail's half tile: lanes g' = 2 (nx & 1) and + 1
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const F4 G = gather4(second ? t1[r] : t0[r]);
+                    lo[r] = odd ? G.g2 : G.g0;
+                    hi[r] = odd ? G.g3 : G.g1;
+                }
+#pragma unroll
+                for (int r = 0; r < 4; ++r) fin += lo[r];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) fin += hi[r];
+                float v0[4], v1[4];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const F4 G = gather4(vl[r]);
+                    v0[r] = G.g0;
+                    v1[r] = G.g1;
+                }
+#pragma unroll
+                for (int r = 0; r < 4; ++r) fin += v0[r];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) fin += v1[r];
+            }
+            factor = floorf(4294967296.0f / fin) * 0.5f;     // ibert_modules.py:313; the half: see prob_word
+        } else {
+            // ---- pass 2: Shiftmax row sum (ivit_modules.py:171), exact, rounded once to float32
+            unsigned long long esum = 0;
+            unsigned sum16 = 0;
+#pragma unroll
+            for (int kt = 0; kt < NKT; ++kt) {
+                if (kt < nf) {
+                    const unsigned dk = rep - sc[kt];  // bytes: idx of the four keys (every k <= qmax: no borrow)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) sum16 += expo((dk >> (8 * r)) & 255u);
+                }
+                if ((kt & 3) == 3) {
+                    esum += sum16;
+                    sum16 = 0;
+                }
+            }
+            if (partial) {
+                const unsigned dk = rep - sl;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) sum16 += r < vr ? expo((dk >> (8 * r)) & 255u) : 0u;
+            }
+            esum = rows_allsum_u64(esum + sum16);
+            float S = (float)esum;                                         // :171
+            S = fminf(S, 2147483648.0f);                                   // :173
+            factor = floorf((1.0f / S) * 2147483648.0f);                   // :174
         }
-        esum = rows_allsum_u64(esum + sum16);
-        float S = (float)esum;                                         // :171
-        S = fminf(S, 2147483648.0f);                                   // :173
-        const float factor = floorf((1.0f / S) * 2147483648.0f);       // :174
 
         // ---- pass 3: p = floor(fl32(e * factor) / 2^24) (:175) as bytes, P . V per key step of 64
+        // I-BERT: p = floor(fl32(e * factor) / 2^25) in [0, 128] (ibert_modules.py:314).  factor / 2 is an exact scaling, so
+        // trunc(e * (factor / 2)) has p in its top byte as well; p = 128 is the byte 0x80, split below.
         auto prob_word = [&](unsigned packed, int nreal) -> unsigned {
             const unsigned dk = rep - packed;
             unsigned p[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const unsigned idx = (dk >> (8 * r)) & 255u;
-                const float ev = MODE == 0 ? lutf[idx] : (float)expo(idx);
+                const float ev = MODE == 0 ? lutf[idx] : MODE == 2 ? __int_as_float((int)expo(idx)) : (float)expo(idx);
                 p[r] = r < nreal ? (unsigned)(ev * factor) : 0u;          // float32 product (:175), < 2^31
             }
             return __builtin_amdgcn_perm(p[1], p[0], 0x0c0c0703u) | __builtin_amdgcn_perm(p[3], p[2], 0x07030c0cu);
@@ -810,11 +926,25 @@ __global__ __launch_bounds__(NTH, 1) void attention_long_kernel(LongArgs a)
                 if (kt < NKT && kt < nf) w = prob_word(sc[kt < NKT ? kt : 0], 4);
                 pk[t] = (int)w;
             }
+            v4i ph = {0, 0, 0, 0};
+            bool hi_pass = false;
+            if constexpr (MODE == 2) {             // a byte 0x80 (p = 128) becomes 127 in pk and 1 in ph
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    const unsigned h128 = ((unsigned)pk[t] >> 7) & 0x01010101u;
+                    pk[t] = (int)((unsigned)pk[t] - h128);     // no borrow: the byte is >= 1
+                    ph[t] = (int)h128;
+                }
+                hi_pass = __builtin_amdgcn_ballot_w64((ph[0] | ph[1] | ph[2] | ph[3]) != 0) != 0;    // wave-uniform, rare
+            }
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt) {
                 const int d = 16 * dt + l15;
                 const v4i vf = *reinterpret_cast<const v4i*>(vt + d * vt_row + (((4 * ks + g) ^ (d & 15)) << 4));
                 o[dt] = __builtin_amdgcn_mfma_i32_16x16x64_i8(vf, pk, o[dt], 0, 0, 0);
+                if constexpr (MODE == 2) {
+                    if (hi_pass) o[dt] = __builtin_amdgcn_mfma_i32_16x16x64_i8(vf, ph, o[dt], 0, 0, 0);
+                }
             }
         }
 
@@ -1077,4 +1207,50 @@ IVIT_EXPORT int ivit_attention_fused_i8_long(const int8_t* qkv, int8_t* out, int
         else hipLaunchKernelGGL((attention_long_kernel<0, false, 64, 768>), grid, blk, lds, st, a);
     }
     IVIT_CHECK_LAUNCH("ivit_attention_fused_i8_long");
+}
+
+IVIT_EXPORT int ivit_attention_fused_i8_ibert_long(const int8_t* qkv, int8_t* out, int batch, int heads, int tokens, int head_dim,
+                                                   uint32_t m_s, int32_t e_s, uint32_t m_o, int32_t e_o, const float* table,
+                                                   const float* band, int band_w, int out_blocks, ivit_stream_t stream)
+{
+    IVIT_REQUIRE(qkv && out && table, "ivit_attention_fused_i8_ibert_long: bad operand (NULL qkv, out or table)");
+    IVIT_REQUIRE(batch > 0 && heads > 0, "ivit_attention_fused_i8_ibert_long: empty batch");
+    if (head_dim != HD || tokens < LONG_T_MIN || tokens > LONG_T_MAX) {
+        ivit_set_error("ivit_attention_fused_i8_ibert_long: unsupported geometry head_dim=%d tokens=%d (need 64, %d..%d)", head_dim,
+                       tokens, LONG_T_MIN, LONG_T_MAX);
+        return IVIT_ERR_UNSUPPORTED;
+    }
+    IVIT_REQUIRE(((uintptr_t)qkv % 16 == 0) && ((uintptr_t)out % 16 == 0) && ((uintptr_t)table % 4 == 0),
+                 "ivit_attention_fused_i8_ibert_long: misaligned operand (16-byte rows)");
+    IVIT_REQUIRE(out_blocks == 0 || (out_blocks == 1 && ((int64_t)batch * tokens + 15) * heads * head_dim < 2147483648ll),
+                 "ivit_attention_fused_i8_ibert_long: bad output layout (block-layout buffers stay below 2 GiB)");
+    IVIT_REQUIRE((int64_t)batch * heads * tokens * head_dim * 3 < ((int64_t)1 << 40), "ivit_attention_fused_i8_ibert_long: qkv too large");
+    IVIT_REQUIRE(band_w == 0 || (band && band_w >= 16 && band_w <= 256 && band_w % 16 == 0 && (uintptr_t)band % 16 == 0),
+                 "ivit_attention_fused_i8_ibert_long: band table must be 16-byte aligned, width a multiple of 16 in [16, 256]");
+    LongArgs a{};
+    a.qkv = qkv; a.out = out; a.batch = batch; a.heads = heads; a.tokens = tokens;
+    a.out_blocks = out_blocks;
+    a.Ms = ivit_dyadic_to_double(m_s, e_s);
+    a.Mo = ivit_dyadic_to_double(m_o, e_o);
+    IVIT_REQUIRE(a.Ms < 2048.0 && a.Mo < 512.0, "ivit_attention_fused_i8_ibert_long: requant multiplier too large");
+    const bool ms_pow2 = m_s != 0 && (m_s & (m_s - 1)) == 0 && a.Ms >= 1e-30;
+    a.Ms32 = (float)a.Ms;
+    a.table = reinterpret_cast<const unsigned*>(band_w ? band : table);
+    a.band_w = band_w;
+    const int nkt = (tokens + 15) >> 4, nks = (nkt + 3) >> 2;
+    a.vt_row = ((nks + 3) >> 2) * 256;
+    const size_t lds = (size_t)LONG_LUT_BYTES + (size_t)nkt * 16 * HD + (size_t)HD * a.vt_row;
+    const bool wide = (tokens >> 4) > 40;
+    const int nth = wide ? 768 : 1024;
+    a.parts = attention_long_parts(batch * heads, nkt, nth / 64);
+    const dim3 grid(batch * heads * a.parts), blk(nth);
+    hipStream_t st = ivit_stream(stream);
+    if (!wide) {
+        if (ms_pow2) hipLaunchKernelGGL((attention_long_kernel<2, true, 40, 1024>), grid, blk, lds, st, a);
+        else hipLaunchKernelGGL((attention_long_kernel<2, false, 40, 1024>), grid, blk, lds, st, a);
+    } else {
+        if (ms_pow2) hipLaunchKernelGGL((attention_long_kernel<2, true, 64, 768>), grid, blk, lds, st, a);
+        else hipLaunchKernelGGL((attention_long_kernel<2, false, 64, 768>), grid, blk, lds, st, a);
+    }
+    IVIT_CHECK_LAUNCH("ivit_attention_fused_i8_ibert_long");
 }

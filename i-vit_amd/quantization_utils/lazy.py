@@ -453,7 +453,7 @@ class Requant(Node):
             return None
         H, hd = mq.shape[1], mq.shape[3]
         C = H * hd
-        if 3 * C != C3 or hd != 64 or N > 207 or any(tuple(m.shape) != (B, H, N, hd) or m.stride() != (N * C3, hd, C3, 1)
+        if 3 * C != C3 or hd != 64 or N > 1025 or any(tuple(m.shape) != (B, H, N, hd) or m.stride() != (N * C3, hd, C3, 1)
                                                      or m.storage_offset() != i * C for i, m in enumerate((mq, mk, mv))):
             return None
         device = self.a8.device
@@ -614,6 +614,13 @@ def _resolve_gelu(node, s_g_out, s_out, device):
     return out
 
 
+def _long_multipliers_ok(a):
+    """the long-row kernels' bounds on the two requantisation multipliers (score < 2048, output < 512).  A model whose attention
+    output range collapsed in calibration (all probabilities 0) breaks the second; such rows ran the literal path before the
+    long-row kernels were routed here and still do"""
+    return a["ms"][0] / 2.0 ** a["ms"][1] < 2048.0 and a["mo"][0] / 2.0 ** a["mo"][1] < 512.0
+
+
 def _resolve_attention(node, s_pv, s_out, device):
     """matmul_2(probs, v) behind qact2, where probs = Shiftmax(qact_attn1(matmul_1(q, k^T) * scale)): the fused attention kernel"""
     P, v = node.inputs
@@ -638,7 +645,7 @@ def _resolve_attention(node, s_pv, s_out, device):
         if q.q8 is None or kT.q8 is None or v.q8 is None:
             return None
         q8, k8, v8 = q.q8, kT.q8.transpose(-2, -1), v.q8
-        if q8.dim() != 4 or q8.shape != k8.shape or q8.shape != v8.shape or q8.shape[-1] != 64 or q8.shape[-2] > 207:
+        if q8.dim() != 4 or q8.shape != k8.shape or q8.shape != v8.shape or q8.shape[-1] != 64 or q8.shape[-2] > 1025:
             return None
         B, H, T, hd = q8.shape
         hm = torch.empty(3, B, H, T, hd, dtype=torch.int8, device=device)
@@ -651,8 +658,9 @@ def _resolve_attention(node, s_pv, s_out, device):
     sm = P.node.mod
     if type(sm).__name__ == "IBERTIntSoftmax":
         # IBERTIntSoftmax (ibert_modules.py:237-319): exp_int after its internal 16-bit QuantAct as a (row max, q) table, row sum in
-        # torch's float32 order inside the kernel (attention.hip MODE 3 / 4); the kernel holds 193 .. 207 tokens
-        if not (192 < T < 208) or sm.output_bit != 8 or sm.act.running_stat:
+        # torch's float32 order inside the kernel (attention.hip MODE 3 / 4); that kernel holds 193 .. 207 tokens, the long-row
+        # form (attention_long_kernel MODE 2) 208 .. 1025
+        if not (192 < T <= 1025) or sm.output_bit != 8 or sm.act.running_stat:
             return None
 
         def build_ib():
@@ -670,9 +678,11 @@ def _resolve_attention(node, s_pv, s_out, device):
             return d
         a = _cache(sc.qact, ("ibattn", _key(s_S, np.asarray(s_at), s_pv, np.asarray(s_out)), id(sm.act.x_min), sm.act.x_min._version,
                              id(sm.act.x_max), sm.act.x_max._version, str(device)), build_ib)
+        if T > 207 and not _long_multipliers_ok(a):
+            return None
         out = torch.empty(B * T, H * hd, dtype=torch.int8, device=device)
-        _lib.call("ivit_attention_fused_i8_ibert", _lib.ptr(hm), _lib.ptr(out), B, H, T, hd, a["ms"][0], a["ms"][1], a["mo"][0], a["mo"][1],
-                  _lib.ptr(a["tab"]), _lib.ptr(a["band"]), a["band_w"], 0, _st())
+        _lib.call("ivit_attention_fused_i8_ibert" if T < 208 else "ivit_attention_fused_i8_ibert_long", _lib.ptr(hm), _lib.ptr(out), B, H, T,
+                  hd, a["ms"][0], a["ms"][1], a["mo"][0], a["mo"][1], _lib.ptr(a["tab"]), _lib.ptr(a["band"]), a["band_w"], 0, _st())
         return out.view(B, T, H, hd).permute(0, 2, 1, 3)
 
     def build():
@@ -687,9 +697,12 @@ def _resolve_attention(node, s_pv, s_out, device):
                 d["exp2d"] = _dev(tab.view(np.int32), device)
         return d
     a = _cache(sc.qact, ("attn", _key(s_S, np.asarray(s_at), s_pv, np.asarray(s_out)), str(device)), build)
+    if T > 207 and not _long_multipliers_ok(a):
+        return None
     out = torch.empty(B * T, H * hd, dtype=torch.int8, device=device)
-    _lib.call("ivit_attention_fused_i8_compat_band", _lib.ptr(hm), _lib.ptr(out), B, H, T, hd, a["ms"][0], a["ms"][1], float(s_at),
-              a["mo"][0], a["mo"][1], _lib.ptr(a["exp2d"]), _lib.ptr(a["band"]), a["band_w"], 0, _st())
+    # up to 207 tokens the short kernel; 208 .. 1025 the long-row one (the same arguments)
+    _lib.call("ivit_attention_fused_i8_compat_band" if T < 208 else "ivit_attention_fused_i8_long", _lib.ptr(hm), _lib.ptr(out), B, H, T, hd,
+              a["ms"][0], a["ms"][1], float(s_at), a["mo"][0], a["mo"][1], _lib.ptr(a["exp2d"]), _lib.ptr(a["band"]), a["band_w"], 0, _st())
     return out.view(B, T, H, hd).permute(0, 2, 1, 3)
 
 

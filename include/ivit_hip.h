@@ -585,6 +585,14 @@ int ivit_ibert_layernorm_f32_f32(const float* x, int64_t ldx, int rows, int C, c
  *    order, factor = floor(2^32 / sum), p = floor(fl(e * factor) / 2^25) in [0, 128] (output_bit 8, scale 2^-7).  tokens 193..207.
  *    band / band_w: the table in the band form of ivit_attention_fused_i8_compat_band (band[(qm + 128) * band_w + j] = entry of
  *    q = qm - j, entry band_w - 1 already the saturated value), staged in LDS per query tile; band_w = 0: gather from `table`.
+ *  - ivit_attention_fused_i8_ibert_long: the same attention on rows of 208..1025 tokens (384 / 16 -> 577, 224 / 8 -> 785,
+ *    512 / 16 -> 1025), the row organisation of ivit_attention_fused_i8_long; 8-bit probabilities only.  The row sum is torch's
+ *    for these lengths: 32 interleaved partials (key % 32) over the first 32 * (tokens >> 5) keys, each summed in groups of 16 steps,
+ *    the up to three 8-key vectors behind them added to partials 0..7, ((P[l] + P[l+8]) + P[l+16]) + P[l+24] for l = 0..7, and the
+ *    final accumulator takes the scalar tail (tokens % 8 keys) first, then those eight sums.  table / band / band_w as above, both
+ *    gathered from global memory (no LDS staging: K and V^T of the head fill it).  Errors as ivit_attention_fused_i8_long:
+ *    IVIT_ERR_UNSUPPORTED ("unsupported geometry") for head_dim != 64 or tokens outside 208..1025; IVIT_ERR_INVALID for a NULL
+ *    qkv / out / table ("bad operand"), misalignment, a bad band, multipliers out of range, a block-layout buffer >= 2 GiB.
  *  - ivit_ibert_layernorm_i8: IBERTIntLayerNorm (:126-153; mean and variance sums in torch's order) + the QuantAct behind it.
  *    bias_int / s_out / (m, e) as for ivit_layernorm_i8; shift_pow2 = 2^shift (the module's overflow buffer). */
 int ivit_ibert_gelu_build_lut(float s, float b_int, float c_int, float shift_int, float s_out, uint32_t m_q, int32_t e_q,
@@ -598,6 +606,9 @@ int ivit_attention_fused_i8_ibert(const int8_t* qkv, int8_t* out, int batch, int
 int ivit_attention_fused_i8_ibert_wide(const int8_t* qkv, int8_t* out, int batch, int heads, int tokens, int head_dim, uint32_t m_s,
                                        int32_t e_s, uint32_t m_o, int32_t e_o, const float* table, const float* band, int band_w,
                                        int softmax_bits, int out_blocks, ivit_stream_t stream);
+int ivit_attention_fused_i8_ibert_long(const int8_t* qkv, int8_t* out, int batch, int heads, int tokens, int head_dim,
+                                       uint32_t m_s, int32_t e_s, uint32_t m_o, int32_t e_o, const float* table,
+                                       const float* band, int band_w, int out_blocks, ivit_stream_t stream);
 int ivit_ibert_layernorm_i8(const int8_t* x, int64_t ldx, int rows, int C, float s_in, const float* bias_int, const float* s_out,
                             float shift_pow2, const uint32_t* m, const int32_t* e, int8_t* out, int64_t ldo, int out_blocks,
                             ivit_stream_t stream);

@@ -6,7 +6,14 @@ from the kernel trace of one run:
     python scripts/time_long_attention.py summary prof/run_results.db
 
 `summary` reads the trace database and prints, per attention kernel form and token count, the dispatch durations and the time
-per score (T is recovered from the launch's LDS size, B from the cases below; the model's launches are the natural-scale form)."""
+per score (T is recovered from the launch's LDS size, B from the cases below; the model's launches are the natural-scale form).
+
+    python scripts/time_long_attention.py --family ibert [kernels] [model]
+
+times the I-BERT family instead: ivit_attention_fused_i8_ibert_long (table and band form) against ivit_attention_fused_i8_long at 577
+and 1025 tokens, batch 64, and the forward of a depth-2 I-BERT model of DeiT-B's geometry (C = 768, 12 heads) at 384 / 16, batch 64,
+through the module path (the fused engine does not take I-BERT models of more than 207 tokens).  Every figure is the median of
+seven event-timed repeats after warm-up, with the smallest and largest repeat."""
 import os
 import sys
 
@@ -48,6 +55,74 @@ def attention(B, T):
                                     int(eo[0]), None, None, 0, 0, st()))
 
 
+def repeats(fn, n, reps=7):
+    """(median, min, max) in us of `reps` event-timed windows of n calls each"""
+    t = sorted(timeit(fn, n) for _ in range(reps))
+    return t[reps // 2], t[0], t[-1]
+
+
+def ibert_tables(s_at=0.25, hi=1.0):
+    """the (row max, q) table of the I-BERT softmax at input scale s_at, internal QuantAct range [0, hi], and its band form"""
+    from ivit_amd.prepare import shiftexp_band
+    from ivit_amd.quantization_utils.ibert_modules import softmax_constants
+    x0i, bi, ci, exp_sf, act_sf, ma, ea = softmax_constants(s_at, 0.0, hi)
+    tab = torch.empty(65536, dtype=torch.float32, device=DEV)
+    _lib.call("ivit_ibert_softmax_build_table", float(s_at), x0i, bi, ci, float(exp_sf), float(act_sf), ma, ea, _lib.ptr(tab), st())
+    band, bw = shiftexp_band(tab.cpu().numpy().view(np.uint32).reshape(256, 256))
+    return tab, (torch.from_numpy(band.view(np.float32)).to(DEV) if bw else None), bw
+
+
+def ibert_attention(B, T):
+    """us per launch (median, min, max) of ivit_attention_fused_i8_long (power-of-two form: exponents from LDS; natural-scale form:
+    gathered from the global band table) and of the I-BERT entry, table and band form, on the same operands"""
+    qkv = torch.from_numpy(np.clip(np.rint(rng.normal(0, 40, size=(3, B, H, T, hd))), -128, 127).astype(np.int8)).to(DEV)
+    out = torch.empty(B * T, H * hd, dtype=torch.int8, device=DEV)
+    ms, es = dyadic(np.float32(2.0 ** -11), np.float32(2.0 ** -2))
+    mo, eo = dyadic(np.float32(2.0 ** -11), np.float32(2.0 ** -3))
+    tab, band, bw = ibert_tables()
+    a = (_lib.ptr(qkv), _lib.ptr(out), B, H, T, hd, int(ms[0]), int(es[0]))
+    from ivit_amd.prepare import shiftexp2d, shiftexp_band
+    nb, nbw = shiftexp_band(shiftexp2d(np.float32(0.0437)))          # I-ViT at a natural scale: the same two gathers per score
+    nband = torch.from_numpy(nb.view(np.int32)).to(DEV)
+    res = {"ivit": repeats(lambda: _lib.call("ivit_attention_fused_i8_long", *a, 0.25, int(mo[0]), int(eo[0]), None, None, 0, 0, st()), 10),
+           "ibert table": repeats(lambda: _lib.call("ivit_attention_fused_i8_ibert_long", *a, int(mo[0]), int(eo[0]), _lib.ptr(tab), None, 0,
+                                                    0, st()), 10)}
+    res[f"ivit band {nbw}"] = repeats(lambda: _lib.call("ivit_attention_fused_i8_long", *a, 0.0437, int(mo[0]), int(eo[0]), None,
+                                                       _lib.ptr(nband), nbw, 0, st()), 10)
+    if bw:
+        res[f"ibert band {bw}"] = repeats(lambda: _lib.call("ivit_attention_fused_i8_ibert_long", *a, int(mo[0]), int(eo[0]), _lib.ptr(tab),
+                                                            _lib.ptr(band), bw, 0, st()), 10)
+    return res
+
+
+def ibert_model():
+    """forward of a frozen depth-2 I-BERT model, C = 768, 12 heads, 384 / 16, batch 64, as the reference calls it (module by module)"""
+    from ivit_amd.quantization_utils import lazy
+    torch.manual_seed(0)
+    model = ivit_amd.VisionTransformer(img_size=384, patch_size=16, embed_dim=768, depth=2, num_heads=12, mlp_ratio=4, qkv_bias=True,
+                                       num_classes=1000, gelu_type="ibert", softmax_type="ibert", layernorm_type="ibert").to(DEV).eval()
+    imgs = torch.from_numpy(np.concatenate([synth.make_images(32, 5 + i) for i in range(2)])).to(DEV)
+    x = torch.nn.functional.interpolate(imgs, size=(384, 384), mode="bilinear", align_corners=False).float().contiguous()
+    with torch.no_grad():
+        for p in model.parameters():
+            if p.dim() > 1:
+                p.mul_(3.0)
+        model(x[:8])
+        ivit_amd.freeze_model(model)
+        assert model.engine_unsupported_reason() is not None
+        names = []
+        orig = _lib.call
+        _lib.call = lambda name, *args: (names.append(name), orig(name, *args))[1]
+        try:
+            model(x)
+        finally:
+            _lib.call = orig
+        med, lo, hi = repeats(lambda: model(x), 3)
+    attn = sorted({n for n in names if "attention" in n or "bgemm" in n or "softmax" in n})
+    print(f"I-BERT C=768 depth 2, 384 px b64, module path: forward {med / 1e3:.2f} ms (min {lo / 1e3:.2f}, max {hi / 1e3:.2f}); "
+          f"{len(names)} launches, attention through {attn}; int8-carrying path {'on' if lazy.ENABLED else 'off'}")
+
+
 CASES = [(256, 197), (64, 209), (64, 577), (64, 785)]
 
 
@@ -71,7 +146,24 @@ def summary(db):
         print(f"{form:52s} T={T} B={B}: {n:3d} dispatches, mean {avg / 1e3:8.1f} us, min {mn / 1e3:8.1f} us, {ps:.3f} ps/score (min)")
 
 
-which = sys.argv[1:] or ["kernels", "model"]
+argv = sys.argv[1:]
+family = "ivit"
+if "--family" in argv:
+    i = argv.index("--family")
+    family = argv[i + 1]
+    del argv[i:i + 2]
+    assert family in ("ivit", "ibert"), family
+which = argv or ["kernels", "model"]
+if family == "ibert":
+    if "kernels" in which:
+        for B, T in [(64, 577), (64, 1025)]:
+            res = ibert_attention(B, T)
+            for k, (med, lo, hi) in res.items():
+                print(f"attention B={B} T={T:4d} {k:14s} {med:8.1f} us (min {lo:.1f}, max {hi:.1f})  {med * 1e6 / (B * H * T * T):.3f} ps/score  "
+                      f"{med / res['ivit'][0]:.2f}x ivit")
+    if "model" in which:
+        ibert_model()
+    sys.exit(0)
 if which[0] == "summary":
     summary(which[1])
     sys.exit(0)
