@@ -2,7 +2,7 @@
 """Headline benchmark: images/s of the integer-only DeiT-B forward (batch 256 per GPU, 224x224
 synthetic images resident in HBM) on N MI355X, one process per GPU.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1: spawns its own N ranks)
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] (N > 1: spawns its own N ranks)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A step = one forward of the whole hot path over one batch: input quantisation + im2col, patch-embed
@@ -11,16 +11,18 @@ fc2 GEMM + residual), final LN, head GEMM, per-class scaling + arg-max; for N > 
 RCCL all-gather of the top-1 indices.  Images are independent, so ranks share nothing else (weak
 scaling: 256 images per GPU).  Prints ONE JSON line on rank 0.
 
-Separate phases, in this order, so that nothing perturbs the number it does not belong to:
+A plain run does what the headline figure needs and no more: set-up, phase 1, the outputs if --dump-outputs is given, the
+JSON line (`roofline` is null, the keys of phases 3 and 4 are absent).  --full adds phases 2 to 4, which cost several times
+what the plain run does.  Separate phases, in this order, so that nothing perturbs the number it does not belong to:
   1. the timed region: W warm-up + K steps, nothing but launches (HIP-graph replay of the forward reading the
      resident image tensor + the all-gather), bracketed by barrier + synchronize;
-  2. an instrumented pass (untimed): a few eager forwards with device-scope HIP events around every launch of the
+  2. --full: an instrumented pass (untimed): a few eager forwards with device-scope HIP events around every launch of the
      dominant kernel -> `roofline`;
-  3. extra keys of the same line, each with its own barrier-bracketed timed loop (never part of `value`):
+  3. --full: extra keys of the same line, each with its own barrier-bracketed timed loop (never part of `value`):
      `natural_scales` -- the headline workload with activation ranges AS CALIBRATED (the regime of a real checkpoint), rank 0;
      `config4` -- BASELINE.json's config 4: ViT-B, GLOBAL batch 1024 split over the ranks with parallel.shard_bounds (strong
      scaling: 128 per rank at N = 8), all-gather of the top-1 per step;
-  4. rank 0, N = 1 only: the CPU oracle on a bounded sample -> `cpu_baseline`.
+  4. --full, rank 0, N = 1 only: the CPU oracle on a bounded sample -> `cpu_baseline`.
 --dump-outputs DIR: right after phase 1, rank 0 writes what the last timed step returned (dump_outputs()).  Images and
 weights are seeded, so two builds run with the same arguments can be compared array for array.
 Each rank pins its host threads to the NUMA node of its GPU before anything touches the GPU (no exec, no re-launch).
@@ -52,10 +54,14 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the natural_scales and config4 keys (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything that is not the headline figure: the instrumented pass "
+                         "(`roofline`), the natural_scales and config4 keys, the CPU baseline.  Off by default: a plain run sets "
+                         "up, warms up, times the steps and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline key")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the natural_scales and config4 keys (profiling runs)")
     ap.add_argument("--no-graph", action="store_true", help="eager launches in the timed region instead of HIP-graph replay")
-    ap.add_argument("--probe-forwards", type=int, default=3, help="forwards of the instrumented pass (0 = skip)")
+    ap.add_argument("--probe-forwards", type=int, default=3, help="with --full: forwards of the instrumented pass (0 = skip)")
     ap.add_argument("--operators", choices=("ivit", "ibert"), default="ivit",
                     help="operator family of GELU / Softmax / LayerNorm: 'ivit' (the headline, BASELINE.json) or 'ibert' (the fork's "
                          "default family; ranges calibrated on the spot, as calibrated; no cpu_baseline)")
@@ -426,10 +432,10 @@ def worker(args):
         dump_outputs(args.dump_outputs, top1, keep.last)
         progress(f"outputs of the last timed step written to {args.dump_outputs}")
 
-    # ---- phase 2: dominant-kernel duration, outside the timed region
-    progress(f"timed region done: {dt / args.steps * 1e3:.3f} ms per step; probing the dominant kernel")
+    # ---- phase 2 (--full): dominant-kernel duration, outside the timed region
+    progress(f"timed region done: {dt / args.steps * 1e3:.3f} ms per step" + ("; probing the dominant kernel" if args.full else ""))
     roof = None
-    if rank == 0 and not stub and args.probe_forwards > 0:
+    if args.full and rank == 0 and not stub and args.probe_forwards > 0:
         from ivit_amd.hiptime import KernelProbe
         eng.forward(images)
         torch.cuda.synchronize()
@@ -465,11 +471,11 @@ def worker(args):
     if grouped:
         dist.barrier()
 
-    # ---- phase 3: extra keys, each with its own timed loop (never part of `value`)
+    # ---- phase 3 (--full): extra keys, each with its own timed loop (never part of `value`)
     headline = args.operators == "ivit" and args.bitwidth == 8 and not args.natural_scales
     natural = None
     config4 = None
-    if stub and not args.no_extras:
+    if args.full and stub and not args.no_extras:
         # launcher self-test: the config-4 code path (uneven shards, padded all-gather, timing) with the stub engine over gloo
         n4 = 33
         lo, hi = shard_bounds(n4, world, rank)
@@ -480,7 +486,7 @@ def worker(args):
         dt4 = timed_steps(lambda: dp4.step(images4), 3, 1, sync, grouped, dev)
         config4 = {"workload": f"launcher self-test: {n4} images over {world} rank(s)", "ms_per_step": round(dt4 / 3 * 1e3, 3),
                    "images_per_s": round(n4 * 3 / dt4, 1), "steps": 3, "per_rank_batch": hi - lo, "scaling": "strong"}
-    if headline and not stub and not args.no_extras:
+    if args.full and headline and not stub and not args.no_extras:
         del dp
         eng = None
         torch.cuda.empty_cache()
@@ -515,7 +521,7 @@ def worker(args):
         value = world * batch * args.steps / dt
         out = {"metric": "images/sec DeiT-B INT8 @batch256, 1→8 MI355X; % INT8 MFMA peak",
                "value": round(value, 1), "unit": "images/s", "n_gpus": world, "steps": args.steps,
-               "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True,
+               "warmup": args.warmup, "full": args.full, "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True,
                "scaling": "weak", "vs_baseline": None, "dtype": "int8", "data": "synthetic",
                "config": {"workload": "DeiT-B INT8 integer-only forward, batch 256 per GPU, 224x224" if not stub
                           else "launcher self-test (stub engine, CPU, gloo)",
@@ -532,7 +538,7 @@ def worker(args):
             out["natural_scales"] = natural
         if config4 is not None:
             out["config4"] = config4
-        if world == 1 and not stub and not args.no_cpu_baseline and args.operators == "ivit" and args.bitwidth == 8:
+        if args.full and world == 1 and not stub and not args.no_cpu_baseline and args.operators == "ivit" and args.bitwidth == 8:
             out["cpu_baseline"] = cpu_baseline(fs, ranges, cfg)
         print(json.dumps(out, ensure_ascii=False), flush=True)
     if grouped:

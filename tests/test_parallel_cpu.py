@@ -118,16 +118,37 @@ def test_bench_launcher_spawns_ranks_gloo_stub():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR")}
     env["IVIT_BENCH_STUB"] = "1"
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full"],
                        env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["steps"] == 3 and d["config"]["global_batch"] == 16 and d["value"] > 0
-    # the config-4 path of the same command: 33 images over 2 ranks (17 + 16), one padded all-gather per step
+    # the config-4 path of the same command (--full): 33 images over 2 ranks (17 + 16), one padded all-gather per step
     assert d["config4"]["per_rank_batch"] == 17 and d["config4"]["scaling"] == "strong" and d["config4"]["images_per_s"] > 0
     assert "host_affinity" in d
+
+
+def test_bench_plain_run_has_headline_only_stub():
+    """without --full the line carries the headline figure and none of the keys that take runs of their own; --full is
+    handed on to the ranks the launcher starts (the test above) and says so in the line"""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR")}
+    env["IVIT_BENCH_STUB"] = "1"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1"],
+                       env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in d
+    assert d["full"] is False and d["steps"] == 3 and d["value"] > 0 and d["roofline"] is None
+    assert not {"config4", "natural_scales", "cpu_baseline"} & set(d)
 
 
 def test_bench_launcher_propagates_failure():
