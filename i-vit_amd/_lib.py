@@ -31,6 +31,7 @@ SIGNATURES = {
     "ivit_attention_fused_i8_compat_band": [vp, vp, ci, ci, ci, ci, u32, i32, f32, u32, i32, vp, vp, ci, ci, vp],
     "ivit_attention_fused_i8_wide": [vp, vp, ci, ci, ci, ci, u32, i32, f32, u32, i32, vp, vp, ci, ci, ci, vp],
     "ivit_attention_fused_i8_long": [vp, vp, ci, ci, ci, ci, u32, i32, f32, u32, i32, vp, vp, ci, ci, vp],
+    "ivit_attention_cls_i8": [vp, vp, vp, vp, i64, ci, ci, ci, ci, u32, i32, f32, u32, i32, vp, vp, ci, vp],
     "ivit_shiftgelu_build_lut_ex": [f32, u32, i32, vp, vp, vp],
     "ivit_shiftgelu_lut_i8_ex": [vp, i64, ci, ci, vp, vp, i64, ci, vp],
     "ivit_pack_weight_frags_i8": [vp, i64, ci, ci, vp, vp],
@@ -40,6 +41,7 @@ SIGNATURES = {
     "ivit_gemm_i8_requant_ex": [vp, i64, vp, i64, vp, vp, vp, vp, i64, ci, ci, ci, ci, vp],
     "ivit_gemm_i8_requant_residual_ex": [vp, i64, vp, i64, vp, vp, vp, vp, i64, u32, i32, u32, i32, vp, i64, ci, ci, ci, ci, vp],
     "ivit_gemm_i8_requant_qkv_ex": [vp, i64, vp, i64, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp],
+    "ivit_gemm_i8_requant_qkv_planes_ex": [vp, i64, vp, i64, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp],
     "ivit_gemm_i8_requant_residual_i16": [vp, i64, vp, i64, vp, vp, vp, vp, i64, u32, i32, u32, i32, vp, i64, ci, ci, ci, vp],
     "ivit_gemm_i8_requant_lut_ex": [vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, ci, ci, ci, ci, vp],
     "ivit_gemm_i8_requant_i16": [vp, i64, vp, i64, vp, vp, vp, vp, i64, ci, ci, ci, vp],

@@ -991,7 +991,169 @@ int attention_long_parts(int batch_heads, int nqt, int nw)
     return best;
 }
 
+// ---- one query per (image, head): the class row of the last block, the only row of its output the classifier reads
+// (vit_quant.py:302-304).  attention_kernel's arithmetic for that query -- score requantisation, row maximum over the T real keys,
+// exponent from the 256-entry table (MODE 0) or from the host's band / [256][256] table (MODE 1 / 2), exact u32 sum, float32
+// factor, p = floor(fl32(e * factor) / 2^24), P.V in int32, output requantisation -- without MFMAs: the work is reading 25 KB of
+// K and V once.  One wave per (image, head).  K and V are walked as 16-byte chunks, chunk c = lane + 64 i (c >> 2 = key, c & 3 =
+// quarter of the head dimension): every load instruction reads 1 KB contiguous, and the 2 x 13 loads are written ahead of the
+// first use of any of them so that the compiler may have them all in flight (it keeps all 104 dwords in registers: no scratch,
+// csrc/check_resources.py; their order in the instruction stream is the compiler's).
+// A lane's four v_dot4 give a quarter of a score, two quad DPP adds leave the score of key (lane >> 2) + 16 i in all four lanes of
+// the quad -- the same lanes that hold that key's V chunks, so the probability needs no exchange: 16 int32 accumulators per lane
+// (d = 16 (lane & 3) + j), reduced over the 16 lanes of equal lane & 3 at the end.
+// The scores are requantised in float64 for every multiplier: for a power-of-two one that is what attention_kernel's float32 form
+// computes (its proof is that equality), and 13 v_fma_f64 per lane are not what this kernel waits for.
+struct ClsArgs {
+    const int8_t *k, *v, *q;     // k, v: [batch][heads][tokens][64] planes; q: [batch][heads * 64]
+    int8_t* out;                 // [batch][ldo], heads * 64 bytes per row
+    int64_t ldo;
+    int pairs, heads, tokens;    // pairs = batch * heads
+    double Ms, Mo;
+    int x0;
+    const unsigned* exp2d;       // as AttnArgs
+    const unsigned* band;
+    int band_w;
+};
+
+constexpr int CLS_NCH = (KP * 4 + 63) / 64;      // 13 chunks of K (and of V) per lane
+// CLS_OCC: the occupancy the kernel is compiled for.  3 workgroups per CU is what one round of DeiT-B at batch 256 needs (3072
+// pairs = 768 workgroups on 256 CUs) and leaves 168 VGPRs; the compiler uses 118-124, so 4 are resident where a launch has them.
+// Measured at that shape, kernel trace of the bench command, 100 replays each: compiled for 2 / 3 / 4 the kernel takes
+// 13.92 / 13.88 / 13.85 us (116-118, 118-124, 122-126 VGPRs: four fit per CU each time), spread of one build 13.5-14.6 us.  The
+// value does not matter there; 3 stays because it is the round the launcher counts on.
+constexpr int CLS_WAVES = NT / 64, CLS_OCC = 3;
+
+template <int MODE>
+__global__ __launch_bounds__(NT, CLS_OCC) void attention_cls_kernel(ClsArgs a)
+{
+    __shared__ unsigned lut[256];
+    const int tid = threadIdx.x, lane = tid & 63;
+    if constexpr (MODE == 0) {
+        lut[tid] = shiftexp_int(-tid, a.x0, 15);
+        __syncthreads();
+    }
+    const int bh = blockIdx.x * CLS_WAVES + (tid >> 6);
+    if (bh >= a.pairs) return;
+    const int b = bh / a.heads, hh = bh - b * a.heads;
+    const int T = a.tokens, c4 = lane & 3;
+    const int8_t* kg = a.k + (int64_t)bh * T * HD;
+    const int8_t* vg = a.v + (int64_t)bh * T * HD;
+
+    v4i kc[CLS_NCH], vc[CLS_NCH];
+#pragma unroll
+    for (int i = 0; i < CLS_NCH; ++i)
+        kc[i] = *reinterpret_cast<const v4i*>(kg + 16 * min(lane + 64 * i, 4 * T - 1));       // unconditional, clamped
+    const v4i qf = *reinterpret_cast<const v4i*>(a.q + ((int64_t)b * a.heads + hh) * HD + 16 * c4);
+#pragma unroll
+    for (int i = 0; i < CLS_NCH; ++i)
+        vc[i] = *reinterpret_cast<const v4i*>(vg + 16 * min(lane + 64 * i, 4 * T - 1));
+
+    // ---- scores, negated like attention_kernel's: nk = -k = RNE(S * -Ms) in [-127, 128]; keys >= T carry the sentinel
+    int nk[CLS_NCH];
+    int nmin = 1000;
+#pragma unroll
+    for (int i = 0; i < CLS_NCH; ++i) {
+        int s = 0;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) s = __builtin_amdgcn_sdot4(kc[i][w], qf[w], s, false);
+        s += (int)IVIT_DPP_U32(s, 0xB1);
+        s += (int)IVIT_DPP_U32(s, 0x4E);
+        const int n = clamp_i32(requant_exact(s, -a.Ms), -127, 128);       // |S| <= 2^20: exact float64 product
+        nk[i] = ((lane >> 2) + 16 * i < T) ? n : 1000;
+        nmin = min(nmin, nk[i]);
+    }
+    const int rmax = wave_allmax_i32(-nmin);
+
+    // ---- Shiftmax (ivit_modules.py:164-175)
+    unsigned ev[CLS_NCH], esum = 0;
+#pragma unroll
+    for (int i = 0; i < CLS_NCH; ++i) {
+        const int idx = min(nk[i] + rmax, 255);       // max - k in [0, 255] for a real key
+        unsigned e;
+        if constexpr (MODE == 0) e = lut[idx];
+        else if constexpr (MODE == 1) e = a.band[(size_t)(rmax + 128) * a.band_w + min(idx, a.band_w - 1)];
+        else e = a.exp2d[((rmax + 128) << 8) + 128 - min(nk[i], 128)];      // entry of q = -nk
+        e = nk[i] == 1000 ? 0u : e;
+        ev[i] = e;
+        esum += c4 == 0 ? e : 0u;                     // the four lanes of a quad hold the same key
+    }
+    esum = (unsigned)lanes_allsum_i32<64>((int)esum);
+    float S = (float)esum;                                         // exp_int.sum (:171)
+    S = fminf(S, 2147483648.0f);                                   // clamp_max_(2**31-1) in float32 (:173)
+    const float factor = floorf((1.0f / S) * 2147483648.0f);       // (:174)
+
+    // ---- O = P . V over this lane's chunks
+    int acc[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) acc[j] = 0;
+#pragma unroll
+    for (int i = 0; i < CLS_NCH; ++i) {
+        const int p = (int)((unsigned)((float)ev[i] * factor) >> 24);      // float32 product (:175), <= 2^31; 0 for a padding key
+#pragma unroll
+        for (int j = 0; j < 16; ++j) acc[j] += p * (int)(int8_t)((unsigned)vc[i][j >> 2] >> (8 * (j & 3)));
+    }
+    // sum over the 16 lanes of equal lane & 3: rotations by 4 and 8 inside a row of 16, then the rows
+    int ob[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        typedef unsigned v2u __attribute__((ext_vector_type(2)));
+        int t = acc[j];
+        t += (int)IVIT_DPP_U32(t, 0x124);      // row_ror:4
+        t += (int)IVIT_DPP_U32(t, 0x128);      // row_ror:8
+        const v2u r = __builtin_amdgcn_permlane16_swap((unsigned)t, (unsigned)t, false, false);
+        t = (int)(r.x + r.y);
+        const v2u q = __builtin_amdgcn_permlane32_swap((unsigned)t, (unsigned)t, false, false);
+        t = (int)(q.x + q.y);
+        ob[j] = clamp_i32(requant_exact(t, a.Mo), -128, 127);      // |O| <= 208 * 128 * 128 < 2^22
+    }
+    if (lane < 4) {
+        v4i chunk;
+#pragma unroll
+        for (int w = 0; w < 4; ++w)
+            chunk[w] = (int)(__builtin_amdgcn_perm((unsigned)ob[4 * w + 1], (unsigned)ob[4 * w], 0x0c0c0400u) |
+                             __builtin_amdgcn_perm((unsigned)ob[4 * w + 3], (unsigned)ob[4 * w + 2], 0x04000c0cu));
+        *reinterpret_cast<v4i*>(a.out + (int64_t)b * a.ldo + hh * HD + 16 * c4) = chunk;
+    }
+}
+
 }  // namespace
+
+IVIT_EXPORT int ivit_attention_cls_i8(const int8_t* k, const int8_t* v, const int8_t* q, int8_t* out, int64_t ldo, int batch,
+                                      int heads, int tokens, int head_dim, uint32_t m_s, int32_t e_s, float s_attn, uint32_t m_o,
+                                      int32_t e_o, const uint32_t* exp2d, const uint32_t* band, int band_w, ivit_stream_t stream)
+{
+    IVIT_REQUIRE(k && v && q && out, "ivit_attention_cls_i8: NULL operand");
+    IVIT_REQUIRE(batch > 0 && heads > 0 && (int64_t)batch * heads < 2147483648ll, "ivit_attention_cls_i8: empty batch");
+    if (head_dim != HD || tokens < 1 || tokens > KP) {
+        ivit_set_error("ivit_attention_cls_i8: unsupported geometry head_dim=%d tokens=%d (need 64, 1..208)", head_dim, tokens);
+        return IVIT_ERR_UNSUPPORTED;
+    }
+    IVIT_REQUIRE(((uintptr_t)k % 16 == 0) && ((uintptr_t)v % 16 == 0) && ((uintptr_t)q % 16 == 0) && ((uintptr_t)out % 16 == 0) &&
+                 ldo >= (int64_t)heads * head_dim && ldo % 16 == 0, "ivit_attention_cls_i8: misaligned operand (16-byte rows)");
+    IVIT_REQUIRE(s_attn > 0.0f, "ivit_attention_cls_i8: scale must be positive");
+    IVIT_REQUIRE((uintptr_t)exp2d % 4 == 0, "ivit_attention_cls_i8: misaligned exponent table");
+    IVIT_REQUIRE(band_w == 0 || (band && band_w >= 16 && band_w <= 256 && band_w % 16 == 0 && (uintptr_t)band % 16 == 0),
+                 "ivit_attention_cls_i8: band table must be 16-byte aligned, width a multiple of 16 in [16, 256]");
+    ClsArgs a{};
+    a.k = k; a.v = v; a.q = q; a.out = out; a.ldo = ldo;
+    a.pairs = batch * heads; a.heads = heads; a.tokens = tokens;
+    a.exp2d = exp2d; a.band = band; a.band_w = band_w;
+    a.Ms = ivit_dyadic_to_double(m_s, e_s);
+    a.Mo = ivit_dyadic_to_double(m_o, e_o);
+    IVIT_REQUIRE(a.Ms < 2048.0 && a.Mo < 512.0, "ivit_attention_cls_i8: requant multiplier too large");
+    const float x0f = __builtin_floorf((1.0f / s_attn) * -1.0f);  // ivit_modules.py:154
+    IVIT_REQUIRE(x0f <= -1.0f && x0f >= -4096.0f, "ivit_attention_cls_i8: x0=%g outside [-4096,-1]", (double)x0f);
+    a.x0 = (int)x0f;
+    IVIT_REQUIRE((double)tokens * (double)(-a.x0) * 32768.0 < 4294967296.0,
+                 "ivit_attention_cls_i8: Shiftmax row sum could overflow 32 bits (x0=%d)", a.x0);
+    const dim3 grid((a.pairs + CLS_WAVES - 1) / CLS_WAVES), blk(NT);
+    hipStream_t st = ivit_stream(stream);
+    if (band_w) hipLaunchKernelGGL(attention_cls_kernel<1>, grid, blk, 0, st, a);
+    else if (exp2d) hipLaunchKernelGGL(attention_cls_kernel<2>, grid, blk, 0, st, a);
+    else hipLaunchKernelGGL(attention_cls_kernel<0>, grid, blk, 0, st, a);
+    IVIT_CHECK_LAUNCH("ivit_attention_cls_i8");
+}
 
 IVIT_EXPORT int ivit_attention_fused_i8_ex(const int8_t* qkv, int8_t* out, int batch, int heads, int tokens,
                                         int head_dim, uint32_t m_s, int32_t e_s, float s_attn, uint32_t m_o,

@@ -51,6 +51,10 @@ def occupancy_rules(path, what):
             # NTH / 256 waves per SIMD; the packed score rows must stay in registers: no scratch
             m = re.search(r"attention_long_kernelILi(\d+)ELb([01])ELi(\d+)ELi(\d+)E", name)
             occ, need_no_scratch = int(m.group(4)) // 256, True
+        elif what == "attention" and "attention_cls_kernel" in name:
+            # attention_cls_kernel<MODE>: CLS_OCC = 3 workgroups of four waves per CU (its __launch_bounds__; DeiT-B at batch 256
+            # is then one round); the 26 K / V chunks a lane requests up front must stay in registers: no scratch
+            occ, need_no_scratch = 3, True
         elif what == "attention":
             m = re.search(r"attention_kernelILi(\d+)ELi(\d+)ELi(\d+)ELb([01])E", name)
             if not m:

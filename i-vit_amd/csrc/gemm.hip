@@ -1105,7 +1105,7 @@ __global__ __launch_bounds__(SK_NT, 2) void gemm_i8_skinny_kernel(GemmArgs g)
 #include "gemm_wp.h"
 
 template <int EPI>
-int launch_gemm(GemmArgs& g, const char* name, ivit_stream_t stream)
+int launch_gemm(GemmArgs& g, const char* name, ivit_stream_t stream, int qkv_planes = 3)   // EPI_QKV: N = qkv_planes * heads * head_dim
 {
     IVIT_REQUIRE(g.A && g.W && g.out, "%s: NULL operand", name);
     IVIT_REQUIRE(g.M > 0 && g.N > 0 && g.K > 0, "%s: empty problem M=%d N=%d K=%d", name, g.M, g.N, g.K);
@@ -1141,8 +1141,8 @@ int launch_gemm(GemmArgs& g, const char* name, ivit_stream_t stream)
                      "%s: bad head geometry tokens=%d heads=%d head_dim=%d", name, g.tokens, g.heads, g.head_dim);
         IVIT_REQUIRE((int64_t)g.M * g.N < 2147483648ll, "%s: q/k/v output of %lld bytes exceeds the 2 GiB the 32-bit head-major offsets cover",
                      name, (long long)g.M * g.N);
-        IVIT_REQUIRE(g.N == 3 * g.heads * g.head_dim && g.M % g.tokens == 0,
-                     "%s: N=%d != 3*heads*head_dim or M=%d %% tokens=%d != 0", name, g.N, g.M, g.tokens);
+        IVIT_REQUIRE(g.N == qkv_planes * g.heads * g.head_dim && g.M % g.tokens == 0,
+                     "%s: N=%d != %d*heads*head_dim or M=%d %% tokens=%d != 0", name, g.N, qkv_planes, g.M, g.tokens);
     }
     g.flags = g_debug_flags & (31 | 128 | 256 | 512);
     g.flags2 = g_debug_flags2;
@@ -1545,6 +1545,29 @@ IVIT_EXPORT int ivit_gemm_i8_requant_qkv_ex(const int8_t* A, int64_t lda, const 
     g.a_blocks = layouts & 1; g.w_blocks = (layouts >> 1) & 1; g.w_frags = (layouts & 16) ? 2 : ((layouts >> 3) & 1);
     IVIT_REQUIRE((layouts & ~27) == 0 && (layouts & 24) != 24, "ivit_gemm_i8_requant_qkv_ex: unknown layout bits");
     return launch_gemm<EPI_QKV>(g, "ivit_gemm_i8_requant_qkv_ex", stream);
+}
+
+// A subset of the three planes.  Every kernel form addresses channel n of row (b, tok) at
+//   ((which * B + b) * heads + h) * tokens + tok) * head_dim + d,   which = n / (heads * head_dim)
+// relative to g.out, with B = M / tokens: a plane of the full [3][B][H][T][d] buffer is B * heads * tokens * head_dim = M * heads *
+// head_dim bytes whatever N is, so `which + plane0` is the same kernels on an output pointer advanced by plane0 planes.  No kernel
+// reads the plane count; launch_gemm holds N against it.
+IVIT_EXPORT int ivit_gemm_i8_requant_qkv_planes_ex(const int8_t* A, int64_t lda, const int8_t* W, int64_t ldw,
+                                                   const int32_t* bias, const uint32_t* m, const int32_t* e, int8_t* qkv,
+                                                   int tokens, int heads, int head_dim, int plane0, int nplanes, int M, int N,
+                                                   int K, int layouts, ivit_stream_t stream)
+{
+    IVIT_REQUIRE(plane0 >= 0 && nplanes >= 1 && plane0 + nplanes <= 3, "ivit_gemm_i8_requant_qkv_planes_ex: planes %d .. %d outside q, k, v",
+                 plane0, plane0 + nplanes - 1);
+    IVIT_REQUIRE(qkv && M > 0 && heads > 0 && head_dim > 0 && (int64_t)3 * M * heads * head_dim < 2147483648ll,
+                 "ivit_gemm_i8_requant_qkv_planes_ex: NULL output or a q/k/v buffer beyond 2 GiB");
+    GemmArgs g{};
+    g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.bias = bias; g.m = m; g.e = e;
+    g.out = qkv + (int64_t)plane0 * M * heads * head_dim; g.ldo = 0; g.M = M; g.N = N; g.K = K;
+    g.tokens = tokens; g.heads = heads; g.head_dim = head_dim;
+    g.a_blocks = layouts & 1; g.w_blocks = (layouts >> 1) & 1; g.w_frags = (layouts & 16) ? 2 : ((layouts >> 3) & 1);
+    IVIT_REQUIRE((layouts & ~27) == 0 && (layouts & 24) != 24, "ivit_gemm_i8_requant_qkv_planes_ex: unknown layout bits");
+    return launch_gemm<EPI_QKV>(g, "ivit_gemm_i8_requant_qkv_planes_ex", stream, nplanes);
 }
 
 IVIT_EXPORT int ivit_gemm_i8_requant_qkv(const int8_t* A, int64_t lda, const int8_t* W, int64_t ldw,

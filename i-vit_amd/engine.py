@@ -13,6 +13,10 @@ Dataflow = the reference's frozen-model forward
          -> ShiftGELU table gather (+requant) -> GEMM fc2 (+requant +residual requant) }
     --LN(cls rows)+requant--> GEMM head --> INT32 logits --scale+argmax--> top-1
 
+The logits read token 0 of the last block's output alone, and every operator of a block but attention's K and V works row by
+row: with cls_tail (the graph replays, forward(images, cls_tail=True)) the last block computes K and V for every token and
+everything else for the B class rows only (_cls_block) -- the same logits, bit for bit.
+
 There is no fallback path: a missing libivit_hip.so or a kernel error raises.
 """
 from __future__ import annotations
@@ -225,6 +229,8 @@ class IntViTEngine(EngineBase):
         for lin in lins:
             narrow = id(lin) not in wide
             lin["Wf"], lin["Wf_bit"] = frag_copy(lin["W"], self._stream(), order16=self.frags16 and narrow, narrow=narrow)
+        for b in self.blocks:
+            b["q"] = dict(b["qkv"], N=C)      # the first C rows of attn.qkv, row-major: Q of the class rows (_cls_block)
         self.weight_frags = True      # False: block-layout weights through the LDS-DMA kernel (A/B timing)
         self.block_operands = True    # False: row-major activations / weights everywhere (tests, A/B timing)
         # which producers write their output (a GEMM A operand) in the block layout.  Measured per producer / consumer pair
@@ -251,6 +257,10 @@ class IntViTEngine(EngineBase):
             qkv=torch.empty(3 * M * C, **i8), ao=torch.empty(M16, C, **i8),
             f1=torch.empty(M16, 4 * C, **i8), g=torch.empty(M16, 4 * C, **i8), untile=torch.empty(M, 4 * C, **i8),
             cls=torch.empty(B, C, **i8),
+            # the last block on the class rows (_cls_block): LayerNorm output, query, attention output, the stream after the
+            # projection and after fc2, fc1 / GELU
+            c_h=torch.empty(B, C, **i8), c_q=torch.empty(B, C, **i8), c_ao=torch.empty(B, C, **i8), c_x=torch.empty(B, C, **i8),
+            c_y=torch.empty(B, C, **i8), c_f1=torch.empty(B, 4 * C, **i8),
             **({} if self.stream_bits == 8 else dict(
                 pe16=torch.empty(B * self.NP, C, dtype=torch.int16, device=self.dev),
                 x16=torch.empty(M, C, dtype=torch.int16, device=self.dev), y16=torch.empty(M, C, dtype=torch.int16, device=self.dev),
@@ -262,13 +272,17 @@ class IntViTEngine(EngineBase):
             topk=torch.empty(B * TOPK_MAX, dtype=torch.int32, device=self.dev),
         )
 
-    def _w(self, lin, blocks):
-        """(weight pointer, layout bit) -- the block-layout copy when the call goes to the persistent kernel"""
+    def _w(self, lin, blocks, row0=0):
+        """(weight pointer, layout bit) -- the block-layout copy when the call goes to the persistent kernel.  row0: the weight
+        from that output channel on (a multiple of 64: the same byte offset row0 * K in all three layouts)"""
         if blocks and self.weight_frags and lin.get("Wf") is not None:
-            return _lib.ptr(lin["Wf"]), lin["Wf_bit"]
-        if blocks and lin["Wb"] is not None:
-            return _lib.ptr(lin["Wb"]), 2
-        return _lib.ptr(lin["W"]), 0
+            W, bit = lin["Wf"], lin["Wf_bit"]
+        elif blocks and lin["Wb"] is not None:
+            W, bit = lin["Wb"], 2
+        else:
+            W, bit = lin["W"], 0
+        assert row0 % 64 == 0
+        return _lib.ptr(W.view(-1)[row0 * lin["K"]:] if row0 else W), bit
 
     def _compact(self, on=True):
         """Alias workspaces whose lifetimes do not overlap, so that one layer touches ~230 MB instead of ~430 MB at batch
@@ -291,10 +305,12 @@ class IntViTEngine(EngineBase):
                   _lib.ptr(lin["m"]), _lib.ptr(lin["e"]), _lib.ptr(out), ldo, M, lin["N"], lin["K"],
                   lay | int(a_blocks) | (4 if out_blocks else 0), st)
 
-    def _gemm_res(self, A, lda, lin, res, me4, out, M, st, blocks=False, a_blocks=False):
+    def _gemm_res(self, A, lda, lin, res, me4, out, M, st, blocks=False, a_blocks=False, ldr=None):
         """projection / fc2 + its QuantAct + the block's residual QuantAct (in place when out is res).  On the 16-bit stream the
-        GEMM requantises to 16 bits per channel; without fuse_res16 that GEMM and the two-operand residual kernel are separate"""
+        GEMM requantises to 16 bits per channel; without fuse_res16 that GEMM and the two-operand residual kernel are separate.
+        ldr: row stride of `res` on the 8-bit stream (default C)"""
         C, r = self.C, me4
+        ldr = C if ldr is None else ldr
         if self.stream_bits == 16 and not self.fuse_res16:
             k16 = self.ws["k16"]
             _lib.call("ivit_gemm_i8_requant_i16", _lib.ptr(A), lda, _lib.ptr(lin["W"]), lin["K"], _lib.ptr(lin["b"]),
@@ -309,7 +325,7 @@ class IntViTEngine(EngineBase):
         if self.stream_bits == 8:
             w, lay = self._w(lin, blocks)
             _lib.call("ivit_gemm_i8_requant_residual_ex", _lib.ptr(A), lda, w, lin["K"],
-                      _lib.ptr(lin["b"]), _lib.ptr(lin["m"]), _lib.ptr(lin["e"]), _lib.ptr(res), C,
+                      _lib.ptr(lin["b"]), _lib.ptr(lin["m"]), _lib.ptr(lin["e"]), _lib.ptr(res), ldr,
                       r[0], r[1], r[2], r[3], _lib.ptr(out), C, M, lin["N"], lin["K"], lay | int(a_blocks), st)
         else:
             # the weights-in-registers form where it applies, else the 128 x 128-tile kernel (any shape; no block layouts)
@@ -331,14 +347,53 @@ class IntViTEngine(EngineBase):
             _lib.call("ivit_quantize_patchify_f32_i8", _lib.ptr(images), _lib.ptr(ws["a0"]), B, 3, self.IMG, self.P, self.inv_s0, st)
 
     # ------------------------------------------------------------------ forward
-    def forward(self, images: torch.Tensor, taps: dict | None = None):
+    def forward(self, images: torch.Tensor, taps: dict | None = None, cls_tail: bool = False):
         """images: float32 [B,3,224,224] on the engine's device.  Returns (logits_int32 [B,classes],
         logits_f32 [B,classes], top1 int32 [B]) -- views of the engine's workspace, valid until the
-        next call.  `taps` (debug/tests) receives clones of intermediate int8 tensors."""
-        return self._forward(images, taps)
+        next call.  `taps` (debug/tests) receives clones of intermediate int8 tensors.
+        cls_tail: the last block on the class rows only, as the graph replays run it (tests, profiling); the same results."""
+        return self._forward(images, taps, cls_tail=cls_tail)
 
-    def _forward(self, images: torch.Tensor, taps: dict | None = None, topk=None):
+    @property
+    def cls_tail_ok(self):
+        """the engines whose last block can run on the class rows alone (_cls_block)"""
+        return self.family == "ivit" and self.stream_bits == 8 and self.T <= 207
+
+    # what forward_graph / forward_topk_graph capture (graph.py): the pruned last block wherever it exists
+    def _graph_forward(self, images):
+        return self._forward(images, cls_tail=self.cls_tail_ok)
+
+    def _graph_forward_topk(self, images, k, targets, hits):
+        return self._forward(images, None, (k, targets, hits), cls_tail=self.cls_tail_ok)
+
+    def _cls_block(self, blk, x, B, st, a_ln, blk_l):
+        """The last block when only token 0 of its output is read (vit_quant.py:302-304): K and V for every token, everything
+        else -- Q, attention, projection, MLP, both residual QuantActs -- for the B class rows (row b * T of x).  Every operator
+        on that path is row-wise except attention, which ivit_attention_cls_i8 runs for the one query: the rows computed are
+        bit for bit those of the full block.  -> the block's output for the class rows, dense [B, C]"""
+        C, H, hd, T = self.C, self.H, self.hd, self.T
+        M, ws, q = B * T, self.ws, blk["qkv"]
+        layernorm(blk["ln1"], x, C, M, C, ws["h"], C, st, blocks=a_ln)
+        kvw, kvlay = self._w(q, blk_l, row0=C)
+        _lib.call("ivit_gemm_i8_requant_qkv_planes_ex", _lib.ptr(ws["h"]), C, kvw, q["K"], _lib.ptr(q["b"][C:]),
+                  _lib.ptr(q["m"][C:]), _lib.ptr(q["e"][C:]), _lib.ptr(ws["qkv"]), T, H, hd, 1, 2, M, 2 * C, C, kvlay | int(a_ln), st)
+        layernorm(blk["ln1"], x, T * C, B, C, ws["c_h"], C, st, blocks=False)
+        self._gemm(ws["c_h"], C, blk["q"], ws["c_q"], C, B, st)
+        a = blk["attn"]
+        _lib.call("ivit_attention_cls_i8", _lib.ptr(ws["qkv"][M * C:]), _lib.ptr(ws["qkv"][2 * M * C:]), _lib.ptr(ws["c_q"]),
+                  _lib.ptr(ws["c_ao"]), C, B, H, T, hd, a["ms"][0], a["ms"][1], a["s_attn"], a["mo"][0], a["mo"][1],
+                  _lib.ptr(a["exp2d"]), _lib.ptr(a["band"]), a["band_w"], st)
+        self._gemm_res(ws["c_ao"], C, blk["proj"], x, blk["res1"], ws["c_x"], B, st, ldr=T * C)
+        layernorm(blk["ln2"], ws["c_x"], C, B, C, ws["c_h"], C, st, blocks=False)
+        self._gemm(ws["c_h"], C, blk["fc1"], ws["c_f1"], 4 * C, B, st)
+        _lib.call("ivit_shiftgelu_lut_i8_ex", _lib.ptr(ws["c_f1"]), 4 * C, B, 4 * C, _lib.ptr(blk["gelu_lut"]),
+                  _lib.ptr(ws["c_f1"]), 4 * C, 0, st)
+        self._gemm_res(ws["c_f1"], 4 * C, blk["fc2"], ws["c_x"], blk["res2"], ws["c_y"], B, st)
+        return ws["c_y"]
+
+    def _forward(self, images: torch.Tensor, taps: dict | None = None, topk=None, cls_tail: bool = False):
         """forward; topk = (k, targets, hits): the classifier launch is the top-k selection (forward_topk).
+        cls_tail: the last block through _cls_block (cls_tail_ok engines, no taps).
         stream_bits = 16: the same dataflow with an int16 residual stream.  The patch GEMM, the embedding assembly and the
         projection / fc2 GEMMs write 16 bits (csrc/swin.hip's kernels), LayerNorm reads int16 rows, attention is the "wide"
         form (softmax_bits); qkv / fc1 / GELU are the int8 kernels unchanged, every operand in row-major order."""
@@ -348,6 +403,8 @@ class IntViTEngine(EngineBase):
         wide = self.stream_bits == 16
         if wide and taps is not None:
             raise NotImplementedError("taps are not recorded on the 16-bit-stream path")
+        if cls_tail and (taps is not None or not self.cls_tail_ok):
+            raise ValueError("cls_tail: I-ViT operators, 8-bit stream, at most 207 tokens, no taps")
         C, H, hd, T = self.C, self.H, self.hd, self.T
         M = B * T
         ws = self.ws
@@ -380,8 +437,12 @@ class IntViTEngine(EngineBase):
         _lib.call("ivit_embed_assemble_i16" if wide else "ivit_embed_assemble_i8", _lib.ptr(ws["pe16" if wide else "pe"]),
                   _lib.ptr(self.pos_add), _lib.ptr(self.cls_row), self.embed_me[0], self.embed_me[1], _lib.ptr(x), B, T, C, st)
         tap("qact1", x, (B, T, C))
+        y_cls = None
         for i, blk in enumerate(self.blocks):
             p = f"blocks.{i}."
+            if cls_tail and i == self.D - 1:
+                y_cls = self._cls_block(blk, x, B, st, a_ln, blk_l)
+                break
             layernorm(blk["ln1"], x, C, M, C, ws["h"], C, st, blocks=a_ln)
             tap(p + "qact1", ws["h"], (B, T, C), a_ln)
             q = blk["qkv"]
@@ -431,6 +492,8 @@ class IntViTEngine(EngineBase):
         if wide:
             ws["cls16"][:B].copy_(x.view(-1, T, C)[:B, 0])
             layernorm(self.ln_f, ws["cls16"], C, B, C, ws["cls"], C, st, blocks=False)
+        elif y_cls is not None:
+            layernorm(self.ln_f, y_cls, C, B, C, ws["cls"], C, st, blocks=False)
         else:
             layernorm(self.ln_f, x, T * C, B, C, ws["cls"], C, st, blocks=False)
         tap("qact2", ws["cls"], (B, C))

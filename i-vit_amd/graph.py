@@ -17,7 +17,7 @@ class GraphReplay:
         """resident=False: `images` is copied into the graph's own input buffer before every replay.
         resident=True: the graph reads `images` itself (the caller keeps that tensor alive and refills it in place,
         e.g. a loader's device-side staging buffer) -- no copy per step."""
-        return self._replay(images, resident, (), lambda x, warm: self.forward(x))
+        return self._replay(images, resident, (), lambda x, warm: self._graph_forward(x))
 
     def forward_topk_graph(self, images: torch.Tensor, k: int = 5, targets=None, hits=None, resident: bool = False):
         """forward_topk as a graph replay.  `targets` / `hits` are read and accumulated in place like a resident image tensor:
@@ -25,8 +25,16 @@ class GraphReplay:
         `hits` when it likes.  The warm-up forward outside the capture runs without them, so `hits` only counts replays."""
         check_request(self.num_classes, images.shape[0], self.dev, k, targets, hits)
         tag = ("topk", k, 0 if targets is None else targets.data_ptr(), 0 if hits is None else hits.data_ptr())
-        return self._replay(images, resident, tag, lambda x, warm: self.forward_topk(x, k, None if warm else targets,
-                                                                                    None if warm else hits))
+        return self._replay(images, resident, tag, lambda x, warm: self._graph_forward_topk(x, k, None if warm else targets,
+                                                                                           None if warm else hits))
+
+    # what the replays capture: an engine may override these with a forward that issues other launches for the same results
+    # (IntViTEngine: the last block on the class rows)
+    def _graph_forward(self, images):
+        return self.forward(images)
+
+    def _graph_forward_topk(self, images, k, targets, hits):
+        return self.forward_topk(images, k, targets, hits)
 
     def _replay(self, images, resident, tag, run):
         """run(x, warm): the forward to capture (warm=True: the uncaptured warm-up call); tag: extends the cache key"""

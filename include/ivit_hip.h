@@ -164,6 +164,14 @@ int ivit_gemm_i8_requant_qkv(const int8_t* A, int64_t lda, const int8_t* W, int6
 int ivit_gemm_i8_requant_qkv_ex(const int8_t* A, int64_t lda, const int8_t* W, int64_t ldw, const int32_t* bias,
                                 const uint32_t* m, const int32_t* e, int8_t* qkv, int tokens, int heads,
                                 int head_dim, int M, int N, int K, int layouts, ivit_stream_t stream);
+/* the same for `nplanes` consecutive planes of q / k / v starting at `plane0` (0 <= plane0, 1 <= nplanes, plane0 + nplanes <= 3):
+ * N = nplanes * heads * head_dim.  W, bias, m, e point at the FIRST SELECTED channel (plane0 * heads * head_dim rows into the
+ * weight: the same byte offset in every weight layout when heads * head_dim % 64 == 0); `qkv` is the whole [3][B][H][T][d]
+ * buffer, of which only the selected planes are written. */
+int ivit_gemm_i8_requant_qkv_planes_ex(const int8_t* A, int64_t lda, const int8_t* W, int64_t ldw, const int32_t* bias,
+                                       const uint32_t* m, const int32_t* e, int8_t* qkv, int tokens, int heads,
+                                       int head_dim, int plane0, int nplanes, int M, int N, int K, int layouts,
+                                       ivit_stream_t stream);
 
 /* 16-bit per-channel QuantAct of the accumulators (Swin attn.proj + attn.qact4, swin_quant.py:164-166):
  *   out[t][n] = clamp16(RNE(acc * m[n] / 2^e[n])),  out int16 [M, N] (ldo in elements), N % 4 == 0, ldo % 4 == 0.
@@ -242,6 +250,18 @@ int ivit_attention_fused_i8_wide(const int8_t* qkv, int8_t* out, int batch, int 
 int ivit_attention_fused_i8_long(const int8_t* qkv, int8_t* out, int batch, int heads, int tokens, int head_dim, uint32_t m_s,
                                  int32_t e_s, float s_attn, uint32_t m_o, int32_t e_o, const uint32_t* exp2d,
                                  const uint32_t* band, int band_w, int out_blocks, ivit_stream_t stream);
+
+/* One query per (image, head): the attention of a block whose output is read for one token only (the class token of the last
+ * block, vit_quant.py:302-304).  The arithmetic of ivit_attention_fused_i8_compat_band for that query, bit for bit.
+ *   k, v  [batch][heads][tokens][64] int8: planes 1 and 2 of the head-major qkv buffer
+ *   q     [batch][heads * 64] int8, row-major, dense: the query of each image
+ *   out   [batch][ldo] int8, heads * 64 bytes per row, column h * 64 + d
+ * Requantisers and tables as ivit_attention_fused_i8_compat_band (band_w > 0: the band table; else exp2d non-NULL: the full
+ * table; both absent: power-of-two scale).  Preconditions: head_dim 64, 1 <= tokens <= 208 (IVIT_ERR_UNSUPPORTED otherwise);
+ * operands 16-byte aligned, ldo >= heads * 64 and a multiple of 16; x0 and the multipliers in the ranges stated there. */
+int ivit_attention_cls_i8(const int8_t* k, const int8_t* v, const int8_t* q, int8_t* out, int64_t ldo, int batch, int heads,
+                          int tokens, int head_dim, uint32_t m_s, int32_t e_s, float s_attn, uint32_t m_o, int32_t e_o,
+                          const uint32_t* exp2d, const uint32_t* band, int band_w, ivit_stream_t stream);
 
 /* ---- I-LayerNorm + the QuantAct behind it ---------------------------------------------------
  * IVITIntLayerNorm.forward (ivit_modules.py:30-65) then QuantAct (fixedpoint_mul).
