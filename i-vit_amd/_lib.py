@@ -86,6 +86,7 @@ SIGNATURES = {
     "ivit_layernorm_i16_i8": [vp, ci, ci, vp, vp, vp, vp, vp, i64, ci, ci, ci, ci, vp],
     "ivit_layernorm_i16_i8_compat": [vp, ci, ci, f32, ci, vp, vp, vp, vp, vp, i64, ci, ci, ci, ci, vp],
     "ivit_patch_merge_i16": [vp, vp, ci, ci, ci, ci, vp],
+    "ivit_window_rows": [vp, vp, ci, ci, ci, i64, ci, ci, ci, vp],
     "ivit_avgpool_requant_i8": [vp, vp, ci, ci, ci, u32, i32, vp],
     "ivit_avgpool_requant_i8_literal": [vp, vp, ci, ci, ci, f32, u32, i32, vp],
     # I-BERT operator family (include/ivit_hip.h, last section)

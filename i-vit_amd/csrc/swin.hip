@@ -706,6 +706,24 @@ __global__ __launch_bounds__(NT) void patch_merge_kernel(const int16_t* x, int16
 }
 
 // ------------------------------------------------------------------------------------------------
+// Window partition + cyclic shift (or their inverse) of whole rows, any element type: a gather of 16-byte chunks.  Consecutive
+// lanes walk the chunks of one destination row, then the next row: 16-byte loads and stores on both sides.  No LDS.
+//   inverse == 0: dst row R (window order) = src row win_row_inv(R);   inverse == 1: dst row r (image order) = src row win_row(r)
+// ------------------------------------------------------------------------------------------------
+constexpr int WINDOW_ROWS_MAX_GRID = 2048;   // 8 workgroups per CU on 256 CUs; larger tensors take further trips of the loop
+
+__global__ __launch_bounds__(NT) void window_rows_kernel(const v4i* src, v4i* dst, int64_t rows, int chunks, WinMap map, int inverse)
+{
+    const int64_t total = rows * chunks;
+    for (int64_t q = (int64_t)blockIdx.x * NT + threadIdx.x; q < total; q += (int64_t)gridDim.x * NT) {
+        const int64_t R = q / chunks;
+        const int c = (int)(q - R * chunks);
+        const int64_t r = inverse ? win_row(map, R) : win_row_inv(map, R);
+        dst[q] = src[r * chunks + c];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Token average pooling + QuantAct (swin_quant.py:554-555): z = round(fl32(sum_t k[t][c] / T)), requant -> int8
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(NT) void avgpool_kernel(const int8_t* x, int8_t* out, int B, int T, int C, double Mq)
@@ -1405,6 +1423,29 @@ IVIT_EXPORT int ivit_patch_merge_i16(const int16_t* x, int16_t* out, int batch, 
     IVIT_CHECK_LAUNCH("ivit_patch_merge_i16");
 }
 
+IVIT_EXPORT int ivit_window_rows(const void* src, void* dst, int batch, int H, int W, int64_t row_bytes, int ws, int shift,
+                                 int inverse, ivit_stream_t stream)
+{
+    IVIT_REQUIRE(src && dst, "ivit_window_rows: NULL operand");
+    IVIT_REQUIRE(((uintptr_t)src % 16 == 0) && ((uintptr_t)dst % 16 == 0), "ivit_window_rows: misaligned operand (16 bytes)");
+    IVIT_REQUIRE(batch > 0 && H > 0 && W > 0 && (int64_t)H * W <= (1 << 30), "ivit_window_rows: bad shape");
+    IVIT_REQUIRE(row_bytes > 0 && row_bytes % 16 == 0 && row_bytes <= (1 << 20),
+                 "ivit_window_rows: row_bytes must be a positive multiple of 16");
+    IVIT_REQUIRE(ws > 0 && H % ws == 0 && W % ws == 0, "ivit_window_rows: the window does not divide the map");
+    IVIT_REQUIRE(shift >= 0 && shift < ws, "ivit_window_rows: shift outside [0, ws)");
+    IVIT_REQUIRE(inverse == 0 || inverse == 1, "ivit_window_rows: inverse must be 0 or 1");
+    const int64_t rows = (int64_t)batch * H * W;
+    const int64_t bytes = rows * row_bytes;
+    const uintptr_t s = (uintptr_t)src, d = (uintptr_t)dst;
+    IVIT_REQUIRE(s + (uintptr_t)bytes <= d || d + (uintptr_t)bytes <= s, "ivit_window_rows: src and dst overlap (not an in-place pass)");
+    const int chunks = (int)(row_bytes / 16);
+    const int64_t blocks = (rows * chunks + NT - 1) / NT;
+    const int grid = (int)(blocks > WINDOW_ROWS_MAX_GRID ? WINDOW_ROWS_MAX_GRID : blocks);
+    hipLaunchKernelGGL(window_rows_kernel, dim3(grid), dim3(NT), 0, ivit_stream(stream), reinterpret_cast<const v4i*>(src),
+                       reinterpret_cast<v4i*>(dst), rows, chunks, WinMap{H, W, ws, shift}, inverse);
+    IVIT_CHECK_LAUNCH("ivit_window_rows");
+}
+
 IVIT_EXPORT int ivit_avgpool_requant_i8(const int8_t* x, int8_t* out, int batch, int tokens, int C, uint32_t m, int32_t e,
                                         ivit_stream_t stream)
 {
@@ -1480,10 +1521,15 @@ static int window_attention_launch(const int8_t* qkv, int8_t* out, int64_t ldo, 
     IVIT_REQUIRE((double)tokens * (double)(-a.x0) * 32768.0 < 4294967296.0,
                  "ivit_window_attention_i8: Shiftmax row sum could overflow 32 bits (x0=%d)", a.x0);
     a.ksat = 255;
+    bool saturates = false;
     for (int i = 0; i < 256; ++i) {
         const int d = -i;
-        if (d + (d >> 1) - (d >> 4) <= 15 * a.x0) { a.ksat = i; break; }
+        if (d + (d >> 1) - (d >> 4) <= 15 * a.x0) { a.ksat = i; saturates = true; break; }
     }
+    // the short kernel's integer form gives a score under the shift mask the table's last entry: the saturated value only if the
+    // table gets there within its 256 distances (x0 >= -24); the literal form (phi tables) is exact at any scale
+    IVIT_REQUIRE(long_rows || saturates || !mask_region || phi || band,
+                 "ivit_window_attention_i8: x0=%d: the integer form cannot place masked scores (use the phi tables)", a.x0);
     if (a.band1) {      // one row for every maximum: the distance table of the power-of-two form, with the host's values
         a.ksat = band_w - 1;
         a.mask_value = -1024;       // a masked score lands beyond the last (saturated) entry whatever the maximum

@@ -31,7 +31,8 @@ class IVITIntLayerNorm(nn.LayerNorm):
     def forward(self, x, scaling_factor=None):
         if isinstance(x, lazy.QT):
             s_in = lazy.host_of(scaling_factor)
-            if x.q8 is not None and s_in is not None and s_in.size == 1:
+            outer = lazy.ln_outer(x.fl)
+            if lazy.int_width(x) is not None and outer is not None and s_in is not None and s_in.size == 1:
                 def build():
                     lp = LayerNormParams(self.weight.detach().cpu().numpy(), self.bias.detach().cpu().numpy(), f32(1.0))
                     self.bias_integer = _dev_table(lp.bias_int, x.device)       # :59
@@ -39,7 +40,9 @@ class IVITIntLayerNorm(nn.LayerNorm):
                     self.norm_scaling_factor = s.as_subclass(torch.Tensor)      # :64
                     return s
                 s_ln = lazy._cache(self, ("s_ln", self.weight._version, self.bias._version, str(x.device)), build)
-                return lazy.pending("ln", self, x.shape, x.device, (x,), (scaling_factor,), s_ln)
+                # the result keeps the transposed layout of an outer-order input, as the elementwise chain of :79-80 does
+                return lazy.pending("ln", self, x.shape, x.device, (x,), (scaling_factor,), s_ln,
+                                    fl=torch.empty_like(x.fl) if outer else None)
             x = x.to_float()
         return self._slow(x, scaling_factor)
 
@@ -138,7 +141,9 @@ class IVITIntSoftmax(nn.Module):
 
     def forward(self, x, scaling_factor):
         if isinstance(x, lazy.QT):
-            if isinstance(x.node, lazy.Scores) and not x.views and self.output_bit == 8 and scaling_factor is x.node.s_out_qs:
+            if (self.output_bit == 8 and scaling_factor is getattr(x.node, "s_out_qs", None) and x.dim() == 4
+                    and (isinstance(x.node, (lazy.Scores, lazy.Biased)) and not x.views
+                         or isinstance(x.node, lazy.Masked) and len(x.views) == 1)):
                 s = lazy._cache(self, ("s_out", str(x.device)), lambda: lazy.QS.make(f32(1 / 2 ** (self.output_bit - 1)), x.device))  # :176
                 self.act_scaling_factor = s.as_subclass(torch.Tensor)
                 return lazy.QT.wrap(x.shape, x.device, node=lazy.Probs(x, self)), s

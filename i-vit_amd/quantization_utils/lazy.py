@@ -1,27 +1,38 @@
-"""The frozen module-by-module path without float round trips: int8-carrying tensors and fusion at the QuantAct.
+"""The frozen module-by-module path without float round trips: integer-carrying tensors and fusion at the QuantAct.
 
-The reference's model files (/root/reference/models/vit_quant.py:61-90, 142-155, 285-312) call QuantLinear, QuantAct,
-IVITIntLayerNorm, ... one by one and move float32 `value = integer * scale` tensors between them.  Executed literally that is
-a float -> integer conversion, an integer kernel and an integer -> float conversion per module, plus host read-backs of every
-scale: 250 ms for a DeiT-B batch of 256 that the fused engine does in 6.5 ms.  This module keeps the calls and removes the
-round trips, for a FROZEN model (every QuantAct fixed):
+The reference's model files (/root/reference/models/vit_quant.py:61-90, 142-155, 285-312; swin_quant.py:121-169, 251-301, 328-349,
+539-564) call QuantLinear, QuantAct, IVITIntLayerNorm, ... one by one and move float32 `value = integer * scale` tensors between
+them.  Executed literally that is a float -> integer conversion, an integer kernel and an integer -> float conversion per module,
+plus host read-backs of every scale: 250 ms for a DeiT-B batch of 256 that the fused engine does in 6.5 ms.  This module keeps the
+calls and removes the round trips, for a FROZEN model (every QuantAct fixed):
 
-  * a frozen 8-bit QuantAct returns a `QT` -- a torch.Tensor subclass with the float tensor's shape / dtype / device but an
-    **int8 payload** (no float storage) -- and a `QS` scale tensor that carries its value on the host as well;
+  * a frozen QuantAct returns a `QT` -- a torch.Tensor subclass with the float tensor's shape / dtype / device but an **integer
+    payload** (no float storage): int8 (`q8`) behind an 8-bit QuantAct, int16 (`q16`) behind a 16-bit one in the Swin patterns
+    below, `q` for either -- and a `QS` scale tensor that carries its value on the host as well;
   * a module whose input is a QT does not compute: it returns a QT holding a **pending node** (linear, conv, layer norm, GELU,
-    the matmul -> scale -> QuantAct -> softmax -> matmul chain of attention);
-  * the shape operations the model files apply in between (reshape, permute, transpose, indexing, unbind, flatten, eval-mode
-    dropout, `* scalar`) act on the payload, or are recorded on the pending node;
-  * the NEXT QuantAct launches ONE fused integer kernel for the node (GEMM + requantisation, LayerNorm + requantisation, GELU
-    table, fused attention, residual add) -- the kernels of the fused engine -- and returns a QT again;
-  * anything else that touches a QT (an unexpected torch function, a hook, the caller reading the logits) materialises the
-    float tensor the reference would have produced, through the module's ordinary path, and continues from there.
+    the matmul -> scale -> QuantAct -> softmax -> matmul chain of attention, with Swin's bias QuantAct and `+ mask` in it);
+  * the shape operations the model files apply in between (reshape, permute, transpose, roll, flatten, contiguous) are recorded
+    on the payload, or on the pending node, and not executed; indexing, unbind, eval-mode dropout and `* scalar` act on the payload;
+  * the next consumer of a payload composes the recorded operations into ONE row permutation (replayed once per shape and
+    sequence on an int32 row-index tensor on the host): Swin's window partition / cyclic shift and their inverse become one
+    `ivit_window_rows` launch, any other row permutation one index_select, anything else the torch operations themselves;
+  * the NEXT QuantAct launches ONE fused integer kernel for the node (GEMM + requantisation to 8 or 16 bits, LayerNorm on the
+    8- or 16-bit stream + requantisation, GELU table, fused (window) attention, residual add, residual GEMM) -- the kernels of
+    the fused engines -- and returns a QT again;
+  * a QT also carries `fl`, the strides the reference's FLOAT tensor would have (each recorded view replayed on a meta tensor; a
+    QuantAct / LayerNorm result keeps its input's layout as the elementwise chain does): IVITIntLayerNorm's float32 mean runs in
+    the outer order over the transposed view behind Swin's patch embedding (ivit_modules.py:56-61), and every LayerNorm of Swin's
+    first stage inherits that layout.  A layout that is neither contiguous nor that transpose materialises;
+  * anything else that touches a QT (an unexpected torch function, a hook, the float pooling of Swin's tail, the caller reading
+    the logits) materialises the float tensor the reference would have produced, through the module's ordinary path, with the
+    reference's strides, and continues from there.
 
-Every (m, e) pair, table and integer weight is derived on the host from host-side scales and cached per module, so after the
-first (warm-up) forward a frozen forward reads nothing back from the device: it runs under
-`torch.cuda.set_sync_debug_mode("error")` and can be captured into a HIP graph (tests/test_gpu_modules.py).
-Covers the I-ViT and the I-BERT operator families (ivit_modules.py, ibert_modules.py) at 8-bit QuantAct widths; other configurations
-(16-bit widths, mixed families, Swin) take the ordinary module path through the materialisation rule above.
+Every (m, e) pair, table, row map, bias / mask table and integer weight is derived on the host from host-side scales and cached
+per module, so after the first (warm-up) forward a frozen forward reads nothing back from the device: it runs under
+`torch.cuda.set_sync_debug_mode("error")` and can be captured into a HIP graph (tests/test_gpu_modules.py, test_gpu_swin_lazy.py).
+Covers the I-ViT and the I-BERT operator families (ivit_modules.py, ibert_modules.py) at 8-bit QuantAct widths and Swin with the
+I-ViT operators (8-bit QuantActs, 16-bit residual stream); other configurations (ViT's 16-bit widths, mixed families) take the
+ordinary module path through the materialisation rule above.
 """
 from __future__ import annotations
 
@@ -34,7 +45,7 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ..engine_common import frag_copy
+from ..engine_common import frag_copy, layernorm, ln_spec
 from ..prepare import (LayerNormParams, LinearParams, dyadic, f32, phi_tables, quant_sym, shiftexp2d, shiftexp_band,
                        sym_scale)
 
@@ -43,6 +54,7 @@ _ALWAYS = [os.environ.get("IVIT_LAZY") == "always"]      # enable_everywhere(): 
 _TLS = threading.local()                                  # .depth: open `scope(True)` blocks of THIS thread; .mat: nested to_float calls
 STATS = {"fused": 0, "materialised": 0}     # fused launches at a QuantAct / float tensors materialised, since the last reset
 _WARNED = set()
+ROW_KERNEL = True       # pure row permutations of a payload (Swin's window partition / shift) as one launch; False: the torch ops
 
 
 def active() -> bool:
@@ -52,10 +64,10 @@ def active() -> bool:
 
 
 def enable_everywhere(on: bool = True):
-    """Frozen 8-bit QuantActs carry int8 wherever they are called from -- for callers that drive the modules themselves, e.g. the
-    reference's own models/vit_quant.py imported on top of this package.  The mirror's VisionTransformer.forward
-    opens the scope by itself; nothing else does by default (Swin's LayerNorms depend on the memory layout of their float inputs,
-    DESIGN.md section 2, which an int8 payload does not carry).  Same as IVIT_LAZY=always in the environment."""
+    """Frozen QuantActs carry integers wherever they are called from -- for callers that drive the modules themselves, e.g. the
+    reference's own models/vit_quant.py or swin_quant.py imported on top of this package (INTEGRATION.md).  The mirrors'
+    VisionTransformer.forward and SwinTransformer.forward open the scope by themselves; nothing else does by default.  Same as
+    IVIT_LAZY=always in the environment."""
     _ALWAYS[0] = bool(on)       # never touches the scope depth: switching it off inside an open scope leaves the scope intact
 
 
@@ -129,28 +141,111 @@ def host_of(s):
 
 # ----------------------------------------------------------------------------------------------------------- int-carrying tensors
 _VIEW = {"reshape", "view", "permute", "transpose", "__getitem__", "flatten", "contiguous", "unbind", "squeeze", "unsqueeze",
-         "select", "narrow", "expand"}
+         "select", "narrow", "expand", "roll"}
+_ROWOPS = {"reshape", "view", "permute", "transpose", "flatten", "contiguous", "roll"}      # recorded on a payload, not executed
 _META = {"size", "dim", "numel", "__len__", "is_floating_point", "element_size", "is_contiguous", "stride", "storage_offset",
          "ndimension", "nelement", "is_complex", "get_device", "type"}
 
 
+def _sig(name, args, kwargs):
+    """hashable description of one recorded shape operation (cache key of the composed row permutation, of the bias integers)"""
+    def one(a):
+        if isinstance(a, torch.Tensor):
+            return ("T", a.data_ptr(), tuple(a.shape), tuple(a.stride()), str(a.dtype), a._version)
+        if isinstance(a, (tuple, list)):
+            return tuple(one(b) for b in a)
+        if isinstance(a, slice):
+            return ("S", a.start, a.stop, a.step)
+        if a is None or a is Ellipsis or isinstance(a, (int, float, str, bool)):
+            return a
+        return repr(a)
+    return (name, tuple(one(a) for a in args), tuple(sorted((k, one(v)) for k, v in kwargs.items())))
+
+
+def _meta_replay(fn, fl, name):
+    """the float layout (a meta tensor: shape and strides of the tensor the reference would hold) after one shape operation"""
+    if name == "roll":                    # torch.roll returns a contiguous tensor
+        return torch.empty(fl.shape, device="meta")
+    return fn(fl)
+
+
+def _dense_strides(fl):
+    """strides of a non-contiguous but dense float layout (a permuted tensor: elementwise results keep it), else None"""
+    if fl.is_contiguous():
+        return None
+    st = fl.stride()
+    return st if torch.empty_like(fl).stride() == st else None
+
+
+def act_layout(x_fl, id_fl=None):
+    """layout of a QuantAct's result (quant_modules.py QuantAct._slow): the identity's when it has the result's shape, else the
+    input's; a dense permuted layout is kept, anything else comes out contiguous"""
+    lay = id_fl if (id_fl is not None and tuple(id_fl.shape) == tuple(x_fl.shape)) else x_fl
+    return torch.empty_like(lay) if not lay.is_contiguous() else torch.empty(x_fl.shape, device="meta")
+
+
+def ln_outer(fl):
+    """how IVITIntLayerNorm reduces a row of this layout (ivit_modules.py:56-61): 0 -- the contiguous order; L -- the outer order
+    over the [B, L, C] transpose of a contiguous [B, C, L] tensor; None -- neither (the caller materialises)"""
+    if fl.dim() < 2 or fl.stride(-1) == 1 or fl.shape[-1] <= 1:
+        return 0
+    if fl.dim() == 3 and fl.stride(1) == 1 and fl.stride(2) == fl.shape[1] and fl.stride(0) == fl.shape[1] * fl.shape[2]:
+        return int(fl.shape[1])
+    return None
+
+
+def _reshapes_only(views):
+    """exactly one recorded view, a reshape / view"""
+    return len(views) == 1 and getattr(views[0], "view_name", None) in ("reshape", "view")
+
+
 class QT(torch.Tensor):
-    """float32-shaped tensor WITHOUT float storage: `q8` holds the int8 payload (a real tensor, same logical shape), or `node`
-    a pending operation plus `views`, the shape operations recorded since"""
+    """float32-shaped tensor WITHOUT float storage: an integer payload -- `q8` int8, or `q16` int16 for a frozen 16-bit QuantAct;
+    `q` is whichever it holds -- plus `rops`, shape operations recorded on it and not executed yet; or `node`, a pending
+    operation, plus `views`, the shape operations recorded since.  `fl` (a meta tensor) carries the strides the reference's float
+    tensor would have: the reduction order of a LayerNorm depends on them."""
 
     @staticmethod
-    def wrap(shape, device, q8=None, scale=None, node=None, views=()):
+    def wrap(shape, device, q8=None, scale=None, node=None, views=(), q16=None, fl=None, rops=(), origin=None):
         r = torch.Tensor._make_wrapper_subclass(QT, tuple(shape), dtype=torch.float32, device=device, requires_grad=False)
-        r._q8, r.scale, r.node, r.views = q8, scale, node, tuple(views)
+        r._q8, r._q16, r.scale, r.node, r.views, r.rops, r.origin = q8, q16, scale, node, tuple(views), tuple(rops), origin
+        r.fl = fl if fl is not None else torch.empty(tuple(shape), device="meta")
         return r
+
+    def _run_rops(self):
+        if self.rops:
+            out = run_rows(self._q8 if self._q8 is not None else self._q16, self.rops, tuple(self.shape))
+            if self._q8 is not None:
+                self._q8 = out
+            else:
+                self._q16 = out
+            self.rops = ()
 
     @property
     def q8(self):
-        """the int8 payload; a deferred requantising GEMM (Requant) is launched the first time anybody asks for it"""
-        if self._q8 is None and isinstance(self.node, Requant):
+        """the int8 payload (None for an int16 one); a deferred requantising GEMM (Requant) is launched the first time anybody asks
+        for it, recorded shape operations are executed"""
+        if self._q8 is None and self._q16 is None and isinstance(self.node, Requant):
             self._q8 = self.apply_views(self.node.force())
             self.node, self.views = None, ()
+        self._run_rops()
         return self._q8
+
+    @property
+    def q16(self):
+        """the int16 payload (None for an int8 one)"""
+        self._run_rops()
+        return self._q16
+
+    @property
+    def q(self):
+        """the integer payload of either width"""
+        a = self.q8
+        return a if a is not None else self.q16
+
+    def _like(self, shape, fl, **kw):
+        """a QT of the same width, scale and origin around another payload / more recorded operations"""
+        return QT.wrap(shape, self.device, scale=self.scale, fl=fl, **kw)
 
     # -- materialisation: the float tensor the reference's module would have returned
     def to_float(self, boundary=False):
@@ -160,8 +255,8 @@ class QT(torch.Tensor):
         STATS["materialised"] += 1
         depth = getattr(_TLS, "mat", 0)
         if depth == 0 and not boundary:
-            what = "int8 payload" if self._q8 is not None else type(self.node).__name__ + (
-                f"({self.node.kind})" if hasattr(self.node, "kind") else "")
+            what = "int8 payload" if self._q8 is not None else "int16 payload" if self._q16 is not None else (
+                type(self.node).__name__ + (f"({self.node.kind})" if hasattr(self.node, "kind") else ""))
             if what not in _WARNED:
                 _WARNED.add(what)
                 warnings.warn(f"ivit_amd.lazy: an int8-carrying activation ({what}) was materialised as float32 inside the model; the "
@@ -169,8 +264,15 @@ class QT(torch.Tensor):
                               stacklevel=2)
         _TLS.mat = depth + 1
         try:
-            if self.q8 is not None:
-                return self.q8.to(torch.float32) * self.scale.as_subclass(torch.Tensor).reshape(-1)[0]
+            q = self.q
+            if q is not None:
+                y = q.to(torch.float32) * self.scale.as_subclass(torch.Tensor).reshape(-1)[0]
+                st = _dense_strides(self.fl)         # a permuted layout the reference's tensor has (Swin's first stage): consumers
+                if st is not None and tuple(y.stride()) != tuple(st):     # that reduce over it depend on it
+                    y = torch.empty_strided(tuple(y.shape), tuple(st), dtype=y.dtype, device=y.device).copy_(y)
+                elif self.fl.is_contiguous() and not y.is_contiguous() and _dense_strides(y) is not None:
+                    y = y.contiguous()
+                return y
             t = self.node.to_float()
             for fn in self.views:
                 t = fn(t)
@@ -203,17 +305,39 @@ class QT(torch.Tensor):
 
             def fn(t, _f=func, _r=rest, _k=kwargs):
                 return _f(t, *_r, **_k)
+            fn.view_name = name
 
-            if self._q8 is not None:
-                out = fn(self._q8)
+            payload = self._q8 if self._q8 is not None else self._q16
+            if payload is not None:
+                sig = _sig(name, rest, kwargs)
+                origin = None if self.origin is None else self.origin + (sig,)
+                wide = {"q8": None, "q16": None}
+                if name in _ROWOPS:
+                    # not executed: the next consumer composes the recorded operations into one row permutation (run_rows)
+                    fl = _meta_replay(fn, self.fl, name)
+                    wide["q8" if self._q8 is not None else "q16"] = payload
+                    return self._like(fl.shape, fl, rops=self.rops + ((name, fn, sig, rest, kwargs),), origin=origin, **wide)
+                out = fn(self.q)
+                try:
+                    fl = _meta_replay(fn, self.fl, name)
+                except Exception:          # e.g. an index tensor on the device: the result of such an operation is contiguous
+                    fl = None
+
+                def one(o, f):
+                    wide["q8" if o.dtype == torch.int8 else "q16"] = o
+                    return self._like(o.shape, f if f is not None and tuple(f.shape) == tuple(o.shape) else None, origin=origin, **wide)
                 if isinstance(out, (tuple, list)):
-                    return tuple(QT.wrap(o.shape, o.device, q8=o, scale=self.scale) for o in out)
-                return QT.wrap(out.shape, out.device, q8=out, scale=self.scale)
-            meta = fn(torch.empty(self.shape, device="meta"))
+                    res = []
+                    for i, o in enumerate(out):
+                        wide = {"q8": None, "q16": None}
+                        res.append(one(o, None if fl is None else fl[i]))
+                    return tuple(res)
+                return one(out, fl)
+            meta = _meta_replay(fn, self.fl, name)
             if isinstance(meta, (tuple, list)):
-                return tuple(QT.wrap(m.shape, self.device, scale=self.scale, node=self.node,
+                return tuple(QT.wrap(m.shape, self.device, scale=self.scale, node=self.node, fl=m,
                                      views=self.views + ((lambda t, _fn=fn, _i=i: _fn(t)[_i]),)) for i, m in enumerate(meta))
-            return QT.wrap(meta.shape, self.device, scale=self.scale, node=self.node, views=self.views + (fn,))
+            return QT.wrap(meta.shape, self.device, scale=self.scale, node=self.node, views=self.views + (fn,), fl=meta)
         if name in ("dropout", "dropout_", "feature_dropout", "alpha_dropout") and self is not None:
             training = kwargs.get("training", args[2] if len(args) > 2 else kwargs.get("train", True))
             if not training:
@@ -223,12 +347,21 @@ class QT(torch.Tensor):
             if isinstance(b, (int, float)) and not isinstance(b, bool):
                 # value * c with the scale multiplied by c alongside (vit_quant.py:74-75): the integers stay what they are
                 if a.q8 is not None:
-                    return QT.wrap(a.shape, a.device, q8=a.q8, scale=a.scale * b)
-                return QT.wrap(a.shape, a.device, node=Scaled(a, float(b)))
+                    return QT.wrap(a.shape, a.device, q8=a.q8, scale=a.scale * b, fl=a.fl)
+                if a._q16 is None:
+                    return QT.wrap(a.shape, a.device, node=Scaled(a, float(b)))
+        if name in ("add", "__add__", "__radd__") and len(args) == 2 and ENABLED:
+            a, b = (args[0], args[1]) if isinstance(args[0], QT) else (args[1], args[0])
+            # `+ mask` on the pending, biased scores of a shifted window (swin_quant.py:149-155): stays pending
+            # the scores reshaped to [B, nW, nH, N, N], the mask [1, nW, 1, N, N] (mask.unsqueeze(1).unsqueeze(0)): nothing else
+            if (isinstance(a, QT) and isinstance(a.node, Biased) and _reshapes_only(a.views) and type(b) is torch.Tensor
+                    and b.dtype == torch.float32 and not kwargs and a.dim() == 5 and a.shape[3] == a.shape[4]
+                    and tuple(b.shape) == (1, a.shape[1], 1, a.shape[3], a.shape[4])):
+                return QT.wrap(a.shape, a.device, node=Masked(a, b))
         if name == "cat" and ENABLED:
             tensors = args[0]
             dim = kwargs.get("dim", args[1] if len(args) > 1 else 0)
-            if all(isinstance(t, QT) and t.q8 is not None or not isinstance(t, QT) for t in tensors):
+            if all(isinstance(t, QT) and t.q is not None or not isinstance(t, QT) for t in tensors):
                 shapes = [torch.empty(t.shape, device="meta") for t in tensors]
                 meta = torch.cat(shapes, dim=dim)
                 return QT.wrap(meta.shape, next(t.device for t in tensors if isinstance(t, QT)), node=Cat(list(tensors), dim))
@@ -239,6 +372,132 @@ class QT(torch.Tensor):
         args = torch.utils._pytree.tree_map(real, args)
         kwargs = torch.utils._pytree.tree_map(real, kwargs)
         return func(*args, **kwargs)
+
+
+# ----------------------------------------------------------------------------------------------------------- row permutations
+_ROWPLAN = {}
+
+
+_TORCH_PLAN = ("torch",)
+
+
+def row_plan(shape, rops):
+    """What the recorded shape operations `rops` do to the rows (the last dimension, left whole) of a contiguous tensor of `shape`,
+    found by replaying them on an int32 row-index tensor on the host:
+      ("identity",) | ("window", B, H, W, ws, shift, inverse) -- swin_engine.window_row_map or its inverse, one ivit_window_rows
+      launch | ("index", perm) -- any other row permutation: destination row j takes source row perm[j] | ("torch",) -- not a
+      row permutation: the operations run on the payload as they are"""
+    from ..swin_engine import window_row_map
+    C = shape[-1]
+    if len(shape) < 2:
+        return _TORCH_PLAN
+    rows = int(np.prod(shape[:-1]))
+    if rows >= 2 ** 31:
+        return _TORCH_PLAN
+    idx = torch.arange(rows, dtype=torch.int32).reshape(*shape[:-1], 1)
+    meta = torch.empty(shape, device="meta")
+    cands = [tuple(shape)]
+    for name, fn, _, args, kwargs in rops:
+        nd = meta.dim()
+        try:
+            new = _meta_replay(fn, meta, name)
+            if new.shape[-1] != C or new.numel() != meta.numel():
+                return _TORCH_PLAN
+            if name in ("reshape", "view", "flatten"):
+                idx = idx.reshape(*new.shape[:-1], 1)
+            elif name == "permute":
+                dims = args[0] if len(args) == 1 and isinstance(args[0], (tuple, list)) else args
+                if kwargs or int(dims[-1]) % nd != nd - 1:
+                    return _TORCH_PLAN
+                idx = fn(idx)
+            elif name == "transpose":
+                if kwargs or len(args) != 2 or any(int(d) % nd == nd - 1 for d in args):
+                    return _TORCH_PLAN
+                idx = fn(idx)
+            elif name == "roll":
+                dims = kwargs.get("dims", args[1] if len(args) > 1 else None)
+                if dims is None:
+                    return _TORCH_PLAN
+                dims = dims if isinstance(dims, (tuple, list)) else (dims,)
+                if any(int(d) % nd == nd - 1 for d in dims):
+                    return _TORCH_PLAN
+                idx = fn(idx)
+            elif name != "contiguous":
+                return _TORCH_PLAN
+        except Exception:
+            return _TORCH_PLAN
+        if tuple(idx.shape[:-1]) != tuple(new.shape[:-1]):
+            return _TORCH_PLAN
+        meta = new
+        cands.append(tuple(meta.shape))
+    perm = idx.reshape(-1).numpy().astype(np.int64)
+    if perm.size != rows or not np.array_equal(np.sort(perm), np.arange(rows)):
+        return _TORCH_PLAN
+    if np.array_equal(perm, np.arange(rows)):
+        return ("identity",)
+    for B, H, W in dict.fromkeys(c[:3] for c in cands if len(c) == 4 and c[0] * c[1] * c[2] == rows):
+        L = H * W
+        first = perm[:L]
+        if first.max() >= L:
+            continue
+        g = int(np.gcd(H, W))
+        for ws in (d for d in range(2, g + 1) if g % d == 0):
+            for shift in range(ws):
+                m1 = window_row_map(1, H, W, ws, shift)
+                inverse = np.array_equal(first, m1)                 # dst row r = src row map[r]
+                if not inverse:
+                    inv = np.empty(L, np.int64)
+                    inv[m1] = np.arange(L)
+                    if not np.array_equal(first, inv):              # dst row map[r] = src row r
+                        continue
+                m = window_row_map(B, H, W, ws, shift)
+                if not inverse:
+                    inv = np.empty(rows, np.int64)
+                    inv[m] = np.arange(rows)
+                    m = inv
+                if np.array_equal(perm, m):
+                    return ("window", B, H, W, ws, shift, int(inverse))
+    return ("index", perm)
+
+
+def run_rows(base, rops, out_shape):
+    """executes the shape operations recorded on a payload: one row gather where they compose to a row permutation"""
+    plan = None
+    if ROW_KERNEL and base.dim() >= 2 and base.is_contiguous():
+        key = (tuple(base.shape), tuple(r[2] for r in rops))
+        plan = _ROWPLAN.get(key)
+        if plan is None:
+            if len(_ROWPLAN) >= 256:
+                _ROWPLAN.clear()
+            plan = _ROWPLAN[key] = [row_plan(tuple(base.shape), rops), {}]
+        plan, dev_maps = plan
+        if plan[0] == "identity":
+            return base.reshape(out_shape)
+        row_bytes = base.shape[-1] * base.element_size()
+        if plan[0] == "window" and base.is_cuda and row_bytes % 16 == 0 and base.data_ptr() % 16 == 0:
+            _, B, H, W, ws, shift, inverse = plan
+            out = torch.empty(out_shape, dtype=base.dtype, device=base.device)
+            _lib.call("ivit_window_rows", _lib.ptr(base), _lib.ptr(out), B, H, W, row_bytes, ws, shift, inverse, _st())
+            return out
+        if plan[0] in ("window", "index"):
+            dk = str(base.device)
+            if dk not in dev_maps:
+                if plan[0] == "window":
+                    from ..swin_engine import window_row_map
+                    _, B, H, W, ws, shift, inverse = plan
+                    perm = window_row_map(B, H, W, ws, shift)
+                    if not inverse:
+                        inv = np.empty(perm.size, np.int64)
+                        inv[perm] = np.arange(perm.size)
+                        perm = inv
+                else:
+                    perm = plan[1]
+                dev_maps[dk] = _dev(perm.astype(np.int64), base.device)
+            return base.reshape(-1, base.shape[-1]).index_select(0, dev_maps[dk]).reshape(out_shape)
+    t = base
+    for r in rops:
+        t = r[1](t)
+    return t
 
 
 # ----------------------------------------------------------------------------------------------------------- pending nodes
@@ -265,6 +524,29 @@ class Cat(Node):
         return torch.cat([p.to_float() if isinstance(p, QT) else p for p in self.parts], dim=self.dim)
 
 
+class Biased(Node):
+    """WindowAttention.qact2 on the pending scores with the float relative position bias as its identity (swin_quant.py:143-147):
+    pending until Shiftmax and the second matmul arrive"""
+
+    def __init__(self, x, pre_sf, identity, identity_sf, s_out, s_out_qs, qact):
+        self.x, self.pre_sf, self.identity, self.identity_sf, self.qact = x, pre_sf, identity, identity_sf, qact
+        self.s_in, self.s_id, self.s_out, self.s_out_qs = pre_sf.host, identity_sf.host, s_out, s_out_qs
+
+    def to_float(self):
+        return self.qact._slow(self.x.to_float(), self.pre_sf, self.identity.to_float(), self.identity_sf)[0]
+
+
+class Masked(Node):
+    """`+ mask` on the biased scores of a shifted window (swin_quant.py:149-155)"""
+
+    def __init__(self, x, mask):
+        self.x, self.mask = x, mask
+        self.s_out_qs = x.node.s_out_qs
+
+    def to_float(self):
+        return self.x.to_float() + self.mask
+
+
 class ModNode(Node):
     """the pending call of a module: `mod._slow(*float inputs)` reproduces what the ordinary path returns"""
 
@@ -280,9 +562,9 @@ class ModNode(Node):
         return self.mod._slow(*xs, *self.scales)[0]
 
 
-def pending(kind, mod, shape, device, inputs, scales, out_scale):
+def pending(kind, mod, shape, device, inputs, scales, out_scale, fl=None):
     """-> (QT holding the pending call, out_scale): what the module's forward returns"""
-    return QT.wrap(shape, device, node=ModNode(kind, mod, shape, inputs, scales, out_scale)), out_scale
+    return QT.wrap(shape, device, node=ModNode(kind, mod, shape, inputs, scales, out_scale), fl=fl), out_scale
 
 
 def q8_contig(x):
@@ -290,6 +572,57 @@ def q8_contig(x):
     if isinstance(x, QT) and x.q8 is not None:
         return x.q8 if x.q8.is_contiguous() else x.q8.contiguous()
     return None
+
+
+def q16_contig(x):
+    if isinstance(x, QT) and x.q16 is not None:
+        return x.q16 if x.q16.is_contiguous() else x.q16.contiguous()
+    return None
+
+
+def _merged_patches(parts, dim):
+    """PatchMerging's cat of the four strided slices of one int16 [B, H, W, C] payload (swin_quant.py:337-344) as one
+    ivit_patch_merge_i16 launch; None if the parts are anything else"""
+    if len(parts) != 4 or any(p.dim() != 4 or p.dtype != torch.int16 for p in parts) or dim not in (-1, 3):
+        return None
+    B, H2, W2, C = parts[0].shape
+    H, W = 2 * H2, 2 * W2
+    p0 = parts[0]
+    base = p0.data_ptr()
+    for p, (dy, dx) in zip(parts, ((0, 0), (1, 0), (0, 1), (1, 1))):
+        if (tuple(p.shape) != (B, H2, W2, C) or tuple(p.stride()) != (H * W * C, 2 * W * C, 2 * C, 1)
+                or p.data_ptr() - base != 2 * (dy * W + dx) * C or p.untyped_storage().data_ptr() != p0.untyped_storage().data_ptr()):
+            return None
+    if C % 4 or base % 8:
+        return None
+    out = torch.empty(B, H2, W2, 4 * C, dtype=torch.int16, device=p0.device)
+    _lib.call("ivit_patch_merge_i16", _lib.ptr(p0), _lib.ptr(out), B, H, W, C, _st())
+    return out
+
+
+def int_width(x):
+    """8 / 16: x holds (or is a cat of parts that hold) an integer payload of that width; None otherwise"""
+    if not isinstance(x, QT):
+        return None
+    if x.q is not None:
+        return 8 if x._q8 is not None else 16
+    if isinstance(x.node, Cat) and x.node.parts and all(isinstance(p, QT) and p.q is not None for p in x.node.parts):
+        widths = {8 if p._q8 is not None else 16 for p in x.node.parts}
+        if len(widths) == 1:
+            return widths.pop()
+    return None
+
+
+def int_payload(x):
+    """the contiguous integer payload of a QT for which int_width(x) is not None"""
+    q = x.q
+    if q is None:
+        parts = [p.q for p in x.node.parts]
+        q = _merged_patches(parts, x.node.dim)
+        if q is None:
+            q = torch.cat(parts, dim=x.node.dim)
+        q = x.apply_views(q)
+    return q if q.is_contiguous() else q.contiguous()
 
 
 # ----------------------------------------------------------------------------------------------------------- the fused launches
@@ -311,28 +644,39 @@ def linear_consts(lin, s_in, device):
     fragment copy where the weights-in-registers GEMM applies), b32, s_acc"""
     def build():
         lp = LinearParams(lin.weight.detach().cpu().numpy(), None if lin.bias is None else lin.bias.detach().cpu().numpy(), s_in)
-        N, K = lp.W8.shape
+        N, Kin = lp.W8.shape
+        K = (Kin + 63) // 64 * 64          # the GEMM kernels step K in 64-byte slabs: zero columns (Swin: K = 96, 48)
+        W8 = lp.W8
+        if K != Kin:
+            W8 = np.zeros((N, K), np.int8)
+            W8[:, :Kin] = lp.W8
         lin._publish(lp, device)           # the buffers the reference rewrites on every call
-        d = dict(lp=lp, N=N, K=K, W=_dev(lp.W8, device), b=None if lp.b32 is None else _dev(lp.b32, device),
+        d = dict(lp=lp, N=N, K=K, Kin=Kin, W=_dev(W8, device), b=None if lp.b32 is None else _dev(lp.b32, device),
                  s_acc=QS.make(lp.s_acc, device))
         d["Wf"], _ = frag_copy(d["W"], _st())       # every consumer here has an int8 epilogue
         return d
     return _cache(lin, ("lin", lin.weight._version, None if lin.bias is None else lin.bias._version, _key(s_in), str(device)), build)
 
 
-def _gemm_me(lin, s_in, s_out, device):
-    """device (m, e) tables of the per-channel requantisation s_acc -> s_out, or None outside the kernels' contract (e < 31)"""
+def _gemm_me(lin, s_in, s_out, device, need_e31=True):
+    """device (m, e) tables of the per-channel requantisation s_acc -> s_out, or None outside the int8 epilogues' contract (e < 31;
+    need_e31 = False: the 16-bit epilogue, which takes any pair)"""
     c = linear_consts(lin, s_in, device)
 
     def build():
         m, e = dyadic(c["lp"].s_acc, s_out)
-        if np.any(e < 31):
+        if need_e31 and np.any(e < 31):
             return None
         return _dev(m.view(np.int32), device), _dev(e, device)
     # keyed on the weight / bias versions as linear_consts is: an in-place weight edit under unchanged ranges rebuilds W8 and
     # s_acc there, and the per-channel multipliers must follow (round-3 advisor finding: they did not)
-    return _cache(lin, ("rq", lin.weight._version, None if lin.bias is None else lin.bias._version, _key(s_in, s_out), str(device)),
-                  build)
+    return _cache(lin, ("rq", need_e31, lin.weight._version, None if lin.bias is None else lin.bias._version, _key(s_in, s_out),
+                        str(device)), build)
+
+
+def _operand(a8, c):
+    """the A operand of a GEMM whose K was padded to the kernels' 64-byte slabs: zero columns to match"""
+    return a8 if c["K"] == c["Kin"] else torch.nn.functional.pad(a8, (0, c["K"] - c["Kin"]))
 
 
 def gemm_requant(lin, a8, s_in, s_out, device):
@@ -340,11 +684,12 @@ def gemm_requant(lin, a8, s_in, s_out, device):
     kernels' contract"""
     c = linear_consts(lin, s_in, device)
     N, K = c["N"], c["K"]
-    if K % 64 != 0 or N % 16 != 0:
+    if N % 16 != 0:
         return None
     me = _gemm_me(lin, s_in, s_out, device)
     if me is None:
         return None
+    a8 = _operand(a8, c)
     M = a8.shape[0]
     out = torch.empty(M, N, dtype=torch.int8, device=device)
     frags = c["Wf"] is not None and M >= 2048
@@ -361,11 +706,18 @@ def resolve(qact, x, pre_sf, identity, identity_sf, s_out, s_out_qs):
         return None
     node = x.node
     out = None
+    fl = act_layout(x.fl, identity.fl if isinstance(identity, QT) else None)
+    if isinstance(node, Scores) and identity is not None:
+        # WindowAttention.qact2: the scores plus the float relative position bias (swin_quant.py:143-147); stays pending
+        if (not x.views and isinstance(identity, QT) and identity.origin is not None and host_of(identity_sf) is not None
+                and s_in is node.s_out_qs.host and host_of(identity_sf).size == 1 and s_in.size == 1):
+            return QT.wrap(x.shape, device, node=Biased(x, pre_sf, identity, identity_sf, s_out, s_out_qs, qact))
+        return None
     if isinstance(node, Requant) and x._q8 is None and identity is not None and not x.views:
         out = node.with_residual(identity, host_of(identity_sf), s_in, s_out, device)
         if out is not None:
             STATS["fused"] += 1
-            return QT.wrap(out.shape, device, q8=out, scale=s_out_qs)
+            return QT.wrap(out.shape, device, q8=out, scale=s_out_qs, fl=fl)
     if x.q8 is not None:
         if identity is None:
             return None
@@ -378,7 +730,7 @@ def resolve(qact, x, pre_sf, identity, identity_sf, s_out, s_out_qs):
         _lib.call("ivit_residual_requant_i8", _lib.ptr(x8), int(m1[0]), int(e1[0]), _lib.ptr(i8), int(m2[0]), int(e2[0]),
                   _lib.ptr(out), x8.numel(), _st())
         STATS["fused"] += 1
-        return QT.wrap(out.shape, device, q8=out, scale=s_out_qs)
+        return QT.wrap(out.shape, device, q8=out, scale=s_out_qs, fl=fl)
     if isinstance(node, Cat):
         out = _resolve_cat(qact, node, s_in, identity, identity_sf, s_out, device)
     elif isinstance(node, ModNode) and identity is None:
@@ -399,7 +751,7 @@ def resolve(qact, x, pre_sf, identity, identity_sf, s_out, s_out_qs):
                 # this requantisation and that one are ONE kernel; any other consumer launches the GEMM as it is
                 rq = Requant(node.mod, a8, s_a, s_out, node.shape, s_out_qs)
                 if rq.ok:
-                    return QT.wrap(x.shape, device, scale=s_out_qs, node=rq)
+                    return QT.wrap(x.shape, device, scale=s_out_qs, node=rq, fl=fl)
             o = gemm_requant(node.mod, a8, s_a, s_out, device) if a8 is not None else None
             if o is not None:
                 sh = node.shape
@@ -424,7 +776,99 @@ def resolve(qact, x, pre_sf, identity, identity_sf, s_out, s_out_qs):
         return None
     STATS["fused"] += 1
     out = x.apply_views(out)
-    return QT.wrap(out.shape, device, q8=out, scale=s_out_qs)
+    return QT.wrap(out.shape, device, q8=out, scale=s_out_qs, fl=fl if tuple(fl.shape) == tuple(out.shape) else None)
+
+
+def _sme(pre, z):
+    m, e = dyadic(pre, z)
+    return int(m[0]), int(e[0])
+
+
+def resolve_float(qact, x, pre_sf, s_out, s_out_qs):
+    """The frozen 8-bit QuantAct on a float tensor whose scale is known on the host (Swin's qact3 behind the float pooling,
+    swin_quant.py:554-555): round(x / s), the requantisation, int8 out -- nothing read back.  None: ordinary path."""
+    s_in = host_of(pre_sf)
+    if s_in is None or s_in.size != 1 or s_in[0] <= 0 or x.dtype != torch.float32 or x.dim() < 1:
+        return None
+    device = x.device
+    m, e = dyadic(s_in, s_out)
+    md, ed = _cache(qact, ("me", _key(s_in, np.asarray(s_out)), str(device)), lambda: (_dev(m.view(np.int32), device), _dev(e, device)))
+    xin = x.contiguous()
+    C = xin.shape[-1]
+    z = torch.empty(xin.shape, dtype=torch.int32, device=device)
+    _lib.call("ivit_f32_to_i32", _lib.ptr(xin), xin.numel() // C, C, _lib.ptr(pre_sf.as_subclass(torch.Tensor).reshape(-1)), 1, 0,
+              _lib.ptr(z), _st())
+    q = torch.empty_like(z)
+    _lib.call("ivit_requant_i32", _lib.ptr(z), z.numel() // C, C, _lib.ptr(md), _lib.ptr(ed), 1, None, None, None, 0, 8, _lib.ptr(q), _st())
+    STATS["fused"] += 1
+    return QT.wrap(q.shape, device, q8=q.to(torch.int8), scale=s_out_qs, fl=act_layout(torch.empty_like(x, device="meta")))
+
+
+def resolve16(qact, x, pre_sf, identity, identity_sf, s_out, s_out_qs):
+    """The frozen 16-bit QuantAct on a QT, in the patterns of the Swin forward (swin_quant.py): one launch -> int16 QT.
+      int8 payload                                  -> ivit_requant_i8_i16               (the model's qact1, :546)
+      pending linear                                -> ivit_gemm_i8_requant_i16          (attn.proj -> attn.qact4, :166)
+      int16 / int8 payload + int16 / int8 identity  -> ivit_residual_requant_i16         (the residual qact2, :291)
+      deferred fc2 + mlp.qact2 (Requant) + identity -> ivit_gemm_i8_requant_residual_i16_ex   (the residual qact4, :297-299)
+    None: not one of these (ordinary path)."""
+    device = x.device
+    s_in = host_of(pre_sf)
+    if s_in is None:
+        return None
+    fl = act_layout(x.fl, identity.fl if isinstance(identity, QT) else None)
+    node = x.node
+    out = None
+    if identity is not None:
+        s_id = host_of(identity_sf)
+        if (not isinstance(identity, QT) or s_id is None or s_id.size != 1 or s_in.size != 1
+                or tuple(identity.shape) != tuple(x.shape)):
+            return None
+        i16 = q16_contig(identity)
+        if i16 is None:
+            i8 = q8_contig(identity)
+            if i8 is None:
+                return None
+            i16 = torch.empty(i8.shape, dtype=torch.int16, device=device)      # an 8-bit stream (behind a PatchMerging): widened
+            _lib.call("ivit_requant_i8_i16", _lib.ptr(i8), 1 << 30, 30, _lib.ptr(i16), i8.numel(), _st())
+        C = x.shape[-1]
+        (m1, e1), (m2, e2) = _sme(s_in, s_out), _sme(s_id, s_out)
+        if isinstance(node, Requant) and x._q8 is None and not x.views and node.out is None:
+            out = node.with_residual16(i16, s_in, (m1, e1, m2, e2), device)
+        if out is None:
+            a = x.q
+            if a is None or C % 4:
+                return None
+            a = a if a.is_contiguous() else a.contiguous()
+            out = torch.empty(a.shape, dtype=torch.int16, device=device)
+            _lib.call("ivit_residual_requant_i16", _lib.ptr(a), 8 * a.element_size(), None, None, m1, e1, _lib.ptr(i16), m2, e2, _lib.ptr(out),
+                      a.numel() // C, C, 0, 0, 0, 0, _st())
+    elif x.q8 is not None:
+        if s_in.size != 1:
+            return None
+        a = q8_contig(x)
+        m, e = _sme(s_in, s_out)
+        out = torch.empty(a.shape, dtype=torch.int16, device=device)
+        _lib.call("ivit_requant_i8_i16", _lib.ptr(a), m, e, _lib.ptr(out), a.numel(), _st())
+    elif isinstance(node, ModNode) and node.kind == "linear" and s_in is host_of(node.out_scale):
+        s_a = host_of(node.scales[0])
+        a8 = q8_contig(node.inputs[0])
+        if s_a is None or s_a.size != 1 or a8 is None:
+            return None
+        c = linear_consts(node.mod, s_a, device)
+        me = _gemm_me(node.mod, s_a, s_out, device, need_e31=False)
+        N, K = c["N"], c["K"]
+        if N % 8:
+            return None
+        a8 = _operand(a8.reshape(-1, a8.shape[-1]), c)
+        M = a8.shape[0]
+        o = torch.empty(M, N, dtype=torch.int16, device=device)
+        _lib.call("ivit_gemm_i8_requant_i16", _lib.ptr(a8), K, _lib.ptr(c["W"]), K, _lib.ptr(c["b"]), _lib.ptr(me[0]), _lib.ptr(me[1]),
+                  _lib.ptr(o), N, M, N, K, _st())
+        out = x.apply_views(o.view(*node.shape))
+    if out is None:
+        return None
+    STATS["fused"] += 1
+    return QT.wrap(out.shape, device, q16=out, scale=s_out_qs, fl=fl if tuple(fl.shape) == tuple(out.shape) else None)
 
 
 class Requant(Node):
@@ -441,9 +885,10 @@ class Requant(Node):
             self.out = gemm_requant(self.lin, self.a8, self.s_a, self.s_out, self.a8.device).view(*self.shape)
         return self.out
 
-    def head_major(self, q, kT, v):
+    def head_major(self, q, kT, v, head_dim=64, max_tokens=1025, frags=True):
         """q, k^T and v of vit_quant.py:66-70 as recorded views of THIS linear's output [B, N, 3 H hd]: the GEMM writes them head-major
-        ([3, B, H, N, hd], what the attention kernel reads) itself -> that tensor; None if the views are anything else"""
+        ([3, B, H, N, hd], what the attention kernel reads) itself -> that tensor; None if the views are anything else.
+        frags = False (Swin's windows, head_dim 32): row-major weights where the fragment copy does not apply"""
         if self.out is not None or len(self.shape) != 3 or any(t._q8 is not None or t.node is not self for t in (q, kT, v)):
             return None
         B, N, C3 = self.shape
@@ -453,17 +898,18 @@ class Requant(Node):
             return None
         H, hd = mq.shape[1], mq.shape[3]
         C = H * hd
-        if 3 * C != C3 or hd != 64 or N > 1025 or any(tuple(m.shape) != (B, H, N, hd) or m.stride() != (N * C3, hd, C3, 1)
-                                                     or m.storage_offset() != i * C for i, m in enumerate((mq, mk, mv))):
+        if 3 * C != C3 or hd != head_dim or N > max_tokens or any(tuple(m.shape) != (B, H, N, hd) or m.stride() != (N * C3, hd, C3, 1)
+                                                                 or m.storage_offset() != i * C for i, m in enumerate((mq, mk, mv))):
             return None
         device = self.a8.device
         c = linear_consts(self.lin, self.s_a, device)
         me = _gemm_me(self.lin, self.s_a, self.s_out, device)
-        if c["Wf"] is None or c["K"] != C:
+        use_frags = c["Wf"] is not None and (frags or B * N >= 2048)
+        if (frags and c["Wf"] is None) or c["Kin"] != C:
             return None
         hm = torch.empty(3, B, H, N, hd, dtype=torch.int8, device=device)
-        _lib.call("ivit_gemm_i8_requant_qkv_ex", _lib.ptr(self.a8), c["K"], _lib.ptr(c["Wf"]), c["K"], _lib.ptr(c["b"]), _lib.ptr(me[0]),
-                  _lib.ptr(me[1]), _lib.ptr(hm), N, H, hd, B * N, C3, c["K"], 16, _st())
+        _lib.call("ivit_gemm_i8_requant_qkv_ex", _lib.ptr(_operand(self.a8, c)), c["K"], _lib.ptr(c["Wf"] if use_frags else c["W"]), c["K"],
+                  _lib.ptr(c["b"]), _lib.ptr(me[0]), _lib.ptr(me[1]), _lib.ptr(hm), N, H, hd, B * N, C3, c["K"], 16 if use_frags else 0, _st())
         STATS["fused"] += 1
         return hm
 
@@ -484,6 +930,23 @@ class Requant(Node):
         out = torch.empty(M, N, dtype=torch.int8, device=device)
         _lib.call("ivit_gemm_i8_requant_residual_ex", _lib.ptr(self.a8), K, _lib.ptr(c["Wf"]), K, _lib.ptr(c["b"]), _lib.ptr(me[0]),
                   _lib.ptr(me[1]), _lib.ptr(i8), N, int(m1[0]), int(e1[0]), int(m2[0]), int(e2[0]), _lib.ptr(out), N, M, N, K, 16, _st())
+        return out.view(*self.shape)
+
+    def with_residual16(self, i16, s_in, mes, device):
+        """mlp.fc2 + mlp.qact2 + the 16-bit residual QuantAct in one kernel (swin_engine.py does the same): int16 out, or None"""
+        c = linear_consts(self.lin, self.s_a, device)
+        N, K = c["N"], c["K"]
+        if s_in[0] != f32(self.s_out) or tuple(i16.shape) != tuple(self.shape) or N % 8:
+            return None
+        me = _gemm_me(self.lin, self.s_a, self.s_out, device)
+        a8 = _operand(self.a8, c)
+        M = a8.shape[0]
+        # the fragment copy with a 16-bit-residual epilogue works in 256-channel tiles: where they fit (engine_common.frag_copy)
+        frags = c["Wf"] is not None and M >= 2048 and (N + 255) // 256 * 256 * 8 <= N * 9
+        out = torch.empty(M, N, dtype=torch.int16, device=device)
+        _lib.call("ivit_gemm_i8_requant_residual_i16_ex", _lib.ptr(a8), K, _lib.ptr(c["Wf"] if frags else c["W"]), K, _lib.ptr(c["b"]),
+                  _lib.ptr(me[0]), _lib.ptr(me[1]), _lib.ptr(i16), N, mes[0], mes[1], mes[2], mes[3], _lib.ptr(out), N, M, N, K,
+                  16 if frags else 0, _st())
         return out.view(*self.shape)
 
 
@@ -521,11 +984,24 @@ def _patchify_i8(conv, x):
 
 def _resolve_ln(node, s_out, device):
     ln, x = node.mod, node.inputs[0]
-    x8 = q8_contig(x)
     s_in = host_of(node.scales[0])
-    if x8 is None or s_in is None or s_in.size != 1:
+    bits = int_width(x)
+    outer = ln_outer(x.fl) if isinstance(x, QT) else None       # the reduction order follows the FLOAT tensor's layout
+    if bits is None or outer is None or s_in is None or s_in.size != 1:
         return None
+    x8 = int_payload(x)
     C = x8.shape[-1]
+    if bits == 16:
+        def build16():
+            lp = LayerNormParams(ln.weight.detach().cpu().numpy(), ln.bias.detach().cpu().numpy(), s_out)
+            return ln_spec(lp, lambda a: _dev(a, device), s_in[0], 16)
+        try:
+            spec = _cache(ln, ("ln16", ln.weight._version, ln.bias._version, _key(s_in, s_out), str(device)), build16)
+        except ValueError:
+            return None
+        out = torch.empty(x8.shape, dtype=torch.int8, device=device)
+        layernorm(spec, x8, C, x8.numel() // C, C, out, C, _st(), outer=outer)
+        return out
 
     def build():
         lp = LayerNormParams(ln.weight.detach().cpu().numpy(), ln.bias.detach().cpu().numpy(), s_out)
@@ -540,7 +1016,7 @@ def _resolve_ln(node, s_out, device):
     out = torch.empty_like(x8)
     if tabs is not None:
         _lib.call("ivit_layernorm_i8_compat", _lib.ptr(x8), C, rows, C, _lib.ptr(c["bias"]), _lib.ptr(c["s"]), _lib.ptr(c["m"]),
-                  _lib.ptr(c["e"]), _lib.ptr(tabs[0]), _lib.ptr(tabs[1]), _lib.ptr(out), C, 0, _st())
+                  _lib.ptr(c["e"]), _lib.ptr(tabs[0]), _lib.ptr(tabs[1]), _lib.ptr(out), C, outer << 8, _st())
     else:
         _lib.call("ivit_layernorm_i8_ex", _lib.ptr(x8), C, rows, C, _lib.ptr(c["bias"]), _lib.ptr(c["s"]), _lib.ptr(c["m"]),
                   _lib.ptr(c["e"]), _lib.ptr(out), C, 0, _st())
@@ -627,6 +1103,8 @@ def _resolve_attention(node, s_pv, s_out, device):
     if not (isinstance(P, QT) and isinstance(P.node, Probs) and not P.views and isinstance(v, QT)):
         return None
     sc_qt = P.node.x
+    if isinstance(sc_qt.node, (Biased, Masked)):
+        return _resolve_window_attention(P, sc_qt, v, s_pv, s_out, device)
     sc = sc_qt.node
     scaled = sc.x.node if isinstance(sc.x.node, Scaled) else None
     mm = scaled.x.node if scaled is not None else sc.x.node
@@ -706,6 +1184,114 @@ def _resolve_attention(node, s_pv, s_out, device):
     return out.view(B, T, H, hd).permute(0, 2, 1, 3)
 
 
+def _mask_regions(mask, nW, N):
+    """region ids [nW, N] of a float shift mask that is exactly where(region_i != region_j, -100, 0) (swin_quant.py:223-246), else
+    None.  One read-back, at the warm-up forward."""
+    if mask.numel() != nW * N * N:
+        return None
+    m = mask.detach().reshape(nW, N, N).cpu().numpy()
+    if not np.all((m == 0) | (m == f32(-100.0))):
+        return None
+    same = m == 0
+    region = np.argmax(same, axis=1)               # first token every token shares a region with
+    if not np.array_equal(same, region[:, :, None] == region[:, None, :]):
+        return None
+    return region.astype(np.uint8)
+
+
+def _resolve_window_attention(P, top, v, s_pv, s_out, device):
+    """WindowAttention (swin_quant.py:137-161): matmul_1 -> * scale -> qact_attn1 -> qact2 with the relative position bias ->
+    (+ mask) -> Shiftmax -> matmul_2 behind qact3, as one launch of the ivit_window_attention_i8* family, selected as
+    swin_engine.IntSwinEngine selects it (window order out)"""
+    from ..swin_engine import HEAD_DIM, LONG_WINDOW, key_pad, window_attention_spec
+    sm = P.node.mod
+    if type(sm).__name__ != "IVITIntSoftmax" or sm.output_bit != 8:
+        return None
+    mask = None
+    if isinstance(top.node, Masked):
+        if not _reshapes_only(top.views):
+            return None
+        mask, biased = top.node.mask, top.node.x
+    else:
+        if top.views:
+            return None
+        biased = top
+    bn = biased.node
+    sc = bn.x.node
+    if not isinstance(sc, Scores) or bn.x.views:
+        return None
+    scaled = sc.x.node if isinstance(sc.x.node, Scaled) else None
+    if scaled is None or scaled.x.views:
+        return None
+    mm = scaled.x.node
+    if not (isinstance(mm, ModNode) and mm.kind == "matmul"):
+        return None
+    s_mm = host_of(mm.out_scale)
+    if s_mm is None or not np.array_equal(sc.s_in, (s_mm * f32(scaled.c)).astype(f32)):
+        return None
+    q, kT = mm.inputs
+    if not (isinstance(q, QT) and isinstance(kT, QT)) or len(q.shape) != 4:
+        return None
+    B_, nH, N, hd = q.shape
+    if hd != HEAD_DIM or not 2 <= N <= LONG_WINDOW or tuple(top.shape) != (B_, nH, N, N) or tuple(v.shape) != (B_, nH, N, hd):
+        return None
+    ws = int(round(N ** 0.5))
+    if N > 64 and ws * ws != N:
+        return None
+    nW = 1
+    if mask is not None:
+        nW = mask.shape[1]
+        if tuple(mask.shape) != (1, nW, 1, N, N) or B_ % nW or tuple(biased.shape) != (B_ // nW, nW, nH, N, N):
+            return None
+    # ---- constants: once per (bias table version and path, mask tensor, ranges, device)
+    ident = bn.identity
+    s_S, s_at, s_tab, s_A = sc.s_in, sc.s_out, bn.s_id, bn.s_out
+    mkey = None if mask is None else _sig("mask", (mask,), {})
+
+    def build():
+        i8 = ident.q8                          # the bias integers as the model code gathered them: read back once
+        if i8 is None or i8.numel() != nH * N * N:
+            return None
+        bias = i8.reshape(nH, N, N).cpu().numpy().astype(np.int32)
+        region = None
+        if mask is not None:
+            region = _mask_regions(mask, nW, N)
+            if region is None:
+                return None
+        spec, _ = window_attention_spec(lambda a: _dev(a, device), bias, s_tab, s_S, s_at, s_A, s_pv, s_out, region, N)
+        return spec
+    a = _cache(bn.qact, ("wattn", ident.origin, mkey, _key(s_S, np.asarray(s_at), s_tab, np.asarray(s_A), s_pv, np.asarray(s_out)),
+                         str(device)), build)
+    if a is None:
+        return None
+    # ---- q, k, v head-major per window
+    hm = q.node.head_major(q, kT, v, head_dim=HEAD_DIM, max_tokens=LONG_WINDOW, frags=False) if isinstance(q.node, Requant) else None
+    if hm is None:
+        if q.q8 is None or kT.q8 is None or v.q8 is None:
+            return None
+        hm = torch.empty(3, B_, nH, N, hd, dtype=torch.int8, device=device)
+        hm[0].copy_(q.q8)
+        hm[1].copy_(kT.q8.transpose(-2, -1))
+        hm[2].copy_(v.q8)
+    C = nH * hd
+    out = torch.empty(B_ * N, C, dtype=torch.int8, device=device)
+    band = a["band"]
+    if a["long"]:
+        _lib.call("ivit_window_attention_i8_long", _lib.ptr(hm), _lib.ptr(out), C, _lib.ptr(a["bias"]), _lib.ptr(a["region"]),
+                  a["mask_value"], B_, nW, nH, N, hd, a["ms"][0], a["ms"][1], a["mb"][0], a["mb"][1], a["s_attn"], a["mo"][0], a["mo"][1],
+                  _lib.ptr(None if band is not None else a["phi"]), _lib.ptr(None if band is not None else a["phim"]), _lib.ptr(band),
+                  a["band_w"], 0 if band is None else int(band.shape[0]), ws * nW, ws, ws, 0, 0, _st())
+    elif band is not None:
+        _lib.call("ivit_window_attention_i8_band", _lib.ptr(hm), _lib.ptr(out), C, _lib.ptr(a["bias"]), _lib.ptr(a["region"]), B_, nW, nH,
+                  N, hd, a["ms"][0], a["ms"][1], a["mb"][0], a["mb"][1], a["s_attn"], a["mo"][0], a["mo"][1], _lib.ptr(band), a["band_w"],
+                  int(band.shape[0]), 0, 0, 0, 0, _st())
+    else:
+        _lib.call("ivit_window_attention_i8_compat", _lib.ptr(hm), _lib.ptr(out), C, _lib.ptr(a["bias"]), _lib.ptr(a["region"]),
+                  a["mask_value"], B_, nW, nH, N, hd, a["ms"][0], a["ms"][1], a["mb"][0], a["mb"][1], a["s_attn"], a["mo"][0], a["mo"][1],
+                  _lib.ptr(a["phi"]), _lib.ptr(a["phim"]), _st())
+    return out.view(B_, N, nH, hd).permute(0, 2, 1, 3)
+
+
 def _resolve_cat(qact, node, s_in, identity, identity_sf, s_out, device):
     """qact1(cat(cls_token, patches), s, pos, s_pos) (vit_quant.py:293-297): the raw float rows go through round(x / s), the
     int8 part is widened, then the two-operand requantisation"""
@@ -748,14 +1334,18 @@ def linear_to_float(lin, x, s_in_qs):
         return None
     c = linear_consts(lin, s_in, a8.device)
     N, K = c["N"], c["K"]
-    if K % 64 != 0:
-        return None
     Np = (N + 3) // 4 * 4
+    W, b = c["W"], c["b"]
+    if Np != N:          # the GEMM wants N % 4 == 0: zero rows, sliced off again below (as QuantLinear._params does)
+        if "Wp" not in c:
+            c["Wp"] = torch.cat([W, torch.zeros(Np - N, K, dtype=W.dtype, device=W.device)])
+            c["bp"] = None if b is None else torch.cat([b, torch.zeros(Np - N, dtype=b.dtype, device=b.device)])
+        W, b = c["Wp"], c["bp"]
+    a2 = _operand(a8.reshape(-1, c["Kin"]), c)
+    acc = torch.empty(a2.shape[0], Np, dtype=torch.int32, device=a8.device)
+    _lib.call("ivit_gemm_i8_i32", _lib.ptr(a2), K, _lib.ptr(W), K, _lib.ptr(b), _lib.ptr(acc), Np, a2.shape[0], Np, K, _st())
     if Np != N:
-        return None
-    a2 = a8.reshape(-1, K)
-    acc = torch.empty(a2.shape[0], N, dtype=torch.int32, device=a8.device)
-    _lib.call("ivit_gemm_i8_i32", _lib.ptr(a2), K, _lib.ptr(c["W"]), K, _lib.ptr(c["b"]), _lib.ptr(acc), N, a2.shape[0], N, K, _st())
+        acc = acc[:, :N].contiguous()
     y = torch.empty(acc.shape, dtype=torch.float32, device=a8.device)
     s = c["s_acc"].as_subclass(torch.Tensor)
     _lib.call("ivit_i32_to_f32", _lib.ptr(acc), acc.shape[0], N, _lib.ptr(s), N, _lib.ptr(y), _st())

@@ -240,7 +240,7 @@ class QuantLinear(nn.Linear):
     def forward(self, x, prev_act_scaling_factor=None):
         if isinstance(x, lazy.QT):
             s_in = lazy.host_of(prev_act_scaling_factor)
-            if x.q8 is not None and s_in is not None and s_in.size == 1 and self.in_features % 64 == 0:
+            if x.q8 is not None and s_in is not None and s_in.size == 1 and self.in_features % 16 == 0:
                 # int8-carrying input of a frozen model: nothing runs here; the QuantAct behind launches GEMM + requantisation
                 c = lazy.linear_consts(self, s_in, x.device)
                 return lazy.pending("linear", self, (*x.shape[:-1], self.out_features), x.device, (x,),
@@ -331,18 +331,25 @@ class QuantAct(nn.Module):
     def _fast(self, x, pre_sf, identity, identity_sf):
         """frozen 8-bit QuantAct of an int8-carrying forward (lazy.py): int8 out, one fused launch, nothing read back"""
         if pre_sf is None:
-            if isinstance(x, lazy.QT) or identity is not None or not x.is_cuda:
+            if isinstance(x, lazy.QT) or identity is not None or not x.is_cuda or self.activation_bit != 8:
                 return None
             s_out, qs, plain = self._frozen_scale(x.device)
             xin = x.detach().contiguous().float()
             q8 = torch.empty(xin.shape, dtype=torch.int8, device=x.device)
             _lib.call("ivit_quantize_input_f32_i8", _lib.ptr(xin), _lib.ptr(q8), xin.numel(), float(f32(1.0) / s_out), _st())
             self.act_scaling_factor = plain
-            return lazy.QT.wrap(q8.shape, x.device, q8=q8, scale=qs), qs
-        if not isinstance(x, lazy.QT):
-            return None
+            # a parameter (WindowAttention's relative position bias table): what it is and what is done to it since stays known,
+            # so that the QuantAct it becomes the identity of can cache its integers
+            origin = (id(x), x._version, float(s_out)) if isinstance(x, nn.Parameter) else None
+            return lazy.QT.wrap(q8.shape, x.device, q8=q8, scale=qs, origin=origin), qs
         s_out, qs, plain = self._frozen_scale(x.device)
-        r = lazy.resolve(self, x, pre_sf, identity, identity_sf, s_out, qs)
+        if not isinstance(x, lazy.QT):
+            # a float tensor behind a known scale (Swin's qact3 behind the float pooling)
+            r = lazy.resolve_float(self, x, pre_sf, s_out, qs) if (identity is None and x.is_cuda and self.activation_bit == 8) else None
+        elif self.activation_bit == 16:
+            r = lazy.resolve16(self, x, pre_sf, identity, identity_sf, s_out, qs)
+        else:
+            r = lazy.resolve(self, x, pre_sf, identity, identity_sf, s_out, qs)
         if r is None:
             return None
         self.act_scaling_factor = plain
@@ -350,7 +357,7 @@ class QuantAct(nn.Module):
 
     def forward(self, x, pre_act_scaling_factor=None, identity=None, identity_scaling_factor=None,
                 specified_min=None, specified_max=None):
-        if (lazy.active() and not self.running_stat and self.activation_bit == 8 and specified_min is None
+        if (lazy.active() and not self.running_stat and self.activation_bit in (8, 16) and specified_min is None
                 and specified_max is None):
             r = self._fast(x, pre_act_scaling_factor, identity, identity_scaling_factor)
             if r is not None:
@@ -500,7 +507,7 @@ class QuantConv2d(nn.Conv2d):
             s_in = lazy.host_of(pre_act_scaling_factor)
             kh, kw = self.kernel_size
             K = self.in_channels * kh * kw
-            if (x.q8 is not None and s_in is not None and s_in.size == 1 and K % 64 == 0 and self.groups == 1
+            if (x.q8 is not None and s_in is not None and s_in.size == 1 and K % 16 == 0 and self.groups == 1
                     and self.dilation == (1, 1) and self.bias is not None and x.dim() == 4
                     and kh == kw == self.stride[0] == self.stride[1] and self.padding == (0, 0)
                     and x.shape[2] % kh == 0 and x.shape[3] % kw == 0):

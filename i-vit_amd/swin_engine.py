@@ -90,6 +90,61 @@ def window_row_map(B: int, H: int, W: int, ws: int, shift: int) -> np.ndarray:
     return (np.arange(B)[:, None] * (H * W) + idx.reshape(-1)[None, :]).reshape(-1)
 
 
+def window_attention_spec(upload, bias, s_tab, s_S, s_at, s_A, s_pv, s_a3, region, N):
+    """Constants of one window-attention launch (the ivit_window_attention_i8* family), shared by the engine and the module path
+    (quantization_utils/lazy.py).  bias: the 8-bit relative position bias [nH, N, N] at scale s_tab (the identity operand of
+    attn.qact2, swin_quant.py:143-147); s_S the scale the scores arrive with, s_at / s_A the scales of qact_attn1 / qact2, s_pv /
+    s_a3 those around qact3; region [nW, N] the region ids of a shifted block's mask, or None.
+    -> (dict of launch arguments, form): form is None on the integer kernel, else the natural-scale Shiftmax form ("band1xW" /
+    "band256xW" / "literal", prepare.window_shiftexp_band)."""
+    nH = bias.shape[0]
+
+    def sme(pre, z):
+        m, e = dyadic(pre, z)
+        return int(m[0]), int(e[0])
+
+    m2, e2 = dyadic(s_tab, s_A)
+    bias_add = requant_host(bias, m2[0], e2[0])                    # identity operand of qact2, :143-147
+    assert np.abs(bias_add).max() < 32768
+    kp = key_pad(N)
+    bias_pad = np.zeros((nH, N, kp), np.int16)
+    bias_pad[:, :, :N] = bias_add
+    region_pad, mask_value = None, 0
+    # Shiftmax input: phi(q) = fl(fl(q*s)/s) for a plain score, fl(fl(fl(q*s) - 100)/s) for one under the shift
+    # mask (:149-156 adds float -100 to q*s, ivit_modules.py:165 divides by s).  Integer kernel when phi is the
+    # identity and -100/s an integer; else the literal float sequence on the two 256-entry tables
+    qv = np.arange(-128, 128, dtype=f32)
+    phi_m = ((((qv * s_A).astype(f32) + f32(-100.0)).astype(f32)) / s_A).astype(f32)
+    att_nat = not phi_is_identity(s_A)
+    if region is not None:
+        mval = f32(-100.0) / s_A                                    # :149-155: (k*s + (-100)) / s
+        if mval != np.rint(mval) or abs(mval) >= 32768:
+            att_nat = True
+            mask_value = -1                                         # unused by the literal form
+        else:
+            mask_value = int(mval)
+        # the integer form of the short entries reads Shiftmax's exp_int from a table over the 256 distances to the row maximum and
+        # gives a masked score (|mask_value| or more below it) the LAST entry: right only if the table has saturated by then, i.e.
+        # -d - floor(d / 2) + floor(d / 16) <= 15 x0 for some d <= 255 (ivit_modules.py:151-155; x0 = floor(-1 / s) <= -25 never
+        # does).  Otherwise the literal form, which is exact at any scale
+        x0 = int(np.floor(f32(-1.0) / s_A))
+        if N <= SHORT_WINDOW and not any(-d + (-d >> 1) - (-d >> 4) <= 15 * x0 for d in range(256)):
+            att_nat = True
+        region_pad = np.zeros((region.shape[0], kp), np.uint8)
+        region_pad[:, :N] = region
+    band, band_w, form = None, 0, None
+    if att_nat:
+        # table form of the natural-scale Shiftmax where it is provably what the reference computes (every masked score
+        # saturated, no masked row maximum); else the kernel's literal float sequence on phi / phi_m
+        band, band_w = window_shiftexp_band(s_A, region is not None)
+        form = "literal" if band is None else f"band{band.shape[0]}x{band_w}"
+    spec = dict(ms=sme(s_S, s_at), mb=sme(s_at, s_A), s_attn=float(s_A), mo=sme(s_pv, s_a3),
+                bias=upload(bias_pad), region=None if region_pad is None else upload(region_pad),
+                mask_value=mask_value, phi=upload(phi_table(s_A)) if att_nat else None, phim=upload(phi_m) if att_nat else None,
+                band=None if band is None else upload(band), band_w=band_w, long=N > SHORT_WINDOW)
+    return spec, form
+
+
 def pool_literal_host(q: np.ndarray, s: float) -> np.ndarray:
     """Host restatement of ivit_avgpool_requant_i8_literal's float32 mean (csrc/swin.hip, rowsum.h torch_outer_rowsum): q int8
     [B, T, C], s the input scale -> float32 [B, C], torch's CPU mean over the transposed view of y = fl(q * s) (serial order)."""
@@ -220,43 +275,15 @@ class IntSwinEngine(EngineBase):
                 s_tab = s(p + "attn.qact_table")
                 s_A = s(p + "attn.qact2")
                 ktab = quant_sym(P[p + "attn.relative_position_bias_table"], s_tab, 8)   # [(2ws-1)^2, nH]
-                m2, e2 = dyadic(s_tab, s_A)
                 bias = ktab[rel_position_index(win).reshape(-1)].reshape(N, N, nH).transpose(2, 0, 1)
-                bias_add = requant_host(bias, m2[0], e2[0])                    # identity operand of qact2, :143-147
-                assert np.abs(bias_add).max() < 32768
-                kp = key_pad(N)
-                bias_pad = np.zeros((nH, N, kp), np.int16)
-                bias_pad[:, :, :N] = bias_add
-                region, mask_value = None, 0
-                # Shiftmax input: phi(q) = fl(fl(q*s)/s) for a plain score, fl(fl(fl(q*s) - 100)/s) for one under the shift
-                # mask (:149-156 adds float -100 to q*s, ivit_modules.py:165 divides by s).  Integer kernel when phi is the
-                # identity and -100/s an integer; else the literal float sequence on the two 256-entry tables
-                qv = np.arange(-128, 128, dtype=f32)
-                phi_m = ((((qv * s_A).astype(f32) + f32(-100.0)).astype(f32)) / s_A).astype(f32)
-                att_nat = not phi_is_identity(s_A)
-                if shift:
-                    mval = f32(-100.0) / s_A                                    # :149-155: (k*s + (-100)) / s
-                    if mval != np.rint(mval) or abs(mval) >= 32768:
-                        att_nat = True
-                        mask_value = -1                                         # unused by the literal form
-                    else:
-                        mask_value = int(mval)
-                    region = np.zeros(((H // win) * (W // win), kp), np.uint8)
-                    region[:, :N] = shift_mask_regions(H, W, win, shift)
-                band, band_w = (None, 0)
-                if att_nat:
-                    self.natural_sites += 1
-                    # table form of the natural-scale Shiftmax where it is provably what the reference computes (every masked score
-                    # saturated, no masked row maximum); else the kernel's literal float sequence on phi / phi_m
-                    band, band_w = window_shiftexp_band(s_A, bool(shift))
-                    self.window_softmax_forms.append("literal" if band is None else f"band{band.shape[0]}x{band_w}")
+                region = shift_mask_regions(H, W, win, shift) if shift else None
                 s_pv = f32(f32(1.0 / 128.0) * s_a1)
                 s_a3 = s(p + "attn.qact3")
-                blk["attn"] = dict(ms=sme(s_S, s_at), mb=sme(s_at, s_A), s_attn=float(s_A), mo=sme(s_pv, s_a3),
-                                   bias=dev(bias_pad), region=None if region is None else dev(region),
-                                   mask_value=mask_value, nW=(H // win) * (W // win),
-                                   phi=dev(phi_table(s_A)) if att_nat else None, phim=dev(phi_m) if att_nat else None,
-                                   band=None if band is None else dev(band), band_w=band_w, long=N > SHORT_WINDOW)
+                blk["attn"], form = window_attention_spec(dev, bias, s_tab, s_S, s_at, s_A, s_pv, s_a3, region, N)
+                blk["attn"]["nW"] = (H // win) * (W // win)
+                if form is not None:
+                    self.natural_sites += 1
+                    self.window_softmax_forms.append(form)
                 lp, d = lin_host(p + "attn.proj", s_a3)
                 s_a4 = s(p + "attn.qact4", 16)
                 mp, ep = dyadic(lp.s_acc, s_a4)

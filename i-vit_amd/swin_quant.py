@@ -21,7 +21,7 @@ from torch import nn
 
 from .dispatch import EngineDispatch
 from .layers_quant import DropPath, Mlp, PatchEmbed, to_2tuple, trunc_normal_
-from .quantization_utils import IntGELU, IntLayerNorm, IntSoftmax, QuantAct, QuantLinear, QuantMatMul
+from .quantization_utils import IntGELU, IntLayerNorm, IntSoftmax, QuantAct, QuantLinear, QuantMatMul, lazy
 
 __all__ = ["swin_tiny_patch4_window7_224", "swin_small_patch4_window7_224", "swin_base_patch4_window7_224",
            "SwinTransformer", "window_partition", "window_reverse"]
@@ -294,6 +294,8 @@ class SwinTransformer(EngineDispatch, nn.Module):
             return "no classification head"
         if any(int(self.embed_dim * 2 ** i) // h != 32 for i, h in enumerate(self.num_heads)):
             return "head_dim != 32"
+        if self.num_features % 64:
+            return f"{self.num_features} features at the classifier (fused engine: a multiple of 64)"
         for n, m in self._quant_acts():
             if int(m.activation_bit) != self._reference_widths[n]:
                 return f"QuantAct {n} is {int(m.activation_bit)}-bit (fused engine: {self._reference_widths[n]})"
@@ -317,9 +319,11 @@ class SwinTransformer(EngineDispatch, nn.Module):
             return logits_f32.clone()
         if not self.is_frozen():
             self.invalidate_engine()
-        x, s = self.forward_features(x)
-        x, _ = self.head(x, s)
-        return x
+        # a frozen model run module by module carries int8 / int16 between its modules (quantization_utils/lazy.py)
+        with lazy.scope(x.is_cuda and not self.training and self.is_frozen()):
+            x, s = self.forward_features(x)
+            x, _ = self.head(x, s)
+        return x.to_float(boundary=True) if isinstance(x, lazy.QT) else x
 
 
 def _factory(embed_dim, depths, num_heads, name):

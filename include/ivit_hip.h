@@ -474,6 +474,16 @@ int ivit_layernorm_i16_i8_compat(const int16_t* x, int rows, int C, float s_in, 
  * channel blocks (even y, even x), (odd y, even x), (even y, odd x), (odd y, odd x). */
 int ivit_patch_merge_i16(const int16_t* x, int16_t* out, int batch, int H, int W, int C, ivit_stream_t stream);
 
+/* Window partition + cyclic shift of whole rows (swin_quant.py:258-271: reshape(B, H, W, C), roll by -shift, window_partition),
+ * or the way back (window_reverse, roll by +shift, :281-289), for rows of row_bytes bytes of any element type (int8 rows of C
+ * bytes, int16 rows of 2C bytes): src, dst [batch * H * W, row_bytes].
+ *   inverse = 0: dst row (b, wy, wx, iy, ix), window order, = src row (b, (wy ws + iy + shift) % H, (wx ws + ix + shift) % W)
+ *   inverse = 1: dst row (b, (wy ws + iy + shift) % H, (wx ws + ix + shift) % W) = src row (b, wy, wx, iy, ix)
+ * Refused: NULL pointers or pointers not aligned to 16 bytes, row_bytes % 16 != 0, H % ws or W % ws != 0, shift outside [0, ws),
+ * overlapping src and dst (src == dst among them: the pass is not in place). */
+int ivit_window_rows(const void* src, void* dst, int batch, int H, int W, int64_t row_bytes, int ws, int shift, int inverse,
+                     ivit_stream_t stream);
+
 /* AdaptiveAvgPool1d over the tokens + qact3 (swin_quant.py:554-555):
  *   out[b][c] = clamp8(RNE(round(fl32(sum_t x[b][t][c] / tokens)) * m / 2^e)) */
 int ivit_avgpool_requant_i8(const int8_t* x, int8_t* out, int batch, int tokens, int C, uint32_t m, int32_t e,
@@ -498,7 +508,9 @@ int ivit_avgpool_requant_i8_literal(const int8_t* x, int8_t* out, int batch, int
  *            as the reference adds the float mask to the fake-quantised scores (:149-155, 243-246)
  *   (m_s,e_s): q.k^T -> qact_attn1;  (m_b,e_b): qact_attn1 -> qact2;  s_attn: scale of qact2 (Shiftmax input);
  *   (m_o,e_o): P.v -> qact3.
- * Supported: head_dim 32, 2 <= tokens <= 64. */
+ * Supported: head_dim 32, 2 <= tokens <= 64; with a mask, s_attn >= 1 / 24 (x0 = floor(-1 / s_attn) >= -24: the exponent table
+ * over the 256 distances to the row maximum has saturated by its last entry, which masked scores take) -- below that the
+ * entry refuses and the literal form of ivit_window_attention_i8_compat applies (exact at any scale). */
 int ivit_window_attention_i8(const int8_t* qkv, int8_t* out, int64_t ldo, const int16_t* bias_add,
                              const uint8_t* mask_region, int mask_value, int windows, int windows_per_image, int heads,
                              int tokens, int head_dim, uint32_t m_s, int32_t e_s, uint32_t m_b, int32_t e_b,
