@@ -27,8 +27,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .engine_common import EngineBase, _np, block_copy, frag_copy, layernorm
-from .prepare import dyadic, f32, pad_head, phi_tables, quant_sym, requant_host, shiftexp2d, shiftexp_band
+from .engine_common import EngineBase, _np, attention, attention_spec, block_copy, frag_copy, layernorm
+from .prepare import dyadic, dyadic1, f32, pad_head, quant_sym, requant_host
 from .topk import TOPK_MAX
 
 
@@ -91,15 +91,6 @@ class IntViTEngine(EngineBase):
             m, e = lp.requant_to(s_out)
             return dict(W=dev(lp.W8), b=dev(lp.b32), m=dev(m.view(np.int32)), e=dev(e), K=lp.K, N=lp.W8.shape[0])
 
-        def phi_dev(s_in):
-            """natural (non power-of-two) scale of an operator's input: the reference's operator sees phi(q) = fl(fl(q*s)/s),
-            not q (prepare.py).  -> (remap int8[256], phi f32[256]) on the device, or (None, None) when phi is the identity"""
-            t = phi_tables(s_in)
-            if t is None:
-                return None, None
-            self.natural_sites += 1
-            return dev(t[0]), dev(t[1])
-
         def ln_dev(prefix, s_out, s_in):
             shift = None
             if family == "ibert":
@@ -108,10 +99,6 @@ class IntViTEngine(EngineBase):
                 except KeyError:
                     shift = 0.0
             return self._ln_spec(source.layernorm(prefix, s_out), s_in, sb, shift)
-
-        def scalar_me(pre, z):
-            m, e = dyadic(pre, z)
-            return int(m[0]), int(e[0])
 
         def ranges_of(name):
             if ranges is None or name not in ranges:
@@ -158,56 +145,23 @@ class IntViTEngine(EngineBase):
             s_at = s(p + "attn.qact_attn1")
             s_pv = f32(f32(1.0 / 2 ** (softmax_bits - 1)) * s_a1)         # Shiftmax scale 2^-(bits-1) (:176) x value scale
             s_a2 = s(p + "attn.qact2")
-            blk["attn"] = dict(ms=scalar_me(s_S, s_at), s_attn=float(s_at), mo=scalar_me(s_pv, s_a2), exp2d=None, band=None, band_w=0)
-            if family == "ibert":
-                # IBERTIntSoftmax (output_bit 8, scale 2 / 2^8 = 2^-7 like Shiftmax's): exp_int after its internal 16-bit
-                # QuantAct, tabulated over (row max, q) with the reference's float32 sequence (csrc/ibert.hip)
-                from .quantization_utils.ibert_modules import softmax_constants
-                lo, hi = ranges_of(p + "attn.int_softmax.act")
-                x0i, bi, ci, exp_sf, act_sf, ma, ea = softmax_constants(s_at, lo, hi)
-                tab = torch.empty(65536, dtype=torch.float32, device=self.dev)
-                _lib.call("ivit_ibert_softmax_build_table", float(s_at), x0i, bi, ci, float(exp_sf), float(act_sf), ma, ea,
-                          _lib.ptr(tab), self._stream())
-                blk["attn"]["ib_table"] = tab
-                # band form (LDS path) when the exponent saturates within 128 steps of the row maximum
-                band, bw = shiftexp_band(tab.cpu().numpy().view(np.uint32).reshape(256, 256))
-                if bw and bw <= 128:
-                    blk["attn"].update(band=dev(band.view(np.float32)), band_w=bw)
-            elif phi_tables(s_at) is not None:       # Shiftmax on phi(q): exponent tabulated over (row max, q)
-                self.natural_sites += 1
-                tab = shiftexp2d(s_at)
-                band, bw = shiftexp_band(tab)
-                if bw and bw <= 128:               # band rows staged in LDS per query tile (34 KB per workgroup at width 128)
-                    blk["attn"].update(band=dev(band.view(np.int32)), band_w=bw)
-                else:                              # very fine input scale: full-table gather
-                    blk["attn"]["exp2d"] = dev(tab.view(np.int32))
+            blk["attn"] = a = attention_spec(family, s_S, s_at, s_pv, s_a2, dev, self.dev, self._stream(),
+                                             ranges_of(p + "attn.int_softmax.act") if family == "ibert" else None)
+            self.natural_sites += int(family == "ivit" and (a["band"] is not None or a["exp2d"] is not None))
             s_a3 = s(p + "attn.qact3", sb)
             blk["proj"] = lin_dev(source.linear(p + "attn.proj", s_a2), s_a3)
             s_b2 = s(p + "qact2", sb)
-            blk["res1"] = scalar_me(s_a3, s_b2) + scalar_me(s_x, s_b2)
+            blk["res1"] = dyadic1(s_a3, s_b2) + dyadic1(s_x, s_b2)
             s_b3 = s(p + "qact3")
             blk["ln2"] = ln_dev(p + "norm2", s_b3, s_b2)
             s_g = s(p + "mlp.qact_gelu")
             blk["fc1"] = lin_dev(source.linear(p + "mlp.fc1", s_b3), s_g)
             s_m1 = s(p + "mlp.qact1")
-            lut = torch.empty(65536, dtype=torch.int8, device=self.dev)
-            if family == "ibert":
-                # IBERTIntGELU + mlp.qact1 depend on q alone: one 256-entry map, replicated over the table's row-max axis.  Its
-                # output scale is negative (ibert_modules.py:213, 232): requant(z, s) == requant(-z, -s) (quant_modules.QuantAct)
-                from .quantization_utils.ibert_modules import gelu_constants
-                gb, gc, gsh, gso = gelu_constants(s_g)
-                mg, eg = scalar_me(abs(f32(gso)), s_m1)
-                _lib.call("ivit_ibert_gelu_build_lut", float(s_g), gb, gc, gsh, float(gso), mg, eg, _lib.ptr(lut), self._stream())
-            else:
-                s_go = f32(s_g * f32(1.0 / 128.0))                             # ivit_modules.py:121,124
-                mg, eg = scalar_me(s_go, s_m1)
-                g_remap, _ = phi_dev(s_g)              # ShiftGELU sees trunc(phi(q)) (ivit_modules.py:106-107)
-                _lib.call("ivit_shiftgelu_build_lut_ex", float(s_g), mg, eg, _lib.ptr(g_remap), _lib.ptr(lut), self._stream())
-            blk["gelu_lut"] = lut
+            blk["gelu_lut"] = self._gelu_lut(family, s_g, s_m1)
             s_m2 = s(p + "mlp.qact2", sb)
             blk["fc2"] = lin_dev(source.linear(p + "mlp.fc2", s_m1), s_m2)
             s_b4 = s(p + "qact4", sb)
-            blk["res2"] = scalar_me(s_m2, s_b4) + scalar_me(s_b2, s_b4)
+            blk["res2"] = dyadic1(s_m2, s_b4) + dyadic1(s_b2, s_b4)
             s_x = s_b4
             self.blocks.append(blk)
 
@@ -450,19 +404,8 @@ class IntViTEngine(EngineBase):
             _lib.call("ivit_gemm_i8_requant_qkv_ex", _lib.ptr(ws["h"]), C, qw, q["K"], _lib.ptr(q["b"]),
                       _lib.ptr(q["m"]), _lib.ptr(q["e"]), _lib.ptr(ws["qkv"]), T, H, hd, M, 3 * C, C, qlay | int(a_ln), st)
             tap(p + "attn.qkv_headmajor", ws["qkv"], (3, B, H, T, hd))
-            a = blk["attn"]
-            # the 16-bit stream's "wide" forms take softmax_bits before the layout flag
-            sm = (self.softmax_bits,) if wide else ()
-            if self.family == "ibert":
-                _lib.call("ivit_attention_fused_i8_ibert_wide" if wide else "ivit_attention_fused_i8_ibert", _lib.ptr(ws["qkv"]),
-                          _lib.ptr(ws["ao"]), B, H, T, hd, a["ms"][0], a["ms"][1], a["mo"][0], a["mo"][1], _lib.ptr(a["ib_table"]),
-                          _lib.ptr(a["band"]), a["band_w"], *sm, int(a_at), st)
-            else:
-                name = "ivit_attention_fused_i8_wide" if wide else ("ivit_attention_fused_i8_long" if T > 207 else
-                                                                     "ivit_attention_fused_i8_compat_band")
-                _lib.call(name, _lib.ptr(ws["qkv"]),
-                          _lib.ptr(ws["ao"]), B, H, T, hd, a["ms"][0], a["ms"][1], a["s_attn"], a["mo"][0], a["mo"][1],
-                          _lib.ptr(a["exp2d"]), _lib.ptr(a["band"]), a["band_w"], *sm, int(a_at), st)
+            attention(blk["attn"], self.family, ws["qkv"], ws["ao"], B, H, T, hd, st, blocks=a_at,
+                      softmax_bits=self.softmax_bits if wide else None)
             tap(p + "attn.qact2", ws["ao"], (B, T, C), a_at)
             self._gemm_res(ws["ao"], C, blk["proj"], x, blk["res1"], x2, M, st, blocks=blk_l, a_blocks=a_at)
             tap(p + "qact2", x2, (B, T, C))

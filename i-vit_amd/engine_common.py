@@ -1,5 +1,8 @@
 """Host code shared by the fused engines (engine.IntViTEngine, swin_engine.IntSwinEngine) and the module path
-(quantization_utils/lazy.py): device uploads, the LayerNorm specs and their one launcher, and the GEMM weight copies."""
+(quantization_utils/lazy.py), written once per operator: the GEMM weight copies (block_copy, frag_copy); the LayerNorm constants
+and their launcher (ln_spec, layernorm); the ViT attention constants and their launcher (attention_spec, attention); the GELU
+table of both families (gelu_lut); what the two engines share as classes (EngineBase).  Window attention's pair
+(window_attention_spec, window_attention) lives in swin_engine.py; the scalar dyadic pair is prepare.dyadic1."""
 from __future__ import annotations
 
 import numpy as np
@@ -7,7 +10,8 @@ import torch
 
 from . import _lib
 from .graph import GraphReplay
-from .prepare import IMAGENET_MEAN, IMAGENET_STD, input_lut_u8, markstein_division_ok, phi_is_identity, phi_tables
+from .prepare import (IMAGENET_MEAN, IMAGENET_STD, dyadic1, f32, input_lut_u8, markstein_division_ok, phi_is_identity, phi_tables,
+                      shiftexp2d, shiftexp_band)
 from .topk import HeadTopK
 
 
@@ -96,6 +100,75 @@ def layernorm(ln, x, ldx, rows, C, out, ldo, st, blocks=None, H=0, W=0, ws=0, sh
         raise ValueError(f"LayerNorm kind {kind!r}")
 
 
+# ----------------------------------------------------------------------------------------------------------- ViT attention
+def attention_spec(family, s_S, s_at, s_pv, s_out, upload, device, st, ibert_range=None) -> dict:
+    """Device constants of one fused ViT attention (vit_quant.py:72-82).  s_S: the scale the scores arrive with, s_at that of
+    qact_attn1, s_pv / s_out those around qact2.  -> ms, mo (the two requantisations), s_attn, and Softmax's exponent as a table
+    where it needs one:
+      family "ivit", natural s_at: Shiftmax on phi(q), tabulated over (row max, q) -- `band` / `band_w` (rows staged in LDS per query
+        tile, 34 KB per workgroup at width 128) when the exponent saturates within 128 steps of the row maximum, else `exp2d`, the
+        full-table gather of a very fine input scale;
+      family "ibert": IBERTIntSoftmax (output_bit 8, scale 2 / 2^8 = 2^-7 like Shiftmax's) -- exp_int after its internal 16-bit
+        QuantAct of range ibert_range = (x_min, x_max), tabulated over (row max, q) with the reference's float32 sequence
+        (csrc/ibert.hip) in `ib_table`, its band form as above, and `act_sf`, that QuantAct's scale."""
+    d = dict(ms=dyadic1(s_S, s_at), s_attn=float(s_at), mo=dyadic1(s_pv, s_out), exp2d=None, band=None, band_w=0)
+    if family == "ibert":
+        from .quantization_utils.ibert_modules import softmax_constants
+        x0i, bi, ci, exp_sf, act_sf, ma, ea = softmax_constants(s_at, *ibert_range)
+        tab = torch.empty(65536, dtype=torch.float32, device=device)
+        _lib.call("ivit_ibert_softmax_build_table", float(s_at), x0i, bi, ci, float(exp_sf), float(act_sf), ma, ea, _lib.ptr(tab), st)
+        d.update(ib_table=tab, act_sf=float(act_sf))
+        band, bw = shiftexp_band(tab.cpu().numpy().view(np.uint32).reshape(256, 256))
+        if bw and bw <= 128:
+            d.update(band=upload(band.view(np.float32)), band_w=bw)
+    elif phi_tables(s_at) is not None:
+        tab = shiftexp2d(s_at)
+        band, bw = shiftexp_band(tab)
+        if bw and bw <= 128:
+            d.update(band=upload(band.view(np.int32)), band_w=bw)
+        else:
+            d["exp2d"] = upload(tab.view(np.int32))
+    return d
+
+
+def attention(a, family, qkv, out, B, H, T, hd, st, blocks=False, softmax_bits=None):
+    """Fused attention of an attention_spec `a` on head-major qkv [3, B, H, T, hd] -> out [B * T, H * hd] (`blocks`: in the block
+    layout).  Up to 207 tokens the short kernels, 208 .. 1025 the long-row ones (the same arguments); softmax_bits: given on the
+    16-bit stream, whose "wide" forms take it before the layout flag."""
+    p, wide, long = _lib.ptr, softmax_bits is not None, T > 207
+    sm = (softmax_bits,) if wide else ()
+    if family == "ibert":
+        name = ("ivit_attention_fused_i8_ibert_wide" if wide else "ivit_attention_fused_i8_ibert_long" if long else
+                "ivit_attention_fused_i8_ibert")
+        _lib.call(name, p(qkv), p(out), B, H, T, hd, a["ms"][0], a["ms"][1], a["mo"][0], a["mo"][1], p(a["ib_table"]), p(a["band"]),
+                  a["band_w"], *sm, int(blocks), st)
+    else:
+        name = ("ivit_attention_fused_i8_wide" if wide else "ivit_attention_fused_i8_long" if long else
+                "ivit_attention_fused_i8_compat_band")
+        _lib.call(name, p(qkv), p(out), B, H, T, hd, a["ms"][0], a["ms"][1], a["s_attn"], a["mo"][0], a["mo"][1], p(a["exp2d"]),
+                  p(a["band"]), a["band_w"], *sm, int(blocks), st)
+
+
+# ----------------------------------------------------------------------------------------------------------- GELU
+def gelu_lut(family, s_g, s_m1, upload, device, st):
+    """The 65536-entry table ivit_shiftgelu_lut_i8* gathers from: GELU on an int8 input of scale s_g + the QuantAct behind it
+    (mlp.qact1, scale s_m1).  -> (lut, natural).  family "ivit": ShiftGELU, which sees trunc(phi(q)) at a natural s_g
+    (ivit_modules.py:106-107; `natural`) and has the output scale s_g / 128 (:121,124).  family "ibert": IBERTIntGELU + mlp.qact1
+    depend on q alone -- one 256-entry map, replicated over the table's row-max axis; its output scale is negative
+    (ibert_modules.py:213, 232): requant(z, s) == requant(-z, -s) (quant_modules.QuantAct)."""
+    lut = torch.empty(65536, dtype=torch.int8, device=device)
+    if family == "ibert":
+        from .quantization_utils.ibert_modules import gelu_constants
+        gb, gc, gsh, gso = gelu_constants(s_g)
+        mg, eg = dyadic1(abs(f32(gso)), s_m1)
+        _lib.call("ivit_ibert_gelu_build_lut", float(s_g), gb, gc, gsh, float(gso), mg, eg, _lib.ptr(lut), st)
+        return lut, False
+    mg, eg = dyadic1(f32(s_g * f32(1.0 / 128.0)), s_m1)
+    t = phi_tables(s_g)
+    _lib.call("ivit_shiftgelu_build_lut_ex", float(s_g), mg, eg, _lib.ptr(None if t is None else upload(t[0])), _lib.ptr(lut), st)
+    return lut, t is not None
+
+
 # ----------------------------------------------------------------------------------------------------------- engines
 class EngineBase(GraphReplay, HeadTopK):
     """What IntViTEngine and IntSwinEngine share beyond their mixins.  Subclasses set self.dev, self.s0, self.input_lut and
@@ -111,6 +184,11 @@ class EngineBase(GraphReplay, HeadTopK):
         d = ln_spec(lp, self._upload, s_in, bits, ibert_shift)
         self.natural_sites += int(d["kind"].endswith("_compat"))
         return d
+
+    def _gelu_lut(self, family, s_g, s_m1):
+        lut, natural = gelu_lut(family, s_g, s_m1, self._upload, self.dev, self._stream())
+        self.natural_sites += int(natural)
+        return lut
 
     def set_input_normalisation(self, mean=IMAGENET_MEAN, std=IMAGENET_STD):
         """uint8 input: the (mean, std) of the Normalize transform in front of the model (default: ImageNet's).  forward() then

@@ -54,6 +54,12 @@ def dyadic(pre_sf, z_sf):
     return m.astype(np.uint32), (31 - ex).astype(np.int32)
 
 
+def dyadic1(pre_sf, z_sf):
+    """dyadic of two scalar scales -> (m, e) as Python ints, the form the kernels take by value"""
+    m, e = dyadic(pre_sf, z_sf)
+    return int(m[0]), int(e[0])
+
+
 def requant_host(z, m, e) -> np.ndarray:
     """RNE(z*m/2^e) in float64 exactly as quant_utils.py:229-230 (used for load-time constants)."""
     return np.rint(np.asarray(z, np.float64) * np.asarray(m, np.float64) / np.exp2(np.asarray(e, np.float64)))

@@ -45,9 +45,8 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ..engine_common import frag_copy, layernorm, ln_spec
-from ..prepare import (LayerNormParams, LinearParams, dyadic, f32, phi_tables, quant_sym, shiftexp2d, shiftexp_band,
-                       sym_scale)
+from ..engine_common import attention, attention_spec, frag_copy, gelu_lut, layernorm, ln_spec
+from ..prepare import LayerNormParams, LinearParams, dyadic, dyadic1, f32, quant_sym, sym_scale
 
 ENABLED = os.environ.get("IVIT_LAZY", "1") != "0"
 _ALWAYS = [os.environ.get("IVIT_LAZY") == "always"]      # enable_everywhere(): process-wide, independent of any open scope
@@ -725,9 +724,8 @@ def resolve(qact, x, pre_sf, identity, identity_sf, s_out, s_out_qs):
         s_id = host_of(identity_sf)
         if i8 is None or s_id is None or i8.shape != x8.shape or s_in.size != 1 or s_id.size != 1:
             return None
-        (m1, e1), (m2, e2) = dyadic(s_in, s_out), dyadic(s_id, s_out)
         out = torch.empty_like(x8)
-        _lib.call("ivit_residual_requant_i8", _lib.ptr(x8), int(m1[0]), int(e1[0]), _lib.ptr(i8), int(m2[0]), int(e2[0]),
+        _lib.call("ivit_residual_requant_i8", _lib.ptr(x8), *dyadic1(s_in, s_out), _lib.ptr(i8), *dyadic1(s_id, s_out),
                   _lib.ptr(out), x8.numel(), _st())
         STATS["fused"] += 1
         return QT.wrap(out.shape, device, q8=out, scale=s_out_qs, fl=fl)
@@ -760,10 +758,8 @@ def resolve(qact, x, pre_sf, identity, identity_sf, s_out, s_out_qs):
             out = _resolve_ln(node, s_out, device)
         elif node.kind == "ibln":
             out = _resolve_ibert_ln(node, s_out, device)
-        elif node.kind == "gelu":
-            out = _resolve_gelu(node, s_in, s_out, device)
-        elif node.kind == "ibgelu":
-            out = _resolve_ibert_gelu(node, s_in, s_out, device)
+        elif node.kind in ("gelu", "ibgelu"):
+            out = _resolve_gelu(node, s_out, device)
         elif node.kind == "matmul":
             out = _resolve_attention(node, s_in, s_out, device)
             if out is None:      # the first matmul of the attention chain: stays pending as the Shiftmax input
@@ -777,11 +773,6 @@ def resolve(qact, x, pre_sf, identity, identity_sf, s_out, s_out_qs):
     STATS["fused"] += 1
     out = x.apply_views(out)
     return QT.wrap(out.shape, device, q8=out, scale=s_out_qs, fl=fl if tuple(fl.shape) == tuple(out.shape) else None)
-
-
-def _sme(pre, z):
-    m, e = dyadic(pre, z)
-    return int(m[0]), int(e[0])
 
 
 def resolve_float(qact, x, pre_sf, s_out, s_out_qs):
@@ -831,7 +822,7 @@ def resolve16(qact, x, pre_sf, identity, identity_sf, s_out, s_out_qs):
             i16 = torch.empty(i8.shape, dtype=torch.int16, device=device)      # an 8-bit stream (behind a PatchMerging): widened
             _lib.call("ivit_requant_i8_i16", _lib.ptr(i8), 1 << 30, 30, _lib.ptr(i16), i8.numel(), _st())
         C = x.shape[-1]
-        (m1, e1), (m2, e2) = _sme(s_in, s_out), _sme(s_id, s_out)
+        (m1, e1), (m2, e2) = dyadic1(s_in, s_out), dyadic1(s_id, s_out)
         if isinstance(node, Requant) and x._q8 is None and not x.views and node.out is None:
             out = node.with_residual16(i16, s_in, (m1, e1, m2, e2), device)
         if out is None:
@@ -846,7 +837,7 @@ def resolve16(qact, x, pre_sf, identity, identity_sf, s_out, s_out_qs):
         if s_in.size != 1:
             return None
         a = q8_contig(x)
-        m, e = _sme(s_in, s_out)
+        m, e = dyadic1(s_in, s_out)
         out = torch.empty(a.shape, dtype=torch.int16, device=device)
         _lib.call("ivit_requant_i8_i16", _lib.ptr(a), m, e, _lib.ptr(out), a.numel(), _st())
     elif isinstance(node, ModNode) and node.kind == "linear" and s_in is host_of(node.out_scale):
@@ -925,11 +916,10 @@ class Requant(Node):
                 or tuple(i8.shape) != tuple(self.shape)):
             return None
         me = _gemm_me(self.lin, self.s_a, self.s_out, device)
-        (m1, e1), (m2, e2) = dyadic(s_in, s_out2), dyadic(s_id, s_out2)
         M = self.a8.shape[0]
         out = torch.empty(M, N, dtype=torch.int8, device=device)
         _lib.call("ivit_gemm_i8_requant_residual_ex", _lib.ptr(self.a8), K, _lib.ptr(c["Wf"]), K, _lib.ptr(c["b"]), _lib.ptr(me[0]),
-                  _lib.ptr(me[1]), _lib.ptr(i8), N, int(m1[0]), int(e1[0]), int(m2[0]), int(e2[0]), _lib.ptr(out), N, M, N, K, 16, _st())
+                  _lib.ptr(me[1]), _lib.ptr(i8), N, *dyadic1(s_in, s_out2), *dyadic1(s_id, s_out2), _lib.ptr(out), N, M, N, K, 16, _st())
         return out.view(*self.shape)
 
     def with_residual16(self, i16, s_in, mes, device):
@@ -982,6 +972,23 @@ def _patchify_i8(conv, x):
     return x8.reshape(B, Cin, g, kh, h, kw).permute(0, 2, 4, 1, 3, 5).reshape(B * g * h, Cin * kh * kw)
 
 
+def _layernorm(ln, x, s_in, s_out, bits, device, outer=0, ibert=False):
+    """LayerNorm (I-ViT's, or with `ibert` IBERTIntLayerNorm) of the contiguous `bits`-wide payload x + the QuantAct behind it ->
+    int8: engine_common's ln_spec, cached per weights, scales and device, and its launcher.  None outside the kernels' contract"""
+    def build():
+        lp = LayerNormParams(ln.weight.detach().cpu().numpy(), ln.bias.detach().cpu().numpy(), s_out)
+        return ln_spec(lp, lambda a: _dev(a, device), s_in[0], bits, float(ln.shift.reshape(-1)[0]) if ibert else None)
+    key = ("ibln", id(ln.shift), ln.shift._version) if ibert else ("ln", bits)
+    try:
+        spec = _cache(ln, key + (ln.weight._version, ln.bias._version, _key(s_in, s_out), str(device)), build)
+    except ValueError:
+        return None
+    C = x.shape[-1]
+    out = torch.empty(x.shape, dtype=torch.int8, device=device)
+    layernorm(spec, x, C, x.numel() // C, C, out, C, _st(), blocks=False, outer=outer)
+    return out
+
+
 def _resolve_ln(node, s_out, device):
     ln, x = node.mod, node.inputs[0]
     s_in = host_of(node.scales[0])
@@ -989,101 +996,28 @@ def _resolve_ln(node, s_out, device):
     outer = ln_outer(x.fl) if isinstance(x, QT) else None       # the reduction order follows the FLOAT tensor's layout
     if bits is None or outer is None or s_in is None or s_in.size != 1:
         return None
-    x8 = int_payload(x)
-    C = x8.shape[-1]
-    if bits == 16:
-        def build16():
-            lp = LayerNormParams(ln.weight.detach().cpu().numpy(), ln.bias.detach().cpu().numpy(), s_out)
-            return ln_spec(lp, lambda a: _dev(a, device), s_in[0], 16)
-        try:
-            spec = _cache(ln, ("ln16", ln.weight._version, ln.bias._version, _key(s_in, s_out), str(device)), build16)
-        except ValueError:
-            return None
-        out = torch.empty(x8.shape, dtype=torch.int8, device=device)
-        layernorm(spec, x8, C, x8.numel() // C, C, out, C, _st(), outer=outer)
-        return out
-
-    def build():
-        lp = LayerNormParams(ln.weight.detach().cpu().numpy(), ln.bias.detach().cpu().numpy(), s_out)
-        return dict(bias=_dev(lp.bias_int, device), s=_dev(lp.s_ln, device), m=_dev(lp.m.view(np.int32), device), e=_dev(lp.e, device))
-    try:
-        c = _cache(ln, ("ln", ln.weight._version, ln.bias._version, _key(s_out), str(device)), build)
-    except ValueError:
-        return None
-    tabs = _cache(ln, ("phi", _key(s_in), str(device)),
-                  lambda: (lambda t: None if t is None else (_dev(t[0], device), _dev(t[1], device)))(phi_tables(s_in[0])))
-    rows = x8.numel() // C
-    out = torch.empty_like(x8)
-    if tabs is not None:
-        _lib.call("ivit_layernorm_i8_compat", _lib.ptr(x8), C, rows, C, _lib.ptr(c["bias"]), _lib.ptr(c["s"]), _lib.ptr(c["m"]),
-                  _lib.ptr(c["e"]), _lib.ptr(tabs[0]), _lib.ptr(tabs[1]), _lib.ptr(out), C, outer << 8, _st())
-    else:
-        _lib.call("ivit_layernorm_i8_ex", _lib.ptr(x8), C, rows, C, _lib.ptr(c["bias"]), _lib.ptr(c["s"]), _lib.ptr(c["m"]),
-                  _lib.ptr(c["e"]), _lib.ptr(out), C, 0, _st())
-    return out
+    return _layernorm(ln, int_payload(x), s_in, s_out, bits, device, outer=outer)
 
 
 def _resolve_ibert_ln(node, s_out, device):
     """IBERTIntLayerNorm (ibert_modules.py:126-153) + the QuantAct behind it on int8: ivit_ibert_layernorm_i8 (csrc/ibert.hip), which
     works on fl(q * s_in) literally -- any input scale"""
-    ln, x = node.mod, node.inputs[0]
-    x8 = q8_contig(x)
+    ln, x8 = node.mod, q8_contig(node.inputs[0])
     s_in = host_of(node.scales[0])
     if x8 is None or s_in is None or s_in.size != 1 or ln.overflow_handling:
         return None
-    C = x8.shape[-1]
-
-    def build():
-        lp = LayerNormParams(ln.weight.detach().cpu().numpy(), ln.bias.detach().cpu().numpy(), s_out)
-        return dict(bias=_dev(lp.bias_int, device), s=_dev(lp.s_ln, device), m=_dev(lp.m.view(np.int32), device), e=_dev(lp.e, device),
-                    shift_pow2=float(2.0 ** float(ln.shift.reshape(-1)[0])))
-    try:
-        c = _cache(ln, ("ibln", ln.weight._version, ln.bias._version, id(ln.shift), ln.shift._version, _key(s_out), str(device)), build)
-    except ValueError:
-        return None
-    out = torch.empty_like(x8)
-    _lib.call("ivit_ibert_layernorm_i8", _lib.ptr(x8), C, x8.numel() // C, C, float(s_in[0]), _lib.ptr(c["bias"]), _lib.ptr(c["s"]),
-              c["shift_pow2"], _lib.ptr(c["m"]), _lib.ptr(c["e"]), _lib.ptr(out), C, 0, _st())
-    return out
+    return _layernorm(ln, x8, s_in, s_out, 8, device, ibert=True)
 
 
-def _resolve_ibert_gelu(node, s_g_out, s_out, device):
-    """IBERTIntGELU (ibert_modules.py:205-232) + mlp.qact1: a map of the input byte alone, as a table (ivit_ibert_gelu_build_lut;
-    replicated over the row-maximum axis of the ShiftGELU table format).  The GELU's output scale is negative: requant(z, s) ==
-    requant(-z, -s), handled inside the table build"""
+def _resolve_gelu(node, s_out, device):
+    """ShiftGELU ("gelu") or IBERTIntGELU ("ibgelu") + mlp.qact1: a gather from engine_common's gelu_lut"""
     x8 = q8_contig(node.inputs[0])
     s_g = host_of(node.scales[0])
     if x8 is None or s_g is None or s_g.size != 1:
         return None
-
-    def build():
-        from .ibert_modules import gelu_constants
-        gb, gc, gsh, gso = gelu_constants(s_g[0])
-        mg, eg = dyadic(abs(f32(gso)), s_out)
-        lut = torch.empty(65536, dtype=torch.int8, device=device)
-        _lib.call("ivit_ibert_gelu_build_lut", float(s_g[0]), gb, gc, gsh, float(gso), int(mg[0]), int(eg[0]), _lib.ptr(lut), _st())
-        return lut
-    lut = _cache(node.mod, ("ibgelu", _key(s_g, s_out), str(device)), build)
-    L = x8.shape[-1]
-    out = torch.empty_like(x8)
-    _lib.call("ivit_shiftgelu_lut_i8_ex", _lib.ptr(x8), L, x8.numel() // L, L, _lib.ptr(lut), _lib.ptr(out), L, 0, _st())
-    return out
-
-
-def _resolve_gelu(node, s_g_out, s_out, device):
-    x8 = q8_contig(node.inputs[0])
-    s_g = host_of(node.scales[0])
-    if x8 is None or s_g is None or s_g.size != 1:
-        return None
-
-    def build():
-        mg, eg = dyadic(f32(s_g[0] * f32(1.0 / 128.0)), s_out)              # ivit_modules.py:121,124
-        lut = torch.empty(65536, dtype=torch.int8, device=device)
-        t = phi_tables(s_g[0])
-        remap = None if t is None else _dev(t[0], device)
-        _lib.call("ivit_shiftgelu_build_lut_ex", float(s_g[0]), int(mg[0]), int(eg[0]), _lib.ptr(remap), _lib.ptr(lut), _st())
-        return lut
-    lut = _cache(node.mod, ("gelu", _key(s_g, s_out), str(device)), build)
+    family = "ibert" if node.kind == "ibgelu" else "ivit"
+    lut = _cache(node.mod, (node.kind, _key(s_g, s_out), str(device)),
+                 lambda: gelu_lut(family, s_g[0], s_out, lambda a: _dev(a, device), device, _st())[0])
     L = x8.shape[-1]
     out = torch.empty_like(x8)
     _lib.call("ivit_shiftgelu_lut_i8_ex", _lib.ptr(x8), L, x8.numel() // L, L, _lib.ptr(lut), _lib.ptr(out), L, 0, _st())
@@ -1105,83 +1039,75 @@ def _resolve_attention(node, s_pv, s_out, device):
     sc_qt = P.node.x
     if isinstance(sc_qt.node, (Biased, Masked)):
         return _resolve_window_attention(P, sc_qt, v, s_pv, s_out, device)
-    sc = sc_qt.node
-    scaled = sc.x.node if isinstance(sc.x.node, Scaled) else None
-    mm = scaled.x.node if scaled is not None else sc.x.node
-    if not (isinstance(mm, ModNode) and mm.kind == "matmul") or (scaled is not None and scaled.x.views):
+    chain = _score_operands(sc_qt.node)
+    if chain is None:
         return None
-    s_mm = host_of(mm.out_scale)          # the scale the scores arrive with: s_q * s_k, times the model's factor
-    if s_mm is None or not np.array_equal(sc.s_in, s_mm if scaled is None else (s_mm * f32(scaled.c)).astype(f32)):
+    sc, _, q, kT = chain
+    hm = _head_major(q, kT, v, device)
+    if hm is None:
         return None
-    q, kT = mm.inputs
-    if not (isinstance(q, QT) and isinstance(kT, QT)):
-        return None
-    hm = q.node.head_major(q, kT, v) if isinstance(q.node, Requant) else None
-    if hm is not None:
-        B, H, T, hd = hm.shape[1:]
-    else:
-        if q.q8 is None or kT.q8 is None or v.q8 is None:
-            return None
-        q8, k8, v8 = q.q8, kT.q8.transpose(-2, -1), v.q8
-        if q8.dim() != 4 or q8.shape != k8.shape or q8.shape != v8.shape or q8.shape[-1] != 64 or q8.shape[-2] > 1025:
-            return None
-        B, H, T, hd = q8.shape
-        hm = torch.empty(3, B, H, T, hd, dtype=torch.int8, device=device)
-        hm[0].copy_(q8)
-        hm[1].copy_(k8)
-        hm[2].copy_(v8)
+    B, H, T, hd = hm.shape[1:]
     s_S, s_at = sc.s_in, sc.s_out
     if s_S.size != 1 or s_pv.size != 1:
         return None
     sm = P.node.mod
+    family, act, key = "ivit", None, ("attn",)
     if type(sm).__name__ == "IBERTIntSoftmax":
         # IBERTIntSoftmax (ibert_modules.py:237-319): exp_int after its internal 16-bit QuantAct as a (row max, q) table, row sum in
         # torch's float32 order inside the kernel (attention.hip MODE 3 / 4); that kernel holds 193 .. 207 tokens, the long-row
         # form (attention_long_kernel MODE 2) 208 .. 1025
         if not (192 < T <= 1025) or sm.output_bit != 8 or sm.act.running_stat:
             return None
-
-        def build_ib():
-            from .ibert_modules import softmax_constants
-            lo, hi = float(sm.act.x_min.reshape(-1)[0]), float(sm.act.x_max.reshape(-1)[0])
-            x0i, bi, ci, exp_sf, act_sf, ma, ea = softmax_constants(s_at, lo, hi)
-            tab = torch.empty(65536, dtype=torch.float32, device=device)
-            _lib.call("ivit_ibert_softmax_build_table", float(s_at), x0i, bi, ci, float(exp_sf), float(act_sf), ma, ea, _lib.ptr(tab), _st())
-            ms, mo = dyadic(s_S, s_at), dyadic(s_pv, s_out)
-            d = dict(ms=(int(ms[0][0]), int(ms[1][0])), mo=(int(mo[0][0]), int(mo[1][0])), tab=tab, band=None, band_w=0)
-            band, bw = shiftexp_band(tab.cpu().numpy().view(np.uint32).reshape(256, 256))
-            if bw and bw <= 128:
-                d.update(band=_dev(band.view(np.float32), device), band_w=bw)
-            sm.act.act_scaling_factor = torch.full((1,), float(act_sf), dtype=torch.float32, device=device)
-            return d
-        a = _cache(sc.qact, ("ibattn", _key(s_S, np.asarray(s_at), s_pv, np.asarray(s_out)), id(sm.act.x_min), sm.act.x_min._version,
-                             id(sm.act.x_max), sm.act.x_max._version, str(device)), build_ib)
-        if T > 207 and not _long_multipliers_ok(a):
-            return None
-        out = torch.empty(B * T, H * hd, dtype=torch.int8, device=device)
-        _lib.call("ivit_attention_fused_i8_ibert" if T < 208 else "ivit_attention_fused_i8_ibert_long", _lib.ptr(hm), _lib.ptr(out), B, H, T,
-                  hd, a["ms"][0], a["ms"][1], a["mo"][0], a["mo"][1], _lib.ptr(a["tab"]), _lib.ptr(a["band"]), a["band_w"], 0, _st())
-        return out.view(B, T, H, hd).permute(0, 2, 1, 3)
+        family, act = "ibert", sm.act
+        key = ("ibattn", id(act.x_min), act.x_min._version, id(act.x_max), act.x_max._version)
 
     def build():
-        ms, mo = dyadic(s_S, s_at), dyadic(s_pv, s_out)
-        d = dict(ms=(int(ms[0][0]), int(ms[1][0])), mo=(int(mo[0][0]), int(mo[1][0])), exp2d=None, band=None, band_w=0)
-        if phi_tables(s_at) is not None:
-            tab = shiftexp2d(s_at)
-            band, bw = shiftexp_band(tab)
-            if bw and bw <= 128:
-                d.update(band=_dev(band.view(np.int32), device), band_w=bw)
-            else:
-                d["exp2d"] = _dev(tab.view(np.int32), device)
+        lo_hi = None if act is None else (float(act.x_min.reshape(-1)[0]), float(act.x_max.reshape(-1)[0]))
+        d = attention_spec(family, s_S, s_at, s_pv, s_out, lambda a: _dev(a, device), device, _st(), lo_hi)
+        if act is not None:
+            act.act_scaling_factor = torch.full((1,), d["act_sf"], dtype=torch.float32, device=device)
         return d
-    a = _cache(sc.qact, ("attn", _key(s_S, np.asarray(s_at), s_pv, np.asarray(s_out)), str(device)), build)
+    a = _cache(sc.qact, key + (_key(s_S, np.asarray(s_at), s_pv, np.asarray(s_out)), str(device)), build)
     if T > 207 and not _long_multipliers_ok(a):
         return None
     out = torch.empty(B * T, H * hd, dtype=torch.int8, device=device)
-    # up to 207 tokens the short kernel; 208 .. 1025 the long-row one (the same arguments)
-    _lib.call("ivit_attention_fused_i8_compat_band" if T < 208 else "ivit_attention_fused_i8_long", _lib.ptr(hm), _lib.ptr(out), B, H, T, hd,
-              a["ms"][0], a["ms"][1], float(s_at), a["mo"][0], a["mo"][1], _lib.ptr(a["exp2d"]), _lib.ptr(a["band"]), a["band_w"], 0, _st())
+    attention(a, family, hm, out, B, H, T, hd, _st())
     return out.view(B, T, H, hd).permute(0, 2, 1, 3)
+
+
+def _score_operands(sc):
+    """the walk from qact_attn1's pending node `sc` back to matmul_1: Scores -> (Scaled ->) matmul, where the scale the scores
+    arrive with must be the matmul's s_q * s_k, times the model's factor -> (sc, matmul node, q, k^T), or None"""
+    if not isinstance(sc, Scores):
+        return None
+    scaled = sc.x.node if isinstance(sc.x.node, Scaled) else None
+    mm = scaled.x.node if scaled is not None else sc.x.node
+    if not (isinstance(mm, ModNode) and mm.kind == "matmul") or (scaled is not None and scaled.x.views):
+        return None
+    s_mm = host_of(mm.out_scale)
+    if s_mm is None or not np.array_equal(sc.s_in, s_mm if scaled is None else (s_mm * f32(scaled.c)).astype(f32)):
+        return None
+    q, kT = mm.inputs
+    if not (isinstance(q, QT) and isinstance(kT, QT)):
+        return None
+    return sc, mm, q, kT
+
+
+def _head_major(q, kT, v, device, head_dim=64, max_tokens=1025, frags=True):
+    """q, k, v as the attention kernels read them, one int8 [3, B, H, N, hd]: written by the qkv GEMM itself (Requant.head_major),
+    else three copies of the payloads; None if they are not [B, H, N, head_dim] payloads of at most max_tokens tokens"""
+    hm = q.node.head_major(q, kT, v, head_dim=head_dim, max_tokens=max_tokens, frags=frags) if isinstance(q.node, Requant) else None
+    if hm is None:
+        if q.q8 is None or kT.q8 is None or v.q8 is None:
+            return None
+        q8, k8, v8 = q.q8, kT.q8.transpose(-2, -1), v.q8
+        if q8.dim() != 4 or q8.shape != k8.shape or q8.shape != v8.shape or q8.shape[-1] != head_dim or q8.shape[-2] > max_tokens:
+            return None
+        hm = torch.empty(3, *q8.shape, dtype=torch.int8, device=device)
+        hm[0].copy_(q8)
+        hm[1].copy_(k8)
+        hm[2].copy_(v8)
+    return hm
 
 
 def _mask_regions(mask, nW, N):
@@ -1203,7 +1129,7 @@ def _resolve_window_attention(P, top, v, s_pv, s_out, device):
     """WindowAttention (swin_quant.py:137-161): matmul_1 -> * scale -> qact_attn1 -> qact2 with the relative position bias ->
     (+ mask) -> Shiftmax -> matmul_2 behind qact3, as one launch of the ivit_window_attention_i8* family, selected as
     swin_engine.IntSwinEngine selects it (window order out)"""
-    from ..swin_engine import HEAD_DIM, LONG_WINDOW, key_pad, window_attention_spec
+    from ..swin_engine import HEAD_DIM, LONG_WINDOW, window_attention, window_attention_spec
     sm = P.node.mod
     if type(sm).__name__ != "IVITIntSoftmax" or sm.output_bit != 8:
         return None
@@ -1217,21 +1143,10 @@ def _resolve_window_attention(P, top, v, s_pv, s_out, device):
             return None
         biased = top
     bn = biased.node
-    sc = bn.x.node
-    if not isinstance(sc, Scores) or bn.x.views:
+    chain = None if bn.x.views else _score_operands(bn.x.node)
+    if chain is None or not isinstance(chain[0].x.node, Scaled) or len(chain[2].shape) != 4:      # Swin always scales the scores
         return None
-    scaled = sc.x.node if isinstance(sc.x.node, Scaled) else None
-    if scaled is None or scaled.x.views:
-        return None
-    mm = scaled.x.node
-    if not (isinstance(mm, ModNode) and mm.kind == "matmul"):
-        return None
-    s_mm = host_of(mm.out_scale)
-    if s_mm is None or not np.array_equal(sc.s_in, (s_mm * f32(scaled.c)).astype(f32)):
-        return None
-    q, kT = mm.inputs
-    if not (isinstance(q, QT) and isinstance(kT, QT)) or len(q.shape) != 4:
-        return None
+    sc, _, q, kT = chain
     B_, nH, N, hd = q.shape
     if hd != HEAD_DIM or not 2 <= N <= LONG_WINDOW or tuple(top.shape) != (B_, nH, N, N) or tuple(v.shape) != (B_, nH, N, hd):
         return None
@@ -1265,30 +1180,14 @@ def _resolve_window_attention(P, top, v, s_pv, s_out, device):
     if a is None:
         return None
     # ---- q, k, v head-major per window
-    hm = q.node.head_major(q, kT, v, head_dim=HEAD_DIM, max_tokens=LONG_WINDOW, frags=False) if isinstance(q.node, Requant) else None
+    hm = _head_major(q, kT, v, device, head_dim=HEAD_DIM, max_tokens=LONG_WINDOW, frags=False)
     if hm is None:
-        if q.q8 is None or kT.q8 is None or v.q8 is None:
-            return None
-        hm = torch.empty(3, B_, nH, N, hd, dtype=torch.int8, device=device)
-        hm[0].copy_(q.q8)
-        hm[1].copy_(kT.q8.transpose(-2, -1))
-        hm[2].copy_(v.q8)
+        return None
     C = nH * hd
     out = torch.empty(B_ * N, C, dtype=torch.int8, device=device)
-    band = a["band"]
-    if a["long"]:
-        _lib.call("ivit_window_attention_i8_long", _lib.ptr(hm), _lib.ptr(out), C, _lib.ptr(a["bias"]), _lib.ptr(a["region"]),
-                  a["mask_value"], B_, nW, nH, N, hd, a["ms"][0], a["ms"][1], a["mb"][0], a["mb"][1], a["s_attn"], a["mo"][0], a["mo"][1],
-                  _lib.ptr(None if band is not None else a["phi"]), _lib.ptr(None if band is not None else a["phim"]), _lib.ptr(band),
-                  a["band_w"], 0 if band is None else int(band.shape[0]), ws * nW, ws, ws, 0, 0, _st())
-    elif band is not None:
-        _lib.call("ivit_window_attention_i8_band", _lib.ptr(hm), _lib.ptr(out), C, _lib.ptr(a["bias"]), _lib.ptr(a["region"]), B_, nW, nH,
-                  N, hd, a["ms"][0], a["ms"][1], a["mb"][0], a["mb"][1], a["s_attn"], a["mo"][0], a["mo"][1], _lib.ptr(band), a["band_w"],
-                  int(band.shape[0]), 0, 0, 0, 0, _st())
-    else:
-        _lib.call("ivit_window_attention_i8_compat", _lib.ptr(hm), _lib.ptr(out), C, _lib.ptr(a["bias"]), _lib.ptr(a["region"]),
-                  a["mask_value"], B_, nW, nH, N, hd, a["ms"][0], a["ms"][1], a["mb"][0], a["mb"][1], a["s_attn"], a["mo"][0], a["mo"][1],
-                  _lib.ptr(a["phi"]), _lib.ptr(a["phim"]), _st())
+    # window order out; the long entry takes the windows' geometry regardless (one row of nW windows), the band entry none
+    geometry = (ws * nW, ws, ws, 0) if a["long"] else (0, 0, 0, 0)
+    window_attention(a, hm, out, C, B_, nW, nH, N, *geometry, False, _st())
     return out.view(B_, N, nH, hd).permute(0, 2, 1, 3)
 
 

@@ -22,7 +22,7 @@ import torch
 
 from . import _lib
 from .engine_common import EngineBase, _np, block_copy, frag_copy, layernorm
-from .prepare import (LayerNormParams, LinearParams, dyadic, f32, pad_head, phi_is_identity, phi_table, phi_tables, quant_sym,
+from .prepare import (LayerNormParams, LinearParams, dyadic, dyadic1, f32, pad_head, phi_is_identity, phi_table, quant_sym,
                       requant_host, sym_scale, window_shiftexp_band)
 from .topk import TOPK_MAX
 
@@ -99,10 +99,6 @@ def window_attention_spec(upload, bias, s_tab, s_S, s_at, s_A, s_pv, s_a3, regio
     "band256xW" / "literal", prepare.window_shiftexp_band)."""
     nH = bias.shape[0]
 
-    def sme(pre, z):
-        m, e = dyadic(pre, z)
-        return int(m[0]), int(e[0])
-
     m2, e2 = dyadic(s_tab, s_A)
     bias_add = requant_host(bias, m2[0], e2[0])                    # identity operand of qact2, :143-147
     assert np.abs(bias_add).max() < 32768
@@ -138,11 +134,33 @@ def window_attention_spec(upload, bias, s_tab, s_S, s_at, s_A, s_pv, s_a3, regio
         # saturated, no masked row maximum); else the kernel's literal float sequence on phi / phi_m
         band, band_w = window_shiftexp_band(s_A, region is not None)
         form = "literal" if band is None else f"band{band.shape[0]}x{band_w}"
-    spec = dict(ms=sme(s_S, s_at), mb=sme(s_at, s_A), s_attn=float(s_A), mo=sme(s_pv, s_a3),
+    spec = dict(ms=dyadic1(s_S, s_at), mb=dyadic1(s_at, s_A), s_attn=float(s_A), mo=dyadic1(s_pv, s_a3),
                 bias=upload(bias_pad), region=None if region_pad is None else upload(region_pad),
                 mask_value=mask_value, phi=upload(phi_table(s_A)) if att_nat else None, phim=upload(phi_m) if att_nat else None,
                 band=None if band is None else upload(band), band_w=band_w, long=N > SHORT_WINDOW)
     return spec, form
+
+
+def window_attention(a, qkv, out, ldo, nwin, nW, nH, N, H, W, win, shift, fuse_proj, st):
+    """One window attention of a window_attention_spec `a` on qkv, head-major per window [3, nwin, nH, N, HEAD_DIM] -> out, row
+    stride ldo.  H, W, win, shift: the map's geometry for the forms that store to image rows or take it regardless (the long and the
+    band entry); fuse_proj: the output goes straight to its image rows (window reverse + roll back in the store address), so that
+    attn.proj + attn.qact4 + the residual QuantAct qact2 are then ONE GEMM, in place on the residual stream -- else window order."""
+    p, band = _lib.ptr, a["band"]
+    head = (p(qkv), p(out), ldo, p(a["bias"]), p(a["region"]))
+    dims = (nwin, nW, nH, N, HEAD_DIM, a["ms"][0], a["ms"][1], a["mb"][0], a["mb"][1], a["s_attn"], a["mo"][0], a["mo"][1])
+    if a["long"]:
+        # windows of 65..144 tokens: one entry for every Shiftmax form and both output orders
+        _lib.call("ivit_window_attention_i8_long", *head, a["mask_value"], *dims, p(None if band is not None else a["phi"]),
+                  p(None if band is not None else a["phim"]), p(band), a["band_w"], 0 if band is None else int(band.shape[0]),
+                  H, W, win, shift, int(fuse_proj), st)
+    elif band is not None:
+        _lib.call("ivit_window_attention_i8_band", *head, *dims, p(band), a["band_w"], int(band.shape[0]), H, W,
+                  win if fuse_proj else 0, shift, st)
+    elif fuse_proj:
+        _lib.call("ivit_window_attention_i8_unwindow", *head, a["mask_value"], *dims, p(a["phi"]), p(a["phim"]), H, W, win, shift, st)
+    else:
+        _lib.call("ivit_window_attention_i8_compat", *head, a["mask_value"], *dims, p(a["phi"]), p(a["phim"]), st)
 
 
 def pool_literal_host(q: np.ndarray, s: float) -> np.ndarray:
@@ -235,10 +253,6 @@ class IntSwinEngine(EngineBase):
             patch norm the table form of the DeiT engine."""
             return self._ln_spec(LayerNormParams(P[prefix + ".weight"], P[prefix + ".bias"], s_out), s_in, bits_in)
 
-        def sme(pre, z):
-            m, e = dyadic(pre, z)
-            return int(m[0]), int(e[0])
-
         # ---- stem (layers_quant.py:191-203 with norm_layer; swin_quant.py:541-546)
         s0 = s("qact_input")
         self.inv_s0 = float(f32(1.0) / s0)
@@ -249,7 +263,7 @@ class IntSwinEngine(EngineBase):
         s_pq = s("patch_embed.qact")
         self.patch_ln = ln_dev("patch_embed.norm", s_pq, s_bn, 8)
         s_x = s("qact1", 16)
-        self.stem_me = sme(s_pq, s_x)
+        self.stem_me = dyadic1(s_pq, s_x)
 
         # ---- stages
         self.stages = []
@@ -290,26 +304,17 @@ class IntSwinEngine(EngineBase):
                 d.update(m=dev(mp.view(np.int32)), e=dev(ep))
                 blk["proj"] = d
                 s_b2 = s(p + "qact2", 16)
-                blk["res1"] = sme(s_a4, s_b2) + sme(s_x, s_b2)
+                blk["res1"] = dyadic1(s_a4, s_b2) + dyadic1(s_x, s_b2)
                 s_b3 = s(p + "qact3")
                 blk["ln2"] = ln_dev(p + "norm2", s_b3, s_b2)
                 s_g = s(p + "mlp.qact_gelu")
                 blk["fc1"] = lin_dev(p + "mlp.fc1", s_b3, s_g)
-                s_go = f32(s_g * f32(1.0 / 128.0))
                 s_m1 = s(p + "mlp.qact1")
-                mg, eg = sme(s_go, s_m1)
-                lut = torch.empty(65536, dtype=torch.int8, device=self.dev)
-                g_tabs = phi_tables(s_g)            # ShiftGELU sees trunc(phi(q)) (ivit_modules.py:106-107)
-                g_remap = None
-                if g_tabs is not None:
-                    self.natural_sites += 1
-                    g_remap = dev(g_tabs[0])
-                _lib.call("ivit_shiftgelu_build_lut_ex", float(s_g), mg, eg, _lib.ptr(g_remap), _lib.ptr(lut), self._stream())
-                blk["gelu_lut"] = lut
+                blk["gelu_lut"] = self._gelu_lut("ivit", s_g, s_m1)
                 s_m2 = s(p + "mlp.qact2")
                 blk["fc2"] = lin_dev(p + "mlp.fc2", s_m1, s_m2)
                 s_b4 = s(p + "qact4", 16)
-                blk["res2"] = sme(s_m2, s_b4) + sme(s_b2, s_b4)
+                blk["res2"] = dyadic1(s_m2, s_b4) + dyadic1(s_b2, s_b4)
                 s_x = s_b4
                 st["blocks"].append(blk)
             if li < len(self.depths) - 1:
@@ -327,7 +332,7 @@ class IntSwinEngine(EngineBase):
         s_q2 = s("qact2")
         self.ln_f = ln_dev("norm", s_q2, s_x)
         s_q3 = s("qact3")
-        self.pool_me = sme(s_q2, s_q3)
+        self.pool_me = dyadic1(s_q2, s_q3)
         # the tail's float mean over an even token count can land on an exact .5 tie; at a natural scale its float32 rounding then decides
         # qact3: the literal pooling restates torch's CPU order (ivit_avgpool_requant_i8_literal).  224 px (49 tokens): the integer form
         self.pool_literal = self.T_last % 2 == 0 and not phi_is_identity(s_q2)
@@ -471,30 +476,7 @@ class IntSwinEngine(EngineBase):
                     taps[p + "attn.qact1"] = hm.permute(1, 3, 0, 2, 4).reshape(nwin, N, 3 * C).clone()
                 a = blk["attn"]
                 fuse_proj = self.proj_fused and taps is None
-                if a["long"]:
-                    # windows of 65..144 tokens: one entry for every Shiftmax form and both output orders
-                    band = a["band"]
-                    _lib.call("ivit_window_attention_i8_long", _lib.ptr(ws["qkv"]), _lib.ptr(ws["ao"]), ld, _lib.ptr(a["bias"]),
-                              _lib.ptr(a["region"]), a["mask_value"], nwin, a["nW"], nH, N, HEAD_DIM, a["ms"][0], a["ms"][1], a["mb"][0],
-                              a["mb"][1], a["s_attn"], a["mo"][0], a["mo"][1], _lib.ptr(None if band is not None else a["phi"]),
-                              _lib.ptr(None if band is not None else a["phim"]), _lib.ptr(band), a["band_w"],
-                              0 if band is None else int(band.shape[0]), H, W, win, shift, int(fuse_proj), st)
-                elif a["band"] is not None:
-                    _lib.call("ivit_window_attention_i8_band", _lib.ptr(ws["qkv"]), _lib.ptr(ws["ao"]), ld, _lib.ptr(a["bias"]),
-                              _lib.ptr(a["region"]), nwin, a["nW"], nH, N, HEAD_DIM, a["ms"][0], a["ms"][1], a["mb"][0], a["mb"][1],
-                              a["s_attn"], a["mo"][0], a["mo"][1], _lib.ptr(a["band"]), a["band_w"], int(a["band"].shape[0]), H, W,
-                              win if fuse_proj else 0, shift, st)
-                elif fuse_proj:
-                    # the attention output goes straight to its image rows (window reverse + roll back in the store address):
-                    # attn.proj + attn.qact4 + the residual QuantAct qact2 are then ONE GEMM, in place on the residual stream
-                    _lib.call("ivit_window_attention_i8_unwindow", _lib.ptr(ws["qkv"]), _lib.ptr(ws["ao"]), ld, _lib.ptr(a["bias"]),
-                              _lib.ptr(a["region"]), a["mask_value"], nwin, a["nW"], nH, N, HEAD_DIM, a["ms"][0], a["ms"][1],
-                              a["mb"][0], a["mb"][1], a["s_attn"], a["mo"][0], a["mo"][1], _lib.ptr(a["phi"]), _lib.ptr(a["phim"]),
-                              H, W, win, shift, st)
-                else:
-                    _lib.call("ivit_window_attention_i8_compat", _lib.ptr(ws["qkv"]), _lib.ptr(ws["ao"]), ld, _lib.ptr(a["bias"]),
-                              _lib.ptr(a["region"]), a["mask_value"], nwin, a["nW"], nH, N, HEAD_DIM, a["ms"][0], a["ms"][1], a["mb"][0],
-                              a["mb"][1], a["s_attn"], a["mo"][0], a["mo"][1], _lib.ptr(a["phi"]), _lib.ptr(a["phim"]), st)
+                window_attention(a, ws["qkv"], ws["ao"], ld, nwin, a["nW"], nH, N, H, W, win, shift, fuse_proj, st)
                 tap(p + "attn.qact3", ws["ao"], M, C, ld)
                 pj = blk["proj"]
                 r = blk["res1"]
