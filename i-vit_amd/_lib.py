@@ -133,8 +133,7 @@ LAB_SIGNATURES = {
     "ivit_debug_ln_ablate": [ci],
     "ivit_debug_ln_stream_cfg": [ci],
     "ivit_debug_ln_stamp_buffer": [vp],
-    "ivit_gemm_i8_requant_gelu_ex": [vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, i64, ci, ci, ci, ci, vp],
-    "ivit_gemm_gelu_workspace_bytes": [ci, vp],
+    "ivit_debug_attention": [ci],
     "ivit_debug_set_stamp_buffer": [vp],
 }
 LAB_PATH = os.path.join(_HERE, "libivit_hip_lab.so")
@@ -206,6 +205,7 @@ class lab_session:
         L.ivit_debug_ln_ablate(0)
         L.ivit_debug_ln_stream_cfg(0)
         L.ivit_debug_ln_stamp_buffer(None)
+        L.ivit_debug_attention(0)
         _use_lab = self.prev
         return False
 

@@ -20,9 +20,10 @@
 #include "common.h"
 
 #if IVIT_LAB
-extern int g_ln_ablate;     // rowops.hip (ivit_debug_ln_ablate); bits 20-24 ablate phases of attention_kernel<0> (scripts/attn_ablate.py)
+static int g_attn_debug = 0;     // ivit_debug_attention (include/ivit_hip_debug.h): phase ablations, score form, part count
+IVIT_EXPORT int ivit_debug_attention(int bits) { g_attn_debug = bits; return IVIT_OK; }
 #else
-constexpr int g_ln_ablate = 0;
+constexpr int g_attn_debug = 0;
 #endif
 
 namespace {
@@ -590,7 +591,7 @@ int attention_parts(int batch_heads, int tokens, int slots)
 {
     const int nqt = (tokens + 15) >> 4;
 #if IVIT_LAB
-    if ((g_ln_ablate >> 28) & 7) return (g_ln_ablate >> 28) & 7;      // lab: forced (scripts/attn_parts.py)
+    if ((g_attn_debug >> 8) & 7) return (g_attn_debug >> 8) & 7;      // lab: forced (scripts/attn_parts.py)
 #endif
     int best = 1;
     double best_t = 0.0;
@@ -1203,7 +1204,7 @@ IVIT_EXPORT int ivit_attention_fused_i8_wide(const int8_t* qkv, int8_t* out, int
     IVIT_REQUIRE(band_w == 0 || (band && band_w >= 16 && band_w <= 256 && band_w % 16 == 0 && (uintptr_t)band % 16 == 0),
                  "ivit_attention_fused_i8_compat_band: band table must be 16-byte aligned, width a multiple of 16 in [16, 256]");
     AttnArgs a{};
-    a.abl = (g_ln_ablate >> 20) & 31;
+    a.abl = g_attn_debug & 31;
     a.exp2d = exp2d;
     a.band = band;
     a.band_w = band_w;
@@ -1211,8 +1212,8 @@ IVIT_EXPORT int ivit_attention_fused_i8_wide(const int8_t* qkv, int8_t* out, int
     a.qkv = qkv; a.out = out; a.batch = batch; a.heads = heads; a.tokens = tokens;
     a.Ms = ivit_dyadic_to_double(m_s, e_s);
     a.Mo = ivit_dyadic_to_double(m_o, e_o);
-    // a power-of-two score multiplier (m = 2^k): the float32 requantisation of the RQ32 kernels is exact (lab bit 26: off, A/B)
-    const bool ms_pow2 = m_s != 0 && (m_s & (m_s - 1)) == 0 && a.Ms >= 1e-30 && !(IVIT_LAB && (g_ln_ablate & (1 << 26)));
+    // a power-of-two score multiplier (m = 2^k): the float32 requantisation of the RQ32 kernels is exact (lab bit 5: off, A/B)
+    const bool ms_pow2 = m_s != 0 && (m_s & (m_s - 1)) == 0 && a.Ms >= 1e-30 && !(IVIT_LAB && (g_attn_debug & (1 << 5)));
     a.nMs32 = (float)-a.Ms;
     const float x0f = __builtin_floorf((1.0f / s_attn) * -1.0f);  // ivit_modules.py:154
     IVIT_REQUIRE(x0f <= -1.0f && x0f >= -4096.0f, "ivit_attention_fused_i8: x0=%g outside [-4096,-1]", (double)x0f);
@@ -1254,7 +1255,6 @@ IVIT_EXPORT int ivit_attention_fused_i8_wide(const int8_t* qkv, int8_t* out, int
     } else {
         if (band_w) hipLaunchKernelGGL(attention_kernel<1>, grid, blk, band_lds_bytes, st, a);
         else if (exp2d) hipLaunchKernelGGL(attention_kernel<2>, grid, blk, 0, st, a);
-        else if (IVIT_LAB && (g_ln_ablate & (1 << 25))) hipLaunchKernelGGL((attention_kernel<0, 8, 3>), grid, blk, 0, st, a);   // lab A/B: three workgroups per CU as before round 3
         else if (ms_pow2) hipLaunchKernelGGL((attention_kernel<0, 8, 4, false, true>), grid, blk, 0, st, a);
         else hipLaunchKernelGGL(attention_kernel<0>, grid, blk, 0, st, a);
     }

@@ -23,14 +23,14 @@ file checks the property itself, on the final instruction stream:
         v_permlane*_swap in the epilogue; the compiler pads its own stores, not these).
   (iv)  no VALU instruction writes an operand register of an inline-asm v_mfma within VALU_MFMA_GAP instructions in front of it
         (round 4, measured: `v_mov_b64 acc, bias` sunk by the scheduler to just in front of a tile's first MFMA left half of the C
-        operand's dwords stale, by lane parity -- gemm_wp.h's first parity run; the hazard recognizer does not look into inline asm).
+        operand's dwords stale, by lane parity -- the first parity run of the since-removed wave-pipelined kernel; the hazard recognizer does not look into inline asm).
 
 Exit status 1 and one line per finding if any guarded kernel violates a rule; the guarded kernels found are listed otherwise."""
 import re
 import sys
 from collections import defaultdict
 
-GUARDED = ("gemm_i8_wreg_kernel", "gemm_i8_pers_kernel", "gemm_i8_wp_kernel")
+GUARDED = ("gemm_i8_wreg_kernel", "gemm_i8_pers_kernel")
 MFMA_VALU_WAIT = 19      # wait states between an MFMA's write and a VALU read of the result (16-pass bound: covers every shape here)
 MFMA_MFMA_GAP = 4        # instructions between two MFMAs on the same accumulator
 VALU_MFMA_GAP = 4        # instructions between a VALU write of a register and an inline-asm MFMA that reads it

@@ -17,9 +17,10 @@
 // (token panel reuse in the XCD-private L2).
 #include <type_traits>
 //
-// This file holds the product kernels: the 128 x 128 register-staged kernel for small problems and raw int32 outputs,
-// and the persistent 256 x 128 LDS-DMA kernel everything large goes through.  Other forms of the large kernel
-// (relaunch per tile with ablation switches, 256 x 256 tiles, deep ring) live in gemm_lab.hip for A/B measurement.
+// This file holds the kernels: the 128 x 128 register-staged kernel for small problems and raw int32 outputs, the persistent
+// 256 x 128 LDS-DMA kernel, the weights-in-registers kernel for fragment-packed weights and the skinny-K streaming form.  The lab
+// build (IVIT_LAB = 1) adds form selectors and instruments on these kernels (include/ivit_hip_debug.h); forms that were tried and
+// lost (relaunch per tile, wave-pipelined, fused ShiftGELU) are in profiles/HISTORY.md and the git history, not here.
 #include "gemm_common.h"
 
 namespace {
@@ -214,7 +215,7 @@ IVIT_DEV PersWork pers_work(const GemmArgs& g, int i, int b, int G)
     return PersWork{-1, 0, 0};
 }
 
-template <int EPI, int EABL = 0>
+template <int EPI>
 __global__ __launch_bounds__(BIG_NT, 2) void gemm_i8_pers_kernel(GemmArgs g)
 {
     __shared__ __attribute__((aligned(16))) char smem[PERS_SMEM];
@@ -435,8 +436,8 @@ __global__ __launch_bounds__(BIG_NT, 2) void gemm_i8_pers_kernel(GemmArgs g)
         Hook hook{g, nxt.n0, tid, tab_next, more, PersTableLoad{0u, 0, 0, false}};
         int tid_o = tid;   // opaque: the epilogue's per-thread addresses are computed here, not carried through the main loop
         asm volatile("" : "+v"(tid_o));
-        epilogue_i8<EPI, 2, TJ, (HALF ? 128 : BTOK), BIG_NT, EABL, BCH, Hook>(acc, g, smem + BIG_STAGE, tab, cur.m0, cur.n0,
-                                                                           64 * wc, WTOK * wt, tid_o, (tid_o >> 5) & 1, tid_o & 31, hook);
+        epilogue_i8<EPI, 2, TJ, (HALF ? 128 : BTOK), BIG_NT, BCH, Hook>(acc, g, smem + BIG_STAGE, tab, cur.m0, cur.n0,
+                                                                     64 * wc, WTOK * wt, tid_o, (tid_o >> 5) & 1, tid_o & 31, hook);
         __syncthreads();   // staging reads done before the next item's stage 1 DMA overwrites buffer 1
     };
 
@@ -449,7 +450,7 @@ __global__ __launch_bounds__(BIG_NT, 2) void gemm_i8_pers_kernel(GemmArgs g)
         pers_table_write(tl, smem + PT_OFF, tid);
     }
     set_sources(cur);
-    if (g.stagger && blockIdx.x < (unsigned)g.stagger) {   // see gemm_i8_big_kernel: de-phase the two co-resident groups
+    if (g.stagger && blockIdx.x < (unsigned)g.stagger) {   // de-phase the two co-resident groups
         const unsigned slot = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 4) & 1u;
         if (slot)
             for (int it = 0; it < g.stagger_units; ++it) __builtin_amdgcn_s_sleep(16);
@@ -515,7 +516,9 @@ IVIT_DEV WrWork wr_work(const GemmArgs& g, int i, int b, int G)
     return WrWork{-1, 0, 0};
 }
 
-// ABL (lab build only): 1 no epilogue, 2 no weight loads in the loop, 4 no DMA in the loop, 8 no MFMA, 16 time stamps
+// ABL (lab build only; include/ivit_hip_debug.h): 1 no epilogue, 2 no weight loads in the loop, 4 no DMA in the loop, 8 no MFMA
+// (results WRONG); 16 time stamps, 2048 the stamps kept in registers until the tile ends; 4096 (product too, chosen by the launcher
+// when GemmArgs::res_f32) the residual QuantAct on float32 fmas
 //
 // Narrow tiles (GemmArgs::narrow, round 4; S16 only): 128 tokens x 128 channels per work item, wave w = channel group w & 1
 // x token half w >> 1, i.e. every wave does a half tile's arithmetic (64 ch x 64 tok, 16 accumulator tiles) on a full tile's
@@ -890,27 +893,22 @@ __global__ __launch_bounds__(BIG_NT, 2) void gemm_i8_wreg_kernel(GemmArgs g)
             int tid_o = tid;   // opaque: the epilogue's per-thread addresses are computed here, not carried through the main loop
             asm volatile("" : "+v"(tid_o));
             if constexpr (S16) asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");     // MFMA results -> VALU reads: see mfma16 (c)
-            if constexpr (S16 && (EPI == EPI_RQ || EPI == EPI_RESID || EPI == EPI_QKV) && !(ABL & 8192)) {
-                // straight from the registers (lane transpose, no LDS staging); ABL bit 13: the staged form below (A/B, lab)
-                epilogue_direct_16<EPI, 2 * TJ, (ABL & (64 | 2048 | 4096 | 32768)), Hook>(acc16, g, tab, cur.m0 + wtok, cur.n0, wch, (tid_o >> 4) & 3, tid_o & 15, hook,
+            if constexpr (S16 && (EPI == EPI_RQ || EPI == EPI_RESID || EPI == EPI_QKV)) {
+                // straight from the registers (lane transpose, no LDS staging)
+                epilogue_direct_16<EPI, 2 * TJ, (ABL & (2048 | 4096)), Hook>(acc16, g, tab, cur.m0 + wtok, cur.n0, wch, (tid_o >> 4) & 3, tid_o & 15, hook,
                                                                                g.lut ? reinterpret_cast<const unsigned char*>(smem + WR_LUT) : nullptr,
                                                                                (ABL & 2048) ? tv : nullptr);
-                if constexpr ((ABL & 32768) != 0) {      // ShiftGELU of a token panel by the workgroup that completes it (staging region: free here)
-                    __builtin_amdgcn_s_setprio(0);
-                    gelu_panel_phase<BIG_NT>(g, cs, cur.m0, cur.half, tid_o);
-                }
-            } else if constexpr (S16) {
+            } else if constexpr (S16) {      // EPI_RESID16: staged through LDS
                 static_assert(!S16 || EPI != EPI_RQ16_RES16, "the 16-bit epilogue exists for the 32x32 form only");
-                epilogue_i8_16<EPI, 2 * TJ, BIG_NT, (ABL & (64 | 2048 | 4096)), WR_CH, Hook>(acc16, g, cs, tab, cur.m0, cur.n0, 64 * wave, tid_o, (tid_o >> 4) & 3,
+                epilogue_i8_16<EPI, 2 * TJ, BIG_NT, WR_CH, Hook>(acc16, g, cs, tab, cur.m0, cur.n0, 64 * wave, tid_o, (tid_o >> 4) & 3,
                                                                           tid_o & 15, hook,
-                                                                          g.lut ? reinterpret_cast<const unsigned char*>(smem + WR_LUT) : nullptr, (ABL & 2048) ? tv : nullptr);
+                                                                          g.lut ? reinterpret_cast<const unsigned char*>(smem + WR_LUT) : nullptr);
             } else if constexpr (EPI == EPI_RQ16_RES16)
                 epilogue_rq16_res16<TJ, BIG_NT, Hook>(acc, g, cs, cur.m0, cur.n0, 64 * wave, tid_o, (tid_o >> 5) & 1, tid_o & 31, hook);
             else
-            epilogue_i8<EPI, 2, TJ, 32 * TJ, BIG_NT, (ABL & 64), WR_CH, Hook>(acc, g, cs, tab, cur.m0, cur.n0, 64 * wave, 0, tid_o, (tid_o >> 5) & 1,
+            epilogue_i8<EPI, 2, TJ, 32 * TJ, BIG_NT, WR_CH, Hook>(acc, g, cs, tab, cur.m0, cur.n0, 64 * wave, 0, tid_o, (tid_o >> 5) & 1,
                                                                       tid_o & 31, hook,
                                                                       g.lut ? reinterpret_cast<const unsigned char*>(smem + WR_LUT) : nullptr);
-            if constexpr (ABL & 32) __builtin_amdgcn_s_setprio(0);   // lab: main loops back at priority 0 (the epilogue raises it to 2)
         }
     };
 
@@ -940,7 +938,7 @@ __global__ __launch_bounds__(BIG_NT, 2) void gemm_i8_wreg_kernel(GemmArgs g)
                 stamp[16] = __builtin_amdgcn_s_memrealtime();   // constant 100 MHz: the shader clock follows from the pair
             }
         }
-        if constexpr (S16 && (EPI == EPI_RQ || EPI == EPI_RESID || EPI == EPI_QKV) && !(ABL & (8192 | 32768 | 16))) {
+        if constexpr (S16 && (EPI == EPI_RQ || EPI == EPI_RESID || EPI == EPI_QKV) && !(ABL & 16)) {
             if (cur.half == 2) run(std::integral_constant<int, 2>{}, cur, nxt, tab, tab_next);
             else if (cur.half) run(std::integral_constant<int, 1>{}, cur, nxt, tab, tab_next);
             else run(std::integral_constant<int, 0>{}, cur, nxt, tab, tab_next);
@@ -1102,8 +1100,6 @@ __global__ __launch_bounds__(SK_NT, 2) void gemm_i8_skinny_kernel(GemmArgs g)
     }
 }
 
-#include "gemm_wp.h"
-
 template <int EPI>
 int launch_gemm(GemmArgs& g, const char* name, ivit_stream_t stream, int qkv_planes = 3)   // EPI_QKV: N = qkv_planes * heads * head_dim
 {
@@ -1144,18 +1140,16 @@ int launch_gemm(GemmArgs& g, const char* name, ivit_stream_t stream, int qkv_pla
         IVIT_REQUIRE(g.N == qkv_planes * g.heads * g.head_dim && g.M % g.tokens == 0,
                      "%s: N=%d != %d*heads*head_dim or M=%d %% tokens=%d != 0", name, g.N, qkv_planes, g.M, g.tokens);
     }
-    g.flags = g_debug_flags & (31 | 128 | 256 | 512);
-    g.flags2 = g_debug_flags2;
 #if IVIT_LAB
     g.stamp = reinterpret_cast<unsigned long long*>(g_stamp_buf);
 #endif
     const bool blocks = g.a_blocks || g.w_blocks;
     if constexpr (EPI == EPI_RQ || EPI == EPI_QKV) {
         // skinny-K form: a streaming pass with the whole weight matrix in LDS (Swin stage 0); lab flags2 bit 20: off (A/B, parity of both)
-        if (!blocks && !g.w_frags && !g.out_blocks && !g.lut && !g.gelu_ws && g.M >= 8192 && g.K >= 32 && g.K <= SK_MAXK && g.K % 32 == 0 && g.N >= 16 &&
+        if (!blocks && !g.w_frags && !g.out_blocks && !g.lut && g.M >= 8192 && g.K >= 32 && g.K <= SK_MAXK && g.K % 32 == 0 && g.N >= 16 &&
             g.N <= SK_MAXN && g.N % 16 == 0 && g.lda % 16 == 0 && g.ldw % 8 == 0 && ((uintptr_t)g.A % 16 == 0) && ((uintptr_t)g.W % 8 == 0) &&
             ((uintptr_t)g.out % 16 == 0) && (EPI == EPI_QKV || g.ldo % 16 == 0) && (EPI != EPI_QKV || g.head_dim % 16 == 0) && (int64_t)g.M * (EPI == EPI_QKV ? g.N : g.ldo) < 4294967296ll &&
-            !g_force_small && !(IVIT_LAB && ((g_debug_flags2 & (1 << 20)) || (g_debug_flags & (31 | 128 | 256 | 512 | 1024))))) {
+            !g_force_small && !(IVIT_LAB && (g_debug_flags2 & (1 << 20)))) {
             const int nstrips = (g.M + 15) >> 4;
             const int grid = (nstrips + SK_WPB - 1) / SK_WPB < 512 ? (nstrips + SK_WPB - 1) / SK_WPB : 512;      // two workgroups of 8 waves per CU
             const bool any_k = IVIT_LAB && (g_debug_flags2 & (1 << 21));      // lab A/B: the run-time-K instantiation for every K
@@ -1186,47 +1180,12 @@ int launch_gemm(GemmArgs& g, const char* name, ivit_stream_t stream, int qkv_pla
             // (padding of 25 / 10 / 11 %) instead of the LDS-DMA kernel: DeiT-S b64 proj 17 -> 11 us.  Lab flags2 bit 13 selects them.
             g.narrow = 0;
             if constexpr (EPI == EPI_RQ || EPI == EPI_RESID || EPI == EPI_QKV) {
-                if (IVIT_LAB && g.w_frags == 2 && !g.lut && !g.gelu_ws && (g_debug_flags2 & 8192) && !(g_debug_flags2 & (256 | 512))) {
+                if (IVIT_LAB && g.w_frags == 2 && !g.lut && (g_debug_flags2 & 8192) && !(g_debug_flags2 & 256)) {
                     g.narrow = 1;
                     g.tiles_n = (g.N + WR_CH / 2 - 1) / (WR_CH / 2);
                 }
             }
             const int ntiles = g.tiles_m * g.tiles_n;
-            // Round 4 experiment, LAB ONLY (flags2 bit 15): the wave-pipelined form (gemm_wp.h: one workgroup of eight waves per CU, a
-            // tile's requantisation inside the next tile's main loop).  Exact, and SLOWER than the kernel below (fc1 150 vs 116 us,
-            // qkv 121 vs 97 us): with 64 accumulator registers per wave the token fragments are re-read from LDS twice as often per
-            // MFMA, and the bare eight-wave loop alone (no epilogue at all) takes 110 us -- profiles/r04p_*, DESIGN.md section 8
-            if constexpr (IVIT_LAB != 0 && (EPI == EPI_RQ || EPI == EPI_QKV)) {
-                if (g.w_frags == 2 && !g.lut && !g.gelu_ws && !g.narrow && (g.K / BK) >= 12 && (g_debug_flags2 & 32768) && !(g_debug_flags2 & (256 | 512)) &&
-                    !(g_debug_flags & 127)) {
-                    IVIT_REQUIRE(((int64_t)g.M + 16) * (EPI == EPI_QKV ? g.N : g.ldo) < 4294967296ll,
-                                 "%s: IVIT_W_FRAGS16 addresses its output with 32-bit offsets: operand of 4 GiB or more", name);
-                    g.split_from = ntiles;
-                    if constexpr (EPI == EPI_QKV) {
-                        IVIT_REQUIRE((int64_t)g.M * g.tokens < 4294967296ll, "%s: M * tokens must stay below 2^32", name);
-                        g.tokens_magic = (unsigned)(4294967296ull / (unsigned)g.tokens) + 1u;
-                    }
-                    static bool lds_set = false;      // 94 KB of dynamic LDS: beyond the default 64 KB limit of a launch
-                    if (!lds_set) {
-                        IVIT_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_i8_wp_kernel<EPI>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                         WP_SMEM) == hipSuccess, "%s: the device refuses %d bytes of LDS per workgroup", name, WP_SMEM);
-                        lds_set = true;
-                    }
-#if IVIT_LAB
-                    if constexpr (EPI == EPI_RQ) {      // timing ablations (results wrong): flags2 bits 16-19 = ABL of gemm_wp.h
-                        const int abl = (g_debug_flags2 >> 16) & 15;
-                        if (abl) {
-#define IVIT_WP_ABL(v) if (abl == v) { hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_i8_wp_kernel<EPI_RQ, v>), hipFuncAttributeMaxDynamicSharedMemorySize, WP_SMEM); \
-                                       hipLaunchKernelGGL((gemm_i8_wp_kernel<EPI_RQ, v>), dim3(ntiles < 256 ? ntiles : 256), dim3(WP_NT), WP_SMEM, ivit_stream(stream), g); IVIT_CHECK_LAUNCH(name); }
-                            IVIT_WP_ABL(1) IVIT_WP_ABL(3) IVIT_WP_ABL(2)
-#undef IVIT_WP_ABL
-                        }
-                    }
-#endif
-                    hipLaunchKernelGGL((gemm_i8_wp_kernel<EPI>), dim3(ntiles < 256 ? ntiles : 256), dim3(WP_NT), WP_SMEM, ivit_stream(stream), g);
-                    IVIT_CHECK_LAUNCH(name);
-                }
-            }
             // A sparse last round (R tiles on 512 slots) runs as 2R half tiles of 64 tokens (wr_work) when every half tile still
             // finds a CU of its own (2R <= 256): fc1 at the headline shape, R = 120, 144 -> 136 us.  Beyond that two half tiles
             // share a CU while a lone full tile has one to itself and runs nearly twice as fast: measured slower (N = 768,
@@ -1237,15 +1196,15 @@ int launch_gemm(GemmArgs& g, const char* name, ivit_stream_t stream, int qkv_pla
             // Round 4: a launch with at most 256 tiles (DeiT-S attn.proj / fc2 at batch 64: 198; Swin stage 3: 147) runs ALL of them as half
             // tiles of 64 tokens, one per workgroup: such a launch lasts as long as ONE tile (main loop + epilogue, ~15 K cycles), and a
             // half tile's epilogue is half as long, its K steps 16 MFMAs per wave instead of 32 (lab bit 27: off)
-            const bool all_halves = g.w_frags == 2 && !g.narrow && !g.gelu_ws && rounds == 0 && 2 * ntiles <= 512 && !(g_debug_flags & 134217728);
+            const bool all_halves = g.w_frags == 2 && !g.narrow && rounds == 0 && 2 * ntiles <= 512 && !(g_debug_flags & 134217728);
             if (all_halves) g.split_from = 0;
             const dim3 grid(all_halves ? 2 * ntiles : (ntiles < 512 ? ntiles : 512));
 #if IVIT_LAB
-            if constexpr (EPI == EPI_RQ) {   // ablations (scripts/gemm_ab.py --frags): what each stream of the kernel costs
-                switch (g_debug_flags & 127) {
+            if constexpr (EPI == EPI_RQ) {   // timing ablations (scripts/gemm_ab.py --frags): what each stream of the kernel costs
+                switch (g_debug_flags & 31) {
 #define IVIT_WR_ABL(v) case v: hipLaunchKernelGGL((gemm_i8_wreg_kernel<EPI_RQ, v>), grid, dim3(BIG_NT), 0, ivit_stream(stream), g); IVIT_CHECK_LAUNCH(name)
                     case 16: g.res = (const int8_t*)g_stamp_buf; hipLaunchKernelGGL((gemm_i8_wreg_kernel<EPI_RQ, 16>), (g_debug_flags & 4096) ? dim3(256) : grid, dim3(BIG_NT), (g_debug_flags & 4096) ? 40960 : 0, ivit_stream(stream), g); IVIT_CHECK_LAUNCH(name);
-                    IVIT_WR_ABL(64); IVIT_WR_ABL(32); IVIT_WR_ABL(1); IVIT_WR_ABL(2); IVIT_WR_ABL(4); IVIT_WR_ABL(6); IVIT_WR_ABL(8); IVIT_WR_ABL(14); IVIT_WR_ABL(15); IVIT_WR_ABL(7);
+                    IVIT_WR_ABL(1); IVIT_WR_ABL(2); IVIT_WR_ABL(4); IVIT_WR_ABL(6); IVIT_WR_ABL(8); IVIT_WR_ABL(14); IVIT_WR_ABL(15); IVIT_WR_ABL(7);
 #undef IVIT_WR_ABL
                     default: break;
                 }
@@ -1266,21 +1225,6 @@ int launch_gemm(GemmArgs& g, const char* name, ivit_stream_t stream, int qkv_pla
                         }
                     }
 #endif
-#if IVIT_LAB
-                    if constexpr (EPI == EPI_RQ || EPI == EPI_RESID || EPI == EPI_QKV) {
-                        if (g_debug_flags2 & 512) {     // A/B: the LDS-staged epilogue instead of the direct one (scripts/gemm_ab.py 0:512)
-                            if (EPI == EPI_RESID && g.res_f32) hipLaunchKernelGGL((gemm_i8_wreg_kernel<EPI, 8192 | 4096, true>), grid, dim3(BIG_NT), 0, ivit_stream(stream), g);
-                            else hipLaunchKernelGGL((gemm_i8_wreg_kernel<EPI, 8192, true>), grid, dim3(BIG_NT), 0, ivit_stream(stream), g);
-                            IVIT_CHECK_LAUNCH(name);
-                        }
-                    }
-#endif
-                    if constexpr (EPI == EPI_RQ && IVIT_LAB != 0) {
-                        if (g.gelu_ws) {     // ABL bit 15: ShiftGELU + mlp.qact1 applied per completed token panel (gelu_panel_phase)
-                            hipLaunchKernelGGL((gemm_i8_wreg_kernel<EPI, 32768, true>), grid, dim3(BIG_NT), 0, ivit_stream(stream), g);
-                            IVIT_CHECK_LAUNCH(name);
-                        }
-                    }
                     if constexpr (EPI == EPI_RESID) {
                         if (g.res_f32) {     // ABL bit 12: the residual QuantAct on float32 fmas (residual_f32_form)
                             hipLaunchKernelGGL((gemm_i8_wreg_kernel<EPI, 4096, true>), grid, dim3(BIG_NT), 0, ivit_stream(stream), g);
@@ -1298,12 +1242,6 @@ int launch_gemm(GemmArgs& g, const char* name, ivit_stream_t stream, int qkv_pla
         }
     }
     if constexpr (EPI != EPI_I32 && EPI != EPI_RQ16 && EPI != EPI_RQ16_RES16) {
-#if IVIT_LAB
-        if (EPI <= EPI_QKV && !blocks && (g_debug_flags & (31 | 128 | 256 | 512 | 1024))) {   // a lab form was asked for (tests, scripts)
-            int rc = IVIT_OK;
-            if (ivit_gemm_lab_launch(EPI, &g, name, stream, &rc)) return rc;
-        }
-#endif
         if (g.M >= 2048 && g.N >= BCH && !g_force_small) {
             g.stagger = (g_debug_flags & 64) ? 0 : 512;  // 2 workgroups x 256 CUs
             g.tiles_m = (g.M + BTOK - 1) / BTOK;
@@ -1328,12 +1266,7 @@ int launch_gemm(GemmArgs& g, const char* name, ivit_stream_t stream, int qkv_pla
             // equivalent and the former half-main-loop delay (26 / 98 units at K = 768 / 3072) cost 4-8 %: off by default
             g.stagger_units = (g_debug_flags >> 16) & 63;
             const int grid = rounds > 0 ? SLOTS : (split ? 2 * R : R);
-            if (EPI == EPI_RQ && (g_debug_flags & 16384))   // A/B of epilogue variants (EPI_RQ only)
-                hipLaunchKernelGGL((gemm_i8_pers_kernel<EPI_RQ, 32>), dim3(grid), dim3(BIG_NT), one_per_cu ? 20480 : 0,
-                                   ivit_stream(stream), g);
-            else
-                hipLaunchKernelGGL((gemm_i8_pers_kernel<EPI>), dim3(grid), dim3(BIG_NT), one_per_cu ? 20480 : 0,
-                                   ivit_stream(stream), g);
+            hipLaunchKernelGGL((gemm_i8_pers_kernel<EPI>), dim3(grid), dim3(BIG_NT), one_per_cu ? 20480 : 0, ivit_stream(stream), g);
             IVIT_CHECK_LAUNCH(name);
         }
     }
@@ -1421,32 +1354,6 @@ IVIT_EXPORT int ivit_gemm_i8_requant_lut_ex(const int8_t* A, int64_t lda, const 
                  "ivit_gemm_i8_requant_lut_ex: block-layout output needs N %% 64 == 0, ldo == N and a buffer below 2 GiB");
     return launch_gemm<EPI_RQ>(g, "ivit_gemm_i8_requant_lut_ex", stream);
 }
-
-#if IVIT_LAB     // the fc1 + ShiftGELU experiment (include/ivit_hip_debug.h): lab library only
-IVIT_EXPORT int ivit_gemm_gelu_workspace_bytes(int M, int64_t* bytes)
-{
-    IVIT_REQUIRE(M > 0 && bytes, "ivit_gemm_gelu_workspace_bytes: M > 0 and a result pointer");
-    const int64_t panels = ((int64_t)M + WR_TOK - 1) / WR_TOK;
-    *bytes = panels * (int64_t)sizeof(int);
-    return IVIT_OK;
-}
-
-IVIT_EXPORT int ivit_gemm_i8_requant_gelu_ex(const int8_t* A, int64_t lda, const int8_t* W, int64_t ldw, const int32_t* bias,
-                                             const uint32_t* m, const int32_t* e, const int8_t* gelu_lut, void* workspace,
-                                             int8_t* out, int64_t ldo, int M, int N, int K, int layouts, ivit_stream_t stream)
-{
-    GemmArgs g{};
-    g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.bias = bias; g.m = m; g.e = e;
-    g.out = out; g.ldo = ldo; g.M = M; g.N = N; g.K = K; g.gelu_lut = gelu_lut; g.gelu_ws = static_cast<int*>(workspace);
-    g.a_blocks = layouts & 1; g.out_blocks = (layouts >> 2) & 1; g.w_frags = (layouts & 16) ? 2 : 0;
-    IVIT_REQUIRE(gelu_lut && workspace && ((uintptr_t)workspace % 4 == 0) && (layouts & ~(1 | 4 | 16)) == 0 && g.w_frags == 2,
-                 "ivit_gemm_i8_requant_gelu_ex: needs the table, the workspace and IVIT_W_FRAGS16 (| IVIT_A_BLOCKS | IVIT_OUT_BLOCKS)");
-    IVIT_REQUIRE(N <= 4096, "ivit_gemm_i8_requant_gelu_ex: N = %d, at most 4096 channels per token", N);
-    IVIT_REQUIRE(!g.out_blocks || (N % 64 == 0 && ldo == N && ((int64_t)M + 15) * N < 2147483648ll),
-                 "ivit_gemm_i8_requant_gelu_ex: block-layout output needs N %% 64 == 0, ldo == N and a buffer below 2 GiB");
-    return launch_gemm<EPI_RQ>(g, "ivit_gemm_i8_requant_gelu_ex", stream);
-}
-#endif
 
 IVIT_EXPORT int ivit_gemm_i8_requant(const int8_t* A, int64_t lda, const int8_t* W, int64_t ldw, const int32_t* bias,
                                      const uint32_t* m, const int32_t* e, int8_t* out, int64_t ldo, int M, int N,
@@ -1616,3 +1523,34 @@ IVIT_EXPORT int ivit_gemm_i8_i32(const int8_t* A, int64_t lda, const int8_t* W, 
     g.out = out; g.ldo = ldo; g.M = M; g.N = N; g.K = K;
     return launch_gemm<EPI_I32>(g, "ivit_gemm_i8_i32", stream);
 }
+
+#if IVIT_LAB     // include/ivit_hip_debug.h: process-wide test and measurement state, lab library only
+bool g_force_small = false;
+void* g_stamp_buf = nullptr;
+int g_debug_flags = 0;
+int g_debug_flags2 = 0;
+
+IVIT_EXPORT int ivit_debug_force_small_gemm(int on)
+{
+    g_force_small = (on != 0);
+    return IVIT_OK;
+}
+
+IVIT_EXPORT int ivit_debug_set_gemm_flags(int flags)
+{
+    g_debug_flags = flags;
+    return IVIT_OK;
+}
+
+IVIT_EXPORT int ivit_debug_set_gemm_flags2(int flags)
+{
+    g_debug_flags2 = flags;
+    return IVIT_OK;
+}
+
+IVIT_EXPORT int ivit_debug_set_stamp_buffer(void* buf)
+{
+    g_stamp_buf = buf;
+    return IVIT_OK;
+}
+#endif

@@ -1,31 +1,25 @@
 // gemm_common.h -- shared pieces of the INT8 GEMM kernels: tile constants, argument block, LDS swizzle, the requantising
-// int8 epilogue and the persistent-kernel helpers.  Included by gemm.hip (the product kernels) and gemm_lab.hip (kernel
-// forms kept for A/B measurement and ablation).
+// int8 epilogue and the persistent-kernel helpers.  Included by gemm.hip.
 #pragma once
 #include <type_traits>
 
 #include "common.h"
 
 // Two builds of the same sources (csrc/Makefile):
-//   libivit_hip.so      IVIT_LAB = 0: the product.  No process-wide state -- the knobs below are compile-time constants, the
-//                       lab kernels (gemm_lab.hip) and the ivit_debug_* hooks are not in it;
+//   libivit_hip.so      IVIT_LAB = 0: the product.  No process-wide state -- the knobs below are compile-time constants and
+//                       the ivit_debug_* hooks are not in it;
 //   libivit_hip_lab.so  IVIT_LAB = 1: the same entry points plus include/ivit_hip_debug.h (kernel-form A/B, ablations,
 //                       time stamps), for tests/ and scripts/ only.
 #if IVIT_LAB
-// test / measurement state set through include/ivit_hip_debug.h (defined in gemm_lab.hip)
-extern int g_kernel_choice;   // 0 = automatic, 1 = never the 256x256 kernel
+// test / measurement state set through include/ivit_hip_debug.h (defined in gemm.hip)
 extern bool g_force_small;    // route every problem through the small-tile kernel
 extern void* g_stamp_buf;     // timeline buffer of the stamped builds
 extern int g_debug_flags;     // see ivit_debug_set_gemm_flags
-extern int g_debug_flags2;    // see ivit_debug_set_gemm_flags2 (cache-policy A/B of the weights-in-registers kernel)
+extern int g_debug_flags2;    // see ivit_debug_set_gemm_flags2
 #else
-constexpr int g_kernel_choice = 0;
 constexpr bool g_force_small = false;
 constexpr int g_debug_flags = 0;
 constexpr int g_debug_flags2 = 0;
-#endif
-#ifndef IVIT_STORE_POLICY
-#define IVIT_STORE_POLICY 0    // product default of store16_sel (see there)
 #endif
 
 namespace {
@@ -67,7 +61,8 @@ struct GemmArgs {
     int M, N, K;
     int tokens, heads, head_dim;
     int tiles_m, tiles_n;
-    int flags;
+    int flags;       // unused since the relaunch-per-tile lab kernel left; kept: without it every field below moves by 4 bytes and the
+                     // persistent kernel's scalar argument loads (and with them its register allocation) come out differently
     int stagger;  // number of first-generation blocks subject to the start stagger (0 = off)
     int cu_turns;       // persistent kernel: 1 = co-resident workgroups alternate main loops through the per-CU token
     int stagger_units;  // persistent kernel: start delay of the second co-resident workgroup, in s_sleep(16) (~1K cycle) units
@@ -77,19 +72,9 @@ struct GemmArgs {
     int out_blocks;           // EPI_RQ: the int8 output in the block layout (row length N): it is the next GEMM's A operand
     int w_frags;              // W is the MFMA-fragment copy (ivit_pack_weight_frags_i8): the weights-in-registers kernel
     unsigned long long* stamp;   // lab build only: timeline buffer of the stamped kernel forms (ivit_debug_set_stamp_buffer)
-    int flags2;               // lab build only (ivit_debug_set_gemm_flags2): cache policies of the epilogue's stores / residual loads
     const int8_t* lut;        // EPI_RQ, weights-in-registers kernel: out = lut[q + 128] applied to every requantised byte (an
                               // elementwise int8 -> int8 operator behind the QuantAct, e.g. I-BERT GELU + mlp.qact1), or NULL
-    // EPI_RQ, 16x16x64 weights-in-registers kernel, ABL bit 15 (ivit_gemm_i8_requant_gelu_ex, EXPERIMENTAL): ShiftGELU + mlp.qact1
-    // behind the QuantAct, applied by the workgroup that completes a token panel (gelu_panel_phase)
-    const int8_t* gelu_lut;   // [256][256] (row max + 128, k + 128) -> int8: the table of ivit_shiftgelu_build_lut_ex
-    int* gelu_ws;             // caller-owned arrival counters of the 128-token panels [tiles_m]: zero before the first use, left
-                              // zero by every launch
-    unsigned tokens_magic;    // EPI_QKV, wave-pipelined kernel (gemm_wp.h): floor(2^32 / tokens) + 1 -- t / tokens == umulhi(t, magic) for
-                              // every row index (the launcher checks M * tokens < 2^32): no per-lane division inside the main loop
 };
-
-IVIT_DEV int nk_of(const GemmArgs& g) { return g.K / 64; }
 
 // byte offset of 16-byte chunk c (0..3) of tile row r; rows are 64 B, four rows per 256-B bank row.
 IVIT_DEV int swz(int r, int c) { return r * BK + ((c ^ ((r >> 2) & 3)) << 4); }
@@ -125,49 +110,6 @@ IVIT_DEV int pack4_i8(int a, int b, int c, int d)
 }
 
 
-// Cache policy of the epilogue's 16-byte output stores (MI355X_MICROARCH.md, "stores of each flavour": plain / nt keep the line in
-// the XCD's L2, sc1 / sc0 sc1 write through and drop it).  The output of a GEMM is consumed by the NEXT kernel, never by this one:
-// keeping it in L2 only displaces the weight and token panels the other workgroups of the XCD are re-reading.
-// POL: 0 plain, 1 nt, 2 sc1, 3 sc0 sc1.  The asm stores are invisible to the compiler's vmcnt bookkeeping, which can only make its
-// own counted waits wait for more (loads and stores retire in issue order).
-template <int POL>
-IVIT_DEV void store16_pol(void* p, int4 v)
-{
-    typedef int v4i_ __attribute__((ext_vector_type(4)));
-    const v4i_ d = {v.x, v.y, v.z, v.w};
-    // (lab A/B of cache policies only.  The s_nop: the data comes straight out of v_permlane16_swap / v_permlane32_swap in
-    // epilogue_direct_16; the compiler's hazard recognizer puts wait states in front of its own VMEM instructions but does not look
-    // into inline asm.)
-    if constexpr (POL == 0) *reinterpret_cast<int4*>(p) = v;
-    else if constexpr (POL == 1) asm volatile("s_nop 7\n\tglobal_store_dwordx4 %0, %1, off nt" ::"v"(p), "v"(d) : "memory");
-    else if constexpr (POL == 2) asm volatile("s_nop 7\n\tglobal_store_dwordx4 %0, %1, off sc1" ::"v"(p), "v"(d) : "memory");
-    else asm volatile("s_nop 7\n\tglobal_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(p), "v"(d) : "memory");
-}
-IVIT_DEV void store16_sel(void* p, int4 v, int pol)
-{
-#if IVIT_LAB
-    switch (pol & 3) {     // uniform
-        case 1: store16_pol<1>(p, v); return;
-        case 2: store16_pol<2>(p, v); return;
-        case 3: store16_pol<3>(p, v); return;
-        default: break;
-    }
-#endif
-    store16_pol<IVIT_STORE_POLICY>(p, v);
-}
-// the residual operand is read exactly once: nt keeps it from displacing L2 lines that are re-read
-IVIT_DEV int4 load16_sel(const void* p, int pol)
-{
-#if IVIT_LAB
-    if (pol & 4) {
-        typedef int v4i_ __attribute__((ext_vector_type(4)));
-        const v4i_ d = __builtin_nontemporal_load(reinterpret_cast<const v4i_*>(p));
-        return make_int4(d.x, d.y, d.z, d.w);
-    }
-#endif
-    return *reinterpret_cast<const int4*>(p);
-}
-
 // ---- shared int8 epilogue --------------------------------------------------------------------
 // acc[TI][TJ]: TI channel sub-tiles x TJ token sub-tiles of 32x32 owned by this wave, channel origin
 // `wch`, token origin `wtok` inside a block tile of TOK tokens x 128 channels.
@@ -199,14 +141,11 @@ struct NoHook {
 
 // Phase 2 of the int8 epilogues: the staged tile Cs[token][channel] (row stride CH + 4) -> 16-byte row-contiguous chunks: optional
 // residual QuantAct, optional head-major remap or byte map, store.  Called by every thread right after its phase-1 LDS writes.
-template <int EPI, int TOK, int NTHREADS, int ABL, int CH, typename Hook>
-IVIT_DEV void epilogue_phase2(const GemmArgs& g, char* smem, int m0, int n0, int tid, const Hook& hook, const unsigned char* lut_lds,
-                              unsigned long long* st = nullptr)
+template <int EPI, int TOK, int NTHREADS, int CH, typename Hook>
+IVIT_DEV void epilogue_phase2(const GemmArgs& g, char* smem, int m0, int n0, int tid, const Hook& hook, const unsigned char* lut_lds)
 {
     constexpr int CSS = CH + 4;
     constexpr int CPR = CH / 16;
-    unsigned long long t_p1 = 0, t_sync = 0;
-    if constexpr (ABL & (512 | 2048)) t_p1 = __builtin_amdgcn_s_memtime();
     // Phase 2 work items of this thread: NIT chunks (token row tl, 16-byte column chunk cc).  The residual loads go out BEFORE the
     // barrier (the accumulators are dead, their registers free), so their latency runs under the barrier wait and the LDS reads.
     constexpr int NIT = TOK * CPR / NTHREADS;
@@ -220,20 +159,18 @@ IVIT_DEV void epilogue_phase2(const GemmArgs& g, char* smem, int m0, int n0, int
     constexpr int RPI = NTHREADS / CPR;                              // rows between a thread's consecutive chunks
     static_assert(NTHREADS % CPR == 0, "a thread keeps its chunk column");
     if constexpr (EPI == EPI_RESID || EPI == EPI_RESID16) {
-        if constexpr (!(ABL & 16)) {
-            const int8_t* rbase = g.res + (int64_t)(m0 + tid / CPR) * g.ldr + (n0 + 16 * (tid % CPR));
+        const int8_t* rbase = g.res + (int64_t)(m0 + tid / CPR) * g.ldr + (n0 + 16 * (tid % CPR));
 #pragma unroll
-            for (int it = 0; it < NIT; ++it) {
-                const int q = tid + NTHREADS * it;
-                const int tl = q / CPR, cc = q % CPR;
-                const int t = min(m0 + tl, g.M - 1), cn = min(n0 + 16 * cc, g.N - 16);
-                if constexpr (EPI == EPI_RESID) {
-                    rv[it] = load16_sel(interior ? rbase + (int64_t)(it * RPI) * g.ldr : g.res + (int64_t)t * g.ldr + cn, g.flags2);
-                } else {
-                    const int4* rp = reinterpret_cast<const int4*>(reinterpret_cast<const int16_t*>(g.res) + (int64_t)t * g.ldr + cn);
-                    rw[it][0] = rp[0];
-                    rw[it][1] = rp[1];
-                }
+        for (int it = 0; it < NIT; ++it) {
+            const int q = tid + NTHREADS * it;
+            const int tl = q / CPR, cc = q % CPR;
+            const int t = min(m0 + tl, g.M - 1), cn = min(n0 + 16 * cc, g.N - 16);
+            if constexpr (EPI == EPI_RESID) {
+                rv[it] = *reinterpret_cast<const int4*>(interior ? rbase + (int64_t)(it * RPI) * g.ldr : g.res + (int64_t)t * g.ldr + cn);
+            } else {
+                const int4* rp = reinterpret_cast<const int4*>(reinterpret_cast<const int16_t*>(g.res) + (int64_t)t * g.ldr + cn);
+                rw[it][0] = rp[0];
+                rw[it][1] = rp[1];
             }
         }
     }
@@ -241,15 +178,6 @@ IVIT_DEV void epilogue_phase2(const GemmArgs& g, char* smem, int m0, int n0, int
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    if constexpr (ABL & 512) {
-        t_sync = __builtin_amdgcn_s_memtime();
-        if (tid == 0 && g.res != nullptr) {
-            unsigned long long* d = reinterpret_cast<unsigned long long*>(const_cast<int8_t*>(g.res)) + 8ull * blockIdx.x;
-            d[4] = t_p1; d[5] = t_sync;
-        }
-    }
-    if constexpr ((ABL & 16) && !(ABL & 2048)) return;
-    if constexpr (ABL & 2048) { st[4] = t_p1; st[5] = __builtin_amdgcn_s_memtime(); }
 
     int8_t* out = reinterpret_cast<int8_t*>(g.out);
     int v[NIT][4];
@@ -267,7 +195,6 @@ IVIT_DEV void epilogue_phase2(const GemmArgs& g, char* smem, int m0, int n0, int
         v[it][0] = vv[it][0].x; v[it][1] = vv[it][0].y; v[it][2] = vv[it][1].x; v[it][3] = vv[it][1].y;
     }
     hook.consume();
-    if constexpr (ABL & 2048) st[6] = __builtin_amdgcn_s_memtime();
     const bool oblk = (EPI == EPI_RQ) && g.out_blocks;
     const int64_t off0 = oblk ? (int64_t)block_off(block_row(m0 + tid / CPR, g.N), block_col(n0 + 16 * (tid % CPR)))
                               : (int64_t)(m0 + tid / CPR) * g.ldo + (n0 + 16 * (tid % CPR));
@@ -303,30 +230,6 @@ IVIT_DEV void epilogue_phase2(const GemmArgs& g, char* smem, int m0, int n0, int
         if (!interior && (t >= g.M || cn >= g.N)) continue;
         if constexpr (EPI == EPI_RESID) {
             const int rr[4] = {rv[it].x, rv[it].y, rv[it].z, rv[it].w};
-            if constexpr (ABL & 4096) {   // kernel form chosen by the launcher when g.res_f32.  RNE(k * M) as ONE float32 fma against 1.5 * 2^23 per product: the float's low bits are the
-                               // integer, and the launcher has checked all 256 int8 inputs of both multipliers against the
-                               // float64 evaluation (the epilogue's VALU instructions issue at ~1 per 8 cycles beside the
-                               // co-resident workgroup's MFMA stream: 11 -> 7 instructions per output byte)
-#pragma unroll
-                for (int d = 0; d < 4; ++d) {
-                    unsigned o[4];
-#pragma unroll
-                    for (int bb = 0; bb < 4; ++bb) {
-                        const float kf = (float)(int)(int8_t)(v[it][d] >> (8 * bb));
-                        const float xf = (float)(int)(int8_t)(rr[d] >> (8 * bb));
-                        // plain v_fma_f32 through asm: left to itself the compiler packs the pair into v_pk_fma_f32, which costs more
-                        // than two scalar fmas beside an MFMA stream (cdna guide, 'packed f32 VALU')
-                        float f1, f2;
-                        asm("v_fma_f32 %0, %1, %2, %3" : "=v"(f1) : "v"(kf), "s"(g.Mf_main), "v"(magic_v));
-                        asm("v_fma_f32 %0, %1, %2, %3" : "=v"(f2) : "v"(xf), "s"(g.Mf_res), "v"(magic_v));
-                        // quant_utils.py:229-245: two rounded products, then the sum; + 128 so that the clamp leaves an unsigned byte
-                        o[bb] = (unsigned)clamp_i32((int)((unsigned)__float_as_int(f1) + (unsigned)__float_as_int(f2) - 2u * 0x4B400000u), -128, 127);
-                    }
-                    const unsigned w01 = __builtin_amdgcn_perm(o[1], o[0], 0x0c0c0400u);
-                    const unsigned w23 = __builtin_amdgcn_perm(o[3], o[2], 0x04000c0cu);
-                    v[it][d] = (int)(w01 | w23);
-                }
-            } else {
 #pragma unroll
             for (int d = 0; d < 4; ++d) {
                 int o[4];
@@ -339,7 +242,6 @@ IVIT_DEV void epilogue_phase2(const GemmArgs& g, char* smem, int m0, int n0, int
                     o[bb] = clamp_i32(sres, -128, 127);
                 }
                 v[it][d] = pack4_i8(o[0], o[1], o[2], o[3]);
-            }
             }
         }
         if constexpr (EPI == EPI_RESID16) {
@@ -389,11 +291,11 @@ IVIT_DEV void epilogue_phase2(const GemmArgs& g, char* smem, int m0, int n0, int
         } else {
             off = (EPI == EPI_RQ && g.out_blocks) ? (int64_t)block_off(block_row(t, g.N), block_col(cn)) : (int64_t)t * g.ldo + cn;
         }
-        store16_sel(out + off, make_int4(v[it][0], v[it][1], v[it][2], v[it][3]), g.flags2);
+        *reinterpret_cast<int4*>(out + off) = make_int4(v[it][0], v[it][1], v[it][2], v[it][3]);
     }
 }
 
-template <int EPI, int TI, int TJ, int TOK, int NTHREADS, int ABL = 0, int CH = 128, typename Hook = NoHook>
+template <int EPI, int TI, int TJ, int TOK, int NTHREADS, int CH = 128, typename Hook = NoHook>
 IVIT_DEV void epilogue_i8(v16i (&acc)[TI][TJ], const GemmArgs& g, char* smem, const char* rq_lds, int m0, int n0,
                           int wch, int wtok, int tid, int h, int l31, const Hook& hook = Hook(),
                           const unsigned char* lut_lds = nullptr)
@@ -441,33 +343,16 @@ IVIT_DEV void epilogue_i8(v16i (&acc)[TI][TJ], const GemmArgs& g, char* smem, co
             for (int j = 0; j < TJ; ++j)
 #pragma unroll
                 for (int jj = 0; jj < 4; ++jj) {
-                    if constexpr (ABL & 8) {
-                        b[j][jj] = acc[i][j][4 * q + jj] + (int)lo[jj];
-                    } else {
-                        const float a = (float)acc[i][j][4 * q + jj];
-                        int tl, th;
-                        if constexpr (ABL & 64) {   // A/B: both brackets in one packed fma (lo, hi are adjacent table entries)
-                            typedef float v2f_ __attribute__((ext_vector_type(2)));
-                            const v2f_ r = __builtin_elementwise_fma((v2f_){a, a}, (v2f_){lo[jj], hi[jj]}, (v2f_){12582912.0f, 12582912.0f});
-                            tl = __float_as_int(r.x);
-                            th = __float_as_int(r.y);
-                        } else {
-                            tl = __float_as_int(__builtin_fmaf(a, lo[jj], 12582912.0f));
-                            th = __float_as_int(__builtin_fmaf(a, hi[jj], 12582912.0f));
-                        }
-                        // unc += |tl - th| in ONE instruction (v_sad_u32): zero iff every certificate of the batch holds.
-                        // tl, th are bit patterns of floats next to 1.5 * 2^23, their differences are tiny: no wrap-around.
-                        if constexpr (ABL & 32) {   // A/B: the former two-instruction form
-                            unc |= (unsigned)(tl ^ th);
-                            asm volatile("" : "+v"(unc));
-                        } else {
-                            asm("v_sad_u32 %0, %1, %2, %3" : "=v"(unc) : "v"(tl), "v"(th), "v"(unc));
-                        }
-                        amax = fmaxf(amax, fabsf(a));
-                        b[j][jj] = clamp_i32(tl, 0x4B400000 - 128, 0x4B400000 + 127);  // low byte = int8 result
-                    }
+                    const float a = (float)acc[i][j][4 * q + jj];
+                    const int tl = __float_as_int(__builtin_fmaf(a, lo[jj], 12582912.0f));
+                    const int th = __float_as_int(__builtin_fmaf(a, hi[jj], 12582912.0f));
+                    // unc += |tl - th| in ONE instruction (v_sad_u32): zero iff every certificate of the batch holds.
+                    // tl, th are bit patterns of floats next to 1.5 * 2^23, their differences are tiny: no wrap-around.
+                    asm("v_sad_u32 %0, %1, %2, %3" : "=v"(unc) : "v"(tl), "v"(th), "v"(unc));
+                    amax = fmaxf(amax, fabsf(a));
+                    b[j][jj] = clamp_i32(tl, 0x4B400000 - 128, 0x4B400000 + 127);  // low byte = int8 result
                 }
-            if constexpr (!(ABL & 8)) {
+            {
                 const bool bad = (unc != 0) | (amax >= 4194304.0f);
                 if (__builtin_amdgcn_ballot_w64(bad) != 0) {  // rare: exact float64 evaluation of the batch
                     const int c0 = min(n0 + cl, g.N - 4);
@@ -496,7 +381,7 @@ IVIT_DEV void epilogue_i8(v16i (&acc)[TI][TJ], const GemmArgs& g, char* smem, co
         }
         __builtin_amdgcn_sched_barrier(0);
     }
-    epilogue_phase2<EPI, TOK, NTHREADS, ABL, CH, Hook>(g, smem, m0, n0, tid, hook, lut_lds);
+    epilogue_phase2<EPI, TOK, NTHREADS, CH, Hook>(g, smem, m0, n0, tid, hook, lut_lds);
 }
 
 // ---- the int8 epilogue for accumulators of v_mfma_i32_16x16x64_i8 (the weights-in-registers kernel's S16 form).
@@ -504,9 +389,9 @@ IVIT_DEV void epilogue_i8(v16i (&acc)[TI][TJ], const GemmArgs& g, char* smem, co
 // 16 j + l15 and the four consecutive channels wch + 16 i + 4 g4 + r of register r -- again one dword of four channels per
 // token, so phase 1 is the arithmetic of epilogue_i8 with other loop bounds (batches of 16 outputs per certificate ballot) and
 // phase 2 is shared.
-template <int EPI, int NJ, int NTHREADS, int ABL, int CH, typename Hook>
+template <int EPI, int NJ, int NTHREADS, int CH, typename Hook>
 IVIT_DEV void epilogue_i8_16(v4i (&acc)[4][NJ], const GemmArgs& g, char* smem, const char* rq_lds, int m0, int n0, int wch, int tid,
-                             int g4, int l15, const Hook& hook, const unsigned char* lut_lds, unsigned long long* st = nullptr)
+                             int g4, int l15, const Hook& hook, const unsigned char* lut_lds)
 {
     static_assert(NJ % 4 == 0, "batches of four token sub-tiles");
     __builtin_amdgcn_s_setprio(2);
@@ -571,7 +456,7 @@ IVIT_DEV void epilogue_i8_16(v4i (&acc)[4][NJ], const GemmArgs& g, char* smem, c
         }
         __builtin_amdgcn_sched_barrier(0);
     }
-    epilogue_phase2<EPI, 16 * NJ, NTHREADS, ABL, CH, Hook>(g, smem, m0, n0, tid, hook, lut_lds, st);
+    epilogue_phase2<EPI, 16 * NJ, NTHREADS, CH, Hook>(g, smem, m0, n0, tid, hook, lut_lds);
 }
 
 // ---- the same epilogue WITHOUT the LDS round trip (EPI_RQ row-major or block layout, EPI_RESID, EPI_QKV).
@@ -635,8 +520,6 @@ IVIT_DEV void epilogue_direct_16(v4i (&acc)[4][NJ], const GemmArgs& g, const cha
     // store -- batch 0 runs under the flight of batch 1's residual loads; the next work item's table (hook.consume: vmcnt(0) for its
     // loads, issued before this epilogue) is written between the two batches.
     constexpr int NB = NJ / 4;
-    constexpr bool GELU = (ABL & 32768) != 0;     // the tile is read back by the workgroup that completes its panel (gelu_panel_phase)
-    static_assert(!GELU || EPI == EPI_RQ, "the fused ShiftGELU follows a plain requantising epilogue");
     unsigned D[NB][4][4];     // [batch][i][j]: bytes 16 i + 4 g4 .. + 3 of token 16 (4 batch + j) + l15
     int4 rv[EPI == EPI_RESID ? NB : 1][4];
     v4f lhbuf[2][2];
@@ -692,14 +575,13 @@ IVIT_DEV void epilogue_direct_16(v4i (&acc)[4][NJ], const GemmArgs& g, const cha
             // ALL residual chunks are requested as soon as the first batch's accumulators are dead (64 registers free, 16 of them
             // for its packed results): requested batch by batch, the last batch's loads were only one batch of phase B old when
             // hook.consume() drained vmcnt -- 3.4 K cycles of a 15 K cycle epilogue spent waiting for them (stamped timeline)
-            const bool batchwise = IVIT_LAB && (g.flags2 & 1024);      // lab A/B: the former order
 #pragma unroll
             for (int b2 = 0; b2 < NB; ++b2) {
-                if (batchwise ? b2 != bi : bi != 0) continue;         // uniform
+                if (bi != 0) continue;         // uniform
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int t = min(m0 + 16 * (4 * b2 + j) + l15, g.M - 1);
-                    rv[b2][j] = load16_sel(g.res + ((unsigned)t * (unsigned)g.ldr + (unsigned)min(c, g.N - 16)), g.flags2);   // 32-bit offsets: launcher
+                    rv[b2][j] = *reinterpret_cast<const int4*>(g.res + ((unsigned)t * (unsigned)g.ldr + (unsigned)min(c, g.N - 16)));   // 32-bit offsets: launcher
                 }
             }
         }
@@ -779,120 +661,9 @@ IVIT_DEV void epilogue_direct_16(v4i (&acc)[4][NJ], const GemmArgs& g, const cha
             } else {
                 off = off0 + (unsigned)(jb + j) * ostep;
             }
-            if constexpr (GELU) {
-                // written through to memory (sc1 = device scope): read back by whichever workgroup completes the panel, possibly on
-                // another XCD.  Two 64-bit atomic stores, not an inline-asm 128-bit one: compiler-visible, so its hazard and
-                // s_waitcnt bookkeeping cover them
-                if (col_ok && t < g.M) {
-                    long long* q = reinterpret_cast<long long*>(out + off);
-                    __hip_atomic_store(q, (long long)(((unsigned long long)(unsigned)v[1] << 32) | (unsigned)v[0]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(q + 1, (long long)(((unsigned long long)(unsigned)v[3] << 32) | (unsigned)v[2]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-            } else {
-                if (col_ok && t < g.M) store16_sel(out + off, make_int4(v[0], v[1], v[2], v[3]), g.flags2);
-            }
+            if (col_ok && t < g.M) *reinterpret_cast<int4*>(out + off) = make_int4(v[0], v[1], v[2], v[3]);
         }
     }
-}
-
-// ---- EXPERIMENTAL (measured slower than GEMM + table pass; no engine uses it): ShiftGELU + mlp.qact1 behind
-// mlp.fc1 + mlp.qact_gelu inside the GEMM that produces its input (ivit_modules.py:105-126).
-// The map of a byte depends on the maximum over ALL N outputs of its token (the exponent's argument is k - max), and a token's N
-// channels are N / 256 tiles of N / 256 different workgroups.  So: every tile writes its requantised bytes through to memory and
-// counts itself in at its 128-token panel; the workgroup whose arrival completes the panel reads the panel's 128 x N bytes back,
-// takes the row maxima, and maps the rows in place.  Nobody waits for anybody: a workgroup either finds the panel complete or
-// leaves.  Visibility across XCDs (one L2 each): sc1 stores, all acknowledged (s_waitcnt vmcnt(0)) and written back (release)
-// before the arrival is counted; the completing workgroup reads with sc1 loads.  The counters are left as they were found (zero).
-template <int NTHREADS>
-IVIT_DEV void gelu_panel_phase(const GemmArgs& g, char* lds, int m0, int half, int tid)
-{
-    typedef int v4i_ __attribute__((ext_vector_type(4)));
-    constexpr int RG = 4;                          // rows per wave and step: RG x N / 1024 16-byte chunks in flight per lane
-    constexpr int MAXC = 4;                        // 16-byte chunks per lane and row: N <= 4096
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this thread's tile stores have been acknowledged
-    __syncthreads();
-    int* flag = reinterpret_cast<int*>(lds);
-    const int panel = m0 >> 7, mp = panel << 7;
-    int* cnt = g.gelu_ws + panel;
-    if (tid == 0) {
-        const int inc = half ? 1 : 2;
-        const int old = __hip_atomic_fetch_add(cnt, inc, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);   // acquire too: the completing workgroup reads the other tiles next
-        flag[0] = (old + inc == 2 * g.tiles_n) ? 1 : 0;
-    }
-    __syncthreads();
-    if (flag[0] == 0) return;                      // uniform: the panel is not complete (or another workgroup completes it)
-#if IVIT_LAB
-    if (g.flags2 & 0x1000) {      // timing ablation: count, but leave the panel unmapped (results wrong)
-        if (tid == 0) __hip_atomic_store(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return;
-    }
-#endif
-    const int lane = tid & 63, wave = tid >> 6;
-    unsigned char* tab = reinterpret_cast<unsigned char*>(lds) + 64 + wave * (RG * 256);
-    int8_t* const out = reinterpret_cast<int8_t*>(g.out);
-    const int nch = g.N >> 4;                      // 16-byte chunks per row (N % 64 == 0)
-    constexpr int RPW = 128 / (NTHREADS / 64);     // rows per wave
-    for (int rs = 0; rs < RPW; rs += RG) {
-        const int r0 = mp + wave * RPW + rs;
-        if (r0 >= g.M) break;                      // uniform
-        v4i_ w[RG][MAXC];
-        unsigned off[RG][MAXC];
-#pragma unroll
-        for (int r = 0; r < RG; ++r) {
-            const int row = min(r0 + r, g.M - 1);
-            const BlockRow br = block_row(row, g.N);
-#pragma unroll
-            for (int c = 0; c < MAXC; ++c) {
-                w[r][c] = (v4i_){0, 0, 0, 0};
-                const int ch = min(lane + 64 * c, nch - 1);
-                off[r][c] = g.out_blocks ? block_off(br, block_col(16 * ch)) : (unsigned)row * (unsigned)g.ldo + 16u * (unsigned)ch;
-                if (64 * c < nch) {                // uniform.  (An inline-asm 128-bit sc1 load here returned wrong first dwords now and
-                                                   // then: the compiler reuses these registers for the mapped output and knows nothing of
-                                                   // a load it cannot see.  Compiler-visible atomic loads, twice as many, are exact.)
-                    const long long* q = reinterpret_cast<const long long*>(out + off[r][c]);
-                    const long long lo = __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    const long long hi = __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    w[r][c] = (v4i_){(int)lo, (int)(lo >> 32), (int)hi, (int)(hi >> 32)};
-                }
-            }
-        }
-        // the rows' maxima from the bytes themselves, then their table slices
-#pragma unroll
-        for (int r = 0; r < RG; ++r) {
-            int km = -128;
-#pragma unroll
-            for (int c = 0; c < MAXC; ++c) {
-                if (64 * c >= nch) continue;
-                if (lane + 64 * c < nch) {
-#pragma unroll
-                    for (int d = 0; d < 4; ++d)
-                        km = max(max(km, (int)(int8_t)(w[r][c][d])), max((int)(int8_t)(w[r][c][d] >> 8), max((int)(int8_t)(w[r][c][d] >> 16), w[r][c][d] >> 24)));
-                }
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) km = max(km, __shfl_xor(km, o));
-            reinterpret_cast<int*>(tab + 256 * r)[lane] = reinterpret_cast<const int*>(g.gelu_lut + (int64_t)(km + 128) * 256)[lane];
-        }
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int r = 0; r < RG; ++r) {
-            const unsigned char* tb = tab + 256 * r;
-#pragma unroll
-            for (int c = 0; c < MAXC; ++c) {
-                if (64 * c >= nch) continue;       // uniform
-                int o[4];
-#pragma unroll
-                for (int d = 0; d < 4; ++d) {
-                    const unsigned u = (unsigned)w[r][c][d] ^ 0x80808080u;      // k + 128 per byte
-                    o[d] = (int)((unsigned)tb[u & 255] | ((unsigned)tb[(u >> 8) & 255] << 8) | ((unsigned)tb[(u >> 16) & 255] << 16) |
-                                 ((unsigned)tb[u >> 24] << 24));
-                }
-                if (lane + 64 * c < nch && r0 + r < g.M) *reinterpret_cast<int4*>(out + off[r][c]) = make_int4(o[0], o[1], o[2], o[3]);
-            }
-        }
-        __builtin_amdgcn_wave_barrier();           // every lane has read its slices before the next step overwrites them
-    }
-    if (tid == 0) __hip_atomic_store(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // ---- 16-bit epilogue of the weights-in-registers kernel (EPI_RQ16_RES16).  A wave owns 64 of the tile's 256 channels x 32 TJ
@@ -1050,7 +821,7 @@ IVIT_DEV void epilogue_rq16_res16_small(v16i (&acc)[2][2], const GemmArgs& g, ch
     }
 }
 
-// ---- 256 x 128 LDS-DMA tiles (persistent kernel, relaunch form, deep-ring form)
+// ---- 256 x 128 LDS-DMA tiles (persistent kernel)
 constexpr int BTOK = 256, BCH = 128, BIG_NT = 256, BIG_STAGES = 3;
 constexpr int BIG_A_BYTES = BTOK * BK;                 // 16 KiB
 constexpr int BIG_STAGE = (BTOK + BCH) * BK;           // 24 KiB
@@ -1119,8 +890,3 @@ IVIT_DEV void pers_table_write(const PersTableLoad& r, char* tab, int tid)
 // whole one (DeiT-B, N = 768: 1182 tiles on 512 workgroups = 2.31 rounds -> 2.5 instead of 3).
 
 }  // namespace
-
-// kernel forms of gemm_lab.hip: returns 1 if `g_debug_flags` selected one of them and it was launched (status in *rc)
-#if IVIT_LAB
-int ivit_gemm_lab_launch(int epi, void* gemm_args, const char* name, ivit_stream_t stream, int* rc);
-#endif

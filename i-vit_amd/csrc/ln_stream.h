@@ -346,8 +346,8 @@ __global__ __launch_bounds__(NT, OCC) void layernorm_i8_stream_kernel(LnArgs a)
             // Issue priority by progress: the SIMD arbitrates by priority, then age, so at equal priority the four waves of a SIMD
             // finish one after another and the youngest ends alone, at a single wave's issue rate (4.9 instead of 1.95 / 3.2 cycles
             // per instruction).  A wave that is behind gets the higher priority: they finish together (20.2 vs 21.4 us, natural
-            // scales 21.7 vs 23.6: profiles/r04i_*).  Lab bit 5: off.
-            if (!(abl & 32)) {
+            // scales 21.7 vs 23.6: profiles/r04i_*).
+            {
                 const int q4 = (4 * k) / g_cnt;
                 if (q4 == 0) __builtin_amdgcn_s_setprio(3);
                 else if (q4 == 1) __builtin_amdgcn_s_setprio(2);
@@ -374,7 +374,7 @@ __global__ __launch_bounds__(NT, OCC) void layernorm_i8_stream_kernel(LnArgs a)
         // the current one is done.
         for (int k = 0; k < g_cnt; k += 2) {
             load_group(k + 1, w[1]);
-            if (!(abl & 32)) {  // issue priority by progress, as in the rounds loop above
+            {   // issue priority by progress, as in the rounds loop above
                 const int q4 = (4 * k) / g_cnt;      // quarter of the wave's groups it is in
                 if (q4 == 0) __builtin_amdgcn_s_setprio(3);
                 else if (q4 == 1) __builtin_amdgcn_s_setprio(2);

@@ -18,7 +18,7 @@
 // (ivit_debug_ln_wave_per_row)
 #if IVIT_LAB
 int g_ln_wave_per_row = 0;
-int g_ln_ablate = 0;     // lab build only (ivit_debug_ln_ablate): 1 no element chain, 2 no statistics, 4 no stores, 8 no table build
+int g_ln_ablate = 0;     // lab build only (ivit_debug_ln_ablate, include/ivit_hip_debug.h); also read by swin.hip (bits 16-20, 23)
 int g_ln_stream_cfg = 0; // lab build only (ivit_debug_ln_stream_cfg): ring depth / workgroups per CU of the streaming kernel
 unsigned long long* g_ln_stamps = nullptr;   // lab build only (ivit_debug_ln_stamp_buffer): 8 x s_memrealtime per wave of the streaming kernel
 #else
@@ -512,20 +512,10 @@ __global__ __launch_bounds__(NT, NJ <= 3 ? 4 : 3) void layernorm_i8_pair_kernel(
                 sq[q] = __builtin_amdgcn_sdot4(w[q][j], w[q][j], sq[q], false);   // <= 1536 * 128^2 < 2^25
             }
         }
-        if (IVIT_LAB && (a.abl & (1 << 27))) {      // lab A/B: the ds_bpermute butterfly of rounds 2-4
 #pragma unroll
-            for (int o = 16; o > 0; o >>= 1)
-#pragma unroll
-                for (int q = 0; q < G2; ++q) {
-                    sum[q] += __shfl_xor(sum[q], o);
-                    sq[q] += __shfl_xor(sq[q], o);
-                }
-        } else {
-#pragma unroll
-            for (int q = 0; q < G2; ++q) {
-                sum[q] = half_wave_allreduce(sum[q]);
-                sq[q] = half_wave_allreduce(sq[q]);
-            }
+        for (int q = 0; q < G2; ++q) {
+            sum[q] = half_wave_allreduce(sum[q]);
+            sq[q] = half_wave_allreduce(sq[q]);
         }
         // lane (half, l32 = q) : statistics of row 2q + half, computed once; ivit_modules.py:37, 40-51
         int my_sum = sum[0], my_sq = sq[0];
@@ -643,9 +633,9 @@ __global__ __launch_bounds__(NT, NJ <= 3 ? 4 : 3) void layernorm_i8_pair_kernel(
 // (COMPAT at groups of 8: three workgroups per CU -- at four the remap tables' extra registers spilled six dwords; natural-scale
 // DeiT-B b256 6.95 -> 6.90 ms)
 template <int NJ, bool COMPAT, int G>
-__global__ __launch_bounds__(NT, (G == 4 && NJ <= 3 ? 5 : G == 8 && NJ <= 3 ? (COMPAT ? 3 : 4) : NJ <= 1 ? 4 : NJ <= 3 ? 3 : 2)) void layernorm_i8_v2_kernel(LnArgs a)
+__global__ __launch_bounds__(NT, (G == 8 && NJ <= 3 ? (COMPAT ? 3 : 4) : NJ <= 1 ? 4 : NJ <= 3 ? 3 : 2)) void layernorm_i8_v2_kernel(LnArgs a)
 {
-    static_assert(G == 4 || G == 8 || G == 16, "G");
+    static_assert(G == 8 || G == 16, "G");
     typedef unsigned v2u __attribute__((ext_vector_type(2)));
     extern __shared__ __attribute__((aligned(16))) float lds_tab[];   // [C] bias | [C] lo | [C] hi
     __shared__ unsigned char s_remap[COMPAT ? 256 : 4];
@@ -664,12 +654,6 @@ __global__ __launch_bounds__(NT, (G == 4 && NJ <= 3 ? 5 : G == 8 && NJ <= 3 ? (C
     __syncthreads();
     const int8_t* xin = reinterpret_cast<const int8_t*>(a.x);
     int8_t* out = reinterpret_cast<int8_t*>(a.out);
-#if IVIT_LAB
-    if ((abl & 128) && (blockIdx.x & 1)) {      // lab: start every other workgroup late (phase-overlap experiment)
-        const int units = (abl >> 8) & 15;
-        for (int it = 0; it < units; ++it) __builtin_amdgcn_s_sleep(127);
-    }
-#endif
     BlockCol bcol[NJ];
 #pragma unroll
     for (int j = 0; j < NJ; ++j) bcol[j] = block_col(4 * (lane + 64 * j));
@@ -700,9 +684,8 @@ __global__ __launch_bounds__(NT, (G == 4 && NJ <= 3 ? 5 : G == 8 && NJ <= 3 ? (C
             }
         }
     };
-    int step = ((wave_id & 1) != 0 && (abl & 64) != 0) ? G / 2 : G;     // lab bit 6: the de-phasing experiment (no gain)
-    for (int row0 = r_begin; row0 < r_end; row0 += step, step = G) {
-        const int nrow = min(step, r_end - row0);
+    for (int row0 = r_begin; row0 < r_end; row0 += G) {
+        const int nrow = min(G, r_end - row0);
         int w[G][NJ];
         int s1[G], s2[G];
         int sq[COMPAT ? G : 1];
@@ -732,19 +715,7 @@ __global__ __launch_bounds__(NT, (G == 4 && NJ <= 3 ? 5 : G == 8 && NJ <= 3 ? (C
         constexpr int LPR = 64 / G;          // lanes that end up holding one row's totals
         auto treduce = [&](int (&v)[G]) -> int {
             int t8[8], t4[4], t2[2];
-            if constexpr (G == 4) {
-                for (int i = 0; i < 2; ++i) {
-                    const v2u r = __builtin_amdgcn_permlane32_swap((unsigned)v[i], (unsigned)v[i + 2], false, false);
-                    t2[i] = (int)(r.x + r.y);
-                }
-                const v2u r = __builtin_amdgcn_permlane16_swap((unsigned)t2[0], (unsigned)t2[1], false, false);
-                int t = (int)(r.x + r.y);
-                t += __shfl_xor(t, 8);
-                t += __shfl_xor(t, 4);
-                t += __shfl_xor(t, 2);
-                t += __shfl_xor(t, 1);
-                return t;
-            } else if constexpr (G == 16) {
+            if constexpr (G == 16) {
 #pragma unroll
                 for (int i = 0; i < 8; ++i) {
                     const v2u r = __builtin_amdgcn_permlane32_swap((unsigned)v[i], (unsigned)v[i + 8], false, false);
@@ -1598,19 +1569,17 @@ static int launch_ln_v2(const LnArgs& a, hipStream_t st, const char* who)
     // timeline is serial -- first loads, arithmetic, store drain -- so shorter waves that start as others finish overlap those
     // phases across waves, which neither prefetching nor de-phasing a resident set achieved.
     // At four times the rows the order flips (90.9 vs 87.6 us: the statistics are paid once per 16 rows and a resident set then
-    // has several groups per wave anyway); groups of 4 rows: 27.0 us.  Lab bits 4-5: 1 / 2 / 3 force groups of 8 / 16 / 4.
+    // has several groups per wave anyway); groups of 4 rows: 27.0 us.  Lab bits 4-5: 1 / 2 force groups of 8 / 16.
     const int force = (a.abl >> 4) & 3;
-    const bool g8 = force == 1 || force == 3 || (force == 0 && a.rows <= 131072);
-    const bool g4 = force == 3;
-    const int gsz = g4 ? 4 : g8 ? 8 : 16;
+    const bool g8 = force == 1 || (force != 2 && a.rows <= 131072);
+    const int gsz = g8 ? 8 : 16;
     int grid = (int)(((int64_t)a.rows + gsz * WPB - 1) / (gsz * WPB));    // one full group per wave
     if (grid > resident && !g8) grid = resident;
     if (grid < 1) grid = 1;
     const size_t lds = (size_t)3 * a.C * sizeof(float);
 #define IVIT_LN_V2(NJv)                                                                                              \
     do {                                                                                                             \
-        if (g4) hipLaunchKernelGGL((layernorm_i8_v2_kernel<NJv, COMPAT, 4>), dim3(grid), dim3(NT), lds, st, a);      \
-        else if (g8) hipLaunchKernelGGL((layernorm_i8_v2_kernel<NJv, COMPAT, 8>), dim3(grid), dim3(NT), lds, st, a); \
+        if (g8) hipLaunchKernelGGL((layernorm_i8_v2_kernel<NJv, COMPAT, 8>), dim3(grid), dim3(NT), lds, st, a); \
         else hipLaunchKernelGGL((layernorm_i8_v2_kernel<NJv, COMPAT, 16>), dim3(grid), dim3(NT), lds, st, a);        \
     } while (0)
     if (nj <= 1) IVIT_LN_V2(1);
@@ -1709,7 +1678,7 @@ IVIT_EXPORT int ivit_layernorm_i8_ex(const int8_t* x, int64_t ldx, int rows, int
         const size_t lds = (size_t)3 * C * sizeof(float);
         // C <= 128 (Swin's patch norm, 401 408 rows of 96): one dword per lane -- the NJ = 2 form computes a second, fully masked one
         // -- and 8 row pairs per wave from 64 K rows (the row statistics of 16 rows in one pass of lanes 0-7)
-        const bool one = nj2 == 1 && g2 == 4 && !(g_ln_ablate & (1u << 25));
+        const bool one = nj2 == 1 && g2 == 4;
         if (one && rows > 65536 && !(g_ln_ablate & (1u << 26))) {
             grid = grid_for_rows(rows, 16);
             if (grid > 1024) grid = 1024;
@@ -1862,11 +1831,10 @@ IVIT_DEV int half_wave_allmax(int v)
     return max((int)r.x, (int)r.y);
 }
 
-// PIPE (lab bit 28; measured 57.2 us against 55.3 without at 401 408 rows of 384, so not the product form): the rows of the NEXT
-// iteration are requested right after this iteration's table slices -- the slices are the older loads, so the wait for them leaves the
-// rows in flight (loads return in order).  What the launch was missing were unconditional loads (shiftgelu_lut_apply_kernel): 72.8 ->
-// 55-57 us (5.4-5.6 TB/s) with them, eight waves per SIMD hide the chain of an iteration without a prefetch.
-template <int NJ, bool INB, bool PIPE = false>
+// What the launch was missing were unconditional loads (shiftgelu_lut_apply_kernel): 72.8 -> 55-57 us (5.4-5.6 TB/s) at 401 408 rows
+// of 384 with them; eight waves per SIMD hide the chain of an iteration without a prefetch of the next iteration's rows (tried: 57.2
+// against 55.3 us, profiles/HISTORY.md).
+template <int NJ, bool INB>
 __global__ __launch_bounds__(NT) void shiftgelu_lut_apply_half_kernel(GeluArgs a)
 {
     constexpr int RP = 2;                      // row pairs per wave and iteration
@@ -1891,9 +1859,8 @@ __global__ __launch_bounds__(NT) void shiftgelu_lut_apply_half_kernel(GeluArgs a
         }
     };
     const int row_first = (blockIdx.x * WPB + wave) * (2 * RP);
-    if (PIPE && row_first < a.rows) load_rows(w, row_first);
     for (int row0 = row_first; row0 < a.rows; row0 += stride) {
-        if (!PIPE) load_rows(w, row0);
+        load_rows(w, row0);
         int kmax[RP];
 #pragma unroll
         for (int p = 0; p < RP; ++p) {
@@ -1908,8 +1875,6 @@ __global__ __launch_bounds__(NT) void shiftgelu_lut_apply_half_kernel(GeluArgs a
 #pragma unroll
         for (int p = 0; p < RP; ++p)           // each half wave fetches its row's 256-byte slice: 8 bytes per lane
             slice[p] = reinterpret_cast<const int2*>(a.lut + (int64_t)(kmax[p] + 128) * 256)[l32];
-        int wn[RP][NJ];
-        if (PIPE) load_rows(wn, row0 + stride);      // unconditional (rows clamp to the last one: the final iteration's prefetch is not used)
 #pragma unroll
         for (int p = 0; p < RP; ++p) reinterpret_cast<int2*>(tab[wave][2 * p + half])[l32] = slice[p];
         __builtin_amdgcn_wave_barrier();
@@ -1934,12 +1899,6 @@ __global__ __launch_bounds__(NT) void shiftgelu_lut_apply_half_kernel(GeluArgs a
             }
         }
         __builtin_amdgcn_wave_barrier();
-        if (PIPE) {
-#pragma unroll
-            for (int p = 0; p < RP; ++p)
-#pragma unroll
-                for (int j = 0; j < NJ; ++j) w[p][j] = wn[p][j];
-        }
     }
 }
 
@@ -1963,11 +1922,10 @@ IVIT_EXPORT int ivit_shiftgelu_lut_i8_ex(const int8_t* x, int64_t ldx, int rows,
     const int nj = (L / 4 + 63) / 64;
     if (L <= 384 && rows >= 4096 && !(g_ln_ablate & (1 << 24))) {      // lab bit 24: the whole-wave-per-row form (A/B, parity of both)
         const dim3 gridh(grid_for_rows(rows, 4));
-#define IVIT_GELU_HALF(NJ_, ...) do { if (in_blocks) hipLaunchKernelGGL((shiftgelu_lut_apply_half_kernel<NJ_, true, ##__VA_ARGS__>), gridh, blk, 0, st, a); \
-                                      else hipLaunchKernelGGL((shiftgelu_lut_apply_half_kernel<NJ_, false, ##__VA_ARGS__>), gridh, blk, 0, st, a); } while (0)
+#define IVIT_GELU_HALF(NJ_) do { if (in_blocks) hipLaunchKernelGGL((shiftgelu_lut_apply_half_kernel<NJ_, true>), gridh, blk, 0, st, a); \
+                                 else hipLaunchKernelGGL((shiftgelu_lut_apply_half_kernel<NJ_, false>), gridh, blk, 0, st, a); } while (0)
         if (L <= 128) IVIT_GELU_HALF(1);
         else if (L <= 256) IVIT_GELU_HALF(2);
-        else if (IVIT_LAB && (g_ln_ablate & (1 << 28))) IVIT_GELU_HALF(3, true);   // lab A/B: with the prefetch of the next iteration's rows
         else IVIT_GELU_HALF(3);
 #undef IVIT_GELU_HALF
         IVIT_CHECK_LAUNCH("ivit_shiftgelu_lut_i8");

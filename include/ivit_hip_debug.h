@@ -1,6 +1,14 @@
 /*
- * ivit_hip_debug.h -- test and measurement hooks of libivit_hip.so.  NOT part of the drop-in boundary
- * (include/ivit_hip.h): process-wide, not thread-safe, for tests/ and scripts/ only.
+ * ivit_hip_debug.h -- test and measurement hooks of libivit_hip_lab.so (csrc built with IVIT_LAB = 1).  NOT part of the
+ * drop-in boundary (include/ivit_hip.h) and not in libivit_hip.so: process-wide, not thread-safe, for tests/ and scripts/ only.
+ *
+ * Two kinds of hook, nothing else:
+ *   form selector   forces a kernel form that the product library itself launches for some other shape or scale, so that tests
+ *                   pin every product form on the same inputs.  Results stay correct.
+ *   instrument      time stamps, or "skip this phase" timing ablations, of a kernel the product ships.  Ablations make the
+ *                   results WRONG; they exist to be timed.
+ * Forms that were tried and lost are not kept here: profiles/HISTORY.md and the git history are their record.
+ * Every bit of every word has one meaning and one reader; bits not listed are ignored.  0 restores the product's behaviour.
  */
 #ifndef IVIT_HIP_DEBUG_H
 #define IVIT_HIP_DEBUG_H
@@ -9,71 +17,114 @@
 extern "C" {
 #endif
 
-/* Test hook: ivit_gemm_i8_* pick between two kernels by problem size (a 256x128-tile LDS-DMA kernel
- * for M >= 2048, N >= 128; a 128x128-tile kernel otherwise).  on != 0 forces the small-tile kernel so
- * tests can cover both on the same inputs.  Process-wide, not thread-safe; not for production use. */
+/* ivit_gemm_i8_* (csrc/gemm.hip)
+ *   value | meaning                                                                 | results | used by
+ *   ------+-------------------------------------------------------------------------+---------+--------------------------------
+ *   0     | automatic: the persistent 256 x 128 LDS-DMA kernel for M >= 2048,       | correct |
+ *         | N >= 128, the 128 x 128 register-staged kernel otherwise                |         |
+ *   != 0  | always the 128 x 128 kernel (selector; also keeps the skinny-K form off) | correct | tests/test_gpu_ops.py,
+ *         |                                                                         |         | scripts/gemm_ab.py */
 int ivit_debug_force_small_gemm(int on);
-/* Perf-ablation hook for scripts/gemm_ablate.py (bit 0: skip the in-loop DMA, bit 1: skip the MFMAs,
- * bit 2: skip the epilogue, ...); results are WRONG whenever flags & 1023 != 0.  Bits that keep results correct
- * (A/B timing): 64 no start stagger, 1024 the relaunch-per-tile form instead of the persistent one, 2048 split a sparse last
- * round of tiles into half tiles, 4096 one workgroup per CU, 32768 per-CU turn-taking of the main loops, bits 16-21 start delay of the second co-resident workgroup in
- * ~1K-cycle units, bit 26 a 256-workgroup grid of the persistent kernel without the LDS blocker (two-stream probe). */
+
+/* ivit_gemm_i8_* (csrc/gemm.hip), first flag word
+ *   bits      | meaning                                                              | results | used by
+ *   ----------+----------------------------------------------------------------------+---------+-----------------------------
+ *   0-3       | weights-in-registers kernel, 32x32x32 form, ivit_gemm_i8_requant_ex: | WRONG   | scripts/gemm_ab.py --frags,
+ *             | timing ablations 1 no epilogue, 2 no weight loads in the loop, 4 no  |         | scripts/gemm_ablate.py
+ *             | DMA in the loop, 8 no MFMA; the sums 6, 7, 14, 15 exist too          |         |
+ *   4 (16)    | the same kernel writes its stamps: 32 x uint64 per                   | WRONG   | scripts/wreg_timeline.py
+ *             | (workgroup, tile < 4) into the stamp buffer; alone in bits 0-4       |         |
+ *   6 (64)    | persistent kernel: no start stagger of the co-resident workgroups    | correct | scripts/gemm_ab.py
+ *   11 (2048) | both large kernels: split a sparse last round into half tiles up to  | correct | tests/test_gpu_ops.py,
+ *             | 2R <= all workgroup slots (the product stops at 2R <= 256)           |         | scripts/gemm_ab.py
+ *   12 (4096) | persistent kernel: one workgroup per CU (with bit 4: the stamped     | correct | tests/test_gpu_ops.py,
+ *             | kernel likewise)                                                     |         | scripts/wreg_timeline.py,
+ *             |                                                                      |         | scripts/gemm_one.py
+ *   15 (32768)| persistent kernel: co-resident workgroups take turns in their main   | correct | scripts/gemm_ab.py
+ *             | loops through a per-CU token                                         |         |
+ *   16-21     | persistent kernel: start delay of the second co-resident workgroup,  | correct | scripts/gemm_ab.py
+ *             | in ~1K-cycle units                                                   |         |
+ *   26        | persistent kernel: a 256-workgroup grid without the LDS blocker      | correct | scripts/dual_stream_probe.py
+ *   27        | both large kernels: no half tiles at all                             | correct | scripts/gemm_ab.py */
 int ivit_debug_set_gemm_flags(int flags);
-/* Second flag word: A/B of cache policies in the GEMM epilogue (results stay correct).  Bits 0-1: policy of the int8 output
- * stores (0 plain, 1 nt, 2 sc1, 3 sc0 sc1); bit 2: the residual operand is read with nt loads; bit 13: narrow (128 x 128) work items of
- * the weights-in-registers kernel (16x16x64 form; measured slower than its 128 x 256 tiles, scripts/gemm_narrow_ab.py); bit 15: the
- * wave-pipelined form of csrc/gemm_wp.h (one workgroup of eight waves per CU, a tile's epilogue inside the next tile's main loop;
- * plain and head-major int8 epilogues, K >= 768; exact, measured slower), bits 16-17 its timing ablations (results WRONG: 1 no
- * epilogue work inside the loop, 2 no barrier per K step); scripts/gemm_ab.py --frags16 ... -- 0:0 0:32768 0:98304; bit 20: no
- * skinny-K form (K <= 128, N <= 320, M >= 8192: the tile kernels instead; A/B and parity of both), bit 21: the skinny-K form's
- * run-time-K instantiation also for K = 64 / 128 (the form before the compile-time ones) */
+
+/* ivit_gemm_i8_* (csrc/gemm.hip), second flag word
+ *   bits      | meaning                                                              | results | used by
+ *   ----------+----------------------------------------------------------------------+---------+-----------------------------
+ *   8 (256)   | weights-in-registers kernel, 16x16x64 form, plain and residual       | correct | scripts/wreg_timeline.py
+ *             | epilogue: the stamped instantiation, if a stamp buffer is set (stamps|         | --s16
+ *             | kept in registers until the tile ends: the timing is the product's)  |         |
+ *   13 (8192) | the same kernel: narrow 128 x 128 work items.  The product compiles  | correct | tests/test_gpu_ops.py,
+ *             | this arm into its kernels (a run-time branch) and launches it for no |         | scripts/gemm_narrow_ab.py
+ *             | shape: measured slower (x 1.08 - 1.44, profiles/HISTORY.md)          |         |
+ *   20        | no skinny-K form (K <= 128, N <= 320, M >= 8192): the tile kernels   | correct | tests/test_gpu_ops.py,
+ *             | the product uses for every other shape (selector)                    |         | scripts/gemm_ab.py
+ *   21        | the skinny-K form's run-time-K instantiation also for K = 64 / 128   | correct | tests/test_gpu_ops.py
+ *             | (the product uses it for every other K; selector)                    |         | */
 int ivit_debug_set_gemm_flags2(int flags);
-/* Diagnostic timeline buffer (8 x uint64 per workgroup) for the stamped build (flags = 512); scripts/gemm_timeline.py */
+
+/* Device buffer for the stamped weights-in-registers kernels (flags bit 4, flags2 bit 8): 32 x uint64 per (workgroup,
+ * tile < 4) -- tile start, loop start, loop end, epilogue end, K-step starts / epilogue phases, s_memrealtime at [16].
+ * NULL = off.  scripts/wreg_timeline.py */
 int ivit_debug_set_stamp_buffer(void* buf);
 
-/* ivit_layernorm_i8 kernel form: 0 = automatic (the streaming kernel of ln_stream.h for C = 192 / 384 / 512 / 768 / 1024,
- * else half a wave per row for C <= 384, the grouped kernel up to 1024, a wave per row above), 1 = always a wave per row,
- * 2 = half a wave per row wherever it exists (C <= 1536), 3 = the automatic choice without the streaming kernel (rounds 2-3),
- * 4 = the streaming kernel wherever it applies, whatever the size: parity tests of every form, A/B timing */
+/* ivit_layernorm_i8(_ex, _compat) kernel form (csrc/rowops.hip); every value is a selector, results correct
+ *   value | meaning                                                                            | used by
+ *   ------+------------------------------------------------------------------------------------+-----------------------------
+ *   0     | automatic: the streaming kernel of ln_stream.h for C = 192 / 384 / 512 / 768 / 1024 |
+ *         | from ~12 MB of rows, else half a wave per row for C <= 384, the grouped kernel up   |
+ *         | to 1024, a wave per row above                                                       |
+ *   1     | always a wave per row                                                              | tests/test_gpu_ops.py,
+ *   2     | half a wave per row wherever it exists (C <= 1536)                                 | tests/test_gpu_compat.py,
+ *   3     | the automatic choice without the streaming kernel                                  | scripts/ln_ab.py,
+ *   4     | the streaming kernel wherever it applies, whatever the size                        | scripts/ln_ablate.py */
 int ivit_debug_ln_wave_per_row(int on);
 
-/* streaming LayerNorm kernel, A/B timing (results stay correct): bits 0-3 ring depth (2, 3, 6; else the default 4; C = 768
- * only), bits 4-7 workgroups per CU (1-4; 0 = the default 2); scripts/ln_ablate.py */
+/* streaming LayerNorm kernel (csrc/ln_stream.h), A/B timing; results correct
+ *   bits | meaning                                                                   | used by
+ *   -----+---------------------------------------------------------------------------+----------------------------------------
+ *   0-3  | C = 768 only: ring depth / occupancy variant (1, 3-7; 0 = the product's)  | scripts/ln_ab.py, scripts/ln_one.py,
+ *   4-7  | workgroups per CU the grid and the LDS request are sized for (0 = 4)      | scripts/ln_timeline.py */
 int ivit_debug_ln_stream_cfg(int cfg);
+
 /* wave timeline of the streaming LayerNorm kernel: 8 x uint64 per wave (s_memrealtime, 100 MHz: entry, table ready, slots 0-2 of
  * the first round computed, -, all stores done, groups of the wave); NULL = off; scripts/ln_timeline.py */
 int ivit_debug_ln_stamp_buffer(void* buf);
 
-/* timing ablations of the default int8 LayerNorm kernel (results WRONG when non-zero): 1 no element chain, 2 no row
- * statistics, 4 no stores, 8 no per-workgroup table build; correct results: bits 4-5 = 1 / 2 / 3 force groups of 8 rows (oversubscribed
- * grid) / 16 rows (one resident set of workgroups) / 4 rows, bit 6 odd waves start with half a group, bit 7 + bits 8-11 delayed start of every
- * other workgroup; bits 16-19 workgroup cap of the tiled 16-bit LayerNorm (x 256), bit 20 natural-scale 16-bit LayerNorm with its
- * row sums through LDS (the round-3 form; results stay correct), bits 21-22 = 1 / 2 / 3 the half-wave int8 kernel with 4 / 2 / 1 row
- * pairs per wave whatever the row count, bit 23 the Swin window attention requantises its scores in float64 also where the float32
- * form is exact (power-of-two multipliers), bit 24 the ShiftGELU table pass takes a whole wave per row also for rows of at most 384
- * bytes, bit 25 rows of at most 128 channels on the two-dword half-wave kernel (the form before round 4's one-dword one), bit 26
- * the one-dword kernel with 4 row pairs per wave also from 64 K rows, bit 27 the half-wave kernel's row sums by ds_bpermute butterflies
- * (the form before the DPP / v_permlane16_swap one), bit 28 the short-row ShiftGELU table pass with a prefetch of the next
- * iteration's rows (measured: no gain); scripts/ln_ablate.py, scripts/ln_ab.py --small, scripts/time_swin_kernels.py */
+/* row operators (csrc/rowops.hip, csrc/ln_stream.h) and Swin kernels (csrc/swin.hip)
+ *   bits   | reader     | meaning                                                       | results | used by
+ *   -------+------------+---------------------------------------------------------------+---------+--------------------------
+ *   0-3    | rowops.hip,| int8 LayerNorm, grouped and streaming kernels: timing         | WRONG   | scripts/ln_ablate.py,
+ *          | ln_stream.h| ablations 1 no element chain, 2 no row statistics, 4 no       |         | scripts/ln_timeline.py
+ *          |            | stores, 8 no per-workgroup table build (grouped kernel only)  |         |
+ *   4-5    | rowops.hip | grouped int8 LayerNorm: 1 groups of 8 rows on an              | correct | scripts/ln_ablate.py,
+ *          |            | oversubscribed grid, 2 groups of 16 rows on one resident set  |         | scripts/ln_ab.py
+ *          |            | (the product picks by row count; selector)                    |         |
+ *   16-19  | swin.hip   | workgroup cap of the tiled 16-bit LayerNorm, x 256 (0 = 1024) | correct | scripts/probes/ln16_cap.py
+ *   20     | swin.hip   | natural-scale 16-bit LayerNorm: row sums through LDS also     | correct | tests/test_gpu_swin.py,
+ *          |            | where the register form applies (selector)                    |         | scripts/time_swin_kernels.py
+ *   21-22  | rowops.hip | half-wave int8 LayerNorm: 1 / 2 / 3 = 4 / 2 / 1 row pairs per | correct | scripts/ln_ab.py --small
+ *          |            | wave whatever the row count (selector)                        |         |
+ *   23     | swin.hip   | window attention: scores requantised in float64 also where    | correct | tests/test_gpu_swin.py,
+ *          |            | the float32 form is exact (selector)                          |         | scripts/time_swin_kernels.py
+ *   24     | rowops.hip | ShiftGELU table pass: a whole wave per row also for rows of   | correct | tests/test_gpu_ops.py
+ *          |            | at most 384 bytes (selector)                                  |         |
+ *   26     | rowops.hip | one-dword half-wave LayerNorm (C <= 128): 4 row pairs per     | correct | scripts/ln_ab.py --small
+ *          |            | wave also from 64 K rows (selector)                           |         |
+ * No attention kernel reads this word: see ivit_debug_attention. */
 int ivit_debug_ln_ablate(int bits);
 
-/* (lab library only since round 4: the engines never called it and it is slower than the pair it replaces)
- * EXPERIMENTAL -- measured SLOWER than the two launches it replaces ("ShiftGELU stays a pass of its own"); kept,
- * bit-exact and tested, as the record of that experiment; the engines do not call it.
- * mlp.fc1 + mlp.qact_gelu + ShiftGELU + mlp.qact1 in ONE launch (layers_quant.py:141-146; ivit_modules.py:105-126):
- *   k   = clamp8(RNE(acc * m[n] / 2^e[n]))                  as ivit_gemm_i8_requant_ex
- *   out = gelu_lut[(max_n k[t][:] + 128) * 256 + (k + 128)]   the table of ivit_shiftgelu_build_lut(_ex): ShiftGELU with the row
- *                                                             maximum over all N outputs of token t, requantised by mlp.qact1
- * = ivit_gemm_i8_requant_ex followed by ivit_shiftgelu_lut_i8_ex in place, bit for bit: every channel tile counts itself in at
- * its 128-token panel and the workgroup that completes a panel reads it back, takes the row maxima and maps it
- * (gemm_common.h: gelu_panel_phase).  Needs the weights-in-registers kernel: layouts contains IVIT_W_FRAGS16 (M >= 2048,
- * K % 192 == 0, N % 64 == 0, 128 <= N <= 4096), optionally IVIT_A_BLOCKS / IVIT_OUT_BLOCKS.
- * `workspace`: ivit_gemm_gelu_workspace_bytes(M) bytes = 4 * ceil(M / 128), owned by the caller, ZERO before the first launch;
- * every launch leaves it zero again (launches that share a workspace must not overlap). */
-int ivit_gemm_gelu_workspace_bytes(int M, int64_t* bytes);
-int ivit_gemm_i8_requant_gelu_ex(const int8_t* A, int64_t lda, const int8_t* W, int64_t ldw, const int32_t* bias,
-                                 const uint32_t* m, const int32_t* e, const int8_t* gelu_lut, void* workspace,
-                                 int8_t* out, int64_t ldo, int M, int N, int K, int layouts, ivit_stream_t stream);
+/* ivit_attention_fused_i8* for at most 208 tokens (csrc/attention.hip)
+ *   bits  | meaning                                                                      | results | used by
+ *   ------+------------------------------------------------------------------------------+---------+--------------------------
+ *   0-4   | phase ablations of attention_kernel<0>: 1 no score requantisation, 2 no      | WRONG   | scripts/attn_ablate.py
+ *         | table lookups, 4 no probability products, 8 no P.V and output, 16 one query  |         |
+ *         | tile per wave                                                                |         |
+ *   5     | no float32 score requantisation where the multiplier is a power of two: the  | correct | scripts/attn_ablate.py
+ *         | general form instead (selector)                                              |         |
+ *   8-10  | forced number of workgroups per (image, head), 1-7 (0 = the model's choice;  | correct | scripts/attn_parts.py,
+ *         | selector)                                                                    |         | */
+int ivit_debug_attention(int bits);
 
 #ifdef __cplusplus
 }

@@ -1,4 +1,4 @@
-"""Ablation of the fused attention kernel (lab build; bits 20-24 of ivit_debug_ln_ablate): what each phase costs.
+"""Ablation of the fused attention kernel (lab build; bits 0-4 of ivit_debug_attention): what each phase costs.
 1 no score requant / clamp, 2 no table lookups, 4 no probability products, 8 no P.V + output, 16 one query tile per wave
 (K / V staging + one tile: the fixed cost of a workgroup)."""
 import os; os.environ.setdefault("IVIT_USE_LAB_LIBRARY", "1")
@@ -22,9 +22,9 @@ def run():
               _lib.stream_ptr())
 
 
-# bit 6 (= bit 26 of the knob): the float64 requantisation of the scores instead of the float32 one (A/B of attention_kernel<.., RQ32>)
-for bits in [int(x) for x in (sys.argv[1:] or ["0", "64", "1", "2", "4", "8", "3", "7", "15", "16", "31"])]:
-    _lib.call("ivit_debug_ln_ablate", bits << 20)
+# 32 (bit 5): the general requantisation of the scores instead of the float32 one (A/B of attention_kernel<.., RQ32>)
+for bits in [int(x) for x in (sys.argv[1:] or ["0", "32", "1", "2", "4", "8", "3", "7", "15", "16", "31"])]:
+    _lib.call("ivit_debug_attention", bits)
     for _ in range(5):
         run()
     torch.cuda.synchronize()
@@ -35,4 +35,4 @@ for bits in [int(x) for x in (sys.argv[1:] or ["0", "64", "1", "2", "4", "8", "3
     e1.record()
     torch.cuda.synchronize()
     print(f"ablate {bits:2d}: {e0.elapsed_time(e1) / 20 * 1e3:7.1f} us", flush=True)
-_lib.call("ivit_debug_ln_ablate", 0)
+_lib.call("ivit_debug_attention", 0)

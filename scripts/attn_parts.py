@@ -1,4 +1,4 @@
-"""Workgroups per (image, head) of the fused attention kernel against the batch (lab build; bits 28-30 of ivit_debug_ln_ablate
+"""Workgroups per (image, head) of the fused attention kernel against the batch (lab build; bits 8-10 of ivit_debug_attention
 force the split): the launch time for parts = 1, 2, 4 and what attention_parts() picks (0 = its own choice)."""
 import os; os.environ.setdefault("IVIT_USE_LAB_LIBRARY", "1")
 import sys
@@ -17,7 +17,7 @@ for B, H in [(1, 3), (1, 12), (16, 12), (32, 12), (64, 6), (64, 12), (96, 12), (
     out = torch.empty(B * T, H * HD, dtype=torch.int8, device=DEV)
     res = {}
     for parts in (0, 1, 2, 4):
-        _lib.call("ivit_debug_ln_ablate", parts << 28)
+        _lib.call("ivit_debug_attention", parts << 8)
         def run():
             _lib.call("ivit_attention_fused_i8", _lib.ptr(qkv), _lib.ptr(out), B, H, T, HD, int(ms[0]), int(es[0]), 0.25, int(mo[0]),
                       int(eo[0]), _lib.stream_ptr())
@@ -32,4 +32,4 @@ for B, H in [(1, 3), (1, 12), (16, 12), (32, 12), (64, 6), (64, 12), (96, 12), (
         torch.cuda.synchronize()
         res[parts] = e0.elapsed_time(e1) / 30 * 1e3
     print(f"B={B:4d} H={H:2d} (B*H={B*H:5d}): auto {res[0]:6.1f}  parts 1 {res[1]:6.1f}  2 {res[2]:6.1f}  4 {res[4]:6.1f} us", flush=True)
-_lib.call("ivit_debug_ln_ablate", 0)
+_lib.call("ivit_debug_attention", 0)

@@ -25,7 +25,7 @@ def time_us(fn, n=40):
 shapes = [(197 * 256, 768), (197 * 64, 384), (197 * 128, 768), (197 * 1024, 768), (197, 192)]
 if len(sys.argv) > 1 and sys.argv[1] == "--headline":
     shapes = shapes[:1]
-variants = [("grouped(r3)", 3, 0, 0), ("stream", 0, 0, 0), ("stream equal-prio", 0, 0, 32), ("stream ng2", 0, 4, 0), ("stream dbuf", 0, 5, 0),
+variants = [("grouped(r3)", 3, 0, 0), ("stream", 0, 0, 0), ("stream ng2", 0, 4, 0), ("stream dbuf", 0, 5, 0),
             ("stream 5 wg/CU", 0, 7 | (5 << 4), 0), ("stream 6 wg/CU", 0, 6 | (6 << 4), 0)]
 if len(sys.argv) > 1 and sys.argv[1] == "--small":     # launches below ~12 MB: the half-wave kernel with 4 / 2 / 1 row pairs per wave (lab bits 21-22)
     shapes = [(197 * 64, 384), (197 * 16, 384), (197, 192), (197 * 8, 192)]

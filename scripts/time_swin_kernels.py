@@ -78,7 +78,7 @@ if "lnc" in which:     # natural-scale 16-bit LayerNorm: registers (product) aga
             print(f"ln16 natural rows={rows:7d} C={C:4d} outer-reduction order: registers {np.median(ro[0]):7.1f} us   LDS sums {np.median(ro[1 << 20]):7.1f} us", flush=True)
         print(f"ln16 natural rows={rows:7d} C={C:4d}: registers {np.median(res[0]):7.1f} us   LDS sums {np.median(res[1 << 20]):7.1f} us   "
               f"(power-of-two kernel {us:7.1f} us; {3 * rows * C / np.median(res[0]) / 1e3:7.1f} GB/s algorithmic)", flush=True)
-if "pn" in which:      # the patch norm (8-bit LayerNorm over 96 channels): one-dword half-wave kernel against the two-dword one (lab bits 25 / 26)
+if "pn" in which:      # the patch norm (8-bit LayerNorm over 96 channels): one-dword half-wave kernel, 8 against 4 row pairs per wave (lab bit 26)
     rows, C = B * 56 * 56, 96
     x = d(rng.integers(-128, 128, size=(rows, C)).astype(np.int8))
     out = torch.empty(rows, C, dtype=torch.int8, device=DEV)
@@ -86,16 +86,16 @@ if "pn" in which:      # the patch norm (8-bit LayerNorm over 96 channels): one-
     bi, sl, mm, ee = d(lp.bias_int), d(lp.s_ln), d(lp.m.view(np.int32)), d(lp.e)
     res, outs = {}, {}
     for rnd in range(5):
-        for form in (0, 1 << 27, 1 << 26, 1 << 25):
+        for form in (0, 1 << 26):
             _lib.call("ivit_debug_ln_ablate", form)
             res.setdefault(form, []).append(timeit(lambda: _lib.call("ivit_layernorm_i8", _lib.ptr(x), C, rows, C, _lib.ptr(bi), _lib.ptr(sl), _lib.ptr(mm),
                                                                      _lib.ptr(ee), _lib.ptr(out), C, st()), n=10))
             outs[form] = out.clone()
     _lib.call("ivit_debug_ln_ablate", 0)
     assert all(torch.equal(outs[0], o) for o in outs.values())
-    print(f"patch norm rows={rows} C={C}: one dword, 8 row pairs {np.median(res[0]):7.1f} us   one dword, 4 row pairs {np.median(res[1 << 26]):7.1f} us   ds_bpermute row sums {np.median(res[1 << 27]):7.1f} us   "
-          f"two dwords (round 3) {np.median(res[1 << 25]):7.1f} us   ({2 * rows * C / np.median(res[0]) / 1e3:7.1f} GB/s algorithmic)", flush=True)
-if "gelu" in which:    # ShiftGELU table pass, row-major rows (the Swin MLP) and the ViT shapes in both layouts; lab bits 24 / 28: whole wave per short row / prefetch of the next rows
+    print(f"patch norm rows={rows} C={C}: one dword, 8 row pairs {np.median(res[0]):7.1f} us   one dword, 4 row pairs {np.median(res[1 << 26]):7.1f} us   "
+          f"({2 * rows * C / np.median(res[0]) / 1e3:7.1f} GB/s algorithmic)", flush=True)
+if "gelu" in which:    # ShiftGELU table pass, row-major rows (the Swin MLP) and the ViT shapes in both layouts; lab bit 24: whole wave per short row
     lut = torch.empty(65536, dtype=torch.int8, device=DEV)
     mg, eg = dyadic(np.float32(0.05 * 0.05 / 128), np.float32(0.02))
     _lib.call("ivit_shiftgelu_build_lut", 0.05, int(mg[0]), int(eg[0]), _lib.ptr(lut), st())
@@ -103,7 +103,7 @@ if "gelu" in which:    # ShiftGELU table pass, row-major rows (the Swin MLP) and
         x = d(np.clip(np.rint(rng.normal(0, 30, size=(rows, L))), -128, 127).astype(np.int8))
         out = torch.empty_like(x)
         line = f"ShiftGELU table pass rows={rows:7d} L={L:5d}:"
-        forms = [("row-major", 0, 0)] + ([("with prefetch", 0, 1 << 28), ("wave per row", 0, 1 << 24)] if L <= 384 else []) + ([("block layout", 3, 0)] if L % 64 == 0 else [])
+        forms = [("row-major", 0, 0)] + ([("wave per row", 0, 1 << 24)] if L <= 384 else []) + ([("block layout", 3, 0)] if L % 64 == 0 else [])
         res = {}
         for rnd in range(5):
             for name, lay, bits in forms:
