@@ -42,7 +42,8 @@ def parse(text):
 def occupancy_rules(path, what):
     """attention.hip / rowops.hip: kernels whose launchers size their grids for a number of resident workgroups.  The number is a
     template argument (the OCC of attention_kernel<MODE, PB, OCC, ...>, the last argument of layernorm_i8_stream_kernel<LPR, NC, NG,
-    COMPAT, OCC>): the compiler must reach it (waves per SIMD) and, for the variants on the headline path, without scratch."""
+    COMPAT, OCC>) or follows from them (the other int8 LayerNorm kernels): the compiler must reach it (waves per SIMD) and, for the
+    variants on the headline path, without scratch."""
     kernels = parse(open(path, errors="replace").read())
     bad, seen = [], 0
     for name, r in sorted(kernels.items()):
@@ -76,6 +77,21 @@ def occupancy_rules(path, what):
         elif "head_topk_kernel" in name:
             # the per-lane top-k lists live in registers (constant indices only): no scratch, full occupancy for any k <= 8
             occ, need_no_scratch = 8, True
+        elif re.search(r"layernorm_i8_(pair_|v2_)?kernelI", name):
+            # the other int8 LayerNorm kernels of the product: the occupancy is their __launch_bounds__ (`resident` and `grid > 1024`
+            # in their launchers), restated here from the template arguments; no scratch
+            if (m := re.search(r"layernorm_i8_kernelILi(\d+)ELb([01])E", name)):
+                nj, compat = int(m.group(1)), m.group(2) == "1"
+                occ = 3 if nj <= 3 and not compat else 2 if nj <= 8 else 1
+            elif (m := re.search(r"layernorm_i8_pair_kernelILi(\d+)ELi(\d+)E", name)):
+                occ = 4 if int(m.group(1)) <= 3 else 3
+            else:
+                m = re.search(r"layernorm_i8_v2_kernelILi(\d+)ELb([01])ELi(\d+)E", name)
+                nj, compat, g = int(m.group(1)), m.group(2) == "1", int(m.group(3))
+                occ = (3 if compat else 4) if g == 8 and nj <= 3 else 4 if nj <= 1 else 3 if nj <= 3 else 2
+            # the one exception: layernorm_i8_v2_kernel<3, true, 16> (natural scales, 512 < C <= 768, more than 131 072 rows that the
+            # streaming kernel does not take) spills three dwords, 12 bytes per lane
+            need_no_scratch = "layernorm_i8_v2_kernelILi3ELb1ELi16E" not in name
         else:
             m = re.search(r"layernorm_i8_stream_kernelILi(\d+)ELi(\d+)ELi(\d+)ELb([01])ELi(\d+)E", name)
             if not m:

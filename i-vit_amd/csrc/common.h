@@ -151,7 +151,7 @@ IVIT_DEV unsigned long long wave_allmax_u64(unsigned long long v)
 }
 
 // The per-channel constants of the int8-output LayerNorm kernels, once per workgroup into LDS: bias_int and the float32 bracket
-// [lo, hi] of the output requantiser's multiplier (the certificate of layernorm_i8_kernel, rowops.hip).  ALL global loads of a pass
+// [lo, hi] of the output requantiser's multiplier (the certificate of ln_chain.h).  ALL global loads of a pass
 // (two channels per thread: C <= 2 x NTHREADS is one pass) are issued before the first use -- written as one loop with the loads where
 // they are consumed, the compiler waited for m / e / s_ln, did the float64 arithmetic, then requested bias_int and waited again: two
 // global latencies per channel and thread, 3-4 us of an 8.6 us launch at 12 608 rows of 384 channels (DeiT-S, late round 4).

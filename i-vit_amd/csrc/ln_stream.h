@@ -1,5 +1,5 @@
 // ln_stream.h -- layernorm_i8_stream_kernel: the int8 I-LayerNorm as a STREAMING kernel (round 4).  Included by rowops.hip
-// inside its anonymous namespace (uses LnArgs, ln_mean, NT, WPB, v2f, dyadic_mult, sx8, pack4 from there).
+// inside its anonymous namespace (uses LnArgs, ln_mean, NT, WPB, dyadic_mult and ln_chain.h from there).
 // Reference: /root/reference/models/quantization_utils/ivit_modules.py:30-65 (IVITIntLayerNorm), quant_utils.py:220-230.
 //
 // Why another form.  layernorm_i8_v2_kernel ran at 0.34 of the HBM peak (27.5 us for 75 MB at the headline shape) and its
@@ -262,27 +262,10 @@ __global__ __launch_bounds__(NT, OCC) void layernorm_i8_stream_kernel(LnArgs a)
                 }
                 const float bias[4] = {b4.x, b4.y, b4.z, b4.w}, lo[4] = {l4.x, l4.y, l4.z, l4.w}, hi[4] = {h4.x, h4.y, h4.z, h4.w};
                 const unsigned wu = wg[i][d] ^ 0x80808080u;
-                int ob[4];
-                if (!(abl & 1)) {
-                    // (v_pk_add / v_pk_mul / v_pk_fma cost 3.2 cycles per pair against 2 x 1.95 for the plain forms
-                    // (profiles/r04_valu_price_list.txt), but the register pairs they need made the kernel spill at 128 VGPRs)
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        const float xf = (float)((wu >> (8 * c)) & 0xffu);
-                        const float dl = xf - mean128;                   // x - mean, exact
-                        const float vv = floorf(dl * hfac);              // :52
-                        const float y = vv + bias[c];                    // :61
-                        const int tl = __float_as_int(__builtin_fmaf(y, lo[c], 12582912.0f));
-                        const int th = __float_as_int(__builtin_fmaf(y, hi[c], 12582912.0f));
-                        asm("v_sad_u32 %0, %1, %2, %3" : "=v"(u) : "v"(tl), "v"(th), "v"(u));
-                        ob[c] = clamp_i32(tl, 0x4B400000 - 128, 0x4B400000 + 127);   // low byte = int8 result
-                    }
-                } else {
-                    ob[0] = ob[1] = ob[2] = ob[3] = (int)wu;
-                }
-                const unsigned w01 = __builtin_amdgcn_perm((unsigned)ob[1], (unsigned)ob[0], 0x0c0c0400u);
-                const unsigned w23 = __builtin_amdgcn_perm((unsigned)ob[3], (unsigned)ob[2], 0x04000c0cu);
-                res[d] = w01 | w23;
+                // the scalar form: v_pk_add / v_pk_mul / v_pk_fma cost 3.2 cycles per pair against 2 x 1.95 for the plain forms
+                // (profiles/r04_valu_price_list.txt), but the register pairs they need made the kernel spill at 128 VGPRs
+                if (!(abl & 1)) res[d] = (unsigned)ln_cert4(wu, mean128, hfac, bias, lo, hi, u);
+                else res[d] = (wu & 0xffu) * 0x01010101u;      // lab: no element chain
             }
             // literal evaluation of a chunk with an uncertified element (wave-uniform, ~1 % of the chunks)
             if (__builtin_amdgcn_ballot_w64(u != 0) != 0) {
@@ -298,20 +281,7 @@ __global__ __launch_bounds__(NT, OCC) void layernorm_i8_stream_kernel(LnArgs a)
                     const float bias[4] = {b4.x, b4.y, b4.z, b4.w};
                     const double Mq[4] = {dyadic_mult(m4.x, (int)e4.x), dyadic_mult(m4.y, (int)e4.y), dyadic_mult(m4.z, (int)e4.z),
                                           dyadic_mult(m4.w, (int)e4.w)};
-                    int ob[4];
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        float dl = (float)(sx8((int)wg[i][d], c) - mean_i);
-                        float v = floorf(dl * hfac);                       // :52
-                        float y = v + bias[c];                             // :61
-                        float x = y * sl[c];                               // :63
-                        float qf = (float)((double)x * (1.0 / (double)sl[c]));   // quant_utils.py:220, see layernorm_i8_kernel
-                        float z = rintf(qf);
-                        double p = (double)z * Mq[c];                      // :229
-                        double t = p + IVIT_MAGIC;                         // :230
-                        ob[c] = clamp_i32((int)(unsigned)__double_as_longlong(t), -128, 127);
-                    }
-                    res[d] = (unsigned)pack4(ob[0], ob[1], ob[2], ob[3]);
+                    res[d] = (unsigned)ln_literal4((int)wg[i][d], mean_i, hfac, bias, sl, Mq);
                 }
             }
             wg[i] = res;

@@ -29,8 +29,6 @@ constexpr int g_ln_stream_cfg = 0;
 
 namespace {
 
-typedef float v2f __attribute__((ext_vector_type(2)));
-
 constexpr int NT = 256;
 constexpr int WPB = NT / 64;  // waves (rows in flight) per block
 
@@ -40,6 +38,8 @@ IVIT_DEV int pack4(int a, int b, int c, int d)
 {
     return (a & 0xff) | ((b & 0xff) << 8) | ((c & 0xff) << 16) | ((d & 0xff) << 24);
 }
+
+#include "ln_chain.h"
 
 static inline int grid_for_rows(int64_t rows, int rows_per_wave = 1)
 {
@@ -86,10 +86,7 @@ IVIT_DEV void ln_mean(int sum, int C, int& mean_int)
 IVIT_DEV float ln_factor(long long var)
 {
     // :45-49  ten Newton steps; var_int / k promotes to float32, all divisions correctly rounded
-    float varf = (float)var;
-    float t = 65536.0f;
-#pragma unroll 1
-    for (int it = 0; it < 10; ++it) t = floorf((t + floorf(varf / t)) * 0.5f);
+    const float t = ln_newton10_literal((float)var);
     // :51  (2**31-1)/std  ==  reciprocal(std) * 2^31 in float32
     return floorf((1.0f / t) * 2147483648.0f);
 }
@@ -205,16 +202,8 @@ IVIT_DEV float torch_rowsum_phi(const int8_t* qrow, int C, const float* phi_lds,
 // int8 in -> int8 out, NJ dwords (4 channels each) per lane, per-channel constants kept in registers
 // across the rows a wave processes.
 //
-// The tail of the reference's chain for one element is  x = y * s_ln (:63, float32),  z = round(x / s_ln)
-// (quant_utils.py:220, float32 quotient),  out = clamp8(RNE(float64(z) * M)) (:229-230), M = m * 2^-e.  It costs six
-// float64 instructions per element when evaluated literally.  Fast path: z = y * (1 + eps) with |eps| <= 2^-22 (two
-// float32 roundings of relative size 2^-24 each, plus the round() step, which is a no-op for |y| >= 2^23, moves
-// 2^22 <= |y| < 2^23 by at most 1/2 <= |y| * 2^-23 and gives back z = y exactly for |y| < 2^22), so the real number
-// the reference rounds lies between y * lo and y * hi for float32 lo <= M * (1 - 1.25 * 2^-22), hi >= M * (1 + 1.25 * 2^-22).
-// t_lo = fma(y, lo, 1.5 * 2^23) and t_hi = fma(y, hi, 1.5 * 2^23) are RNE(y * lo) and RNE(y * hi) exactly (one rounding,
-// ulp 1) while |y * hi| < 2^22; RNE is monotone, so t_lo == t_hi certifies the reference's result.  Products beyond
-// 2^22 saturate the int8 clamp on either side whatever their rounding (float bit patterns are monotone), so they need
-// no separate range test.  A row with any uncertified element (about 1 % of the rows) is redone literally.
+// The element chain is ln_chain.h's: the float32 bracket certificate (ln_cert4_pk), and a row with any uncertified element
+// (about 1 % of the rows) is redone literally (ln_literal4).
 //
 // COMPAT (natural activation scales): the row is seen through phi.  Bytes are remapped to k' = trunc(phi(q)) through a
 // 256-byte LDS table before anything else; the mean is round(fl(sum phi / C)) -- equal to RNE(sum q / C) except on rows
@@ -372,29 +361,8 @@ __global__ __launch_bounds__(NT, (NJ <= 3 && !COMPAT ? 3 : NJ <= 8 ? 2 : 1)) voi
             unsigned unc = 0;
 #pragma unroll
             for (int j = 0; j < NJ; ++j) {
-                const unsigned wu = (unsigned)w[rr][j] ^ 0x80808080u;      // bytes x + 128: v_cvt_f32_ubyteN below
-                int o[4];
-                // two channels per packed float32 instruction (v_pk_add / v_pk_mul / v_pk_fma: the same IEEE operations,
-                // two lanes of data per issue slot); floor, the certificate and the clamp stay scalar
-#pragma unroll
-                for (int c = 0; c < 4; c += 2) {
-                    const v2f xf = {(float)((wu >> (8 * c)) & 0xffu), (float)((wu >> (8 * c + 8)) & 0xffu)};
-                    const v2f dl = xf - (v2f){mean128, mean128};           // x - mean, exact
-                    const v2f pr = dl * (v2f){hfactor, hfactor};           // :52  float32 product (the /2 is in the factor)
-                    const v2f vv = {floorf(pr.x), floorf(pr.y)};
-                    const v2f y = vv + (v2f){bias[j][c], bias[j][c + 1]};  // :61  float32 add
-                    const v2f tlv = __builtin_elementwise_fma(y, (v2f){lo[j][c], lo[j][c + 1]}, (v2f){12582912.0f, 12582912.0f});
-                    const v2f thv = __builtin_elementwise_fma(y, (v2f){hi[j][c], hi[j][c + 1]}, (v2f){12582912.0f, 12582912.0f});
-#pragma unroll
-                    for (int k = 0; k < 2; ++k) {
-                        const int tl = __float_as_int(tlv[k]), th = __float_as_int(thv[k]);
-                        asm("v_sad_u32 %0, %1, %2, %3" : "=v"(unc) : "v"(tl), "v"(th), "v"(unc));
-                        o[c + k] = clamp_i32(tl, 0x4B400000 - 128, 0x4B400000 + 127);   // low byte = int8 result
-                    }
-                }
-                const unsigned w01 = __builtin_amdgcn_perm((unsigned)o[1], (unsigned)o[0], 0x0c0c0400u);
-                const unsigned w23 = __builtin_amdgcn_perm((unsigned)o[3], (unsigned)o[2], 0x04000c0cu);
-                res[j] = (int)(w01 | w23);
+                const unsigned wu = (unsigned)w[rr][j] ^ 0x80808080u;      // bytes x + 128
+                res[j] = ln_cert4_pk(wu, mean128, hfactor, bias[j], lo[j], hi[j], unc);
             }
             // lanes beyond the row (d >= nd) hold lo = hi = 0: always certified
             if (__builtin_amdgcn_ballot_w64(unc != 0) != 0) {
@@ -409,22 +377,7 @@ __global__ __launch_bounds__(NT, (NJ <= 3 && !COMPAT ? 3 : NJ <= 8 ? 2 : 1)) voi
                     const float sl[4] = {s4.x, s4.y, s4.z, s4.w};
                     const double Mq[4] = {dyadic_mult(m4.x, e4.x), dyadic_mult(m4.y, e4.y), dyadic_mult(m4.z, e4.z),
                                           dyadic_mult(m4.w, e4.w)};
-                    int o[4];
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        float dl = (float)(sx8(w[rr][j], c) - mean_int[rr]);
-                        float v = floorf(dl * hfactor);                    // :52
-                        float y = v + bias[j][c];                          // :61
-                        float x = y * sl[c];                               // :63  float32 product
-                        // quant_utils.py:220  z = round(x / s): the correctly rounded float32 quotient,
-                        // obtained as RN24(RN53(x * RN53(1/s))) (no midpoint can lie within 2^-52 of x/s)
-                        float qf = (float)((double)x * (1.0 / (double)sl[c]));
-                        float z = rintf(qf);
-                        double p = (double)z * Mq[c];                      // :229 float64 product
-                        double t = p + IVIT_MAGIC;                         // :230 round half to even
-                        o[c] = clamp_i32((int)(unsigned)__double_as_longlong(t), -128, 127);
-                    }
-                    res[j] = pack4(o[0], o[1], o[2], o[3]);
+                    res[j] = ln_literal4(w[rr][j], mean_int[rr], hfactor, bias[j], sl, Mq);
                 }
             }
             if (a.out_blocks) {
@@ -455,21 +408,9 @@ __global__ __launch_bounds__(NT, (NJ <= 3 && !COMPAT ? 3 : NJ <= 8 ? 2 : 1)) voi
 // bandwidth): G2 = 2 or 1 row pairs per wave instead of 4 puts 2-4 x as many waves on the chip for the same rows, the first
 // group's rows are requested BEFORE the constants table is derived (its loads and float64 arithmetic run under their flight),
 // and the ten Newton steps are the sqrt shortcut of ln_std10 where it is proven (var < 2^24: C <= 1024).
-// Sum over the 32 lanes of a half wave, every lane ends with the total: four DPP steps inside the rows of 16 lanes and one
-// v_permlane16_swap of the value with itself (odd rows of the one copy against even rows of the other: the two copies then hold
-// row 0 | row 0 and row 1 | row 1 of each half).  No LDS instruction: the __shfl_xor form was five ds_bpermute_b32 round trips per
-// value, 12 per row pair with the broadcasts -- at 401 408 rows of 96 channels the LDS pipe, not the VALU, set the pace.
-IVIT_DEV int half_wave_allreduce(int v)
-{
-    typedef unsigned v2u_ __attribute__((ext_vector_type(2)));
-    v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, false);    // quad_perm [1,0,3,2]
-    v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xf, 0xf, false);    // quad_perm [2,3,0,1]
-    v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xf, 0xf, false);   // row_half_mirror
-    v += __builtin_amdgcn_update_dpp(0, v, 0x140, 0xf, 0xf, false);   // row_mirror
-    const v2u_ r = __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false);
-    return (int)(r.x + r.y);
-}
-
+// The row sums over the 32 lanes of a half wave are common.h's lanes_allsum_i32<32> (four DPP steps inside the rows of 16 lanes and
+// one v_permlane16_swap): no LDS instruction -- the __shfl_xor form was five ds_bpermute_b32 round trips per value, 12 per row pair
+// with the broadcasts, and at 401 408 rows of 96 channels the LDS pipe, not the VALU, set the pace.
 template <int NJ, int G2 = 4>
 __global__ __launch_bounds__(NT, NJ <= 3 ? 4 : 3) void layernorm_i8_pair_kernel(LnArgs a)
 {
@@ -514,8 +455,8 @@ __global__ __launch_bounds__(NT, NJ <= 3 ? 4 : 3) void layernorm_i8_pair_kernel(
         }
 #pragma unroll
         for (int q = 0; q < G2; ++q) {
-            sum[q] = half_wave_allreduce(sum[q]);
-            sq[q] = half_wave_allreduce(sq[q]);
+            sum[q] = lanes_allsum_i32<32>(sum[q]);
+            sq[q] = lanes_allsum_i32<32>(sq[q]);
         }
         // lane (half, l32 = q) : statistics of row 2q + half, computed once; ivit_modules.py:37, 40-51
         int my_sum = sum[0], my_sq = sq[0];
@@ -551,24 +492,12 @@ __global__ __launch_bounds__(NT, NJ <= 3 ? 4 : 3) void layernorm_i8_pair_kernel(
             const float bias[4] = {b4.x, b4.y, b4.z, b4.w}, lo[4] = {l4.x, l4.y, l4.z, l4.w}, hi[4] = {h4.x, h4.y, h4.z, h4.w};
 #pragma unroll
             for (int q = 0; q < G2; ++q) {
-                const unsigned wu = (unsigned)w[q][j] ^ 0x80808080u;   // bytes x + 128: v_cvt_f32_ubyteN below
-                int o[4];
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    const float dl = (float)((wu >> (8 * c)) & 0xffu) - mean128[q];   // x - mean, exact
-                    const float v = floorf(dl * hfactor[q]);               // :52
-                    const float y = v + bias[c];                           // :61
-                    const int tl = __float_as_int(__builtin_fmaf(y, lo[c], 12582912.0f));
-                    const int th = __float_as_int(__builtin_fmaf(y, hi[c], 12582912.0f));
-                    asm("v_sad_u32 %0, %1, %2, %3" : "=v"(unc[q]) : "v"(tl), "v"(th), "v"(unc[q]));
-                    o[c] = clamp_i32(tl, 0x4B400000 - 128, 0x4B400000 + 127);
-                }
-                const unsigned w01 = __builtin_amdgcn_perm((unsigned)o[1], (unsigned)o[0], 0x0c0c0400u);
-                const unsigned w23 = __builtin_amdgcn_perm((unsigned)o[3], (unsigned)o[2], 0x04000c0cu);
+                const unsigned wu = (unsigned)w[q][j] ^ 0x80808080u;   // bytes x + 128
+                const int res = ln_cert4(wu, mean128[q], hfactor[q], bias, lo, hi, unc[q]);
                 const int row = row0 + 2 * q + half, dd = l32 + 32 * j;
                 if (row < a.rows && dd < nd) {
                     const int64_t off = a.out_blocks ? (int64_t)block_off(block_row(row, C), block_col(4 * dd)) : (int64_t)row * a.ldo + 4 * dd;
-                    *reinterpret_cast<int*>(out + off) = (int)(w01 | w23);
+                    *reinterpret_cast<int*>(out + off) = res;
                 }
             }
             __builtin_amdgcn_sched_barrier(0);   // keep the constants of one channel group live at a time
@@ -588,23 +517,11 @@ __global__ __launch_bounds__(NT, NJ <= 3 ? 4 : 3) void layernorm_i8_pair_kernel(
                     const float bias[4] = {b4.x, b4.y, b4.z, b4.w}, sl[4] = {s4.x, s4.y, s4.z, s4.w};
                     const double Mq[4] = {dyadic_mult(m4.x, e4.x), dyadic_mult(m4.y, e4.y), dyadic_mult(m4.z, e4.z),
                                           dyadic_mult(m4.w, e4.w)};
-                    int o[4];
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        float dl = (float)(sx8(w[q][j], c) - mean_int[q]);
-                        float v = floorf(dl * hfactor[q]);
-                        float y = v + bias[c];
-                        float x = y * sl[c];                               // :63
-                        float qf = (float)((double)x * (1.0 / (double)sl[c]));   // quant_utils.py:220, see layernorm_i8_kernel
-                        float z = rintf(qf);
-                        double p = (double)z * Mq[c];                      // :229
-                        double t = p + IVIT_MAGIC;                         // :230
-                        o[c] = clamp_i32((int)(unsigned)__double_as_longlong(t), -128, 127);
-                    }
+                    const int res = ln_literal4(w[q][j], mean_int[q], hfactor[q], bias, sl, Mq);   // outside the store guard
                     const int dd = l32 + 32 * j;
                     if (row < a.rows && dd < nd) {
                         const int64_t off = a.out_blocks ? ivit_block_offset(row, 4 * dd, C) : (int64_t)row * a.ldo + 4 * dd;
-                        *reinterpret_cast<int*>(out + off) = pack4(o[0], o[1], o[2], o[3]);
+                        *reinterpret_cast<int*>(out + off) = res;
                     }
                 }
             }
@@ -805,28 +722,7 @@ __global__ __launch_bounds__(NT, (G == 8 && NJ <= 3 ? (COMPAT ? 3 : 4) : NJ <= 1
             for (int rr = 0; rr < G; ++rr) {
                 if (rr >= nrow) continue;   // wave-uniform
                 const unsigned wu = (unsigned)w[rr][j] ^ 0x80808080u;
-                int o[4];
-                unsigned u = unc[rr];
-#pragma unroll
-                for (int c = 0; c < 4; c += 2) {
-                    const v2f xf = {(float)((wu >> (8 * c)) & 0xffu), (float)((wu >> (8 * c + 8)) & 0xffu)};
-                    const v2f dl = xf - (v2f){mean128[rr], mean128[rr]};   // x - mean, exact
-                    const v2f pr = dl * (v2f){hfac[rr], hfac[rr]};         // :52
-                    const v2f vv = {floorf(pr.x), floorf(pr.y)};
-                    const v2f y = vv + (v2f){bias[c], bias[c + 1]};        // :61
-                    const v2f tlv = __builtin_elementwise_fma(y, (v2f){lo[c], lo[c + 1]}, (v2f){12582912.0f, 12582912.0f});
-                    const v2f thv = __builtin_elementwise_fma(y, (v2f){hi[c], hi[c + 1]}, (v2f){12582912.0f, 12582912.0f});
-#pragma unroll
-                    for (int k = 0; k < 2; ++k) {
-                        const int tl = __float_as_int(tlv[k]), th = __float_as_int(thv[k]);
-                        asm("v_sad_u32 %0, %1, %2, %3" : "=v"(u) : "v"(tl), "v"(th), "v"(u));
-                        o[c + k] = clamp_i32(tl, 0x4B400000 - 128, 0x4B400000 + 127);
-                    }
-                }
-                unc[rr] = u;
-                const unsigned w01 = __builtin_amdgcn_perm((unsigned)o[1], (unsigned)o[0], 0x0c0c0400u);
-                const unsigned w23 = __builtin_amdgcn_perm((unsigned)o[3], (unsigned)o[2], 0x04000c0cu);
-                w[rr][j] = (int)(w01 | w23);      // the input dword is dead from here on
+                w[rr][j] = ln_cert4_pk(wu, mean128[rr], hfac[rr], bias, lo, hi, unc[rr]);      // the input dword is dead from here on
             }
         }
 #pragma unroll
@@ -854,20 +750,7 @@ __global__ __launch_bounds__(NT, (G == 8 && NJ <= 3 ? (COMPAT ? 3 : 4) : NJ <= 1
                     const float sl[4] = {s4.x, s4.y, s4.z, s4.w}, bias[4] = {b4.x, b4.y, b4.z, b4.w};
                     const double Mq[4] = {dyadic_mult(m4.x, e4.x), dyadic_mult(m4.y, e4.y), dyadic_mult(m4.z, e4.z),
                                           dyadic_mult(m4.w, e4.w)};
-                    int o[4];
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        float dl = (float)(sx8(wv, c) - mean_i);
-                        float v = floorf(dl * hfac[rr]);                   // :52
-                        float y = v + bias[c];                             // :61
-                        float x = y * sl[c];                               // :63
-                        float qf = (float)((double)x * (1.0 / (double)sl[c]));   // quant_utils.py:220, see layernorm_i8_kernel
-                        float z = rintf(qf);
-                        double p = (double)z * Mq[c];                      // :229
-                        double t = p + IVIT_MAGIC;                         // :230
-                        o[c] = clamp_i32((int)(unsigned)__double_as_longlong(t), -128, 127);
-                    }
-                    w[rr][j] = pack4(o[0], o[1], o[2], o[3]);
+                    w[rr][j] = ln_literal4(wv, mean_i, hfac[rr], bias, sl, Mq);
                 }
             }
             if (abl & 4) continue;
@@ -1582,8 +1465,14 @@ static int launch_ln_v2(const LnArgs& a, hipStream_t st, const char* who)
         if (g8) hipLaunchKernelGGL((layernorm_i8_v2_kernel<NJv, COMPAT, 8>), dim3(grid), dim3(NT), lds, st, a); \
         else hipLaunchKernelGGL((layernorm_i8_v2_kernel<NJv, COMPAT, 16>), dim3(grid), dim3(NT), lds, st, a);        \
     } while (0)
-    if (nj <= 1) IVIT_LN_V2(1);
-    else if (nj <= 2) IVIT_LN_V2(2);
+    // one dword per lane: natural scales only in the product (the plain entry point sends C < 512 to the half-wave kernel)
+    if constexpr (IVIT_LAB || COMPAT) {
+        if (nj <= 1) {
+            IVIT_LN_V2(1);
+            IVIT_CHECK_LAUNCH(who);
+        }
+    }
+    if (nj <= 2) IVIT_LN_V2(2);
     else if (nj <= 3) IVIT_LN_V2(3);
     else IVIT_LN_V2(4);
 #undef IVIT_LN_V2
@@ -1636,21 +1525,98 @@ IVIT_EXPORT int ivit_debug_ln_stamp_buffer(void* buf)
 }
 #endif
 
+// layernorm_i8_pair_kernel: half a wave per row (constants in LDS, 3 * C floats), C <= 1536
+static int launch_ln_pair(const LnArgs& a, hipStream_t st, const char* who)
+{
+    const int rows = a.rows, nj2 = (a.C / 4 + 31) / 32;
+    // row pairs per wave: 4 from 16 K rows (4 waves per SIMD busy either way), fewer below so that a small launch still fills the
+    // chip (lab: ln_ablate bits 21-22 = 1 / 2 / 3 force 4 / 2 / 1)
+    int g2 = rows > 16384 ? 4 : rows > 8192 ? 2 : 1;
+    if (nj2 > 3) g2 = 4;
+    if ((g_ln_ablate >> 21) & 3) g2 = nj2 > 3 ? 4 : 8 >> ((g_ln_ablate >> 21) & 3);
+    int grid = grid_for_rows(rows, 2 * g2);
+    if (grid > 1024) grid = 1024;          // 4 waves per SIMD resident
+    const size_t lds = (size_t)3 * a.C * sizeof(float);
+#define IVIT_LN_PAIR(...) hipLaunchKernelGGL((layernorm_i8_pair_kernel<__VA_ARGS__>), dim3(grid), dim3(NT), lds, st, a)
+    // C <= 128 (Swin's patch norm, 401 408 rows of 96): one dword per lane -- the NJ = 2 form computes a second, fully masked one
+    // -- and 8 row pairs per wave from 64 K rows (the row statistics of 16 rows in one pass of lanes 0-7)
+    const bool one = nj2 == 1 && g2 == 4;
+    if (one && rows > 65536 && !(g_ln_ablate & (1u << 26))) {
+        grid = grid_for_rows(rows, 16);
+        if (grid > 1024) grid = 1024;
+        IVIT_LN_PAIR(1, 8);
+    } else if (one) IVIT_LN_PAIR(1, 4);
+    else if (nj2 <= 2 && g2 == 1) IVIT_LN_PAIR(2, 1);
+    else if (nj2 <= 2 && g2 == 2) IVIT_LN_PAIR(2, 2);
+    else if (nj2 <= 3 && g2 == 1) IVIT_LN_PAIR(3, 1);
+    else if (nj2 <= 3 && g2 == 2) IVIT_LN_PAIR(3, 2);
+    else if (nj2 <= 2) IVIT_LN_PAIR(2);
+    else if (nj2 <= 3) IVIT_LN_PAIR(3);
+#if IVIT_LAB      // C > 384: only the lab form 2 comes here
+    else if (nj2 <= 6) IVIT_LN_PAIR(6);
+    else if (nj2 <= 8) IVIT_LN_PAIR(8);
+    else IVIT_LN_PAIR(12);
+#endif
+#undef IVIT_LN_PAIR
+    IVIT_CHECK_LAUNCH(who);
+}
+
+// layernorm_i8_kernel: a wave per row.  Each wave sets up its per-channel constants (bias and the requant bracket, 12 * NJ registers
+// per lane) once: launch no more workgroups than stay resident (256 CUs x waves / SIMD at the kernel's register count) and let them
+// stride over the rows.  The product comes here with 384 < C < 512 or C > 1024 (NJ = 2, 8, 16) and, at natural scales, with
+// C > 1024 (NJ = 8, 16); every other NJ is reached through the lab forms only.
+template <bool COMPAT>
+static int launch_ln_wave_per_row(const LnArgs& a, hipStream_t st, const char* who)
+{
+    const int nj = (a.C / 4 + 63) / 64;
+    const int resident = 256 * (nj <= 3 && !COMPAT ? 3 : nj <= 8 ? 2 : 1);     // = the kernel's __launch_bounds__ occupancy
+    int grid = grid_for_rows(a.rows, nj <= 3 ? 8 : nj <= 4 ? 4 : 1);            // rows per wave and iteration: G of the kernel
+    if (grid > resident) grid = resident;
+#define IVIT_LN_WPR(NJv) hipLaunchKernelGGL((layernorm_i8_kernel<NJv, COMPAT>), dim3(grid), dim3(NT), 0, st, a)
+#if IVIT_LAB
+    if (nj <= 1) IVIT_LN_WPR(1);
+    else if (nj <= 2) IVIT_LN_WPR(2);
+    else if (nj <= 3) IVIT_LN_WPR(3);
+    else if (nj <= 4) IVIT_LN_WPR(4);
+    else
+#else      // of nj <= 4 the product's ladders send only 384 < C < 512 at plain scales here
+    if constexpr (!COMPAT) {
+        if (nj <= 2) {
+            IVIT_LN_WPR(2);
+            IVIT_CHECK_LAUNCH(who);
+        }
+    }
+#endif
+    if (nj <= 8) IVIT_LN_WPR(8);
+    else IVIT_LN_WPR(16);
+#undef IVIT_LN_WPR
+    IVIT_CHECK_LAUNCH(who);
+}
+
+// the operand checks ivit_layernorm_i8_ex and ivit_layernorm_i8_compat share
+static int ln8_check(const char* who, const char* who_blocks, const int8_t* x, int64_t ldx, int rows, int C, const float* bias_int,
+                     const float* s_ln, const uint32_t* m, const int32_t* e, const int8_t* out, int64_t ldo, int out_blocks)
+{
+    IVIT_REQUIRE(x && out && bias_int && s_ln && m && e, "%s: NULL operand", who);
+    IVIT_REQUIRE(rows > 0 && C > 0 && C % 4 == 0 && C <= 4096, "%s: rows=%d C=%d unsupported", who, rows, C);
+    IVIT_REQUIRE(ldx % 4 == 0 && ldo % 4 == 0 && ldx >= C && ldo >= C && ((uintptr_t)x % 4 == 0) &&
+                     ((uintptr_t)out % 4 == 0),
+                 "%s: rows must be 4-byte aligned", who);
+    IVIT_REQUIRE(((uintptr_t)bias_int % 16 == 0) && ((uintptr_t)s_ln % 16 == 0) && ((uintptr_t)m % 16 == 0) &&
+                     ((uintptr_t)e % 16 == 0),
+                 "%s: per-channel tables must be 16-byte aligned", who);
+    IVIT_REQUIRE(out_blocks == 0 || (out_blocks == 1 && C % 64 == 0 && ldo == C && ((uintptr_t)out % 16 == 0) &&
+                                     ((int64_t)rows + 15) * C < 2147483648ll),
+                 "%s: block-layout output needs C %% 64 == 0, ldo == C and a buffer below 2 GiB", who_blocks);
+    return IVIT_OK;
+}
+
 IVIT_EXPORT int ivit_layernorm_i8_ex(const int8_t* x, int64_t ldx, int rows, int C, const float* bias_int,
                                   const float* s_ln, const uint32_t* m, const int32_t* e, int8_t* out, int64_t ldo,
                                      int out_blocks, ivit_stream_t stream)
 {
-    IVIT_REQUIRE(x && out && bias_int && s_ln && m && e, "ivit_layernorm_i8: NULL operand");
-    IVIT_REQUIRE(rows > 0 && C > 0 && C % 4 == 0 && C <= 4096, "ivit_layernorm_i8: rows=%d C=%d unsupported", rows, C);
-    IVIT_REQUIRE(ldx % 4 == 0 && ldo % 4 == 0 && ldx >= C && ldo >= C && ((uintptr_t)x % 4 == 0) &&
-                     ((uintptr_t)out % 4 == 0),
-                 "ivit_layernorm_i8: rows must be 4-byte aligned");
-    IVIT_REQUIRE(((uintptr_t)bias_int % 16 == 0) && ((uintptr_t)s_ln % 16 == 0) && ((uintptr_t)m % 16 == 0) &&
-                     ((uintptr_t)e % 16 == 0),
-                 "ivit_layernorm_i8: per-channel tables must be 16-byte aligned");
-    IVIT_REQUIRE(out_blocks == 0 || (out_blocks == 1 && C % 64 == 0 && ldo == C && ((uintptr_t)out % 16 == 0) &&
-                                     ((int64_t)rows + 15) * C < 2147483648ll),
-                 "ivit_layernorm_i8_ex: block-layout output needs C %% 64 == 0, ldo == C and a buffer below 2 GiB");
+    const char* who = "ivit_layernorm_i8";
+    if (const int rc = ln8_check(who, "ivit_layernorm_i8_ex", x, ldx, rows, C, bias_int, s_ln, m, e, out, ldo, out_blocks)) return rc;
     LnArgs a{x, ldx, rows, C, bias_int, s_ln, m, e, out, ldo, out_blocks, nullptr, nullptr, g_ln_ablate, 0};
 #if IVIT_LAB
     a.stamps = g_ln_stamps;
@@ -1662,92 +1628,36 @@ IVIT_EXPORT int ivit_layernorm_i8_ex(const int8_t* x, int64_t ldx, int rows, int
     // CU, the constants table before the first row -- lose against the kernels below: 12 608 x 384 10.5 vs 8.7 us, r04e);
     // lab form 3: never, lab form 4: wherever it applies
     if (((g_ln_wave_per_row == 0 && ln_stream_pays(a)) || g_ln_wave_per_row == 4) && ln_stream_takes(a))
-        return launch_ln_stream<false>(a, st, "ivit_layernorm_i8", g_ln_stream_cfg);
-    if (C >= 512 && C <= 1024 && (g_ln_wave_per_row == 0 || g_ln_wave_per_row >= 3)) return launch_ln_v2<false>(a, st, "ivit_layernorm_i8");
-    // half a wave per row (constants in LDS, 3 * C floats) where it is the faster form: measured 17.5 vs 20.7 us at
-    // C = 384 and 14.0 vs 14.9 us at C = 192, but 36 vs 30 us at C = 768 (rows = 50 432)
-    if ((C <= 384 || g_ln_wave_per_row == 2) && C <= 1536 && g_ln_wave_per_row != 1) {
-        const int nj2 = (C / 4 + 31) / 32;
-        // row pairs per wave: 4 from 16 K rows (4 waves per SIMD busy either way), fewer below so that a small launch still fills the
-        // chip (lab: ln_ablate bits 21-22 = 1 / 2 / 3 force 4 / 2 / 1)
-        int g2 = rows > 16384 ? 4 : rows > 8192 ? 2 : 1;
-        if (nj2 > 3) g2 = 4;
-        if ((g_ln_ablate >> 21) & 3) g2 = nj2 > 3 ? 4 : 8 >> ((g_ln_ablate >> 21) & 3);
-        int grid = grid_for_rows(rows, 2 * g2);
-        if (grid > 1024) grid = 1024;          // 4 waves per SIMD resident
-        const size_t lds = (size_t)3 * C * sizeof(float);
-        // C <= 128 (Swin's patch norm, 401 408 rows of 96): one dword per lane -- the NJ = 2 form computes a second, fully masked one
-        // -- and 8 row pairs per wave from 64 K rows (the row statistics of 16 rows in one pass of lanes 0-7)
-        const bool one = nj2 == 1 && g2 == 4;
-        if (one && rows > 65536 && !(g_ln_ablate & (1u << 26))) {
-            grid = grid_for_rows(rows, 16);
-            if (grid > 1024) grid = 1024;
-            hipLaunchKernelGGL((layernorm_i8_pair_kernel<1, 8>), dim3(grid), dim3(NT), lds, st, a);
-        } else if (one) hipLaunchKernelGGL((layernorm_i8_pair_kernel<1, 4>), dim3(grid), dim3(NT), lds, st, a);
-        else if (nj2 <= 2 && g2 == 1) hipLaunchKernelGGL((layernorm_i8_pair_kernel<2, 1>), dim3(grid), dim3(NT), lds, st, a);
-        else if (nj2 <= 2 && g2 == 2) hipLaunchKernelGGL((layernorm_i8_pair_kernel<2, 2>), dim3(grid), dim3(NT), lds, st, a);
-        else if (nj2 <= 3 && g2 == 1) hipLaunchKernelGGL((layernorm_i8_pair_kernel<3, 1>), dim3(grid), dim3(NT), lds, st, a);
-        else if (nj2 <= 3 && g2 == 2) hipLaunchKernelGGL((layernorm_i8_pair_kernel<3, 2>), dim3(grid), dim3(NT), lds, st, a);
-        else if (nj2 <= 2) hipLaunchKernelGGL(layernorm_i8_pair_kernel<2>, dim3(grid), dim3(NT), lds, st, a);
-        else if (nj2 <= 3) hipLaunchKernelGGL(layernorm_i8_pair_kernel<3>, dim3(grid), dim3(NT), lds, st, a);
-        else if (nj2 <= 6) hipLaunchKernelGGL(layernorm_i8_pair_kernel<6>, dim3(grid), dim3(NT), lds, st, a);
-        else if (nj2 <= 8) hipLaunchKernelGGL(layernorm_i8_pair_kernel<8>, dim3(grid), dim3(NT), lds, st, a);
-        else hipLaunchKernelGGL(layernorm_i8_pair_kernel<12>, dim3(grid), dim3(NT), lds, st, a);
-        IVIT_CHECK_LAUNCH("ivit_layernorm_i8");
-    }
-    const int nj = (C / 4 + 63) / 64;
-    // each wave sets up its per-channel constants (bias and the requant bracket, 12*NJ registers per lane) once: launch no more workgroups than
-    // stay resident (256 CUs x waves/SIMD at the kernel's register count) and let them stride over the rows
-    const int resident = 256 * (nj <= 3 ? 3 : nj <= 8 ? 2 : 1);     // = the kernel's __launch_bounds__ occupancy
-    int grid = grid_for_rows(rows, nj <= 3 ? 8 : nj <= 4 ? 4 : 1);   // rows per wave and iteration: G of the kernel
-    if (grid > resident) grid = resident;
-    if (nj <= 1) hipLaunchKernelGGL(layernorm_i8_kernel<1>, dim3(grid), dim3(NT), 0, st, a);
-    else if (nj <= 2) hipLaunchKernelGGL(layernorm_i8_kernel<2>, dim3(grid), dim3(NT), 0, st, a);
-    else if (nj <= 3) hipLaunchKernelGGL(layernorm_i8_kernel<3>, dim3(grid), dim3(NT), 0, st, a);
-    else if (nj <= 4) hipLaunchKernelGGL(layernorm_i8_kernel<4>, dim3(grid), dim3(NT), 0, st, a);
-    else if (nj <= 8) hipLaunchKernelGGL(layernorm_i8_kernel<8>, dim3(grid), dim3(NT), 0, st, a);
-    else hipLaunchKernelGGL(layernorm_i8_kernel<16>, dim3(grid), dim3(NT), 0, st, a);
-    IVIT_CHECK_LAUNCH("ivit_layernorm_i8");
+        return launch_ln_stream<false>(a, st, who, g_ln_stream_cfg);
+    if (C >= 512 && C <= 1024 && (g_ln_wave_per_row == 0 || g_ln_wave_per_row >= 3)) return launch_ln_v2<false>(a, st, who);
+    // half a wave per row where it is the faster form: measured 17.5 vs 20.7 us at C = 384 and 14.0 vs 14.9 us at C = 192, but
+    // 36 vs 30 us at C = 768 (rows = 50 432)
+    if ((C <= 384 || g_ln_wave_per_row == 2) && C <= 1536 && g_ln_wave_per_row != 1) return launch_ln_pair(a, st, who);
+    return launch_ln_wave_per_row<false>(a, st, who);
 }
 
 IVIT_EXPORT int ivit_layernorm_i8_compat(const int8_t* x, int64_t ldx, int rows, int C, const float* bias_int,
                                          const float* s_ln, const uint32_t* m, const int32_t* e, const int8_t* remap,
                                          const float* phi, int8_t* out, int64_t ldo, int flags, ivit_stream_t stream)
 {
+    const char* who = "ivit_layernorm_i8_compat";
     const int out_blocks = flags & 1, outer = flags >> 8;     // IVIT_LN_OUT_BLOCKS, IVIT_LN_OUTER_MEAN(L)
-    IVIT_REQUIRE((flags & 0xfe) == 0 && outer >= 0 && (outer == 0 || rows % outer == 0), "ivit_layernorm_i8_compat: bad flags");
-    IVIT_REQUIRE(x && out && bias_int && s_ln && m && e && remap && phi, "ivit_layernorm_i8_compat: NULL operand");
-    IVIT_REQUIRE(rows > 0 && C >= 32 && C % 8 == 0 && C <= 4096, "ivit_layernorm_i8_compat: rows=%d C=%d unsupported", rows, C);
-    IVIT_REQUIRE(ldx % 4 == 0 && ldo % 4 == 0 && ldx >= C && ldo >= C && ((uintptr_t)x % 4 == 0) &&
-                     ((uintptr_t)out % 4 == 0),
-                 "ivit_layernorm_i8_compat: rows must be 4-byte aligned");
-    IVIT_REQUIRE(((uintptr_t)bias_int % 16 == 0) && ((uintptr_t)s_ln % 16 == 0) && ((uintptr_t)m % 16 == 0) &&
-                     ((uintptr_t)e % 16 == 0) && ((uintptr_t)phi % 4 == 0),
-                 "ivit_layernorm_i8_compat: per-channel tables must be 16-byte aligned");
-    IVIT_REQUIRE(out_blocks == 0 || (out_blocks == 1 && C % 64 == 0 && ldo == C && ((uintptr_t)out % 16 == 0) &&
-                                     ((int64_t)rows + 15) * C < 2147483648ll),
-                 "ivit_layernorm_i8_compat: block-layout output needs C %% 64 == 0, ldo == C and a buffer below 2 GiB");
+    IVIT_REQUIRE((flags & 0xfe) == 0 && outer >= 0 && (outer == 0 || rows % outer == 0), "%s: bad flags", who);
+    IVIT_REQUIRE(remap && phi, "%s: NULL operand", who);
+    IVIT_REQUIRE(C >= 32 && C % 8 == 0, "%s: rows=%d C=%d unsupported", who, rows, C);
+    if (const int rc = ln8_check(who, who, x, ldx, rows, C, bias_int, s_ln, m, e, out, ldo, out_blocks)) return rc;
+    IVIT_REQUIRE((uintptr_t)phi % 4 == 0, "%s: per-channel tables must be 16-byte aligned", who);
     LnArgs a{x, ldx, rows, C, bias_int, s_ln, m, e, out, ldo, out_blocks, remap, phi, g_ln_ablate, outer};
 #if IVIT_LAB
     a.stamps = g_ln_stamps;
 #endif
     hipStream_t st = ivit_stream(stream);
-    // C < 512 as well (Swin's patch norm, C = 96, 401 408 rows at batch 128: 255 us in the one-row-per-wave kernel below, whose waves
+    // C < 512 as well (Swin's patch norm, C = 96, 401 408 rows at batch 128: 255 us in the one-row-per-wave kernel, whose waves
     // are three-quarters idle at that width): the grouped kernel keeps 8 / 16 rows per wave in flight whatever the width
     if (((g_ln_wave_per_row == 0 && ln_stream_pays(a)) || g_ln_wave_per_row == 4) && ln_stream_takes(a))
-        return launch_ln_stream<true>(a, st, "ivit_layernorm_i8_compat", g_ln_stream_cfg);
-    if (C <= 1024 && (g_ln_wave_per_row == 0 || g_ln_wave_per_row >= 3)) return launch_ln_v2<true>(a, st, "ivit_layernorm_i8_compat");
-    const int nj = (C / 4 + 63) / 64;
-    const int resident = 256 * (nj <= 8 ? 2 : 1);                   // = the kernel's __launch_bounds__ occupancy
-    int grid = grid_for_rows(rows, nj <= 3 ? 8 : nj <= 4 ? 4 : 1);
-    if (grid > resident) grid = resident;
-    if (nj <= 1) hipLaunchKernelGGL((layernorm_i8_kernel<1, true>), dim3(grid), dim3(NT), 0, st, a);
-    else if (nj <= 2) hipLaunchKernelGGL((layernorm_i8_kernel<2, true>), dim3(grid), dim3(NT), 0, st, a);
-    else if (nj <= 3) hipLaunchKernelGGL((layernorm_i8_kernel<3, true>), dim3(grid), dim3(NT), 0, st, a);
-    else if (nj <= 4) hipLaunchKernelGGL((layernorm_i8_kernel<4, true>), dim3(grid), dim3(NT), 0, st, a);
-    else if (nj <= 8) hipLaunchKernelGGL((layernorm_i8_kernel<8, true>), dim3(grid), dim3(NT), 0, st, a);
-    else hipLaunchKernelGGL((layernorm_i8_kernel<16, true>), dim3(grid), dim3(NT), 0, st, a);
-    IVIT_CHECK_LAUNCH("ivit_layernorm_i8_compat");
+        return launch_ln_stream<true>(a, st, who, g_ln_stream_cfg);
+    if (C <= 1024 && (g_ln_wave_per_row == 0 || g_ln_wave_per_row >= 3)) return launch_ln_v2<true>(a, st, who);
+    return launch_ln_wave_per_row<true>(a, st, who);
 }
 
 IVIT_EXPORT int ivit_layernorm_i8(const int8_t* x, int64_t ldx, int rows, int C, const float* bias_int,
@@ -1819,7 +1729,7 @@ IVIT_EXPORT int ivit_shiftgelu_build_lut_ex(float s, uint32_t m, int32_t e, cons
 // Short rows (L <= 384: Swin stage 0, 401 408 rows of 384 bytes per launch at batch 128): HALF a wave per row, four rows per wave and
 // iteration.  With a whole wave per row only 96 of 2 x 192 lane-dwords carry data at L = 384, every row pays its own 256-byte table
 // slice and reduction chain, and the launch ran at 3.4 TB/s (90 us) where the wide rows of the ViT MLP reach 5.9 (round 4).
-// Maximum over the 32 lanes of a half wave in every lane (DPP inside the rows of 16, v_permlane16_swap across them: half_wave_allreduce)
+// Maximum over the 32 lanes of a half wave in every lane (DPP inside the rows of 16, v_permlane16_swap across them: as common.h lanes_allsum_i32<32>)
 IVIT_DEV int half_wave_allmax(int v)
 {
     typedef unsigned v2u_ __attribute__((ext_vector_type(2)));

@@ -4,6 +4,8 @@
 // PatchMerging :328-349, SwinTransformer.forward_features :539-558); operators as in rowops.hip / attention.hip.
 // The fork's swin_quant.py does not run as shipped (SURVEY.md finding 6); semantics are SURVEY Appendix A.8, pinned by
 // tests/golden/swin_tiny.npz (generated from the reference with harness-side shims).
+#include <type_traits>
+
 #include "common.h"
 #include "rowsum.h"
 
@@ -36,6 +38,8 @@ IVIT_DEV int pack4(int a, int b, int c, int d)
 {
     return (a & 0xff) | ((b & 0xff) << 8) | ((c & 0xff) << 16) | ((d & 0xff) << 24);
 }
+
+#include "ln_chain.h"
 
 // ------------------------------------------------------------------------------------------------
 // Row maps: the window partition / cyclic shift of SwinTransformerBlock.forward (swin_quant.py:258-271, 278-289) are
@@ -166,15 +170,7 @@ __global__ __launch_bounds__(NT) void layernorm_i16_i8_kernel(Ln16Args a)
             long long d = (long long)xr[c] - mean_int;
             var += d * d;
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            int vlo = __shfl_xor((int)(var & 0xffffffffll), o);
-            int vhi = __shfl_xor((int)(var >> 32), o);
-            var += ((long long)vhi << 32) | (unsigned)vlo;
-        }
-        float varf = (float)var, t = 65536.0f;                       // :45-49
-#pragma unroll 1
-        for (int it = 0; it < 10; ++it) t = floorf((t + floorf(varf / t)) * 0.5f);
+        const float t = ln_newton10_literal((float)(long long)lanes_allsum_u64<64>(var));   // :45-49
         const float factor = floorf((1.0f / t) * 2147483648.0f);     // :51
         int8_t* orow = a.out + win_row(a.map, row) * a.ldo;
         for (int c = lane; c < C; c += 64) {
@@ -215,15 +211,7 @@ __global__ __launch_bounds__(NT) void layernorm_i16_i8_literal_kernel(Ln16LitArg
             const long long d = (long long)(int)truncf(xint(c)) - mean_int;    // :38-40
             var += d * d;
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            int vlo = __shfl_xor((int)(var & 0xffffffffll), o);
-            int vhi = __shfl_xor((int)(var >> 32), o);
-            var += ((long long)vhi << 32) | (unsigned)vlo;
-        }
-        float varf = (float)var, t = 65536.0f;                                 // :45-49
-#pragma unroll 1
-        for (int it = 0; it < 10; ++it) t = floorf((t + floorf(varf / t)) * 0.5f);
+        const float t = ln_newton10_literal((float)(long long)lanes_allsum_u64<64>(var));   // :45-49
         const float factor = floorf((1.0f / t) * 2147483648.0f);               // :51
         int8_t* orow = a.out + win_row(a.map, row) * a.ldo;
         for (int c = lane; c < C; c += 64) {
@@ -241,7 +229,7 @@ __global__ __launch_bounds__(NT) void layernorm_i16_i8_literal_kernel(Ln16LitArg
 }
 
 // Round 4: the per-channel constants (bias, float32 bracket (lo, hi) of the QuantAct multiplier: the certificate of
-// layernorm_i8_kernel, rowops.hip) of the tiled 16-bit kernels are derived ONCE PER WORKGROUP into LDS -- one or two channels per
+// ln_chain.h) of the tiled 16-bit kernels are derived ONCE PER WORKGROUP into LDS -- one or two channels per
 // thread -- and read per chunk of 8 channels where the element chain needs them.  Rounds 1-3 kept them in 72 registers per lane
 // (NJ = 3), derived by every lane for its 24 channels in float64: 195-244 VGPRs = two waves per SIMD, where this VALU-bound chain
 // issues its half-rate instructions at 4.4 cycles instead of 3.2, and a prologue that a launch of few rows
@@ -260,18 +248,100 @@ IVIT_DEV float ln16_std10(float varf)
     const double gap = (s + 1.0) * (s + 1.0) - v;
     const bool slow = varf < 16777216.0f ? (varf < 142883.0f || gap == 1.0)      // rowops.hip LN_NEWTON_CONVERGED, ln_std10
                                           : gap <= (double)(varf * 2.384185791015625e-07f);   // 2^-22
-    if (__builtin_amdgcn_ballot_w64(slow) != 0) {
-        float t = 65536.0f;
-#pragma unroll 1
-        for (int it = 0; it < 10; ++it) t = floorf((t + floorf(varf / t)) * 0.5f);
-        return t;
-    }
+    if (__builtin_amdgcn_ballot_w64(slow) != 0) return ln_newton10_literal(varf);
     return (float)s;
 }
 
 IVIT_DEV void ln16_build_table(const Ln16Args& a, float* t_bias, float* t_lo, float* t_hi)
 {
     ln_build_table<NT>(a.m, a.e, a.s_ln, a.bias_int, a.C, t_bias, t_lo, t_hi);      // common.h: every load before the first use
+}
+
+// channel c (0-7) of a chunk of eight int16 held as four packed pairs
+IVIT_DEV int ln16_channel(const v4i& w, int c) { return (c & 1) ? (w[c >> 1] >> 16) : (int)(int16_t)w[c >> 1]; }
+
+// The tiled kernels from (w, mean_int) to the stores: w[j] = chunk sub + LPR * j of the lane's row (the integers the reference's
+// LayerNorm sees: q, or k' = trunc(phi(q)) at a natural scale), LPR lanes per row.  Variance (:40-42) -> ten Newton steps and the
+// factor (:45-52) -> the chain of ln_chain.h per channel: certificate, a wave with any uncertified element is redone literally.
+// `row` is clamped to the matrix, `live` says whether it exists.
+template <int LPR, int NJ>
+IVIT_DEV void ln16_tail(const Ln16Args& a, const v4i (&w)[NJ], int mean_int, int sub, bool live, int row, const float* t_bias,
+                        const float* t_lo, const float* t_hi)
+{
+    const int nd = a.C >> 3;
+    unsigned long long var = 0;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        if (sub + LPR * j < nd) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const unsigned d0 = (unsigned)abs((int)(int16_t)w[j][q] - mean_int);
+                const unsigned d1 = (unsigned)abs((w[j][q] >> 16) - mean_int);
+                var += (unsigned long long)d0 * d0;
+                var += (unsigned long long)d1 * d1;
+            }
+        }
+    }
+    var = lanes_allsum_u64<LPR>(var);
+    const float t = ln16_std10((float)var);                                 // :45-49
+    const float hfactor = floorf((1.0f / t) * 2147483648.0f) * 0.5f;        // :51; the /2 of :52 commutes (exact scaling)
+    int8_t* orow = a.out + win_row(a.map, row) * a.ldo;
+    int2 res[NJ];
+    unsigned unc = 0;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        int o[8];
+        const int dt = min(sub + LPR * j, nd - 1);      // this chunk's constants: 6 x 16 bytes from the workgroup's table
+        float bias8[8], lo8[8], hi8[8];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const float4 b4 = *reinterpret_cast<const float4*>(t_bias + 8 * dt + 4 * h);
+            const float4 l4 = *reinterpret_cast<const float4*>(t_lo + 8 * dt + 4 * h);
+            const float4 h4 = *reinterpret_cast<const float4*>(t_hi + 8 * dt + 4 * h);
+            bias8[4 * h] = b4.x; bias8[4 * h + 1] = b4.y; bias8[4 * h + 2] = b4.z; bias8[4 * h + 3] = b4.w;
+            lo8[4 * h] = l4.x; lo8[4 * h + 1] = l4.y; lo8[4 * h + 2] = l4.z; lo8[4 * h + 3] = l4.w;
+            hi8[4 * h] = h4.x; hi8[4 * h + 1] = h4.y; hi8[4 * h + 2] = h4.z; hi8[4 * h + 3] = h4.w;
+        }
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            const float dl = (float)(ln16_channel(w[j], c) - mean_int);
+            const float v = floorf(dl * hfactor);                           // :52
+            o[c] = ln_cert(v + bias8[c], lo8[c], hi8[c], unc);              // :61
+        }
+        res[j].x = pack4(o[0], o[1], o[2], o[3]);
+        res[j].y = pack4(o[4], o[5], o[6], o[7]);
+        __builtin_amdgcn_sched_barrier(0);      // one chunk's constants live at a time
+    }
+    if (__builtin_amdgcn_ballot_w64(unc != 0) != 0) {      // wave-uniform
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const int d = min(sub + LPR * j, nd - 1);
+            int o[8];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const float4 s4 = *reinterpret_cast<const float4*>(a.s_ln + 8 * d + 4 * h);
+                const uint4 m4 = *reinterpret_cast<const uint4*>(a.m + 8 * d + 4 * h);
+                const int4 e4 = *reinterpret_cast<const int4*>(a.e + 8 * d + 4 * h);
+                const float ss[4] = {s4.x, s4.y, s4.z, s4.w};
+                const double MM[4] = {dyadic_mult(m4.x, e4.x), dyadic_mult(m4.y, e4.y), dyadic_mult(m4.z, e4.z),
+                                      dyadic_mult(m4.w, e4.w)};
+#pragma unroll
+                for (int cc = 0; cc < 4; ++cc) {
+                    const int c = 4 * h + cc;
+                    const float dl = (float)(ln16_channel(w[j], c) - mean_int);
+                    const float v = floorf(dl * hfactor);
+                    o[c] = ln_literal(v + t_bias[8 * d + c], ss[cc], MM[cc]);
+                }
+            }
+            res[j].x = pack4(o[0], o[1], o[2], o[3]);
+            res[j].y = pack4(o[4], o[5], o[6], o[7]);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int d = sub + LPR * j;
+        if (live && d < nd) *reinterpret_cast<int2*>(orow + 8 * d) = res[j];
+    }
 }
 
 // Sub-wave tiling of the same computation for C % 8 == 0, C <= 1536: LPR lanes share a row (64 / LPR rows per wave and
@@ -307,91 +377,7 @@ __global__ __launch_bounds__(NT, 4) void layernorm_i16_i8_tiled_kernel(Ln16Args 
         }
         sum = lanes_allsum_i32<LPR>(sum);      // common.h: DPP / permlane swaps instead of ds_bpermute butterflies
         const int mean_int = (int)rintf((float)sum / fC);                       // :37
-        unsigned long long var = 0;
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            if (sub + LPR * j < nd) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const unsigned d0 = (unsigned)abs((int)(int16_t)w[j][q] - mean_int);
-                    const unsigned d1 = (unsigned)abs((w[j][q] >> 16) - mean_int);
-                    var += (unsigned long long)d0 * d0;
-                    var += (unsigned long long)d1 * d1;
-                }
-            }
-        }
-        var = lanes_allsum_u64<LPR>(var);
-        const float t = ln16_std10((float)var);                                 // :45-49
-        const float hfactor = floorf((1.0f / t) * 2147483648.0f) * 0.5f;        // :51; the /2 of :52 commutes (exact scaling)
-        int8_t* orow = a.out + win_row(a.map, min(row, a.rows - 1)) * a.ldo;
-        int2 res[NJ];
-        unsigned unc = 0;
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            int o[8];
-            const int dt = min(sub + LPR * j, nd - 1);      // this chunk's constants: 6 x 16 bytes from the workgroup's table
-            float bias8[8], lo8[8], hi8[8];
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const float4 b4 = *reinterpret_cast<const float4*>(t_bias + 8 * dt + 4 * h);
-                const float4 l4 = *reinterpret_cast<const float4*>(t_lo + 8 * dt + 4 * h);
-                const float4 h4 = *reinterpret_cast<const float4*>(t_hi + 8 * dt + 4 * h);
-                bias8[4 * h] = b4.x; bias8[4 * h + 1] = b4.y; bias8[4 * h + 2] = b4.z; bias8[4 * h + 3] = b4.w;
-                lo8[4 * h] = l4.x; lo8[4 * h + 1] = l4.y; lo8[4 * h + 2] = l4.z; lo8[4 * h + 3] = l4.w;
-                hi8[4 * h] = h4.x; hi8[4 * h + 1] = h4.y; hi8[4 * h + 2] = h4.z; hi8[4 * h + 3] = h4.w;
-            }
-#pragma unroll
-            for (int c = 0; c < 8; ++c) {
-                const int xv = (c & 1) ? (w[j][c >> 1] >> 16) : (int)(int16_t)w[j][c >> 1];
-                const float dl = (float)(xv - mean_int);
-                const float v = floorf(dl * hfactor);                           // :52
-                const float y = v + bias8[c];                                   // :61
-                const int tl = __float_as_int(__builtin_fmaf(y, lo8[c], 12582912.0f));
-                const int th = __float_as_int(__builtin_fmaf(y, hi8[c], 12582912.0f));
-                asm("v_sad_u32 %0, %1, %2, %3" : "=v"(unc) : "v"(tl), "v"(th), "v"(unc));
-                o[c] = clamp_i32(tl, 0x4B400000 - 128, 0x4B400000 + 127);       // low byte = int8 result
-            }
-            res[j].x = pack4(o[0], o[1], o[2], o[3]);
-            res[j].y = pack4(o[4], o[5], o[6], o[7]);
-            __builtin_amdgcn_sched_barrier(0);      // one chunk's constants live at a time
-        }
-        if (__builtin_amdgcn_ballot_w64(unc != 0) != 0) {
-            // literal evaluation (wave-uniform branch): x = y * s_ln (:63), z = round(x / s_ln) (quant_utils.py:220),
-            // RNE(float64(z) * M) (:229-230)
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) {
-                const int d = min(sub + LPR * j, nd - 1);
-                int o[8];
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const float4 s4 = *reinterpret_cast<const float4*>(a.s_ln + 8 * d + 4 * h);
-                    const uint4 m4 = *reinterpret_cast<const uint4*>(a.m + 8 * d + 4 * h);
-                    const int4 e4 = *reinterpret_cast<const int4*>(a.e + 8 * d + 4 * h);
-                    const float ss[4] = {s4.x, s4.y, s4.z, s4.w};
-                    const double MM[4] = {dyadic_mult(m4.x, e4.x), dyadic_mult(m4.y, e4.y), dyadic_mult(m4.z, e4.z),
-                                          dyadic_mult(m4.w, e4.w)};
-#pragma unroll
-                    for (int cc = 0; cc < 4; ++cc) {
-                        const int c = 4 * h + cc;
-                        const int xv = (c & 1) ? (w[j][c >> 1] >> 16) : (int)(int16_t)w[j][c >> 1];
-                        const float dl = (float)(xv - mean_int);
-                        const float v = floorf(dl * hfactor);
-                        const float y = v + t_bias[8 * d + c];
-                        const float x = y * ss[cc];
-                        const float z = rintf((float)((double)x * (1.0 / (double)ss[cc])));   // see layernorm_i8_kernel
-                        const double tt = (double)z * MM[cc] + IVIT_MAGIC;
-                        o[c] = clamp_i32((int)(unsigned)__double_as_longlong(tt), -128, 127);
-                    }
-                }
-                res[j].x = pack4(o[0], o[1], o[2], o[3]);
-                res[j].y = pack4(o[4], o[5], o[6], o[7]);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            const int d = sub + LPR * j;
-            if (live && d < nd) *reinterpret_cast<int2*>(orow + 8 * d) = res[j];
-        }
+        ln16_tail<LPR, NJ>(a, w, mean_int, sub, live, min(row, a.rows - 1), t_bias, t_lo, t_hi);
     }
 }
 
@@ -475,8 +461,7 @@ __global__ __launch_bounds__(NT, NJ >= 2 ? 3 : 4) void layernorm_i16_i8_tiled_co
             w[j] = (d < nd) ? *reinterpret_cast<const v4i*>(xr + 8 * d) : v4i{0, 0, 0, 0};
 #pragma unroll
             for (int c = 0; c < 8; ++c) {
-                const int qv = (c & 1) ? (w[j][c >> 1] >> 16) : (int)(int16_t)w[j][c >> 1];
-                const float x = (float)qv * s_in;                                   // quant_modules.py:387
+                const float x = (float)ln16_channel(w[j], c) * s_in;                                  // quant_modules.py:387
                 const float q0 = x * r_in;                                          // :36  x / s_in (Markstein, see above)
                 const float e = __builtin_fmaf(-s_in, q0, x);
                 ph[j][c] = __builtin_fmaf(e, r_in, q0);
@@ -593,91 +578,7 @@ __global__ __launch_bounds__(NT, NJ >= 2 ? 3 : 4) void layernorm_i16_i8_tiled_co
         __builtin_amdgcn_wave_barrier();                                        // before the next iteration overwrites s_phi
         }
         const int mean_int = (int)rintf(S / fC);                                // :37
-        unsigned long long var = 0;
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            if (sub + LPR * j < nd) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const unsigned d0 = (unsigned)abs((int)(int16_t)w[j][q] - mean_int);
-                    const unsigned d1 = (unsigned)abs((w[j][q] >> 16) - mean_int);
-                    var += (unsigned long long)d0 * d0;
-                    var += (unsigned long long)d1 * d1;
-                }
-            }
-        }
-        var = lanes_allsum_u64<LPR>(var);
-        const float t = ln16_std10((float)var);                                 // :45-49
-        const float hfactor = floorf((1.0f / t) * 2147483648.0f) * 0.5f;        // :51; the /2 of :52 commutes (exact scaling)
-        int8_t* orow = a.out + win_row(a.map, min(row, a.rows - 1)) * a.ldo;
-        int2 res[NJ];
-        unsigned unc = 0;
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            int o[8];
-            const int dt = min(sub + LPR * j, nd - 1);      // this chunk's constants: 6 x 16 bytes from the workgroup's table
-            float bias8[8], lo8[8], hi8[8];
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const float4 b4 = *reinterpret_cast<const float4*>(t_bias + 8 * dt + 4 * h);
-                const float4 l4 = *reinterpret_cast<const float4*>(t_lo + 8 * dt + 4 * h);
-                const float4 h4 = *reinterpret_cast<const float4*>(t_hi + 8 * dt + 4 * h);
-                bias8[4 * h] = b4.x; bias8[4 * h + 1] = b4.y; bias8[4 * h + 2] = b4.z; bias8[4 * h + 3] = b4.w;
-                lo8[4 * h] = l4.x; lo8[4 * h + 1] = l4.y; lo8[4 * h + 2] = l4.z; lo8[4 * h + 3] = l4.w;
-                hi8[4 * h] = h4.x; hi8[4 * h + 1] = h4.y; hi8[4 * h + 2] = h4.z; hi8[4 * h + 3] = h4.w;
-            }
-#pragma unroll
-            for (int c = 0; c < 8; ++c) {
-                const int xv = (c & 1) ? (w[j][c >> 1] >> 16) : (int)(int16_t)w[j][c >> 1];
-                const float dl = (float)(xv - mean_int);
-                const float v = floorf(dl * hfactor);                           // :52
-                const float y = v + bias8[c];                                   // :61
-                const int tl = __float_as_int(__builtin_fmaf(y, lo8[c], 12582912.0f));
-                const int th = __float_as_int(__builtin_fmaf(y, hi8[c], 12582912.0f));
-                asm("v_sad_u32 %0, %1, %2, %3" : "=v"(unc) : "v"(tl), "v"(th), "v"(unc));
-                o[c] = clamp_i32(tl, 0x4B400000 - 128, 0x4B400000 + 127);       // low byte = int8 result
-            }
-            res[j].x = pack4(o[0], o[1], o[2], o[3]);
-            res[j].y = pack4(o[4], o[5], o[6], o[7]);
-            __builtin_amdgcn_sched_barrier(0);      // one chunk's constants live at a time
-        }
-        if (__builtin_amdgcn_ballot_w64(unc != 0) != 0) {
-            // literal evaluation (wave-uniform branch): x = y * s_ln (:63), z = round(x / s_ln) (quant_utils.py:220),
-            // RNE(float64(z) * M) (:229-230)
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) {
-                const int d = min(sub + LPR * j, nd - 1);
-                int o[8];
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const float4 s4 = *reinterpret_cast<const float4*>(a.s_ln + 8 * d + 4 * h);
-                    const uint4 m4 = *reinterpret_cast<const uint4*>(a.m + 8 * d + 4 * h);
-                    const int4 e4 = *reinterpret_cast<const int4*>(a.e + 8 * d + 4 * h);
-                    const float ss[4] = {s4.x, s4.y, s4.z, s4.w};
-                    const double MM[4] = {dyadic_mult(m4.x, e4.x), dyadic_mult(m4.y, e4.y), dyadic_mult(m4.z, e4.z),
-                                          dyadic_mult(m4.w, e4.w)};
-#pragma unroll
-                    for (int cc = 0; cc < 4; ++cc) {
-                        const int c = 4 * h + cc;
-                        const int xv = (c & 1) ? (w[j][c >> 1] >> 16) : (int)(int16_t)w[j][c >> 1];
-                        const float dl = (float)(xv - mean_int);
-                        const float v = floorf(dl * hfactor);
-                        const float y = v + t_bias[8 * d + c];
-                        const float x = y * ss[cc];
-                        const float z = rintf((float)((double)x * (1.0 / (double)ss[cc])));   // see layernorm_i8_kernel
-                        const double tt = (double)z * MM[cc] + IVIT_MAGIC;
-                        o[c] = clamp_i32((int)(unsigned)__double_as_longlong(tt), -128, 127);
-                    }
-                }
-                res[j].x = pack4(o[0], o[1], o[2], o[3]);
-                res[j].y = pack4(o[4], o[5], o[6], o[7]);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            const int d = sub + LPR * j;
-            if (live && d < nd) *reinterpret_cast<int2*>(orow + 8 * d) = res[j];
-        }
+        ln16_tail<LPR, NJ>(a, w, mean_int, sub, live, min(row, a.rows - 1), t_bias, t_lo, t_hi);
     }
 }
 
@@ -1329,6 +1230,35 @@ IVIT_EXPORT int ivit_residual_requant_i16(const void* a, int a_bits, const uint3
     IVIT_CHECK_LAUNCH("ivit_residual_requant_i16");
 }
 
+// Do the tiled 16-bit LayerNorm kernels take this operand, and with which tiling: lpr = the smallest group of lanes that covers a
+// row with nj <= 3 chunks of 8 channels per lane.
+static bool ln16_tiling(const int16_t* x, int C, int64_t ldo, const float* bias_int, const float* s_ln, const uint32_t* m, const int32_t* e,
+                        const int8_t* out, int* lpr, int* nj)
+{
+    if (!(C % 8 == 0 && C <= 1536 && ldo % 8 == 0 && ((uintptr_t)x % 16 == 0) && ((uintptr_t)out % 8 == 0) &&
+          ((uintptr_t)bias_int % 16 == 0) && ((uintptr_t)s_ln % 16 == 0) && ((uintptr_t)m % 16 == 0) && ((uintptr_t)e % 16 == 0)))
+        return false;
+    const int nd = C / 8;
+    *lpr = 4;
+    while ((nd + *lpr - 1) / *lpr > 3) *lpr *= 2;
+    *nj = (nd + *lpr - 1) / *lpr;
+    return true;
+}
+
+// launch(integral_constant<LPR>, integral_constant<NJ>) for the tiling ln16_tiling chose: the eleven pairs it can return
+template <class F>
+static void ln16_dispatch(int lpr, int nj, F launch)
+{
+#define LN16_CASE(L, J) \
+    if (lpr == L && nj == J) launch(std::integral_constant<int, L>(), std::integral_constant<int, J>())
+    LN16_CASE(4, 1); LN16_CASE(4, 2); LN16_CASE(4, 3);
+    LN16_CASE(8, 2); LN16_CASE(8, 3);
+    LN16_CASE(16, 2); LN16_CASE(16, 3);
+    LN16_CASE(32, 2); LN16_CASE(32, 3);
+    LN16_CASE(64, 2); LN16_CASE(64, 3);
+#undef LN16_CASE
+}
+
 IVIT_EXPORT int ivit_layernorm_i16_i8(const int16_t* x, int rows, int C, const float* bias_int, const float* s_ln,
                                       const uint32_t* m, const int32_t* e, int8_t* out, int64_t ldo, int H, int W, int ws,
                                       int shift, ivit_stream_t stream)
@@ -1339,33 +1269,19 @@ IVIT_EXPORT int ivit_layernorm_i16_i8(const int16_t* x, int rows, int C, const f
     if (rc) return rc;
     Ln16Args a{x, rows, C, bias_int, s_ln, m, e, out, ldo, WinMap{H, W, ws, shift}, 0, 0};
     hipStream_t st = ivit_stream(stream);
-    const bool tiled = C % 8 == 0 && C <= 1536 && ldo % 8 == 0 && ((uintptr_t)x % 16 == 0) && ((uintptr_t)out % 8 == 0) &&
-                       ((uintptr_t)bias_int % 16 == 0) && ((uintptr_t)s_ln % 16 == 0) && ((uintptr_t)m % 16 == 0) &&
-                       ((uintptr_t)e % 16 == 0);
-    if (!tiled) {
+    int lpr, nj;
+    if (!ln16_tiling(x, C, ldo, bias_int, s_ln, m, e, out, &lpr, &nj)) {
         hipLaunchKernelGGL(layernorm_i16_i8_kernel, dim3(grid_for_rows(rows)), dim3(NT), 0, st, a);
         IVIT_CHECK_LAUNCH("ivit_layernorm_i16_i8");
     }
-    const int nd = C / 8;
-    int lpr = 4;
-    while ((nd + lpr - 1) / lpr > 3) lpr *= 2;   // smallest group of lanes that covers a row with <= 3 chunks per lane
-    const int nj = (nd + lpr - 1) / lpr;
-    // persistent-style launch: the per-channel constants (24 f64 reciprocals per lane) are set up once per wave, so keep
-    // the grid at the number of resident workgroups (2 per CU at ~195 VGPRs) and let each wave stride over many rows
-    int nblk = grid_for_rows(rows, 64 / lpr);
     // four workgroups per CU (128 VGPRs since the constants moved to LDS, round 4); each builds the table once and strides over rows
+    int nblk = grid_for_rows(rows, 64 / lpr);
     const int cap = ((g_ln_ablate >> 16) & 15) ? 256 * ((g_ln_ablate >> 16) & 15) : 1024;
     if (nblk > cap) nblk = cap;
-    const dim3 grid(nblk), blk(NT);
     const size_t tab_bytes = (size_t)3 * C * sizeof(float);
-#define LN16_CASE(L, J) \
-    if (lpr == L && nj == J) hipLaunchKernelGGL((layernorm_i16_i8_tiled_kernel<L, J>), grid, blk, tab_bytes, st, a)
-    LN16_CASE(4, 1); LN16_CASE(4, 2); LN16_CASE(4, 3);
-    LN16_CASE(8, 2); LN16_CASE(8, 3);
-    LN16_CASE(16, 2); LN16_CASE(16, 3);
-    LN16_CASE(32, 2); LN16_CASE(32, 3);
-    LN16_CASE(64, 2); LN16_CASE(64, 3);
-#undef LN16_CASE
+    ln16_dispatch(lpr, nj, [&](auto L, auto J) {
+        hipLaunchKernelGGL((layernorm_i16_i8_tiled_kernel<L.value, J.value>), dim3(nblk), dim3(NT), tab_bytes, st, a);
+    });
     IVIT_CHECK_LAUNCH("ivit_layernorm_i16_i8");
 }
 
@@ -1382,31 +1298,16 @@ IVIT_EXPORT int ivit_layernorm_i16_i8_compat(const int16_t* x, int rows, int C, 
     IVIT_REQUIRE(outer >= 0 && (outer == 0 || rows % outer == 0) && fast_division <= 1, "ivit_layernorm_i16_i8_compat: bad flags");
     Ln16Args b{x, rows, C, bias_int, s_ln, m, e, out, ldo, WinMap{H, W, ws, shift}, outer, (g_ln_ablate >> 20) & 1};   // lab bit 20: sums through LDS
     hipStream_t st = ivit_stream(stream);
-    const bool tiled = fast_division && C % 8 == 0 && C <= 1536 && ldo % 8 == 0 && ((uintptr_t)x % 16 == 0) &&
-                       ((uintptr_t)out % 8 == 0) && ((uintptr_t)bias_int % 16 == 0) && ((uintptr_t)s_ln % 16 == 0) &&
-                       ((uintptr_t)m % 16 == 0) && ((uintptr_t)e % 16 == 0);
-    if (tiled) {
-        const int nd = C / 8;
-        int lpr = 4;
-        while ((nd + lpr - 1) / lpr > 3) lpr *= 2;
-        const int nj = (nd + lpr - 1) / lpr;
+    int lpr, nj;
+    if (fast_division && ln16_tiling(x, C, ldo, bias_int, s_ln, m, e, out, &lpr, &nj)) {
         int nblk = grid_for_rows(rows, 64 / lpr);
         if (nblk > (nj >= 2 ? 768 : 1024)) nblk = nj >= 2 ? 768 : 1024;      // = the kernel's launch bounds: 3 / 4 workgroups per CU
         const size_t tab_bytes = (size_t)3 * C * sizeof(float);
         const float r_in = 1.0f / s_in;
-        bool launched = false;
-#define LN16C_CASE(L, J)                                                                                                  \
-    if (lpr == L && nj == J) {                                                                                            \
-        hipLaunchKernelGGL((layernorm_i16_i8_tiled_compat_kernel<L, J>), dim3(nblk), dim3(NT), tab_bytes, st, b, s_in, r_in);     \
-        launched = true;                                                                                                  \
-    }
-        LN16C_CASE(4, 1); LN16C_CASE(4, 2); LN16C_CASE(4, 3);
-        LN16C_CASE(8, 2); LN16C_CASE(8, 3);
-        LN16C_CASE(16, 2); LN16C_CASE(16, 3);
-        LN16C_CASE(32, 2); LN16C_CASE(32, 3);
-        LN16C_CASE(64, 2); LN16C_CASE(64, 3);
-#undef LN16C_CASE
-        if (launched) IVIT_CHECK_LAUNCH("ivit_layernorm_i16_i8_compat");
+        ln16_dispatch(lpr, nj, [&](auto L, auto J) {
+            hipLaunchKernelGGL((layernorm_i16_i8_tiled_compat_kernel<L.value, J.value>), dim3(nblk), dim3(NT), tab_bytes, st, b, s_in, r_in);
+        });
+        IVIT_CHECK_LAUNCH("ivit_layernorm_i16_i8_compat");
     }
     Ln16LitArgs a{b, s_in};
     hipLaunchKernelGGL(layernorm_i16_i8_literal_kernel, dim3(grid_for_rows(rows)), dim3(NT), 0, st, a);

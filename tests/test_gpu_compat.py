@@ -46,9 +46,10 @@ def ckat(golden_dir):
     return np.load(os.path.join(golden_dir, "compat_kat.npz"))
 
 
-@pytest.fixture(params=[0, 4, 3], ids=["product", "lab_streaming", "lab_grouped"])
+@pytest.fixture(params=[0, 4, 3, 1], ids=["product", "lab_streaming", "lab_grouped", "lab_wave_per_row"])
 def ln_form(request):
-    """the product library's own choice of LayerNorm kernel, and the streaming / grouped kernels forced through the lab build"""
+    """the product library's own choice of LayerNorm kernel, and the streaming / grouped / wave-per-row kernels forced through the
+    lab build (a wave per row with C <= 1024 exists in the lab library only)"""
     if request.param == 0:
         yield 0
         return

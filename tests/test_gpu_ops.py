@@ -1,5 +1,6 @@
 """GPU parity, operator level: every HIP kernel (through the C ABI) against the CPU oracle and the
 reference-generated known-answer vectors.  Bit-exact: these are integer results."""
+import functools
 import os
 
 import numpy as np
@@ -13,6 +14,7 @@ pytestmark = pytest.mark.gpu
 ivit = pytest.importorskip("ivit_amd")
 from ivit_amd import _lib  # noqa: E402
 from ivit_amd.prepare import dyadic  # noqa: E402
+import ln_cert_ref  # noqa: E402
 
 DEV = "cuda:0"
 
@@ -893,6 +895,48 @@ def test_layernorm_certificate_regimes(regime, Cn, ln_form):
               _lib.ptr(dev(lp.s_ln)), _lib.ptr(md), _lib.ptr(ed), _lib.ptr(out), Cn, st())
     got = out.cpu().numpy().astype(np.int32)
     assert np.array_equal(got, exp), f"{regime}: {(got != exp).sum()} of {got.size} differ"
+
+
+@functools.lru_cache(maxsize=None)
+def _literal_tail_case(Cn):
+    """18 rows whose certificate fails (the kernel must redo them literally) among 19 it certifies, told apart on the CPU
+    (tests/ln_cert_ref.py) -> (k, LayerNormParams, expected output)"""
+    k, gamma, beta = ln_cert_ref.draw_i8(Cn)
+    ks, s_out, exp, _ = ln_cert_ref.case(k, gamma, beta)
+    return ks, _ln_host(gamma, beta, s_out), exp
+
+
+@pytest.mark.parametrize("Cn", [100, 388, 520, 1100, 1540, 4096])
+def test_layernorm_literal_tail_rows(Cn, ln_form):
+    """the literal tail of every int8 LayerNorm kernel (ln_chain.h ln_literal4) is reached by construction: 37 rows, 18 of them
+    with an element whose float32 bracket certificate fails; NJ = 1, 2, 3, 5 -> 8, 7 -> 8, 16 dwords per lane of a wave per row,
+    each with a partial last group of dwords, and every other family at the widths it takes"""
+    k, lp, exp = _literal_tail_case(Cn)
+    rows = len(k)
+    out = torch.empty(rows, Cn, dtype=torch.int8, device=DEV)
+    md, ed = me_dev(lp.m, lp.e)
+    _lib.call("ivit_layernorm_i8", _lib.ptr(dev(k)), Cn, rows, Cn, _lib.ptr(dev(lp.bias_int)),
+              _lib.ptr(dev(lp.s_ln)), _lib.ptr(md), _lib.ptr(ed), _lib.ptr(out), Cn, st())
+    got = out.cpu().numpy().astype(np.int32)
+    assert np.array_equal(got, exp), f"{(got != exp).sum()} of {got.size} differ"
+
+
+def test_layernorm_literal_tail_rows_block_layout(ln_form):
+    """the same rows into the GEMM block layout: the half-wave and streaming kernels store while they compute and store again
+    after a literal redo"""
+    Cn = 1088
+    k, lp, exp = _literal_tail_case(Cn)
+    rows = len(k)
+    md, ed = me_dev(lp.m, lp.e)
+    bl = torch.zeros((rows + 15) // 16 * 16 * Cn, dtype=torch.int8, device=DEV)
+    _lib.call("ivit_layernorm_i8_ex", _lib.ptr(dev(k)), Cn, rows, Cn, _lib.ptr(dev(lp.bias_int)),
+              _lib.ptr(dev(lp.s_ln)), _lib.ptr(md), _lib.ptr(ed), _lib.ptr(bl), Cn, 1, st())
+    want = torch.zeros_like(bl)
+    _lib.call("ivit_tile_operand_i8", _lib.ptr(dev(exp.astype(np.int8))), Cn, rows, Cn, _lib.ptr(want), st())
+    v = _block_layout_host(np.ones((rows, Cn), np.int8)).astype(bool)
+    got, want = bl.cpu().numpy(), want.cpu().numpy()
+    assert np.array_equal(got[v], want[v]), f"{(got[v] != want[v]).sum()} of {v.sum()} differ"
+    assert not got[~v].any()
 
 
 @pytest.mark.parametrize("Cn", [192, 768])

@@ -16,6 +16,7 @@ from ivit_amd import _lib, synth  # noqa: E402
 from ivit_amd.checkpoint import load_fixture  # noqa: E402
 from ivit_amd.prepare import LayerNormParams, dyadic  # noqa: E402
 from ivit_amd.swin_engine import IntSwinEngine  # noqa: E402
+import ln_cert_ref  # noqa: E402
 
 DEV = "cuda:0"
 _KEEP = []
@@ -210,6 +211,28 @@ def test_layernorm_i16_certificate_regimes(regime, C):
               _lib.ptr(dev(lp.m.view(np.int32))), _lib.ptr(dev(lp.e)), _lib.ptr(out), C, 0, 0, 0, 0, st())
     got = out.cpu().numpy().astype(np.int32)
     assert np.array_equal(got, ref), f"{regime}: {(got != ref).sum()} of {got.size} differ"
+
+
+@pytest.mark.parametrize("C", [96, 200, 1536])      # (LPR, NJ) = (4, 3), (16, 2), (64, 3)
+def test_layernorm_i16_literal_tail_rows(C):
+    """the literal tail of the tiled 16-bit kernels (swin.hip ln16_tail) is reached by construction: 37 rows, 18 of them with an
+    element whose float32 bracket certificate fails, told apart on the CPU (tests/ln_cert_ref.py); power-of-two and natural
+    input scale"""
+    from ivit_amd.prepare import markstein_division_ok
+    x, gamma, beta = ln_cert_ref.draw_i16(C)
+    s_in = np.float32(0.000913)
+    assert markstein_division_ok(s_in, 16)
+    for name, layernorm in (("ivit_layernorm_i16_i8", orc.layernorm),
+                            ("ivit_layernorm_i16_i8_compat", lambda q, g, b: orc.layernorm_scaled(q, s_in, g, b))):
+        xs, s_out, ref, _ = ln_cert_ref.case(x, gamma, beta, layernorm)
+        lp = LayerNormParams(gamma, beta, s_out)
+        rows = len(xs)
+        out = torch.zeros(rows, C, dtype=torch.int8, device=DEV)
+        extra = (float(s_in), 1) if name.endswith("compat") else ()
+        _lib.call(name, _lib.ptr(dev(xs)), rows, C, *extra, _lib.ptr(dev(lp.bias_int)), _lib.ptr(dev(lp.s_ln)),
+                  _lib.ptr(dev(lp.m.view(np.int32))), _lib.ptr(dev(lp.e)), _lib.ptr(out), C, 0, 0, 0, 0, st())
+        got = out.cpu().numpy().astype(np.int32)
+        assert np.array_equal(got, ref), f"{name}: {(got != ref).sum()} of {got.size} differ"
 
 
 def test_swin_aliased_workspaces_equal_separate_buffers():
