@@ -31,6 +31,7 @@ SIGNATURES = {
     "ivit_attention_fused_i8_compat_band": [vp, vp, ci, ci, ci, ci, u32, i32, f32, u32, i32, vp, vp, ci, ci, vp],
     "ivit_attention_fused_i8_wide": [vp, vp, ci, ci, ci, ci, u32, i32, f32, u32, i32, vp, vp, ci, ci, ci, vp],
     "ivit_attention_fused_i8_long": [vp, vp, ci, ci, ci, ci, u32, i32, f32, u32, i32, vp, vp, ci, ci, vp],
+    "ivit_attention_fused_i8_wide_long": [vp, vp, ci, ci, ci, ci, u32, i32, f32, u32, i32, vp, vp, ci, ci, ci, vp],
     "ivit_attention_cls_i8": [vp, vp, vp, vp, i64, ci, ci, ci, ci, u32, i32, f32, u32, i32, vp, vp, ci, vp],
     "ivit_shiftgelu_build_lut_ex": [f32, u32, i32, vp, vp, vp],
     "ivit_shiftgelu_lut_i8_ex": [vp, i64, ci, ci, vp, vp, i64, ci, vp],

@@ -641,10 +641,16 @@ struct LongArgs {
 
 // NKT: full key tiles held in registers (T >> 4 <= NKT); NTH: threads per workgroup, one workgroup per CU (1024: 128 VGPRs, enough
 // for 40 tiles; 768: 168 VGPRs, 142-149 used, for 64 tiles)
-template <int MODE, bool RQ32, int NKT, int NTH>
+// PB: width of the Shiftmax output as in attention_kernel: 8, or 16 -- passes 1 and 2 are the same, pass 3 takes
+// p16 = floor(fl32(e * factor) / 2^16) in [0, 2^15] as three 7-bit planes p = c + 128 b + 16384 a with one P . V accumulator set
+// each (the a plane only for a key step in which a wave holds such a probability), and the output is requantised in the
+// reference's two steps.  The two further accumulator sets are 32 registers: 40 tiles in the 12-wave form, 64 in an 8-wave one
+// (512 threads: 256 VGPRs).
+template <int MODE, bool RQ32, int NKT, int NTH, int PB = 8>
 __global__ __launch_bounds__(NTH, 1) void attention_long_kernel(LongArgs a)
 {
     static_assert(!RQ32 || MODE != 1, "RQ32: a power-of-two score multiplier (Shiftmax: power-of-two input scale)");
+    static_assert(PB == 8 || (PB == 16 && MODE != 2), "16-bit probabilities: Shiftmax only");
     constexpr int NKS = NKT / 4 + 1;          // key steps of 64: NKT full key tiles and the partial one
     constexpr int KOFF = RQ32 ? RQ_OFF : 0;    // RQ32: scores carry the magic constant's exponent bits (low byte = k + 128)
     extern __shared__ __attribute__((aligned(16))) char lsm[];
@@ -912,13 +918,91 @@ __global__ __launch_bounds__(NTH, 1) void attention_long_kernel(LongArgs a)
             }
             return __builtin_amdgcn_perm(p[1], p[0], 0x0c0c0703u) | __builtin_amdgcn_perm(p[3], p[2], 0x07030c0cu);
         };
-        const unsigned wl = partial ? prob_word(sl, vr) : 0u;
+        // PB 16: u = trunc(fl32(e * factor)) <= 2^31, p16 = u >> 16 (:175 with output_bit 16): plane c = bits 16 .. 22 of u, plane b
+        // = bits 23 .. 29, plane a = bits 30, 31 (attention_kernel PB 16).  -> the OR of the four u (whether plane a is needed)
+        auto prob_planes = [&](unsigned packed, int nreal, unsigned& wc, unsigned& wb) -> unsigned {
+            const unsigned dk = rep - packed;
+            unsigned p[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const unsigned idx = (dk >> (8 * r)) & 255u;
+                const float ev = MODE == 0 ? lutf[idx] : (float)expo(idx);
+                p[r] = r < nreal ? (unsigned)(ev * factor) : 0u;
+            }
+            wc = (__builtin_amdgcn_perm(p[1], p[0], 0x0c0c0602u) | __builtin_amdgcn_perm(p[3], p[2], 0x06020c0cu)) & 0x7f7f7f7fu;
+            wb = (__builtin_amdgcn_perm(p[1] << 1, p[0] << 1, 0x0c0c0703u) | __builtin_amdgcn_perm(p[3] << 1, p[2] << 1, 0x07030c0cu)) &
+                 0x7f7f7f7fu;
+            return p[0] | p[1] | p[2] | p[3];
+        };
+        auto prob_plane_a = [&](unsigned packed, int nreal) -> unsigned {      // from the products again: rare
+            const unsigned dk = rep - packed;
+            unsigned w = 0;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const unsigned idx = (dk >> (8 * r)) & 255u;
+                const float ev = MODE == 0 ? lutf[idx] : (float)expo(idx);
+                const unsigned u = r < nreal ? (unsigned)(ev * factor) : 0u;
+                w |= (u >> 30) << (8 * r);
+            }
+            return w;
+        };
+        unsigned wl = 0u, wlb = 0u, ul = 0u;       // the partial tile's words (PB 16: planes c and b, and the OR of its u)
+        if constexpr (PB == 16) {
+            if (partial) ul = prob_planes(sl, vr, wl, wlb);
+        } else {
+            wl = partial ? prob_word(sl, vr) : 0u;
+        }
+        // PB 16: three accumulator sets, O = o + (o_b << 7) + (o_a << 14) = sum p16 * v.  Bounds for T <= 1025 keys, |v| <= 128:
+        //   S not clamped: factor <= 2^31 / S, so the row's p16 sum to at most 2^15 (+ the float32 roundings) and |O| <= 2^22 for any T;
+        //   S clamped at 2^31 (:173): factor = 1, p16 = e >> 16 with e <= 2 |x0| 2^14 <= 2^27 (x0 >= -4096), i.e. p16 <= 2^11 per key
+        //   and |O| <= 1025 * 2^11 * 128 = 1025 * 2^18 < 2^28.01.
+        // Every plane term is bounded by the same sum: c, 128 b and 16384 a are each <= p16, so |o|, |o_b << 7| and |o_a << 14| are
+        // each <= 128 * sum p16 <= 1025 * 2^18, the accumulators themselves |o|, |o_b| <= 1025 * 127 * 128 < 2^24 and |o_a| <=
+        // 1025 * 2 * 128 < 2^19, and any partial sum of the three terms is below 3 * 2^28.01 < 2^30: all in int32.
         v4i o[4];
+        v4i o_b[PB == 16 ? 4 : 1], o_a[PB == 16 ? 4 : 1];
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) o[dt] = v4i{0, 0, 0, 0};
+        if constexpr (PB == 16) {
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt) o_b[dt] = o_a[dt] = v4i{0, 0, 0, 0};
+        }
 #pragma unroll
         for (int ks = 0; ks < NKS; ++ks) {
             if (ks >= nks) continue;
+            if constexpr (PB == 16) {
+                v4i pc, pb;
+                unsigned any_u = 0;
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    const int kt = 4 * ks + t;
+                    unsigned wc = kt == nf ? wl : 0u, wb = kt == nf ? wlb : 0u;
+                    any_u |= kt == nf ? ul : 0u;
+                    if (kt < NKT && kt < nf) any_u |= prob_planes(sc[kt < NKT ? kt : 0], 4, wc, wb);
+                    pc[t] = (int)wc;
+                    pb[t] = (int)wb;
+                }
+                const bool hi_pass = __builtin_amdgcn_ballot_w64((any_u >> 30) != 0) != 0;      // wave-uniform, rare
+                v4i pa = {0, 0, 0, 0};
+                if (hi_pass) {
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) {
+                        const int kt = 4 * ks + t;
+                        unsigned w = (partial && kt == nf) ? prob_plane_a(sl, vr) : 0u;
+                        if (kt < NKT && kt < nf) w = prob_plane_a(sc[kt < NKT ? kt : 0], 4);
+                        pa[t] = (int)w;
+                    }
+                }
+#pragma unroll
+                for (int dt = 0; dt < 4; ++dt) {
+                    const int d = 16 * dt + l15;
+                    const v4i vf = *reinterpret_cast<const v4i*>(vt + d * vt_row + (((4 * ks + g) ^ (d & 15)) << 4));
+                    o[dt] = __builtin_amdgcn_mfma_i32_16x16x64_i8(vf, pc, o[dt], 0, 0, 0);
+                    o_b[dt] = __builtin_amdgcn_mfma_i32_16x16x64_i8(vf, pb, o_b[dt], 0, 0, 0);
+                    if (hi_pass) o_a[dt] = __builtin_amdgcn_mfma_i32_16x16x64_i8(vf, pa, o_a[dt], 0, 0, 0);
+                }
+                continue;
+            }
             v4i pk;
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
@@ -955,7 +1039,17 @@ __global__ __launch_bounds__(NTH, 1) void attention_long_kernel(LongArgs a)
         for (int dt = 0; dt < 4; ++dt) {
             int ob[4];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) ob[r] = clamp_i32(requant_exact(o[dt][r], a.Mo), -128, 127);
+            for (int r = 0; r < 4; ++r) {
+                if constexpr (PB == 16) {
+                    // |O| < 2^29 (above): the reference's float64 product rounds at 53 bits first (quant_utils.py:229-230), so
+                    // product and rounding are two steps, as in attention_kernel
+                    const int O = o[dt][r] + (o_b[dt][r] << 7) + (o_a[dt][r] << 14);
+                    const double t = (double)O * a.Mo + IVIT_MAGIC;
+                    ob[r] = clamp_i32((int)(unsigned)__double_as_longlong(t), -128, 127);
+                } else {
+                    ob[r] = clamp_i32(requant_exact(o[dt][r], a.Mo), -128, 127);
+                }
+            }
             wq[dt] = __builtin_amdgcn_perm((unsigned)ob[1], (unsigned)ob[0], 0x0c0c0400u) | __builtin_amdgcn_perm((unsigned)ob[3], (unsigned)ob[2], 0x04000c0cu);
         }
         // 4 x 4 dword transpose over the four lanes of a query: lane g ends with bytes d = 16 g .. 16 g + 15 (as attention_kernel)
@@ -1318,48 +1412,59 @@ IVIT_EXPORT int ivit_attention_fused_i8(const int8_t* qkv, int8_t* out, int batc
     return ivit_attention_fused_i8_ex(qkv, out, batch, heads, tokens, head_dim, m_s, e_s, s_attn, m_o, e_o, 0, stream);
 }
 
-IVIT_EXPORT int ivit_attention_fused_i8_long(const int8_t* qkv, int8_t* out, int batch, int heads, int tokens, int head_dim,
-                                             uint32_t m_s, int32_t e_s, float s_attn, uint32_t m_o, int32_t e_o,
-                                             const uint32_t* exp2d, const uint32_t* band, int band_w, int out_blocks,
-                                             ivit_stream_t stream)
+// fn: the entry point's name for the messages; pb: 8 or 16, the width of the Shiftmax output
+static int attention_long_launch(const char* fn, const int8_t* qkv, int8_t* out, int batch, int heads, int tokens, int head_dim,
+                                 uint32_t m_s, int32_t e_s, float s_attn, uint32_t m_o, int32_t e_o, const uint32_t* exp2d,
+                                 const uint32_t* band, int band_w, int pb, int out_blocks, ivit_stream_t stream)
 {
-    IVIT_REQUIRE(qkv && out, "ivit_attention_fused_i8_long: NULL operand");
-    IVIT_REQUIRE(batch > 0 && heads > 0, "ivit_attention_fused_i8_long: empty batch");
+    IVIT_REQUIRE(qkv && out, "%s: NULL operand", fn);
+    IVIT_REQUIRE(batch > 0 && heads > 0, "%s: empty batch", fn);
     if (head_dim != HD || tokens < LONG_T_MIN || tokens > LONG_T_MAX) {
-        ivit_set_error("ivit_attention_fused_i8_long: unsupported geometry head_dim=%d tokens=%d (need 64, %d..%d)", head_dim, tokens,
+        ivit_set_error("%s: unsupported geometry head_dim=%d tokens=%d (need 64, %d..%d)", fn, head_dim, tokens,
                        LONG_T_MIN, LONG_T_MAX);
         return IVIT_ERR_UNSUPPORTED;
     }
-    IVIT_REQUIRE(((uintptr_t)qkv % 16 == 0) && ((uintptr_t)out % 16 == 0), "ivit_attention_fused_i8_long: misaligned operand (16-byte rows)");
-    IVIT_REQUIRE(s_attn > 0.0f, "ivit_attention_fused_i8_long: scale must be positive");
+    IVIT_REQUIRE(((uintptr_t)qkv % 16 == 0) && ((uintptr_t)out % 16 == 0), "%s: misaligned operand (16-byte rows)", fn);
+    IVIT_REQUIRE(s_attn > 0.0f, "%s: scale must be positive", fn);
     IVIT_REQUIRE(out_blocks == 0 || (out_blocks == 1 && ((int64_t)batch * tokens + 15) * heads * head_dim < 2147483648ll),
-                 "ivit_attention_fused_i8_long: bad output layout (block-layout buffers stay below 2 GiB)");
-    IVIT_REQUIRE((int64_t)batch * heads * tokens * head_dim * 3 < ((int64_t)1 << 40), "ivit_attention_fused_i8_long: qkv too large");
-    IVIT_REQUIRE((uintptr_t)exp2d % 4 == 0, "ivit_attention_fused_i8_long: misaligned exponent table");
+                 "%s: bad output layout (block-layout buffers stay below 2 GiB)", fn);
+    IVIT_REQUIRE((int64_t)batch * heads * tokens * head_dim * 3 < ((int64_t)1 << 40), "%s: qkv too large", fn);
+    IVIT_REQUIRE((uintptr_t)exp2d % 4 == 0, "%s: misaligned exponent table", fn);
     IVIT_REQUIRE(band_w == 0 || (band && band_w >= 16 && band_w <= 256 && band_w % 16 == 0 && (uintptr_t)band % 16 == 0),
-                 "ivit_attention_fused_i8_long: band table must be 16-byte aligned, width a multiple of 16 in [16, 256]");
+                 "%s: band table must be 16-byte aligned, width a multiple of 16 in [16, 256]", fn);
     LongArgs a{};
     a.qkv = qkv; a.out = out; a.batch = batch; a.heads = heads; a.tokens = tokens;
     a.out_blocks = out_blocks;
     a.Ms = ivit_dyadic_to_double(m_s, e_s);
     a.Mo = ivit_dyadic_to_double(m_o, e_o);
-    IVIT_REQUIRE(a.Ms < 2048.0 && a.Mo < 512.0, "ivit_attention_fused_i8_long: requant multiplier too large");
+    IVIT_REQUIRE(a.Ms < 2048.0 && a.Mo < 512.0, "%s: requant multiplier too large", fn);
     const bool ms_pow2 = m_s != 0 && (m_s & (m_s - 1)) == 0 && a.Ms >= 1e-30;
     a.Ms32 = (float)a.Ms;
     const float x0f = __builtin_floorf((1.0f / s_attn) * -1.0f);   // ivit_modules.py:154
-    IVIT_REQUIRE(x0f <= -1.0f && x0f >= -4096.0f, "ivit_attention_fused_i8_long: x0=%g outside [-4096,-1]", (double)x0f);
+    IVIT_REQUIRE(x0f <= -1.0f && x0f >= -4096.0f, "%s: x0=%g outside [-4096,-1]", fn, (double)x0f);
     a.x0 = (int)x0f;    // exp_int <= 2 |x0| * 2^14 <= 2^27: 16 of them in u32, the row in u64 (common.h rows_allsum_u64)
     a.table = band_w ? band : exp2d;
     a.band_w = band_w;
     const int nkt = (tokens + 15) >> 4, nks = (nkt + 3) >> 2;
     a.vt_row = ((nks + 3) >> 2) * 256;
     const size_t lds = (size_t)LONG_LUT_BYTES + (size_t)nkt * 16 * HD + (size_t)HD * a.vt_row;    // <= 150528 bytes at 1025 tokens
+    // 16-bit probabilities: two more accumulator sets, so each token range takes the next smaller workgroup
     const bool natural = band_w || exp2d, wide = (tokens >> 4) > 40;
-    const int nth = wide ? 768 : 1024;
+    const int nth = pb == 16 ? (wide ? 512 : 768) : (wide ? 768 : 1024);
     a.parts = attention_long_parts(batch * heads, nkt, nth / 64);
     const dim3 grid(batch * heads * a.parts), blk(nth);
     hipStream_t st = ivit_stream(stream);
-    if (!wide) {
+    if (pb == 16) {
+        if (!wide) {
+            if (natural) hipLaunchKernelGGL((attention_long_kernel<1, false, 40, 768, 16>), grid, blk, lds, st, a);
+            else if (ms_pow2) hipLaunchKernelGGL((attention_long_kernel<0, true, 40, 768, 16>), grid, blk, lds, st, a);
+            else hipLaunchKernelGGL((attention_long_kernel<0, false, 40, 768, 16>), grid, blk, lds, st, a);
+        } else {
+            if (natural) hipLaunchKernelGGL((attention_long_kernel<1, false, 64, 512, 16>), grid, blk, lds, st, a);
+            else if (ms_pow2) hipLaunchKernelGGL((attention_long_kernel<0, true, 64, 512, 16>), grid, blk, lds, st, a);
+            else hipLaunchKernelGGL((attention_long_kernel<0, false, 64, 512, 16>), grid, blk, lds, st, a);
+        }
+    } else if (!wide) {
         if (natural) hipLaunchKernelGGL((attention_long_kernel<1, false, 40, 1024>), grid, blk, lds, st, a);
         else if (ms_pow2) hipLaunchKernelGGL((attention_long_kernel<0, true, 40, 1024>), grid, blk, lds, st, a);
         else hipLaunchKernelGGL((attention_long_kernel<0, false, 40, 1024>), grid, blk, lds, st, a);
@@ -1368,7 +1473,26 @@ IVIT_EXPORT int ivit_attention_fused_i8_long(const int8_t* qkv, int8_t* out, int
         else if (ms_pow2) hipLaunchKernelGGL((attention_long_kernel<0, true, 64, 768>), grid, blk, lds, st, a);
         else hipLaunchKernelGGL((attention_long_kernel<0, false, 64, 768>), grid, blk, lds, st, a);
     }
-    IVIT_CHECK_LAUNCH("ivit_attention_fused_i8_long");
+    IVIT_CHECK_LAUNCH(fn);
+}
+
+IVIT_EXPORT int ivit_attention_fused_i8_long(const int8_t* qkv, int8_t* out, int batch, int heads, int tokens, int head_dim,
+                                             uint32_t m_s, int32_t e_s, float s_attn, uint32_t m_o, int32_t e_o,
+                                             const uint32_t* exp2d, const uint32_t* band, int band_w, int out_blocks,
+                                             ivit_stream_t stream)
+{
+    return attention_long_launch("ivit_attention_fused_i8_long", qkv, out, batch, heads, tokens, head_dim, m_s, e_s, s_attn, m_o, e_o,
+                                 exp2d, band, band_w, 8, out_blocks, stream);
+}
+
+IVIT_EXPORT int ivit_attention_fused_i8_wide_long(const int8_t* qkv, int8_t* out, int batch, int heads, int tokens, int head_dim,
+                                                  uint32_t m_s, int32_t e_s, float s_attn, uint32_t m_o, int32_t e_o,
+                                                  const uint32_t* exp2d, const uint32_t* band, int band_w, int softmax_bits,
+                                                  int out_blocks, ivit_stream_t stream)
+{
+    IVIT_REQUIRE(softmax_bits == 8 || softmax_bits == 16, "ivit_attention_fused_i8_wide_long: softmax_bits must be 8 or 16");
+    return attention_long_launch("ivit_attention_fused_i8_wide_long", qkv, out, batch, heads, tokens, head_dim, m_s, e_s, s_attn, m_o,
+                                 e_o, exp2d, band, band_w, softmax_bits, out_blocks, stream);
 }
 
 IVIT_EXPORT int ivit_attention_fused_i8_ibert_long(const int8_t* qkv, int8_t* out, int batch, int heads, int tokens, int head_dim,

@@ -48,9 +48,10 @@ def occupancy_rules(path, what):
     bad, seen = [], 0
     for name, r in sorted(kernels.items()):
         if what == "attention" and "attention_long_kernel" in name:
-            # attention_long_kernel<MODE, RQ32, NKT, NTH>: one workgroup of NTH threads per CU (the launcher's 256 slots), i.e.
-            # NTH / 256 waves per SIMD; the packed score rows must stay in registers: no scratch
-            m = re.search(r"attention_long_kernelILi(\d+)ELb([01])ELi(\d+)ELi(\d+)E", name)
+            # attention_long_kernel<MODE, RQ32, NKT, NTH, PB>: one workgroup of NTH threads per CU (the launcher's 256 slots), i.e.
+            # NTH / 256 waves per SIMD; the packed score rows must stay in registers: no scratch.  PB = 16 (the three probability
+            # planes): 768 threads up to 40 key tiles, 512 above
+            m = re.search(r"attention_long_kernelILi(\d+)ELb([01])ELi(\d+)ELi(\d+)ELi(8|16)E", name)
             occ, need_no_scratch = int(m.group(4)) // 256, True
         elif what == "attention" and "attention_cls_kernel" in name:
             # attention_cls_kernel<MODE>: CLS_OCC = 3 workgroups of four waves per CU (its __launch_bounds__; DeiT-B at batch 256

@@ -133,18 +133,21 @@ def attention_spec(family, s_S, s_at, s_pv, s_out, upload, device, st, ibert_ran
 
 def attention(a, family, qkv, out, B, H, T, hd, st, blocks=False, softmax_bits=None):
     """Fused attention of an attention_spec `a` on head-major qkv [3, B, H, T, hd] -> out [B * T, H * hd] (`blocks`: in the block
-    layout).  Up to 207 tokens the short kernels, 208 .. 1025 the long-row ones (the same arguments); softmax_bits: given on the
-    16-bit stream, whose "wide" forms take it before the layout flag."""
+    layout).  Up to 207 tokens the short kernels, 208 .. 1025 the long-row ones (the same arguments); softmax_bits: given where
+    the Shiftmax output may be 16 bits wide (the 16-bit stream of the engine, a 16-bit softmax on the module path), whose "wide"
+    forms take it before the layout flag.  I-BERT's softmax has no wide long-row kernel: an error, nothing is launched."""
     p, wide, long = _lib.ptr, softmax_bits is not None, T > 207
     sm = (softmax_bits,) if wide else ()
+    if family == "ibert" and wide and long:
+        raise NotImplementedError(f"no fused I-BERT attention with a softmax_bits argument above 207 tokens (tokens={T})")
     if family == "ibert":
         name = ("ivit_attention_fused_i8_ibert_wide" if wide else "ivit_attention_fused_i8_ibert_long" if long else
                 "ivit_attention_fused_i8_ibert")
         _lib.call(name, p(qkv), p(out), B, H, T, hd, a["ms"][0], a["ms"][1], a["mo"][0], a["mo"][1], p(a["ib_table"]), p(a["band"]),
                   a["band_w"], *sm, int(blocks), st)
     else:
-        name = ("ivit_attention_fused_i8_wide" if wide else "ivit_attention_fused_i8_long" if long else
-                "ivit_attention_fused_i8_compat_band")
+        name = ("ivit_attention_fused_i8_wide_long" if wide and long else "ivit_attention_fused_i8_wide" if wide else
+                "ivit_attention_fused_i8_long" if long else "ivit_attention_fused_i8_compat_band")
         _lib.call(name, p(qkv), p(out), B, H, T, hd, a["ms"][0], a["ms"][1], a["s_attn"], a["mo"][0], a["mo"][1], p(a["exp2d"]),
                   p(a["band"]), a["band_w"], *sm, int(blocks), st)
 

@@ -84,7 +84,7 @@ class IBERTIntLayerNorm(nn.Module):
     def forward(self, x, scaling_factor=None, exponents=None):
         if isinstance(x, lazy.QT):
             s_in = lazy.host_of(scaling_factor)
-            if x.q8 is not None and s_in is not None and s_in.size == 1 and not self.overflow_handling:
+            if (x.q8 is not None or x.q16 is not None) and s_in is not None and s_in.size == 1 and not self.overflow_handling:
                 def build():      # the scale this module returns: sqrt(C) / 2^30 * gamma (:145-153)
                     C_ = x.shape[-1]
                     sf = f32(np.sqrt(f32(C_)).astype(np.float32) / f32(2 ** 30))
@@ -189,7 +189,7 @@ class IBERTIntSoftmax(nn.Module):
 
     def forward(self, x, scaling_factor):
         if isinstance(x, lazy.QT):
-            if (isinstance(x.node, lazy.Scores) and not x.views and self.output_bit == 8 and not self.act.running_stat
+            if (isinstance(x.node, lazy.Scores) and not x.views and self.output_bit in (8, 16) and not self.act.running_stat
                     and scaling_factor is x.node.s_out_qs):
                 so = lazy._cache(self, ("s_out", str(x.device)), lambda: lazy.QS.make(f32(2 / 2 ** self.output_bit), x.device))   # :317
                 return lazy.QT.wrap(x.shape, x.device, node=lazy.Probs(x, self)), so

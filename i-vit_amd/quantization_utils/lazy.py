@@ -30,9 +30,10 @@ calls and removes the round trips, for a FROZEN model (every QuantAct fixed):
 Every (m, e) pair, table, row map, bias / mask table and integer weight is derived on the host from host-side scales and cached
 per module, so after the first (warm-up) forward a frozen forward reads nothing back from the device: it runs under
 `torch.cuda.set_sync_debug_mode("error")` and can be captured into a HIP graph (tests/test_gpu_modules.py, test_gpu_swin_lazy.py).
-Covers the I-ViT and the I-BERT operator families (ivit_modules.py, ibert_modules.py) at 8-bit QuantAct widths and Swin with the
-I-ViT operators (8-bit QuantActs, 16-bit residual stream); other configurations (ViT's 16-bit widths, mixed families) take the
-ordinary module path through the materialisation rule above.
+Covers the I-ViT and the I-BERT operator families (ivit_modules.py, ibert_modules.py) at 8-bit QuantAct widths, ViT's 16-bit
+configurations (vit_quant.py:180-187: the 16-bit residual stream with softmax and position embedding at 8 or 16 bits, resolve16)
+and Swin with the I-ViT operators (8-bit QuantActs, 16-bit residual stream); other configurations (other width mixtures, mixed
+families) take the ordinary module path through the materialisation rule above wherever a step is not one of the patterns.
 """
 from __future__ import annotations
 
@@ -232,7 +233,11 @@ class QT(torch.Tensor):
 
     @property
     def q16(self):
-        """the int16 payload (None for an int8 one)"""
+        """the int16 payload (None for an int8 one); a deferred GEMM with a 16-bit QuantAct (Requant16) is launched the first time
+        anybody asks for it"""
+        if self._q8 is None and self._q16 is None and isinstance(self.node, Requant16):
+            self._q16 = self.apply_views(self.node.force())
+            self.node, self.views = None, ()
         self._run_rops()
         return self._q16
 
@@ -306,6 +311,8 @@ class QT(torch.Tensor):
                 return _f(t, *_r, **_k)
             fn.view_name = name
 
+            if self._q8 is None and self._q16 is None and isinstance(self.node, Requant16):
+                self.q16      # a shape operation on a deferred 16-bit GEMM: launched now, the operation recorded on its payload
             payload = self._q8 if self._q8 is not None else self._q16
             if payload is not None:
                 sig = _sig(name, rest, kwargs)
@@ -766,6 +773,11 @@ def resolve(qact, x, pre_sf, identity, identity_sf, s_out, s_out_qs):
                 base = node.inputs[0]
                 if isinstance(base, QT) and not x.views:
                     return QT.wrap(x.shape, device, node=Scores(x, pre_sf, s_out, s_out_qs, qact))
+                if isinstance(base, QT) and isinstance(base.node, Probs) and base.node.mod.output_bit == 16:
+                    # 16-bit probabilities without a fused kernel (I-BERT's softmax outside 193 .. 207 tokens, multipliers beyond
+                    # the long-row kernels' bounds): the attention core runs literally, its float result re-enters the integer
+                    # stream here, so the rest of the forward is still carried
+                    return resolve_float(qact, x.to_float(), pre_sf, s_out, s_out_qs)
     elif isinstance(node, Scaled) and identity is None and not x.views:
         return QT.wrap(x.shape, device, node=Scores(x, pre_sf, s_out, s_out_qs, qact))
     if out is None:
@@ -795,12 +807,43 @@ def resolve_float(qact, x, pre_sf, s_out, s_out_qs):
     return QT.wrap(q.shape, device, q8=q.to(torch.int8), scale=s_out_qs, fl=act_layout(torch.empty_like(x, device="meta")))
 
 
+def gemm_requant_i16(lin, a8, s_in, s_out, device):
+    """a8 [M, K] int8 contiguous -> int16 [M, N]: GEMM + per-channel requantisation to the 16-bit scale s_out in one kernel; None
+    outside the kernel's contract"""
+    c = linear_consts(lin, s_in, device)
+    me = _gemm_me(lin, s_in, s_out, device, need_e31=False)
+    N, K = c["N"], c["K"]
+    if N % 8:
+        return None
+    a8 = _operand(a8, c)
+    M = a8.shape[0]
+    o = torch.empty(M, N, dtype=torch.int16, device=device)
+    _lib.call("ivit_gemm_i8_requant_i16", _lib.ptr(a8), K, _lib.ptr(c["W"]), K, _lib.ptr(c["b"]), _lib.ptr(me[0]), _lib.ptr(me[1]),
+              _lib.ptr(o), N, M, N, K, _st())
+    return o
+
+
+def _frags32(lin, s_in, device):
+    """the 32x32x32 fragment copy of a linear's weight: the order the 16-bit-stream epilogue of
+    ivit_gemm_i8_requant_i16_residual_i16_ex exists for (engine.py does the same for attn.proj / mlp.fc2), in 256-channel tiles
+    where they fit (engine_common.frag_copy); None otherwise.  Built the first time a 16-bit QuantAct behind the linear asks"""
+    c = linear_consts(lin, s_in, device)
+    if "Wf32" not in c:
+        c["Wf32"] = frag_copy(c["W"], _st(), order16=False, narrow=False) if c["K"] == c["Kin"] else (None, None)
+    return c["Wf32"]
+
+
 def resolve16(qact, x, pre_sf, identity, identity_sf, s_out, s_out_qs):
-    """The frozen 16-bit QuantAct on a QT, in the patterns of the Swin forward (swin_quant.py): one launch -> int16 QT.
-      int8 payload                                  -> ivit_requant_i8_i16               (the model's qact1, :546)
-      pending linear                                -> ivit_gemm_i8_requant_i16          (attn.proj -> attn.qact4, :166)
+    """The frozen 16-bit QuantAct on a QT, in the patterns of the Swin forward (swin_quant.py) and of ViT's 16-bit configurations
+    (vit_quant.py:180-187): one launch -> int16 QT.
+      int8 payload                                  -> ivit_requant_i8_i16               (Swin's qact1, :546)
+      pending linear / patch convolution            -> ivit_gemm_i8_requant_i16          (attn.proj -> attn.qact4, :166; ViT's
+                                                       patch_embed.qact, attn.qact3, mlp.qact2), from 2048 rows with the fragment
+                                                       weight copy deferred (Requant16) for the residual QuantAct behind it
+      cat(cls, int16 patches) + position identity   -> ivit_embed_assemble_i16           (ViT's qact1, vit_quant.py:293-297)
       int16 / int8 payload + int16 / int8 identity  -> ivit_residual_requant_i16         (the residual qact2, :291)
       deferred fc2 + mlp.qact2 (Requant) + identity -> ivit_gemm_i8_requant_residual_i16_ex   (the residual qact4, :297-299)
+      deferred Requant16 + int16 identity           -> ivit_gemm_i8_requant_i16_residual_i16_ex   (ViT's residual qact2 / qact4)
     None: not one of these (ordinary path)."""
     device = x.device
     s_in = host_of(pre_sf)
@@ -809,7 +852,11 @@ def resolve16(qact, x, pre_sf, identity, identity_sf, s_out, s_out_qs):
     fl = act_layout(x.fl, identity.fl if isinstance(identity, QT) else None)
     node = x.node
     out = None
-    if identity is not None:
+    if isinstance(node, Cat) and x._q8 is None and x._q16 is None:
+        if identity is None or x.views:
+            return None
+        out = _resolve_embed16(qact, node, s_in, identity, host_of(identity_sf), s_out, device)
+    elif identity is not None:
         s_id = host_of(identity_sf)
         if (not isinstance(identity, QT) or s_id is None or s_id.size != 1 or s_in.size != 1
                 or tuple(identity.shape) != tuple(x.shape)):
@@ -825,6 +872,8 @@ def resolve16(qact, x, pre_sf, identity, identity_sf, s_out, s_out_qs):
         (m1, e1), (m2, e2) = dyadic1(s_in, s_out), dyadic1(s_id, s_out)
         if isinstance(node, Requant) and x._q8 is None and not x.views and node.out is None:
             out = node.with_residual16(i16, s_in, (m1, e1, m2, e2), device)
+        elif isinstance(node, Requant16) and x._q16 is None and not x.views and node.out is None:
+            out = node.with_residual(i16, s_in, (m1, e1, m2, e2), device)
         if out is None:
             a = x.q
             if a is None or C % 4:
@@ -840,26 +889,103 @@ def resolve16(qact, x, pre_sf, identity, identity_sf, s_out, s_out_qs):
         m, e = dyadic1(s_in, s_out)
         out = torch.empty(a.shape, dtype=torch.int16, device=device)
         _lib.call("ivit_requant_i8_i16", _lib.ptr(a), m, e, _lib.ptr(out), a.numel(), _st())
-    elif isinstance(node, ModNode) and node.kind == "linear" and s_in is host_of(node.out_scale):
+    elif isinstance(node, ModNode) and node.kind in ("linear", "conv") and s_in is host_of(node.out_scale):
         s_a = host_of(node.scales[0])
-        a8 = q8_contig(node.inputs[0])
-        if s_a is None or s_a.size != 1 or a8 is None:
+        if s_a is None or s_a.size != 1:
             return None
-        c = linear_consts(node.mod, s_a, device)
-        me = _gemm_me(node.mod, s_a, s_out, device, need_e31=False)
-        N, K = c["N"], c["K"]
-        if N % 8:
+        if node.kind == "conv":
+            a8 = _patchify_i8(node.mod, node.inputs[0])
+        else:
+            a8 = q8_contig(node.inputs[0])
+            a8 = None if a8 is None else a8.reshape(-1, a8.shape[-1])
+        if a8 is None:
             return None
-        a8 = _operand(a8.reshape(-1, a8.shape[-1]), c)
-        M = a8.shape[0]
-        o = torch.empty(M, N, dtype=torch.int16, device=device)
-        _lib.call("ivit_gemm_i8_requant_i16", _lib.ptr(a8), K, _lib.ptr(c["W"]), K, _lib.ptr(c["b"]), _lib.ptr(me[0]), _lib.ptr(me[1]),
-                  _lib.ptr(o), N, M, N, K, _st())
-        out = x.apply_views(o.view(*node.shape))
+        if node.kind == "linear" and not x.views and a8.shape[0] >= 2048 and _frags32(node.mod, s_a, device)[0] is not None:
+            # not launched yet: if the next QuantAct adds the 16-bit residual (Block.qact2 / qact4 with attention_out_bw = mlp_out_bw =
+            # norm2_in_bw = att_block_out_bw = 16, vit_quant.py:147,153) the GEMM, this requantisation and that one are ONE kernel;
+            # any other consumer launches the GEMM as it is
+            rq = Requant16(node.mod, a8, s_a, s_out, node.shape, s_out_qs)
+            if rq.ok:
+                return QT.wrap(x.shape, device, scale=s_out_qs, node=rq, fl=fl)
+        o = gemm_requant_i16(node.mod, a8, s_a, s_out, device)
+        if o is None:
+            return None
+        sh = node.shape
+        out = x.apply_views(o.view(*sh) if node.kind == "linear" else o.view(sh[0], sh[2], sh[3], sh[1]).permute(0, 3, 1, 2))
     if out is None:
         return None
     STATS["fused"] += 1
     return QT.wrap(out.shape, device, q16=out, scale=s_out_qs, fl=fl if tuple(fl.shape) == tuple(out.shape) else None)
+
+
+def _resolve_embed16(qact, node, s_in, identity, s_id, s_out, device):
+    """qact1(cat(cls_token, patches), s, pos, s_pos) at 16 bits (vit_quant.py:293-297, block_input_bw = 16) on the int16 patch
+    embedding: ivit_embed_assemble_i16, as engine.IntViTEngine launches it.  Its constants -- the position term
+    RNE(k_pos * m2 / 2^e2) per (token, channel) and the finished class row -- are built once per (position payload, class token,
+    scales) from one read-back of each at the warm-up forward.  None: anything but that pattern"""
+    if (len(node.parts) != 2 or node.dim != 1 or s_in.size != 1 or s_id is None or s_id.size != 1 or not isinstance(identity, QT)
+            or identity.q is None or identity.origin is None):
+        return None
+    cls, pe = node.parts
+    if isinstance(cls, QT) or not isinstance(pe, QT) or pe.q16 is None or pe.dim() != 3 or cls.dtype != torch.float32:
+        return None
+    B, NP, C = pe.shape
+    T = NP + 1
+    if (tuple(cls.shape) != (B, 1, C) or (B > 1 and cls.stride(0) != 0) or tuple(identity.shape) != (1, T, C) or C % 8
+            or B * T >= 2 ** 31 // C):
+        return None
+
+    def build():
+        kpos = identity.q.reshape(T, C).cpu().numpy().astype(np.int64)
+        m1, e1 = dyadic(s_in, s_out)
+        m2, e2 = dyadic(s_id, s_out)
+        pos_add = np.rint(kpos.astype(np.float64) * np.float64(m2[0]) / np.exp2(np.float64(e2[0])))      # quant_utils.py:229-230
+        z_cls = np.rint((cls.detach()[0, 0].cpu().numpy().astype(f32) / f32(s_in[0])).astype(f32))     # :220 on the raw class row
+        row = np.rint(z_cls.astype(np.float64) * np.float64(m1[0]) / np.exp2(np.float64(e1[0]))) + pos_add[0]
+        if np.abs(pos_add).max() >= 2 ** 31:
+            return None
+        return (_dev(pos_add.astype(np.int32), device), _dev(np.clip(row, -32768, 32767).astype(np.int16), device), int(m1[0]), int(e1[0]))
+    k = _cache(qact, ("embed16", identity.origin, _sig("cls", (cls,), {}), _key(s_in, s_id, np.asarray(s_out)), str(device)), build)
+    if k is None:
+        return None
+    pe16 = q16_contig(pe)
+    out = torch.empty(B, T, C, dtype=torch.int16, device=device)
+    _lib.call("ivit_embed_assemble_i16", _lib.ptr(pe16), _lib.ptr(k[0]), _lib.ptr(k[1]), k[2], k[3], _lib.ptr(out), B, T, C, _st())
+    return out
+
+
+class Requant16(Node):
+    """a linear + its 16-bit QuantAct, not launched yet (see resolve16)"""
+
+    def __init__(self, lin, a8, s_a, s_out, shape, s_out_qs):
+        self.lin, self.a8, self.s_a, self.s_out, self.shape, self.s_out_qs = lin, a8, s_a, s_out, shape, s_out_qs
+        c = linear_consts(lin, s_a, a8.device)
+        self.ok = c["N"] % 8 == 0 and c["K"] == c["Kin"]
+        self.out = None
+
+    def force(self):
+        if self.out is None:
+            STATS["fused"] += 1
+            self.out = gemm_requant_i16(self.lin, self.a8, self.s_a, self.s_out, self.a8.device).view(*self.shape)
+        return self.out
+
+    def to_float(self):
+        return self.force().to(torch.float32) * self.s_out_qs.as_subclass(torch.Tensor).reshape(-1)[0]
+
+    def with_residual(self, i16, s_in, mes, device):
+        """out = clamp16(RNE(clamp16(RNE(acc * M)) * m1 / 2^e1) + RNE(identity * m2 / 2^e2)): ivit_gemm_i8_requant_i16_residual_i16_ex
+        with the fragment weight copy; int16 out, or None"""
+        c = linear_consts(self.lin, self.s_a, device)
+        Wf, bit = _frags32(self.lin, self.s_a, device)
+        N, K = c["N"], c["K"]
+        if s_in[0] != f32(self.s_out) or tuple(i16.shape) != tuple(self.shape) or Wf is None:
+            return None
+        me = _gemm_me(self.lin, self.s_a, self.s_out, device, need_e31=False)
+        M = self.a8.shape[0]
+        out = torch.empty(M, N, dtype=torch.int16, device=device)
+        _lib.call("ivit_gemm_i8_requant_i16_residual_i16_ex", _lib.ptr(self.a8), K, _lib.ptr(Wf), K, _lib.ptr(c["b"]), _lib.ptr(me[0]),
+                  _lib.ptr(me[1]), _lib.ptr(i16), N, mes[0], mes[1], mes[2], mes[3], _lib.ptr(out), N, M, N, K, bit, _st())
+        return out.view(*self.shape)
 
 
 class Requant(Node):
@@ -1000,13 +1126,17 @@ def _resolve_ln(node, s_out, device):
 
 
 def _resolve_ibert_ln(node, s_out, device):
-    """IBERTIntLayerNorm (ibert_modules.py:126-153) + the QuantAct behind it on int8: ivit_ibert_layernorm_i8 (csrc/ibert.hip), which
-    works on fl(q * s_in) literally -- any input scale"""
-    ln, x8 = node.mod, q8_contig(node.inputs[0])
+    """IBERTIntLayerNorm (ibert_modules.py:126-153) + the QuantAct behind it on int8 or on the int16 stream: ivit_ibert_layernorm_i8 /
+    ivit_ibert_layernorm_i16_i8_ex (csrc/ibert.hip), which work on fl(q * s_in) literally -- any input scale"""
+    ln, x = node.mod, node.inputs[0]
+    xq = q8_contig(x)
+    bits = 8
+    if xq is None:
+        xq, bits = q16_contig(x), 16
     s_in = host_of(node.scales[0])
-    if x8 is None or s_in is None or s_in.size != 1 or ln.overflow_handling:
+    if xq is None or s_in is None or s_in.size != 1 or ln.overflow_handling:
         return None
-    return _layernorm(ln, x8, s_in, s_out, 8, device, ibert=True)
+    return _layernorm(ln, xq, s_in, s_out, bits, device, ibert=True)
 
 
 def _resolve_gelu(node, s_out, device):
@@ -1051,12 +1181,17 @@ def _resolve_attention(node, s_pv, s_out, device):
     if s_S.size != 1 or s_pv.size != 1:
         return None
     sm = P.node.mod
+    if sm.output_bit not in (8, 16):
+        return None
+    # softmax_bw = 16 (vit_quant.py:184): the "wide" entries, whose probabilities reach 2^15 at scale 2^-15 (s_pv is 2^-15 * s_v)
+    softmax_bits = 16 if sm.output_bit == 16 else None
     family, act, key = "ivit", None, ("attn",)
     if type(sm).__name__ == "IBERTIntSoftmax":
         # IBERTIntSoftmax (ibert_modules.py:237-319): exp_int after its internal 16-bit QuantAct as a (row max, q) table, row sum in
         # torch's float32 order inside the kernel (attention.hip MODE 3 / 4); that kernel holds 193 .. 207 tokens, the long-row
         # form (attention_long_kernel MODE 2) 208 .. 1025
-        if not (192 < T <= 1025) or sm.output_bit != 8 or sm.act.running_stat:
+        # with output_bit = 16 only the short kernel has a form (ivit_attention_fused_i8_ibert_wide): other token counts stay literal
+        if not (192 < T <= 1025) or sm.output_bit not in (8, 16) or (sm.output_bit == 16 and T > 207) or sm.act.running_stat:
             return None
         family, act = "ibert", sm.act
         key = ("ibattn", id(act.x_min), act.x_min._version, id(act.x_max), act.x_max._version)
@@ -1071,7 +1206,7 @@ def _resolve_attention(node, s_pv, s_out, device):
     if T > 207 and not _long_multipliers_ok(a):
         return None
     out = torch.empty(B * T, H * hd, dtype=torch.int8, device=device)
-    attention(a, family, hm, out, B, H, T, hd, _st())
+    attention(a, family, hm, out, B, H, T, hd, _st(), softmax_bits=softmax_bits)
     return out.view(B, T, H, hd).permute(0, 2, 1, 3)
 
 
@@ -1200,6 +1335,8 @@ def _resolve_cat(qact, node, s_in, identity, identity_sf, s_out, device):
     parts = []
     for p in node.parts:
         if isinstance(p, QT):
+            if p.q8 is None:          # an int16 patch embedding in front of an 8-bit block input: not a pattern
+                return None
             parts.append(p.q8.to(torch.int32))
         else:
             pf = p.detach()

@@ -331,9 +331,23 @@ class QuantAct(nn.Module):
     def _fast(self, x, pre_sf, identity, identity_sf):
         """frozen 8-bit QuantAct of an int8-carrying forward (lazy.py): int8 out, one fused launch, nothing read back"""
         if pre_sf is None:
-            if isinstance(x, lazy.QT) or identity is not None or not x.is_cuda or self.activation_bit != 8:
+            if isinstance(x, lazy.QT) or identity is not None or not x.is_cuda:
                 return None
             s_out, qs, plain = self._frozen_scale(x.device)
+            if self.activation_bit == 16:
+                # a 16-bit QuantAct on a parameter (qact_pos with pos_encoding_bw = 16, vit_quant.py:181): int16 payload, quantised
+                # once per parameter version and range
+                if not isinstance(x, nn.Parameter):
+                    return None
+
+                def build():
+                    xin = x.detach().contiguous().float()
+                    q32 = torch.empty(xin.shape, dtype=torch.int32, device=x.device)
+                    _lib.call("ivit_quantize_input_f32_i32", _lib.ptr(xin), _lib.ptr(q32), xin.numel(), float(f32(1.0) / s_out), 16, _st())
+                    return q32.to(torch.int16)
+                q16 = lazy._cache(self, ("param16", id(x), x._version, float(s_out), str(x.device)), build)
+                self.act_scaling_factor = plain
+                return lazy.QT.wrap(q16.shape, x.device, q16=q16, scale=qs, origin=(id(x), x._version, float(s_out))), qs
             xin = x.detach().contiguous().float()
             q8 = torch.empty(xin.shape, dtype=torch.int8, device=x.device)
             _lib.call("ivit_quantize_input_f32_i8", _lib.ptr(xin), _lib.ptr(q8), xin.numel(), float(f32(1.0) / s_out), _st())

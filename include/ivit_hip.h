@@ -251,6 +251,21 @@ int ivit_attention_fused_i8_long(const int8_t* qkv, int8_t* out, int batch, int 
                                  int32_t e_s, float s_attn, uint32_t m_o, int32_t e_o, const uint32_t* exp2d,
                                  const uint32_t* band, int band_w, int out_blocks, ivit_stream_t stream);
 
+/* Long rows with the softmax output width as a parameter: ivit_attention_fused_i8_long's arguments, layouts, tables and
+ * preconditions (208 <= tokens <= 1025, head_dim 64, x0 in [-4096, -1], the same multiplier bounds, all three Shiftmax regimes,
+ * both output layouts) plus softmax_bits = 8 or 16, as ivit_attention_fused_i8_wide has it for up to 208 keys.
+ *   16: p = floor(fl32(e * factor) / 2^16) <= 2^15 at scale 2^-15 (ivit_modules.py:175-176) on the long kernel's row organisation
+ *       (packed scores, exact 64-bit row sum, the clamp at 2^31), carried into P.V as three 7-bit planes; (m_o, e_o) is the
+ *       requantiser of 2^-15 * s_v, applied to O = sum p * v (|O| < 2^29 for 1025 keys) in the reference's two steps: the
+ *       float64 product rounded at 53 bits, then the rounding to an integer (quant_utils.py:229-230).
+ *   8:  exactly ivit_attention_fused_i8_long.
+ * Errors: any other softmax_bits is IVIT_ERR_INVALID ("softmax_bits must be 8 or 16") ahead of everything else; then as
+ * ivit_attention_fused_i8_long: IVIT_ERR_UNSUPPORTED ("unsupported geometry") outside the token range or for another
+ * head_dim, IVIT_ERR_INVALID ("NULL operand", ...) otherwise. */
+int ivit_attention_fused_i8_wide_long(const int8_t* qkv, int8_t* out, int batch, int heads, int tokens, int head_dim,
+                                      uint32_t m_s, int32_t e_s, float s_attn, uint32_t m_o, int32_t e_o, const uint32_t* exp2d,
+                                      const uint32_t* band, int band_w, int softmax_bits, int out_blocks, ivit_stream_t stream);
+
 /* One query per (image, head): the attention of a block whose output is read for one token only (the class token of the last
  * block, vit_quant.py:302-304).  The arithmetic of ivit_attention_fused_i8_compat_band for that query, bit for bit.
  *   k, v  [batch][heads][tokens][64] int8: planes 1 and 2 of the head-major qkv buffer

@@ -13,7 +13,12 @@ per score (T is recovered from the launch's LDS size, B from the cases below; th
 times the I-BERT family instead: ivit_attention_fused_i8_ibert_long (table and band form) against ivit_attention_fused_i8_long at 577
 and 1025 tokens, batch 64, and the forward of a depth-2 I-BERT model of DeiT-B's geometry (C = 768, 12 heads) at 384 / 16, batch 64,
 through the module path (the fused engine does not take I-BERT models of more than 207 tokens).  Every figure is the median of
-seven event-timed repeats after warm-up, with the smallest and largest repeat."""
+seven event-timed repeats after warm-up, with the smallest and largest repeat.
+
+    python scripts/time_long_attention.py --softmax-bits 16
+
+times ivit_attention_fused_i8_wide_long with 16-bit probabilities beside the 8-bit long-row kernel in the same run, on the same
+operands: 577 and 785 tokens, batch 64, 12 heads, power-of-two scales and a natural scale (band table); the same seven repeats."""
 import os
 import sys
 
@@ -95,6 +100,28 @@ def ibert_attention(B, T):
     return res
 
 
+def wide_attention(B, T, bits):
+    """us per launch (median, min, max) of the 8-bit long-row kernel and of ivit_attention_fused_i8_wide_long with `bits`-wide
+    probabilities on the same operands, at power-of-two scales and at a natural scale (band table); the output requantiser
+    follows the width of the probabilities (2^-(bits-1) times the scale of V)"""
+    from ivit_amd.prepare import shiftexp2d, shiftexp_band
+    qkv = torch.from_numpy(np.clip(np.rint(rng.normal(0, 40, size=(3, B, H, T, hd))), -128, 127).astype(np.int8)).to(DEV)
+    out = torch.empty(B * T, H * hd, dtype=torch.int8, device=DEV)
+    ms, es = dyadic(np.float32(2.0 ** -11), np.float32(2.0 ** -2))
+    mo8, eo8 = dyadic(np.float32(2.0 ** -11), np.float32(2.0 ** -3))
+    mow, eow = dyadic(np.float32(2.0 ** -(bits + 3)), np.float32(2.0 ** -3))
+    nb, nbw = shiftexp_band(shiftexp2d(np.float32(0.0437)))
+    nband = torch.from_numpy(nb.view(np.int32)).to(DEV)
+    a = (_lib.ptr(qkv), _lib.ptr(out), B, H, T, hd, int(ms[0]), int(es[0]))
+    res = {}
+    for regime, s_at, band, bw in (("pow2", 0.25, None, 0), (f"band {nbw}", 0.0437, nband, nbw)):
+        res[f"8 bit {regime}"] = repeats(lambda: _lib.call("ivit_attention_fused_i8_long", *a, s_at, int(mo8[0]), int(eo8[0]), None,
+                                                           _lib.ptr(band), bw, 0, st()), 10)
+        res[f"{bits} bit {regime}"] = repeats(lambda: _lib.call("ivit_attention_fused_i8_wide_long", *a, s_at, int(mow[0]), int(eow[0]),
+                                                                None, _lib.ptr(band), bw, bits, 0, st()), 10)
+    return res
+
+
 def ibert_model():
     """forward of a frozen depth-2 I-BERT model, C = 768, 12 heads, 384 / 16, batch 64, as the reference calls it (module by module)"""
     from ivit_amd.quantization_utils import lazy
@@ -153,6 +180,17 @@ if "--family" in argv:
     family = argv[i + 1]
     del argv[i:i + 2]
     assert family in ("ivit", "ibert"), family
+if "--softmax-bits" in argv:
+    i = argv.index("--softmax-bits")
+    sm_bits = int(argv[i + 1])
+    assert sm_bits in (8, 16), sm_bits
+    for B, T in [(64, 577), (64, 785)]:
+        res = wide_attention(B, T, sm_bits)
+        for k, (med, lo, hi) in res.items():
+            base = res["8 bit " + k.split(" bit ")[1]][0]
+            print(f"attention B={B} T={T:4d} {k:16s} {med:8.1f} us (min {lo:.1f}, max {hi:.1f})  {med * 1e6 / (B * H * T * T):.3f} ps/score  "
+                  f"{med / base:.2f}x the 8-bit kernel")
+    sys.exit(0)
 which = argv or ["kernels", "model"]
 if family == "ibert":
     if "kernels" in which:
