@@ -39,6 +39,8 @@ constexpr int VT_BYTES = HD * VT_ROW;  // 16384
 constexpr int LUT_OFF = K_BYTES + VT_BYTES;
 constexpr int SMEM_BYTES = LUT_OFF + 2 * 256 * 4;   // exponent table as u32 (exact row sum) and as float32 (the product of :175)
 
+#include "attn_parts.h"
+
 struct AttnArgs {
     const int8_t* qkv;
     int8_t* out;
@@ -151,14 +153,8 @@ __global__ __launch_bounds__(NT, OCC) void attention_kernel(AttnArgs a)
         for (int w = 0; w < 4; ++w) {
             // rows = keys r (v[r][w] holds d = 16c+4w .. +3 in its bytes) -> columns: dword bb = 4 keys of d = 16c+4w+bb
             const unsigned a0 = (unsigned)v[0][w], a1 = (unsigned)v[1][w], a2 = (unsigned)v[2][w], a3 = (unsigned)v[3][w];
-            const unsigned lo01 = __builtin_amdgcn_perm(a1, a0, 0x05010400u);  // a0.b0 a1.b0 a0.b1 a1.b1
-            const unsigned hi01 = __builtin_amdgcn_perm(a1, a0, 0x07030602u);  // a0.b2 a1.b2 a0.b3 a1.b3
-            const unsigned lo23 = __builtin_amdgcn_perm(a3, a2, 0x05010400u);
-            const unsigned hi23 = __builtin_amdgcn_perm(a3, a2, 0x07030602u);
-            const unsigned t[4] = {__builtin_amdgcn_perm(lo23, lo01, 0x05040100u),   // d+0: a0.b0 a1.b0 a2.b0 a3.b0
-                                   __builtin_amdgcn_perm(lo23, lo01, 0x07060302u),   // d+1
-                                   __builtin_amdgcn_perm(hi23, hi01, 0x05040100u),   // d+2
-                                   __builtin_amdgcn_perm(hi23, hi01, 0x07060302u)};  // d+3
+            unsigned t[4];
+            bytes4x4_transpose(a0, a1, a2, a3, t);
 #pragma unroll
             for (int bb = 0; bb < 4; ++bb) {
                 const int d = 16 * c + 4 * w + bb;
@@ -287,20 +283,7 @@ __global__ __launch_bounds__(NT, OCC) void attention_kernel(AttnArgs a)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) Pp[0][r] += e12[r];
             }
-            // all-gather over the four lanes of a query (lane = 16 g + l15) in VALU instructions: v_permlane32_swap of a value
-            // with itself leaves every lane with the values of rows {0,1} and {2,3} of 16 lanes, v_permlane16_swap of each of
-            // those with itself then separates row 0 / 1 and row 2 / 3: out[g'] = the value lane 16 g' + l15 held
-            typedef unsigned v2u __attribute__((ext_vector_type(2)));
-            auto gather4 = [&](float x, float (&out)[4]) {
-                const unsigned xb = (unsigned)__float_as_int(x);
-                const v2u h = __builtin_amdgcn_permlane32_swap(xb, xb, false, false);       // h.x: rows 0,1,0,1; h.y: rows 2,3,2,3
-                const v2u a01 = __builtin_amdgcn_permlane16_swap(h.x, h.x, false, false);   // .x: row 0 everywhere, .y: row 1
-                const v2u a23 = __builtin_amdgcn_permlane16_swap(h.y, h.y, false, false);   // .x: row 2, .y: row 3
-                out[0] = __int_as_float((int)a01.x);
-                out[1] = __int_as_float((int)a01.y);
-                out[2] = __int_as_float((int)a23.x);
-                out[3] = __int_as_float((int)a23.y);
-            };
+            // the tail and the partials are exchanged among the four lanes of the query (gather4)
             float fin = 0.0f;
             {
                 float t12[4][4];                   // [r][g']
@@ -371,10 +354,7 @@ __global__ __launch_bounds__(NT, OCC) void attention_kernel(AttnArgs a)
         if constexpr (MODE >= 3) {
             factor = floorf(4294967296.0f / __int_as_float((int)esum));        // ibert_modules.py:313
         } else {
-            esum = rows_allsum_u32(esum);
-            float S = (float)esum;                                     // exp_int.sum (:171)
-            S = fminf(S, 2147483648.0f);                               // clamp_max_(2**31-1) in float32 (:173)
-            factor = floorf((1.0f / S) * 2147483648.0f);               // (:174)
+            factor = shiftmax_factor(rows_allsum_u32(esum));
         }
 
         // packed probabilities: dword t of key step ks = bytes r = 0..3 of key tile 4ks + t
@@ -464,8 +444,8 @@ __global__ __launch_bounds__(NT, OCC) void attention_kernel(AttnArgs a)
                         }
                     }
                     if constexpr (PB == 16) {
-                        // p16 = u >> 16 = floor(fl32(e * factor) / 2^16) (Shiftmax :175) resp. / 2^17 (I-BERT :314) with u as above:
-                        // plane c = bits 16..22 (byte 2 & 0x7f), plane b = bits 23..29 (byte 3 of u << 1, & 0x7f), plane a = bits 30, 31
+                        // planes c and b of p16 (attn_parts.h plane_c, plane_b): this kernel keeps its own copy, the helpers reorder
+                        // the schedule of the natural-scale forms
                         if constexpr (MODE < 3) any_u |= p[0] | p[1] | p[2] | p[3];
                         const unsigned c4 = __builtin_amdgcn_perm(p[1], p[0], 0x0c0c0602u) | __builtin_amdgcn_perm(p[3], p[2], 0x06020c0cu);
                         const unsigned b4 = __builtin_amdgcn_perm(p[1] << 1, p[0] << 1, 0x0c0c0703u) |
@@ -473,10 +453,7 @@ __global__ __launch_bounds__(NT, OCC) void attention_kernel(AttnArgs a)
                         w = c4 & 0x7f7f7f7fu;
                         pkb[ks][t] = (int)(b4 & 0x7f7f7f7fu);
                     } else {
-                    // floor(. / 2^24) = the top byte of each product: gather the four top bytes with two byte permutes
-                    const unsigned lo = __builtin_amdgcn_perm(p[1], p[0], 0x0c0c0703u);  // [p0.b3, p1.b3, 0, 0]
-                    const unsigned hi = __builtin_amdgcn_perm(p[3], p[2], 0x07030c0cu);  // [0, 0, p2.b3, p3.b3]
-                    w = lo | hi;
+                        w = top_bytes(p);
                     }
                 }
                 pk[ks][t] = (int)w;
@@ -495,22 +472,22 @@ __global__ __launch_bounds__(NT, OCC) void attention_kernel(AttnArgs a)
                             for (int r = 0; r < 4; ++r) {
                                 const float ev = ef_is_float ? __int_as_float(s[4 * ks + t][r]) : (float)(unsigned)s[4 * ks + t][r];
                                 const unsigned u = (unsigned)(ev * (MODE >= 3 ? factor_h : factor));
-                                w |= (u >> 30) << (8 * r);
+                                w |= plane_a_byte(u, r);
                             }
                         }
                         pkh[ks][t] = (int)w;
                     }
             }
         } else if constexpr (MODE >= 3) {
-            if (any_hi) {      // a byte 0x80 (p = 128) becomes 127 in pk and 1 in pkh
+            if (any_hi) {      // p = 128 = 127 in pk + 1 in pkh (split_p128)
 #pragma unroll
                 for (int ks = 0; ks < NKS; ++ks)
 #pragma unroll
                     for (int t = 0; t < 4; ++t) {
-                        const unsigned w = (unsigned)pk[ks][t];
-                        const unsigned h128 = (w >> 7) & 0x01010101u;          // 1 in every byte that is 0x80
-                        pk[ks][t] = (int)(w - h128);                          // 0x80 -> 0x7f (no borrow: the byte is >= 1)
-                        pkh[ks][t] = (int)h128;
+                        unsigned lo, hi;
+                        split_p128((unsigned)pk[ks][t], lo, hi);
+                        pk[ks][t] = (int)lo;
+                        pkh[ks][t] = (int)hi;
                     }
             }
         }
@@ -542,37 +519,12 @@ __global__ __launch_bounds__(NT, OCC) void attention_kernel(AttnArgs a)
                     if (hi_pass) acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(vf, pkh[ks], acc, 0, 0, 0);
                 }
             }
-            int ob[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                int o;
-                if constexpr (PB == 16) {
-                    // O = sum p16 * v up to 208 * 32768 * 128 < 2^30: the reference's float64 product rounds at 53 bits first
-                    // (quant_utils.py:229-230), so product and rounding are two steps here
-                    const int O = acc[r] + (accb[r] << 7) + (acca[r] << 14);
-                    const double t = (double)O * a.Mo + IVIT_MAGIC;
-                    o = clamp_i32((int)(unsigned)__double_as_longlong(t), -128, 127);
-                } else {
-                    // |O| <= 208*127*128 < 2^22: exact float64 product
-                    o = clamp_i32(requant_exact(acc[r], a.Mo), -128, 127);
-                }
-                ob[r] = o;
-            }
-            // the four low bytes by two byte permutes and an OR (was: and / shift / or per byte)
-            wq[dt] = __builtin_amdgcn_perm((unsigned)ob[1], (unsigned)ob[0], 0x0c0c0400u) | __builtin_amdgcn_perm((unsigned)ob[3], (unsigned)ob[2], 0x04000c0cu);
+            wq[dt] = attn_out_word<PB>(acc, accb, acca, a.Mo);
         }
-        // A query's 64 output bytes sit as 4 x 4 dwords in its four lanes (g = lane >> 4).  A 4 x 4 word transpose across those
-        // lanes -- two v_permlane32_swap, two v_permlane16_swap -- leaves lane g with the 16 CONTIGUOUS bytes d = 16 g .. 16 g + 15:
-        // one 16-byte store per lane instead of four 4-byte ones (a quarter of the store instructions and of the segments the
-        // memory pipeline has to merge).
+        // lane g ends with the 16 contiguous bytes d = 16 g .. 16 g + 15 of its query (attn_out_transpose): one 16-byte store
         {
-            typedef unsigned v2u __attribute__((ext_vector_type(2)));
-            const v2u ab = __builtin_amdgcn_permlane32_swap(wq[0], wq[2], false, false);    // g < 2: (w0[g], w0[g+2]); g >= 2: (w2[g-2], w2[g])
-            const v2u cd = __builtin_amdgcn_permlane32_swap(wq[1], wq[3], false, false);    // g < 2: (w1[g], w1[g+2]); g >= 2: (w3[g-2], w3[g])
-            const v2u ac = __builtin_amdgcn_permlane16_swap(ab.x, cd.x, false, false);      // (w_g[0], w_g[1]) of the lanes 0, 1
-            const v2u bd = __builtin_amdgcn_permlane16_swap(ab.y, cd.y, false, false);      // (w_g[2], w_g[3])
+            const v4i chunk = attn_out_transpose(wq);
             if (qrow < T) {
-                const v4i chunk = {(int)ac.x, (int)ac.y, (int)bd.x, (int)bd.y};
                 if (a.out_blocks)   // column = 64 hh + 16 g: chunk index g, column block hh
                     *reinterpret_cast<v4i*>(a.out + obrow.base + (unsigned)hh * 1024u + (((unsigned)g ^ obrow.rs) << 4)) = chunk;
                 else
@@ -587,17 +539,15 @@ __global__ __launch_bounds__(NT, OCC) void attention_kernel(AttnArgs a)
 // workgroup per head is right (DeiT-B b256: 3072 = 3 rounds of 1024; 4 of 768 before round 3); a launch that fills only part of a round is bound by that
 // walk -- DeiT-S b64 (384 heads) took a whole round's 17 us -- so the tiles are dealt out among 2 or 4 workgroups per head when
 // the model below says the launch gets shorter (each stages K / V^T itself: L2 hits).
-int attention_parts(int batch_heads, int tokens, int slots)
+// The long kernel is the same model with one workgroup per CU (256 slots) and `waves` waves walking the tiles, staging and a query
+// tile both growing with T alike.
+int attention_parts(int batch_heads, int nqt, int waves, int slots)
 {
-    const int nqt = (tokens + 15) >> 4;
-#if IVIT_LAB
-    if ((g_attn_debug >> 8) & 7) return (g_attn_debug >> 8) & 7;      // lab: forced (scripts/attn_parts.py)
-#endif
     int best = 1;
     double best_t = 0.0;
     for (int p = 1; p <= 4; p *= 2) {
-        if (p > 1 && 4 * (p / 2) >= nqt) break;     // no wave would lose a tile
-        const int rounds = (batch_heads * p + slots - 1) / slots, tiles = (nqt + 4 * p - 1) / (4 * p);
+        if (p > 1 && waves * (p / 2) >= nqt) break;     // no wave would lose a tile
+        const int rounds = (batch_heads * p + slots - 1) / slots, tiles = (nqt + waves * p - 1) / (waves * p);
         const double t = rounds * (3.0 + 3.45 * tiles);
         if (p == 1 || t < 0.95 * best_t) { best = p; best_t = t; }
     }
@@ -709,10 +659,8 @@ __global__ __launch_bounds__(NTH, 1) void attention_long_kernel(LongArgs a)
 #pragma unroll
         for (int w = 0; w < 4; ++w) {
             const unsigned a0 = (unsigned)vst[i][0][w], a1 = (unsigned)vst[i][1][w], a2 = (unsigned)vst[i][2][w], a3 = (unsigned)vst[i][3][w];
-            const unsigned lo01 = __builtin_amdgcn_perm(a1, a0, 0x05010400u), hi01 = __builtin_amdgcn_perm(a1, a0, 0x07030602u);
-            const unsigned lo23 = __builtin_amdgcn_perm(a3, a2, 0x05010400u), hi23 = __builtin_amdgcn_perm(a3, a2, 0x07030602u);
-            const unsigned t[4] = {__builtin_amdgcn_perm(lo23, lo01, 0x05040100u), __builtin_amdgcn_perm(lo23, lo01, 0x07060302u),
-                                   __builtin_amdgcn_perm(hi23, hi01, 0x05040100u), __builtin_amdgcn_perm(hi23, hi01, 0x07060302u)};
+            unsigned t[4];
+            bytes4x4_transpose(a0, a1, a2, a3, t);
 #pragma unroll
             for (int bb = 0; bb < 4; ++bb) {
                 const int d = 16 * c + 4 * w + bb;
@@ -819,16 +767,6 @@ __global__ __launch_bounds__(NTH, 1) void attention_long_kernel(LongArgs a)
                     else t1[r] = e;
                 }
             }
-            // all-gather over the four lanes of a query (attention_kernel MODE 3): out[g'] = the value lane 16 g' + l15 held
-            typedef unsigned v2u __attribute__((ext_vector_type(2)));
-            struct F4 { float g0, g1, g2, g3; };
-            auto gather4 = [&](float x) -> F4 {
-                const unsigned xb = (unsigned)__float_as_int(x);
-                const v2u h = __builtin_amdgcn_permlane32_swap(xb, xb, false, false);       // h.x: rows 0,1,0,1; h.y: rows 2,3,2,3
-                const v2u a01 = __builtin_amdgcn_permlane16_swap(h.x, h.x, false, false);   // .x: row 0 everywhere, .y: row 1
-                const v2u a23 = __builtin_amdgcn_permlane16_swap(h.y, h.y, false, false);   // .x: row 2, .y: row 3
-                return F4{__int_as_float((int)a01.x), __int_as_float((int)a01.y), __int_as_float((int)a23.x), __int_as_float((int)a23.y)};
-            };
             // partials 0 .. 7 (hi = 0 of the lanes g = 0, 1) take the vectors behind the interleaved part: vector 0 = this lane's own
             // keys of tile I2, vector 1 = those of lane g + 2, vector 2 = its own of tile I2 + 1; then
             // v_l = ((P_l + P_{l+8}) + P_{l+16}) + P_{l+24}, l = 4 g + r: P_{l+8}, P_{l+24} are lane g + 2's.  v_permlane32_swap of a
@@ -856,9 +794,10 @@ __global__ __launch_bounds__(NTH, 1) void attention_long_kernel(LongArgs a)
                 float lo[4], hi[4];                    // the tail's half tile: lanes g' = 2 (nx & 1) and + 1
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const F4 G = gather4(second ? t1[r] : t0[r]);
-                    lo[r] = odd ? G.g2 : G.g0;
-                    hi[r] = odd ? G.g3 : G.g1;
+                    float G[4];
+                    gather4(second ? t1[r] : t0[r], G);
+                    lo[r] = odd ? G[2] : G[0];
+                    hi[r] = odd ? G[3] : G[1];
                 }
 #pragma unroll
                 for (int r = 0; r < 4; ++r) fin += lo[r];
@@ -867,9 +806,10 @@ __global__ __launch_bounds__(NTH, 1) void attention_long_kernel(LongArgs a)
                 float v0[4], v1[4];
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const F4 G = gather4(vl[r]);
-                    v0[r] = G.g0;
-                    v1[r] = G.g1;
+                    float G[4];
+                    gather4(vl[r], G);
+                    v0[r] = G[0];
+                    v1[r] = G[1];
                 }
 #pragma unroll
                 for (int r = 0; r < 4; ++r) fin += v0[r];
@@ -898,10 +838,7 @@ __global__ __launch_bounds__(NTH, 1) void attention_long_kernel(LongArgs a)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) sum16 += r < vr ? expo((dk >> (8 * r)) & 255u) : 0u;
             }
-            esum = rows_allsum_u64(esum + sum16);
-            float S = (float)esum;                                         // :171
-            S = fminf(S, 2147483648.0f);                                   // :173
-            factor = floorf((1.0f / S) * 2147483648.0f);                   // :174
+            factor = shiftmax_factor(rows_allsum_u64(esum + sum16));
         }
 
         // ---- pass 3: p = floor(fl32(e * factor) / 2^24) (:175) as bytes, P . V per key step of 64
@@ -916,10 +853,9 @@ __global__ __launch_bounds__(NTH, 1) void attention_long_kernel(LongArgs a)
                 const float ev = MODE == 0 ? lutf[idx] : MODE == 2 ? __int_as_float((int)expo(idx)) : (float)expo(idx);
                 p[r] = r < nreal ? (unsigned)(ev * factor) : 0u;          // float32 product (:175), < 2^31
             }
-            return __builtin_amdgcn_perm(p[1], p[0], 0x0c0c0703u) | __builtin_amdgcn_perm(p[3], p[2], 0x07030c0cu);
+            return top_bytes(p);
         };
-        // PB 16: u = trunc(fl32(e * factor)) <= 2^31, p16 = u >> 16 (:175 with output_bit 16): plane c = bits 16 .. 22 of u, plane b
-        // = bits 23 .. 29, plane a = bits 30, 31 (attention_kernel PB 16).  -> the OR of the four u (whether plane a is needed)
+        // PB 16: the planes c and b of p16 = u >> 16 (plane_c, plane_b).  -> the OR of the four u (whether plane a is needed)
         auto prob_planes = [&](unsigned packed, int nreal, unsigned& wc, unsigned& wb) -> unsigned {
             const unsigned dk = rep - packed;
             unsigned p[4];
@@ -929,9 +865,8 @@ __global__ __launch_bounds__(NTH, 1) void attention_long_kernel(LongArgs a)
                 const float ev = MODE == 0 ? lutf[idx] : (float)expo(idx);
                 p[r] = r < nreal ? (unsigned)(ev * factor) : 0u;
             }
-            wc = (__builtin_amdgcn_perm(p[1], p[0], 0x0c0c0602u) | __builtin_amdgcn_perm(p[3], p[2], 0x06020c0cu)) & 0x7f7f7f7fu;
-            wb = (__builtin_amdgcn_perm(p[1] << 1, p[0] << 1, 0x0c0c0703u) | __builtin_amdgcn_perm(p[3] << 1, p[2] << 1, 0x07030c0cu)) &
-                 0x7f7f7f7fu;
+            wc = plane_c(p);
+            wb = plane_b(p);
             return p[0] | p[1] | p[2] | p[3];
         };
         auto prob_plane_a = [&](unsigned packed, int nreal) -> unsigned {      // from the products again: rare
@@ -942,7 +877,7 @@ __global__ __launch_bounds__(NTH, 1) void attention_long_kernel(LongArgs a)
                 const unsigned idx = (dk >> (8 * r)) & 255u;
                 const float ev = MODE == 0 ? lutf[idx] : (float)expo(idx);
                 const unsigned u = r < nreal ? (unsigned)(ev * factor) : 0u;
-                w |= (u >> 30) << (8 * r);
+                w |= plane_a_byte(u, r);
             }
             return w;
         };
@@ -1013,12 +948,13 @@ __global__ __launch_bounds__(NTH, 1) void attention_long_kernel(LongArgs a)
             }
             v4i ph = {0, 0, 0, 0};
             bool hi_pass = false;
-            if constexpr (MODE == 2) {             // a byte 0x80 (p = 128) becomes 127 in pk and 1 in ph
+            if constexpr (MODE == 2) {             // p = 128: split_p128
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
-                    const unsigned h128 = ((unsigned)pk[t] >> 7) & 0x01010101u;
-                    pk[t] = (int)((unsigned)pk[t] - h128);     // no borrow: the byte is >= 1
-                    ph[t] = (int)h128;
+                    unsigned lo, hi;
+                    split_p128((unsigned)pk[t], lo, hi);
+                    pk[t] = (int)lo;
+                    ph[t] = (int)hi;
                 }
                 hi_pass = __builtin_amdgcn_ballot_w64((ph[0] | ph[1] | ph[2] | ph[3]) != 0) != 0;    // wave-uniform, rare
             }
@@ -1040,26 +976,13 @@ __global__ __launch_bounds__(NTH, 1) void attention_long_kernel(LongArgs a)
             int ob[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                if constexpr (PB == 16) {
-                    // |O| < 2^29 (above): the reference's float64 product rounds at 53 bits first (quant_utils.py:229-230), so
-                    // product and rounding are two steps, as in attention_kernel
-                    const int O = o[dt][r] + (o_b[dt][r] << 7) + (o_a[dt][r] << 14);
-                    const double t = (double)O * a.Mo + IVIT_MAGIC;
-                    ob[r] = clamp_i32((int)(unsigned)__double_as_longlong(t), -128, 127);
-                } else {
-                    ob[r] = clamp_i32(requant_exact(o[dt][r], a.Mo), -128, 127);
-                }
+                ob[r] = attn_out_requant<PB>(o[dt][r], PB == 16 ? o_b[PB == 16 ? dt : 0][r] : 0, PB == 16 ? o_a[PB == 16 ? dt : 0][r] : 0, a.Mo);
             }
-            wq[dt] = __builtin_amdgcn_perm((unsigned)ob[1], (unsigned)ob[0], 0x0c0c0400u) | __builtin_amdgcn_perm((unsigned)ob[3], (unsigned)ob[2], 0x04000c0cu);
+            wq[dt] = low_bytes(ob);
         }
-        // 4 x 4 dword transpose over the four lanes of a query: lane g ends with bytes d = 16 g .. 16 g + 15 (as attention_kernel)
-        typedef unsigned v2u __attribute__((ext_vector_type(2)));
-        const v2u ab = __builtin_amdgcn_permlane32_swap(wq[0], wq[2], false, false);
-        const v2u cd = __builtin_amdgcn_permlane32_swap(wq[1], wq[3], false, false);
-        const v2u ac = __builtin_amdgcn_permlane16_swap(ab.x, cd.x, false, false);
-        const v2u bd = __builtin_amdgcn_permlane16_swap(ab.y, cd.y, false, false);
+        // lane g ends with bytes d = 16 g .. 16 g + 15 of its query
+        const v4i chunk = attn_out_transpose(wq);
         if (qrow < T) {
-            const v4i chunk = {(int)ac.x, (int)ac.y, (int)bd.x, (int)bd.y};
             const int64_t orow_idx = (int64_t)b * T + qrow;
             if (a.out_blocks) {
                 const BlockRow obrow = block_row((int)orow_idx, a.heads * HD);
@@ -1069,21 +992,6 @@ __global__ __launch_bounds__(NTH, 1) void attention_long_kernel(LongArgs a)
             }
         }
     }
-}
-
-// Workgroups per (image, head) for the long kernel: one workgroup per CU (256 slots), nw waves walking nqt query tiles.  The same
-// cost model as attention_parts, staging and a query tile both growing with T alike.
-int attention_long_parts(int batch_heads, int nqt, int nw)
-{
-    int best = 1;
-    double best_t = 0.0;
-    for (int p = 1; p <= 4; p *= 2) {
-        if (p > 1 && nw * (p / 2) >= nqt) break;
-        const int rounds = (batch_heads * p + 255) / 256, tiles = (nqt + nw * p - 1) / (nw * p);
-        const double t = rounds * (3.0 + 3.45 * tiles);
-        if (p == 1 || t < 0.95 * best_t) { best = p; best_t = t; }
-    }
-    return best;
 }
 
 // ---- one query per (image, head): the class row of the last block, the only row of its output the classifier reads
@@ -1174,9 +1082,7 @@ __global__ __launch_bounds__(NT, CLS_OCC) void attention_cls_kernel(ClsArgs a)
         esum += c4 == 0 ? e : 0u;                     // the four lanes of a quad hold the same key
     }
     esum = (unsigned)lanes_allsum_i32<64>((int)esum);
-    float S = (float)esum;                                         // exp_int.sum (:171)
-    S = fminf(S, 2147483648.0f);                                   // clamp_max_(2**31-1) in float32 (:173)
-    const float factor = floorf((1.0f / S) * 2147483648.0f);       // (:174)
+    const float factor = shiftmax_factor(esum);
 
     // ---- O = P . V over this lane's chunks
     int acc[16];
@@ -1192,7 +1098,6 @@ __global__ __launch_bounds__(NT, CLS_OCC) void attention_cls_kernel(ClsArgs a)
     int ob[16];
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
-        typedef unsigned v2u __attribute__((ext_vector_type(2)));
         int t = acc[j];
         t += (int)IVIT_DPP_U32(t, 0x124);      // row_ror:4
         t += (int)IVIT_DPP_U32(t, 0x128);      // row_ror:8
@@ -1212,58 +1117,217 @@ __global__ __launch_bounds__(NT, CLS_OCC) void attention_cls_kernel(ClsArgs a)
     }
 }
 
+
+// ---- host side: every exported entry fills an AttnDesc and returns attention_launch(desc)
+enum AttnFamily {
+    SHIFTMAX_SHORT,   // attention_kernel MODE 0 / 1 / 2, 1 .. 208 tokens
+    SHIFTMAX_LONG,    // attention_long_kernel MODE 0 / 1, 208 .. 1025 tokens
+    IBERT_SHORT,      // attention_kernel MODE 3 / 4, 193 .. 207 tokens (the 13-tile form; the float32 row-sum order of rowsum.h)
+    IBERT_LONG,       // attention_long_kernel MODE 2, 208 .. 1025 tokens
+    SHIFTMAX_CLS      // attention_cls_kernel, 1 .. 208 tokens
+};
+
+struct AttnDesc {     // never passed to a kernel
+    const char* name;             // the called entry, for the messages
+    AttnFamily family;
+    const int8_t* qkv;            // cls: k
+    int8_t* out;
+    int batch, heads, tokens, head_dim;
+    uint32_t m_s;
+    int32_t e_s;
+    float s_attn;                 // Shiftmax families
+    uint32_t m_o;
+    int32_t e_o;
+    const void* table;            // Shiftmax: exp2d (u32) or NULL; I-BERT: the (row max, q) table (float32), required
+    const void* band;
+    int band_w;
+    int softmax_bits, out_blocks;
+    ivit_stream_t stream;
+    const int8_t *v, *q;          // cls only
+    int64_t ldo;                  // cls only
+    double Ms, Mo;                // filled by attention_check
+    int x0;
+};
+
+// Every check the entries share; a family's own checks are marked.  On success the two multipliers and x0 are in the descriptor.
+int attention_check(AttnDesc& d)
+{
+    const char* fn = d.name;
+    const bool ibert = d.family == IBERT_SHORT || d.family == IBERT_LONG, cls = d.family == SHIFTMAX_CLS;
+    const bool lng = d.family == SHIFTMAX_LONG || d.family == IBERT_LONG;
+    IVIT_REQUIRE(d.softmax_bits == 8 || d.softmax_bits == 16, "%s: softmax_bits must be 8 or 16", fn);
+    const bool operands = d.qkv && d.out && (!ibert || d.table) && (!cls || (d.v && d.q));
+    if (d.family == IBERT_SHORT) {
+        IVIT_REQUIRE(operands && d.batch > 0 && d.heads > 0, "%s: bad operand", fn);
+    } else {
+        IVIT_REQUIRE(operands, ibert ? "%s: bad operand (NULL qkv, out or table)" : "%s: NULL operand", fn);
+        IVIT_REQUIRE(d.batch > 0 && d.heads > 0 && (int64_t)d.batch * d.heads < 2147483648ll, "%s: empty batch", fn);
+    }
+    const int t_min = lng ? LONG_T_MIN : d.family == IBERT_SHORT ? 16 * (NKT - 1) + 1 : 1;
+    const int t_max = lng ? LONG_T_MAX : d.family == IBERT_SHORT ? KP - 1 : KP;
+    if (d.head_dim != HD || d.tokens < t_min || d.tokens > t_max) {
+        ivit_set_error("%s: unsupported geometry head_dim=%d tokens=%d (need 64, %d..%d)", fn, d.head_dim, d.tokens, t_min, t_max);
+        return IVIT_ERR_UNSUPPORTED;
+    }
+    const bool aligned = ((uintptr_t)d.qkv % 16 == 0) && ((uintptr_t)d.out % 16 == 0) && (!ibert || (uintptr_t)d.table % 4 == 0) &&
+                         (!cls || (((uintptr_t)d.v % 16 == 0) && ((uintptr_t)d.q % 16 == 0) &&
+                                   d.ldo >= (int64_t)d.heads * d.head_dim && d.ldo % 16 == 0));
+    IVIT_REQUIRE(aligned, d.family == IBERT_SHORT ? "%s: misaligned operand" : "%s: misaligned operand (16-byte rows)", fn);
+    if (!ibert) IVIT_REQUIRE(d.s_attn > 0.0f, "%s: scale must be positive", fn);
+    IVIT_REQUIRE(d.out_blocks == 0 || (d.out_blocks == 1 && ((int64_t)d.batch * d.tokens + 15) * d.heads * d.head_dim < 2147483648ll),
+                 "%s: bad output layout (block-layout buffers stay below 2 GiB)", fn);
+    if (lng)      // long rows only
+        IVIT_REQUIRE((int64_t)d.batch * d.heads * d.tokens * d.head_dim * 3 < ((int64_t)1 << 40), "%s: qkv too large", fn);
+    IVIT_REQUIRE((uintptr_t)d.table % 4 == 0, "%s: misaligned exponent table", fn);
+    IVIT_REQUIRE(d.band_w == 0 || (d.band && d.band_w >= 16 && d.band_w <= 256 && d.band_w % 16 == 0 && (uintptr_t)d.band % 16 == 0),
+                 "%s: band table must be 16-byte aligned, width a multiple of 16 in [16, 256]", fn);
+    d.Ms = ivit_dyadic_to_double(d.m_s, d.e_s);
+    d.Mo = ivit_dyadic_to_double(d.m_o, d.e_o);
+    IVIT_REQUIRE(d.Ms < 2048.0 && d.Mo < 512.0, "%s: requant multiplier too large", fn);
+    d.x0 = 0;
+    if (!ibert) {
+        const float x0f = __builtin_floorf((1.0f / d.s_attn) * -1.0f);  // ivit_modules.py:154
+        IVIT_REQUIRE(x0f <= -1.0f && x0f >= -4096.0f, "%s: x0=%g outside [-4096,-1]", fn, (double)x0f);
+        d.x0 = (int)x0f;
+        // short rows only: the exact u32 row sum, tokens * |x0| * 2^15, must stay below 2^32.  Long rows: exp_int <= 2 |x0| * 2^14
+        // <= 2^27, 16 of them in u32, the row in u64 (common.h rows_allsum_u64)
+        if (!lng)
+            IVIT_REQUIRE((double)d.tokens * (double)(-d.x0) * 32768.0 < 4294967296.0,
+                         "%s: Shiftmax row sum could overflow 32 bits (x0=%d)", fn, d.x0);
+    }
+    return IVIT_OK;
+}
+
+// The instantiations, by what selects them.  An empty slot is never selected (RQ32 exists for 8-bit probabilities only, the I-BERT
+// long form for 8-bit only).
+typedef void (*ShortKernel)(AttnArgs);
+typedef void (*LongKernel)(LongArgs);
+typedef void (*ClsKernel)(ClsArgs);
+// [GENT: tokens <= 192][PB 16][MODE 0, MODE 1 (band), MODE 2 (exp2d), MODE 0 with RQ32]
+const ShortKernel SHIFTMAX_SHORT_KERNELS[2][2][4] = {
+    {{attention_kernel<0>, attention_kernel<1>, attention_kernel<2>, attention_kernel<0, 8, 4, false, true>},
+     {attention_kernel<0, 16>, attention_kernel<1, 16>, attention_kernel<2, 16>, nullptr}},
+    {{attention_kernel<0, 8, 4, true>, attention_kernel<1, 8, 4, true>, attention_kernel<2, 8, 4, true>, attention_kernel<0, 8, 4, true, true>},
+     {attention_kernel<0, 16, 3, true>, attention_kernel<1, 16, 3, true>, attention_kernel<2, 16, 3, true>, nullptr}}};
+// [PB 16][MODE 3 (table), MODE 4 (band)]
+const ShortKernel IBERT_SHORT_KERNELS[2][2] = {{attention_kernel<3>, attention_kernel<4>}, {attention_kernel<3, 16>, attention_kernel<4, 16>}};
+// [PB 16][(tokens >> 4) > 40][MODE 0, MODE 0 with RQ32, MODE 1 (natural), MODE 2 (I-BERT), MODE 2 with RQ32]; the threads per
+// workgroup alongside: 16-bit probabilities are two more accumulator sets, so each token range takes the next smaller workgroup
+const int LONG_THREADS[2][2] = {{1024, 768}, {768, 512}};
+const LongKernel LONG_KERNELS[2][2][5] = {
+    {{attention_long_kernel<0, false, 40, 1024>, attention_long_kernel<0, true, 40, 1024>, attention_long_kernel<1, false, 40, 1024>,
+      attention_long_kernel<2, false, 40, 1024>, attention_long_kernel<2, true, 40, 1024>},
+     {attention_long_kernel<0, false, 64, 768>, attention_long_kernel<0, true, 64, 768>, attention_long_kernel<1, false, 64, 768>,
+      attention_long_kernel<2, false, 64, 768>, attention_long_kernel<2, true, 64, 768>}},
+    {{attention_long_kernel<0, false, 40, 768, 16>, attention_long_kernel<0, true, 40, 768, 16>, attention_long_kernel<1, false, 40, 768, 16>,
+      nullptr, nullptr},
+     {attention_long_kernel<0, false, 64, 512, 16>, attention_long_kernel<0, true, 64, 512, 16>, attention_long_kernel<1, false, 64, 512, 16>,
+      nullptr, nullptr}}};
+const ClsKernel CLS_KERNELS[3] = {attention_cls_kernel<0>, attention_cls_kernel<1>, attention_cls_kernel<2>};   // [MODE]
+
+int attention_launch(AttnDesc d)
+{
+    if (const int rc = attention_check(d)) return rc;
+    const bool ibert = d.family == IBERT_SHORT || d.family == IBERT_LONG;
+    const int pairs = d.batch * d.heads, pb16 = d.softmax_bits == 16;
+    // a power-of-two score multiplier (m = 2^k): the float32 requantisation of the RQ32 kernels is exact
+    const bool ms_pow2 = d.m_s != 0 && (d.m_s & (d.m_s - 1)) == 0 && d.Ms >= 1e-30;
+    hipStream_t st = ivit_stream(d.stream);
+    if (d.family == SHIFTMAX_CLS) {
+        ClsArgs a{};
+        a.k = d.qkv; a.v = d.v; a.q = d.q; a.out = d.out; a.ldo = d.ldo;
+        a.pairs = pairs; a.heads = d.heads; a.tokens = d.tokens;
+        a.exp2d = static_cast<const unsigned*>(d.table); a.band = static_cast<const unsigned*>(d.band); a.band_w = d.band_w;
+        a.Ms = d.Ms; a.Mo = d.Mo; a.x0 = d.x0;
+        hipLaunchKernelGGL(CLS_KERNELS[d.band_w ? 1 : d.table ? 2 : 0], dim3((pairs + CLS_WAVES - 1) / CLS_WAVES), dim3(NT), 0, st, a);
+        IVIT_CHECK_LAUNCH(d.name);
+    }
+    const int nqt = (d.tokens + 15) >> 4;
+    if (d.family == SHIFTMAX_LONG || d.family == IBERT_LONG) {
+        LongArgs a{};
+        a.qkv = d.qkv; a.out = d.out; a.batch = d.batch; a.heads = d.heads; a.tokens = d.tokens;
+        a.out_blocks = d.out_blocks;
+        a.Ms = d.Ms; a.Mo = d.Mo; a.Ms32 = (float)d.Ms; a.x0 = d.x0;
+        a.table = static_cast<const unsigned*>(d.band_w ? d.band : d.table);
+        a.band_w = d.band_w;
+        a.vt_row = ((((nqt + 3) >> 2) + 3) >> 2) * 256;
+        const size_t lds = (size_t)LONG_LUT_BYTES + (size_t)nqt * 16 * HD + (size_t)HD * a.vt_row;    // <= 150528 bytes at 1025 tokens
+        const int wide = (d.tokens >> 4) > 40, nth = LONG_THREADS[pb16][wide];
+        a.parts = attention_parts(pairs, nqt, nth / 64, 256);
+        const int sel = ibert ? (ms_pow2 ? 4 : 3) : (d.band_w || d.table) ? 2 : ms_pow2 ? 1 : 0;
+        hipLaunchKernelGGL(LONG_KERNELS[pb16][wide][sel], dim3(pairs * a.parts), dim3(nth), lds, st, a);
+        IVIT_CHECK_LAUNCH(d.name);
+    }
+    AttnArgs a{};
+    a.qkv = d.qkv; a.out = d.out; a.batch = d.batch; a.heads = d.heads; a.tokens = d.tokens;
+    a.out_blocks = d.out_blocks;
+    a.Ms = d.Ms; a.Mo = d.Mo;
+    a.band = static_cast<const unsigned*>(d.band);
+    a.band_w = d.band_w;
+    const size_t band_lds_bytes = d.band_w ? (size_t)4 * 16 * (d.band_w + BAND_PAD) * sizeof(unsigned) : 0;
+    {   // resident workgroups: 4 per CU for 8-bit probabilities (128 VGPRs), 3 for the 16-bit planes; the band rows add dynamic LDS
+        const int by_regs = pb16 ? 3 : 4, by_lds = (int)(163840 / (SMEM_BYTES + 512 + band_lds_bytes));
+        a.parts = attention_parts(pairs, nqt, NT / 64, 256 * (by_regs < by_lds ? by_regs : by_lds));
+#if IVIT_LAB
+        if ((g_attn_debug >> 8) & 7) a.parts = (g_attn_debug >> 8) & 7;      // lab: forced (scripts/attn_parts.py), this form only
+#endif
+    }
+    ShortKernel kernel;
+    if (ibert) {
+        a.ib_table = static_cast<const float*>(d.table);
+        kernel = IBERT_SHORT_KERNELS[pb16][d.band_w ? 1 : 0];
+    } else {
+        a.abl = g_attn_debug & 31;
+        a.exp2d = static_cast<const unsigned*>(d.table);
+        a.nMs32 = (float)-d.Ms;
+        a.x0 = d.x0;
+        a.ksat = 255;
+        for (int i = 0; i < 256; ++i) {
+            const int dd = -i;
+            const int x = dd + (dd >> 1) - (dd >> 4);  // ivit_modules.py:151 (arithmetic shifts = floor)
+            if (x <= 15 * a.x0) { a.ksat = i; break; }
+        }
+        const bool rq32 = ms_pow2 && !pb16 && !(IVIT_LAB && (g_attn_debug & (1 << 5)));     // lab bit 5: off, A/B
+        kernel = SHIFTMAX_SHORT_KERNELS[d.tokens <= 16 * (NKT - 1)][pb16][d.band_w ? 1 : d.table ? 2 : rq32 ? 3 : 0];
+    }
+    hipLaunchKernelGGL(kernel, dim3(pairs * a.parts), dim3(NT), band_lds_bytes, st, a);
+    IVIT_CHECK_LAUNCH(d.name);
+}
+
 }  // namespace
 
+// The eleven entries (contracts: include/ivit_hip.h).  Descriptor order: name, family, qkv, out, batch, heads, tokens, head_dim, m_s,
+// e_s, s_attn, m_o, e_o, table, band, band_w, softmax_bits, out_blocks, stream (cls: + v, q, ldo).
 IVIT_EXPORT int ivit_attention_cls_i8(const int8_t* k, const int8_t* v, const int8_t* q, int8_t* out, int64_t ldo, int batch,
                                       int heads, int tokens, int head_dim, uint32_t m_s, int32_t e_s, float s_attn, uint32_t m_o,
                                       int32_t e_o, const uint32_t* exp2d, const uint32_t* band, int band_w, ivit_stream_t stream)
 {
-    IVIT_REQUIRE(k && v && q && out, "ivit_attention_cls_i8: NULL operand");
-    IVIT_REQUIRE(batch > 0 && heads > 0 && (int64_t)batch * heads < 2147483648ll, "ivit_attention_cls_i8: empty batch");
-    if (head_dim != HD || tokens < 1 || tokens > KP) {
-        ivit_set_error("ivit_attention_cls_i8: unsupported geometry head_dim=%d tokens=%d (need 64, 1..208)", head_dim, tokens);
-        return IVIT_ERR_UNSUPPORTED;
-    }
-    IVIT_REQUIRE(((uintptr_t)k % 16 == 0) && ((uintptr_t)v % 16 == 0) && ((uintptr_t)q % 16 == 0) && ((uintptr_t)out % 16 == 0) &&
-                 ldo >= (int64_t)heads * head_dim && ldo % 16 == 0, "ivit_attention_cls_i8: misaligned operand (16-byte rows)");
-    IVIT_REQUIRE(s_attn > 0.0f, "ivit_attention_cls_i8: scale must be positive");
-    IVIT_REQUIRE((uintptr_t)exp2d % 4 == 0, "ivit_attention_cls_i8: misaligned exponent table");
-    IVIT_REQUIRE(band_w == 0 || (band && band_w >= 16 && band_w <= 256 && band_w % 16 == 0 && (uintptr_t)band % 16 == 0),
-                 "ivit_attention_cls_i8: band table must be 16-byte aligned, width a multiple of 16 in [16, 256]");
-    ClsArgs a{};
-    a.k = k; a.v = v; a.q = q; a.out = out; a.ldo = ldo;
-    a.pairs = batch * heads; a.heads = heads; a.tokens = tokens;
-    a.exp2d = exp2d; a.band = band; a.band_w = band_w;
-    a.Ms = ivit_dyadic_to_double(m_s, e_s);
-    a.Mo = ivit_dyadic_to_double(m_o, e_o);
-    IVIT_REQUIRE(a.Ms < 2048.0 && a.Mo < 512.0, "ivit_attention_cls_i8: requant multiplier too large");
-    const float x0f = __builtin_floorf((1.0f / s_attn) * -1.0f);  // ivit_modules.py:154
-    IVIT_REQUIRE(x0f <= -1.0f && x0f >= -4096.0f, "ivit_attention_cls_i8: x0=%g outside [-4096,-1]", (double)x0f);
-    a.x0 = (int)x0f;
-    IVIT_REQUIRE((double)tokens * (double)(-a.x0) * 32768.0 < 4294967296.0,
-                 "ivit_attention_cls_i8: Shiftmax row sum could overflow 32 bits (x0=%d)", a.x0);
-    const dim3 grid((a.pairs + CLS_WAVES - 1) / CLS_WAVES), blk(NT);
-    hipStream_t st = ivit_stream(stream);
-    if (band_w) hipLaunchKernelGGL(attention_cls_kernel<1>, grid, blk, 0, st, a);
-    else if (exp2d) hipLaunchKernelGGL(attention_cls_kernel<2>, grid, blk, 0, st, a);
-    else hipLaunchKernelGGL(attention_cls_kernel<0>, grid, blk, 0, st, a);
-    IVIT_CHECK_LAUNCH("ivit_attention_cls_i8");
+    return attention_launch({"ivit_attention_cls_i8", SHIFTMAX_CLS, k, out, batch, heads, tokens, head_dim, m_s, e_s, s_attn, m_o, e_o,
+                             exp2d, band, band_w, 8, 0, stream, v, q, ldo});
+}
+
+IVIT_EXPORT int ivit_attention_fused_i8(const int8_t* qkv, int8_t* out, int batch, int heads, int tokens,
+                                        int head_dim, uint32_t m_s, int32_t e_s, float s_attn, uint32_t m_o,
+                                        int32_t e_o, ivit_stream_t stream)
+{
+    return attention_launch({"ivit_attention_fused_i8", SHIFTMAX_SHORT, qkv, out, batch, heads, tokens, head_dim, m_s, e_s, s_attn, m_o,
+                             e_o, nullptr, nullptr, 0, 8, 0, stream});
 }
 
 IVIT_EXPORT int ivit_attention_fused_i8_ex(const int8_t* qkv, int8_t* out, int batch, int heads, int tokens,
                                         int head_dim, uint32_t m_s, int32_t e_s, float s_attn, uint32_t m_o,
                                         int32_t e_o, int out_blocks, ivit_stream_t stream)
 {
-    return ivit_attention_fused_i8_compat(qkv, out, batch, heads, tokens, head_dim, m_s, e_s, s_attn, m_o, e_o, nullptr,
-                                          out_blocks, stream);
+    return attention_launch({"ivit_attention_fused_i8_ex", SHIFTMAX_SHORT, qkv, out, batch, heads, tokens, head_dim, m_s, e_s, s_attn, m_o,
+                             e_o, nullptr, nullptr, 0, 8, out_blocks, stream});
 }
 
 IVIT_EXPORT int ivit_attention_fused_i8_compat(const int8_t* qkv, int8_t* out, int batch, int heads, int tokens,
                                                int head_dim, uint32_t m_s, int32_t e_s, float s_attn, uint32_t m_o,
                                                int32_t e_o, const uint32_t* exp2d, int out_blocks, ivit_stream_t stream)
 {
-    return ivit_attention_fused_i8_compat_band(qkv, out, batch, heads, tokens, head_dim, m_s, e_s, s_attn, m_o, e_o, exp2d,
-                                               nullptr, 0, out_blocks, stream);
+    return attention_launch({"ivit_attention_fused_i8_compat", SHIFTMAX_SHORT, qkv, out, batch, heads, tokens, head_dim, m_s, e_s, s_attn,
+                             m_o, e_o, exp2d, nullptr, 0, 8, out_blocks, stream});
 }
 
 IVIT_EXPORT int ivit_attention_fused_i8_compat_band(const int8_t* qkv, int8_t* out, int batch, int heads, int tokens,
@@ -1271,8 +1335,8 @@ IVIT_EXPORT int ivit_attention_fused_i8_compat_band(const int8_t* qkv, int8_t* o
                                                     int32_t e_o, const uint32_t* exp2d, const uint32_t* band, int band_w,
                                                     int out_blocks, ivit_stream_t stream)
 {
-    return ivit_attention_fused_i8_wide(qkv, out, batch, heads, tokens, head_dim, m_s, e_s, s_attn, m_o, e_o, exp2d, band, band_w, 8,
-                                        out_blocks, stream);
+    return attention_launch({"ivit_attention_fused_i8_compat_band", SHIFTMAX_SHORT, qkv, out, batch, heads, tokens, head_dim, m_s, e_s,
+                             s_attn, m_o, e_o, exp2d, band, band_w, 8, out_blocks, stream});
 }
 
 IVIT_EXPORT int ivit_attention_fused_i8_wide(const int8_t* qkv, int8_t* out, int batch, int heads, int tokens, int head_dim,
@@ -1280,200 +1344,8 @@ IVIT_EXPORT int ivit_attention_fused_i8_wide(const int8_t* qkv, int8_t* out, int
                                              const uint32_t* exp2d, const uint32_t* band, int band_w, int softmax_bits,
                                              int out_blocks, ivit_stream_t stream)
 {
-    IVIT_REQUIRE(softmax_bits == 8 || softmax_bits == 16, "ivit_attention_fused_i8_wide: softmax_bits must be 8 or 16");
-    IVIT_REQUIRE(qkv && out, "ivit_attention_fused_i8: NULL operand");
-    IVIT_REQUIRE(batch > 0 && heads > 0, "ivit_attention_fused_i8: empty batch");
-    if (head_dim != HD || tokens < 1 || tokens > KP) {
-        ivit_set_error("ivit_attention_fused_i8: unsupported geometry head_dim=%d tokens=%d (need 64, 1..208)",
-                       head_dim, tokens);
-        return IVIT_ERR_UNSUPPORTED;
-    }
-    IVIT_REQUIRE(((uintptr_t)qkv % 16 == 0) && ((uintptr_t)out % 16 == 0) && ((heads * head_dim) % 16 == 0),
-                 "ivit_attention_fused_i8: misaligned operand (16-byte rows)");
-    IVIT_REQUIRE(s_attn > 0.0f, "ivit_attention_fused_i8: scale must be positive");
-    IVIT_REQUIRE(out_blocks == 0 || (out_blocks == 1 && ((uintptr_t)out % 16 == 0) &&
-                                     ((int64_t)batch * tokens + 15) * heads * head_dim < 2147483648ll),
-                 "ivit_attention_fused_i8_ex: bad output layout (block-layout buffers stay below 2 GiB)");
-    IVIT_REQUIRE((uintptr_t)exp2d % 4 == 0, "ivit_attention_fused_i8_compat: misaligned exponent table");
-    IVIT_REQUIRE(band_w == 0 || (band && band_w >= 16 && band_w <= 256 && band_w % 16 == 0 && (uintptr_t)band % 16 == 0),
-                 "ivit_attention_fused_i8_compat_band: band table must be 16-byte aligned, width a multiple of 16 in [16, 256]");
-    AttnArgs a{};
-    a.abl = g_attn_debug & 31;
-    a.exp2d = exp2d;
-    a.band = band;
-    a.band_w = band_w;
-    a.out_blocks = out_blocks;
-    a.qkv = qkv; a.out = out; a.batch = batch; a.heads = heads; a.tokens = tokens;
-    a.Ms = ivit_dyadic_to_double(m_s, e_s);
-    a.Mo = ivit_dyadic_to_double(m_o, e_o);
-    // a power-of-two score multiplier (m = 2^k): the float32 requantisation of the RQ32 kernels is exact (lab bit 5: off, A/B)
-    const bool ms_pow2 = m_s != 0 && (m_s & (m_s - 1)) == 0 && a.Ms >= 1e-30 && !(IVIT_LAB && (g_attn_debug & (1 << 5)));
-    a.nMs32 = (float)-a.Ms;
-    const float x0f = __builtin_floorf((1.0f / s_attn) * -1.0f);  // ivit_modules.py:154
-    IVIT_REQUIRE(x0f <= -1.0f && x0f >= -4096.0f, "ivit_attention_fused_i8: x0=%g outside [-4096,-1]", (double)x0f);
-    a.x0 = (int)x0f;
-    // exact u32 row sum: tokens * |x0| * 2^15 must stay below 2^32
-    IVIT_REQUIRE((double)tokens * (double)(-a.x0) * 32768.0 < 4294967296.0,
-                 "ivit_attention_fused_i8: Shiftmax row sum could overflow 32 bits (x0=%d)", a.x0);
-    IVIT_REQUIRE(a.Ms < 2048.0 && a.Mo < 512.0, "ivit_attention_fused_i8: requant multiplier too large");
-    a.ksat = 255;
-    for (int i = 0; i < 256; ++i) {
-        const int d = -i;
-        const int x = d + (d >> 1) - (d >> 4);  // ivit_modules.py:151 (arithmetic shifts = floor)
-        if (x <= 15 * a.x0) { a.ksat = i; break; }
-    }
-    const size_t band_lds_bytes = band_w ? (size_t)4 * 16 * (band_w + BAND_PAD) * sizeof(unsigned) : 0;
-    {   // resident workgroups: 4 per CU for 8-bit probabilities (128 VGPRs), 3 for the 16-bit planes; the band rows add dynamic LDS
-        const int by_regs = softmax_bits == 16 ? 3 : 4, by_lds = (int)(163840 / (SMEM_BYTES + 512 + band_lds_bytes));
-        a.parts = attention_parts(batch * heads, tokens, 256 * (by_regs < by_lds ? by_regs : by_lds));
-    }
-    const dim3 grid(batch * heads * a.parts), blk(NT);
-    hipStream_t st = ivit_stream(stream);
-    if (tokens <= 16 * (NKT - 1)) {      // fewer than 193 tokens: the general-T form
-        if (softmax_bits == 16) {
-            if (band_w) hipLaunchKernelGGL((attention_kernel<1, 16, 3, true>), grid, blk, band_lds_bytes, st, a);
-            else if (exp2d) hipLaunchKernelGGL((attention_kernel<2, 16, 3, true>), grid, blk, 0, st, a);
-            else hipLaunchKernelGGL((attention_kernel<0, 16, 3, true>), grid, blk, 0, st, a);
-        } else {
-            if (band_w) hipLaunchKernelGGL((attention_kernel<1, 8, 4, true>), grid, blk, band_lds_bytes, st, a);
-            else if (exp2d) hipLaunchKernelGGL((attention_kernel<2, 8, 4, true>), grid, blk, 0, st, a);
-            else if (ms_pow2) hipLaunchKernelGGL((attention_kernel<0, 8, 4, true, true>), grid, blk, 0, st, a);
-            else hipLaunchKernelGGL((attention_kernel<0, 8, 4, true>), grid, blk, 0, st, a);
-        }
-        IVIT_CHECK_LAUNCH("ivit_attention_fused_i8");
-    }
-    if (softmax_bits == 16) {
-        if (band_w) hipLaunchKernelGGL((attention_kernel<1, 16>), grid, blk, band_lds_bytes, st, a);
-        else if (exp2d) hipLaunchKernelGGL((attention_kernel<2, 16>), grid, blk, 0, st, a);
-        else hipLaunchKernelGGL((attention_kernel<0, 16>), grid, blk, 0, st, a);
-    } else {
-        if (band_w) hipLaunchKernelGGL(attention_kernel<1>, grid, blk, band_lds_bytes, st, a);
-        else if (exp2d) hipLaunchKernelGGL(attention_kernel<2>, grid, blk, 0, st, a);
-        else if (ms_pow2) hipLaunchKernelGGL((attention_kernel<0, 8, 4, false, true>), grid, blk, 0, st, a);
-        else hipLaunchKernelGGL(attention_kernel<0>, grid, blk, 0, st, a);
-    }
-    IVIT_CHECK_LAUNCH("ivit_attention_fused_i8");
-}
-
-IVIT_EXPORT int ivit_attention_fused_i8_ibert(const int8_t* qkv, int8_t* out, int batch, int heads, int tokens, int head_dim,
-                                              uint32_t m_s, int32_t e_s, uint32_t m_o, int32_t e_o, const float* table,
-                                              const float* band, int band_w, int out_blocks, ivit_stream_t stream)
-{
-    return ivit_attention_fused_i8_ibert_wide(qkv, out, batch, heads, tokens, head_dim, m_s, e_s, m_o, e_o, table, band, band_w, 8,
-                                              out_blocks, stream);
-}
-
-IVIT_EXPORT int ivit_attention_fused_i8_ibert_wide(const int8_t* qkv, int8_t* out, int batch, int heads, int tokens, int head_dim,
-                                                   uint32_t m_s, int32_t e_s, uint32_t m_o, int32_t e_o, const float* table,
-                                                   const float* band, int band_w, int softmax_bits, int out_blocks,
-                                                   ivit_stream_t stream)
-{
-    IVIT_REQUIRE(softmax_bits == 8 || softmax_bits == 16, "ivit_attention_fused_i8_ibert_wide: softmax_bits must be 8 or 16");
-    IVIT_REQUIRE(qkv && out && table && batch > 0 && heads > 0, "ivit_attention_fused_i8_ibert: bad operand");
-    IVIT_REQUIRE(band_w == 0 || (band && band_w >= 16 && band_w <= 256 && band_w % 16 == 0 && (uintptr_t)band % 16 == 0),
-                 "ivit_attention_fused_i8_ibert: band table must be 16-byte aligned, width a multiple of 16 in [16, 256]");
-    if (head_dim != HD || tokens <= 16 * (NKT - 1) || tokens >= KP) {
-        ivit_set_error("ivit_attention_fused_i8_ibert: unsupported geometry head_dim=%d tokens=%d (need 64, 193..207)", head_dim, tokens);
-        return IVIT_ERR_UNSUPPORTED;
-    }
-    IVIT_REQUIRE(((uintptr_t)qkv % 16 == 0) && ((uintptr_t)out % 16 == 0) && ((uintptr_t)table % 4 == 0),
-                 "ivit_attention_fused_i8_ibert: misaligned operand");
-    IVIT_REQUIRE(out_blocks == 0 || (out_blocks == 1 && ((uintptr_t)out % 16 == 0) &&
-                                     ((int64_t)batch * tokens + 15) * heads * head_dim < 2147483648ll),
-                 "ivit_attention_fused_i8_ibert: bad output layout (block-layout buffers stay below 2 GiB)");
-    AttnArgs a{};
-    a.ib_table = table;
-    a.out_blocks = out_blocks;
-    a.qkv = qkv; a.out = out; a.batch = batch; a.heads = heads; a.tokens = tokens;
-    a.Ms = ivit_dyadic_to_double(m_s, e_s);
-    a.Mo = ivit_dyadic_to_double(m_o, e_o);
-    IVIT_REQUIRE(a.Ms < 2048.0 && a.Mo < 512.0, "ivit_attention_fused_i8_ibert: requant multiplier too large");
-    a.band = reinterpret_cast<const unsigned*>(band);
-    a.band_w = band_w;
-    const size_t band_lds_bytes = band_w ? (size_t)4 * 16 * (band_w + BAND_PAD) * sizeof(unsigned) : 0;
-    {
-        const int by_regs = softmax_bits == 16 ? 3 : 4, by_lds = (int)(163840 / (SMEM_BYTES + 512 + band_lds_bytes));
-        a.parts = attention_parts(batch * heads, tokens, 256 * (by_regs < by_lds ? by_regs : by_lds));
-    }
-    if (softmax_bits == 16) {
-        if (band_w) hipLaunchKernelGGL((attention_kernel<4, 16>), dim3(batch * heads * a.parts), dim3(NT), band_lds_bytes, ivit_stream(stream), a);
-        else hipLaunchKernelGGL((attention_kernel<3, 16>), dim3(batch * heads * a.parts), dim3(NT), 0, ivit_stream(stream), a);
-    } else {
-        if (band_w) hipLaunchKernelGGL(attention_kernel<4>, dim3(batch * heads * a.parts), dim3(NT), band_lds_bytes, ivit_stream(stream), a);
-        else hipLaunchKernelGGL(attention_kernel<3>, dim3(batch * heads * a.parts), dim3(NT), 0, ivit_stream(stream), a);
-    }
-    IVIT_CHECK_LAUNCH("ivit_attention_fused_i8_ibert");
-}
-
-IVIT_EXPORT int ivit_attention_fused_i8(const int8_t* qkv, int8_t* out, int batch, int heads, int tokens,
-                                        int head_dim, uint32_t m_s, int32_t e_s, float s_attn, uint32_t m_o,
-                                        int32_t e_o, ivit_stream_t stream)
-{
-    return ivit_attention_fused_i8_ex(qkv, out, batch, heads, tokens, head_dim, m_s, e_s, s_attn, m_o, e_o, 0, stream);
-}
-
-// fn: the entry point's name for the messages; pb: 8 or 16, the width of the Shiftmax output
-static int attention_long_launch(const char* fn, const int8_t* qkv, int8_t* out, int batch, int heads, int tokens, int head_dim,
-                                 uint32_t m_s, int32_t e_s, float s_attn, uint32_t m_o, int32_t e_o, const uint32_t* exp2d,
-                                 const uint32_t* band, int band_w, int pb, int out_blocks, ivit_stream_t stream)
-{
-    IVIT_REQUIRE(qkv && out, "%s: NULL operand", fn);
-    IVIT_REQUIRE(batch > 0 && heads > 0, "%s: empty batch", fn);
-    if (head_dim != HD || tokens < LONG_T_MIN || tokens > LONG_T_MAX) {
-        ivit_set_error("%s: unsupported geometry head_dim=%d tokens=%d (need 64, %d..%d)", fn, head_dim, tokens,
-                       LONG_T_MIN, LONG_T_MAX);
-        return IVIT_ERR_UNSUPPORTED;
-    }
-    IVIT_REQUIRE(((uintptr_t)qkv % 16 == 0) && ((uintptr_t)out % 16 == 0), "%s: misaligned operand (16-byte rows)", fn);
-    IVIT_REQUIRE(s_attn > 0.0f, "%s: scale must be positive", fn);
-    IVIT_REQUIRE(out_blocks == 0 || (out_blocks == 1 && ((int64_t)batch * tokens + 15) * heads * head_dim < 2147483648ll),
-                 "%s: bad output layout (block-layout buffers stay below 2 GiB)", fn);
-    IVIT_REQUIRE((int64_t)batch * heads * tokens * head_dim * 3 < ((int64_t)1 << 40), "%s: qkv too large", fn);
-    IVIT_REQUIRE((uintptr_t)exp2d % 4 == 0, "%s: misaligned exponent table", fn);
-    IVIT_REQUIRE(band_w == 0 || (band && band_w >= 16 && band_w <= 256 && band_w % 16 == 0 && (uintptr_t)band % 16 == 0),
-                 "%s: band table must be 16-byte aligned, width a multiple of 16 in [16, 256]", fn);
-    LongArgs a{};
-    a.qkv = qkv; a.out = out; a.batch = batch; a.heads = heads; a.tokens = tokens;
-    a.out_blocks = out_blocks;
-    a.Ms = ivit_dyadic_to_double(m_s, e_s);
-    a.Mo = ivit_dyadic_to_double(m_o, e_o);
-    IVIT_REQUIRE(a.Ms < 2048.0 && a.Mo < 512.0, "%s: requant multiplier too large", fn);
-    const bool ms_pow2 = m_s != 0 && (m_s & (m_s - 1)) == 0 && a.Ms >= 1e-30;
-    a.Ms32 = (float)a.Ms;
-    const float x0f = __builtin_floorf((1.0f / s_attn) * -1.0f);   // ivit_modules.py:154
-    IVIT_REQUIRE(x0f <= -1.0f && x0f >= -4096.0f, "%s: x0=%g outside [-4096,-1]", fn, (double)x0f);
-    a.x0 = (int)x0f;    // exp_int <= 2 |x0| * 2^14 <= 2^27: 16 of them in u32, the row in u64 (common.h rows_allsum_u64)
-    a.table = band_w ? band : exp2d;
-    a.band_w = band_w;
-    const int nkt = (tokens + 15) >> 4, nks = (nkt + 3) >> 2;
-    a.vt_row = ((nks + 3) >> 2) * 256;
-    const size_t lds = (size_t)LONG_LUT_BYTES + (size_t)nkt * 16 * HD + (size_t)HD * a.vt_row;    // <= 150528 bytes at 1025 tokens
-    // 16-bit probabilities: two more accumulator sets, so each token range takes the next smaller workgroup
-    const bool natural = band_w || exp2d, wide = (tokens >> 4) > 40;
-    const int nth = pb == 16 ? (wide ? 512 : 768) : (wide ? 768 : 1024);
-    a.parts = attention_long_parts(batch * heads, nkt, nth / 64);
-    const dim3 grid(batch * heads * a.parts), blk(nth);
-    hipStream_t st = ivit_stream(stream);
-    if (pb == 16) {
-        if (!wide) {
-            if (natural) hipLaunchKernelGGL((attention_long_kernel<1, false, 40, 768, 16>), grid, blk, lds, st, a);
-            else if (ms_pow2) hipLaunchKernelGGL((attention_long_kernel<0, true, 40, 768, 16>), grid, blk, lds, st, a);
-            else hipLaunchKernelGGL((attention_long_kernel<0, false, 40, 768, 16>), grid, blk, lds, st, a);
-        } else {
-            if (natural) hipLaunchKernelGGL((attention_long_kernel<1, false, 64, 512, 16>), grid, blk, lds, st, a);
-            else if (ms_pow2) hipLaunchKernelGGL((attention_long_kernel<0, true, 64, 512, 16>), grid, blk, lds, st, a);
-            else hipLaunchKernelGGL((attention_long_kernel<0, false, 64, 512, 16>), grid, blk, lds, st, a);
-        }
-    } else if (!wide) {
-        if (natural) hipLaunchKernelGGL((attention_long_kernel<1, false, 40, 1024>), grid, blk, lds, st, a);
-        else if (ms_pow2) hipLaunchKernelGGL((attention_long_kernel<0, true, 40, 1024>), grid, blk, lds, st, a);
-        else hipLaunchKernelGGL((attention_long_kernel<0, false, 40, 1024>), grid, blk, lds, st, a);
-    } else {
-        if (natural) hipLaunchKernelGGL((attention_long_kernel<1, false, 64, 768>), grid, blk, lds, st, a);
-        else if (ms_pow2) hipLaunchKernelGGL((attention_long_kernel<0, true, 64, 768>), grid, blk, lds, st, a);
-        else hipLaunchKernelGGL((attention_long_kernel<0, false, 64, 768>), grid, blk, lds, st, a);
-    }
-    IVIT_CHECK_LAUNCH(fn);
+    return attention_launch({"ivit_attention_fused_i8_wide", SHIFTMAX_SHORT, qkv, out, batch, heads, tokens, head_dim, m_s, e_s, s_attn,
+                             m_o, e_o, exp2d, band, band_w, softmax_bits, out_blocks, stream});
 }
 
 IVIT_EXPORT int ivit_attention_fused_i8_long(const int8_t* qkv, int8_t* out, int batch, int heads, int tokens, int head_dim,
@@ -1481,8 +1353,8 @@ IVIT_EXPORT int ivit_attention_fused_i8_long(const int8_t* qkv, int8_t* out, int
                                              const uint32_t* exp2d, const uint32_t* band, int band_w, int out_blocks,
                                              ivit_stream_t stream)
 {
-    return attention_long_launch("ivit_attention_fused_i8_long", qkv, out, batch, heads, tokens, head_dim, m_s, e_s, s_attn, m_o, e_o,
-                                 exp2d, band, band_w, 8, out_blocks, stream);
+    return attention_launch({"ivit_attention_fused_i8_long", SHIFTMAX_LONG, qkv, out, batch, heads, tokens, head_dim, m_s, e_s, s_attn,
+                             m_o, e_o, exp2d, band, band_w, 8, out_blocks, stream});
 }
 
 IVIT_EXPORT int ivit_attention_fused_i8_wide_long(const int8_t* qkv, int8_t* out, int batch, int heads, int tokens, int head_dim,
@@ -1490,53 +1362,31 @@ IVIT_EXPORT int ivit_attention_fused_i8_wide_long(const int8_t* qkv, int8_t* out
                                                   const uint32_t* exp2d, const uint32_t* band, int band_w, int softmax_bits,
                                                   int out_blocks, ivit_stream_t stream)
 {
-    IVIT_REQUIRE(softmax_bits == 8 || softmax_bits == 16, "ivit_attention_fused_i8_wide_long: softmax_bits must be 8 or 16");
-    return attention_long_launch("ivit_attention_fused_i8_wide_long", qkv, out, batch, heads, tokens, head_dim, m_s, e_s, s_attn, m_o,
-                                 e_o, exp2d, band, band_w, softmax_bits, out_blocks, stream);
+    return attention_launch({"ivit_attention_fused_i8_wide_long", SHIFTMAX_LONG, qkv, out, batch, heads, tokens, head_dim, m_s, e_s,
+                             s_attn, m_o, e_o, exp2d, band, band_w, softmax_bits, out_blocks, stream});
+}
+
+IVIT_EXPORT int ivit_attention_fused_i8_ibert(const int8_t* qkv, int8_t* out, int batch, int heads, int tokens, int head_dim,
+                                              uint32_t m_s, int32_t e_s, uint32_t m_o, int32_t e_o, const float* table,
+                                              const float* band, int band_w, int out_blocks, ivit_stream_t stream)
+{
+    return attention_launch({"ivit_attention_fused_i8_ibert", IBERT_SHORT, qkv, out, batch, heads, tokens, head_dim, m_s, e_s, 0.0f, m_o,
+                             e_o, table, band, band_w, 8, out_blocks, stream});
+}
+
+IVIT_EXPORT int ivit_attention_fused_i8_ibert_wide(const int8_t* qkv, int8_t* out, int batch, int heads, int tokens, int head_dim,
+                                                   uint32_t m_s, int32_t e_s, uint32_t m_o, int32_t e_o, const float* table,
+                                                   const float* band, int band_w, int softmax_bits, int out_blocks,
+                                                   ivit_stream_t stream)
+{
+    return attention_launch({"ivit_attention_fused_i8_ibert_wide", IBERT_SHORT, qkv, out, batch, heads, tokens, head_dim, m_s, e_s, 0.0f,
+                             m_o, e_o, table, band, band_w, softmax_bits, out_blocks, stream});
 }
 
 IVIT_EXPORT int ivit_attention_fused_i8_ibert_long(const int8_t* qkv, int8_t* out, int batch, int heads, int tokens, int head_dim,
                                                    uint32_t m_s, int32_t e_s, uint32_t m_o, int32_t e_o, const float* table,
                                                    const float* band, int band_w, int out_blocks, ivit_stream_t stream)
 {
-    IVIT_REQUIRE(qkv && out && table, "ivit_attention_fused_i8_ibert_long: bad operand (NULL qkv, out or table)");
-    IVIT_REQUIRE(batch > 0 && heads > 0, "ivit_attention_fused_i8_ibert_long: empty batch");
-    if (head_dim != HD || tokens < LONG_T_MIN || tokens > LONG_T_MAX) {
-        ivit_set_error("ivit_attention_fused_i8_ibert_long: unsupported geometry head_dim=%d tokens=%d (need 64, %d..%d)", head_dim,
-                       tokens, LONG_T_MIN, LONG_T_MAX);
-        return IVIT_ERR_UNSUPPORTED;
-    }
-    IVIT_REQUIRE(((uintptr_t)qkv % 16 == 0) && ((uintptr_t)out % 16 == 0) && ((uintptr_t)table % 4 == 0),
-                 "ivit_attention_fused_i8_ibert_long: misaligned operand (16-byte rows)");
-    IVIT_REQUIRE(out_blocks == 0 || (out_blocks == 1 && ((int64_t)batch * tokens + 15) * heads * head_dim < 2147483648ll),
-                 "ivit_attention_fused_i8_ibert_long: bad output layout (block-layout buffers stay below 2 GiB)");
-    IVIT_REQUIRE((int64_t)batch * heads * tokens * head_dim * 3 < ((int64_t)1 << 40), "ivit_attention_fused_i8_ibert_long: qkv too large");
-    IVIT_REQUIRE(band_w == 0 || (band && band_w >= 16 && band_w <= 256 && band_w % 16 == 0 && (uintptr_t)band % 16 == 0),
-                 "ivit_attention_fused_i8_ibert_long: band table must be 16-byte aligned, width a multiple of 16 in [16, 256]");
-    LongArgs a{};
-    a.qkv = qkv; a.out = out; a.batch = batch; a.heads = heads; a.tokens = tokens;
-    a.out_blocks = out_blocks;
-    a.Ms = ivit_dyadic_to_double(m_s, e_s);
-    a.Mo = ivit_dyadic_to_double(m_o, e_o);
-    IVIT_REQUIRE(a.Ms < 2048.0 && a.Mo < 512.0, "ivit_attention_fused_i8_ibert_long: requant multiplier too large");
-    const bool ms_pow2 = m_s != 0 && (m_s & (m_s - 1)) == 0 && a.Ms >= 1e-30;
-    a.Ms32 = (float)a.Ms;
-    a.table = reinterpret_cast<const unsigned*>(band_w ? band : table);
-    a.band_w = band_w;
-    const int nkt = (tokens + 15) >> 4, nks = (nkt + 3) >> 2;
-    a.vt_row = ((nks + 3) >> 2) * 256;
-    const size_t lds = (size_t)LONG_LUT_BYTES + (size_t)nkt * 16 * HD + (size_t)HD * a.vt_row;
-    const bool wide = (tokens >> 4) > 40;
-    const int nth = wide ? 768 : 1024;
-    a.parts = attention_long_parts(batch * heads, nkt, nth / 64);
-    const dim3 grid(batch * heads * a.parts), blk(nth);
-    hipStream_t st = ivit_stream(stream);
-    if (!wide) {
-        if (ms_pow2) hipLaunchKernelGGL((attention_long_kernel<2, true, 40, 1024>), grid, blk, lds, st, a);
-        else hipLaunchKernelGGL((attention_long_kernel<2, false, 40, 1024>), grid, blk, lds, st, a);
-    } else {
-        if (ms_pow2) hipLaunchKernelGGL((attention_long_kernel<2, true, 64, 768>), grid, blk, lds, st, a);
-        else hipLaunchKernelGGL((attention_long_kernel<2, false, 64, 768>), grid, blk, lds, st, a);
-    }
-    IVIT_CHECK_LAUNCH("ivit_attention_fused_i8_ibert_long");
+    return attention_launch({"ivit_attention_fused_i8_ibert_long", IBERT_LONG, qkv, out, batch, heads, tokens, head_dim, m_s, e_s, 0.0f,
+                             m_o, e_o, table, band, band_w, 8, out_blocks, stream});
 }

@@ -1,0 +1,128 @@
+// attn_parts.h -- the device pieces the fused attention kernels share, stated ONCE (attention.hip: attention_kernel,
+// attention_long_kernel, attention_cls_kernel; swin.hip: window_attention_kernel, window_attention_long_kernel).  Included inside
+// the anonymous namespace of those files, after common.h.  Arithmetic and lane exchanges only: loads, stores and their addresses,
+// loop structure, scheduling barriers and the lab ablation branches stay in the kernels.  Every helper is force-inlined and leaves
+// each kernel's instruction sequence as it was (scripts/kernel_table.py, profiles/attn_parts_kernel_table.csv); where a kernel
+// keeps a copy of its own, a helper in its place changed that sequence.
+// Lane roles throughout: lane = 16 g + l15 owns query l15 of its tile and the keys 16 kt + 4 g + r of every key tile; the lanes
+// l, l ^ 16, l ^ 32, l ^ 48 are "the four lanes of a query".
+#pragma once
+
+typedef unsigned v2u __attribute__((ext_vector_type(2)));
+
+// ---- V^T staging: the 4 x 4 byte block of four consecutive keys (rows a0 .. a3, each holding d .. d + 3 in its bytes) transposed
+// in registers with eight v_perm_b32: t[bb] = the 4 keys of d + bb, so every LDS write of V^T is a whole dword
+IVIT_DEV void bytes4x4_transpose(unsigned a0, unsigned a1, unsigned a2, unsigned a3, unsigned (&t)[4])
+{
+    const unsigned lo01 = __builtin_amdgcn_perm(a1, a0, 0x05010400u);  // a0.b0 a1.b0 a0.b1 a1.b1
+    const unsigned hi01 = __builtin_amdgcn_perm(a1, a0, 0x07030602u);  // a0.b2 a1.b2 a0.b3 a1.b3
+    const unsigned lo23 = __builtin_amdgcn_perm(a3, a2, 0x05010400u);
+    const unsigned hi23 = __builtin_amdgcn_perm(a3, a2, 0x07030602u);
+    t[0] = __builtin_amdgcn_perm(lo23, lo01, 0x05040100u);   // d+0: a0.b0 a1.b0 a2.b0 a3.b0
+    t[1] = __builtin_amdgcn_perm(lo23, lo01, 0x07060302u);   // d+1
+    t[2] = __builtin_amdgcn_perm(hi23, hi01, 0x05040100u);   // d+2
+    t[3] = __builtin_amdgcn_perm(hi23, hi01, 0x07060302u);   // d+3
+}
+
+// ---- Shiftmax factor (ivit_modules.py:171-174) from the exact integer row sum, rounded once to float32 (= the reference's
+// float32 sum whenever that is exact)
+IVIT_DEV float shiftmax_factor(unsigned esum)
+{
+    float S = (float)esum;                                     // exp_int.sum (:171)
+    S = fminf(S, 2147483648.0f);                               // clamp_max_(2**31-1) in float32 (:173)
+    return floorf((1.0f / S) * 2147483648.0f);                 // (:174)
+}
+IVIT_DEV float shiftmax_factor(unsigned long long esum)       // long rows: the sum passes 2^32 (1025 * 255 * 2^15)
+{
+    float S = (float)esum;
+    S = fminf(S, 2147483648.0f);
+    return floorf((1.0f / S) * 2147483648.0f);
+}
+
+// ---- 8-bit probabilities: p = floor(fl32(e * factor) / 2^24) (:175) = the top byte of each product u, four gathered with two
+// byte permutes
+IVIT_DEV unsigned top_bytes(const unsigned (&u)[4])
+{
+    return __builtin_amdgcn_perm(u[1], u[0], 0x0c0c0703u) |     // [u0.b3, u1.b3, 0, 0]
+           __builtin_amdgcn_perm(u[3], u[2], 0x07030c0cu);      // [0, 0, u2.b3, u3.b3]
+}
+
+// ---- 16-bit probabilities as 7-bit planes.  u = trunc(fl32(e * factor)) <= 2^31 and p16 = u >> 16 = floor(fl32(e * factor) / 2^16)
+// (Shiftmax :175 with output_bit 16; I-BERT :314 is / 2^17, taken from the product with the halved factor): p16 = c + 128 b +
+// 16384 a with plane c = bits 16..22 of u (byte 2 & 0x7f), plane b = bits 23..29 (byte 3 of u << 1, & 0x7f), plane a = bits 30, 31.
+// One P.V MFMA set per plane; a is needed only where some u of the wave reaches 2^30, and is then taken from the products again.
+IVIT_DEV unsigned plane_c(const unsigned (&u)[4])
+{
+    return (__builtin_amdgcn_perm(u[1], u[0], 0x0c0c0602u) | __builtin_amdgcn_perm(u[3], u[2], 0x06020c0cu)) & 0x7f7f7f7fu;
+}
+IVIT_DEV unsigned plane_b(const unsigned (&u)[4])
+{
+    return (__builtin_amdgcn_perm(u[1] << 1, u[0] << 1, 0x0c0c0703u) | __builtin_amdgcn_perm(u[3] << 1, u[2] << 1, 0x07030c0cu)) & 0x7f7f7f7fu;
+}
+IVIT_DEV unsigned plane_a_byte(unsigned u, int r) { return (u >> 30) << (8 * r); }      // key r's byte of the packed plane a
+
+// ---- I-BERT: probabilities reach 128 (a one-hot row), one more than an int8 MFMA operand holds.  128 = 127 + 1: a byte 0x80 of w
+// becomes 0x7f in lo and 1 in hi, the operand of a second P.V MFMA that is issued only where a wave holds such a byte.
+IVIT_DEV void split_p128(unsigned w, unsigned& lo, unsigned& hi)
+{
+    const unsigned h128 = (w >> 7) & 0x01010101u;          // 1 in every byte that is 0x80
+    lo = w - h128;                                         // 0x80 -> 0x7f (no borrow: the byte is >= 1)
+    hi = h128;
+}
+
+// ---- all-gather over the four lanes of a query in VALU instructions: v_permlane32_swap of a value with itself leaves every lane
+// with the values of rows {0,1} and {2,3} of 16 lanes, v_permlane16_swap of each of those with itself then separates row 0 / 1
+// and row 2 / 3: out[g'] = the value lane 16 g' + l15 held
+IVIT_DEV void gather4(float x, float (&out)[4])
+{
+    const unsigned xb = (unsigned)__float_as_int(x);
+    const v2u h = __builtin_amdgcn_permlane32_swap(xb, xb, false, false);       // h.x: rows 0,1,0,1; h.y: rows 2,3,2,3
+    const v2u a01 = __builtin_amdgcn_permlane16_swap(h.x, h.x, false, false);   // .x: row 0 everywhere, .y: row 1
+    const v2u a23 = __builtin_amdgcn_permlane16_swap(h.y, h.y, false, false);   // .x: row 2, .y: row 3
+    out[0] = __int_as_float((int)a01.x);
+    out[1] = __int_as_float((int)a01.y);
+    out[2] = __int_as_float((int)a23.x);
+    out[3] = __int_as_float((int)a23.y);
+}
+
+// ---- output tail: O^T = Vt . P^T requantised (attn.qact2) to int8, one accumulator element.
+//   PB 8:  |O| <= 1025 * 127 * 128 < 2^24: the float64 product is exact, one fma against the magic constant (requant_exact).
+//   PB 16: O = o + (o_b << 7) + (o_a << 14) = sum p16 * v over the three planes, below 2^30 (bounds: attention_long_kernel); the
+//          reference's float64 product rounds at 53 bits first (quant_utils.py:229-230), so product and rounding are two steps.
+template <int PB>
+IVIT_DEV int attn_out_requant(int o, int o_b, int o_a, double Mo)
+{
+    if constexpr (PB == 16) {
+        const int O = o + (o_b << 7) + (o_a << 14);
+        const double t = (double)O * Mo + IVIT_MAGIC;
+        return clamp_i32((int)(unsigned)__double_as_longlong(t), -128, 127);
+    } else {
+        return clamp_i32(requant_exact(o, Mo), -128, 127);
+    }
+}
+// the low bytes of four values in one dword, by two byte permutes and an OR
+IVIT_DEV unsigned low_bytes(const int (&v)[4])
+{
+    return __builtin_amdgcn_perm((unsigned)v[1], (unsigned)v[0], 0x0c0c0400u) | __builtin_amdgcn_perm((unsigned)v[3], (unsigned)v[2], 0x04000c0cu);
+}
+// one 16 d x 16 queries accumulator tile -> bytes d = 16 dt + 4 g + 0..3 of this lane's query
+template <int PB>
+IVIT_DEV unsigned attn_out_word(const v4i& o, const v4i& o_b, const v4i& o_a, double Mo)
+{
+    int ob[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) ob[r] = attn_out_requant<PB>(o[r], o_b[r], o_a[r], Mo);
+    return low_bytes(ob);
+}
+// A query's 64 output bytes sit as 4 x 4 dwords in its four lanes (wq[dt] of lane g).  A 4 x 4 word transpose across those lanes --
+// two v_permlane32_swap, two v_permlane16_swap -- leaves lane g with the 16 CONTIGUOUS bytes d = 16 g .. 16 g + 15: one 16-byte
+// store per lane instead of four 4-byte ones (a quarter of the store instructions and of the segments the memory pipeline has to
+// merge).  Every lane of the wave takes part.
+IVIT_DEV v4i attn_out_transpose(const unsigned (&wq)[4])
+{
+    const v2u ab = __builtin_amdgcn_permlane32_swap(wq[0], wq[2], false, false);    // g < 2: (w0[g], w0[g+2]); g >= 2: (w2[g-2], w2[g])
+    const v2u cd = __builtin_amdgcn_permlane32_swap(wq[1], wq[3], false, false);    // g < 2: (w1[g], w1[g+2]); g >= 2: (w3[g-2], w3[g])
+    const v2u ac = __builtin_amdgcn_permlane16_swap(ab.x, cd.x, false, false);      // (w_g[0], w_g[1]) of the lanes 0, 1
+    const v2u bd = __builtin_amdgcn_permlane16_swap(ab.y, cd.y, false, false);      // (w_g[2], w_g[3])
+    return v4i{(int)ac.x, (int)ac.y, (int)bd.x, (int)bd.y};
+}

@@ -40,6 +40,7 @@ IVIT_DEV int pack4(int a, int b, int c, int d)
 }
 
 #include "ln_chain.h"
+#include "attn_parts.h"
 
 // ------------------------------------------------------------------------------------------------
 // Row maps: the window partition / cyclic shift of SwinTransformerBlock.forward (swin_quant.py:258-271, 278-289) are
@@ -739,10 +740,8 @@ __global__ __launch_bounds__(NT, 4) void window_attention_kernel(WinAttnArgs a)
 #pragma unroll
             for (int w = 0; w < 4; ++w) {
                 const unsigned a0 = (unsigned)v[0][w], a1 = (unsigned)v[1][w], a2 = (unsigned)v[2][w], a3 = (unsigned)v[3][w];
-                const unsigned lo01 = __builtin_amdgcn_perm(a1, a0, 0x05010400u), hi01 = __builtin_amdgcn_perm(a1, a0, 0x07030602u);
-                const unsigned lo23 = __builtin_amdgcn_perm(a3, a2, 0x05010400u), hi23 = __builtin_amdgcn_perm(a3, a2, 0x07030602u);
-                const unsigned t4[4] = {__builtin_amdgcn_perm(lo23, lo01, 0x05040100u), __builtin_amdgcn_perm(lo23, lo01, 0x07060302u),
-                                        __builtin_amdgcn_perm(hi23, hi01, 0x05040100u), __builtin_amdgcn_perm(hi23, hi01, 0x07060302u)};
+                unsigned t4[4];
+                bytes4x4_transpose(a0, a1, a2, a3, t4);
 #pragma unroll
                 for (int bb = 0; bb < 4; ++bb) {
                     const int d = 16 * c + 4 * w + bb;
@@ -867,9 +866,7 @@ __global__ __launch_bounds__(NT, 4) void window_attention_kernel(WinAttnArgs a)
                     s[kt][r] = (int)e;
                     esum += e;
                 }
-            esum = rows_allsum_u32(esum);
-            float S = fminf((float)esum, 2147483648.0f);                 // ivit_modules.py:171-173
-            const float factor = floorf((1.0f / S) * 2147483648.0f);     // :174
+            const float factor = shiftmax_factor(rows_allsum_u32(esum));
             v4i pk;
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
@@ -982,10 +979,8 @@ __global__ __launch_bounds__(NT, 2) void window_attention_long_kernel(WinAttnArg
 #pragma unroll
             for (int w = 0; w < 4; ++w) {
                 const unsigned a0 = (unsigned)v[0][w], a1 = (unsigned)v[1][w], a2 = (unsigned)v[2][w], a3 = (unsigned)v[3][w];
-                const unsigned lo01 = __builtin_amdgcn_perm(a1, a0, 0x05010400u), hi01 = __builtin_amdgcn_perm(a1, a0, 0x07030602u);
-                const unsigned lo23 = __builtin_amdgcn_perm(a3, a2, 0x05010400u), hi23 = __builtin_amdgcn_perm(a3, a2, 0x07030602u);
-                const unsigned t4[4] = {__builtin_amdgcn_perm(lo23, lo01, 0x05040100u), __builtin_amdgcn_perm(lo23, lo01, 0x07060302u),
-                                        __builtin_amdgcn_perm(hi23, hi01, 0x05040100u), __builtin_amdgcn_perm(hi23, hi01, 0x07060302u)};
+                unsigned t4[4];
+                bytes4x4_transpose(a0, a1, a2, a3, t4);
 #pragma unroll
                 for (int bb = 0; bb < 4; ++bb) {
                     const int d = 16 * c + 4 * w + bb;
@@ -1106,9 +1101,7 @@ __global__ __launch_bounds__(NT, 2) void window_attention_long_kernel(WinAttnArg
                         esum += e;
                     }
             }
-            esum = rows_allsum_u32(esum);
-            const float S = fminf((float)esum, 2147483648.0f);             // ivit_modules.py:171-173
-            const float factor = floorf((1.0f / S) * 2147483648.0f);       // :174
+            const float factor = shiftmax_factor(rows_allsum_u32(esum));
             v4i pk[WL_NKS];
 #pragma unroll
             for (int ks = 0; ks < WL_NKS; ++ks)

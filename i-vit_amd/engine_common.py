@@ -131,23 +131,43 @@ def attention_spec(family, s_S, s_at, s_pv, s_out, upload, device, st, ibert_ran
     return d
 
 
+def attention_entry(family, T, softmax_bits=None):
+    """The fused attention entry that serves rows of T tokens, or None where no fused kernel exists: the one Python statement of the
+    token ranges of csrc/attention.hip.  Shiftmax ("ivit"): the short kernels up to 207 tokens, the long-row ones 208 .. 1025.
+    I-BERT: 193 .. 207 short, 208 .. 1025 long.  softmax_bits: given where the softmax output may be 16 bits wide (the 16-bit stream
+    of the engine, a 16-bit softmax on the module path): the "wide" entries, which take it before the layout flag; I-BERT's softmax
+    has no wide long-row kernel."""
+    wide, long = softmax_bits is not None, T > 207
+    if family == "ibert":
+        if not 193 <= T <= 1025 or (wide and long):
+            return None
+        return "ivit_attention_fused_i8_ibert_wide" if wide else "ivit_attention_fused_i8_ibert_long" if long else "ivit_attention_fused_i8_ibert"
+    if not 1 <= T <= 1025:
+        return None
+    return ("ivit_attention_fused_i8_wide_long" if wide and long else "ivit_attention_fused_i8_wide" if wide else
+            "ivit_attention_fused_i8_long" if long else "ivit_attention_fused_i8_compat_band")
+
+
+def long_multipliers_ok(a):
+    """the long-row kernels' bounds on the two requantisation multipliers of an attention_spec (score < 2048, output < 512).  A model
+    whose attention output range collapsed in calibration (all probabilities 0) breaks the second; such rows ran the literal path
+    before the long-row kernels were routed to the module path and still do"""
+    return a["ms"][0] / 2.0 ** a["ms"][1] < 2048.0 and a["mo"][0] / 2.0 ** a["mo"][1] < 512.0
+
+
 def attention(a, family, qkv, out, B, H, T, hd, st, blocks=False, softmax_bits=None):
     """Fused attention of an attention_spec `a` on head-major qkv [3, B, H, T, hd] -> out [B * T, H * hd] (`blocks`: in the block
-    layout).  Up to 207 tokens the short kernels, 208 .. 1025 the long-row ones (the same arguments); softmax_bits: given where
-    the Shiftmax output may be 16 bits wide (the 16-bit stream of the engine, a 16-bit softmax on the module path), whose "wide"
-    forms take it before the layout flag.  I-BERT's softmax has no wide long-row kernel: an error, nothing is launched."""
-    p, wide, long = _lib.ptr, softmax_bits is not None, T > 207
-    sm = (softmax_bits,) if wide else ()
-    if family == "ibert" and wide and long:
-        raise NotImplementedError(f"no fused I-BERT attention with a softmax_bits argument above 207 tokens (tokens={T})")
+    layout) through attention_entry's kernel (the same arguments for short and long rows).  No entry: an error, nothing is
+    launched."""
+    p, name = _lib.ptr, attention_entry(family, T, softmax_bits)
+    if name is None:
+        raise NotImplementedError(f"no fused {'I-BERT' if family == 'ibert' else 'Shiftmax'} attention for these rows "
+                                  f"(softmax_bits={softmax_bits}, tokens={T})")
+    sm = () if softmax_bits is None else (softmax_bits,)
     if family == "ibert":
-        name = ("ivit_attention_fused_i8_ibert_wide" if wide else "ivit_attention_fused_i8_ibert_long" if long else
-                "ivit_attention_fused_i8_ibert")
         _lib.call(name, p(qkv), p(out), B, H, T, hd, a["ms"][0], a["ms"][1], a["mo"][0], a["mo"][1], p(a["ib_table"]), p(a["band"]),
                   a["band_w"], *sm, int(blocks), st)
     else:
-        name = ("ivit_attention_fused_i8_wide_long" if wide and long else "ivit_attention_fused_i8_wide" if wide else
-                "ivit_attention_fused_i8_long" if long else "ivit_attention_fused_i8_compat_band")
         _lib.call(name, p(qkv), p(out), B, H, T, hd, a["ms"][0], a["ms"][1], a["s_attn"], a["mo"][0], a["mo"][1], p(a["exp2d"]),
                   p(a["band"]), a["band_w"], *sm, int(blocks), st)
 

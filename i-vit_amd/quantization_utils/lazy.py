@@ -46,7 +46,7 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ..engine_common import attention, attention_spec, frag_copy, gelu_lut, layernorm, ln_spec
+from ..engine_common import attention, attention_entry, attention_spec, frag_copy, gelu_lut, layernorm, ln_spec, long_multipliers_ok
 from ..prepare import LayerNormParams, LinearParams, dyadic, dyadic1, f32, quant_sym, sym_scale
 
 ENABLED = os.environ.get("IVIT_LAZY", "1") != "0"
@@ -1154,13 +1154,6 @@ def _resolve_gelu(node, s_out, device):
     return out
 
 
-def _long_multipliers_ok(a):
-    """the long-row kernels' bounds on the two requantisation multipliers (score < 2048, output < 512).  A model whose attention
-    output range collapsed in calibration (all probabilities 0) breaks the second; such rows ran the literal path before the
-    long-row kernels were routed here and still do"""
-    return a["ms"][0] / 2.0 ** a["ms"][1] < 2048.0 and a["mo"][0] / 2.0 ** a["mo"][1] < 512.0
-
-
 def _resolve_attention(node, s_pv, s_out, device):
     """matmul_2(probs, v) behind qact2, where probs = Shiftmax(qact_attn1(matmul_1(q, k^T) * scale)): the fused attention kernel"""
     P, v = node.inputs
@@ -1188,13 +1181,13 @@ def _resolve_attention(node, s_pv, s_out, device):
     family, act, key = "ivit", None, ("attn",)
     if type(sm).__name__ == "IBERTIntSoftmax":
         # IBERTIntSoftmax (ibert_modules.py:237-319): exp_int after its internal 16-bit QuantAct as a (row max, q) table, row sum in
-        # torch's float32 order inside the kernel (attention.hip MODE 3 / 4); that kernel holds 193 .. 207 tokens, the long-row
-        # form (attention_long_kernel MODE 2) 208 .. 1025
-        # with output_bit = 16 only the short kernel has a form (ivit_attention_fused_i8_ibert_wide): other token counts stay literal
-        if not (192 < T <= 1025) or sm.output_bit not in (8, 16) or (sm.output_bit == 16 and T > 207) or sm.act.running_stat:
+        # torch's float32 order inside the kernel (attention.hip MODE 3 / 4, attention_long_kernel MODE 2)
+        if sm.act.running_stat:
             return None
         family, act = "ibert", sm.act
         key = ("ibattn", id(act.x_min), act.x_min._version, id(act.x_max), act.x_max._version)
+    if attention_entry(family, T, softmax_bits) is None:      # token counts without a fused kernel stay literal
+        return None
 
     def build():
         lo_hi = None if act is None else (float(act.x_min.reshape(-1)[0]), float(act.x_max.reshape(-1)[0]))
@@ -1203,7 +1196,7 @@ def _resolve_attention(node, s_pv, s_out, device):
             act.act_scaling_factor = torch.full((1,), d["act_sf"], dtype=torch.float32, device=device)
         return d
     a = _cache(sc.qact, key + (_key(s_S, np.asarray(s_at), s_pv, np.asarray(s_out)), str(device)), build)
-    if T > 207 and not _long_multipliers_ok(a):
+    if T > 207 and not long_multipliers_ok(a):
         return None
     out = torch.empty(B * T, H * hd, dtype=torch.int8, device=device)
     attention(a, family, hm, out, B, H, T, hd, _st(), softmax_bits=softmax_bits)

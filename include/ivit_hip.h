@@ -206,7 +206,8 @@ int ivit_gemm_i8_i32(const int8_t* A, int64_t lda, const int8_t* W, int64_t ldw,
  *   s_attn: float32 scale of the Shiftmax input (x0 = floor(-1/s_attn), n = 15)
  *   (m_o, e_o): requantiser of P.v into the 8-bit output.
  * Supported: head_dim 64, 1 <= tokens <= 208 (13 key tiles of 16; 193 .. 208 take the tuned form in which only the last key tile is
- * partial, fewer tokens the general one); IVIT_ERR_UNSUPPORTED ("unsupported geometry") otherwise. */
+ * partial, fewer tokens the general one); IVIT_ERR_UNSUPPORTED ("unsupported geometry") otherwise.
+ * All ivit_attention_* entries below share one argument check and one launcher; a message names the entry that was called. */
 int ivit_attention_fused_i8(const int8_t* qkv, int8_t* out, int batch, int heads, int tokens, int head_dim,
                             uint32_t m_s, int32_t e_s, float s_attn, uint32_t m_o, int32_t e_o,
                             ivit_stream_t stream);

@@ -98,13 +98,51 @@ def test_engine_unsupported_reason_across_family_width_tokens(img, patch, tokens
         assert m._engine_widths[0] == stream
 
 
-def test_long_attention_prototype_matches_ctypes_table():
+def _prototype_kinds(name):
+    """the ctypes kinds of the parameters `name` is declared with in include/ivit_hip.h"""
     hdr = open(os.path.join(ROOT, "include", "ivit_hip.h")).read()
-    m = re.search(r"int ivit_attention_fused_i8_long\(([^)]*)\);", hdr)
-    assert m, "ivit_attention_fused_i8_long is not declared"
-    kinds = {"const int8_t*": _lib.vp, "int8_t*": _lib.vp, "const uint32_t*": _lib.vp, "int": _lib.ci, "uint32_t": _lib.u32,
-             "int32_t": _lib.i32, "float": _lib.f32, "ivit_stream_t": _lib.vp}
-    types = [re.sub(r"\s+\w+$", "", p.strip()) for p in m.group(1).split(",")]
-    assert _lib.SIGNATURES["ivit_attention_fused_i8_long"] == [kinds[t] for t in types]
+    m = re.search(r"int %s\(([^)]*)\);" % name, hdr)
+    assert m, f"{name} is not declared"
+    kinds = {"const int8_t*": _lib.vp, "int8_t*": _lib.vp, "const uint32_t*": _lib.vp, "const float*": _lib.vp, "int": _lib.ci,
+             "int64_t": _lib.i64, "uint32_t": _lib.u32, "int32_t": _lib.i32, "float": _lib.f32, "ivit_stream_t": _lib.vp}
+    return [kinds[re.sub(r"\s+\w+$", "", p.strip())] for p in m.group(1).split(",")]
+
+
+def test_long_attention_prototype_matches_ctypes_table():
+    assert _lib.SIGNATURES["ivit_attention_fused_i8_long"] == _prototype_kinds("ivit_attention_fused_i8_long")
     # the arguments of ivit_attention_fused_i8_compat_band, out_blocks and the stream included
     assert _lib.SIGNATURES["ivit_attention_fused_i8_long"] == _lib.SIGNATURES["ivit_attention_fused_i8_compat_band"]
+
+
+ENTRIES = ATTN + ("ivit_attention_fused_i8_wide_long", "ivit_attention_fused_i8_ibert_long", "ivit_attention_cls_i8")
+
+
+@pytest.mark.parametrize("name", ENTRIES)
+def test_attention_prototypes_match_ctypes_table(name):
+    """every exported attention entry: the header's prototype is the row _lib.call converts its arguments by"""
+    assert len(ENTRIES) == len(set(ENTRIES)) == 11
+    assert _lib.SIGNATURES[name] == _prototype_kinds(name)
+
+
+# ----------------------------------------------------------------------------------- which entry serves which rows
+S, L = "ivit_attention_fused_i8_", "_long"
+# (family, softmax_bits) -> the entry per token count, written from the expressions of engine_common.attention (T > 207: long rows;
+# softmax_bits given: the wide entries; I-BERT wide and long: none) and lazy._resolve_attention (I-BERT: 192 < T <= 1025) as they
+# stood before attention_entry, and from the launchers' ranges (Shiftmax 1 .. 1025)
+TOKENS = (1, 192, 193, 207, 208, 1025, 1026)
+ENTRY_TABLE = {
+    ("ivit", None): (S + "compat_band",) * 4 + (S[:-1] + L,) * 2 + (None,),
+    ("ivit", 8): (S + "wide",) * 4 + (S + "wide" + L,) * 2 + (None,),
+    ("ivit", 16): (S + "wide",) * 4 + (S + "wide" + L,) * 2 + (None,),
+    ("ibert", None): (None, None, S + "ibert", S + "ibert", S + "ibert" + L, S + "ibert" + L, None),
+    ("ibert", 8): (None, None, S + "ibert_wide", S + "ibert_wide", None, None, None),
+    ("ibert", 16): (None, None, S + "ibert_wide", S + "ibert_wide", None, None, None),
+}
+
+
+@pytest.mark.parametrize("family,bits", sorted(ENTRY_TABLE, key=str))
+def test_attention_entry_table(family, bits):
+    from ivit_amd.engine_common import attention_entry
+    assert tuple(attention_entry(family, T, bits) for T in TOKENS) == ENTRY_TABLE[(family, bits)]
+    for name in ENTRY_TABLE[(family, bits)]:
+        assert name is None or name in ENTRIES

@@ -12,50 +12,17 @@ pytestmark = pytest.mark.gpu
 
 ivit = pytest.importorskip("ivit_amd")
 from ivit_amd import _lib  # noqa: E402
-from ivit_amd.prepare import dyadic, shiftexp_band  # noqa: E402
+from ivit_amd.prepare import dyadic  # noqa: E402
 import ivit_amd.quantization_utils as q  # noqa: E402
 import ibert_long_ref as R  # noqa: E402
+import attention_ref as A  # noqa: E402
+from attention_ref import DEV, release, st  # noqa: E402,F401  (release: the autouse fixture)
 
-DEV = "cuda:0"
-_KEEP = []
 NAME = "ivit_attention_fused_i8_ibert_long"
 
 
-def dev(a):
-    t = torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-    _KEEP.append(t)
-    return t
-
-
-@pytest.fixture(autouse=True)
-def _release():
-    yield
-    torch.cuda.synchronize()
-    _KEEP.clear()
-
-
-def st():
-    return _lib.stream_ptr()
-
-
 def _run(qkv, ms, es, mo, eo, tab, band, blocks):
-    _, B, H, T, hd = qkv.shape
-    M, C = B * T, H * hd
-    bandt, bw = None, 0
-    if band:
-        bt, bw = shiftexp_band(tab.view(np.uint32))
-        assert bw and 16 <= bw <= 128
-        bandt = dev(bt.view(np.float32).reshape(-1))
-    rows = (M + 15) // 16 * 16 if blocks else M
-    out = torch.full((rows, C), 99, dtype=torch.int8, device=DEV)
-    _lib.call("ivit_attention_fused_i8_ibert_long", _lib.ptr(dev(qkv)), _lib.ptr(out), B, H, T, hd, int(ms[0]), int(es[0]), int(mo[0]),
-              int(eo[0]), _lib.ptr(dev(tab.reshape(-1))), _lib.ptr(bandt), bw, int(blocks), st())
-    if blocks:
-        rm = torch.empty((M, C), dtype=torch.int8, device=DEV)
-        _lib.call("ivit_untile_operand_i8", _lib.ptr(out), M, C, _lib.ptr(rm), C, st())
-        out = rm
-    torch.cuda.synchronize()
-    return out[:M].cpu().numpy().astype(np.int32).reshape(B, T, C)
+    return A.run_ibert(NAME, qkv, ms, es, mo, eo, tab, band, blocks)
 
 
 # (B, H, T, score multiplier, band form, block-layout output).  s_mult 1: Ms a power of two (float32 requantisation of the scores),

@@ -10,66 +10,18 @@ pytestmark = pytest.mark.gpu
 
 ivit = pytest.importorskip("ivit_amd")
 from ivit_amd import _lib  # noqa: E402
-from ivit_amd.prepare import dyadic, shiftexp2d, shiftexp_band  # noqa: E402
+from ivit_amd.prepare import dyadic  # noqa: E402
 import ivit_amd.quantization_utils as q  # noqa: E402
-
-DEV = "cuda:0"
-_KEEP = []
-
-
-def dev(a):
-    t = torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-    _KEEP.append(t)
-    return t
-
-
-@pytest.fixture(autouse=True)
-def _release():
-    yield
-    torch.cuda.synchronize()
-    _KEEP.clear()
-
-
-def st():
-    return _lib.stream_ptr()
+import attention_ref as A  # noqa: E402
+from attention_ref import DEV, release, st  # noqa: E402,F401  (release: the autouse fixture)
 
 
 def _expected(qkv, ms, es, s_at, mo, eo, compat):
-    _, B, H, T, hd = qkv.shape
-    exp = np.empty((B, T, H * hd), np.int32)
-    for b in range(B):
-        for h in range(H):
-            S = orc.gemm_i8(qkv[0, b, h], qkv[1, b, h])
-            ka = orc.requant(S, ms.astype(np.float64), es, 8)
-            P = orc.shiftmax_compat(ka, s_at) if compat else orc.shiftmax(ka, s_at)
-            assert P.max() <= 127
-            O = orc.gemm_i8(P.astype(np.int8), qkv[2, b, h], transB=False)
-            exp[b, :, h * hd:(h + 1) * hd] = orc.requant(O, mo.astype(np.float64), eo, 8)
-    return exp
+    return A.expected(qkv, s_at, ms, es, mo, eo, compat, 8, pmax=127)[0]
 
 
 def _run(qkv, ms, es, s_at, mo, eo, form, blocks):
-    _, B, H, T, hd = qkv.shape
-    M, C = B * T, H * hd
-    exp2d, band, bw = None, None, 0
-    if form != "pow2":
-        tab = shiftexp2d(s_at)
-        if form == "band":
-            bt, bw = shiftexp_band(tab)
-            assert 16 <= bw <= 256
-            band = dev(bt.view(np.int32))
-        else:
-            exp2d = dev(tab.view(np.int32))
-    rows = (M + 15) // 16 * 16 if blocks else M
-    out = torch.full((rows, C), 99, dtype=torch.int8, device=DEV)
-    _lib.call("ivit_attention_fused_i8_long", _lib.ptr(dev(qkv)), _lib.ptr(out), B, H, T, hd, int(ms[0]), int(es[0]), float(s_at),
-              int(mo[0]), int(eo[0]), _lib.ptr(exp2d), _lib.ptr(band), bw, int(blocks), st())
-    if blocks:
-        rm = torch.empty((M, C), dtype=torch.int8, device=DEV)
-        _lib.call("ivit_untile_operand_i8", _lib.ptr(out), M, C, _lib.ptr(rm), C, st())
-        out = rm
-    torch.cuda.synchronize()
-    return out[:M].cpu().numpy().astype(np.int32).reshape(B, T, C)
+    return A.run("ivit_attention_fused_i8_long", qkv, s_at, ms, es, mo, eo, form, 8, blocks)
 
 
 # (B, H, T, score multiplier, Shiftmax regime, block-layout output).  s_mult 1: Ms a power of two (float32 requantisation of the
@@ -90,15 +42,7 @@ def test_attention_long_equals_oracle(B, H, T, s_mult, form, blocks):
     qkv[1, 0, 0] = np.clip(qkv[1, 0, 0], -20, 20)
     qkv[1, 0, 0, 17, :8] = 127
     natural = form != "pow2"
-    s_a1 = np.float32(0.0571 if natural else 2.0 ** -4)
-    s_S = np.float32(np.float32(np.float32(s_a1 * s_a1) * np.float32(0.125)) * np.float32(s_mult))
-    s_at = np.float32(0.0437 if natural else 2.0 ** -3)
-    s_pv = np.float32(np.float32(1 / 128.0) * s_a1)
-    s_a2 = np.float32(0.1173 if natural else 2.0 ** -3)
-    ms, es = dyadic(s_S, s_at)
-    mo, eo = dyadic(s_pv, s_a2)
-    if not natural:
-        assert ((int(ms[0]) & (int(ms[0]) - 1)) == 0) == (s_mult == 1.0)
+    s_at, ms, es, mo, eo = A.scales(natural, s_mult, 8)
     exp = _expected(qkv, ms, es, s_at, mo, eo, natural)
     got = _run(qkv, ms, es, s_at, mo, eo, form, blocks)
     assert np.array_equal(got, exp), f"{(got != exp).sum()} of {got.size} differ"

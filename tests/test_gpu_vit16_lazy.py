@@ -233,7 +233,7 @@ def test_other_width_patterns_equal_the_literal_path(widths):
 @pytest.mark.parametrize("widths", [W16, W16ALL], ids=["softmax8", "softmax16"])
 def test_collapsed_attention_range_keeps_the_literal_attention(widths):
     """an attention output range of 0 (every probability of the calibration images 0): the output multiplier s_pv / s_out is beyond
-    the long-row kernels' 512 (lazy._long_multipliers_ok), so no fused attention is launched, without an error, and the logits
+    the long-row kernels' 512 (engine_common.long_multipliers_ok), so no fused attention is launched, without an error, and the logits
     are the literal path's.  With 16-bit probabilities s_pv is 2^-15 * s_v and stays inside the bound at a calibrated value scale:
     the range of attn.qact1 is widened to 512 (s_v = 4) so that the multiplier is beyond it there, too"""
     model, g = _calibrated(384, 16, 128, 2, 2, False, 5, "ivit", widths, freeze=False)
