@@ -81,6 +81,7 @@ SIGNATURES = {
     "ivit_quantize_patchify_ld_f32_i8": [vp, vp, i64, ci, ci, ci, ci, f32, vp],
     "ivit_quantize_patchify_u8_i8": [vp, vp, i64, ci, ci, ci, ci, vp, vp],
     "ivit_minmax_f32": [vp, i64, vp, vp],
+    "ivit_quantile_pair_f32": [vp, i64, f32, f32, vp, vp, i64, vp],
     "ivit_shiftmax_i32_i8": [vp, i64, ci, ci, f32, vp, i64, vp],
     "ivit_requant_i8_i16": [vp, u32, i32, vp, i64, vp],
     "ivit_residual_requant_i16": [vp, ci, vp, vp, u32, i32, vp, u32, i32, vp, i64, ci, ci, ci, ci, ci, vp],
@@ -138,6 +139,8 @@ LAB_SIGNATURES = {
     "ivit_debug_set_stamp_buffer": [vp],
 }
 LAB_PATH = os.path.join(_HERE, "libivit_hip_lab.so")
+
+QUANTILE_WS_BYTES = 16640      # IVIT_QUANTILE_WS_BYTES of include/ivit_hip.h: the workspace of ivit_quantile_pair_f32
 
 
 class IvitError(RuntimeError):

@@ -34,8 +34,24 @@ _BW_KEYS = ("patch_embed_bw", "pos_encoding_bw", "block_input_bw", "attention_ou
             "norm2_in_bw", "att_block_out_bw")
 
 
-def calibrate_model(model, device, batches: Optional[Iterable[torch.Tensor]] = None, use_random_calibration: bool = False):
-    """Running-stat forward passes that initialise / update every QuantAct range (inference.py:33-91)."""
+def set_act_percentile(model, p):
+    """Set `percentile` on every QuantAct of `model` (the one inside IBERTIntSoftmax included): while its statistics run, each then
+    observes torch.quantile at (100 - p) / 2 and 100 - (100 - p) / 2 per cent of its flattened input instead of min / max
+    (quant_modules.py:319-329; ivit_quantile_pair_f32 on the device).  None restores min / max.  `percentile` is a plain attribute,
+    not a buffer: like the reference's it is not part of the state_dict, so a checkpoint does not carry it -- only the ranges it led to."""
+    from .quantization_utils.quant_modules import QuantAct
+    for m in model.modules():
+        if isinstance(m, QuantAct):
+            m.percentile = p
+    return model
+
+
+def calibrate_model(model, device, batches: Optional[Iterable[torch.Tensor]] = None, use_random_calibration: bool = False,
+                    act_percentile=None):
+    """Running-stat forward passes that initialise / update every QuantAct range (inference.py:33-91).  `act_percentile`: call
+    set_act_percentile(model, act_percentile) first (the attribute stays set afterwards and is never saved)."""
+    if act_percentile is not None:
+        set_act_percentile(model, act_percentile)
     model.eval()
     with torch.no_grad():
         if use_random_calibration:
@@ -80,9 +96,10 @@ def build_model(model_config: Optional[dict] = None, num_classes: int = 1000, ge
 
 def load_model(checkpoint_path, device="cuda", num_classes=1000, gelu_type=None, softmax_type=None, layernorm_type=None,
                bitwidth=None, calibration_batches: Optional[Iterable[torch.Tensor]] = None, strict_load=False,
-               use_random_calibration_warmup=False):
+               use_random_calibration_warmup=False, act_percentile=None):
     """inference.py:94-224: build from the saved configuration (arguments override it), load the weights, warm up the
-    quantisation ranges unless `strict_load`, freeze."""
+    quantisation ranges unless `strict_load`, freeze.  `act_percentile`: the warm-up observes percentiles instead of min / max
+    (set_act_percentile; an attribute of the modules, not a buffer, so no checkpoint holds it)."""
     checkpoint = torch.load(checkpoint_path, map_location="cpu", weights_only=False)
     has_cfg = isinstance(checkpoint, dict) and "model_config" in checkpoint
     model = build_model(checkpoint["model_config"] if has_cfg else None, num_classes, gelu_type, softmax_type,
@@ -95,6 +112,8 @@ def load_model(checkpoint_path, device="cuda", num_classes=1000, gelu_type=None,
             weights[name] = param.unsqueeze(0)   # scalar buffers of older checkpoints (:203-207)
     model.load_state_dict(weights, strict=strict_load)
     model.to(device)
+    if act_percentile is not None:
+        set_act_percentile(model, act_percentile)
     if not strict_load:
         if use_random_calibration_warmup:
             calibrate_model(model, device, use_random_calibration=True)

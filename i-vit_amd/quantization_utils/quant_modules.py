@@ -270,6 +270,24 @@ class QuantLinear(nn.Linear):
 
 
 # ----------------------------------------------------------------------------- QuantAct
+def percentile_qs(percentile):
+    """the two q of the reference's percentile mode (quant_modules.py:325-329), as the float32 torch.quantile makes of them"""
+    percentile_min = (100 - percentile) / 2
+    percentile_max = 100 - percentile_min
+    return float(f32(percentile_min / 100.0)), float(f32(percentile_max / 100.0))
+
+
+_QUANTILE_WS = {}
+
+
+def _quantile_workspace(device):
+    """ivit_quantile_pair_f32's workspace: one per device, reused by every observation (launches on one stream are ordered)"""
+    ws = _QUANTILE_WS.get(str(device))
+    if ws is None:
+        ws = _QUANTILE_WS[str(device)] = torch.empty(_lib.QUANTILE_WS_BYTES, dtype=torch.uint8, device=device)
+    return ws
+
+
 class QuantAct(nn.Module):
     """quant_modules.py:229-387 (fixedpoint_mul quant_utils.py:193-253; input mode :79-97)."""
 
@@ -298,11 +316,18 @@ class QuantAct(nn.Module):
         self.running_stat = True
 
     def _observe(self, x_act):
-        """calibration statistics (quant_modules.py:310-360): min / max by the HIP reduction, then the reference's
-        initialise / running-min-max / EMA update on the two scalars"""
+        """calibration statistics (quant_modules.py:310-360): min / max by the HIP reduction -- with `percentile` set, the two
+        quantiles by the HIP selection -- then the reference's initialise / running-min-max / EMA update on the two scalars"""
         xa = x_act.detach().contiguous().float()
         mm = torch.empty(2, dtype=torch.float32, device=xa.device)
-        _lib.call("ivit_minmax_f32", _lib.ptr(xa), xa.numel(), _lib.ptr(mm), _st())
+        if self.percentile is None:
+            _lib.call("ivit_minmax_f32", _lib.ptr(xa), xa.numel(), _lib.ptr(mm), _st())
+        else:
+            # percentile calibration (quant_modules.py:319-329): torch.quantile(x_flat, q) at the two ends, by exact selection
+            q_lo, q_hi = percentile_qs(self.percentile)
+            ws = _quantile_workspace(xa.device)
+            _lib.call("ivit_quantile_pair_f32", _lib.ptr(xa), xa.numel(), q_lo, q_hi, _lib.ptr(mm), _lib.ptr(ws),
+                      _lib.QUANTILE_WS_BYTES, _st())
         self._observe_update(mm[0], mm[1])
 
     def _observe_update(self, x_min, x_max):

@@ -44,6 +44,21 @@ const char* ivit_last_error_string(void);
  * out_min_max[0] = min, out_min_max[1] = max over x[0..n) (device float[2]; NaNs are skipped). */
 int ivit_minmax_f32(const float* x, int64_t n, float* out_min_max, ivit_stream_t stream);
 
+/* QuantAct with `percentile` set (quant_modules.py:319-329) observes torch.quantile(x_flat, q_lo) and torch.quantile(x_flat, q_hi)
+ * instead, q_lo = (100 - p) / 2 / 100, q_hi = (100 - (100 - p) / 2) / 100, rounded to float32 by the caller.
+ * out2[0], out2[1] (device float[2]) are those two values, default linear interpolation, bit for bit (a zero may carry either sign):
+ *   rank = fl32(q * fl32(n - 1)), lo = floor(rank), hi = ceil(rank), w = rank - lo, a / b = the lo-th / hi-th smallest element,
+ *   d = b - a, result = fma(w, d, a) if w < 0.5, else fma(-d, 1 - w, b)   (float32; the last product and sum are one fused
+ *   multiply-add, as in torch's lerp kernels; everything else is rounded on its own).
+ * A NaN anywhere in x makes both results NaN (torch's rule; ivit_minmax_f32 skips NaNs).  torch refuses n > 2^24; here 1 <= n < 2^31,
+ * with fl32(n - 1) rounded to nearest and both indices clamped to n - 1.
+ * Exact selection, not a sort: a radix select over an order-preserving 32-bit key, four passes over x, nothing read back.
+ * `workspace`: at least IVIT_QUANTILE_WS_BYTES device bytes, 4-byte aligned, any contents; cleared on the stream by the entry itself.
+ * x needs 4-byte alignment only. */
+#define IVIT_QUANTILE_WS_BYTES 16640
+int ivit_quantile_pair_f32(const float* x, int64_t n, float q_lo, float q_hi, float* out2, void* workspace, int64_t workspace_bytes,
+                           ivit_stream_t stream);
+
 /* ---- input quantisation ---------------------------------------------------------------
  * QuantAct input mode = SymmetricQuantFunction.forward (quant_utils.py:79-97,
  * linear_quantize :13-49):  q = clamp(round(inv_scale * x), -128, 127), inv_scale = fl(1/s)
