@@ -95,6 +95,7 @@ SIGNATURES = {
     "ivit_ibert_gelu_i32": [vp, i64, f32, f32, f32, vp, vp],
     "ivit_ibert_softmax_i32": [vp, i64, ci, ci, f32, f32, f32, f32, f32, u32, i32, ci, vp, i64, vp, vp],
     "ivit_ibert_layernorm_i32_f32": [vp, i64, ci, ci, vp, vp, f32, vp, i64, vp],
+    "ivit_ibert_layernorm_i32_f32_ex": [vp, i64, ci, ci, vp, vp, f32, vp, i64, ci, vp],
     "ivit_ibert_gelu_build_lut": [f32, f32, f32, f32, f32, u32, i32, vp, vp],
     "ivit_ibert_softmax_build_table": [f32, f32, f32, f32, f32, f32, u32, i32, vp, vp],
     "ivit_attention_fused_i8_ibert": [vp, vp, ci, ci, ci, ci, u32, i32, u32, i32, vp, vp, ci, ci, vp],
@@ -106,6 +107,7 @@ SIGNATURES = {
     "ivit_ibert_gelu_f32_f32": [vp, i64, f32, f32, f32, f32, f32, vp, vp],
     "ivit_ibert_softmax_f32_f32": [vp, i64, ci, ci, f32, f32, f32, f32, f32, f32, u32, i32, ci, vp, i64, vp, vp],
     "ivit_ibert_layernorm_f32_f32": [vp, i64, ci, ci, vp, ci, vp, vp, f32, vp, i64, vp],
+    "ivit_ibert_layernorm_f32_f32_ex": [vp, i64, ci, ci, vp, ci, vp, vp, f32, vp, i64, ci, vp],
     "ivit_window_attention_i8": [vp, vp, i64, vp, vp, ci, ci, ci, ci, ci, ci, u32, i32, u32, i32, f32, u32, i32, vp],
     "ivit_window_attention_i8_compat": [vp, vp, i64, vp, vp, ci, ci, ci, ci, ci, ci, u32, i32, u32, i32, f32, u32, i32, vp, vp, vp],
     "ivit_window_attention_i8_band": [vp, vp, i64, vp, vp, ci, ci, ci, ci, ci, u32, i32, u32, i32, f32, u32, i32, vp, ci, ci, ci, ci, ci, ci, vp],
@@ -137,6 +139,7 @@ LAB_SIGNATURES = {
     "ivit_debug_ln_stamp_buffer": [vp],
     "ivit_debug_attention": [ci],
     "ivit_debug_set_stamp_buffer": [vp],
+    "ivit_debug_ibert_integer_sqrt": [vp, i64, vp, vp],
 }
 LAB_PATH = os.path.join(_HERE, "libivit_hip_lab.so")
 

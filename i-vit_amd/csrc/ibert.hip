@@ -12,6 +12,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "isqrt.h"
 #include "rowsum.h"
 
 namespace {
@@ -118,6 +119,7 @@ struct IbLnArgs {
     int64_t ldo;
 };
 
+template <bool ISQ>
 __global__ __launch_bounds__(NT) void ibert_layernorm_kernel(IbLnArgs a)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -131,7 +133,7 @@ __global__ __launch_bounds__(NT) void ibert_layernorm_kernel(IbLnArgs a)
             return ys * ys;                                                   // :130 float32 square
         };
         const float var_int = torch_rowsum(sq, C, lane);                      // :131
-        const float std_int = floorf(sqrtf(var_int)) * a.shift_pow2;          // :142
+        const float std_int = ib_std_int<ISQ>(var_int, a.shift_pow2);          // :142-145
         const float factor = floorf(2147483648.0f / std_int);                 // :143
         float* orow = a.out + (int64_t)row * a.ldo;
         for (int c = lane; c < C; c += 64) {
@@ -272,7 +274,7 @@ struct IbLnI8Args {
 };
 
 // one row, literally (whole wave)
-template <typename TX = int8_t>
+template <typename TX = int8_t, bool ISQ = false>
 IVIT_DEV void ib_ln_row_literal(const IbLnI8Args& a, int row, int lane)
 {
     const int C = a.C;
@@ -285,7 +287,7 @@ IVIT_DEV void ib_ln_row_literal(const IbLnI8Args& a, int row, int lane)
             return ys * ys;                                                                   // :130
         };
         const float var_int = torch_rowsum(sq, C, lane);                                      // :131
-        const float std_int = floorf(sqrtf(var_int)) * a.shift_pow2;                          // :142
+        const float std_int = ib_std_int<ISQ>(var_int, a.shift_pow2);                          // :142-145
         const float factor = floorf(2147483648.0f / std_int);                                 // :143
         const BlockRow brow = block_row(row, C);
         for (int c = lane; c < C; c += 64) {
@@ -304,11 +306,11 @@ IVIT_DEV void ib_ln_row_literal(const IbLnI8Args& a, int row, int lane)
     }
 }
 
-template <typename TX>
+template <typename TX, bool ISQ>
 __global__ __launch_bounds__(NT) void ibert_layernorm_i8_kernel(IbLnI8Args a)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int row = blockIdx.x * WPB + wave; row < a.rows; row += gridDim.x * WPB) ib_ln_row_literal<TX>(a, row, lane);
+    for (int row = blockIdx.x * WPB + wave; row < a.rows; row += gridDim.x * WPB) ib_ln_row_literal<TX, ISQ>(a, row, lane);
 }
 
 // The same result without evaluating the two float32 row sums term by term.  Both sums only feed a rounding:
@@ -320,7 +322,7 @@ __global__ __launch_bounds__(NT) void ibert_layernorm_i8_kernel(IbLnI8Args a)
 //     deep): floor(sqrt) is decided unless sqrt(V) is that close to an integer.
 // Undecided rows (and std = 0) take ib_ln_row_literal.  Element steps are the literal float32 operations on phi(q) from a
 // 256-entry table; the QuantAct's z = round(fl(fl(v * s) / s)) equals v for |v| < 2^21 (two roundings: error < 0.25).
-template <int NJ>
+template <int NJ, bool ISQ>
 __global__ __launch_bounds__(NT, 4) void ibert_layernorm_i8_fast_kernel(IbLnI8Args a)
 {
     __shared__ float tphi[256];
@@ -376,7 +378,7 @@ __global__ __launch_bounds__(NT, 4) void ibert_layernorm_i8_fast_kernel(IbLnI8Ar
         const float m0 = (float)sq / (float)C;
         const float fr = m0 - floorf(m0);
         if (fabsf(fr - 0.5f) < 2.2e-3f) {                 // wave-uniform
-            ib_ln_row_literal(a, row, lane);
+            ib_ln_row_literal<int8_t, ISQ>(a, row, lane);
             continue;
         }
         const float mean_int = rintf(m0);
@@ -401,14 +403,18 @@ __global__ __launch_bounds__(NT, 4) void ibert_layernorm_i8_fast_kernel(IbLnI8Ar
         V = wave_reduce_sum_i32(V);
         bool ok = V > 0;
         if (V >= (1 << 24)) {
-            const double r = __builtin_sqrt((double)V);
-            ok = __builtin_floor(r * (1.0 - 3e-6)) == __builtin_floor(r * (1.0 + 3e-6));
+            if constexpr (ISQ) {
+                ok = false;     // integer_sqrt is a function of the float32 S2 itself (not monotonic in it): decided only where S2 == V
+            } else {
+                const double r = __builtin_sqrt((double)V);
+                ok = __builtin_floor(r * (1.0 - 3e-6)) == __builtin_floor(r * (1.0 + 3e-6));
+            }
         }
         if (!ok) {
-            ib_ln_row_literal(a, row, lane);
+            ib_ln_row_literal<int8_t, ISQ>(a, row, lane);
             continue;
         }
-        const float std_int = floorf(sqrtf((float)V)) * a.shift_pow2;             // :142
+        const float std_int = ib_std_int<ISQ>((float)V, a.shift_pow2);            // :142-145
         const float factor = floorf(2147483648.0f / std_int);                    // :143
         const BlockRow brow = block_row(row, C);
         unsigned unc = 0;
@@ -431,7 +437,7 @@ __global__ __launch_bounds__(NT, 4) void ibert_layernorm_i8_fast_kernel(IbLnI8Ar
                 else *reinterpret_cast<int*>(a.out + (int64_t)row * a.ldo + 4 * d) = pw;
             }
         }
-        if (__builtin_amdgcn_ballot_w64(unc != 0) != 0) ib_ln_row_literal(a, row, lane);   // wave-uniform, rare
+        if (__builtin_amdgcn_ballot_w64(unc != 0) != 0) ib_ln_row_literal<int8_t, ISQ>(a, row, lane);   // wave-uniform, rare
     }
 }
 
@@ -486,7 +492,7 @@ IVIT_DEV float torch_rowsum_regs(const float (&own)[NK], int lane)
 
 // FASTDIV: x / s_in by the 3-instruction quotient q0 = x * r, e = fma(-s, q0, x), fma(e, r, q0) with r = RN(1 / s_in) -- correctly
 // rounded for every 16-bit q at this s_in, which the host checked exhaustively (prepare.markstein_division_ok) before asking for it.
-template <int NK, bool FASTDIV>
+template <int NK, bool FASTDIV, bool ISQ>
 __global__ __launch_bounds__(NT) void ibert_layernorm_i16_fast_kernel(IbLnI8Args a, float r_in)
 {
     const int C = a.C;     // == 64 NK
@@ -533,9 +539,9 @@ __global__ __launch_bounds__(NT) void ibert_layernorm_i16_fast_kernel(IbLnI8Args
             sq[k] = ys * ys;                                                                   // :130
         }
         const float var_int = torch_rowsum_regs<NK>(sq, lane);                                // :131
-        const float std_int = floorf(sqrtf(var_int)) * a.shift_pow2;                           // :142
+        const float std_int = ib_std_int<ISQ>(var_int, a.shift_pow2);                           // :142-145
         if (!(std_int > 0.0f)) {                           // wave-uniform
-            ib_ln_row_literal<int16_t>(a, row, lane);
+            ib_ln_row_literal<int16_t, ISQ>(a, row, lane);
             continue;
         }
         const float factor = floorf(2147483648.0f / std_int);                                 // :143
@@ -550,7 +556,7 @@ __global__ __launch_bounds__(NT) void ibert_layernorm_i16_fast_kernel(IbLnI8Args
             unc |= (tl != th) ? 1u : 0u;                                                     // uncertified: the row is redone literally
             orow[lane + 64 * k] = (int8_t)clamp_i32(tl, 0x4B400000 - 128, 0x4B400000 + 127);
         }
-        if (__builtin_amdgcn_ballot_w64(unc != 0) != 0) ib_ln_row_literal<int16_t>(a, row, lane);   // wave-uniform, rare
+        if (__builtin_amdgcn_ballot_w64(unc != 0) != 0) ib_ln_row_literal<int16_t, ISQ>(a, row, lane);   // wave-uniform, rare
     }
 }
 
@@ -567,6 +573,7 @@ struct IbLnLitArgs {
     int64_t ldo;
 };
 
+template <bool ISQ>
 __global__ __launch_bounds__(NT) void ibert_layernorm_f32_kernel(IbLnLitArgs a)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -580,7 +587,7 @@ __global__ __launch_bounds__(NT) void ibert_layernorm_f32_kernel(IbLnLitArgs a)
             return ys * ys;                                                                   // :130
         };
         const float var_int = torch_rowsum(sq, C, lane);                                      // :131
-        const float std_int = floorf(sqrtf(var_int)) * a.shift_pow2;                          // :142
+        const float std_int = ib_std_int<ISQ>(var_int, a.shift_pow2);                          // :142-145
         const float factor = floorf(2147483648.0f / std_int);                                 // :143
         float* orow = a.out + (int64_t)row * a.ldo;
         for (int c = lane; c < C; c += 64) {
@@ -627,11 +634,21 @@ IVIT_EXPORT int ivit_ibert_layernorm_i32_f32(const int32_t* k, int64_t ldx, int 
                                              const float* s_out, float shift_pow2, float* out, int64_t ldo,
                                              ivit_stream_t stream)
 {
+    return ivit_ibert_layernorm_i32_f32_ex(k, ldx, rows, C, bias_int, s_out, shift_pow2, out, ldo, 0, stream);
+}
+
+IVIT_EXPORT int ivit_ibert_layernorm_i32_f32_ex(const int32_t* k, int64_t ldx, int rows, int C, const float* bias_int,
+                                                const float* s_out, float shift_pow2, float* out, int64_t ldo, int flags,
+                                                ivit_stream_t stream)
+{
     IVIT_REQUIRE(k && out && bias_int && s_out && rows > 0 && C > 0 && ldx >= C && ldo >= C,
                  "ivit_ibert_layernorm_i32_f32: bad operand");
     IVIT_REQUIRE(shift_pow2 >= 1.0f, "ivit_ibert_layernorm_i32_f32: shift_pow2 = 2^shift must be >= 1");
+    IVIT_REQUIRE((flags & ~IVIT_IBERT_LN_INT_SQRT) == 0, "ivit_ibert_layernorm_i32_f32: unknown flags %d", flags);
     IbLnArgs a{k, ldx, rows, C, bias_int, s_out, shift_pow2, out, ldo};
-    hipLaunchKernelGGL(ibert_layernorm_kernel, dim3(grid_for_rows(rows)), dim3(NT), 0, ivit_stream(stream), a);
+    const dim3 grid(grid_for_rows(rows)), blk(NT);
+    if (flags & IVIT_IBERT_LN_INT_SQRT) hipLaunchKernelGGL(ibert_layernorm_kernel<true>, grid, blk, 0, ivit_stream(stream), a);
+    else hipLaunchKernelGGL(ibert_layernorm_kernel<false>, grid, blk, 0, ivit_stream(stream), a);
     IVIT_CHECK_LAUNCH("ivit_ibert_layernorm_i32_f32");
 }
 
@@ -668,11 +685,21 @@ IVIT_EXPORT int ivit_ibert_layernorm_f32_f32(const float* x, int64_t ldx, int ro
                                              const float* bias_int, const float* s_out, float shift_pow2, float* out,
                                              int64_t ldo, ivit_stream_t stream)
 {
+    return ivit_ibert_layernorm_f32_f32_ex(x, ldx, rows, C, s_in, n_s, bias_int, s_out, shift_pow2, out, ldo, 0, stream);
+}
+
+IVIT_EXPORT int ivit_ibert_layernorm_f32_f32_ex(const float* x, int64_t ldx, int rows, int C, const float* s_in, int n_s,
+                                                const float* bias_int, const float* s_out, float shift_pow2, float* out,
+                                                int64_t ldo, int flags, ivit_stream_t stream)
+{
     IVIT_REQUIRE(x && s_in && out && bias_int && s_out && rows > 0 && C > 0 && ldx >= C && ldo >= C && (n_s == 1 || n_s == C),
                  "ivit_ibert_layernorm_f32_f32: bad operand");
     IVIT_REQUIRE(shift_pow2 >= 1.0f, "ivit_ibert_layernorm_f32_f32: shift_pow2 = 2^shift must be >= 1");
+    IVIT_REQUIRE((flags & ~IVIT_IBERT_LN_INT_SQRT) == 0, "ivit_ibert_layernorm_f32_f32: unknown flags %d", flags);
     IbLnLitArgs a{x, ldx, rows, C, s_in, n_s, bias_int, s_out, shift_pow2, out, ldo};
-    hipLaunchKernelGGL(ibert_layernorm_f32_kernel, dim3(grid_for_rows(rows)), dim3(NT), 0, ivit_stream(stream), a);
+    const dim3 grid(grid_for_rows(rows)), blk(NT);
+    if (flags & IVIT_IBERT_LN_INT_SQRT) hipLaunchKernelGGL(ibert_layernorm_f32_kernel<true>, grid, blk, 0, ivit_stream(stream), a);
+    else hipLaunchKernelGGL(ibert_layernorm_f32_kernel<false>, grid, blk, 0, ivit_stream(stream), a);
     IVIT_CHECK_LAUNCH("ivit_ibert_layernorm_f32_f32");
 }
 
@@ -700,6 +727,8 @@ IVIT_EXPORT int ivit_ibert_layernorm_i8(const int8_t* x, int64_t ldx, int rows, 
                                         const float* s_out, float shift_pow2, const uint32_t* m, const int32_t* e, int8_t* out,
                                         int64_t ldo, int out_blocks, ivit_stream_t stream)
 {
+    const bool isq = (out_blocks & IVIT_IBERT_LN_INT_SQRT) != 0;     // the one flag above the layout choice
+    out_blocks &= ~IVIT_IBERT_LN_INT_SQRT;
     IVIT_REQUIRE(x && out && bias_int && s_out && m && e && rows > 0 && C > 0 && ldx >= C && ldo >= C && s_in > 0.0f,
                  "ivit_ibert_layernorm_i8: bad operand");
     IVIT_REQUIRE(shift_pow2 >= 1.0f, "ivit_ibert_layernorm_i8: shift_pow2 = 2^shift must be >= 1");
@@ -715,13 +744,20 @@ IVIT_EXPORT int ivit_ibert_layernorm_i8(const int8_t* x, int64_t ldx, int rows, 
         const int want = grid_for_rows(rows);
         const dim3 grid(want < 1024 ? want : 1024), blk(NT);
         hipStream_t st = ivit_stream(stream);
-        if (nj <= 1) hipLaunchKernelGGL(ibert_layernorm_i8_fast_kernel<1>, grid, blk, lds, st, a);
-        else if (nj <= 2) hipLaunchKernelGGL(ibert_layernorm_i8_fast_kernel<2>, grid, blk, lds, st, a);
-        else if (nj <= 3) hipLaunchKernelGGL(ibert_layernorm_i8_fast_kernel<3>, grid, blk, lds, st, a);
-        else hipLaunchKernelGGL(ibert_layernorm_i8_fast_kernel<4>, grid, blk, lds, st, a);
+#define IB_LN8(NJv)                                                                                            \
+    do {                                                                                                       \
+        if (isq) hipLaunchKernelGGL((ibert_layernorm_i8_fast_kernel<NJv, true>), grid, blk, lds, st, a);        \
+        else hipLaunchKernelGGL((ibert_layernorm_i8_fast_kernel<NJv, false>), grid, blk, lds, st, a);           \
+    } while (0)
+        if (nj <= 1) IB_LN8(1);
+        else if (nj <= 2) IB_LN8(2);
+        else if (nj <= 3) IB_LN8(3);
+        else IB_LN8(4);
+#undef IB_LN8
         IVIT_CHECK_LAUNCH("ivit_ibert_layernorm_i8");
     }
-    hipLaunchKernelGGL(ibert_layernorm_i8_kernel<int8_t>, dim3(grid_for_rows(rows)), dim3(NT), 0, ivit_stream(stream), a);
+    if (isq) hipLaunchKernelGGL((ibert_layernorm_i8_kernel<int8_t, true>), dim3(grid_for_rows(rows)), dim3(NT), 0, ivit_stream(stream), a);
+    else hipLaunchKernelGGL((ibert_layernorm_i8_kernel<int8_t, false>), dim3(grid_for_rows(rows)), dim3(NT), 0, ivit_stream(stream), a);
     IVIT_CHECK_LAUNCH("ivit_ibert_layernorm_i8");
 }
 
@@ -736,6 +772,8 @@ IVIT_EXPORT int ivit_ibert_layernorm_i16_i8_ex(const int16_t* x, int64_t ldx, in
                                                const float* s_out, float shift_pow2, const uint32_t* m, const int32_t* e, int8_t* out,
                                                int64_t ldo, int fast_division, ivit_stream_t stream)
 {
+    const bool isq = (fast_division & IVIT_IBERT_LN_INT_SQRT) != 0;  // the one flag above the division choice
+    fast_division &= ~IVIT_IBERT_LN_INT_SQRT;
     IVIT_REQUIRE(x && out && bias_int && s_out && m && e && rows > 0 && C > 0 && ldx >= C && ldo >= C && s_in > 0.0f,
                  "ivit_ibert_layernorm_i16_i8: bad operand");
     IVIT_REQUIRE(shift_pow2 >= 1.0f, "ivit_ibert_layernorm_i16_i8: shift_pow2 = 2^shift must be >= 1");
@@ -745,14 +783,35 @@ IVIT_EXPORT int ivit_ibert_layernorm_i16_i8_ex(const int16_t* x, int64_t ldx, in
     const float r_in = 1.0f / s_in;
 #define IB_LN16(NKv)                                                                                                   \
     do {                                                                                                               \
-        if (fast_division) hipLaunchKernelGGL((ibert_layernorm_i16_fast_kernel<NKv, true>), grid, blk, 0, st, a, r_in); \
-        else hipLaunchKernelGGL((ibert_layernorm_i16_fast_kernel<NKv, false>), grid, blk, 0, st, a, r_in);              \
+        if (fast_division && isq) hipLaunchKernelGGL((ibert_layernorm_i16_fast_kernel<NKv, true, true>), grid, blk, 0, st, a, r_in);  \
+        else if (fast_division) hipLaunchKernelGGL((ibert_layernorm_i16_fast_kernel<NKv, true, false>), grid, blk, 0, st, a, r_in);   \
+        else if (isq) hipLaunchKernelGGL((ibert_layernorm_i16_fast_kernel<NKv, false, true>), grid, blk, 0, st, a, r_in);            \
+        else hipLaunchKernelGGL((ibert_layernorm_i16_fast_kernel<NKv, false, false>), grid, blk, 0, st, a, r_in);                    \
     } while (0)
     if (C == 192) IB_LN16(3);
     else if (C == 384) IB_LN16(6);
     else if (C == 768) IB_LN16(12);
     else if (C == 1024) IB_LN16(16);
-    else hipLaunchKernelGGL(ibert_layernorm_i8_kernel<int16_t>, grid, blk, 0, st, a);
+    else if (isq) hipLaunchKernelGGL((ibert_layernorm_i8_kernel<int16_t, true>), grid, blk, 0, st, a);
+    else hipLaunchKernelGGL((ibert_layernorm_i8_kernel<int16_t, false>), grid, blk, 0, st, a);
 #undef IB_LN16
     IVIT_CHECK_LAUNCH("ivit_ibert_layernorm_i16_i8");
 }
+
+#if IVIT_LAB
+// lab build only (include/ivit_hip_debug.h): ib_integer_sqrt on an array, the one way to put chosen values of the float32 row sum
+// in front of the device function
+namespace {
+__global__ __launch_bounds__(NT) void ibert_integer_sqrt_kernel(const float* n, int64_t count, int32_t* out)
+{
+    for (int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x; i < count; i += (int64_t)gridDim.x * NT) out[i] = ib_integer_sqrt(n[i]);
+}
+}  // namespace
+
+IVIT_EXPORT int ivit_debug_ibert_integer_sqrt(const float* n, int64_t count, int32_t* out, void* stream)
+{
+    IVIT_REQUIRE(n && out && count > 0, "ivit_debug_ibert_integer_sqrt: bad operand");
+    hipLaunchKernelGGL(ibert_integer_sqrt_kernel, dim3(ew_grid(count)), dim3(NT), 0, ivit_stream(stream), n, count, out);
+    IVIT_CHECK_LAUNCH("ivit_debug_ibert_integer_sqrt");
+}
+#endif

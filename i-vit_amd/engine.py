@@ -39,7 +39,7 @@ class IntViTEngine(EngineBase):
 
     def __init__(self, float_state=None, ranges=None, embed_dim: int = 768, depth: int = 12, num_heads: int = 12,
                  device="cuda:0", max_batch: int = 256, source=None, family: str = "ivit", stream_bits: int = 8,
-                 softmax_bits: int = 8, pos_bits: int = 8, img_size: int = 224, patch_size: int = 16):
+                 softmax_bits: int = 8, pos_bits: int = 8, img_size: int = 224, patch_size: int = 16, int_sqrt: bool = False):
         """float_state: name -> float32 array (the reference's state_dict names, SURVEY Appendix D);
         ranges: QuantAct name -> (x_min, x_max) of the frozen model.  Alternatively `source`: any object with the
         FloatSource interface of export.py (e.g. export.ExportSource: integer parameters + scale table, no floats)."""
@@ -59,6 +59,11 @@ class IntViTEngine(EngineBase):
         if family not in ("ivit", "ibert"):
             raise ValueError(f"operator family {family!r}: the fused engine implements 'ivit' and 'ibert'")
         self.family = family
+        # IBERTIntLayerNorm(use_int_sqrt=True) (layernorm_type 'ibert_use-int-sqrt_true'): norm1, norm2 and the final norm of the
+        # model take std from integer_sqrt (ibert_modules.py:85-109, 143), on the 8- and on the 16-bit stream
+        if int_sqrt and family != "ibert":
+            raise ValueError("int_sqrt (use_int_sqrt) is a parameter of the 'ibert' LayerNorm")
+        self.int_sqrt = bool(int_sqrt)
         # width of the residual stream and of the QuantActs that feed it (vit_quant.py:180-187): 8, or 16 = patch_embed_bw,
         # block_input_bw, attention_out_bw, mlp_out_bw, norm2_in_bw, att_block_out_bw all 16 (softmax_bw, pos_encoding_bw 8): the
         # GEMM operands stay int8, the stream and the projection / fc2 outputs are int16 (the kernels of the Swin engine)
@@ -98,7 +103,7 @@ class IntViTEngine(EngineBase):
                     shift = float(np.asarray(source.tensor(prefix + ".shift")).reshape(-1)[0])
                 except KeyError:
                     shift = 0.0
-            return self._ln_spec(source.layernorm(prefix, s_out), s_in, sb, shift)
+            return self._ln_spec(source.layernorm(prefix, s_out), s_in, sb, shift, self.int_sqrt)
 
         def ranges_of(name):
             if ranges is None or name not in ranges:

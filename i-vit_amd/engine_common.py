@@ -50,15 +50,22 @@ def frag_copy(W: torch.Tensor, st, order16: bool = True, narrow: bool = True):
 
 
 # ----------------------------------------------------------------------------------------------------------- LayerNorm
-def ln_spec(lp, upload, s_in, bits: int, ibert_shift=None) -> dict:
+IBERT_LN_INT_SQRT = 0x100     # IVIT_IBERT_LN_INT_SQRT of include/ivit_hip.h
+
+
+def ln_spec(lp, upload, s_in, bits: int, ibert_shift=None, int_sqrt: bool = False) -> dict:
     """Device constants of one LayerNorm (prepare.LayerNormParams `lp`) on a `bits`-wide input of scale s_in, with its
     `kind`: "i8" / "i16" (I-LayerNorm on integers); "i8_compat" / "i16_compat" (natural input scale: the reference's
     operator sees fl(fl(q * s_in) / s_in), not q -- the table form on 8 bits, the literal / Markstein-quotient form on 16);
     "ibert_i8" / "ibert_i16" (ibert_shift given: IBERTIntLayerNorm, the same per-channel constants plus its overflow shift
-    buffer, ibert_modules.py:134-153; the kernel works on fl(q * s_in) literally)."""
+    buffer, ibert_modules.py:134-153; the kernel works on fl(q * s_in) literally; int_sqrt: its use_int_sqrt = True form, std from
+    integer_sqrt, carried as `flags` = IVIT_IBERT_LN_INT_SQRT)."""
+    if int_sqrt and ibert_shift is None:
+        raise ValueError("int_sqrt is a parameter of IBERTIntLayerNorm (ibert_shift)")
     d = dict(bias=upload(lp.bias_int), s=upload(lp.s_ln), m=upload(lp.m.view(np.int32)), e=upload(lp.e))
     if ibert_shift is not None:
-        d.update(kind=f"ibert_i{bits}", s_in=float(s_in), shift_pow2=float(2.0 ** ibert_shift))
+        d.update(kind=f"ibert_i{bits}", s_in=float(s_in), shift_pow2=float(2.0 ** ibert_shift),
+                 flags=IBERT_LN_INT_SQRT if int_sqrt else 0)
         if bits == 16:
             d["fast_div"] = int(markstein_division_ok(s_in, 16))
     elif phi_is_identity(s_in, bits):
@@ -87,10 +94,10 @@ def layernorm(ln, x, ldx, rows, C, out, ldo, st, blocks=None, H=0, W=0, ws=0, sh
                   int(blocks or 0) | (outer << 8), st)
     elif kind == "ibert_i8":
         _lib.call("ivit_ibert_layernorm_i8", p(x), ldx, rows, C, ln["s_in"], bias, s, ln["shift_pow2"], m, e, p(out), ldo,
-                  int(blocks or 0), st)
+                  int(blocks or 0) | ln["flags"], st)
     elif kind == "ibert_i16":
         _lib.call("ivit_ibert_layernorm_i16_i8_ex", p(x), ldx, rows, C, ln["s_in"], bias, s, ln["shift_pow2"], m, e, p(out), ldo,
-                  ln["fast_div"], st)
+                  ln["fast_div"] | ln["flags"], st)
     elif kind == "i16_compat":
         _lib.call("ivit_layernorm_i16_i8_compat", p(x), rows, C, ln["s_in"], ln["fast_div"] | (outer << 8), bias, s, m, e, p(out),
                   ldo, H, W, ws, shift, st)
@@ -203,8 +210,8 @@ class EngineBase(GraphReplay, HeadTopK):
     def _upload(self, a):
         return torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)
 
-    def _ln_spec(self, lp, s_in, bits, ibert_shift=None):
-        d = ln_spec(lp, self._upload, s_in, bits, ibert_shift)
+    def _ln_spec(self, lp, s_in, bits, ibert_shift=None, int_sqrt=False):
+        d = ln_spec(lp, self._upload, s_in, bits, ibert_shift, int_sqrt)
         self.natural_sites += int(d["kind"].endswith("_compat"))
         return d
 

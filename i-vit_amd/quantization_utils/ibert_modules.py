@@ -17,6 +17,7 @@ import torch.nn as nn
 from .. import _lib
 from ..prepare import EPS32, dyadic, f32
 from . import lazy
+from ..engine_common import IBERT_LN_INT_SQRT
 from .quant_modules import QuantAct, _dev_table, _st, to_float, to_int32
 
 
@@ -63,9 +64,9 @@ class IBERTIntLayerNorm(nn.Module):
                  force_dequant="none", elementwise_affine=True, eps=1e-5, use_int_sqrt=False):
         super().__init__()
         _check_mode(quant_mode, force_dequant, "layernorm")
-        if use_int_sqrt:
-            raise NotImplementedError("IBERT layernorm: use_int_sqrt=True (Newton integer sqrt) is not implemented")
-        self.quant_mode, self.overflow_handling, self.use_int_sqrt = quant_mode, overflow_handling, use_int_sqrt
+        # use_int_sqrt: std_int = integer_sqrt(var_int) * 2^shift (:85-109, 143 -- four float32 Newton steps, csrc/isqrt.h) instead of
+        # floor(sqrt(var_int)) * 2^shift (:145)
+        self.quant_mode, self.overflow_handling, self.use_int_sqrt = quant_mode, overflow_handling, bool(use_int_sqrt)
         self.register_buffer("shift", torch.zeros(1))
         self.output_bit, self.dim_sqrt, self.eps = output_bit, None, eps
         if isinstance(normalized_shape, int):
@@ -121,6 +122,10 @@ class IBERTIntLayerNorm(nn.Module):
         # the literal kernel: x / scaling_factor, float32 mean and variance sums in torch's reduction order, ... (:126-153) for
         # any input scale (csrc/ibert.hip, second half)
         out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+        if self.use_int_sqrt:
+            _lib.call("ivit_ibert_layernorm_f32_f32_ex", _lib.ptr(xin), C, xin.numel() // C, C, _lib.ptr(s_in), s_in.numel(),
+                      _lib.ptr(bias_int), _lib.ptr(s_out), float(2.0 ** float(self.shift)), _lib.ptr(out), C, IBERT_LN_INT_SQRT, _st())
+            return out, s_out
         _lib.call("ivit_ibert_layernorm_f32_f32", _lib.ptr(xin), C, xin.numel() // C, C, _lib.ptr(s_in), s_in.numel(),
                   _lib.ptr(bias_int), _lib.ptr(s_out), float(2.0 ** float(self.shift)), _lib.ptr(out), C, _st())
         return out, s_out

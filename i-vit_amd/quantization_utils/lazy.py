@@ -1103,8 +1103,9 @@ def _layernorm(ln, x, s_in, s_out, bits, device, outer=0, ibert=False):
     int8: engine_common's ln_spec, cached per weights, scales and device, and its launcher.  None outside the kernels' contract"""
     def build():
         lp = LayerNormParams(ln.weight.detach().cpu().numpy(), ln.bias.detach().cpu().numpy(), s_out)
-        return ln_spec(lp, lambda a: _dev(a, device), s_in[0], bits, float(ln.shift.reshape(-1)[0]) if ibert else None)
-    key = ("ibln", id(ln.shift), ln.shift._version) if ibert else ("ln", bits)
+        return ln_spec(lp, lambda a: _dev(a, device), s_in[0], bits, float(ln.shift.reshape(-1)[0]) if ibert else None,
+                       int_sqrt=ibert and bool(ln.use_int_sqrt))
+    key = ("ibln", id(ln.shift), ln.shift._version, bool(ln.use_int_sqrt)) if ibert else ("ln", bits)
     try:
         spec = _cache(ln, key + (ln.weight._version, ln.bias._version, _key(s_in, s_out), str(device)), build)
     except ValueError:
@@ -1127,7 +1128,8 @@ def _resolve_ln(node, s_out, device):
 
 def _resolve_ibert_ln(node, s_out, device):
     """IBERTIntLayerNorm (ibert_modules.py:126-153) + the QuantAct behind it on int8 or on the int16 stream: ivit_ibert_layernorm_i8 /
-    ivit_ibert_layernorm_i16_i8_ex (csrc/ibert.hip), which work on fl(q * s_in) literally -- any input scale"""
+    ivit_ibert_layernorm_i16_i8_ex (csrc/ibert.hip), which work on fl(q * s_in) literally -- any input scale; the module's
+    use_int_sqrt goes with the launch as IVIT_IBERT_LN_INT_SQRT"""
     ln, x = node.mod, node.inputs[0]
     xq = q8_contig(x)
     bits = 8

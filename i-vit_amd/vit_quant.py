@@ -18,6 +18,7 @@ from .dispatch import EngineDispatch
 from .layers_quant import DropPath, Mlp, PatchEmbed, trunc_normal_
 from .quantization_utils import (QuantAct, QuantLinear, QuantMatMul, get_gelu, get_layernorm, get_softmax)
 from .quantization_utils import lazy
+from .quantization_utils.layer_selection import _parse_layer_name
 
 __all__ = ["deit_tiny_patch16_224", "deit_small_patch16_224", "deit_base_patch16_224", "vit_base_patch16_224",
            "vit_large_patch16_224", "VisionTransformer"]
@@ -98,7 +99,10 @@ class VisionTransformer(EngineDispatch, nn.Module):
         self.num_features = self.embed_dim = embed_dim
         self.depth, self.num_heads = depth, num_heads
         self.geometry = (img_size, patch_size, in_chans, float(mlp_ratio), bool(qkv_bias), qk_scale)
-        self.op_types = (str(gelu_type).lower(), str(softmax_type).lower(), str(layernorm_type).lower())
+        # 'base_arg_value...' names (layer_selection.py): the family is the base name; the constructor parameters are kept beside it
+        parsed = [_parse_layer_name(str(t)) for t in (gelu_type, softmax_type, layernorm_type)]
+        self.op_types = tuple(base for base, _ in parsed)
+        self.op_params = tuple(params for _, params in parsed)
         gelu_layer, softmax_cls, norm_layer = get_gelu(gelu_type), get_softmax(softmax_type), get_layernorm(layernorm_type)
 
         self.qact_input = QuantAct()
@@ -152,10 +156,28 @@ class VisionTransformer(EngineDispatch, nn.Module):
         return self.pre_logits(x), s
 
     # ---------------------------------------------------------------- fused engine path (dispatch.py)
-    def engine_unsupported_reason(self):
-        """None when the fused int8 engine computes exactly what this module tree would; else why not."""
+    def _operator_reason(self):
+        """None when the fused engine and the integer-carrying module path (lazy.scope) implement this choice of operators: all
+        three 'ivit' or all three 'ibert', no constructor parameter in a name but the I-BERT LayerNorm's use_int_sqrt."""
         if len(set(self.op_types)) != 1 or self.op_types[0] not in ("ivit", "ibert"):
             return f"operator family {self.op_types} (fused engine: all three operators 'ivit', or all three 'ibert')"
+        for kind, base, params in zip(("gelu", "softmax", "layernorm"), self.op_types, self.op_params):
+            for k, v in params.items():
+                if not ((kind, base, k) == ("layernorm", "ibert", "use_int_sqrt") and isinstance(v, bool)):
+                    return (f"{kind} parameter {k}={v!r} of '{base}' (fused engine: default constructor arguments, or use_int_sqrt "
+                            "of the 'ibert' layernorm)")
+        return None
+
+    @property
+    def ln_int_sqrt(self):
+        """IBERTIntLayerNorm(use_int_sqrt=True): every LayerNorm of the model takes std from integer_sqrt (ibert_modules.py:143)"""
+        return bool(getattr(self.norm, "use_int_sqrt", False))
+
+    def engine_unsupported_reason(self):
+        """None when the fused int8 engine computes exactly what this module tree would; else why not."""
+        bad = self._operator_reason()
+        if bad:
+            return bad
         if self.embed_dim // self.num_heads != 64 or self.embed_dim % 64:
             return "head_dim != 64"
         img, patch = self.geometry[0], self.geometry[1]
@@ -196,10 +218,13 @@ class VisionTransformer(EngineDispatch, nn.Module):
     def _build_engine(self, device, max_batch):
         from .engine import IntViTEngine
         return IntViTEngine(dict(self.state_dict()), self.ranges(), self.embed_dim, self.depth, self.num_heads,
-                            device=device, max_batch=max_batch, family=self.op_types[0],
+                            device=device, max_batch=max_batch, family=self.op_types[0], **self._engine_operator_args(),
                             img_size=self.geometry[0], patch_size=self.geometry[1],
                             **dict(zip(("stream_bits", "softmax_bits", "pos_bits"),
                                        self._engine_widths if self.engine_unsupported_reason() is None else (8, 8, 8))))
+
+    def _engine_operator_args(self):
+        return dict(int_sqrt=True) if self.ln_int_sqrt else {}      # a plain model's engine is built with today's arguments
 
     def forward(self, x):
         if self.takes_engine(x):
@@ -208,7 +233,7 @@ class VisionTransformer(EngineDispatch, nn.Module):
         if not self.is_frozen():
             self.invalidate_engine()     # running-stat QuantActs replace their range buffers: any snapshot is stale
         # a frozen I-ViT model run module by module carries int8 between its modules (quantization_utils/lazy.py)
-        with lazy.scope(x.is_cuda and not self.training and self.op_types in (("ivit",) * 3, ("ibert",) * 3) and self.is_frozen()):
+        with lazy.scope(x.is_cuda and not self.training and self._operator_reason() is None and self.is_frozen()):
             x, s = self.forward_features(x)
             x, _ = self.head(x, s)
         return x.to_float(boundary=True) if isinstance(x, lazy.QT) else x

@@ -625,6 +625,23 @@ int ivit_ibert_softmax_i32(const int32_t* k, int64_t ldx, int rows, int L, float
 int ivit_ibert_layernorm_i32_f32(const int32_t* k, int64_t ldx, int rows, int C, const float* bias_int,
                                  const float* s_out, float shift_pow2, float* out, int64_t ldo, ivit_stream_t stream);
 
+/* use_int_sqrt = True (:142-143): std = integer_sqrt(var) * 2^shift in every I-BERT LayerNorm entry below that takes this flag.
+ * integer_sqrt (:85-109) on the float32 row sum n = var:
+ *   0 for n <= 0;  bits = floor(log2(max(n, 1))) + 1 with the log2 a correctly rounded FLOAT32 -- it is E for a value within
+ *   floor(ln 2 * 2^P) float32 steps below 2^E, P = ceil(log2 E) - 1 (e.g. 2^24 - 11 .. 2^24 - 1 -> bits 25), so bits is not the bit
+ *   length;  x = 2^ceil(bits / 2);  four times:  inv = floor(n / max(x, 1)),  x = floor((x + inv) / 2)  in float32;  int32(x).
+ * It is not floor(sqrt(n)) either: four steps can stop on the upper value of a two-cycle (3 -> 2, 15 -> 4, 255 -> 16,
+ * 16777215 -> 4096).  The kernels run the four steps literally (csrc/isqrt.h).  n = 0 gives std = 0 and factor = floor(2^31 / 0) as
+ * in the reference.
+ * The flag is the whole of `flags` in the _ex entries; in ivit_ibert_layernorm_i8 it is OR-ed into `out_blocks`, in
+ * ivit_ibert_layernorm_i16_i8_ex into `fast_division` (as ivit_layernorm_i8_compat takes IVIT_LN_OUTER_MEAN above its layout bit).
+ * Without it every entry computes what it computed before the flag existed. */
+#define IVIT_IBERT_LN_INT_SQRT 0x100
+/* ivit_ibert_layernorm_i32_f32 with flags = 0 or IVIT_IBERT_LN_INT_SQRT; IVIT_ERR_INVALID for any other bit */
+int ivit_ibert_layernorm_i32_f32_ex(const int32_t* k, int64_t ldx, int rows, int C, const float* bias_int,
+                                    const float* s_out, float shift_pow2, float* out, int64_t ldo, int flags,
+                                    ivit_stream_t stream);
+
 /* LITERAL forms of the three I-BERT operators: the float view x = q*s and its scale in, the reference's float32 sequence on
  * x / s itself (ibert_modules.py:126, 226, 303) -- any scale, not only the power-of-two ones for which x / s is the integer q;
  * row sums in torch's CPU reduction order.  Outputs are the modules' float outputs (GELU :234, Softmax :319, LayerNorm :153). */
@@ -636,6 +653,10 @@ int ivit_ibert_softmax_f32_f32(const float* x, int64_t ldx, int rows, int L, flo
 int ivit_ibert_layernorm_f32_f32(const float* x, int64_t ldx, int rows, int C, const float* s_in, int n_s,
                                  const float* bias_int, const float* s_out, float shift_pow2, float* out, int64_t ldo,
                                  ivit_stream_t stream);
+/* the literal LayerNorm with flags = 0 or IVIT_IBERT_LN_INT_SQRT (above); IVIT_ERR_INVALID for any other bit */
+int ivit_ibert_layernorm_f32_f32_ex(const float* x, int64_t ldx, int rows, int C, const float* s_in, int n_s,
+                                    const float* bias_int, const float* s_out, float shift_pow2, float* out, int64_t ldo,
+                                    int flags, ivit_stream_t stream);
 
 /* ---- the I-BERT family inside the fused int8 engine (engine.py, family "ibert"; ibert_modules.py:12-319) ---------------
  * int8 activations in and out; every operator runs the reference's float32 sequence on fl(q * s) (what its float tensors hold)
@@ -657,7 +678,10 @@ int ivit_ibert_layernorm_f32_f32(const float* x, int64_t ldx, int rows, int C, c
  *    IVIT_ERR_UNSUPPORTED ("unsupported geometry") for head_dim != 64 or tokens outside 208..1025; IVIT_ERR_INVALID for a NULL
  *    qkv / out / table ("bad operand"), misalignment, a bad band, multipliers out of range, a block-layout buffer >= 2 GiB.
  *  - ivit_ibert_layernorm_i8: IBERTIntLayerNorm (:126-153; mean and variance sums in torch's order) + the QuantAct behind it.
- *    bias_int / s_out / (m, e) as for ivit_layernorm_i8; shift_pow2 = 2^shift (the module's overflow buffer). */
+ *    bias_int / s_out / (m, e) as for ivit_layernorm_i8; shift_pow2 = 2^shift (the module's overflow buffer).
+ *    out_blocks = 0 / 1 (row-major / IVIT_LAYOUT_BLOCKS), optionally | IVIT_IBERT_LN_INT_SQRT.  With the flag the kernel decides
+ *    std from the exact integer sum V of the squares only where V < 2^24 (the float32 sum then equals V in any order); a row with
+ *    V >= 2^24 is evaluated literally, its sum added in torch's order. */
 int ivit_ibert_gelu_build_lut(float s, float b_int, float c_int, float shift_int, float s_out, uint32_t m_q, int32_t e_q,
                               int8_t* lut, ivit_stream_t stream);
 int ivit_ibert_softmax_build_table(float s, float x0_int, float b_int, float c_int, float exp_sf, float act_sf, uint32_t m_act,
@@ -679,7 +703,8 @@ int ivit_ibert_layernorm_i8(const int8_t* x, int64_t ldx, int rows, int C, float
 int ivit_ibert_layernorm_i16_i8(const int16_t* x, int64_t ldx, int rows, int C, float s_in, const float* bias_int,
                                 const float* s_out, float shift_pow2, const uint32_t* m, const int32_t* e, int8_t* out, int64_t ldo,
                                 ivit_stream_t stream);
-/* fast_division = 1: the caller has checked (for all 65536 inputs at this s_in) that the three-instruction quotient by the
+/* fast_division = 0 / 1, optionally | IVIT_IBERT_LN_INT_SQRT (the variance sum is the float32 sum in torch's order in either form).
+ * fast_division = 1: the caller has checked (for all 65536 inputs at this s_in) that the three-instruction quotient by the
  * invariant s_in -- q0 = x * r, e = fma(-s, q0, x), fma(e, r, q0), r = RN(1 / s_in) -- is the correctly rounded x / s_in */
 int ivit_ibert_layernorm_i16_i8_ex(const int16_t* x, int64_t ldx, int rows, int C, float s_in, const float* bias_int,
                                    const float* s_out, float shift_pow2, const uint32_t* m, const int32_t* e, int8_t* out, int64_t ldo,

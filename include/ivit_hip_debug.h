@@ -2,11 +2,13 @@
  * ivit_hip_debug.h -- test and measurement hooks of libivit_hip_lab.so (csrc built with IVIT_LAB = 1).  NOT part of the
  * drop-in boundary (include/ivit_hip.h) and not in libivit_hip.so: process-wide, not thread-safe, for tests/ and scripts/ only.
  *
- * Two kinds of hook, nothing else:
+ * Three kinds of hook, nothing else:
  *   form selector   forces a kernel form that the product library itself launches for some other shape or scale, so that tests
  *                   pin every product form on the same inputs.  Results stay correct.
  *   instrument      time stamps, or "skip this phase" timing ablations, of a kernel the product ships.  Ablations make the
  *                   results WRONG; they exist to be timed.
+ *   probe           runs one device function of a product kernel on the caller's array, for inputs no row of activations can be
+ *                   made to produce on demand.  No state.
  * Forms that were tried and lost are not kept here: profiles/HISTORY.md and the git history are their record.
  * Every bit of every word has one meaning and one reader; bits not listed are ignored.  0 restores the product's behaviour.
  */
@@ -125,6 +127,12 @@ int ivit_debug_ln_ablate(int bits);
  *   8-10  | forced number of workgroups per (image, head), 1-7 (0 = the model's choice;  | correct | scripts/attn_parts.py,
  *         | selector)                                                                    |         | */
 int ivit_debug_attention(int bits);
+
+/* probe: out[i] = integer_sqrt(n[i]) for i < count, the device function every I-BERT LayerNorm kernel calls under
+ * IVIT_IBERT_LN_INT_SQRT (csrc/isqrt.h; ibert_modules.py:85-109 -- four float32 Newton steps from 2^ceil(bits / 2), bits from the
+ * float32 log2).  n: device float32 (the row sum var_int), out: device int32.  tests/test_gpu_ibert_intsqrt.py runs it over
+ * tests/golden/ibert_intsqrt_kat.npz: the values next to the powers of two where log2 rounds up and the two-cycle values k^2 - 1. */
+int ivit_debug_ibert_integer_sqrt(const float* n, int64_t count, int32_t* out, void* stream);
 
 #ifdef __cplusplus
 }
