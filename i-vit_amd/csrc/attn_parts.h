@@ -1,9 +1,9 @@
 // attn_parts.h -- the device pieces the fused attention kernels share, stated ONCE (attention.hip: attention_kernel,
-// attention_long_kernel, attention_cls_kernel; swin.hip: window_attention_kernel, window_attention_long_kernel).  Included inside
+// attention_long_kernel, attention_cls_kernel; swin.hip: window_attention_kernel; literal.hip: shiftmax_f32_kernel).  Included inside
 // the anonymous namespace of those files, after common.h.  Arithmetic and lane exchanges only: loads, stores and their addresses,
 // loop structure, scheduling barriers and the lab ablation branches stay in the kernels.  Every helper is force-inlined and leaves
-// each kernel's instruction sequence as it was (scripts/kernel_table.py, profiles/attn_parts_kernel_table.csv); where a kernel
-// keeps a copy of its own, a helper in its place changed that sequence.
+// each kernel's instruction sequence as it was (scripts/kernel_table.py, profiles/attn_parts_kernel_table.csv,
+// profiles/window_attention_kernel_table.csv); where a kernel keeps a copy of its own, a helper in its place changed that sequence.
 // Lane roles throughout: lane = 16 g + l15 owns query l15 of its tile and the keys 16 kt + 4 g + r of every key tile; the lanes
 // l, l ^ 16, l ^ 32, l ^ 48 are "the four lanes of a query".
 #pragma once
@@ -22,6 +22,20 @@ IVIT_DEV void bytes4x4_transpose(unsigned a0, unsigned a1, unsigned a2, unsigned
     t[1] = __builtin_amdgcn_perm(lo23, lo01, 0x07060302u);   // d+1
     t[2] = __builtin_amdgcn_perm(hi23, hi01, 0x05040100u);   // d+2
     t[3] = __builtin_amdgcn_perm(hi23, hi01, 0x07060302u);   // d+3
+}
+
+// ---- Shiftmax's exponent on a float32 argument: int_exp_shift, ivit_modules.py:150-162 verbatim (n = 15), for d = x / s - max
+// (:168) at ANY input scale.  The one statement of the literal sequence (literal.hip shiftmax_f32_kernel; the SM == 1 form of
+// swin.hip window_attention_kernel on its phi values)
+IVIT_DEV float shiftexp_lit(float d, float x0)
+{
+    float x = (d + floorf(d / 2.0f)) - floorf(d / 16.0f);     // :151
+    x = fmaxf(x, 15.0f * x0);                                  // :155
+    const float q = floorf(x / x0);                            // :157
+    const float r = x - x0 * q;                                // :158
+    float ex = r / 2.0f - x0;                                  // :159
+    ex = floorf(ex * ldexpf(1.0f, 15 - (int)q));               // :160
+    return fmaxf(ex, 0.0f);
 }
 
 // ---- Shiftmax factor (ivit_modules.py:171-174) from the exact integer row sum, rounded once to float32 (= the reference's

@@ -65,11 +65,13 @@ def occupancy_rules(path, what):
             # (other geometries, "not tuned") may keep a few dwords of the Q prefetch in scratch
             occ, need_no_scratch = int(m.group(3)), m.group(4) == "0"
         elif what == "swin":
-            if "window_attention_long_kernel" in name:
-                # 65..144 tokens: = its __launch_bounds__ (two workgroups per CU); the 36 scores per lane stay in registers: no scratch
-                occ, need_no_scratch = 2, True
-            elif "window_attention_kernel" in name:
-                occ, need_no_scratch = 4, True
+            if (m := re.search(r"window_attention_kernelILi(\d+)ELb([01])ELi(\d+)E", name)):
+                # window_attention_kernel<SM, RQ32, NKT>: = its __launch_bounds__.  NKT 4 (2..64 tokens): four workgroups per CU;
+                # NKT 9 (65..144 tokens): two, the 36 scores per lane stay in registers.  No scratch in either
+                occ, need_no_scratch = (4 if int(m.group(3)) == 4 else 2), True
+            elif "window_attention" in name:
+                print("check_resources: unknown window attention kernel", name)
+                return 1
             else:
                 m = re.search(r"layernorm_i16_i8_tiled(_compat)?_kernelILi(\d+)ELi(\d+)E", name)
                 if not m:

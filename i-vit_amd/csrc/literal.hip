@@ -18,6 +18,8 @@ namespace {
 constexpr int NT = 256;
 constexpr int WPB = NT / 64;
 
+#include "attn_parts.h"
+
 struct LnLitArgs {
     const float* x;
     int64_t ldx;
@@ -77,18 +79,6 @@ struct SmLitArgs {
     int64_t ldo;
     float two_sh;    // 2^(31 - output_bit + 1), ivit_modules.py:175
 };
-
-// int_exp_shift on a float32 argument, ivit_modules.py:150-162 verbatim (n = 15)
-IVIT_DEV float shiftexp_lit(float d, float x0)
-{
-    float x = (d + floorf(d / 2.0f)) - floorf(d / 16.0f);     // :151
-    x = fmaxf(x, 15.0f * x0);                                  // :155
-    const float q = floorf(x / x0);                            // :157
-    const float r = x - x0 * q;                                // :158
-    float ex = r / 2.0f - x0;                                  // :159
-    ex = floorf(ex * ldexpf(1.0f, 15 - (int)q));               // :160
-    return fmaxf(ex, 0.0f);
-}
 
 // IVITIntSoftmax.forward, ivit_modules.py:164-176, line by line
 template <typename TO>

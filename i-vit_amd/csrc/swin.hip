@@ -641,18 +641,25 @@ __global__ __launch_bounds__(NT) void avgpool_kernel(const int8_t* x, int8_t* ou
 }
 
 // ------------------------------------------------------------------------------------------------
-// Windowed attention: one wave per (window, head); T = ws*ws <= 64 tokens, head_dim 32.
+// Windowed attention: one wave per (window, head); T = ws*ws tokens in NKT key tiles of 16, head_dim 32.
 //   S^T = K . Q^T on v_mfma_i32_16x16x32_i8 (the head dimension is one instruction deep), qact_attn1 (8 bit),
 //   + relative position bias through the two-operand qact2 (the bias operand RNE(k_tab * m / 2^e) is a load-time
-//   constant table [nH, T, 64] int16, keys padded to 64), + shift mask (the integer -100/s wherever the region ids of
-//   query and key differ, added after the clamp, swin_quant.py:149-155), Shiftmax, O^T = Vt . P^T on v_mfma_i32_16x16x64_i8 (all 64 key slots in one step), qact3.
+//   constant table [nH, T, kp] int16, keys padded to whole key tiles), + shift mask (the integer -100/s wherever the region ids of
+//   query and key differ, added after the clamp, swin_quant.py:149-155), Shiftmax, O^T = Vt . P^T on v_mfma_i32_16x16x64_i8 in
+//   key steps of 64 (slots past T are zero probabilities), qact3.
+//   NKT 4: 2..64 tokens (windows up to 8x8, Swin at 224 px): a row of scores is 16 per lane, P.V one key step, kp = 64, four
+//          workgroups per CU.
+//   NKT 9: 65..144 tokens (9x9 .. 12x12, Swin at 384 px): 36 scores per lane (and the literal form's 36 float views) stay in
+//          registers at two workgroups per CU (<= 256 VGPRs), P.V up to 3 key steps, kp = 16 * ceil(T / 16).
+//   The bias rows stay in global memory (L2): per score they are 2 bytes against the 16 of the score's 16x16x32 operand rows, and
+//   staging them in LDS would add a wave barrier per query tile for data each wave reads once.
 // ------------------------------------------------------------------------------------------------
 struct WinAttnArgs {
     const int8_t* qkv;      // [3][B_][nH][T][32]
     int8_t* out;            // [B_*T, nH*32] with row stride ldo
     int64_t ldo;
-    const int16_t* bias;    // [nH][T][64]
-    const uint8_t* region;  // [nW][64] or NULL
+    const int16_t* bias;    // [nH][T][kp]
+    const uint8_t* region;  // [nW][kp] or NULL
     int mask_value;
     int nwin, heads, T, nW;
     double Ms, Mb, Mo;      // qact_attn1; qact2 main operand; qact3
@@ -676,38 +683,46 @@ struct WinAttnArgs {
     // ws != 0: the output rows go to their IMAGE positions (window reverse + roll back applied here): the projection is
     // row-wise, so attn.proj and the residual QuantAct behind it then need no row map (and fuse into one GEMM)
     WinMap omap;
-    int omap_inv;           // 65536 / ws + 1: (q * omap_inv) >> 16 == q / ws for q < 64
+    int omap_inv;           // 65536 / ws + 1: (q * omap_inv) >> 16 == q / ws for q < T (NKT 4: q < 64)
 };
 
 constexpr int WHD = 32;
-constexpr int WVT_ROW = 64;                      // Vt row: 64 key slots
-constexpr int WVT_BYTES = WHD * WVT_ROW;         // 2 KiB per wave
-constexpr int WLUT_OFF = WPB * WVT_BYTES;
-
 constexpr int WBAND_PAD = 4;     // dwords: keeps the slices 16-byte aligned and rotates their banks
 
 // SM: Shiftmax form -- 0 the table of distances to the row maximum (power-of-two scales; natural scales whose band table has one
 // row), 1 the literal float32 sequence on the phi tables, 2 band rows per row maximum staged through LDS.  Template parameters, not
 // run-time branches: with all three forms in one body the kernel took 135 VGPRs = three workgroups per CU instead of four, and the
 // power-of-two form lost 12 % (44 -> 49.5 us per call in Swin-T, profiles/r04q vs r04h).
-template <int SM, bool RQ32>
-__global__ __launch_bounds__(NT, 4) void window_attention_kernel(WinAttnArgs a)
+// NKT: key tiles of 16 per row, 4 or 9; everything the two sizes differ in follows from it.  `if constexpr (NKT == 4)` keeps the
+// statements that make the short form cheap where the uniform statement generated other code (profiles/HISTORY.md §9), and
+// `if constexpr (NKT > 4)` the one arithmetic difference ("Large windows").
+// kp_long: the bias / region row stride of NKT 9 (NKT 4 folds the literal 64).  A kernel parameter of its own, not a field of
+// WinAttnArgs: as a field its scalar load merges with the neighbouring ones and the six NKT 9 forms lose the instruction sequence
+// they were measured with (HISTORY.md §9).
+template <int SM, bool RQ32, int NKT>
+__global__ __launch_bounds__(NT, NKT == 4 ? 4 : 2) void window_attention_kernel(WinAttnArgs a, int kp_long)
 {
-    __shared__ __attribute__((aligned(16))) char smem[WLUT_OFF + 256 * 4];
+    constexpr int NKS = (NKT + 3) / 4;               // P.V key steps of 64
+    constexpr int VT_ROW = 64 * NKS;                 // Vt row: 64 key slots per step
+    constexpr int VT_BYTES = WHD * VT_ROW;           // 2 / 6 KiB per wave
+    constexpr int LUT_OFF = WPB * VT_BYTES;
+    __shared__ __attribute__((aligned(16))) char smem[LUT_OFF + 256 * 4];
     __shared__ float s_phi[2][256];
     extern __shared__ __attribute__((aligned(16))) unsigned band_lds[];     // [4 waves][16 queries][band_w + WBAND_PAD], band form only
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = lane >> 4, l15 = lane & 15;
     const int T = a.T;
-    reinterpret_cast<unsigned*>(smem + WLUT_OFF)[tid] = a.band1 ? a.band1[min(tid, a.band_w - 1)] : shiftexp_int(-tid, a.x0, 15);
+    const int nkt = NKT == 4 ? NKT : (T + 15) >> 4, nks = (nkt + 3) >> 2;     // NKT 9: 5..9 key tiles, 2..3 key steps
+    const int kp = NKT == 4 ? 64 : kp_long;
+    reinterpret_cast<unsigned*>(smem + LUT_OFF)[tid] = a.band1 ? a.band1[min(tid, a.band_w - 1)] : shiftexp_int(-tid, a.x0, 15);
     constexpr bool band = SM == 2, compat = SM == 1;
     if constexpr (compat) {
         s_phi[0][tid] = a.phi[tid];
         s_phi[1][tid] = a.phim[tid];
     }
     __syncthreads();
-    const unsigned* lut = reinterpret_cast<const unsigned*>(smem + WLUT_OFF);
-    char* vt = smem + wave * WVT_BYTES;
+    const unsigned* lut = reinterpret_cast<const unsigned*>(smem + LUT_OFF);
+    char* vt = smem + wave * VT_BYTES;
     const int64_t plane = (int64_t)a.nwin * a.heads * T * WHD;
     const int npairs = a.nwin * a.heads;
 
@@ -727,15 +742,18 @@ __global__ __launch_bounds__(NT, 4) void window_attention_kernel(WinAttnArgs a)
         const int8_t* qg = a.qkv + (int64_t)pair * T * WHD;
         const int8_t* kg = qg + plane;
         const int8_t* vg = qg + 2 * plane;
-        // ---- V transposed into this wave's LDS tile: Vt[d][chunk g'][byte 4t + r] = V[key 16t + 4g' + r][d];
-        //      chunk j of row d at slot (j + 2*((d>>2)&1)) & 3.  Work item = 4 keys x 16 d (13 x 2 items).
+        // ---- V transposed into this wave's LDS tile: Vt[d][64 s + slot(chunk g') + 4t + r] = V[key 64 s + 16t + 4g' + r][d];
+        //      chunk j of row d at slot (j + 2*((d>>2)&1)) & 3.  Work item = 4 keys x 16 d.  NKT 4: one guarded pass over the keys below T
+        //      (13 x 2 items at 49 tokens); NKT 9: every slot of the nks segments written (keys past T repeat key T - 1: their
+        //      probabilities are 0).
         __builtin_amdgcn_wave_barrier();
-        if (lane < ((T + 3) >> 2) * 2) {
-            const int kg4 = lane >> 1, c = lane & 1;
+        const int nitems = NKT == 4 ? ((T + 3) >> 2) * 2 : nks * 32;
+        for (int item = lane; item < nitems; item += 64) {
+            const int kg4 = item >> 1, c = item & 1;
             v4i v[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) v[r] = *reinterpret_cast<const v4i*>(vg + (int64_t)min(4 * kg4 + r, T - 1) * WHD + 16 * c);
-            const int key0 = 4 * kg4;
+            const int key0 = 4 * kg4, seg = NKT == 4 ? 0 : key0 >> 6;
             const int j = (key0 >> 2) & 3, boff = 4 * ((key0 >> 4) & 3);
 #pragma unroll
             for (int w = 0; w < 4; ++w) {
@@ -745,38 +763,61 @@ __global__ __launch_bounds__(NT, 4) void window_attention_kernel(WinAttnArgs a)
 #pragma unroll
                 for (int bb = 0; bb < 4; ++bb) {
                     const int d = 16 * c + 4 * w + bb;
-                    *reinterpret_cast<unsigned*>(vt + d * WVT_ROW + (((j + 2 * ((d >> 2) & 1)) & 3) << 4) + boff) = t4[bb];
+                    *reinterpret_cast<unsigned*>(vt + d * VT_ROW + 64 * seg + (((j + 2 * ((d >> 2) & 1)) & 3) << 4) + boff) = t4[bb];
                 }
             }
+            if constexpr (NKT == 4) break;      // at most 32 items: a guarded pass, not a loop
         }
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
 
-        // K fragments of the 4 key tiles: lane (key 16kt + l15, 8 bytes at 8g)
-        long kf[4];
+        // K fragments of the key tiles: lane (key 16kt + l15, 8 bytes at 8g); shift mask (swin_quant.py:223-249): tokens of different
+        // regions of the rolled image do not attend to each other, kreg = the region ids of the lane's keys
+        long kf[NKT];
+        unsigned kreg[NKT];
+        const uint8_t* regrow;
+        if constexpr (NKT == 4) {      // all four tiles, unguarded (rows past T repeat row T - 1), the region row behind one branch
 #pragma unroll
-        for (int kt = 0; kt < 4; ++kt)
-            kf[kt] = *reinterpret_cast<const long*>(kg + (int64_t)min(16 * kt + l15, T - 1) * WHD + 8 * g);
-
-        // shift mask (swin_quant.py:223-249): tokens of different regions of the rolled image do not attend to each other
-        unsigned kreg[4] = {0u, 0u, 0u, 0u};
-        const uint8_t* regrow = a.region ? a.region + (win % a.nW) * 64 : nullptr;
-        if (regrow) {
+            for (int kt = 0; kt < NKT; ++kt) {
+                kf[kt] = *reinterpret_cast<const long*>(kg + (int64_t)min(16 * kt + l15, T - 1) * WHD + 8 * g);
+                kreg[kt] = 0u;
+            }
+            regrow = a.region ? a.region + (win % a.nW) * 64 : nullptr;
+            if (regrow) {
 #pragma unroll
-            for (int kt = 0; kt < 4; ++kt) kreg[kt] = *reinterpret_cast<const unsigned*>(regrow + 16 * kt + 4 * g);
+                for (int kt = 0; kt < NKT; ++kt) kreg[kt] = *reinterpret_cast<const unsigned*>(regrow + 16 * kt + 4 * g);
+            }
+        } else {
+            regrow = a.region ? a.region + (int64_t)(win % a.nW) * kp : nullptr;
+#pragma unroll
+            for (int kt = 0; kt < NKT; ++kt) {
+                kf[kt] = 0;
+                kreg[kt] = 0u;
+                if (kt < nkt) {
+                    kf[kt] = *reinterpret_cast<const long*>(kg + (int64_t)min(16 * kt + l15, T - 1) * WHD + 8 * g);
+                    if (regrow) kreg[kt] = *reinterpret_cast<const unsigned*>(regrow + 16 * kt + 4 * g);
+                }
+            }
         }
-        for (int qt = 0; qt < 4; ++qt) {
+        for (int qt = 0; qt < nkt; ++qt) {
             const int qrow = 16 * qt + l15;
-            if (16 * qt >= T) break;  // uniform
+            if constexpr (NKT == 4) {
+                if (16 * qt >= T) break;  // uniform
+            }
             const int qld = min(qrow, T - 1);
             const long qf = *reinterpret_cast<const long*>(qg + (int64_t)qld * WHD + 8 * g);
-            const int16_t* brow = a.bias + ((int64_t)hh * T + qld) * 64 + 4 * g;
+            const int16_t* brow = a.bias + ((int64_t)hh * T + qld) * kp + 4 * g;
             const unsigned qreg = regrow ? regrow[qld] : 0u;
-            int s[4][4];
+            int s[NKT][4];
             int rmax = -100000;
-            float xv[4][4], xmax = -__builtin_inff();     // compat: the float view x / s of every score
+            float xv[NKT][4], xmax = -__builtin_inff();     // compat: the float view x / s of every score
 #pragma unroll
-            for (int kt = 0; kt < 4; ++kt) {
+            for (int kt = 0; kt < NKT; ++kt) {
+                if constexpr (NKT > 4) {      // -100000 / -inf: no score (key or whole tile past T)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) { s[kt][r] = -100000; xv[kt][r] = -__builtin_inff(); }
+                    if (kt >= nkt) continue;     // uniform
+                }
                 v4i acc = {0, 0, 0, 0};
                 acc = __builtin_amdgcn_mfma_i32_16x16x32_i8(kf[kt], qf, acc, 0, 0, 0);
                 const int2 bw = *reinterpret_cast<const int2*>(brow + 16 * kt);
@@ -785,22 +826,23 @@ __global__ __launch_bounds__(NT, 4) void window_attention_kernel(WinAttnArgs a)
                 for (int r = 0; r < 4; ++r) {
                     const int key = 16 * kt + 4 * g + r;
                     int ka = -100000;
-                    xv[kt][r] = -__builtin_inff();
+                    if constexpr (NKT == 4) xv[kt][r] = -__builtin_inff();      // NKT 4: the defaults per score, one store behind the branch
                     if (key < T) {
                         if constexpr (RQ32) {      // round 4: 7 float32 / integer instructions instead of 6 float64 ones + 3 (attention.hip RQ32)
                             const int tb = clamp_i32(__float_as_int(__builtin_fmaf((float)acc[r], a.Ms32, 12582912.0f)), 0x4B400000 - 128, 0x4B400000 + 127);
                             const float kSf = __int_as_float(tb) - 12582912.0f;                  // qact_attn1, exact small integer
                             ka = clamp_i32(__float_as_int(__builtin_fmaf(kSf, a.Mb32, 12582912.0f)) - 0x4B400000 + bv[r], -128, 127);
                         } else {
-                        const int kS = clamp_i32(requant_exact(acc[r], a.Ms), -128, 127);        // qact_attn1
-                        ka = clamp_i32(requant_exact(kS, a.Mb) + bv[r], -128, 127);              // qact2 (two operands)
+                            const int kS = clamp_i32(requant_exact(acc[r], a.Ms), -128, 127);        // qact_attn1
+                            ka = clamp_i32(requant_exact(kS, a.Mb) + bv[r], -128, 127);              // qact2 (two operands)
                         }
                         const bool masked = ((kreg[kt] >> (8 * r)) & 0xffu) != qreg;
                         if constexpr (compat) xv[kt][r] = s_phi[masked ? 1 : 0][ka + 128];
                         if (masked) ka = band ? -50000 : ka + a.mask_value;                      // shift mask, after the clamp
+                        if constexpr (NKT > 4) s[kt][r] = ka;
                     }
-                    s[kt][r] = ka;
-                    rmax = max(rmax, ka);
+                    if constexpr (NKT == 4) s[kt][r] = ka;
+                    rmax = max(rmax, s[kt][r]);
                     xmax = fmaxf(xmax, xv[kt][r]);
                 }
             }
@@ -812,19 +854,10 @@ __global__ __launch_bounds__(NT, 4) void window_attention_kernel(WinAttnArgs a)
                 xmax = fmaxf(xmax, __shfl_xor(xmax, 32));
                 const float x0f = (float)a.x0;
 #pragma unroll
-                for (int kt = 0; kt < 4; ++kt)
+                for (int kt = 0; kt < NKT; ++kt)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        unsigned e = 0u;
-                        if (s[kt][r] != -100000) {
-                            const float d = xv[kt][r] - xmax;                                    // :168
-                            float x = (d + floorf(d / 2.0f)) - floorf(d / 16.0f);                // :151
-                            x = fmaxf(x, 15.0f * x0f);                                           // :155
-                            const float qq = floorf(x / x0f);                                    // :157
-                            const float rr = x - x0f * qq;                                       // :158
-                            const float ex = floorf((rr / 2.0f - x0f) * ldexpf(1.0f, 15 - (int)qq));   // :159-160
-                            e = (unsigned)fmaxf(ex, 0.0f);
-                        }
+                        const unsigned e = (s[kt][r] == -100000) ? 0u : (unsigned)shiftexp_lit(xv[kt][r] - xmax, x0f);      // :168
                         s[kt][r] = (int)e;
                         esum += e;
                     }
@@ -844,279 +877,60 @@ __global__ __launch_bounds__(NT, 4) void window_attention_kernel(WinAttnArgs a)
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                unsigned ev[4][4];
+                unsigned ev[NKT][4];
+                if constexpr (NKT == 4) {      // all sixteen gathers in flight before the first is used
 #pragma unroll
-                for (int kt = 0; kt < 4; ++kt)
+                    for (int kt = 0; kt < NKT; ++kt)
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) ev[kt][r] = slice[min(rm - max(s[kt][r], -50000), W1)];
+                        for (int r = 0; r < 4; ++r) ev[kt][r] = slice[min(rm - max(s[kt][r], -50000), W1)];
+                }
 #pragma unroll
-                for (int kt = 0; kt < 4; ++kt)
+                for (int kt = 0; kt < NKT; ++kt)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
+                        if constexpr (NKT > 4) ev[kt][r] = slice[min(rm - max(s[kt][r], -50000), W1)];
                         const unsigned e = (s[kt][r] == -100000) ? 0u : ev[kt][r];
                         s[kt][r] = (int)e;
                         esum += e;
                     }
-            } else
-#pragma unroll
-            for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    unsigned e = (s[kt][r] == -100000) ? 0u : lut[min(rmax - s[kt][r], a.ksat) & 255];
-                    s[kt][r] = (int)e;
-                    esum += e;
-                }
-            const float factor = shiftmax_factor(rows_allsum_u32(esum));
-            v4i pk;
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                unsigned w = 0;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    float pr = (float)(unsigned)s[t][r] * factor;       // :175
-                    w |= ((((unsigned)pr) >> 24) & 0xffu) << (8 * r);
-                }
-                pk[t] = (int)w;
-            }
-            int64_t orow_idx = (int64_t)win * T + qrow;
-            if (a.omap.ws) {      // window reverse + roll back: (iy, ix) of the query in its window -> (y, x) of the image
-                const int qr = min(qrow, T - 1);
-                const int iy = (qr * a.omap_inv) >> 16, ix = qr - iy * a.omap.ws;      // qr / ws for qr < 64 (checked by the launcher)
-                int y = wy0 + iy, x = wx0 + ix;
-                y = y >= a.omap.H ? y - a.omap.H : y;
-                x = x >= a.omap.W ? x - a.omap.W : x;
-                orow_idx = img_base + y * a.omap.W + x;
-            }
-            int8_t* orow = a.out + orow_idx * a.ldo + hh * WHD;
-            unsigned wq[2];      // wq[dt]: bytes d = 16 dt + 4 g + 0..3 of this lane's query
-#pragma unroll
-            for (int dt = 0; dt < 2; ++dt) {
-                const int d = 16 * dt + l15;
-                const v4i vf = *reinterpret_cast<const v4i*>(vt + d * WVT_ROW + (((g + 2 * ((d >> 2) & 1)) & 3) << 4));
-                v4i acc = {0, 0, 0, 0};
-                acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(vf, pk, acc, 0, 0, 0);
-                unsigned w = 0;
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    w |= ((unsigned)clamp_i32(requant_exact(acc[r], a.Mo), -128, 127) & 0xffu) << (8 * r);
-                wq[dt] = w;
-            }
-            // the query's 32 bytes sit as 2 x 4 dwords in its four lanes: a word exchange (v_permlane32_swap, v_permlane16_swap)
-            // leaves lane g with the 8 contiguous bytes d = 8 g .. 8 g + 7 -> one 8-byte store instead of two 4-byte ones
-            {
-                typedef unsigned v2u __attribute__((ext_vector_type(2)));
-                const v2u ab = __builtin_amdgcn_permlane32_swap(wq[0], wq[1], false, false);   // g < 2: (w0[g], w0[g+2]); g >= 2: (w1[g-2], w1[g])
-                const v2u pr = __builtin_amdgcn_permlane16_swap(ab.x, ab.y, false, false);     // lane g: words 2 (g & 1), 2 (g & 1) + 1 of w_{g >> 1}
-                if (qrow < T) *reinterpret_cast<int2*>(orow + 8 * g) = make_int2((int)pr.x, (int)pr.y);
-            }
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Windowed attention for 65..144 tokens (windows of 9x9 .. 12x12, Swin at 384 px): the arithmetic of window_attention_kernel, every
-// Shiftmax form and both output orders, with a row of up to 9 key tiles of 16.  Still one wave per (window, head): a row of 144 scores
-// is 36 per lane (9 key tiles x 4), S^T on 16x16x32 per key tile, O^T = Vt . P^T in up to 3 key steps of 64 on 16x16x64 (slots past T
-// are zero probabilities).  Vt of the wave's pair in LDS (32 x 192 bytes, each 64-key segment in window_attention_kernel's layout).
-// The bias is [nH][T][kp] int16 and the region table [nW][kp], kp = 16 * ceil(T / 16): rows of whole key tiles.  The bias rows stay
-// in global memory (L2): per score they are 2 bytes against the 16 of the score's 16x16x32 operand rows, and staging them in LDS
-// would add a wave barrier per query tile for data each wave reads once.
-// ------------------------------------------------------------------------------------------------
-constexpr int WL_NKT = 9;                          // key tiles of 16: up to 144 tokens
-constexpr int WL_NKS = 3;                          // P.V key steps of 64
-constexpr int WL_VT_ROW = 64 * WL_NKS;             // Vt row: 192 key slots
-constexpr int WL_VT_BYTES = WHD * WL_VT_ROW;       // 6 KiB per wave
-constexpr int WL_LUT_OFF = WPB * WL_VT_BYTES;
-
-// two workgroups of four waves per CU (<= 256 VGPRs): the 36 scores per lane (and the literal form's 36 float views) stay in registers
-template <int SM, bool RQ32>
-__global__ __launch_bounds__(NT, 2) void window_attention_long_kernel(WinAttnArgs a, int kp)
-{
-    __shared__ __attribute__((aligned(16))) char smem[WL_LUT_OFF + 256 * 4];
-    __shared__ float s_phi[2][256];
-    extern __shared__ __attribute__((aligned(16))) unsigned band_lds[];     // [4 waves][16 queries][band_w + WBAND_PAD], band form only
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int g = lane >> 4, l15 = lane & 15;
-    const int T = a.T;
-    const int nkt = (T + 15) >> 4, nks = (nkt + 3) >> 2;     // 6..9 key tiles, 2..3 key steps
-    reinterpret_cast<unsigned*>(smem + WL_LUT_OFF)[tid] = a.band1 ? a.band1[min(tid, a.band_w - 1)] : shiftexp_int(-tid, a.x0, 15);
-    constexpr bool band = SM == 2, compat = SM == 1;
-    if constexpr (compat) {
-        s_phi[0][tid] = a.phi[tid];
-        s_phi[1][tid] = a.phim[tid];
-    }
-    __syncthreads();
-    const unsigned* lut = reinterpret_cast<const unsigned*>(smem + WL_LUT_OFF);
-    char* vt = smem + wave * WL_VT_BYTES;
-    const int64_t plane = (int64_t)a.nwin * a.heads * T * WHD;
-    const int npairs = a.nwin * a.heads;
-
-    for (int pair = blockIdx.x * WPB + wave; pair < npairs; pair += gridDim.x * WPB) {
-        const int win = pair / a.heads, hh = pair - win * a.heads;
-        int64_t img_base = 0;
-        int wy0 = 0, wx0 = 0;
-        if (a.omap.ws) {
-            const int nwx = a.omap.W / a.omap.ws;
-            const int bimg = win / a.nW, wrem = win - bimg * a.nW;
-            const int wy = wrem / nwx;
-            wy0 = wy * a.omap.ws + a.omap.shift;
-            wx0 = (wrem - wy * nwx) * a.omap.ws + a.omap.shift;
-            img_base = (int64_t)bimg * a.omap.H * a.omap.W;
-        }
-        const int8_t* qg = a.qkv + (int64_t)pair * T * WHD;
-        const int8_t* kg = qg + plane;
-        const int8_t* vg = qg + 2 * plane;
-        // ---- Vt[d][64 s + slot(chunk g') + 4t + r] = V[key 64 s + 16t + 4g' + r][d], every slot of the nks segments written (keys past
-        //      T repeat key T - 1: their probabilities are 0).  Work item = 4 keys x 16 d.
-        __builtin_amdgcn_wave_barrier();
-        for (int item = lane; item < nks * 32; item += 64) {
-            const int kg4 = item >> 1, c = item & 1;
-            v4i v[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] = *reinterpret_cast<const v4i*>(vg + (int64_t)min(4 * kg4 + r, T - 1) * WHD + 16 * c);
-            const int key0 = 4 * kg4, seg = key0 >> 6;
-            const int j = (key0 >> 2) & 3, boff = 4 * ((key0 >> 4) & 3);
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                const unsigned a0 = (unsigned)v[0][w], a1 = (unsigned)v[1][w], a2 = (unsigned)v[2][w], a3 = (unsigned)v[3][w];
-                unsigned t4[4];
-                bytes4x4_transpose(a0, a1, a2, a3, t4);
-#pragma unroll
-                for (int bb = 0; bb < 4; ++bb) {
-                    const int d = 16 * c + 4 * w + bb;
-                    *reinterpret_cast<unsigned*>(vt + d * WL_VT_ROW + 64 * seg + (((j + 2 * ((d >> 2) & 1)) & 3) << 4) + boff) = t4[bb];
-                }
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
-
-        long kf[WL_NKT];
-        unsigned kreg[WL_NKT];
-        const uint8_t* regrow = a.region ? a.region + (int64_t)(win % a.nW) * kp : nullptr;
-#pragma unroll
-        for (int kt = 0; kt < WL_NKT; ++kt) {
-            kf[kt] = 0;
-            kreg[kt] = 0u;
-            if (kt < nkt) {
-                kf[kt] = *reinterpret_cast<const long*>(kg + (int64_t)min(16 * kt + l15, T - 1) * WHD + 8 * g);
-                if (regrow) kreg[kt] = *reinterpret_cast<const unsigned*>(regrow + 16 * kt + 4 * g);
-            }
-        }
-        for (int qt = 0; qt < nkt; ++qt) {
-            const int qrow = 16 * qt + l15;
-            const int qld = min(qrow, T - 1);
-            const long qf = *reinterpret_cast<const long*>(qg + (int64_t)qld * WHD + 8 * g);
-            const int16_t* brow = a.bias + ((int64_t)hh * T + qld) * kp + 4 * g;
-            const unsigned qreg = regrow ? regrow[qld] : 0u;
-            int s[WL_NKT][4];
-            int rmax = -100000;
-            float xv[WL_NKT][4], xmax = -__builtin_inff();
-#pragma unroll
-            for (int kt = 0; kt < WL_NKT; ++kt) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) { s[kt][r] = -100000; xv[kt][r] = -__builtin_inff(); }
-                if (kt >= nkt) continue;     // uniform
-                v4i acc = {0, 0, 0, 0};
-                acc = __builtin_amdgcn_mfma_i32_16x16x32_i8(kf[kt], qf, acc, 0, 0, 0);
-                const int2 bw = *reinterpret_cast<const int2*>(brow + 16 * kt);
-                const int bv[4] = {(int)(int16_t)bw.x, bw.x >> 16, (int)(int16_t)bw.y, bw.y >> 16};
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int key = 16 * kt + 4 * g + r;
-                    if (key < T) {
-                        int ka;
-                        if constexpr (RQ32) {
-                            const int tb = clamp_i32(__float_as_int(__builtin_fmaf((float)acc[r], a.Ms32, 12582912.0f)), 0x4B400000 - 128, 0x4B400000 + 127);
-                            const float kSf = __int_as_float(tb) - 12582912.0f;
-                            ka = clamp_i32(__float_as_int(__builtin_fmaf(kSf, a.Mb32, 12582912.0f)) - 0x4B400000 + bv[r], -128, 127);
-                        } else {
-                            const int kS = clamp_i32(requant_exact(acc[r], a.Ms), -128, 127);        // qact_attn1
-                            ka = clamp_i32(requant_exact(kS, a.Mb) + bv[r], -128, 127);              // qact2 (two operands)
-                        }
-                        const bool masked = ((kreg[kt] >> (8 * r)) & 0xffu) != qreg;
-                        if constexpr (compat) xv[kt][r] = s_phi[masked ? 1 : 0][ka + 128];
-                        if (masked) ka = band ? -50000 : ka + a.mask_value;                      // shift mask, after the clamp
-                        s[kt][r] = ka;
-                    }
-                    rmax = max(rmax, s[kt][r]);
-                    xmax = fmaxf(xmax, xv[kt][r]);
-                }
-            }
-            rmax = rows_allmax_i32(rmax);
-            unsigned esum = 0;
-            if constexpr (compat) {
-                xmax = fmaxf(xmax, __shfl_xor(xmax, 16));
-                xmax = fmaxf(xmax, __shfl_xor(xmax, 32));
-                const float x0f = (float)a.x0;
-#pragma unroll
-                for (int kt = 0; kt < WL_NKT; ++kt)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        unsigned e = 0u;
-                        if (s[kt][r] != -100000) {
-                            const float d = xv[kt][r] - xmax;                                    // ivit_modules.py:168
-                            float x = (d + floorf(d / 2.0f)) - floorf(d / 16.0f);                // :151
-                            x = fmaxf(x, 15.0f * x0f);                                           // :155
-                            const float qq = floorf(x / x0f);                                    // :157
-                            const float rr = x - x0f * qq;                                       // :158
-                            const float ex = floorf((rr / 2.0f - x0f) * ldexpf(1.0f, 15 - (int)qq));   // :159-160
-                            e = (unsigned)fmaxf(ex, 0.0f);
-                        }
-                        s[kt][r] = (int)e;
-                        esum += e;
-                    }
-            } else if constexpr (band) {
-                const int W = a.band_w, W1 = W - 1, stride = W + WBAND_PAD;
-                const int rm = max(rmax, -128);
-                unsigned* slice = band_lds + (wave * 16 + l15) * stride;
-                __builtin_amdgcn_wave_barrier();      // the previous tile's gathers are done
-                {
-                    const uint4* src = reinterpret_cast<const uint4*>(a.band + (size_t)(rm + 128) * W);
-                    uint4* dst = reinterpret_cast<uint4*>(slice);
-                    for (int i = g; i < (W >> 2); i += 4) dst[i] = src[i];
-                }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#pragma unroll
-                for (int kt = 0; kt < WL_NKT; ++kt)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const unsigned e = (s[kt][r] == -100000) ? 0u : slice[min(rm - max(s[kt][r], -50000), W1)];
-                        s[kt][r] = (int)e;
-                        esum += e;
-                    }
             } else {
-                // a masked score lies |mask_value| - 255 or more below the maximum: beyond the table's 256 distances when Shiftmax has not
-                // saturated by distance 255 (|x0| above about 24), so those take the exact integer form (band1: the host's saturated entry)
 #pragma unroll
-                for (int kt = 0; kt < WL_NKT; ++kt)
+                for (int kt = 0; kt < NKT; ++kt)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const int d = rmax - s[kt][r];
                         unsigned e = 0u;
-                        if (s[kt][r] != -100000) e = (d <= a.ksat || a.band1) ? lut[min(d, a.ksat) & 255] : shiftexp_int(-d, a.x0, 15);
+                        // NKT 9: a masked score lies |mask_value| - 255 or more below the maximum: beyond the table's 256 distances
+                        // when Shiftmax has not saturated by distance 255 (|x0| above about 24), so those take the exact integer
+                        // form (band1: the host's saturated entry).  NKT 4 takes the table's last entry, and its launcher rejects
+                        // the geometries where that is not the saturated value.
+                        bool in_table = true;
+                        if constexpr (NKT > 4) in_table = d <= a.ksat || a.band1;
+                        if (s[kt][r] != -100000) e = in_table ? lut[min(d, a.ksat) & 255] : shiftexp_int(-d, a.x0, 15);
                         s[kt][r] = (int)e;
                         esum += e;
                     }
             }
             const float factor = shiftmax_factor(rows_allsum_u32(esum));
-            v4i pk[WL_NKS];
+            // NKS 1: built in pk0 -- with element writes into an array of ONE vector the compiler unrolled the query-tile loop four times
+            // (SM 1: 128 VGPRs and scratch)
+            v4i pk[NKS], pk0;
 #pragma unroll
-            for (int ks = 0; ks < WL_NKS; ++ks)
+            for (int ks = 0; ks < NKS; ++ks)
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
                     unsigned w = 0;
-                    if (4 * ks + t < WL_NKT) {
+                    if (4 * ks + t < NKT) {
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
                             const float pr = (float)(unsigned)s[4 * ks + t][r] * factor;     // :175
                             w |= ((((unsigned)pr) >> 24) & 0xffu) << (8 * r);
                         }
                     }
-                    pk[ks][t] = (int)w;
+                    if constexpr (NKS == 1) pk0[t] = (int)w;
+                    else pk[ks][t] = (int)w;
                 }
+            if constexpr (NKS == 1) pk[0] = pk0;
             int64_t orow_idx = (int64_t)win * T + qrow;
             if (a.omap.ws) {      // window reverse + roll back: (iy, ix) of the query in its window -> (y, x) of the image
                 const int qr = min(qrow, T - 1);
@@ -1127,14 +941,14 @@ __global__ __launch_bounds__(NT, 2) void window_attention_long_kernel(WinAttnArg
                 orow_idx = img_base + y * a.omap.W + x;
             }
             int8_t* orow = a.out + orow_idx * a.ldo + hh * WHD;
-            unsigned wq[2];
+            unsigned wq[2];      // wq[dt]: bytes d = 16 dt + 4 g + 0..3 of this lane's query
 #pragma unroll
             for (int dt = 0; dt < 2; ++dt) {
                 const int d = 16 * dt + l15;
-                const char* vrow = vt + d * WL_VT_ROW + (((g + 2 * ((d >> 2) & 1)) & 3) << 4);
+                const char* vrow = vt + d * VT_ROW + (((g + 2 * ((d >> 2) & 1)) & 3) << 4);
                 v4i acc = {0, 0, 0, 0};
 #pragma unroll
-                for (int ks = 0; ks < WL_NKS; ++ks)
+                for (int ks = 0; ks < NKS; ++ks)
                     if (ks < nks) acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(*reinterpret_cast<const v4i*>(vrow + 64 * ks), pk[ks], acc, 0, 0, 0);
                 unsigned w = 0;
 #pragma unroll
@@ -1142,10 +956,11 @@ __global__ __launch_bounds__(NT, 2) void window_attention_long_kernel(WinAttnArg
                     w |= ((unsigned)clamp_i32(requant_exact(acc[r], a.Mo), -128, 127) & 0xffu) << (8 * r);
                 wq[dt] = w;
             }
+            // the query's 32 bytes sit as 2 x 4 dwords in its four lanes: a word exchange (v_permlane32_swap, v_permlane16_swap)
+            // leaves lane g with the 8 contiguous bytes d = 8 g .. 8 g + 7 -> one 8-byte store instead of two 4-byte ones
             {
-                typedef unsigned v2u __attribute__((ext_vector_type(2)));
-                const v2u ab = __builtin_amdgcn_permlane32_swap(wq[0], wq[1], false, false);
-                const v2u pr = __builtin_amdgcn_permlane16_swap(ab.x, ab.y, false, false);
+                const v2u ab = __builtin_amdgcn_permlane32_swap(wq[0], wq[1], false, false);   // g < 2: (w0[g], w0[g+2]); g >= 2: (w1[g-2], w1[g])
+                const v2u pr = __builtin_amdgcn_permlane16_swap(ab.x, ab.y, false, false);     // lane g: words 2 (g & 1), 2 (g & 1) + 1 of w_{g >> 1}
                 if (qrow < T) *reinterpret_cast<int2*>(orow + 8 * g) = make_int2((int)pr.x, (int)pr.y);
             }
         }
@@ -1360,6 +1175,24 @@ IVIT_EXPORT int ivit_window_attention_i8(const int8_t* qkv, int8_t* out, int64_t
                                            tokens, head_dim, m_s, e_s, m_b, e_b, s_attn, m_o, e_o, nullptr, nullptr, stream);
 }
 
+// launch(integral_constant<SM>, bool_constant<RQ32>, integral_constant<NKT>) for the Shiftmax form, the score requantisation and
+// the row length the launcher chose: the twelve instantiations of window_attention_kernel
+template <class F>
+static void winattn_dispatch(int sm, bool rq32, bool long_rows, F launch)
+{
+    auto by_nkt = [&](auto SM, auto RQ32) {
+        if (long_rows) launch(SM, RQ32, std::integral_constant<int, 9>());
+        else launch(SM, RQ32, std::integral_constant<int, 4>());
+    };
+    auto by_rq32 = [&](auto SM) {
+        if (rq32) by_nkt(SM, std::true_type());
+        else by_nkt(SM, std::false_type());
+    };
+    if (sm == 2) by_rq32(std::integral_constant<int, 2>());
+    else if (sm == 1) by_rq32(std::integral_constant<int, 1>());
+    else by_rq32(std::integral_constant<int, 0>());
+}
+
 static int window_attention_launch(const int8_t* qkv, int8_t* out, int64_t ldo, const int16_t* bias_add,
                                    const uint8_t* mask_region, int mask_value, int windows, int windows_per_image,
                                    int heads, int tokens, int head_dim, uint32_t m_s, int32_t e_s, uint32_t m_b,
@@ -1420,7 +1253,7 @@ static int window_attention_launch(const int8_t* qkv, int8_t* out, int64_t ldo, 
         const int d = -i;
         if (d + (d >> 1) - (d >> 4) <= 15 * a.x0) { a.ksat = i; saturates = true; break; }
     }
-    // the short kernel's integer form gives a score under the shift mask the table's last entry: the saturated value only if the
+    // the short form's (NKT 4) distance table gives a score under the shift mask the table's last entry: the saturated value only if the
     // table gets there within its 256 distances (x0 >= -24); the literal form (phi tables) is exact at any scale
     IVIT_REQUIRE(long_rows || saturates || !mask_region || phi || band,
                  "ivit_window_attention_i8: x0=%d: the integer form cannot place masked scores (use the phi tables)", a.x0);
@@ -1433,30 +1266,11 @@ static int window_attention_launch(const int8_t* qkv, int8_t* out, int64_t ldo, 
     const size_t band_bytes = a.band ? (size_t)WPB * 16 * (band_w + WBAND_PAD) * sizeof(unsigned) : 0;
     const dim3 grd(grid < 8192 ? grid : 8192), blk(NT);
     hipStream_t st = ivit_stream(stream);
-    if (long_rows) {
-        const int kp = 16 * ((tokens + 15) >> 4);
-        if (a.band) {
-            if (a.rq32) hipLaunchKernelGGL((window_attention_long_kernel<2, true>), grd, blk, band_bytes, st, a, kp);
-            else hipLaunchKernelGGL((window_attention_long_kernel<2, false>), grd, blk, band_bytes, st, a, kp);
-        } else if (a.phi) {
-            if (a.rq32) hipLaunchKernelGGL((window_attention_long_kernel<1, true>), grd, blk, 0, st, a, kp);
-            else hipLaunchKernelGGL((window_attention_long_kernel<1, false>), grd, blk, 0, st, a, kp);
-        } else {
-            if (a.rq32) hipLaunchKernelGGL((window_attention_long_kernel<0, true>), grd, blk, 0, st, a, kp);
-            else hipLaunchKernelGGL((window_attention_long_kernel<0, false>), grd, blk, 0, st, a, kp);
-        }
-        IVIT_CHECK_LAUNCH("ivit_window_attention_i8_long");
-    }
-    if (a.band) {
-        if (a.rq32) hipLaunchKernelGGL((window_attention_kernel<2, true>), grd, blk, band_bytes, st, a);
-        else hipLaunchKernelGGL((window_attention_kernel<2, false>), grd, blk, band_bytes, st, a);
-    } else if (a.phi) {
-        if (a.rq32) hipLaunchKernelGGL((window_attention_kernel<1, true>), grd, blk, 0, st, a);
-        else hipLaunchKernelGGL((window_attention_kernel<1, false>), grd, blk, 0, st, a);
-    } else {
-        if (a.rq32) hipLaunchKernelGGL((window_attention_kernel<0, true>), grd, blk, 0, st, a);
-        else hipLaunchKernelGGL((window_attention_kernel<0, false>), grd, blk, 0, st, a);
-    }
+    const int kp = 16 * ((tokens + 15) >> 4);
+    winattn_dispatch(a.band ? 2 : a.phi ? 1 : 0, a.rq32 != 0, long_rows, [&](auto SM, auto RQ32, auto NKT) {
+        hipLaunchKernelGGL((window_attention_kernel<SM.value, RQ32.value, NKT.value>), grd, blk, band_bytes, st, a, kp);
+    });
+    if (long_rows) IVIT_CHECK_LAUNCH("ivit_window_attention_i8_long");
     IVIT_CHECK_LAUNCH("ivit_window_attention_i8");
 }
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-kernel resource table of one HIP source, and its comparison with an earlier build of the same source.
 
-  kernel_table.py NEW.s NEW.remarks [OLD.s OLD.remarks] [--match REGEX] [--csv OUT]
+  kernel_table.py NEW.s NEW.remarks [OLD.s OLD.remarks] [--match REGEX] [--csv OUT] [--rename REGEX=REPL ...]
 
 NEW.s / OLD.s:       hipcc ... -S --cuda-device-only
 NEW.remarks / OLD..: stderr of hipcc ... -Rpass-analysis=kernel-resource-usage
@@ -9,7 +9,9 @@ NEW.remarks / OLD..: stderr of hipcc ... -Rpass-analysis=kernel-resource-usage
 Prints one row per kernel whose demangled name matches REGEX (default: every kernel): VGPRs, scratch bytes per lane, occupancy
 (waves per SIMD), number of device instructions; with an OLD build also the old figures and whether the opcode sequence (mnemonics
 only: register numbering and label names may differ) is the same.  Kernels outside REGEX are only compared: the script ends with
-status 1 when one of them changed its opcode sequence."""
+status 1 when one of them changed its opcode sequence.  --rename rewrites the demangled names of the OLD build (re.sub) before the
+two are paired, for kernels that changed their name or template arguments, e.g.
+  --rename 'window_attention_long_kernel<(.*)>=window_attention_kernel<\1, 9>' 'window_attention_kernel<(\d, \w+)>$=window_attention_kernel<\1, 4>'"""
 import argparse
 import csv
 import re
@@ -47,21 +49,30 @@ def main():
     ap.add_argument("files", nargs="+")
     ap.add_argument("--match", default=".")
     ap.add_argument("--csv")
+    ap.add_argument("--rename", nargs="*", default=[])
     args = ap.parse_args()
-    new_ops, new_res = opcodes(args.files[0]), parse(open(args.files[1], errors="replace").read())
-    old_ops, old_res = (opcodes(args.files[2]), parse(open(args.files[3], errors="replace").read())) if len(args.files) == 4 else ({}, {})
-    names = demangle(sorted(set(new_res) | set(old_res)))
+    def load(s_path, remarks_path, renames=()):
+        """demangled kernel name -> (resources, opcode list)"""
+        ops, res = opcodes(s_path), parse(open(remarks_path, errors="replace").read())
+        names = demangle(sorted(res))
+        for r in renames:
+            pat, repl = r.split("=", 1)
+            names = {k: re.sub(pat, repl, v) for k, v in names.items()}
+        return {names[k]: (res[k], ops[k]) for k in res}
+
+    new = load(args.files[0], args.files[1])
+    old = load(args.files[2], args.files[3], args.rename) if len(args.files) == 4 else {}
     rows, changed_outside = [], []
-    for k in sorted(names, key=names.get):
-        n, o = new_res.get(k), old_res.get(k)
-        same = "" if not (n and o) else "same" if new_ops.get(k) == old_ops.get(k) else "differs"
-        if not re.search(args.match, names[k]):
+    for name in sorted(set(new) | set(old)):
+        (n, n_ops), (o, o_ops) = new.get(name, (None, None)), old.get(name, (None, None))
+        same = "" if not (n and o) else "same" if n_ops == o_ops else "differs"
+        if not re.search(args.match, name):
             if same == "differs":
-                changed_outside.append(names[k])
+                changed_outside.append(name)
             continue
         f = lambda r, key: "" if r is None else r.get(key, "")
-        rows.append([names[k], f(n, "VGPRs"), f(n, "Scratch"), f(n, "Occupancy"), len(new_ops[k]) if n else "",
-                     f(o, "VGPRs"), f(o, "Scratch"), f(o, "Occupancy"), len(old_ops[k]) if o else "", same or ("new" if n else "gone")])
+        rows.append([name, f(n, "VGPRs"), f(n, "Scratch"), f(n, "Occupancy"), len(n_ops) if n else "",
+                     f(o, "VGPRs"), f(o, "Scratch"), f(o, "Occupancy"), len(o_ops) if o else "", same or ("new" if n else "gone")])
     head = ["kernel", "vgprs", "scratch", "occupancy", "instructions", "parent_vgprs", "parent_scratch", "parent_occupancy",
             "parent_instructions", "opcodes"]
     if args.csv:

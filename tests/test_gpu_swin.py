@@ -399,6 +399,46 @@ def test_window_attention_rejects_unsupported_geometry():
                   1 << 30, 40, 1 << 30, 31, 0.25, 1 << 30, 40, st())
 
 
+@pytest.mark.parametrize("N,entry", [(16, "ivit_window_attention_i8"), (81, "ivit_window_attention_i8_long")])
+def test_window_attention_second_pass(N, entry):
+    """More (window, head) pairs than the grid cap holds waves for (4 x 8192 = 32768): the last 40 of the 16404 x 2 pairs are a second
+    trip of a wave's pair loop, which rewrites the wave's V^T tile behind the first pair's reads.  Window w carries the data of window
+    w mod 20 (32768 mod 40 = 8: a wave's second pair differs from its first), so the oracle runs on 20 windows and is tiled."""
+    nwin, period, nH, hd, nW = 16404, 20, 2, 32, 1
+    ws_ = int(round(np.sqrt(N)))
+    kp = 64 if N <= 64 else (N + 15) // 16 * 16
+    rng = np.random.default_rng(N)
+    qkv = rng.integers(-128, 128, size=(3, period, nH, N, hd)).astype(np.int8)
+    s_S, s_at = np.float32(2.0 ** -9), np.float32(0.25)
+    ms, omS = sme(s_S, s_at), ome(s_S, s_at)
+    mb, omB = sme(s_at * np.float32(0.5), s_at), ome(s_at * np.float32(0.5), s_at)
+    assert int(ms[0]) & (int(ms[0]) - 1) == 0 and int(mb[0]) & (int(mb[0]) - 1) == 0      # power-of-two scores
+    mo, omO = sme(np.float32(2.0 ** -7 * 0.05), 0.043), ome(np.float32(2.0 ** -7 * 0.05), 0.043)
+    bias_add = rng.integers(-60, 61, size=(nH, N, N)).astype(np.int16)
+    bias_pad = np.full((nH, N, kp), 99, np.int16)
+    bias_pad[:, :, :N] = bias_add
+    mval = int(np.float32(-100.0) / s_at)
+    region = np.full((nW, kp), 200, np.uint8)
+    region[:, :N] = rng.integers(0, 4, size=(nW, N))
+    mask_add = np.where(region[:, :N, None] != region[:, None, :N], mval, 0).astype(np.int16)
+    ref, _, Pm = window_attention_ref(qkv[0], qkv[1], qkv[2], bias_add, mask_add, nW, omS, omB, s_at, omO)
+    assert Pm.max() > 0
+    reps = -(-nwin // period)
+    assert nwin * nH > 4 * 8192 and (4 * 8192) % (period * nH) != 0
+    qkv_d = dev(qkv).repeat(1, reps, 1, 1, 1)[:, :nwin].contiguous()
+    ld = nH * hd
+    out = torch.zeros(nwin * N, ld, dtype=torch.int8, device=DEV)
+    head = (_lib.ptr(qkv_d), _lib.ptr(out), ld, _lib.ptr(dev(bias_pad)), _lib.ptr(dev(region)), mval, nwin, nW, nH, N, hd,
+            ms[0], ms[1], mb[0], mb[1], float(s_at), mo[0], mo[1])
+    if entry == "ivit_window_attention_i8":
+        _lib.call(entry, *head, st())
+    else:
+        _lib.call(entry, *head, None, None, None, 0, 0, ws_, ws_, ws_, 0, 0, st())      # window order
+    got = out.cpu().numpy().reshape(nwin, N, ld)
+    want = np.tile(ref.astype(np.int8), (reps, 1, 1))[:nwin]
+    assert np.array_equal(got, want), f"windows {np.unique(np.nonzero(got != want)[0])[:8]} differ"
+
+
 # ----------------------------------------------------------------------------------- whole model
 def build_swin(max_batch, tag="swin_tiny"):
     z, meta, ranges = load_fixture(tag)
