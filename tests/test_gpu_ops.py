@@ -247,6 +247,11 @@ def test_gemm_requant_residual(M, N, K):
         assert torch.equal(inpl, out), (s_main, s_res, s_out)
 
 
+def _head_major(X, B, T, H, hd):
+    """the q/k/v epilogue's rearrangement: [B * T, 3 * H * hd] -> [3, B, H, T, hd]"""
+    return X.reshape(B, T, 3, H, hd).transpose(2, 0, 3, 1, 4)  # vit_quant.py:65-66
+
+
 @pytest.mark.parametrize("B,H", [(3, 3), (11, 6)])
 def test_gemm_requant_qkv_layout(B, H):
     rng = np.random.default_rng(12 + B)
@@ -257,8 +262,7 @@ def test_gemm_requant_qkv_layout(B, H):
     W = rng.integers(-128, 128, size=(N, K)).astype(np.int8)
     b = rng.integers(-50000, 50000, size=N).astype(np.int32)
     m, e = rand_me(rng, N, -16, -9)
-    exp = orc.requant(orc.gemm_i8(A, W, b), m.astype(np.float64), e, 8)
-    exp = exp.reshape(B, T, 3, H, hd).transpose(2, 0, 3, 1, 4)  # vit_quant.py:65-66
+    exp = _head_major(orc.requant(orc.gemm_i8(A, W, b), m.astype(np.float64), e, 8), B, T, H, hd)
     out = torch.empty(3 * M * Cn, dtype=torch.int8, device=DEV)
     md, ed = me_dev(m, e)
     _lib.call("ivit_gemm_i8_requant_qkv", _lib.ptr(dev(A)), K, _lib.ptr(dev(W)), K, _lib.ptr(dev(b)), _lib.ptr(md),
@@ -302,8 +306,9 @@ def _block_layout_host(X):
     rows, K = X.shape
     R16 = (rows + 15) // 16
     out = np.zeros(R16 * 16 * K, dtype=np.int8)
-    r = np.arange(rows)[:, None]
-    c = np.arange(K)[None, :]
+    idt = np.int32 if out.size < 2 ** 31 else np.int64      # the offsets of a large operand: half the index traffic
+    r = np.arange(rows, dtype=idt)[:, None]
+    c = np.arange(K, dtype=idt)[None, :]
     rl = r & 15
     off = ((r >> 4) * (K >> 6) + (c >> 6)) * 1024 + (((rl << 2) + (((c >> 4) & 3) ^ ((rl >> 2) & 3))) << 4) + (c & 15)
     out[off.reshape(-1)] = X.reshape(-1)
@@ -509,6 +514,11 @@ def test_gemm_weights_in_registers_ties_and_failed_certificates(M, N, K):
 
     ref = run_all()
     assert np.array_equal(ref[0][: M * N], ref[1][: M * N])
+    # the block-layout output and the head-major q/k/v output are the row-major bytes rearranged (pad rows of the blocks stay zero)
+    rm = ref[0][: M * N].reshape(M, N)
+    assert np.array_equal(ref[2], _block_layout_host(rm))
+    if qkv:
+        assert np.array_equal(ref[3], _head_major(rm, M // 197, 197, N // 192, 64).reshape(-1))
     # and a slice against the oracle (the first 300 rows and the last 200: first and last tiles of the launch)
     rows = np.r_[0:300, M - 200:M]
     exp = orc.requant(orc.gemm_i8(A[rows], W, b), m.astype(np.float64), e, 8)
