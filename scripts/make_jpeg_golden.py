@@ -5,6 +5,10 @@ the large ones.  Fallback cases (progressive, CMYK, PNG) carry their pixels too.
 only, and the GPU tests compare the device decoder with it without Pillow.
 
     python scripts/make_jpeg_golden.py
+
+A second entry point writes tests/golden/jpeg_batches_pil.npz, the files of the device decoder's batch tests (below):
+
+    python scripts/make_jpeg_golden.py batches
 """
 import hashlib
 import io
@@ -95,5 +99,82 @@ def main():
     print(path, os.path.getsize(path), "bytes")
 
 
+# ------------------------------------------------------------------------------------------------------------------------------
+# tests/golden/jpeg_batches_pil.npz: files for the device decoder's batch tests (tests/test_jpeg_batches_cpu.py says what each
+# structured file has to be).  JPEG bytes, sizes and the SHA-256 of Pillow's pixels; no pixels: the host decoder supplies them
+# and the CPU test ties it to the hash.  A seed of its own: the first fixture's random stream is untouched.
+
+BATCHES_SEED = 20261019
+BATCHES_DATA_MAX = 1_000_000      # JPEG bytes in the fixture; the file stays under 1 MiB
+
+# name, (h, w), mode, sigma, save arguments
+STRUCTURED = [
+    # several restart segments of 8-40 subsequences, >= 150 in all
+    ("rows_mid", (256, 384), "RGB", 10, dict(quality=92, subsampling=0, restart_marker_rows=2)),
+    # two restart segments, the first longer than 256 subsequences (20 of the 28 MCU rows)
+    ("two_long", (448, 448), "RGB", 22, dict(quality=97, subsampling=2, restart_marker_rows=20)),
+    # noise at quality 100: long codewords, slow self-synchronisation; one segment of 100-300 subsequences
+    ("noise_q100", (124, 124), "RGB", 60, dict(quality=100, subsampling=0)),
+    # an interval that does not divide 256, segments of 2 and 3 subsequences
+    ("blocks37_opt", (200, 300), "RGB", 6, dict(quality=85, subsampling=1, optimize=True, restart_marker_blocks=37)),
+    # thin images: downsampled widths / heights of 1 and 2, where libjpeg-turbo replicates instead of interpolating
+    ("thin_130x2_420", (130, 2), "RGB", 8, dict(quality=90, subsampling=2)),
+    ("thin_2x130_420", (2, 130), "RGB", 8, dict(quality=90, subsampling=2)),
+    ("thin_3x200_422", (3, 200), "RGB", 8, dict(quality=90, subsampling=1)),
+    ("thin_200x3_422", (200, 3), "RGB", 8, dict(quality=90, subsampling=1)),
+    ("thin_1x64_444", (1, 64), "RGB", 8, dict(quality=90, subsampling=0)),
+    ("thin_64x1_444", (64, 1), "RGB", 8, dict(quality=90, subsampling=0)),
+    ("thin_17x1_gray", (17, 1), "L", 8, dict(quality=90)),
+]
+RANDOM_MIN = 130
+RANDOM_DRAWS = 400
+
+
+def build_batches():
+    """the arrays of jpeg_batches_pil.npz"""
+    import sys
+    for p in (ROOT, os.path.join(ROOT, "tests")):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+    from test_jpeg_cpu import _random_jpeg      # the CPU test's distribution, not a copy of it
+
+    rng = np.random.default_rng(BATCHES_SEED)
+    names, blobs = [], []
+    for name, (h, w), mode, sigma, kw in STRUCTURED:
+        names.append(name)
+        blobs.append(encode(textured(rng, h, w, sigma), mode, kw))
+    total = sum(len(b) for b in blobs)
+    for _ in range(RANDOM_DRAWS):                 # as many small random files as the size cap allows
+        data, kw = _random_jpeg(rng, Image)
+        if data is None or total + len(data) > BATCHES_DATA_MAX:
+            continue
+        names.append(f"random_{len(names) - len(STRUCTURED):03d}")
+        blobs.append(data)
+        total += len(data)
+    assert len(names) - len(STRUCTURED) >= RANDOM_MIN, len(names)
+    sizes, sha = [], []
+    for data in blobs:
+        px = np.asarray(Image.open(io.BytesIO(data)).convert("RGB"))
+        sizes.append(px.shape[:2])
+        sha.append(np.frombuffer(hashlib.sha256(px.tobytes()).digest(), np.uint8))
+    data_off = np.concatenate([[0], np.cumsum([len(b) for b in blobs])]).astype(np.int64)
+    return dict(names=np.array(names), data=np.concatenate([np.frombuffer(b, np.uint8) for b in blobs]), data_off=data_off,
+                sizes=np.array(sizes, np.int32), sha256=np.stack(sha))
+
+
+def main_batches():
+    z = build_batches()
+    for i, name in enumerate(z["names"][:len(STRUCTURED)]):
+        print(f"{name:28s} {int(z['data_off'][i + 1] - z['data_off'][i]):8d} bytes")
+    print(len(z["names"]) - len(STRUCTURED), "random files,", int(z["data_off"][-1]), "bytes of JPEG in all")
+    path = os.path.join(ROOT, "tests", "golden", "jpeg_batches_pil.npz")
+    np.savez_compressed(path, **z)
+    print(path, os.path.getsize(path), "bytes")
+
+
 if __name__ == "__main__":
-    main()
+    import sys
+    if sys.argv[1:] == ["batches"]:
+        main_batches()
+    else:
+        main()
