@@ -684,11 +684,19 @@ struct WinAttnArgs {
     // row-wise, so attn.proj and the residual QuantAct behind it then need no row map (and fuse into one GEMM)
     WinMap omap;
     int omap_inv;           // 65536 / ws + 1: (q * omap_inv) >> 16 == q / ws for q < T (NKT 4: q < 64)
+    // SM 3, IBERTIntSoftmax (ibert_modules.py:237-319): exp_int behind its internal 16-bit QuantAct as the float32 the reference sums,
+    // ib_tab[(qmax + 128) * 256 + q + 128] (ivit_ibert_softmax_build_table), or with band_w > 0 its band form
+    // ib_tab[(qmax + 128) * band_w + min(qmax - q, band_w - 1)]; ib_sat: the one value of a score under the shift mask (the host
+    // proves that every such score lands on int_exp's clamp and none is a row maximum, prepare.ibert_window_mask_ok)
+    const float* ib_tab;
+    float ib_sat;
 };
 
 constexpr int WHD = 32;
 constexpr int WBAND_PAD = 4;     // dwords: keeps the slices 16-byte aligned and rotates their banks
 
+// SM 3: IBERTIntSoftmax from its (row max, q) table; the 16 x T exponents of a query tile pass through the wave's slice of the dynamic
+// LDS so that the four lanes of a query add them in torch's float32 order (window_rowsum below); p reaches 128 (split_p128).
 // SM: Shiftmax form -- 0 the table of distances to the row maximum (power-of-two scales; natural scales whose band table has one
 // row), 1 the literal float32 sequence on the phi tables, 2 band rows per row maximum staged through LDS.  Template parameters, not
 // run-time branches: with all three forms in one body the kernel took 135 VGPRs = three workgroups per CU instead of four, and the
@@ -699,6 +707,50 @@ constexpr int WBAND_PAD = 4;     // dwords: keeps the slices 16-byte aligned and
 // kp_long: the bias / region row stride of NKT 9 (NKT 4 folds the literal 64).  A kernel parameter of its own, not a field of
 // WinAttnArgs: as a field its scalar load merges with the neighbouring ones and the six NKT 9 forms lose the instruction sequence
 // they were measured with (HISTORY.md §9).
+// float32 sum of e[0 .. n - 1], 2 <= n <= 144, in the order of torch's CPU sum kernel (rowsum.h torch_rowsum, restated for ONE row per
+// four lanes): with n / 8 <= 18 vectors the cascade never folds (its level step is 16 groups of four vectors), so partial p = key % 32
+// adds its n / 32 elements in turn, the vectors past the last whole group of four join partials 0..7, lane sum l is
+// ((P[l] + P[l+8]) + P[l+16]) + P[l+24], and the scalar tail goes first into the accumulator that then takes the eight lane sums.
+// Lane g of the query computes lane sums 2g and 2g + 1; every lane of the wave calls it (gather4 exchanges).
+IVIT_DEV float window_rowsum(const float* e, int n, int g)
+{
+    if (n < 8) {      // scalar_inner_sum: four accumulators
+        float ps[4] = {0.f, 0.f, 0.f, 0.f};
+        const int size_ilp = n >> 2;
+        for (int i = 0; i < size_ilp; ++i)
+            for (int k = 0; k < 4; ++k) ps[k] += e[i * 4 + k];
+        for (int i = size_ilp * 4; i < n; ++i) ps[0] += e[i];
+        for (int k = 1; k < 4; ++k) ps[0] += ps[k];
+        return ps[0];
+    }
+    const int vec_size = n >> 3, size_ilp = vec_size >> 2;
+    float v[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int l = 2 * g + j;
+        float P[4];
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            float acc = 0.f;
+            for (int i = 0; i < size_ilp; ++i) acc += e[i * 32 + l + 8 * m];
+            P[m] = acc;
+        }
+        for (int i = size_ilp * 4; i < vec_size; ++i) P[0] += e[i * 8 + l];
+        v[j] = ((P[0] + P[1]) + P[2]) + P[3];
+    }
+    float t0[4], t1[4];
+    gather4(v[0], t0);
+    gather4(v[1], t1);
+    float fin = 0.f;
+    for (int i = vec_size * 8; i < n; ++i) fin += e[i];
+#pragma unroll
+    for (int gp = 0; gp < 4; ++gp) {
+        fin += t0[gp];
+        fin += t1[gp];
+    }
+    return fin;
+}
+
 template <int SM, bool RQ32, int NKT>
 __global__ __launch_bounds__(NT, NKT == 4 ? 4 : 2) void window_attention_kernel(WinAttnArgs a, int kp_long)
 {
@@ -708,14 +760,15 @@ __global__ __launch_bounds__(NT, NKT == 4 ? 4 : 2) void window_attention_kernel(
     constexpr int LUT_OFF = WPB * VT_BYTES;
     __shared__ __attribute__((aligned(16))) char smem[LUT_OFF + 256 * 4];
     __shared__ float s_phi[2][256];
-    extern __shared__ __attribute__((aligned(16))) unsigned band_lds[];     // [4 waves][16 queries][band_w + WBAND_PAD], band form only
+    extern __shared__ __attribute__((aligned(16))) unsigned band_lds[];     // [4 waves][16 queries][band_w + WBAND_PAD], band form; SM 3:
+                                                                            // [4 waves][16 queries][kp + 1] exponents
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = lane >> 4, l15 = lane & 15;
     const int T = a.T;
     const int nkt = NKT == 4 ? NKT : (T + 15) >> 4, nks = (nkt + 3) >> 2;     // NKT 9: 5..9 key tiles, 2..3 key steps
     const int kp = NKT == 4 ? 64 : kp_long;
-    reinterpret_cast<unsigned*>(smem + LUT_OFF)[tid] = a.band1 ? a.band1[min(tid, a.band_w - 1)] : shiftexp_int(-tid, a.x0, 15);
-    constexpr bool band = SM == 2, compat = SM == 1;
+    constexpr bool band = SM == 2, compat = SM == 1, ibert = SM == 3;
+    if constexpr (!ibert) reinterpret_cast<unsigned*>(smem + LUT_OFF)[tid] = a.band1 ? a.band1[min(tid, a.band_w - 1)] : shiftexp_int(-tid, a.x0, 15);
     if constexpr (compat) {
         s_phi[0][tid] = a.phi[tid];
         s_phi[1][tid] = a.phim[tid];
@@ -838,7 +891,7 @@ __global__ __launch_bounds__(NT, NKT == 4 ? 4 : 2) void window_attention_kernel(
                         }
                         const bool masked = ((kreg[kt] >> (8 * r)) & 0xffu) != qreg;
                         if constexpr (compat) xv[kt][r] = s_phi[masked ? 1 : 0][ka + 128];
-                        if (masked) ka = band ? -50000 : ka + a.mask_value;                      // shift mask, after the clamp
+                        if (masked) ka = (band || ibert) ? -50000 : ka + a.mask_value;           // shift mask, after the clamp
                         if constexpr (NKT > 4) s[kt][r] = ka;
                     }
                     if constexpr (NKT == 4) s[kt][r] = ka;
@@ -848,7 +901,36 @@ __global__ __launch_bounds__(NT, NKT == 4 ? 4 : 2) void window_attention_kernel(
             }
             rmax = rows_allmax_i32(rmax);      // over the four lanes of a query (common.h: permlane swaps, no LDS round trip)
             unsigned esum = 0;
-            if constexpr (compat) {
+            float isum = 0.0f;
+            if constexpr (ibert) {
+                // IBERTIntSoftmax: e = table[row max][q] (float32), a masked score the saturated value (never the maximum: its own key
+                // is unmasked), S = e.sum() in torch's float32 order over the T keys of the row (:311)
+                const int rm = max(rmax, -128);
+                const float* trow = a.ib_tab + (a.band_w ? (rm + 128) * a.band_w : ((rm + 128) << 8) + 128);
+                float* erow = reinterpret_cast<float*>(band_lds) + (wave * 16 + l15) * (kp + 1);
+                __builtin_amdgcn_wave_barrier();      // the previous tile's sums are done
+#pragma unroll
+                for (int kt = 0; kt < NKT; ++kt) {
+                    if (NKT > 4 && kt >= nkt) {      // uniform; no key here
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) s[kt][r] = 0;
+                        continue;
+                    }
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int sc = s[kt][r];
+                        float e = 0.0f;
+                        if (sc == -50000) e = a.ib_sat;
+                        else if (sc != -100000) e = a.band_w ? trow[min(rm - sc, a.band_w - 1)] : trow[sc];
+                        s[kt][r] = __float_as_int(e);
+                        erow[16 * kt + 4 * g + r] = e;
+                    }
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                isum = window_rowsum(erow, T, g);
+            } else if constexpr (compat) {
                 // Shiftmax's float32 sequence on the phi values themselves (ivit_modules.py:150-170), per score
                 xmax = fmaxf(xmax, __shfl_xor(xmax, 16));
                 xmax = fmaxf(xmax, __shfl_xor(xmax, 32));
@@ -911,10 +993,17 @@ __global__ __launch_bounds__(NT, NKT == 4 ? 4 : 2) void window_attention_kernel(
                         esum += e;
                     }
             }
-            const float factor = shiftmax_factor(rows_allsum_u32(esum));
+            float factor;
+            if constexpr (ibert) factor = floorf(4294967296.0f / isum) * 0.5f;      // ibert_modules.py:313; the half: see below
+            else factor = shiftmax_factor(rows_allsum_u32(esum));
             // NKS 1: built in pk0 -- with element writes into an array of ONE vector the compiler unrolled the query-tile loop four times
             // (SM 1: 128 VGPRs and scratch)
             v4i pk[NKS], pk0;
+            // I-BERT: p = floor(fl32(e * factor) / 2^25) in [0, 128] (:314, output_bit 8).  Halving the factor is exact, so
+            // trunc(fl32(e * (factor / 2))) <= 2^31 has p in its top byte; p = 128 (a one-hot row) is the byte 0x80, one more than an int8
+            // MFMA operand holds: 127 stays in pk, the 1 goes to pkh, a second P.V operand issued only where a wave holds such a byte
+            v4i pkh[ibert ? NKS : 1];
+            unsigned any_u = 0;
 #pragma unroll
             for (int ks = 0; ks < NKS; ++ks)
 #pragma unroll
@@ -923,7 +1012,10 @@ __global__ __launch_bounds__(NT, NKT == 4 ? 4 : 2) void window_attention_kernel(
                     if (4 * ks + t < NKT) {
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
-                            const float pr = (float)(unsigned)s[4 * ks + t][r] * factor;     // :175
+                            float pr;
+                            if constexpr (ibert) pr = __int_as_float(s[4 * ks + t][r]) * factor;
+                            else pr = (float)(unsigned)s[4 * ks + t][r] * factor;     // :175
+                            if constexpr (ibert) any_u |= (unsigned)pr;
                             w |= ((((unsigned)pr) >> 24) & 0xffu) << (8 * r);
                         }
                     }
@@ -931,6 +1023,19 @@ __global__ __launch_bounds__(NT, NKT == 4 ? 4 : 2) void window_attention_kernel(
                     else pk[ks][t] = (int)w;
                 }
             if constexpr (NKS == 1) pk[0] = pk0;
+            bool any_hi = false;
+            if constexpr (ibert) {
+                any_hi = __builtin_amdgcn_ballot_w64((any_u >> 31) != 0) != 0;      // wave-uniform, rare
+#pragma unroll
+                for (int ks = 0; ks < NKS; ++ks)
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) {
+                        unsigned lo = (unsigned)pk[ks][t], hi = 0u;
+                        if (any_hi) split_p128((unsigned)pk[ks][t], lo, hi);
+                        pk[ks][t] = (int)lo;
+                        pkh[ks][t] = (int)hi;
+                    }
+            }
             int64_t orow_idx = (int64_t)win * T + qrow;
             if (a.omap.ws) {      // window reverse + roll back: (iy, ix) of the query in its window -> (y, x) of the image
                 const int qr = min(qrow, T - 1);
@@ -949,7 +1054,12 @@ __global__ __launch_bounds__(NT, NKT == 4 ? 4 : 2) void window_attention_kernel(
                 v4i acc = {0, 0, 0, 0};
 #pragma unroll
                 for (int ks = 0; ks < NKS; ++ks)
-                    if (ks < nks) acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(*reinterpret_cast<const v4i*>(vrow + 64 * ks), pk[ks], acc, 0, 0, 0);
+                    if (ks < nks) {
+                        acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(*reinterpret_cast<const v4i*>(vrow + 64 * ks), pk[ks], acc, 0, 0, 0);
+                        if constexpr (ibert) {
+                            if (any_hi) acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(*reinterpret_cast<const v4i*>(vrow + 64 * ks), pkh[ks], acc, 0, 0, 0);
+                        }
+                    }
                 unsigned w = 0;
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
@@ -1176,7 +1286,7 @@ IVIT_EXPORT int ivit_window_attention_i8(const int8_t* qkv, int8_t* out, int64_t
 }
 
 // launch(integral_constant<SM>, bool_constant<RQ32>, integral_constant<NKT>) for the Shiftmax form, the score requantisation and
-// the row length the launcher chose: the twelve instantiations of window_attention_kernel
+// the row length the launcher chose: the sixteen instantiations of window_attention_kernel
 template <class F>
 static void winattn_dispatch(int sm, bool rq32, bool long_rows, F launch)
 {
@@ -1188,7 +1298,8 @@ static void winattn_dispatch(int sm, bool rq32, bool long_rows, F launch)
         if (rq32) by_nkt(SM, std::true_type());
         else by_nkt(SM, std::false_type());
     };
-    if (sm == 2) by_rq32(std::integral_constant<int, 2>());
+    if (sm == 3) by_rq32(std::integral_constant<int, 3>());
+    else if (sm == 2) by_rq32(std::integral_constant<int, 2>());
     else if (sm == 1) by_rq32(std::integral_constant<int, 1>());
     else by_rq32(std::integral_constant<int, 0>());
 }
@@ -1198,11 +1309,14 @@ static int window_attention_launch(const int8_t* qkv, int8_t* out, int64_t ldo, 
                                    int heads, int tokens, int head_dim, uint32_t m_s, int32_t e_s, uint32_t m_b,
                                    int32_t e_b, float s_attn, uint32_t m_o, int32_t e_o, const float* phi,
                                    const float* phi_masked, WinMap omap, ivit_stream_t stream, const uint32_t* band = nullptr,
-                                   int band_w = 0, int band_rows = 256, bool long_rows = false)
+                                   int band_w = 0, int band_rows = 256, bool long_rows = false, const float* ib_tab = nullptr,
+                                   float ib_sat = 0.0f)
 {
+    // ib_tab: the I-BERT softmax form (ivit_window_attention_i8_ibert, which has checked its own table): band_w is then the width of the
+    // table's band form, `band` NULL, and Shiftmax's s_attn / mask_value are not used
     IVIT_REQUIRE(qkv && out && bias_add, "ivit_window_attention_i8: NULL operand");
     // (16 band rows per wave in LDS: 4 x 16 x (192 + 4) dwords = 49 KB beside the kernel's 11 KB stay below the 64 KB of a default launch)
-    IVIT_REQUIRE(band_w == 0 ? band == nullptr : (band && band_w >= 16 && band_w <= 192 && band_w % 16 == 0 && (uintptr_t)band % 16 == 0),
+    IVIT_REQUIRE(ib_tab || band_w == 0 ? band == nullptr : (band && band_w >= 16 && band_w <= 192 && band_w % 16 == 0 && (uintptr_t)band % 16 == 0),
                  "ivit_window_attention_i8_band: the band table must be 16-byte aligned, its width a multiple of 16 in [16, 192]");
     IVIT_REQUIRE(windows > 0 && heads > 0 && windows_per_image > 0 && windows % windows_per_image == 0,
                  "ivit_window_attention_i8: bad window counts");
@@ -1218,9 +1332,10 @@ static int window_attention_launch(const int8_t* qkv, int8_t* out, int64_t ldo, 
                  "ivit_window_attention_i8: misaligned operand or ldo too small");
     IVIT_REQUIRE(((uintptr_t)bias_add % 8 == 0) && ((uintptr_t)mask_region % 4 == 0), "ivit_window_attention_i8: misaligned table");
     IVIT_REQUIRE(mask_value <= 0 && mask_value >= -32768, "ivit_window_attention_i8: mask_value=%d outside [-32768, 0]", mask_value);
-    IVIT_REQUIRE(s_attn > 0.0f, "ivit_window_attention_i8: scale must be positive");
+    IVIT_REQUIRE(ib_tab || s_attn > 0.0f, "ivit_window_attention_i8: scale must be positive");
     IVIT_REQUIRE((phi == nullptr) == (phi_masked == nullptr), "ivit_window_attention_i8_compat: phi and phi_masked go together");
     WinAttnArgs a;
+    a.ib_tab = ib_tab; a.ib_sat = ib_sat;
     a.omap = omap;
     a.omap_inv = omap.ws ? 65536 / omap.ws + 1 : 0;
     for (int qv = 0; qv < (long_rows ? tokens : 64) && omap.ws; ++qv)
@@ -1241,7 +1356,7 @@ static int window_attention_launch(const int8_t* qkv, int8_t* out, int64_t ldo, 
              !(g_ln_ablate & (1 << 23));      // lab bit 23: the float64 form (A/B, parity of both forms)
     a.Ms32 = (float)a.Ms;
     a.Mb32 = (float)a.Mb;
-    const float x0f = __builtin_floorf((1.0f / s_attn) * -1.0f);
+    const float x0f = ib_tab ? -1.0f : __builtin_floorf((1.0f / s_attn) * -1.0f);
     IVIT_REQUIRE(x0f <= -1.0f && x0f >= -4096.0f, "ivit_window_attention_i8: x0=%g outside [-4096,-1]", (double)x0f);
     a.x0 = (int)x0f;
     // exact u32 row sum: tokens * |x0| * 2^15 must stay below 2^32
@@ -1255,7 +1370,7 @@ static int window_attention_launch(const int8_t* qkv, int8_t* out, int64_t ldo, 
     }
     // the short form's (NKT 4) distance table gives a score under the shift mask the table's last entry: the saturated value only if the
     // table gets there within its 256 distances (x0 >= -24); the literal form (phi tables) is exact at any scale
-    IVIT_REQUIRE(long_rows || saturates || !mask_region || phi || band,
+    IVIT_REQUIRE(long_rows || saturates || !mask_region || phi || band || ib_tab,
                  "ivit_window_attention_i8: x0=%d: the integer form cannot place masked scores (use the phi tables)", a.x0);
     if (a.band1) {      // one row for every maximum: the distance table of the power-of-two form, with the host's values
         a.ksat = band_w - 1;
@@ -1263,13 +1378,17 @@ static int window_attention_launch(const int8_t* qkv, int8_t* out, int64_t ldo, 
     }
     const int npairs = windows * heads;
     const int grid = (npairs + WPB - 1) / WPB;
-    const size_t band_bytes = a.band ? (size_t)WPB * 16 * (band_w + WBAND_PAD) * sizeof(unsigned) : 0;
+    // I-BERT: the exponents of a query tile, [4 waves][16 queries][kp + 1] float32 (37 KB at 144 tokens, beside the kernel's 27 KB)
+    const size_t band_bytes = ib_tab  ? (size_t)WPB * 16 * ((long_rows ? 16 * ((tokens + 15) >> 4) : 64) + 1) * sizeof(float)
+                              : a.band ? (size_t)WPB * 16 * (band_w + WBAND_PAD) * sizeof(unsigned)
+                                       : 0;
     const dim3 grd(grid < 8192 ? grid : 8192), blk(NT);
     hipStream_t st = ivit_stream(stream);
     const int kp = 16 * ((tokens + 15) >> 4);
-    winattn_dispatch(a.band ? 2 : a.phi ? 1 : 0, a.rq32 != 0, long_rows, [&](auto SM, auto RQ32, auto NKT) {
+    winattn_dispatch(ib_tab ? 3 : a.band ? 2 : a.phi ? 1 : 0, a.rq32 != 0, long_rows, [&](auto SM, auto RQ32, auto NKT) {
         hipLaunchKernelGGL((window_attention_kernel<SM.value, RQ32.value, NKT.value>), grd, blk, band_bytes, st, a, kp);
     });
+    if (ib_tab) IVIT_CHECK_LAUNCH("ivit_window_attention_i8_ibert");
     if (long_rows) IVIT_CHECK_LAUNCH("ivit_window_attention_i8_long");
     IVIT_CHECK_LAUNCH("ivit_window_attention_i8");
 }
@@ -1339,6 +1458,37 @@ IVIT_EXPORT int ivit_window_attention_i8_long(const int8_t* qkv, int8_t* out, in
                                    head_dim, m_s, e_s, m_b, e_b, s_attn, m_o, e_o, phi, phi_masked,
                                    image_order ? WinMap{H, W, ws, shift} : WinMap{0, 0, 0, 0}, stream, band, band ? band_w : 0,
                                    band ? band_rows : 256, true);
+}
+
+IVIT_EXPORT int ivit_window_attention_i8_ibert(const int8_t* qkv, int8_t* out, int64_t ldo, const int16_t* bias_add,
+                                               const uint8_t* mask_region, float masked_exp, int windows, int windows_per_image, int heads,
+                                               int tokens, int head_dim, uint32_t m_s, int32_t e_s, uint32_t m_b, int32_t e_b, uint32_t m_o,
+                                               int32_t e_o, const float* table, int band_w, int H, int W, int ws, int shift, int image_order,
+                                               ivit_stream_t stream)
+{
+    if (head_dim != WHD || tokens < 2 || tokens > 144) {
+        ivit_set_error("ivit_window_attention_i8_ibert: unsupported geometry head_dim=%d tokens=%d (need 32, 2..144)", head_dim, tokens);
+        return IVIT_ERR_UNSUPPORTED;
+    }
+    if (ws != 0 && !(ws > 0 && ws * ws == tokens && H > 0 && W > 0 && H % ws == 0 && W % ws == 0 && shift >= 0 && shift < ws &&
+                     windows_per_image == (H / ws) * (W / ws))) {
+        ivit_set_error("ivit_window_attention_i8_ibert: H=%d W=%d ws=%d shift=%d do not describe %d windows of %d tokens per image", H, W,
+                       ws, shift, windows_per_image, tokens);
+        return IVIT_ERR_UNSUPPORTED;
+    }
+    if (band_w != 0 && (band_w < 16 || band_w > 256 || band_w % 16 != 0)) {
+        ivit_set_error("ivit_window_attention_i8_ibert: bad band table (width a multiple of 16 in [16, 256], or 0 for the full table)");
+        return IVIT_ERR_UNSUPPORTED;
+    }
+    IVIT_REQUIRE(table, "ivit_window_attention_i8_ibert: NULL operand");
+    IVIT_REQUIRE((uintptr_t)table % 16 == 0, "ivit_window_attention_i8_ibert: misaligned table");
+    IVIT_REQUIRE(image_order == 0 || (image_order == 1 && ws != 0),
+                 "ivit_window_attention_i8_ibert: image_order must be 0 or 1, and 1 needs the windows' geometry");
+    IVIT_REQUIRE(!mask_region || (masked_exp >= 0.0f && masked_exp <= 32768.0f),
+                 "ivit_window_attention_i8_ibert: masked_exp=%g outside [0, 32768]", (double)masked_exp);
+    return window_attention_launch(qkv, out, ldo, bias_add, mask_region, 0, windows, windows_per_image, heads, tokens, head_dim, m_s, e_s,
+                                   m_b, e_b, 1.0f, m_o, e_o, nullptr, nullptr, image_order ? WinMap{H, W, ws, shift} : WinMap{0, 0, 0, 0},
+                                   stream, nullptr, band_w, 256, tokens > 64, table, masked_exp);
 }
 
 IVIT_EXPORT int ivit_avgpool_requant_i8_literal(const int8_t* x, int8_t* out, int batch, int tokens, int C, float s_in, uint32_t m,

@@ -10,7 +10,7 @@ What differs, deliberately:
   * the reference always instantiates `deit_tiny_patch16_224` whatever `model_config['model_name']` says (:133); here
     the name selects the factory when it is one this package provides (DeiT-T/S/B, ViT-B/L, Swin-T/S/B) and falls back
     to DeiT-T otherwise;
-  * operator families: 'ivit' (fused engine) and 'ibert' (module path) exist; the reference's DEFAULTS are kept -- 'ibert'
+  * operator families: 'ivit' and 'ibert' exist, for DeiT / ViT and for Swin; the reference's DEFAULTS are kept -- 'ibert'
     when the saved configuration lacks a type (:111-113), and for a checkpoint without any configuration the reference
     picks its 'ppoly_...' GELU / softmax (:160-162), which this path does not implement: that case raises with a message
     naming the override to pass, instead of silently substituting another operator;
@@ -83,12 +83,9 @@ def build_model(model_config: Optional[dict] = None, num_classes: int = 1000, ge
         ops = dict(gelu_type=gelu_type if gelu_type is not None else cfg.get("gelu_type", "ibert"),       # :111-113
                    softmax_type=softmax_type if softmax_type is not None else cfg.get("softmax_type", "ibert"),
                    layernorm_type=layernorm_type if layernorm_type is not None else cfg.get("layernorm_type", "ibert"))
-    if factory.__name__.startswith("swin"):
-        for k, v in ops.items():
-            if not str(v).lower().startswith("ivit"):
-                raise KeyError(f"{k}={v!r}: the Swin models of the MI355X integer path implement the 'ivit' operators only (DeiT / ViT: 'ivit' and 'ibert')")
+    if factory.__name__.startswith("swin"):      # no per-site width arguments: the reference's Swin fixes its QuantAct widths
         return factory(pretrained=False, num_classes=cfg.get("num_classes", num_classes),
-                       drop_rate=cfg.get("drop_rate", 0.0), drop_path_rate=cfg.get("drop_path_rate", 0.1))
+                       drop_rate=cfg.get("drop_rate", 0.0), drop_path_rate=cfg.get("drop_path_rate", 0.1), **ops)
     bws = {k: (bitwidth if bitwidth is not None else cfg.get(k, 8)) for k in _BW_KEYS}
     return factory(pretrained=False, num_classes=cfg.get("num_classes", num_classes), drop_rate=cfg.get("drop_rate", 0.0),
                    drop_path_rate=cfg.get("drop_path_rate", 0.1), **bws, **ops)

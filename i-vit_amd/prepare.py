@@ -218,6 +218,38 @@ def window_shiftexp_band(s, masked: bool):
     return band, W
 
 
+def ibert_window_mask_ok(s, x0_int, n: int = 30) -> bool:
+    """May ivit_window_attention_i8_ibert take a shift mask at the scale s of attn.qact2?  The reference adds float -100 to the
+    float view fl(q*s) of a masked score (swin_quant.py:149-155) and IBERTIntSoftmax divides by s again (ibert_modules.py:303), so a
+    masked score is fl(fl(fl(q*s) - 100) / s), off the integer grid, and an unmasked one phi(q) = fl(fl(q*s) / s).  The kernel gives
+    every masked score ONE value and leaves it out of the row maximum.  That is what the reference computes iff, for every masked
+    q and every row maximum qm in [-128, 127] (the maximum is an unmasked score: a query always attends to itself),
+      (a) no masked value reaches an unmasked one: max(phi_m) < min(phi), and
+      (b) fl(phi_m(q) - phi(qm)) <= fl(n * x0_int): int_exp's clamp (:288) -- exp_int is then that of the clamp itself.
+    Evaluated in float32, step by step, on all 256 x 256 pairs.  Holds for about s <= 0.29 (100 / s - 255 >= 30 * ceil(0.6931 / s))."""
+    s = f32(s)
+    q = np.arange(-128, 128, dtype=f32)
+    ph = phi_table(s)
+    phm = ((((q * s).astype(f32) + f32(-100.0)).astype(f32)) / s).astype(f32)
+    d = (phm[None, :] - ph[:, None]).astype(f32)              # :305  x_int - x_int_max
+    return bool(phm.max() < ph.min() and np.all(d <= f32(f32(n) * f32(x0_int))))
+
+
+def ibert_saturated_exp(x0_int, b_int, c_int, exp_sf, act_sf, m, e, n: int = 30) -> np.float32:
+    """exp_int of IBERTIntSoftmax on int_exp's clamp n * x0_int, behind its internal 16-bit QuantAct, as the float32 the reference
+    sums (ibert_modules.py:288-295, 308-310; csrc/ibert.hip ib_exp_int and ibert_softmax_table_kernel restated): q = n, r = 0, so
+    the polynomial is c_int and the shift 2^0"""
+    x0, b, c = f32(x0_int), f32(b_int), f32(c_int)
+    x = f32(f32(n) * x0)
+    qq = np.floor(f32(x / x0))
+    r = f32(x - f32(x0 * qq))
+    z = f32(f32(r * f32(r + b)) + c)                          # :279-281
+    ex = max(np.floor(f32(z * np.ldexp(f32(1.0), int(n - qq)))), f32(0))     # :293
+    z_int = np.rint(f32(f32(ex) / f32(exp_sf)))               # the internal QuantAct(16): quant_utils.py:220-245
+    q16 = np.clip(np.rint(np.float64(z_int) * (np.float64(m) / np.exp2(np.float64(e)))), -32768.0, 32767.0)
+    return f32(f32(f32(q16) * f32(act_sf)) / f32(act_sf))     # :309-310
+
+
 def markstein_division_ok(s, bits: int = 16) -> bool:
     """Is the 3-instruction quotient by the invariant s -- q0 = fl(x*r), e = fma(-s, q0, x), fma(e, r, q0), r = fl(1/s) -- the
     correctly rounded fl(x / s) for EVERY x = fl(q*s), q a `bits`-bit integer?  (Markstein's theorem says yes unless the

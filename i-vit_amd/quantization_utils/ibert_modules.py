@@ -85,7 +85,8 @@ class IBERTIntLayerNorm(nn.Module):
     def forward(self, x, scaling_factor=None, exponents=None):
         if isinstance(x, lazy.QT):
             s_in = lazy.host_of(scaling_factor)
-            if (x.q8 is not None or x.q16 is not None) and s_in is not None and s_in.size == 1 and not self.overflow_handling:
+            # an int8 / int16 payload, or PatchMerging's cat of four int16 slices (swin_quant.py:337-345)
+            if lazy.int_width(x) is not None and s_in is not None and s_in.size == 1 and not self.overflow_handling:
                 def build():      # the scale this module returns: sqrt(C) / 2^30 * gamma (:145-153)
                     C_ = x.shape[-1]
                     sf = f32(np.sqrt(f32(C_)).astype(np.float32) / f32(2 ** 30))
@@ -194,8 +195,11 @@ class IBERTIntSoftmax(nn.Module):
 
     def forward(self, x, scaling_factor):
         if isinstance(x, lazy.QT):
-            if (isinstance(x.node, lazy.Scores) and not x.views and self.output_bit in (8, 16) and not self.act.running_stat
-                    and scaling_factor is x.node.s_out_qs):
+            # ViT's scores at either width; Swin's biased (and, through one reshape, masked) scores at 8 bits (swin_quant.py:143-156)
+            if (not self.act.running_stat and scaling_factor is getattr(x.node, "s_out_qs", None)
+                    and (isinstance(x.node, lazy.Scores) and not x.views and self.output_bit in (8, 16)
+                         or self.output_bit == 8 and x.dim() == 4 and (isinstance(x.node, lazy.Biased) and not x.views
+                                                                        or isinstance(x.node, lazy.Masked) and len(x.views) == 1))):
                 so = lazy._cache(self, ("s_out", str(x.device)), lambda: lazy.QS.make(f32(2 / 2 ** self.output_bit), x.device))   # :317
                 return lazy.QT.wrap(x.shape, x.device, node=lazy.Probs(x, self)), so
             x = x.to_float()

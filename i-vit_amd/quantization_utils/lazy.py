@@ -32,8 +32,9 @@ per module, so after the first (warm-up) forward a frozen forward reads nothing 
 `torch.cuda.set_sync_debug_mode("error")` and can be captured into a HIP graph (tests/test_gpu_modules.py, test_gpu_swin_lazy.py).
 Covers the I-ViT and the I-BERT operator families (ivit_modules.py, ibert_modules.py) at 8-bit QuantAct widths, ViT's 16-bit
 configurations (vit_quant.py:180-187: the 16-bit residual stream with softmax and position embedding at 8 or 16 bits, resolve16)
-and Swin with the I-ViT operators (8-bit QuantActs, 16-bit residual stream); other configurations (other width mixtures, mixed
-families) take the ordinary module path through the materialisation rule above wherever a step is not one of the patterns.
+and Swin with either family (8-bit QuantActs, 16-bit residual stream), in any mixture: every site is resolved by the class of its own
+module.  Other configurations (other width mixtures, operator names with constructor parameters) take the ordinary module path through
+the materialisation rule above wherever a step is not one of the patterns.
 """
 from __future__ import annotations
 
@@ -773,9 +774,12 @@ def resolve(qact, x, pre_sf, identity, identity_sf, s_out, s_out_qs):
                 base = node.inputs[0]
                 if isinstance(base, QT) and not x.views:
                     return QT.wrap(x.shape, device, node=Scores(x, pre_sf, s_out, s_out_qs, qact))
-                if isinstance(base, QT) and isinstance(base.node, Probs) and base.node.mod.output_bit == 16:
+                if isinstance(base, QT) and isinstance(base.node, Probs) and (
+                        base.node.mod.output_bit == 16 or (type(base.node.mod).__name__ == "IBERTIntSoftmax"
+                                                           and isinstance(base.node.x.node, (Biased, Masked)))):
                     # 16-bit probabilities without a fused kernel (I-BERT's softmax outside 193 .. 207 tokens, multipliers beyond
-                    # the long-row kernels' bounds): the attention core runs literally, its float result re-enters the integer
+                    # the long-row kernels' bounds), or Swin's I-BERT softmax under a shift mask the window kernel cannot take
+                    # (prepare.ibert_window_mask_ok): the attention core runs literally, its float result re-enters the integer
                     # stream here, so the rest of the forward is still carried
                     return resolve_float(qact, x.to_float(), pre_sf, s_out, s_out_qs)
     elif isinstance(node, Scaled) and identity is None and not x.views:
@@ -1131,14 +1135,11 @@ def _resolve_ibert_ln(node, s_out, device):
     ivit_ibert_layernorm_i16_i8_ex (csrc/ibert.hip), which work on fl(q * s_in) literally -- any input scale; the module's
     use_int_sqrt goes with the launch as IVIT_IBERT_LN_INT_SQRT"""
     ln, x = node.mod, node.inputs[0]
-    xq = q8_contig(x)
-    bits = 8
-    if xq is None:
-        xq, bits = q16_contig(x), 16
+    bits = int_width(x)
     s_in = host_of(node.scales[0])
-    if xq is None or s_in is None or s_in.size != 1 or ln.overflow_handling:
+    if bits is None or s_in is None or s_in.size != 1 or ln.overflow_handling:
         return None
-    return _layernorm(ln, xq, s_in, s_out, bits, device, ibert=True)
+    return _layernorm(ln, int_payload(x), s_in, s_out, bits, device, ibert=True)
 
 
 def _resolve_gelu(node, s_out, device):
@@ -1258,10 +1259,14 @@ def _mask_regions(mask, nW, N):
 def _resolve_window_attention(P, top, v, s_pv, s_out, device):
     """WindowAttention (swin_quant.py:137-161): matmul_1 -> * scale -> qact_attn1 -> qact2 with the relative position bias ->
     (+ mask) -> Shiftmax -> matmul_2 behind qact3, as one launch of the ivit_window_attention_i8* family, selected as
-    swin_engine.IntSwinEngine selects it (window order out)"""
-    from ..swin_engine import HEAD_DIM, LONG_WINDOW, window_attention, window_attention_spec
+    swin_engine.IntSwinEngine selects it (window order out); with IBERTIntSoftmax(8) in Shiftmax's place (softmax_type='ibert'),
+    ivit_window_attention_i8_ibert.  None -- the attention core then runs literally -- for any other softmax, and for a shift mask
+    the I-BERT entry cannot take (prepare.ibert_window_mask_ok)"""
+    from ..swin_engine import (HEAD_DIM, LONG_WINDOW, window_attention, window_attention_ibert, window_attention_ibert_spec,
+                               window_attention_spec)
     sm = P.node.mod
-    if type(sm).__name__ != "IVITIntSoftmax" or sm.output_bit != 8:
+    ibert = type(sm).__name__ == "IBERTIntSoftmax"
+    if not (ibert or type(sm).__name__ == "IVITIntSoftmax") or sm.output_bit != 8 or (ibert and sm.act.running_stat):
         return None
     mask = None
     if isinstance(top.node, Masked):
@@ -1281,7 +1286,7 @@ def _resolve_window_attention(P, top, v, s_pv, s_out, device):
     if hd != HEAD_DIM or not 2 <= N <= LONG_WINDOW or tuple(top.shape) != (B_, nH, N, N) or tuple(v.shape) != (B_, nH, N, hd):
         return None
     ws = int(round(N ** 0.5))
-    if N > 64 and ws * ws != N:
+    if N > 64 and ws * ws != N and not ibert:
         return None
     nW = 1
     if mask is not None:
@@ -1303,10 +1308,18 @@ def _resolve_window_attention(P, top, v, s_pv, s_out, device):
             region = _mask_regions(mask, nW, N)
             if region is None:
                 return None
+        if ibert:      # the range of the softmax's internal 16-bit QuantAct from its frozen buffers, as _resolve_attention takes it
+            act = sm.act
+            spec = window_attention_ibert_spec(lambda a: _dev(a, device), device, _st(), bias, s_tab, s_S, s_at, s_A, s_pv, s_out, region, N,
+                                               (float(act.x_min.reshape(-1)[0]), float(act.x_max.reshape(-1)[0])))
+            if spec is not None:
+                act.act_scaling_factor = torch.full((1,), spec["act_sf"], dtype=torch.float32, device=device)
+            return spec
         spec, _ = window_attention_spec(lambda a: _dev(a, device), bias, s_tab, s_S, s_at, s_A, s_pv, s_out, region, N)
         return spec
+    akey = (id(sm.act.x_min), sm.act.x_min._version, id(sm.act.x_max), sm.act.x_max._version) if ibert else ()
     a = _cache(bn.qact, ("wattn", ident.origin, mkey, _key(s_S, np.asarray(s_at), s_tab, np.asarray(s_A), s_pv, np.asarray(s_out)),
-                         str(device)), build)
+                         str(device)) + akey, build)
     if a is None:
         return None
     # ---- q, k, v head-major per window
@@ -1316,8 +1329,11 @@ def _resolve_window_attention(P, top, v, s_pv, s_out, device):
     C = nH * hd
     out = torch.empty(B_ * N, C, dtype=torch.int8, device=device)
     # window order out; the long entry takes the windows' geometry regardless (one row of nW windows), the band entry none
-    geometry = (ws * nW, ws, ws, 0) if a["long"] else (0, 0, 0, 0)
-    window_attention(a, hm, out, C, B_, nW, nH, N, *geometry, False, _st())
+    if ibert:
+        window_attention_ibert(a, hm, out, C, B_, nW, nH, N, 0, 0, 0, 0, False, _st())
+    else:
+        geometry = (ws * nW, ws, ws, 0) if a["long"] else (0, 0, 0, 0)
+        window_attention(a, hm, out, C, B_, nW, nH, N, *geometry, False, _st())
     return out.view(B_, N, nH, hd).permute(0, 2, 1, 3)
 
 

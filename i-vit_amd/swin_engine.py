@@ -22,8 +22,8 @@ import torch
 
 from . import _lib
 from .engine_common import EngineBase, _np, block_copy, frag_copy, layernorm
-from .prepare import (LayerNormParams, LinearParams, dyadic, dyadic1, f32, pad_head, phi_is_identity, phi_table, quant_sym,
-                      requant_host, sym_scale, window_shiftexp_band)
+from .prepare import (LayerNormParams, LinearParams, dyadic, dyadic1, f32, ibert_saturated_exp, ibert_window_mask_ok, pad_head,
+                      phi_is_identity, phi_table, quant_sym, requant_host, shiftexp_band, sym_scale, window_shiftexp_band)
 from .topk import TOPK_MAX
 
 PATCH = 4
@@ -90,6 +90,17 @@ def window_row_map(B: int, H: int, W: int, ws: int, shift: int) -> np.ndarray:
     return (np.arange(B)[:, None] * (H * W) + idx.reshape(-1)[None, :]).reshape(-1)
 
 
+def _bias_pad(bias, s_tab, s_A, N):
+    """the identity operand of attn.qact2 (swin_quant.py:143-147) as the kernels read it: RNE(k_tab * m / 2^e), int16 [nH, N, kp]"""
+    m2, e2 = dyadic(s_tab, s_A)
+    bias_add = requant_host(bias, m2[0], e2[0])
+    assert np.abs(bias_add).max() < 32768
+    kp = key_pad(N)
+    bias_pad = np.zeros((bias.shape[0], N, kp), np.int16)
+    bias_pad[:, :, :N] = bias_add
+    return bias_pad, kp
+
+
 def window_attention_spec(upload, bias, s_tab, s_S, s_at, s_A, s_pv, s_a3, region, N):
     """Constants of one window-attention launch (the ivit_window_attention_i8* family), shared by the engine and the module path
     (quantization_utils/lazy.py).  bias: the 8-bit relative position bias [nH, N, N] at scale s_tab (the identity operand of
@@ -97,14 +108,7 @@ def window_attention_spec(upload, bias, s_tab, s_S, s_at, s_A, s_pv, s_a3, regio
     s_a3 those around qact3; region [nW, N] the region ids of a shifted block's mask, or None.
     -> (dict of launch arguments, form): form is None on the integer kernel, else the natural-scale Shiftmax form ("band1xW" /
     "band256xW" / "literal", prepare.window_shiftexp_band)."""
-    nH = bias.shape[0]
-
-    m2, e2 = dyadic(s_tab, s_A)
-    bias_add = requant_host(bias, m2[0], e2[0])                    # identity operand of qact2, :143-147
-    assert np.abs(bias_add).max() < 32768
-    kp = key_pad(N)
-    bias_pad = np.zeros((nH, N, kp), np.int16)
-    bias_pad[:, :, :N] = bias_add
+    bias_pad, kp = _bias_pad(bias, s_tab, s_A, N)
     region_pad, mask_value = None, 0
     # Shiftmax input: phi(q) = fl(fl(q*s)/s) for a plain score, fl(fl(fl(q*s) - 100)/s) for one under the shift
     # mask (:149-156 adds float -100 to q*s, ivit_modules.py:165 divides by s).  Integer kernel when phi is the
@@ -161,6 +165,42 @@ def window_attention(a, qkv, out, ldo, nwin, nW, nH, N, H, W, win, shift, fuse_p
         _lib.call("ivit_window_attention_i8_unwindow", *head, a["mask_value"], *dims, p(a["phi"]), p(a["phim"]), H, W, win, shift, st)
     else:
         _lib.call("ivit_window_attention_i8_compat", *head, a["mask_value"], *dims, p(a["phi"]), p(a["phim"]), st)
+
+
+def window_attention_ibert_spec(upload, device, st, bias, s_tab, s_S, s_at, s_A, s_pv, s_a3, region, N, act_range, form=None):
+    """window_attention_spec for a WindowAttention whose softmax is IBERTIntSoftmax(8) (ivit_window_attention_i8_ibert).  act_range:
+    (x_min, x_max) of the softmax's internal 16-bit QuantAct.  form: "table" the [256][256] table of
+    ivit_ibert_softmax_build_table, "band" its band form, None the band where it is at most 128 wide (as engine_common.attention_spec
+    chooses).  -> the dict of launch arguments (`act_sf`: that QuantAct's scale), or None where the entry's precondition does not
+    hold: a shift mask whose scores do not all land on int_exp's clamp (prepare.ibert_window_mask_ok) -- nothing may be launched."""
+    from .quantization_utils.ibert_modules import softmax_constants
+    x0i, bi, ci, exp_sf, act_sf, ma, ea = softmax_constants(s_A, *act_range)
+    if region is not None and not ibert_window_mask_ok(s_A, x0i):
+        return None
+    bias_pad, kp = _bias_pad(bias, s_tab, s_A, N)
+    region_pad = None
+    if region is not None:
+        region_pad = np.zeros((region.shape[0], kp), np.uint8)
+        region_pad[:, :N] = region
+    tab = torch.empty(65536, dtype=torch.float32, device=device)
+    _lib.call("ivit_ibert_softmax_build_table", float(s_A), x0i, bi, ci, float(exp_sf), float(act_sf), ma, ea, _lib.ptr(tab), st)
+    band_w = 0
+    if form != "table":
+        band, bw = shiftexp_band(tab.cpu().numpy().view(np.uint32).reshape(256, 256))
+        if form == "band" and not bw:
+            raise ValueError("the exponent table has no band form at this scale")
+        if bw and (form == "band" or bw <= 128):
+            tab, band_w = upload(band.view(np.float32)), bw
+    return dict(ms=dyadic1(s_S, s_at), mb=dyadic1(s_at, s_A), mo=dyadic1(s_pv, s_a3), bias=upload(bias_pad),
+                region=None if region_pad is None else upload(region_pad), table=tab, band_w=band_w, act_sf=float(act_sf),
+                masked_exp=float(ibert_saturated_exp(x0i, bi, ci, exp_sf, act_sf, ma, ea)))
+
+
+def window_attention_ibert(a, qkv, out, ldo, nwin, nW, nH, N, H, W, win, shift, image_order, st):
+    """One window attention of a window_attention_ibert_spec `a`: operands as window_attention; win == 0: no geometry, window order"""
+    p = _lib.ptr
+    _lib.call("ivit_window_attention_i8_ibert", p(qkv), p(out), ldo, p(a["bias"]), p(a["region"]), a["masked_exp"], nwin, nW, nH, N,
+              HEAD_DIM, *a["ms"], *a["mb"], *a["mo"], p(a["table"]), a["band_w"], H, W, win, shift, int(image_order), st)
 
 
 def pool_literal_host(q: np.ndarray, s: float) -> np.ndarray:

@@ -7,6 +7,9 @@ As in vit_quant.py two execution paths give bit-identical results:
   * otherwise (calibration, debugging, module-level tests) the modules run one by one as the reference's forward
     does, with the reshapes / rolls / mask addition between them done on the float views.
 
+GELU, Softmax and LayerNorm come from the registry (gelu_type / softmax_type / layernorm_type, layer_selection.py) as in
+vit_quant.py; the fused engine implements the 'ivit' family, any 'ibert' operator runs on the integer-carrying module path.
+
 The fork's own swin_quant.py cannot be imported or run as shipped (SURVEY.md finding 6: missing aliases, a
 bias-free QuantLinear crash); this mirror implements the behaviour the file specifies, pinned by
 tests/golden/swin_tiny.npz (generated from the reference with harness-side shims only).
@@ -21,7 +24,8 @@ from torch import nn
 
 from .dispatch import EngineDispatch
 from .layers_quant import DropPath, Mlp, PatchEmbed, to_2tuple, trunc_normal_
-from .quantization_utils import IntGELU, IntLayerNorm, IntSoftmax, QuantAct, QuantLinear, QuantMatMul, lazy
+from .quantization_utils import IntGELU, IntSoftmax, QuantAct, QuantLinear, QuantMatMul, get_gelu, get_layernorm, get_softmax, lazy
+from .quantization_utils.layer_selection import _parse_layer_name
 
 __all__ = ["swin_tiny_patch4_window7_224", "swin_small_patch4_window7_224", "swin_base_patch4_window7_224",
            "SwinTransformer", "window_partition", "window_reverse"]
@@ -44,7 +48,7 @@ def window_reverse(windows, window_size: int, H: int, W: int):
 class WindowAttention(nn.Module):
     """W-MSA / SW-MSA with relative position bias (swin_quant.py:52-169)."""
 
-    def __init__(self, dim, window_size, num_heads, qkv_bias=True, attn_drop=0.0, proj_drop=0.0):
+    def __init__(self, dim, window_size, num_heads, qkv_bias=True, attn_drop=0.0, proj_drop=0.0, softmax_cls=IntSoftmax):
         super().__init__()
         self.dim, self.window_size, self.num_heads = dim, window_size, num_heads
         self.scale = (dim // num_heads) ** -0.5
@@ -59,7 +63,7 @@ class WindowAttention(nn.Module):
         self.qact_table = QuantAct()
         self.qact2 = QuantAct()
         self.attn_drop = nn.Dropout(attn_drop)
-        self.log_int_softmax = IntSoftmax()
+        self.log_int_softmax = softmax_cls(8)      # the output width: Shiftmax's default, IBERTIntSoftmax's required argument
         self.qact3 = QuantAct()
         self.qact4 = QuantAct(16)
         self.proj = QuantLinear(dim, dim)
@@ -94,7 +98,7 @@ class SwinTransformerBlock(nn.Module):
     """swin_quant.py:172-301."""
 
     def __init__(self, dim, input_resolution, num_heads, window_size=7, shift_size=0, mlp_ratio=4.0, qkv_bias=True,
-                 drop=0.0, attn_drop=0.0, drop_path=0.0, act_layer=nn.GELU, norm_layer=nn.LayerNorm):
+                 drop=0.0, attn_drop=0.0, drop_path=0.0, act_layer=nn.GELU, norm_layer=nn.LayerNorm, softmax_cls=IntSoftmax):
         super().__init__()
         self.dim, self.input_resolution, self.num_heads = dim, input_resolution, num_heads
         self.window_size, self.shift_size, self.mlp_ratio = window_size, shift_size, mlp_ratio
@@ -105,7 +109,7 @@ class SwinTransformerBlock(nn.Module):
         self.norm1 = norm_layer(dim)
         self.qact1 = QuantAct()
         self.attn = WindowAttention(dim, window_size=to_2tuple(self.window_size), num_heads=num_heads,
-                                    qkv_bias=qkv_bias, attn_drop=attn_drop, proj_drop=drop)
+                                    qkv_bias=qkv_bias, attn_drop=attn_drop, proj_drop=drop, softmax_cls=softmax_cls)
         self.drop_path = DropPath(drop_path) if drop_path > 0.0 else nn.Identity()
         self.qact2 = QuantAct(16)
         self.norm2 = norm_layer(dim)
@@ -180,7 +184,8 @@ class BasicLayer(nn.Module):
     """One stage (swin_quant.py:363-421)."""
 
     def __init__(self, dim, input_resolution, depth, num_heads, window_size, mlp_ratio=4.0, qkv_bias=True, drop=0.0,
-                 attn_drop=0.0, drop_path=0.0, norm_layer=nn.LayerNorm, downsample=None, use_checkpoint=False):
+                 attn_drop=0.0, drop_path=0.0, norm_layer=nn.LayerNorm, downsample=None, use_checkpoint=False, act_layer=IntGELU,
+                 softmax_cls=IntSoftmax):
         super().__init__()
         if use_checkpoint:
             raise NotImplementedError("activation checkpointing is a training feature; the integer path is inference")
@@ -190,7 +195,7 @@ class BasicLayer(nn.Module):
                                  window_size=window_size, shift_size=0 if i % 2 == 0 else window_size // 2,
                                  mlp_ratio=mlp_ratio, qkv_bias=qkv_bias, drop=drop, attn_drop=attn_drop,
                                  drop_path=drop_path[i] if isinstance(drop_path, list) else drop_path,
-                                 act_layer=IntGELU, norm_layer=norm_layer) for i in range(depth)])
+                                 act_layer=act_layer, norm_layer=norm_layer, softmax_cls=softmax_cls) for i in range(depth)])
         self.downsample = downsample(input_resolution, dim=dim, norm_layer=norm_layer) if downsample is not None else None
 
     def forward(self, x, act_scaling_factor):
@@ -209,9 +214,16 @@ class SwinTransformer(EngineDispatch, nn.Module):
 
     def __init__(self, img_size=224, patch_size=4, in_chans=3, num_classes=1000, embed_dim=96, depths=(2, 2, 6, 2),
                  num_heads=(3, 6, 12, 24), window_size=7, mlp_ratio=4.0, qkv_bias=True, drop_rate=0.0,
-                 attn_drop_rate=0.0, drop_path_rate=0.1, norm_layer=nn.LayerNorm, ape=False, patch_norm=True,
-                 use_checkpoint=False, **kwargs):
+                 attn_drop_rate=0.0, drop_path_rate=0.1, norm_layer=None, ape=False, patch_norm=True,
+                 use_checkpoint=False, gelu_type="ivit", softmax_type="ivit", layernorm_type="ivit", **kwargs):
         super().__init__()
+        # 'base_arg_value...' names (layer_selection.py), as VisionTransformer keeps them; an explicit norm_layer= wins over the name
+        parsed = [_parse_layer_name(str(t)) for t in (gelu_type, softmax_type, layernorm_type)]
+        self.op_types = tuple(base for base, _ in parsed)
+        self.op_params = tuple(params for _, params in parsed)
+        gelu_layer, softmax_cls = get_gelu(gelu_type), get_softmax(softmax_type)
+        if norm_layer is None:
+            norm_layer = partial(get_layernorm(layernorm_type), eps=1e-6)
         self.num_classes, self.num_layers, self.embed_dim = num_classes, len(depths), embed_dim
         self.depths, self.num_heads, self.window_size = tuple(depths), tuple(num_heads), window_size
         self.ape, self.patch_norm, self.mlp_ratio = ape, patch_norm, mlp_ratio
@@ -234,7 +246,8 @@ class SwinTransformer(EngineDispatch, nn.Module):
                        depth=depths[i], num_heads=num_heads[i], window_size=window_size, mlp_ratio=mlp_ratio,
                        qkv_bias=qkv_bias, drop=drop_rate, attn_drop=attn_drop_rate,
                        drop_path=dpr[sum(depths[:i]):sum(depths[:i + 1])], norm_layer=norm_layer,
-                       downsample=PatchMerging if i < self.num_layers - 1 else None, use_checkpoint=use_checkpoint)
+                       downsample=PatchMerging if i < self.num_layers - 1 else None, use_checkpoint=use_checkpoint,
+                       act_layer=gelu_layer, softmax_cls=softmax_cls)
             for i in range(self.num_layers)])
         self.norm = norm_layer(self.num_features)
         self.qact2 = QuantAct()
@@ -288,6 +301,8 @@ class SwinTransformer(EngineDispatch, nn.Module):
     _frozen_exempt = ("act_out",)      # constructed by the reference (swin_quant.py:518) and never called
 
     def engine_unsupported_reason(self):
+        if self.op_types != ("ivit",) * 3 or any(self.op_params):
+            return f"operator family {self.op_types} (fused engine: all three operators 'ivit', default constructor arguments)"
         if self.ape or not self.patch_norm:
             return "absolute position embedding / no patch norm"
         if self.num_classes <= 0:
@@ -332,7 +347,7 @@ def _factory(embed_dim, depths, num_heads, name):
             raise RuntimeError(f"{name}(pretrained=True) downloads weights (swin_quant.py:579-584); there is no network "
                                "here -- load a state_dict instead")
         return SwinTransformer(patch_size=4, window_size=7, embed_dim=embed_dim, depths=depths, num_heads=num_heads,
-                               norm_layer=partial(IntLayerNorm, eps=1e-6), **kwargs)
+                               **kwargs)
     make.__name__ = name
     return make
 

@@ -130,6 +130,8 @@ SWIN_CONFIGS = {
     "swin_base_patch4_window7_224": dict(embed_dim=128, depths=(2, 2, 18, 2), num_heads=(4, 8, 16, 32), window=7),
     # Swin-B widths with two blocks per stage: a test-sized stand-in that exercises C = 128 * 2^k and heads 4..32
     "swin_base_shallow": dict(embed_dim=128, depths=(2, 2, 2, 2), num_heads=(4, 8, 16, 32), window=7),
+    # two stages at 56 px: the model of tests/golden/swin_ibert_small.npz (scripts/gen_swin_ibert_golden.py)
+    "swin_ibert_small": dict(embed_dim=96, depths=(2, 2), num_heads=(3, 6), window=7),
 }
 REL_POS_STD = 0.5   # reference init is 0.02 (swin_quant.py:112); widened so the bias path is exercised
 

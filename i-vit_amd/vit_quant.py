@@ -168,6 +168,17 @@ class VisionTransformer(EngineDispatch, nn.Module):
                             "of the 'ibert' layernorm)")
         return None
 
+    def _carries_integers(self):
+        """the integer-carrying module path (lazy.scope) resolves every site by its own module, so it takes any combination of
+        'ivit' / 'ibert' operators; a name with constructor parameters other than the I-BERT LayerNorm's use_int_sqrt keeps the
+        literal path"""
+        for kind, base, params in zip(("gelu", "softmax", "layernorm"), self.op_types, self.op_params):
+            if base not in ("ivit", "ibert"):
+                return False
+            if any(not ((kind, base, k) == ("layernorm", "ibert", "use_int_sqrt") and isinstance(v, bool)) for k, v in params.items()):
+                return False
+        return True
+
     @property
     def ln_int_sqrt(self):
         """IBERTIntLayerNorm(use_int_sqrt=True): every LayerNorm of the model takes std from integer_sqrt (ibert_modules.py:143)"""
@@ -232,8 +243,8 @@ class VisionTransformer(EngineDispatch, nn.Module):
             return logits_f32.clone()
         if not self.is_frozen():
             self.invalidate_engine()     # running-stat QuantActs replace their range buffers: any snapshot is stale
-        # a frozen I-ViT model run module by module carries int8 between its modules (quantization_utils/lazy.py)
-        with lazy.scope(x.is_cuda and not self.training and self._operator_reason() is None and self.is_frozen()):
+        # a frozen model run module by module carries int8 between its modules (quantization_utils/lazy.py)
+        with lazy.scope(x.is_cuda and not self.training and self._carries_integers() and self.is_frozen()):
             x, s = self.forward_features(x)
             x, _ = self.head(x, s)
         return x.to_float(boundary=True) if isinstance(x, lazy.QT) else x

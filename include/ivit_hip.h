@@ -592,6 +592,29 @@ int ivit_window_attention_i8_long(const int8_t* qkv, int8_t* out, int64_t ldo, c
                                   int32_t e_s, uint32_t m_b, int32_t e_b, float s_attn, uint32_t m_o, int32_t e_o, const float* phi,
                                   const float* phi_masked, const uint32_t* band, int band_w, int band_rows, int H, int W, int ws,
                                   int shift, int image_order, ivit_stream_t stream);
+/* Window attention with IBERTIntSoftmax (ibert_modules.py:237-319, output_bit 8) in place of Shiftmax: Swin built with
+ * softmax_type='ibert'.  Operands and layouts of ivit_window_attention_i8_long for every window of 2..144 tokens: head-major qkv,
+ * bias_add [heads][tokens][kp] int16 and mask_region [windows_per_image][kp] uint8 (or NULL) with kp = 64 up to 64 tokens and
+ * 16 * ceil(tokens / 16) above, (m_s,e_s), (m_b,e_b), (m_o,e_o).  table: float32 on the device, 16-byte aligned -- band_w == 0 the
+ * [256][256] table of ivit_ibert_softmax_build_table for the scale of attn.qact2, band_w > 0 (a multiple of 16, at most 256) its band
+ * form table[(qmax + 128) * band_w + min(qmax - q, band_w - 1)] as ivit_attention_fused_i8_ibert takes it.  Behind the lookup the
+ * arithmetic is that entry's: the row sum in float32 in torch's CPU order (csrc/rowsum.h), factor = floor(2^32 / sum),
+ * p = floor(fl(e * factor) / 2^25) in [0, 128] -- 128 reaches P.V --, then (m_o,e_o).
+ * ws == 0: no window geometry, rows out in window order (image_order must be 0); ws != 0: H, W, ws, shift describe the windows
+ * (tokens == ws * ws, windows_per_image == (H / ws) * (W / ws), 0 <= shift < ws) and image_order = 1 writes the rows at their image
+ * positions as ivit_window_attention_i8_unwindow does.
+ * PRECONDITION the caller proves and the entry cannot check (prepare.ibert_window_mask_ok does, for all 256 x 256 pairs of a
+ * masked score q and a row maximum qm, in the reference's float32 sequence): the reference adds float -100 to q * s_attn under the
+ * shift mask, so a masked score lies off the integer grid; with mask_region != NULL every masked score must land on int_exp's clamp
+ * 30 * x0_int whatever the maximum, and none may be a row maximum (about s_attn <= 0.29).  Each masked score then contributes
+ * masked_exp, the one saturated value (c_int through the softmax's internal 16-bit QuantAct), and takes no part in the maximum.
+ * Where the proof fails the caller runs the attention core literally.
+ * Errors: IVIT_ERR_UNSUPPORTED for tokens outside 2..144, head_dim != 32, a bad band width or a window description that does not
+ * match; IVIT_ERR_INVALID ("NULL operand", alignment, multipliers, masked_exp outside [0, 32768]) otherwise. */
+int ivit_window_attention_i8_ibert(const int8_t* qkv, int8_t* out, int64_t ldo, const int16_t* bias_add, const uint8_t* mask_region,
+                                   float masked_exp, int windows, int windows_per_image, int heads, int tokens, int head_dim,
+                                   uint32_t m_s, int32_t e_s, uint32_t m_b, int32_t e_b, uint32_t m_o, int32_t e_o, const float* table,
+                                   int band_w, int H, int W, int ws, int shift, int image_order, ivit_stream_t stream);
 
 /* =================================================================================================
  * I-BERT operator family (models/quantization_utils/ibert_modules.py; registry key 'ibert', the fork's default,
