@@ -1823,6 +1823,9 @@ IVIT_EXPORT int ivit_shiftgelu_lut_i8_ex(const int8_t* x, int64_t ldx, int rows,
     const int out_blocks = layouts & 1, in_blocks = (layouts >> 1) & 1;   // bit 0: output, bit 1: input in the block layout
     IVIT_REQUIRE((layouts & ~3) == 0 && (!in_blocks || (L % 64 == 0 && ldx == L)) && (x != out || in_blocks == out_blocks),
                  "ivit_shiftgelu_lut_i8_ex: bad layouts (in place needs the same layout on both sides)");
+    // row-major in place with two strides: row r of `out` overlaps a later (or earlier) row of `x` that another wave has yet to read
+    IVIT_REQUIRE(x != out || in_blocks || ldx == ldo, "ivit_shiftgelu_lut_i8_ex: in place (out == x) needs ldx == ldo, got %lld and %lld",
+                 (long long)ldx, (long long)ldo);
     IVIT_REQUIRE(out_blocks == 0 || (out_blocks == 1 && L % 64 == 0 && ldo == L && ((uintptr_t)out % 16 == 0) &&
                                      ((int64_t)rows + 15) * L < 2147483648ll),
                  "ivit_shiftgelu_lut_i8_ex: block-layout output needs L %% 64 == 0, ldo == L and a buffer below 2 GiB");

@@ -361,7 +361,8 @@ int ivit_shiftgelu_build_lut_ex(float s, uint32_t m, int32_t e, const int8_t* re
 int ivit_shiftgelu_lut_i8(const int8_t* x, int64_t ldx, int rows, int L, const int8_t* lut, int8_t* out,
                           int64_t ldo, ivit_stream_t stream);
 /* layouts bit 0: `out` is written in IVIT_LAYOUT_BLOCKS (L % 64 == 0, ldo == L, rows padded to 16); bit 1: `x` is read in
- * it (ldx == L).  In place (out == x) is allowed when both sides use the same layout. */
+ * it (ldx == L).  In place (out == x) is allowed when both sides use the same layout and, row-major, the same stride (ldx == ldo):
+ * with two strides the rows of `out` overlap other rows of `x`, IVIT_ERR_INVALID. */
 int ivit_shiftgelu_lut_i8_ex(const int8_t* x, int64_t ldx, int rows, int L, const int8_t* lut, int8_t* out,
                              int64_t ldo, int layouts, ivit_stream_t stream);
 
