@@ -32,6 +32,8 @@ static inline int grid_for_rows(int64_t rows)
     return (int)(blocks < 4096 ? blocks : 4096);
 }
 
+#include "win_map.h"     // WinMap, win_row: the 16-bit LayerNorm stores its rows in Swin's window order
+
 // ------------------------------------------------------------------------------------------------ GELU
 // ibert_modules.py:203-235 with x_int = k (integer activations):
 //   sign * ((min(|x|, -b) + b)^2 + c) -> floor(. / 2^6) = sigmoid_int;  out = x * (sigmoid_int + shift_int)
@@ -271,11 +273,12 @@ struct IbLnI8Args {
     int8_t* out;
     int64_t ldo;
     int out_blocks;
+    WinMap map;             // int16 rows only: row r is stored as row win_row(map, r) of `out` (ws == 0: in order)
 };
 
-// one row, literally (whole wave)
+// one row, literally (whole wave); orow: the row of `out` it is stored to (row-major output)
 template <typename TX = int8_t, bool ISQ = false>
-IVIT_DEV void ib_ln_row_literal(const IbLnI8Args& a, int row, int lane)
+IVIT_DEV void ib_ln_row_literal(const IbLnI8Args& a, int row, int lane, int64_t orow)
 {
     const int C = a.C;
     {
@@ -301,7 +304,7 @@ IVIT_DEV void ib_ln_row_literal(const IbLnI8Args& a, int row, int lane)
             r = fmin(fmax(r, -128.0), 127.0);
             const int8_t o = (int8_t)(int)r;
             if (a.out_blocks) a.out[block_off(brow, block_col(c))] = o;
-            else a.out[(int64_t)row * a.ldo + c] = o;
+            else a.out[orow * a.ldo + c] = o;
         }
     }
 }
@@ -310,7 +313,8 @@ template <typename TX, bool ISQ>
 __global__ __launch_bounds__(NT) void ibert_layernorm_i8_kernel(IbLnI8Args a)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int row = blockIdx.x * WPB + wave; row < a.rows; row += gridDim.x * WPB) ib_ln_row_literal<TX, ISQ>(a, row, lane);
+    for (int row = blockIdx.x * WPB + wave; row < a.rows; row += gridDim.x * WPB)
+        ib_ln_row_literal<TX, ISQ>(a, row, lane, sizeof(TX) == 2 ? win_row(a.map, row) : (int64_t)row);
 }
 
 // The same result without evaluating the two float32 row sums term by term.  Both sums only feed a rounding:
@@ -378,7 +382,7 @@ __global__ __launch_bounds__(NT, 4) void ibert_layernorm_i8_fast_kernel(IbLnI8Ar
         const float m0 = (float)sq / (float)C;
         const float fr = m0 - floorf(m0);
         if (fabsf(fr - 0.5f) < 2.2e-3f) {                 // wave-uniform
-            ib_ln_row_literal<int8_t, ISQ>(a, row, lane);
+            ib_ln_row_literal<int8_t, ISQ>(a, row, lane, row);
             continue;
         }
         const float mean_int = rintf(m0);
@@ -411,7 +415,7 @@ __global__ __launch_bounds__(NT, 4) void ibert_layernorm_i8_fast_kernel(IbLnI8Ar
             }
         }
         if (!ok) {
-            ib_ln_row_literal<int8_t, ISQ>(a, row, lane);
+            ib_ln_row_literal<int8_t, ISQ>(a, row, lane, row);
             continue;
         }
         const float std_int = ib_std_int<ISQ>((float)V, a.shift_pow2);            // :142-145
@@ -437,7 +441,7 @@ __global__ __launch_bounds__(NT, 4) void ibert_layernorm_i8_fast_kernel(IbLnI8Ar
                 else *reinterpret_cast<int*>(a.out + (int64_t)row * a.ldo + 4 * d) = pw;
             }
         }
-        if (__builtin_amdgcn_ballot_w64(unc != 0) != 0) ib_ln_row_literal<int8_t, ISQ>(a, row, lane);   // wave-uniform, rare
+        if (__builtin_amdgcn_ballot_w64(unc != 0) != 0) ib_ln_row_literal<int8_t, ISQ>(a, row, lane, row);   // wave-uniform, rare
     }
 }
 
@@ -515,6 +519,7 @@ __global__ __launch_bounds__(NT) void ibert_layernorm_i16_fast_kernel(IbLnI8Args
     const float inv_shift = 1.0f / a.shift_pow2;      // a power of two: y / 2^shift == y * 2^-shift exactly
     for (int row = blockIdx.x * WPB + wave; row < a.rows; row += gridDim.x * WPB) {
         const int16_t* xr = reinterpret_cast<const int16_t*>(a.x) + (int64_t)row * a.ldx;
+        const int64_t orow_i = win_row(a.map, row);        // wave-uniform: the window partition + cyclic shift on the store address
         int xq[NK];
 #pragma unroll
         for (int k = 0; k < NK; ++k) xq[k] = xr[lane + 64 * k];
@@ -541,12 +546,12 @@ __global__ __launch_bounds__(NT) void ibert_layernorm_i16_fast_kernel(IbLnI8Args
         const float var_int = torch_rowsum_regs<NK>(sq, lane);                                // :131
         const float std_int = ib_std_int<ISQ>(var_int, a.shift_pow2);                           // :142-145
         if (!(std_int > 0.0f)) {                           // wave-uniform
-            ib_ln_row_literal<int16_t, ISQ>(a, row, lane);
+            ib_ln_row_literal<int16_t, ISQ>(a, row, lane, orow_i);
             continue;
         }
         const float factor = floorf(2147483648.0f / std_int);                                 // :143
         unsigned unc = 0;
-        int8_t* orow = a.out + (int64_t)row * a.ldo;
+        int8_t* orow = a.out + orow_i * a.ldo;
 #pragma unroll
         for (int k = 0; k < NK; ++k) {
             float v = floorf((ph[k] * factor) / 2.0f);                                         // :144
@@ -556,7 +561,7 @@ __global__ __launch_bounds__(NT) void ibert_layernorm_i16_fast_kernel(IbLnI8Args
             unc |= (tl != th) ? 1u : 0u;                                                     // uncertified: the row is redone literally
             orow[lane + 64 * k] = (int8_t)clamp_i32(tl, 0x4B400000 - 128, 0x4B400000 + 127);
         }
-        if (__builtin_amdgcn_ballot_w64(unc != 0) != 0) ib_ln_row_literal<int16_t, ISQ>(a, row, lane);   // wave-uniform, rare
+        if (__builtin_amdgcn_ballot_w64(unc != 0) != 0) ib_ln_row_literal<int16_t, ISQ>(a, row, lane, orow_i);   // wave-uniform, rare
     }
 }
 
@@ -768,16 +773,15 @@ IVIT_EXPORT int ivit_ibert_layernorm_i16_i8(const int16_t* x, int64_t ldx, int r
     return ivit_ibert_layernorm_i16_i8_ex(x, ldx, rows, C, s_in, bias_int, s_out, shift_pow2, m, e, out, ldo, 0, stream);
 }
 
-IVIT_EXPORT int ivit_ibert_layernorm_i16_i8_ex(const int16_t* x, int64_t ldx, int rows, int C, float s_in, const float* bias_int,
-                                               const float* s_out, float shift_pow2, const uint32_t* m, const int32_t* e, int8_t* out,
-                                               int64_t ldo, int fast_division, ivit_stream_t stream)
+// the three int16 entries: `who` names the caller in messages, map the window order of the stored rows (ws == 0: in order)
+static int ibert_ln16_launch(const char* who, const int16_t* x, int64_t ldx, int rows, int C, float s_in, const float* bias_int,
+                             const float* s_out, float shift_pow2, const uint32_t* m, const int32_t* e, int8_t* out, int64_t ldo,
+                             bool fast_division, bool isq, WinMap map, ivit_stream_t stream)
 {
-    const bool isq = (fast_division & IVIT_IBERT_LN_INT_SQRT) != 0;  // the one flag above the division choice
-    fast_division &= ~IVIT_IBERT_LN_INT_SQRT;
     IVIT_REQUIRE(x && out && bias_int && s_out && m && e && rows > 0 && C > 0 && ldx >= C && ldo >= C && s_in > 0.0f,
-                 "ivit_ibert_layernorm_i16_i8: bad operand");
-    IVIT_REQUIRE(shift_pow2 >= 1.0f, "ivit_ibert_layernorm_i16_i8: shift_pow2 = 2^shift must be >= 1");
-    IbLnI8Args a{reinterpret_cast<const int8_t*>(x), ldx, rows, C, s_in, bias_int, s_out, shift_pow2, m, e, out, ldo, 0};
+                 "%s: bad operand", who);
+    IVIT_REQUIRE(shift_pow2 >= 1.0f, "%s: shift_pow2 = 2^shift must be >= 1", who);
+    IbLnI8Args a{reinterpret_cast<const int8_t*>(x), ldx, rows, C, s_in, bias_int, s_out, shift_pow2, m, e, out, ldo, 0, map};
     const dim3 grid(grid_for_rows(rows)), blk(NT);
     hipStream_t st = ivit_stream(stream);
     const float r_in = 1.0f / s_in;
@@ -795,7 +799,33 @@ IVIT_EXPORT int ivit_ibert_layernorm_i16_i8_ex(const int16_t* x, int64_t ldx, in
     else if (isq) hipLaunchKernelGGL((ibert_layernorm_i8_kernel<int16_t, true>), grid, blk, 0, st, a);
     else hipLaunchKernelGGL((ibert_layernorm_i8_kernel<int16_t, false>), grid, blk, 0, st, a);
 #undef IB_LN16
-    IVIT_CHECK_LAUNCH("ivit_ibert_layernorm_i16_i8");
+    IVIT_CHECK_LAUNCH(who);
+}
+
+IVIT_EXPORT int ivit_ibert_layernorm_i16_i8_ex(const int16_t* x, int64_t ldx, int rows, int C, float s_in, const float* bias_int,
+                                               const float* s_out, float shift_pow2, const uint32_t* m, const int32_t* e, int8_t* out,
+                                               int64_t ldo, int fast_division, ivit_stream_t stream)
+{
+    const bool isq = (fast_division & IVIT_IBERT_LN_INT_SQRT) != 0;  // the one flag above the division choice
+    fast_division &= ~IVIT_IBERT_LN_INT_SQRT;
+    return ibert_ln16_launch("ivit_ibert_layernorm_i16_i8", x, ldx, rows, C, s_in, bias_int, s_out, shift_pow2, m, e, out, ldo,
+                             fast_division != 0, isq, WinMap{0, 0, 0, 0}, stream);
+}
+
+IVIT_EXPORT int ivit_ibert_layernorm_i16_i8_win(const int16_t* x, int64_t ldx, int rows, int C, float s_in, const float* bias_int,
+                                                const float* s_out, float shift_pow2, const uint32_t* m, const int32_t* e, int8_t* out,
+                                                int64_t ldo, int fast_division, int H, int W, int ws, int shift, ivit_stream_t stream)
+{
+    IVIT_REQUIRE((fast_division & ~(1 | IVIT_IBERT_LN_INT_SQRT)) == 0,
+                 "ivit_ibert_layernorm_i16_i8_win: fast_division is 0 or 1, optionally | IVIT_IBERT_LN_INT_SQRT");
+    if (!win_map_ok(rows, H, W, ws, shift)) {
+        ivit_set_error("ivit_ibert_layernorm_i16_i8_win: unsupported geometry (window map H=%d W=%d ws=%d shift=%d rows=%d)", H, W, ws,
+                       shift, rows);
+        return IVIT_ERR_UNSUPPORTED;
+    }
+    return ibert_ln16_launch("ivit_ibert_layernorm_i16_i8_win", x, ldx, rows, C, s_in, bias_int, s_out, shift_pow2, m, e, out, ldo,
+                             (fast_division & 1) != 0, (fast_division & IVIT_IBERT_LN_INT_SQRT) != 0,
+                             ws ? WinMap{H, W, ws, shift} : WinMap{0, 0, 0, 0}, stream);
 }
 
 #if IVIT_LAB

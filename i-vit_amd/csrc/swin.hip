@@ -42,45 +42,7 @@ IVIT_DEV int pack4(int a, int b, int c, int d)
 #include "ln_chain.h"
 #include "attn_parts.h"
 
-// ------------------------------------------------------------------------------------------------
-// Row maps: the window partition / cyclic shift of SwinTransformerBlock.forward (swin_quant.py:258-271, 278-289) are
-// pure row permutations of a [B, H*W, C] tensor.  win_row(r) = index, in window-major order
-// (image, window row, window col, row in window, col in window), of token r = (b, y, x) after rolling by -shift.
-// ------------------------------------------------------------------------------------------------
-struct WinMap {
-    int H, W, ws, shift;  // ws == 0: identity
-};
-
-IVIT_DEV int64_t win_row(const WinMap& m, int64_t r)
-{
-    if (m.ws == 0) return r;
-    const int L = m.H * m.W;
-    const int b = (int)(r / L);
-    const int t = (int)(r - (int64_t)b * L);
-    int y = t / m.W, x = t - y * m.W;
-    // shifted_x[y'] = x[(y' + shift) mod H]  =>  token (y, x) lands at y' = (y - shift) mod H
-    y = y - m.shift; if (y < 0) y += m.H;
-    x = x - m.shift; if (x < 0) x += m.W;
-    const int wy = y / m.ws, iy = y - wy * m.ws, wx = x / m.ws, ix = x - wx * m.ws;
-    const int nwx = m.W / m.ws;
-    return ((int64_t)b * (m.H / m.ws) * nwx + (int64_t)wy * nwx + wx) * (m.ws * m.ws) + iy * m.ws + ix;
-}
-
-// the inverse: row R of the window-ordered tensor (window index, position in the window) -> row of the image-ordered one
-// (window_reverse + the roll back, swin_quant.py:278-287)
-IVIT_DEV int64_t win_row_inv(const WinMap& m, int64_t R)
-{
-    if (m.ws == 0) return R;
-    const int T = m.ws * m.ws, nwx = m.W / m.ws, nwy = m.H / m.ws;
-    const int64_t widx = R / T;
-    const int pos = (int)(R - widx * T);
-    const int iy = pos / m.ws, ix = pos - iy * m.ws;
-    const int b = (int)(widx / (nwy * nwx)), wrem = (int)(widx - (int64_t)b * (nwy * nwx));
-    const int wy = wrem / nwx, wx = wrem - wy * nwx;
-    int y = wy * m.ws + iy + m.shift; if (y >= m.H) y -= m.H;
-    int x = wx * m.ws + ix + m.shift; if (x >= m.W) x -= m.W;
-    return (int64_t)b * m.H * m.W + (int64_t)y * m.W + x;
-}
+#include "win_map.h"     // WinMap, win_row, win_row_inv: the window partition / cyclic shift as row maps
 
 // ------------------------------------------------------------------------------------------------
 // 8 -> 16 bit QuantAct (SwinTransformer.qact1, swin_quant.py:546; also used as an exact int8 -> int16 widening)
@@ -1111,9 +1073,7 @@ IVIT_EXPORT int ivit_requant_i8_i16(const int8_t* x, uint32_t m, int32_t e, int1
 
 static int check_map(const char* who, int64_t rows, int H, int W, int ws, int shift)
 {
-    if (ws == 0) return IVIT_OK;
-    IVIT_REQUIRE(H > 0 && W > 0 && ws > 0 && H % ws == 0 && W % ws == 0 && shift >= 0 && shift < ws && rows % ((int64_t)H * W) == 0,
-                 "%s: bad window map H=%d W=%d ws=%d shift=%d rows=%lld", who, H, W, ws, shift, (long long)rows);
+    IVIT_REQUIRE(win_map_ok(rows, H, W, ws, shift), "%s: bad window map H=%d W=%d ws=%d shift=%d rows=%lld", who, H, W, ws, shift, (long long)rows);
     return IVIT_OK;
 }
 

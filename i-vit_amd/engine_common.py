@@ -81,7 +81,7 @@ def ln_spec(lp, upload, s_in, bits: int, ibert_shift=None, int_sqrt: bool = Fals
 def layernorm(ln, x, ldx, rows, C, out, ldo, st, blocks=None, H=0, W=0, ws=0, shift=0, outer=0):
     """LayerNorm + requantisation of `rows` rows of x to int8, for every kind of ln_spec.
     blocks: the int8-input kinds write `out` in the block layout (None: the "i8" kind goes through the entry point without a
-    layout argument).  H, W, ws, shift: the Swin window map of the 16-bit kinds (0: rows in order).  outer:
+    layout argument).  H, W, ws, shift: the Swin window map of the 16-bit kinds, "ibert_i16" included (0: rows in order).  outer:
     IVIT_LN_OUTER_MEAN(outer) of the compat kinds -- the float32 mean in torch's outer-reduction order."""
     kind, p = ln["kind"], _lib.ptr
     bias, s, m, e = p(ln["bias"]), p(ln["s"]), p(ln["m"]), p(ln["e"])
@@ -95,6 +95,9 @@ def layernorm(ln, x, ldx, rows, C, out, ldo, st, blocks=None, H=0, W=0, ws=0, sh
     elif kind == "ibert_i8":
         _lib.call("ivit_ibert_layernorm_i8", p(x), ldx, rows, C, ln["s_in"], bias, s, ln["shift_pow2"], m, e, p(out), ldo,
                   int(blocks or 0) | ln["flags"], st)
+    elif kind == "ibert_i16" and ws:
+        _lib.call("ivit_ibert_layernorm_i16_i8_win", p(x), ldx, rows, C, ln["s_in"], bias, s, ln["shift_pow2"], m, e, p(out), ldo,
+                  ln["fast_div"] | ln["flags"], H, W, ws, shift, st)
     elif kind == "ibert_i16":
         _lib.call("ivit_ibert_layernorm_i16_i8_ex", p(x), ldx, rows, C, ln["s_in"], bias, s, ln["shift_pow2"], m, e, p(out), ldo,
                   ln["fast_div"] | ln["flags"], st)

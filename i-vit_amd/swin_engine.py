@@ -13,6 +13,12 @@ Dataflow = the reference's frozen-model forward (/root/reference/models/swin_qua
   per stage end { 2x2 patch-merge gather int16 -> LN16->8 -> GEMM reduction (+requant) -> widen to int16 }
   LN16->8 -> token average pool + requant -> GEMM head -> INT32 logits -> scale + argmax
 
+family="ibert" (gelu_type = softmax_type = layernorm_type = 'ibert', the reference fork's default) keeps this dataflow and replaces
+the three operators: every LayerNorm is IBERTIntLayerNorm with its overflow shift (ivit_ibert_layernorm_i8 for the patch norm,
+ivit_ibert_layernorm_i16_i8_ex on the stream, norm1 through ivit_ibert_layernorm_i16_i8_win, which stores in window order), the window
+attention is ivit_window_attention_i8_ibert (IBERTIntSoftmax(8)), and IBERTIntGELU + mlp.qact1 is a 256-entry map applied in the fc1
+epilogue (ivit_gemm_i8_requant_lut_ex) where fc1 takes the fragment weight copy, by ivit_shiftgelu_lut_i8 elsewhere.
+
 There is no fallback path: a missing libivit_hip.so or a kernel error raises.
 """
 from __future__ import annotations
@@ -245,8 +251,17 @@ def pool_literal_host(q: np.ndarray, s: float) -> np.ndarray:
 
 class IntSwinEngine(EngineBase):
     def __init__(self, float_state, ranges, embed_dim=96, depths=(2, 2, 6, 2), num_heads=(3, 6, 12, 24), window=7,
-                 device="cuda:0", max_batch: int = 64, img_size: int = 224):
+                 device="cuda:0", max_batch: int = 64, img_size: int = 224, family: str = "ivit", int_sqrt: bool = False):
+        """float_state: name -> float32 array (the model's state_dict); ranges: QuantAct name -> (x_min, x_max) of the frozen model.
+        family: the operator family of LayerNorm / Softmax / GELU, "ivit" or "ibert" (all three); int_sqrt: IBERTIntLayerNorm's
+        use_int_sqrt (layernorm_type 'ibert_use-int-sqrt_true')."""
         self.C0, self.depths, self.heads, self.window = embed_dim, tuple(depths), tuple(num_heads), window
+        if family not in ("ivit", "ibert"):
+            raise ValueError(f"operator family {family!r}: the fused engine implements 'ivit' and 'ibert'")
+        if int_sqrt and family != "ibert":
+            raise ValueError("int_sqrt (use_int_sqrt) is a parameter of the 'ibert' LayerNorm")
+        self.family, self.int_sqrt = family, bool(int_sqrt)
+        ibert = family == "ibert"
         why = unsupported_geometry(img_size, PATCH, window, len(self.depths))
         if why is not None:
             raise ValueError(why)
@@ -290,8 +305,13 @@ class IntSwinEngine(EngineBase):
         def ln_dev(prefix, s_out, s_in, bits_in=16):
             """s_in: scale of the LayerNorm's input.  If fl(fl(q*s_in)/s_in) != q for some q of that width, the reference's
             LayerNorm sees those neighbouring floats (ivit_modules.py:36-38): 16-bit inputs take the literal kernel, the 8-bit
-            patch norm the table form of the DeiT engine."""
-            return self._ln_spec(LayerNormParams(P[prefix + ".weight"], P[prefix + ".bias"], s_out), s_in, bits_in)
+            patch norm the table form of the DeiT engine.  family "ibert": IBERTIntLayerNorm works on fl(q * s_in) at any scale; its
+            overflow shift is the module's frozen buffer (ibert_modules.py:134-140; absent from the state: 0)."""
+            lp = LayerNormParams(P[prefix + ".weight"], P[prefix + ".bias"], s_out)
+            if not ibert:
+                return self._ln_spec(lp, s_in, bits_in)
+            shift = float(P[prefix + ".shift"].reshape(-1)[0]) if prefix + ".shift" in P else 0.0
+            return self._ln_spec(lp, s_in, bits_in, ibert_shift=shift, int_sqrt=self.int_sqrt)
 
         # ---- stem (layers_quant.py:191-203 with norm_layer; swin_quant.py:541-546)
         s0 = s("qact_input")
@@ -333,7 +353,18 @@ class IntSwinEngine(EngineBase):
                 region = shift_mask_regions(H, W, win, shift) if shift else None
                 s_pv = f32(f32(1.0 / 128.0) * s_a1)
                 s_a3 = s(p + "attn.qact3")
-                blk["attn"], form = window_attention_spec(dev, bias, s_tab, s_S, s_at, s_A, s_pv, s_a3, region, N)
+                if ibert:
+                    act = p + "attn.log_int_softmax.act"        # the softmax's internal 16-bit QuantAct (ibert_modules.py:260)
+                    if act not in R:
+                        raise KeyError(f"the 'ibert' engine needs the range of {act} (the softmax's internal 16-bit QuantAct)")
+                    blk["attn"], form = window_attention_ibert_spec(dev, self.dev, self._stream(), bias, s_tab, s_S, s_at, s_A, s_pv,
+                                                                    s_a3, region, N, (float(R[act][0]), float(R[act][1]))), None
+                    if blk["attn"] is None:
+                        # no literal attention core in the engine: such a model runs module by module
+                        raise ValueError(f"{p[:-1]}: the shift mask at s_attn = {float(s_A):.6g} is outside what "
+                                         "ivit_window_attention_i8_ibert takes (prepare.ibert_window_mask_ok, about s_attn <= 0.29)")
+                else:
+                    blk["attn"], form = window_attention_spec(dev, bias, s_tab, s_S, s_at, s_A, s_pv, s_a3, region, N)
                 blk["attn"]["nW"] = (H // win) * (W // win)
                 if form is not None:
                     self.natural_sites += 1
@@ -350,7 +381,7 @@ class IntSwinEngine(EngineBase):
                 s_g = s(p + "mlp.qact_gelu")
                 blk["fc1"] = lin_dev(p + "mlp.fc1", s_b3, s_g)
                 s_m1 = s(p + "mlp.qact1")
-                blk["gelu_lut"] = self._gelu_lut("ivit", s_g, s_m1)
+                blk["gelu_lut"] = self._gelu_lut(family, s_g, s_m1)
                 s_m2 = s(p + "mlp.qact2")
                 blk["fc2"] = lin_dev(p + "mlp.fc2", s_m1, s_m2)
                 s_b4 = s(p + "qact4", 16)
@@ -516,7 +547,10 @@ class IntSwinEngine(EngineBase):
                     taps[p + "attn.qact1"] = hm.permute(1, 3, 0, 2, 4).reshape(nwin, N, 3 * C).clone()
                 a = blk["attn"]
                 fuse_proj = self.proj_fused and taps is None
-                window_attention(a, ws["qkv"], ws["ao"], ld, nwin, a["nW"], nH, N, H, W, win, shift, fuse_proj, st)
+                if self.family == "ibert":
+                    window_attention_ibert(a, ws["qkv"], ws["ao"], ld, nwin, a["nW"], nH, N, H, W, win, shift, fuse_proj, st)
+                else:
+                    window_attention(a, ws["qkv"], ws["ao"], ld, nwin, a["nW"], nH, N, H, W, win, shift, fuse_proj, st)
                 tap(p + "attn.qact3", ws["ao"], M, C, ld)
                 pj = blk["proj"]
                 r = blk["res1"]
@@ -540,10 +574,18 @@ class IntSwinEngine(EngineBase):
                 tap(p + "qact2", x2, M, C)
                 layernorm(blk["ln2"], x2, C, M, C, ws["h"], ld, st, outer=outer)
                 tap(p + "qact3", ws["h"], M, C, ld)
-                self._gemm(ws["h"], ld, blk["fc1"], ws["f1"], 4 * C, M, st)
-                tap(p + "mlp.qact_gelu", ws["f1"], M, 4 * C)
-                _lib.call("ivit_shiftgelu_lut_i8", _lib.ptr(ws["f1"]), 4 * C, M, 4 * C, _lib.ptr(blk["gelu_lut"]),
-                          _lib.ptr(ws["g"]), 4 * C, st)
+                f1 = blk["fc1"]
+                if self.family == "ibert" and taps is None and f1.get("Wf") is not None and M >= 2048:
+                    # I-BERT GELU + mlp.qact1 is a map of the requantised byte alone (no row maximum): applied in the fc1 epilogue
+                    # of the weights-in-registers GEMM, the GELU kernel and its pass over the 4C-wide intermediate disappear
+                    _lib.call("ivit_gemm_i8_requant_lut_ex", _lib.ptr(ws["h"]), ld, _lib.ptr(f1["Wf"]), f1["K"], _lib.ptr(f1["b"]),
+                              _lib.ptr(f1["m"]), _lib.ptr(f1["e"]), _lib.ptr(blk["gelu_lut"]), _lib.ptr(ws["g"]), 4 * C, M, f1["N"],
+                              f1["K"], f1["Wf_bit"], st)
+                else:
+                    self._gemm(ws["h"], ld, f1, ws["f1"], 4 * C, M, st)
+                    tap(p + "mlp.qact_gelu", ws["f1"], M, 4 * C)
+                    _lib.call("ivit_shiftgelu_lut_i8", _lib.ptr(ws["f1"]), 4 * C, M, 4 * C, _lib.ptr(blk["gelu_lut"]),
+                              _lib.ptr(ws["g"]), 4 * C, st)
                 tap(p + "mlp.qact1", ws["g"], M, 4 * C)
                 r = blk["res2"]
                 f2 = blk["fc2"]
@@ -583,3 +625,37 @@ class IntSwinEngine(EngineBase):
         return self._classify(B, st, topk)
 
     __call__ = forward
+
+
+def operator_family(model):
+    """("ivit" | "ibert", int_sqrt) of a SwinTransformer whose three operators IntSwinEngine implements together; raises ValueError
+    with the reason for a mixture of families and for a constructor parameter in an operator name other than the I-BERT LayerNorm's
+    use_int_sqrt"""
+    if len(set(model.op_types)) != 1 or model.op_types[0] not in ("ivit", "ibert"):
+        raise ValueError(f"operator family {model.op_types} (fused engine: all three operators 'ivit', or all three 'ibert')")
+    for kind, base, params in zip(("gelu", "softmax", "layernorm"), model.op_types, model.op_params):
+        for k, v in params.items():
+            if not ((kind, base, k) == ("layernorm", "ibert", "use_int_sqrt") and isinstance(v, bool)):
+                raise ValueError(f"{kind} parameter {k}={v!r} of '{base}' (fused engine: default constructor arguments, or use_int_sqrt "
+                                 "of the 'ibert' layernorm)")
+    return model.op_types[0], bool(getattr(model.norm, "use_int_sqrt", False))
+
+
+def engine_from_model(model, device=None, max_batch: int = 64):
+    """IntSwinEngine for a frozen SwinTransformer of either operator family (all three operators 'ivit', or all three 'ibert' with
+    or without the LayerNorm's use_int_sqrt): a snapshot of its parameters, ranges and LayerNorm shifts.  model(x) itself dispatches
+    the I-ViT family only; this is how the I-BERT family reaches the engine.  Raises ValueError with the reason for a model the engine
+    does not implement (operator mixture, another operator parameter, edited QuantAct widths, ape, no patch norm, geometry) and for
+    a shift mask outside ivit_window_attention_i8_ibert's precondition (the block is named)."""
+    family, int_sqrt = operator_family(model)
+    why = model.engine_structure_reason()
+    if why is not None:
+        raise ValueError(why)
+    if not model.is_frozen():
+        raise ValueError("the model is not frozen (freeze_model): its QuantAct ranges are still running statistics")
+    if device is None:
+        device = next(model.parameters()).device
+    # a plain I-ViT model's engine is built with the arguments SwinTransformer._build_engine passes
+    ops = dict(family=family, int_sqrt=int_sqrt) if family == "ibert" else {}
+    return IntSwinEngine(dict(model.state_dict()), model.ranges(), model.embed_dim, model.depths, model.num_heads, model.window_size,
+                         device=device, max_batch=max_batch, img_size=model.patch_embed.img_size[0], **ops)

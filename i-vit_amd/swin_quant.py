@@ -301,8 +301,14 @@ class SwinTransformer(EngineDispatch, nn.Module):
     _frozen_exempt = ("act_out",)      # constructed by the reference (swin_quant.py:518) and never called
 
     def engine_unsupported_reason(self):
+        """what model(x) dispatches on: the engine it builds is the I-ViT one (swin_engine.engine_from_model also takes the I-BERT
+        family, by construction)"""
         if self.op_types != ("ivit",) * 3 or any(self.op_params):
             return f"operator family {self.op_types} (fused engine: all three operators 'ivit', default constructor arguments)"
+        return self.engine_structure_reason()
+
+    def engine_structure_reason(self):
+        """None when IntSwinEngine implements this model apart from its operator family: stem, head, widths, geometry"""
         if self.ape or not self.patch_norm:
             return "absolute position embedding / no patch norm"
         if self.num_classes <= 0:

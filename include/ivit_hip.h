@@ -733,6 +733,17 @@ int ivit_ibert_layernorm_i16_i8(const int16_t* x, int64_t ldx, int rows, int C, 
 int ivit_ibert_layernorm_i16_i8_ex(const int16_t* x, int64_t ldx, int rows, int C, float s_in, const float* bias_int,
                                    const float* s_out, float shift_pow2, const uint32_t* m, const int32_t* e, int8_t* out, int64_t ldo,
                                    int fast_division, ivit_stream_t stream);
+/* ivit_ibert_layernorm_i16_i8_ex with the rows of `out` in Swin's window order, as ivit_layernorm_i16_i8 stores them: row r = (b, y, x)
+ * of x [rows = batch * H * W, C] is written to row win_row(r) of out -- the cyclic shift by -shift and the partition into ws x ws windows
+ * of SwinTransformerBlock.forward (swin_quant.py:258-271) applied to the store address, so that norm1 of a block needs no gather behind
+ * it.  ws == 0: rows in order, identical to the _ex entry (H, W, shift are not read).  The arithmetic, the kernels and the meaning of
+ * every other argument are the _ex entry's; ldo may exceed C (the pad columns are not written).
+ * Errors, nothing launched: a bit of fast_division other than 1 and IVIT_IBERT_LN_INT_SQRT is IVIT_ERR_INVALID; with ws != 0 a window
+ * description other than H, W > 0, H % ws == 0, W % ws == 0, 0 <= shift < ws, rows % (H * W) == 0 is IVIT_ERR_UNSUPPORTED ("unsupported
+ * geometry"); then as the _ex entry: IVIT_ERR_INVALID ("bad operand") for a NULL operand, ldx < C, ldo < C, s_in <= 0. */
+int ivit_ibert_layernorm_i16_i8_win(const int16_t* x, int64_t ldx, int rows, int C, float s_in, const float* bias_int,
+                                    const float* s_out, float shift_pow2, const uint32_t* m, const int32_t* e, int8_t* out, int64_t ldo,
+                                    int fast_division, int H, int W, int ws, int shift, ivit_stream_t stream);
 
 /* ---- evaluation transform (the reference's data pipeline in front of the model) ----------------------------------------
  * torchvision Resize([resize_short], BICUBIC) on a PIL image, then CenterCrop(crop) (scripts/inference.py:63-66,
