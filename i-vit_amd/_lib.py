@@ -41,6 +41,8 @@ SIGNATURES = {
     "ivit_untile_operand_i8": [vp, i64, ci, vp, i64, vp],
     "ivit_gemm_i8_requant_ex": [vp, i64, vp, i64, vp, vp, vp, vp, i64, ci, ci, ci, ci, vp],
     "ivit_gemm_i8_requant_residual_ex": [vp, i64, vp, i64, vp, vp, vp, vp, i64, u32, i32, u32, i32, vp, i64, ci, ci, ci, ci, vp],
+    "ivit_gemm_i8_requant_bits_ex": [vp, i64, vp, i64, vp, vp, vp, vp, i64, ci, ci, ci, ci, ci, vp],
+    "ivit_gemm_i8_requant_residual_bits_ex": [vp, i64, vp, i64, vp, vp, vp, vp, i64, u32, i32, u32, i32, vp, i64, ci, ci, ci, ci, ci, ci, vp],
     "ivit_gemm_i8_requant_qkv_ex": [vp, i64, vp, i64, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp],
     "ivit_gemm_i8_requant_qkv_planes_ex": [vp, i64, vp, i64, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp],
     "ivit_gemm_i8_requant_residual_i16": [vp, i64, vp, i64, vp, vp, vp, vp, i64, u32, i32, u32, i32, vp, i64, ci, ci, ci, vp],
@@ -67,7 +69,9 @@ SIGNATURES = {
     "ivit_shiftmax_i8": [vp, i64, ci, ci, f32, vp, i64, vp],
     "ivit_requant_i32": [vp, i64, ci, vp, vp, ci, vp, vp, vp, ci, ci, vp, vp],
     "ivit_residual_requant_i8": [vp, u32, i32, vp, u32, i32, vp, i64, vp],
+    "ivit_residual_requant_i8_bits": [vp, u32, i32, vp, u32, i32, vp, i64, ci, vp],
     "ivit_embed_assemble_i8": [vp, vp, vp, u32, i32, vp, ci, ci, ci, vp],
+    "ivit_embed_assemble_i8_bits": [vp, vp, vp, u32, i32, vp, ci, ci, ci, ci, vp],
     "ivit_embed_assemble_i16": [vp, vp, vp, u32, i32, vp, ci, ci, ci, vp],
     "ivit_head_argmax": [vp, vp, ci, ci, vp, vp, vp],
     "ivit_head_topk": [vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp],

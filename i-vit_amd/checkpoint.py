@@ -28,7 +28,10 @@ TAGS = {"deit_tiny": "deit_tiny_patch16_224", "deit_small": "deit_small_patch16_
         "swin_small": "swin_small_patch4_window7_224", "swin_small_natural": "swin_small_patch4_window7_224",
         # I-BERT operators with layernorm_type 'ibert_use-int-sqrt_true' (scripts/make_ibert_intsqrt_golden.py)
         "deit_tiny_ibert_isqrt": "deit_tiny_patch16_224", "deit_tiny_ibert_isqrt_natural": "deit_tiny_patch16_224",
-        "deit_tiny_ibert_isqrt_w16all": "deit_tiny_patch16_224"}
+        "deit_tiny_ibert_isqrt_w16all": "deit_tiny_patch16_224",
+        # every width knob at 4 (scripts/gen_w4_golden.py)
+        "deit_tiny_w4": "deit_tiny_patch16_224", "deit_tiny_w4_natural": "deit_tiny_patch16_224",
+        "deit_tiny_ibert_w4": "deit_tiny_patch16_224", "deit_tiny_ibert_w4_natural": "deit_tiny_patch16_224"}
 
 
 def load_fixture(tag: str):
@@ -36,6 +39,23 @@ def load_fixture(tag: str):
     meta = json.loads(str(z["meta"]))
     ranges = {str(n): (np.float32(lo), np.float32(hi)) for n, lo, hi in zip(z["range_names"], z["x_min"], z["x_max"])}
     return z, meta, ranges
+
+
+def sharpen_float_state(fs, meta):
+    """The 4-bit fixtures' weights: synth.make_float_state's with the q and k rows of every attn.qkv scaled by meta["qk_gain"] and
+    the class token by meta["cls_gain"] (absent: 1).  At 4 bits a softmax row of 197 keys whose largest probability is below 1/8 is
+    all zeros, and a class token far below the activation step is a zero row: the plain synthetic weights give both."""
+    qk, cg = float(meta.get("qk_gain", 1.0)), float(meta.get("cls_gain", 1.0))
+    if qk == 1.0 and cg == 1.0:
+        return fs
+    fs = dict(fs)
+    for k in list(fs):
+        if k.endswith("attn.qkv.weight") or k.endswith("attn.qkv.bias"):
+            v = np.array(fs[k], np.float32)
+            v[:2 * v.shape[0] // 3] *= np.float32(qk)
+            fs[k] = v
+    fs["cls_token"] = (np.asarray(fs["cls_token"], np.float32) * np.float32(cg)).astype(np.float32)
+    return fs
 
 
 def load_synthetic_model(tag: str):
@@ -46,5 +66,5 @@ def load_synthetic_model(tag: str):
         fs = synth.make_swin_float_state(meta["factory"], meta["weight_seed"])
     else:
         cfg = synth.MODEL_CONFIGS[meta["factory"]]
-        fs = synth.make_float_state(meta["factory"], meta["weight_seed"])
+        fs = sharpen_float_state(synth.make_float_state(meta["factory"], meta["weight_seed"]), meta)
     return fs, ranges, cfg, meta, z

@@ -80,7 +80,8 @@ IVIT_DEV int kswz(int r, int c) { return r * HD + (((c + 2 * ((r >> 2) & 1)) & 3
 // 3 / 4: the I-BERT softmax (ibert_modules.py:237-319) from its (row max, q) table (3: gathered from global memory, 4: band rows
 // staged in LDS like mode 1), row sum in torch's float32 reduction order
 // PB: width of the softmax output (softmax_bw, vit_quant.py:184): 8, or 16 -- probabilities up to 2^15 as three 7-bit planes
-// (p = c + 128 b + 16384 a), one P.V MFMA set per plane (the a plane only when a wave has such a score)
+// (p = c + 128 b + 16384 a), one P.V MFMA set per plane (the a plane only when a wave has such a score) -- or 4: the code path of
+// 8 with the factor scaled by 2^-4, probabilities below 8 (Shiftmax) or up to 8 inclusive (I-BERT) in the one byte plane
 // GENT ("general T", Shiftmax modes only): any token count up to 207 -- every key tile takes the masked path of the last one
 // (keys >= T carry the sentinel), all 13 key tiles are still walked: for geometries other than 14 x 14 patches, not tuned.
 // RQ32 (MODE 0, PB 8): the requantisation of the scores in float32 -- one v_cvt_f32_i32 + one v_fma_f32 against the magic constant
@@ -93,7 +94,8 @@ constexpr int RQ_OFF = 0x4B400000;
 template <int MODE, int PB = 8, int OCC = (PB == 8 ? 4 : 3), bool GENT = false, bool RQ32 = false>
 __global__ __launch_bounds__(NT, OCC) void attention_kernel(AttnArgs a)
 {
-    static_assert(!RQ32 || (MODE == 0 && PB == 8), "RQ32: Shiftmax with a power-of-two input scale, 8-bit probabilities");
+    static_assert(PB == 4 || PB == 8 || PB == 16, "softmax output width");
+    static_assert(!RQ32 || (MODE == 0 && PB <= 8), "RQ32: Shiftmax with a power-of-two input scale, one plane of probabilities");
     constexpr int SOFF = RQ32 ? RQ_OFF : 0;       // offset the (negated) scores are carried with
     constexpr int PADK = SOFF + 1000;             // sentinel of the padding keys
     __shared__ __attribute__((aligned(16))) char smem[SMEM_BYTES];
@@ -356,21 +358,27 @@ __global__ __launch_bounds__(NT, OCC) void attention_kernel(AttnArgs a)
         } else {
             factor = shiftmax_factor(rows_allsum_u32(esum));
         }
+        if constexpr (PB == 4) factor *= 0.0625f;      // the last shift is 2^(31 - 4 + 1) (:175; I-BERT :313-314): see below
 
         // packed probabilities: dword t of key step ks = bytes r = 0..3 of key tile 4ks + t
         v4i pk[NKS];
         v4i pkb[PB == 16 ? NKS : 1];       // 16-bit probabilities: the second 7-bit plane
-        v4i pkh[(MODE >= 3 || PB == 16) ? NKS : 1];      // I-BERT: probabilities reach 128 (a one-hot row): 128 = 127 + 1, the 1 in a second operand
+        // I-BERT at 4 bits: p = floor(fl32(e * factor) / 2^29) in [0, 8]; the 8 of a one-hot row is an ordinary int8 value and needs no
+        // second operand
+        constexpr bool HI_PLANE = (MODE >= 3 && PB == 8) || PB == 16;
+        v4i pkh[HI_PLANE ? NKS : 1];      // I-BERT: probabilities reach 128 (a one-hot row): 128 = 127 + 1, the 1 in a second operand
         // I-BERT: p = floor(fl32(e * factor) / 2^25) in [0, 128] (ibert_modules.py:314, output_bit = 8).  factor / 2 is an exact
         // scaling, so u = trunc(e * (factor / 2)) has p in its top byte like the Shiftmax product below -- except p = 128, which
         // shows as the sign bit of u: the OR of all u of the tile is tested once and the tile repacked in that rare case.
         const float factor_h = factor * 0.5f;
         unsigned any_u = 0;
-        constexpr bool SDWA_PACK = MODE < 3 && PB == 8;
+        constexpr bool SDWA_PACK = MODE < 3 && PB <= 8;
         if constexpr (SDWA_PACK) {
             // p = floor(fl32(e * factor) / 2^24) (:175) = trunc(fl32(e * (factor * 2^-24))): the scaling by a power of two commutes
             // with the float32 rounding of the product (no operand or result is subnormal: factor >= 1, e >= 1 or e == 0), and
-            // p < 128.  v_cvt_u32_f32 with SDWA destination select writes the truncated value straight into byte r of the packed
+            // p < 128.  For a width PB <= 8 in general the shift is 2^(32 - PB): the scaling by 2^-(32 - PB) is as exact (at PB = 4
+            // the smallest non-zero product, 2^-28, is far from subnormal) and p < 2^(PB - 1) (8 at PB = 4); `factor` already
+            // carries the 2^-(8 - PB).  v_cvt_u32_f32 with SDWA destination select writes the truncated value straight into byte r of the packed
             // dword (UNUSED_PRESERVE keeps the other bytes; semantics checked by scripts/probes/cvt_pack_probe.hip): one
             // instruction per score instead of a conversion plus 3/4 of a byte permute / OR.  The four dwords of a key step are
             // written round-robin, so that no instruction reads the register the previous one wrote with a destination select
@@ -427,7 +435,7 @@ __global__ __launch_bounds__(NT, OCC) void attention_kernel(AttnArgs a)
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
                 unsigned w = 0;
-                if constexpr (MODE >= 3 || PB == 16) pkh[ks][t] = 0;
+                if constexpr (HI_PLANE) pkh[ks][t] = 0;
                 if constexpr (PB == 16) pkb[ks][t] = 0;
                 if (4 * ks + t < NKT) {
                     unsigned p[4];
@@ -458,7 +466,7 @@ __global__ __launch_bounds__(NT, OCC) void attention_kernel(AttnArgs a)
                 }
                 pk[ks][t] = (int)w;
             }
-        const bool any_hi = (MODE >= 3 || PB == 16) &&
+        const bool any_hi = HI_PLANE &&
                             __builtin_amdgcn_ballot_w64((any_u >> (PB == 16 ? 30 : 31)) != 0) != 0;   // wave-uniform, almost never
         if constexpr (PB == 16) {
             if (any_hi) {      // plane a (bits 30, 31 of u: p16 >= 16384) from the products again
@@ -478,7 +486,7 @@ __global__ __launch_bounds__(NT, OCC) void attention_kernel(AttnArgs a)
                         pkh[ks][t] = (int)w;
                     }
             }
-        } else if constexpr (MODE >= 3) {
+        } else if constexpr (MODE >= 3 && PB == 8) {
             if (any_hi) {      // p = 128 = 127 in pk + 1 in pkh (split_p128)
 #pragma unroll
                 for (int ks = 0; ks < NKS; ++ks)
@@ -515,7 +523,7 @@ __global__ __launch_bounds__(NT, OCC) void attention_kernel(AttnArgs a)
                 if constexpr (PB == 16) {
                     accb = __builtin_amdgcn_mfma_i32_16x16x64_i8(vf, pkb[ks], accb, 0, 0, 0);
                     if (hi_pass) acca = __builtin_amdgcn_mfma_i32_16x16x64_i8(vf, pkh[ks], acca, 0, 0, 0);
-                } else if constexpr (MODE >= 3) {
+                } else if constexpr (MODE >= 3 && PB == 8) {
                     if (hi_pass) acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(vf, pkh[ks], acc, 0, 0, 0);
                 }
             }
@@ -600,7 +608,7 @@ template <int MODE, bool RQ32, int NKT, int NTH, int PB = 8>
 __global__ __launch_bounds__(NTH, 1) void attention_long_kernel(LongArgs a)
 {
     static_assert(!RQ32 || MODE != 1, "RQ32: a power-of-two score multiplier (Shiftmax: power-of-two input scale)");
-    static_assert(PB == 8 || (PB == 16 && MODE != 2), "16-bit probabilities: Shiftmax only");
+    static_assert(PB == 8 || ((PB == 16 || PB == 4) && MODE != 2), "4- and 16-bit probabilities: Shiftmax only");
     constexpr int NKS = NKT / 4 + 1;          // key steps of 64: NKT full key tiles and the partial one
     constexpr int KOFF = RQ32 ? RQ_OFF : 0;    // RQ32: scores carry the magic constant's exponent bits (low byte = k + 128)
     extern __shared__ __attribute__((aligned(16))) char lsm[];
@@ -839,6 +847,7 @@ __global__ __launch_bounds__(NTH, 1) void attention_long_kernel(LongArgs a)
                 for (int r = 0; r < 4; ++r) sum16 += r < vr ? expo((dk >> (8 * r)) & 255u) : 0u;
             }
             factor = shiftmax_factor(rows_allsum_u64(esum + sum16));
+            if constexpr (PB == 4) factor *= 0.0625f;    // p = floor(fl32(e * factor) / 2^28) < 8: an exact scaling, as in attention_kernel
         }
 
         // ---- pass 3: p = floor(fl32(e * factor) / 2^24) (:175) as bytes, P . V per key step of 64
@@ -1155,7 +1164,7 @@ int attention_check(AttnDesc& d)
     const char* fn = d.name;
     const bool ibert = d.family == IBERT_SHORT || d.family == IBERT_LONG, cls = d.family == SHIFTMAX_CLS;
     const bool lng = d.family == SHIFTMAX_LONG || d.family == IBERT_LONG;
-    IVIT_REQUIRE(d.softmax_bits == 8 || d.softmax_bits == 16, "%s: softmax_bits must be 8 or 16", fn);
+    IVIT_REQUIRE(d.softmax_bits == 4 || d.softmax_bits == 8 || d.softmax_bits == 16, "%s: softmax_bits must be 4, 8 or 16", fn);
     const bool operands = d.qkv && d.out && (!ibert || d.table) && (!cls || (d.v && d.q));
     if (d.family == IBERT_SHORT) {
         IVIT_REQUIRE(operands && d.batch > 0 && d.heads > 0, "%s: bad operand", fn);
@@ -1203,18 +1212,22 @@ int attention_check(AttnDesc& d)
 typedef void (*ShortKernel)(AttnArgs);
 typedef void (*LongKernel)(LongArgs);
 typedef void (*ClsKernel)(ClsArgs);
-// [GENT: tokens <= 192][PB 16][MODE 0, MODE 1 (band), MODE 2 (exp2d), MODE 0 with RQ32]
-const ShortKernel SHIFTMAX_SHORT_KERNELS[2][2][4] = {
+// The width index PBI: 0 = 8-bit probabilities, 1 = 16, 2 = 4 (instantiations of their own: the 8- and 16-bit ones keep their code)
+// [GENT: tokens <= 192][PBI][MODE 0, MODE 1 (band), MODE 2 (exp2d), MODE 0 with RQ32]
+const ShortKernel SHIFTMAX_SHORT_KERNELS[2][3][4] = {
     {{attention_kernel<0>, attention_kernel<1>, attention_kernel<2>, attention_kernel<0, 8, 4, false, true>},
-     {attention_kernel<0, 16>, attention_kernel<1, 16>, attention_kernel<2, 16>, nullptr}},
+     {attention_kernel<0, 16>, attention_kernel<1, 16>, attention_kernel<2, 16>, nullptr},
+     {attention_kernel<0, 4, 4>, attention_kernel<1, 4, 4>, attention_kernel<2, 4, 4>, attention_kernel<0, 4, 4, false, true>}},
     {{attention_kernel<0, 8, 4, true>, attention_kernel<1, 8, 4, true>, attention_kernel<2, 8, 4, true>, attention_kernel<0, 8, 4, true, true>},
-     {attention_kernel<0, 16, 3, true>, attention_kernel<1, 16, 3, true>, attention_kernel<2, 16, 3, true>, nullptr}}};
-// [PB 16][MODE 3 (table), MODE 4 (band)]
-const ShortKernel IBERT_SHORT_KERNELS[2][2] = {{attention_kernel<3>, attention_kernel<4>}, {attention_kernel<3, 16>, attention_kernel<4, 16>}};
-// [PB 16][(tokens >> 4) > 40][MODE 0, MODE 0 with RQ32, MODE 1 (natural), MODE 2 (I-BERT), MODE 2 with RQ32]; the threads per
+     {attention_kernel<0, 16, 3, true>, attention_kernel<1, 16, 3, true>, attention_kernel<2, 16, 3, true>, nullptr},
+     {attention_kernel<0, 4, 4, true>, attention_kernel<1, 4, 4, true>, attention_kernel<2, 4, 4, true>, attention_kernel<0, 4, 4, true, true>}}};
+// [PBI][MODE 3 (table), MODE 4 (band)]
+const ShortKernel IBERT_SHORT_KERNELS[3][2] = {{attention_kernel<3>, attention_kernel<4>}, {attention_kernel<3, 16>, attention_kernel<4, 16>},
+                                               {attention_kernel<3, 4, 4>, attention_kernel<4, 4, 4>}};
+// [PBI][(tokens >> 4) > 40][MODE 0, MODE 0 with RQ32, MODE 1 (natural), MODE 2 (I-BERT), MODE 2 with RQ32]; the threads per
 // workgroup alongside: 16-bit probabilities are two more accumulator sets, so each token range takes the next smaller workgroup
-const int LONG_THREADS[2][2] = {{1024, 768}, {768, 512}};
-const LongKernel LONG_KERNELS[2][2][5] = {
+const int LONG_THREADS[3][2] = {{1024, 768}, {768, 512}, {1024, 768}};
+const LongKernel LONG_KERNELS[3][2][5] = {
     {{attention_long_kernel<0, false, 40, 1024>, attention_long_kernel<0, true, 40, 1024>, attention_long_kernel<1, false, 40, 1024>,
       attention_long_kernel<2, false, 40, 1024>, attention_long_kernel<2, true, 40, 1024>},
      {attention_long_kernel<0, false, 64, 768>, attention_long_kernel<0, true, 64, 768>, attention_long_kernel<1, false, 64, 768>,
@@ -1222,6 +1235,10 @@ const LongKernel LONG_KERNELS[2][2][5] = {
     {{attention_long_kernel<0, false, 40, 768, 16>, attention_long_kernel<0, true, 40, 768, 16>, attention_long_kernel<1, false, 40, 768, 16>,
       nullptr, nullptr},
      {attention_long_kernel<0, false, 64, 512, 16>, attention_long_kernel<0, true, 64, 512, 16>, attention_long_kernel<1, false, 64, 512, 16>,
+      nullptr, nullptr}},
+    {{attention_long_kernel<0, false, 40, 1024, 4>, attention_long_kernel<0, true, 40, 1024, 4>, attention_long_kernel<1, false, 40, 1024, 4>,
+      nullptr, nullptr},
+     {attention_long_kernel<0, false, 64, 768, 4>, attention_long_kernel<0, true, 64, 768, 4>, attention_long_kernel<1, false, 64, 768, 4>,
       nullptr, nullptr}}};
 const ClsKernel CLS_KERNELS[3] = {attention_cls_kernel<0>, attention_cls_kernel<1>, attention_cls_kernel<2>};   // [MODE]
 
@@ -1229,7 +1246,7 @@ int attention_launch(AttnDesc d)
 {
     if (const int rc = attention_check(d)) return rc;
     const bool ibert = d.family == IBERT_SHORT || d.family == IBERT_LONG;
-    const int pairs = d.batch * d.heads, pb16 = d.softmax_bits == 16;
+    const int pairs = d.batch * d.heads, pb16 = d.softmax_bits == 16, pbi = pb16 ? 1 : d.softmax_bits == 4 ? 2 : 0;
     // a power-of-two score multiplier (m = 2^k): the float32 requantisation of the RQ32 kernels is exact
     const bool ms_pow2 = d.m_s != 0 && (d.m_s & (d.m_s - 1)) == 0 && d.Ms >= 1e-30;
     hipStream_t st = ivit_stream(d.stream);
@@ -1252,10 +1269,10 @@ int attention_launch(AttnDesc d)
         a.band_w = d.band_w;
         a.vt_row = ((((nqt + 3) >> 2) + 3) >> 2) * 256;
         const size_t lds = (size_t)LONG_LUT_BYTES + (size_t)nqt * 16 * HD + (size_t)HD * a.vt_row;    // <= 150528 bytes at 1025 tokens
-        const int wide = (d.tokens >> 4) > 40, nth = LONG_THREADS[pb16][wide];
+        const int wide = (d.tokens >> 4) > 40, nth = LONG_THREADS[pbi][wide];
         a.parts = attention_parts(pairs, nqt, nth / 64, 256);
         const int sel = ibert ? (ms_pow2 ? 4 : 3) : (d.band_w || d.table) ? 2 : ms_pow2 ? 1 : 0;
-        hipLaunchKernelGGL(LONG_KERNELS[pb16][wide][sel], dim3(pairs * a.parts), dim3(nth), lds, st, a);
+        hipLaunchKernelGGL(LONG_KERNELS[pbi][wide][sel], dim3(pairs * a.parts), dim3(nth), lds, st, a);
         IVIT_CHECK_LAUNCH(d.name);
     }
     AttnArgs a{};
@@ -1275,7 +1292,7 @@ int attention_launch(AttnDesc d)
     ShortKernel kernel;
     if (ibert) {
         a.ib_table = static_cast<const float*>(d.table);
-        kernel = IBERT_SHORT_KERNELS[pb16][d.band_w ? 1 : 0];
+        kernel = IBERT_SHORT_KERNELS[pbi][d.band_w ? 1 : 0];
     } else {
         a.abl = g_attn_debug & 31;
         a.exp2d = static_cast<const unsigned*>(d.table);
@@ -1288,7 +1305,7 @@ int attention_launch(AttnDesc d)
             if (x <= 15 * a.x0) { a.ksat = i; break; }
         }
         const bool rq32 = ms_pow2 && !pb16 && !(IVIT_LAB && (g_attn_debug & (1 << 5)));     // lab bit 5: off, A/B
-        kernel = SHIFTMAX_SHORT_KERNELS[d.tokens <= 16 * (NKT - 1)][pb16][d.band_w ? 1 : d.table ? 2 : rq32 ? 3 : 0];
+        kernel = SHIFTMAX_SHORT_KERNELS[d.tokens <= 16 * (NKT - 1)][pbi][d.band_w ? 1 : d.table ? 2 : rq32 ? 3 : 0];
     }
     hipLaunchKernelGGL(kernel, dim3(pairs * a.parts), dim3(NT), band_lds_bytes, st, a);
     IVIT_CHECK_LAUNCH(d.name);

@@ -100,7 +100,7 @@ IVIT_DEV void gather4(float x, float (&out)[4])
 }
 
 // ---- output tail: O^T = Vt . P^T requantised (attn.qact2) to int8, one accumulator element.
-//   PB 8:  |O| <= 1025 * 127 * 128 < 2^24: the float64 product is exact, one fma against the magic constant (requant_exact).
+//   PB 4, 8 (one byte plane of probabilities):  |O| <= 1025 * 127 * 128 < 2^24: the float64 product is exact, one fma against the magic constant (requant_exact).
 //   PB 16: O = o + (o_b << 7) + (o_a << 14) = sum p16 * v over the three planes, below 2^30 (bounds: attention_long_kernel); the
 //          reference's float64 product rounds at 53 bits first (quant_utils.py:229-230), so product and rounding are two steps.
 template <int PB>

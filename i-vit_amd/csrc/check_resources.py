@@ -39,6 +39,39 @@ def parse(text):
     return kernels
 
 
+def twin_of(name):
+    """the 8-bit instantiation a 4-bit one was made from, by its mangled name, or None: the width flags 0x100 / 0x200 on the first
+    template argument of the GEMM kernels (gemm_common.h EPI_NARROW_*), PB = 4 of attention_kernel<MODE, PB, ..> and
+    attention_long_kernel<.., PB>"""
+    m = re.search(r"(gemm_i8_\w*kernelILi)(\d+)E", name)
+    if m and int(m.group(2)) >= 256:
+        return name.replace(m.group(0), m.group(1) + str(int(m.group(2)) & 255) + "E")
+    m = re.search(r"(?:embed|residual_requant)_kernelI(Lin8ELi7E)", name)      # rowops.hip: <LO, HI> = <-8, 7> against <-128, 127>
+    if m:
+        return name[:m.start(1)] + "Lin128ELi127E" + name[m.end(1):]
+    m = re.search(r"attention_kernelILi\d+E(Li4E)", name)
+    if m:
+        return name[:m.start(1)] + "Li8E" + name[m.end(1):]
+    m = re.search(r"attention_long_kernelILi\d+ELb[01]ELi\d+ELi\d+E(Li4E)", name)
+    if m:
+        return name[:m.start(1)] + "Li8E" + name[m.end(1):]
+    return None
+
+
+def narrow_rule(kernels, name):
+    """a narrow form differs from its twin in constants only: it may not need more registers or any more scratch.  -> error text or None"""
+    twin = twin_of(name)
+    if twin is None:
+        return None
+    if twin not in kernels:
+        return f"no 8-bit twin {twin}"
+    r, t = kernels[name], kernels[twin]
+    regs, tregs = r.get("VGPRs", 0) + r.get("AGPRs", 0), t.get("VGPRs", 0) + t.get("AGPRs", 0)
+    if regs > tregs or r.get("Scratch", 0) > t.get("Scratch", 0):
+        return f"VGPR+AGPR {regs}, scratch {r.get('Scratch')} against {tregs}, {t.get('Scratch')} of its 8-bit twin"
+    return None
+
+
 def occupancy_rules(path, what):
     """attention.hip / rowops.hip: kernels whose launchers size their grids for a number of resident workgroups.  The number is a
     template argument (the OCC of attention_kernel<MODE, PB, OCC, ...>, the last argument of layernorm_i8_stream_kernel<LPR, NC, NG,
@@ -51,7 +84,7 @@ def occupancy_rules(path, what):
             # attention_long_kernel<MODE, RQ32, NKT, NTH, PB>: one workgroup of NTH threads per CU (the launcher's 256 slots), i.e.
             # NTH / 256 waves per SIMD; the packed score rows must stay in registers: no scratch.  PB = 16 (the three probability
             # planes): 768 threads up to 40 key tiles, 512 above
-            m = re.search(r"attention_long_kernelILi(\d+)ELb([01])ELi(\d+)ELi(\d+)ELi(8|16)E", name)
+            m = re.search(r"attention_long_kernelILi(\d+)ELb([01])ELi(\d+)ELi(\d+)ELi(4|8|16)E", name)
             occ, need_no_scratch = int(m.group(4)) // 256, True
         elif what == "attention" and "attention_cls_kernel" in name:
             # attention_cls_kernel<MODE>: CLS_OCC = 3 workgroups of four waves per CU (its __launch_bounds__; DeiT-B at batch 256
@@ -77,6 +110,9 @@ def occupancy_rules(path, what):
                 if not m:
                     continue
                 occ, need_no_scratch = (3 if m.group(1) and int(m.group(3)) >= 2 else 4), True      # = their __launch_bounds__
+        elif re.search(r"(embed|residual_requant)_kernelILin", name):
+            # the two elementwise kernels with a clamp as template arguments (8-bit and 4-bit forms): one row each, no scratch
+            occ, need_no_scratch = 1, True
         elif "head_topk_kernel" in name:
             # the per-lane top-k lists live in registers (constant indices only): no scratch, full occupancy for any k <= 8
             occ, need_no_scratch = 8, True
@@ -105,8 +141,10 @@ def occupancy_rules(path, what):
             need_no_scratch = m.group(4) == "0" or int(m.group(2)) == 3
         seen += 1
         ok = r.get("Occupancy", 0) >= occ and (r.get("Scratch") == 0 and r.get("VGPRSpill", 0) == 0 or not need_no_scratch)
+        narrow = narrow_rule(kernels, name)
+        ok = ok and narrow is None
         print(("ok   " if ok else "FAIL ") + f"{name}: VGPR {r.get('VGPRs')}, scratch {r.get('Scratch')}, occupancy {r.get('Occupancy')} (launcher assumes {occ}"
-              f"{', no scratch' if need_no_scratch else ''})")
+              f"{', no scratch' if need_no_scratch else ''})" + (f" -- {narrow}" if narrow else ""))
         if not ok:
             bad.append(name)
     if seen == 0:
@@ -123,6 +161,12 @@ def main(path):
     bad, seen = [], 0
     for name, r in sorted(kernels.items()):
         if not any(g in name for g in GUARDED):
+            narrow = narrow_rule(kernels, name)      # the small-tile and skinny-K kernels: no budget of their own, but a narrow form
+            if twin_of(name):                        # still may not need more than its 8-bit twin
+                print(("ok   " if narrow is None else "FAIL ") + f"{name}: VGPR+AGPR {r.get('VGPRs', 0) + r.get('AGPRs', 0)}, scratch "
+                      f"{r.get('Scratch')}" + (f" -- {narrow}" if narrow else ""))
+                if narrow:
+                    bad.append(name)
             continue
         seen += 1
         regs = r.get("VGPRs", 0) + r.get("AGPRs", 0)
@@ -130,7 +174,9 @@ def main(path):
                 f"SGPR spill {r.get('SGPRSpill')}, occupancy {r.get('Occupancy')}, LDS {r.get('LDS')}")
         ok = (r.get("Scratch") == 0 and r.get("VGPRSpill") == 0 and regs <= 256 and r.get("Occupancy", 0) >= 2
               and r.get("LDS", 0) <= 81920)
-        print(("ok   " if ok else "FAIL ") + line)
+        narrow = narrow_rule(kernels, name)
+        ok = ok and narrow is None
+        print(("ok   " if ok else "FAIL ") + line + (f" -- {narrow}" if narrow else ""))
         if not ok:
             bad.append(name)
     if seen == 0:

@@ -25,9 +25,11 @@
 
 namespace {
 
-template <int EPI>
+// EPIW (every kernel of this file): the epilogue kind, for the 4-bit forms with the width flags of gemm_common.h (EPI_NARROW_*)
+template <int EPIW>
 __global__ __launch_bounds__(NT) void gemm_i8_kernel(GemmArgs g)
 {
+    constexpr int EPI = epi_kind(EPIW);
     __shared__ __attribute__((aligned(16))) char smem[SMEM_BYTES + BN * 8];
 
     // ---- XCD-aware block -> tile map (bijective for any block count)
@@ -174,7 +176,7 @@ __global__ __launch_bounds__(NT) void gemm_i8_kernel(GemmArgs g)
             }
         return;
     } else {
-        epilogue_i8<EPI, 2, 2, BM, NT>(acc, g, smem, smem + SMEM_BYTES, m0, n0, 64 * wn, 64 * wm, tid, h, l31);
+        epilogue_i8<EPIW, 2, 2, BM, NT>(acc, g, smem, smem + SMEM_BYTES, m0, n0, 64 * wn, 64 * wm, tid, h, l31);
     }
 }
 
@@ -215,9 +217,10 @@ IVIT_DEV PersWork pers_work(const GemmArgs& g, int i, int b, int G)
     return PersWork{-1, 0, 0};
 }
 
-template <int EPI>
+template <int EPIW>
 __global__ __launch_bounds__(BIG_NT, 2) void gemm_i8_pers_kernel(GemmArgs g)
 {
+    constexpr int EPI = epi_kind(EPIW);
     __shared__ __attribute__((aligned(16))) char smem[PERS_SMEM];
     const int tid = threadIdx.x;
 #if IVIT_LAB
@@ -436,7 +439,7 @@ __global__ __launch_bounds__(BIG_NT, 2) void gemm_i8_pers_kernel(GemmArgs g)
         Hook hook{g, nxt.n0, tid, tab_next, more, PersTableLoad{0u, 0, 0, false}};
         int tid_o = tid;   // opaque: the epilogue's per-thread addresses are computed here, not carried through the main loop
         asm volatile("" : "+v"(tid_o));
-        epilogue_i8<EPI, 2, TJ, (HALF ? 128 : BTOK), BIG_NT, BCH, Hook>(acc, g, smem + BIG_STAGE, tab, cur.m0, cur.n0,
+        epilogue_i8<EPIW, 2, TJ, (HALF ? 128 : BTOK), BIG_NT, BCH, Hook>(acc, g, smem + BIG_STAGE, tab, cur.m0, cur.n0,
                                                                      64 * wc, WTOK * wt, tid_o, (tid_o >> 5) & 1, tid_o & 31, hook);
         __syncthreads();   // staging reads done before the next item's stage 1 DMA overwrites buffer 1
     };
@@ -535,9 +538,10 @@ IVIT_DEV WrWork wr_work(const GemmArgs& g, int i, int b, int G)
 // l = 16 c + r holding chunk c of row r, i.e. simply 1 KB in lane order: the LDS-DMA lays a token piece into its stage in
 // exactly that order (per-lane source addresses pick chunk (r, c) out of the row-major or block-layout operand), so the
 // fragment read is ds_read_b128 at lane * 16 -- conflict-free by construction, no swizzle on either side.
-template <int EPI, int ABL = 0, bool S16 = false>
+template <int EPIW, int ABL = 0, bool S16 = false>
 __global__ __launch_bounds__(BIG_NT, 2) void gemm_i8_wreg_kernel(GemmArgs g)
 {
+    constexpr int EPI = epi_kind(EPIW);
     __shared__ __attribute__((aligned(16))) char smem[WR_SMEM];
     char* const cs = smem + WR_RING;
     const int tid = threadIdx.x;
@@ -895,18 +899,18 @@ __global__ __launch_bounds__(BIG_NT, 2) void gemm_i8_wreg_kernel(GemmArgs g)
             if constexpr (S16) asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");     // MFMA results -> VALU reads: see mfma16 (c)
             if constexpr (S16 && (EPI == EPI_RQ || EPI == EPI_RESID || EPI == EPI_QKV)) {
                 // straight from the registers (lane transpose, no LDS staging)
-                epilogue_direct_16<EPI, 2 * TJ, (ABL & (2048 | 4096)), Hook>(acc16, g, tab, cur.m0 + wtok, cur.n0, wch, (tid_o >> 4) & 3, tid_o & 15, hook,
+                epilogue_direct_16<EPIW, 2 * TJ, (ABL & (2048 | 4096)), Hook>(acc16, g, tab, cur.m0 + wtok, cur.n0, wch, (tid_o >> 4) & 3, tid_o & 15, hook,
                                                                                g.lut ? reinterpret_cast<const unsigned char*>(smem + WR_LUT) : nullptr,
                                                                                (ABL & 2048) ? tv : nullptr);
             } else if constexpr (S16) {      // EPI_RESID16: staged through LDS
                 static_assert(!S16 || EPI != EPI_RQ16_RES16, "the 16-bit epilogue exists for the 32x32 form only");
-                epilogue_i8_16<EPI, 2 * TJ, BIG_NT, WR_CH, Hook>(acc16, g, cs, tab, cur.m0, cur.n0, 64 * wave, tid_o, (tid_o >> 4) & 3,
+                epilogue_i8_16<EPIW, 2 * TJ, BIG_NT, WR_CH, Hook>(acc16, g, cs, tab, cur.m0, cur.n0, 64 * wave, tid_o, (tid_o >> 4) & 3,
                                                                           tid_o & 15, hook,
                                                                           g.lut ? reinterpret_cast<const unsigned char*>(smem + WR_LUT) : nullptr);
             } else if constexpr (EPI == EPI_RQ16_RES16)
                 epilogue_rq16_res16<TJ, BIG_NT, Hook>(acc, g, cs, cur.m0, cur.n0, 64 * wave, tid_o, (tid_o >> 5) & 1, tid_o & 31, hook);
             else
-            epilogue_i8<EPI, 2, TJ, 32 * TJ, BIG_NT, WR_CH, Hook>(acc, g, cs, tab, cur.m0, cur.n0, 64 * wave, 0, tid_o, (tid_o >> 5) & 1,
+            epilogue_i8<EPIW, 2, TJ, 32 * TJ, BIG_NT, WR_CH, Hook>(acc, g, cs, tab, cur.m0, cur.n0, 64 * wave, 0, tid_o, (tid_o >> 5) & 1,
                                                                       tid_o & 31, hook,
                                                                       g.lut ? reinterpret_cast<const unsigned char*>(smem + WR_LUT) : nullptr);
         }
@@ -976,9 +980,11 @@ constexpr int SK_SMEM = SK_MAXN * SK_MAXK + SK_MAXN * 12 + (SK_MAXN / 4) * 4;   
 // NKS = K / 32 at compile time (2: patch embedding, 4: stage-0 qkv; 0: any K, run time).  With a run-time K the `ks < nks` test around
 // every MFMA became a scalar branch and each weight fragment a ds_read_b64 / s_waitcnt lgkmcnt(0) / v_mfma triple: 16 exposed LDS
 // latencies per batch of four channel sub-tiles.  Straight-line, a batch's fragment reads are issued together (late round 4).
-template <int EPI, int NKS = 0>
+template <int EPIW, int NKS = 0>
 __global__ __launch_bounds__(SK_NT, 2) void gemm_i8_skinny_kernel(GemmArgs g)
 {
+    constexpr int EPI = epi_kind(EPIW);
+    constexpr int QLO = epi_lo(EPIW, EPI_NARROW_MID), QHI = epi_hi(EPIW, EPI_NARROW_MID);   // -128, 127 unless the 4-bit form
     static_assert(EPI == EPI_RQ || EPI == EPI_QKV, "skinny-K form: int8 outputs");
     __shared__ __attribute__((aligned(16))) char smem[SK_SMEM];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1063,7 +1069,7 @@ __global__ __launch_bounds__(SK_NT, 2) void gemm_i8_skinny_kernel(GemmArgs g)
                     const int tl = __float_as_int(__builtin_fmaf(a, lh.x, 12582912.0f));
                     const int th = __float_as_int(__builtin_fmaf(a, lh.y, 12582912.0f));
                     asm("v_sad_u32 %0, %1, %2, %3" : "=v"(unc) : "v"(tl), "v"(th), "v"(unc));
-                    b[ii][r] = clamp_i32(tl, 0x4B400000 - 128, 0x4B400000 + 127);       // low byte = int8 result
+                    b[ii][r] = clamp_i32(tl, 0x4B400000 + QLO, 0x4B400000 + QHI);       // low byte = int8 result
                 }
             }
             if (__builtin_amdgcn_ballot_w64(unc != 0) != 0) {      // rare: exact float64 evaluation of the batch (quant_utils.py:229-230)
@@ -1073,7 +1079,7 @@ __global__ __launch_bounds__(SK_NT, 2) void gemm_i8_skinny_kernel(GemmArgs g)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const double tq = (double)acc[ii][r] * dyadic_mult(g.m[c0 + r], g.e[c0 + r]) + IVIT_MAGIC;
-                        b[ii][r] = clamp_i32((int)(unsigned)__double_as_longlong(tq), -128, 127);
+                        b[ii][r] = clamp_i32((int)(unsigned)__double_as_longlong(tq), QLO, QHI);
                     }
                 }
             }
@@ -1100,9 +1106,11 @@ __global__ __launch_bounds__(SK_NT, 2) void gemm_i8_skinny_kernel(GemmArgs g)
     }
 }
 
-template <int EPI>
+template <int EPIW>
 int launch_gemm(GemmArgs& g, const char* name, ivit_stream_t stream, int qkv_planes = 3)   // EPI_QKV: N = qkv_planes * heads * head_dim
 {
+    constexpr int EPI = epi_kind(EPIW);
+    constexpr bool NARROW = EPIW != EPI;     // a 4-bit form: the product's kernels only, none of the lab build's ablations
     IVIT_REQUIRE(g.A && g.W && g.out, "%s: NULL operand", name);
     IVIT_REQUIRE(g.M > 0 && g.N > 0 && g.K > 0, "%s: empty problem M=%d N=%d K=%d", name, g.M, g.N, g.K);
     IVIT_REQUIRE(g.K % BK == 0, "%s: K=%d must be a multiple of %d", name, g.K, BK);
@@ -1153,9 +1161,9 @@ int launch_gemm(GemmArgs& g, const char* name, ivit_stream_t stream, int qkv_pla
             const int nstrips = (g.M + 15) >> 4;
             const int grid = (nstrips + SK_WPB - 1) / SK_WPB < 512 ? (nstrips + SK_WPB - 1) / SK_WPB : 512;      // two workgroups of 8 waves per CU
             const bool any_k = IVIT_LAB && (g_debug_flags2 & (1 << 21));      // lab A/B: the run-time-K instantiation for every K
-            if (g.K == 128 && !any_k) hipLaunchKernelGGL((gemm_i8_skinny_kernel<EPI, 4>), dim3(grid), dim3(SK_NT), 0, ivit_stream(stream), g);
-            else if (g.K == 64 && !any_k) hipLaunchKernelGGL((gemm_i8_skinny_kernel<EPI, 2>), dim3(grid), dim3(SK_NT), 0, ivit_stream(stream), g);
-            else hipLaunchKernelGGL((gemm_i8_skinny_kernel<EPI, 0>), dim3(grid), dim3(SK_NT), 0, ivit_stream(stream), g);
+            if (g.K == 128 && !any_k) hipLaunchKernelGGL((gemm_i8_skinny_kernel<EPIW, 4>), dim3(grid), dim3(SK_NT), 0, ivit_stream(stream), g);
+            else if (g.K == 64 && !any_k) hipLaunchKernelGGL((gemm_i8_skinny_kernel<EPIW, 2>), dim3(grid), dim3(SK_NT), 0, ivit_stream(stream), g);
+            else hipLaunchKernelGGL((gemm_i8_skinny_kernel<EPIW, 0>), dim3(grid), dim3(SK_NT), 0, ivit_stream(stream), g);
             IVIT_CHECK_LAUNCH(name);
         }
     }
@@ -1200,7 +1208,7 @@ int launch_gemm(GemmArgs& g, const char* name, ivit_stream_t stream, int qkv_pla
             if (all_halves) g.split_from = 0;
             const dim3 grid(all_halves ? 2 * ntiles : (ntiles < 512 ? ntiles : 512));
 #if IVIT_LAB
-            if constexpr (EPI == EPI_RQ) {   // timing ablations (scripts/gemm_ab.py --frags): what each stream of the kernel costs
+            if constexpr (EPI == EPI_RQ && !NARROW) {   // timing ablations (scripts/gemm_ab.py --frags): what each stream of the kernel costs
                 switch (g_debug_flags & 31) {
 #define IVIT_WR_ABL(v) case v: hipLaunchKernelGGL((gemm_i8_wreg_kernel<EPI_RQ, v>), grid, dim3(BIG_NT), 0, ivit_stream(stream), g); IVIT_CHECK_LAUNCH(name)
                     case 16: g.res = (const int8_t*)g_stamp_buf; hipLaunchKernelGGL((gemm_i8_wreg_kernel<EPI_RQ, 16>), (g_debug_flags & 4096) ? dim3(256) : grid, dim3(BIG_NT), (g_debug_flags & 4096) ? 40960 : 0, ivit_stream(stream), g); IVIT_CHECK_LAUNCH(name);
@@ -1217,7 +1225,7 @@ int launch_gemm(GemmArgs& g, const char* name, ivit_stream_t stream, int qkv_pla
                                      (EPI != EPI_RESID || ((int64_t)g.M + 16) * g.ldr < 4294967296ll),
                                  "%s: IVIT_W_FRAGS16 addresses its output (and residual) with 32-bit offsets: operand of 4 GiB or more", name);
 #if IVIT_LAB
-                    if constexpr (EPI == EPI_RQ || EPI == EPI_RESID) {
+                    if constexpr ((EPI == EPI_RQ || EPI == EPI_RESID) && !NARROW) {
                         if ((g_debug_flags2 & 256) && g.stamp) {   // stamped timeline (scripts/wreg_timeline.py --s16)
                             if (EPI == EPI_RESID && g.res_f32) hipLaunchKernelGGL((gemm_i8_wreg_kernel<EPI, 16 | 2048 | 4096, true>), grid, dim3(BIG_NT), 0, ivit_stream(stream), g);
                             else hipLaunchKernelGGL((gemm_i8_wreg_kernel<EPI, 16 | 2048, true>), grid, dim3(BIG_NT), 0, ivit_stream(stream), g);
@@ -1227,17 +1235,17 @@ int launch_gemm(GemmArgs& g, const char* name, ivit_stream_t stream, int qkv_pla
 #endif
                     if constexpr (EPI == EPI_RESID) {
                         if (g.res_f32) {     // ABL bit 12: the residual QuantAct on float32 fmas (residual_f32_form)
-                            hipLaunchKernelGGL((gemm_i8_wreg_kernel<EPI, 4096, true>), grid, dim3(BIG_NT), 0, ivit_stream(stream), g);
+                            hipLaunchKernelGGL((gemm_i8_wreg_kernel<EPIW, 4096, true>), grid, dim3(BIG_NT), 0, ivit_stream(stream), g);
                             IVIT_CHECK_LAUNCH(name);
                         }
                     }
-                    hipLaunchKernelGGL((gemm_i8_wreg_kernel<EPI, 0, true>), grid, dim3(BIG_NT), 0, ivit_stream(stream), g);
+                    hipLaunchKernelGGL((gemm_i8_wreg_kernel<EPIW, 0, true>), grid, dim3(BIG_NT), 0, ivit_stream(stream), g);
                     IVIT_CHECK_LAUNCH(name);
                 } else {
                     IVIT_REQUIRE(false, "%s: IVIT_W_FRAGS16 has no 16-bit epilogue; pack the weights with ivit_pack_weight_frags_i8", name);
                 }
             }
-            hipLaunchKernelGGL((gemm_i8_wreg_kernel<EPI>), grid, dim3(BIG_NT), 0, ivit_stream(stream), g);
+            hipLaunchKernelGGL((gemm_i8_wreg_kernel<EPIW>), grid, dim3(BIG_NT), 0, ivit_stream(stream), g);
             IVIT_CHECK_LAUNCH(name);
         }
     }
@@ -1266,13 +1274,13 @@ int launch_gemm(GemmArgs& g, const char* name, ivit_stream_t stream, int qkv_pla
             // equivalent and the former half-main-loop delay (26 / 98 units at K = 768 / 3072) cost 4-8 %: off by default
             g.stagger_units = (g_debug_flags >> 16) & 63;
             const int grid = rounds > 0 ? SLOTS : (split ? 2 * R : R);
-            hipLaunchKernelGGL((gemm_i8_pers_kernel<EPI>), dim3(grid), dim3(BIG_NT), one_per_cu ? 20480 : 0, ivit_stream(stream), g);
+            hipLaunchKernelGGL((gemm_i8_pers_kernel<EPIW>), dim3(grid), dim3(BIG_NT), one_per_cu ? 20480 : 0, ivit_stream(stream), g);
             IVIT_CHECK_LAUNCH(name);
         }
     }
     g.tiles_m = (g.M + BM - 1) / BM;
     g.tiles_n = (g.N + BN - 1) / BN;
-    hipLaunchKernelGGL(gemm_i8_kernel<EPI>, dim3(g.tiles_m * g.tiles_n), dim3(NT), 0, ivit_stream(stream), g);
+    hipLaunchKernelGGL(gemm_i8_kernel<EPIW>, dim3(g.tiles_m * g.tiles_n), dim3(NT), 0, ivit_stream(stream), g);
     IVIT_CHECK_LAUNCH(name);
 }
 
@@ -1327,18 +1335,37 @@ IVIT_EXPORT int ivit_pack_weight_frags_i8(const int8_t* W, int64_t ldw, int N, i
     IVIT_CHECK_LAUNCH("ivit_pack_weight_frags_i8");
 }
 
-IVIT_EXPORT int ivit_gemm_i8_requant_ex(const int8_t* A, int64_t lda, const int8_t* W, int64_t ldw, const int32_t* bias,
-                                     const uint32_t* m, const int32_t* e, int8_t* out, int64_t ldo, int M, int N,
-                                     int K, int layouts, ivit_stream_t stream)
+// ivit_gemm_i8_requant_ex and its 4-bit form (EPIW = EPI_RQ | EPI_NARROW_MID): one argument block, one set of checks
+template <int EPIW>
+static int gemm_requant_ex(const char* name, const int8_t* A, int64_t lda, const int8_t* W, int64_t ldw, const int32_t* bias,
+                           const uint32_t* m, const int32_t* e, int8_t* out, int64_t ldo, int M, int N, int K, int layouts,
+                           ivit_stream_t stream)
 {
     GemmArgs g{};
     g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.bias = bias; g.m = m; g.e = e;
     g.out = out; g.ldo = ldo; g.M = M; g.N = N; g.K = K;
     g.a_blocks = layouts & 1; g.w_blocks = (layouts >> 1) & 1; g.out_blocks = (layouts >> 2) & 1; g.w_frags = (layouts & 16) ? 2 : ((layouts >> 3) & 1);
-    IVIT_REQUIRE((layouts & ~31) == 0 && (layouts & 24) != 24, "ivit_gemm_i8_requant_ex: unknown layout bits");
+    IVIT_REQUIRE((layouts & ~31) == 0 && (layouts & 24) != 24, "%s: unknown layout bits", name);
     IVIT_REQUIRE(!g.out_blocks || (N % 64 == 0 && ldo == N && ((int64_t)M + 15) * N < 2147483648ll),
-                 "ivit_gemm_i8_requant_ex: block-layout output needs N %% 64 == 0, ldo == N and a buffer below 2 GiB");
-    return launch_gemm<EPI_RQ>(g, "ivit_gemm_i8_requant_ex", stream);
+                 "%s: block-layout output needs N %% 64 == 0, ldo == N and a buffer below 2 GiB", name);
+    return launch_gemm<EPIW>(g, name, stream);
+}
+
+IVIT_EXPORT int ivit_gemm_i8_requant_ex(const int8_t* A, int64_t lda, const int8_t* W, int64_t ldw, const int32_t* bias,
+                                     const uint32_t* m, const int32_t* e, int8_t* out, int64_t ldo, int M, int N,
+                                     int K, int layouts, ivit_stream_t stream)
+{
+    return gemm_requant_ex<EPI_RQ>("ivit_gemm_i8_requant_ex", A, lda, W, ldw, bias, m, e, out, ldo, M, N, K, layouts, stream);
+}
+
+IVIT_EXPORT int ivit_gemm_i8_requant_bits_ex(const int8_t* A, int64_t lda, const int8_t* W, int64_t ldw, const int32_t* bias,
+                                             const uint32_t* m, const int32_t* e, int8_t* out, int64_t ldo, int M, int N,
+                                             int K, int layouts, int bits, ivit_stream_t stream)
+{
+    const char* name = "ivit_gemm_i8_requant_bits_ex";
+    IVIT_REQUIRE(bits == 4 || bits == 8, "%s: bits=%d must be 4 or 8", name, bits);
+    if (bits == 8) return gemm_requant_ex<EPI_RQ>(name, A, lda, W, ldw, bias, m, e, out, ldo, M, N, K, layouts, stream);
+    return gemm_requant_ex<EPI_RQ | EPI_NARROW_MID>(name, A, lda, W, ldw, bias, m, e, out, ldo, M, N, K, layouts, stream);
 }
 
 IVIT_EXPORT int ivit_gemm_i8_requant_lut_ex(const int8_t* A, int64_t lda, const int8_t* W, int64_t ldw, const int32_t* bias,
@@ -1385,11 +1412,12 @@ static void residual_f32_form(GemmArgs& g)
     g.res_f32 = 1;
 }
 
-IVIT_EXPORT int ivit_gemm_i8_requant_residual_ex(const int8_t* A, int64_t lda, const int8_t* W, int64_t ldw,
-                                              const int32_t* bias, const uint32_t* m, const int32_t* e,
-                                              const int8_t* res, int64_t ldr, uint32_t m_main, int32_t e_main,
-                                              uint32_t m_res, int32_t e_res, int8_t* out, int64_t ldo, int M, int N,
-                                              int K, int layouts, ivit_stream_t stream)
+// ivit_gemm_i8_requant_residual_ex and its 4-bit forms (EPIW = EPI_RESID with EPI_NARROW_MID and / or EPI_NARROW_OUT)
+template <int EPIW>
+static int gemm_residual_ex(const char* name, const int8_t* A, int64_t lda, const int8_t* W, int64_t ldw, const int32_t* bias,
+                            const uint32_t* m, const int32_t* e, const int8_t* res, int64_t ldr, uint32_t m_main, int32_t e_main,
+                            uint32_t m_res, int32_t e_res, int8_t* out, int64_t ldo, int M, int N, int K, int layouts,
+                            ivit_stream_t stream)
 {
     GemmArgs g{};
     g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.bias = bias; g.m = m; g.e = e;
@@ -1397,11 +1425,38 @@ IVIT_EXPORT int ivit_gemm_i8_requant_residual_ex(const int8_t* A, int64_t lda, c
     g.M_main = ivit_dyadic_to_double(m_main, e_main);
     g.M_res = ivit_dyadic_to_double(m_res, e_res);
     residual_f32_form(g);
-    IVIT_REQUIRE(g.M_main < 1048576.0 && g.M_res < 1048576.0,
-                 "ivit_gemm_i8_requant_residual_ex: residual multiplier >= 2^20 is outside the int8 fast path");
+    IVIT_REQUIRE(g.M_main < 1048576.0 && g.M_res < 1048576.0, "%s: residual multiplier >= 2^20 is outside the int8 fast path", name);
     g.a_blocks = layouts & 1; g.w_blocks = (layouts >> 1) & 1; g.w_frags = (layouts & 16) ? 2 : ((layouts >> 3) & 1);
-    IVIT_REQUIRE((layouts & ~27) == 0 && (layouts & 24) != 24, "ivit_gemm_i8_requant_residual_ex: unknown layout bits");
-    return launch_gemm<EPI_RESID>(g, "ivit_gemm_i8_requant_residual_ex", stream);
+    IVIT_REQUIRE((layouts & ~27) == 0 && (layouts & 24) != 24, "%s: unknown layout bits", name);
+    return launch_gemm<EPIW>(g, name, stream);
+}
+
+IVIT_EXPORT int ivit_gemm_i8_requant_residual_ex(const int8_t* A, int64_t lda, const int8_t* W, int64_t ldw,
+                                              const int32_t* bias, const uint32_t* m, const int32_t* e,
+                                              const int8_t* res, int64_t ldr, uint32_t m_main, int32_t e_main,
+                                              uint32_t m_res, int32_t e_res, int8_t* out, int64_t ldo, int M, int N,
+                                              int K, int layouts, ivit_stream_t stream)
+{
+    return gemm_residual_ex<EPI_RESID>("ivit_gemm_i8_requant_residual_ex", A, lda, W, ldw, bias, m, e, res, ldr, m_main, e_main, m_res,
+                                       e_res, out, ldo, M, N, K, layouts, stream);
+}
+
+IVIT_EXPORT int ivit_gemm_i8_requant_residual_bits_ex(const int8_t* A, int64_t lda, const int8_t* W, int64_t ldw,
+                                                      const int32_t* bias, const uint32_t* m, const int32_t* e,
+                                                      const int8_t* res, int64_t ldr, uint32_t m_main, int32_t e_main,
+                                                      uint32_t m_res, int32_t e_res, int8_t* out, int64_t ldo, int M, int N,
+                                                      int K, int layouts, int bits_mid, int bits_out, ivit_stream_t stream)
+{
+    const char* name = "ivit_gemm_i8_requant_residual_bits_ex";
+    IVIT_REQUIRE((bits_mid == 4 || bits_mid == 8) && (bits_out == 4 || bits_out == 8), "%s: bits_mid=%d, bits_out=%d must be 4 or 8",
+                 name, bits_mid, bits_out);
+#define IVIT_RESID_BITS(EPIW) \
+    return gemm_residual_ex<EPIW>(name, A, lda, W, ldw, bias, m, e, res, ldr, m_main, e_main, m_res, e_res, out, ldo, M, N, K, layouts, stream)
+    if (bits_mid == 8 && bits_out == 8) IVIT_RESID_BITS(EPI_RESID);
+    if (bits_mid == 4 && bits_out == 8) IVIT_RESID_BITS(EPI_RESID | EPI_NARROW_MID);
+    if (bits_mid == 8) IVIT_RESID_BITS(EPI_RESID | EPI_NARROW_OUT);
+    IVIT_RESID_BITS(EPI_RESID | EPI_NARROW_MID | EPI_NARROW_OUT);
+#undef IVIT_RESID_BITS
 }
 
 IVIT_EXPORT int ivit_gemm_i8_requant_residual(const int8_t* A, int64_t lda, const int8_t* W, int64_t ldw,

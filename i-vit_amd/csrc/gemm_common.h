@@ -40,6 +40,16 @@ constexpr int SMEM_BYTES = 2 * STAGE_BYTES;  // 32 KiB >= 128 * 132
 //   QuantAct): k16 = clamp16(RNE(acc * M[n])), out16 = clamp16(RNE(k16 * M_main) + RNE(res16 * M_res)), straight from the
 //   accumulator registers (weights-in-registers kernel only)
 enum { EPI_RQ = 0, EPI_RESID = 1, EPI_QKV = 2, EPI_I32 = 3, EPI_RESID16 = 4, EPI_RQ16 = 5, EPI_RQ16_RES16 = 6 };
+// 4-bit QuantActs (the width knobs of vit_quant.py:180-187 at 4: the clamp is [-8, 7], quant_utils.py:209,247-249; the value still
+// lives in an int8 byte).  The template argument of a kernel or an epilogue is the kind above, optionally with these flags: the
+// narrow forms are instantiations of their own, selected by the `_bits` entries only, and an argument without a flag is the 8-bit
+// form with its literal bounds.
+//   EPI_NARROW_MID: the QuantAct of the accumulators (EPI_RQ: the output; EPI_RESID: k) clamps to 4 bits
+//   EPI_NARROW_OUT: EPI_RESID only: the residual QuantAct clamps its output to 4 bits
+constexpr int EPI_NARROW_MID = 0x100, EPI_NARROW_OUT = 0x200;
+constexpr int epi_kind(int epiw) { return epiw & 0xff; }
+constexpr int epi_lo(int epiw, int flag) { return (epiw & flag) ? -8 : -128; }
+constexpr int epi_hi(int epiw, int flag) { return (epiw & flag) ? 7 : 127; }
 
 
 struct GemmArgs {
@@ -141,9 +151,10 @@ struct NoHook {
 
 // Phase 2 of the int8 epilogues: the staged tile Cs[token][channel] (row stride CH + 4) -> 16-byte row-contiguous chunks: optional
 // residual QuantAct, optional head-major remap or byte map, store.  Called by every thread right after its phase-1 LDS writes.
-template <int EPI, int TOK, int NTHREADS, int CH, typename Hook>
+template <int EPIW, int TOK, int NTHREADS, int CH, typename Hook>
 IVIT_DEV void epilogue_phase2(const GemmArgs& g, char* smem, int m0, int n0, int tid, const Hook& hook, const unsigned char* lut_lds)
 {
+    constexpr int EPI = epi_kind(EPIW);
     constexpr int CSS = CH + 4;
     constexpr int CPR = CH / 16;
     // Phase 2 work items of this thread: NIT chunks (token row tl, 16-byte column chunk cc).  The residual loads go out BEFORE the
@@ -239,7 +250,7 @@ IVIT_DEV void epilogue_phase2(const GemmArgs& g, char* smem, int m0, int n0, int
                     int xr = (int)(int8_t)(rr[d] >> (8 * bb));
                     // quant_utils.py:229-245: two independently rounded products, then the sum
                     int sres = requant_exact(k3, g.M_main) + requant_exact(xr, g.M_res);
-                    o[bb] = clamp_i32(sres, -128, 127);
+                    o[bb] = clamp_i32(sres, epi_lo(EPIW, EPI_NARROW_OUT), epi_hi(EPIW, EPI_NARROW_OUT));
                 }
                 v[it][d] = pack4_i8(o[0], o[1], o[2], o[3]);
             }
@@ -295,11 +306,12 @@ IVIT_DEV void epilogue_phase2(const GemmArgs& g, char* smem, int m0, int n0, int
     }
 }
 
-template <int EPI, int TI, int TJ, int TOK, int NTHREADS, int CH = 128, typename Hook = NoHook>
+template <int EPIW, int TI, int TJ, int TOK, int NTHREADS, int CH = 128, typename Hook = NoHook>
 IVIT_DEV void epilogue_i8(v16i (&acc)[TI][TJ], const GemmArgs& g, char* smem, const char* rq_lds, int m0, int n0,
                           int wch, int wtok, int tid, int h, int l31, const Hook& hook = Hook(),
                           const unsigned char* lut_lds = nullptr)
 {
+    constexpr int QLO = epi_lo(EPIW, EPI_NARROW_MID), QHI = epi_hi(EPIW, EPI_NARROW_MID);   // -128, 127 unless the narrow form
     // The epilogue is a short VALU burst next to the co-resident workgroup's MFMA stream: give it issue priority
     // so its dependent chains do not wait behind queued MFMAs (which run in the matrix pipe once issued).
     __builtin_amdgcn_s_setprio(2);
@@ -350,7 +362,7 @@ IVIT_DEV void epilogue_i8(v16i (&acc)[TI][TJ], const GemmArgs& g, char* smem, co
                     // tl, th are bit patterns of floats next to 1.5 * 2^23, their differences are tiny: no wrap-around.
                     asm("v_sad_u32 %0, %1, %2, %3" : "=v"(unc) : "v"(tl), "v"(th), "v"(unc));
                     amax = fmaxf(amax, fabsf(a));
-                    b[j][jj] = clamp_i32(tl, 0x4B400000 - 128, 0x4B400000 + 127);  // low byte = int8 result
+                    b[j][jj] = clamp_i32(tl, 0x4B400000 + QLO, 0x4B400000 + QHI);  // low byte = int8 result
                 }
             {
                 const bool bad = (unc != 0) | (amax >= 4194304.0f);
@@ -367,7 +379,7 @@ IVIT_DEV void epilogue_i8(v16i (&acc)[TI][TJ], const GemmArgs& g, char* smem, co
                             // quant_utils.py:229-230: float64 product (53-bit rounding), /2^e, round-half-even
                             double p = (double)acc[i][j][4 * q + jj] * Mc[jj];
                             double t = p + IVIT_MAGIC;
-                            b[j][jj] = clamp_i32((int)(unsigned)__double_as_longlong(t), -128, 127);
+                            b[j][jj] = clamp_i32((int)(unsigned)__double_as_longlong(t), QLO, QHI);
                         }
                 }
             }
@@ -381,7 +393,7 @@ IVIT_DEV void epilogue_i8(v16i (&acc)[TI][TJ], const GemmArgs& g, char* smem, co
         }
         __builtin_amdgcn_sched_barrier(0);
     }
-    epilogue_phase2<EPI, TOK, NTHREADS, CH, Hook>(g, smem, m0, n0, tid, hook, lut_lds);
+    epilogue_phase2<EPIW, TOK, NTHREADS, CH, Hook>(g, smem, m0, n0, tid, hook, lut_lds);
 }
 
 // ---- the int8 epilogue for accumulators of v_mfma_i32_16x16x64_i8 (the weights-in-registers kernel's S16 form).
@@ -389,10 +401,11 @@ IVIT_DEV void epilogue_i8(v16i (&acc)[TI][TJ], const GemmArgs& g, char* smem, co
 // 16 j + l15 and the four consecutive channels wch + 16 i + 4 g4 + r of register r -- again one dword of four channels per
 // token, so phase 1 is the arithmetic of epilogue_i8 with other loop bounds (batches of 16 outputs per certificate ballot) and
 // phase 2 is shared.
-template <int EPI, int NJ, int NTHREADS, int CH, typename Hook>
+template <int EPIW, int NJ, int NTHREADS, int CH, typename Hook>
 IVIT_DEV void epilogue_i8_16(v4i (&acc)[4][NJ], const GemmArgs& g, char* smem, const char* rq_lds, int m0, int n0, int wch, int tid,
                              int g4, int l15, const Hook& hook, const unsigned char* lut_lds)
 {
+    constexpr int QLO = epi_lo(EPIW, EPI_NARROW_MID), QHI = epi_hi(EPIW, EPI_NARROW_MID);
     static_assert(NJ % 4 == 0, "batches of four token sub-tiles");
     __builtin_amdgcn_s_setprio(2);
     hook.issue();
@@ -430,7 +443,7 @@ IVIT_DEV void epilogue_i8_16(v4i (&acc)[4][NJ], const GemmArgs& g, char* smem, c
                     const int tl = __float_as_int(__builtin_fmaf(a, lo[r], 12582912.0f));
                     const int th = __float_as_int(__builtin_fmaf(a, hi[r], 12582912.0f));
                     asm("v_sad_u32 %0, %1, %2, %3" : "=v"(unc) : "v"(tl), "v"(th), "v"(unc));
-                    b[j][r] = clamp_i32(tl, 0x4B400000 - 128, 0x4B400000 + 127);  // low byte = int8 result
+                    b[j][r] = clamp_i32(tl, 0x4B400000 + QLO, 0x4B400000 + QHI);  // low byte = int8 result
                 }
             const bool bad = unc != 0;
             if (__builtin_amdgcn_ballot_w64(bad) != 0) {  // rare: exact float64 evaluation of the batch (quant_utils.py:229-230)
@@ -443,7 +456,7 @@ IVIT_DEV void epilogue_i8_16(v4i (&acc)[4][NJ], const GemmArgs& g, char* smem, c
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const double t = (double)acc[i][jb + j][r] * Mc[r] + IVIT_MAGIC;
-                        b[j][r] = clamp_i32((int)(unsigned)__double_as_longlong(t), -128, 127);
+                        b[j][r] = clamp_i32((int)(unsigned)__double_as_longlong(t), QLO, QHI);
                     }
             }
 #pragma unroll
@@ -456,7 +469,7 @@ IVIT_DEV void epilogue_i8_16(v4i (&acc)[4][NJ], const GemmArgs& g, char* smem, c
         }
         __builtin_amdgcn_sched_barrier(0);
     }
-    epilogue_phase2<EPI, 16 * NJ, NTHREADS, CH, Hook>(g, smem, m0, n0, tid, hook, lut_lds);
+    epilogue_phase2<EPIW, 16 * NJ, NTHREADS, CH, Hook>(g, smem, m0, n0, tid, hook, lut_lds);
 }
 
 // ---- the same epilogue WITHOUT the LDS round trip (EPI_RQ row-major or block layout, EPI_RESID, EPI_QKV).
@@ -469,6 +482,7 @@ IVIT_DEV void epilogue_i8_16(v4i (&acc)[4][NJ], const GemmArgs& g, char* smem, c
 // per-chunk address arithmetic on the same bytes; its VALU and LDS instructions issue at one per ~8 cycles beside the co-resident
 // workgroup's MFMA stream (profiles/r03g_wreg16_timeline.txt, r03i_epilogue_probe.txt), so what is not issued is what is saved.
 // The residual QuantAct works on the transposed chunk against a 16-byte residual load of the same row segment.
+template <int LO = -128, int HI = 127>
 IVIT_DEV void residual_chunk_f32(int (&v)[4], const int4& res, float Mf_main, float Mf_res, float magic_v)
 {
     const int rr[4] = {res.x, res.y, res.z, res.w};
@@ -482,12 +496,13 @@ IVIT_DEV void residual_chunk_f32(int (&v)[4], const int4& res, float Mf_main, fl
             float f1, f2;      // plain v_fma_f32 through asm: see epilogue_phase2
             asm("v_fma_f32 %0, %1, %2, %3" : "=v"(f1) : "v"(kf), "s"(Mf_main), "v"(magic_v));
             asm("v_fma_f32 %0, %1, %2, %3" : "=v"(f2) : "v"(xf), "s"(Mf_res), "v"(magic_v));
-            o[bb] = (unsigned)clamp_i32((int)((unsigned)__float_as_int(f1) + (unsigned)__float_as_int(f2) - 2u * 0x4B400000u), -128, 127);
+            o[bb] = (unsigned)clamp_i32((int)((unsigned)__float_as_int(f1) + (unsigned)__float_as_int(f2) - 2u * 0x4B400000u), LO, HI);
         }
         v[d] = (int)(__builtin_amdgcn_perm(o[1], o[0], 0x0c0c0400u) | __builtin_amdgcn_perm(o[3], o[2], 0x04000c0cu));
     }
 }
 
+template <int LO = -128, int HI = 127>
 IVIT_DEV void residual_chunk_f64(int (&v)[4], const int4& res, double M_main, double M_res)
 {
     const int rr[4] = {res.x, res.y, res.z, res.w};
@@ -498,16 +513,19 @@ IVIT_DEV void residual_chunk_f64(int (&v)[4], const int4& res, double M_main, do
         for (int bb = 0; bb < 4; ++bb) {
             const int k3 = (int)(int8_t)(v[d] >> (8 * bb));
             const int xr = (int)(int8_t)(rr[d] >> (8 * bb));
-            o[bb] = clamp_i32(requant_exact(k3, M_main) + requant_exact(xr, M_res), -128, 127);   // quant_utils.py:229-245
+            o[bb] = clamp_i32(requant_exact(k3, M_main) + requant_exact(xr, M_res), LO, HI);   // quant_utils.py:229-245
         }
         v[d] = pack4_i8(o[0], o[1], o[2], o[3]);
     }
 }
 
-template <int EPI, int NJ, int ABL, typename Hook>
+template <int EPIW, int NJ, int ABL, typename Hook>
 IVIT_DEV void epilogue_direct_16(v4i (&acc)[4][NJ], const GemmArgs& g, const char* rq_lds, int m0, int n0, int wch, int g4, int l15,
                                  const Hook& hook, const unsigned char* lut_lds, unsigned long long* st = nullptr)
 {
+    constexpr int EPI = epi_kind(EPIW);
+    constexpr int QLO = epi_lo(EPIW, EPI_NARROW_MID), QHI = epi_hi(EPIW, EPI_NARROW_MID);
+    constexpr int RLO = epi_lo(EPIW, EPI_NARROW_OUT), RHI = epi_hi(EPIW, EPI_NARROW_OUT);     // the residual QuantAct
     static_assert(NJ % 4 == 0 && (EPI == EPI_RQ || EPI == EPI_RESID || EPI == EPI_QKV), "direct epilogue: int8 outputs");
     __builtin_amdgcn_s_setprio(2);
     hook.issue();
@@ -551,7 +569,7 @@ IVIT_DEV void epilogue_direct_16(v4i (&acc)[4][NJ], const GemmArgs& g, const cha
                     const int tl = __float_as_int(__builtin_fmaf(a, lo[r], 12582912.0f));
                     const int th = __float_as_int(__builtin_fmaf(a, hi[r], 12582912.0f));
                     asm("v_sad_u32 %0, %1, %2, %3" : "=v"(unc) : "v"(tl), "v"(th), "v"(unc));
-                    b[j][r] = clamp_i32(tl, 0x4B400000 - 128, 0x4B400000 + 127);  // low byte = int8 result
+                    b[j][r] = clamp_i32(tl, 0x4B400000 + QLO, 0x4B400000 + QHI);  // low byte = int8 result
                 }
             if (__builtin_amdgcn_ballot_w64(unc != 0) != 0) {  // rare: exact float64 evaluation of the batch (quant_utils.py:229-230)
                 const int c0 = min(ncol + 16 * i + 4 * g4, g.N - 4);
@@ -563,7 +581,7 @@ IVIT_DEV void epilogue_direct_16(v4i (&acc)[4][NJ], const GemmArgs& g, const cha
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const double t = (double)acc[i][jb + j][r] * Mc[r] + IVIT_MAGIC;
-                        b[j][r] = clamp_i32((int)(unsigned)__double_as_longlong(t), -128, 127);
+                        b[j][r] = clamp_i32((int)(unsigned)__double_as_longlong(t), QLO, QHI);
                     }
             }
 #pragma unroll
@@ -631,8 +649,8 @@ IVIT_DEV void epilogue_direct_16(v4i (&acc)[4][NJ], const GemmArgs& g, const cha
             const v2u bd = __builtin_amdgcn_permlane16_swap(ab.y, cd.y, false, false);
             int v[4] = {(int)ac.x, (int)ac.y, (int)bd.x, (int)bd.y};
             if constexpr (EPI == EPI_RESID) {
-                if constexpr (ABL & 4096) residual_chunk_f32(v, rv[bi][j], g.Mf_main, g.Mf_res, magic_v);
-                else residual_chunk_f64(v, rv[bi][j], g.M_main, g.M_res);
+                if constexpr (ABL & 4096) residual_chunk_f32<RLO, RHI>(v, rv[bi][j], g.Mf_main, g.Mf_res, magic_v);
+                else residual_chunk_f64<RLO, RHI>(v, rv[bi][j], g.M_main, g.M_res);
             }
             if constexpr (EPI == EPI_RQ) {
                 if (lut_lds) {      // uniform: a 256-entry int8 -> int8 map (LDS) over the 16 bytes of the chunk

@@ -1126,7 +1126,8 @@ __global__ __launch_bounds__(NT) void patchify_u8_kernel(const uint8_t* img, int
     }
 }
 
-// cls row + position embedding, vit_quant.py:290-296 (see ivit_hip.h)
+// cls row + position embedding, vit_quant.py:290-296 (see ivit_hip.h).  LO, HI: the clamp of qact1 ([-8, 7] at block_input_bw = 4)
+template <int LO, int HI>
 __global__ __launch_bounds__(NT) void embed_kernel(const int8_t* patch, const int16_t* pos_add, const int8_t* cls_row,
                                                    double Mq, int8_t* out, int batch, int tokens, int C)
 {
@@ -1145,7 +1146,7 @@ __global__ __launch_bounds__(NT) void embed_kernel(const int8_t* patch, const in
             const int16_t* pa = pos_add + (int64_t)tok * C + 4 * d;
             int o[4];
 #pragma unroll
-            for (int c = 0; c < 4; ++c) o[c] = clamp_i32(requant_exact(sx8(w, c), Mq) + (int)pa[c], -128, 127);
+            for (int c = 0; c < 4; ++c) o[c] = clamp_i32(requant_exact(sx8(w, c), Mq) + (int)pa[c], LO, HI);
             res = pack4(o[0], o[1], o[2], o[3]);
         }
         *reinterpret_cast<int*>(out + ((int64_t)b * tokens + tok) * C + 4 * d) = res;
@@ -1292,11 +1293,12 @@ __global__ __launch_bounds__(NT) void requant_i32_kernel(const int32_t* z, int64
     }
 }
 
+template <int LO, int HI>      // the clamp of the residual QuantAct: [-128, 127], or [-8, 7] at 4 bits
 __global__ __launch_bounds__(NT) void residual_requant_kernel(const int8_t* a, double Ma, const int8_t* b, double Mb,
                                                               int8_t* out, int64_t n)
 {
     for (int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * NT)
-        out[i] = (int8_t)clamp_i32(requant_exact(a[i], Ma) + requant_exact(b[i], Mb), -128, 127);
+        out[i] = (int8_t)clamp_i32(requant_exact(a[i], Ma) + requant_exact(b[i], Mb), LO, HI);
 }
 
 __global__ __launch_bounds__(NT) void f32_to_i32_kernel(const float* x, int64_t rows, int C, const float* s, int n_s,
@@ -1955,20 +1957,39 @@ IVIT_EXPORT int ivit_quantize_patchify_ld_f32_i8(const float* img, int8_t* A, in
     return launch_patchify("ivit_quantize_patchify_ld_f32_i8", img, A, lda, batch, chans, hw, patch, inv_scale, stream);
 }
 
+namespace {
+int launch_embed_i8(const char* name, const int8_t* patch, const int16_t* pos_add, const int8_t* cls_row, uint32_t m, int32_t e,
+                    int8_t* out, int batch, int tokens, int C, int bits, ivit_stream_t stream)
+{
+    IVIT_REQUIRE(bits == 4 || bits == 8, "%s: bits=%d must be 4 or 8", name, bits);
+    IVIT_REQUIRE(patch && pos_add && cls_row && out, "%s: NULL operand", name);
+    IVIT_REQUIRE(batch > 0 && tokens > 1 && C > 0 && C % 4 == 0, "%s: bad shape", name);
+    IVIT_REQUIRE(((uintptr_t)patch % 4 == 0) && ((uintptr_t)out % 4 == 0) && ((uintptr_t)cls_row % 4 == 0) &&
+                     ((uintptr_t)pos_add % 8 == 0),
+                 "%s: misaligned", name);
+    const double Mq = ivit_dyadic_to_double(m, e);
+    IVIT_REQUIRE(Mq < 1048576.0, "%s: requant multiplier too large", name);
+    const int64_t total = (int64_t)batch * tokens * (C / 4);
+    if (bits == 8)
+        hipLaunchKernelGGL((embed_kernel<-128, 127>), dim3(ew_grid(total)), dim3(NT), 0, ivit_stream(stream), patch, pos_add, cls_row,
+                           Mq, out, batch, tokens, C);
+    else
+        hipLaunchKernelGGL((embed_kernel<-8, 7>), dim3(ew_grid(total)), dim3(NT), 0, ivit_stream(stream), patch, pos_add, cls_row,
+                           Mq, out, batch, tokens, C);
+    IVIT_CHECK_LAUNCH(name);
+}
+}  // namespace
+
 IVIT_EXPORT int ivit_embed_assemble_i8(const int8_t* patch, const int16_t* pos_add, const int8_t* cls_row, uint32_t m,
                                        int32_t e, int8_t* out, int batch, int tokens, int C, ivit_stream_t stream)
 {
-    IVIT_REQUIRE(patch && pos_add && cls_row && out, "ivit_embed_assemble_i8: NULL operand");
-    IVIT_REQUIRE(batch > 0 && tokens > 1 && C > 0 && C % 4 == 0, "ivit_embed_assemble_i8: bad shape");
-    IVIT_REQUIRE(((uintptr_t)patch % 4 == 0) && ((uintptr_t)out % 4 == 0) && ((uintptr_t)cls_row % 4 == 0) &&
-                     ((uintptr_t)pos_add % 8 == 0),
-                 "ivit_embed_assemble_i8: misaligned");
-    const double Mq = ivit_dyadic_to_double(m, e);
-    IVIT_REQUIRE(Mq < 1048576.0, "ivit_embed_assemble_i8: requant multiplier too large");
-    const int64_t total = (int64_t)batch * tokens * (C / 4);
-    hipLaunchKernelGGL(embed_kernel, dim3(ew_grid(total)), dim3(NT), 0, ivit_stream(stream), patch, pos_add, cls_row,
-                       Mq, out, batch, tokens, C);
-    IVIT_CHECK_LAUNCH("ivit_embed_assemble_i8");
+    return launch_embed_i8("ivit_embed_assemble_i8", patch, pos_add, cls_row, m, e, out, batch, tokens, C, 8, stream);
+}
+
+IVIT_EXPORT int ivit_embed_assemble_i8_bits(const int8_t* patch, const int16_t* pos_add, const int8_t* cls_row, uint32_t m,
+                                            int32_t e, int8_t* out, int batch, int tokens, int C, int bits, ivit_stream_t stream)
+{
+    return launch_embed_i8("ivit_embed_assemble_i8_bits", patch, pos_add, cls_row, m, e, out, batch, tokens, C, bits, stream);
 }
 
 IVIT_EXPORT int ivit_embed_assemble_i16(const int16_t* patch, const int32_t* pos_add, const int16_t* cls_row, uint32_t m,
@@ -2047,15 +2068,32 @@ IVIT_EXPORT int ivit_requant_i32(const int32_t* z, int64_t rows, int C, const ui
     IVIT_CHECK_LAUNCH("ivit_requant_i32");
 }
 
+namespace {
+int launch_residual_requant_i8(const char* name, const int8_t* a, uint32_t m_a, int32_t e_a, const int8_t* b, uint32_t m_b, int32_t e_b,
+                               int8_t* out, int64_t n, int bits, ivit_stream_t stream)
+{
+    IVIT_REQUIRE(bits == 4 || bits == 8, "%s: bits=%d must be 4 or 8", name, bits);
+    IVIT_REQUIRE(a && b && out && n > 0, "%s: bad operand", name);
+    const double Ma = ivit_dyadic_to_double(m_a, e_a), Mb = ivit_dyadic_to_double(m_b, e_b);
+    IVIT_REQUIRE(Ma < 1048576.0 && Mb < 1048576.0, "%s: multiplier too large", name);
+    if (bits == 8)
+        hipLaunchKernelGGL((residual_requant_kernel<-128, 127>), dim3(ew_grid(n)), dim3(NT), 0, ivit_stream(stream), a, Ma, b, Mb, out, n);
+    else
+        hipLaunchKernelGGL((residual_requant_kernel<-8, 7>), dim3(ew_grid(n)), dim3(NT), 0, ivit_stream(stream), a, Ma, b, Mb, out, n);
+    IVIT_CHECK_LAUNCH(name);
+}
+}  // namespace
+
 IVIT_EXPORT int ivit_residual_requant_i8(const int8_t* a, uint32_t m_a, int32_t e_a, const int8_t* b, uint32_t m_b,
                                          int32_t e_b, int8_t* out, int64_t n, ivit_stream_t stream)
 {
-    IVIT_REQUIRE(a && b && out && n > 0, "ivit_residual_requant_i8: bad operand");
-    const double Ma = ivit_dyadic_to_double(m_a, e_a), Mb = ivit_dyadic_to_double(m_b, e_b);
-    IVIT_REQUIRE(Ma < 1048576.0 && Mb < 1048576.0, "ivit_residual_requant_i8: multiplier too large");
-    hipLaunchKernelGGL(residual_requant_kernel, dim3(ew_grid(n)), dim3(NT), 0, ivit_stream(stream), a, Ma, b, Mb, out,
-                       n);
-    IVIT_CHECK_LAUNCH("ivit_residual_requant_i8");
+    return launch_residual_requant_i8("ivit_residual_requant_i8", a, m_a, e_a, b, m_b, e_b, out, n, 8, stream);
+}
+
+IVIT_EXPORT int ivit_residual_requant_i8_bits(const int8_t* a, uint32_t m_a, int32_t e_a, const int8_t* b, uint32_t m_b,
+                                              int32_t e_b, int8_t* out, int64_t n, int bits, ivit_stream_t stream)
+{
+    return launch_residual_requant_i8("ivit_residual_requant_i8_bits", a, m_a, e_a, b, m_b, e_b, out, n, bits, stream);
 }
 
 IVIT_EXPORT int ivit_bgemm_qk_i8(const int8_t* Q, const int8_t* K, int32_t* S, int batch, int Tq, int Tk, int D,

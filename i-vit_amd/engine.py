@@ -67,15 +67,19 @@ class IntViTEngine(EngineBase):
         # width of the residual stream and of the QuantActs that feed it (vit_quant.py:180-187): 8, or 16 = patch_embed_bw,
         # block_input_bw, attention_out_bw, mlp_out_bw, norm2_in_bw, att_block_out_bw all 16 (softmax_bw, pos_encoding_bw 8): the
         # GEMM operands stay int8, the stream and the projection / fc2 outputs are int16 (the kernels of the Swin engine)
-        if stream_bits not in (8, 16):
-            raise ValueError("stream_bits must be 8 or 16")
-        if self.T > 207 and (family != "ivit" or stream_bits != 8):
+        # stream_bits = 4: the same six QuantActs at 4 bits ('--bitwidth 4').  A 4-bit activation is an int8 byte clamped to [-8, 7]:
+        # the 8-bit engine's dataflow, buffers and layouts, with the `_bits` entries at the six sites
+        if stream_bits not in (4, 8, 16):
+            raise ValueError("stream_bits must be 4, 8 or 16")
+        if self.T > 207 and (family != "ivit" or stream_bits == 16):
             raise ValueError(f"geometry {self.IMG} / {self.P}: {self.T} tokens; the I-BERT softmax and the 16-bit stream take at most "
-                             "207 tokens (more: family 'ivit' with stream_bits = 8)")
+                             "207 tokens (more: family 'ivit' with stream_bits = 8 or 4)")
         self.stream_bits = sb = stream_bits
-        # softmax_bw / pos_encoding_bw (vit_quant.py:181, 184) may be 16 on the 16-bit-stream path ('--bitwidth 16' sets all eight)
-        if softmax_bits not in (8, 16) or pos_bits not in (8, 16) or (sb == 8 and (softmax_bits, pos_bits) != (8, 8)):
-            raise ValueError("softmax_bits / pos_bits: 8, or 16 together with stream_bits = 16")
+        # softmax_bw / pos_encoding_bw (vit_quant.py:181, 184) may be 16 on the 16-bit-stream path ('--bitwidth 16' sets all eight),
+        # and 4 on the 4-bit-stream path
+        other = {8: (8,), 16: (8, 16), 4: (4, 8)}[sb]
+        if softmax_bits not in other or pos_bits not in other:
+            raise ValueError("softmax_bits / pos_bits: 8, or 16 together with stream_bits = 16, or 4 together with stream_bits = 4")
         self.softmax_bits, self.pos_bits = softmax_bits, pos_bits
         self.hd = embed_dim // num_heads
         if self.hd != 64:
@@ -103,7 +107,7 @@ class IntViTEngine(EngineBase):
                     shift = float(np.asarray(source.tensor(prefix + ".shift")).reshape(-1)[0])
                 except KeyError:
                     shift = 0.0
-            return self._ln_spec(source.layernorm(prefix, s_out), s_in, sb, shift, self.int_sqrt)
+            return self._ln_spec(source.layernorm(prefix, s_out), s_in, 16 if sb == 16 else 8, shift, self.int_sqrt)   # payload width
 
         def ranges_of(name):
             if ranges is None or name not in ranges:
@@ -258,11 +262,17 @@ class IntViTEngine(EngineBase):
         else:
             ws.update(ws["_own"])
 
-    def _gemm(self, A, lda, lin, out, ldo, M, st, a_blocks=False, blocks=False, out_blocks=False):
+    def _gemm(self, A, lda, lin, out, ldo, M, st, a_blocks=False, blocks=False, out_blocks=False, bits=8):
+        """GEMM + its QuantAct; bits = 4: a stream site of the 4-bit engine (the patch embedding)"""
         w, lay = self._w(lin, blocks)
-        _lib.call("ivit_gemm_i8_requant_ex", _lib.ptr(A), lda, w, lin["K"], _lib.ptr(lin["b"]),
-                  _lib.ptr(lin["m"]), _lib.ptr(lin["e"]), _lib.ptr(out), ldo, M, lin["N"], lin["K"],
-                  lay | int(a_blocks) | (4 if out_blocks else 0), st)
+        if bits == 8:
+            _lib.call("ivit_gemm_i8_requant_ex", _lib.ptr(A), lda, w, lin["K"], _lib.ptr(lin["b"]),
+                      _lib.ptr(lin["m"]), _lib.ptr(lin["e"]), _lib.ptr(out), ldo, M, lin["N"], lin["K"],
+                      lay | int(a_blocks) | (4 if out_blocks else 0), st)
+        else:
+            _lib.call("ivit_gemm_i8_requant_bits_ex", _lib.ptr(A), lda, w, lin["K"], _lib.ptr(lin["b"]),
+                      _lib.ptr(lin["m"]), _lib.ptr(lin["e"]), _lib.ptr(out), ldo, M, lin["N"], lin["K"],
+                      lay | int(a_blocks) | (4 if out_blocks else 0), bits, st)
 
     def _gemm_res(self, A, lda, lin, res, me4, out, M, st, blocks=False, a_blocks=False, ldr=None):
         """projection / fc2 + its QuantAct + the block's residual QuantAct (in place when out is res).  On the 16-bit stream the
@@ -286,6 +296,11 @@ class IntViTEngine(EngineBase):
             _lib.call("ivit_gemm_i8_requant_residual_ex", _lib.ptr(A), lda, w, lin["K"],
                       _lib.ptr(lin["b"]), _lib.ptr(lin["m"]), _lib.ptr(lin["e"]), _lib.ptr(res), ldr,
                       r[0], r[1], r[2], r[3], _lib.ptr(out), C, M, lin["N"], lin["K"], lay | int(a_blocks), st)
+        elif self.stream_bits == 4:      # attn.qact3 / mlp.qact2 and the block's residual QuantAct, both at 4 bits
+            w, lay = self._w(lin, blocks)
+            _lib.call("ivit_gemm_i8_requant_residual_bits_ex", _lib.ptr(A), lda, w, lin["K"],
+                      _lib.ptr(lin["b"]), _lib.ptr(lin["m"]), _lib.ptr(lin["e"]), _lib.ptr(res), ldr,
+                      r[0], r[1], r[2], r[3], _lib.ptr(out), C, M, lin["N"], lin["K"], lay | int(a_blocks), 4, 4, st)
         else:
             # the weights-in-registers form where it applies, else the 128 x 128-tile kernel (any shape; no block layouts)
             frags = blocks and self.weight_frags and lin["Wf"] is not None
@@ -353,6 +368,8 @@ class IntViTEngine(EngineBase):
     def _forward(self, images: torch.Tensor, taps: dict | None = None, topk=None, cls_tail: bool = False):
         """forward; topk = (k, targets, hits): the classifier launch is the top-k selection (forward_topk).
         cls_tail: the last block through _cls_block (cls_tail_ok engines, no taps).
+        stream_bits = 4: the 8-bit dataflow; the six stream QuantActs clamp to [-8, 7] (the `_bits` entries), attention is the
+        "wide" form with softmax_bits.
         stream_bits = 16: the same dataflow with an int16 residual stream.  The patch GEMM, the embedding assembly and the
         projection / fc2 GEMMs write 16 bits (csrc/swin.hip's kernels), LayerNorm reads int16 rows, attention is the "wide"
         form (softmax_bits); qkv / fc1 / GELU are the int8 kernels unchanged, every operand in row-major order."""
@@ -363,7 +380,7 @@ class IntViTEngine(EngineBase):
         if wide and taps is not None:
             raise NotImplementedError("taps are not recorded on the 16-bit-stream path")
         if cls_tail and (taps is not None or not self.cls_tail_ok):
-            raise ValueError("cls_tail: I-ViT operators, 8-bit stream, at most 207 tokens, no taps")
+            raise ValueError("cls_tail: I-ViT operators, 8-bit stream, at most 207 tokens, no taps (ivit_attention_cls_i8 has no width)")
         C, H, hd, T = self.C, self.H, self.hd, self.T
         M = B * T
         ws = self.ws
@@ -390,11 +407,15 @@ class IntViTEngine(EngineBase):
             x, x2 = ws["x16"], (ws["x16"] if self.fuse_res16 else ws["y16"])
         else:
             self._gemm(ws["a0"], 3 * self.P * self.P, self.patch, ws["pe"], C, B * self.NP, st,
-                       blocks=bool(self.block_operands) and B * self.NP >= 2048 and C >= 128)
+                       blocks=bool(self.block_operands) and B * self.NP >= 2048 and C >= 128, bits=self.stream_bits)
             tap("patch_embed.qact", ws["pe"], (B, self.NP, C))
             x, x2 = ws["x"], ws["x2"]
-        _lib.call("ivit_embed_assemble_i16" if wide else "ivit_embed_assemble_i8", _lib.ptr(ws["pe16" if wide else "pe"]),
-                  _lib.ptr(self.pos_add), _lib.ptr(self.cls_row), self.embed_me[0], self.embed_me[1], _lib.ptr(x), B, T, C, st)
+        if self.stream_bits == 4:
+            _lib.call("ivit_embed_assemble_i8_bits", _lib.ptr(ws["pe"]), _lib.ptr(self.pos_add), _lib.ptr(self.cls_row), self.embed_me[0],
+                      self.embed_me[1], _lib.ptr(x), B, T, C, 4, st)
+        else:
+            _lib.call("ivit_embed_assemble_i16" if wide else "ivit_embed_assemble_i8", _lib.ptr(ws["pe16" if wide else "pe"]),
+                      _lib.ptr(self.pos_add), _lib.ptr(self.cls_row), self.embed_me[0], self.embed_me[1], _lib.ptr(x), B, T, C, st)
         tap("qact1", x, (B, T, C))
         y_cls = None
         for i, blk in enumerate(self.blocks):
@@ -410,7 +431,7 @@ class IntViTEngine(EngineBase):
                       _lib.ptr(q["m"]), _lib.ptr(q["e"]), _lib.ptr(ws["qkv"]), T, H, hd, M, 3 * C, C, qlay | int(a_ln), st)
             tap(p + "attn.qkv_headmajor", ws["qkv"], (3, B, H, T, hd))
             attention(blk["attn"], self.family, ws["qkv"], ws["ao"], B, H, T, hd, st, blocks=a_at,
-                      softmax_bits=self.softmax_bits if wide else None)
+                      softmax_bits=self.softmax_bits if self.stream_bits != 8 else None)
             tap(p + "attn.qact2", ws["ao"], (B, T, C), a_at)
             self._gemm_res(ws["ao"], C, blk["proj"], x, blk["res1"], x2, M, st, blocks=blk_l, a_blocks=a_at)
             tap(p + "qact2", x2, (B, T, C))

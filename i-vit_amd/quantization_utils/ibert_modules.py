@@ -197,7 +197,7 @@ class IBERTIntSoftmax(nn.Module):
         if isinstance(x, lazy.QT):
             # ViT's scores at either width; Swin's biased (and, through one reshape, masked) scores at 8 bits (swin_quant.py:143-156)
             if (not self.act.running_stat and scaling_factor is getattr(x.node, "s_out_qs", None)
-                    and (isinstance(x.node, lazy.Scores) and not x.views and self.output_bit in (8, 16)
+                    and (isinstance(x.node, lazy.Scores) and not x.views and self.output_bit in (4, 8, 16)
                          or self.output_bit == 8 and x.dim() == 4 and (isinstance(x.node, lazy.Biased) and not x.views
                                                                         or isinstance(x.node, lazy.Masked) and len(x.views) == 1))):
                 so = lazy._cache(self, ("s_out", str(x.device)), lambda: lazy.QS.make(f32(2 / 2 ** self.output_bit), x.device))   # :317

@@ -141,11 +141,11 @@ class IVITIntSoftmax(nn.Module):
 
     def forward(self, x, scaling_factor):
         if isinstance(x, lazy.QT):
-            # output_bit = 16 (softmax_bw, vit_quant.py:184): on ViT's scores only (the "wide" attention kernels)
+            # output_bit = 4 or 16 (softmax_bw, vit_quant.py:184): on ViT's scores only (the "wide" attention kernels)
             if (scaling_factor is getattr(x.node, "s_out_qs", None) and x.dim() == 4
                     and (self.output_bit == 8 and (isinstance(x.node, (lazy.Scores, lazy.Biased)) and not x.views
                                                    or isinstance(x.node, lazy.Masked) and len(x.views) == 1)
-                         or self.output_bit == 16 and isinstance(x.node, lazy.Scores) and not x.views)):
+                         or self.output_bit in (4, 16) and isinstance(x.node, lazy.Scores) and not x.views)):
                 s = lazy._cache(self, ("s_out", str(x.device)), lambda: lazy.QS.make(f32(1 / 2 ** (self.output_bit - 1)), x.device))  # :176
                 self.act_scaling_factor = s.as_subclass(torch.Tensor)
                 return lazy.QT.wrap(x.shape, x.device, node=lazy.Probs(x, self)), s

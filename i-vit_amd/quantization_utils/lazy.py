@@ -686,9 +686,9 @@ def _operand(a8, c):
     return a8 if c["K"] == c["Kin"] else torch.nn.functional.pad(a8, (0, c["K"] - c["Kin"]))
 
 
-def gemm_requant(lin, a8, s_in, s_out, device):
+def gemm_requant(lin, a8, s_in, s_out, device, bits=8):
     """a8 [M, K] int8 contiguous -> int8 [M, N]: GEMM + per-channel requantisation to s_out in one kernel; None if outside the
-    kernels' contract"""
+    kernels' contract.  bits = 4: the QuantAct clamps to [-8, 7] (ivit_gemm_i8_requant_bits_ex); the 8-bit launch is as it was"""
     c = linear_consts(lin, s_in, device)
     N, K = c["N"], c["K"]
     if N % 16 != 0:
@@ -700,18 +700,29 @@ def gemm_requant(lin, a8, s_in, s_out, device):
     M = a8.shape[0]
     out = torch.empty(M, N, dtype=torch.int8, device=device)
     frags = c["Wf"] is not None and M >= 2048
-    _lib.call("ivit_gemm_i8_requant_ex", _lib.ptr(a8), K, _lib.ptr(c["Wf"] if frags else c["W"]), K, _lib.ptr(c["b"]),
-              _lib.ptr(me[0]), _lib.ptr(me[1]), _lib.ptr(out), N, M, N, K, 16 if frags else 0, _st())
+    if bits == 8:
+        _lib.call("ivit_gemm_i8_requant_ex", _lib.ptr(a8), K, _lib.ptr(c["Wf"] if frags else c["W"]), K, _lib.ptr(c["b"]),
+                  _lib.ptr(me[0]), _lib.ptr(me[1]), _lib.ptr(out), N, M, N, K, 16 if frags else 0, _st())
+    else:
+        _lib.call("ivit_gemm_i8_requant_bits_ex", _lib.ptr(a8), K, _lib.ptr(c["Wf"] if frags else c["W"]), K, _lib.ptr(c["b"]),
+                  _lib.ptr(me[0]), _lib.ptr(me[1]), _lib.ptr(out), N, M, N, K, 16 if frags else 0, bits, _st())
     return out
 
 
 def resolve(qact, x, pre_sf, identity, identity_sf, s_out, s_out_qs):
-    """The frozen 8-bit QuantAct on a QT: one fused launch -> int8 QT.  None: not a recognised pattern (ordinary path)."""
+    """The frozen 8-bit QuantAct on a QT: one fused launch -> int8 QT.  None: not a recognised pattern (ordinary path).
+    A 4-bit QuantAct (a width knob of vit_quant.py:180-187 at 4: the clamp is [-8, 7], the payload still int8) is carried at the
+    sites the knobs reach -- a linear or the patch convolution, the residual add alone or fused into the GEMM, the cat + position
+    identity of qact1; behind any other producer it takes the ordinary path."""
     device = x.device
     s_in = host_of(pre_sf)
     if s_in is None:
         return None
     node = x.node
+    bits = qact.activation_bit
+    if bits != 8 and not (isinstance(node, (Requant, Cat)) or x._q8 is not None
+                          or (isinstance(node, ModNode) and node.kind in ("linear", "conv"))):
+        return None
     out = None
     fl = act_layout(x.fl, identity.fl if isinstance(identity, QT) else None)
     if isinstance(node, Scores) and identity is not None:
@@ -721,7 +732,7 @@ def resolve(qact, x, pre_sf, identity, identity_sf, s_out, s_out_qs):
             return QT.wrap(x.shape, device, node=Biased(x, pre_sf, identity, identity_sf, s_out, s_out_qs, qact))
         return None
     if isinstance(node, Requant) and x._q8 is None and identity is not None and not x.views:
-        out = node.with_residual(identity, host_of(identity_sf), s_in, s_out, device)
+        out = node.with_residual(identity, host_of(identity_sf), s_in, s_out, device, bits)
         if out is not None:
             STATS["fused"] += 1
             return QT.wrap(out.shape, device, q8=out, scale=s_out_qs, fl=fl)
@@ -733,12 +744,16 @@ def resolve(qact, x, pre_sf, identity, identity_sf, s_out, s_out_qs):
         if i8 is None or s_id is None or i8.shape != x8.shape or s_in.size != 1 or s_id.size != 1:
             return None
         out = torch.empty_like(x8)
-        _lib.call("ivit_residual_requant_i8", _lib.ptr(x8), *dyadic1(s_in, s_out), _lib.ptr(i8), *dyadic1(s_id, s_out),
-                  _lib.ptr(out), x8.numel(), _st())
+        if bits == 8:
+            _lib.call("ivit_residual_requant_i8", _lib.ptr(x8), *dyadic1(s_in, s_out), _lib.ptr(i8), *dyadic1(s_id, s_out),
+                      _lib.ptr(out), x8.numel(), _st())
+        else:
+            _lib.call("ivit_residual_requant_i8_bits", _lib.ptr(x8), *dyadic1(s_in, s_out), _lib.ptr(i8), *dyadic1(s_id, s_out),
+                      _lib.ptr(out), x8.numel(), bits, _st())
         STATS["fused"] += 1
         return QT.wrap(out.shape, device, q8=out, scale=s_out_qs, fl=fl)
     if isinstance(node, Cat):
-        out = _resolve_cat(qact, node, s_in, identity, identity_sf, s_out, device)
+        out = _resolve_cat(qact, node, s_in, identity, identity_sf, s_out, device, bits)
     elif isinstance(node, ModNode) and identity is None:
         if s_in is not host_of(node.out_scale):     # the scale handed in must be the one the pending module returned
             return None
@@ -755,10 +770,10 @@ def resolve(qact, x, pre_sf, identity, identity_sf, s_out, s_out_qs):
                     and linear_consts(node.mod, s_a, device)["Wf"] is not None):
                 # not launched yet: if the next QuantAct adds a residual (Block.qact2 / qact4, vit_quant.py:147,153) the GEMM,
                 # this requantisation and that one are ONE kernel; any other consumer launches the GEMM as it is
-                rq = Requant(node.mod, a8, s_a, s_out, node.shape, s_out_qs)
+                rq = Requant(node.mod, a8, s_a, s_out, node.shape, s_out_qs, bits)
                 if rq.ok:
                     return QT.wrap(x.shape, device, scale=s_out_qs, node=rq, fl=fl)
-            o = gemm_requant(node.mod, a8, s_a, s_out, device) if a8 is not None else None
+            o = gemm_requant(node.mod, a8, s_a, s_out, device, bits) if a8 is not None else None
             if o is not None:
                 sh = node.shape
                 out = o.view(*sh) if node.kind == "linear" else o.view(sh[0], sh[2], sh[3], sh[1]).permute(0, 3, 1, 2)
@@ -775,9 +790,9 @@ def resolve(qact, x, pre_sf, identity, identity_sf, s_out, s_out_qs):
                 if isinstance(base, QT) and not x.views:
                     return QT.wrap(x.shape, device, node=Scores(x, pre_sf, s_out, s_out_qs, qact))
                 if isinstance(base, QT) and isinstance(base.node, Probs) and (
-                        base.node.mod.output_bit == 16 or (type(base.node.mod).__name__ == "IBERTIntSoftmax"
+                        base.node.mod.output_bit in (4, 16) or (type(base.node.mod).__name__ == "IBERTIntSoftmax"
                                                            and isinstance(base.node.x.node, (Biased, Masked)))):
-                    # 16-bit probabilities without a fused kernel (I-BERT's softmax outside 193 .. 207 tokens, multipliers beyond
+                    # 4- or 16-bit probabilities without a fused kernel (I-BERT's softmax outside 193 .. 207 tokens, multipliers beyond
                     # the long-row kernels' bounds), or Swin's I-BERT softmax under a shift mask the window kernel cannot take
                     # (prepare.ibert_window_mask_ok): the attention core runs literally, its float result re-enters the integer
                     # stream here, so the rest of the forward is still carried
@@ -993,24 +1008,24 @@ class Requant16(Node):
 
 
 class Requant(Node):
-    """a linear + its 8-bit QuantAct, not launched yet (see resolve)"""
+    """a linear + its 8-bit (or, bits = 4, its 4-bit) QuantAct, not launched yet (see resolve)"""
 
-    def __init__(self, lin, a8, s_a, s_out, shape, s_out_qs):
-        self.lin, self.a8, self.s_a, self.s_out, self.shape, self.s_out_qs = lin, a8, s_a, s_out, shape, s_out_qs
+    def __init__(self, lin, a8, s_a, s_out, shape, s_out_qs, bits=8):
+        self.lin, self.a8, self.s_a, self.s_out, self.shape, self.s_out_qs, self.bits = lin, a8, s_a, s_out, shape, s_out_qs, bits
         self.ok = _gemm_me(lin, s_a, s_out, a8.device) is not None
         self.out = None
 
     def force(self):
         if self.out is None:
             STATS["fused"] += 1
-            self.out = gemm_requant(self.lin, self.a8, self.s_a, self.s_out, self.a8.device).view(*self.shape)
+            self.out = gemm_requant(self.lin, self.a8, self.s_a, self.s_out, self.a8.device, self.bits).view(*self.shape)
         return self.out
 
     def head_major(self, q, kT, v, head_dim=64, max_tokens=1025, frags=True):
         """q, k^T and v of vit_quant.py:66-70 as recorded views of THIS linear's output [B, N, 3 H hd]: the GEMM writes them head-major
         ([3, B, H, N, hd], what the attention kernel reads) itself -> that tensor; None if the views are anything else.
         frags = False (Swin's windows, head_dim 32): row-major weights where the fragment copy does not apply"""
-        if self.out is not None or len(self.shape) != 3 or any(t._q8 is not None or t.node is not self for t in (q, kT, v)):
+        if self.out is not None or self.bits != 8 or len(self.shape) != 3 or any(t._q8 is not None or t.node is not self for t in (q, kT, v)):
             return None
         B, N, C3 = self.shape
         base = torch.empty(self.shape, dtype=torch.int8, device="meta")
@@ -1037,8 +1052,9 @@ class Requant(Node):
     def to_float(self):
         return self.force().to(torch.float32) * self.s_out_qs.as_subclass(torch.Tensor).reshape(-1)[0]
 
-    def with_residual(self, identity, s_id, s_in, s_out2, device):
-        """out = clamp8(RNE(RNE(acc * M) * m1 / 2^e1) + RNE(identity * m2 / 2^e2)): ivit_gemm_i8_requant_residual_ex"""
+    def with_residual(self, identity, s_id, s_in, s_out2, device, bits_out=8):
+        """out = clamp8(RNE(RNE(acc * M) * m1 / 2^e1) + RNE(identity * m2 / 2^e2)): ivit_gemm_i8_requant_residual_ex; with either of
+        the two QuantActs at 4 bits ivit_gemm_i8_requant_residual_bits_ex"""
         i8 = q8_contig(identity)
         c = linear_consts(self.lin, self.s_a, device)
         N, K = c["N"], c["K"]
@@ -1048,15 +1064,20 @@ class Requant(Node):
         me = _gemm_me(self.lin, self.s_a, self.s_out, device)
         M = self.a8.shape[0]
         out = torch.empty(M, N, dtype=torch.int8, device=device)
-        _lib.call("ivit_gemm_i8_requant_residual_ex", _lib.ptr(self.a8), K, _lib.ptr(c["Wf"]), K, _lib.ptr(c["b"]), _lib.ptr(me[0]),
-                  _lib.ptr(me[1]), _lib.ptr(i8), N, *dyadic1(s_in, s_out2), *dyadic1(s_id, s_out2), _lib.ptr(out), N, M, N, K, 16, _st())
+        if self.bits == 8 and bits_out == 8:
+            _lib.call("ivit_gemm_i8_requant_residual_ex", _lib.ptr(self.a8), K, _lib.ptr(c["Wf"]), K, _lib.ptr(c["b"]), _lib.ptr(me[0]),
+                      _lib.ptr(me[1]), _lib.ptr(i8), N, *dyadic1(s_in, s_out2), *dyadic1(s_id, s_out2), _lib.ptr(out), N, M, N, K, 16, _st())
+        else:
+            _lib.call("ivit_gemm_i8_requant_residual_bits_ex", _lib.ptr(self.a8), K, _lib.ptr(c["Wf"]), K, _lib.ptr(c["b"]), _lib.ptr(me[0]),
+                      _lib.ptr(me[1]), _lib.ptr(i8), N, *dyadic1(s_in, s_out2), *dyadic1(s_id, s_out2), _lib.ptr(out), N, M, N, K, 16,
+                      self.bits, bits_out, _st())
         return out.view(*self.shape)
 
     def with_residual16(self, i16, s_in, mes, device):
         """mlp.fc2 + mlp.qact2 + the 16-bit residual QuantAct in one kernel (swin_engine.py does the same): int16 out, or None"""
         c = linear_consts(self.lin, self.s_a, device)
         N, K = c["N"], c["K"]
-        if s_in[0] != f32(self.s_out) or tuple(i16.shape) != tuple(self.shape) or N % 8:
+        if self.bits != 8 or s_in[0] != f32(self.s_out) or tuple(i16.shape) != tuple(self.shape) or N % 8:
             return None
         me = _gemm_me(self.lin, self.s_a, self.s_out, device)
         a8 = _operand(self.a8, c)
@@ -1177,10 +1198,11 @@ def _resolve_attention(node, s_pv, s_out, device):
     if s_S.size != 1 or s_pv.size != 1:
         return None
     sm = P.node.mod
-    if sm.output_bit not in (8, 16):
+    if sm.output_bit not in (4, 8, 16):
         return None
-    # softmax_bw = 16 (vit_quant.py:184): the "wide" entries, whose probabilities reach 2^15 at scale 2^-15 (s_pv is 2^-15 * s_v)
-    softmax_bits = 16 if sm.output_bit == 16 else None
+    # softmax_bw = 16 (vit_quant.py:184): the "wide" entries, whose probabilities reach 2^15 at scale 2^-15 (s_pv is 2^-15 * s_v);
+    # softmax_bw = 4: the same entries, probabilities below 8 (I-BERT: up to 8) at scale 2^-3
+    softmax_bits = sm.output_bit if sm.output_bit in (4, 16) else None
     family, act, key = "ivit", None, ("attn",)
     if type(sm).__name__ == "IBERTIntSoftmax":
         # IBERTIntSoftmax (ibert_modules.py:237-319): exp_int after its internal 16-bit QuantAct as a (row max, q) table, row sum in
@@ -1199,7 +1221,8 @@ def _resolve_attention(node, s_pv, s_out, device):
             act.act_scaling_factor = torch.full((1,), d["act_sf"], dtype=torch.float32, device=device)
         return d
     a = _cache(sc.qact, key + (_key(s_S, np.asarray(s_at), s_pv, np.asarray(s_out)), str(device)), build)
-    if T > 207 and not long_multipliers_ok(a):
+    # (4-bit probabilities: a row of many keys easily rounds to all zeros, and a calibration on such rows leaves qact2 no range)
+    if (T > 207 or softmax_bits == 4) and not long_multipliers_ok(a):
         return None
     out = torch.empty(B * T, H * hd, dtype=torch.int8, device=device)
     attention(a, family, hm, out, B, H, T, hd, _st(), softmax_bits=softmax_bits)
@@ -1337,7 +1360,7 @@ def _resolve_window_attention(P, top, v, s_pv, s_out, device):
     return out.view(B_, N, nH, hd).permute(0, 2, 1, 3)
 
 
-def _resolve_cat(qact, node, s_in, identity, identity_sf, s_out, device):
+def _resolve_cat(qact, node, s_in, identity, identity_sf, s_out, device, bits=8):
     """qact1(cat(cls_token, patches), s, pos, s_pos) (vit_quant.py:293-297): the raw float rows go through round(x / s), the
     int8 part is widened, then the two-operand requantisation"""
     s_id = host_of(identity_sf)
@@ -1369,7 +1392,7 @@ def _resolve_cat(qact, node, s_in, identity, identity_sf, s_out, device):
         n2 = 1
     q = torch.empty_like(z)
     _lib.call("ivit_requant_i32", _lib.ptr(z), z.numel() // C, C, _lib.ptr(md), _lib.ptr(ed), 1, _lib.ptr(z2), _lib.ptr(m2d),
-              _lib.ptr(e2d), n2, 8, _lib.ptr(q), _st())
+              _lib.ptr(e2d), n2, bits, _lib.ptr(q), _st())
     return q.to(torch.int8)
 
 

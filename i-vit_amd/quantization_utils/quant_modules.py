@@ -354,7 +354,9 @@ class QuantAct(nn.Module):
         return c[1], c[2], c[3]
 
     def _fast(self, x, pre_sf, identity, identity_sf):
-        """frozen 8-bit QuantAct of an int8-carrying forward (lazy.py): int8 out, one fused launch, nothing read back"""
+        """frozen 8-bit (or 4-bit: the same int8 payload, clamped to [-8, 7]) QuantAct of an int8-carrying forward (lazy.py): int8
+        out, one fused launch, nothing read back.  (A 4-bit QuantAct on a float tensor -- qact_pos, once per parameter version -- is
+        two: ivit_quantize_input_f32_i32 and the narrowing copy.)"""
         if pre_sf is None:
             if isinstance(x, lazy.QT) or identity is not None or not x.is_cuda:
                 return None
@@ -374,8 +376,20 @@ class QuantAct(nn.Module):
                 self.act_scaling_factor = plain
                 return lazy.QT.wrap(q16.shape, x.device, q16=q16, scale=qs, origin=(id(x), x._version, float(s_out))), qs
             xin = x.detach().contiguous().float()
-            q8 = torch.empty(xin.shape, dtype=torch.int8, device=x.device)
-            _lib.call("ivit_quantize_input_f32_i8", _lib.ptr(xin), _lib.ptr(q8), xin.numel(), float(f32(1.0) / s_out), _st())
+            if self.activation_bit == 4:
+                # clamp(round(x / s)) to [-8, 7] in an int8 payload; on a parameter (qact_pos with pos_encoding_bw = 4) quantised once
+                # per parameter version and range
+                def build4():
+                    q32 = torch.empty(xin.shape, dtype=torch.int32, device=x.device)
+                    _lib.call("ivit_quantize_input_f32_i32", _lib.ptr(xin), _lib.ptr(q32), xin.numel(), float(f32(1.0) / s_out), 4, _st())
+                    return q32.to(torch.int8)
+                if isinstance(x, nn.Parameter):
+                    q8 = lazy._cache(self, ("param4", id(x), x._version, float(s_out), str(x.device)), build4)
+                else:
+                    q8 = build4()
+            else:
+                q8 = torch.empty(xin.shape, dtype=torch.int8, device=x.device)
+                _lib.call("ivit_quantize_input_f32_i8", _lib.ptr(xin), _lib.ptr(q8), xin.numel(), float(f32(1.0) / s_out), _st())
             self.act_scaling_factor = plain
             # a parameter (WindowAttention's relative position bias table): what it is and what is done to it since stays known,
             # so that the QuantAct it becomes the identity of can cache its integers
@@ -396,7 +410,7 @@ class QuantAct(nn.Module):
 
     def forward(self, x, pre_act_scaling_factor=None, identity=None, identity_scaling_factor=None,
                 specified_min=None, specified_max=None):
-        if (lazy.active() and not self.running_stat and self.activation_bit in (8, 16) and specified_min is None
+        if (lazy.active() and not self.running_stat and self.activation_bit in (4, 8, 16) and specified_min is None
                 and specified_max is None):
             r = self._fast(x, pre_act_scaling_factor, identity, identity_scaling_factor)
             if r is not None:

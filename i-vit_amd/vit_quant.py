@@ -215,6 +215,12 @@ class VisionTransformer(EngineDispatch, nn.Module):
                 if self._width_mismatch({**w16, "qact_pos": pos_bits}) is None and sm_bits in (8, 16):
                     bad, self._engine_widths = None, (16, sm_bits, pos_bits)
         if bad:
+            # ... or the same six QuantActs at 4 ('--bitwidth 4'), softmax_bw and pos_encoding_bw 4 or 8: engine stream_bits = 4
+            w4 = {k: (4 if v == 16 and k not in inner else v) for k, v in w16.items()}
+            for pos_bits in (8, 4):
+                if self._width_mismatch({**w4, "qact_pos": pos_bits}) is None and sm_bits in (4, 8):
+                    bad, self._engine_widths = None, (4, sm_bits, pos_bits)
+        if bad:
             return bad
         if (sm_bits != 8 and self._engine_widths[0] == 8) or getattr(m, "output_bit", 8) != 8:
             return "Shiftmax / ShiftGELU output width != 8"
@@ -222,7 +228,7 @@ class VisionTransformer(EngineDispatch, nn.Module):
         # 8-bit stream has the long-row kernel (208 .. 1025 tokens)
         if self.op_types[0] == "ibert" and not 193 <= tokens <= 207:
             return f"geometry {self.geometry}: {tokens} tokens (fused I-BERT attention: 193 .. 207 tokens)"
-        if tokens > 207 and self._engine_widths[0] != 8:
+        if tokens > 207 and self._engine_widths[0] == 16:
             return f"geometry {self.geometry}: {tokens} tokens (16-bit residual stream: at most 207 tokens)"
         return None
 

@@ -129,6 +129,14 @@ int ivit_gemm_i8_requant_ex(const int8_t* A, int64_t lda, const int8_t* W, int64
                             const uint32_t* m, const int32_t* e, int8_t* out, int64_t ldo,
                             int M, int N, int K, int layouts, ivit_stream_t stream);
 
+/* ivit_gemm_i8_requant_ex with the width of the QuantAct as a parameter (the width knobs of vit_quant.py:180-187):
+ *   out[t][n] = clampB(RNE(acc * m[n] / 2^e[n])),  clamp4 = [-8, 7] (quant_utils.py:209,247-249), the value in an int8 byte.
+ * bits = 4 or 8; any other value is IVIT_ERR_INVALID ("bits=.. must be 4 or 8") ahead of everything else, nothing is launched.
+ * Every shape, layout and kernel form of ivit_gemm_i8_requant_ex; at bits = 8 the same kernels, byte for byte. */
+int ivit_gemm_i8_requant_bits_ex(const int8_t* A, int64_t lda, const int8_t* W, int64_t ldw, const int32_t* bias,
+                                 const uint32_t* m, const int32_t* e, int8_t* out, int64_t ldo,
+                                 int M, int N, int K, int layouts, int bits, ivit_stream_t stream);
+
 /* ivit_gemm_i8_requant_ex followed by an elementwise int8 -> int8 map on every output: out = lut[k + 128], lut int8[256] -- an
  * operator behind the QuantAct that depends on the value alone (I-BERT GELU + mlp.qact1: ivit_ibert_gelu_build_lut row 0),
  * applied in the epilogue instead of by a kernel of its own.  Needs IVIT_W_FRAGS (the weights-in-registers kernel). */
@@ -152,6 +160,18 @@ int ivit_gemm_i8_requant_residual_ex(const int8_t* A, int64_t lda, const int8_t*
                                      const int8_t* res, int64_t ldr, uint32_t m_main, int32_t e_main,
                                      uint32_t m_res, int32_t e_res, int8_t* out, int64_t ldo,
                                      int M, int N, int K, int layouts, ivit_stream_t stream);
+
+/* the same with the widths of its two QuantActs as parameters (attention_out_bw / mlp_out_bw and norm2_in_bw / att_block_out_bw
+ * are separate knobs, vit_quant.py:180-187):
+ *   k = clamp_mid(RNE(acc * m[n] / 2^e[n]))
+ *   out = clamp_out(RNE(k * m_main / 2^e_main) + RNE(res[t][n] * m_res / 2^e_res))
+ * bits_mid, bits_out = 4 or 8 independently (clamp4 = [-8, 7]); any other value is IVIT_ERR_INVALID ahead of everything else,
+ * nothing is launched.  `out` may be `res` itself.  At (8, 8) the kernels of ivit_gemm_i8_requant_residual_ex, byte for byte. */
+int ivit_gemm_i8_requant_residual_bits_ex(const int8_t* A, int64_t lda, const int8_t* W, int64_t ldw,
+                                          const int32_t* bias, const uint32_t* m, const int32_t* e,
+                                          const int8_t* res, int64_t ldr, uint32_t m_main, int32_t e_main,
+                                          uint32_t m_res, int32_t e_res, int8_t* out, int64_t ldo,
+                                          int M, int N, int K, int layouts, int bits_mid, int bits_out, ivit_stream_t stream);
 
 /* Swin form of the above: the residual stream is 16 bits wide (swin_quant.py:299, mlp.fc2 + shortcut):
  *   k = clamp8(RNE(acc * m[n] / 2^e[n]))                       (mlp.qact2)
@@ -248,9 +268,10 @@ int ivit_attention_fused_i8_compat_band(const int8_t* qkv, int8_t* out, int batc
                                         uint32_t m_s, int32_t e_s, float s_attn, uint32_t m_o, int32_t e_o,
                                         const uint32_t* exp2d, const uint32_t* band, int band_w, int out_blocks,
                                         ivit_stream_t stream);
-/* the same with the softmax output width as a parameter (softmax_bw, vit_quant.py:184): softmax_bits = 8 or 16.  16:
+/* the same with the softmax output width as a parameter (softmax_bw, vit_quant.py:184): softmax_bits = 4, 8 or 16.  16:
  * p = floor(fl32(e * factor) / 2^16) <= 2^15 at scale 2^-15 (ivit_modules.py:175-176), carried into P.V as three 7-bit planes;
- * (m_o, e_o) then is the requantiser of 2^-15 * s_v. */
+ * (m_o, e_o) then is the requantiser of 2^-15 * s_v.  4: p = floor(fl32(e * factor) / 2^28) < 8 at scale 2^-3, the 8-bit code
+ * path with another power-of-two scale; (m_o, e_o) is the requantiser of 2^-3 * s_v. */
 int ivit_attention_fused_i8_wide(const int8_t* qkv, int8_t* out, int batch, int heads, int tokens, int head_dim, uint32_t m_s,
                                  int32_t e_s, float s_attn, uint32_t m_o, int32_t e_o, const uint32_t* exp2d,
                                  const uint32_t* band, int band_w, int softmax_bits, int out_blocks, ivit_stream_t stream);
@@ -269,13 +290,14 @@ int ivit_attention_fused_i8_long(const int8_t* qkv, int8_t* out, int batch, int 
 
 /* Long rows with the softmax output width as a parameter: ivit_attention_fused_i8_long's arguments, layouts, tables and
  * preconditions (208 <= tokens <= 1025, head_dim 64, x0 in [-4096, -1], the same multiplier bounds, all three Shiftmax regimes,
- * both output layouts) plus softmax_bits = 8 or 16, as ivit_attention_fused_i8_wide has it for up to 208 keys.
+ * both output layouts) plus softmax_bits = 4, 8 or 16, as ivit_attention_fused_i8_wide has it for up to 208 keys.
  *   16: p = floor(fl32(e * factor) / 2^16) <= 2^15 at scale 2^-15 (ivit_modules.py:175-176) on the long kernel's row organisation
  *       (packed scores, exact 64-bit row sum, the clamp at 2^31), carried into P.V as three 7-bit planes; (m_o, e_o) is the
  *       requantiser of 2^-15 * s_v, applied to O = sum p * v (|O| < 2^29 for 1025 keys) in the reference's two steps: the
  *       float64 product rounded at 53 bits, then the rounding to an integer (quant_utils.py:229-230).
  *   8:  exactly ivit_attention_fused_i8_long.
- * Errors: any other softmax_bits is IVIT_ERR_INVALID ("softmax_bits must be 8 or 16") ahead of everything else; then as
+ *   4:  p = floor(fl32(e * factor) / 2^28) < 8 at scale 2^-3: the 8-bit kernels with the factor scaled by 2^-4 (exact).
+ * Errors: any other softmax_bits is IVIT_ERR_INVALID ("softmax_bits must be 4, 8 or 16") ahead of everything else; then as
  * ivit_attention_fused_i8_long: IVIT_ERR_UNSUPPORTED ("unsupported geometry") outside the token range or for another
  * head_dim, IVIT_ERR_INVALID ("NULL operand", ...) otherwise. */
 int ivit_attention_fused_i8_wide_long(const int8_t* qkv, int8_t* out, int batch, int heads, int tokens, int head_dim,
@@ -396,6 +418,10 @@ int ivit_requant_i32(const int32_t* z, int64_t rows, int C, const uint32_t* m, c
 /* int8 two-operand form (Block.qact2 / qact4 as a stand-alone op) */
 int ivit_residual_requant_i8(const int8_t* a, uint32_t m_a, int32_t e_a, const int8_t* b, uint32_t m_b,
                              int32_t e_b, int8_t* out, int64_t n, ivit_stream_t stream);
+/* the same with the output width as a parameter: out = clampB(RNE(a * m_a / 2^e_a) + RNE(b * m_b / 2^e_b)), bits = 4 ([-8, 7]) or 8;
+ * any other value is IVIT_ERR_INVALID and nothing is launched.  At 8 exactly ivit_residual_requant_i8. */
+int ivit_residual_requant_i8_bits(const int8_t* a, uint32_t m_a, int32_t e_a, const int8_t* b, uint32_t m_b,
+                                  int32_t e_b, int8_t* out, int64_t n, int bits, ivit_stream_t stream);
 
 /* ---- cls token + position embedding (vit_quant.py:290-296) -------------------------------------
  * patch [B*(T-1), C] int8 (PatchEmbed output); out [B*T, C] int8:
@@ -404,6 +430,11 @@ int ivit_residual_requant_i8(const int8_t* a, uint32_t m_a, int32_t e_a, const i
  * pos_add [T, C] int16 = RNE(qact_pos(pos_embed) * m_pos / 2^e_pos) prepared by the caller. */
 int ivit_embed_assemble_i8(const int8_t* patch, const int16_t* pos_add, const int8_t* cls_row, uint32_t m,
                            int32_t e, int8_t* out, int batch, int tokens, int C, ivit_stream_t stream);
+/* the same with the width of qact1 (block_input_bw) as a parameter: out[b][1+p][c] = clampB(RNE(patch*m/2^e) + pos_add[1+p][c]),
+ * bits = 4 ([-8, 7]) or 8; any other value is IVIT_ERR_INVALID and nothing is launched.  The caller prepares cls_row (copied as it
+ * is) and pos_add at the widths of their own QuantActs.  At 8 exactly ivit_embed_assemble_i8. */
+int ivit_embed_assemble_i8_bits(const int8_t* patch, const int16_t* pos_add, const int8_t* cls_row, uint32_t m,
+                                int32_t e, int8_t* out, int batch, int tokens, int C, int bits, ivit_stream_t stream);
 
 /* the same for a 16-bit patch embedding and block input (patch_embed_bw = block_input_bw = 16, vit_quant.py:180-187):
  * out16 = clamp16(RNE(patch16 * m / 2^e) + pos_add[tok][c]) for tok >= 1, out16[b][0] = cls_row; pos_add int32 [tokens, C]. */
@@ -713,7 +744,8 @@ int ivit_ibert_softmax_build_table(float s, float x0_int, float b_int, float c_i
 int ivit_attention_fused_i8_ibert(const int8_t* qkv, int8_t* out, int batch, int heads, int tokens, int head_dim, uint32_t m_s,
                                   int32_t e_s, uint32_t m_o, int32_t e_o, const float* table, const float* band, int band_w,
                                   int out_blocks, ivit_stream_t stream);
-/* softmax_bits = 16: p = floor(fl32(e * factor) / 2^17) <= 2^15 at scale 2 / 2^16 (ibert_modules.py:314-317) */
+/* softmax_bits = 16: p = floor(fl32(e * factor) / 2^17) <= 2^15 at scale 2 / 2^16 (ibert_modules.py:314-317);
+ * softmax_bits = 4: p = floor(fl32(e * factor) / 2^29) in [0, 8] at scale 2 / 2^4, one byte plane (the 8 of a one-hot row included) */
 int ivit_attention_fused_i8_ibert_wide(const int8_t* qkv, int8_t* out, int batch, int heads, int tokens, int head_dim, uint32_t m_s,
                                        int32_t e_s, uint32_t m_o, int32_t e_o, const float* table, const float* band, int band_w,
                                        int softmax_bits, int out_blocks, ivit_stream_t stream);
