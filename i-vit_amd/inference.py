@@ -129,9 +129,10 @@ def save_checkpoint(model, path, model_config: Optional[dict] = None, **extra):
     torch.save(d, path)
 
 
-def _forward_transformed(model, transform, packed, lo, hi, device):
+def _forward_transformed(model, transform, packed, lo, hi, device, graph=False):
     """logits of images [lo, hi) of a transforms.PackedImages batch: the device resize + crop, then the fused engine on the uint8
-    crops (its input table set to the transform's Normalize) or, for any other model, the float32 tensor ToTensor + Normalize give"""
+    crops (its input table set to the transform's Normalize) or, for any other model, the float32 tensor ToTensor + Normalize give
+    (`graph`: through model.forward_graph)"""
     u8 = transform(packed, lo, hi, device=device)
     takes = getattr(model, "takes_engine", None)
     if takes is not None and takes(u8):
@@ -141,11 +142,21 @@ def _forward_transformed(model, transform, packed, lo, hi, device):
             eng.set_input_normalisation(*norm)
         _, logits_f32, _ = eng(u8)
         return logits_f32.clone()
-    return model(transform.to_float(u8))
+    return model.forward_graph(transform.to_float(u8)) if graph else model(transform.to_float(u8))
 
 
-def evaluate_dataset(model, data_loader, device, *, print_batch_stats: bool = True, transform=None):
+def _check_graph_status(model, graph):
+    """after a graph=True loop: the checks the captured forwards made on the device, read once (graph.ModuleGraph.graph_status)"""
+    if graph:
+        model.graph_status()
+
+
+def evaluate_dataset(model, data_loader, device, *, print_batch_stats: bool = True, transform=None, graph: bool = False):
     """inference.py:231-267 -> (top-1, top-3, top-5) accuracy in percent over (images, targets) batches.
+
+    graph: batches go through `model.forward_graph` (graph.ModuleGraph: one captured graph per batch size, so a ragged last batch
+    gets its own) instead of `model(imgs)`, and `model.graph_status()` is checked once after the loop.  With a `transform` the
+    fused-engine branch is as without it; a model the engine declines replays its module path on the transform's float tensor.
 
     transform: None (the loader yields image tensors, as the reference's does), or a transforms.EvalTransform -- the loader then
     yields (transforms.PackedImages, targets) and the reference's Resize -> CenterCrop -> ToTensor -> Normalize runs on the device."""
@@ -158,9 +169,9 @@ def evaluate_dataset(model, data_loader, device, *, print_batch_stats: bool = Tr
             t0 = time.perf_counter()
             if transform is None:
                 imgs, targets = imgs.to(device), targets.to(device)
-                logits = model(imgs)
+                logits = model.forward_graph(imgs) if graph else model(imgs)
             else:
-                logits = _forward_transformed(model, transform, imgs, 0, imgs.size(0), device)
+                logits = _forward_transformed(model, transform, imgs, 0, imgs.size(0), device, graph)
                 targets = targets.to(device)
             pred5 = logits.topk(5, dim=1).indices
             hit = pred5 == targets.reshape(-1, 1)
@@ -169,6 +180,7 @@ def evaluate_dataset(model, data_loader, device, *, print_batch_stats: bool = Tr
             correct5 += int(hit.any(dim=1).sum())
             tot += imgs.size(0)
             batch_times.append(time.perf_counter() - t0)
+    _check_graph_status(model, graph)
     total_time = time.perf_counter() - start_total
     if print_batch_stats and batch_times:
         print(f"Finished evaluation: total={total_time:.1f}s | avg/batch={sum(batch_times) / len(batch_times) * 1000:.1f} ms | "
@@ -178,7 +190,8 @@ def evaluate_dataset(model, data_loader, device, *, print_batch_stats: bool = Tr
     return 100 * correct1 / tot, 100 * correct3 / tot, 100 * correct5 / tot
 
 
-def evaluate_dataset_parallel(model, data_loader, device, *, scorer=None, print_batch_stats: bool = True, transform=None):
+def evaluate_dataset_parallel(model, data_loader, device, *, scorer=None, print_batch_stats: bool = True, transform=None,
+                              graph: bool = False):
     """evaluate_dataset data-parallel over the ranks of the default process group (world 1 without one) -> the same
     (top-1, top-3, top-5) percentages on every rank.
 
@@ -192,7 +205,8 @@ def evaluate_dataset_parallel(model, data_loader, device, *, scorer=None, print_
     logits (value descending, equal logits by ascending class -- where evaluate_dataset's torch.topk leaves the order of
     tied logits unspecified).
 
-    transform: as for evaluate_dataset; a rank transforms only its shard_bounds slice of each packed batch."""
+    transform: as for evaluate_dataset; a rank transforms only its shard_bounds slice of each packed batch.
+    graph: as for evaluate_dataset, on the rank's slice (the scorer reads the graph's output buffer before the next replay)."""
     if dist.is_available() and dist.is_initialized():
         world, rank = dist.get_world_size(), dist.get_rank()
     else:
@@ -210,11 +224,12 @@ def evaluate_dataset_parallel(model, data_loader, device, *, scorer=None, print_
             if transform is None:
                 x = imgs[lo:hi].to(device)
                 t = targets[lo:hi].to(device=device, dtype=torch.int32)
-                scorer(model(x), t, hits, 5)
+                scorer(model.forward_graph(x) if graph else model(x), t, hits, 5)
             else:
                 t = targets[lo:hi].to(device=device, dtype=torch.int32)
-                scorer(_forward_transformed(model, transform, imgs, lo, hi, device), t, hits, 5)
+                scorer(_forward_transformed(model, transform, imgs, lo, hi, device, graph), t, hits, 5)
             local += hi - lo
+    _check_graph_status(model, graph)
     hits, tot = allreduce_hits(hits, local)
     total_time = time.perf_counter() - start_total
     if print_batch_stats and rank == 0 and tot:

@@ -123,12 +123,13 @@ class IBERTIntLayerNorm(nn.Module):
         # the literal kernel: x / scaling_factor, float32 mean and variance sums in torch's reduction order, ... (:126-153) for
         # any input scale (csrc/ibert.hip, second half)
         out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+        factor = lazy.taped("IBERTIntLayerNorm shift", lambda: float(2.0 ** float(self.shift)))
         if self.use_int_sqrt:
             _lib.call("ivit_ibert_layernorm_f32_f32_ex", _lib.ptr(xin), C, xin.numel() // C, C, _lib.ptr(s_in), s_in.numel(),
-                      _lib.ptr(bias_int), _lib.ptr(s_out), float(2.0 ** float(self.shift)), _lib.ptr(out), C, IBERT_LN_INT_SQRT, _st())
+                      _lib.ptr(bias_int), _lib.ptr(s_out), factor, _lib.ptr(out), C, IBERT_LN_INT_SQRT, _st())
             return out, s_out
         _lib.call("ivit_ibert_layernorm_f32_f32", _lib.ptr(xin), C, xin.numel() // C, C, _lib.ptr(s_in), s_in.numel(),
-                  _lib.ptr(bias_int), _lib.ptr(s_out), float(2.0 ** float(self.shift)), _lib.ptr(out), C, _st())
+                  _lib.ptr(bias_int), _lib.ptr(s_out), factor, _lib.ptr(out), C, _st())
         return out, s_out
 
 
@@ -164,7 +165,7 @@ class IBERTIntGELU(nn.Module):
         return self._slow(x, scaling_factor)
 
     def _slow(self, x, scaling_factor=None):
-        s = float(scaling_factor.reshape(-1)[0])
+        s = lazy.taped("IBERTIntGELU input scale", lambda: float(scaling_factor.reshape(-1)[0]))
         b_int, c_int, shift_int, s_out = self.constants(s)
         xin = x.contiguous().float()
         out = torch.empty(xin.shape, dtype=torch.float32, device=x.device)
@@ -206,7 +207,7 @@ class IBERTIntSoftmax(nn.Module):
         return self._slow(x, scaling_factor)
 
     def _slow(self, x, scaling_factor):
-        s = f32(float(scaling_factor.reshape(-1)[0]))
+        s = f32(lazy.taped("IBERTIntSoftmax input scale", lambda: float(scaling_factor.reshape(-1)[0])))
         L = x.shape[-1]
         x0_int, b_int, c_int, exp_sf = softmax_constants(s, -1.0, 1.0)[:4]         # :277-294 (the range-dependent ones below)
         xin = x.contiguous().float()                                               # literal kernel: x / s itself (:303)
@@ -218,11 +219,12 @@ class IBERTIntSoftmax(nn.Module):
             _lib.call("ivit_ibert_softmax_f32_f32", _lib.ptr(xin), L, rows, L, float(s), float(x0_int), float(b_int), float(c_int),
                       float(exp_sf), 1.0, 1 << 30, 30, self.output_bit, None, L, _lib.ptr(ex), st)
             self.act._observe(ex)
-        lo, hi = float(self.act.x_min.reshape(-1)[0]), float(self.act.x_max.reshape(-1)[0])
+        lo, hi = lazy.taped("IBERTIntSoftmax range", lambda: (float(self.act.x_min.reshape(-1)[0]), float(self.act.x_max.reshape(-1)[0])))
         act_sf, m, e = softmax_constants(s, lo, hi)[4:]                                 # quant_utils.py:52-70, 16 bit
         self.act.act_scaling_factor = torch.full((1,), float(act_sf), dtype=torch.float32, device=x.device)
         out = torch.empty(xin.shape, dtype=torch.float32, device=x.device)
         _lib.call("ivit_ibert_softmax_f32_f32", _lib.ptr(xin), L, rows, L, float(s), float(x0_int), float(b_int), float(c_int),
                   float(exp_sf), float(act_sf), m, e, self.output_bit, _lib.ptr(out), L, None, st)
-        so = torch.tensor([2 / 2 ** self.output_bit], dtype=torch.float32, device=x.device)   # :317
+        so = lazy.taped("IBERTIntSoftmax output scale",
+                        lambda: torch.tensor([2 / 2 ** self.output_bit], dtype=torch.float32, device=x.device))   # :317
         return out, so

@@ -115,10 +115,10 @@ class IVITIntGELU(nn.Module):
         L = x.shape[-1]
         k8 = narrow_i8(to_int32(x, scaling_factor, trunc=True), "IVITIntGELU input")   # :106-107
         out = torch.empty(x.shape, dtype=torch.int32, device=x.device)
-        _lib.call("ivit_shiftgelu_i8_i32", _lib.ptr(k8), L, k8.numel() // L, L, float(scaling_factor.reshape(-1)[0]),
-                  _lib.ptr(out), L, _st())
-        s = (scaling_factor.reshape(-1)[:1].float() * torch.tensor([1 / 2 ** (self.output_bit - 1)],
-                                                                  device=x.device)).float()  # :121,124
+        _lib.call("ivit_shiftgelu_i8_i32", _lib.ptr(k8), L, k8.numel() // L, L,
+                  lazy.taped("ShiftGELU input scale", lambda: float(scaling_factor.reshape(-1)[0])), _lib.ptr(out), L, _st())
+        step = lazy.taped("ShiftGELU output step", lambda: torch.tensor([1 / 2 ** (self.output_bit - 1)], device=x.device))
+        s = (scaling_factor.reshape(-1)[:1].float() * step).float()  # :121,124
         self.act_scaling_factor = s
         return to_float(out, s), s
 
@@ -157,14 +157,14 @@ class IVITIntSoftmax(nn.Module):
         # the literal kernel: the reference discards its .to(int32) (:166) and runs the float32 sequence on x / s itself
         # (Swin's masked scores, swin_quant.py:151-156, included), csrc/literal.hip
         xin = x.contiguous().float()
+        s_in = lazy.taped("Shiftmax input scale", lambda: float(scaling_factor.reshape(-1)[0]))
         if self.output_bit == 8:
             out8 = torch.empty(x.shape, dtype=torch.int8, device=x.device)
-            _lib.call("ivit_shiftmax_f32_i8", _lib.ptr(xin), L, xin.numel() // L, L, float(scaling_factor.reshape(-1)[0]),
-                      _lib.ptr(out8), L, _st())
+            _lib.call("ivit_shiftmax_f32_i8", _lib.ptr(xin), L, xin.numel() // L, L, s_in, _lib.ptr(out8), L, _st())
         else:     # the softmax_bw knob (vit_quant.py:184): the same sequence with floor(. / 2^(31 - output_bit + 1)) (:175)
             out8 = torch.empty(x.shape, dtype=torch.int16, device=x.device)
-            _lib.call("ivit_shiftmax_f32_i16", _lib.ptr(xin), L, xin.numel() // L, L, float(scaling_factor.reshape(-1)[0]),
-                      self.output_bit, _lib.ptr(out8), L, _st())
-        s = torch.tensor([1 / 2 ** (self.output_bit - 1)], dtype=torch.float32, device=x.device)  # :176
+            _lib.call("ivit_shiftmax_f32_i16", _lib.ptr(xin), L, xin.numel() // L, L, s_in, self.output_bit, _lib.ptr(out8), L, _st())
+        s = lazy.taped("Shiftmax output scale",
+                       lambda: torch.tensor([1 / 2 ** (self.output_bit - 1)], dtype=torch.float32, device=x.device))  # :176
         self.act_scaling_factor = s
         return to_float(out8.to(torch.int32), s), s

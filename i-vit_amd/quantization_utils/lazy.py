@@ -34,7 +34,8 @@ Covers the I-ViT and the I-BERT operator families (ivit_modules.py, ibert_module
 configurations (vit_quant.py:180-187: the 16-bit residual stream with softmax and position embedding at 8 or 16 bits, resolve16)
 and Swin with either family (8-bit QuantActs, 16-bit residual stream), in any mixture: every site is resolved by the class of its own
 module.  Other configurations (other width mixtures, operator names with constructor parameters) take the ordinary module path through
-the materialisation rule above wherever a step is not one of the patterns.
+the materialisation rule above wherever a step is not one of the patterns.  Such a literal step does read scales and ranges back on
+every call; `Tape` (below) is what lets graph.ModuleGraph capture a forward that contains one.
 """
 from __future__ import annotations
 
@@ -82,6 +83,80 @@ class scope:
     def __exit__(self, *exc):
         _TLS.depth = getattr(_TLS, "depth", 0) - int(self.on)
         return False
+
+
+# ----------------------------------------------------------------------------------------------------------- graph capture
+class Tape:
+    """What a literal step (a module's `_slow`) of a frozen forward takes to the host, for graph.ModuleGraph: the modules' ordinary
+    forms read scales, ranges and the I-BERT LayerNorm shift back from the device and upload (m, e) pairs on every call, and two of
+    them decide on the activations (narrow_i8's overflow flag, QuantMatMul's choice of kernel by the largest probability).  A
+    capture allows neither.  Both kinds go through the tape of the thread:
+
+      * `take(label, build)`: a value that depends on frozen constants only.  While the tape RECORDS (the warm-up forward, run
+        eagerly) `build()` runs and its result is kept, device tensors included; while it REPLAYS (the capture) the recorded value
+        is returned in the same order, and a forward that asks for anything else than its warm-up did is an error.  The graph is
+        keyed on everything those constants were built from (graph.ModuleGraph.graph_signature);
+      * `flag(message)`: a check on the activations.  Recording: None -- the eager check runs, and raises as ever.  Replaying: one
+        int32 word of the graph's status tensor, which the captured kernel (or torch operation) sets to non-zero instead;
+        ModuleGraph.graph_status() reads the words and raises `message`.
+
+    Without a tape -- every eager call -- nothing changes."""
+
+    def __init__(self):
+        self.items, self.messages, self.recording, self.pos, self.used, self.status = [], [], True, 0, 0, None
+
+    def replay(self, status):
+        """status: int32 [max(1, len(self.messages))], zeroed"""
+        self.recording, self.pos, self.used, self.status = False, 0, 0, status
+
+    def take(self, label, build):
+        if self.recording:
+            v = build()
+            self.items.append((label, v))
+            return v
+        if self.pos >= len(self.items) or self.items[self.pos][0] != label:
+            raise RuntimeError(f"module graph: the captured forward asks for {label!r} where its warm-up forward asked for "
+                               f"{self.items[self.pos][0] if self.pos < len(self.items) else 'nothing more'!r}")
+        self.pos += 1
+        return self.items[self.pos - 1][1]
+
+    def flag(self, message):
+        if self.recording:
+            self.messages.append(message)
+            return None
+        if self.used >= len(self.messages) or self.messages[self.used] != message:
+            raise RuntimeError(f"module graph: the captured forward checks {message!r}, which its warm-up forward did not")
+        self.used += 1
+        return self.status[self.used - 1:self.used]
+
+    def complete(self):
+        return self.pos == len(self.items) and self.used == len(self.messages)
+
+
+class taping:
+    """`with lazy.taping(tape):` -- the literal steps of this thread's forwards go through `tape`"""
+
+    def __init__(self, tape):
+        self.tape = tape
+
+    def __enter__(self):
+        self.prev = getattr(_TLS, "tape", None)
+        _TLS.tape = self.tape
+        return self.tape
+
+    def __exit__(self, *exc):
+        _TLS.tape = self.prev
+        return False
+
+
+def tape():
+    return getattr(_TLS, "tape", None)
+
+
+def taped(label, build):
+    """build(), or under a Tape its recorded result (Tape.take)"""
+    t = getattr(_TLS, "tape", None)
+    return build() if t is None else t.take(label, build)
 
 
 def _st():

@@ -159,10 +159,16 @@ def to_float(z: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
 
 def narrow_i8(z: torch.Tensor, what: str) -> torch.Tensor:
     out = torch.empty(z.shape, dtype=torch.int8, device=z.device)
+    message = f"{what}: integer activations exceed 8 bits; the int8 MFMA kernels cannot represent them"
+    t = lazy.tape()
+    word = None if t is None else t.flag(message)
+    if word is not None:      # inside a graph capture: the kernel sets the graph's status word, ModuleGraph.graph_status() raises
+        _lib.call("ivit_narrow_i32_i8", _lib.ptr(z), _lib.ptr(out), z.numel(), _lib.ptr(word), _st())
+        return out
     flag = torch.zeros(1, dtype=torch.int32, device=z.device)
     _lib.call("ivit_narrow_i32_i8", _lib.ptr(z), _lib.ptr(out), z.numel(), _lib.ptr(flag), _st())
     if int(flag.item()) != 0:
-        raise _lib.IvitError(f"{what}: integer activations exceed 8 bits; the int8 MFMA kernels cannot represent them")
+        raise _lib.IvitError(message)
     return out
 
 
@@ -180,8 +186,10 @@ def _pad_cols(a: np.ndarray, kp: int) -> np.ndarray:
 
 
 def _me_tables(pre_sf: torch.Tensor, z_sf, device):
-    m, e = dyadic(pre_sf.detach().reshape(-1).cpu().numpy(), f32(z_sf))
-    return _dev_table(m.view(np.int32), device), _dev_table(e, device), m.size
+    def build():
+        m, e = dyadic(pre_sf.detach().reshape(-1).cpu().numpy(), f32(z_sf))
+        return _dev_table(m.view(np.int32), device), _dev_table(e, device), m.size
+    return lazy.taped("QuantAct (m, e)", build)
 
 
 # ----------------------------------------------------------------------------- QuantLinear
@@ -250,7 +258,7 @@ class QuantLinear(nn.Linear):
 
     def _slow(self, x, prev_act_scaling_factor=None):
         assert prev_act_scaling_factor is not None and prev_act_scaling_factor.shape == (1,)
-        W8, b32, s_acc = self._params(float(prev_act_scaling_factor.item()))
+        W8, b32, s_acc = self._params(lazy.taped("QuantLinear input scale", lambda: float(prev_act_scaling_factor.item())))
         K, N = self.in_features, self.out_features
         if K % 16 != 0:
             raise NotImplementedError("ivit_gemm_i8_i32 needs in_features % 16 == 0")
@@ -428,7 +436,8 @@ class QuantAct(nn.Module):
             self._observe(x if identity is None else identity + x)
         x_min = self.x_min if specified_min is None else specified_min
         x_max = self.x_max if specified_max is None else specified_max
-        s_out = sym_scale(float(x_min.reshape(-1)[0]), float(x_max.reshape(-1)[0]), self.activation_bit)
+        lo, hi = lazy.taped("QuantAct range", lambda: (float(x_min.reshape(-1)[0]), float(x_max.reshape(-1)[0])))
+        s_out = sym_scale(lo, hi, self.activation_bit)
         self.act_scaling_factor = torch.full((1,), float(s_out), dtype=torch.float32, device=x.device)
         bits = self.activation_bit
         if pre_act_scaling_factor is None:
@@ -446,7 +455,8 @@ class QuantAct(nn.Module):
         else:
             z = to_int32(x, pre_act_scaling_factor)
             C = x.shape[-1]
-            if pre_act_scaling_factor.numel() == 1 and float(pre_act_scaling_factor.reshape(-1)[0]) < 0:
+            if pre_act_scaling_factor.numel() == 1 and lazy.taped("QuantAct input scale sign",
+                                                                  lambda: float(pre_act_scaling_factor.reshape(-1)[0]) < 0):
                 # a negative incoming scale (the I-BERT GELU's, ibert_modules.py:213,232): round-half-even and the
                 # half-away-from-zero mantissa rounding of batch_frexp are both odd functions, so
                 # requant(z, s) == requant(-z, -s) exactly
@@ -509,6 +519,20 @@ class QuantMatMul(nn.Module):
         assert B.shape[-2] == Kd and A.shape[:-2] == B.shape[:-2]
         batch = a32.numel() // (Tq * Kd)
         out = torch.empty((*A.shape[:-1], N), dtype=torch.int32, device=A.device)
+        t = lazy.tape()
+        # the entry's own bound on |P| (p_absmax * 128 * Tk < 2^31), which the eager call below is refused beyond
+        bound = (2 ** 31 - 1) // (128 * Kd)
+        word = None if t is None else t.flag(f"QuantMatMul: |A| above {bound} over {Kd} terms overflows the int32 product sum "
+                                             "(ivit_bgemm_pv_i32_i8)")
+        if word is not None:
+            # inside a graph capture the largest |A| cannot choose the kernel: the int32 form computes the same int32 sums as the two
+            # narrower ones wherever they apply (up to 32767, whatever Kd), and beyond them its bound is checked on the device into
+            # the graph's status word
+            word.copy_(torch.maximum(word, (a32.abs().amax() > max(bound, 32767)).to(torch.int32).reshape(1)))
+            _lib.call("ivit_bgemm_pv_i32_i8", _lib.ptr(a32), _lib.ptr(b8), _lib.ptr(out), batch, Tq, Kd, N, bound, _st())
+            s = (pre_act_scaling_factor_A * pre_act_scaling_factor_B).float()
+            self.act_scaling_factor = s
+            return to_float(out, s), s
         amax = int(a32.abs().max())
         if amax <= 127:
             a8 = a32.to(torch.int8)
@@ -577,7 +601,7 @@ class QuantConv2d(nn.Conv2d):
             raise NotImplementedError("QuantConv2d on the HIP path is the non-overlapping patch convolution")
         B, Cin, H, Wd = x.shape
         assert H == Wd and H % kh == 0
-        s_in = float(pre_act_scaling_factor.reshape(-1)[0])
+        s_in = lazy.taped("QuantConv2d input scale", lambda: float(pre_act_scaling_factor.reshape(-1)[0]))
         key = (self.weight._version, self.bias._version, s_in, self.weight.device)
         if self._cache is None or self._cache[0] != key:
             lp = LinearParams(self.weight.detach().cpu().numpy(), self.bias.detach().cpu().numpy(), s_in)

@@ -23,6 +23,7 @@ import torch
 from torch import nn
 
 from .dispatch import EngineDispatch
+from .graph import ModuleGraph
 from .layers_quant import DropPath, Mlp, PatchEmbed, to_2tuple, trunc_normal_
 from .quantization_utils import IntGELU, IntSoftmax, QuantAct, QuantLinear, QuantMatMul, get_gelu, get_layernorm, get_softmax, lazy
 from .quantization_utils.layer_selection import _parse_layer_name
@@ -209,7 +210,7 @@ class BasicLayer(nn.Module):
         return f"dim={self.dim}, input_resolution={self.input_resolution}, depth={self.depth}"
 
 
-class SwinTransformer(EngineDispatch, nn.Module):
+class SwinTransformer(EngineDispatch, ModuleGraph, nn.Module):
     """swin_quant.py:424-564."""
 
     def __init__(self, img_size=224, patch_size=4, in_chans=3, num_classes=1000, embed_dim=96, depths=(2, 2, 6, 2),

@@ -15,6 +15,7 @@ import torch
 from torch import nn
 
 from .dispatch import EngineDispatch
+from .graph import ModuleGraph
 from .layers_quant import DropPath, Mlp, PatchEmbed, trunc_normal_
 from .quantization_utils import (QuantAct, QuantLinear, QuantMatMul, get_gelu, get_layernorm, get_softmax)
 from .quantization_utils import lazy
@@ -86,7 +87,7 @@ class Block(nn.Module):
         return self.qact4(self.drop_path(x), s, x_2, s_2)          # residual 2
 
 
-class VisionTransformer(EngineDispatch, nn.Module):
+class VisionTransformer(EngineDispatch, ModuleGraph, nn.Module):
     def __init__(self, img_size=224, patch_size=16, in_chans=3, num_classes=1000, embed_dim=768, depth=12,
                  num_heads=12, mlp_ratio=4.0, qkv_bias=True, qk_scale=None, representation_size=None, drop_rate=0.0,
                  attn_drop_rate=0.0, drop_path_rate=0.0, patch_embed_bw=8, pos_encoding_bw=8, block_input_bw=8,
