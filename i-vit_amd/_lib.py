@@ -86,6 +86,8 @@ SIGNATURES = {
     "ivit_quantize_patchify_u8_i8": [vp, vp, i64, ci, ci, ci, ci, vp, vp],
     "ivit_minmax_f32": [vp, i64, vp, vp],
     "ivit_quantile_pair_f32": [vp, i64, f32, f32, vp, vp, i64, vp],
+    "ivit_weight_quant_rows_f32_i8": [vp, i64, ci, ci, vp, vp, i64, vp, vp],
+    "ivit_bias_quant_f32_i32": [vp, vp, ci, f32, vp, vp, vp, vp],
     "ivit_shiftmax_i32_i8": [vp, i64, ci, ci, f32, vp, i64, vp],
     "ivit_requant_i8_i16": [vp, u32, i32, vp, i64, vp],
     "ivit_residual_requant_i16": [vp, ci, vp, vp, u32, i32, vp, u32, i32, vp, i64, ci, ci, ci, ci, ci, vp],

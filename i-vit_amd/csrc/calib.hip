@@ -10,7 +10,12 @@
 //                                extends the prefix by that byte and rebases the rank to the bin.  After the last pass the prefix IS the
 //                                key: the kernel turns the four keys back into floats and writes the two interpolations.
 // Everything is stream-ordered, nothing is read back, the workspace is cleared by the first kernel.
+//
+// Second half: the integer parameters of a QuantLinear / QuantConv2d while the ranges still move (ivit_weight_quant_rows_f32_i8,
+// ivit_bias_quant_f32_i32): the per-row weight scale, the 8-bit weights and the 32-bit bias of quant_modules.py:202-220 / 486-504 of
+// the reference, in the float32 operations of prepare.weight_scale / quant_sym / LinearParams, one rounding each.
 #include "common.h"
+#include <cfloat>
 
 namespace {
 
@@ -239,6 +244,155 @@ void launch_pass(const float* x, int64_t n, unsigned* ws, float w_lo, float w_hi
     hipLaunchKernelGGL(quantile_select_kernel<PASS>, dim3(1), dim3(QNT), 0, st, ws, w_lo, w_hi, out2);
 }
 
+// ----------------------------------------------------------------------------------------------- weight and bias quantisation
+constexpr int WQ_NT = 256;            // four waves: one row each
+constexpr int WQ_CHUNK = 256;         // columns a wave takes per step: one float4 per lane
+constexpr int WQ_KEEP = 16;           // steps whose float4 stay in registers between the two passes: rows of up to 4096 columns
+constexpr int WQ_OUT4 = 1;            // flags: w8 rows admit dword stores;
+constexpr int WQ_INT4 = 2;            //        w_int rows admit 16-byte stores
+
+// order-preserving signed key of a float (-0 below +0; denormals keep their place: no float comparison is involved) and back
+IVIT_DEV int wq_key(float v)
+{
+    const int b = __float_as_int(v);
+    return b ^ ((b >> 31) & 0x7fffffff);
+}
+IVIT_DEV float wq_unkey(int k) { return __int_as_float(k ^ ((k >> 31) & 0x7fffffff)); }
+
+// column of element t of the float4 a lane holds of step `step`: VEC four consecutive columns (one 16-byte load), else four columns
+// 64 apart (four dword loads, each coalesced over the wave)
+template <bool VEC>
+IVIT_DEV int64_t wq_col(int64_t step, int lane, int t)
+{
+    return VEC ? step * WQ_CHUNK + 4 * lane + t : step * WQ_CHUNK + 64 * t + lane;
+}
+
+// columns at and behind `cols` are never read: they take `fill`, an element of the row (neutral for its minimum and maximum)
+template <bool VEC>
+IVIT_DEV float4 wq_load(const float* wr, int64_t step, int lane, int cols, float fill)
+{
+    if (VEC && wq_col<VEC>(step, lane, 3) < cols) return *reinterpret_cast<const float4*>(wr + wq_col<VEC>(step, lane, 0));
+    float c[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const int64_t col = wq_col<VEC>(step, lane, t);
+        c[t] = col < cols ? wr[col] : fill;
+    }
+    return make_float4(c[0], c[1], c[2], c[3]);
+}
+
+IVIT_DEV void wq_minmax(const float4& v, int& kmin, int& kmax)
+{
+    const int k0 = wq_key(v.x), k1 = wq_key(v.y), k2 = wq_key(v.z), k3 = wq_key(v.w);
+    kmin = min(min(kmin, k0), min(k1, min(k2, k3)));
+    kmax = max(max(kmax, k0), max(k1, max(k2, k3)));
+}
+
+// clamp(rint(fl(rs * v)), -128, 127): SymmetricQuantFunction on one weight (the file is built without contraction)
+IVIT_DEV int wq_quant(float v, float rs)
+{
+    const float p = rs * v;
+    return (int)fminf(fmaxf(__builtin_rintf(p), -128.0f), 127.0f);
+}
+
+template <bool VEC>
+IVIT_DEV void wq_store(const float4& v, float rs, int8_t* o8, float* oi, int64_t step, int lane, int cols, int flags)
+{
+    const int q[4] = {wq_quant(v.x, rs), wq_quant(v.y, rs), wq_quant(v.z, rs), wq_quant(v.w, rs)};
+    if (VEC && wq_col<VEC>(step, lane, 3) < cols) {
+        const int64_t c0 = wq_col<VEC>(step, lane, 0);
+        if (flags & WQ_OUT4) {
+            *reinterpret_cast<uint32_t*>(o8 + c0) = (unsigned)(q[0] & 255) | ((unsigned)(q[1] & 255) << 8) | ((unsigned)(q[2] & 255) << 16) |
+                                                    ((unsigned)q[3] << 24);
+        } else {
+#pragma unroll
+            for (int t = 0; t < 4; ++t) o8[c0 + t] = (int8_t)q[t];
+        }
+        if (oi) {
+            if (flags & WQ_INT4) {
+                *reinterpret_cast<float4*>(oi + c0) = make_float4((float)q[0], (float)q[1], (float)q[2], (float)q[3]);
+            } else {
+#pragma unroll
+                for (int t = 0; t < 4; ++t) oi[c0 + t] = (float)q[t];
+            }
+        }
+        return;
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const int64_t col = wq_col<VEC>(step, lane, t);
+        if (col < cols) {
+            o8[col] = (int8_t)q[t];
+            if (oi) oi[col] = (float)q[t];
+        }
+    }
+}
+
+// One wave per row.  Pass 1 reads the row and reduces its minimum and maximum over the wave; pass 2 quantises.  KEEP: the row is at
+// most WQ_KEEP steps long and stays in registers (constant indices only: no scratch); else it is read a second time.
+template <bool VEC, bool KEEP>
+__global__ __launch_bounds__(WQ_NT) void weight_quant_rows_kernel(const float* w, int64_t ldw, int rows, int cols, float* scale, int8_t* w8,
+                                                                   int64_t ldo, float* w_int, int flags)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * (WQ_NT / 64) + (threadIdx.x >> 6);
+    if (row >= rows) return;                                        // whole waves leave; there is no barrier in this kernel
+    const float* wr = w + row * ldw;
+    const float first = wr[0];
+    int kmin = wq_key(first), kmax = kmin;
+    const int64_t steps = ((int64_t)cols + WQ_CHUNK - 1) / WQ_CHUNK;
+    float4 keep[KEEP ? WQ_KEEP : 1];
+    if constexpr (KEEP) {
+#pragma unroll
+        for (int j = 0; j < WQ_KEEP; ++j) {
+            if (j < steps) {                                        // wave-uniform
+                keep[j] = wq_load<VEC>(wr, j, lane, cols, first);
+                wq_minmax(keep[j], kmin, kmax);
+            }
+        }
+    } else {
+        for (int64_t j = 0; j < steps; ++j) {
+            const float4 v = wq_load<VEC>(wr, j, lane, cols, first);
+            wq_minmax(v, kmin, kmax);
+        }
+    }
+    kmax = wave_allmax_i32(kmax);
+    kmin = ~wave_allmax_i32(~kmin);
+    // mx = max(-min, max), in keys; scale = max(fl(mx / 127), eps); rs = fl(1 / scale): two correctly rounded divisions
+    const float mx = wq_unkey(max(wq_key(-wq_unkey(kmin)), kmax));
+    const float q = mx / 127.0f;
+    const float sc = q > FLT_EPSILON ? q : FLT_EPSILON;
+    const float rs = 1.0f / sc;
+    if (lane == 0) scale[row] = sc;
+    int8_t* o8 = w8 + row * ldo;
+    float* oi = w_int ? w_int + row * (int64_t)cols : nullptr;
+    if constexpr (KEEP) {
+#pragma unroll
+        for (int j = 0; j < WQ_KEEP; ++j)
+            if (j < steps) wq_store<VEC>(keep[j], rs, o8, oi, j, lane, cols, flags);
+    } else {
+        for (int64_t j = 0; j < steps; ++j) wq_store<VEC>(wq_load<VEC>(wr, j, lane, cols, first), rs, o8, oi, j, lane, cols, flags);
+    }
+}
+
+// s_acc = fl(scale * s_in); b32 = clamp(rint(fl(fl(1 / s_acc) * bias))): quant_sym at 32 bits clips the float to [-2^31, 2^31] (the
+// upper bound 2^31 - 1 is not a float32) and then takes the integer minimum with 2^31 - 1
+__global__ __launch_bounds__(256) void bias_quant_kernel(const float* bias, const float* scale, int n, float s_in, float* s_acc, int32_t* b32,
+                                                         float* b_int)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float sa = scale[i] * s_in;
+    s_acc[i] = sa;
+    if (bias == nullptr) return;
+    const float rs = 1.0f / sa;
+    const float p = rs * bias[i];
+    const float r = __builtin_rintf(p);
+    const int32_t b = r >= 2147483648.0f ? 2147483647 : r <= -2147483648.0f ? (-2147483647 - 1) : (int32_t)r;
+    b32[i] = b;
+    if (b_int) b_int[i] = (float)b;
+}
+
 }  // namespace
 
 IVIT_EXPORT int ivit_quantile_pair_f32(const float* x, int64_t n, float q_lo, float q_hi, float* out2, void* workspace,
@@ -266,4 +420,43 @@ IVIT_EXPORT int ivit_quantile_pair_f32(const float* x, int64_t n, float q_lo, fl
     launch_pass<2>(x, n, ws, w_lo, w_hi, out2, grid, st);
     launch_pass<3>(x, n, ws, w_lo, w_hi, out2, grid, st);
     IVIT_CHECK_LAUNCH("ivit_quantile_pair_f32");
+}
+
+IVIT_EXPORT int ivit_weight_quant_rows_f32_i8(const float* w, int64_t ldw, int rows, int cols, float* scale, int8_t* w8, int64_t ldo,
+                                              float* w_int, ivit_stream_t stream)
+{
+    IVIT_REQUIRE(rows >= 1 && cols >= 1, "ivit_weight_quant_rows_f32_i8: rows = %d, cols = %d (both at least 1)", rows, cols);
+    IVIT_REQUIRE(ldw >= cols && ldo >= cols, "ivit_weight_quant_rows_f32_i8: ldw = %lld, ldo = %lld below cols = %d", (long long)ldw,
+                 (long long)ldo, cols);
+    IVIT_REQUIRE(w && scale && w8, "ivit_weight_quant_rows_f32_i8: NULL operand");
+    IVIT_REQUIRE(((uintptr_t)w % 4 == 0) && ((uintptr_t)scale % 4 == 0) && ((uintptr_t)w_int % 4 == 0),
+                 "ivit_weight_quant_rows_f32_i8: misaligned operand (4 bytes)");
+    hipStream_t st = ivit_stream(stream);
+    const bool vec = ((uintptr_t)w % 16 == 0) && (ldw % 4 == 0);    // every row starts on a 16-byte boundary
+    const bool keep = cols <= WQ_KEEP * WQ_CHUNK;
+    const int flags = ((((uintptr_t)w8 % 4 == 0) && (ldo % 4 == 0)) ? WQ_OUT4 : 0) |
+                      ((w_int && ((uintptr_t)w_int % 16 == 0) && (cols % 4 == 0)) ? WQ_INT4 : 0);
+    const dim3 grid((unsigned)(((int64_t)rows + WQ_NT / 64 - 1) / (WQ_NT / 64))), block(WQ_NT);
+#define IVIT_WQ_LAUNCH(V, K) hipLaunchKernelGGL((weight_quant_rows_kernel<V, K>), grid, block, 0, st, w, ldw, rows, cols, scale, w8, ldo, w_int, flags)
+    if (vec && keep) IVIT_WQ_LAUNCH(true, true);
+    else if (vec) IVIT_WQ_LAUNCH(true, false);
+    else if (keep) IVIT_WQ_LAUNCH(false, true);
+    else IVIT_WQ_LAUNCH(false, false);
+#undef IVIT_WQ_LAUNCH
+    IVIT_CHECK_LAUNCH("ivit_weight_quant_rows_f32_i8");
+}
+
+IVIT_EXPORT int ivit_bias_quant_f32_i32(const float* bias, const float* scale, int n, float s_in, float* s_acc, int32_t* b32, float* b_int,
+                                        ivit_stream_t stream)
+{
+    IVIT_REQUIRE(n >= 1, "ivit_bias_quant_f32_i32: n = %d (at least 1)", n);
+    IVIT_REQUIRE(scale && s_acc, "ivit_bias_quant_f32_i32: NULL operand");
+    IVIT_REQUIRE(bias ? b32 != nullptr : (b32 == nullptr && b_int == nullptr),
+                 "ivit_bias_quant_f32_i32: b32 goes with bias, b_int only with both");
+    IVIT_REQUIRE(((uintptr_t)bias % 4 == 0) && ((uintptr_t)scale % 4 == 0) && ((uintptr_t)s_acc % 4 == 0) && ((uintptr_t)b32 % 4 == 0) &&
+                     ((uintptr_t)b_int % 4 == 0),
+                 "ivit_bias_quant_f32_i32: misaligned operand (4 bytes)");
+    hipStream_t st = ivit_stream(stream);
+    hipLaunchKernelGGL(bias_quant_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, bias, scale, n, s_in, s_acc, b32, b_int);
+    IVIT_CHECK_LAUNCH("ivit_bias_quant_f32_i32");
 }

@@ -97,6 +97,12 @@ def occupancy_rules(path, what):
             # scratch-free: the forms of 193-208 tokens (14 x 14 patches + cls: every BASELINE config); the general-T forms
             # (other geometries, "not tuned") may keep a few dwords of the Q prefetch in scratch
             occ, need_no_scratch = int(m.group(3)), m.group(4) == "0"
+        elif what == "calib":
+            # weight_quant_rows_kernel<VEC, KEEP>: one wave per row, four per workgroup; KEEP holds up to 64 dwords of the row per lane
+            # between its two passes, with constant indices only: no scratch in any form
+            if "weight_quant_rows_kernel" not in name and "bias_quant_kernel" not in name:
+                continue
+            occ, need_no_scratch = 1, True
         elif what == "swin":
             if (m := re.search(r"window_attention_kernelILi(\d+)ELb([01])ELi(\d+)E", name)):
                 # window_attention_kernel<SM, RQ32, NKT>: = its __launch_bounds__.  NKT 4 (2..64 tokens): four workgroups per CU;

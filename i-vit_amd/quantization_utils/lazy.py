@@ -721,10 +721,65 @@ def _key(*hosts):
     return tuple(np.asarray(h, f32).tobytes() if h is not None else None for h in hosts)
 
 
+def params_on_device(mod) -> bool:
+    """the integer parameters of this QuantLinear / QuantConv2d are derived on the device (quant_modules.LINEAR_PARAMS_ON_DEVICE)"""
+    from . import quant_modules
+    return mod.weight.device.type == "cuda" and quant_modules.LINEAR_PARAMS_ON_DEVICE
+
+
+def device_linear_params(mod, s_in):
+    """Integer parameters of a QuantLinear / QuantConv2d whose weight lives on a GPU, for input scale s_in, without a weight crossing
+    the bus: prepare.LinearParams bit for bit, by ivit_weight_quant_rows_f32_i8 and ivit_bias_quant_f32_i32.  Two caches on the module:
+      weight part, key (weight._version, device): W [Np, Kp] int8, zero-filled, K padded to the GEMM's 64-byte slabs and, for a
+          QuantLinear, N to a multiple of 4 (its callers slice [:N] where they want no row padding); scale [N]; w_int [N, K] float32;
+      bias part, key (weight._version, bias._version, s_in, device): s_acc [N]; b [Np] int32 (zero behind N) and b_int [N] float32,
+          both None without a bias.
+    A batch that only moved the ranges launches the bias kernel alone.  -> (weight part, bias part)"""
+    w, bias = mod.weight, mod.bias
+    dev = w.device
+    N = w.shape[0]
+    Kin = w.numel() // N
+    wkey = (w._version, str(dev))
+    wp = mod.__dict__.get("_dev_weight_part")
+    if wp is None or wp["key"] != wkey:
+        wf = w.detach().reshape(N, Kin).contiguous().float()
+        K = (Kin + 63) // 64 * 64
+        Np = N + (-N % 4 if isinstance(mod, torch.nn.Linear) else 0)     # the GEMM wants N % 4 == 0: zero rows (QuantLinear._slow)
+        W = torch.zeros(Np, K, dtype=torch.int8, device=dev)
+        scale = torch.empty(N, dtype=torch.float32, device=dev)
+        w_int = torch.empty(N, Kin, dtype=torch.float32, device=dev)
+        _lib.call("ivit_weight_quant_rows_f32_i8", _lib.ptr(wf), Kin, N, Kin, _lib.ptr(scale), _lib.ptr(W), K, _lib.ptr(w_int), _st())
+        # scale feeds the bias kernel of every later batch: the module's buffer gets a copy of its own (scale_out), made once here
+        wp = mod.__dict__["_dev_weight_part"] = dict(key=wkey, N=N, Np=Np, K=K, Kin=Kin, W=W, scale=scale, scale_out=scale.clone(),
+                                                     w_int=w_int)
+    s = float(np.asarray(s_in, f32).reshape(-1)[0])
+    bkey = (w._version, None if bias is None else bias._version, s, str(dev))
+    bp = mod.__dict__.get("_dev_bias_part")
+    if bp is None or bp["key"] != bkey:
+        s_acc = torch.empty(N, dtype=torch.float32, device=dev)
+        b = b_int = bf = None
+        if bias is not None:
+            bf = bias.detach().contiguous().float()
+            b = torch.zeros(wp["Np"], dtype=torch.int32, device=dev)
+            b_int = torch.empty(N, dtype=torch.float32, device=dev)
+        _lib.call("ivit_bias_quant_f32_i32", _lib.ptr(bf), _lib.ptr(wp["scale"]), N, s, _lib.ptr(s_acc), _lib.ptr(b), _lib.ptr(b_int), _st())
+        bp = mod.__dict__["_dev_bias_part"] = dict(key=bkey, s_acc=s_acc, b=b, b_int=b_int)
+    return wp, bp
+
+
 def linear_consts(lin, s_in, device):
     """integer weights of a QuantLinear / QuantConv2d for input scale s_in (host float32): W8 row-major (+ the 16x16x64
-    fragment copy where the weights-in-registers GEMM applies), b32, s_acc"""
+    fragment copy where the weights-in-registers GEMM applies), b32, s_acc (and its host copy for the per-channel multipliers)"""
     def build():
+        if params_on_device(lin):
+            wp, bp = device_linear_params(lin, s_in)
+            lin._publish_device(wp, bp)
+            N, K, Kin = wp["N"], wp["K"], wp["Kin"]
+            s_acc = bp["s_acc"].cpu().numpy()      # N floats: QS and dyadic (_gemm_me) want them on the host
+            d = dict(N=N, K=K, Kin=Kin, W=wp["W"][:N], b=None if bp["b"] is None else bp["b"][:N], s_acc=QS.make(s_acc, device),
+                     s_acc_host=s_acc)
+            d["Wf"], _ = frag_copy(d["W"], _st())
+            return d
         lp = LinearParams(lin.weight.detach().cpu().numpy(), None if lin.bias is None else lin.bias.detach().cpu().numpy(), s_in)
         N, Kin = lp.W8.shape
         K = (Kin + 63) // 64 * 64          # the GEMM kernels step K in 64-byte slabs: zero columns (Swin: K = 96, 48)
@@ -733,8 +788,8 @@ def linear_consts(lin, s_in, device):
             W8 = np.zeros((N, K), np.int8)
             W8[:, :Kin] = lp.W8
         lin._publish(lp, device)           # the buffers the reference rewrites on every call
-        d = dict(lp=lp, N=N, K=K, Kin=Kin, W=_dev(W8, device), b=None if lp.b32 is None else _dev(lp.b32, device),
-                 s_acc=QS.make(lp.s_acc, device))
+        d = dict(N=N, K=K, Kin=Kin, W=_dev(W8, device), b=None if lp.b32 is None else _dev(lp.b32, device),
+                 s_acc=QS.make(lp.s_acc, device), s_acc_host=lp.s_acc)
         d["Wf"], _ = frag_copy(d["W"], _st())       # every consumer here has an int8 epilogue
         return d
     return _cache(lin, ("lin", lin.weight._version, None if lin.bias is None else lin.bias._version, _key(s_in), str(device)), build)
@@ -746,7 +801,7 @@ def _gemm_me(lin, s_in, s_out, device, need_e31=True):
     c = linear_consts(lin, s_in, device)
 
     def build():
-        m, e = dyadic(c["lp"].s_acc, s_out)
+        m, e = dyadic(c["s_acc_host"], s_out)
         if need_e31 and np.any(e < 31):
             return None
         return _dev(m.view(np.int32), device), _dev(e, device)

@@ -193,6 +193,21 @@ def _me_tables(pre_sf: torch.Tensor, z_sf, device):
 
 
 # ----------------------------------------------------------------------------- QuantLinear
+# True: a QuantLinear / QuantConv2d whose weight lives on a GPU derives W8, b32 and its scales there (lazy.device_linear_params: no
+# weight crosses the bus in a forward); False: the host form (prepare.LinearParams), which CPU tensors always take.  Same values.
+LINEAR_PARAMS_ON_DEVICE = True
+
+
+def _publish_device(mod, scale_name, wp, bp):
+    """the buffers the reference overwrites on every call (quant_modules.py:211-220, 496-504), from the device caches: tensors that
+    nothing computes from (the caches keep W8, b32 and the scale the bias kernel reads for themselves), so a caller who writes into
+    a buffer changes that buffer only"""
+    setattr(mod, scale_name, wp["scale_out"])
+    mod.weight_integer = wp["w_int"].view(mod.weight.shape)
+    if bp["b_int"] is not None:
+        mod.bias_integer = bp["b_int"]
+
+
 class QuantLinear(nn.Linear):
     """quant_modules.py:131-226."""
 
@@ -222,7 +237,12 @@ class QuantLinear(nn.Linear):
 
     def _params(self, s_in: float):
         key = (self.weight._version, None if self.bias is None else self.bias._version, s_in, self.weight.device)
-        if self._cache is None or self._cache[0] != key:
+        miss = self._cache is None or self._cache[0] != key
+        if miss and lazy.params_on_device(self):
+            wp, bp = lazy.device_linear_params(self, s_in)      # W and b carry the N % 4 row padding
+            self._publish_device(wp, bp)
+            self._cache = (key, wp["W"], bp["b"], bp["s_acc"])
+        elif miss:
             lp = LinearParams(self.weight.detach().cpu().numpy(),
                               None if self.bias is None else self.bias.detach().cpu().numpy(), s_in)
             dev = self.weight.device
@@ -244,6 +264,9 @@ class QuantLinear(nn.Linear):
         self.weight_integer = _dev_table(lp.W8, dev).float().reshape(self.weight.shape)
         if lp.b32 is not None:
             self.bias_integer = _dev_table(lp.b32, dev).float()
+
+    def _publish_device(self, wp, bp):
+        _publish_device(self, "fc_scaling_factor", wp, bp)
 
     def forward(self, x, prev_act_scaling_factor=None):
         if isinstance(x, lazy.QT):
@@ -579,6 +602,9 @@ class QuantConv2d(nn.Conv2d):
         self.weight_integer = _dev_table(lp.W8, dev).float().reshape(self.weight.shape)
         self.bias_integer = _dev_table(lp.b32, dev).float()
 
+    def _publish_device(self, wp, bp):
+        _publish_device(self, "conv_scaling_factor", wp, bp)
+
     def forward(self, x, pre_act_scaling_factor=None):
         if isinstance(x, lazy.QT):
             s_in = lazy.host_of(pre_act_scaling_factor)
@@ -603,7 +629,12 @@ class QuantConv2d(nn.Conv2d):
         assert H == Wd and H % kh == 0
         s_in = lazy.taped("QuantConv2d input scale", lambda: float(pre_act_scaling_factor.reshape(-1)[0]))
         key = (self.weight._version, self.bias._version, s_in, self.weight.device)
-        if self._cache is None or self._cache[0] != key:
+        miss = self._cache is None or self._cache[0] != key
+        if miss and lazy.params_on_device(self):
+            wp, bp = lazy.device_linear_params(self, s_in)
+            self._cache = (key, wp["W"], bp["b"], bp["s_acc"])
+            self._publish_device(wp, bp)
+        elif miss:
             lp = LinearParams(self.weight.detach().cpu().numpy(), self.bias.detach().cpu().numpy(), s_in)
             dev = x.device
             self._cache = (key, _dev_table(_pad_cols(lp.W8, _pad_k(lp.K)), dev), _dev_table(lp.b32, dev),

@@ -59,6 +59,39 @@ int ivit_minmax_f32(const float* x, int64_t n, float* out_min_max, ivit_stream_t
 int ivit_quantile_pair_f32(const float* x, int64_t n, float q_lo, float q_hi, float* out2, void* workspace, int64_t workspace_bytes,
                            ivit_stream_t stream);
 
+/* ---- integer parameters of a linear layer while the ranges move -------------------------------
+ * QuantLinear / QuantConv2d recompute their integer weights and bias inside every forward (quant_modules.py:202-220, 486-504); a
+ * frozen model derives them once on the host (prepare.LinearParams), a calibrating one here, on the device, on every batch.
+ *
+ * Per-output-row symmetric 8-bit weight quantisation (quant_modules.py:204-215, 488-500; quant_utils.py:52-70, 79-97).
+ * For each row r of w [rows, ldw]:
+ *   mx       = max(-min_c w[r][c], max_c w[r][c])
+ *   scale[r] = max(fl32(mx / 127), FLT_EPSILON)
+ *   rs       = fl32(1 / scale[r])
+ *   q        = clamp(rint(fl32(rs * w[r][c])), -128, 127)
+ *   w8[r * ldo + c] = q   for c < cols
+ * Columns >= cols of w8 are not written: the caller zero-fills the K padding.
+ * w_int (may be NULL): dense [rows, cols] float32 = (float)q, converted from the integer, so a zero is +0.0f.
+ * Every operation is a single IEEE float32 rounding (correctly rounded division, round-to-nearest-even rint, no contraction):
+ * prepare.weight_scale and prepare.quant_sym bit for bit.  Denormal weights are not flushed.  Finite weights; on a non-finite one
+ * the values are unspecified, the access pattern is the same.
+ * One wave per row; 16-byte loads when w is 16-byte aligned and ldw % 4 == 0, dword loads otherwise; a row of up to 4096 columns is
+ * read once, a longer one twice.  w, scale and w_int need 4-byte alignment, w8 none.
+ * Errors: IVIT_ERR_INVALID for rows or cols below 1, ldw or ldo below cols, a NULL w, scale or w8, a misaligned float pointer. */
+int ivit_weight_quant_rows_f32_i8(const float* w, int64_t ldw, int rows, int cols, float* scale, int8_t* w8, int64_t ldo, float* w_int,
+                                  ivit_stream_t stream);
+
+/* bias_scaling_factor and the 32-bit bias (quant_modules.py:217-220), s_in the (host scalar) scale of the layer's input:
+ *   s_acc[i] = fl32(scale[i] * s_in)
+ *   b32[i]   = clamp(rint(fl32(fl32(1 / s_acc[i]) * bias[i])), -2^31, 2^31 - 1)
+ * The clamp is prepare.quant_sym's for bits = 32: the float clip bound 2^31 - 1 rounds to 2^31, then the integer minimum applies.
+ * bias == NULL (PatchMerging's reduction): b32 and b_int must be NULL too; only s_acc is written.  With a bias, b32 is required.
+ * b_int (may be NULL): (float)b32[i].  Finite biases, s_in a positive normal float.
+ * Errors: IVIT_ERR_INVALID for n below 1, a NULL scale or s_acc, b32 without bias or bias without b32, b_int without bias, a
+ * misaligned pointer (4 bytes). */
+int ivit_bias_quant_f32_i32(const float* bias, const float* scale, int n, float s_in, float* s_acc, int32_t* b32, float* b_int,
+                            ivit_stream_t stream);
+
 /* ---- input quantisation ---------------------------------------------------------------
  * QuantAct input mode = SymmetricQuantFunction.forward (quant_utils.py:79-97,
  * linear_quantize :13-49):  q = clamp(round(inv_scale * x), -128, 127), inv_scale = fl(1/s)
