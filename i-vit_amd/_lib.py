@@ -107,6 +107,8 @@ SIGNATURES = {
     "ivit_attention_fused_i8_ibert": [vp, vp, ci, ci, ci, ci, u32, i32, u32, i32, vp, vp, ci, ci, vp],
     "ivit_attention_fused_i8_ibert_wide": [vp, vp, ci, ci, ci, ci, u32, i32, u32, i32, vp, vp, ci, ci, ci, vp],
     "ivit_attention_fused_i8_ibert_long": [vp, vp, ci, ci, ci, ci, u32, i32, u32, i32, vp, vp, ci, ci, vp],
+    "ivit_attention_probs_u8": [vp, vp, i64, ci, ci, ci, ci, ci, u32, i32, f32, vp, vp, ci, vp],
+    "ivit_attention_probs_u8_ibert": [vp, vp, i64, ci, ci, ci, ci, ci, u32, i32, vp, vp, ci, vp],
     "ivit_ibert_layernorm_i8": [vp, i64, ci, ci, f32, vp, vp, f32, vp, vp, vp, i64, ci, vp],
     "ivit_ibert_layernorm_i16_i8": [vp, i64, ci, ci, f32, vp, vp, f32, vp, vp, vp, i64, vp],
     "ivit_ibert_layernorm_i16_i8_ex": [vp, i64, ci, ci, f32, vp, vp, f32, vp, vp, vp, i64, ci, vp],

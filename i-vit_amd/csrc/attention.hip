@@ -18,6 +18,7 @@
 // (256 x u32) with the reference's arithmetic (shiftexp_int); the row sum is an exact u32 sum rounded once to
 // float32 (= the reference's float32 sum whenever that is exact).
 #include "common.h"
+#include "rowsum.h"
 
 #if IVIT_LAB
 static int g_attn_debug = 0;     // ivit_debug_attention (include/ivit_hip_debug.h): phase ablations, score form, part count
@@ -1126,6 +1127,171 @@ __global__ __launch_bounds__(NT, CLS_OCC) void attention_cls_kernel(ClsArgs a)
     }
 }
 
+// ---- the probabilities themselves: P of the fused kernels above (8-bit softmax output), written to memory instead of multiplied
+// with V.  [batch][heads][q_rows][ldp] uint8, row r of an (image, head) = query r over the keys 0 .. tokens - 1; scale 2^-7.
+// One workgroup of four waves per (image, head, group of four query tiles); only the tiles that hold one of the first q_rows
+// queries are computed (q_rows = 1: the class token's row, one wave).  K is staged once per workgroup (kswz); a wave takes one
+// query tile and makes three passes:
+//   1. S^T tile = K . Q^T per key tile (v_mfma_i32_16x16x64_i8), requantised (qact_attn1) to the byte u = k + 128, stored in the
+//      wave's LDS slice [16 queries][16 * ceil(T / 16) + pad] -- no row lives in registers, so one form serves 1 .. 1025 tokens;
+//      the row maximum over the four lanes of a query
+//   2. the row sum.  Shiftmax: exact integer sum of exp_int over the lane's own keys, u64 (attention_long_kernel pass 2), then the
+//      float32 factor.  I-BERT: float32 in torch's CPU order by torch_rowsum_half (rowsum.h), two rows at a time, the exponents
+//      looked up from the slice's bytes -- the order is the general one, not a lane pattern per token count
+//   3. row by row, lane d takes the dword of keys 4 d .. 4 d + 3: exponent again from the table, p = floor(fl32(e * factor) / 2^24)
+//      (I-BERT: the halved factor, p in [0, 128]), packed (top_bytes), stored as a dword where every row of probs starts on one,
+//      byte by byte otherwise and for the last keys of a row whose length is no multiple of four.  Bytes tokens .. ldp - 1 stay.
+// MODE 0: Shiftmax, power-of-two input scale (256-entry table in LDS); 1: Shiftmax, natural scale (band or [256][256] table in
+// global memory, as attention_long_kernel MODE 1); 2: I-BERT (its float32 table, band or full).
+// LDS at 1025 tokens: 1.5 KB + 65 KB of K + 4 x 16.3 KB of slices = 132 KB.  Wave barriers and one __syncthreads; no scratch
+// (csrc/check_resources.py).
+struct ProbsArgs {
+    const int8_t* qkv;
+    uint8_t* probs;
+    int64_t ldp;
+    int batch, heads, tokens, q_rows;
+    double Ms;
+    int x0;
+    const unsigned* table;     // as LongArgs
+    int band_w;
+    int groups;                // workgroups per (image, head): ceil(ceil(q_rows / 16) / 4)
+    int dwords;                // probs and ldp are multiples of four: packed stores
+};
+
+constexpr int PROBS_HEAD_BYTES = 256 * 4 + 2 * 4 * 16 * 4;    // exponent table; row maximum and factor of every wave's 16 queries
+constexpr int PROBS_ROW_PAD = 4;                              // bytes: an odd number of dwords per slice row
+inline size_t probs_lds_bytes(int tokens)
+{
+    const int nkt = (tokens + 15) >> 4;
+    return (size_t)PROBS_HEAD_BYTES + (size_t)nkt * 16 * HD + (size_t)4 * 16 * (16 * nkt + PROBS_ROW_PAD);
+}
+
+template <int MODE>
+__global__ __launch_bounds__(NT) void attention_probs_kernel(ProbsArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) char psm[];
+    const int T = a.tokens, nkt = (T + 15) >> 4, rs = 16 * nkt + PROBS_ROW_PAD;
+    const int bh = blockIdx.x / a.groups, grp = blockIdx.x - bh * a.groups;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int g = lane >> 4, l15 = lane & 15;
+    const int64_t plane = (int64_t)a.batch * a.heads * T * HD;
+    const int8_t* qg = a.qkv + (int64_t)bh * T * HD;
+    const int8_t* kg = qg + plane;
+    unsigned* lut = reinterpret_cast<unsigned*>(psm);
+    int* rowmax = reinterpret_cast<int*>(psm + 1024) + 16 * wave;
+    float* rowfac = reinterpret_cast<float*>(psm + 1024 + 256) + 16 * wave;
+    char* ksm = psm + PROBS_HEAD_BYTES;                                // K image, nkt * 16 rows of 64 bytes (kswz)
+    unsigned char* slice = reinterpret_cast<unsigned char*>(ksm + nkt * 16 * HD) + wave * 16 * rs;
+
+    if constexpr (MODE == 0) lut[tid] = shiftexp_int(-tid, a.x0, 15);
+    // ---- K: 4 T chunks of 16 bytes, four per thread requested before the first is written; rows >= T are never consumed unmasked
+    for (int q0 = tid; q0 < 4 * T; q0 += 4 * NT) {
+        v4i kst[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int q = min(q0 + NT * i, 4 * T - 1);
+            kst[i] = *reinterpret_cast<const v4i*>(kg + (int64_t)(q >> 2) * HD + 16 * (q & 3));
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int q = q0 + NT * i;
+            if (q < 4 * T) *reinterpret_cast<v4i*>(ksm + kswz(q >> 2, q & 3)) = kst[i];
+        }
+    }
+    __syncthreads();
+    const int qt = 4 * grp + wave;
+    if (16 * qt >= a.q_rows) return;          // no requested row in this wave's tile (the only workgroup barrier is behind it)
+    const int nrows = min(16, a.q_rows - 16 * qt);
+    const v4i qf = *reinterpret_cast<const v4i*>(qg + (int64_t)min(16 * qt + l15, T - 1) * HD + 16 * g);
+
+    // ---- pass 1: scores, requantised to u = k + 128, four keys to a dword of the slice; padding keys: byte 0, never the maximum
+    int umax = 0;
+    for (int kt = 0; kt < nkt; ++kt) {
+        const v4i kf = *reinterpret_cast<const v4i*>(ksm + kswz(16 * kt + l15, g));
+        v4i acc = {0, 0, 0, 0};
+        acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(kf, qf, acc, 0, 0, 0);
+        int u[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            u[r] = clamp_i32(requant_exact(acc[r], a.Ms), -128, 127) + 128;      // |S| <= 2^20: the float64 product is exact
+            u[r] = (16 * kt + 4 * g + r < T) ? u[r] : 0;
+            umax = max(umax, u[r]);
+        }
+        *reinterpret_cast<unsigned*>(slice + l15 * rs + 16 * kt + 4 * g) = low_bytes(u);
+    }
+    umax = rows_allmax_i32(umax);             // qmax + 128, over the four lanes of the query
+
+    // exp_int of a key from idx = qmax - k in [0, 255], as attention_long_kernel takes it
+    const int W = a.band_w;
+    auto table_row = [&](int um) -> const unsigned* { return MODE == 0 ? nullptr : a.table + (W ? um * W : um * 257); };
+    auto expo = [&](const unsigned* trow, int idx) -> unsigned {
+        if constexpr (MODE == 0) return lut[idx];
+        else return W ? trow[min(idx, W - 1)] : trow[-idx];
+    };
+
+    // ---- pass 2: the row sum and its factor, left in LDS for pass 3 (which walks the rows with all 64 lanes)
+    if constexpr (MODE != 2) {
+        const unsigned* trow = table_row(umax);
+        unsigned long long esum = 0;           // exp_int <= 2^27, 1025 keys: beyond 32 bits
+        for (int kt = 0; kt < nkt; ++kt) {
+            const unsigned word = *reinterpret_cast<const unsigned*>(slice + l15 * rs + 16 * kt + 4 * g);      // this lane's own store
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                esum += (16 * kt + 4 * g + r < T) ? expo(trow, umax - (int)((word >> (8 * r)) & 255u)) : 0u;
+        }
+        const float factor = shiftmax_factor(rows_allsum_u64(esum));
+        if (g == 0) rowfac[l15] = factor;
+    }
+    if (g == 0) rowmax[l15] = umax;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if constexpr (MODE == 2) {
+        // IBERTIntSoftmax: S = e.sum() in float32 in torch's order, factor = floor(2^32 / S) (ibert_modules.py:313); the half: pass 3
+        for (int it = 0; 2 * it < nrows; ++it) {
+            const int row = 2 * it + (lane >> 5);          // the second row of the last pair may lie behind nrows: computed, not written
+            const int um = rowmax[row];
+            const unsigned* trow = table_row(um);
+            const unsigned char* srow = slice + row * rs;
+            const float S = torch_rowsum_half([&](int i) { return __int_as_float((int)expo(trow, um - (int)srow[i])); }, T, lane);
+            if ((lane & 31) == 0) rowfac[row] = floorf(4294967296.0f / S) * 0.5f;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+
+    // ---- pass 3: p = floor(fl32(e * factor) / 2^24) (ivit_modules.py:175) = the top byte of the truncated product.  I-BERT:
+    // floor(fl32(e * factor) / 2^25) in [0, 128] (ibert_modules.py:314) from the halved factor, an exact scaling
+    uint8_t* obase = a.probs + ((int64_t)bh * a.q_rows + 16 * qt) * a.ldp;
+    const int nd = (T + 3) >> 2;
+    for (int row = 0; row < nrows; ++row) {
+        const int um = rowmax[row];
+        const float fac = rowfac[row];
+        const unsigned* trow = table_row(um);
+        const unsigned char* srow = slice + row * rs;
+        uint8_t* orow = obase + (int64_t)row * a.ldp;
+        for (int d = lane; d < nd; d += 64) {
+            const unsigned word = *reinterpret_cast<const unsigned*>(srow + 4 * d);
+            unsigned p[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const unsigned e = expo(trow, um - (int)((word >> (8 * r)) & 255u));
+                const float ev = MODE == 2 ? __int_as_float((int)e) : (float)e;
+                p[r] = (unsigned)(ev * fac);      // float32 product, <= 2^31
+            }
+            const unsigned w = top_bytes(p);
+            if (a.dwords && 4 * d + 3 < T) {
+                *reinterpret_cast<unsigned*>(orow + 4 * d) = w;
+            } else {
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (4 * d + r < T) orow[4 * d + r] = (uint8_t)(w >> (8 * r));
+            }
+        }
+    }
+}
+
 
 // ---- host side: every exported entry fills an AttnDesc and returns attention_launch(desc)
 enum AttnFamily {
@@ -1133,14 +1299,16 @@ enum AttnFamily {
     SHIFTMAX_LONG,    // attention_long_kernel MODE 0 / 1, 208 .. 1025 tokens
     IBERT_SHORT,      // attention_kernel MODE 3 / 4, 193 .. 207 tokens (the 13-tile form; the float32 row-sum order of rowsum.h)
     IBERT_LONG,       // attention_long_kernel MODE 2, 208 .. 1025 tokens
-    SHIFTMAX_CLS      // attention_cls_kernel, 1 .. 208 tokens
+    SHIFTMAX_CLS,     // attention_cls_kernel, 1 .. 208 tokens
+    SHIFTMAX_PROBS,   // attention_probs_kernel MODE 0 / 1, 1 .. 1025 tokens
+    IBERT_PROBS       // attention_probs_kernel MODE 2, 1 .. 1025 tokens
 };
 
 struct AttnDesc {     // never passed to a kernel
     const char* name;             // the called entry, for the messages
     AttnFamily family;
     const int8_t* qkv;            // cls: k
-    int8_t* out;
+    int8_t* out;                  // probs: the uint8 probabilities
     int batch, heads, tokens, head_dim;
     uint32_t m_s;
     int32_t e_s;
@@ -1153,7 +1321,8 @@ struct AttnDesc {     // never passed to a kernel
     int softmax_bits, out_blocks;
     ivit_stream_t stream;
     const int8_t *v, *q;          // cls only
-    int64_t ldo;                  // cls only
+    int64_t ldo;                  // cls; probs: ldp
+    int q_rows;                   // probs only
     double Ms, Mo;                // filled by attention_check
     int x0;
 };
@@ -1162,8 +1331,9 @@ struct AttnDesc {     // never passed to a kernel
 int attention_check(AttnDesc& d)
 {
     const char* fn = d.name;
-    const bool ibert = d.family == IBERT_SHORT || d.family == IBERT_LONG, cls = d.family == SHIFTMAX_CLS;
-    const bool lng = d.family == SHIFTMAX_LONG || d.family == IBERT_LONG;
+    const bool probs = d.family == SHIFTMAX_PROBS || d.family == IBERT_PROBS;
+    const bool ibert = d.family == IBERT_SHORT || d.family == IBERT_LONG || d.family == IBERT_PROBS, cls = d.family == SHIFTMAX_CLS;
+    const bool lng = d.family == SHIFTMAX_LONG || d.family == IBERT_LONG || (probs && d.tokens >= LONG_T_MIN);
     IVIT_REQUIRE(d.softmax_bits == 4 || d.softmax_bits == 8 || d.softmax_bits == 16, "%s: softmax_bits must be 4, 8 or 16", fn);
     const bool operands = d.qkv && d.out && (!ibert || d.table) && (!cls || (d.v && d.q));
     if (d.family == IBERT_SHORT) {
@@ -1172,16 +1342,19 @@ int attention_check(AttnDesc& d)
         IVIT_REQUIRE(operands, ibert ? "%s: bad operand (NULL qkv, out or table)" : "%s: NULL operand", fn);
         IVIT_REQUIRE(d.batch > 0 && d.heads > 0 && (int64_t)d.batch * d.heads < 2147483648ll, "%s: empty batch", fn);
     }
-    const int t_min = lng ? LONG_T_MIN : d.family == IBERT_SHORT ? 16 * (NKT - 1) + 1 : 1;
-    const int t_max = lng ? LONG_T_MAX : d.family == IBERT_SHORT ? KP - 1 : KP;
+    const int t_min = probs ? 1 : lng ? LONG_T_MIN : d.family == IBERT_SHORT ? 16 * (NKT - 1) + 1 : 1;
+    const int t_max = probs || lng ? LONG_T_MAX : d.family == IBERT_SHORT ? KP - 1 : KP;
     if (d.head_dim != HD || d.tokens < t_min || d.tokens > t_max) {
         ivit_set_error("%s: unsupported geometry head_dim=%d tokens=%d (need 64, %d..%d)", fn, d.head_dim, d.tokens, t_min, t_max);
         return IVIT_ERR_UNSUPPORTED;
     }
-    const bool aligned = ((uintptr_t)d.qkv % 16 == 0) && ((uintptr_t)d.out % 16 == 0) && (!ibert || (uintptr_t)d.table % 4 == 0) &&
+    // probs: the output may start on any byte (the kernel packs dwords where the rows allow it)
+    const bool aligned = ((uintptr_t)d.qkv % 16 == 0) && (probs || (uintptr_t)d.out % 16 == 0) && (!ibert || (uintptr_t)d.table % 4 == 0) &&
                          (!cls || (((uintptr_t)d.v % 16 == 0) && ((uintptr_t)d.q % 16 == 0) &&
                                    d.ldo >= (int64_t)d.heads * d.head_dim && d.ldo % 16 == 0));
     IVIT_REQUIRE(aligned, d.family == IBERT_SHORT ? "%s: misaligned operand" : "%s: misaligned operand (16-byte rows)", fn);
+    if (probs)
+        IVIT_REQUIRE(d.q_rows >= 1 && d.q_rows <= d.tokens && d.ldo >= d.tokens, "%s: q_rows must be in 1..tokens and ldp >= tokens", fn);
     if (!ibert) IVIT_REQUIRE(d.s_attn > 0.0f, "%s: scale must be positive", fn);
     IVIT_REQUIRE(d.out_blocks == 0 || (d.out_blocks == 1 && ((int64_t)d.batch * d.tokens + 15) * d.heads * d.head_dim < 2147483648ll),
                  "%s: bad output layout (block-layout buffers stay below 2 GiB)", fn);
@@ -1241,15 +1414,31 @@ const LongKernel LONG_KERNELS[3][2][5] = {
      {attention_long_kernel<0, false, 64, 768, 4>, attention_long_kernel<0, true, 64, 768, 4>, attention_long_kernel<1, false, 64, 768, 4>,
       nullptr, nullptr}}};
 const ClsKernel CLS_KERNELS[3] = {attention_cls_kernel<0>, attention_cls_kernel<1>, attention_cls_kernel<2>};   // [MODE]
+typedef void (*ProbsKernel)(ProbsArgs);
+const ProbsKernel PROBS_KERNELS[3] = {attention_probs_kernel<0>, attention_probs_kernel<1>, attention_probs_kernel<2>};   // [MODE]
 
 int attention_launch(AttnDesc d)
 {
     if (const int rc = attention_check(d)) return rc;
-    const bool ibert = d.family == IBERT_SHORT || d.family == IBERT_LONG;
+    const bool ibert = d.family == IBERT_SHORT || d.family == IBERT_LONG || d.family == IBERT_PROBS;
     const int pairs = d.batch * d.heads, pb16 = d.softmax_bits == 16, pbi = pb16 ? 1 : d.softmax_bits == 4 ? 2 : 0;
     // a power-of-two score multiplier (m = 2^k): the float32 requantisation of the RQ32 kernels is exact
     const bool ms_pow2 = d.m_s != 0 && (d.m_s & (d.m_s - 1)) == 0 && d.Ms >= 1e-30;
     hipStream_t st = ivit_stream(d.stream);
+    if (d.family == SHIFTMAX_PROBS || d.family == IBERT_PROBS) {
+        ProbsArgs a{};
+        a.qkv = d.qkv; a.probs = reinterpret_cast<uint8_t*>(d.out); a.ldp = d.ldo;
+        a.batch = d.batch; a.heads = d.heads; a.tokens = d.tokens; a.q_rows = d.q_rows;
+        a.Ms = d.Ms; a.x0 = d.x0;
+        a.table = static_cast<const unsigned*>(d.band_w ? d.band : d.table);
+        a.band_w = d.band_w;
+        a.groups = (((d.q_rows + 15) >> 4) + 3) >> 2;
+        a.dwords = (uintptr_t)d.out % 4 == 0 && d.ldo % 4 == 0;
+        IVIT_REQUIRE((int64_t)pairs * a.groups < 2147483648ll, "%s: too many workgroups", d.name);
+        hipLaunchKernelGGL(PROBS_KERNELS[ibert ? 2 : (d.band_w || d.table) ? 1 : 0], dim3(pairs * a.groups), dim3(NT),
+                           probs_lds_bytes(d.tokens), st, a);
+        IVIT_CHECK_LAUNCH(d.name);
+    }
     if (d.family == SHIFTMAX_CLS) {
         ClsArgs a{};
         a.k = d.qkv; a.v = d.v; a.q = d.q; a.out = d.out; a.ldo = d.ldo;
@@ -1313,8 +1502,8 @@ int attention_launch(AttnDesc d)
 
 }  // namespace
 
-// The eleven entries (contracts: include/ivit_hip.h).  Descriptor order: name, family, qkv, out, batch, heads, tokens, head_dim, m_s,
-// e_s, s_attn, m_o, e_o, table, band, band_w, softmax_bits, out_blocks, stream (cls: + v, q, ldo).
+// The thirteen entries (contracts: include/ivit_hip.h).  Descriptor order: name, family, qkv, out, batch, heads, tokens, head_dim, m_s,
+// e_s, s_attn, m_o, e_o, table, band, band_w, softmax_bits, out_blocks, stream (cls: + v, q, ldo; probs: + NULL, NULL, ldp, q_rows).
 IVIT_EXPORT int ivit_attention_cls_i8(const int8_t* k, const int8_t* v, const int8_t* q, int8_t* out, int64_t ldo, int batch,
                                       int heads, int tokens, int head_dim, uint32_t m_s, int32_t e_s, float s_attn, uint32_t m_o,
                                       int32_t e_o, const uint32_t* exp2d, const uint32_t* band, int band_w, ivit_stream_t stream)
@@ -1406,4 +1595,21 @@ IVIT_EXPORT int ivit_attention_fused_i8_ibert_long(const int8_t* qkv, int8_t* ou
 {
     return attention_launch({"ivit_attention_fused_i8_ibert_long", IBERT_LONG, qkv, out, batch, heads, tokens, head_dim, m_s, e_s, 0.0f,
                              m_o, e_o, table, band, band_w, 8, out_blocks, stream});
+}
+
+// the two probability entries have no output requantisation: m_o = 0 passes attention_check's bound
+IVIT_EXPORT int ivit_attention_probs_u8(const int8_t* qkv, uint8_t* probs, int64_t ldp, int batch, int heads, int tokens,
+                                        int head_dim, int q_rows, uint32_t m_s, int32_t e_s, float s_attn,
+                                        const uint32_t* exp2d, const uint32_t* band, int band_w, ivit_stream_t stream)
+{
+    return attention_launch({"ivit_attention_probs_u8", SHIFTMAX_PROBS, qkv, reinterpret_cast<int8_t*>(probs), batch, heads, tokens,
+                             head_dim, m_s, e_s, s_attn, 0, 0, exp2d, band, band_w, 8, 0, stream, nullptr, nullptr, ldp, q_rows});
+}
+
+IVIT_EXPORT int ivit_attention_probs_u8_ibert(const int8_t* qkv, uint8_t* probs, int64_t ldp, int batch, int heads, int tokens,
+                                              int head_dim, int q_rows, uint32_t m_s, int32_t e_s,
+                                              const float* table, const float* band, int band_w, ivit_stream_t stream)
+{
+    return attention_launch({"ivit_attention_probs_u8_ibert", IBERT_PROBS, qkv, reinterpret_cast<int8_t*>(probs), batch, heads, tokens,
+                             head_dim, m_s, e_s, 0.0f, 0, 0, table, band, band_w, 8, 0, stream, nullptr, nullptr, ldp, q_rows});
 }

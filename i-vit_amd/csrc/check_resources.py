@@ -90,6 +90,10 @@ def occupancy_rules(path, what):
             # attention_cls_kernel<MODE>: CLS_OCC = 3 workgroups of four waves per CU (its __launch_bounds__; DeiT-B at batch 256
             # is then one round); the 26 K / V chunks a lane requests up front must stay in registers: no scratch
             occ, need_no_scratch = 3, True
+        elif what == "attention" and "attention_probs_kernel" in name:
+            # attention_probs_kernel<MODE>: rows live in LDS and every loop runs over the token count, so nothing may be indexed
+            # dynamically in registers: no scratch.  Its launcher assumes no number of resident workgroups
+            occ, need_no_scratch = 1, True
         elif what == "attention":
             m = re.search(r"attention_kernelILi(\d+)ELi(\d+)ELi(\d+)ELb([01])E", name)
             if not m:

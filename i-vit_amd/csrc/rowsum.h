@@ -52,6 +52,54 @@ IVIT_DEV float torch_rowsum(F elem, int n, int lane)
     return fin;
 }
 
+// torch_rowsum for TWO rows at a time, one per half of the wave (lanes 0 .. 31 and 32 .. 63): elem(i) is the element of the calling
+// lane's own row.  The same order for any n -- the scalar form below 8 elements, the 32 interleaved partials with the cascade
+// above -- so a caller needs no lane pattern per row length (attention.hip attention_probs_kernel: rows of 1 .. 1025 exponents in
+// LDS).  Whole wave calls it with the same n; every lane of a half gets its row's sum.
+template <class F>
+IVIT_DEV float torch_rowsum_half(F elem, int n, int lane)
+{
+    const int hl = lane & 31, hb = lane & 32;
+    if (n < 8) {   // scalar_inner_sum: four scalar accumulators, every lane on its own
+        float ps[4] = {0.f, 0.f, 0.f, 0.f};
+        const int size_ilp = n >> 2;
+        for (int i = 0; i < size_ilp; ++i)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) ps[k] += elem(i * 4 + k);
+        for (int i = size_ilp * 4; i < n; ++i) ps[0] += elem(i);
+#pragma unroll
+        for (int k = 1; k < 4; ++k) ps[0] += ps[k];
+        return ps[0];
+    }
+    const int vec_size = n >> 3, size_ilp = vec_size >> 2;
+    float acc0 = 0.f, acc1 = 0.f, acc2 = 0.f, acc3 = 0.f;
+    {
+        int lg = 0;
+        while ((1 << lg) < size_ilp) ++lg;
+        const int lp = max(4, lg / 4), step = 1 << lp, mask = step - 1;
+        int i = 0;
+        while (i + step <= size_ilp) {
+            for (int j = 0; j < step; ++j, ++i) acc0 += elem(i * 32 + hl);
+            acc1 += acc0; acc0 = 0.f;
+            if ((i & (mask << lp)) == 0) {
+                acc2 += acc1; acc1 = 0.f;
+                if ((i & (mask << (2 * lp))) == 0) { acc3 += acc2; acc2 = 0.f; }
+            }
+        }
+        for (; i < size_ilp; ++i) acc0 += elem(i * 32 + hl);
+        acc0 += acc1; acc0 += acc2; acc0 += acc3;
+    }
+    if (hl < 8)
+        for (int i = size_ilp * 4; i < vec_size; ++i) acc0 += elem(i * 8 + hl);
+    const float p1 = __shfl(acc0, hb | ((hl + 8) & 31)), p2 = __shfl(acc0, hb | ((hl + 16) & 31)), p3 = __shfl(acc0, hb | ((hl + 24) & 31));
+    const float v = ((acc0 + p1) + p2) + p3;
+    float fin = 0.f;
+    for (int i = vec_size * 8; i < n; ++i) fin += elem(i);
+#pragma unroll
+    for (int l = 0; l < 8; ++l) fin += __shfl(v, hb | l);
+    return fin;
+}
+
 // The same sum when the reduced dimension is NOT the contiguous one of the tensor (a transposed view, e.g. the Swin patch embedding:
 // layers_quant.py:198 hands `x.flatten(2).transpose(1, 2)` through an elementwise QuantAct, which keeps the strides, to the
 // LayerNorm's x_int.mean(axis=2)).  ATen then takes vectorized_outer_sum: every output column (an index of the contiguous

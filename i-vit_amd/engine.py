@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .engine_common import EngineBase, _np, attention, attention_spec, block_copy, frag_copy, layernorm
+from .engine_common import EngineBase, _np, attention, attention_probs, attention_spec, block_copy, frag_copy, layernorm
 from .prepare import dyadic, dyadic1, f32, pad_head, quant_sym, requant_host
 from .topk import TOPK_MAX
 
@@ -365,9 +365,29 @@ class IntViTEngine(EngineBase):
         self._gemm_res(ws["c_f1"], 4 * C, blk["fc2"], ws["c_x"], blk["res2"], ws["c_y"], B, st)
         return ws["c_y"]
 
-    def _forward(self, images: torch.Tensor, taps: dict | None = None, topk=None, cls_tail: bool = False):
+    def attention_maps(self, images: torch.Tensor, layers=None, rows: str = "cls"):
+        """The integer softmax probabilities of the selected blocks -> ({layer: uint8 [B, H, R, T]}, scale 2^-7): R = 1 (rows="cls":
+        the class token's attention over every token) or R = T (rows="all": the full map).  layers: block indices (None: every
+        block).  The ordinary eager forward runs -- its logits stay in the workspace as after forward() -- and behind the qkv GEMM
+        of each selected block one more launch (engine_common.attention_probs) writes the P that the fused attention kernel
+        multiplies with V into a fresh tensor.  8-bit softmax output only; not part of taps, of the graph replays or of cls_tail."""
+        if self.softmax_bits != 8:
+            raise ValueError(f"attention_maps: the softmax output is {self.softmax_bits} bits wide (the probability kernel writes 8-bit "
+                             "probabilities only)")
+        if rows not in ("cls", "all"):
+            raise ValueError(f"rows={rows!r}: 'cls' (the class token's row) or 'all' (the full map)")
+        layers = range(self.D) if layers is None else [int(i) for i in layers]
+        if any(not 0 <= i < self.D for i in layers):
+            raise ValueError(f"layers {list(layers)}: block indices in 0..{self.D - 1}")
+        B, R = images.shape[0], 1 if rows == "cls" else self.T
+        maps = {i: torch.empty(B, self.H, R, self.T, dtype=torch.uint8, device=self.dev) for i in layers}
+        self._forward(images, maps=maps)
+        return maps, 2.0 ** -7
+
+    def _forward(self, images: torch.Tensor, taps: dict | None = None, topk=None, cls_tail: bool = False, maps: dict | None = None):
         """forward; topk = (k, targets, hits): the classifier launch is the top-k selection (forward_topk).
         cls_tail: the last block through _cls_block (cls_tail_ok engines, no taps).
+        maps: {block index: uint8 [B, H, R, T]} to fill with the softmax probabilities of those blocks (attention_maps).
         stream_bits = 4: the 8-bit dataflow; the six stream QuantActs clamp to [-8, 7] (the `_bits` entries), attention is the
         "wide" form with softmax_bits.
         stream_bits = 16: the same dataflow with an int16 residual stream.  The patch GEMM, the embedding assembly and the
@@ -430,6 +450,8 @@ class IntViTEngine(EngineBase):
             _lib.call("ivit_gemm_i8_requant_qkv_ex", _lib.ptr(ws["h"]), C, qw, q["K"], _lib.ptr(q["b"]),
                       _lib.ptr(q["m"]), _lib.ptr(q["e"]), _lib.ptr(ws["qkv"]), T, H, hd, M, 3 * C, C, qlay | int(a_ln), st)
             tap(p + "attn.qkv_headmajor", ws["qkv"], (3, B, H, T, hd))
+            if maps is not None and i in maps:
+                attention_probs(blk["attn"], self.family, ws["qkv"], maps[i], B, H, T, hd, maps[i].shape[2], st)
             attention(blk["attn"], self.family, ws["qkv"], ws["ao"], B, H, T, hd, st, blocks=a_at,
                       softmax_bits=self.softmax_bits if self.stream_bits != 8 else None)
             tap(p + "attn.qact2", ws["ao"], (B, T, C), a_at)

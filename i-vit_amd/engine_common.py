@@ -1,6 +1,7 @@
 """Host code shared by the fused engines (engine.IntViTEngine, swin_engine.IntSwinEngine) and the module path
 (quantization_utils/lazy.py), written once per operator: the GEMM weight copies (block_copy, frag_copy); the LayerNorm constants
-and their launcher (ln_spec, layernorm); the ViT attention constants and their launcher (attention_spec, attention); the GELU
+and their launcher (ln_spec, layernorm); the ViT attention constants and their launchers (attention_spec, attention,
+attention_probs: the probabilities alone); the GELU
 table of both families (gelu_lut); what the two engines share as classes (EngineBase).  Window attention's pair
 (window_attention_spec, window_attention) lives in swin_engine.py; the scalar dyadic pair is prepare.dyadic1."""
 from __future__ import annotations
@@ -180,6 +181,19 @@ def attention(a, family, qkv, out, B, H, T, hd, st, blocks=False, softmax_bits=N
     else:
         _lib.call(name, p(qkv), p(out), B, H, T, hd, a["ms"][0], a["ms"][1], a["s_attn"], a["mo"][0], a["mo"][1], p(a["exp2d"]),
                   p(a["band"]), a["band_w"], *sm, int(blocks), st)
+
+
+def attention_probs(a, family, qkv, probs, B, H, T, hd, q_rows, st):
+    """The softmax probabilities of an attention_spec `a` on head-major qkv [3, B, H, T, hd] -> probs uint8 [B, H, q_rows, T]
+    (dense), scale 2^-7: the P that attention()'s kernel multiplies with V, for the first q_rows queries of every (image, head).
+    One launch; any T in 1 .. 1025 for both families (8-bit softmax output only)."""
+    p = _lib.ptr
+    if family == "ibert":
+        _lib.call("ivit_attention_probs_u8_ibert", p(qkv), p(probs), T, B, H, T, hd, q_rows, a["ms"][0], a["ms"][1],
+                  p(a["ib_table"]), p(a["band"]), a["band_w"], st)
+    else:
+        _lib.call("ivit_attention_probs_u8", p(qkv), p(probs), T, B, H, T, hd, q_rows, a["ms"][0], a["ms"][1], a["s_attn"],
+                  p(a["exp2d"]), p(a["band"]), a["band_w"], st)
 
 
 # ----------------------------------------------------------------------------------------------------------- GELU

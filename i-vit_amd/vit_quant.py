@@ -256,6 +256,49 @@ class VisionTransformer(EngineDispatch, ModuleGraph, nn.Module):
             x, _ = self.head(x, s)
         return x.to_float(boundary=True) if isinstance(x, lazy.QT) else x
 
+    def attention_maps(self, x, layers=None, rows="cls"):
+        """The integer softmax probabilities of the selected blocks -> ({layer: uint8 [B, H, R, T]}, scale 2^-7); R = 1 for
+        rows="cls" (the class token's attention), R = T for rows="all"; layers: block indices (None: every block).
+        Where forward() takes the fused engine this is IntViTEngine.attention_maps: the eager engine forward plus one launch per
+        selected block.  Otherwise the modules are called one by one as the reference's forward calls them, with forward hooks on
+        the selected int_softmax modules, and their float output is converted back to its integers: the reference's own tensor, at
+        the module path's speed.  8-bit softmax output only."""
+        if rows not in ("cls", "all"):
+            raise ValueError(f"rows={rows!r}: 'cls' (the class token's row) or 'all' (the full map)")
+        layers = list(range(self.depth)) if layers is None else [int(i) for i in layers]
+        if any(not 0 <= i < self.depth for i in layers):
+            raise ValueError(f"layers {layers}: block indices in 0..{self.depth - 1}")
+        bits = int(getattr(self.blocks[0].attn.int_softmax, "output_bit", 8))
+        if bits != 8:          # on either path, and before an engine is built for it
+            raise ValueError(f"attention_maps: the softmax output is {bits} bits wide (8-bit probabilities only)")
+        if self.takes_engine(x):
+            return self.engine(x.shape[0]).attention_maps(x.contiguous().float(), layers, rows)
+        maps, handles = {}, []
+
+        def hook(i):
+            def record(mod, args, out):
+                p, s = out
+                if isinstance(p, lazy.QT):
+                    p = p.to_float()
+                q = torch.round(p / s)
+                assert bool((q * s == p).all()) and bool((q >= 0).all()) and bool((q <= 128).all()), \
+                    f"blocks.{i}.attn.int_softmax: the output is not an integer in [0, 128] times its scale"
+                maps[i] = (q[:, :, :1] if rows == "cls" else q).to(torch.uint8).contiguous()
+            return record
+
+        for i in layers:
+            handles.append(self.blocks[i].attn.int_softmax.register_forward_hook(hook(i)))
+        try:
+            with torch.no_grad():
+                if not self.is_frozen():
+                    self.invalidate_engine()
+                f, s = self.forward_features(x)
+                self.head(f, s)
+        finally:
+            for h in handles:
+                h.remove()
+        return {i: maps[i] for i in layers}, 2.0 ** -7
+
 
 def _factory(embed_dim, depth, num_heads, name):
     def make(pretrained=False, **kwargs):

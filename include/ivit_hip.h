@@ -785,6 +785,30 @@ int ivit_attention_fused_i8_ibert_wide(const int8_t* qkv, int8_t* out, int batch
 int ivit_attention_fused_i8_ibert_long(const int8_t* qkv, int8_t* out, int batch, int heads, int tokens, int head_dim,
                                        uint32_t m_s, int32_t e_s, uint32_t m_o, int32_t e_o, const float* table,
                                        const float* band, int band_w, int out_blocks, ivit_stream_t stream);
+/* ---- attention maps: the probabilities P that the fused attention entries multiply with V, written to memory ----------
+ * qkv: the head-major [3, batch, heads, tokens, 64] int8 of the fused entries (16-byte aligned); V is not read.
+ * probs: [batch][heads][q_rows][ldp] uint8, ldp >= tokens, any alignment (rows are stored as packed dwords when probs and ldp are
+ *   multiples of four, byte by byte otherwise).  Row r of an (image, head) holds the probabilities of query r over the keys
+ *   0 .. tokens - 1 at scale 2^-7; bytes tokens .. ldp - 1 of a row are not written.  q_rows in 1 .. tokens: 1 = the class
+ *   token's row alone, tokens = the full map; only the 16-query tiles that hold a requested row are computed.
+ * Arithmetic: exactly that of the fused entries with an 8-bit softmax output.
+ *  - ivit_attention_probs_u8 (Shiftmax, ivit_modules.py:150-175): scores requantised by (m_s, e_s) and clamped to int8; exp_int from
+ *    the power-of-two table (exp2d = NULL, band_w = 0), the band table or the full [256][256] table as
+ *    ivit_attention_fused_i8_compat_band takes them; exact row sum, factor, p = (e * factor) >> 24 in [0, 127].
+ *  - ivit_attention_probs_u8_ibert (IBERTIntSoftmax, ibert_modules.py:303-314): e from the (row max, q) table of
+ *    ivit_ibert_softmax_build_table or its band form; row sum in float32 in torch's CPU reduction order for ANY row length (the
+ *    scalar form below 8 keys, 32 interleaved partials with the cascade above); factor = floor(2^32 / S),
+ *    p = floor(fl32(e * factor) / 2^25) in [0, 128] -- 128 for a one-hot row, hence the unsigned output.
+ * tokens 1 .. 1025 in both families, head_dim 64.  Errors: IVIT_ERR_UNSUPPORTED for head_dim != 64 or tokens outside 1..1025;
+ * IVIT_ERR_INVALID for a NULL qkv / probs (I-BERT: table), q_rows outside 1..tokens, ldp < tokens, a misaligned qkv or table, a bad
+ * band width, a score multiplier >= 2048, s_attn <= 0 or x0 outside [-4096, -1], and below 208 tokens a Shiftmax row sum that
+ * could pass 32 bits (the bound of the fused short-row entries).  Nothing is written on an error. */
+int ivit_attention_probs_u8(const int8_t* qkv, uint8_t* probs, int64_t ldp, int batch, int heads, int tokens,
+                            int head_dim, int q_rows, uint32_t m_s, int32_t e_s, float s_attn,
+                            const uint32_t* exp2d, const uint32_t* band, int band_w, ivit_stream_t stream);
+int ivit_attention_probs_u8_ibert(const int8_t* qkv, uint8_t* probs, int64_t ldp, int batch, int heads, int tokens,
+                                  int head_dim, int q_rows, uint32_t m_s, int32_t e_s,
+                                  const float* table, const float* band, int band_w, ivit_stream_t stream);
 int ivit_ibert_layernorm_i8(const int8_t* x, int64_t ldx, int rows, int C, float s_in, const float* bias_int, const float* s_out,
                             float shift_pow2, const uint32_t* m, const int32_t* e, int8_t* out, int64_t ldo, int out_blocks,
                             ivit_stream_t stream);
