@@ -136,6 +136,11 @@ SIGNATURES = {
     "ivit_jpeg_workspace": [vp, i64, vp, vp, ci, vp, vp],
     "ivit_jpeg_decode_host": [vp, i64, vp, i64],
     "ivit_jpeg_decode_u8": [vp, vp, ci, i64, i64, i64, vp, i64, vp, vp, vp],
+    # feature maps (include/ivit_hip.h, end)
+    "ivit_tokens_to_nchw_i8_f32": [vp, i64, ci, ci, ci, ci, ci, f32, vp, vp],
+    "ivit_tokens_to_nchw_i16_f32": [vp, i64, ci, ci, ci, ci, ci, f32, vp, vp],
+    "ivit_tokens_to_nchw_i8": [vp, i64, ci, ci, ci, ci, ci, vp, vp],
+    "ivit_tokens_to_nchw_i16": [vp, i64, ci, ci, ci, ci, ci, vp, vp],
 }
 
 

@@ -12,7 +12,7 @@ change that breaks the budget must fail the build here, on the CPU, not on the G
 wait without spilling.  csrc/check_isa.py checks the emitted instruction stream for exactly that; the bit-exact GEMM tests on the
 GPU remain the proof of the result.
 
-Second use (`check_resources.py <remarks> attention|rowops|swin`): the occupancy the launchers of attention.hip / rowops.hip / swin.hip assume
+Second use (`check_resources.py <remarks> attention|rowops|swin|calib|features`): the occupancy the launchers of those files assume
 when they size their grids (occupancy_rules below)."""
 import re
 import sys
@@ -107,6 +107,12 @@ def occupancy_rules(path, what):
             if "weight_quant_rows_kernel" not in name and "bias_quant_kernel" not in name:
                 continue
             occ, need_no_scratch = 1, True
+        elif what == "features":
+            # tokens_to_nchw_kernel<TI, TO, VB>: up to 32 loaded pieces per thread are indexed by constants only: no scratch; four
+            # workgroups of four waves per CU fit beside their LDS tiles (the launcher assumes no more than that they are resident together)
+            if "tokens_to_nchw_kernel" not in name:
+                continue
+            occ, need_no_scratch = 4, True
         elif what == "swin":
             if (m := re.search(r"window_attention_kernelILi(\d+)ELb([01])ELi(\d+)E", name)):
                 # window_attention_kernel<SM, RQ32, NKT>: = its __launch_bounds__.  NKT 4 (2..64 tokens): four workgroups per CU;

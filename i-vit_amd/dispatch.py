@@ -114,3 +114,38 @@ class EngineDispatch:
     def ranges(self):
         return {n: (float(m.x_min.reshape(-1)[0]), float(m.x_max.reshape(-1)[0]))
                 for n, m in self.named_modules() if isinstance(m, QuantAct)}
+
+    def _hooked_intermediates(self, x, sites, integers):
+        """forward_intermediates off the engine: the modules are called one by one as the reference's forward calls them, with a
+        forward hook on each selected module.  sites = {key: (module, its name, the QuantAct whose output it returns, t0, (H, W))};
+        the hooked (x [B, t0 + H * W, C], s) is checked to be integers of that QuantAct's width times s, its first t0 tokens are
+        dropped and the rest goes to [B, C, H, W].  -> {key: (map, scale)}; the hooks are removed in any case."""
+        got, handles = {}, []
+
+        def hook(key, name, qact, t0, hw):
+            def record(mod, args, out):
+                v, s = out
+                s = s.reshape(-1)
+                assert s.numel() == 1 and s.dtype == torch.float32, f"{name}: a per-tensor float32 scale"
+                bits = int(qact.activation_bit)
+                q = torch.round(v / s)
+                assert bool((q * s == v).all()) and bool((q >= -2 ** (bits - 1)).all()) and bool((q < 2 ** (bits - 1)).all()), \
+                    f"{name}: the output is not a {bits}-bit integer times its scale"
+                B, C = v.shape[0], v.shape[-1]
+                assert v.shape[1] == t0 + hw[0] * hw[1], f"{name}: {v.shape[1]} tokens"
+                keep = (q.to(torch.int16 if bits > 8 else torch.int8) if integers else v)[:, t0:]
+                got[key] = (keep.permute(0, 2, 1).reshape(B, C, *hw).contiguous(), float(s[0]))
+            return record
+
+        for key, (mod, name, qact, t0, hw) in sites.items():
+            handles.append(mod.register_forward_hook(hook(key, name, qact, t0, hw)))
+        try:
+            with torch.no_grad():
+                if not self.is_frozen():
+                    self.invalidate_engine()
+                f, s = self.forward_features(x)
+                self.head(f, s)
+        finally:
+            for h in handles:
+                h.remove()
+        return got

@@ -27,7 +27,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .engine_common import EngineBase, _np, attention, attention_probs, attention_spec, block_copy, frag_copy, layernorm
+from .engine_common import (EngineBase, _np, attention, attention_probs, attention_spec, block_copy, frag_copy, intermediate_indices,
+                            layernorm, tokens_to_nchw)
 from .prepare import dyadic, dyadic1, f32, pad_head, quant_sym, requant_host
 from .topk import TOPK_MAX
 
@@ -172,6 +173,7 @@ class IntViTEngine(EngineBase):
             s_b4 = s(p + "qact4", sb)
             blk["res2"] = dyadic1(s_m2, s_b4) + dyadic1(s_b2, s_b4)
             s_x = s_b4
+            blk["s_out"] = float(s_b4)      # the float32 act_scaling_factor of blocks.i.qact4 (forward_intermediates)
             self.blocks.append(blk)
 
         # ---- tail
@@ -384,10 +386,28 @@ class IntViTEngine(EngineBase):
         self._forward(images, maps=maps)
         return maps, 2.0 ** -7
 
-    def _forward(self, images: torch.Tensor, taps: dict | None = None, topk=None, cls_tail: bool = False, maps: dict | None = None):
+    def forward_intermediates(self, images: torch.Tensor, indices=None, integers: bool = False):
+        """The residual stream behind the selected blocks as feature maps -> (maps, scales): maps = {index: float32 [B, C, G, G]},
+        the tensor blocks.i.qact4 returns in the reference (integers times its scale) without the class token, channels first;
+        integers=True: the integers themselves (int8; int16 on the 16-bit stream).  scales = {index: float}, the float32
+        act_scaling_factor of blocks.i.qact4.  indices: block indices (None: every block); ValueError for one out of range or
+        repeated, before anything is launched.  The ordinary eager forward runs -- its logits stay in the workspace as after
+        forward() -- and behind the second residual GEMM of each selected block one more launch (engine_common.tokens_to_nchw)
+        writes the stream into a fresh tensor.  Not part of taps, of the graph replays or of cls_tail (which never computes the
+        last block's stream)."""
+        idx = intermediate_indices(indices, self.D, "block")
+        B, G = images.shape[0], self.IMG // self.P
+        dt = torch.float32 if not integers else torch.int16 if self.stream_bits == 16 else torch.int8
+        feats = {i: torch.empty(B, self.C, G, G, dtype=dt, device=self.dev) for i in idx}
+        self._forward(images, feats=feats)
+        return feats, {i: self.blocks[i]["s_out"] for i in idx}
+
+    def _forward(self, images: torch.Tensor, taps: dict | None = None, topk=None, cls_tail: bool = False, maps: dict | None = None,
+                 feats: dict | None = None):
         """forward; topk = (k, targets, hits): the classifier launch is the top-k selection (forward_topk).
         cls_tail: the last block through _cls_block (cls_tail_ok engines, no taps).
         maps: {block index: uint8 [B, H, R, T]} to fill with the softmax probabilities of those blocks (attention_maps).
+        feats: {block index: [B, C, G, G]} to fill with the stream behind those blocks, class token dropped (forward_intermediates).
         stream_bits = 4: the 8-bit dataflow; the six stream QuantActs clamp to [-8, 7] (the `_bits` entries), attention is the
         "wide" form with softmax_bits.
         stream_bits = 16: the same dataflow with an int16 residual stream.  The patch GEMM, the embedding assembly and the
@@ -479,6 +499,8 @@ class IntViTEngine(EngineBase):
             tap(p + "mlp.qact1", g_buf, (B, T, 4 * C), a_ge)
             self._gemm_res(g_buf, 4 * C, blk["fc2"], x2, blk["res2"], x, M, st, blocks=blk_l, a_blocks=a_ge)
             tap(p + "qact4", x, (B, T, C))
+            if feats is not None and i in feats:
+                tokens_to_nchw(x, C, B, T, 1, T - 1, C, blk["s_out"], feats[i], st)
         # final LayerNorm is row-wise and only the cls row is consumed (vit_quant.py:302-304); the int16 kernels want dense rows
         if wide:
             ws["cls16"][:B].copy_(x.view(-1, T, C)[:B, 0])

@@ -2,7 +2,8 @@
 (quantization_utils/lazy.py), written once per operator: the GEMM weight copies (block_copy, frag_copy); the LayerNorm constants
 and their launcher (ln_spec, layernorm); the ViT attention constants and their launchers (attention_spec, attention,
 attention_probs: the probabilities alone); the GELU
-table of both families (gelu_lut); what the two engines share as classes (EngineBase).  Window attention's pair
+table of both families (gelu_lut); the feature-map launcher and its index check (tokens_to_nchw, intermediate_indices); what the
+two engines share as classes (EngineBase).  Window attention's pair
 (window_attention_spec, window_attention) lives in swin_engine.py; the scalar dyadic pair is prepare.dyadic1."""
 from __future__ import annotations
 
@@ -214,6 +215,28 @@ def gelu_lut(family, s_g, s_m1, upload, device, st):
     t = phi_tables(s_g)
     _lib.call("ivit_shiftgelu_build_lut_ex", float(s_g), mg, eg, _lib.ptr(None if t is None else upload(t[0])), _lib.ptr(lut), st)
     return lut, t is not None
+
+
+# ----------------------------------------------------------------------------------------------------------- feature maps
+def tokens_to_nchw(x, ldx, B, T_all, t0, T, C, scale, out, st):
+    """Tokens t0 .. t0 + T - 1 of a token-major integer stream x (int8 / int16, element (b, t, c) at (b * T_all + t) * ldx + c) ->
+    out, dense [B, C, T] (a [B, C, H, W] tensor): float32 out = q * scale in one float32 multiplication, or -- an out of x's own
+    dtype -- the integers.  One launch (ivit_tokens_to_nchw_*, csrc/features.hip)."""
+    name = {(torch.int8, torch.float32): "ivit_tokens_to_nchw_i8_f32", (torch.int16, torch.float32): "ivit_tokens_to_nchw_i16_f32",
+            (torch.int8, torch.int8): "ivit_tokens_to_nchw_i8", (torch.int16, torch.int16): "ivit_tokens_to_nchw_i16"}[(x.dtype, out.dtype)]
+    assert out.is_contiguous() and out.numel() == B * C * T
+    if out.dtype == torch.float32:
+        _lib.call(name, _lib.ptr(x), ldx, B, T_all, t0, T, C, float(scale), _lib.ptr(out), st)
+    else:
+        _lib.call(name, _lib.ptr(x), ldx, B, T_all, t0, T, C, _lib.ptr(out), st)
+
+
+def intermediate_indices(indices, n, what):
+    """forward_intermediates' `indices` (None: all of 0 .. n - 1) as a list; ValueError for one out of range or repeated"""
+    idx = list(range(n)) if indices is None else [int(i) for i in indices]
+    if any(not 0 <= i < n for i in idx) or len(set(idx)) != len(idx):
+        raise ValueError(f"indices {idx}: distinct {what} indices in 0..{n - 1}")
+    return idx
 
 
 # ----------------------------------------------------------------------------------------------------------- engines

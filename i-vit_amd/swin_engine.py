@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .engine_common import EngineBase, _np, block_copy, frag_copy, layernorm
+from .engine_common import EngineBase, _np, block_copy, frag_copy, intermediate_indices, layernorm, tokens_to_nchw
 from .prepare import (LayerNormParams, LinearParams, dyadic, dyadic1, f32, ibert_saturated_exp, ibert_window_mask_ok, pad_head,
                       phi_is_identity, phi_table, quant_sym, requant_host, shiftexp_band, sym_scale, window_shiftexp_band)
 from .topk import TOPK_MAX
@@ -388,6 +388,7 @@ class IntSwinEngine(EngineBase):
                 blk["res2"] = dyadic1(s_m2, s_b4) + dyadic1(s_b2, s_b4)
                 s_x = s_b4
                 st["blocks"].append(blk)
+            st["s_out"] = float(s_x)      # the float32 act_scaling_factor of the stage's last qact4 (forward_intermediates)
             if li < len(self.depths) - 1:
                 p = f"layers.{li}.downsample."
                 s_d1 = s(p + "qact1")
@@ -481,8 +482,25 @@ class IntSwinEngine(EngineBase):
         intermediate integer tensors in the reference's layouts."""
         return self._forward(images, taps)
 
-    def _forward(self, images: torch.Tensor, taps: dict | None = None, topk=None):
-        """forward; topk = (k, targets, hits): the classifier launch is the top-k selection (forward_topk)"""
+    def forward_intermediates(self, images: torch.Tensor, indices=None, integers: bool = False):
+        """The residual stream behind the last block of the selected stages as feature maps -> (maps, scales): maps = {stage:
+        float32 [B, C_li, H_li, W_li]}, the tensor layers.li.blocks[-1].qact4 returns in the reference (integers times its scale,
+        before the patch merging), channels first; integers=True: the int16 integers themselves.  scales = {stage: float}, that
+        QuantAct's float32 act_scaling_factor.  indices: stage indices (None: every stage); ValueError for one out of range or
+        repeated, before anything is launched.  The ordinary eager forward runs (fused projection included) -- its logits stay in
+        the workspace as after forward() -- plus one launch per selected stage (engine_common.tokens_to_nchw).  Not part of taps
+        or of the graph replays."""
+        idx = intermediate_indices(indices, len(self.stages), "stage")
+        B = images.shape[0]
+        dt = torch.int16 if integers else torch.float32
+        feats = {li: torch.empty(B, self.stages[li]["C"], self.stages[li]["H"], self.stages[li]["W"], dtype=dt, device=self.dev)
+                 for li in idx}
+        self._forward(images, feats=feats)
+        return feats, {li: self.stages[li]["s_out"] for li in idx}
+
+    def _forward(self, images: torch.Tensor, taps: dict | None = None, topk=None, feats: dict | None = None):
+        """forward; topk = (k, targets, hits): the classifier launch is the top-k selection (forward_topk).
+        feats: {stage index: [B, C, H, W]} to fill with the stream behind the last block of those stages (forward_intermediates)"""
         assert images.is_cuda and images.dtype in (torch.float32, torch.uint8) and images.is_contiguous()
         B = images.shape[0]
         img = self.img_size
@@ -598,6 +616,8 @@ class IntSwinEngine(EngineBase):
                           _lib.ptr(f2["b"]), _lib.ptr(f2["m"]), _lib.ptr(f2["e"]), _lib.ptr(x2), C, r[0], r[1], r[2], r[3],
                           _lib.ptr(x), C, M, f2["N"], f2["K"], f2lay, st)
                 tap(p + "qact4", x, M, C)
+            if feats is not None and li in feats:
+                tokens_to_nchw(x, C, B, H * W, 0, H * W, C, stg["s_out"], feats[li], st)
             dn = stg["down"]
             if dn is not None:
                 p = f"layers.{li}.downsample."

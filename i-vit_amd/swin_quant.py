@@ -347,6 +347,25 @@ class SwinTransformer(EngineDispatch, ModuleGraph, nn.Module):
             x, _ = self.head(x, s)
         return x.to_float(boundary=True) if isinstance(x, lazy.QT) else x
 
+    def forward_intermediates(self, x, indices=None, integers=False):
+        """The residual stream behind the last block of the selected stages as feature maps -> (maps, scales): maps = {stage: float32
+        [B, C_li, H_li, W_li]}, what layers[li].blocks[-1] returns (its qact4: integers times its scale, before the patch merging),
+        channels first; integers=True: the int16 integers.  scales = {stage: float}, its float32 act_scaling_factor.  indices: stage
+        indices (None: every stage); ValueError for one out of range or repeated.
+        Where forward() takes the fused engine this is IntSwinEngine.forward_intermediates: the eager engine forward plus one launch
+        per selected stage.  Otherwise the modules are called one by one as the reference's forward calls them, with forward hooks on
+        those blocks: the reference's own tensor, at the module path's speed."""
+        from .engine_common import intermediate_indices
+        idx = intermediate_indices(indices, self.num_layers, "stage")
+        if self.takes_engine(x):
+            return self.engine(x.shape[0]).forward_intermediates(x.contiguous().float(), idx, integers)
+        sites = {}
+        for li in idx:
+            blk = self.layers[li].blocks[-1]
+            sites[li] = (blk, f"layers.{li}.blocks.{len(self.layers[li].blocks) - 1}", blk.qact4, 0, tuple(self.layers[li].input_resolution))
+        got = self._hooked_intermediates(x, sites, integers)
+        return {li: got[li][0] for li in idx}, {li: got[li][1] for li in idx}
+
 
 def _factory(embed_dim, depths, num_heads, name):
     def make(pretrained=False, quant=False, calibrate=False, cfg=None, **kwargs):

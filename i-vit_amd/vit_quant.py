@@ -299,6 +299,22 @@ class VisionTransformer(EngineDispatch, ModuleGraph, nn.Module):
                 h.remove()
         return {i: maps[i] for i in layers}, 2.0 ** -7
 
+    def forward_intermediates(self, x, indices=None, integers=False):
+        """The residual stream behind the selected blocks as feature maps -> (maps, scales): maps = {index: float32 [B, C, G, G]},
+        what blocks[i] returns (blocks.i.qact4: integers times its scale) without the class token, channels first; integers=True:
+        the integers (int8; int16 where that QuantAct is wider than 8 bits).  scales = {index: float}, its float32
+        act_scaling_factor.  indices: block indices (None: every block); ValueError for one out of range or repeated.
+        Where forward() takes the fused engine this is IntViTEngine.forward_intermediates: the eager engine forward plus one
+        launch per selected block.  Otherwise the modules are called one by one as the reference's forward calls them, with
+        forward hooks on the selected blocks: the reference's own tensor, at the module path's speed."""
+        from .engine_common import intermediate_indices
+        idx = intermediate_indices(indices, self.depth, "block")
+        if self.takes_engine(x):
+            return self.engine(x.shape[0]).forward_intermediates(x.contiguous().float(), idx, integers)
+        G = self.geometry[0] // self.geometry[1]
+        got = self._hooked_intermediates(x, {i: (self.blocks[i], f"blocks.{i}", self.blocks[i].qact4, 1, (G, G)) for i in idx}, integers)
+        return {i: got[i][0] for i in idx}, {i: got[i][1] for i in idx}
+
 
 def _factory(embed_dim, depth, num_heads, name):
     def make(pretrained=False, **kwargs):

@@ -886,6 +886,25 @@ int ivit_jpeg_decode_host(const uint8_t* data, int64_t nbytes, uint8_t* out, int
 int ivit_jpeg_decode_u8(const uint8_t* plan, const void* index, int batch, int64_t nsub, int64_t nblocks, int64_t max_pixels,
                         void* workspace, int64_t workspace_bytes, uint8_t* out, int32_t* errors, ivit_stream_t stream);
 
+/* ---- feature maps: a token-major integer stream as dense channel-major maps (forward_intermediates) -----------------------
+ * x: the residual stream of an engine, rows of ldx >= C elements: element (b, t, c) of the selection is
+ *   x[(b * T_all + t0 + t) * ldx + c], 0 <= t < T, t0 + T <= T_all (t0 = 1 drops the class token of a ViT).  Rows outside the
+ *   selection and elements C .. ldx - 1 of a row are not read.
+ * out: dense [B][C][T], out[(b * C + c) * T + t] -- NCHW once T is viewed as H x W.
+ *  - ivit_tokens_to_nchw_i8_f32 / _i16_f32: out = (float)q * s, ONE float32 multiplication (torch's q.float() * s bit for bit: the
+ *    tensor a QuantAct of the reference returns, quant_act_int * act_scaling_factor).
+ *  - ivit_tokens_to_nchw_i8 / _i16: out = q, the integers themselves.
+ * Any T >= 1 and C >= 1.  x is read with 16-, 8- or 4-byte loads when x and ldx * sizeof(element) are multiples of that size,
+ * element by element otherwise (and for the piece of a row that crosses channel C); every offset is 64-bit.  One launch.
+ * Errors: IVIT_ERR_INVALID for a NULL x or out, B, T or C below 1, t0 < 0, t0 + T > T_all, ldx < C, x or out not aligned to its
+ * element, or more than 2^31 - 1 tiles of 64 tokens x 128 source bytes.  Nothing is launched on an error. */
+int ivit_tokens_to_nchw_i8_f32(const int8_t* x, int64_t ldx, int B, int T_all, int t0, int T, int C, float s, float* out,
+                               ivit_stream_t stream);
+int ivit_tokens_to_nchw_i16_f32(const int16_t* x, int64_t ldx, int B, int T_all, int t0, int T, int C, float s, float* out,
+                                ivit_stream_t stream);
+int ivit_tokens_to_nchw_i8(const int8_t* x, int64_t ldx, int B, int T_all, int t0, int T, int C, int8_t* out, ivit_stream_t stream);
+int ivit_tokens_to_nchw_i16(const int16_t* x, int64_t ldx, int B, int T_all, int t0, int T, int C, int16_t* out, ivit_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
