@@ -15,8 +15,9 @@
 //   once per workgroup into LDS with its keys stored in exactly that byte order, so the "A" fragment is a single
 //   ds_read_b128.  Both LDS images are swizzled for conflict-free 16-lane-group reads.
 // Shiftmax's integer exponential depends only on (row max - k) in [0,255]: tabulated once per workgroup in LDS
-// (256 x u32) with the reference's arithmetic (shiftexp_int); the row sum is an exact u32 sum rounded once to
-// float32 (= the reference's float32 sum whenever that is exact).
+// (256 x u32) with the reference's arithmetic (shiftexp_int); the row sum is an exact u32 sum, which below 2^24 IS the
+// reference's float32 sum; a row that reaches 2^24 takes its float32 sum in the order of torch's CPU kernel instead
+// (attn_parts.h SHIFTMAX_ORDER_SUM, torch_rowsum_tiles), behind one wave-uniform branch per query tile.
 #include "common.h"
 #include "rowsum.h"
 
@@ -232,7 +233,7 @@ __global__ __launch_bounds__(NT, OCC) void attention_kernel(AttnArgs a)
                     const int nk = s[kt][r];
                     unsigned e = slice[min(nk + rmax, W - 1)];     // the 1000 sentinel of the padding keys clamps, too
                     if (GENT || kt == NKT - 1) e = (nk == 1000) ? 0u : e;
-                    s[kt][r] = (int)e;
+                    s[kt][r] = __float_as_int((float)e);     // float32 value of the exponent, as MODE 0 keeps it: what the product below takes
                     esum += e;
                 }
             __builtin_amdgcn_wave_barrier();    // every lane has read its slice before the next tile overwrites it
@@ -326,7 +327,7 @@ __global__ __launch_bounds__(NT, OCC) void attention_kernel(AttnArgs a)
                     const int nk = s[kt][r];
                     unsigned e = row2d[-min(nk, 128)];
                     if (GENT || kt == NKT - 1) e = (nk == 1000) ? 0u : e;
-                    s[kt][r] = (int)e;
+                    s[kt][r] = __float_as_int((float)e);
                     esum += e;
                 }
         } else
@@ -352,12 +353,19 @@ __global__ __launch_bounds__(NT, OCC) void attention_kernel(AttnArgs a)
                 s[kt][r] = (int)ef;       // float32 bit pattern of the exponent
                 esum += e;
             }
-        constexpr bool ef_is_float = MODE == 0 || MODE >= 3;
+        // every mode has left the exponents in s[][] as float32 bit patterns
         float factor;
         if constexpr (MODE >= 3) {
             factor = floorf(4294967296.0f / __int_as_float((int)esum));        // ibert_modules.py:313
         } else {
-            factor = shiftmax_factor(rows_allsum_u32(esum));
+            const unsigned tot = rows_allsum_u32(esum);
+            factor = shiftmax_factor(tot);
+            // a row whose exact sum reaches 2^24: the reference's float32 sum depends on torch's order of additions (attn_parts.h).
+            // Wave-uniform and rare (no row of the model fixtures gets here); the other rows of the tile keep their factor.
+            if (__builtin_expect(__builtin_amdgcn_ballot_w64(tot >= SHIFTMAX_ORDER_SUM) != 0, 0)) {
+                const float S = torch_rowsum_tiles<NKT>(s, [](int v) { return __int_as_float(v); }, T);
+                factor = tot >= SHIFTMAX_ORDER_SUM ? shiftmax_factor(S) : factor;
+            }
         }
         if constexpr (PB == 4) factor *= 0.0625f;      // the last shift is 2^(31 - 4 + 1) (:175; I-BERT :313-314): see below
 
@@ -393,7 +401,7 @@ __global__ __launch_bounds__(NT, OCC) void attention_kernel(AttnArgs a)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const int kt2 = 4 * ks + t < NKT ? 4 * ks + t : 0;
-                        const float ev = ef_is_float ? __int_as_float(s[kt2][r]) : (float)(unsigned)s[kt2][r];
+                        const float ev = __int_as_float(s[kt2][r]);
                         pf[t][r] = (IVIT_LAB && (a.abl & 4)) ? 1.0f : ev * factor24;     // lab bit 2: no products
                     }
                 unsigned w0 = 0, w1 = 0, w2 = 0, w3 = 0;
@@ -442,7 +450,7 @@ __global__ __launch_bounds__(NT, OCC) void attention_kernel(AttnArgs a)
                     unsigned p[4];
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        const float ev = ef_is_float ? __int_as_float(s[4 * ks + t][r]) : (float)(unsigned)s[4 * ks + t][r];
+                        const float ev = __int_as_float(s[4 * ks + t][r]);
                         if constexpr (MODE >= 3) {
                             p[r] = (unsigned)(ev * factor_h);
                             any_u |= p[r];
@@ -479,7 +487,7 @@ __global__ __launch_bounds__(NT, OCC) void attention_kernel(AttnArgs a)
                         if (4 * ks + t < NKT) {
 #pragma unroll
                             for (int r = 0; r < 4; ++r) {
-                                const float ev = ef_is_float ? __int_as_float(s[4 * ks + t][r]) : (float)(unsigned)s[4 * ks + t][r];
+                                const float ev = __int_as_float(s[4 * ks + t][r]);
                                 const unsigned u = (unsigned)(ev * (MODE >= 3 ? factor_h : factor));
                                 w |= plane_a_byte(u, r);
                             }
@@ -727,16 +735,20 @@ __global__ __launch_bounds__(NTH, 1) void attention_long_kernel(LongArgs a)
             else return W ? trow[min((int)idx, W - 1)] : trow[-(int)idx];
         };
 
-        float factor;
-        if constexpr (MODE == 2) {
-            // ---- pass 2 (I-BERT): S = e.sum() in float32 in torch's order (rowsum.h torch_rowsum; attention_kernel MODE 3 is the same
-            // for T < 208).  V = T >> 3 vectors of 8, I = V >> 2 = T >> 5 interleaved steps of 32 keys: partial j = key % 32 takes keys
-            // j + 32 i, i < I, in groups of 16 steps (each group summed from zero, the group sums added up, the remainder's sum
-            // added last); I <= 32, so the cascade never passes its second level.  With key = 16 kt + 4 g + r a lane owns the whole
-            // sequence of its eight partials (hi = kt & 1, r), step kt >> 1: key tiles 0 .. 2 I - 1.  The at most 31 keys behind them
-            // (key tiles 2 I and 2 I + 1: up to three vectors of 8 that join partials 0 .. 7, then the scalar tail) are exchanged
-            // among the four lanes of the query together with the partials, and every lane finishes the sum alike.  Padding keys
-            // and absent tiles are +0.0f, which changes no sum of non-negative terms: the selections below are by value.
+        // ---- the row's float32 sum in torch's order (rowsum.h torch_rowsum; attention_kernel MODE 3 is the same for T < 208): what
+        // IBERTIntSoftmax's e.sum() is for every row, and Shiftmax's exp_int.sum() for the rows whose exact sum reaches 2^24
+        // (attn_parts.h SHIFTMAX_ORDER_SUM).  V = T >> 3 vectors of 8, I = V >> 2 = T >> 5 interleaved steps of 32 keys: partial
+        // j = key % 32 takes keys j + 32 i, i < I, in groups of 16 steps (each group summed from zero, the group sums added up, the
+        // remainder's sum added last); I <= 32, so the cascade never passes its second level.  With key = 16 kt + 4 g + r a lane owns
+        // the whole sequence of its eight partials (hi = kt & 1, r), step kt >> 1: key tiles 0 .. 2 I - 1.  The at most 31 keys behind
+        // them (key tiles 2 I and 2 I + 1) go to torch_rowsum_finish (attn_parts.h) together with the partials.  Padding keys and
+        // absent tiles are +0.0f, which changes no sum of non-negative terms: the selections below are by value.
+        auto expf_of = [&](unsigned idx) -> float {
+            if constexpr (MODE == 0) return lutf[idx];
+            else if constexpr (MODE == 2) return __int_as_float((int)expo(idx));
+            else return (float)expo(idx);
+        };
+        auto torch_order_sum = [&]() -> float {
             int I2 = (T >> 5) << 1;                    // key tiles of the interleaved part; nf is I2 or I2 + 1
             asm volatile("" : "+s"(I2));               // opaque per query tile, as nf: no hoisted masks
             float p0[2][4], p1[2][4], t0[4], t1[4];
@@ -748,7 +760,7 @@ __global__ __launch_bounds__(NTH, 1) void attention_long_kernel(LongArgs a)
                     const unsigned dk = rep - sc[kt];
                     float e[4];
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) e[r] = __int_as_float((int)expo((dk >> (8 * r)) & 255u));
+                    for (int r = 0; r < 4; ++r) e[r] = expf_of((dk >> (8 * r)) & 255u);
                     if (kt < I2) {
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
@@ -771,63 +783,24 @@ __global__ __launch_bounds__(NTH, 1) void attention_long_kernel(LongArgs a)
                 const unsigned dk = rep - sl;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const float e = r < vr ? __int_as_float((int)expo((dk >> (8 * r)) & 255u)) : 0.0f;
+                    const float e = r < vr ? expf_of((dk >> (8 * r)) & 255u) : 0.0f;
                     if (nf == I2) t0[r] = e;
                     else t1[r] = e;
                 }
             }
-            // partials 0 .. 7 (hi = 0 of the lanes g = 0, 1) take the vectors behind the interleaved part: vector 0 = this lane's own
-            // keys of tile I2, vector 1 = those of lane g + 2, vector 2 = its own of tile I2 + 1; then
-            // v_l = ((P_l + P_{l+8}) + P_{l+16}) + P_{l+24}, l = 4 g + r: P_{l+8}, P_{l+24} are lane g + 2's.  v_permlane32_swap of a
-            // value with itself: .y = the value of lane + 32 in the lanes below 32 (the other lanes' results are not used)
-            auto upper = [&](float x) -> float {
-                const unsigned xb = (unsigned)__float_as_int(x);
-                const v2u h = __builtin_amdgcn_permlane32_swap(xb, xb, false, false);
-                return __int_as_float((int)h.y);
-            };
-            const int nx = (T >> 3) - 2 * I2;          // 0 .. 3 vectors of 8 behind the interleaved part
-            float vl[4];
+            float P[2][4];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                float P = p0[0][r] + p1[0][r];         // the remainder's sum plus the groups' total
-                P += nx > 0 ? t0[r] : 0.0f;
-                P += nx > 1 ? upper(t0[r]) : 0.0f;
-                P += nx > 2 ? t1[r] : 0.0f;
-                vl[r] = ((P + upper(p0[0][r] + p1[0][r])) + (p0[1][r] + p1[1][r])) + upper(p0[1][r] + p1[1][r]);
-            }
-            // scalar tail: keys 8 V .. T - 1 (at most 7, in the half tile behind the last vector) in order, first into the final
-            // accumulator; then v_0 .. v_7
-            float fin = 0.0f;
-            {
-                const bool odd = nx & 1, second = nx >= 2;
-                float lo[4], hi[4];                    // the tail's half tile: lanes g' = 2 (nx & 1) and + 1
+            for (int hi = 0; hi < 2; ++hi)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    float G[4];
-                    gather4(second ? t1[r] : t0[r], G);
-                    lo[r] = odd ? G[2] : G[0];
-                    hi[r] = odd ? G[3] : G[1];
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) fin += lo[r];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) fin += hi[r];
-                float v0[4], v1[4];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    float G[4];
-                    gather4(vl[r], G);
-                    v0[r] = G[0];
-                    v1[r] = G[1];
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) fin += v0[r];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) fin += v1[r];
-            }
+                for (int r = 0; r < 4; ++r) P[hi][r] = p0[hi][r] + p1[hi][r];      // the remainder's sum plus the groups' total
+            return torch_rowsum_finish(P, t0, t1, T);
+        };
+        float factor;
+        if constexpr (MODE == 2) {
+            const float fin = torch_order_sum();        // ---- pass 2 (I-BERT): S = e.sum() (ibert_modules.py:311)
             factor = floorf(4294967296.0f / fin) * 0.5f;     // ibert_modules.py:313; the half: see prob_word
         } else {
-            // ---- pass 2: Shiftmax row sum (ivit_modules.py:171), exact, rounded once to float32
+            // ---- pass 2: Shiftmax row sum (ivit_modules.py:171): the exact integer sum; in torch's order where it reaches 2^24
             unsigned long long esum = 0;
             unsigned sum16 = 0;
 #pragma unroll
@@ -847,7 +820,12 @@ __global__ __launch_bounds__(NTH, 1) void attention_long_kernel(LongArgs a)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) sum16 += r < vr ? expo((dk >> (8 * r)) & 255u) : 0u;
             }
-            factor = shiftmax_factor(rows_allsum_u64(esum + sum16));
+            const unsigned long long tot = rows_allsum_u64(esum + sum16);
+            factor = shiftmax_factor(tot);
+            if (__builtin_amdgcn_ballot_w64(tot >= SHIFTMAX_ORDER_SUM) != 0) {      // wave-uniform, rare: some row of the tile
+                const float S = torch_order_sum();
+                factor = tot >= SHIFTMAX_ORDER_SUM ? shiftmax_factor(S) : factor;
+            }
             if constexpr (PB == 4) factor *= 0.0625f;    // p = floor(fl32(e * factor) / 2^28) < 8: an exact scaling, as in attention_kernel
         }
 
@@ -1041,6 +1019,7 @@ template <int MODE>
 __global__ __launch_bounds__(NT, CLS_OCC) void attention_cls_kernel(ClsArgs a)
 {
     __shared__ unsigned lut[256];
+    __shared__ float order_row[CLS_WAVES][KP];      // a row whose sum reaches 2^24 (below)
     const int tid = threadIdx.x, lane = tid & 63;
     if constexpr (MODE == 0) {
         lut[tid] = shiftexp_int(-tid, a.x0, 15);
@@ -1092,7 +1071,17 @@ __global__ __launch_bounds__(NT, CLS_OCC) void attention_cls_kernel(ClsArgs a)
         esum += c4 == 0 ? e : 0u;                     // the four lanes of a quad hold the same key
     }
     esum = (unsigned)lanes_allsum_i32<64>((int)esum);
-    const float factor = shiftmax_factor(esum);
+    float factor = shiftmax_factor(esum);
+    if (esum >= SHIFTMAX_ORDER_SUM) {      // wave-uniform, rare: the float32 sum in torch's order (attn_parts.h), the row passed through LDS
+        float* erow = order_row[tid >> 6];
+#pragma unroll
+        for (int i = 0; i < CLS_NCH; ++i)
+            if (c4 == 0) erow[(lane >> 2) + 16 * i] = (float)ev[i];      // key < KP; 0 for a padding key
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        factor = shiftmax_factor(torch_rowsum([&](int i) { return erow[i]; }, T, lane));
+    }
 
     // ---- O = P . V over this lane's chunks
     int acc[16];
@@ -1136,7 +1125,7 @@ __global__ __launch_bounds__(NT, CLS_OCC) void attention_cls_kernel(ClsArgs a)
 //      wave's LDS slice [16 queries][16 * ceil(T / 16) + pad] -- no row lives in registers, so one form serves 1 .. 1025 tokens;
 //      the row maximum over the four lanes of a query
 //   2. the row sum.  Shiftmax: exact integer sum of exp_int over the lane's own keys, u64 (attention_long_kernel pass 2), then the
-//      float32 factor.  I-BERT: float32 in torch's CPU order by torch_rowsum_half (rowsum.h), two rows at a time, the exponents
+//      float32 factor; rows whose sum reaches 2^24 take the I-BERT route below afterwards.  I-BERT: float32 in torch's CPU order by torch_rowsum_half (rowsum.h), two rows at a time, the exponents
 //      looked up from the slice's bytes -- the order is the general one, not a lane pattern per token count
 //   3. row by row, lane d takes the dword of keys 4 d .. 4 d + 3: exponent again from the table, p = floor(fl32(e * factor) / 2^24)
 //      (I-BERT: the halved factor, p in [0, 128]), packed (top_bytes), stored as a dword where every row of probs starts on one,
@@ -1230,6 +1219,7 @@ __global__ __launch_bounds__(NT) void attention_probs_kernel(ProbsArgs a)
     };
 
     // ---- pass 2: the row sum and its factor, left in LDS for pass 3 (which walks the rows with all 64 lanes)
+    unsigned order_rows = 0;      // Shiftmax: the rows whose exact sum reaches 2^24 (wave-uniform)
     if constexpr (MODE != 2) {
         const unsigned* trow = table_row(umax);
         unsigned long long esum = 0;           // exp_int <= 2^27, 1025 keys: beyond 32 bits
@@ -1239,8 +1229,9 @@ __global__ __launch_bounds__(NT) void attention_probs_kernel(ProbsArgs a)
             for (int r = 0; r < 4; ++r)
                 esum += (16 * kt + 4 * g + r < T) ? expo(trow, umax - (int)((word >> (8 * r)) & 255u)) : 0u;
         }
-        const float factor = shiftmax_factor(rows_allsum_u64(esum));
-        if (g == 0) rowfac[l15] = factor;
+        const unsigned long long tot = rows_allsum_u64(esum);
+        if (g == 0) rowfac[l15] = shiftmax_factor(tot);
+        order_rows = (unsigned)__builtin_amdgcn_ballot_w64(tot >= SHIFTMAX_ORDER_SUM) & 0xffffu;      // bit r: query r of the tile
     }
     if (g == 0) rowmax[l15] = umax;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -1255,6 +1246,21 @@ __global__ __launch_bounds__(NT) void attention_probs_kernel(ProbsArgs a)
             const unsigned char* srow = slice + row * rs;
             const float S = torch_rowsum_half([&](int i) { return __int_as_float((int)expo(trow, um - (int)srow[i])); }, T, lane);
             if ((lane & 31) == 0) rowfac[row] = floorf(4294967296.0f / S) * 0.5f;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    } else if (order_rows != 0) {
+        // Shiftmax rows whose exact sum reaches 2^24: the reference's float32 sum is the one of torch's order (attn_parts.h
+        // SHIFTMAX_ORDER_SUM), taken like the I-BERT sum above, a pair of rows at a time; the other rows keep their factor.  Rare.
+        for (int it = 0; 2 * it < 16; ++it) {
+            if (((order_rows >> (2 * it)) & 3u) == 0) continue;      // uniform
+            const int row = 2 * it + (lane >> 5);
+            const int um = rowmax[row];
+            const unsigned* trow = table_row(um);
+            const unsigned char* srow = slice + row * rs;
+            const float S = torch_rowsum_half([&](int i) { return (float)expo(trow, um - (int)srow[i]); }, T, lane);
+            if ((lane & 31) == 0 && ((order_rows >> row) & 1u)) rowfac[row] = shiftmax_factor(S);
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();

@@ -38,20 +38,19 @@ IVIT_DEV float shiftexp_lit(float d, float x0)
     return fmaxf(ex, 0.0f);
 }
 
-// ---- Shiftmax factor (ivit_modules.py:171-174) from the exact integer row sum, rounded once to float32 (= the reference's
-// float32 sum whenever that is exact)
-IVIT_DEV float shiftmax_factor(unsigned esum)
+// ---- Shiftmax factor (ivit_modules.py:171-174) from the row sum.  The reference's sum is a float32 sum of integers: below 2^24 it
+// is exact whatever the order, and the integer forms below give it (the exact integer sum converts without rounding).  From
+// SHIFTMAX_ORDER_SUM on, the reference's value is the one torch's CPU kernel reaches in ITS order of additions, every one rounded
+// (rowsum.h; tests/golden/shiftmax_bigsum_kat.npz holds rows where the exact sum rounded once gives another factor): a kernel
+// tests the exact sum against SHIFTMAX_ORDER_SUM and hands such rows' sum, taken in that order, to the float32 form.
+constexpr unsigned SHIFTMAX_ORDER_SUM = 1u << 24;
+IVIT_DEV float shiftmax_factor(float S)
 {
-    float S = (float)esum;                                     // exp_int.sum (:171)
     S = fminf(S, 2147483648.0f);                               // clamp_max_(2**31-1) in float32 (:173)
     return floorf((1.0f / S) * 2147483648.0f);                 // (:174)
 }
-IVIT_DEV float shiftmax_factor(unsigned long long esum)       // long rows: the sum passes 2^32 (1025 * 255 * 2^15)
-{
-    float S = (float)esum;
-    S = fminf(S, 2147483648.0f);
-    return floorf((1.0f / S) * 2147483648.0f);
-}
+IVIT_DEV float shiftmax_factor(unsigned esum) { return shiftmax_factor((float)esum); }                // exp_int.sum (:171) below 2^24
+IVIT_DEV float shiftmax_factor(unsigned long long esum) { return shiftmax_factor((float)esum); }      // long rows: the sum passes 2^32
 
 // ---- 8-bit probabilities: p = floor(fl32(e * factor) / 2^24) (:175) = the top byte of each product u, four gathered with two
 // byte permutes
@@ -97,6 +96,112 @@ IVIT_DEV void gather4(float x, float (&out)[4])
     out[1] = __int_as_float((int)a01.y);
     out[2] = __int_as_float((int)a23.x);
     out[3] = __int_as_float((int)a23.y);
+}
+
+// ---- torch's CPU float32 row sum (rowsum.h torch_rowsum) of a row of T >= 1 exponents spread over the four lanes of a query as the
+// fused kernels hold it: key = 16 kt + 4 g + r.  With V = T >> 3 vectors of 8 and I = V >> 2 = T >> 5 interleaved steps of 32 keys,
+// partial j = key % 32 takes keys j + 32 i, i < I: a lane owns the whole sequence of its eight partials (hi = kt & 1, r), which the
+// caller adds up in that order (cascade included) into P[hi][r].  The at most 31 keys behind them -- key tiles 2 I (t0[r]) and
+// 2 I + 1 (t1[r]): up to three vectors of 8 that join partials 0 .. 7, then the scalar tail -- are exchanged among the four lanes
+// together with the partials, and every lane finishes the sum alike.  Keys at or behind T and absent tiles must be +0.0f, which
+// changes no sum of non-negative terms.  Every lane of the wave calls it.
+IVIT_DEV float torch_rowsum_finish(const float (&P)[2][4], const float (&t0)[4], const float (&t1)[4], int T)
+{
+    if (T < 8) {       // scalar_inner_sum: four accumulators over keys 0 .. 7 = t0 of the lanes g = 0, 1
+        float x[8];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            float G[4];
+            gather4(t0[r], G);
+            x[r] = G[0];
+            x[4 + r] = G[1];
+        }
+        float ps0 = T >= 4 ? x[0] : 0.0f;
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+            ps0 += (i >= (T & 4) && i < T) ? x[i] : 0.0f;      // the keys behind the whole group of four (T >= 4) or all of them, in order
+        if (T >= 4) {
+            ps0 += x[1];
+            ps0 += x[2];
+            ps0 += x[3];
+        }
+        return ps0;
+    }
+    // partials 0 .. 7 (hi = 0 of the lanes g = 0, 1) take the vectors behind the interleaved part: vector 0 = this lane's own keys of
+    // tile 2 I, vector 1 = those of lane g + 2, vector 2 = its own of tile 2 I + 1; then v_l = ((P_l + P_{l+8}) + P_{l+16}) + P_{l+24},
+    // l = 4 g + r: P_{l+8}, P_{l+24} are lane g + 2's.  v_permlane32_swap of a value with itself: .y = the value of lane + 32 in the
+    // lanes below 32 (the other lanes' results are not used)
+    auto upper = [&](float x) -> float {
+        const unsigned xb = (unsigned)__float_as_int(x);
+        const v2u h = __builtin_amdgcn_permlane32_swap(xb, xb, false, false);
+        return __int_as_float((int)h.y);
+    };
+    const int nx = (T >> 3) - 4 * (T >> 5);    // 0 .. 3 vectors of 8 behind the interleaved part
+    float vl[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        float Q = P[0][r];
+        Q += nx > 0 ? t0[r] : 0.0f;
+        Q += nx > 1 ? upper(t0[r]) : 0.0f;
+        Q += nx > 2 ? t1[r] : 0.0f;
+        vl[r] = ((Q + upper(P[0][r])) + P[1][r]) + upper(P[1][r]);
+    }
+    // scalar tail: keys 8 V .. T - 1 (at most 7, in the half tile behind the last vector) in order, first into the final accumulator;
+    // then v_0 .. v_7
+    float fin = 0.0f;
+    const bool odd = nx & 1, second = nx >= 2;
+    float lo[4], hi[4];                        // the tail's half tile: lanes g' = 2 (nx & 1) and + 1
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        float G[4];
+        gather4(second ? t1[r] : t0[r], G);
+        lo[r] = odd ? G[2] : G[0];
+        hi[r] = odd ? G[3] : G[1];
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) fin += lo[r];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) fin += hi[r];
+    float v0[4], v1[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        float G[4];
+        gather4(vl[r], G);
+        v0[r] = G[0];
+        v1[r] = G[1];
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) fin += v0[r];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) fin += v1[r];
+    return fin;
+}
+
+// the same for a row that sits in registers as s[kt][r] (val(s[kt][r]) = the float32 exponent of key 16 kt + 4 g + r, +0.0f at and
+// behind T), NKT <= 31 key tiles: fewer than 16 interleaved steps, so the cascade never folds and partial (hi, r) is the plain
+// sequence of the tiles 2 m + hi, m < I.  I is a run-time value: the tiles are selected by value, never by a register index.
+template <int NKT, class VAL>
+IVIT_DEV float torch_rowsum_tiles(const int (&s)[NKT][4], VAL val, int T)
+{
+    static_assert(NKT <= 31, "the cascade of torch's sum folds after 16 steps of 32 keys");
+    const int I = T >> 5;
+    float P[2][4], t0[4], t1[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        P[0][r] = P[1][r] = t0[r] = t1[r] = 0.0f;
+#pragma unroll
+        for (int m = 0; 2 * m < NKT; ++m) {
+            const float e0 = val(s[2 * m][r]);
+            P[0][r] += m < I ? e0 : 0.0f;
+            t0[r] = m == I ? e0 : t0[r];
+            if (2 * m + 1 < NKT) {
+                const float e1 = val(s[2 * m + 1][r]);
+                P[1][r] += m < I ? e1 : 0.0f;
+                t1[r] = m == I ? e1 : t1[r];
+            }
+        }
+    }
+    return torch_rowsum_finish(P, t0, t1, T);
 }
 
 // ---- output tail: O^T = Vt . P^T requantised (attn.qact2) to int8, one accumulator element.

@@ -116,8 +116,8 @@ def occupancy_rules(path, what):
         elif what == "swin":
             if (m := re.search(r"window_attention_kernelILi(\d+)ELb([01])ELi(\d+)E", name)):
                 # window_attention_kernel<SM, RQ32, NKT>: = its __launch_bounds__.  NKT 4 (2..64 tokens): four workgroups per CU;
-                # NKT 9 (65..144 tokens): two, the 36 scores per lane stay in registers.  No scratch in either
-                occ, need_no_scratch = (4 if int(m.group(3)) == 4 else 2), True
+                # NKT 9 (65..144 tokens): three, the 36 scores per lane stay in registers.  No scratch in either
+                occ, need_no_scratch = (4 if int(m.group(3)) == 4 else 3), True
             elif "window_attention" in name:
                 print("check_resources: unknown window attention kernel", name)
                 return 1

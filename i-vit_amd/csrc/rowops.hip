@@ -1011,7 +1011,10 @@ __global__ __launch_bounds__(NT) void shiftmax_kernel(SmArgs<TX> a)
             unsigned hi = (unsigned)__shfl_xor((int)(sum >> 32), o);
             sum += ((unsigned long long)hi << 32) | lo;
         }
-        float S = (float)sum;                                     // :171 (RN24 of the exact sum)
+        float S = (float)sum;                                     // :171: exact below 2^24
+        // from 2^24 on the reference's float32 sum is the one torch's CPU kernel reaches in its order of additions (rowsum.h;
+        // tests/golden/shiftmax_bigsum_kat.npz).  Wave-uniform, rare.
+        if (sum >= (1ull << 24)) S = torch_rowsum([&](int i) { return (float)shiftexp_int((int)xr[i] - kmax, a.x0, 15); }, a.L, lane);
         S = fminf(S, 2147483648.0f);                              // :173
         const float factor = floorf((1.0f / S) * 2147483648.0f);  // :174
         for (int i = lane; i < a.L; i += 64) {

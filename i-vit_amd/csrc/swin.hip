@@ -612,7 +612,7 @@ __global__ __launch_bounds__(NT) void avgpool_kernel(const int8_t* x, int8_t* ou
 //   NKT 4: 2..64 tokens (windows up to 8x8, Swin at 224 px): a row of scores is 16 per lane, P.V one key step, kp = 64, four
 //          workgroups per CU.
 //   NKT 9: 65..144 tokens (9x9 .. 12x12, Swin at 384 px): 36 scores per lane (and the literal form's 36 float views) stay in
-//          registers at two workgroups per CU (<= 256 VGPRs), P.V up to 3 key steps, kp = 16 * ceil(T / 16).
+//          registers at three workgroups per CU (<= 168 VGPRs), P.V up to 3 key steps, kp = 16 * ceil(T / 16).
 //   The bias rows stay in global memory (L2): per score they are 2 bytes against the 16 of the score's 16x16x32 operand rows, and
 //   staging them in LDS would add a wave barrier per query tile for data each wave reads once.
 // ------------------------------------------------------------------------------------------------
@@ -669,6 +669,9 @@ constexpr int WBAND_PAD = 4;     // dwords: keeps the slices 16-byte aligned and
 // kp_long: the bias / region row stride of NKT 9 (NKT 4 folds the literal 64).  A kernel parameter of its own, not a field of
 // WinAttnArgs: as a field its scalar load merges with the neighbouring ones and the six NKT 9 forms lose the instruction sequence
 // they were measured with (HISTORY.md §9).
+// Occupancy: NKT 4 is compiled for four workgroups per CU, NKT 9 for three: the long form used 150-158 VGPRs and ran three per CU; with
+// the ordered-sum branch of the Shiftmax forms (attn_parts.h SHIFTMAX_ORDER_SUM) a bound of two let it grow to 171-177 and lose the
+// third workgroup, under a bound of three it stays at 165-168 without scratch (csrc/check_resources.py holds both).
 // float32 sum of e[0 .. n - 1], 2 <= n <= 144, in the order of torch's CPU sum kernel (rowsum.h torch_rowsum, restated for ONE row per
 // four lanes): with n / 8 <= 18 vectors the cascade never folds (its level step is 16 groups of four vectors), so partial p = key % 32
 // adds its n / 32 elements in turn, the vectors past the last whole group of four join partials 0..7, lane sum l is
@@ -713,8 +716,12 @@ IVIT_DEV float window_rowsum(const float* e, int n, int g)
     return fin;
 }
 
-template <int SM, bool RQ32, int NKT>
-__global__ __launch_bounds__(NT, NKT == 4 ? 4 : 2) void window_attention_kernel(WinAttnArgs a, int kp_long)
+// ORD (Shiftmax forms): the branch that gives a row whose exact sum reaches 2^24 its float32 sum in torch's order (attn_parts.h
+// SHIFTMAX_ORDER_SUM).  Its registers cost the power-of-two form of NKT 4 its fifth workgroup per CU (94 -> 118 VGPRs, 80.6 -> 87.1 us
+// per call at 8192 windows x 3 heads), so the launcher leaves it out (ORD false: the kernel as it was) where no row can get there:
+// an exponent is at most |x0| * 2^15, T of them stay below 2^24 while T * |x0| < 512 -- Swin-T's 49 keys up to |x0| = 10.
+template <int SM, bool RQ32, int NKT, bool ORD = true>
+__global__ __launch_bounds__(NT, NKT == 4 ? 4 : 3) void window_attention_kernel(WinAttnArgs a, int kp_long)
 {
     constexpr int NKS = (NKT + 3) / 4;               // P.V key steps of 64
     constexpr int VT_ROW = 64 * NKS;                 // Vt row: 64 key slots per step
@@ -902,7 +909,7 @@ __global__ __launch_bounds__(NT, NKT == 4 ? 4 : 2) void window_attention_kernel(
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const unsigned e = (s[kt][r] == -100000) ? 0u : (unsigned)shiftexp_lit(xv[kt][r] - xmax, x0f);      // :168
-                        s[kt][r] = (int)e;
+                        s[kt][r] = ORD ? __float_as_int((float)e) : (int)e;      // ORD: the float32 value the product below takes
                         esum += e;
                     }
             } else if constexpr (band) {
@@ -934,7 +941,7 @@ __global__ __launch_bounds__(NT, NKT == 4 ? 4 : 2) void window_attention_kernel(
                     for (int r = 0; r < 4; ++r) {
                         if constexpr (NKT > 4) ev[kt][r] = slice[min(rm - max(s[kt][r], -50000), W1)];
                         const unsigned e = (s[kt][r] == -100000) ? 0u : ev[kt][r];
-                        s[kt][r] = (int)e;
+                        s[kt][r] = ORD ? __float_as_int((float)e) : (int)e;      // ORD: the float32 value the product below takes
                         esum += e;
                     }
             } else {
@@ -951,13 +958,22 @@ __global__ __launch_bounds__(NT, NKT == 4 ? 4 : 2) void window_attention_kernel(
                         bool in_table = true;
                         if constexpr (NKT > 4) in_table = d <= a.ksat || a.band1;
                         if (s[kt][r] != -100000) e = in_table ? lut[min(d, a.ksat) & 255] : shiftexp_int(-d, a.x0, 15);
-                        s[kt][r] = (int)e;
+                        s[kt][r] = ORD ? __float_as_int((float)e) : (int)e;      // ORD: the float32 value the product below takes
                         esum += e;
                     }
             }
             float factor;
             if constexpr (ibert) factor = floorf(4294967296.0f / isum) * 0.5f;      // ibert_modules.py:313; the half: see below
-            else factor = shiftmax_factor(rows_allsum_u32(esum));
+            else {
+                const unsigned tot = rows_allsum_u32(esum);
+                factor = shiftmax_factor(tot);
+                // a row whose exact sum reaches 2^24: the reference's float32 sum is the one of torch's order (attn_parts.h
+                // SHIFTMAX_ORDER_SUM).  Wave-uniform and rare; the other rows of the tile keep their factor.
+                if (ORD && __builtin_expect(__builtin_amdgcn_ballot_w64(tot >= SHIFTMAX_ORDER_SUM) != 0, 0)) {
+                    const float S = torch_rowsum_tiles<NKT>(s, [](int v) { return __int_as_float(v); }, T);
+                    factor = tot >= SHIFTMAX_ORDER_SUM ? shiftmax_factor(S) : factor;
+                }
+            }
             // NKS 1: built in pk0 -- with element writes into an array of ONE vector the compiler unrolled the query-tile loop four times
             // (SM 1: 128 VGPRs and scratch)
             v4i pk[NKS], pk0;
@@ -975,8 +991,8 @@ __global__ __launch_bounds__(NT, NKT == 4 ? 4 : 2) void window_attention_kernel(
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
                             float pr;
-                            if constexpr (ibert) pr = __int_as_float(s[4 * ks + t][r]) * factor;
-                            else pr = (float)(unsigned)s[4 * ks + t][r] * factor;     // :175
+                            if constexpr (ibert || ORD) pr = __int_as_float(s[4 * ks + t][r]) * factor;     // :175; I-BERT :314
+                            else pr = (float)(unsigned)s[4 * ks + t][r] * factor;
                             if constexpr (ibert) any_u |= (unsigned)pr;
                             w |= ((((unsigned)pr) >> 24) & 0xffu) << (8 * r);
                         }
@@ -1345,7 +1361,15 @@ static int window_attention_launch(const int8_t* qkv, int8_t* out, int64_t ldo, 
     const dim3 grd(grid < 8192 ? grid : 8192), blk(NT);
     hipStream_t st = ivit_stream(stream);
     const int kp = 16 * ((tokens + 15) >> 4);
+    // no row of `tokens` exponents of at most |x0| * 2^15 reaches 2^24: the short Shiftmax forms then run without the ordered-sum branch
+    const bool order_sum_possible = (int64_t)tokens * -(int64_t)a.x0 >= 512;
     winattn_dispatch(ib_tab ? 3 : a.band ? 2 : a.phi ? 1 : 0, a.rq32 != 0, long_rows, [&](auto SM, auto RQ32, auto NKT) {
+        if constexpr (decltype(NKT)::value == 4 && decltype(SM)::value != 3) {
+            if (!order_sum_possible) {
+                hipLaunchKernelGGL((window_attention_kernel<SM.value, RQ32.value, NKT.value, false>), grd, blk, band_bytes, st, a, kp);
+                return;
+            }
+        }
         hipLaunchKernelGGL((window_attention_kernel<SM.value, RQ32.value, NKT.value>), grd, blk, band_bytes, st, a, kp);
     });
     if (ib_tab) IVIT_CHECK_LAUNCH("ivit_window_attention_i8_ibert");

@@ -794,7 +794,8 @@ int ivit_attention_fused_i8_ibert_long(const int8_t* qkv, int8_t* out, int batch
  * Arithmetic: exactly that of the fused entries with an 8-bit softmax output.
  *  - ivit_attention_probs_u8 (Shiftmax, ivit_modules.py:150-175): scores requantised by (m_s, e_s) and clamped to int8; exp_int from
  *    the power-of-two table (exp2d = NULL, band_w = 0), the band table or the full [256][256] table as
- *    ivit_attention_fused_i8_compat_band takes them; exact row sum, factor, p = (e * factor) >> 24 in [0, 127].
+ *    ivit_attention_fused_i8_compat_band takes them; the reference's float32 row sum (the exact integer sum below 2^24, the sum in
+ *    torch's CPU reduction order from there on, as in every Shiftmax entry), factor, p = (e * factor) >> 24 in [0, 127].
  *  - ivit_attention_probs_u8_ibert (IBERTIntSoftmax, ibert_modules.py:303-314): e from the (row max, q) table of
  *    ivit_ibert_softmax_build_table or its band form; row sum in float32 in torch's CPU reduction order for ANY row length (the
  *    scalar form below 8 keys, 32 interleaved partials with the cascade above); factor = floor(2^32 / S),

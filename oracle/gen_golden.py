@@ -977,6 +977,217 @@ def gen_calib_trace():
     np.savez_compressed(os.path.join(GOLD, "calib_trace.npz"), **out)
 
 
+BIGSUM_LENGTHS = (49, 144, 197, 208, 577, 1025)
+BIGSUM_SCALES = ((0.25, -4), (0.125, -8), (0.2113, -5), (0.11873, -9), (0.0571, -18))      # (s, x0): two pow2, three natural
+BIGSUM_SCALES_49 = ((0.0625, -16),)      # 49 keys reach 2^24 only from |x0| = 11 on: one more pow2 scale, for the window entries
+
+
+def _bigsum_boundary(smo, f):
+    """the two adjacent float32 S1 < S2 with factor(S1) = f and factor(S2) = f - 1"""
+    S = np.float32(2.0 ** 31 / f)
+    for _ in range(4):
+        S = np.nextafter(S, np.float32(0))
+    for _ in range(16):
+        S2 = np.nextafter(S, np.float32(np.inf))
+        if smo.factor_of(S) == f and smo.factor_of(S2) == f - 1:
+            return int(S), int(S2)
+        S = S2
+    return None
+
+
+def _bigsum_multiset(rng, E, T, lo, hi, force):
+    """distances from the row maximum, one per key, whose exponents E[dist] sum to a value in (lo, hi), as near the middle as
+    the far keys' small terms allow.  Most keys lie within 3 steps of the maximum; about 12-15 % (more where the target sum is
+    small) lie far below and make the fine adjustment.  force: a distance that at least a tenth of the near keys take."""
+    mid = (lo + hi) // 2
+    near = np.arange(4) if force is None else np.unique(np.append(np.arange(4), force))
+    n_far = max(3, int(round(T * rng.uniform(0.12, 0.15))))
+    e_near = float(np.mean(E[near]))
+    if (T - n_far) * e_near > mid:                                     # a small target: fewer near keys
+        n_far = T - int(mid / e_near)
+    n_near = T - n_far
+    if n_near < 1 or n_far < 3 or n_near * int(E[0]) + n_far * int(E[4]) < mid:
+        return None
+    d = rng.choice(near, size=n_near)
+    d[0] = 0                                                           # the row maximum itself
+    if force is not None:
+        d[1:1 + max(1, n_near // 10)] = force
+    # coarse: move near keys one step until what is left for the far keys is something they can make
+    want_lo, want_hi = n_far * 64, (n_far - 2) * int(E[4]) // 2 + 1
+    for _ in range(20 * T):
+        rest = mid - int(E[d].sum())
+        if want_lo <= rest <= want_hi:
+            break
+        i = int(rng.integers(1, n_near)) if n_near > 1 else 0
+        if force is not None and i < 1 + max(1, n_near // 10):
+            continue
+        if rest < want_lo and d[i] < 3:
+            d[i] += 1
+        elif rest > want_hi and d[i] > 0 and i > 0:
+            d[i] -= 1
+    rest = mid - int(E[d].sum())
+    if not want_lo <= rest <= want_hi:
+        return None
+    far_d = np.arange(4, len(E))
+    far = []
+    e_min = int(E[far_d].min())
+    for k in range(n_far - 2):
+        left = n_far - 1 - k                                           # keys still to come after this one; each adds e_min at least
+        room = rest - 3 * e_min * left
+        if left > 12:                                                  # the first: near the even share, with some spread
+            want = min(room, rest / (left + 1) * rng.uniform(0.6, 1.4))
+        else:                                                          # the last ten: the largest term that still fits
+            want = room
+        fits = far_d[E[far_d] <= max(want, e_min)]
+        j = int(fits[np.argmax(E[fits])])
+        far.append(j)
+        rest -= int(E[j])
+    pair = E[far_d][:, None] + E[far_d][None, :]                       # the last two: every pair of far distances
+    a, b = np.unravel_index(np.argmin(np.abs(pair - rest)), pair.shape)
+    far += [int(far_d[a]), int(far_d[b])]
+    d = np.concatenate([d, np.array(far)])
+    return d if lo < int(E[d].sum()) < hi else None
+
+
+def gen_shiftmax_bigsum():
+    """tests/golden/shiftmax_bigsum_kat.npz: IVITIntSoftmax on rows whose exponent sum reaches 2^24, where the float32 sum
+    (ivit_modules.py:171) depends on the order of torch's CPU kernel.  Stored per row: the int8 scores, the scale, output_bit,
+    the REFERENCE's output, the output that the exact sum rounded once would give, and the row's class (tests/shiftmax_order_ref.py:
+    a = order-free, b = the sums differ but not the outputs, c = the outputs differ).  Class (c) rows come from a seeded, directed
+    search: a near-flat multiset of scores tuned until its exact sum lies between the two float32 neighbours of a boundary
+    2^31 / f, then permuted until the two sums fall on either side of it."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import shiftmax_order_ref as smo
+    rng = np.random.default_rng(20261020)
+    t_start = time.time()
+    recs = {T: [] for T in BIGSUM_LENGTHS}                             # T -> [(q int8 [T], s, bits, cls, out_torch, out_exact)]
+
+    def take(T, q, s, bits, want, limit):
+        """classify the rows q [N, T]; keep up to `limit` rows of class `want` -> number kept"""
+        cls, ot, oe = smo.classify(q, s, bits)
+        idx = np.flatnonzero(cls == want)[:limit]
+        for i in idx:
+            recs[T].append((q[i].astype(np.int8), np.float32(s), bits, want, ot[i], oe[i]))
+        return len(idx)
+
+    notes = {}
+    for T in BIGSUM_LENGTHS:
+        for s, x0 in BIGSUM_SCALES + (BIGSUM_SCALES_49 if T == 49 else ()):
+            s = np.float32(s)
+            assert smo.x0_of(s) == x0
+            assert T > 208 or T * abs(x0) * 2 ** 15 < 2 ** 32           # the short entries' bound on the row sum
+            qmax = 127
+            E = smo.shiftexp(smo.phi_table(s)[::-1] - smo.phi_table(s)[qmax + 128], x0).astype(np.int64)   # E[dist], dist = 0 .. 255
+            s_hi = (T - 3) * int(E[0])
+            if s_hi < 1 << 24:
+                notes[f"T{T}_x0{x0}"] = "no row reaches 2^24"
+                continue
+            # ---- class (a): every key within a few steps of the maximum; (b): near-flat with far keys, as drawn
+            for bits in (8, 16):
+                for qm in (127, 120, 112, 96, 64, 33, 0):                # natural scales: a maximum whose neighbours phi leaves whole
+                    qa = (qm - rng.integers(0, 4, size=(64, T))).astype(np.int64)
+                    qa[:, 0] = qm
+                    if take(T, qa, s, bits, smo.CLASS_A, 2 if T == 49 else 1):
+                        break
+                qb = (qmax - rng.integers(0, 4, size=(256, T))).astype(np.int64)
+                far = rng.random(size=qb.shape) < 0.135
+                qb[far] = qmax - rng.integers(40, 256, size=int(far.sum()))
+                qb[:, 0] = qmax
+                take(T, qb, s, bits, smo.CLASS_B, 1)
+            # ---- class (c), directed: for a factor f, a multiset whose exact sum lies between the float32 neighbours of 2^31 / f
+            f_lo = max(2, int(np.ceil(2.0 ** 31 / s_hi)) + 1)
+            found = {8: 0, 16: 0}
+            fs = list(range(f_lo, 128))
+            rng.shuffle(fs)
+            # factors at which some near key's 8-bit output changes come first: they can give class (c) at 8 bits
+            d8 = {}
+            for f in fs:
+                chg = np.flatnonzero((E[:24] * f >> 24) != (E[:24] * (f - 1) >> 24))
+                if len(chg):
+                    d8[f] = int(chg[0])
+            fs.sort(key=lambda f: f not in d8)
+            for f in fs:
+                if found[16] >= 4 and (found[8] >= 2 or f not in d8):
+                    continue
+                if time.time() - t_start > 1500:
+                    break
+                bd = _bigsum_boundary(smo, f)
+                if bd is None:
+                    continue
+                for attempt in range(6):
+                    d = _bigsum_multiset(rng, E, T, bd[0], bd[1], d8.get(f) if attempt % 2 == 0 else None)
+                    if d is None:
+                        continue
+                    q = qmax - np.stack([rng.permutation(d) for _ in range(192)])    # the key order changes torch's sum only
+                    got = 0
+                    if found[8] < 2 and f in d8:
+                        got = take(T, q, s, 8, smo.CLASS_C, 1)
+                        found[8] += got
+                    if not got and found[16] < 4:
+                        found[16] += take(T, q, s, 16, smo.CLASS_C, 1)
+                    if found[16] >= 4 and (found[8] >= 2 or f not in d8):
+                        break
+            notes[f"T{T}_x0{x0}"] = f"class c: {found[16]} rows at 16 bits, {found[8]} at 8"
+            print(f"[bigsum] T={T} x0={x0}: {notes[f'T{T}_x0{x0}']}  ({time.time() - t_start:.0f} s)", flush=True)
+
+    # ---- the reference itself on every row; the restatement must agree with it, sum and output
+    out = {}
+    counts = {}
+    for T in BIGSUM_LENGTHS:
+        R = recs[T]
+        q = np.stack([r[0] for r in R])
+        sc = np.array([r[1] for r in R], np.float32)
+        bits = np.array([r[2] for r in R], np.int32)
+        cls = np.array([r[3] for r in R], np.uint8)
+        ot = np.stack([r[4] for r in R])
+        oe = np.stack([r[5] for r in R])
+        ref = np.empty_like(ot)
+        for s in np.unique(sc):
+            for b in (8, 16):
+                m = np.flatnonzero((sc == s) & (bits == b))
+                if not len(m):
+                    continue
+                sm = rq.IVITIntSoftmax(output_bit=b)
+                st = torch.tensor([s])
+                x = (torch.from_numpy(q[m].astype(np.float32))[None, None] * st).float()
+                ys, ss = sm(x, st)
+                ref[m] = torch.round(ys / ss).numpy().reshape(len(m), T).astype(np.int32)
+                xi = x / st
+                ex, _ = sm.int_exp_shift(xi - xi.max(dim=-1, keepdim=True)[0], st)
+                ef = smo.exponents(q[m], s)
+                assert np.array_equal(ex.numpy().reshape(len(m), T), ef)
+                St, Se, isum = smo.both_sums(ef)
+                assert np.array_equal(ex.sum(dim=-1).numpy().reshape(-1), St), "torch's sum is not the restated order"
+                assert np.all(isum >= 1 << 24)
+        assert np.array_equal(ref, ot), "the reference's output is not the restatement's"
+        for c in (smo.CLASS_A, smo.CLASS_B, smo.CLASS_C):
+            for b in (8, 16):
+                counts[f"T{T}_{smo.CLASS_NAMES[c]}{b}"] = int(((cls == c) & (bits == b)).sum())
+        pow2 = np.isin(sc, [np.float32(0.25), np.float32(0.125), np.float32(0.0625)])
+        if T >= 144:
+            assert ((cls == smo.CLASS_C) & (bits == 16) & pow2).sum() >= 4 and ((cls == smo.CLASS_C) & (bits == 16) & ~pow2).sum() >= 4, T
+            assert (cls == smo.CLASS_A).sum() >= 4 and (cls == smo.CLASS_B).sum() >= 4, T
+        else:
+            assert (cls == smo.CLASS_A).sum() >= 4, T
+            if not (cls != smo.CLASS_A).any():
+                notes[f"T{T}"] = "class (a) only: the search found no row here whose two sums differ"
+        assert np.all(np.any(ref != oe, axis=1) == (cls == smo.CLASS_C))
+        assert ref.min() >= 0 and ref.max() <= 32768 and np.abs(oe - ref).max() < 32768
+        out[f"q_{T}"], out[f"s_{T}"], out[f"bits_{T}"], out[f"cls_{T}"] = q, sc, bits.astype(np.uint8), cls
+        out[f"ref_{T}"] = ref.astype(np.uint16)                        # the reference's output
+        out[f"exact_minus_ref_{T}"] = (oe - ref).astype(np.int16)       # the exact-sum-rounded-once candidate, as a difference
+    n_c8 = sum(v for k, v in counts.items() if k.endswith("_c8"))
+    assert n_c8 >= 4, n_c8
+    out["lengths"] = np.array(BIGSUM_LENGTHS, np.int32)
+    out["meta"] = np.array(json.dumps(dict(seed=20261020, scales=[[float(np.float32(s)), x0] for s, x0 in BIGSUM_SCALES],
+                                           scales_49_only=[[float(np.float32(s)), x0] for s, x0 in BIGSUM_SCALES_49],
+                                           classes=dict(a=0, b=1, c=2), counts=counts, notes=notes, torch=torch.__version__)))
+    path = os.path.join(GOLD, "shiftmax_bigsum_kat.npz")
+    np.savez_compressed(path, **out)
+    assert os.path.getsize(path) < 300 * 1024, os.path.getsize(path)
+    print(f"shiftmax_bigsum_kat.npz written: {os.path.getsize(path)} bytes; {counts}")
+
+
 def gen_schema():
     """state_dict keys and shapes of the reference's DeiT and Swin models (the on-disk checkpoint format)"""
     out = {}
@@ -1011,6 +1222,8 @@ if __name__ == "__main__":
             gen_calib_trace()
         elif w == "schema":
             gen_schema()
+        elif w == "shiftmax_bigsum":
+            gen_shiftmax_bigsum()
         elif w in ("deit_tiny_ibert_natural", "deit_tiny_ibert_w16all"):
             gen_ibert_natural(w)
         elif w.endswith("_natural") and not w.startswith("swin"):
