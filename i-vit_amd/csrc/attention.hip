@@ -15,9 +15,10 @@
 //   once per workgroup into LDS with its keys stored in exactly that byte order, so the "A" fragment is a single
 //   ds_read_b128.  Both LDS images are swizzled for conflict-free 16-lane-group reads.
 // Shiftmax's integer exponential depends only on (row max - k) in [0,255]: tabulated once per workgroup in LDS
-// (256 x u32) with the reference's arithmetic (shiftexp_int); the row sum is an exact u32 sum, which below 2^24 IS the
-// reference's float32 sum; a row that reaches 2^24 takes its float32 sum in the order of torch's CPU kernel instead
-// (attn_parts.h SHIFTMAX_ORDER_SUM, torch_rowsum_tiles), behind one wave-uniform branch per query tile.
+// (256 x float32, every entry an integer that float32 holds exactly) with the reference's arithmetic (shiftexp_int), ONE gather per score; the
+// row sum is a float32 sum of the gathered values, which below 2^24 is exact and IS the reference's float32 sum (the natural-scale
+// forms keep an exact u32 sum of their u32 tables); a row that reaches 2^24 takes its float32 sum in the order of torch's CPU
+// kernel instead (attn_parts.h SHIFTMAX_ORDER_SUM, torch_rowsum_tiles), behind one wave-uniform branch per query tile.
 #include "common.h"
 #include "rowsum.h"
 
@@ -39,7 +40,11 @@ constexpr int VT_ROW = NKS * 64;       // 256 B per d row: one bank row, chunk j
 constexpr int K_BYTES = KP * HD;       // 13312
 constexpr int VT_BYTES = HD * VT_ROW;  // 16384
 constexpr int LUT_OFF = K_BYTES + VT_BYTES;
-constexpr int SMEM_BYTES = LUT_OFF + 2 * 256 * 4;   // exponent table as u32 (exact row sum) and as float32 (the product of :175)
+constexpr int SMEM_BYTES = LUT_OFF + 2 * 256 * 4;   // the natural-scale and I-BERT forms (tables elsewhere): K, V^T and 2 KB of slack, the footprint their occupancy was measured with
+// MODE 0: the exponent table as float32, the one value both the row sum and the product of :175 take (attn_parts.h
+// SHIFTMAX_ORDER_SUM).  Entry i on bank i % 32: the indices of a row cluster, and neighbouring indices never meet on a bank
+// (lane-interleaved copies of the table narrow each copy to fewer banks and measured MORE conflicts: DESIGN.md section 8)
+constexpr int SMEM0_BYTES = LUT_OFF + 256 * 4;
 
 #include "attn_parts.h"
 
@@ -100,7 +105,7 @@ __global__ __launch_bounds__(NT, OCC) void attention_kernel(AttnArgs a)
     static_assert(!RQ32 || (MODE == 0 && PB <= 8), "RQ32: Shiftmax with a power-of-two input scale, one plane of probabilities");
     constexpr int SOFF = RQ32 ? RQ_OFF : 0;       // offset the (negated) scores are carried with
     constexpr int PADK = SOFF + 1000;             // sentinel of the padding keys
-    __shared__ __attribute__((aligned(16))) char smem[SMEM_BYTES];
+    __shared__ __attribute__((aligned(16))) char smem[MODE == 0 ? SMEM0_BYTES : SMEM_BYTES];
     extern __shared__ __attribute__((aligned(16))) unsigned band_lds[];   // [4 waves][16 queries][band_w + BAND_PAD], compat only
     const int T = a.tokens;
     const int bh = blockIdx.x / a.parts, part = blockIdx.x - bh * a.parts;
@@ -112,12 +117,8 @@ __global__ __launch_bounds__(NT, OCC) void attention_kernel(AttnArgs a)
     const int8_t* kg = qg + plane;
     const int8_t* vg = qg + 2 * plane;
 
-    // ---- Shiftmax exponent table: lut[i] = int_exp_shift(-i), i = kmax - k in [0,255]
-    if constexpr (MODE < 3) {
-        const unsigned e0 = shiftexp_int(-tid, a.x0, 15);
-        reinterpret_cast<unsigned*>(smem + LUT_OFF)[tid] = e0;
-        reinterpret_cast<float*>(smem + LUT_OFF)[256 + tid] = (float)e0;   // same address + 1 KB: one more ds_read, one cvt fewer per score
-    }
+    // ---- Shiftmax exponent table: lut[i] = int_exp_shift(-i) as float32 (exact: attn_parts.h), i = kmax - k in [0,255]
+    if constexpr (MODE == 0) reinterpret_cast<float*>(smem + LUT_OFF)[tid] = (float)shiftexp_int(-tid, a.x0, 15);
 
     // ---- K tile [key][64]; rows >= T are never consumed unmasked.  ALL of a thread's K and V chunks are requested before the
     //      first is written to LDS (T <= 208: at most 4 K chunks and one V work item of 4 chunks per thread): one memory latency
@@ -168,7 +169,7 @@ __global__ __launch_bounds__(NT, OCC) void attention_kernel(AttnArgs a)
     }
     __syncthreads();
 
-    const unsigned* lut = reinterpret_cast<const unsigned*>(smem + LUT_OFF);
+    const float* lut = reinterpret_cast<const float*>(smem + LUT_OFF);
     const int nqt = (T + 15) >> 4;
 
     // 13 query tiles over 4 waves: one wave gets four tiles, the others three.  Which wave that is rotates with the
@@ -214,7 +215,8 @@ __global__ __launch_bounds__(NT, OCC) void attention_kernel(AttnArgs a)
         // ---- Shiftmax (ivit_modules.py:164-175): e = exp_int(k - max), sum, factor, e*factor >> 24
         // k - max is in [-255, 0] for every real key: the 256-entry table covers it without a clamp (the entries from
         // ksat on are identical anyway); only the padding keys of the last tile carry the -1000 sentinel
-        unsigned esum = 0;
+        unsigned esum = 0;      // natural scales: exact integer row sum; I-BERT: the float32 sum's bits
+        float fsum = 0.0f;      // MODE 0: float32 row sum of the gathered float32 exponents
         if constexpr (MODE == 1) {     // natural input scale, band rows of this tile's 16 queries staged in LDS
             const int W = a.band_w, stride = W + BAND_PAD;
             unsigned* slice = band_lds + (wave * 16 + l15) * stride;
@@ -330,41 +332,47 @@ __global__ __launch_bounds__(NT, OCC) void attention_kernel(AttnArgs a)
                     s[kt][r] = __float_as_int((float)e);
                     esum += e;
                 }
-        } else
+        } else {
+            // ONE gather per score: the float32 entry is the factor of the product below AND the term of the row sum, which is
+            // taken in float32 (attn_parts.h SHIFTMAX_ORDER_SUM: exact below 2^24, and at or above 2^24 exactly when the exact sum
+            // is)
 #pragma unroll
-        for (int kt = 0; kt < NKT; ++kt)
+            for (int kt = 0; kt < NKT; ++kt)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                unsigned e, ef;
-                if (GENT || kt == NKT - 1) {
-                    const int idx = min(rmax + s[kt][r], 255);
-                    e = lut[idx];
-                    ef = lut[256 + idx];
-                    const bool pad = s[kt][r] == PADK;
-                    e = pad ? 0u : e;
-                    ef = pad ? 0u : ef;
-                } else if (IVIT_LAB && (a.abl & 2)) {
-                    e = (unsigned)s[kt][r];
-                    ef = (unsigned)__float_as_int(1.0f);
-                } else {
-                    e = lut[rmax + s[kt][r]];
-                    ef = lut[256 + rmax + s[kt][r]];
+                for (int r = 0; r < 4; ++r) {
+                    float ef;
+                    if (GENT || kt == NKT - 1) {
+                        ef = lut[min(rmax + s[kt][r], 255)];
+                        ef = s[kt][r] == PADK ? 0.0f : ef;
+                    } else if (IVIT_LAB && (a.abl & 2)) {
+                        ef = 1.0f;
+                    } else {
+                        ef = lut[rmax + s[kt][r]];
+                    }
+                    s[kt][r] = __float_as_int(ef);       // float32 bit pattern of the exponent
+                    fsum += ef;
                 }
-                s[kt][r] = (int)ef;       // float32 bit pattern of the exponent
-                esum += e;
-            }
+        }
         // every mode has left the exponents in s[][] as float32 bit patterns
         float factor;
         if constexpr (MODE >= 3) {
             factor = floorf(4294967296.0f / __int_as_float((int)esum));        // ibert_modules.py:313
         } else {
-            const unsigned tot = rows_allsum_u32(esum);
-            factor = shiftmax_factor(tot);
+            bool ordered;
+            if constexpr (MODE == 0) {
+                const float tot = rows_allsum_f32(fsum);      // the four lanes may round differently only at or above 2^24
+                ordered = tot >= (float)SHIFTMAX_ORDER_SUM;
+                factor = shiftmax_factor(tot);
+            } else {
+                const unsigned tot = rows_allsum_u32(esum);
+                ordered = tot >= SHIFTMAX_ORDER_SUM;
+                factor = shiftmax_factor(tot);
+            }
             // a row whose exact sum reaches 2^24: the reference's float32 sum depends on torch's order of additions (attn_parts.h).
             // Wave-uniform and rare (no row of the model fixtures gets here); the other rows of the tile keep their factor.
-            if (__builtin_expect(__builtin_amdgcn_ballot_w64(tot >= SHIFTMAX_ORDER_SUM) != 0, 0)) {
+            if (__builtin_expect(__builtin_amdgcn_ballot_w64(ordered) != 0, 0)) {
                 const float S = torch_rowsum_tiles<NKT>(s, [](int v) { return __int_as_float(v); }, T);
-                factor = tot >= SHIFTMAX_ORDER_SUM ? shiftmax_factor(S) : factor;
+                factor = ordered ? shiftmax_factor(S) : factor;
             }
         }
         if constexpr (PB == 4) factor *= 0.0625f;      // the last shift is 2^(31 - 4 + 1) (:175; I-BERT :313-314): see below
@@ -1478,7 +1486,8 @@ int attention_launch(AttnDesc d)
     a.band_w = d.band_w;
     const size_t band_lds_bytes = d.band_w ? (size_t)4 * 16 * (d.band_w + BAND_PAD) * sizeof(unsigned) : 0;
     {   // resident workgroups: 4 per CU for 8-bit probabilities (128 VGPRs), 3 for the 16-bit planes; the band rows add dynamic LDS
-        const int by_regs = pb16 ? 3 : 4, by_lds = (int)(163840 / (SMEM_BYTES + 512 + band_lds_bytes));
+        const int smem_bytes = (ibert || d.band_w || d.table) ? SMEM_BYTES : SMEM0_BYTES;     // MODE 0: one float32 table
+        const int by_regs = pb16 ? 3 : 4, by_lds = (int)(163840 / (smem_bytes + 512 + band_lds_bytes));
         a.parts = attention_parts(pairs, nqt, NT / 64, 256 * (by_regs < by_lds ? by_regs : by_lds));
 #if IVIT_LAB
         if ((g_attn_debug >> 8) & 7) a.parts = (g_attn_debug >> 8) & 7;      // lab: forced (scripts/attn_parts.py), this form only

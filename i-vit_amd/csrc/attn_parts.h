@@ -43,6 +43,15 @@ IVIT_DEV float shiftexp_lit(float d, float x0)
 // SHIFTMAX_ORDER_SUM on, the reference's value is the one torch's CPU kernel reaches in ITS order of additions, every one rounded
 // (rowsum.h; tests/golden/shiftmax_bigsum_kat.npz holds rows where the exact sum rounded once gives another factor): a kernel
 // tests the exact sum against SHIFTMAX_ORDER_SUM and hands such rows' sum, taken in that order, to the float32 form.
+// A kernel that holds the exponents as float32 only (attention_kernel MODE 0: one table gather per score) takes the test and the
+// sum from a float32 sum in ITS OWN order, fsum.  Every exponent is a non-negative integer that float32 holds exactly
+// ((r - 2 x0) 2^(14 - q), |x0| <= 4096: at most 15 significant bits).  (a) Exact total below 2^24: every term and every partial
+// sum, of any grouping, is an integer below 2^24 and is held exactly, so fsum is the exact total = the reference's float32 sum.
+// (b) Exact total at least 2^24: take, in the tree of additions that leads to fsum, a lowest node whose exact value reaches 2^24
+// (the root's does).  It is a term, held exactly, or an addition of two nodes below 2^24, both exact by (a), whose exact sum
+// rounds to no less than 2^24 (2^24 is representable, rounding is monotone).  Every addition above it adds a non-negative value,
+// and fl(x + y) >= x for y >= 0.  So fsum >= 2^24 exactly when the exact total >= SHIFTMAX_ORDER_SUM, in every lane, whatever
+// the lanes' order of additions; below it shiftmax_factor receives the same float as from the integer sum.
 constexpr unsigned SHIFTMAX_ORDER_SUM = 1u << 24;
 IVIT_DEV float shiftmax_factor(float S)
 {
@@ -51,6 +60,13 @@ IVIT_DEV float shiftmax_factor(float S)
 }
 IVIT_DEV float shiftmax_factor(unsigned esum) { return shiftmax_factor((float)esum); }                // exp_int.sum (:171) below 2^24
 IVIT_DEV float shiftmax_factor(unsigned long long esum) { return shiftmax_factor((float)esum); }      // long rows: the sum passes 2^32
+// float32 sum over the four lanes of a query, (row 0 + row 1) + (row 2 + row 3) in every lane (common.h rows_allreduce_u32)
+IVIT_DEV float rows_allsum_f32(float v)
+{
+    return __int_as_float((int)rows_allreduce_u32((unsigned)__float_as_int(v), [](unsigned x, unsigned y) {
+        return (unsigned)__float_as_int(__int_as_float((int)x) + __int_as_float((int)y));
+    }));
+}
 
 // ---- 8-bit probabilities: p = floor(fl32(e * factor) / 2^24) (:175) = the top byte of each product u, four gathered with two
 // byte permutes
