@@ -47,8 +47,8 @@ __global__ __launch_bounds__(NT) void layernorm_f32_f32_kernel(LnLitArgs a)
         const int mean_int = (int)rintf(mean);                                    //      round_ste
         long long var = 0;
         for (int c = lane; c < C; c += 64) {
-            const long long d = (long long)(int)truncf(xint(c)) - mean_int;       // :38-40  .to(int32); y = x - mean
-            var += d * d;                                                         // :41-42  int32 squares, int64 sum
+            const unsigned d = (unsigned)((int)truncf(xint(c)) - mean_int);       // :38-40  .to(int32); y = x - mean
+            var += (long long)(int)(d * d);                                       // :41-42  int32 squares (they wrap), int64 sum
         }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {

@@ -781,17 +781,19 @@ __global__ __launch_bounds__(NT) void layernorm_i32_f32_kernel(LnArgs a)
     float* out = reinterpret_cast<float*>(a.out);
     for (int row = blockIdx.x * WPB + wave; row < a.rows; row += gridDim.x * WPB) {
         const int32_t* xr = xin + (int64_t)row * a.ldx;
-        // float32 sum of integers (exact below 2^24; 16-bit rows may exceed it: then this is
-        // RN24 of the exact sum)
+        // float32 sum of integers: exact in any order below 2^24; 16-bit rows may exceed it, and then it is the value torch's CPU
+        // kernel reaches in its order of additions (rowsum.h)
         int sum = 0;  // |sum| < 2^31 for C <= 4096 and 16-bit values
         for (int c = lane; c < C; c += 64) sum += xr[c];
         sum = wave_reduce_sum_i32(sum);
-        float mean = (float)sum / (float)C;
-        int mean_int = (int)rintf(mean);
+        float fsum = (float)sum;
+        if (__builtin_amdgcn_readfirstlane(abs(sum) >= (1 << 24)))
+            fsum = torch_rowsum([&](int c) { return (float)xr[c]; }, C, lane);
+        const int mean_int = (int)rintf(fsum / (float)C);
         long long var = 0;
         for (int c = lane; c < C; c += 64) {
-            long long d = (long long)xr[c] - mean_int;
-            var += d * d;
+            const unsigned d = (unsigned)(xr[c] - mean_int);
+            var += (long long)(int)(d * d);               // :41 int32 squares (they wrap from |d| = 46 341 on), :42 int64 sum
         }
         // 64-bit wave reduction
 #pragma unroll

@@ -117,6 +117,11 @@ struct Ln16Args {
     int lab_lds_sum;   // lab A/B: the row sums through LDS (the round-3 form) where the register form applies
 };
 
+// :41  y_int ** 2 on an int32 tensor keeps the low 32 bits of the product: from |d| = 46 341 on the square wraps (a 16-bit row with
+// |mean| >= 13 573 and an element at the opposite rail); :42 sums the wrapped values in int64.
+constexpr unsigned LN16_WRAP_FROM = 46341u;
+IVIT_DEV long long ln16_square(int d) { return (long long)(int)((unsigned)d * (unsigned)d); }
+
 __global__ __launch_bounds__(NT) void layernorm_i16_i8_kernel(Ln16Args a)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -126,13 +131,12 @@ __global__ __launch_bounds__(NT) void layernorm_i16_i8_kernel(Ln16Args a)
         int sum = 0;  // |sum| < 2^31 for C <= 4096
         for (int c = lane; c < C; c += 64) sum += xr[c];
         sum = wave_reduce_sum_i32(sum);
-        const float mean = (float)sum / (float)C;                    // :37 (RN24 of the exact sum, / C)
-        const int mean_int = (int)rintf(mean);
+        float fsum = (float)sum;                                      // :37 exact in any order below 2^24 ...
+        if (__builtin_amdgcn_readfirstlane(abs(sum) >= (1 << 24)))    // ... from there on torch's order of additions (rowsum.h)
+            fsum = torch_rowsum([&](int c) { return (float)xr[c]; }, C, lane);
+        const int mean_int = (int)rintf(fsum / (float)C);
         long long var = 0;
-        for (int c = lane; c < C; c += 64) {
-            long long d = (long long)xr[c] - mean_int;
-            var += d * d;
-        }
+        for (int c = lane; c < C; c += 64) var += ln16_square(xr[c] - mean_int);      // :41-42
         const float t = ln_newton10_literal((float)(long long)lanes_allsum_u64<64>(var));   // :45-49
         const float factor = floorf((1.0f / t) * 2147483648.0f);     // :51
         int8_t* orow = a.out + win_row(a.map, row) * a.ldo;
@@ -171,8 +175,7 @@ __global__ __launch_bounds__(NT) void layernorm_i16_i8_literal_kernel(Ln16LitArg
         const int mean_int = (int)rintf(S / (float)C);                         // :37
         long long var = 0;
         for (int c = lane; c < C; c += 64) {
-            const long long d = (long long)(int)truncf(xint(c)) - mean_int;    // :38-40
-            var += d * d;
+            var += ln16_square((int)truncf(xint(c)) - mean_int);               // :38-42
         }
         const float t = ln_newton10_literal((float)(long long)lanes_allsum_u64<64>(var));   // :45-49
         const float factor = floorf((1.0f / t) * 2147483648.0f);               // :51
@@ -198,15 +201,17 @@ __global__ __launch_bounds__(NT) void layernorm_i16_i8_literal_kernel(Ln16LitArg
 // issues its half-rate instructions at 4.4 cycles instead of 3.2, and a prologue that a launch of few rows
 // (Swin stages 2-3: 14-29 MB) spent most of its time in.
 // The ten float32 Newton steps of ivit_modules.py:45-49 on varf = RN24(var) WITHOUT iterating, where that is provably the same
-// (round 4; scripts/probes/ln16_newton_exhaustive.py walks every float32 value in [2^24, 2^37), ln_newton_exhaustive.py every
-// integer below 2^24): t10 == floor(sqrt(varf)) unless varf lies within 2^(ex - 22) below the next square (then t10 is that or one
-// more).  Those rows (<= 3 %), and rows below 2^24 that rowops.hip's rule sends there, run the literal loop -- wave-uniformly.
+// (round 4; scripts/probes/ln16_newton_exhaustive.py walks every float32 value in [2^24, 2^42), ln_newton_exhaustive.py every
+// integer below 2^24; a sum of C <= 1536 int32 squares stays below 1536 * 2^31 < 2^42): t10 == floor(sqrt(varf)) unless varf lies
+// within 2^(ex - 22) below the next square (then t10 is that or one more).  Those rows (sqrt(varf) * 2^-23 of all values: <= 3 % below
+// 2^36, a quarter at 2^42), and rows below 2^24 that rowops.hip's rule sends there, run the literal loop -- wave-uniformly.  A wrapped
+// sum that is zero or negative (outside the reference's own domain: its Newton steps divide by zero) takes the literal loop too.
 // 40 % of the instructions of a C = 384 / 768 row group were this loop (ten IEEE divisions per group of 4 / 2 rows).
 IVIT_DEV float ln16_std10(float varf)
 {
-    const double v = (double)varf;                          // an integer below 2^37, exact
+    const double v = (double)varf;                          // an integer below 2^42, exact
     double s = __builtin_floor(__builtin_sqrt(v));
-    s = (s * s > v) ? s - 1.0 : s;                          // (exact products: s < 2^19)
+    s = (s * s > v) ? s - 1.0 : s;                          // (exact products: s < 2^21)
     s = ((s + 1.0) * (s + 1.0) <= v) ? s + 1.0 : s;
     const double gap = (s + 1.0) * (s + 1.0) - v;
     const bool slow = varf < 16777216.0f ? (varf < 142883.0f || gap == 1.0)      // rowops.hip LN_NEWTON_CONVERGED, ln_std10
@@ -233,6 +238,7 @@ IVIT_DEV void ln16_tail(const Ln16Args& a, const v4i (&w)[NJ], int mean_int, int
 {
     const int nd = a.C >> 3;
     unsigned long long var = 0;
+    unsigned dmax = 0;
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
         if (sub + LPR * j < nd) {
@@ -242,11 +248,28 @@ IVIT_DEV void ln16_tail(const Ln16Args& a, const v4i (&w)[NJ], int mean_int, int
                 const unsigned d1 = (unsigned)abs((w[j][q] >> 16) - mean_int);
                 var += (unsigned long long)d0 * d0;
                 var += (unsigned long long)d1 * d1;
+                dmax = max(dmax, max(d0, d1));
             }
         }
     }
-    var = lanes_allsum_u64<LPR>(var);
-    const float t = ln16_std10((float)var);                                 // :45-49
+    // :41 the reference's squares are int32: where an element of the wave's rows reaches 46 341 the sum is taken again over the wrapped
+    // values (wave-uniform, unlikely); below, the 64-bit products above are the same numbers.  (Measured alternatives, 6272 x 768: the
+    // test on |mean_int| >= 46 341 - 32 768 with the two loops as if / else cost 0.06 us more per launch than this maximum; a second
+    // instantiation of this function for such waves spilled to scratch.)
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(dmax >= LN16_WRAP_FROM) != 0, 0)) {
+        long long wv = 0;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            if (sub + LPR * j < nd) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    wv += ln16_square((int)(int16_t)w[j][q] - mean_int) + ln16_square((w[j][q] >> 16) - mean_int);
+            }
+        }
+        var = (unsigned long long)wv;
+    }
+    var = lanes_allsum_u64<LPR>(var);                                       // (two's complement: a wrapped sum may be negative)
+    const float t = ln16_std10((float)(long long)var);                      // :45-49
     const float hfactor = floorf((1.0f / t) * 2147483648.0f) * 0.5f;        // :51; the /2 of :52 commutes (exact scaling)
     int8_t* orow = a.out + win_row(a.map, row) * a.ldo;
     int2 res[NJ];
@@ -307,6 +330,25 @@ IVIT_DEV void ln16_tail(const Ln16Args& a, const v4i (&w)[NJ], int mean_int, int
     }
 }
 
+// :37 for the rows of a wave whose integer sum reaches 2^24 in magnitude: x_int.mean() is a float32 sum, and from there on its value is
+// the one torch's CPU kernel reaches in its order of additions (rowsum.h; tests/golden/ln16_bigrows_kat.npz holds rows on which the
+// exact sum rounded once gives another mean_int).  The whole wave sums one such row at a time from memory (the row was just loaded:
+// L1 / L2); rows below 2^24 keep (float)sum, which every order gives.  Called by all lanes under a wave-uniform condition.
+template <int LPR>
+IVIT_DEV float ln16_ordered_sum(const int16_t* x, int C, int row0, int rows, int grp, int lane, int sum)
+{
+    float S = (float)sum;
+#pragma unroll 1
+    for (int g = 0; g < 64 / LPR; ++g) {
+        const int sg = __builtin_amdgcn_readlane(sum, g * LPR);                 // the sum of row row0 + g: uniform
+        if (abs(sg) < (1 << 24)) continue;
+        const int16_t* xr = x + (int64_t)min(row0 + g, rows - 1) * C;
+        const float Sg = torch_rowsum([&](int c) { return (float)xr[c]; }, C, lane);
+        S = (grp == g) ? Sg : S;
+    }
+    return S;
+}
+
 // Sub-wave tiling of the same computation for C % 8 == 0, C <= 1536: LPR lanes share a row (64 / LPR rows per wave and
 // iteration), each lane owns NJ chunks of 8 channels (one 16-byte load each) and keeps their per-channel constants in
 // registers for the whole kernel.  The per-row scalar work (mean division, Newton steps) is evaluated once per
@@ -339,7 +381,10 @@ __global__ __launch_bounds__(NT, 4) void layernorm_i16_i8_tiled_kernel(Ln16Args 
             for (int q = 0; q < 4; ++q) sum += (int)(int16_t)w[j][q] + (w[j][q] >> 16);
         }
         sum = lanes_allsum_i32<LPR>(sum);      // common.h: DPP / permlane swaps instead of ds_bpermute butterflies
-        const int mean_int = (int)rintf((float)sum / fC);                       // :37
+        float fsum = (float)sum;                                                // :37 exact in any order below 2^24
+        if (__builtin_expect(__builtin_amdgcn_ballot_w64(abs(sum) >= (1 << 24)) != 0, 0))
+            fsum = ln16_ordered_sum<LPR>(a.x, C, row0, a.rows, grp, lane, sum);
+        const int mean_int = (int)rintf(fsum / fC);
         ln16_tail<LPR, NJ>(a, w, mean_int, sub, live, min(row, a.rows - 1), t_bias, t_lo, t_hi);
     }
 }

@@ -551,7 +551,12 @@ int ivit_residual_requant_i16(const void* a, int a_bits, const uint32_t* m_pre, 
 /* I-LayerNorm on the 16-bit stream + 8-bit QuantAct (ivit_modules.py:30-65 with the Newton iteration on
  * float32(var), as the reference runs it); row r of x is written to row win_row(r) of out (stride ldo >= C):
  * norm1 writes straight into window order (swin_quant.py:258-271).  Same constants and contract as
- * ivit_layernorm_i8. */
+ * ivit_layernorm_i8.  Domain: every int16 row whose variance sum the reference itself can take, its two float32 / int32 effects
+ * included -- a row whose integer sum reaches 2^24 in magnitude takes the mean from the float32 sum in torch's CPU reduction order
+ * (:37), and the squares are int32 as the reference's (:41: they wrap from |x - mean| = 46 341 on), summed in int64.  A row whose
+ * wrapped sum is zero or negative is outside it (the reference divides by zero): its bytes are unspecified, nothing else is written.
+ * ivit_layernorm_i16_i8_compat, ivit_layernorm_i32_f32 and ivit_layernorm_f32_f32(_ex) treat both steps the same way
+ * (tests/golden/ln16_bigrows_kat.npz). */
 int ivit_layernorm_i16_i8(const int16_t* x, int rows, int C, const float* bias_int, const float* s_ln,
                           const uint32_t* m, const int32_t* e, int8_t* out, int64_t ldo, int H, int W, int ws, int shift,
                           ivit_stream_t stream);

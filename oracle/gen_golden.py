@@ -1188,6 +1188,252 @@ def gen_shiftmax_bigsum():
     print(f"shiftmax_bigsum_kat.npz written: {os.path.getsize(path)} bytes; {counts}")
 
 
+LN16_RANGES = {0: 4.0, 1: 3.71}          # the QuantAct range behind the LayerNorm, per scale index (power-of-two, natural)
+
+
+def _ln16_fix_sum(rng, q, tgt):
+    """move the integer row sums of q [N, C] to tgt [N] by steps of +-1 on |delta| distinct random elements (|delta| <= C)"""
+    delta = tgt - q.sum(axis=1)
+    assert np.abs(delta).max() <= q.shape[1]
+    rank = np.argsort(rng.random(q.shape), axis=1).argsort(axis=1)
+    return q + np.sign(delta)[:, None] * (rank < np.abs(delta)[:, None])
+
+
+def _ln16_v_row(rng, C, T, ulp, ok_value):
+    """a row of +- pairs (mean 0, var = 2 sum a^2) whose variance rounds to the float32 T: -> int64 [C] or None"""
+    x = int(T) // 2
+    tol = 0 if ulp <= 2 else ulp // 4 - 1                    # |2 sum a^2 - T| < ulp / 2, no tie
+    half = C // 2
+    vals = []
+    n0 = min(half - 14, max(1, -(-x // (30000 * 30000))))
+    a0 = int(np.sqrt(x // n0))
+    while a0 > 0 and not ok_value(a0):
+        a0 -= 1
+    if a0 > 32767:
+        return None
+    if a0 > 0:
+        vals += [a0] * n0
+        x -= n0 * a0 * a0
+    while x > tol and len(vals) < half:
+        a = min(int(np.sqrt(x)), 32767)
+        while a * a > x:
+            a -= 1
+        while a > 1 and not ok_value(a):
+            a -= 1
+        vals.append(a)
+        x -= a * a
+    if abs(x) > tol:
+        return None
+    row = np.zeros(C, np.int64)
+    row[:len(vals)] = vals
+    row[half:half + len(vals)] = [-v for v in vals]
+    return row
+
+
+def gen_ln16_bigrows():
+    """tests/golden/ln16_bigrows_kat.npz: IVITIntLayerNorm + an 8-bit QuantAct on 16-bit rows whose float32 sum reaches 2^24 (the
+    mean, ivit_modules.py:37, then depends on the order of torch's CPU kernel), whose int32 squares wrap (:41), or whose variance
+    lies where swin.hip's ln16_std10 decides between its shortcut and the literal Newton loop.  Stored per width C and scale: the
+    int16 rows, gamma, beta, the output range, the REFERENCE's int8 output, a class per row (tests/ln16_order_ref.py) and per row
+    the CRC32 of the two other candidates' outputs (exact sum rounded once; 64-bit squares).  Class (c) rows come from a seeded,
+    directed search: rows whose integer sum is moved next to a .5 tie of the mean, kept where the two sums fall on either side."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import ln16_order_ref as lno
+    torch.set_num_threads(1)
+    rng = np.random.default_rng(20261021)
+    t_start = time.time()
+    out, counts, notes = {}, {}, {}
+    for C in lno.TILED_C + lno.OTHER_C:
+        gamma = rng.uniform(0.5, 1.5, size=C).astype(np.float32)
+        beta = rng.normal(0, 0.1, size=C).astype(np.float32)
+        out[f"gamma_{C}"], out[f"beta_{C}"] = gamma, beta
+        for si, s in enumerate(lno.SCALES):
+            hi = LN16_RANGES[si]
+            key = f"{C}_{si}"
+            rows, kinds, vkind, edge = [], [], [], []
+
+            def cls_of(q):
+                return lno.classify(q, s, gamma, beta, -hi, hi)
+
+            def keep(q, want, limit, vk=lno.V_NONE, ed=0):
+                cls, _, _ = cls_of(q)
+                idx = np.flatnonzero(cls == (lno.CLASS_A if want == lno.CLASS_V else want))[:limit]
+                for i in idx:
+                    rows.append(q[i].astype(np.int16)); kinds.append(want); vkind.append(vk); edge.append(ed)
+                return len(idx)
+
+            # ---- (a) control: centred rows, one of small amplitude
+            qa = np.clip(np.rint(rng.normal(0, 3000, size=(8, C))), -32768, 32767).astype(np.int64)
+            qa[1] = rng.integers(-5, 6, size=C)
+            assert keep(qa, lno.CLASS_A, 2) == 2
+            # ---- (b), (c): rows far from zero, either sign, their integer sum moved next to a .5 tie of the mean
+            base_lo = max(8000, (1 << 24) // C + 200)
+            nb, nc = 0, {1: 0, -1: 0}
+            n_c, n_sign = (8, 3) if C in lno.TILED_C else (4, 2)      # (the wave-per-row kernels: one form, fewer rows); rows per sign at least
+            for attempt in range(400):
+                if nc[1] + nc[-1] >= n_c and min(nc.values()) >= n_sign:
+                    break
+                N = 4096
+                sign = rng.choice([-1, 1], size=(N, 1))
+                sigma = np.exp(rng.uniform(np.log(3), np.log(16), size=(N, 1)))
+                base = rng.uniform(base_lo, 31500, size=(N, 1))
+                q = np.rint(sign * base + sigma * rng.normal(size=(N, C))).astype(np.int64)
+                k = np.floor(q.sum(axis=1) / C).astype(np.int64)
+                q = _ln16_fix_sum(rng, q, C * k + C // 2 + rng.integers(-1, 2, size=N))
+                q = q[(np.abs(q).max(axis=1) <= 32767)]
+                xf = lno.xint_of(q, s)
+                St, Se = lno.both_sums(xf)
+                m = lno.mean_int_of(St, C) != lno.mean_int_of(Se, C)
+                if nb < 2:
+                    nb += keep(q[~m][:64], lno.CLASS_B, 2 - nb)
+                for sg in (1, -1):
+                    qs = q[m & (q[:, 0] * sg > 0)]
+                    if len(qs) and nc[sg] < n_c - n_sign and nc[1] + nc[-1] < n_c:
+                        nc[sg] += keep(qs, lno.CLASS_C, min(n_c - n_sign - nc[sg], n_c - nc[1] - nc[-1]))
+            assert nb == 2 and nc[1] + nc[-1] == n_c and min(nc.values()) >= n_sign, (key, nb, nc)
+            # ---- (w): a cluster around a mean of 14 000 or more, 1..4 elements at the opposite rail; the first two rows have
+            #      max |d| = 46 341 exactly (class w) and 46 340 exactly (no wrap: stored with edge = 1, class a or b)
+            nw = 0
+            for attempt in range(200):
+                if nw >= 9:
+                    break
+                sg = 1 if attempt % 2 == 0 else -1            # the sign of the cluster; the rail is the other one
+                rail = -32768 if sg > 0 else 32767
+                krail = int(np.trunc(lno.xint_of(np.array([rail]), s))[0])
+                nr = 1 if nw < 2 else int(rng.integers(1, 5))
+                if nw < 2:
+                    want_d = lno.WRAP_FROM - nw                # 46 341, then 46 340
+                    target = krail + want_d if sg > 0 else krail - want_d
+                else:
+                    target = sg * int(rng.integers(14000, 19000))
+                sigma = 2500 + 700 * nr
+                # (sixteen levels of the normal distribution, not its whole range: the rows compress)
+                q = np.clip(np.rint(target + sigma * np.rint(rng.normal(size=(1, C)) * 3) / 3), -32768, 32767).astype(np.int64)
+                q[0, rng.choice(C, size=nr, replace=False)] = rail
+                # the mean: the rails are part of it
+                for _ in range(3):
+                    delta = C * target - int(q.sum())
+                    cl = q[0] != rail
+                    q[0, cl] = np.clip(q[0, cl] + delta // int(cl.sum()), -32767, 32766)
+                delta = C * target - int(q.sum())
+                if not 0 <= delta < int(cl.sum()):
+                    continue
+                q[0, np.flatnonzero(cl)[:delta]] += 1          # the integer sum is C * target exactly
+                cls, cand, ref = cls_of(q)
+                if nw == 1:
+                    if ref["maxd"][0] == lno.WRAP_FROM - 1 and cls[0] in (lno.CLASS_A, lno.CLASS_B):
+                        rows.append(q[0].astype(np.int16)); kinds.append(int(cls[0])); vkind.append(lno.V_NONE); edge.append(1)
+                        nw += 1
+                    continue
+                if nw == 0 and ref["maxd"][0] != lno.WRAP_FROM:
+                    continue
+                if cls[0] != lno.CLASS_W or not np.any(cand[("torch", True)] != cand[("torch", False)]):
+                    continue
+                assert ref["var"][0] > 0
+                nw += keep(q, lno.CLASS_W, 1)
+            assert nw == 9, (key, nw)
+            # ---- (v): +- pairs whose variance rounds into, or just outside, the band of ln16_std10, per binade; the 2^37 boundary
+            k_ok = np.trunc(lno.xint_of(np.arange(32768), s)).astype(np.int64) == np.arange(32768)
+
+            def ok_value(a):
+                return bool(k_ok[a])
+
+            reach = C // 2 * 2 * 32767 ** 2
+            # (the wave-per-row kernels of C = 772 / 2048 always run the ten literal steps: four binades and the boundary there)
+            for ex in (range(24, 42) if C in lno.TILED_C else lno.V_BINADES_OTHER_C):
+                lo_sq, hi_sq = 2.0 ** ex * 1.05, min(2.0 ** (ex + 1) * 0.95, reach * 0.93)
+                if lo_sq >= hi_sq:
+                    notes[f"{key}_v{ex}"] = "out of reach of 16-bit +- pairs at this width"
+                    continue
+                got = {lno.V_INSIDE: 0, lno.V_OUTSIDE: 0}
+                for attempt in range(40):
+                    if got[lno.V_INSIDE] and got[lno.V_OUTSIDE]:
+                        break
+                    s1 = int(np.sqrt(rng.uniform(lo_sq, hi_sq)))
+                    T = np.float32(s1 * s1)
+                    if float(T) >= s1 * s1:
+                        T = np.nextafter(T, np.float32(0))
+                    for _ in range(12):                         # walk down from the square: in the band first, then out of it
+                        slow = bool(lno.std10_rule(T)[0])
+                        vk = lno.V_INSIDE if slow else lno.V_OUTSIDE
+                        if not got[vk]:
+                            row = _ln16_v_row(rng, C, int(T), 1 << (ex - 23), ok_value)
+                            if row is not None:
+                                chk = lno.layernorm(row[None], s, gamma, beta)
+                                if np.float32(chk["var"][0]) == T and chk["mean_int"][0] == 0:
+                                    got[vk] += keep(row[None], lno.CLASS_V, 1, vk)
+                        if not slow:
+                            break
+                        T = np.nextafter(T, np.float32(0))
+                assert got[lno.V_INSIDE] and got[lno.V_OUTSIDE], (key, ex, got)
+            if reach > 2 ** 37:
+                for T in (np.float32(2.0 ** 37), np.nextafter(np.float32(2.0 ** 37), np.float32(0))):
+                    row = _ln16_v_row(rng, C, int(T), 1 << 13, ok_value)
+                    assert row is not None and np.float32(lno.layernorm(row[None], s, gamma, beta)["var"][0]) == T
+                    assert keep(row[None], lno.CLASS_V, 1, lno.V_BOUNDARY) == 1
+            # ---- the reference itself on every row of the group
+            q = np.stack(rows).astype(np.int64)
+            kinds, vkind, edge = np.array(kinds, np.uint8), np.array(vkind, np.uint8), np.array(edge, np.uint8)
+            ln = rq.IVITIntLayerNorm(C)
+            ln.weight.data, ln.bias.data = torch.from_numpy(gamma), torch.from_numpy(beta)
+            st = torch.tensor([s])
+            x = (torch.from_numpy(q.astype(np.float32))[None] * st).float().contiguous()
+            yl, sl = ln(x, st)
+            assert bool(torch.isfinite(yl).all()), key
+            qa_mod = rq.QuantAct()
+            qa_mod.x_min.fill_(-hi)
+            qa_mod.x_max.fill_(hi)
+            qa_mod.fix()
+            yq, sq = qa_mod(yl, sl)
+            ref_out = torch.round(yq / sq).numpy().reshape(len(q), C).astype(np.int32)
+            assert ref_out.min() >= -128 and ref_out.max() <= 127
+            # the restatement must agree with it, and the classes hold what they say
+            cls, cand, ref = cls_of(q)
+            assert np.array_equal(cand[("torch", True)], ref_out), (key, "the reference's output is not the restatement's")
+            assert np.array_equal((ref["y"] * ref["s_ln"]).astype(np.float32).view(np.int32), yl.numpy().reshape(len(q), C).view(np.int32)), key
+            assert np.array_equal(np.where(kinds == lno.CLASS_V, lno.CLASS_A, kinds), cls), key
+            xf = lno.xint_of(q, s)
+            big = np.abs(xf.astype(np.float64).sum(axis=1)) >= 2.0 ** 24
+            St, Se = lno.both_sums(xf)
+            assert np.array_equal(x[0].div(st).sum(dim=-1).numpy(), St), "torch's sum is not the restated order"
+            same_mean = lno.mean_int_of(St, C) == lno.mean_int_of(Se, C)
+            d_exact = np.any(cand[("exact", True)] != ref_out, axis=1)
+            d_nowrap = np.any(cand[("torch", False)] != ref_out, axis=1)
+            a = np.isin(kinds, (lno.CLASS_A, lno.CLASS_V))
+            assert not big[a].any() and (ref["maxd"][a] < lno.WRAP_FROM).all() and not d_exact[a].any() and not d_nowrap[a].any()
+            b = kinds == lno.CLASS_B
+            assert big[b].all() and same_mean[b].all() and not d_exact[b].any() and not d_nowrap[b].any()
+            c = kinds == lno.CLASS_C
+            assert big[c].all() and not same_mean[c].any() and d_exact[c].all() and not d_nowrap[c].any()
+            assert (St[c] > 0).sum() >= n_sign and (St[c] < 0).sum() >= n_sign and c.sum() == n_c
+            w = kinds == lno.CLASS_W
+            assert (ref["maxd"][w] >= lno.WRAP_FROM).all() and (ref["var"][w] > 0).all() and d_nowrap[w].all() and not d_exact[w].any()
+            assert w.sum() >= 8 and (ref["maxd"][w] == lno.WRAP_FROM).any() and (ref["maxd"][edge == 1] == lno.WRAP_FROM - 1).all()
+            assert edge.sum() == 1 and (ref["var"] > 0).all()
+            v = kinds == lno.CLASS_V
+            slow = lno.std10_rule(ref["var"][v].astype(np.float32))[0]
+            assert np.array_equal(slow[vkind[v] == lno.V_INSIDE], np.ones((vkind[v] == lno.V_INSIDE).sum(), bool))
+            assert not slow[vkind[v] == lno.V_OUTSIDE].any() and (ref["mean_int"][v] == 0).all()
+            out[f"q_{key}"], out[f"cls_{key}"], out[f"vkind_{key}"], out[f"edge_{key}"] = q.astype(np.int16), kinds, vkind, edge
+            out[f"ref_{key}"] = ref_out.astype(np.int8)
+            out[f"exact_crc_{key}"] = np.array([zlib.crc32(r.tobytes()) for r in cand[("exact", True)]], np.uint32)
+            out[f"nowrap_crc_{key}"] = np.array([zlib.crc32(r.tobytes()) for r in cand[("torch", False)]], np.uint32)
+            for kc in lno.CLASS_NAMES:
+                counts[f"{key}_{lno.CLASS_NAMES[kc]}"] = int((kinds == kc).sum())
+            print(f"[ln16_bigrows] C={C} s={float(s):.6g}: {len(q)} rows, "
+                  f"{ {lno.CLASS_NAMES[kc]: int((kinds == kc).sum()) for kc in lno.CLASS_NAMES} }  ({time.time() - t_start:.0f} s)", flush=True)
+    out["widths"] = np.array(lno.TILED_C + lno.OTHER_C, np.int32)
+    out["scales"] = np.array(lno.SCALES, np.float32)
+    out["ranges"] = np.array([LN16_RANGES[0], LN16_RANGES[1]], np.float32)
+    out["meta"] = np.array(json.dumps(dict(seed=20261021, classes={v: k for k, v in lno.CLASS_NAMES.items()}, counts=counts, notes=notes,
+                                           torch=torch.__version__)))
+    path = os.path.join(GOLD, "ln16_bigrows_kat.npz")
+    np.savez_compressed(path, **out)
+    # (8 (c) and 8 (w) rows at six widths and two scales are about 190 000 elements whose int16 inputs and int8 outputs barely compress)
+    assert os.path.getsize(path) < 640 * 1024, os.path.getsize(path)
+    print(f"ln16_bigrows_kat.npz written: {os.path.getsize(path)} bytes")
+
+
 def gen_schema():
     """state_dict keys and shapes of the reference's DeiT and Swin models (the on-disk checkpoint format)"""
     out = {}
@@ -1224,6 +1470,8 @@ if __name__ == "__main__":
             gen_schema()
         elif w == "shiftmax_bigsum":
             gen_shiftmax_bigsum()
+        elif w == "ln16_bigrows":
+            gen_ln16_bigrows()
         elif w in ("deit_tiny_ibert_natural", "deit_tiny_ibert_w16all"):
             gen_ibert_natural(w)
         elif w.endswith("_natural") and not w.startswith("swin"):
