@@ -126,6 +126,8 @@ SIGNATURES = {
                                       ci, ci, ci, ci, ci, ci, vp],
     "ivit_window_attention_i8_ibert": [vp, vp, i64, vp, vp, f32, ci, ci, ci, ci, ci, u32, i32, u32, i32, u32, i32, vp, ci, ci, ci, ci,
                                        ci, ci, vp],
+    "ivit_window_attention_probs_u8": [vp, vp, i64, vp, vp, ci, ci, ci, ci, ci, ci, u32, i32, u32, i32, f32, vp, vp, vp, ci, ci, vp],
+    "ivit_window_attention_probs_u8_ibert": [vp, vp, i64, vp, vp, f32, ci, ci, ci, ci, ci, u32, i32, u32, i32, vp, ci, vp],
     # evaluation transform (include/ivit_hip.h, end): the first two are host functions
     "ivit_eval_geometry": [ci, ci, ci, ci, vp],
     "ivit_resize_crop_workspace": [vp, ci, ci, vp, vp],

@@ -118,6 +118,10 @@ def occupancy_rules(path, what):
                 # window_attention_kernel<SM, RQ32, NKT>: = its __launch_bounds__.  NKT 4 (2..64 tokens): four workgroups per CU;
                 # NKT 9 (65..144 tokens): three, the 36 scores per lane stay in registers.  No scratch in either
                 occ, need_no_scratch = (4 if int(m.group(3)) == 4 else 3), True
+            elif re.search(r"window_attention_probs_kernelILi[0-3]EE", name):
+                # window_attention_probs_kernel<SM> (swin_probs.hip): rows live in LDS and every loop runs over the token count, so
+                # nothing may be indexed dynamically in registers: no scratch.  Its launcher assumes no number of resident workgroups
+                occ, need_no_scratch = 1, True
             elif "window_attention" in name:
                 print("check_resources: unknown window attention kernel", name)
                 return 1

@@ -209,6 +209,42 @@ def window_attention_ibert(a, qkv, out, ldo, nwin, nW, nH, N, H, W, win, shift, 
               HEAD_DIM, *a["ms"], *a["mb"], *a["mo"], p(a["table"]), a["band_w"], H, W, win, shift, int(image_order), st)
 
 
+def window_attention_probs(a, family, qkv, probs, nwin, nW, nH, N, st):
+    """The softmax probabilities of one window attention: the P that window_attention / window_attention_ibert multiply with V for
+    the same spec `a` (family "ivit": a window_attention_spec, "ibert": a window_attention_ibert_spec) and the same head-major qkv,
+    written to probs, uint8 [nwin, nH, N, ldp >= N] (scale 2^-7; row stride = probs.stride(-2)).  One launch."""
+    p = _lib.ptr
+    head = (p(qkv), p(probs), int(probs.stride(-2)), p(a["bias"]), p(a["region"]))
+    if family == "ibert":
+        _lib.call("ivit_window_attention_probs_u8_ibert", *head, a["masked_exp"], nwin, nW, nH, N, HEAD_DIM, *a["ms"], *a["mb"],
+                  p(a["table"]), a["band_w"], st)
+    else:
+        band = a["band"]      # form selection as window_attention: a band table first, then the phi tables, else the integer form
+        _lib.call("ivit_window_attention_probs_u8", *head, a["mask_value"], nwin, nW, nH, N, HEAD_DIM, *a["ms"], *a["mb"], a["s_attn"],
+                  p(None if band is not None else a["phi"]), p(None if band is not None else a["phim"]), p(band), a["band_w"],
+                  0 if band is None else int(band.shape[0]), st)
+
+
+def map_blocks(blocks, depths):
+    """the (stage, block) pairs of an attention_maps call, validated: None = every block; ValueError for a pair out of range or
+    repeated"""
+    every = [(li, bi) for li, d in enumerate(depths) for bi in range(d)]
+    if blocks is None:
+        return every
+    sel = []
+    for pair in blocks:
+        try:
+            li, bi = (int(v) for v in pair)
+        except (TypeError, ValueError):
+            raise ValueError(f"blocks: {pair!r} is not a (stage, block) pair") from None
+        if (li, bi) not in every:
+            raise ValueError(f"blocks: {(li, bi)} is outside the model's blocks (depths {tuple(depths)})")
+        if (li, bi) in sel:
+            raise ValueError(f"blocks: {(li, bi)} is repeated")
+        sel.append((li, bi))
+    return sel
+
+
 def pool_literal_host(q: np.ndarray, s: float) -> np.ndarray:
     """Host restatement of ivit_avgpool_requant_i8_literal's float32 mean (csrc/swin.hip, rowsum.h torch_outer_rowsum): q int8
     [B, T, C], s the input scale -> float32 [B, C], torch's CPU mean over the transposed view of y = fl(q * s) (serial order)."""
@@ -498,9 +534,29 @@ class IntSwinEngine(EngineBase):
         self._forward(images, feats=feats)
         return feats, {li: self.stages[li]["s_out"] for li in idx}
 
-    def _forward(self, images: torch.Tensor, taps: dict | None = None, topk=None, feats: dict | None = None):
+    def attention_maps(self, images: torch.Tensor, blocks=None):
+        """The integer softmax probabilities of the selected blocks -> ({(stage, block): uint8 [B, nW, nH, N, N]}, scale 2^-7): nW
+        windows per image in the order of window_partition on the rolled map, N = win * win tokens, queries and keys in window
+        order -- the tensor attn.log_int_softmax returns in the reference, divided by its scale.  blocks: (stage, block) pairs (None:
+        every block); ValueError for a pair out of range or repeated, before anything is launched.  The ordinary eager forward runs
+        (fused projection included) -- its logits stay in the workspace as after forward() -- and behind the qkv GEMM of each
+        selected block one more launch (window_attention_probs) writes the P that the fused window attention multiplies with V
+        into a fresh tensor.  Both operator families; not part of taps or of the graph replays."""
+        sel = map_blocks(blocks, self.depths)
+        B = images.shape[0]
+        maps = {}
+        for li, bi in sel:
+            stg, blk = self.stages[li], self.stages[li]["blocks"][bi]
+            N = blk["win"] * blk["win"]
+            maps[(li, bi)] = torch.empty(B, blk["attn"]["nW"], stg["nH"], N, N, dtype=torch.uint8, device=self.dev)
+        self._forward(images, maps=maps)
+        return maps, 2.0 ** -7
+
+    def _forward(self, images: torch.Tensor, taps: dict | None = None, topk=None, feats: dict | None = None,
+                 maps: dict | None = None):
         """forward; topk = (k, targets, hits): the classifier launch is the top-k selection (forward_topk).
-        feats: {stage index: [B, C, H, W]} to fill with the stream behind the last block of those stages (forward_intermediates)"""
+        feats: {stage index: [B, C, H, W]} to fill with the stream behind the last block of those stages (forward_intermediates)
+        maps: {(stage, block): uint8 [B, nW, nH, N, N]} to fill with the softmax probabilities of those blocks (attention_maps)"""
         assert images.is_cuda and images.dtype in (torch.float32, torch.uint8) and images.is_contiguous()
         B = images.shape[0]
         img = self.img_size
@@ -564,6 +620,8 @@ class IntSwinEngine(EngineBase):
                     hm = ws["qkv"][: 3 * M * C].view(3, nwin, nH, N, HEAD_DIM)
                     taps[p + "attn.qact1"] = hm.permute(1, 3, 0, 2, 4).reshape(nwin, N, 3 * C).clone()
                 a = blk["attn"]
+                if maps is not None and (li, bi) in maps:
+                    window_attention_probs(a, self.family, ws["qkv"], maps[(li, bi)], nwin, a["nW"], nH, N, st)
                 fuse_proj = self.proj_fused and taps is None
                 if self.family == "ibert":
                     window_attention_ibert(a, ws["qkv"], ws["ao"], ld, nwin, a["nW"], nH, N, H, W, win, shift, fuse_proj, st)

@@ -347,6 +347,52 @@ class SwinTransformer(EngineDispatch, ModuleGraph, nn.Module):
             x, _ = self.head(x, s)
         return x.to_float(boundary=True) if isinstance(x, lazy.QT) else x
 
+    def attention_maps(self, x, blocks=None):
+        """The integer softmax probabilities of the selected blocks -> ({(stage, block): uint8 [B, nW, nH, N, N]}, scale 2^-7): what
+        layers[stage].blocks[block].attn.log_int_softmax returns, divided by its scale -- nW windows per image in the order of
+        window_partition on the rolled map, N tokens per window, queries and keys in window order.  blocks: (stage, block) pairs
+        (None: every block); ValueError for a pair out of range or repeated.
+        Where forward() takes the fused engine this is IntSwinEngine.attention_maps: the eager engine forward plus one launch per
+        selected block.  Otherwise the modules are called one by one as the reference's forward calls them, with forward hooks on
+        the selected log_int_softmax modules, and their float output is converted back to its integers: the reference's own tensor,
+        at the module path's speed (an I-BERT model answers this way; swin_engine.engine_from_model(model).attention_maps is its
+        engine route).  8-bit softmax output only."""
+        from .swin_engine import map_blocks
+        sel = map_blocks(blocks, self.depths)
+        for layer in self.layers:
+            for blk in layer.blocks:
+                bits = int(getattr(blk.attn.log_int_softmax, "output_bit", 8))
+                if bits != 8:          # on either path, and before an engine is built for it
+                    raise ValueError(f"attention_maps: the softmax output is {bits} bits wide (8-bit probabilities only)")
+        if self.takes_engine(x):
+            return self.engine(x.shape[0]).attention_maps(x.contiguous().float(), sel)
+        maps, handles = {}, []
+        B = x.shape[0]
+
+        def hook(key):
+            def record(mod, args, out):
+                p, s = out
+                if isinstance(p, lazy.QT):
+                    p = p.to_float()
+                q = torch.round(p / s)
+                assert bool((q * s == p).all()) and bool((q >= 0).all()) and bool((q <= 128).all()), \
+                    f"layers.{key[0]}.blocks.{key[1]}.attn.log_int_softmax: the output is not an integer in [0, 128] times its scale"
+                maps[key] = q.to(torch.uint8).reshape(B, -1, *q.shape[1:]).contiguous()
+            return record
+
+        for li, bi in sel:
+            handles.append(self.layers[li].blocks[bi].attn.log_int_softmax.register_forward_hook(hook((li, bi))))
+        try:
+            with torch.no_grad():
+                if not self.is_frozen():
+                    self.invalidate_engine()
+                f, s = self.forward_features(x)
+                self.head(f, s)
+        finally:
+            for h in handles:
+                h.remove()
+        return {key: maps[key] for key in sel}, 2.0 ** -7
+
     def forward_intermediates(self, x, indices=None, integers=False):
         """The residual stream behind the last block of the selected stages as feature maps -> (maps, scales): maps = {stage: float32
         [B, C_li, H_li, W_li]}, what layers[li].blocks[-1] returns (its qact4: integers times its scale, before the patch merging),

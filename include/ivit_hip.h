@@ -685,6 +685,35 @@ int ivit_window_attention_i8_ibert(const int8_t* qkv, int8_t* out, int64_t ldo, 
                                    float masked_exp, int windows, int windows_per_image, int heads, int tokens, int head_dim,
                                    uint32_t m_s, int32_t e_s, uint32_t m_b, int32_t e_b, uint32_t m_o, int32_t e_o, const float* table,
                                    int band_w, int H, int W, int ws, int shift, int image_order, ivit_stream_t stream);
+/* The softmax probabilities of a window attention, written to memory: the P the entries above multiply with V (attention maps; an
+ * inspection path of one launch, csrc/swin_probs.hip).  probs: uint8 [nwin][heads][tokens][ldp], scale 2^-7, ldp >= tokens; row
+ * (window, head, query) holds the query's probabilities over the keys 0 .. tokens - 1, queries and keys in window order, windows in
+ * the order of window_partition on the rolled map: the tensor attn.log_int_softmax returns (swin_quant.py:121-169), divided by its
+ * scale.  Bytes tokens .. ldp - 1 of a row are never written; rows are stored as dwords where probs and ldp are multiples of four.
+ * Inputs as the entries above for every window of 2..144 tokens: qkv int8 [3][nwin][heads][tokens][32] (16-byte aligned), bias
+ * int16 [heads][tokens][kp] (16-byte aligned) and region uint8 [windows_per_image][kp] (4-byte aligned, or NULL: no shift mask; a
+ * window's row is region[win % windows_per_image]) with kp = 64 up to 64 tokens and 16 * ceil(tokens / 16) above, (m_s,e_s) of
+ * qact_attn1 and (m_b,e_b) of qact2's main operand.  Shiftmax form, as swin_engine.window_attention selects it: band != NULL with
+ * band_rows = 256 the band table [256][band_w] of ivit_window_attention_i8_band, with band_rows = 1 its one-row form (band 16-byte
+ * aligned, band_w a multiple of 16 in [16, 192]; mask_value and the phi tables are not used); else phi / phim (float32 [256] each)
+ * the literal form of ivit_window_attention_i8_compat; else the power-of-two form with the integer mask_value in [-32768, 0].  The
+ * power-of-two form places a masked score at any input scale (beyond the table of distances it evaluates exp_int itself).  A row
+ * whose exact sum of exponents reaches 2^24 takes the float32 sum in torch's order (csrc/rowsum.h), as the reference does.
+ * Errors: IVIT_ERR_UNSUPPORTED for tokens outside 2..144 or head_dim != 32; IVIT_ERR_INVALID otherwise (NULL operand, ldp < tokens,
+ * alignment, band width or rows, multipliers, window counts: windows_per_image >= 1, and nwin a multiple of it when region is
+ * given).  A rejected call writes nothing. */
+int ivit_window_attention_probs_u8(const int8_t* qkv, uint8_t* probs, int64_t ldp, const int16_t* bias, const uint8_t* region,
+                                   int mask_value, int nwin, int windows_per_image, int heads, int tokens, int head_dim,
+                                   uint32_t m_s, int32_t e_s, uint32_t m_b, int32_t e_b, float s_attn,
+                                   const float* phi, const float* phim, const uint32_t* band, int band_w, int band_rows, ivit_stream_t stream);
+/* The same for IBERTIntSoftmax (ivit_window_attention_i8_ibert, its PRECONDITION on the shift mask included): table float32 on the
+ * device, 4-byte aligned -- band_w == 0 the [256][256] table of ivit_ibert_softmax_build_table, band_w > 0 (a multiple of 16, at
+ * most 256) its band form; masked_exp the one value of a score under the shift mask.  The row sum is float32 in torch's order,
+ * factor = floor(2^32 / sum), p = floor(fl(e * factor) / 2^25) in [0, 128]; a one-hot row's 128 is the byte 0x80.  probs, layouts
+ * and errors as ivit_window_attention_probs_u8 (and masked_exp outside [0, 32768] with a region: IVIT_ERR_INVALID). */
+int ivit_window_attention_probs_u8_ibert(const int8_t* qkv, uint8_t* probs, int64_t ldp, const int16_t* bias, const uint8_t* region,
+                                         float masked_exp, int nwin, int windows_per_image, int heads, int tokens, int head_dim,
+                                         uint32_t m_s, int32_t e_s, uint32_t m_b, int32_t e_b, const float* table, int band_w, ivit_stream_t stream);
 
 /* =================================================================================================
  * I-BERT operator family (models/quantization_utils/ibert_modules.py; registry key 'ibert', the fork's default,
