@@ -84,6 +84,8 @@ SIGNATURES = {
     # Swin (include/ivit_hip.h, second half)
     "ivit_quantize_patchify_ld_f32_i8": [vp, vp, i64, ci, ci, ci, ci, f32, vp],
     "ivit_quantize_patchify_u8_i8": [vp, vp, i64, ci, ci, ci, ci, vp, vp],
+    "ivit_quantize_patchify_hw_f32_i8": [vp, vp, i64, ci, ci, ci, ci, ci, f32, vp],
+    "ivit_quantize_patchify_hw_u8_i8": [vp, vp, i64, ci, ci, ci, ci, ci, vp, vp],
     "ivit_minmax_f32": [vp, i64, vp, vp],
     "ivit_quantile_pair_f32": [vp, i64, f32, f32, vp, vp, i64, vp],
     "ivit_weight_quant_rows_f32_i8": [vp, i64, ci, ci, vp, vp, i64, vp, vp],
@@ -97,6 +99,7 @@ SIGNATURES = {
     "ivit_window_rows": [vp, vp, ci, ci, ci, i64, ci, ci, ci, vp],
     "ivit_avgpool_requant_i8": [vp, vp, ci, ci, ci, u32, i32, vp],
     "ivit_avgpool_requant_i8_literal": [vp, vp, ci, ci, ci, f32, u32, i32, vp],
+    "ivit_avgpool_f32_literal": [vp, vp, ci, ci, ci, vp],
     # I-BERT operator family (include/ivit_hip.h, last section)
     "ivit_ibert_gelu_i32": [vp, i64, f32, f32, f32, vp, vp],
     "ivit_ibert_softmax_i32": [vp, i64, ci, ci, f32, f32, f32, f32, f32, u32, i32, ci, vp, i64, vp, vp],

@@ -68,3 +68,20 @@ def load_synthetic_model(tag: str):
         cfg = synth.MODEL_CONFIGS[meta["factory"]]
         fs = sharpen_float_state(synth.make_float_state(meta["factory"], meta["weight_seed"]), meta)
     return fs, ranges, cfg, meta, z
+
+
+def load_dims_model(tag: str):
+    """-> (float_state, ranges, meta, fixture) for a fixture whose meta record carries the model's dimensions instead of a factory
+    name (scripts/gen_rect_golden.py: meta["kind"] "vit" | "swin", meta["dims"], meta["img_size"] = [height, width]).  The I-BERT
+    LayerNorm shifts the fixture holds go into the float state under their state_dict names (`<module>.shift`)."""
+    z, meta, ranges = load_fixture(tag)
+    d = meta["dims"]
+    img = tuple(meta["img_size"])
+    if meta["kind"] == "swin":
+        fs = synth.make_swin_float_state_dims(d["embed_dim"], tuple(d["depths"]), tuple(d["num_heads"]), d["window"], meta["weight_seed"],
+                                              img, meta["num_classes"])
+    else:
+        fs = synth.make_float_state_dims(d["embed_dim"], d["depth"], meta["weight_seed"], img, d["patch"], meta["num_classes"])
+    for name, sh in zip(z["shift_names"], z["shifts"]):
+        fs[str(name) + ".shift"] = np.array([sh], np.float32)
+    return fs, ranges, meta, z

@@ -133,6 +133,10 @@ def occupancy_rules(path, what):
         elif re.search(r"(embed|residual_requant)_kernelILin", name):
             # the two elementwise kernels with a clamp as template arguments (8-bit and 4-bit forms): one row each, no scratch
             occ, need_no_scratch = 1, True
+        elif "patchify_hw_kernel" in name:
+            # patchify_hw_kernel<float | uint8_t>: an elementwise grid-stride kernel whose launcher assumes no number of resident
+            # workgroups; the index chain and the four table reads stay in registers: no scratch
+            occ, need_no_scratch = 1, True
         elif "head_topk_kernel" in name:
             # the per-lane top-k lists live in registers (constant indices only): no scratch, full occupancy for any k <= 8
             occ, need_no_scratch = 8, True

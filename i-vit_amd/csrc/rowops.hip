@@ -1131,6 +1131,56 @@ __global__ __launch_bounds__(NT) void patchify_u8_kernel(const uint8_t* img, int
     }
 }
 
+// Both of the above for h x w images: img [B, chans, h, w] -> A [B*gh*gw, chans*patch*patch], row (b, py, px) at (b*gh + py)*gw + px.
+// TP = float: quant_sym_i8 per pixel; TP = uint8_t: the 3 x 256 table.  One thread owns 4 consecutive pixels of an image row (a
+// coalesced 16- or 4-byte read, a 4-byte store).  The index chain is written once over its integer type: 32-bit below 2^31 pixel
+// groups (both pixel types -- the 64-bit divisions cost more than the bytes they place), 64-bit for larger batches
+template <typename TP>
+__global__ __launch_bounds__(NT) void patchify_hw_kernel(const TP* img, int8_t* A, int64_t lda, int batch, int chans, int h, int w,
+                                                         int patch, float inv_scale, const int8_t* lut)
+{
+    constexpr bool U8 = sizeof(TP) == 1;
+    __shared__ int8_t s_lut[U8 ? 4 * 256 : 4];
+    if constexpr (U8) {
+        for (int i = threadIdx.x; i < chans * 256; i += NT) s_lut[i] = lut[i];
+        __syncthreads();
+    }
+    const unsigned gh = (unsigned)(h / patch), gw = (unsigned)(w / patch), pw4 = (unsigned)patch >> 2, w4 = (unsigned)w >> 2;
+    auto run = [&](auto q, auto total, auto stride) {
+        using IT = decltype(q);
+        for (; q < total; q += stride) {
+            // source order: q = ((b * chans + c) * h + y) * w4 + x4
+            const IT r = q / (IT)w4;
+            const unsigned x4 = (unsigned)(q - r * (IT)w4);
+            const IT r2 = r / (IT)h;
+            const unsigned y = (unsigned)(r - r2 * (IT)h);
+            const IT b = r2 / (IT)chans;
+            const unsigned c = (unsigned)(r2 - b * (IT)chans);
+            const unsigned px = x4 / pw4, kw = (x4 - px * pw4) * 4;
+            const unsigned py = y / (unsigned)patch, kh = y - py * (unsigned)patch;
+            const int64_t row = ((int64_t)b * gh + py) * gw + px;
+            const unsigned col = (c * patch + kh) * patch + kw;
+            const TP* src = img + (size_t)r * w + 4 * x4;
+            int packed;
+            if constexpr (U8) {
+                const unsigned v = *reinterpret_cast<const unsigned*>(src);
+                const int8_t* t = s_lut + 256 * c;
+                packed = pack4(t[v & 255], t[(v >> 8) & 255], t[(v >> 16) & 255], t[v >> 24]);
+            } else {
+                const float4 v = *reinterpret_cast<const float4*>(src);
+                packed = pack4(quant_sym_i8(v.x, inv_scale), quant_sym_i8(v.y, inv_scale), quant_sym_i8(v.z, inv_scale),
+                               quant_sym_i8(v.w, inv_scale));
+            }
+            *reinterpret_cast<int*>(A + row * lda + col) = packed;
+        }
+    };
+    const int64_t total = (int64_t)batch * chans * h * w4;      // groups of 4 pixels
+    if (total < 2147483648ll)      // uniform.  The grid has at most 8192 * NT threads: q + stride stays below 2^32
+        run((unsigned)(blockIdx.x * NT + threadIdx.x), (unsigned)total, (unsigned)(gridDim.x * NT));
+    else
+        run((int64_t)blockIdx.x * NT + threadIdx.x, total, (int64_t)gridDim.x * NT);
+}
+
 // cls row + position embedding, vit_quant.py:290-296 (see ivit_hip.h).  LO, HI: the clamp of qact1 ([-8, 7] at block_input_bw = 4)
 template <int LO, int HI>
 __global__ __launch_bounds__(NT) void embed_kernel(const int8_t* patch, const int16_t* pos_add, const int8_t* cls_row,
@@ -1960,6 +2010,39 @@ IVIT_EXPORT int ivit_quantize_patchify_ld_f32_i8(const float* img, int8_t* A, in
                                                  int patch, float inv_scale, ivit_stream_t stream)
 {
     return launch_patchify("ivit_quantize_patchify_ld_f32_i8", img, A, lda, batch, chans, hw, patch, inv_scale, stream);
+}
+
+// h x w images: one launcher for both pixel types (lut == nullptr: float pixels)
+template <typename TP>
+static int launch_patchify_hw(const char* who, const TP* img, int8_t* A, int64_t lda, int batch, int chans, int h, int w, int patch,
+                              float inv_scale, const int8_t* lut, ivit_stream_t stream)
+{
+    constexpr bool U8 = sizeof(TP) == 1;
+    IVIT_REQUIRE(img && A && (lut || !U8), "%s: NULL operand", who);
+    IVIT_REQUIRE(batch > 0 && chans > 0 && (!U8 || chans <= 4), "%s: batch=%d chans=%d (at least 1%s)", who, batch, chans,
+                 U8 ? ", at most 4 channels" : "");
+    IVIT_REQUIRE(patch > 0 && patch % 4 == 0 && h > 0 && w > 0 && h % patch == 0 && w % patch == 0,
+                 "%s: h=%d w=%d patch=%d (h %% patch == 0, w %% patch == 0, patch %% 4 == 0)", who, h, w, patch);
+    IVIT_REQUIRE(lda >= (int64_t)chans * patch * patch && lda % 4 == 0, "%s: lda=%lld too small or not a multiple of 4", who,
+                 (long long)lda);
+    IVIT_REQUIRE(((uintptr_t)img % (4 * sizeof(TP)) == 0) && ((uintptr_t)A % 4 == 0), "%s: misaligned", who);
+    const int64_t total = (int64_t)batch * chans * h * (w / 4);
+    hipLaunchKernelGGL(patchify_hw_kernel<TP>, dim3(ew_grid(total)), dim3(NT), 0, ivit_stream(stream), img, A, lda, batch, chans, h,
+                       w, patch, inv_scale, lut);
+    IVIT_CHECK_LAUNCH(who);
+}
+
+IVIT_EXPORT int ivit_quantize_patchify_hw_f32_i8(const float* img, int8_t* A, int64_t lda, int batch, int chans, int h, int w,
+                                                 int patch, float inv_scale, ivit_stream_t stream)
+{
+    return launch_patchify_hw<float>("ivit_quantize_patchify_hw_f32_i8", img, A, lda, batch, chans, h, w, patch, inv_scale, nullptr,
+                                     stream);
+}
+
+IVIT_EXPORT int ivit_quantize_patchify_hw_u8_i8(const uint8_t* img, int8_t* A, int64_t lda, int batch, int chans, int h, int w,
+                                                int patch, const int8_t* lut, ivit_stream_t stream)
+{
+    return launch_patchify_hw<uint8_t>("ivit_quantize_patchify_hw_u8_i8", img, A, lda, batch, chans, h, w, patch, 0.0f, lut, stream);
 }
 
 namespace {

@@ -1120,6 +1120,20 @@ __global__ __launch_bounds__(NT) void avgpool_literal_kernel(const int8_t* x, in
     }
 }
 
+// The float mean of that pooling alone, for the module path (swin_quant.py:554 on the float tensor it is handed): x [B, T, C] float32,
+// out [B, C] = the same outer-reduction sum / float32(T).  One thread per output (b, c).
+__global__ __launch_bounds__(NT) void avgpool_f32_literal_kernel(const float* x, float* out, int B, int T, int C)
+{
+    const int64_t total = (int64_t)B * C;
+    const int cfull = C & ~31;
+    for (int64_t q = (int64_t)blockIdx.x * NT + threadIdx.x; q < total; q += (int64_t)gridDim.x * NT) {
+        const int b = (int)(q / C), c = (int)(q - (int64_t)b * C);
+        const float* col = x + (int64_t)b * T * C + c;
+        const float sum = torch_outer_rowsum([&](int t) { return col[(int64_t)t * C]; }, T, c >= cfull);
+        out[q] = sum / (float)T;
+    }
+}
+
 }  // namespace
 
 // ================================================================================================
@@ -1529,4 +1543,13 @@ IVIT_EXPORT int ivit_avgpool_requant_i8_literal(const int8_t* x, int8_t* out, in
     hipLaunchKernelGGL(avgpool_literal_kernel, dim3(ew_grid((int64_t)batch * C)), dim3(NT), 0, ivit_stream(stream), x, out, batch,
                        tokens, C, s_in, Mq);
     IVIT_CHECK_LAUNCH("ivit_avgpool_requant_i8_literal");
+}
+
+IVIT_EXPORT int ivit_avgpool_f32_literal(const float* x, float* out, int batch, int tokens, int C, ivit_stream_t stream)
+{
+    IVIT_REQUIRE(x && out && batch > 0 && tokens > 0 && C > 0, "ivit_avgpool_f32_literal: bad operand");
+    IVIT_REQUIRE(((uintptr_t)x % 4 == 0) && ((uintptr_t)out % 4 == 0), "ivit_avgpool_f32_literal: misaligned");
+    hipLaunchKernelGGL(avgpool_f32_literal_kernel, dim3(ew_grid((int64_t)batch * C)), dim3(NT), 0, ivit_stream(stream), x, out, batch,
+                       tokens, C);
+    IVIT_CHECK_LAUNCH("ivit_avgpool_f32_literal");
 }

@@ -40,20 +40,24 @@ class IntViTEngine(EngineBase):
 
     def __init__(self, float_state=None, ranges=None, embed_dim: int = 768, depth: int = 12, num_heads: int = 12,
                  device="cuda:0", max_batch: int = 256, source=None, family: str = "ivit", stream_bits: int = 8,
-                 softmax_bits: int = 8, pos_bits: int = 8, img_size: int = 224, patch_size: int = 16, int_sqrt: bool = False):
+                 softmax_bits: int = 8, pos_bits: int = 8, img_size=224, patch_size: int = 16, int_sqrt: bool = False):
         """float_state: name -> float32 array (the reference's state_dict names, SURVEY Appendix D);
         ranges: QuantAct name -> (x_min, x_max) of the frozen model.  Alternatively `source`: any object with the
         FloatSource interface of export.py (e.g. export.ExportSource: integer parameters + scale table, no floats)."""
         self.C, self.D, self.H = embed_dim, depth, num_heads
-        # geometry (vit_quant.py:158-166: img_size, patch_size): square images, non-overlapping patches.  The patch GEMM steps K in
-        # 64-byte slabs.  The fused attention kernels hold a whole Shiftmax row of at most 207 keys in four lanes; I-ViT with the
+        # geometry (vit_quant.py:158-166: img_size, patch_size): images of any height and width, square non-overlapping patches.
+        # The patch GEMM steps K in 64-byte slabs.  The fused attention kernels hold a whole Shiftmax row of at most 207 keys in four lanes; I-ViT with the
         # 8-bit stream takes up to 1025 tokens (ivit_attention_fused_i8_long above 207: packed 8-bit scores)
-        self.IMG, self.P = int(img_size), int(patch_size)
-        tokens = (self.IMG // self.P) ** 2 + 1 if self.P > 0 else 0
-        if self.IMG % self.P or (3 * self.P * self.P) % 64 or tokens > self.LONG_TOKENS:
-            raise ValueError(f"geometry {self.IMG} / {self.P}: needs img_size % patch_size == 0, 3 * patch_size^2 % 64 == 0 and at most "
-                             f"{self.LONG_TOKENS} tokens")
-        self.NP = (self.IMG // self.P) ** 2
+        # img_size: an int or (height, width) (layers_quant.py:168-175); IMG keeps the int of a square model
+        ih, iw = (int(v) for v in img_size) if isinstance(img_size, (tuple, list)) else (int(img_size),) * 2
+        self.IMG_H, self.IMG_W, self.P = ih, iw, int(patch_size)
+        self.IMG = ih if ih == iw else (ih, iw)
+        tokens = (ih // self.P) * (iw // self.P) + 1 if self.P > 0 else 0
+        if self.P <= 0 or ih % self.P or iw % self.P or (3 * self.P * self.P) % 64 or tokens > self.LONG_TOKENS:
+            raise ValueError(f"geometry {self.IMG} / {self.P}: needs height and width % patch_size == 0, 3 * patch_size^2 % 64 == 0 and "
+                             f"at most {self.LONG_TOKENS} tokens")
+        self.grid = (ih // self.P, iw // self.P)
+        self.NP = self.grid[0] * self.grid[1]
         self.T = self.NP + 1
         # operator family of LayerNorm / Softmax / GELU: "ivit" (I-ViT: IVITIntLayerNorm, Shiftmax, ShiftGELU) or "ibert" (the
         # fork's default, ibert_modules.py: literal float32 sequences on fl(q * s), any activation scale)
@@ -314,9 +318,16 @@ class IntViTEngine(EngineBase):
 
     def _patchify(self, images, B, st):
         ws = self.ws
-        if images.dtype == torch.uint8:
-            if self.input_lut is None:
-                self.set_input_normalisation()
+        if images.dtype == torch.uint8 and self.input_lut is None:
+            self.set_input_normalisation()
+        if self.IMG_H != self.IMG_W:      # the h x w entries; a square model keeps the launches it always had
+            if images.dtype == torch.uint8:
+                _lib.call("ivit_quantize_patchify_hw_u8_i8", _lib.ptr(images), _lib.ptr(ws["a0"]), 3 * self.P * self.P, B, 3, self.IMG_H,
+                          self.IMG_W, self.P, _lib.ptr(self.input_lut), st)
+            else:
+                _lib.call("ivit_quantize_patchify_hw_f32_i8", _lib.ptr(images), _lib.ptr(ws["a0"]), 3 * self.P * self.P, B, 3, self.IMG_H,
+                          self.IMG_W, self.P, self.inv_s0, st)
+        elif images.dtype == torch.uint8:
             _lib.call("ivit_quantize_patchify_u8_i8", _lib.ptr(images), _lib.ptr(ws["a0"]), 3 * self.P * self.P, B, 3, self.IMG, self.P,
                       _lib.ptr(self.input_lut), st)
         else:
@@ -324,7 +335,7 @@ class IntViTEngine(EngineBase):
 
     # ------------------------------------------------------------------ forward
     def forward(self, images: torch.Tensor, taps: dict | None = None, cls_tail: bool = False):
-        """images: float32 [B,3,224,224] on the engine's device.  Returns (logits_int32 [B,classes],
+        """images: float32 (or uint8) [B,3,H,W] on the engine's device (224 x 224 unless img_size says otherwise).  Returns (logits_int32 [B,classes],
         logits_f32 [B,classes], top1 int32 [B]) -- views of the engine's workspace, valid until the
         next call.  `taps` (debug/tests) receives clones of intermediate int8 tensors.
         cls_tail: the last block on the class rows only, as the graph replays run it (tests, profiling); the same results."""
@@ -387,8 +398,8 @@ class IntViTEngine(EngineBase):
         return maps, 2.0 ** -7
 
     def forward_intermediates(self, images: torch.Tensor, indices=None, integers: bool = False):
-        """The residual stream behind the selected blocks as feature maps -> (maps, scales): maps = {index: float32 [B, C, G, G]},
-        the tensor blocks.i.qact4 returns in the reference (integers times its scale) without the class token, channels first;
+        """The residual stream behind the selected blocks as feature maps -> (maps, scales): maps = {index: float32 [B, C, Gh, Gw]}
+        (the patch grid: (H / P, W / P)), the tensor blocks.i.qact4 returns in the reference (integers times its scale) without the class token, channels first;
         integers=True: the integers themselves (int8; int16 on the 16-bit stream).  scales = {index: float}, the float32
         act_scaling_factor of blocks.i.qact4.  indices: block indices (None: every block); ValueError for one out of range or
         repeated, before anything is launched.  The ordinary eager forward runs -- its logits stay in the workspace as after
@@ -396,9 +407,9 @@ class IntViTEngine(EngineBase):
         writes the stream into a fresh tensor.  Not part of taps, of the graph replays or of cls_tail (which never computes the
         last block's stream)."""
         idx = intermediate_indices(indices, self.D, "block")
-        B, G = images.shape[0], self.IMG // self.P
+        B = images.shape[0]
         dt = torch.float32 if not integers else torch.int16 if self.stream_bits == 16 else torch.int8
-        feats = {i: torch.empty(B, self.C, G, G, dtype=dt, device=self.dev) for i in idx}
+        feats = {i: torch.empty(B, self.C, *self.grid, dtype=dt, device=self.dev) for i in idx}
         self._forward(images, feats=feats)
         return feats, {i: self.blocks[i]["s_out"] for i in idx}
 
@@ -407,7 +418,7 @@ class IntViTEngine(EngineBase):
         """forward; topk = (k, targets, hits): the classifier launch is the top-k selection (forward_topk).
         cls_tail: the last block through _cls_block (cls_tail_ok engines, no taps).
         maps: {block index: uint8 [B, H, R, T]} to fill with the softmax probabilities of those blocks (attention_maps).
-        feats: {block index: [B, C, G, G]} to fill with the stream behind those blocks, class token dropped (forward_intermediates).
+        feats: {block index: [B, C, Gh, Gw]} to fill with the stream behind those blocks, class token dropped (forward_intermediates).
         stream_bits = 4: the 8-bit dataflow; the six stream QuantActs clamp to [-8, 7] (the `_bits` entries), attention is the
         "wide" form with softmax_bits.
         stream_bits = 16: the same dataflow with an int16 residual stream.  The patch GEMM, the embedding assembly and the
@@ -415,7 +426,7 @@ class IntViTEngine(EngineBase):
         form (softmax_bits); qkv / fc1 / GELU are the int8 kernels unchanged, every operand in row-major order."""
         assert images.is_cuda and images.dtype in (torch.float32, torch.uint8) and images.is_contiguous()
         B = images.shape[0]
-        assert images.shape[1:] == (3, self.IMG, self.IMG) and 0 < B <= self.max_batch
+        assert images.shape[1:] == (3, self.IMG_H, self.IMG_W) and 0 < B <= self.max_batch
         wide = self.stream_bits == 16
         if wide and taps is not None:
             raise NotImplementedError("taps are not recorded on the 16-bit-stream path")

@@ -572,7 +572,8 @@ class QuantMatMul(nn.Module):
 
 # ----------------------------------------------------------------------------- QuantConv2d
 class QuantConv2d(nn.Conv2d):
-    """quant_modules.py:412-511, for the patch-embedding geometry (kernel == stride, no padding)."""
+    """quant_modules.py:412-511, for the patch-embedding geometry (square kernel == stride, no padding; images of any height and width
+    that are multiples of it)."""
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1, bias=True,
                  weight_bit=8, bias_bit=32, quant_mode="symmetric", per_channel=True, weight_percentile=0):
@@ -626,7 +627,7 @@ class QuantConv2d(nn.Conv2d):
                 and self.dilation == (1, 1)):
             raise NotImplementedError("QuantConv2d on the HIP path is the non-overlapping patch convolution")
         B, Cin, H, Wd = x.shape
-        assert H == Wd and H % kh == 0
+        assert H % kh == 0 and Wd % kw == 0
         s_in = lazy.taped("QuantConv2d input scale", lambda: float(pre_act_scaling_factor.reshape(-1)[0]))
         key = (self.weight._version, self.bias._version, s_in, self.weight.device)
         miss = self._cache is None or self._cache[0] != key
@@ -641,15 +642,20 @@ class QuantConv2d(nn.Conv2d):
                            _dev_table(lp.s_acc, dev))
             self._publish(lp, dev)
         _, W8, b32, s_acc = self._cache
-        g = H // kh
+        gh, gw = H // kh, Wd // kw
+        M = B * gh * gw
         K = _pad_k(Cin * kh * kw)
-        A = torch.zeros(B * g * g, K, dtype=torch.int8, device=x.device)
+        A = torch.zeros(M, K, dtype=torch.int8, device=x.device)
         xin = x.contiguous().float()
-        _lib.call("ivit_quantize_patchify_ld_f32_i8", _lib.ptr(xin), _lib.ptr(A), K, B, Cin, H, kh,
-                  float(f32(1.0) / f32(s_in)), _st())
+        if H == Wd:
+            _lib.call("ivit_quantize_patchify_ld_f32_i8", _lib.ptr(xin), _lib.ptr(A), K, B, Cin, H, kh,
+                      float(f32(1.0) / f32(s_in)), _st())
+        else:      # img_size = (H, W) of PatchEmbed (layers_quant.py:168-175)
+            _lib.call("ivit_quantize_patchify_hw_f32_i8", _lib.ptr(xin), _lib.ptr(A), K, B, Cin, H, Wd, kh,
+                      float(f32(1.0) / f32(s_in)), _st())
         N = self.out_channels
-        acc = torch.empty(B * g * g, N, dtype=torch.int32, device=x.device)
-        _lib.call("ivit_gemm_i8_i32", _lib.ptr(A), K, _lib.ptr(W8), K, _lib.ptr(b32), _lib.ptr(acc), N, B * g * g, N, K,
+        acc = torch.empty(M, N, dtype=torch.int32, device=x.device)
+        _lib.call("ivit_gemm_i8_i32", _lib.ptr(A), K, _lib.ptr(W8), K, _lib.ptr(b32), _lib.ptr(acc), N, M, N, K,
                   _st())
-        y = to_float(acc, s_acc).reshape(B, g, g, N).permute(0, 3, 1, 2).contiguous()
+        y = to_float(acc, s_acc).reshape(B, gh, gw, N).permute(0, 3, 1, 2).contiguous()
         return y, s_acc.view(1, -1, 1, 1)

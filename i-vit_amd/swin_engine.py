@@ -4,7 +4,8 @@ hand-written HIP kernel reached through the C ABI (include/ivit_hip.h, second ha
 Dataflow = the reference's frozen-model forward (/root/reference/models/swin_quant.py:539-564; WindowAttention
 :121-169; SwinTransformerBlock :251-301; PatchMerging :328-349; PatchEmbed with norm, layers_quant.py:191-203):
 
-  images f32 --quantize+im2col(4x4)--> int8 [B*3136, 48|64] --GEMM+requant--> qact_before_norm int8
+  images f32 [B, 3, H, W] (224 x 224 below; any multiple of the windows, see unsupported_geometry)
+    --quantize+im2col(4x4)--> int8 [B*3136, 48|64] --GEMM+requant--> qact_before_norm int8
     --I-LayerNorm+requant--> patch_embed.qact int8 --requant 8->16--> x int16 [B*3136, 96]
   per block { LN16->8 written in window order (partition + cyclic shift are a row map inside the kernel)
               -> GEMM qkv (+requant, head-major per window) -> window attention (bias, mask, Shiftmax, P.V)
@@ -44,24 +45,44 @@ def key_pad(N: int) -> int:
     return 64 if N <= SHORT_WINDOW else (N + 15) // 16 * 16
 
 
-def unsupported_geometry(img_size: int, patch: int, window: int, stages: int) -> str | None:
-    """None when IntSwinEngine can run this geometry: square images, patch 4, and at every stage either a map no larger than the
-    window (one window, no shift: SwinTransformerBlock's rule) or a window that divides the map, of at most 144 tokens"""
-    if patch != PATCH:
-        return f"geometry: patch {patch} (fused engine: {PATCH})"
-    if img_size % PATCH:
-        return f"geometry: image size {img_size} is not a multiple of the patch"
-    H = img_size // PATCH
+def image_hw(img_size) -> tuple:
+    """img_size as the reference takes it (to_2tuple, layers_quant.py:168): an int or a pair (height, width)"""
+    if isinstance(img_size, (tuple, list)):
+        ih, iw = img_size
+        return int(ih), int(iw)
+    return int(img_size), int(img_size)
+
+
+def block_window(H: int, W: int, window: int, bi: int) -> tuple:
+    """(window, shift) of block bi of a stage on an H x W map: SwinTransformerBlock's rule (swin_quant.py:200-203) -- a map whose
+    shorter side is no longer than the window is covered by windows of that side, unshifted"""
+    if min(H, W) <= window:
+        return min(H, W), 0
+    return window, (0 if bi % 2 == 0 else window // 2)
+
+
+def unsupported_geometry(img_size, patch, window: int, stages: int) -> str | None:
+    """None when IntSwinEngine can run this geometry: images of (height, width) or one int for both, patch 4 x 4, and at every stage
+    either a map whose shorter side is no longer than the window (windows of that side, no shift: SwinTransformerBlock's rule) or a
+    window that divides both sides; both sides a whole number of the block's windows, of at most 144 tokens, and even where the
+    stage is merged (the reference pads nothing)"""
+    ph, pw = image_hw(patch)
+    if ph != pw or ph != PATCH:
+        return f"geometry: patch {ph}x{pw} (fused engine: {PATCH}x{PATCH})"
+    ih, iw = image_hw(img_size)
+    if ih <= 0 or iw <= 0 or ih % PATCH or iw % PATCH:
+        return f"geometry: image size {ih}x{iw} is not a multiple of the patch"
+    H, W = ih // PATCH, iw // PATCH
     for li in range(stages):
-        win = min(window, H)
-        if H > window and H % window:
-            return f"geometry: stage {li} map {H}x{H} is not a whole number of {window}x{window} windows"
+        win, _ = block_window(H, W, window, 0)
+        if H % win or W % win:
+            return f"geometry: stage {li} map {H}x{W} is not a whole number of {win}x{win} windows"
         if win * win > LONG_WINDOW:
             return f"geometry: {win}x{win} windows ({win * win} tokens; fused window attention: <= {LONG_WINDOW})"
         if li < stages - 1:
-            if H % 2:
-                return f"geometry: stage {li} map {H}x{H} cannot be merged"
-            H //= 2
+            if H % 2 or W % 2:
+                return f"geometry: stage {li} map {H}x{W} cannot be merged"
+            H, W = H // 2, W // 2
     return None
 
 
@@ -287,8 +308,9 @@ def pool_literal_host(q: np.ndarray, s: float) -> np.ndarray:
 
 class IntSwinEngine(EngineBase):
     def __init__(self, float_state, ranges, embed_dim=96, depths=(2, 2, 6, 2), num_heads=(3, 6, 12, 24), window=7,
-                 device="cuda:0", max_batch: int = 64, img_size: int = 224, family: str = "ivit", int_sqrt: bool = False):
+                 device="cuda:0", max_batch: int = 64, img_size=224, family: str = "ivit", int_sqrt: bool = False):
         """float_state: name -> float32 array (the model's state_dict); ranges: QuantAct name -> (x_min, x_max) of the frozen model.
+        img_size: an int or (height, width) (swin_quant.py:462-488 through layers_quant.py:168-175).
         family: the operator family of LayerNorm / Softmax / GELU, "ivit" or "ibert" (all three); int_sqrt: IBERTIntLayerNorm's
         use_int_sqrt (layernorm_type 'ibert_use-int-sqrt_true')."""
         self.C0, self.depths, self.heads, self.window = embed_dim, tuple(depths), tuple(num_heads), window
@@ -301,7 +323,8 @@ class IntSwinEngine(EngineBase):
         why = unsupported_geometry(img_size, PATCH, window, len(self.depths))
         if why is not None:
             raise ValueError(why)
-        self.img_size = img_size
+        self.img_hw = image_hw(img_size)
+        self.img_size = self.img_hw[0] if self.img_hw[0] == self.img_hw[1] else self.img_hw      # the int of a square model
         self.dev = torch.device(device)
         self.max_batch = max_batch
         _lib.lib()  # fail loudly now if the HIP library is absent
@@ -363,8 +386,7 @@ class IntSwinEngine(EngineBase):
 
         # ---- stages
         self.stages = []
-        G = img_size // PATCH
-        H = W = G
+        H, W = self.img_hw[0] // PATCH, self.img_hw[1] // PATCH
         C = embed_dim
         for li, (depth, nH) in enumerate(zip(self.depths, self.heads)):
             if C // nH != HEAD_DIM:
@@ -372,8 +394,7 @@ class IntSwinEngine(EngineBase):
             st = dict(H=H, W=W, C=C, nH=nH, blocks=[], down=None)
             for bi in range(depth):
                 p = f"layers.{li}.blocks.{bi}."
-                win = min(window, H)
-                shift = 0 if (bi % 2 == 0 or min(H, W) <= window) else window // 2
+                win, shift = block_window(H, W, window, bi)
                 N = win * win
                 blk = dict(win=win, shift=shift)
                 s_q1 = s(p + "qact1")
@@ -458,7 +479,7 @@ class IntSwinEngine(EngineBase):
     # ------------------------------------------------------------------ plumbing
     def _alloc(self, B):
         C0 = self.C0
-        M0 = B * (self.img_size // PATCH) ** 2
+        M0 = B * (self.img_hw[0] // PATCH) * (self.img_hw[1] // PATCH)
         ld0 = _pad64(C0)
         i8 = dict(dtype=torch.int8, device=self.dev)
         i16 = dict(dtype=torch.int16, device=self.dev)
@@ -513,7 +534,7 @@ class IntSwinEngine(EngineBase):
 
     # ------------------------------------------------------------------ forward
     def forward(self, images: torch.Tensor, taps: dict | None = None):
-        """images: float32 [B,3,img_size,img_size] on the engine's device.  Returns (logits_int32 [B,1000], logits_f32, top1)
+        """images: float32 [B,3,height,width] on the engine's device.  Returns (logits_int32 [B,1000], logits_f32, top1)
         -- views of the engine's workspace, valid until the next call.  `taps` (tests) receives clones of the
         intermediate integer tensors in the reference's layouts."""
         return self._forward(images, taps)
@@ -559,13 +580,12 @@ class IntSwinEngine(EngineBase):
         maps: {(stage, block): uint8 [B, nW, nH, N, N]} to fill with the softmax probabilities of those blocks (attention_maps)"""
         assert images.is_cuda and images.dtype in (torch.float32, torch.uint8) and images.is_contiguous()
         B = images.shape[0]
-        img = self.img_size
-        assert images.shape[1:] == (3, img, img) and 0 < B <= self.max_batch
+        ih, iw = self.img_hw
+        assert images.shape[1:] == (3, ih, iw) and 0 < B <= self.max_batch
         ws = self.ws
         st = self._stream()
-        G = img // PATCH
         C0 = self.C0
-        M = B * G * G
+        M = B * (ih // PATCH) * (iw // PATCH)
 
         def tap(name, t, rows, C, ld=None, perm=None):
             if taps is None:
@@ -579,10 +599,17 @@ class IntSwinEngine(EngineBase):
         if images.dtype == torch.uint8:      # uint8 pixels: ToTensor + Normalize + the input QuantAct as a 3 x 256 table (engine.py)
             if self.input_lut is None:
                 self.set_input_normalisation()
-            _lib.call("ivit_quantize_patchify_u8_i8", _lib.ptr(images), _lib.ptr(ws["a0"]), 64, B, 3, img, PATCH,
-                      _lib.ptr(self.input_lut), st)
+            if ih != iw:      # the h x w entries; a square model keeps the launches it always had
+                _lib.call("ivit_quantize_patchify_hw_u8_i8", _lib.ptr(images), _lib.ptr(ws["a0"]), 64, B, 3, ih, iw, PATCH,
+                          _lib.ptr(self.input_lut), st)
+            else:
+                _lib.call("ivit_quantize_patchify_u8_i8", _lib.ptr(images), _lib.ptr(ws["a0"]), 64, B, 3, ih, PATCH,
+                          _lib.ptr(self.input_lut), st)
+        elif ih != iw:
+            _lib.call("ivit_quantize_patchify_hw_f32_i8", _lib.ptr(images), _lib.ptr(ws["a0"]), 64, B, 3, ih, iw, PATCH,
+                      self.inv_s0, st)
         else:
-            _lib.call("ivit_quantize_patchify_ld_f32_i8", _lib.ptr(images), _lib.ptr(ws["a0"]), 64, B, 3, img, PATCH,
+            _lib.call("ivit_quantize_patchify_ld_f32_i8", _lib.ptr(images), _lib.ptr(ws["a0"]), 64, B, 3, ih, PATCH,
                       self.inv_s0, st)
         self._gemm(ws["a0"], 64, self.patch, ws["pe"], C0, M, st)
         tap("patch_embed.qact_before_norm", ws["pe"], M, C0)
@@ -705,6 +732,12 @@ class IntSwinEngine(EngineBase):
     __call__ = forward
 
 
+def _model_img_size(model):
+    """img_size of a SwinTransformer as the engine takes it: the int of a square model (today's argument), else (height, width)"""
+    ih, iw = model.patch_embed.img_size
+    return ih if ih == iw else (ih, iw)
+
+
 def operator_family(model):
     """("ivit" | "ibert", int_sqrt) of a SwinTransformer whose three operators IntSwinEngine implements together; raises ValueError
     with the reason for a mixture of families and for a constructor parameter in an operator name other than the I-BERT LayerNorm's
@@ -736,4 +769,4 @@ def engine_from_model(model, device=None, max_batch: int = 64):
     # a plain I-ViT model's engine is built with the arguments SwinTransformer._build_engine passes
     ops = dict(family=family, int_sqrt=int_sqrt) if family == "ibert" else {}
     return IntSwinEngine(dict(model.state_dict()), model.ranges(), model.embed_dim, model.depths, model.num_heads, model.window_size,
-                         device=device, max_batch=max_batch, img_size=model.patch_embed.img_size[0], **ops)
+                         device=device, max_batch=max_batch, img_size=_model_img_size(model), **ops)

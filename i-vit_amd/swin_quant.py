@@ -22,9 +22,11 @@ from typing import Optional
 import torch
 from torch import nn
 
+from . import _lib
 from .dispatch import EngineDispatch
 from .graph import ModuleGraph
 from .layers_quant import DropPath, Mlp, PatchEmbed, to_2tuple, trunc_normal_
+from .prepare import phi_is_identity
 from .quantization_utils import IntGELU, IntSoftmax, QuantAct, QuantLinear, QuantMatMul, get_gelu, get_layernorm, get_softmax, lazy
 from .quantization_utils.layer_selection import _parse_layer_name
 
@@ -294,9 +296,28 @@ class SwinTransformer(EngineDispatch, ModuleGraph, nn.Module):
             x, s = layer(x, s)
         x, s = self.norm(x, s)
         x, s = self.qact2(x, s)
-        x = self.avgpool(x.transpose(1, 2))                       # [B, C, 1] float mean over the tokens
+        x = self._pool_tokens(x, s)                               # [B, C, 1] float mean over the tokens
         x, s = self.qact3(x.transpose(1, 2), s)                   # channels last for the per-tensor requant kernel
         return torch.flatten(x, 1), s
+
+    def _pool_tokens(self, x, s):
+        """avgpool(x.transpose(1, 2)) of swin_quant.py:554 -> [B, C, 1].  An even token count can put a column's float mean on an
+        exact .5 tie of qact3, which the order of the float32 sum then decides: the reference's is torch's CPU reduction over the
+        transposed view, CUDA's mean rounds some of those columns the other way.  Where that can happen -- a tensor on the GPU, an even
+        count, a scale s with fl(fl(q s) / s) != q for some q -- the mean is taken in the CPU's order (ivit_avgpool_f32_literal, the sum
+        the fused engine's literal pooling forms), for a dense [B, T, C] tensor; everywhere else the call is the reference's."""
+        B, T, C = x.shape
+        if x.is_cuda and T % 2 == 0:
+            host = lazy.host_of(s)
+            s_in = float(host.reshape(-1)[0]) if host is not None else lazy.taped("Swin pooling scale", lambda: float(s.reshape(-1)[0]))
+            if not phi_is_identity(s_in):
+                xf = x.to_float() if isinstance(x, lazy.QT) else x
+                if xf.dtype == torch.float32 and xf.is_contiguous():
+                    out = torch.empty(B, C, dtype=torch.float32, device=xf.device)
+                    _lib.call("ivit_avgpool_f32_literal", _lib.ptr(xf), _lib.ptr(out), B, T, C, _lib.stream_ptr())
+                    return out.unsqueeze(-1)
+                return self.avgpool(xf.transpose(1, 2))
+        return self.avgpool(x.transpose(1, 2))
 
     # ---------------------------------------------------------------- fused engine path (dispatch.py)
     _frozen_exempt = ("act_out",)      # constructed by the reference (swin_quant.py:518) and never called
@@ -324,16 +345,16 @@ class SwinTransformer(EngineDispatch, ModuleGraph, nn.Module):
         from .swin_engine import unsupported_geometry
         ih, iw = self.patch_embed.img_size
         ph, pw = self.patch_embed.patch_size
-        if ih != iw or ph != pw:
-            return f"geometry: {ih}x{iw} images, {ph}x{pw} patches (fused engine: square)"
+        if ph != pw:
+            return f"geometry: {ph}x{pw} patches (fused engine: square patches)"
         # an even token count of the tail pooling (swin_quant.py:554) can put its float mean on an exact .5 tie; at natural scales the
         # engine then runs the literal pooling in torch's CPU order (ivit_avgpool_requant_i8_literal)
-        return unsupported_geometry(ih, ph, self.window_size, self.num_layers)
+        return unsupported_geometry((ih, iw), ph, self.window_size, self.num_layers)
 
     def _build_engine(self, device, max_batch):
-        from .swin_engine import IntSwinEngine
+        from .swin_engine import IntSwinEngine, _model_img_size
         return IntSwinEngine(dict(self.state_dict()), self.ranges(), self.embed_dim, self.depths, self.num_heads,
-                             self.window_size, device=device, max_batch=max_batch, img_size=self.patch_embed.img_size[0])
+                             self.window_size, device=device, max_batch=max_batch, img_size=_model_img_size(self))
 
     def forward(self, x):
         if self.takes_engine(x):

@@ -70,8 +70,16 @@ def _uniform(seed, name, shape, lo, hi):
 def make_float_state(model: str, seed: int = 0, depth: int | None = None) -> "OrderedDict[str, np.ndarray]":
     """Float32 parameters with the reference's state_dict names."""
     cfg = MODEL_CONFIGS[model]
-    C = cfg["embed_dim"]
-    D = cfg["depth"] if depth is None else depth
+    return make_float_state_dims(cfg["embed_dim"], cfg["depth"] if depth is None else depth, seed)
+
+
+def make_float_state_dims(embed_dim: int, depth: int, seed: int = 0, img_size=IMG_SIZE, patch: int = PATCH,
+                          num_classes: int = NUM_CLASSES) -> "OrderedDict[str, np.ndarray]":
+    """make_float_state for explicit dimensions: img_size an int or (height, width).  A tensor's values depend on (seed, its name)
+    and its shape alone, so the named models above are this function at 224 / 16."""
+    ih, iw = tuple(img_size) if isinstance(img_size, (tuple, list)) else (img_size, img_size)
+    C, D, PATCH, NUM_CLASSES = embed_dim, depth, patch, num_classes
+    NUM_TOKENS = (ih // patch) * (iw // patch) + 1
     sd: "OrderedDict[str, np.ndarray]" = OrderedDict()
 
     def lin(prefix, out_f, in_f, gain=1.0):
@@ -99,11 +107,12 @@ def make_float_state(model: str, seed: int = 0, depth: int | None = None) -> "Or
     return sd
 
 
-def make_images(batch: int, seed: int, start: int = 0) -> np.ndarray:
-    """float32 N(0,1) images [batch,3,224,224]; image i depends only on (seed, start+i)."""
-    out = np.empty((batch, 3, IMG_SIZE, IMG_SIZE), dtype=np.float32)
+def make_images(batch: int, seed: int, start: int = 0, img_size=IMG_SIZE) -> np.ndarray:
+    """float32 N(0,1) images [batch,3,224,224] (img_size: an int or (height, width)); image i depends only on (seed, start+i)."""
+    ih, iw = tuple(img_size) if isinstance(img_size, (tuple, list)) else (img_size, img_size)
+    out = np.empty((batch, 3, ih, iw), dtype=np.float32)
     for i in range(batch):
-        out[i] = _rng(seed, f"image.{start + i}").standard_normal(size=(3, IMG_SIZE, IMG_SIZE)).astype(np.float32)
+        out[i] = _rng(seed, f"image.{start + i}").standard_normal(size=(3, ih, iw)).astype(np.float32)
     return out
 
 
@@ -139,7 +148,19 @@ REL_POS_STD = 0.5   # reference init is 0.02 (swin_quant.py:112); widened so the
 def make_swin_float_state(model: str, seed: int = 0) -> "OrderedDict[str, np.ndarray]":
     """Float32 parameters with the reference's Swin state_dict names."""
     cfg = SWIN_CONFIGS[model]
-    C0, depths, heads, ws = cfg["embed_dim"], cfg["depths"], cfg["num_heads"], cfg["window"]
+    return make_swin_float_state_dims(cfg["embed_dim"], cfg["depths"], cfg["num_heads"], cfg["window"], seed)
+
+
+def make_swin_float_state_dims(embed_dim: int, depths, num_heads, window: int, seed: int = 0, img_size=None,
+                               num_classes: int = NUM_CLASSES) -> "OrderedDict[str, np.ndarray]":
+    """make_swin_float_state for explicit dimensions.  img_size (an int or (height, width), patch 4): a stage whose map's shorter
+    side is no longer than the window has windows of that side (swin_quant.py:200-203), which sizes its relative position bias
+    tables; None: every table is (2 * window - 1)^2, as for the named models above."""
+    C0, heads, NUM_CLASSES = embed_dim, num_heads, num_classes
+    grid = None
+    if img_size is not None:
+        ih, iw = tuple(img_size) if isinstance(img_size, (tuple, list)) else (img_size, img_size)
+        grid = (ih // 4, iw // 4)
     sd: "OrderedDict[str, np.ndarray]" = OrderedDict()
 
     def lin(prefix, out_f, in_f, gain=1.0, bias=True):
@@ -156,6 +177,7 @@ def make_swin_float_state(model: str, seed: int = 0) -> "OrderedDict[str, np.nda
     ln("patch_embed.norm", C0)
     for li, (depth, nh) in enumerate(zip(depths, heads)):
         C = C0 * 2 ** li
+        ws = window if grid is None else min(window, grid[0] >> li, grid[1] >> li)
         for bi in range(depth):
             p = f"layers.{li}.blocks.{bi}."
             ln(p + "norm1", C)

@@ -193,11 +193,13 @@ class VisionTransformer(EngineDispatch, ModuleGraph, nn.Module):
         if self.embed_dim // self.num_heads != 64 or self.embed_dim % 64:
             return "head_dim != 64"
         img, patch = self.geometry[0], self.geometry[1]
-        if (self.geometry[2:] != (3, 4.0, True, None) or not isinstance(img, int) or not isinstance(patch, int) or img % patch
-                or (3 * patch * patch) % 64 or (img // patch) ** 2 + 1 > 1025):
-            return (f"geometry {self.geometry} (fused engine: square images, 3 channels, img_size % patch_size == 0, "
+        # img_size: an int or a pair (height, width) (vit_quant.py:204-214 through layers_quant.py:168-175)
+        ih, iw = img if isinstance(img, (tuple, list)) and len(img) == 2 else (img, img)
+        if (self.geometry[2:] != (3, 4.0, True, None) or not isinstance(ih, int) or not isinstance(iw, int) or not isinstance(patch, int)
+                or patch <= 0 or ih % patch or iw % patch or (3 * patch * patch) % 64 or (ih // patch) * (iw // patch) + 1 > 1025):
+            return (f"geometry {self.geometry} (fused engine: square patches, 3 channels, height and width % patch_size == 0, "
                     "3 * patch_size^2 % 64 == 0, at most 1025 tokens, mlp_ratio 4, qkv bias)")
-        tokens = (img // patch) ** 2 + 1
+        tokens = (ih // patch) * (iw // patch) + 1
         if self.num_classes <= 0:
             return "no classification head"
         # every QuantAct of the DeiT / ViT engine is 8 bit, except the 16-bit one inside IBERTIntSoftmax (ibert_modules.py:247) ...
@@ -300,8 +302,8 @@ class VisionTransformer(EngineDispatch, ModuleGraph, nn.Module):
         return {i: maps[i] for i in layers}, 2.0 ** -7
 
     def forward_intermediates(self, x, indices=None, integers=False):
-        """The residual stream behind the selected blocks as feature maps -> (maps, scales): maps = {index: float32 [B, C, G, G]},
-        what blocks[i] returns (blocks.i.qact4: integers times its scale) without the class token, channels first; integers=True:
+        """The residual stream behind the selected blocks as feature maps -> (maps, scales): maps = {index: float32 [B, C, Gh, Gw]}
+        (patch_embed.grid_size), what blocks[i] returns (blocks.i.qact4: integers times its scale) without the class token, channels first; integers=True:
         the integers (int8; int16 where that QuantAct is wider than 8 bits).  scales = {index: float}, its float32
         act_scaling_factor.  indices: block indices (None: every block); ValueError for one out of range or repeated.
         Where forward() takes the fused engine this is IntViTEngine.forward_intermediates: the eager engine forward plus one
@@ -311,8 +313,8 @@ class VisionTransformer(EngineDispatch, ModuleGraph, nn.Module):
         idx = intermediate_indices(indices, self.depth, "block")
         if self.takes_engine(x):
             return self.engine(x.shape[0]).forward_intermediates(x.contiguous().float(), idx, integers)
-        G = self.geometry[0] // self.geometry[1]
-        got = self._hooked_intermediates(x, {i: (self.blocks[i], f"blocks.{i}", self.blocks[i].qact4, 1, (G, G)) for i in idx}, integers)
+        grid = tuple(self.patch_embed.grid_size)
+        got = self._hooked_intermediates(x, {i: (self.blocks[i], f"blocks.{i}", self.blocks[i].qact4, 1, grid) for i in idx}, integers)
         return {i: got[i][0] for i in idx}, {i: got[i][1] for i in idx}
 
 

@@ -116,6 +116,18 @@ int ivit_quantize_patchify_ld_f32_i8(const float* img, int8_t* A, int64_t lda, i
  * the results are identical to the float path on the same pixels and the input is a quarter of the bytes. */
 int ivit_quantize_patchify_u8_i8(const uint8_t* img, int8_t* A, int64_t lda, int batch, int chans, int hw, int patch,
                                  const int8_t* lut, ivit_stream_t stream);
+/* The two above for images that are not square (img_size = (h, w) of PatchEmbed, layers_quant.py:168-175):
+ *   img [batch, chans, h, w] -> A [batch*(h/patch)*(w/patch), chans*patch*patch] int8 with row stride lda,
+ *   row (b, py, px) at (b * (h/patch) + py) * (w/patch) + px, column order (c, kh, kw) as above; columns [K, lda) are not written.
+ * Every element is computed as in the square forms (h == w gives their bytes): quant_sym of float pixels with inv_scale, the
+ * 3 x 256 table `lut` for uint8 pixels (at most 4 channels).
+ * Errors: IVIT_ERR_INVALID for a NULL pointer, batch or chans below 1, h or w not a multiple of patch, patch not a multiple of 4
+ * (one thread moves 4 consecutive pixels of a row), lda below chans*patch*patch or not a multiple of 4, a misaligned pointer
+ * (img: 4 pixels; A: 4 bytes). */
+int ivit_quantize_patchify_hw_f32_i8(const float* img, int8_t* A, int64_t lda, int batch, int chans, int h, int w, int patch,
+                                     float inv_scale, ivit_stream_t stream);
+int ivit_quantize_patchify_hw_u8_i8(const uint8_t* img, int8_t* A, int64_t lda, int batch, int chans, int h, int w, int patch,
+                                    const int8_t* lut, ivit_stream_t stream);
 
 /* ---- INT8 GEMM on v_mfma_i32_32x32x32_i8 with fused epilogues -------------------------------
  * QuantLinear.forward / QuantConv2d.forward (quant_modules.py:186-226, 478-511) followed by
@@ -596,6 +608,10 @@ int ivit_avgpool_requant_i8(const int8_t* x, int8_t* out, int batch, int tokens,
  * when batch >= the thread count (same order), else along the columns (a different order for the tail columns). */
 int ivit_avgpool_requant_i8_literal(const int8_t* x, int8_t* out, int batch, int tokens, int C, float s_in, uint32_t m, int32_t e,
                                     ivit_stream_t stream);
+/* The float mean of that pooling alone, for a caller that holds the float tensor (the module path's avgpool(x.transpose(1, 2)) on the
+ * GPU): x [batch, tokens, C] float32, dense; out [batch, C] = the same outer-reduction sum over the tokens / float32(tokens).
+ * Errors: IVIT_ERR_INVALID for a NULL or misaligned (4 bytes) pointer or a dimension below 1. */
+int ivit_avgpool_f32_literal(const float* x, float* out, int batch, int tokens, int C, ivit_stream_t stream);
 
 /* WindowAttention core (swin_quant.py:137-161): matmul_1 -> qact_attn1 -> + relative position bias through the
  * two-operand qact2 -> + shift mask -> Shiftmax -> matmul_2 -> qact3, one wave per (window, head).
