@@ -144,7 +144,14 @@ int ivit_quantize_patchify_hw_u8_i8(const uint8_t* img, int8_t* A, int64_t lda, 
  * -- the order in which the GEMM's LDS-DMA lays a piece into its LDS stage, so that one instruction reads 1 KB
  * contiguous.  Rows padded to a multiple of 16 (ceil(rows / 16) * 16 * K bytes), K % 64 == 0.  The `_ex` forms take
  * `layouts` = IVIT_A_BLOCKS | IVIT_W_BLOCKS; block operands need M >= 2048 and N >= 128.  Producers that can write the
- * block layout directly: ivit_layernorm_i8_ex, ivit_attention_fused_i8_ex, ivit_shiftgelu_lut_i8_ex. */
+ * block layout directly: ivit_layernorm_i8_ex, ivit_attention_fused_i8_ex, ivit_shiftgelu_lut_i8_ex.  Block offsets are 32-bit: every
+ * entry that writes the layout wants (rows + 15) * K < 2^31 and is IVIT_ERR_INVALID beyond.
+ *
+ * Operands of 2 GiB and more.  Leading dimensions and flat sizes are int64_t and row-major operands are addressed in 64 bits: a row
+ * may start at any byte offset.  The exceptions are stated where they apply and refuse (IVIT_ERR_INVALID, nothing launched): the
+ * block layout above, IVIT_W_FRAGS16 below, and the dense head-major q/k/v outputs (M * N < 2^31 bytes; planes form
+ * 3 * M * heads * head_dim < 2^31).  Fast paths with 32-bit offsets that have a 64-bit form behind them (the streaming int8
+ * LayerNorm below 2^31 bytes per matrix, the skinny-K GEMM below M * ldo = 2^32) fall back to it without a visible difference. */
 #define IVIT_A_BLOCKS 1
 #define IVIT_W_BLOCKS 2
 #define IVIT_OUT_BLOCKS 4   /* ivit_gemm_i8_requant_ex only: the int8 output in the block layout (ldo == N, N % 64 == 0) */
@@ -159,7 +166,9 @@ int ivit_pack_weight_frags_i8(const int8_t* W, int64_t ldw, int N, int K, int8_t
 /* IVIT_W_FRAGS16: the same idea for v_mfma_i32_16x16x64_i8 (the chip holds a higher clock on that shape under the power limit:
  * DESIGN.md section 5): channel n, byte k at ((n / 64) * (K / 64) + k / 64) * 4096 + ((n / 16) % 4) * 1024 + ((k / 16) % 4) * 256
  * + (n % 16) * 16 + k % 16 (copy made by ivit_pack_weight_frags16_i8; same size, same constraints as IVIT_W_FRAGS; the two bits
- * exclude each other).  Accepted by the int8-output `_ex` forms (requant, requant_lut, residual, residual_i16, qkv). */
+ * exclude each other).  Accepted by the int8-output `_ex` forms (requant, requant_lut, residual, residual_i16, qkv).  Its epilogue
+ * addresses the output and the residual with 32-bit byte offsets: (M + 16) * ldo < 2^32 and (M + 16) * ldr < 2^32, otherwise
+ * IVIT_ERR_INVALID (IVIT_W_FRAGS has no such bound). */
 #define IVIT_W_FRAGS16 16
 int ivit_pack_weight_frags16_i8(const int8_t* W, int64_t ldw, int N, int K, int8_t* dst, ivit_stream_t stream);
 int ivit_tile_operand_i8(const int8_t* src, int64_t ld, int64_t rows, int K, int8_t* dst, ivit_stream_t stream);
@@ -592,7 +601,8 @@ int ivit_patch_merge_i16(const int16_t* x, int16_t* out, int batch, int H, int W
  * bytes, int16 rows of 2C bytes): src, dst [batch * H * W, row_bytes].
  *   inverse = 0: dst row (b, wy, wx, iy, ix), window order, = src row (b, (wy ws + iy + shift) % H, (wx ws + ix + shift) % W)
  *   inverse = 1: dst row (b, (wy ws + iy + shift) % H, (wx ws + ix + shift) % W) = src row (b, wy, wx, iy, ix)
- * Refused: NULL pointers or pointers not aligned to 16 bytes, row_bytes % 16 != 0, H % ws or W % ws != 0, shift outside [0, ws),
+ * Refused: NULL pointers or pointers not aligned to 16 bytes, row_bytes % 16 != 0 or row_bytes > 2^20 (the chunk index of a row is
+ * 32-bit; rows * row_bytes is 64-bit and may pass 4 GiB), H * W > 2^30, H % ws or W % ws != 0, shift outside [0, ws),
  * overlapping src and dst (src == dst among them: the pass is not in place). */
 int ivit_window_rows(const void* src, void* dst, int batch, int H, int W, int64_t row_bytes, int ws, int shift, int inverse,
                      ivit_stream_t stream);
