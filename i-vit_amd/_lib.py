@@ -135,6 +135,10 @@ SIGNATURES = {
     "ivit_eval_geometry": [ci, ci, ci, ci, vp],
     "ivit_resize_crop_workspace": [vp, ci, ci, vp, vp],
     "ivit_resize_crop_bicubic_u8": [vp, vp, vp, ci, ci, ci, ci, ci, vp, i64, vp, vp],
+    # ... with an h x w crop, an exact-size resize and zero padding: the first two are host functions
+    "ivit_eval_geometry_hw": [ci, ci, ci, ci, ci, ci, ci, vp],
+    "ivit_resize_crop_workspace_hw": [vp, ci, ci, ci, vp, vp],
+    "ivit_resize_crop_bicubic_hw_u8": [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, i64, vp, vp],
     # JPEG decoding (include/ivit_hip.h, end): the first four are host functions
     "ivit_jpeg_probe": [vp, i64, vp],
     "ivit_jpeg_plan_image": [vp, i64, vp, i64, vp],

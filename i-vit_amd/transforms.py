@@ -3,12 +3,15 @@ Resize(s, BICUBIC) -> CenterCrop(c) -> ToTensor -> Normalize, without torchvisio
 
 ImageFolderU8 decodes on the CPU; ImageFolderJPEG hands the compressed bytes on, and EvalTransform decodes baseline JPEGs on the
 device (ivit_jpeg_decode_u8, byte-identical to Image.open(f).convert("RGB")), every other file in the loader worker with Pillow.
-The resize and crop run in ivit_resize_crop_bicubic_u8 and are byte-identical to Pillow's resize plus torchvision's CenterCrop.  The fused engines take the uint8 crops as they are (their input table folds
+The resize and crop run in ivit_resize_crop_bicubic_u8 (h x w crops, an exact-size Resize((h, w)) and CenterCrop's zero padding:
+ivit_resize_crop_bicubic_hw_u8) and are byte-identical to Pillow's resize plus torchvision's CenterCrop.  The fused engines take the uint8 crops as they are (their input table folds
 ToTensor + Normalize + the input QuantAct); the module path takes EvalTransform.to_float(crops), the float32 tensor ToTensor +
 Normalize would give.
 
     loader = torch.utils.data.DataLoader(ImageFolderU8(root), batch_size=256, collate_fn=ImageFolderU8.collate)
     inference.evaluate_dataset_parallel(model, loader, "cuda", transform=EvalTransform.for_input_size(224))
+
+EvalTransform.for_model(model) is the transform of the model's own image size, square or h x w.
 
 ImageFolderJPEG / ImageFolderJPEG.collate in place of ImageFolderU8 / ImageFolderU8.collate decode on the device instead.
 """
@@ -39,10 +42,64 @@ def eval_geometry(h: int, w: int, resize: int, crop: int):
     return tuple(int(v) for v in out)
 
 
+def _key(v, what):
+    """an int or a pair (h, w) in the form a geometry cache key and an EvalTransform hold: a scalar becomes an int, a pair a tuple
+    of two ints"""
+    try:
+        a, b = v
+    except TypeError:
+        return int(v)
+    except ValueError:
+        raise ValueError(f"{what} must be an int or a pair (h, w), got {v!r}") from None
+    return int(a), int(b)
+
+
+def _pair(v, what):
+    """an int n -> (n, n); a pair -> (int, int)"""
+    k = _key(v, what)
+    return (k, k) if isinstance(k, int) else k
+
+
+def eval_geometry_hw(h: int, w: int, resize, crop, pad: bool = False):
+    """(new_h, new_w, top, left) of Resize(resize) + CenterCrop(crop) for an h x w image, the library's ivit_eval_geometry_hw (a host
+    function: the rule exists once).  resize: an int (the short side goes to it) or a pair (exactly that size); crop: an int or a
+    pair (h, w).  Where a crop side is longer than the resized image torchvision pads with zeros: with pad the offset on that axis
+    is minus the zeros in front, -((c - n) // 2); without it the geometry is unsupported.  ValueError for an unsupported geometry."""
+    resize = _key(resize, "resize")
+    if isinstance(resize, int):
+        rh, rw = resize, 0            # the library's spelling of the short-side rule
+    else:
+        rh, rw = resize
+        if rw < 1:
+            raise ValueError(f"unsupported geometry (resize {rh} x {rw})")
+    ch, cw = _pair(crop, "crop")
+    out = (C.c_int32 * 4)()
+    L = _lib.lib()
+    rc = L.ivit_eval_geometry_hw(int(h), int(w), rh, rw, ch, cw, int(bool(pad)), out)
+    if rc != 0:
+        raise ValueError(L.ivit_last_error_string().decode())
+    return tuple(int(v) for v in out)
+
+
+def _geometry_rows(sizes, cache, resize, crop, pad):
+    """int32 [B, 6] rows (h, w, new_h, new_w, top, left) of a batch, cached under the full (resize, crop, pad) tuple.  Two ints
+    without pad go through eval_geometry (the square rule and its refusals), everything else through eval_geometry_hw."""
+    key = (_key(resize, "resize"), _key(crop, "crop"), bool(pad))
+    g = cache.get(key)
+    if g is None:
+        square = isinstance(key[0], int) and isinstance(key[1], int) and not key[2]
+        g = np.empty((len(sizes), 6), np.int32)
+        for b, (h, w) in enumerate(sizes):
+            g[b, :2] = (h, w)
+            g[b, 2:] = eval_geometry(h, w, key[0], key[1]) if square else eval_geometry_hw(h, w, key[0], key[1], key[2])
+        cache[key] = g
+    return g
+
+
 @dataclass
 class PackedImages:
     """A batch of decoded RGB images in one flat uint8 buffer (HWC, image b at data[offsets[b]:]), their sizes, and the per-image
-    geometry rows the device transform takes (cached per (resize, crop))."""
+    geometry rows the device transform takes (cached per (resize, crop, pad))."""
     data: torch.Tensor          # uint8 [total bytes], pinned when a GPU is present
     offsets: np.ndarray         # int64 [B]
     sizes: np.ndarray           # int32 [B, 2]: (h, w)
@@ -56,17 +113,9 @@ class PackedImages:
             raise IndexError("PackedImages has one dimension: images")
         return len(self)
 
-    def geometry(self, resize: int, crop: int) -> np.ndarray:
-        """int32 [B, 6]: (h, w, new_h, new_w, top, left) per image"""
-        key = (int(resize), int(crop))
-        g = self._geom.get(key)
-        if g is None:
-            g = np.empty((len(self), 6), np.int32)
-            for b, (h, w) in enumerate(self.sizes):
-                g[b, :2] = (h, w)
-                g[b, 2:] = eval_geometry(h, w, resize, crop)
-            self._geom[key] = g
-        return g
+    def geometry(self, resize, crop, pad: bool = False) -> np.ndarray:
+        """int32 [B, 6]: (h, w, new_h, new_w, top, left) per image; resize and crop an int or a pair (h, w), as eval_geometry_hw"""
+        return _geometry_rows(self.sizes, self._geom, resize, crop, pad)
 
 
 def pack_images(images, pin: bool | None = None) -> PackedImages:
@@ -94,31 +143,68 @@ def pack_images(images, pin: bool | None = None) -> PackedImages:
 
 class EvalTransform:
     """Resize(resize, BICUBIC) -> CenterCrop(crop) on the device; mean / std are the Normalize the model was trained behind.
-    transform(packed, lo, hi) -> device uint8 [hi - lo, 3, crop, crop] of images [lo, hi) of the packed batch."""
+    transform(packed, lo, hi) -> device uint8 [hi - lo, 3, crop_h, crop_w] of images [lo, hi) of the packed batch.
 
-    def __init__(self, resize: int = 256, crop: int = 224, mean=IMAGENET_MEAN, std=IMAGENET_STD):
-        self.resize, self.crop = int(resize), int(crop)
-        if self.crop <= 32:
+    resize: an int (torchvision Resize([s]): the short side goes to s) or a pair (h, w) (Resize((h, w)): exactly that size, whatever
+    the image's aspect ratio -- how Swin's 384 px checkpoints are evaluated).  crop: an int or a pair (h, w).  pad: torchvision's
+    CenterCrop pads with zeros where the crop is longer than the resized image; that has to be asked for.  Without pad, a
+    combination under which some image would be padded is refused here, before any image is seen.  .resize and .crop keep the
+    form they were given in (ints stay ints); .crop_hw is always the pair."""
+
+    def __init__(self, resize=256, crop=224, mean=IMAGENET_MEAN, std=IMAGENET_STD, pad: bool = False):
+        self.resize, self.crop, self.pad = _key(resize, "resize"), _key(crop, "crop"), bool(pad)
+        self.crop_hw = _pair(self.crop, "crop")
+        # two ints without pad: ivit_resize_crop_bicubic_u8 and its rules, as before there were pairs
+        self._square = isinstance(self.resize, int) and isinstance(self.crop, int) and not self.pad
+        if min(self.crop_hw) <= 32:
             raise ValueError(f"crop {self.crop} <= 32: input sizes without a resize (CIFAR) are not supported")
-        if self.crop > self.resize:
-            raise ValueError(f"crop {self.crop} > resize {self.resize}: torchvision would pad")
+        if not self.pad:
+            # Resize([s]) leaves both sides >= s, and the short one at s; Resize((h, w)) leaves exactly (h, w)
+            if isinstance(self.resize, int) and max(self.crop_hw) > self.resize:
+                raise ValueError(f"crop {self.crop} > resize {self.resize}: torchvision would pad")
+            if not isinstance(self.resize, int) and (self.crop_hw[0] > self.resize[0] or self.crop_hw[1] > self.resize[1]):
+                raise ValueError(f"crop {self.crop} > resize {self.resize}: torchvision would pad (pass pad=True)")
+        if min(_pair(self.resize, "resize")) < 1:
+            raise ValueError(f"resize {self.resize} < 1")
         self.mean, self.std = tuple(float(v) for v in mean), tuple(float(v) for v in std)
         self._ws = {}
         self._tables = {}
 
     @classmethod
-    def for_input_size(cls, n: int, mean=IMAGENET_MEAN, std=IMAGENET_STD):
-        """utils/data_utils.py build_transform: Resize(int(256 / 224 * n)) -> CenterCrop(n) (384 -> 438 / 384)"""
-        if n <= 32:
-            raise ValueError(f"input size {n} <= 32: the reference does not resize there (out of scope)")
-        return cls(int((256 / 224) * n), n, mean, std)
+    def for_input_size(cls, n, mean=IMAGENET_MEAN, std=IMAGENET_STD):
+        """utils/data_utils.py build_transform: Resize(int(256 / 224 * n)) -> CenterCrop(n) (384 -> 438 / 384).
+
+        n = (h, w): Resize(int(256 / 224 * max(h, w))) -> CenterCrop((h, w)).  The reference has no rule for h != w; max is chosen
+        because (1) Resize([s]) leaves both sides of every image at least s, so s >= max(h, w) is the only choice of the reference's
+        form under which no image is ever padded, whatever its aspect ratio (with min(h, w), a portrait image into a landscape crop
+        would be), and (2) it is the reference's rule at h == w."""
+        n = _key(n, "input size")
+        if isinstance(n, int):
+            if n <= 32:
+                raise ValueError(f"input size {n} <= 32: the reference does not resize there (out of scope)")
+            return cls(int((256 / 224) * n), n, mean, std)
+        h, w = n
+        if min(h, w) <= 32:
+            raise ValueError(f"input size {h} x {w} <= 32: the reference does not resize there (out of scope)")
+        return cls(int((256 / 224) * max(h, w)), (h, w), mean, std)
+
+    @classmethod
+    def for_model(cls, model, mean=IMAGENET_MEAN, std=IMAGENET_STD):
+        """for_input_size of the model's own image size (VisionTransformer, SwinTransformer: patch_embed.img_size); a square model
+        gets the int form, the reference's transform"""
+        try:
+            h, w = (int(v) for v in model.patch_embed.img_size)
+        except (AttributeError, TypeError, ValueError):
+            raise TypeError(f"{type(model).__name__} has no patch_embed.img_size: pass the size to for_input_size") from None
+        return cls.for_input_size(h if h == w else (h, w), mean, std)
 
     @property
     def default_normalisation(self) -> bool:
         return self.mean == tuple(IMAGENET_MEAN) and self.std == tuple(IMAGENET_STD)
 
     def __repr__(self):
-        return f"EvalTransform(resize={self.resize}, crop={self.crop}, mean={self.mean}, std={self.std})"
+        pad = ", pad=True" if self.pad else ""
+        return f"EvalTransform(resize={self.resize}, crop={self.crop}, mean={self.mean}, std={self.std}{pad})"
 
     def _workspace(self, device, nbytes):
         ws = self._ws.get(device)
@@ -134,23 +220,25 @@ class EvalTransform:
         if isinstance(packed, EncodedImages):
             packed = decode_images(packed, lo, hi, device)
             lo, hi = 0, len(packed)
-        n, c = hi - lo, self.crop
+        n, (ch, cw) = hi - lo, self.crop_hw
         device = torch.device(device)
         if device.type == "cuda" and device.index is None:
             device = torch.device("cuda", torch.cuda.current_device())
         if out is None:
-            out = torch.empty(n, 3, c, c, dtype=torch.uint8, device=device)
-        elif out.shape != (n, 3, c, c) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != device:
-            raise ValueError(f"out must be a contiguous uint8 [{n}, 3, {c}, {c}] tensor on {device}")
+            out = torch.empty(n, 3, ch, cw, dtype=torch.uint8, device=device)
+        elif out.shape != (n, 3, ch, cw) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != device:
+            raise ValueError(f"out must be a contiguous uint8 [{n}, 3, {ch}, {cw}] tensor on {device}")
         if n == 0:
             return out
-        geom = np.ascontiguousarray(packed.geometry(self.resize, c)[lo:hi])
+        geom = np.ascontiguousarray(packed.geometry(self.resize, self.crop, self.pad)[lo:hi])
         plan = (C.c_int32 * 3)()
         nbytes = C.c_int64()
         L = _lib.lib()
-        rc = L.ivit_resize_crop_workspace(geom.ctypes.data_as(C.c_void_p), n, c, plan, C.byref(nbytes))
+        # two ints without pad: the square entries and their refusals; everything else: the h x w entries
+        suffix, crop_args = ("", (ch,)) if self._square else ("_hw", (ch, cw))
+        rc = getattr(L, "ivit_resize_crop_workspace" + suffix)(geom.ctypes.data_as(C.c_void_p), n, *crop_args, plan, C.byref(nbytes))
         if rc != 0:
-            raise _lib.IvitError(f"ivit_resize_crop_workspace failed ({rc}): {L.ivit_last_error_string().decode()}")
+            raise _lib.IvitError(f"ivit_resize_crop_workspace{suffix} failed ({rc}): {L.ivit_last_error_string().decode()}")
         start = int(packed.offsets[lo])
         end = int(packed.offsets[hi]) if hi < len(packed) else packed.data.numel()
         src = packed.data[start:end].to(device, non_blocking=True)
@@ -158,8 +246,8 @@ class EvalTransform:
         g = torch.from_numpy(geom).to(device)
         ws = self._workspace(device, nbytes.value)
         with torch.cuda.device(device):
-            _lib.call("ivit_resize_crop_bicubic_u8", _lib.ptr(src), _lib.ptr(offs), _lib.ptr(g), n, c, plan[0], plan[1], plan[2],
-                      _lib.ptr(ws), ws.numel(), _lib.ptr(out), _lib.stream_ptr())
+            _lib.call(f"ivit_resize_crop_bicubic{suffix}_u8", _lib.ptr(src), _lib.ptr(offs), _lib.ptr(g), n, *crop_args, plan[0], plan[1],
+                      plan[2], _lib.ptr(ws), ws.numel(), _lib.ptr(out), _lib.stream_ptr())
         return out
 
     def table(self) -> np.ndarray:
@@ -266,7 +354,7 @@ def decode_jpeg_host(data) -> np.ndarray:
 
 @dataclass
 class EncodedImages:
-    """A batch of compressed images with PackedImages' interface (len, size(0), geometry(resize, crop) from the header sizes).
+    """A batch of compressed images with PackedImages' interface (len, size(0), geometry(resize, crop, pad) from the header sizes).
     The device images' plan sections (ivit_jpeg_plan_image) lie in one buffer, in image order; the other images carry Pillow's
     pixels (fallback) and the probe's reason (reasons)."""
     plan: torch.Tensor          # uint8 [plan bytes], pinned when a GPU is present
@@ -286,17 +374,9 @@ class EncodedImages:
             raise IndexError("EncodedImages has one dimension: images")
         return len(self)
 
-    def geometry(self, resize: int, crop: int) -> np.ndarray:
-        """int32 [B, 6]: (h, w, new_h, new_w, top, left) per image"""
-        key = (int(resize), int(crop))
-        g = self._geom.get(key)
-        if g is None:
-            g = np.empty((len(self), 6), np.int32)
-            for b, (h, w) in enumerate(self.sizes):
-                g[b, :2] = (h, w)
-                g[b, 2:] = eval_geometry(h, w, resize, crop)
-            self._geom[key] = g
-        return g
+    def geometry(self, resize, crop, pad: bool = False) -> np.ndarray:
+        """int32 [B, 6]: (h, w, new_h, new_w, top, left) per image; resize and crop an int or a pair (h, w), as eval_geometry_hw"""
+        return _geometry_rows(self.sizes, self._geom, resize, crop, pad)
 
 
 def encode_images(files, decode_fallback=None, pin: bool | None = None) -> EncodedImages:

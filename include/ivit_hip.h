@@ -919,6 +919,38 @@ int ivit_resize_crop_workspace(const int32_t* geom, int batch, int crop, int32_t
 int ivit_resize_crop_bicubic_u8(const uint8_t* src, const int64_t* offsets, const int32_t* geom, int batch, int crop, int ksize_h,
                                 int ksize_v, int rows, void* workspace, int64_t workspace_bytes, uint8_t* out, ivit_stream_t stream);
 
+/* The same transform with an h x w crop, an exact-size resize and torchvision's zero padding (DESIGN.md §11 "h x w crops").  The three
+ * entries above are these with crop_h = crop_w, the short-side resize and no padding, and keep their own refusals.
+ *
+ * The rule, per axis and independent per axis, for a resized length n and a crop length c:
+ *   c <= n   offset round((n - c) / 2), half to even (as above)
+ *   c >  n   CenterCrop pads (c - n) / 2 zeros in front and (c - n + 1) / 2 behind (integer division); the offset is reported as
+ *            the negative number -((c - n) / 2)
+ * and output pixel y is resized pixel y + offset, or 0 where that lies outside [0, n).  The zeros are pixel value 0, in front of
+ * ToTensor / Normalize.
+ *
+ * ivit_eval_geometry_hw: HOST function, host out4 = (new_h, new_w, top, left).  resize_w == 0: torchvision Resize([resize_h]), the
+ * short-side rule of ivit_eval_geometry; resize_w > 0: Resize((resize_h, resize_w)), exactly that size.  top and left can be
+ * negative with pad != 0 only: with pad == 0 a crop longer than the resized image on either axis is IVIT_ERR_UNSUPPORTED
+ * ("unsupported geometry"), as are an empty image, resize_h < 1, resize_w < 0 and a crop side <= 32.  IVIT_ERR_INVALID for a
+ * NULL out4. */
+int ivit_eval_geometry_hw(int h, int w, int resize_h, int resize_w, int crop_h, int crop_w, int pad, int32_t* out4);
+/* HOST function: ivit_resize_crop_workspace for a crop_h x crop_w crop, over the same host int32 [batch][6] rows (h, w, new_h,
+ * new_w, top, left).  Per axis a row is accepted with 0 <= offset <= n - c, or, where c > n, with -(c - n) <= offset <= 0;
+ * everything else, an empty image or resized image, and a crop side <= 32 are IVIT_ERR_UNSUPPORTED ("unsupported geometry").
+ * plan3 = (ksize_h, ksize_v, rows); rows counts the source rows that the crop's rows inside the resized image reach. */
+int ivit_resize_crop_workspace_hw(const int32_t* geom, int batch, int crop_h, int crop_w, int32_t* plan3, int64_t* bytes);
+/* ivit_resize_crop_bicubic_u8 for a crop_h x crop_w crop at signed offsets: out = dense planar uint8 [batch][3][crop_h][crop_w],
+ * every byte of it written (out need not be cleared): the padding as 0 by the vertical pass, the pixels inside the resized image
+ * from their taps.  Taps, intermediate rows and intermediate columns exist for the part of the crop inside the resized image
+ * only.  geom, the plan and workspace_bytes from ivit_resize_crop_workspace_hw for the same (crop_h, crop_w); as above the kernels
+ * clamp every index to the plan, so a table that disagrees with the plan reads and writes nothing outside the images, the
+ * workspace and out.  Alignment and IVIT_ERR_INVALID as for the square entry, and for crop_h > 262140 (one launch);
+ * IVIT_ERR_UNSUPPORTED for a crop side <= 32.  Three launches on `stream`. */
+int ivit_resize_crop_bicubic_hw_u8(const uint8_t* src, const int64_t* offsets, const int32_t* geom, int batch, int crop_h, int crop_w,
+                                   int ksize_h, int ksize_v, int rows, void* workspace, int64_t workspace_bytes, uint8_t* out,
+                                   ivit_stream_t stream);
+
 /* ---- JPEG decoding (the reference's image loader, Image.open(f).convert("RGB")) -------------------------------------------
  * Baseline JPEG byte for byte as libjpeg-turbo decodes it at its defaults (JDCT_ISLOW, fancy upsampling): sequential Huffman
  * (SOF0 / SOF1), 8-bit samples, one scan of all components, restart intervals, 1 component (replicated to RGB) or 3 components
