@@ -150,6 +150,8 @@ SIGNATURES = {
     "ivit_tokens_to_nchw_i16_f32": [vp, i64, ci, ci, ci, ci, ci, f32, vp, vp],
     "ivit_tokens_to_nchw_i8": [vp, i64, ci, ci, ci, ci, ci, vp, vp],
     "ivit_tokens_to_nchw_i16": [vp, i64, ci, ci, ci, ci, ci, vp, vp],
+    # backbone outputs (include/ivit_hip.h, end)
+    "ivit_dequant_rows_i8_f32": [vp, i64, i64, ci, f32, vp, i64, vp],
 }
 
 

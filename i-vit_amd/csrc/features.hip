@@ -1,5 +1,6 @@
-// features.hip -- feature maps: a token-major integer stream [B][T_all][ldx] -> dense channel-major maps [B][C][T]
-// (ivit_tokens_to_nchw_*: forward_intermediates of both engines).  Per image this is a C x T transposition; one workgroup moves a
+// features.hip -- what a backbone returns.  Feature maps: a token-major integer stream [B][T_all][ldx] -> dense channel-major maps
+// [B][C][T] (ivit_tokens_to_nchw_*: forward_intermediates of both engines); embeddings: int8 rows -> float32 rows
+// (ivit_dequant_rows_i8_f32: forward_features, further down).  Feature maps, per image this is a C x T transposition; one workgroup moves a
 // tile of FT_TOK tokens x (128 bytes of) channels through LDS so that both sides of it are coalesced:
 //   load   a token row of the tile is 128 contiguous source bytes (one cache line when the row is aligned); lanes take consecutive
 //          VB-byte pieces of a row, VB = the widest of 16 / 8 / 4 bytes that x and ldx admit (else one element).  A piece that
@@ -102,7 +103,77 @@ int tokens_to_nchw(const char* who, const TI* x, int64_t ldx, int B, int T_all, 
     IVIT_CHECK_LAUNCH(who);
 }
 
+// ---- backbone outputs: rows of int8 integers -> float32 rows, out[r][c] = (float)x[r][c] * s (forward_features of both engines) ----
+// A pure stream: 1 byte in, 4 bytes out per element, both sides strided by rows.  A row is cut into slots of 16 channels, one thread
+// per slot, and consecutive threads take consecutive slots of a row, then the next row (256 threads: 5 rows of 768 channels), so
+// that a wave's loads are 1 KB contiguous and its four stores cover 4 KB contiguous.  Per row, from the two row pointers alone:
+//   wide   h = the channels up to the first 16-byte boundary of the input row; if out + h is on a 16-byte boundary too, the slots
+//          k < nb = (C - h) / 16 are one 16-byte load and four float4 stores each, all aligned; slot nb takes the h head channels
+//          and slot nb + 1 the (C - h) % 16 tail channels, element by element;
+//   scalar otherwise (the two rows never reach a 16-byte boundary at the same channel): slot k takes the channels k, k + spr,
+//          k + 2 spr, ... -- a byte load and a dword store per lane, consecutive lanes on consecutive channels.
+// spr = C / 16 + 2 slots per row in either form.  Row offsets are 64-bit products; nothing outside channels 0 .. C - 1 of a row is
+// read or written.
+constexpr int DQ_NT = 256;
+
+IVIT_DEV float4 dq_four(unsigned w, float s)
+{
+    return make_float4((float)(int8_t)(w & 0xffu) * s, (float)(int8_t)((w >> 8) & 0xffu) * s, (float)(int8_t)((w >> 16) & 0xffu) * s,
+                       (float)(int8_t)(w >> 24) * s);
+}
+
+__global__ __launch_bounds__(DQ_NT) void dequant_rows_kernel(const int8_t* __restrict__ x, int64_t ldx, int64_t rows, int C, float s,
+                                                             float* __restrict__ out, int64_t ldo, int spr)
+{
+    // the workgroup's first slot as (row, slot) once, in 64 bits; the thread's own from it in 32
+    const int64_t g0 = (int64_t)blockIdx.x * DQ_NT;
+    const int64_t row0 = g0 / spr;
+    const unsigned t = (unsigned)(g0 - row0 * spr) + threadIdx.x;
+    const int64_t r = row0 + t / (unsigned)spr;
+    const int k = (int)(t % (unsigned)spr);
+    if (r >= rows) return;
+    const int8_t* xr = x + r * ldx;
+    float* orow = out + r * ldo;
+    int h = (int)((0 - (uintptr_t)xr) & 15);
+    if (((((uintptr_t)orow >> 2) + (unsigned)h) & 3) != 0) {
+        for (int c = k; c < C; c += spr) orow[c] = (float)xr[c] * s;
+        return;
+    }
+    h = min(h, C);
+    const int nb = (C - h) >> 4;
+    if (k < nb) {
+        const int c = h + (k << 4);
+        const uint4 w = *reinterpret_cast<const uint4*>(xr + c);
+        float4* dst = reinterpret_cast<float4*>(orow + c);
+        dst[0] = dq_four(w.x, s);
+        dst[1] = dq_four(w.y, s);
+        dst[2] = dq_four(w.z, s);
+        dst[3] = dq_four(w.w, s);
+    } else if (k == nb) {
+        for (int c = 0; c < h; ++c) orow[c] = (float)xr[c] * s;
+    } else if (k == nb + 1) {
+        for (int c = h + (nb << 4); c < C; ++c) orow[c] = (float)xr[c] * s;
+    }
+}
+
 }      // namespace
+
+IVIT_EXPORT int ivit_dequant_rows_i8_f32(const int8_t* x, int64_t ldx, int64_t rows, int C, float s, float* out, int64_t ldo,
+                                         ivit_stream_t stream)
+{
+    const char* who = "ivit_dequant_rows_i8_f32";
+    IVIT_REQUIRE(x && out, "%s: NULL pointer", who);
+    IVIT_REQUIRE(C >= 1 && rows >= 0, "%s: C=%d must be at least 1, rows=%lld at least 0", who, C, (long long)rows);
+    IVIT_REQUIRE(ldx >= C && ldo >= C, "%s: ldx=%lld / ldo=%lld below C=%d", who, (long long)ldx, (long long)ldo, C);
+    IVIT_REQUIRE((uintptr_t)out % sizeof(float) == 0, "%s: out is not aligned to its element", who);
+    if (rows == 0) return IVIT_OK;
+    const int spr = C / 16 + 2;
+    IVIT_REQUIRE(rows <= (INT64_MAX - DQ_NT) / spr, "%s: rows=%lld", who, (long long)rows);
+    const int64_t grid = (rows * spr + DQ_NT - 1) / DQ_NT;
+    IVIT_REQUIRE(grid <= 0x7fffffff, "%s: %lld workgroups of %d slots of 16 channels (at most 2^31 - 1)", who, (long long)grid, DQ_NT);
+    hipLaunchKernelGGL(dequant_rows_kernel, dim3((unsigned)grid), dim3(DQ_NT), 0, ivit_stream(stream), x, ldx, rows, C, s, out, ldo, spr);
+    IVIT_CHECK_LAUNCH(who);
+}
 
 IVIT_EXPORT int ivit_tokens_to_nchw_i8_f32(const int8_t* x, int64_t ldx, int B, int T_all, int t0, int T, int C, float s, float* out,
                                            ivit_stream_t stream)

@@ -96,20 +96,85 @@ class EngineDispatch:
         self._engine = (device, fp, eng)
         return eng
 
-    def _reason_cached(self):
-        """engine_unsupported_reason(), re-evaluated only when a QuantAct's width changed (it builds 4 * depth dictionaries; this
-        predicate runs on every forward, and a DeiT-T batch-1 forward is 0.7 ms)"""
+    def features_unsupported_reason(self):
+        """engine_unsupported_reason() without its head condition: None when the fused engine computes this model's backbone outputs
+        (features, forward_intermediates, attention_maps) exactly, with or without a classifier"""
+        raise NotImplementedError
+
+    def _reason_cached(self, features=False):
+        """engine_unsupported_reason() (features: features_unsupported_reason()), re-evaluated only when a QuantAct's width changed
+        (it builds 4 * depth dictionaries; this predicate runs on every forward, and a DeiT-T batch-1 forward is 0.7 ms)"""
         key = tuple(int(m.activation_bit) for _, m in self._quant_acts())
-        c = self.__dict__.get("_reason_cache")
+        slot = "_features_reason_cache" if features else "_reason_cache"
+        c = self.__dict__.get(slot)
         if c is None or c[0] != key:
-            c = self.__dict__["_reason_cache"] = (key, self.engine_unsupported_reason())
+            c = self.__dict__[slot] = (key, self.features_unsupported_reason() if features else self.engine_unsupported_reason())
         return c[1]
 
-    def takes_engine(self, x: torch.Tensor) -> bool:
+    def _engine_state_ok(self, x):
+        """what both predicates ask of the moment: no io-stat collection, use_engine, eval mode, a GPU input, frozen ranges"""
         if getattr(self, "_io_stat_hooks", False) and _qm.io_stats_enabled():
             return False      # attach_io_stat_hooks: the collector's hooks sit on the sub-modules, which the fused engine never calls
-        return (self.use_engine and not self.training and x.is_cuda and self.is_frozen()
-                and self._reason_cached() is None)
+        return bool(self.use_engine and not self.training and x.is_cuda and self.is_frozen())
+
+    def takes_engine(self, x: torch.Tensor) -> bool:
+        return self._engine_state_ok(x) and self._reason_cached() is None
+
+    def takes_engine_for_features(self, x: torch.Tensor) -> bool:
+        """takes_engine for the calls that never reach the classifier (features, features_graph, forward_intermediates,
+        attention_maps): the same conditions with features_unsupported_reason(), so a headless model (num_classes=0) passes"""
+        return self._engine_state_ok(x) and self._reason_cached(features=True) is None
+
+    # -- backbone outputs -----------------------------------------------------------------------------------------
+    def _carries(self, x):
+        """the lazy.scope condition of forward(): a frozen model in eval mode on the GPU carries integers between its modules"""
+        return x.is_cuda and not self.training and self.is_frozen()
+
+    def _feature_bits(self):
+        """width of the QuantAct whose output forward_features returns (8 in both references)"""
+        raise NotImplementedError
+
+    def features(self, x, integers=False, out=None):
+        """The embedding a frozen backbone is used for -> (features [B, C], scale): the first value of forward_features(x) --
+        float32, integers times scale -- or with integers=True those integers (int8), and the float32 act_scaling_factor of the
+        QuantAct that produced them as a float.  Where takes_engine_for_features(x) holds this is the fused engine's
+        forward_features (no head GEMM, no classifier launch; a headless model included).  Otherwise forward_features runs module by
+        module, under the lazy.scope condition forward() uses; integers=True then converts its float tensor back and checks, as
+        forward_intermediates' module path does, that it is integers of that width times the scale.
+        out: a [B, C] view to write the features into (rows of a feature bank; the engine's `out=`, which the module path fills
+        with a copy)."""
+        from .quantization_utils import lazy
+        if self.takes_engine_for_features(x):
+            return self.engine(x.shape[0]).forward_features(x.contiguous().float(), integers, out)
+        if not self.is_frozen():
+            self.invalidate_engine()
+        with lazy.scope(self._carries(x)):
+            f, s = self.forward_features(x)
+        f = f.to_float(boundary=True) if isinstance(f, lazy.QT) else f
+        s = s.as_subclass(torch.Tensor).reshape(-1)      # (a lazy.QS scale: the plain tensor)
+        assert s.numel() == 1 and s.dtype == torch.float32, "forward_features: a per-tensor float32 scale"
+        if integers:
+            bits = self._feature_bits()
+            q = torch.round(f / s)
+            assert bool((q * s == f).all()) and bool((q >= -2 ** (bits - 1)).all()) and bool((q < 2 ** (bits - 1)).all()), \
+                f"forward_features: the output is not a {bits}-bit integer times its scale"
+            f = q.to(torch.int16 if bits > 8 else torch.int8)
+        if out is not None:
+            if out.dtype != f.dtype or tuple(out.shape) != tuple(f.shape):
+                raise ValueError(f"out must be a {f.dtype} tensor {list(f.shape)}")
+            out.copy_(f)
+            f = out
+        return f, float(s[0])
+
+    def features_graph(self, x, integers=False, resident=False):
+        """features(x) from a graph replay of the fused engine (GraphReplay.forward_features_graph): the same bytes, in the graph's
+        own output tensor, valid until the next replay of that graph.  ValueError where takes_engine_for_features(x) does not hold
+        (the module path's graph replays logits: ModuleGraph.forward_graph)."""
+        if not self.takes_engine_for_features(x):
+            why = self._reason_cached(features=True) or "model not frozen, in training mode, use_engine off, or input not on the GPU"
+            raise ValueError(f"features_graph: the fused engine does not take this call ({why})")
+        xin = x if (x.dtype == torch.float32 and x.is_contiguous()) else x.contiguous().float()
+        return self.engine(x.shape[0]).forward_features_graph(xin, integers, resident)
 
     def ranges(self):
         return {n: (float(m.x_min.reshape(-1)[0]), float(m.x_max.reshape(-1)[0]))
@@ -119,7 +184,9 @@ class EngineDispatch:
         """forward_intermediates off the engine: the modules are called one by one as the reference's forward calls them, with a
         forward hook on each selected module.  sites = {key: (module, its name, the QuantAct whose output it returns, t0, (H, W))};
         the hooked (x [B, t0 + H * W, C], s) is checked to be integers of that QuantAct's width times s, its first t0 tokens are
-        dropped and the rest goes to [B, C, H, W].  -> {key: (map, scale)}; the hooks are removed in any case."""
+        dropped and the rest goes to [B, C, H, W].  -> {key: (map, scale)}; the hooks are removed in any case.
+        This path always runs the whole forward (forward_features, then the head where there is one), for forward_intermediates_early too: the
+        modules are the reference's and are called as it calls them."""
         got, handles = {}, []
 
         def hook(key, name, qact, t0, hw):
@@ -144,7 +211,8 @@ class EngineDispatch:
                 if not self.is_frozen():
                     self.invalidate_engine()
                 f, s = self.forward_features(x)
-                self.head(f, s)
+                if self.num_classes > 0:
+                    self.head(f, s)
         finally:
             for h in handles:
                 h.remove()

@@ -183,12 +183,19 @@ class IntViTEngine(EngineBase):
         # ---- tail
         s_q2 = s("qact2")
         self.ln_f = ln_dev("norm", s_q2, s_x)
-        head = source.linear("head", s_q2)
-        hW, hb, hs, self.num_classes = pad_head(head.W8, head.b32, head.s_acc)    # any class count (num_classes=... of the factory)
-        self.head = dict(W=dev(hW), b=dev(hb), K=head.K, N=hW.shape[0])
-        self.head_scale = dev(hs)
+        self.s_feat = float(s_q2)     # the float32 act_scaling_factor of qact2 (forward_features)
+        try:
+            head = source.linear("head", s_q2)
+        except KeyError:              # a backbone (num_classes=0: no head.weight): forward_features / forward_intermediates / attention_maps
+            head = None
+        if head is None:
+            self.head, self.head_scale, self.num_classes = None, None, 0
+        else:
+            hW, hb, hs, self.num_classes = pad_head(head.W8, head.b32, head.s_acc)    # any class count (num_classes=... of the factory)
+            self.head = dict(W=dev(hW), b=dev(hb), K=head.K, N=hW.shape[0])
+            self.head_scale = dev(hs)
         self.int8_weight_bytes = sum(int(b[k]["W"].numel()) for b in self.blocks for k in ("qkv", "proj", "fc1", "fc2")) \
-            + int(self.patch["W"].numel()) + int(self.head["W"].numel())
+            + int(self.patch["W"].numel()) + (0 if self.head is None else int(self.head["W"].numel()))
         # block-layout and MFMA-fragment copies of the GEMM weights (engine_common).  The 16x16x64 fragment order wherever the
         # epilogue writes int8; the 16-bit-stream epilogue of proj / fc2 exists for the 32x32x32 order only
         lins = [self.patch] + [b[k] for b in self.blocks for k in ("qkv", "proj", "fc1", "fc2")]
@@ -235,8 +242,9 @@ class IntViTEngine(EngineBase):
                 x16=torch.empty(M, C, dtype=torch.int16, device=self.dev), y16=torch.empty(M, C, dtype=torch.int16, device=self.dev),
                 k16=torch.empty(M, C, dtype=torch.int16, device=self.dev),
                 cls16=torch.empty(B, C, dtype=torch.int16, device=self.dev))),
-            logits=torch.empty(B, self.head["N"], dtype=torch.int32, device=self.dev),
-            logits_f=torch.empty(B, self.head["N"], dtype=torch.float32, device=self.dev),
+            **({} if self.head is None else dict(
+                logits=torch.empty(B, self.head["N"], dtype=torch.int32, device=self.dev),
+                logits_f=torch.empty(B, self.head["N"], dtype=torch.float32, device=self.dev))),
             top1=torch.empty(B, dtype=torch.int32, device=self.dev),
             topk=torch.empty(B * TOPK_MAX, dtype=torch.int32, device=self.dev),
         )
@@ -394,8 +402,32 @@ class IntViTEngine(EngineBase):
             raise ValueError(f"layers {list(layers)}: block indices in 0..{self.D - 1}")
         B, R = images.shape[0], 1 if rows == "cls" else self.T
         maps = {i: torch.empty(B, self.H, R, self.T, dtype=torch.uint8, device=self.dev) for i in layers}
-        self._forward(images, maps=maps)
+        self._forward(images, maps=maps, stop="features" if self.head is None else None)      # (a headless engine ends behind the final norm)
         return maps, 2.0 ** -7
+
+    def forward_features(self, images: torch.Tensor, integers: bool = False, out: torch.Tensor | None = None):
+        """The class embedding -> (features [B, C], scale): the tensor qact2 returns behind the final norm, the first value of the
+        reference's forward_features (vit_quant.py:302-305).  features: float32, the integers times scale in one float32
+        multiplication (ivit_dequant_rows_i8_f32) -- that tensor bit for bit; integers=True: the int8 integers.  scale: the float32
+        act_scaling_factor of qact2.  out=None: a fresh tensor (no workspace view).  out: a [B, C] view of that dtype on the engine's
+        device with stride(1) == 1 and any row stride >= C (rows of a feature bank) to write into; TypeError / ValueError for any
+        other, before anything is launched.  The forward stops behind the final LayerNorm: no head GEMM, no classifier launch, and
+        the last block runs on the class rows alone wherever cls_tail_ok holds.  The workspace logits are left as they were.  A
+        headless engine (no head.weight in its source) answers this too."""
+        B = images.shape[0]
+        out = self._features_out(B, self.C, integers, out)
+        self._forward(images, cls_tail=self.cls_tail_ok, stop="features")
+        return self._features_emit(self.ws["cls"], B, self.C, self.s_feat, out), self.s_feat
+
+    def _graph_features(self, images, integers):
+        """what forward_features_graph captures -> (features, scale), features in a tensor the graph owns"""
+        return self.forward_features(images, integers)
+
+    def forward_intermediates_early(self, images: torch.Tensor, indices=None, integers: bool = False):
+        """forward_intermediates with an early stop: nothing behind the last selected block is launched -- no later block, final
+        norm, head or classifier.  The maps and scales are those of forward_intermediates; the workspace logits (and the class
+        embedding) are then STALE, those of an earlier call.  (A method of its own: forward_intermediates keeps its parameters.)"""
+        return self._intermediates(images, indices, integers, True)
 
     def forward_intermediates(self, images: torch.Tensor, indices=None, integers: bool = False):
         """The residual stream behind the selected blocks as feature maps -> (maps, scales): maps = {index: float32 [B, C, Gh, Gw]}
@@ -405,17 +437,22 @@ class IntViTEngine(EngineBase):
         repeated, before anything is launched.  The ordinary eager forward runs -- its logits stay in the workspace as after
         forward() -- and behind the second residual GEMM of each selected block one more launch (engine_common.tokens_to_nchw)
         writes the stream into a fresh tensor.  Not part of taps, of the graph replays or of cls_tail (which never computes the
-        last block's stream)."""
+        last block's stream).  A headless engine stops behind the last selected block (forward_intermediates_early)."""
+        return self._intermediates(images, indices, integers, self.head is None)
+
+    def _intermediates(self, images, indices, integers, stop_early):
         idx = intermediate_indices(indices, self.D, "block")
         B = images.shape[0]
         dt = torch.float32 if not integers else torch.int16 if self.stream_bits == 16 else torch.int8
         feats = {i: torch.empty(B, self.C, *self.grid, dtype=dt, device=self.dev) for i in idx}
-        self._forward(images, feats=feats)
+        self._forward(images, feats=feats, stop=max(idx) if stop_early else None)
         return feats, {i: self.blocks[i]["s_out"] for i in idx}
 
     def _forward(self, images: torch.Tensor, taps: dict | None = None, topk=None, cls_tail: bool = False, maps: dict | None = None,
-                 feats: dict | None = None):
+                 feats: dict | None = None, stop=None):
         """forward; topk = (k, targets, hits): the classifier launch is the top-k selection (forward_topk).
+        stop: None the whole forward; "features": return behind the final LayerNorm (forward_features: no head GEMM, no classifier
+        launch); a block index: return behind that block (forward_intermediates_early).  A headless engine needs one.
         cls_tail: the last block through _cls_block (cls_tail_ok engines, no taps).
         maps: {block index: uint8 [B, H, R, T]} to fill with the softmax probabilities of those blocks (attention_maps).
         feats: {block index: [B, C, Gh, Gw]} to fill with the stream behind those blocks, class token dropped (forward_intermediates).
@@ -427,6 +464,8 @@ class IntViTEngine(EngineBase):
         assert images.is_cuda and images.dtype in (torch.float32, torch.uint8) and images.is_contiguous()
         B = images.shape[0]
         assert images.shape[1:] == (3, self.IMG_H, self.IMG_W) and 0 < B <= self.max_batch
+        if stop is None:
+            self._require_head("forward")
         wide = self.stream_bits == 16
         if wide and taps is not None:
             raise NotImplementedError("taps are not recorded on the 16-bit-stream path")
@@ -512,6 +551,8 @@ class IntViTEngine(EngineBase):
             tap(p + "qact4", x, (B, T, C))
             if feats is not None and i in feats:
                 tokens_to_nchw(x, C, B, T, 1, T - 1, C, blk["s_out"], feats[i], st)
+            if stop == i:      # (never "features": block indices are ints)
+                return None
         # final LayerNorm is row-wise and only the cls row is consumed (vit_quant.py:302-304); the int16 kernels want dense rows
         if wide:
             ws["cls16"][:B].copy_(x.view(-1, T, C)[:B, 0])
@@ -521,6 +562,8 @@ class IntViTEngine(EngineBase):
         else:
             layernorm(self.ln_f, x, T * C, B, C, ws["cls"], C, st, blocks=False)
         tap("qact2", ws["cls"], (B, C))
+        if stop == "features":
+            return None
         hd_ = self.head
         _lib.call("ivit_gemm_i8_i32", _lib.ptr(ws["cls"]), C, _lib.ptr(hd_["W"]), hd_["K"], _lib.ptr(hd_["b"]),
                   _lib.ptr(ws["logits"]), hd_["N"], B, hd_["N"], C, st)

@@ -2,8 +2,9 @@
 (quantization_utils/lazy.py), written once per operator: the GEMM weight copies (block_copy, frag_copy); the LayerNorm constants
 and their launcher (ln_spec, layernorm); the ViT attention constants and their launchers (attention_spec, attention,
 attention_probs: the probabilities alone); the GELU
-table of both families (gelu_lut); the feature-map launcher and its index check (tokens_to_nchw, intermediate_indices); what the
-two engines share as classes (EngineBase).  Window attention's pair
+table of both families (gelu_lut); the feature-map launcher and its index check (tokens_to_nchw, intermediate_indices); the
+embedding's dequantisation (dequant_rows); what the two engines share as classes (EngineBase: the headless refusal and
+forward_features' destination among it).  Window attention's pair
 (window_attention_spec, window_attention) lives in swin_engine.py; the scalar dyadic pair is prepare.dyadic1."""
 from __future__ import annotations
 
@@ -231,6 +232,13 @@ def tokens_to_nchw(x, ldx, B, T_all, t0, T, C, scale, out, st):
         _lib.call(name, _lib.ptr(x), ldx, B, T_all, t0, T, C, _lib.ptr(out), st)
 
 
+def dequant_rows(x, ldx, rows, C, scale, out, ldo, st):
+    """rows x C int8 integers with row stride ldx -> float32 out with row stride ldo (both in elements), out = q * scale in one
+    float32 multiplication: the tensor a QuantAct returns.  One launch (ivit_dequant_rows_i8_f32, csrc/features.hip)."""
+    assert x.dtype == torch.int8 and out.dtype == torch.float32
+    _lib.call("ivit_dequant_rows_i8_f32", _lib.ptr(x), ldx, rows, C, float(scale), _lib.ptr(out), ldo, st)
+
+
 def intermediate_indices(indices, n, what):
     """forward_intermediates' `indices` (None: all of 0 .. n - 1) as a list; ValueError for one out of range or repeated"""
     idx = list(range(n)) if indices is None else [int(i) for i in indices]
@@ -259,6 +267,37 @@ class EngineBase(GraphReplay, HeadTopK):
         lut, natural = gelu_lut(family, s_g, s_m1, self._upload, self.dev, self._stream())
         self.natural_sites += int(natural)
         return lut
+
+    def _require_head(self, what):
+        """the calls that end in the classifier, on an engine built from a source without head.weight: refused before any launch"""
+        if self.head is None:
+            raise ValueError(f"{what}: this engine has no classification head (its source holds no head.weight: a backbone); "
+                             "forward_features, forward_intermediates and attention_maps are what it answers")
+
+    def _features_out(self, B, C, integers, out):
+        """forward_features' destination: a fresh [B, C] tensor, or the caller's `out` once it is seen to be a [B, C] view of the right
+        dtype on the engine's device with unit inner stride (TypeError / ValueError otherwise: before anything is launched)"""
+        dt = torch.int8 if integers else torch.float32
+        if out is None:
+            return torch.empty(B, C, dtype=dt, device=self.dev)
+        if not isinstance(out, torch.Tensor) or out.dtype != dt:
+            raise TypeError(f"out must be a {dt} tensor (integers={bool(integers)})")
+        if out.device.type != self.dev.type or (self.dev.index is not None and out.device.index != self.dev.index):
+            raise ValueError(f"out must be on {self.dev}")
+        if tuple(out.shape) != (B, C):
+            raise ValueError(f"out must be [{B}, {C}], not {list(out.shape)}")
+        if out.stride(1) != 1 or (B > 1 and out.stride(0) < C):
+            raise ValueError(f"out: strides {tuple(out.stride())}; rows of {C} contiguous elements, row stride at least {C}")
+        return out
+
+    def _features_emit(self, q, B, C, scale, out):
+        """the int8 embedding q (workspace, dense [>= B, C]) -> out as _features_out passed it: one ivit_dequant_rows_i8_f32 launch
+        for float32, a strided device copy of the integers for int8"""
+        if out.dtype == torch.float32:
+            dequant_rows(q, C, B, C, scale, out, out.stride(0) if B > 1 else C, self._stream())
+        else:
+            out.copy_(q.view(-1)[: B * C].view(B, C))
+        return out
 
     def set_input_normalisation(self, mean=IMAGENET_MEAN, std=IMAGENET_STD):
         """uint8 input: the (mean, std) of the Normalize transform in front of the model (default: ImageNet's).  forward() then

@@ -20,12 +20,20 @@ class GraphReplay:
         """resident=False: `images` is copied into the graph's own input buffer before every replay.
         resident=True: the graph reads `images` itself (the caller keeps that tensor alive and refills it in place,
         e.g. a loader's device-side staging buffer) -- no copy per step."""
+        self._require_head("forward_graph")
         return self._replay(images, resident, (), lambda x, warm: self._graph_forward(x))
+
+    def forward_features_graph(self, images: torch.Tensor, integers: bool = False, resident: bool = False):
+        """forward_features as a graph replay -> (features [B, C], scale), the bytes of the eager call.  One graph per (batch size,
+        input dtype, integers) -- a key of its own, so the logits graph of the same batch size stays what it is -- and, with
+        resident=True, input pointer.  features is the graph's own output tensor, valid until the next replay of the same graph."""
+        return self._replay(images, resident, ("features", bool(integers)), lambda x, warm: self._graph_features(x, bool(integers)))
 
     def forward_topk_graph(self, images: torch.Tensor, k: int = 5, targets=None, hits=None, resident: bool = False):
         """forward_topk as a graph replay.  `targets` / `hits` are read and accumulated in place like a resident image tensor:
         one graph per (batch size, k, targets pointer, hits pointer); the caller refills `targets` between replays and reads
         `hits` when it likes.  The warm-up forward outside the capture runs without them, so `hits` only counts replays."""
+        self._require_head("forward_topk_graph")
         check_request(self.num_classes, images.shape[0], self.dev, k, targets, hits)
         tag = ("topk", k, 0 if targets is None else targets.data_ptr(), 0 if hits is None else hits.data_ptr())
         return self._replay(images, resident, tag, lambda x, warm: self._graph_forward_topk(x, k, None if warm else targets,

@@ -190,6 +190,137 @@ def evaluate_dataset(model, data_loader, device, *, print_batch_stats: bool = Tr
     return 100 * correct1 / tot, 100 * correct3 / tot, 100 * correct5 / tot
 
 
+def _features_into(model, x, rows, integers, graph, norm=None):
+    """features of the image batch x into `rows`, a [b, C] block of rows of a feature bank (int8 for integers, else float32) -> scale.
+    The fused engine writes them there itself (forward_features(out=rows)); graph: its replay leaves the int8 embedding in the graph's
+    buffer, and the one launch that follows (a dequantisation, or a copy of the integers) has the rows as its destination.  A model
+    the engine declines runs module by module (model.features), with or without `graph`.  norm: the (mean, std) a uint8 x was
+    meant for -- the engine's input table is set to it, as _forward_transformed does."""
+    takes = getattr(model, "takes_engine_for_features", None)
+    if takes is None or not takes(x):
+        if x.dtype == torch.uint8:
+            raise ValueError("uint8 images are what the fused engine takes: convert them (transforms.EvalTransform.to_float)")
+        return model.features(x, integers, out=rows)[1]
+    eng = model.engine(x.shape[0])
+    if x.dtype == torch.uint8:
+        if getattr(eng, "input_lut", None) is None or (norm is not None and getattr(eng, "input_norm", None) != norm):
+            eng.set_input_normalisation(*(norm or ()))
+    else:
+        x = x.contiguous().float()
+    if not graph:
+        return eng.forward_features(x, integers, out=rows)[1]
+    q, scale = eng.forward_features_graph(x, integers=True)
+    if integers:
+        rows.copy_(q)
+    else:
+        from .engine_common import dequant_rows
+        b, C = q.shape
+        dequant_rows(q, q.stride(0) if b > 1 else C, b, C, scale, rows, rows.stride(0) if b > 1 else C, eng._stream())
+    return scale
+
+
+def _sized(data_loader):
+    """(loader, number of images): from the loader's dataset where it has one, else by holding its batches"""
+    ds = getattr(data_loader, "dataset", None)
+    if ds is not None and hasattr(ds, "__len__"):
+        return data_loader, len(ds)
+    batches = list(data_loader)
+    return batches, sum(int(t.shape[0]) for _, t in batches)
+
+
+def extract_features(model, data_loader, device, *, transform=None, graph: bool = False, integers: bool = False):
+    """The embeddings of a dataset -> (features [N, C], labels int64 [N], scale), rows in loader order, on `device`: what linear
+    probing, a retrieval bank or k-NN evaluation start from.  features: float32, model.features' tensor (integers times scale), or
+    with integers=True the int8 integers; scale: the float32 act_scaling_factor they carry (None for an empty loader).
+
+    The bank is allocated once (N: len(data_loader.dataset); a loader without a dataset is held as a list of its batches, and a
+    loader that drops its last batch returns the rows it yielded) and every batch is written straight into its rows
+    (forward_features(out=...)): no float copy per batch, no concatenation.  transform, graph: as for evaluate_dataset -- a
+    transforms.EvalTransform makes the loader's (PackedImages, targets) batches uint8 crops on the device; graph=True replays the
+    fused engine's feature graph (a model the engine declines has no feature graph and runs eagerly) and model.graph_status() is
+    checked once after the loop."""
+    data_loader, N = _sized(data_loader)
+    C = int(model.num_features)
+    bank = torch.empty(N, C, dtype=torch.int8 if integers else torch.float32, device=device)
+    labels = torch.empty(N, dtype=torch.int64, device=device)
+    n, scale = 0, None
+    model.eval()
+    with torch.no_grad():
+        for imgs, targets in data_loader:
+            b = int(targets.shape[0])
+            if b == 0:
+                continue
+            rows = bank[n:n + b]
+            if transform is None:
+                scale = _features_into(model, imgs.to(device), rows, integers, graph)
+            else:
+                u8 = transform(imgs, 0, b, device=device)
+                takes = getattr(model, "takes_engine_for_features", None)
+                x = u8 if takes is not None and takes(u8) else transform.to_float(u8)
+                scale = _features_into(model, x, rows, integers, graph, (transform.mean, transform.std))
+            labels[n:n + b] = targets.to(device)
+            n += b
+    if graph and hasattr(model, "graph_status"):
+        model.graph_status()
+    return bank[:n], labels[:n], scale
+
+
+def extract_features_parallel(model, data_loader, device, *, transform=None, graph: bool = False, integers: bool = False):
+    """extract_features data-parallel over the ranks of the default process group (world 1 without one) -> the same (features [N, C],
+    labels int64 [N], scale) on every rank, rows in loader order.
+
+    Every rank iterates the SAME loader and keeps its parallel.shard_bounds slice of each global batch, as
+    evaluate_dataset_parallel does; it collects the int8 integers of its slices with their labels, and ONE
+    parallel.gather_feature_rows at the end (one all_gather_into_tensor: uneven shards padded to the largest and trimmed by their
+    counts) brings every rank's rows to every rank, where they are put back into loader order.  integers=False: the gathered
+    integers are dequantised once, behind the gather (a quarter of the float32 bytes cross the wire)."""
+    from .parallel import gather_feature_rows
+    if dist.is_available() and dist.is_initialized():
+        world, rank = dist.get_world_size(), dist.get_rank()
+    else:
+        world, rank = 1, 0
+    data_loader, N = _sized(data_loader)
+    C = int(model.num_features)
+    # this rank's rows: its slice of a batch is at most one image more than an even share
+    cap = N // world + len(data_loader) if hasattr(data_loader, "__len__") else N
+    local = torch.empty(min(N, cap), C, dtype=torch.int8, device=device)
+    local_labels = torch.empty(local.shape[0], dtype=torch.int64, device=device)
+    sizes, n, scale = [], 0, None
+    model.eval()
+    with torch.no_grad():
+        for imgs, targets in data_loader:
+            B = int(targets.shape[0])
+            sizes.append(B)
+            lo, hi = shard_bounds(B, world, rank)
+            if hi == lo:
+                continue
+            rows = local[n:n + hi - lo]
+            if transform is None:
+                scale = _features_into(model, imgs[lo:hi].to(device), rows, True, graph)
+            else:
+                u8 = transform(imgs, lo, hi, device=device)
+                takes = getattr(model, "takes_engine_for_features", None)
+                x = u8 if takes is not None and takes(u8) else transform.to_float(u8)
+                scale = _features_into(model, x, rows, True, graph, (transform.mean, transform.std))
+            local_labels[n:n + hi - lo] = targets[lo:hi].to(device)
+            n += hi - lo
+    if graph and hasattr(model, "graph_status"):
+        model.graph_status()
+    q, labels, scale = gather_feature_rows(local[:n], local_labels[:n], scale, sizes, world)
+    if integers:
+        return q, labels, scale
+    if scale is None:
+        return q.float(), labels, scale
+    if q.is_cuda:
+        from . import _lib
+        from .engine_common import dequant_rows
+        f = torch.empty(q.shape, dtype=torch.float32, device=q.device)
+        if q.shape[0]:
+            dequant_rows(q, C, q.shape[0], C, scale, f, C, _lib.stream_ptr())
+        return f, labels, scale
+    return q.float() * torch.tensor(scale, dtype=torch.float32), labels, scale      # (a CPU group: torch's own float32 product)
+
+
 def evaluate_dataset_parallel(model, data_loader, device, *, scorer=None, print_batch_stats: bool = True, transform=None,
                               graph: bool = False):
     """evaluate_dataset data-parallel over the ranks of the default process group (world 1 without one) -> the same

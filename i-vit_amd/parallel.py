@@ -83,6 +83,46 @@ def gather_logits(local_logits: torch.Tensor, world: int, counts=None) -> torch.
     return gather_rows(local_logits, world, counts)
 
 
+def gather_feature_rows(local_q: torch.Tensor, local_labels: torch.Tensor, scale, sizes, world: int):
+    """The end of a data-parallel feature extraction (inference.extract_features_parallel) -> (q int8 [N, C], labels int64 [N],
+    scale) on every rank, rows in loader order.  local_q int8 [n, C] / local_labels int64 [n]: this rank's shard_bounds slices of
+    the global batches, one after the other; sizes: the size of every global batch (each rank saw the same loader); scale: the
+    float32 scale of the integers, None on a rank whose slices were all empty.
+
+    ONE all_gather_into_tensor (gather_rows): a row travels as its C integers followed by the 8 bytes of its label, and one more
+    row per rank carries its scale; uneven shards are padded to the largest and trimmed by `counts`, as gather_top1 does.  The
+    rank-major result is then indexed back into loader order."""
+    assert local_q.dtype == torch.int8 and local_q.dim() == 2 and local_labels.dtype == torch.int64
+    n, C = local_q.shape
+    w = C + 8
+    bounds = [[shard_bounds(B, world, r) for B in sizes] for r in range(world)]
+    counts = [sum(hi - lo for lo, hi in bounds[r]) for r in range(world)]
+    rank = dist.get_rank() if world > 1 else 0
+    assert n == counts[rank] == local_labels.numel()
+    packed = torch.zeros(n + 1, w, dtype=torch.int8, device=local_q.device)
+    packed[:n, :C] = local_q
+    packed[:n, C:] = local_labels.contiguous().view(torch.int8).view(n, 8)
+    if scale is not None:
+        packed[n, :4] = torch.tensor([float(scale)], dtype=torch.float32).view(torch.int8).to(local_q.device)
+        packed[n, 4] = 1
+    got = gather_rows(packed, world, [c + 1 for c in counts])
+    base = [sum(counts[:r]) + r for r in range(world)]      # first row of rank r in `got`
+    order, seen = [], [0] * world
+    for j in range(len(sizes)):
+        for r in range(world):
+            lo, hi = bounds[r][j]
+            order.append(torch.arange(base[r] + seen[r], base[r] + seen[r] + hi - lo))
+            seen[r] += hi - lo
+    order = torch.cat(order).to(got.device) if order else torch.zeros(0, dtype=torch.int64, device=got.device)
+    rows = got[order]
+    for r in range(world):      # the scale of the first rank that has one (every rank computes the same)
+        tail = got[base[r] + counts[r]]
+        if int(tail[4]):
+            scale = float(tail[:4].contiguous().view(torch.float32)[0])
+            break
+    return rows[:, :C].contiguous(), rows[:, C:].contiguous().view(torch.int64).reshape(-1), scale
+
+
 def allreduce_hits(hits: torch.Tensor, total) -> tuple:
     """ONE all_reduce(SUM) of [hits[0..k), total] -> (hits int64 [k] summed over ranks, total summed over ranks) on every
     rank.  hits: the int64 rank-r hit counts of topk.count_hits / forward_topk; total: this rank's image count."""

@@ -468,10 +468,14 @@ class IntSwinEngine(EngineBase):
         self.s_pool = float(s_q2)
         if self.pool_literal:
             self.natural_sites += 1
-        lp = LinearParams(P["head.weight"], P.get("head.bias"), s_q3)
-        hW, hb, hs, self.num_classes = pad_head(lp.W8, lp.b32, lp.s_acc)      # any class count
-        self.head = dict(W=dev(hW), b=dev(hb), K=lp.K, N=hW.shape[0])
-        self.head_scale = dev(hs)
+        self.s_feat = float(s_q3)     # the float32 act_scaling_factor of qact3 (forward_features)
+        if "head.weight" in P:
+            lp = LinearParams(P["head.weight"], P.get("head.bias"), s_q3)
+            hW, hb, hs, self.num_classes = pad_head(lp.W8, lp.b32, lp.s_acc)      # any class count
+            self.head = dict(W=dev(hW), b=dev(hb), K=lp.K, N=hW.shape[0])
+            self.head_scale = dev(hs)
+        else:      # a backbone (num_classes=0): forward_features / forward_intermediates / attention_maps
+            self.head, self.head_scale, self.num_classes = None, None, 0
         self._alloc(max_batch)
         self._compact(True)
         torch.cuda.synchronize(self.dev)
@@ -494,8 +498,9 @@ class IntSwinEngine(EngineBase):
             f1=torch.empty(M0 * 4 * C0, **i8), g=torch.empty(M0 * 4 * C0, **i8), f2=torch.empty(M0 * C0, **i8),
             xm=torch.empty(M0 * C0, **i16), hm=torch.empty(M0 * C0, **i8), red=torch.empty(M0 * C0 // 2, **i8),
             hN=torch.empty(B * self.T_last * self.C_last, **i8), pooled=torch.empty(B * self.C_last, **i8),
-            logits=torch.empty(B, self.head["N"], dtype=torch.int32, device=self.dev),
-            logits_f=torch.empty(B, self.head["N"], dtype=torch.float32, device=self.dev),
+            **({} if self.head is None else dict(
+                logits=torch.empty(B, self.head["N"], dtype=torch.int32, device=self.dev),
+                logits_f=torch.empty(B, self.head["N"], dtype=torch.float32, device=self.dev))),
             top1=torch.empty(B, dtype=torch.int32, device=self.dev),
             topk=torch.empty(B * TOPK_MAX, dtype=torch.int32, device=self.dev),
         )
@@ -539,6 +544,30 @@ class IntSwinEngine(EngineBase):
         intermediate integer tensors in the reference's layouts."""
         return self._forward(images, taps)
 
+    def forward_features(self, images: torch.Tensor, integers: bool = False, out: torch.Tensor | None = None):
+        """The pooled embedding -> (features [B, C_last], scale): the tensor qact3 returns behind norm -> qact2 -> avgpool, the
+        first value of the reference's forward_features (swin_quant.py:551-558).  features: float32, the integers times scale in one
+        float32 multiplication (ivit_dequant_rows_i8_f32) -- that tensor bit for bit; integers=True: the int8 integers.  scale: the
+        float32 act_scaling_factor of qact3.  out=None: a fresh tensor (no workspace view).  out: a [B, C_last] view of that dtype on
+        the engine's device with stride(1) == 1 and any row stride >= C_last (rows of a feature bank) to write into; TypeError /
+        ValueError for any other, before anything is launched.  The forward stops behind the pooling launch: no head GEMM, no
+        classifier launch; the workspace logits are left as they were.  Both operator families; a headless engine answers this too."""
+        B = images.shape[0]
+        out = self._features_out(B, self.C_last, integers, out)
+        self._forward(images, stop="features")
+        return self._features_emit(self.ws["pooled"], B, self.C_last, self.s_feat, out), self.s_feat
+
+    def _graph_features(self, images, integers):
+        """what forward_features_graph captures -> (features, scale), features in a tensor the graph owns"""
+        return self.forward_features(images, integers)
+
+    def forward_intermediates_early(self, images: torch.Tensor, indices=None, integers: bool = False):
+        """forward_intermediates with an early stop: nothing behind the last selected stage is launched -- no patch merging, later
+        stage, final norm, pooling, head or classifier.  The maps and scales are those of forward_intermediates; the workspace
+        logits (and the pooled embedding) are then STALE, those of an earlier call.  (A method of its own: forward_intermediates
+        keeps its parameters.)"""
+        return self._intermediates(images, indices, integers, True)
+
     def forward_intermediates(self, images: torch.Tensor, indices=None, integers: bool = False):
         """The residual stream behind the last block of the selected stages as feature maps -> (maps, scales): maps = {stage:
         float32 [B, C_li, H_li, W_li]}, the tensor layers.li.blocks[-1].qact4 returns in the reference (integers times its scale,
@@ -546,13 +575,16 @@ class IntSwinEngine(EngineBase):
         QuantAct's float32 act_scaling_factor.  indices: stage indices (None: every stage); ValueError for one out of range or
         repeated, before anything is launched.  The ordinary eager forward runs (fused projection included) -- its logits stay in
         the workspace as after forward() -- plus one launch per selected stage (engine_common.tokens_to_nchw).  Not part of taps
-        or of the graph replays."""
+        or of the graph replays.  A headless engine stops behind the last selected stage (forward_intermediates_early)."""
+        return self._intermediates(images, indices, integers, self.head is None)
+
+    def _intermediates(self, images, indices, integers, stop_early):
         idx = intermediate_indices(indices, len(self.stages), "stage")
         B = images.shape[0]
         dt = torch.int16 if integers else torch.float32
         feats = {li: torch.empty(B, self.stages[li]["C"], self.stages[li]["H"], self.stages[li]["W"], dtype=dt, device=self.dev)
                  for li in idx}
-        self._forward(images, feats=feats)
+        self._forward(images, feats=feats, stop=max(idx) if stop_early else None)
         return feats, {li: self.stages[li]["s_out"] for li in idx}
 
     def attention_maps(self, images: torch.Tensor, blocks=None):
@@ -570,18 +602,22 @@ class IntSwinEngine(EngineBase):
             stg, blk = self.stages[li], self.stages[li]["blocks"][bi]
             N = blk["win"] * blk["win"]
             maps[(li, bi)] = torch.empty(B, blk["attn"]["nW"], stg["nH"], N, N, dtype=torch.uint8, device=self.dev)
-        self._forward(images, maps=maps)
+        self._forward(images, maps=maps, stop="features" if self.head is None else None)      # (a headless engine ends behind the pooling)
         return maps, 2.0 ** -7
 
     def _forward(self, images: torch.Tensor, taps: dict | None = None, topk=None, feats: dict | None = None,
-                 maps: dict | None = None):
+                 maps: dict | None = None, stop=None):
         """forward; topk = (k, targets, hits): the classifier launch is the top-k selection (forward_topk).
+        stop: None the whole forward; "features": return behind the pooling launch (forward_features); a stage index: return behind
+        that stage's last block (forward_intermediates_early).  A headless engine needs one.
         feats: {stage index: [B, C, H, W]} to fill with the stream behind the last block of those stages (forward_intermediates)
         maps: {(stage, block): uint8 [B, nW, nH, N, N]} to fill with the softmax probabilities of those blocks (attention_maps)"""
         assert images.is_cuda and images.dtype in (torch.float32, torch.uint8) and images.is_contiguous()
         B = images.shape[0]
         ih, iw = self.img_hw
         assert images.shape[1:] == (3, ih, iw) and 0 < B <= self.max_batch
+        if stop is None:
+            self._require_head("forward")
         ws = self.ws
         st = self._stream()
         C0 = self.C0
@@ -703,6 +739,8 @@ class IntSwinEngine(EngineBase):
                 tap(p + "qact4", x, M, C)
             if feats is not None and li in feats:
                 tokens_to_nchw(x, C, B, H * W, 0, H * W, C, stg["s_out"], feats[li], st)
+            if stop == li:      # (never "features": stage indices are ints)
+                return None
             dn = stg["down"]
             if dn is not None:
                 p = f"layers.{li}.downsample."
@@ -724,6 +762,8 @@ class IntSwinEngine(EngineBase):
             _lib.call("ivit_avgpool_requant_i8", _lib.ptr(ws["hN"]), _lib.ptr(ws["pooled"]), B, T, C, self.pool_me[0],
                       self.pool_me[1], st)
         tap("qact3", ws["pooled"], B, C)
+        if stop == "features":
+            return None
         hd = self.head
         _lib.call("ivit_gemm_i8_i32", _lib.ptr(ws["pooled"]), C, _lib.ptr(hd["W"]), hd["K"], _lib.ptr(hd["b"]),
                   _lib.ptr(ws["logits"]), hd["N"], B, hd["N"], hd["K"], st)
@@ -759,7 +799,7 @@ def engine_from_model(model, device=None, max_batch: int = 64):
     does not implement (operator mixture, another operator parameter, edited QuantAct widths, ape, no patch norm, geometry) and for
     a shift mask outside ivit_window_attention_i8_ibert's precondition (the block is named)."""
     family, int_sqrt = operator_family(model)
-    why = model.engine_structure_reason()
+    why = model.engine_structure_reason(head=False)      # (a headless model gives a headless engine)
     if why is not None:
         raise ValueError(why)
     if not model.is_frozen():

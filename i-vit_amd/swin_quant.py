@@ -325,15 +325,27 @@ class SwinTransformer(EngineDispatch, ModuleGraph, nn.Module):
     def engine_unsupported_reason(self):
         """what model(x) dispatches on: the engine it builds is the I-ViT one (swin_engine.engine_from_model also takes the I-BERT
         family, by construction)"""
+        return self._operator_reason() or self.engine_structure_reason()
+
+    def features_unsupported_reason(self):
+        """engine_unsupported_reason() without its head condition: what features, forward_intermediates and attention_maps ask (an
+        I-BERT model answers those module by module, as attention_maps always has; swin_engine.engine_from_model is its engine route)"""
+        return self._operator_reason() or self.engine_structure_reason(head=False)
+
+    def _operator_reason(self):
         if self.op_types != ("ivit",) * 3 or any(self.op_params):
             return f"operator family {self.op_types} (fused engine: all three operators 'ivit', default constructor arguments)"
-        return self.engine_structure_reason()
+        return None
 
-    def engine_structure_reason(self):
-        """None when IntSwinEngine implements this model apart from its operator family: stem, head, widths, geometry"""
+    def _feature_bits(self):
+        return int(self.qact3.activation_bit)
+
+    def engine_structure_reason(self, head=True):
+        """None when IntSwinEngine implements this model apart from its operator family: stem, head (head=False: not asked for),
+        widths, geometry"""
         if self.ape or not self.patch_norm:
             return "absolute position embedding / no patch norm"
-        if self.num_classes <= 0:
+        if head and self.num_classes <= 0:
             return "no classification head"
         if any(int(self.embed_dim * 2 ** i) // h != 32 for i, h in enumerate(self.num_heads)):
             return "head_dim != 32"
@@ -363,7 +375,7 @@ class SwinTransformer(EngineDispatch, ModuleGraph, nn.Module):
         if not self.is_frozen():
             self.invalidate_engine()
         # a frozen model run module by module carries int8 / int16 between its modules (quantization_utils/lazy.py)
-        with lazy.scope(x.is_cuda and not self.training and self.is_frozen()):
+        with lazy.scope(self._carries(x)):
             x, s = self.forward_features(x)
             x, _ = self.head(x, s)
         return x.to_float(boundary=True) if isinstance(x, lazy.QT) else x
@@ -385,7 +397,7 @@ class SwinTransformer(EngineDispatch, ModuleGraph, nn.Module):
                 bits = int(getattr(blk.attn.log_int_softmax, "output_bit", 8))
                 if bits != 8:          # on either path, and before an engine is built for it
                     raise ValueError(f"attention_maps: the softmax output is {bits} bits wide (8-bit probabilities only)")
-        if self.takes_engine(x):
+        if self.takes_engine_for_features(x):      # (takes_engine's answer for a model with a head)
             return self.engine(x.shape[0]).attention_maps(x.contiguous().float(), sel)
         maps, handles = {}, []
         B = x.shape[0]
@@ -408,11 +420,18 @@ class SwinTransformer(EngineDispatch, ModuleGraph, nn.Module):
                 if not self.is_frozen():
                     self.invalidate_engine()
                 f, s = self.forward_features(x)
-                self.head(f, s)
+                if self.num_classes > 0:
+                    self.head(f, s)
         finally:
             for h in handles:
                 h.remove()
         return {key: maps[key] for key in sel}, 2.0 ** -7
+
+    def forward_intermediates_early(self, x, indices=None, integers=False):
+        """forward_intermediates with an early stop: where the fused engine is taken it launches nothing behind the last selected
+        stage (IntSwinEngine.forward_intermediates_early: the same maps and scales; its workspace logits are then stale).  The
+        module path (_hooked_intermediates) runs the whole forward regardless."""
+        return self._intermediates(x, indices, integers, True)
 
     def forward_intermediates(self, x, indices=None, integers=False):
         """The residual stream behind the last block of the selected stages as feature maps -> (maps, scales): maps = {stage: float32
@@ -422,10 +441,14 @@ class SwinTransformer(EngineDispatch, ModuleGraph, nn.Module):
         Where forward() takes the fused engine this is IntSwinEngine.forward_intermediates: the eager engine forward plus one launch
         per selected stage.  Otherwise the modules are called one by one as the reference's forward calls them, with forward hooks on
         those blocks: the reference's own tensor, at the module path's speed."""
+        return self._intermediates(x, indices, integers, False)
+
+    def _intermediates(self, x, indices, integers, stop_early):
         from .engine_common import intermediate_indices
         idx = intermediate_indices(indices, self.num_layers, "stage")
-        if self.takes_engine(x):
-            return self.engine(x.shape[0]).forward_intermediates(x.contiguous().float(), idx, integers)
+        if self.takes_engine_for_features(x):      # (takes_engine's answer for a model with a head)
+            eng = self.engine(x.shape[0])
+            return (eng.forward_intermediates_early if stop_early else eng.forward_intermediates)(x.contiguous().float(), idx, integers)
         sites = {}
         for li in idx:
             blk = self.layers[li].blocks[-1]

@@ -85,6 +85,7 @@ class HeadTopK:
         valid until the next call.  topk: value descending, equal logits by ascending class (column 0 = forward's top-1).
         targets int32 [B] with hits int64 [k] (both or neither, on the engine's device): hits[r] += the rows whose target
         is their rank-r class, accumulated on the device."""
+        self._require_head("forward_topk")
         check_request(self.num_classes, images.shape[0], self.dev, k, targets, hits)
         return self._forward(images, None, (k, targets, hits))
 

@@ -187,6 +187,20 @@ class VisionTransformer(EngineDispatch, ModuleGraph, nn.Module):
 
     def engine_unsupported_reason(self):
         """None when the fused int8 engine computes exactly what this module tree would; else why not."""
+        return self._engine_reason(head=True)
+
+    def features_unsupported_reason(self):
+        """engine_unsupported_reason() without its head condition: what features, forward_intermediates and attention_maps ask"""
+        return self._engine_reason(head=False)
+
+    def _feature_bits(self):
+        return int(self.qact2.activation_bit)
+
+    def _carries(self, x):
+        return super()._carries(x) and self._carries_integers()
+
+    def _engine_reason(self, head):
+        """the checks of both; head: the classifier must exist"""
         bad = self._operator_reason()
         if bad:
             return bad
@@ -200,7 +214,7 @@ class VisionTransformer(EngineDispatch, ModuleGraph, nn.Module):
             return (f"geometry {self.geometry} (fused engine: square patches, 3 channels, height and width % patch_size == 0, "
                     "3 * patch_size^2 % 64 == 0, at most 1025 tokens, mlp_ratio 4, qkv bias)")
         tokens = (ih // patch) * (iw // patch) + 1
-        if self.num_classes <= 0:
+        if head and self.num_classes <= 0:
             return "no classification head"
         # every QuantAct of the DeiT / ViT engine is 8 bit, except the 16-bit one inside IBERTIntSoftmax (ibert_modules.py:247) ...
         inner = {f"blocks.{i}.attn.int_softmax.act": 16 for i in range(self.depth)} if self.op_types[0] == "ibert" else {}
@@ -241,7 +255,7 @@ class VisionTransformer(EngineDispatch, ModuleGraph, nn.Module):
                             device=device, max_batch=max_batch, family=self.op_types[0], **self._engine_operator_args(),
                             img_size=self.geometry[0], patch_size=self.geometry[1],
                             **dict(zip(("stream_bits", "softmax_bits", "pos_bits"),
-                                       self._engine_widths if self.engine_unsupported_reason() is None else (8, 8, 8))))
+                                       self._engine_widths if self.features_unsupported_reason() is None else (8, 8, 8))))
 
     def _engine_operator_args(self):
         return dict(int_sqrt=True) if self.ln_int_sqrt else {}      # a plain model's engine is built with today's arguments
@@ -253,7 +267,7 @@ class VisionTransformer(EngineDispatch, ModuleGraph, nn.Module):
         if not self.is_frozen():
             self.invalidate_engine()     # running-stat QuantActs replace their range buffers: any snapshot is stale
         # a frozen model run module by module carries int8 between its modules (quantization_utils/lazy.py)
-        with lazy.scope(x.is_cuda and not self.training and self._carries_integers() and self.is_frozen()):
+        with lazy.scope(self._carries(x)):
             x, s = self.forward_features(x)
             x, _ = self.head(x, s)
         return x.to_float(boundary=True) if isinstance(x, lazy.QT) else x
@@ -273,7 +287,7 @@ class VisionTransformer(EngineDispatch, ModuleGraph, nn.Module):
         bits = int(getattr(self.blocks[0].attn.int_softmax, "output_bit", 8))
         if bits != 8:          # on either path, and before an engine is built for it
             raise ValueError(f"attention_maps: the softmax output is {bits} bits wide (8-bit probabilities only)")
-        if self.takes_engine(x):
+        if self.takes_engine_for_features(x):      # (takes_engine's answer for a model with a head)
             return self.engine(x.shape[0]).attention_maps(x.contiguous().float(), layers, rows)
         maps, handles = {}, []
 
@@ -295,11 +309,18 @@ class VisionTransformer(EngineDispatch, ModuleGraph, nn.Module):
                 if not self.is_frozen():
                     self.invalidate_engine()
                 f, s = self.forward_features(x)
-                self.head(f, s)
+                if self.num_classes > 0:
+                    self.head(f, s)
         finally:
             for h in handles:
                 h.remove()
         return {i: maps[i] for i in layers}, 2.0 ** -7
+
+    def forward_intermediates_early(self, x, indices=None, integers=False):
+        """forward_intermediates with an early stop: where the fused engine is taken it launches nothing behind the last selected
+        block (IntViTEngine.forward_intermediates_early: the same maps and scales; its workspace logits are then stale).  The
+        module path (_hooked_intermediates) runs the whole forward regardless."""
+        return self._intermediates(x, indices, integers, True)
 
     def forward_intermediates(self, x, indices=None, integers=False):
         """The residual stream behind the selected blocks as feature maps -> (maps, scales): maps = {index: float32 [B, C, Gh, Gw]}
@@ -309,10 +330,14 @@ class VisionTransformer(EngineDispatch, ModuleGraph, nn.Module):
         Where forward() takes the fused engine this is IntViTEngine.forward_intermediates: the eager engine forward plus one
         launch per selected block.  Otherwise the modules are called one by one as the reference's forward calls them, with
         forward hooks on the selected blocks: the reference's own tensor, at the module path's speed."""
+        return self._intermediates(x, indices, integers, False)
+
+    def _intermediates(self, x, indices, integers, stop_early):
         from .engine_common import intermediate_indices
         idx = intermediate_indices(indices, self.depth, "block")
-        if self.takes_engine(x):
-            return self.engine(x.shape[0]).forward_intermediates(x.contiguous().float(), idx, integers)
+        if self.takes_engine_for_features(x):      # (takes_engine's answer for a model with a head)
+            eng = self.engine(x.shape[0])
+            return (eng.forward_intermediates_early if stop_early else eng.forward_intermediates)(x.contiguous().float(), idx, integers)
         grid = tuple(self.patch_embed.grid_size)
         got = self._hooked_intermediates(x, {i: (self.blocks[i], f"blocks.{i}", self.blocks[i].qact4, 1, grid) for i in idx}, integers)
         return {i: got[i][0] for i in idx}, {i: got[i][1] for i in idx}

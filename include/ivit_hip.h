@@ -998,6 +998,20 @@ int ivit_tokens_to_nchw_i16_f32(const int16_t* x, int64_t ldx, int B, int T_all,
 int ivit_tokens_to_nchw_i8(const int8_t* x, int64_t ldx, int B, int T_all, int t0, int T, int C, int8_t* out, ivit_stream_t stream);
 int ivit_tokens_to_nchw_i16(const int16_t* x, int64_t ldx, int B, int T_all, int t0, int T, int C, int16_t* out, ivit_stream_t stream);
 
+/* ---- backbone outputs: int8 rows as float32 rows (forward_features) ---------------------------------------------------------
+ * out[r * ldo + c] = (float)x[r * ldx + c] * s for 0 <= r < rows, 0 <= c < C: ONE float32 multiplication, the arithmetic of
+ * ivit_tokens_to_nchw_i8_f32 (the reference's quant_act_int * act_scaling_factor bit for bit).  Rows are strided on both sides
+ * (ldx >= C, ldo >= C, in elements): out may be a block of rows and columns of a larger feature bank.  Elements C .. ldx - 1 of an
+ * input row are not read, elements C .. ldo - 1 of an output row are not written, nor is anything outside the rows.
+ * The far dimension is `rows`: r * ldx and r * ldo are 64-bit products, so a row may start beyond 2^31 bytes of x and beyond 2^32
+ * bytes of out; one row (C) stays an int.
+ * x and ldx may have any alignment, out that of a float.  Per row: where the input row and the output row reach a 16-byte
+ * boundary at the same channel, 16 int8 are one load and four float4 stores, with a scalar head and tail; any other row goes
+ * element by element.  One launch; rows == 0 is IVIT_OK without one.
+ * Errors: IVIT_ERR_INVALID for a NULL x or out, C < 1, rows < 0, ldx < C, ldo < C, out not aligned to a float, or more than
+ * 2^31 - 1 workgroups of 256 slots (a row has C / 16 + 2 slots).  Nothing is launched on an error. */
+int ivit_dequant_rows_i8_f32(const int8_t* x, int64_t ldx, int64_t rows, int C, float s, float* out, int64_t ldo, ivit_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
