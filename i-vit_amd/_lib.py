@@ -45,6 +45,7 @@ SIGNATURES = {
     "ivit_gemm_i8_requant_residual_bits_ex": [vp, i64, vp, i64, vp, vp, vp, vp, i64, u32, i32, u32, i32, vp, i64, ci, ci, ci, ci, ci, ci, vp],
     "ivit_gemm_i8_requant_qkv_ex": [vp, i64, vp, i64, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp],
     "ivit_gemm_i8_requant_qkv_planes_ex": [vp, i64, vp, i64, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp],
+    "ivit_gemm_plan": [ci, ci, ci, ci, ci, vp],      # host function: the launcher's decision (gemm_forms.py mirrors it)
     "ivit_gemm_i8_requant_residual_i16": [vp, i64, vp, i64, vp, vp, vp, vp, i64, u32, i32, u32, i32, vp, i64, ci, ci, ci, vp],
     "ivit_gemm_i8_requant_lut_ex": [vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, ci, ci, ci, ci, vp],
     "ivit_gemm_i8_requant_i16": [vp, i64, vp, i64, vp, vp, vp, vp, i64, ci, ci, ci, vp],

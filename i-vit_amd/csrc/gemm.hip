@@ -1106,11 +1106,34 @@ __global__ __launch_bounds__(SK_NT, 2) void gemm_i8_skinny_kernel(GemmArgs g)
     }
 }
 
-template <int EPIW>
-int launch_gemm(GemmArgs& g, const char* name, ivit_stream_t stream, int qkv_planes = 3)   // EPI_QKV: N = qkv_planes * heads * head_dim
+// ---- the launcher: gemm_check (are the arguments a GEMM), gemm_plan (which kernel, on which grid), gemm_launch (the launch) ----
+// which kernels exist for an epilogue kind: the plan and the launch step's instantiations read the same predicates
+constexpr bool epi_has_skinny(int epi) { return epi == EPI_RQ || epi == EPI_QKV; }
+constexpr bool epi_has_wreg(int epi) { return epi != EPI_I32 && epi != EPI_RQ16; }                  // 32x32x32 weights in registers
+constexpr bool epi_has_wreg16(int epi) { return epi_has_wreg(epi) && epi != EPI_RQ16_RES16; }       // 16x16x64 weights in registers
+constexpr bool epi_has_pers(int epi) { return epi_has_wreg(epi) && epi != EPI_RQ16_RES16; }         // persistent LDS-DMA kernel
+constexpr bool epi_int8_out(int epi) { return epi == EPI_RQ || epi == EPI_RESID || epi == EPI_QKV; }
+// the callers' rule for a fragment copy whose consumer works in 256-channel tiles (i-vit_amd/gemm_forms.py; reported by ivit_gemm_plan)
+constexpr bool wr_tiles_fit(int N) { return (N + WR_CH - 1) / WR_CH * WR_CH * WR_WASTE_DEN <= N * (WR_WASTE_DEN + 1); }
+
+enum { GEMM_SMALL = IVIT_GEMM_FORM_SMALL, GEMM_PERS = IVIT_GEMM_FORM_PERS, GEMM_WREG = IVIT_GEMM_FORM_WREG, GEMM_WREG16 = IVIT_GEMM_FORM_WREG16,
+       GEMM_SKINNY = IVIT_GEMM_FORM_SKINNY };
+static_assert(EPI_RQ == IVIT_GEMM_EPI_RQ && EPI_RESID == IVIT_GEMM_EPI_RESID && EPI_QKV == IVIT_GEMM_EPI_QKV && EPI_I32 == IVIT_GEMM_EPI_I32 &&
+              EPI_RESID16 == IVIT_GEMM_EPI_RESID16 && EPI_RQ16 == IVIT_GEMM_EPI_RQ16 && EPI_RQ16_RES16 == IVIT_GEMM_EPI_RQ16_RES16,
+              "include/ivit_hip.h names the epilogue kinds for ivit_gemm_plan");
+
+struct GemmPlan {
+    int form;
+    int nks;                   // GEMM_SKINNY: the instantiation for K = 32 nks (4, 2), 0 = the run-time-K one
+    int res_f32;               // GEMM_WREG16, EPI_RESID: the residual QuantAct on float32 fmas (residual_f32_form)
+    int narrow, stamped, ablation;      // lab build only: 128-channel work items, the stamped instantiation, timing ablation number
+    int grid, lds;             // workgroups, dynamic LDS bytes
+    int tiles_m, tiles_n, split_from;
+    int stagger, stagger_units, cu_turns;       // persistent kernel (GemmArgs)
+};
+
+int gemm_check(int EPI, const GemmArgs& g, const char* name, int qkv_planes)   // EPI_QKV: N = qkv_planes * heads * head_dim
 {
-    constexpr int EPI = epi_kind(EPIW);
-    constexpr bool NARROW = EPIW != EPI;     // a 4-bit form: the product's kernels only, none of the lab build's ablations
     IVIT_REQUIRE(g.A && g.W && g.out, "%s: NULL operand", name);
     IVIT_REQUIRE(g.M > 0 && g.N > 0 && g.K > 0, "%s: empty problem M=%d N=%d K=%d", name, g.M, g.N, g.K);
     IVIT_REQUIRE(g.K % BK == 0, "%s: K=%d must be a multiple of %d", name, g.K, BK);
@@ -1148,27 +1171,33 @@ int launch_gemm(GemmArgs& g, const char* name, ivit_stream_t stream, int qkv_pla
         IVIT_REQUIRE(g.N == qkv_planes * g.heads * g.head_dim && g.M % g.tokens == 0,
                      "%s: N=%d != %d*heads*head_dim or M=%d %% tokens=%d != 0", name, g.N, qkv_planes, g.M, g.tokens);
     }
-#if IVIT_LAB
-    g.stamp = reinterpret_cast<unsigned long long*>(g_stamp_buf);
-#endif
+    return IVIT_OK;
+}
+
+// Which kernel runs a checked problem, on which grid: a function of the epilogue kind, the shape, the leading dimensions, the layout
+// fields of `g` and the lab words.  No HIP call; no pointer of `g` is followed (lut, stamp: present or not).  The operands'
+// 16-byte alignment is gemm_check's.  ivit_gemm_plan exports it; i-vit_amd/gemm_forms.py mirrors the form it names.
+int gemm_plan(int EPIW, const GemmArgs& g, const char* name, GemmPlan& p)
+{
+    const int EPI = epi_kind(EPIW);
+    const bool lab_forms = IVIT_LAB && EPIW == EPI;     // a 4-bit form: the product's kernels only, none of the lab build's ablations
     const bool blocks = g.a_blocks || g.w_blocks;
-    if constexpr (EPI == EPI_RQ || EPI == EPI_QKV) {
-        // skinny-K form: a streaming pass with the whole weight matrix in LDS (Swin stage 0); lab flags2 bit 20: off (A/B, parity of both)
-        if (!blocks && !g.w_frags && !g.out_blocks && !g.lut && g.M >= 8192 && g.K >= 32 && g.K <= SK_MAXK && g.K % 32 == 0 && g.N >= 16 &&
-            g.N <= SK_MAXN && g.N % 16 == 0 && g.lda % 16 == 0 && g.ldw % 8 == 0 && ((uintptr_t)g.A % 16 == 0) && ((uintptr_t)g.W % 8 == 0) &&
-            ((uintptr_t)g.out % 16 == 0) && (EPI == EPI_QKV || g.ldo % 16 == 0) && (EPI != EPI_QKV || g.head_dim % 16 == 0) && (int64_t)g.M * (EPI == EPI_QKV ? g.N : g.ldo) < 4294967296ll &&
-            !g_force_small && !(IVIT_LAB && (g_debug_flags2 & (1 << 20)))) {
-            const int nstrips = (g.M + 15) >> 4;
-            const int grid = (nstrips + SK_WPB - 1) / SK_WPB < 512 ? (nstrips + SK_WPB - 1) / SK_WPB : 512;      // two workgroups of 8 waves per CU
-            const bool any_k = IVIT_LAB && (g_debug_flags2 & (1 << 21));      // lab A/B: the run-time-K instantiation for every K
-            if (g.K == 128 && !any_k) hipLaunchKernelGGL((gemm_i8_skinny_kernel<EPIW, 4>), dim3(grid), dim3(SK_NT), 0, ivit_stream(stream), g);
-            else if (g.K == 64 && !any_k) hipLaunchKernelGGL((gemm_i8_skinny_kernel<EPIW, 2>), dim3(grid), dim3(SK_NT), 0, ivit_stream(stream), g);
-            else hipLaunchKernelGGL((gemm_i8_skinny_kernel<EPIW, 0>), dim3(grid), dim3(SK_NT), 0, ivit_stream(stream), g);
-            IVIT_CHECK_LAUNCH(name);
-        }
+    p = GemmPlan{};
+    // skinny-K form: a streaming pass with the whole weight matrix in LDS (Swin stage 0); lab flags2 bit 20: off (A/B, parity of both)
+    if (epi_has_skinny(EPI) && !blocks && !g.w_frags && !g.out_blocks && !g.lut && g.M >= SK_MIN_M && g.K >= 32 && g.K <= SK_MAXK &&
+        g.K % 32 == 0 && g.N >= 16 && g.N <= SK_MAXN && g.N % 16 == 0 && g.lda % 16 == 0 && g.ldw % 8 == 0 && (EPI == EPI_QKV || g.ldo % 16 == 0) &&
+        (EPI != EPI_QKV || g.head_dim % 16 == 0) && (int64_t)g.M * (EPI == EPI_QKV ? g.N : g.ldo) < 4294967296ll && !g_force_small &&
+        !(g_debug_flags2 & LAB2_NO_SKINNY)) {
+        const int nstrips = (g.M + 15) >> 4, wgs = (nstrips + SK_WPB - 1) / SK_WPB;
+        p.form = GEMM_SKINNY;
+        p.grid = wgs < WG_SLOTS ? wgs : WG_SLOTS;      // two workgroups of 8 waves per CU
+        const bool any_k = (g_debug_flags2 & LAB2_SKINNY_ANY_K) != 0;      // lab A/B: the run-time-K instantiation for every K
+        p.nks = any_k ? 0 : g.K == 128 ? 4 : g.K == 64 ? 2 : 0;
+        return IVIT_OK;
     }
+    const bool big = g.M >= BIG_MIN_M && !g_force_small;
     if (blocks && !g.w_frags) {
-        IVIT_REQUIRE(EPI != EPI_I32 && EPI != EPI_RQ16 && g.M >= 2048 && g.N >= BCH && !g_force_small,
+        IVIT_REQUIRE(epi_has_wreg(EPI) && big && g.N >= BCH,
                      "%s: block-layout operands need the persistent kernel (M >= 2048, N >= 128, requantising epilogue)", name);
         IVIT_REQUIRE(!g.a_blocks || g.lda == g.K, "%s: a block-layout A operand is dense (lda == K)", name);
         IVIT_REQUIRE(!g.w_blocks || g.ldw == g.K, "%s: a block-layout W operand is dense (ldw == K)", name);
@@ -1176,113 +1205,213 @@ int launch_gemm(GemmArgs& g, const char* name, ivit_stream_t stream, int qkv_pla
     if (g.w_frags) IVIT_REQUIRE(!g.a_blocks || g.lda == g.K, "%s: a block-layout A operand is dense (lda == K)", name);
     IVIT_REQUIRE(!g.lut || (g.w_frags && EPI == EPI_RQ), "%s: the output map needs the fragment-packed weight form (IVIT_W_FRAGS)", name);
     if (g.w_frags) {
-        IVIT_REQUIRE(EPI != EPI_I32 && EPI != EPI_RQ16 && g.M >= 2048 && g.N >= 128 && g.N % 64 == 0 && (g.K / BK) % 3 == 0 && !g.w_blocks && !g_force_small,
+        IVIT_REQUIRE(epi_has_wreg(EPI) && big && g.N >= 128 && g.N % 64 == 0 && (g.K / BK) % 3 == 0 && !g.w_blocks,
                      "%s: the fragment-packed weight needs M >= 2048, N >= 128, N %% 64 == 0, K %% 192 == 0 and a requantising epilogue", name);
-        if constexpr (EPI != EPI_I32 && EPI != EPI_RQ16) {
-            g.tiles_m = (g.M + WR_TOK - 1) / WR_TOK;
-            g.tiles_n = (g.N + WR_CH - 1) / WR_CH;
-            // Narrow tiles (128 x 128, wr_tile): built in round 4 for the widths 256-channel tiles fit badly and for launches with few
-            // tiles, measured at every GEMM shape of the BASELINE configs (scripts/gemm_narrow_ab.py, profiles/r04f_*) and SLOWER
-            // nearly everywhere (x 1.08 - 1.44; DeiT-S attn.proj -5 %, Swin stage-1 qkv equal): a wave's 16 MFMAs per K step carry the
-            // same barrier, waits and six loads as 32.  What did pay is running the 256-channel tiles at N = 384 / 1152 / 576 at all
-            // (padding of 25 / 10 / 11 %) instead of the LDS-DMA kernel: DeiT-S b64 proj 17 -> 11 us.  Lab flags2 bit 13 selects them.
-            g.narrow = 0;
-            if constexpr (EPI == EPI_RQ || EPI == EPI_RESID || EPI == EPI_QKV) {
-                if (IVIT_LAB && g.w_frags == 2 && !g.lut && (g_debug_flags2 & 8192) && !(g_debug_flags2 & 256)) {
-                    g.narrow = 1;
-                    g.tiles_n = (g.N + WR_CH / 2 - 1) / (WR_CH / 2);
-                }
-            }
-            const int ntiles = g.tiles_m * g.tiles_n;
-            // A sparse last round (R tiles on 512 slots) runs as 2R half tiles of 64 tokens (wr_work) when every half tile still
-            // finds a CU of its own (2R <= 256): fc1 at the headline shape, R = 120, 144 -> 136 us.  Beyond that two half tiles
-            // share a CU while a lone full tile has one to itself and runs nearly twice as fast: measured slower (N = 768,
-            // R = 158: proj 53.8 -> 60.5 us, fc2 124 -> 135 us with the residual epilogue).  Lab bit 27: off, bit 11: up to 2R <= 512.
-            const int rounds = ntiles / 512, R = ntiles - rounds * 512;
-            const bool split = !g.narrow && rounds > 0 && R > 0 && 2 * R <= ((g_debug_flags & 2048) ? 512 : 256) && !(g_debug_flags & 134217728);
-            g.split_from = split ? rounds * 512 : ntiles;
-            // Round 4: a launch with at most 256 tiles (DeiT-S attn.proj / fc2 at batch 64: 198; Swin stage 3: 147) runs ALL of them as half
-            // tiles of 64 tokens, one per workgroup: such a launch lasts as long as ONE tile (main loop + epilogue, ~15 K cycles), and a
-            // half tile's epilogue is half as long, its K steps 16 MFMAs per wave instead of 32 (lab bit 27: off)
-            const bool all_halves = g.w_frags == 2 && !g.narrow && rounds == 0 && 2 * ntiles <= 512 && !(g_debug_flags & 134217728);
-            if (all_halves) g.split_from = 0;
-            const dim3 grid(all_halves ? 2 * ntiles : (ntiles < 512 ? ntiles : 512));
+        p.tiles_m = (g.M + WR_TOK - 1) / WR_TOK;
+        p.tiles_n = (g.N + WR_CH - 1) / WR_CH;
+        // Narrow tiles (128 x 128, wr_tile): built in round 4 for the widths 256-channel tiles fit badly and for launches with few
+        // tiles, measured at every GEMM shape of the BASELINE configs (scripts/gemm_narrow_ab.py, profiles/r04f_*) and SLOWER
+        // nearly everywhere (x 1.08 - 1.44; DeiT-S attn.proj -5 %, Swin stage-1 qkv equal): a wave's 16 MFMAs per K step carry the
+        // same barrier, waits and six loads as 32.  What did pay is running the 256-channel tiles at N = 384 / 1152 / 576 at all
+        // (padding of 25 / 10 / 11 %) instead of the LDS-DMA kernel: DeiT-S b64 proj 17 -> 11 us.  Lab flags2 bit 13 selects them.
+        if (IVIT_LAB && epi_int8_out(EPI) && g.w_frags == 2 && !g.lut && (g_debug_flags2 & LAB2_WR16_NARROW) && !(g_debug_flags2 & LAB2_WR16_STAMPS)) {
+            p.narrow = 1;
+            p.tiles_n = (g.N + WR_CH / 2 - 1) / (WR_CH / 2);
+        }
+        const int ntiles = p.tiles_m * p.tiles_n;
+        // A sparse last round (R tiles on 512 slots) runs as 2R half tiles of 64 tokens (wr_work) when every half tile still
+        // finds a CU of its own (2R <= 256): fc1 at the headline shape, R = 120, 144 -> 136 us.  Beyond that two half tiles
+        // share a CU while a lone full tile has one to itself and runs nearly twice as fast: measured slower (N = 768,
+        // R = 158: proj 53.8 -> 60.5 us, fc2 124 -> 135 us with the residual epilogue).  Lab bit 27: off, bit 11: up to 2R <= 512.
+        const int rounds = ntiles / WG_SLOTS, R = ntiles - rounds * WG_SLOTS;
+        const bool halves = !p.narrow && !(g_debug_flags & LAB_NO_HALVES);
+        const bool split = halves && rounds > 0 && R > 0 && 2 * R <= ((g_debug_flags & LAB_SPLIT_ALL_SLOTS) ? WG_SLOTS : HALF_TILE_WGS);
+        p.split_from = split ? rounds * WG_SLOTS : ntiles;
+        // Round 4: a launch with at most 256 tiles (DeiT-S attn.proj / fc2 at batch 64: 198; Swin stage 3: 147) runs ALL of them as half
+        // tiles of 64 tokens, one per workgroup: such a launch lasts as long as ONE tile (main loop + epilogue, ~15 K cycles), and a
+        // half tile's epilogue is half as long, its K steps 16 MFMAs per wave instead of 32 (lab bit 27: off)
+        const bool all_halves = halves && g.w_frags == 2 && rounds == 0 && 2 * ntiles <= WG_SLOTS;
+        if (all_halves) p.split_from = 0;
+        p.grid = all_halves ? 2 * ntiles : (ntiles < WG_SLOTS ? ntiles : WG_SLOTS);
+        // timing ablations (scripts/gemm_ab.py --frags): what each stream of the 32x32x32 kernel costs, whichever fragment bit came
+        constexpr unsigned ABLATIONS = 1u << 1 | 1u << 2 | 1u << 4 | 1u << 6 | 1u << 7 | 1u << 8 | 1u << 14 | 1u << 15 | 1u << LAB_WR_STAMPS;
+        const int abl = g_debug_flags & LAB_WR_ABLATION;      // (the instantiations of launch_wreg_ablation; any other number: the product's kernel)
+        if (lab_forms && EPI == EPI_RQ && ((ABLATIONS >> abl) & 1)) {
+            p.form = GEMM_WREG;
+            p.ablation = abl;
+            if (abl == LAB_WR_STAMPS && (g_debug_flags & LAB_ONE_PER_CU)) p.grid = 256, p.lds = 40960;      // one workgroup per CU
+            return IVIT_OK;
+        }
+        if (g.w_frags == 1) {
+            p.form = GEMM_WREG;
+            return IVIT_OK;
+        }
+        // IVIT_W_FRAGS16: the v_mfma_i32_16x16x64_i8 form
+        IVIT_REQUIRE(epi_has_wreg16(EPI), "%s: IVIT_W_FRAGS16 has no 16-bit epilogue; pack the weights with ivit_pack_weight_frags_i8", name);
+        // its epilogue addresses residual and output with 32-bit byte offsets
+        IVIT_REQUIRE(((int64_t)g.M + 16) * (EPI == EPI_QKV ? g.N : g.ldo) < 4294967296ll &&
+                         (EPI != EPI_RESID || ((int64_t)g.M + 16) * g.ldr < 4294967296ll),
+                     "%s: IVIT_W_FRAGS16 addresses its output (and residual) with 32-bit offsets: operand of 4 GiB or more", name);
+        p.form = GEMM_WREG16;
+        // stamped timeline (scripts/wreg_timeline.py --s16)
+        p.stamped = lab_forms && (EPI == EPI_RQ || EPI == EPI_RESID) && (g_debug_flags2 & LAB2_WR16_STAMPS) && g.stamp;
+        p.res_f32 = EPI == EPI_RESID && g.res_f32;      // ABL bit 12: the residual QuantAct on float32 fmas (residual_f32_form)
+        return IVIT_OK;
+    }
+    if (epi_has_pers(EPI) && big && g.N >= BCH) {
+        p.form = GEMM_PERS;
+        p.stagger = (g_debug_flags & LAB_NO_STAGGER) ? 0 : WG_SLOTS;  // 2 workgroups x 256 CUs
+        p.tiles_m = (g.M + BTOK - 1) / BTOK;
+        p.tiles_n = (g.N + BCH - 1) / BCH;
+        const int ntiles = p.tiles_m * p.tiles_n;
+        // 2 resident workgroups x 256 CUs; debug bit 12: one workgroup per CU (extra dynamic LDS blocks the second)
+        const bool one_per_cu = (g_debug_flags & LAB_ONE_PER_CU) != 0;
+        // debug bit 26: a 256-workgroup grid WITHOUT the LDS blocker (probe: two streams' GEMMs sharing the CUs)
+        const int SLOTS = (one_per_cu || (g_debug_flags & LAB_GRID_256)) ? WG_SLOTS / 2 : WG_SLOTS;
+        // tail split (see PersWork): R tiles of a sparse last round become 2R half tiles (256 x 128 -> two 128 x 128).
+        // A CU left with one workgroup runs it nearly twice as fast, so splitting a last round that already occupies more
+        // than half of the CUs does not pay (proj 47.7 -> 50.0 us, fc2 162 -> 173 us with 1182 tiles on 512 slots).
+        const int rounds = ntiles / SLOTS, R = ntiles - rounds * SLOTS;
+        // Default: split only when the 2R half tiles still find a CU each (2R <= 256): then the tail round uses twice the
+        // CUs for half the time (fc1, R = 120: 146 -> 140 us); beyond that two half tiles share a CU and it only adds their
+        // overhead.  Debug bit 11 forces the split up to 2R <= SLOTS, bit 27 disables it.
+        const bool split = R > 0 && !(g_debug_flags & LAB_NO_HALVES) &&
+                           2 * R <= ((g_debug_flags & LAB_SPLIT_ALL_SLOTS) ? SLOTS : HALF_TILE_WGS) && !one_per_cu;
+        p.split_from = split ? rounds * SLOTS : ntiles;
+        p.cu_turns = (g_debug_flags & LAB_CU_TURNS) ? 1 : 0;
+        // start delay of the second co-resident workgroup: measured (scripts/gemm_ab.py, interleaved) 0..10 units are
+        // equivalent and the former half-main-loop delay (26 / 98 units at K = 768 / 3072) cost 4-8 %: off by default
+        p.stagger_units = (g_debug_flags >> LAB_DELAY_SHIFT) & LAB_DELAY_MASK;
+        p.grid = rounds > 0 ? SLOTS : (split ? 2 * R : R);
+        p.lds = one_per_cu ? 20480 : 0;
+        return IVIT_OK;
+    }
+    p.form = GEMM_SMALL;
+    p.tiles_m = (g.M + BM - 1) / BM;
+    p.tiles_n = (g.N + BN - 1) / BN;
+    p.grid = p.tiles_m * p.tiles_n;
+    return IVIT_OK;
+}
+
 #if IVIT_LAB
-            if constexpr (EPI == EPI_RQ && !NARROW) {   // timing ablations (scripts/gemm_ab.py --frags): what each stream of the kernel costs
-                switch (g_debug_flags & 31) {
-#define IVIT_WR_ABL(v) case v: hipLaunchKernelGGL((gemm_i8_wreg_kernel<EPI_RQ, v>), grid, dim3(BIG_NT), 0, ivit_stream(stream), g); IVIT_CHECK_LAUNCH(name)
-                    case 16: g.res = (const int8_t*)g_stamp_buf; hipLaunchKernelGGL((gemm_i8_wreg_kernel<EPI_RQ, 16>), (g_debug_flags & 4096) ? dim3(256) : grid, dim3(BIG_NT), (g_debug_flags & 4096) ? 40960 : 0, ivit_stream(stream), g); IVIT_CHECK_LAUNCH(name);
-                    IVIT_WR_ABL(1); IVIT_WR_ABL(2); IVIT_WR_ABL(4); IVIT_WR_ABL(6); IVIT_WR_ABL(8); IVIT_WR_ABL(14); IVIT_WR_ABL(15); IVIT_WR_ABL(7);
+// the timing ablations of gemm_i8_wreg_kernel<EPI_RQ> (GemmPlan::ablation); false: no such instantiation
+bool launch_wreg_ablation(GemmArgs& g, const GemmPlan& p, ivit_stream_t stream)
+{
+    if (p.ablation == LAB_WR_STAMPS) g.res = (const int8_t*)g_stamp_buf;
+    switch (p.ablation) {
+#define IVIT_WR_ABL(v) case v: hipLaunchKernelGGL((gemm_i8_wreg_kernel<EPI_RQ, v>), dim3(p.grid), dim3(BIG_NT), p.lds, ivit_stream(stream), g); return true
+        IVIT_WR_ABL(16); IVIT_WR_ABL(1); IVIT_WR_ABL(2); IVIT_WR_ABL(4); IVIT_WR_ABL(6); IVIT_WR_ABL(8); IVIT_WR_ABL(14); IVIT_WR_ABL(15); IVIT_WR_ABL(7);
 #undef IVIT_WR_ABL
-                    default: break;
-                }
-            }
+        default: return false;
+    }
+}
 #endif
-            if (g.w_frags == 2) {     // IVIT_W_FRAGS16: the v_mfma_i32_16x16x64_i8 form
-                if constexpr (EPI != EPI_RQ16_RES16) {
-                    // its epilogue addresses residual and output with 32-bit byte offsets
-                    IVIT_REQUIRE(((int64_t)g.M + 16) * (EPI == EPI_QKV ? g.N : g.ldo) < 4294967296ll &&
-                                     (EPI != EPI_RESID || ((int64_t)g.M + 16) * g.ldr < 4294967296ll),
-                                 "%s: IVIT_W_FRAGS16 addresses its output (and residual) with 32-bit offsets: operand of 4 GiB or more", name);
+
+// the launch of a plan: every kernel instantiation appears once
+template <int EPIW>
+int gemm_launch(GemmArgs& g, const GemmPlan& p, const char* name, ivit_stream_t stream)
+{
+    constexpr int EPI = epi_kind(EPIW);
+    g.tiles_m = p.tiles_m; g.tiles_n = p.tiles_n; g.split_from = p.split_from; g.narrow = p.narrow;
+    g.stagger = p.stagger; g.stagger_units = p.stagger_units; g.cu_turns = p.cu_turns;
+#define IVIT_GEMM_LAUNCH(kernel, threads) hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(threads), p.lds, ivit_stream(stream), g)
+#define IVIT_GEMM_NO_KERNEL IVIT_REQUIRE(false, "%s: no kernel of form %d for this epilogue", name, p.form)      // gemm_plan never names one
+    switch (p.form) {
+        case GEMM_SKINNY:
+            if constexpr (epi_has_skinny(EPI)) {
+                if (p.nks == 4) IVIT_GEMM_LAUNCH((gemm_i8_skinny_kernel<EPIW, 4>), SK_NT);
+                else if (p.nks == 2) IVIT_GEMM_LAUNCH((gemm_i8_skinny_kernel<EPIW, 2>), SK_NT);
+                else IVIT_GEMM_LAUNCH((gemm_i8_skinny_kernel<EPIW, 0>), SK_NT);
+                break;
+            }
+            IVIT_GEMM_NO_KERNEL;
+        case GEMM_WREG16:
+            if constexpr (epi_has_wreg16(EPI)) {
 #if IVIT_LAB
-                    if constexpr ((EPI == EPI_RQ || EPI == EPI_RESID) && !NARROW) {
-                        if ((g_debug_flags2 & 256) && g.stamp) {   // stamped timeline (scripts/wreg_timeline.py --s16)
-                            if (EPI == EPI_RESID && g.res_f32) hipLaunchKernelGGL((gemm_i8_wreg_kernel<EPI, 16 | 2048 | 4096, true>), grid, dim3(BIG_NT), 0, ivit_stream(stream), g);
-                            else hipLaunchKernelGGL((gemm_i8_wreg_kernel<EPI, 16 | 2048, true>), grid, dim3(BIG_NT), 0, ivit_stream(stream), g);
-                            IVIT_CHECK_LAUNCH(name);
-                        }
+                if constexpr ((EPI == EPI_RQ || EPI == EPI_RESID) && EPIW == EPI) {
+                    if (p.stamped) {
+                        if (p.res_f32) IVIT_GEMM_LAUNCH((gemm_i8_wreg_kernel<EPI, 16 | 2048 | 4096, true>), BIG_NT);
+                        else IVIT_GEMM_LAUNCH((gemm_i8_wreg_kernel<EPI, 16 | 2048, true>), BIG_NT);
+                        break;
                     }
-#endif
-                    if constexpr (EPI == EPI_RESID) {
-                        if (g.res_f32) {     // ABL bit 12: the residual QuantAct on float32 fmas (residual_f32_form)
-                            hipLaunchKernelGGL((gemm_i8_wreg_kernel<EPIW, 4096, true>), grid, dim3(BIG_NT), 0, ivit_stream(stream), g);
-                            IVIT_CHECK_LAUNCH(name);
-                        }
-                    }
-                    hipLaunchKernelGGL((gemm_i8_wreg_kernel<EPIW, 0, true>), grid, dim3(BIG_NT), 0, ivit_stream(stream), g);
-                    IVIT_CHECK_LAUNCH(name);
-                } else {
-                    IVIT_REQUIRE(false, "%s: IVIT_W_FRAGS16 has no 16-bit epilogue; pack the weights with ivit_pack_weight_frags_i8", name);
                 }
+#endif
+                if constexpr (EPI == EPI_RESID) {
+                    if (p.res_f32) {
+                        IVIT_GEMM_LAUNCH((gemm_i8_wreg_kernel<EPIW, 4096, true>), BIG_NT);
+                        break;
+                    }
+                }
+                IVIT_GEMM_LAUNCH((gemm_i8_wreg_kernel<EPIW, 0, true>), BIG_NT);
+                break;
             }
-            hipLaunchKernelGGL((gemm_i8_wreg_kernel<EPIW>), grid, dim3(BIG_NT), 0, ivit_stream(stream), g);
-            IVIT_CHECK_LAUNCH(name);
-        }
+            IVIT_GEMM_NO_KERNEL;
+        case GEMM_WREG:
+            if constexpr (epi_has_wreg(EPI)) {
+#if IVIT_LAB
+                if constexpr (EPIW == EPI_RQ) {
+                    if (launch_wreg_ablation(g, p, stream)) break;
+                }
+#endif
+                IVIT_GEMM_LAUNCH((gemm_i8_wreg_kernel<EPIW>), BIG_NT);
+                break;
+            }
+            IVIT_GEMM_NO_KERNEL;
+        case GEMM_PERS:
+            if constexpr (epi_has_pers(EPI)) {
+                IVIT_GEMM_LAUNCH((gemm_i8_pers_kernel<EPIW>), BIG_NT);
+                break;
+            }
+            IVIT_GEMM_NO_KERNEL;
+        case GEMM_SMALL:
+            IVIT_GEMM_LAUNCH(gemm_i8_kernel<EPIW>, NT);
+            break;
+        default:
+            IVIT_GEMM_NO_KERNEL;
     }
-    if constexpr (EPI != EPI_I32 && EPI != EPI_RQ16 && EPI != EPI_RQ16_RES16) {
-        if (g.M >= 2048 && g.N >= BCH && !g_force_small) {
-            g.stagger = (g_debug_flags & 64) ? 0 : 512;  // 2 workgroups x 256 CUs
-            g.tiles_m = (g.M + BTOK - 1) / BTOK;
-            g.tiles_n = (g.N + BCH - 1) / BCH;
-            const int ntiles = g.tiles_m * g.tiles_n;
-            // 2 resident workgroups x 256 CUs; debug bit 12: one workgroup per CU (extra dynamic LDS blocks the second)
-            const bool one_per_cu = (g_debug_flags & 4096) != 0;
-            // debug bit 26: a 256-workgroup grid WITHOUT the LDS blocker (probe: two streams' GEMMs sharing the CUs)
-            const int SLOTS = (one_per_cu || (g_debug_flags & 67108864)) ? 256 : 512;
-            // tail split (see PersWork): R tiles of a sparse last round become 2R half tiles (256 x 128 -> two 128 x 128).
-            // A CU left with one workgroup runs it nearly twice as fast, so splitting a last round that already occupies more
-            // than half of the CUs does not pay (proj 47.7 -> 50.0 us, fc2 162 -> 173 us with 1182 tiles on 512 slots).
-            const int rounds = ntiles / SLOTS, R = ntiles - rounds * SLOTS;
-            // Default: split only when the 2R half tiles still find a CU each (2R <= 256): then the tail round uses twice the
-            // CUs for half the time (fc1, R = 120: 146 -> 140 us); beyond that two half tiles share a CU and it only adds their
-            // overhead.  Debug bit 11 forces the split up to 2R <= SLOTS, bit 27 disables it.
-            const bool split = R > 0 && !(g_debug_flags & 134217728) &&
-                               ((g_debug_flags & 2048) ? 2 * R <= SLOTS : 2 * R <= 256) && !one_per_cu;
-            g.split_from = split ? rounds * SLOTS : ntiles;
-            g.cu_turns = (g_debug_flags & 32768) ? 1 : 0;
-            // start delay of the second co-resident workgroup: measured (scripts/gemm_ab.py, interleaved) 0..10 units are
-            // equivalent and the former half-main-loop delay (26 / 98 units at K = 768 / 3072) cost 4-8 %: off by default
-            g.stagger_units = (g_debug_flags >> 16) & 63;
-            const int grid = rounds > 0 ? SLOTS : (split ? 2 * R : R);
-            hipLaunchKernelGGL((gemm_i8_pers_kernel<EPIW>), dim3(grid), dim3(BIG_NT), one_per_cu ? 20480 : 0, ivit_stream(stream), g);
-            IVIT_CHECK_LAUNCH(name);
-        }
-    }
-    g.tiles_m = (g.M + BM - 1) / BM;
-    g.tiles_n = (g.N + BN - 1) / BN;
-    hipLaunchKernelGGL(gemm_i8_kernel<EPIW>, dim3(g.tiles_m * g.tiles_n), dim3(NT), 0, ivit_stream(stream), g);
+#undef IVIT_GEMM_LAUNCH
+#undef IVIT_GEMM_NO_KERNEL
     IVIT_CHECK_LAUNCH(name);
 }
+
+template <int EPIW>
+int launch_gemm(GemmArgs& g, const char* name, ivit_stream_t stream, int qkv_planes = 3)
+{
+    if (const int rc = gemm_check(epi_kind(EPIW), g, name, qkv_planes)) return rc;
+#if IVIT_LAB
+    g.stamp = reinterpret_cast<unsigned long long*>(g_stamp_buf);
+#endif
+    GemmPlan p;
+    if (const int rc = gemm_plan(EPIW, g, name, p)) return rc;
+    return gemm_launch<EPIW>(g, p, name, stream);
+}
+
+// the fields every entry point fills
+GemmArgs gemm_args(const int8_t* A, int64_t lda, const int8_t* W, int64_t ldw, const int32_t* bias, const uint32_t* m, const int32_t* e,
+                   void* out, int64_t ldo, int M, int N, int K)
+{
+    GemmArgs g{};
+    g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.bias = bias; g.m = m; g.e = e;
+    g.out = out; g.ldo = ldo; g.M = M; g.N = N; g.K = K;
+    return g;
+}
+
+// `layouts` of an _ex entry -> the layout fields of g.  allowed: the IVIT_* layout bits that entry takes
+int gemm_layouts(GemmArgs& g, int layouts, int allowed, const char* name)
+{
+    constexpr int FRAGS = IVIT_W_FRAGS | IVIT_W_FRAGS16;
+    IVIT_REQUIRE((layouts & ~allowed) == 0 && (layouts & FRAGS) != FRAGS, "%s: unknown layout bits", name);
+    g.a_blocks = (layouts & IVIT_A_BLOCKS) != 0;
+    g.w_blocks = (layouts & IVIT_W_BLOCKS) != 0;
+    g.out_blocks = (layouts & IVIT_OUT_BLOCKS) != 0;
+    g.w_frags = (layouts & IVIT_W_FRAGS16) ? 2 : (layouts & IVIT_W_FRAGS) ? 1 : 0;
+    IVIT_REQUIRE(!g.out_blocks || (g.N % 64 == 0 && g.ldo == g.N && ((int64_t)g.M + 15) * g.N < 2147483648ll),
+                 "%s: block-layout output needs N %% 64 == 0, ldo == N and a buffer below 2 GiB", name);
+    return IVIT_OK;
+}
+constexpr int LAYOUTS_RQ = IVIT_A_BLOCKS | IVIT_W_BLOCKS | IVIT_OUT_BLOCKS | IVIT_W_FRAGS | IVIT_W_FRAGS16;   // ivit_gemm_i8_requant(_bits, _lut)_ex
+constexpr int LAYOUTS_IN = LAYOUTS_RQ & ~IVIT_OUT_BLOCKS;          // the residual and q/k/v entries: operand layouts only
+constexpr int LAYOUTS_RQ16_RES16 = IVIT_A_BLOCKS | IVIT_W_FRAGS;   // ivit_gemm_i8_requant_i16_residual_i16_ex
 
 // W[N][K] row-major -> MFMA-fragment order (include/ivit_hip.h IVIT_W_FRAGS), one 16-byte chunk per thread; rows >= N are zero
 __global__ __launch_bounds__(256) void pack_weight_frags_kernel(const int8_t* W, int64_t ldw, int N, int K, int8_t* dst)
@@ -1341,13 +1470,8 @@ static int gemm_requant_ex(const char* name, const int8_t* A, int64_t lda, const
                            const uint32_t* m, const int32_t* e, int8_t* out, int64_t ldo, int M, int N, int K, int layouts,
                            ivit_stream_t stream)
 {
-    GemmArgs g{};
-    g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.bias = bias; g.m = m; g.e = e;
-    g.out = out; g.ldo = ldo; g.M = M; g.N = N; g.K = K;
-    g.a_blocks = layouts & 1; g.w_blocks = (layouts >> 1) & 1; g.out_blocks = (layouts >> 2) & 1; g.w_frags = (layouts & 16) ? 2 : ((layouts >> 3) & 1);
-    IVIT_REQUIRE((layouts & ~31) == 0 && (layouts & 24) != 24, "%s: unknown layout bits", name);
-    IVIT_REQUIRE(!g.out_blocks || (N % 64 == 0 && ldo == N && ((int64_t)M + 15) * N < 2147483648ll),
-                 "%s: block-layout output needs N %% 64 == 0, ldo == N and a buffer below 2 GiB", name);
+    GemmArgs g = gemm_args(A, lda, W, ldw, bias, m, e, out, ldo, M, N, K);
+    if (const int rc = gemm_layouts(g, layouts, LAYOUTS_RQ, name)) return rc;
     return launch_gemm<EPIW>(g, name, stream);
 }
 
@@ -1372,14 +1496,12 @@ IVIT_EXPORT int ivit_gemm_i8_requant_lut_ex(const int8_t* A, int64_t lda, const 
                                             const uint32_t* m, const int32_t* e, const int8_t* lut, int8_t* out, int64_t ldo,
                                             int M, int N, int K, int layouts, ivit_stream_t stream)
 {
-    GemmArgs g{};
-    g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.bias = bias; g.m = m; g.e = e;
-    g.out = out; g.ldo = ldo; g.M = M; g.N = N; g.K = K; g.lut = lut;
-    g.a_blocks = layouts & 1; g.w_blocks = (layouts >> 1) & 1; g.out_blocks = (layouts >> 2) & 1; g.w_frags = (layouts & 16) ? 2 : ((layouts >> 3) & 1);
-    IVIT_REQUIRE(lut && (layouts & ~31) == 0 && (layouts & 24) != 24 && g.w_frags, "ivit_gemm_i8_requant_lut_ex: needs a map and IVIT_W_FRAGS");
-    IVIT_REQUIRE(!g.out_blocks || (N % 64 == 0 && ldo == N && ((int64_t)M + 15) * N < 2147483648ll),
-                 "ivit_gemm_i8_requant_lut_ex: block-layout output needs N %% 64 == 0, ldo == N and a buffer below 2 GiB");
-    return launch_gemm<EPI_RQ>(g, "ivit_gemm_i8_requant_lut_ex", stream);
+    const char* name = "ivit_gemm_i8_requant_lut_ex";
+    GemmArgs g = gemm_args(A, lda, W, ldw, bias, m, e, out, ldo, M, N, K);
+    g.lut = lut;
+    IVIT_REQUIRE(lut && (layouts & (IVIT_W_FRAGS | IVIT_W_FRAGS16)), "%s: needs a map and IVIT_W_FRAGS", name);
+    if (const int rc = gemm_layouts(g, layouts, LAYOUTS_RQ, name)) return rc;
+    return launch_gemm<EPI_RQ>(g, name, stream);
 }
 
 IVIT_EXPORT int ivit_gemm_i8_requant(const int8_t* A, int64_t lda, const int8_t* W, int64_t ldw, const int32_t* bias,
@@ -1419,15 +1541,13 @@ static int gemm_residual_ex(const char* name, const int8_t* A, int64_t lda, cons
                             uint32_t m_res, int32_t e_res, int8_t* out, int64_t ldo, int M, int N, int K, int layouts,
                             ivit_stream_t stream)
 {
-    GemmArgs g{};
-    g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.bias = bias; g.m = m; g.e = e;
-    g.out = out; g.ldo = ldo; g.res = res; g.ldr = ldr; g.M = M; g.N = N; g.K = K;
+    GemmArgs g = gemm_args(A, lda, W, ldw, bias, m, e, out, ldo, M, N, K);
+    g.res = res; g.ldr = ldr;
     g.M_main = ivit_dyadic_to_double(m_main, e_main);
     g.M_res = ivit_dyadic_to_double(m_res, e_res);
     residual_f32_form(g);
     IVIT_REQUIRE(g.M_main < 1048576.0 && g.M_res < 1048576.0, "%s: residual multiplier >= 2^20 is outside the int8 fast path", name);
-    g.a_blocks = layouts & 1; g.w_blocks = (layouts >> 1) & 1; g.w_frags = (layouts & 16) ? 2 : ((layouts >> 3) & 1);
-    IVIT_REQUIRE((layouts & ~27) == 0 && (layouts & 24) != 24, "%s: unknown layout bits", name);
+    if (const int rc = gemm_layouts(g, layouts, LAYOUTS_IN, name)) return rc;
     return launch_gemm<EPIW>(g, name, stream);
 }
 
@@ -1474,12 +1594,9 @@ IVIT_EXPORT int ivit_gemm_i8_requant_residual_i16_ex(const int8_t* A, int64_t ld
                                                   uint32_t m_res, int32_t e_res, int16_t* out, int64_t ldo, int M, int N,
                                                   int K, int layouts, ivit_stream_t stream)
 {
-    GemmArgs g{};
-    g.a_blocks = layouts & 1; g.w_blocks = (layouts >> 1) & 1; g.w_frags = (layouts & 16) ? 2 : ((layouts >> 3) & 1);
-    IVIT_REQUIRE((layouts & ~27) == 0 && (layouts & 24) != 24, "ivit_gemm_i8_requant_residual_i16_ex: unknown layout bits");
-    g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.bias = bias; g.m = m; g.e = e;
+    GemmArgs g = gemm_args(A, lda, W, ldw, bias, m, e, out, ldo, M, N, K);
+    if (const int rc = gemm_layouts(g, layouts, LAYOUTS_IN, "ivit_gemm_i8_requant_residual_i16_ex")) return rc;
     g.res = reinterpret_cast<const int8_t*>(res); g.ldr = ldr;
-    g.out = out; g.ldo = ldo; g.M = M; g.N = N; g.K = K;
     g.M_main = ivit_dyadic_to_double(m_main, e_main);
     g.M_res = ivit_dyadic_to_double(m_res, e_res);
     IVIT_REQUIRE(g.M_main < 32768.0 && g.M_res < 32768.0, "ivit_gemm_i8_requant_residual_i16: residual multiplier too large");
@@ -1500,12 +1617,9 @@ IVIT_EXPORT int ivit_gemm_i8_requant_qkv_ex(const int8_t* A, int64_t lda, const 
                                          int tokens, int heads, int head_dim, int M, int N, int K,
                                          int layouts, ivit_stream_t stream)
 {
-    GemmArgs g{};
-    g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.bias = bias; g.m = m; g.e = e;
-    g.out = qkv; g.ldo = 0; g.M = M; g.N = N; g.K = K;
+    GemmArgs g = gemm_args(A, lda, W, ldw, bias, m, e, qkv, 0, M, N, K);
     g.tokens = tokens; g.heads = heads; g.head_dim = head_dim;
-    g.a_blocks = layouts & 1; g.w_blocks = (layouts >> 1) & 1; g.w_frags = (layouts & 16) ? 2 : ((layouts >> 3) & 1);
-    IVIT_REQUIRE((layouts & ~27) == 0 && (layouts & 24) != 24, "ivit_gemm_i8_requant_qkv_ex: unknown layout bits");
+    if (const int rc = gemm_layouts(g, layouts, LAYOUTS_IN, "ivit_gemm_i8_requant_qkv_ex")) return rc;
     return launch_gemm<EPI_QKV>(g, "ivit_gemm_i8_requant_qkv_ex", stream);
 }
 
@@ -1523,12 +1637,9 @@ IVIT_EXPORT int ivit_gemm_i8_requant_qkv_planes_ex(const int8_t* A, int64_t lda,
                  plane0, plane0 + nplanes - 1);
     IVIT_REQUIRE(qkv && M > 0 && heads > 0 && head_dim > 0 && (int64_t)3 * M * heads * head_dim < 2147483648ll,
                  "ivit_gemm_i8_requant_qkv_planes_ex: NULL output or a q/k/v buffer beyond 2 GiB");
-    GemmArgs g{};
-    g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.bias = bias; g.m = m; g.e = e;
-    g.out = qkv + (int64_t)plane0 * M * heads * head_dim; g.ldo = 0; g.M = M; g.N = N; g.K = K;
+    GemmArgs g = gemm_args(A, lda, W, ldw, bias, m, e, qkv + (int64_t)plane0 * M * heads * head_dim, 0, M, N, K);
     g.tokens = tokens; g.heads = heads; g.head_dim = head_dim;
-    g.a_blocks = layouts & 1; g.w_blocks = (layouts >> 1) & 1; g.w_frags = (layouts & 16) ? 2 : ((layouts >> 3) & 1);
-    IVIT_REQUIRE((layouts & ~27) == 0 && (layouts & 24) != 24, "ivit_gemm_i8_requant_qkv_planes_ex: unknown layout bits");
+    if (const int rc = gemm_layouts(g, layouts, LAYOUTS_IN, "ivit_gemm_i8_requant_qkv_planes_ex")) return rc;
     return launch_gemm<EPI_QKV>(g, "ivit_gemm_i8_requant_qkv_planes_ex", stream, nplanes);
 }
 
@@ -1544,9 +1655,7 @@ IVIT_EXPORT int ivit_gemm_i8_requant_i16(const int8_t* A, int64_t lda, const int
                                          const uint32_t* m, const int32_t* e, int16_t* out, int64_t ldo, int M, int N, int K,
                                          ivit_stream_t stream)
 {
-    GemmArgs g{};
-    g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.bias = bias; g.m = m; g.e = e;
-    g.out = out; g.ldo = ldo; g.M = M; g.N = N; g.K = K;
+    GemmArgs g = gemm_args(A, lda, W, ldw, bias, m, e, out, ldo, M, N, K);
     return launch_gemm<EPI_RQ16>(g, "ivit_gemm_i8_requant_i16", stream);
 }
 
@@ -1556,12 +1665,11 @@ IVIT_EXPORT int ivit_gemm_i8_requant_i16_residual_i16_ex(const int8_t* A, int64_
                                                          uint32_t m_res, int32_t e_res, int16_t* out, int64_t ldo, int M, int N,
                                                          int K, int layouts, ivit_stream_t stream)
 {
-    GemmArgs g{};
-    g.a_blocks = layouts & 1; g.w_frags = (layouts & 16) ? 2 : ((layouts >> 3) & 1);
-    IVIT_REQUIRE((layouts & ~9) == 0 && (g.w_frags || !g.a_blocks), "ivit_gemm_i8_requant_i16_residual_i16_ex: layouts is 0 or IVIT_W_FRAGS (| IVIT_A_BLOCKS)");
-    g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.bias = bias; g.m = m; g.e = e;
+    GemmArgs g = gemm_args(A, lda, W, ldw, bias, m, e, out, ldo, M, N, K);
+    IVIT_REQUIRE((layouts & ~LAYOUTS_RQ16_RES16) == 0 && ((layouts & IVIT_W_FRAGS) || !(layouts & IVIT_A_BLOCKS)),
+                 "ivit_gemm_i8_requant_i16_residual_i16_ex: layouts is 0 or IVIT_W_FRAGS (| IVIT_A_BLOCKS)");
+    if (const int rc = gemm_layouts(g, layouts, LAYOUTS_RQ16_RES16, "ivit_gemm_i8_requant_i16_residual_i16_ex")) return rc;
     g.res = reinterpret_cast<const int8_t*>(res); g.ldr = ldr;
-    g.out = out; g.ldo = ldo; g.M = M; g.N = N; g.K = K;
     g.M_main = ivit_dyadic_to_double(m_main, e_main);
     g.M_res = ivit_dyadic_to_double(m_res, e_res);
     IVIT_REQUIRE(g.M_main < 32768.0 && g.M_res < 32768.0, "ivit_gemm_i8_requant_i16_residual_i16_ex: residual multiplier too large");
@@ -1573,10 +1681,31 @@ IVIT_EXPORT int ivit_gemm_i8_requant_i16_residual_i16_ex(const int8_t* A, int64_
 IVIT_EXPORT int ivit_gemm_i8_i32(const int8_t* A, int64_t lda, const int8_t* W, int64_t ldw, const int32_t* bias,
                                  int32_t* out, int64_t ldo, int M, int N, int K, ivit_stream_t stream)
 {
-    GemmArgs g{};
-    g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.bias = bias;
-    g.out = out; g.ldo = ldo; g.M = M; g.N = N; g.K = K;
+    GemmArgs g = gemm_args(A, lda, W, ldw, bias, nullptr, nullptr, out, ldo, M, N, K);
     return launch_gemm<EPI_I32>(g, "ivit_gemm_i8_i32", stream);
+}
+
+// The launcher's decision for a dense problem with 16-byte-aligned operands: gemm_check, the entry's layout mask and gemm_plan as a
+// launch runs them, on an argument block whose pointers are never followed.  Host function: no HIP call.
+IVIT_EXPORT int ivit_gemm_plan(int epilogue, int M, int N, int K, int layouts, int32_t* out8)
+{
+    alignas(16) static int8_t operand[16];
+    static const int allowed[] = {LAYOUTS_RQ, LAYOUTS_IN, LAYOUTS_IN, 0, LAYOUTS_IN, 0, LAYOUTS_RQ16_RES16};      // by EPI_* kind
+    const char* name = "ivit_gemm_plan";
+    IVIT_REQUIRE(out8 && epilogue >= EPI_RQ && epilogue <= EPI_RQ16_RES16, "%s: NULL out8 or epilogue %d outside IVIT_GEMM_EPI_*", name, epilogue);
+    const bool qkv = epilogue == EPI_QKV;      // one plane of heads of 16 channels: any N the int8 epilogues take
+    GemmArgs g = gemm_args(operand, K, operand, K, reinterpret_cast<const int32_t*>(operand), reinterpret_cast<const uint32_t*>(operand),
+                           reinterpret_cast<const int32_t*>(operand), operand, qkv ? 0 : N, M, N, K);
+    g.res = operand; g.ldr = N;
+    g.tokens = 1; g.heads = N / 16; g.head_dim = 16;
+    if (const int rc = gemm_layouts(g, layouts, allowed[epilogue], name)) return rc;
+    IVIT_REQUIRE(epilogue != EPI_RQ16_RES16 || g.w_frags || !g.a_blocks, "%s: layouts is 0 or IVIT_W_FRAGS (| IVIT_A_BLOCKS)", name);
+    if (const int rc = gemm_check(epilogue, g, name, 1)) return rc;
+    GemmPlan p;
+    if (const int rc = gemm_plan(epilogue, g, name, p)) return rc;
+    const int32_t v[8] = {p.form, p.grid, p.tiles_m, p.tiles_n, p.split_from, p.nks, p.lds, wr_tiles_fit(N) ? 1 : 0};
+    for (int i = 0; i < 8; ++i) out8[i] = v[i];
+    return IVIT_OK;
 }
 
 #if IVIT_LAB     // include/ivit_hip_debug.h: process-wide test and measurement state, lab library only

@@ -21,6 +21,20 @@ constexpr bool g_force_small = false;
 constexpr int g_debug_flags = 0;
 constexpr int g_debug_flags2 = 0;
 #endif
+// The bits of the two flag words, as include/ivit_hip_debug.h tabulates them; gemm_plan (gemm.hip) is their only reader.
+constexpr int LAB_WR_ABLATION = 31;          // bits 0-4: timing ablation of the 32x32x32 weights-in-registers kernel; 16 = its stamps
+constexpr int LAB_WR_STAMPS = 16;
+constexpr int LAB_NO_STAGGER = 64;           // bit 6
+constexpr int LAB_SPLIT_ALL_SLOTS = 2048;    // bit 11
+constexpr int LAB_ONE_PER_CU = 4096;         // bit 12
+constexpr int LAB_CU_TURNS = 32768;          // bit 15
+constexpr int LAB_DELAY_SHIFT = 16, LAB_DELAY_MASK = 63;      // bits 16-21
+constexpr int LAB_GRID_256 = 1 << 26;        // bit 26
+constexpr int LAB_NO_HALVES = 1 << 27;       // bit 27
+constexpr int LAB2_WR16_STAMPS = 256;        // second word, bit 8
+constexpr int LAB2_WR16_NARROW = 8192;       // bit 13
+constexpr int LAB2_NO_SKINNY = 1 << 20;      // bit 20
+constexpr int LAB2_SKINNY_ANY_K = 1 << 21;   // bit 21
 
 namespace {
 
@@ -841,6 +855,12 @@ IVIT_DEV void epilogue_rq16_res16_small(v16i (&acc)[2][2], const GemmArgs& g, ch
 
 // ---- 256 x 128 LDS-DMA tiles (persistent kernel)
 constexpr int BTOK = 256, BCH = 128, BIG_NT = 256, BIG_STAGES = 3;
+// ---- dispatch thresholds (gemm_plan in gemm.hip; i-vit_amd/gemm_forms.py mirrors them and tests/test_gemm_plan_cpu.py pins the mirror)
+constexpr int BIG_MIN_M = 2048;      // rows from which the tile-looping kernels (persistent, weights-in-registers) run
+constexpr int SK_MIN_M = 8192;       // rows from which the skinny-K form runs
+constexpr int WG_SLOTS = 512;        // two resident workgroups on each of 256 CUs
+constexpr int HALF_TILE_WGS = 256;   // half tiles while each still finds a CU of its own: 2R <= 256
+constexpr int WR_WASTE_DEN = 8;      // 256-channel tiles "fit" N when they pad at most an eighth of their columns (wr_tiles_fit)
 constexpr int BIG_A_BYTES = BTOK * BK;                 // 16 KiB
 constexpr int BIG_STAGE = (BTOK + BCH) * BK;           // 24 KiB
 constexpr int BIG_SMEM = BIG_STAGES * BIG_STAGE;       // 72 KiB  (>= 256 * 132 epilogue tile)

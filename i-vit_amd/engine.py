@@ -26,7 +26,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, gemm_forms
 from .engine_common import (EngineBase, _np, attention, attention_probs, attention_spec, block_copy, frag_copy, intermediate_indices,
                             layernorm, tokens_to_nchw)
 from .prepare import dyadic, dyadic1, f32, pad_head, quant_sym, requant_host
@@ -249,15 +249,11 @@ class IntViTEngine(EngineBase):
             topk=torch.empty(B * TOPK_MAX, dtype=torch.int32, device=self.dev),
         )
 
-    def _w(self, lin, blocks, row0=0):
-        """(weight pointer, layout bit) -- the block-layout copy when the call goes to the persistent kernel.  row0: the weight
-        from that output channel on (a multiple of 64: the same byte offset row0 * K in all three layouts)"""
-        if blocks and self.weight_frags and lin.get("Wf") is not None:
-            W, bit = lin["Wf"], lin["Wf_bit"]
-        elif blocks and lin["Wb"] is not None:
-            W, bit = lin["Wb"], 2
-        else:
-            W, bit = lin["W"], 0
+    def _w(self, lin, epi, M, blocks, row0=0):
+        """(weight pointer, layout bit) for M rows through epilogue `epi` (gemm_forms.weight); blocks = False: row-major whatever
+        the shape (the class rows, the block_operands switch).  row0: the weight from that output channel on (a multiple of 64:
+        the same byte offset row0 * K in all three layouts)"""
+        W, bit = gemm_forms.weight(lin, epi, M, frags=blocks and self.weight_frags, blocks=blocks)
         assert row0 % 64 == 0
         return _lib.ptr(W.view(-1)[row0 * lin["K"]:] if row0 else W), bit
 
@@ -278,15 +274,14 @@ class IntViTEngine(EngineBase):
 
     def _gemm(self, A, lda, lin, out, ldo, M, st, a_blocks=False, blocks=False, out_blocks=False, bits=8):
         """GEMM + its QuantAct; bits = 4: a stream site of the 4-bit engine (the patch embedding)"""
-        w, lay = self._w(lin, blocks)
+        w, lay = self._w(lin, gemm_forms.RQ, M, blocks)
+        lay |= (gemm_forms.A_BLOCKS if a_blocks else 0) | (gemm_forms.OUT_BLOCKS if out_blocks else 0)
         if bits == 8:
             _lib.call("ivit_gemm_i8_requant_ex", _lib.ptr(A), lda, w, lin["K"], _lib.ptr(lin["b"]),
-                      _lib.ptr(lin["m"]), _lib.ptr(lin["e"]), _lib.ptr(out), ldo, M, lin["N"], lin["K"],
-                      lay | int(a_blocks) | (4 if out_blocks else 0), st)
+                      _lib.ptr(lin["m"]), _lib.ptr(lin["e"]), _lib.ptr(out), ldo, M, lin["N"], lin["K"], lay, st)
         else:
             _lib.call("ivit_gemm_i8_requant_bits_ex", _lib.ptr(A), lda, w, lin["K"], _lib.ptr(lin["b"]),
-                      _lib.ptr(lin["m"]), _lib.ptr(lin["e"]), _lib.ptr(out), ldo, M, lin["N"], lin["K"],
-                      lay | int(a_blocks) | (4 if out_blocks else 0), bits, st)
+                      _lib.ptr(lin["m"]), _lib.ptr(lin["e"]), _lib.ptr(out), ldo, M, lin["N"], lin["K"], lay, bits, st)
 
     def _gemm_res(self, A, lda, lin, res, me4, out, M, st, blocks=False, a_blocks=False, ldr=None):
         """projection / fc2 + its QuantAct + the block's residual QuantAct (in place when out is res).  On the 16-bit stream the
@@ -305,22 +300,21 @@ class IntViTEngine(EngineBase):
         if probe is not None:
             # bench.py's separate instrumented pass (never inside its timed region): HIP events around the dominant kernel
             probe.begin("gemm_resid", st)
+        w, lay = self._w(lin, gemm_forms.RESID if self.stream_bits != 16 else gemm_forms.RQ16_RES16, M, blocks)
+        lay |= gemm_forms.A_BLOCKS if a_blocks else 0
         if self.stream_bits == 8:
-            w, lay = self._w(lin, blocks)
             _lib.call("ivit_gemm_i8_requant_residual_ex", _lib.ptr(A), lda, w, lin["K"],
                       _lib.ptr(lin["b"]), _lib.ptr(lin["m"]), _lib.ptr(lin["e"]), _lib.ptr(res), ldr,
-                      r[0], r[1], r[2], r[3], _lib.ptr(out), C, M, lin["N"], lin["K"], lay | int(a_blocks), st)
+                      r[0], r[1], r[2], r[3], _lib.ptr(out), C, M, lin["N"], lin["K"], lay, st)
         elif self.stream_bits == 4:      # attn.qact3 / mlp.qact2 and the block's residual QuantAct, both at 4 bits
-            w, lay = self._w(lin, blocks)
             _lib.call("ivit_gemm_i8_requant_residual_bits_ex", _lib.ptr(A), lda, w, lin["K"],
                       _lib.ptr(lin["b"]), _lib.ptr(lin["m"]), _lib.ptr(lin["e"]), _lib.ptr(res), ldr,
-                      r[0], r[1], r[2], r[3], _lib.ptr(out), C, M, lin["N"], lin["K"], lay | int(a_blocks), 4, 4, st)
+                      r[0], r[1], r[2], r[3], _lib.ptr(out), C, M, lin["N"], lin["K"], lay, 4, 4, st)
         else:
             # the weights-in-registers form where it applies, else the 128 x 128-tile kernel (any shape; no block layouts)
-            frags = blocks and self.weight_frags and lin["Wf"] is not None
-            _lib.call("ivit_gemm_i8_requant_i16_residual_i16_ex", _lib.ptr(A), lda, _lib.ptr(lin["Wf"] if frags else lin["W"]),
+            _lib.call("ivit_gemm_i8_requant_i16_residual_i16_ex", _lib.ptr(A), lda, w,
                       lin["K"], _lib.ptr(lin["b"]), _lib.ptr(lin["m"]), _lib.ptr(lin["e"]), _lib.ptr(res), C, r[0], r[1], r[2], r[3],
-                      _lib.ptr(out), C, M, C, lin["K"], lin["Wf_bit"] if frags else 0, st)
+                      _lib.ptr(out), C, M, C, lin["K"], lay, st)
         if probe is not None:
             probe.end("gemm_resid", st, (M, lin["N"], lin["K"]))
 
@@ -369,9 +363,9 @@ class IntViTEngine(EngineBase):
         C, H, hd, T = self.C, self.H, self.hd, self.T
         M, ws, q = B * T, self.ws, blk["qkv"]
         layernorm(blk["ln1"], x, C, M, C, ws["h"], C, st, blocks=a_ln)
-        kvw, kvlay = self._w(q, blk_l, row0=C)
+        kvw, kvlay = self._w(q, gemm_forms.QKV, M, blk_l, row0=C)
         _lib.call("ivit_gemm_i8_requant_qkv_planes_ex", _lib.ptr(ws["h"]), C, kvw, q["K"], _lib.ptr(q["b"][C:]),
-                  _lib.ptr(q["m"][C:]), _lib.ptr(q["e"][C:]), _lib.ptr(ws["qkv"]), T, H, hd, 1, 2, M, 2 * C, C, kvlay | int(a_ln), st)
+                  _lib.ptr(q["m"][C:]), _lib.ptr(q["e"][C:]), _lib.ptr(ws["qkv"]), T, H, hd, 1, 2, M, 2 * C, C, kvlay | (gemm_forms.A_BLOCKS if a_ln else 0), st)
         layernorm(blk["ln1"], x, T * C, B, C, ws["c_h"], C, st, blocks=False)
         self._gemm(ws["c_h"], C, blk["q"], ws["c_q"], C, B, st)
         a = blk["attn"]
@@ -476,8 +470,8 @@ class IntViTEngine(EngineBase):
         ws = self.ws
         st = self._stream()
 
-        # GEMM operands in the block layout whenever the calls go to the persistent kernel (M >= 2048; N >= 128 always)
-        blk_l = bool(self.block_operands) and M >= 2048 and C % 64 == 0    # weights (always) and, per producer, activations
+        # GEMM operands in the block layout whenever the calls go to the tile-looping kernels (C is the narrowest GEMM's N and K)
+        blk_l = bool(self.block_operands) and gemm_forms.block_operands_apply(M, C, C)    # weights (always) and, per producer, activations
         a_ln, a_at, a_ge = (blk_l and not wide and self.block_a[k] for k in ("ln", "attn", "gelu"))
 
         def tap(name, t, shape, blocks=False):
@@ -497,7 +491,7 @@ class IntViTEngine(EngineBase):
             x, x2 = ws["x16"], (ws["x16"] if self.fuse_res16 else ws["y16"])
         else:
             self._gemm(ws["a0"], 3 * self.P * self.P, self.patch, ws["pe"], C, B * self.NP, st,
-                       blocks=bool(self.block_operands) and B * self.NP >= 2048 and C >= 128, bits=self.stream_bits)
+                       blocks=bool(self.block_operands), bits=self.stream_bits)
             tap("patch_embed.qact", ws["pe"], (B, self.NP, C))
             x, x2 = ws["x"], ws["x2"]
         if self.stream_bits == 4:
@@ -516,9 +510,9 @@ class IntViTEngine(EngineBase):
             layernorm(blk["ln1"], x, C, M, C, ws["h"], C, st, blocks=a_ln)
             tap(p + "qact1", ws["h"], (B, T, C), a_ln)
             q = blk["qkv"]
-            qw, qlay = self._w(q, blk_l)
+            qw, qlay = self._w(q, gemm_forms.QKV, M, blk_l)
             _lib.call("ivit_gemm_i8_requant_qkv_ex", _lib.ptr(ws["h"]), C, qw, q["K"], _lib.ptr(q["b"]),
-                      _lib.ptr(q["m"]), _lib.ptr(q["e"]), _lib.ptr(ws["qkv"]), T, H, hd, M, 3 * C, C, qlay | int(a_ln), st)
+                      _lib.ptr(q["m"]), _lib.ptr(q["e"]), _lib.ptr(ws["qkv"]), T, H, hd, M, 3 * C, C, qlay | (gemm_forms.A_BLOCKS if a_ln else 0), st)
             tap(p + "attn.qkv_headmajor", ws["qkv"], (3, B, H, T, hd))
             if maps is not None and i in maps:
                 attention_probs(blk["attn"], self.family, ws["qkv"], maps[i], B, H, T, hd, maps[i].shape[2], st)
@@ -532,14 +526,14 @@ class IntViTEngine(EngineBase):
             # mlp.fc1 writes the block layout and GELU works IN PLACE on it: the 155 MB intermediate exists once, so the pair
             # (GELU output, fc2 operand) stays inside the 256 MB Infinity Cache (separate buffers: 310 MB; -0.18 ms / forward)
             f1 = blk["fc1"]
-            if (self.family == "ibert" and self.fuse_ibert_gelu and taps is None and blk_l and self.weight_frags
-                    and f1["Wf"] is not None):
+            f1w, f1lay = self._w(f1, gemm_forms.RQ, M, blk_l) if self.family == "ibert" and self.fuse_ibert_gelu and taps is None else (None, 0)
+            if f1lay & gemm_forms.FRAGS:
                 # I-BERT GELU + mlp.qact1 is a map of the requantised byte alone (no row maximum): applied in the fc1 epilogue,
                 # the GELU kernel and its pass over the 4C-wide intermediate disappear
                 g_buf = ws["f1"]
-                _lib.call("ivit_gemm_i8_requant_lut_ex", _lib.ptr(ws["h"]), C, _lib.ptr(f1["Wf"]), f1["K"], _lib.ptr(f1["b"]),
+                _lib.call("ivit_gemm_i8_requant_lut_ex", _lib.ptr(ws["h"]), C, f1w, f1["K"], _lib.ptr(f1["b"]),
                           _lib.ptr(f1["m"]), _lib.ptr(f1["e"]), _lib.ptr(blk["gelu_lut"]), _lib.ptr(g_buf), 4 * C, M, f1["N"], f1["K"],
-                          f1["Wf_bit"] | int(a_ln) | (4 if a_ge else 0), st)
+                          f1lay | (gemm_forms.A_BLOCKS if a_ln else 0) | (gemm_forms.OUT_BLOCKS if a_ge else 0), st)
             else:
                 self._gemm(ws["h"], C, f1, ws["f1"], 4 * C, M, st, a_blocks=a_ln, blocks=blk_l, out_blocks=a_ge)
                 tap(p + "mlp.qact_gelu", ws["f1"], (B, T, 4 * C), a_ge)

@@ -11,7 +11,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, gemm_forms
 from .graph import GraphReplay
 from .prepare import (IMAGENET_MEAN, IMAGENET_STD, dyadic1, f32, input_lut_u8, markstein_division_ok, phi_is_identity, phi_tables,
                       shiftexp2d, shiftexp_band)
@@ -29,7 +29,7 @@ def block_copy(W: torch.Tensor, st):
     """Block-layout copy of a row-major int8 weight [N, K] (include/ivit_hip.h IVIT_LAYOUT_BLOCKS): the persistent GEMM then
     reads 1 KB contiguous per LDS-DMA instruction instead of 16 half cache lines.  None where block operands do not apply."""
     N, K = W.shape
-    if K % 64 or N % 16 or N < 128:
+    if not gemm_forms.blocks_shape(N, K):
         return None
     Wb = torch.empty_like(W)
     _lib.call("ivit_tile_operand_i8", _lib.ptr(W), K, N, K, _lib.ptr(Wb), st)
@@ -41,15 +41,14 @@ def frag_copy(W: torch.Tensor, st, order16: bool = True, narrow: bool = True):
     order16: the v_mfma_i32_16x16x64_i8 order (IVIT_W_FRAGS16; the chip holds a higher clock on that shape), else the
     32x32x32 one (IVIT_W_FRAGS).  narrow: the consuming epilogue can use 128-channel work items.
 
-    The kernel needs K % 192 == 0, N % 64 == 0 and N >= 128.  Its 128-channel work items exist only for the 16x16x64 order
-    with an int8 epilogue; every other consumer (the 32x32x32 order, a 16-bit-residual epilogue) works in 256-channel tiles,
-    which are used only where they waste at most an eighth of their columns."""
+    Where the kernel takes the weight at all (gemm_forms.frags_shape) and its work items fit N (gemm_forms.frag_items_ok)."""
     N, K = W.shape
-    if K % 192 or N % 64 or N < 128 or not ((narrow and order16) or (N + 255) // 256 * 256 * 8 <= N * 9):
+    bit = gemm_forms.W_FRAGS16 if order16 else gemm_forms.W_FRAGS
+    if not (gemm_forms.frags_shape(N, K) and gemm_forms.frag_items_ok(bit, narrow, N)):
         return None, None
     Wf = torch.empty((N + 63) // 64 * 64 * K, dtype=torch.int8, device=W.device)
     _lib.call("ivit_pack_weight_frags16_i8" if order16 else "ivit_pack_weight_frags_i8", _lib.ptr(W), K, N, K, _lib.ptr(Wf), st)
-    return Wf, 16 if order16 else 8
+    return Wf, bit
 
 
 # ----------------------------------------------------------------------------------------------------------- LayerNorm

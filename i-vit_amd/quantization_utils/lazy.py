@@ -47,7 +47,7 @@ import warnings
 import numpy as np
 import torch
 
-from .. import _lib
+from .. import _lib, gemm_forms
 from ..engine_common import attention, attention_entry, attention_spec, frag_copy, gelu_lut, layernorm, ln_spec, long_multipliers_ok
 from ..prepare import LayerNormParams, LinearParams, dyadic, dyadic1, f32, quant_sym, sym_scale
 
@@ -778,7 +778,7 @@ def linear_consts(lin, s_in, device):
             s_acc = bp["s_acc"].cpu().numpy()      # N floats: QS and dyadic (_gemm_me) want them on the host
             d = dict(N=N, K=K, Kin=Kin, W=wp["W"][:N], b=None if bp["b"] is None else bp["b"][:N], s_acc=QS.make(s_acc, device),
                      s_acc_host=s_acc)
-            d["Wf"], _ = frag_copy(d["W"], _st())
+            d["Wf"], d["Wf_bit"] = frag_copy(d["W"], _st())
             return d
         lp = LinearParams(lin.weight.detach().cpu().numpy(), None if lin.bias is None else lin.bias.detach().cpu().numpy(), s_in)
         N, Kin = lp.W8.shape
@@ -790,7 +790,7 @@ def linear_consts(lin, s_in, device):
         lin._publish(lp, device)           # the buffers the reference rewrites on every call
         d = dict(N=N, K=K, Kin=Kin, W=_dev(W8, device), b=None if lp.b32 is None else _dev(lp.b32, device),
                  s_acc=QS.make(lp.s_acc, device), s_acc_host=lp.s_acc)
-        d["Wf"], _ = frag_copy(d["W"], _st())       # every consumer here has an int8 epilogue
+        d["Wf"], d["Wf_bit"] = frag_copy(d["W"], _st())       # 128-channel work items for the int8 epilogues (gemm_forms.weight)
         return d
     return _cache(lin, ("lin", lin.weight._version, None if lin.bias is None else lin.bias._version, _key(s_in), str(device)), build)
 
@@ -811,6 +811,12 @@ def _gemm_me(lin, s_in, s_out, device, need_e31=True):
                         str(device)), build)
 
 
+def _frag_rows(c, epi, M):
+    """M rows of this linear through epilogue `epi` run the weights-in-registers GEMM: the launch can be deferred (Requant,
+    Requant16) so that a residual QuantAct behind it joins the kernel"""
+    return bool(gemm_forms.weight(c, epi, M)[1] & gemm_forms.FRAGS)
+
+
 def _operand(a8, c):
     """the A operand of a GEMM whose K was padded to the kernels' 64-byte slabs: zero columns to match"""
     return a8 if c["K"] == c["Kin"] else torch.nn.functional.pad(a8, (0, c["K"] - c["Kin"]))
@@ -829,13 +835,13 @@ def gemm_requant(lin, a8, s_in, s_out, device, bits=8):
     a8 = _operand(a8, c)
     M = a8.shape[0]
     out = torch.empty(M, N, dtype=torch.int8, device=device)
-    frags = c["Wf"] is not None and M >= 2048
+    W, lay = gemm_forms.weight(c, gemm_forms.RQ, M)
     if bits == 8:
-        _lib.call("ivit_gemm_i8_requant_ex", _lib.ptr(a8), K, _lib.ptr(c["Wf"] if frags else c["W"]), K, _lib.ptr(c["b"]),
-                  _lib.ptr(me[0]), _lib.ptr(me[1]), _lib.ptr(out), N, M, N, K, 16 if frags else 0, _st())
+        _lib.call("ivit_gemm_i8_requant_ex", _lib.ptr(a8), K, _lib.ptr(W), K, _lib.ptr(c["b"]),
+                  _lib.ptr(me[0]), _lib.ptr(me[1]), _lib.ptr(out), N, M, N, K, lay, _st())
     else:
-        _lib.call("ivit_gemm_i8_requant_bits_ex", _lib.ptr(a8), K, _lib.ptr(c["Wf"] if frags else c["W"]), K, _lib.ptr(c["b"]),
-                  _lib.ptr(me[0]), _lib.ptr(me[1]), _lib.ptr(out), N, M, N, K, 16 if frags else 0, bits, _st())
+        _lib.call("ivit_gemm_i8_requant_bits_ex", _lib.ptr(a8), K, _lib.ptr(W), K, _lib.ptr(c["b"]),
+                  _lib.ptr(me[0]), _lib.ptr(me[1]), _lib.ptr(out), N, M, N, K, lay, bits, _st())
     return out
 
 
@@ -896,8 +902,8 @@ def resolve(qact, x, pre_sf, identity, identity_sf, s_out, s_out_qs):
                 else:
                     a8 = q8_contig(node.inputs[0])
                     a8 = None if a8 is None else a8.reshape(-1, a8.shape[-1])
-            if (a8 is not None and node.kind == "linear" and not x.views and a8.shape[0] >= 2048
-                    and linear_consts(node.mod, s_a, device)["Wf"] is not None):
+            if (a8 is not None and node.kind == "linear" and not x.views
+                    and _frag_rows(linear_consts(node.mod, s_a, device), gemm_forms.RQ, a8.shape[0])):
                 # not launched yet: if the next QuantAct adds a residual (Block.qact2 / qact4, vit_quant.py:147,153) the GEMM,
                 # this requantisation and that one are ONE kernel; any other consumer launches the GEMM as it is
                 rq = Requant(node.mod, a8, s_a, s_out, node.shape, s_out_qs, bits)
@@ -972,14 +978,15 @@ def gemm_requant_i16(lin, a8, s_in, s_out, device):
     return o
 
 
-def _frags32(lin, s_in, device):
-    """the 32x32x32 fragment copy of a linear's weight: the order the 16-bit-stream epilogue of
+def _frags32(lin, s_in, device, M):
+    """linear_consts with "Wf32", the 32x32x32 fragment copy of the weight: the order the 16-bit-stream epilogue of
     ivit_gemm_i8_requant_i16_residual_i16_ex exists for (engine.py does the same for attn.proj / mlp.fc2), in 256-channel tiles
-    where they fit (engine_common.frag_copy); None otherwise.  Built the first time a 16-bit QuantAct behind the linear asks"""
+    where they fit (engine_common.frag_copy); None otherwise.  Built the first time a 16-bit QuantAct behind the linear asks with
+    as many rows M as the weights-in-registers GEMM takes"""
     c = linear_consts(lin, s_in, device)
-    if "Wf32" not in c:
-        c["Wf32"] = frag_copy(c["W"], _st(), order16=False, narrow=False) if c["K"] == c["Kin"] else (None, None)
-    return c["Wf32"]
+    if "Wf32" not in c and gemm_forms.frags_apply(gemm_forms.RQ16_RES16, M, c["N"], c["K"], gemm_forms.W_FRAGS):
+        c["Wf32"] = frag_copy(c["W"], _st(), order16=False, narrow=False)[0] if c["K"] == c["Kin"] else None
+    return c
 
 
 def resolve16(qact, x, pre_sf, identity, identity_sf, s_out, s_out_qs):
@@ -987,7 +994,7 @@ def resolve16(qact, x, pre_sf, identity, identity_sf, s_out, s_out_qs):
     (vit_quant.py:180-187): one launch -> int16 QT.
       int8 payload                                  -> ivit_requant_i8_i16               (Swin's qact1, :546)
       pending linear / patch convolution            -> ivit_gemm_i8_requant_i16          (attn.proj -> attn.qact4, :166; ViT's
-                                                       patch_embed.qact, attn.qact3, mlp.qact2), from 2048 rows with the fragment
+                                                       patch_embed.qact, attn.qact3, mlp.qact2), where the rows reach the fragment
                                                        weight copy deferred (Requant16) for the residual QuantAct behind it
       cat(cls, int16 patches) + position identity   -> ivit_embed_assemble_i16           (ViT's qact1, vit_quant.py:293-297)
       int16 / int8 payload + int16 / int8 identity  -> ivit_residual_requant_i16         (the residual qact2, :291)
@@ -1049,7 +1056,7 @@ def resolve16(qact, x, pre_sf, identity, identity_sf, s_out, s_out_qs):
             a8 = None if a8 is None else a8.reshape(-1, a8.shape[-1])
         if a8 is None:
             return None
-        if node.kind == "linear" and not x.views and a8.shape[0] >= 2048 and _frags32(node.mod, s_a, device)[0] is not None:
+        if node.kind == "linear" and not x.views and _frag_rows(_frags32(node.mod, s_a, device, a8.shape[0]), gemm_forms.RQ16_RES16, a8.shape[0]):
             # not launched yet: if the next QuantAct adds the 16-bit residual (Block.qact2 / qact4 with attention_out_bw = mlp_out_bw =
             # norm2_in_bw = att_block_out_bw = 16, vit_quant.py:147,153) the GEMM, this requantisation and that one are ONE kernel;
             # any other consumer launches the GEMM as it is
@@ -1124,13 +1131,13 @@ class Requant16(Node):
     def with_residual(self, i16, s_in, mes, device):
         """out = clamp16(RNE(clamp16(RNE(acc * M)) * m1 / 2^e1) + RNE(identity * m2 / 2^e2)): ivit_gemm_i8_requant_i16_residual_i16_ex
         with the fragment weight copy; int16 out, or None"""
-        c = linear_consts(self.lin, self.s_a, device)
-        Wf, bit = _frags32(self.lin, self.s_a, device)
+        M = self.a8.shape[0]
+        c = _frags32(self.lin, self.s_a, device, M)
         N, K = c["N"], c["K"]
-        if s_in[0] != f32(self.s_out) or tuple(i16.shape) != tuple(self.shape) or Wf is None:
+        Wf, bit = gemm_forms.weight(c, gemm_forms.RQ16_RES16, M)
+        if s_in[0] != f32(self.s_out) or tuple(i16.shape) != tuple(self.shape) or not bit & gemm_forms.FRAGS:
             return None
         me = _gemm_me(self.lin, self.s_a, self.s_out, device, need_e31=False)
-        M = self.a8.shape[0]
         out = torch.empty(M, N, dtype=torch.int16, device=device)
         _lib.call("ivit_gemm_i8_requant_i16_residual_i16_ex", _lib.ptr(self.a8), K, _lib.ptr(Wf), K, _lib.ptr(c["b"]), _lib.ptr(me[0]),
                   _lib.ptr(me[1]), _lib.ptr(i16), N, mes[0], mes[1], mes[2], mes[3], _lib.ptr(out), N, M, N, K, bit, _st())
@@ -1170,12 +1177,12 @@ class Requant(Node):
         device = self.a8.device
         c = linear_consts(self.lin, self.s_a, device)
         me = _gemm_me(self.lin, self.s_a, self.s_out, device)
-        use_frags = c["Wf"] is not None and (frags or B * N >= 2048)
-        if (frags and c["Wf"] is None) or c["Kin"] != C:
+        W, lay = gemm_forms.weight(c, gemm_forms.QKV, B * N)
+        if (frags and not lay & gemm_forms.FRAGS) or c["Kin"] != C:
             return None
         hm = torch.empty(3, B, H, N, hd, dtype=torch.int8, device=device)
-        _lib.call("ivit_gemm_i8_requant_qkv_ex", _lib.ptr(_operand(self.a8, c)), c["K"], _lib.ptr(c["Wf"] if use_frags else c["W"]), c["K"],
-                  _lib.ptr(c["b"]), _lib.ptr(me[0]), _lib.ptr(me[1]), _lib.ptr(hm), N, H, hd, B * N, C3, c["K"], 16 if use_frags else 0, _st())
+        _lib.call("ivit_gemm_i8_requant_qkv_ex", _lib.ptr(_operand(self.a8, c)), c["K"], _lib.ptr(W), c["K"],
+                  _lib.ptr(c["b"]), _lib.ptr(me[0]), _lib.ptr(me[1]), _lib.ptr(hm), N, H, hd, B * N, C3, c["K"], lay, _st())
         STATS["fused"] += 1
         return hm
 
@@ -1187,19 +1194,19 @@ class Requant(Node):
         the two QuantActs at 4 bits ivit_gemm_i8_requant_residual_bits_ex"""
         i8 = q8_contig(identity)
         c = linear_consts(self.lin, self.s_a, device)
-        N, K = c["N"], c["K"]
-        if (i8 is None or s_id is None or s_id.size != 1 or s_in.size != 1 or s_in[0] != f32(self.s_out) or c["Wf"] is None
+        N, K, M = c["N"], c["K"], self.a8.shape[0]
+        Wf, lay = gemm_forms.weight(c, gemm_forms.RESID, M)
+        if (i8 is None or s_id is None or s_id.size != 1 or s_in.size != 1 or s_in[0] != f32(self.s_out) or not lay & gemm_forms.FRAGS
                 or tuple(i8.shape) != tuple(self.shape)):
             return None
         me = _gemm_me(self.lin, self.s_a, self.s_out, device)
-        M = self.a8.shape[0]
         out = torch.empty(M, N, dtype=torch.int8, device=device)
         if self.bits == 8 and bits_out == 8:
-            _lib.call("ivit_gemm_i8_requant_residual_ex", _lib.ptr(self.a8), K, _lib.ptr(c["Wf"]), K, _lib.ptr(c["b"]), _lib.ptr(me[0]),
-                      _lib.ptr(me[1]), _lib.ptr(i8), N, *dyadic1(s_in, s_out2), *dyadic1(s_id, s_out2), _lib.ptr(out), N, M, N, K, 16, _st())
+            _lib.call("ivit_gemm_i8_requant_residual_ex", _lib.ptr(self.a8), K, _lib.ptr(Wf), K, _lib.ptr(c["b"]), _lib.ptr(me[0]),
+                      _lib.ptr(me[1]), _lib.ptr(i8), N, *dyadic1(s_in, s_out2), *dyadic1(s_id, s_out2), _lib.ptr(out), N, M, N, K, lay, _st())
         else:
-            _lib.call("ivit_gemm_i8_requant_residual_bits_ex", _lib.ptr(self.a8), K, _lib.ptr(c["Wf"]), K, _lib.ptr(c["b"]), _lib.ptr(me[0]),
-                      _lib.ptr(me[1]), _lib.ptr(i8), N, *dyadic1(s_in, s_out2), *dyadic1(s_id, s_out2), _lib.ptr(out), N, M, N, K, 16,
+            _lib.call("ivit_gemm_i8_requant_residual_bits_ex", _lib.ptr(self.a8), K, _lib.ptr(Wf), K, _lib.ptr(c["b"]), _lib.ptr(me[0]),
+                      _lib.ptr(me[1]), _lib.ptr(i8), N, *dyadic1(s_in, s_out2), *dyadic1(s_id, s_out2), _lib.ptr(out), N, M, N, K, lay,
                       self.bits, bits_out, _st())
         return out.view(*self.shape)
 
@@ -1212,12 +1219,12 @@ class Requant(Node):
         me = _gemm_me(self.lin, self.s_a, self.s_out, device)
         a8 = _operand(self.a8, c)
         M = a8.shape[0]
-        # the fragment copy with a 16-bit-residual epilogue works in 256-channel tiles: where they fit (engine_common.frag_copy)
-        frags = c["Wf"] is not None and M >= 2048 and (N + 255) // 256 * 256 * 8 <= N * 9
+        # the fragment copy with a 16-bit-residual epilogue works in 256-channel tiles: where they fit (gemm_forms.frag_items_ok)
+        W, lay = gemm_forms.weight(c, gemm_forms.RESID16, M)
         out = torch.empty(M, N, dtype=torch.int16, device=device)
-        _lib.call("ivit_gemm_i8_requant_residual_i16_ex", _lib.ptr(a8), K, _lib.ptr(c["Wf"] if frags else c["W"]), K, _lib.ptr(c["b"]),
+        _lib.call("ivit_gemm_i8_requant_residual_i16_ex", _lib.ptr(a8), K, _lib.ptr(W), K, _lib.ptr(c["b"]),
                   _lib.ptr(me[0]), _lib.ptr(me[1]), _lib.ptr(i16), N, mes[0], mes[1], mes[2], mes[3], _lib.ptr(out), N, M, N, K,
-                  16 if frags else 0, _st())
+                  lay, _st())
         return out.view(*self.shape)
 
 

@@ -27,7 +27,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, gemm_forms
 from .engine_common import EngineBase, _np, block_copy, frag_copy, intermediate_indices, layernorm, tokens_to_nchw
 from .prepare import (LayerNormParams, LinearParams, dyadic, dyadic1, f32, ibert_saturated_exp, ibert_window_mask_ok, pad_head,
                       phi_is_identity, phi_table, quant_sym, requant_host, shiftexp_band, sym_scale, window_shiftexp_band)
@@ -522,18 +522,14 @@ class IntSwinEngine(EngineBase):
             ws.update(ws["_own"])
 
     @staticmethod
-    def _w(lin, M):
-        """(weight pointer, layouts) -- the block-layout copy when the call goes to the persistent kernel"""
-        if lin.get("Wf") is not None and M >= 2048:
-            return _lib.ptr(lin["Wf"]), lin["Wf_bit"]
-        if lin["K"] <= 128 and lin["N"] <= 320 and M >= 8192:
-            return _lib.ptr(lin["W"]), 0          # row-major operands: the skinny-K form (csrc/gemm.hip, round 4) keeps the whole W in LDS
-        if lin["Wb"] is not None and M >= 2048:
-            return _lib.ptr(lin["Wb"]), 2
-        return _lib.ptr(lin["W"]), 0
+    def _w(lin, epi, M):
+        """(weight pointer, layouts) for M rows through epilogue `epi`: the copy that matches the kernel the launcher picks
+        (gemm_forms.weight -- row-major for the skinny-K form of stage 0, which keeps the whole W in LDS)"""
+        W, lay = gemm_forms.weight(lin, epi, M)
+        return _lib.ptr(W), lay
 
     def _gemm(self, A, lda, lin, out, ldo, M, st):
-        w, lay = self._w(lin, M)
+        w, lay = self._w(lin, gemm_forms.RQ, M)
         _lib.call("ivit_gemm_i8_requant_ex", _lib.ptr(A), lda, w, lin["K"], _lib.ptr(lin["b"]),
                   _lib.ptr(lin["m"]), _lib.ptr(lin["e"]), _lib.ptr(out), ldo, M, lin["N"], lin["K"], lay, st)
 
@@ -676,7 +672,7 @@ class IntSwinEngine(EngineBase):
                 layernorm(blk["ln1"], x, C, M, C, ws["h"], ld, st, H=H, W=W, ws=win, shift=shift, outer=outer)
                 tap(p + "qact1", ws["h"], M, C, ld, perm)
                 q = blk["qkv"]
-                qw, qlay = self._w(q, M)
+                qw, qlay = self._w(q, gemm_forms.QKV, M)
                 _lib.call("ivit_gemm_i8_requant_qkv_ex", _lib.ptr(ws["h"]), ld, qw, q["K"], _lib.ptr(q["b"]),
                           _lib.ptr(q["m"]), _lib.ptr(q["e"]), _lib.ptr(ws["qkv"]), N, nH, HEAD_DIM, M, 3 * C, q["K"], qlay, st)
                 if taps is not None:   # reference layout [B_, N, 3C] (swin_quant.py:131-133)
@@ -694,7 +690,7 @@ class IntSwinEngine(EngineBase):
                 pj = blk["proj"]
                 r = blk["res1"]
                 if fuse_proj:
-                    w_, lay = (_lib.ptr(pj["Wf"]), pj["Wf_bit"]) if (M >= 2048 and pj.get("Wf") is not None) else (_lib.ptr(pj["W"]), 0)
+                    w_, lay = self._w(pj, gemm_forms.RQ16_RES16, M)
                     _lib.call("ivit_gemm_i8_requant_i16_residual_i16_ex", _lib.ptr(ws["ao"]), ld, w_, pj["K"], _lib.ptr(pj["b"]),
                               _lib.ptr(pj["m"]), _lib.ptr(pj["e"]), _lib.ptr(x), C, r[0], r[1], r[2], r[3], _lib.ptr(x2), C, M, C,
                               pj["K"], lay, st)
@@ -714,12 +710,13 @@ class IntSwinEngine(EngineBase):
                 layernorm(blk["ln2"], x2, C, M, C, ws["h"], ld, st, outer=outer)
                 tap(p + "qact3", ws["h"], M, C, ld)
                 f1 = blk["fc1"]
-                if self.family == "ibert" and taps is None and f1.get("Wf") is not None and M >= 2048:
+                f1w, f1lay = self._w(f1, gemm_forms.RQ, M) if self.family == "ibert" and taps is None else (None, 0)
+                if f1lay & gemm_forms.FRAGS:
                     # I-BERT GELU + mlp.qact1 is a map of the requantised byte alone (no row maximum): applied in the fc1 epilogue
                     # of the weights-in-registers GEMM, the GELU kernel and its pass over the 4C-wide intermediate disappear
-                    _lib.call("ivit_gemm_i8_requant_lut_ex", _lib.ptr(ws["h"]), ld, _lib.ptr(f1["Wf"]), f1["K"], _lib.ptr(f1["b"]),
+                    _lib.call("ivit_gemm_i8_requant_lut_ex", _lib.ptr(ws["h"]), ld, f1w, f1["K"], _lib.ptr(f1["b"]),
                               _lib.ptr(f1["m"]), _lib.ptr(f1["e"]), _lib.ptr(blk["gelu_lut"]), _lib.ptr(ws["g"]), 4 * C, M, f1["N"],
-                              f1["K"], f1["Wf_bit"], st)
+                              f1["K"], f1lay, st)
                 else:
                     self._gemm(ws["h"], ld, f1, ws["f1"], 4 * C, M, st)
                     tap(p + "mlp.qact_gelu", ws["f1"], M, 4 * C)
@@ -732,7 +729,7 @@ class IntSwinEngine(EngineBase):
                     self._gemm(ws["g"], 4 * C, f2, ws["f2"], C, M, st)
                     tap(p + "mlp.qact2", ws["f2"], M, C)
                 # mlp.fc2 + mlp.qact2 + the 16-bit residual QuantAct qact4 in one kernel (swin_quant.py:297-299)
-                f2w, f2lay = self._w(f2, M)
+                f2w, f2lay = self._w(f2, gemm_forms.RESID16, M)
                 _lib.call("ivit_gemm_i8_requant_residual_i16_ex", _lib.ptr(ws["g"]), 4 * C, f2w, f2["K"],
                           _lib.ptr(f2["b"]), _lib.ptr(f2["m"]), _lib.ptr(f2["e"]), _lib.ptr(x2), C, r[0], r[1], r[2], r[3],
                           _lib.ptr(x), C, M, f2["N"], f2["K"], f2lay, st)

@@ -285,6 +285,35 @@ int ivit_gemm_i8_requant_i16_residual_i16_ex(const int8_t* A, int64_t lda, const
 int ivit_gemm_i8_i32(const int8_t* A, int64_t lda, const int8_t* W, int64_t ldw, const int32_t* bias,
                      int32_t* out, int64_t ldo, int M, int N, int K, ivit_stream_t stream);
 
+/* ivit_gemm_plan: HOST function -- which kernel an ivit_gemm_i8_* entry runs for a shape and on which grid, by the very function
+ * the launcher calls (csrc/gemm.hip gemm_plan).  The weight copy a caller hands over has to match that form: row-major for
+ * SMALL and SKINNY, any of row-major / IVIT_W_BLOCKS for PERS, the fragment copies for WREG / WREG16.  The rule in short:
+ *   SKINNY  requant / qkv epilogue, no layout bit, M >= 8192, 32 <= K <= 128, K % 32 == 0, 16 <= N <= 320, N % 16 == 0
+ *   WREG(16) IVIT_W_FRAGS(16): needs M >= 2048, N >= 128, N % 64 == 0, K % 192 == 0, refuses otherwise
+ *   PERS    a requantising epilogue with int8 accumulator QuantAct, M >= 2048, N >= 128 (block operands refuse below that)
+ *   SMALL   everything else
+ * epilogue: IVIT_GEMM_EPI_*, the epilogue of the entry asked about (requant_ex / _bits_ex / _lut_ex: RQ; requant_residual(_bits)_ex:
+ * RESID; requant_qkv(_planes)_ex: QKV; i8_i32: I32; requant_residual_i16_ex: RESID16; requant_i16: RQ16;
+ * requant_i16_residual_i16_ex: RQ16_RES16).  Operands are taken as dense (lda = ldw = K, ldo = ldr = N) and 16-byte aligned.
+ * out8 (host) = form (IVIT_GEMM_FORM_*), workgroups, tiles_m, tiles_n, split_from (tiles from this one on run as two half tiles),
+ * skinny variant (K / 32 of the instantiation: 4, 2; 0 = run-time K), dynamic LDS bytes, 1 if 256-channel tiles waste at most an
+ * eighth of their columns at this N (the callers' condition for a fragment copy whose consumer has no 128-channel items).
+ * Errors: the launcher's own -- IVIT_ERR_INVALID with its message where a launch of that shape and layout would refuse -- and
+ * IVIT_ERR_INVALID for a NULL out8 or an unknown epilogue.  Launches nothing, calls no HIP function. */
+#define IVIT_GEMM_EPI_RQ 0
+#define IVIT_GEMM_EPI_RESID 1
+#define IVIT_GEMM_EPI_QKV 2
+#define IVIT_GEMM_EPI_I32 3
+#define IVIT_GEMM_EPI_RESID16 4
+#define IVIT_GEMM_EPI_RQ16 5
+#define IVIT_GEMM_EPI_RQ16_RES16 6
+#define IVIT_GEMM_FORM_SMALL 0
+#define IVIT_GEMM_FORM_PERS 1
+#define IVIT_GEMM_FORM_WREG 2
+#define IVIT_GEMM_FORM_WREG16 3
+#define IVIT_GEMM_FORM_SKINNY 4
+int ivit_gemm_plan(int epilogue, int M, int N, int K, int layouts, int32_t* out8);
+
 /* ---- fused attention core -------------------------------------------------------------------
  * vit_quant.py:72-85: matmul_1 (q.k^T) -> qact_attn1 -> IVITIntSoftmax (Shiftmax,
  * ivit_modules.py:150-179) -> matmul_2 (P.v) -> qact2, per (image, head), never

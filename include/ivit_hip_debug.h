@@ -29,6 +29,8 @@ extern "C" {
 int ivit_debug_force_small_gemm(int on);
 
 /* ivit_gemm_i8_* (csrc/gemm.hip), first flag word
+ * (csrc/gemm_common.h names the bits for their reader, gemm_plan: LAB_WR_ABLATION bits 0-4, LAB_WR_STAMPS 4, LAB_NO_STAGGER 6,
+ * LAB_SPLIT_ALL_SLOTS 11, LAB_ONE_PER_CU 12, LAB_CU_TURNS 15, LAB_DELAY_SHIFT / LAB_DELAY_MASK 16-21, LAB_GRID_256 26, LAB_NO_HALVES 27)
  *   bits      | meaning                                                              | results | used by
  *   ----------+----------------------------------------------------------------------+---------+-----------------------------
  *   0-3       | weights-in-registers kernel, 32x32x32 form, ivit_gemm_i8_requant_ex: | WRONG   | scripts/gemm_ab.py --frags,
@@ -51,6 +53,7 @@ int ivit_debug_force_small_gemm(int on);
 int ivit_debug_set_gemm_flags(int flags);
 
 /* ivit_gemm_i8_* (csrc/gemm.hip), second flag word
+ * (csrc/gemm_common.h: LAB2_WR16_STAMPS 8, LAB2_WR16_NARROW 13, LAB2_NO_SKINNY 20, LAB2_SKINNY_ANY_K 21)
  *   bits      | meaning                                                              | results | used by
  *   ----------+----------------------------------------------------------------------+---------+-----------------------------
  *   8 (256)   | weights-in-registers kernel, 16x16x64 form, plain and residual       | correct | scripts/wreg_timeline.py

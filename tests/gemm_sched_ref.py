@@ -6,7 +6,8 @@ is split into half tiles, depends on the NUMBER of tiles of a launch and not on 
 outputs is one float32 BLAS call, so the whole output of launches with several rounds can be held against a reference.
 
 Nothing here imports the product: the launcher's arithmetic (csrc/gemm.hip launch_gemm, wr_tile / wr_work, pers_tile /
-pers_work) is RESTATED from its comments, and the CPU test holds the shape tables against the restatement."""
+pers_work) is RESTATED from its comments; the CPU test holds the shape tables against the restatement, and the restatement
+against the launcher's own plan (ivit_gemm_plan)."""
 import numpy as np
 
 K_SCHED = 192          # the smallest K the fragment forms accept ((K / 64) % 3 == 0); above the skinny-K form's 128

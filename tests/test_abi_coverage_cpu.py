@@ -27,6 +27,7 @@ HOST_ONLY = {
     "ivit_version": "test_host_logic.py",
     "ivit_last_error_string": "test_host_logic.py",
     "ivit_eval_geometry": "test_eval_transform_cpu.py",
+    "ivit_gemm_plan": "test_gemm_plan_cpu.py",
     "ivit_jpeg_probe": "test_abi_coverage_cpu.py",
     "ivit_jpeg_plan_image": "test_abi_coverage_cpu.py",
     "ivit_jpeg_workspace": "test_abi_coverage_cpu.py",

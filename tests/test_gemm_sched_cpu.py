@@ -87,3 +87,29 @@ def test_entry_b_has_a_split_tile_with_a_dead_second_half(table):
         tm, tn = divmod(int(lid[gs.SLOTS + (b >> 1)]), tiles_n)
         has_half = any(it[0] == b and it[1] == 1 for it in items)
         assert has_half == (not ((tm, tn) in dead and (b & 1))), b
+
+
+@pytest.mark.parametrize("table", ["wreg", "pers"])
+def test_restated_arithmetic_is_the_launchers(table):
+    """the launcher's own plan (ivit_gemm_plan: the function launch_gemm calls, a host function) reports for every table entry
+    the tile counts, the grid and the first split tile that regime / work_items restate: the reference file is held against
+    the launcher, not only against itself"""
+    import ctypes
+
+    pytest.importorskip("ivit_amd")
+    from ivit_amd import _lib, gemm_forms
+
+    (tt, tc), shapes = gs.TABLES[table]
+    out = (ctypes.c_int32 * 8)()
+    for layouts in {"wreg": (gemm_forms.W_FRAGS, gemm_forms.W_FRAGS16), "pers": (0, gemm_forms.W_BLOCKS)}[table]:
+        form = {0: gemm_forms.PERS, gemm_forms.W_BLOCKS: gemm_forms.PERS, gemm_forms.W_FRAGS: gemm_forms.WREG,
+                gemm_forms.W_FRAGS16: gemm_forms.WREG16}[layouts]
+        for sid, (M, N) in shapes.items():
+            assert _lib.lib().ivit_gemm_plan(gemm_forms.RQ, M, N, gs.K_SCHED, layouts, out) == 0, (table, sid)
+            got_form, grid, tiles_m, tiles_n, split_from = list(out)[:5]
+            ntiles, rounds, R, split, _ = gs.regime(M, N, tt, tc)
+            assert got_form == form and (tiles_m, tiles_n) == (-(-M // tt), -(-N // tc)) and tiles_m * tiles_n == ntiles, (table, sid)
+            assert grid == min(ntiles, gs.SLOTS) and split_from == (rounds * gs.SLOTS if split else ntiles), (table, sid, list(out))
+            items = gs.work_items(M, N, tt, tc)
+            assert max(it[0] for it in items) + 1 == grid, (table, sid)
+            assert sum(1 for it in items if it[3] == tt) == split_from, (table, sid)
