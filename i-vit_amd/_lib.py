@@ -168,6 +168,8 @@ LAB_SIGNATURES = {
     "ivit_debug_attention": [ci],
     "ivit_debug_set_stamp_buffer": [vp],
     "ivit_debug_ibert_integer_sqrt": [vp, i64, vp, vp],
+    "ivit_debug_window_attention_dry_run": [ci],
+    "ivit_debug_window_attention_last_plan": [vp],
 }
 LAB_PATH = os.path.join(_HERE, "libivit_hip_lab.so")
 
@@ -241,6 +243,7 @@ class lab_session:
         L.ivit_debug_ln_stream_cfg(0)
         L.ivit_debug_ln_stamp_buffer(None)
         L.ivit_debug_attention(0)
+        L.ivit_debug_window_attention_dry_run(0)
         _use_lab = self.prev
         return False
 

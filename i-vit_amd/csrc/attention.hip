@@ -1382,9 +1382,7 @@ int attention_check(AttnDesc& d)
     IVIT_REQUIRE(d.Ms < 2048.0 && d.Mo < 512.0, "%s: requant multiplier too large", fn);
     d.x0 = 0;
     if (!ibert) {
-        const float x0f = __builtin_floorf((1.0f / d.s_attn) * -1.0f);  // ivit_modules.py:154
-        IVIT_REQUIRE(x0f <= -1.0f && x0f >= -4096.0f, "%s: x0=%g outside [-4096,-1]", fn, (double)x0f);
-        d.x0 = (int)x0f;
+        if (const int rc = shiftmax_x0(d.s_attn, -4096, fn, &d.x0)) return rc;
         // short rows only: the exact u32 row sum, tokens * |x0| * 2^15, must stay below 2^32.  Long rows: exp_int <= 2 |x0| * 2^14
         // <= 2^27, 16 of them in u32, the row in u64 (common.h rows_allsum_u64)
         if (!lng)
@@ -1502,12 +1500,7 @@ int attention_launch(AttnDesc d)
         a.exp2d = static_cast<const unsigned*>(d.table);
         a.nMs32 = (float)-d.Ms;
         a.x0 = d.x0;
-        a.ksat = 255;
-        for (int i = 0; i < 256; ++i) {
-            const int dd = -i;
-            const int x = dd + (dd >> 1) - (dd >> 4);  // ivit_modules.py:151 (arithmetic shifts = floor)
-            if (x <= 15 * a.x0) { a.ksat = i; break; }
-        }
+        a.ksat = shiftmax_ksat(d.x0);
         const bool rq32 = ms_pow2 && !pb16 && !(IVIT_LAB && (g_attn_debug & (1 << 5)));     // lab bit 5: off, A/B
         kernel = SHIFTMAX_SHORT_KERNELS[d.tokens <= 16 * (NKT - 1)][pbi][d.band_w ? 1 : d.table ? 2 : rq32 ? 3 : 0];
     }

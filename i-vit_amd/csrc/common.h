@@ -39,6 +39,33 @@ static inline hipStream_t ivit_stream(ivit_stream_t s) { return reinterpret_cast
 // A dyadic requantiser passed by value: M = m * 2^-e as an exact double.
 static inline double ivit_dyadic_to_double(uint32_t m, int32_t e) { return __builtin_ldexp((double)m, -e); }
 
+// Shiftmax's x0 = floor(-1 / s) (ivit_modules.py:154) of a positive scale s, accepted in [lo, -1]: lo = -4096 for the attention
+// kernels (their exponents, at most |x0| * 2^15, then stay below 2^27), -65535 for the row operator.  who: the name the message carries.
+static inline int shiftmax_x0(float s, int lo, const char* who, int* x0)
+{
+    const float x0f = __builtin_floorf((1.0f / s) * -1.0f);
+    IVIT_REQUIRE(x0f <= -1.0f && x0f >= (float)lo, "%s: x0=%g outside [%d,-1]", who, (double)x0f, lo);
+    *x0 = (int)x0f;
+    return IVIT_OK;
+}
+
+// The saturation rule of Shiftmax's exponent (ivit_modules.py:151-155, arithmetic shifts = floor): the first distance d <= 255 below
+// the row maximum whose argument -d - floor(d / 2) + floor(d / 16) is clamped at 15 x0 -- every later entry of a table over the
+// distances is identical.  255 and *saturates = false where there is none (x0 <= -25).  The one statement of the rule on the host;
+// swin_engine.window_attention_spec mirrors it (tests/test_window_attention_plan_cpu.py).
+static inline int shiftmax_ksat(int x0, bool* saturates = nullptr)
+{
+    for (int i = 0; i < 256; ++i) {
+        const int d = -i;
+        if (d + (d >> 1) - (d >> 4) <= 15 * x0) {
+            if (saturates) *saturates = true;
+            return i;
+        }
+    }
+    if (saturates) *saturates = false;
+    return 255;
+}
+
 // ---- device side -----------------------------------------------------------------------------
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));

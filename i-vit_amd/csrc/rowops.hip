@@ -1922,9 +1922,9 @@ static int launch_shiftmax(const char* who, const TX* x, int64_t ldx, int rows, 
 {
     IVIT_REQUIRE(x && out && rows > 0 && L > 1 && ldx >= L && ldo >= L, "%s: bad operand (L must be > 1)", who);
     IVIT_REQUIRE(s > 0.0f, "%s: scale must be positive", who);
-    const float x0f = __builtin_floorf((1.0f / s) * -1.0f);
-    IVIT_REQUIRE(x0f <= -1.0f && x0f >= -65535.0f, "%s: x0=%g outside [-65535,-1]", who, (double)x0f);
-    SmArgs<TX> a{x, ldx, rows, L, (int)x0f, out, ldo};
+    int x0;
+    if (const int rc = shiftmax_x0(s, -65535, who, &x0)) return rc;
+    SmArgs<TX> a{x, ldx, rows, L, x0, out, ldo};
     hipLaunchKernelGGL(shiftmax_kernel<TX>, dim3(grid_for_rows(rows)), dim3(NT), 0, ivit_stream(stream), a);
     IVIT_CHECK_LAUNCH(who);
 }

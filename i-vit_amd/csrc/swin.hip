@@ -13,6 +13,8 @@
 extern int g_ln_ablate;     // rowops.hip; bits 16-19: workgroup cap of the tiled 16-bit LayerNorm in units of 256 (0 = default);
                             // bit 20: natural-scale 16-bit LayerNorm sums its rows through LDS (the round-3 form);
                             // bit 23: window attention requantises its scores in float64 also where float32 is exact
+int g_winattn_dry_run = 0;  // ivit_debug_window_attention_dry_run: the eight window-attention entries (here and in swin_probs.hip) stop
+int32_t g_winattn_plan[16]; // in front of their launch and leave its plan here (ivit_debug_window_attention_last_plan)
 #else
 constexpr int g_ln_ablate = 0;
 #endif
@@ -1311,129 +1313,79 @@ IVIT_EXPORT int ivit_avgpool_requant_i8(const int8_t* x, int8_t* out, int batch,
     IVIT_CHECK_LAUNCH("ivit_avgpool_requant_i8");
 }
 
+// ---- window attention, host side: every exported entry fills a WinAttnDesc and returns window_attention_launch(desc)
+namespace {
+
+#include "win_attn_host.h"     // WinAttnDesc, win_attn_check, win_attn_form: shared with swin_probs.hip
+
+// The instantiations of window_attention_kernel, by what selects them: SM, RQ32, long rows (NKT 9), ORD.  An empty slot is never
+// selected: ORD false exists for the short Shiftmax forms only.  The table is written down from SM 3 to 0, RQ32 before the float64
+// form and NKT 9 before 4, because a template is instantiated, and placed in the code object, where it is first named: this is the
+// order the kernels have always had there, and their addresses were part of every measurement.  winattn_kernel does the indexing.
+typedef void (*WinAttnKernel)(WinAttnArgs, int);
+#define WINATTN_SHIFTMAX(SM)                                                                                                          \
+    {{{nullptr, window_attention_kernel<SM, true, 9>}, {window_attention_kernel<SM, true, 4, false>, window_attention_kernel<SM, true, 4>}}, \
+     {{nullptr, window_attention_kernel<SM, false, 9>}, {window_attention_kernel<SM, false, 4, false>, window_attention_kernel<SM, false, 4>}}}
+const WinAttnKernel WINATTN_KERNELS[4][2][2][2] = {      // [3 - SM][!RQ32][!long][ORD]
+    {{{nullptr, window_attention_kernel<3, true, 9>}, {nullptr, window_attention_kernel<3, true, 4>}},
+     {{nullptr, window_attention_kernel<3, false, 9>}, {nullptr, window_attention_kernel<3, false, 4>}}},
+    WINATTN_SHIFTMAX(2), WINATTN_SHIFTMAX(1), WINATTN_SHIFTMAX(0)};
+#undef WINATTN_SHIFTMAX
+inline WinAttnKernel winattn_kernel(int sm, bool rq32, bool long_rows, bool ord) { return WINATTN_KERNELS[3 - sm][!rq32][!long_rows][ord]; }
+
+int window_attention_launch(WinAttnDesc d)
+{
+    if (const int rc = win_attn_check(d)) return rc;
+    const WinSoftmaxForm f = win_attn_form(d);
+    const int tokens = d.tokens;
+    WinAttnArgs a{};
+    a.qkv = d.qkv; a.out = static_cast<int8_t*>(d.out); a.ldo = d.ldo; a.bias = d.bias; a.region = d.region;
+    a.nwin = d.windows; a.heads = d.heads; a.T = tokens; a.nW = d.windows_per_image;
+    a.Ms = d.Ms; a.Mb = d.Mb; a.Mo = d.Mo;
+    a.Ms32 = (float)d.Ms;
+    a.Mb32 = (float)d.Mb;
+    a.x0 = f.x0; a.ksat = f.ksat; a.mask_value = f.mask_value;
+    a.phi = f.phi; a.phim = f.phim;
+    a.band = f.band; a.band1 = f.band1; a.band_w = f.band_w;
+    a.ib_tab = f.ib_tab; a.ib_sat = f.ib_sat;
+    if (d.image_order) {
+        a.omap = WinMap{d.H, d.W, d.ws, d.shift};
+        a.omap_inv = 65536 / d.ws + 1;
+    }
+    // ---- the plan: kernel slot, grid, dynamic LDS, the key stride of the long rows
+    const bool long_rows = tokens > 64;
+    // both score multipliers powers of two (m = 2^k) and in float32's range: the float32 form of the two requantisations is exact
+    a.rq32 = d.m_s != 0 && (d.m_s & (d.m_s - 1)) == 0 && d.m_b != 0 && (d.m_b & (d.m_b - 1)) == 0 && a.Ms >= 1e-30 && a.Mb >= 1e-30 &&
+             a.Mb <= 4096.0 && !(g_ln_ablate & (1 << 23));      // lab bit 23: the float64 form (A/B, parity of both forms)
+    // no row of `tokens` exponents of at most |x0| * 2^15 reaches 2^24: the short Shiftmax forms then run without the ordered-sum branch
+    const bool ord = long_rows || f.sm == 3 || (int64_t)tokens * -(int64_t)f.x0 >= 512;
+    const int npairs = d.windows * d.heads, blocks = (npairs + WPB - 1) / WPB, grid = blocks < 8192 ? blocks : 8192;
+    const int kp = 16 * ((tokens + 15) >> 4);
+    // I-BERT: the exponents of a query tile, [4 waves][16 queries][kp + 1] float32 (37 KB at 144 tokens, beside the kernel's 27 KB);
+    // band rows: [4 waves][16 queries][band_w + WBAND_PAD] dwords
+    const size_t lds_bytes = f.sm == 3 ? (size_t)WPB * 16 * ((long_rows ? kp : 64) + 1) * sizeof(float)
+                             : f.band  ? (size_t)WPB * 16 * (f.band_w + WBAND_PAD) * sizeof(unsigned)
+                                       : 0;
+#if IVIT_LAB
+    if (g_winattn_dry_run) return win_plan_record(d, f, a.rq32, long_rows, ord, grid, lds_bytes, kp, a.omap.ws, a.omap_inv, 0);
+#endif
+    hipLaunchKernelGGL(winattn_kernel(f.sm, a.rq32 != 0, long_rows, ord), dim3(grid), dim3(NT), lds_bytes, ivit_stream(d.stream), a, kp);
+    IVIT_CHECK_LAUNCH(d.name);
+}
+
+}  // namespace
+
+// The six fused entries (contracts: include/ivit_hip.h).  Descriptor order: name, family, qkv, out, ldo, bias, region, mask_value,
+// windows, windows_per_image, heads, tokens, head_dim, m_s, e_s, m_b, e_b, s_attn, m_o, e_o, phi, phim, band, band_w, band_rows, ib_tab,
+// masked_exp, H, W, ws, shift, image_order, stream, needs.
 IVIT_EXPORT int ivit_window_attention_i8(const int8_t* qkv, int8_t* out, int64_t ldo, const int16_t* bias_add,
                                          const uint8_t* mask_region, int mask_value, int windows, int windows_per_image,
                                          int heads, int tokens, int head_dim, uint32_t m_s, int32_t e_s, uint32_t m_b,
                                          int32_t e_b, float s_attn, uint32_t m_o, int32_t e_o, ivit_stream_t stream)
 {
-    return ivit_window_attention_i8_compat(qkv, out, ldo, bias_add, mask_region, mask_value, windows, windows_per_image, heads,
-                                           tokens, head_dim, m_s, e_s, m_b, e_b, s_attn, m_o, e_o, nullptr, nullptr, stream);
-}
-
-// launch(integral_constant<SM>, bool_constant<RQ32>, integral_constant<NKT>) for the Shiftmax form, the score requantisation and
-// the row length the launcher chose: the sixteen instantiations of window_attention_kernel
-template <class F>
-static void winattn_dispatch(int sm, bool rq32, bool long_rows, F launch)
-{
-    auto by_nkt = [&](auto SM, auto RQ32) {
-        if (long_rows) launch(SM, RQ32, std::integral_constant<int, 9>());
-        else launch(SM, RQ32, std::integral_constant<int, 4>());
-    };
-    auto by_rq32 = [&](auto SM) {
-        if (rq32) by_nkt(SM, std::true_type());
-        else by_nkt(SM, std::false_type());
-    };
-    if (sm == 3) by_rq32(std::integral_constant<int, 3>());
-    else if (sm == 2) by_rq32(std::integral_constant<int, 2>());
-    else if (sm == 1) by_rq32(std::integral_constant<int, 1>());
-    else by_rq32(std::integral_constant<int, 0>());
-}
-
-static int window_attention_launch(const int8_t* qkv, int8_t* out, int64_t ldo, const int16_t* bias_add,
-                                   const uint8_t* mask_region, int mask_value, int windows, int windows_per_image,
-                                   int heads, int tokens, int head_dim, uint32_t m_s, int32_t e_s, uint32_t m_b,
-                                   int32_t e_b, float s_attn, uint32_t m_o, int32_t e_o, const float* phi,
-                                   const float* phi_masked, WinMap omap, ivit_stream_t stream, const uint32_t* band = nullptr,
-                                   int band_w = 0, int band_rows = 256, bool long_rows = false, const float* ib_tab = nullptr,
-                                   float ib_sat = 0.0f)
-{
-    // ib_tab: the I-BERT softmax form (ivit_window_attention_i8_ibert, which has checked its own table): band_w is then the width of the
-    // table's band form, `band` NULL, and Shiftmax's s_attn / mask_value are not used
-    IVIT_REQUIRE(qkv && out && bias_add, "ivit_window_attention_i8: NULL operand");
-    // (16 band rows per wave in LDS: 4 x 16 x (192 + 4) dwords = 49 KB beside the kernel's 11 KB stay below the 64 KB of a default launch)
-    IVIT_REQUIRE(ib_tab || band_w == 0 ? band == nullptr : (band && band_w >= 16 && band_w <= 192 && band_w % 16 == 0 && (uintptr_t)band % 16 == 0),
-                 "ivit_window_attention_i8_band: the band table must be 16-byte aligned, its width a multiple of 16 in [16, 192]");
-    IVIT_REQUIRE(windows > 0 && heads > 0 && windows_per_image > 0 && windows % windows_per_image == 0,
-                 "ivit_window_attention_i8: bad window counts");
-    if (!long_rows && (head_dim != WHD || tokens < 2 || tokens > 64)) {
-        ivit_set_error("ivit_window_attention_i8: unsupported geometry head_dim=%d tokens=%d (need 32, 2..64)", head_dim, tokens);
-        return IVIT_ERR_UNSUPPORTED;
-    }
-    if (long_rows && (head_dim != WHD || tokens < 65 || tokens > 144)) {
-        ivit_set_error("ivit_window_attention_i8_long: unsupported geometry head_dim=%d tokens=%d (need 32, 65..144)", head_dim, tokens);
-        return IVIT_ERR_UNSUPPORTED;
-    }
-    IVIT_REQUIRE(((uintptr_t)qkv % 16 == 0) && ((uintptr_t)out % 8 == 0) && ldo % 8 == 0 && ldo >= (int64_t)heads * head_dim,
-                 "ivit_window_attention_i8: misaligned operand or ldo too small");
-    IVIT_REQUIRE(((uintptr_t)bias_add % 8 == 0) && ((uintptr_t)mask_region % 4 == 0), "ivit_window_attention_i8: misaligned table");
-    IVIT_REQUIRE(mask_value <= 0 && mask_value >= -32768, "ivit_window_attention_i8: mask_value=%d outside [-32768, 0]", mask_value);
-    IVIT_REQUIRE(ib_tab || s_attn > 0.0f, "ivit_window_attention_i8: scale must be positive");
-    IVIT_REQUIRE((phi == nullptr) == (phi_masked == nullptr), "ivit_window_attention_i8_compat: phi and phi_masked go together");
-    WinAttnArgs a;
-    a.ib_tab = ib_tab; a.ib_sat = ib_sat;
-    a.omap = omap;
-    a.omap_inv = omap.ws ? 65536 / omap.ws + 1 : 0;
-    for (int qv = 0; qv < (long_rows ? tokens : 64) && omap.ws; ++qv)
-        IVIT_REQUIRE(((qv * a.omap_inv) >> 16) == qv / omap.ws, "ivit_window_attention_i8_unwindow: window size %d unsupported", omap.ws);
-    a.phi = phi; a.phim = phi_masked;
-    IVIT_REQUIRE(band_rows == 256 || band_rows == 1, "ivit_window_attention_i8_band: band_rows must be 256 or 1");
-    a.band = band_rows == 256 ? band : nullptr;
-    a.band1 = band_rows == 1 ? band : nullptr;
-    a.band_w = band_w;
-    a.qkv = qkv; a.out = out; a.ldo = ldo; a.bias = bias_add; a.region = mask_region; a.mask_value = mask_value;
-    a.nwin = windows; a.heads = heads; a.T = tokens; a.nW = windows_per_image;
-    a.Ms = ivit_dyadic_to_double(m_s, e_s);
-    a.Mb = ivit_dyadic_to_double(m_b, e_b);
-    a.Mo = ivit_dyadic_to_double(m_o, e_o);
-    IVIT_REQUIRE(a.Ms < 2048.0 && a.Mb < 1048576.0 && a.Mo < 512.0, "ivit_window_attention_i8: requant multiplier too large");
-    // both score multipliers powers of two (m = 2^k) and in float32's range: the float32 form of the two requantisations is exact
-    a.rq32 = m_s != 0 && (m_s & (m_s - 1)) == 0 && m_b != 0 && (m_b & (m_b - 1)) == 0 && a.Ms >= 1e-30 && a.Mb >= 1e-30 && a.Mb <= 4096.0 &&
-             !(g_ln_ablate & (1 << 23));      // lab bit 23: the float64 form (A/B, parity of both forms)
-    a.Ms32 = (float)a.Ms;
-    a.Mb32 = (float)a.Mb;
-    const float x0f = ib_tab ? -1.0f : __builtin_floorf((1.0f / s_attn) * -1.0f);
-    IVIT_REQUIRE(x0f <= -1.0f && x0f >= -4096.0f, "ivit_window_attention_i8: x0=%g outside [-4096,-1]", (double)x0f);
-    a.x0 = (int)x0f;
-    // exact u32 row sum: tokens * |x0| * 2^15 must stay below 2^32
-    IVIT_REQUIRE((double)tokens * (double)(-a.x0) * 32768.0 < 4294967296.0,
-                 "ivit_window_attention_i8: Shiftmax row sum could overflow 32 bits (x0=%d)", a.x0);
-    a.ksat = 255;
-    bool saturates = false;
-    for (int i = 0; i < 256; ++i) {
-        const int d = -i;
-        if (d + (d >> 1) - (d >> 4) <= 15 * a.x0) { a.ksat = i; saturates = true; break; }
-    }
-    // the short form's (NKT 4) distance table gives a score under the shift mask the table's last entry: the saturated value only if the
-    // table gets there within its 256 distances (x0 >= -24); the literal form (phi tables) is exact at any scale
-    IVIT_REQUIRE(long_rows || saturates || !mask_region || phi || band || ib_tab,
-                 "ivit_window_attention_i8: x0=%d: the integer form cannot place masked scores (use the phi tables)", a.x0);
-    if (a.band1) {      // one row for every maximum: the distance table of the power-of-two form, with the host's values
-        a.ksat = band_w - 1;
-        a.mask_value = -1024;       // a masked score lands beyond the last (saturated) entry whatever the maximum
-    }
-    const int npairs = windows * heads;
-    const int grid = (npairs + WPB - 1) / WPB;
-    // I-BERT: the exponents of a query tile, [4 waves][16 queries][kp + 1] float32 (37 KB at 144 tokens, beside the kernel's 27 KB)
-    const size_t band_bytes = ib_tab  ? (size_t)WPB * 16 * ((long_rows ? 16 * ((tokens + 15) >> 4) : 64) + 1) * sizeof(float)
-                              : a.band ? (size_t)WPB * 16 * (band_w + WBAND_PAD) * sizeof(unsigned)
-                                       : 0;
-    const dim3 grd(grid < 8192 ? grid : 8192), blk(NT);
-    hipStream_t st = ivit_stream(stream);
-    const int kp = 16 * ((tokens + 15) >> 4);
-    // no row of `tokens` exponents of at most |x0| * 2^15 reaches 2^24: the short Shiftmax forms then run without the ordered-sum branch
-    const bool order_sum_possible = (int64_t)tokens * -(int64_t)a.x0 >= 512;
-    winattn_dispatch(ib_tab ? 3 : a.band ? 2 : a.phi ? 1 : 0, a.rq32 != 0, long_rows, [&](auto SM, auto RQ32, auto NKT) {
-        if constexpr (decltype(NKT)::value == 4 && decltype(SM)::value != 3) {
-            if (!order_sum_possible) {
-                hipLaunchKernelGGL((window_attention_kernel<SM.value, RQ32.value, NKT.value, false>), grd, blk, band_bytes, st, a, kp);
-                return;
-            }
-        }
-        hipLaunchKernelGGL((window_attention_kernel<SM.value, RQ32.value, NKT.value>), grd, blk, band_bytes, st, a, kp);
-    });
-    if (ib_tab) IVIT_CHECK_LAUNCH("ivit_window_attention_i8_ibert");
-    if (long_rows) IVIT_CHECK_LAUNCH("ivit_window_attention_i8_long");
-    IVIT_CHECK_LAUNCH("ivit_window_attention_i8");
+    return window_attention_launch({"ivit_window_attention_i8", WIN_SHORT, qkv, out, ldo, bias_add, mask_region, mask_value, windows,
+                                    windows_per_image, heads, tokens, head_dim, m_s, e_s, m_b, e_b, s_attn, m_o, e_o, nullptr, nullptr,
+                                    nullptr, 0, 256, nullptr, 0.0f, 0, 0, 0, 0, 0, stream, 0});
 }
 
 IVIT_EXPORT int ivit_window_attention_i8_compat(const int8_t* qkv, int8_t* out, int64_t ldo, const int16_t* bias_add,
@@ -1442,25 +1394,21 @@ IVIT_EXPORT int ivit_window_attention_i8_compat(const int8_t* qkv, int8_t* out, 
                                                 int32_t e_b, float s_attn, uint32_t m_o, int32_t e_o, const float* phi,
                                                 const float* phi_masked, ivit_stream_t stream)
 {
-    return window_attention_launch(qkv, out, ldo, bias_add, mask_region, mask_value, windows, windows_per_image, heads, tokens,
-                                   head_dim, m_s, e_s, m_b, e_b, s_attn, m_o, e_o, phi, phi_masked, WinMap{0, 0, 0, 0}, stream);
+    return window_attention_launch({"ivit_window_attention_i8_compat", WIN_SHORT, qkv, out, ldo, bias_add, mask_region, mask_value,
+                                    windows, windows_per_image, heads, tokens, head_dim, m_s, e_s, m_b, e_b, s_attn, m_o, e_o, phi,
+                                    phi_masked, nullptr, 0, 256, nullptr, 0.0f, 0, 0, 0, 0, 0, stream, 0});
 }
 
+// (the band table carries the mask: mask_value 0; the geometry, where given, means image order)
 IVIT_EXPORT int ivit_window_attention_i8_band(const int8_t* qkv, int8_t* out, int64_t ldo, const int16_t* bias_add,
                                               const uint8_t* mask_region, int windows, int windows_per_image, int heads, int tokens,
                                               int head_dim, uint32_t m_s, int32_t e_s, uint32_t m_b, int32_t e_b, float s_attn,
                                               uint32_t m_o, int32_t e_o, const uint32_t* band, int band_w, int band_rows, int H, int W,
                                               int ws, int shift, ivit_stream_t stream)
 {
-    IVIT_REQUIRE(band && band_w > 0, "ivit_window_attention_i8_band: no band table");
-    if (ws)
-        IVIT_REQUIRE(ws > 0 && ws * ws == tokens && H > 0 && W > 0 && H % ws == 0 && W % ws == 0 && shift >= 0 && shift < ws &&
-                         windows_per_image == (H / ws) * (W / ws),
-                     "ivit_window_attention_i8_band: H=%d W=%d ws=%d shift=%d do not describe %d windows of %d tokens per image", H, W, ws,
-                     shift, windows_per_image, tokens);
-    return window_attention_launch(qkv, out, ldo, bias_add, mask_region, 0, windows, windows_per_image, heads, tokens, head_dim, m_s,
-                                   e_s, m_b, e_b, s_attn, m_o, e_o, nullptr, nullptr, ws ? WinMap{H, W, ws, shift} : WinMap{0, 0, 0, 0},
-                                   stream, band, band_w, band_rows);
+    return window_attention_launch({"ivit_window_attention_i8_band", WIN_SHORT, qkv, out, ldo, bias_add, mask_region, 0, windows,
+                                    windows_per_image, heads, tokens, head_dim, m_s, e_s, m_b, e_b, s_attn, m_o, e_o, nullptr, nullptr,
+                                    band, band_w, band_rows, nullptr, 0.0f, H, W, ws, shift, ws != 0, stream, WIN_NEEDS_BAND});
 }
 
 IVIT_EXPORT int ivit_window_attention_i8_unwindow(const int8_t* qkv, int8_t* out, int64_t ldo, const int16_t* bias_add,
@@ -1469,14 +1417,12 @@ IVIT_EXPORT int ivit_window_attention_i8_unwindow(const int8_t* qkv, int8_t* out
                                                   int32_t e_b, float s_attn, uint32_t m_o, int32_t e_o, const float* phi,
                                                   const float* phi_masked, int H, int W, int ws, int shift, ivit_stream_t stream)
 {
-    IVIT_REQUIRE(ws > 0 && ws * ws == tokens && H > 0 && W > 0 && H % ws == 0 && W % ws == 0 && shift >= 0 && shift < ws &&
-                 windows_per_image == (H / ws) * (W / ws),
-                 "ivit_window_attention_i8_unwindow: H=%d W=%d ws=%d shift=%d do not describe %d windows of %d tokens per image", H, W, ws,
-                 shift, windows_per_image, tokens);
-    return window_attention_launch(qkv, out, ldo, bias_add, mask_region, mask_value, windows, windows_per_image, heads, tokens,
-                                   head_dim, m_s, e_s, m_b, e_b, s_attn, m_o, e_o, phi, phi_masked, WinMap{H, W, ws, shift}, stream);
+    return window_attention_launch({"ivit_window_attention_i8_unwindow", WIN_SHORT, qkv, out, ldo, bias_add, mask_region, mask_value,
+                                    windows, windows_per_image, heads, tokens, head_dim, m_s, e_s, m_b, e_b, s_attn, m_o, e_o, phi,
+                                    phi_masked, nullptr, 0, 256, nullptr, 0.0f, H, W, ws, shift, 1, stream, WIN_NEEDS_GEOMETRY});
 }
 
+// (without a band table band_w and band_rows are not read, and with one mask_value is not)
 IVIT_EXPORT int ivit_window_attention_i8_long(const int8_t* qkv, int8_t* out, int64_t ldo, const int16_t* bias_add,
                                               const uint8_t* mask_region, int mask_value, int windows, int windows_per_image, int heads,
                                               int tokens, int head_dim, uint32_t m_s, int32_t e_s, uint32_t m_b, int32_t e_b, float s_attn,
@@ -1484,23 +1430,10 @@ IVIT_EXPORT int ivit_window_attention_i8_long(const int8_t* qkv, int8_t* out, in
                                               int band_w, int band_rows, int H, int W, int ws, int shift, int image_order,
                                               ivit_stream_t stream)
 {
-    if (!(ws > 0 && ws * ws == tokens && H > 0 && W > 0 && H % ws == 0 && W % ws == 0 && shift >= 0 && shift < ws &&
-          windows_per_image == (H / ws) * (W / ws))) {
-        ivit_set_error("ivit_window_attention_i8_long: H=%d W=%d ws=%d shift=%d do not describe %d windows of %d tokens per image", H, W,
-                       ws, shift, windows_per_image, tokens);
-        return IVIT_ERR_UNSUPPORTED;
-    }
-    if (band && (band_w < 16 || band_w > 192 || band_w % 16 != 0 || (uintptr_t)band % 16 != 0 || (band_rows != 256 && band_rows != 1) ||
-                 phi || phi_masked)) {
-        ivit_set_error("ivit_window_attention_i8_long: bad band table (16-byte aligned, width a multiple of 16 in [16, 192], 256 or 1 rows, "
-                       "no phi tables beside it)");
-        return IVIT_ERR_UNSUPPORTED;
-    }
-    IVIT_REQUIRE(image_order == 0 || image_order == 1, "ivit_window_attention_i8_long: image_order must be 0 or 1");
-    return window_attention_launch(qkv, out, ldo, bias_add, mask_region, band ? 0 : mask_value, windows, windows_per_image, heads, tokens,
-                                   head_dim, m_s, e_s, m_b, e_b, s_attn, m_o, e_o, phi, phi_masked,
-                                   image_order ? WinMap{H, W, ws, shift} : WinMap{0, 0, 0, 0}, stream, band, band ? band_w : 0,
-                                   band ? band_rows : 256, true);
+    return window_attention_launch({"ivit_window_attention_i8_long", WIN_LONG, qkv, out, ldo, bias_add, mask_region, band ? 0 : mask_value,
+                                    windows, windows_per_image, heads, tokens, head_dim, m_s, e_s, m_b, e_b, s_attn, m_o, e_o, phi,
+                                    phi_masked, band, band ? band_w : 0, band ? band_rows : 256, nullptr, 0.0f, H, W, ws, shift,
+                                    image_order, stream, 0});
 }
 
 IVIT_EXPORT int ivit_window_attention_i8_ibert(const int8_t* qkv, int8_t* out, int64_t ldo, const int16_t* bias_add,
@@ -1509,30 +1442,25 @@ IVIT_EXPORT int ivit_window_attention_i8_ibert(const int8_t* qkv, int8_t* out, i
                                                int32_t e_o, const float* table, int band_w, int H, int W, int ws, int shift, int image_order,
                                                ivit_stream_t stream)
 {
-    if (head_dim != WHD || tokens < 2 || tokens > 144) {
-        ivit_set_error("ivit_window_attention_i8_ibert: unsupported geometry head_dim=%d tokens=%d (need 32, 2..144)", head_dim, tokens);
-        return IVIT_ERR_UNSUPPORTED;
-    }
-    if (ws != 0 && !(ws > 0 && ws * ws == tokens && H > 0 && W > 0 && H % ws == 0 && W % ws == 0 && shift >= 0 && shift < ws &&
-                     windows_per_image == (H / ws) * (W / ws))) {
-        ivit_set_error("ivit_window_attention_i8_ibert: H=%d W=%d ws=%d shift=%d do not describe %d windows of %d tokens per image", H, W,
-                       ws, shift, windows_per_image, tokens);
-        return IVIT_ERR_UNSUPPORTED;
-    }
-    if (band_w != 0 && (band_w < 16 || band_w > 256 || band_w % 16 != 0)) {
-        ivit_set_error("ivit_window_attention_i8_ibert: bad band table (width a multiple of 16 in [16, 256], or 0 for the full table)");
-        return IVIT_ERR_UNSUPPORTED;
-    }
-    IVIT_REQUIRE(table, "ivit_window_attention_i8_ibert: NULL operand");
-    IVIT_REQUIRE((uintptr_t)table % 16 == 0, "ivit_window_attention_i8_ibert: misaligned table");
-    IVIT_REQUIRE(image_order == 0 || (image_order == 1 && ws != 0),
-                 "ivit_window_attention_i8_ibert: image_order must be 0 or 1, and 1 needs the windows' geometry");
-    IVIT_REQUIRE(!mask_region || (masked_exp >= 0.0f && masked_exp <= 32768.0f),
-                 "ivit_window_attention_i8_ibert: masked_exp=%g outside [0, 32768]", (double)masked_exp);
-    return window_attention_launch(qkv, out, ldo, bias_add, mask_region, 0, windows, windows_per_image, heads, tokens, head_dim, m_s, e_s,
-                                   m_b, e_b, 1.0f, m_o, e_o, nullptr, nullptr, image_order ? WinMap{H, W, ws, shift} : WinMap{0, 0, 0, 0},
-                                   stream, nullptr, band_w, 256, tokens > 64, table, masked_exp);
+    return window_attention_launch({"ivit_window_attention_i8_ibert", WIN_IBERT, qkv, out, ldo, bias_add, mask_region, 0, windows,
+                                    windows_per_image, heads, tokens, head_dim, m_s, e_s, m_b, e_b, 1.0f, m_o, e_o, nullptr, nullptr,
+                                    nullptr, band_w, 256, table, masked_exp, H, W, ws, shift, image_order, stream, 0});
 }
+
+#if IVIT_LAB
+IVIT_EXPORT int ivit_debug_window_attention_dry_run(int on)
+{
+    g_winattn_dry_run = on;
+    return IVIT_OK;
+}
+
+IVIT_EXPORT int ivit_debug_window_attention_last_plan(int32_t out[16])
+{
+    IVIT_REQUIRE(out, "ivit_debug_window_attention_last_plan: NULL operand");
+    for (int i = 0; i < 16; ++i) out[i] = g_winattn_plan[i];
+    return IVIT_OK;
+}
+#endif
 
 IVIT_EXPORT int ivit_avgpool_requant_i8_literal(const int8_t* x, int8_t* out, int batch, int tokens, int C, float s_in, uint32_t m,
                                                 int32_t e, ivit_stream_t stream)

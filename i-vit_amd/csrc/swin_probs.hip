@@ -1,9 +1,16 @@
 // swin_probs.hip -- the softmax probabilities of the Swin window attention, written to memory: the P that window_attention_kernel
 // (swin.hip) keeps in registers and multiplies with V.  An inspection path (SwinTransformer.attention_maps), not the hot path: it lives
 // in a file of its own so that swin.hip and the instruction sequences of its tuned kernels are not touched by it.
+// What must not drift from swin.hip, the conditions on the arguments and the choice of the softmax form (x0, ksat, mask value, tables),
+// is not restated here: both files take it from win_attn_host.h.
 // Reference: models/swin_quant.py WindowAttention.forward (:121-169): the tensor attn.log_int_softmax returns, divided by its scale.
 #include "common.h"
 #include "rowsum.h"
+
+#if IVIT_LAB
+extern int g_winattn_dry_run;       // swin.hip (ivit_debug_window_attention_dry_run)
+extern int32_t g_winattn_plan[16];
+#endif
 
 namespace {
 
@@ -229,83 +236,42 @@ using WinProbsKernel = void (*)(WinProbsArgs);
 const WinProbsKernel WPROBS_KERNELS[4] = {window_attention_probs_kernel<0>, window_attention_probs_kernel<1>,
                                           window_attention_probs_kernel<2>, window_attention_probs_kernel<3>};      // [SM]
 
-// the checks the two entries share, in the style of attention_check (attention.hip); fills what both forms use
-int window_probs_check(const char* who, WinProbsArgs& a, const int8_t* qkv, uint8_t* probs, int64_t ldp, const int16_t* bias,
-                       const uint8_t* region, int nwin, int windows_per_image, int heads, int tokens, int head_dim, uint32_t m_s,
-                       int32_t e_s, uint32_t m_b, int32_t e_b)
-{
-    IVIT_REQUIRE(qkv && probs && bias, "%s: NULL operand", who);
-    if (head_dim != WHD || tokens < 2 || tokens > 144) {
-        ivit_set_error("%s: unsupported geometry head_dim=%d tokens=%d (need 32, 2..144)", who, head_dim, tokens);
-        return IVIT_ERR_UNSUPPORTED;
-    }
-    IVIT_REQUIRE(nwin > 0 && heads > 0 && (int64_t)nwin * heads <= 0x7fffffff / 4 && windows_per_image >= 1,
-                 "%s: bad window counts", who);
-    IVIT_REQUIRE(!region || nwin % windows_per_image == 0, "%s: %d windows are no whole number of images of %d", who, nwin,
-                 windows_per_image);
-    IVIT_REQUIRE(ldp >= tokens, "%s: ldp=%lld below tokens=%d", who, (long long)ldp, tokens);
-    IVIT_REQUIRE(((uintptr_t)qkv % 16 == 0) && ((uintptr_t)bias % 16 == 0) && ((uintptr_t)region % 4 == 0),
-                 "%s: misaligned operand (qkv, bias: 16 bytes; region: 4)", who);
-    a.qkv = qkv; a.probs = probs; a.ldp = ldp; a.bias = bias; a.region = region;
-    a.nwin = nwin; a.heads = heads; a.T = tokens; a.nW = windows_per_image; a.kp = wprobs_key_pad(tokens);
-    a.Ms = ivit_dyadic_to_double(m_s, e_s);
-    a.Mb = ivit_dyadic_to_double(m_b, e_b);
-    IVIT_REQUIRE(a.Ms < 2048.0 && a.Mb < 1048576.0, "%s: requant multiplier too large", who);
-    a.dwords = ((uintptr_t)probs % 4 == 0) && ldp % 4 == 0;
-    a.mask_value = 0; a.x0 = -1; a.ksat = 255;
-    a.phi = a.phim = nullptr; a.band = a.band1 = nullptr; a.band_w = 0; a.ib_tab = nullptr; a.ib_sat = 0.0f;
-    return IVIT_OK;
-}
+#include "win_attn_host.h"     // WinAttnDesc, win_attn_check, win_attn_form: the conditions and the softmax form, shared with swin.hip
 
-int window_probs_launch(const char* who, int sm, const WinProbsArgs& a, ivit_stream_t stream)
+int window_probs_launch(WinAttnDesc d)
 {
-    const int npairs = a.nwin * a.heads;
-    hipLaunchKernelGGL(WPROBS_KERNELS[sm], dim3((npairs + WPB - 1) / WPB), dim3(NT), wprobs_lds_bytes(a.T), ivit_stream(stream), a);
-    IVIT_CHECK_LAUNCH(who);
+    if (const int rc = win_attn_check(d)) return rc;
+    const WinSoftmaxForm f = win_attn_form(d);
+    WinProbsArgs a{};
+    a.qkv = d.qkv; a.probs = static_cast<uint8_t*>(d.out); a.ldp = d.ldo; a.bias = d.bias; a.region = d.region;
+    a.nwin = d.windows; a.heads = d.heads; a.T = d.tokens; a.nW = d.windows_per_image; a.kp = wprobs_key_pad(d.tokens);
+    a.Ms = d.Ms; a.Mb = d.Mb;
+    a.x0 = f.x0; a.ksat = f.ksat; a.mask_value = f.mask_value;
+    a.phi = f.phi; a.phim = f.phim;
+    a.band = f.band; a.band1 = f.band1; a.band_w = f.band_w;
+    a.ib_tab = f.ib_tab; a.ib_sat = f.ib_sat;
+    a.dwords = ((uintptr_t)d.out % 4 == 0) && d.ldo % 4 == 0;
+    const int npairs = d.windows * d.heads, grid = (npairs + WPB - 1) / WPB;
+    const size_t lds_bytes = wprobs_lds_bytes(d.tokens);
+#if IVIT_LAB
+    if (g_winattn_dry_run) return win_plan_record(d, f, 0, 0, 0, grid, lds_bytes, a.kp, 0, 0, a.dwords);
+#endif
+    hipLaunchKernelGGL(WPROBS_KERNELS[f.sm], dim3(grid), dim3(NT), lds_bytes, ivit_stream(d.stream), a);
+    IVIT_CHECK_LAUNCH(d.name);
 }
 
 }  // namespace
 
+// The two entries (contracts: include/ivit_hip.h).  Descriptor order as in swin.hip; no output requantisation (m_o = 0 passes the
+// check's bound), no geometry, window order.
 IVIT_EXPORT int ivit_window_attention_probs_u8(const int8_t* qkv, uint8_t* probs, int64_t ldp, const int16_t* bias, const uint8_t* region,
                                                int mask_value, int nwin, int windows_per_image, int heads, int tokens, int head_dim,
                                                uint32_t m_s, int32_t e_s, uint32_t m_b, int32_t e_b, float s_attn, const float* phi,
                                                const float* phim, const uint32_t* band, int band_w, int band_rows, ivit_stream_t stream)
 {
-    const char* who = "ivit_window_attention_probs_u8";
-    WinProbsArgs a;
-    if (const int rc = window_probs_check(who, a, qkv, probs, ldp, bias, region, nwin, windows_per_image, heads, tokens, head_dim, m_s,
-                                          e_s, m_b, e_b))
-        return rc;
-    IVIT_REQUIRE(band ? (band_w >= 16 && band_w <= 192 && band_w % 16 == 0 && (uintptr_t)band % 16 == 0 && (band_rows == 256 || band_rows == 1))
-                      : band_w == 0,
-                 "%s: the band table must be 16-byte aligned, its width a multiple of 16 in [16, 192], band_rows 256 or 1", who);
-    IVIT_REQUIRE((phi == nullptr) == (phim == nullptr), "%s: phi and phim go together", who);
-    IVIT_REQUIRE(((uintptr_t)phi % 4 == 0) && ((uintptr_t)phim % 4 == 0), "%s: misaligned table", who);
-    IVIT_REQUIRE(mask_value <= 0 && mask_value >= -32768, "%s: mask_value=%d outside [-32768, 0]", who, mask_value);
-    IVIT_REQUIRE(s_attn > 0.0f, "%s: scale must be positive", who);
-    const float x0f = __builtin_floorf((1.0f / s_attn) * -1.0f);
-    IVIT_REQUIRE(x0f <= -1.0f && x0f >= -4096.0f, "%s: x0=%g outside [-4096,-1]", who, (double)x0f);
-    a.x0 = (int)x0f;
-    // exact u32 row sum: tokens * |x0| * 2^15 must stay below 2^32
-    IVIT_REQUIRE((double)tokens * (double)(-a.x0) * 32768.0 < 4294967296.0, "%s: Shiftmax row sum could overflow 32 bits (x0=%d)", who, a.x0);
-    a.mask_value = mask_value;
-    for (int i = 0; i < 256; ++i) {      // the first distance at which the table of distances has saturated (255: it has not)
-        const int d = -i;
-        if (d + (d >> 1) - (d >> 4) <= 15 * a.x0) { a.ksat = i; break; }
-    }
-    int sm = 0;
-    if (band && band_rows == 256) {
-        a.band = band; a.band_w = band_w;
-        sm = 2;
-    } else if (band) {      // one row for every maximum: the table of distances with the host's values
-        a.band1 = band; a.band_w = band_w;
-        a.ksat = band_w - 1;
-        a.mask_value = -1024;      // a masked score lands beyond the last (saturated) entry whatever the maximum
-    } else if (phi) {
-        a.phi = phi; a.phim = phim;
-        sm = 1;
-    }
-    return window_probs_launch(who, sm, a, stream);
+    return window_probs_launch({"ivit_window_attention_probs_u8", WIN_SHIFTMAX_PROBS, qkv, probs, ldp, bias, region, mask_value, nwin,
+                                windows_per_image, heads, tokens, head_dim, m_s, e_s, m_b, e_b, s_attn, 0, 0, phi, phim, band, band_w,
+                                band_rows, nullptr, 0.0f, 0, 0, 0, 0, 0, stream, 0});
 }
 
 IVIT_EXPORT int ivit_window_attention_probs_u8_ibert(const int8_t* qkv, uint8_t* probs, int64_t ldp, const int16_t* bias,
@@ -313,16 +279,7 @@ IVIT_EXPORT int ivit_window_attention_probs_u8_ibert(const int8_t* qkv, uint8_t*
                                                      int tokens, int head_dim, uint32_t m_s, int32_t e_s, uint32_t m_b, int32_t e_b,
                                                      const float* table, int band_w, ivit_stream_t stream)
 {
-    const char* who = "ivit_window_attention_probs_u8_ibert";
-    WinProbsArgs a;
-    IVIT_REQUIRE(table, "%s: NULL operand", who);
-    if (const int rc = window_probs_check(who, a, qkv, probs, ldp, bias, region, nwin, windows_per_image, heads, tokens, head_dim, m_s,
-                                          e_s, m_b, e_b))
-        return rc;
-    IVIT_REQUIRE((uintptr_t)table % 4 == 0, "%s: misaligned table", who);
-    IVIT_REQUIRE(band_w == 0 || (band_w >= 16 && band_w <= 256 && band_w % 16 == 0),
-                 "%s: bad band width %d (a multiple of 16 in [16, 256], or 0 for the full table)", who, band_w);
-    IVIT_REQUIRE(!region || (masked_exp >= 0.0f && masked_exp <= 32768.0f), "%s: masked_exp=%g outside [0, 32768]", who, (double)masked_exp);
-    a.ib_tab = table; a.ib_sat = masked_exp; a.band_w = band_w;
-    return window_probs_launch(who, 3, a, stream);
+    return window_probs_launch({"ivit_window_attention_probs_u8_ibert", WIN_IBERT_PROBS, qkv, probs, ldp, bias, region, 0, nwin,
+                                windows_per_image, heads, tokens, head_dim, m_s, e_s, m_b, e_b, 1.0f, 0, 0, nullptr, nullptr, nullptr,
+                                band_w, 256, table, masked_exp, 0, 0, 0, 0, 0, stream, 0});
 }

@@ -153,7 +153,9 @@ def window_attention_spec(upload, bias, s_tab, s_S, s_at, s_A, s_pv, s_a3, regio
         # the integer form of the short entries reads Shiftmax's exp_int from a table over the 256 distances to the row maximum and
         # gives a masked score (|mask_value| or more below it) the LAST entry: right only if the table has saturated by then, i.e.
         # -d - floor(d / 2) + floor(d / 16) <= 15 x0 for some d <= 255 (ivit_modules.py:151-155; x0 = floor(-1 / s) <= -25 never
-        # does).  Otherwise the literal form, which is exact at any scale
+        # does).  Otherwise the literal form, which is exact at any scale.  The rule's home is shiftmax_ksat (csrc/common.h), which
+        # win_attn_check (csrc/win_attn_host.h) applies to the short entries; this copy stays because the form is chosen here, before
+        # any launch, and tests/test_window_attention_plan_cpu.py holds it to the launcher's answer
         x0 = int(np.floor(f32(-1.0) / s_A))
         if N <= SHORT_WINDOW and not any(-d + (-d >> 1) - (-d >> 4) <= 15 * x0 for d in range(256)):
             att_nat = True

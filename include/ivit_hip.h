@@ -688,7 +688,10 @@ int ivit_window_attention_i8_compat(const int8_t* qkv, int8_t* out, int64_t ldo,
  * hands the table over only when that is what the reference computes for every masked score and no masked score can be a row
  * maximum (prepare.window_shiftexp_band checks both; otherwise the literal form above runs).  band_rows = 256, or 1 when the rows
  * of the table do not depend on the maximum (the host compares them): `band` is then that one row [band_w] and the kernel runs
- * exactly as at a power-of-two scale, on these values.  ws != 0: output rows at their image positions as in
+ * exactly as at a power-of-two scale, on these values.  (The saturation rule itself -- from which distance the exponent's
+ * argument is clamped at 15 x0 -- has one home on the host, shiftmax_ksat in csrc/common.h; every attention launcher takes it there,
+ * and the conditions and the form selection of all eight window-attention entries are csrc/win_attn_host.h.)
+ * ws != 0: output rows at their image positions as in
  * ivit_window_attention_i8_unwindow (H, W, ws, shift); ws == 0: window order. */
 int ivit_window_attention_i8_band(const int8_t* qkv, int8_t* out, int64_t ldo, const int16_t* bias_add, const uint8_t* mask_region,
                                   int windows, int windows_per_image, int heads, int tokens, int head_dim, uint32_t m_s, int32_t e_s,

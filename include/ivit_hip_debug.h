@@ -131,6 +131,21 @@ int ivit_debug_ln_ablate(int bits);
  *         | selector)                                                                    |         | */
 int ivit_debug_attention(int bits);
 
+/* ivit_window_attention_i8* and ivit_window_attention_probs_u8* (csrc/swin.hip, csrc/swin_probs.hip, csrc/win_attn_host.h): dry run.
+ * on != 0: the eight entries check their arguments and choose their softmax form and kernel as ever, then return IVIT_OK in front of
+ * the launch (nothing reaches the device, no operand is read) and leave the plan of that launch for ivit_debug_window_attention_last_plan:
+ *   out[0..3]   SM (0 table of distances, 1 literal, 2 band rows, 3 I-BERT), RQ32, long rows (NKT 9), ORD -- the slot of the kernel
+ *               table; the probability entries have SM only (the other three 0)
+ *   out[4..6]   grid (workgroups), dynamic LDS bytes, kp (the key stride of the bias / region rows)
+ *   out[7..10]  x0, ksat, the effective mask_value (0 for SM 1 - 3, which do not read it), band_w as the kernel receives them
+ *   out[11]     the tables the kernel receives: 1 band, 2 the one-row band, 4 phi / phim, 8 the I-BERT table
+ *   out[12..13] omap.ws, omap_inv (0 0: window order)
+ *   out[14]     probabilities: packed dword stores
+ *   out[15]     family: 0 short, 1 long, 2 I-BERT, 3 Shiftmax probabilities, 4 I-BERT probabilities
+ * A rejected call leaves the last plan as it was.  tests/test_window_attention_plan_cpu.py */
+int ivit_debug_window_attention_dry_run(int on);
+int ivit_debug_window_attention_last_plan(int32_t out[16]);
+
 /* probe: out[i] = integer_sqrt(n[i]) for i < count, the device function every I-BERT LayerNorm kernel calls under
  * IVIT_IBERT_LN_INT_SQRT (csrc/isqrt.h; ibert_modules.py:85-109 -- four float32 Newton steps from 2^ceil(bits / 2), bits from the
  * float32 log2).  n: device float32 (the row sum var_int), out: device int32.  tests/test_gpu_ibert_intsqrt.py runs it over
