@@ -8,3 +8,4 @@ from .quantization_utils import *  # noqa: F401,F403
 from .vit_quant import *  # noqa: F401,F403
 from .swin_quant import *  # noqa: F401,F403
 from .model_utils import freeze_model, unfreeze_model  # noqa: F401
+from .knn import FeatureBank, knn_classify  # noqa: F401

@@ -153,6 +153,11 @@ SIGNATURES = {
     "ivit_tokens_to_nchw_i16": [vp, i64, ci, ci, ci, ci, ci, vp, vp],
     # backbone outputs (include/ivit_hip.h, end)
     "ivit_dequant_rows_i8_f32": [vp, i64, i64, ci, f32, vp, i64, vp],
+    # k-NN on the int8 feature bank (include/ivit_hip.h, end): ivit_knn_workspace_bytes is a host function
+    "ivit_rows_rnorm_i8_f32": [vp, i64, i64, ci, vp, vp],
+    "ivit_knn_topk_i8": [vp, i64, ci, vp, i64, ci, ci, vp, ci, ci, vp, vp, vp, i64, vp],
+    "ivit_knn_workspace_bytes": [ci, ci, ci, ci, vp],
+    "ivit_knn_vote_f32": [vp, vp, vp, ci, ci, ci, ci, vp, vp, vp],
 }
 
 

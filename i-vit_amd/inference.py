@@ -26,6 +26,7 @@ import torch
 import torch.distributed as dist
 
 from . import swin_quant, topk, vit_quant
+from .knn import FeatureBank, knn_weights
 from .model_utils import freeze_model
 from .parallel import allreduce_hits, shard_bounds
 
@@ -263,6 +264,35 @@ def extract_features(model, data_loader, device, *, transform=None, graph: bool 
     if graph and hasattr(model, "graph_status"):
         model.graph_status()
     return bank[:n], labels[:n], scale
+
+
+def evaluate_knn(model, bank_loader, query_loader, device, *, k=(10, 20, 100, 200), T: float = 0.07, transform=None, graph: bool = False):
+    """Weighted k-NN accuracy of a backbone -> {k: (top-1 %, top-5 %)}.  Both sets go through extract_features(..., integers=True);
+    the bank stays int8 (knn.FeatureBank) and ONE search at max(k) serves every k: the neighbour order is total, so the neighbours
+    for a smaller k are a prefix.  Per k the neighbours vote with w = exp(cos / T) (knn.knn_weights); top-5 counts a hit among the
+    first min(5, k) voted classes.  The two extractions must carry the same scale (the same frozen model): anything else raises."""
+    ks = tuple(sorted({int(v) for v in ((k,) if isinstance(k, int) else k)}))
+    if not ks or ks[0] < 1:
+        raise ValueError(f"evaluate_knn: k={k!r}")
+    rows, labels, s_bank = extract_features(model, bank_loader, device, transform=transform, graph=graph, integers=True)
+    q, targets, s_query = extract_features(model, query_loader, device, transform=transform, graph=graph, integers=True)
+    if s_bank is None or s_query is None:
+        raise ValueError("evaluate_knn: an empty bank or query set")
+    fb, fq = float(torch.as_tensor(s_bank).reshape(-1)[0]), float(torch.as_tensor(s_query).reshape(-1)[0])
+    if fb != fq:
+        raise ValueError(f"evaluate_knn: the bank's rows carry scale {fb!r}, the queries' {fq!r}: not the same frozen model")
+    if ks[-1] > int(rows.shape[0]):
+        raise ValueError(f"evaluate_knn: k={ks[-1]} above the {int(rows.shape[0])} rows of the bank")
+    bank = FeatureBank(rows, labels, s_bank)
+    idx, cos = bank.search(q, ks[-1])
+    w = knn_weights(cos, T)
+    targets = targets.to(torch.int32)
+    out, n = {}, max(int(q.shape[0]), 1)
+    for kk in ks:
+        classes, _ = bank.vote(idx[:, :kk], w[:, :kk], min(5, kk))
+        hit = classes == targets[:, None]
+        out[kk] = (100.0 * int(hit[:, 0].sum()) / n, 100.0 * int(hit.any(dim=1).sum()) / n)
+    return out
 
 
 def extract_features_parallel(model, data_loader, device, *, transform=None, graph: bool = False, integers: bool = False):

@@ -1044,6 +1044,53 @@ int ivit_tokens_to_nchw_i16(const int16_t* x, int64_t ldx, int B, int T_all, int
  * 2^31 - 1 workgroups of 256 slots (a row has C / 16 + 2 slots).  Nothing is launched on an error. */
 int ivit_dequant_rows_i8_f32(const int8_t* x, int64_t ldx, int64_t rows, int C, float s, float* out, int64_t ldo, ivit_stream_t stream);
 
+/* ---- k-NN evaluation on an int8 feature bank: cosine neighbours, exact and unique ---------------------------------------------
+ * Bank rows b_j and query rows q_i are int8 rows of C channels under one per-tensor scale each (the scales cancel in a cosine).
+ *   n2_j     = sum_c b_jc^2 (integer)
+ *   rnorm_j  = 1.0f / sqrtf((float)n2_j), sqrt and division correctly rounded (no rsqrt form); 0.0f where n2_j == 0
+ *   score_ij = fl32((float)dot_ij * rnorm_j), dot_ij the exact int32 dot product: ONE float32 multiplication.  With C <= 1024
+ *              both |dot| and n2 are at most 2^24 and convert exactly.
+ * The neighbours of query i are the k bank rows with the largest score_ij, score descending, equal scores (float comparison,
+ * -0 == +0) by ascending bank index -- the rule of ivit_head_topk.  The order is total, so the result is unique whatever the
+ * tiling or the number of bank segments, and the neighbours for a smaller k are a prefix.  The cosine is
+ * fl32(score_ij * rnorm(q_i)), one more float32 product, left to the caller.
+ *
+ * ivit_rows_rnorm_i8_f32: out[r] = rnorm of row r of x (rows x C, row stride ldx >= C in elements), 1 <= C <= 65536.  The far
+ * dimension is `rows`: r * ldx is a 64-bit product, a row may start beyond 2^32 bytes of x.  x and ldx may have any alignment (rows
+ * on a 16-byte boundary are read 16 bytes at a time), out that of a float; elements C .. ldx - 1 of a row are not read.  One launch,
+ * rows == 0 is IVIT_OK without one.  Errors: IVIT_ERR_INVALID for a NULL pointer, C outside [1, 65536], rows < 0, ldx < C, a
+ * misaligned out; nothing is launched.
+ *
+ * ivit_knn_topk_i8: idx[i * k + n] / score[i * k + n] = bank index and score_ij of the n-th neighbour of query i, 0 <= i < Q.
+ * q is Q x C with row stride ldq, bank N x C with row stride ldb, rnorm [N] as ivit_rows_rnorm_i8_f32 writes it.  Geometry:
+ * C % 64 == 0, 64 <= C <= 1024, 1 <= k <= IVIT_KNN_K_MAX, k <= N < 2^31, Q >= 0 (Q == 0: IVIT_OK, nothing launched).  q, bank, ldq
+ * and ldb are multiples of 16 bytes; row offsets are 64-bit products on q, bank, idx and score.  Elements C .. ld - 1 of a row are
+ * not read.  splits: the bank is cut into that many segments of ceil(N / splits) rows rounded up to 64, searched by separate
+ * workgroups and merged by a second launch -- 1 .. IVIT_KNN_SPLITS_MAX as given (a segment may hold fewer than k rows, or none),
+ * 0 = chosen from Q and N for the 256 CUs the other launchers assume.  workspace: ivit_knn_workspace_bytes(Q, N, k, splits)
+ * bytes aligned to 8 (0 bytes with one segment: workspace may then be NULL).  The [Q][N] scores never reach memory.
+ * Errors, nothing launched and nothing written: IVIT_ERR_INVALID for a NULL operand, Q < 0, N < 1, k < 1, k > N, splits outside
+ * [0, IVIT_KNN_SPLITS_MAX], ldq or ldb below C, a misaligned pointer or leading dimension, a workspace that is NULL, misaligned or
+ * too small; IVIT_ERR_UNSUPPORTED ("unsupported geometry") for k > IVIT_KNN_K_MAX and for any other C.
+ *
+ * ivit_knn_workspace_bytes: a host function; *bytes for that call (the same checks of Q, N, k and splits).
+ *
+ * ivit_knn_vote_f32: the weighted vote of a query's neighbours.  idx [Q][k] (as above), labels [N] int32, w [Q][k] float32.  The
+ * vote of a label is the float32 sum of the w of the neighbours that carry it, added in rank order starting from 0.0f; classes /
+ * votes [Q][r], 1 <= r <= k <= IVIT_KNN_K_MAX: the r labels with the largest vote, vote descending, equal votes by ascending
+ * label; with fewer than r distinct labels the rest is (-1, 0.0f).  Computed among the query's own k neighbours: no per-class
+ * table (any number of classes), no atomics (deterministic).  An index outside [0, N) is NOT checked on the device: idx must be
+ * what ivit_knn_topk_i8 wrote for a bank of N rows.  Errors: IVIT_ERR_INVALID for a NULL or misaligned pointer, Q < 0, N < 1, k
+ * outside [1, IVIT_KNN_K_MAX], r outside [1, k]. */
+#define IVIT_KNN_K_MAX 256
+#define IVIT_KNN_SPLITS_MAX 64
+int ivit_rows_rnorm_i8_f32(const int8_t* x, int64_t ldx, int64_t rows, int C, float* out, ivit_stream_t stream);
+int ivit_knn_topk_i8(const int8_t* q, int64_t ldq, int Q, const int8_t* bank, int64_t ldb, int N, int C, const float* rnorm, int k,
+                     int splits, int32_t* idx, float* score, void* workspace, int64_t workspace_bytes, ivit_stream_t stream);
+int ivit_knn_workspace_bytes(int Q, int N, int k, int splits, int64_t* bytes);
+int ivit_knn_vote_f32(const int32_t* idx, const int32_t* labels, const float* w, int Q, int N, int k, int r, int32_t* classes,
+                      float* votes, ivit_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
