@@ -56,6 +56,11 @@ SIGNATURES = {
     "ivit_attention_fused_i8": [vp, vp, ci, ci, ci, ci, u32, i32, f32, u32, i32, vp],
     "ivit_layernorm_i8": [vp, i64, ci, ci, vp, vp, vp, vp, vp, i64, vp],
     "ivit_layernorm_i32_f32": [vp, i64, ci, ci, vp, vp, vp, i64, vp],
+    # token features (csrc/ln_tokens.h): x, ldx, B, T_all, t0, T, C, ... out, ldo, flags, stream
+    "ivit_layernorm_i8_f32": [vp, i64, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, i64, ci, vp],
+    "ivit_layernorm_i16_f32": [vp, i64, ci, ci, ci, ci, ci, f32, vp, vp, vp, i64, ci, vp],
+    "ivit_ibert_layernorm_i8_f32": [vp, i64, ci, ci, ci, ci, ci, f32, vp, vp, f32, vp, i64, ci, vp],
+    "ivit_ibert_layernorm_i16_f32": [vp, i64, ci, ci, ci, ci, ci, f32, vp, vp, f32, vp, i64, ci, vp],
     "ivit_layernorm_f32_f32": [vp, i64, ci, ci, vp, ci, vp, vp, vp, i64, vp],
     "ivit_layernorm_f32_f32_ex": [vp, i64, ci, ci, vp, ci, vp, vp, vp, i64, ci, vp],
     "ivit_shiftmax_f32_i8": [vp, i64, ci, ci, f32, vp, i64, vp],

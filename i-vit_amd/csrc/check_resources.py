@@ -80,7 +80,12 @@ def occupancy_rules(path, what):
     kernels = parse(open(path, errors="replace").read())
     bad, seen = [], 0
     for name, r in sorted(kernels.items()):
-        if what == "attention" and "attention_long_kernel" in name:
+        if "ln_tokens_f32_kernel" in name:
+            # ln_tokens_f32_kernel<ROW> (ln_tokens.h; rowops.hip: int8 rows, swin.hip: int16 rows): every loop runs over the channel
+            # count and nothing is indexed at run time, so no form keeps anything in scratch at any C; three workgroups of four
+            # waves fit a CU beside their 48 KB token tiles at C = 768 (its launcher assumes no number of resident workgroups)
+            occ, need_no_scratch = 3, True
+        elif what == "attention" and "attention_long_kernel" in name:
             # attention_long_kernel<MODE, RQ32, NKT, NTH, PB>: one workgroup of NTH threads per CU (the launcher's 256 slots), i.e.
             # NTH / 256 waves per SIMD; the packed score rows must stay in registers: no scratch.  PB = 16 (the three probability
             # planes): 768 threads up to 40 key tiles, 512 above

@@ -277,6 +277,26 @@ struct IbLnI8Args {
 };
 
 // one row, literally (whole wave); orow: the row of `out` it is stored to (row-major output)
+// One row of IBERTIntLayerNorm literally (whole wave) from xint(c) = fl(q * s) / s (:126) to v = floor(y * factor / 2) + bias_int
+// (:151); every element goes to tail(c, v): the QuantAct of ib_ln_row_literal, the float product of the token-feature kernel.
+template <bool ISQ, class XINT, class TAIL>
+IVIT_DEV void ib_ln_row(XINT xint, int C, float shift_pow2, const float* bias_int, int lane, TAIL tail)
+{
+    const float mean_int = rintf(torch_rowsum(xint, C, lane) / (float)C);                     // :127
+    auto sq = [&](int c) {
+        const float ys = floorf((xint(c) - mean_int) / shift_pow2);                           // :128-129
+        return ys * ys;                                                                       // :130
+    };
+    const float var_int = torch_rowsum(sq, C, lane);                                          // :131
+    const float std_int = ib_std_int<ISQ>(var_int, shift_pow2);                                // :142-145
+    const float factor = floorf(2147483648.0f / std_int);                                     // :143
+    for (int c = lane; c < C; c += 64) {
+        const float y = xint(c) - mean_int;
+        float v = floorf((y * factor) / 2.0f);                                                // :144
+        tail(c, v + bias_int[c]);                                                             // :151
+    }
+}
+
 template <typename TX = int8_t, bool ISQ = false>
 IVIT_DEV void ib_ln_row_literal(const IbLnI8Args& a, int row, int lane, int64_t orow)
 {
@@ -284,19 +304,8 @@ IVIT_DEV void ib_ln_row_literal(const IbLnI8Args& a, int row, int lane, int64_t 
     {
         const TX* xr = reinterpret_cast<const TX*>(a.x) + (int64_t)row * a.ldx;
         auto xint = [&](int c) { return ((float)xr[c] * a.s_in) / a.s_in; };                  // :126 on fl(q * s)
-        const float mean_int = rintf(torch_rowsum(xint, C, lane) / (float)C);                 // :127
-        auto sq = [&](int c) {
-            const float ys = floorf((xint(c) - mean_int) / a.shift_pow2);                     // :128-129
-            return ys * ys;                                                                   // :130
-        };
-        const float var_int = torch_rowsum(sq, C, lane);                                      // :131
-        const float std_int = ib_std_int<ISQ>(var_int, a.shift_pow2);                          // :142-145
-        const float factor = floorf(2147483648.0f / std_int);                                 // :143
         const BlockRow brow = block_row(row, C);
-        for (int c = lane; c < C; c += 64) {
-            const float y = xint(c) - mean_int;
-            float v = floorf((y * factor) / 2.0f);                                            // :144
-            v = v + a.bias_int[c];                                                            // :151
+        ib_ln_row<ISQ>(xint, C, a.shift_pow2, a.bias_int, lane, [&](int c, float v) {
             const float so = a.s_out[c];
             const float xo = v * so;                                                          // :153
             const float z = rintf(xo / so);                                                   // quant_utils.py:220
@@ -305,9 +314,32 @@ IVIT_DEV void ib_ln_row_literal(const IbLnI8Args& a, int row, int lane, int64_t 
             const int8_t o = (int8_t)(int)r;
             if (a.out_blocks) a.out[block_off(brow, block_col(c))] = o;
             else a.out[orow * a.ldo + c] = o;
-        }
+        });
     }
 }
+
+#include "ln_tokens.h"
+
+// one int8 / int16 row of the token-feature kernel: ib_ln_row with the float product (:153) as its tail
+template <typename TX, bool ISQ, bool FASTDIV>
+struct LnTokRowIbert {
+    static constexpr int TAB = 0;
+    const TX* x;
+    int C;
+    float s_in, r_in, shift_pow2;
+    const float* bias_int;
+    const float* s_out;
+
+    IVIT_DEV void setup(int, unsigned char*, float*) {}
+
+    template <class EMIT>
+    IVIT_DEV void row(int64_t xoff, int lane, EMIT emit) const
+    {
+        const TX* xr = x + xoff;
+        ib_ln_row<ISQ>([&](int c) { return ln_tok_phi16<FASTDIV>(xr[c], s_in, r_in); }, C, shift_pow2, bias_int, lane,
+                       [&](int c, float v) { emit(c, v * s_out[c]); });
+    }
+};
 
 template <typename TX, bool ISQ>
 __global__ __launch_bounds__(NT) void ibert_layernorm_i8_kernel(IbLnI8Args a)
@@ -826,6 +858,42 @@ IVIT_EXPORT int ivit_ibert_layernorm_i16_i8_win(const int16_t* x, int64_t ldx, i
     return ibert_ln16_launch("ivit_ibert_layernorm_i16_i8_win", x, ldx, rows, C, s_in, bias_int, s_out, shift_pow2, m, e, out, ldo,
                              (fast_division & 1) != 0, (fast_division & IVIT_IBERT_LN_INT_SQRT) != 0,
                              ws ? WinMap{H, W, ws, shift} : WinMap{0, 0, 0, 0}, stream);
+}
+
+// the two token-feature entries: TX rows, flags = IVIT_LN_F32_CHANNEL_MAJOR | IVIT_LN_F32_FAST_DIV (int16 only) | IVIT_IBERT_LN_INT_SQRT
+template <typename TX>
+static int ibert_ln_tokens(const char* who, const TX* x, int64_t ldx, int B, int T_all, int t0, int T, int C, float s_in, const float* bias_int,
+                           const float* s_out, float shift_pow2, float* out, int64_t ldo, int flags, ivit_stream_t stream)
+{
+    const bool isq = (flags & IVIT_IBERT_LN_INT_SQRT) != 0, fast = (flags & IVIT_LN_F32_FAST_DIV) != 0;
+    LnTok o;
+    size_t lds;
+    IVIT_REQUIRE(s_in > 0.0f && shift_pow2 >= 1.0f, "%s: s_in must be positive and shift_pow2 = 2^shift at least 1", who);
+    IVIT_REQUIRE(!fast || sizeof(TX) == 2, "%s: IVIT_LN_F32_FAST_DIV belongs to the 16-bit entry", who);
+    if (const int rc = ln_tok_check(who, x, sizeof(TX), ldx, B, T_all, t0, T, C, bias_int, s_out, out, ldo,
+                                    flags & ~(IVIT_IBERT_LN_INT_SQRT | IVIT_LN_F32_FAST_DIV), 0, &o, &lds))
+        return rc;
+    const float r_in = 1.0f / s_in;
+    if constexpr (sizeof(TX) == 2) {
+        if (fast && isq) return ln_tok_launch(who, LnTokRowIbert<TX, true, true>{x, C, s_in, r_in, shift_pow2, bias_int, s_out}, o, lds, stream);
+        if (fast) return ln_tok_launch(who, LnTokRowIbert<TX, false, true>{x, C, s_in, r_in, shift_pow2, bias_int, s_out}, o, lds, stream);
+    }
+    if (isq) return ln_tok_launch(who, LnTokRowIbert<TX, true, false>{x, C, s_in, r_in, shift_pow2, bias_int, s_out}, o, lds, stream);
+    return ln_tok_launch(who, LnTokRowIbert<TX, false, false>{x, C, s_in, r_in, shift_pow2, bias_int, s_out}, o, lds, stream);
+}
+
+IVIT_EXPORT int ivit_ibert_layernorm_i8_f32(const int8_t* x, int64_t ldx, int B, int T_all, int t0, int T, int C, float s_in,
+                                            const float* bias_int, const float* s_out, float shift_pow2, float* out, int64_t ldo,
+                                            int flags, ivit_stream_t stream)
+{
+    return ibert_ln_tokens("ivit_ibert_layernorm_i8_f32", x, ldx, B, T_all, t0, T, C, s_in, bias_int, s_out, shift_pow2, out, ldo, flags, stream);
+}
+
+IVIT_EXPORT int ivit_ibert_layernorm_i16_f32(const int16_t* x, int64_t ldx, int B, int T_all, int t0, int T, int C, float s_in,
+                                             const float* bias_int, const float* s_out, float shift_pow2, float* out, int64_t ldo,
+                                             int flags, ivit_stream_t stream)
+{
+    return ibert_ln_tokens("ivit_ibert_layernorm_i16_f32", x, ldx, B, T_all, t0, T, C, s_in, bias_int, s_out, shift_pow2, out, ldo, flags, stream);
 }
 
 #if IVIT_LAB

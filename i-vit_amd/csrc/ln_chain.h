@@ -1,6 +1,7 @@
 // ln_chain.h -- the tail of the reference's LayerNorm + QuantAct chain for one element, stated ONCE for every int8-output I-ViT
 // LayerNorm kernel (rowops.hip, ln_stream.h, swin.hip).  Included inside the anonymous namespace of those files, after common.h.
-// Arithmetic only: loads, stores, scheduling barriers and the lab ablation branches stay in the kernels.
+// Arithmetic only: loads, stores, scheduling barriers and the lab ablation branches stay in the kernels.  The float-emitting
+// token-feature kernel (ln_tokens.h) takes the chain up to y (ln_y) and ends in ln_f32 instead of the QuantAct.
 // Reference: ivit_modules.py:45-63 (IVITIntLayerNorm), quant_utils.py:220, 229-230 (fixedpoint_mul).
 //
 // With y = floor((x - mean) * factor / 2) + bias_int (:52, :61) the tail for one element is  x = y * s_ln (:63, float32),
@@ -98,15 +99,23 @@ IVIT_DEV int ln_cert4_pk(unsigned wu, float mean128, float hfactor, const float 
     return ln_cert_pack(o);
 }
 
+// y of one element from the integer the LayerNorm sees, literally (hfactor = factor / 2, as above)
+IVIT_DEV float ln_y(int x, int mean_int, float hfactor, float bias)
+{
+    const float dl = (float)(x - mean_int);
+    const float v = floorf(dl * hfactor);                              // :52
+    return v + bias;                                                   // :61
+}
+
 // One dword of (signed) int8 inputs, literally.
 IVIT_DEV int ln_literal4(int w, int mean_int, float hfactor, const float (&bias)[4], const float (&sl)[4], const double (&Mq)[4])
 {
     int o[4];
 #pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const float dl = (float)((int)(int8_t)(w >> (8 * c)) - mean_int);
-        const float v = floorf(dl * hfactor);                          // :52
-        o[c] = ln_literal(v + bias[c], sl[c], Mq[c]);                  // :61
-    }
+    for (int c = 0; c < 4; ++c) o[c] = ln_literal(ln_y((int)(int8_t)(w >> (8 * c)), mean_int, hfactor, bias[c]), sl[c], Mq[c]);
     return pack4(o[0], o[1], o[2], o[3]);
 }
+
+// The float-emitting end of the chain (ln_tokens.h: the token-feature kernels): what IVITIntLayerNorm itself returns, x = y * s_ln
+// (:63, one float32 product), without the QuantAct behind it.
+IVIT_DEV float ln_f32(float y, float s) { return y * s; }

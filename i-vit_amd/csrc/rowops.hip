@@ -812,6 +812,90 @@ __global__ __launch_bounds__(NT) void layernorm_i32_f32_kernel(LnArgs a)
     }
 }
 
+#include "ln_tokens.h"
+
+// One int8 row of the token-feature kernel (ln_tokens.h), a wave per row, lane d + 64 j on dword d: the statistics of
+// layernorm_i8_kernel (v_dot4 sums, the integer tie test of the natural-scale mean with torch_rowsum_phi behind it) and ln_chain.h's
+// element chain, ending in ln_f32 instead of the requantiser.  The row is read twice (the second time from the cache): nothing
+// is indexed at run time, so nothing spills at any C.
+template <bool COMPAT>
+struct LnTokRowI8 {
+    static constexpr int TAB = COMPAT ? 256 : 0;
+    const int8_t* x;
+    int C;
+    const float* bias_int;
+    const float* s_ln;
+    const int8_t* remap;
+    const float* phi;
+    const unsigned char* s_remap;
+    const float* s_phi;
+
+    IVIT_DEV void setup(int tid, unsigned char* t8, float* t32)
+    {
+        if constexpr (COMPAT) {
+            t8[tid] = (unsigned char)remap[tid];      // NT == 256
+            t32[tid] = phi[tid];
+            __syncthreads();
+        }
+        s_remap = t8;
+        s_phi = t32;
+    }
+
+    IVIT_DEV int seen(int w) const      // the dword as the LayerNorm sees it: k' = trunc(phi(q)) at a natural scale
+    {
+        if constexpr (COMPAT) {
+            const unsigned u = (unsigned)w ^ 0x80808080u;      // q + 128 per byte
+            return (int)((unsigned)s_remap[u & 255] | ((unsigned)s_remap[(u >> 8) & 255] << 8) | ((unsigned)s_remap[(u >> 16) & 255] << 16) |
+                         ((unsigned)s_remap[u >> 24] << 24));
+        } else {
+            return w;
+        }
+    }
+
+    template <class EMIT>
+    IVIT_DEV void row(int64_t xoff, int lane, EMIT emit) const
+    {
+        const int8_t* xrow = x + xoff;
+        const int* xr = reinterpret_cast<const int*>(xrow);
+        const int nd = C >> 2;
+        int sum = 0, sq = 0, sumq = 0;
+        for (int d = lane; d < nd; d += 64) {
+            int w = xr[d];
+            if constexpr (COMPAT) sumq = __builtin_amdgcn_sdot4(w, 0x01010101, sumq, false);
+            w = seen(w);
+            sum = __builtin_amdgcn_sdot4(w, 0x01010101, sum, false);
+            sq = __builtin_amdgcn_sdot4(w, w, sq, false);
+        }
+        sum = wave_reduce_sum_i32(sum);
+        sq = wave_reduce_sum_i32(sq);
+        int mean_int;
+        if constexpr (COMPAT) {
+            sumq = wave_reduce_sum_i32(sumq);
+            ln_mean(sumq, C, mean_int);      // = round(fl(sum phi / C)) unless the row is a tie (layernorm_i8_kernel)
+            int r2 = (2 * sumq - C) % (2 * C);
+            r2 = r2 < 0 ? r2 + 2 * C : r2;
+            if (__builtin_amdgcn_readfirstlane(r2 <= 2 || r2 >= 2 * C - 2)) {     // every lane holds the same sums
+                const float S = torch_rowsum_phi(xrow, C, s_phi, lane);
+                mean_int = (int)rintf(S / (float)C);     // ivit_modules.py:37
+            }
+        } else {
+            ln_mean(sum, C, mean_int);
+        }
+        const int var = sq - 2 * mean_int * sum + C * mean_int * mean_int;
+        const float hfactor = ln_factor((long long)var) * 0.5f;      // :45-52
+        for (int d = lane; d < nd; d += 64) {
+            const int w = seen(xr[d]);
+            const float4 b4 = *reinterpret_cast<const float4*>(bias_int + 4 * d);
+            const float4 s4 = *reinterpret_cast<const float4*>(s_ln + 4 * d);
+            const float bias[4] = {b4.x, b4.y, b4.z, b4.w}, sl[4] = {s4.x, s4.y, s4.z, s4.w};
+            float v[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) v[k] = ln_f32(ln_y(sx8(w, k), mean_int, hfactor, bias[k]), sl[k]);
+            emit.four(4 * d, make_float4(v[0], v[1], v[2], v[3]));
+        }
+    }
+};
+
 // ------------------------------------------------------------------------------------------------
 // ShiftGELU
 // ------------------------------------------------------------------------------------------------
@@ -1735,6 +1819,26 @@ IVIT_EXPORT int ivit_layernorm_i32_f32(const int32_t* x, int64_t ldx, int rows, 
 #endif
     hipLaunchKernelGGL(layernorm_i32_f32_kernel, dim3(grid_for_rows(rows)), dim3(NT), 0, ivit_stream(stream), a);
     IVIT_CHECK_LAUNCH("ivit_layernorm_i32_f32");
+}
+
+IVIT_EXPORT int ivit_layernorm_i8_f32(const int8_t* x, int64_t ldx, int B, int T_all, int t0, int T, int C, const float* bias_int,
+                                      const float* s_ln, const int8_t* remap, const float* phi, float* out, int64_t ldo, int flags,
+                                      ivit_stream_t stream)
+{
+    const char* who = "ivit_layernorm_i8_f32";
+    const bool compat = remap != nullptr;
+    LnTok o;
+    size_t lds;
+    IVIT_REQUIRE((remap != nullptr) == (phi != nullptr), "%s: remap and phi come together", who);
+    if (const int rc = ln_tok_check(who, x, 1, ldx, B, T_all, t0, T, C, bias_int, s_ln, out, ldo, flags, compat ? 256 * 5 : 0, &o, &lds))
+        return rc;
+    // the preconditions of ivit_layernorm_i8 / ivit_layernorm_i8_compat
+    IVIT_LN_TOK_UNSUPPORTED(C % 4 == 0 && (!compat || (C >= 32 && C % 8 == 0)), "%s: C=%d unsupported", who, C);
+    IVIT_LN_TOK_UNSUPPORTED(ldx % 4 == 0 && (uintptr_t)x % 4 == 0, "%s: rows must be 4-byte aligned", who);
+    IVIT_LN_TOK_UNSUPPORTED((uintptr_t)bias_int % 16 == 0 && (uintptr_t)s_ln % 16 == 0 && (uintptr_t)phi % 4 == 0,
+                            "%s: per-channel tables must be 16-byte aligned", who);
+    if (compat) return ln_tok_launch(who, LnTokRowI8<true>{x, C, bias_int, s_ln, remap, phi, nullptr, nullptr}, o, lds, stream);
+    return ln_tok_launch(who, LnTokRowI8<false>{x, C, bias_int, s_ln, nullptr, nullptr, nullptr, nullptr}, o, lds, stream);
 }
 
 IVIT_EXPORT int ivit_shiftgelu_i8(const int8_t* x, int64_t ldx, int rows, int L, float s, uint32_t m, int32_t e,

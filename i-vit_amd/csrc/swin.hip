@@ -124,35 +124,61 @@ struct Ln16Args {
 constexpr unsigned LN16_WRAP_FROM = 46341u;
 IVIT_DEV long long ln16_square(int d) { return (long long)(int)((unsigned)d * (unsigned)d); }
 
-__global__ __launch_bounds__(NT) void layernorm_i16_i8_kernel(Ln16Args a)
+// One 16-bit row literally, a wave per row, from the integers to y = floor((x - mean) * factor / 2) + bias_int (:36-61); every
+// element goes to tail(c, y): the QuantAct of the int8-emitting kernels below, the float product of the token-feature kernel
+// (ln_tokens.h).  phi: nullptr_t for integers (a power-of-two scale), else phi(c) = fl(fl(q * s) / s), the float the reference's
+// operator sees at a natural scale -- its mean is the float32 sum over the phi values in torch's CPU reduction order (rowsum.h;
+// outer > 0: the outer-reduction order for the row `row`), its integers are `.to(int32)` truncations.
+template <class PHI, class TAIL>
+IVIT_DEV void ln16_row(const int16_t* xr, int C, PHI phi, int outer, int row, const float* bias_int, int lane, TAIL tail)
 {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int C = a.C;
-    for (int row = blockIdx.x * WPB + wave; row < a.rows; row += gridDim.x * WPB) {
-        const int16_t* xr = a.x + (int64_t)row * C;
+    constexpr bool INTEGERS = std::is_same<PHI, decltype(nullptr)>::value;
+    auto seen = [&](int c) -> int {
+        if constexpr (INTEGERS) return xr[c];
+        else return (int)truncf(phi(c));                                                   // :38
+    };
+    int mean_int;
+    if constexpr (INTEGERS) {
         int sum = 0;  // |sum| < 2^31 for C <= 4096
         for (int c = lane; c < C; c += 64) sum += xr[c];
         sum = wave_reduce_sum_i32(sum);
         float fsum = (float)sum;                                      // :37 exact in any order below 2^24 ...
         if (__builtin_amdgcn_readfirstlane(abs(sum) >= (1 << 24)))    // ... from there on torch's order of additions (rowsum.h)
             fsum = torch_rowsum([&](int c) { return (float)xr[c]; }, C, lane);
-        const int mean_int = (int)rintf(fsum / (float)C);
-        long long var = 0;
-        for (int c = lane; c < C; c += 64) var += ln16_square(xr[c] - mean_int);      // :41-42
-        const float t = ln_newton10_literal((float)(long long)lanes_allsum_u64<64>(var));   // :45-49
-        const float factor = floorf((1.0f / t) * 2147483648.0f);     // :51
+        mean_int = (int)rintf(fsum / (float)C);
+    } else {
+        const float S = outer ? torch_outer_rowsum(phi, C, row % outer >= (outer & ~31)) : torch_rowsum(phi, C, lane);
+        mean_int = (int)rintf(S / (float)C);                         // :37
+    }
+    long long var = 0;
+    for (int c = lane; c < C; c += 64) var += ln16_square(seen(c) - mean_int);            // :38-42
+    const float t = ln_newton10_literal((float)(long long)lanes_allsum_u64<64>(var));       // :45-49
+    const float factor = floorf((1.0f / t) * 2147483648.0f);         // :51
+    for (int c = lane; c < C; c += 64) {
+        float dl = (float)(seen(c) - mean_int);
+        float v = floorf((dl * factor) * 0.5f);                       // :52
+        tail(c, v + bias_int[c]);                                     // :61
+    }
+}
+
+// the QuantAct behind the LayerNorm for one element, literally
+IVIT_DEV int8_t ln16_quantact(const Ln16Args& a, int c, float y)
+{
+    float s = a.s_ln[c];
+    float x = y * s;                                          // :63
+    float z = rintf(x / s);                                   // quant_utils.py:220 (correctly rounded quotient)
+    double p = (double)z * dyadic_mult(a.m[c], a.e[c]);       // :229
+    double tt = p + IVIT_MAGIC;                               // :230
+    return (int8_t)clamp_i32((int)(unsigned)__double_as_longlong(tt), -128, 127);
+}
+
+__global__ __launch_bounds__(NT) void layernorm_i16_i8_kernel(Ln16Args a)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int C = a.C;
+    for (int row = blockIdx.x * WPB + wave; row < a.rows; row += gridDim.x * WPB) {
         int8_t* orow = a.out + win_row(a.map, row) * a.ldo;
-        for (int c = lane; c < C; c += 64) {
-            float dl = (float)(xr[c] - mean_int);
-            float v = floorf((dl * factor) * 0.5f);                   // :52
-            float y = v + a.bias_int[c];                              // :61
-            float s = a.s_ln[c];
-            float x = y * s;                                          // :63
-            float z = rintf(x / s);                                   // quant_utils.py:220 (correctly rounded quotient)
-            double p = (double)z * dyadic_mult(a.m[c], a.e[c]);       // :229
-            double tt = p + IVIT_MAGIC;                               // :230
-            orow[c] = (int8_t)clamp_i32((int)(unsigned)__double_as_longlong(tt), -128, 127);
-        }
+        ln16_row(a.x + (int64_t)row * C, C, nullptr, 0, row, a.bias_int, lane, [&](int c, float y) { orow[c] = ln16_quantact(a, c, y); });
     }
 }
 
@@ -173,28 +199,34 @@ __global__ __launch_bounds__(NT) void layernorm_i16_i8_literal_kernel(Ln16LitArg
     for (int row = blockIdx.x * WPB + wave; row < a.rows; row += gridDim.x * WPB) {
         const int16_t* xr = a.x + (int64_t)row * C;
         auto xint = [&](int c) { return ((float)xr[c] * s_in) / s_in; };       // :36 on the float view q * s
-        const float S = a.outer ? torch_outer_rowsum(xint, C, row % a.outer >= (a.outer & ~31)) : torch_rowsum(xint, C, lane);
-        const int mean_int = (int)rintf(S / (float)C);                         // :37
-        long long var = 0;
-        for (int c = lane; c < C; c += 64) {
-            var += ln16_square((int)truncf(xint(c)) - mean_int);               // :38-42
-        }
-        const float t = ln_newton10_literal((float)(long long)lanes_allsum_u64<64>(var));   // :45-49
-        const float factor = floorf((1.0f / t) * 2147483648.0f);               // :51
         int8_t* orow = a.out + win_row(a.map, row) * a.ldo;
-        for (int c = lane; c < C; c += 64) {
-            float dl = (float)((int)truncf(xint(c)) - mean_int);
-            float v = floorf((dl * factor) * 0.5f);                             // :52
-            float y = v + a.bias_int[c];                                        // :61
-            float s = a.s_ln[c];
-            float x = y * s;                                                    // :63
-            float z = rintf(x / s);                                             // quant_utils.py:220
-            double p = (double)z * dyadic_mult(a.m[c], a.e[c]);                 // :229
-            double tt = p + IVIT_MAGIC;                                         // :230
-            orow[c] = (int8_t)clamp_i32((int)(unsigned)__double_as_longlong(tt), -128, 127);
-        }
+        ln16_row(xr, C, xint, a.outer, row, a.bias_int, lane, [&](int c, float y) { orow[c] = ln16_quantact(a, c, y); });
     }
 }
+
+#include "ln_tokens.h"
+
+// one int16 row of the token-feature kernel: ln16_row with the float product as its tail.  s_in == 0: the integers themselves.
+template <bool COMPAT, bool FASTDIV>
+struct LnTokRowI16 {
+    static constexpr int TAB = 0;
+    const int16_t* x;
+    int C;
+    float s_in, r_in;
+    const float* bias_int;
+    const float* s_ln;
+
+    IVIT_DEV void setup(int, unsigned char*, float*) {}
+
+    template <class EMIT>
+    IVIT_DEV void row(int64_t xoff, int lane, EMIT emit) const
+    {
+        const int16_t* xr = x + xoff;
+        auto tail = [&](int c, float y) { emit(c, ln_f32(y, s_ln[c])); };
+        if constexpr (COMPAT) ln16_row(xr, C, [&](int c) { return ln_tok_phi16<FASTDIV>(xr[c], s_in, r_in); }, 0, 0, bias_int, lane, tail);
+        else ln16_row(xr, C, nullptr, 0, 0, bias_int, lane, tail);
+    }
+};
 
 // Round 4: the per-channel constants (bias, float32 bracket (lo, hi) of the QuantAct multiplier: the certificate of
 // ln_chain.h) of the tiled 16-bit kernels are derived ONCE PER WORKGROUP into LDS -- one or two channels per
@@ -1267,6 +1299,23 @@ IVIT_EXPORT int ivit_layernorm_i16_i8_compat(const int16_t* x, int rows, int C, 
     Ln16LitArgs a{b, s_in};
     hipLaunchKernelGGL(layernorm_i16_i8_literal_kernel, dim3(grid_for_rows(rows)), dim3(NT), 0, st, a);
     IVIT_CHECK_LAUNCH("ivit_layernorm_i16_i8_compat");
+}
+
+IVIT_EXPORT int ivit_layernorm_i16_f32(const int16_t* x, int64_t ldx, int B, int T_all, int t0, int T, int C, float s_in,
+                                       const float* bias_int, const float* s_ln, float* out, int64_t ldo, int flags,
+                                       ivit_stream_t stream)
+{
+    const char* who = "ivit_layernorm_i16_f32";
+    const bool fast = (flags & IVIT_LN_F32_FAST_DIV) != 0;
+    LnTok o;
+    size_t lds;
+    IVIT_REQUIRE(s_in >= 0.0f && (s_in > 0.0f || !fast), "%s: s_in is 0 (integers) or a positive scale; IVIT_LN_F32_FAST_DIV needs a scale", who);
+    if (const int rc = ln_tok_check(who, x, 2, ldx, B, T_all, t0, T, C, bias_int, s_ln, out, ldo, flags & ~IVIT_LN_F32_FAST_DIV, 0, &o, &lds))
+        return rc;
+    const float r_in = s_in > 0.0f ? 1.0f / s_in : 0.0f;
+    if (s_in == 0.0f) return ln_tok_launch(who, LnTokRowI16<false, false>{x, C, s_in, r_in, bias_int, s_ln}, o, lds, stream);
+    if (fast) return ln_tok_launch(who, LnTokRowI16<true, true>{x, C, s_in, r_in, bias_int, s_ln}, o, lds, stream);
+    return ln_tok_launch(who, LnTokRowI16<true, false>{x, C, s_in, r_in, bias_int, s_ln}, o, lds, stream);
 }
 
 IVIT_EXPORT int ivit_patch_merge_i16(const int16_t* x, int16_t* out, int batch, int H, int W, int C, ivit_stream_t stream)

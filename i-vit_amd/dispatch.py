@@ -180,6 +180,25 @@ class EngineDispatch:
         return {n: (float(m.x_min.reshape(-1)[0]), float(m.x_max.reshape(-1)[0]))
                 for n, m in self.named_modules() if isinstance(m, QuantAct)}
 
+    def _hooked_outputs(self, x, modules):
+        """forward_tokens off the engine: the modules are called one by one as the reference's forward calls them (the whole forward,
+        then the head where there is one), with a forward hook on each of modules = {key: module} -> {key: what it returned};
+        the hooks are removed in any case"""
+        got, handles = {}, []
+        for key, mod in modules.items():
+            handles.append(mod.register_forward_hook(lambda m, a, out, key=key: got.__setitem__(key, out)))
+        try:
+            with torch.no_grad():
+                if not self.is_frozen():
+                    self.invalidate_engine()
+                f, s = self.forward_features(x)
+                if self.num_classes > 0:
+                    self.head(f, s)
+        finally:
+            for h in handles:
+                h.remove()
+        return got
+
     def _hooked_intermediates(self, x, sites, integers):
         """forward_intermediates off the engine: the modules are called one by one as the reference's forward calls them, with a
         forward hook on each selected module.  sites = {key: (module, its name, the QuantAct whose output it returns, t0, (H, W))};

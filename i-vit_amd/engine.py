@@ -28,7 +28,7 @@ import torch
 
 from . import _lib, gemm_forms
 from .engine_common import (EngineBase, _np, attention, attention_probs, attention_spec, block_copy, frag_copy, intermediate_indices,
-                            layernorm, tokens_to_nchw)
+                            layernorm, layernorm_f32, ln_spec, token_format, tokens_to_nchw)
 from .prepare import dyadic, dyadic1, f32, pad_head, quant_sym, requant_host
 from .topk import TOPK_MAX
 
@@ -105,14 +105,16 @@ class IntViTEngine(EngineBase):
             m, e = lp.requant_to(s_out)
             return dict(W=dev(lp.W8), b=dev(lp.b32), m=dev(m.view(np.int32)), e=dev(e), K=lp.K, N=lp.W8.shape[0])
 
+        def ln_shift(prefix):
+            if family != "ibert":
+                return None
+            try:
+                return float(np.asarray(source.tensor(prefix + ".shift")).reshape(-1)[0])
+            except KeyError:
+                return 0.0
+
         def ln_dev(prefix, s_out, s_in):
-            shift = None
-            if family == "ibert":
-                try:
-                    shift = float(np.asarray(source.tensor(prefix + ".shift")).reshape(-1)[0])
-                except KeyError:
-                    shift = 0.0
-            return self._ln_spec(source.layernorm(prefix, s_out), s_in, 16 if sb == 16 else 8, shift, self.int_sqrt)   # payload width
+            return self._ln_spec(source.layernorm(prefix, s_out), s_in, 16 if sb == 16 else 8, ln_shift(prefix), self.int_sqrt)   # payload width
 
         def ranges_of(name):
             if ranges is None or name not in ranges:
@@ -183,6 +185,11 @@ class IntViTEngine(EngineBase):
         # ---- tail
         s_q2 = s("qact2")
         self.ln_f = ln_dev("norm", s_q2, s_x)
+        # forward_tokens: the final norm on the stream behind ANY block -- its host parameters and, for "ibert", its frozen shift
+        # buffer; the device constants are derived per block from that block's output scale when first asked for (_ln_tokens)
+        self._norm_lp = source.layernorm("norm", s_q2)
+        self._norm_shift = ln_shift("norm")
+        self._ln_tok = {depth - 1: self.ln_f}
         self.s_feat = float(s_q2)     # the float32 act_scaling_factor of qact2 (forward_features)
         try:
             head = source.linear("head", s_q2)
@@ -442,14 +449,74 @@ class IntViTEngine(EngineBase):
         self._forward(images, feats=feats, stop=max(idx) if stop_early else None)
         return feats, {i: self.blocks[i]["s_out"] for i in idx}
 
+    def _ln_tokens(self, i):
+        """the constants of the final norm on the output of block i (ln_spec at that block's output scale), cached per index"""
+        if i not in self._ln_tok:
+            self._ln_tok[i] = ln_spec(self._norm_lp, self._upload, self.blocks[i]["s_out"], 16 if self.stream_bits == 16 else 8,
+                                      self._norm_shift, self.int_sqrt)
+        return self._ln_tok[i]
+
+    def forward_tokens(self, images: torch.Tensor, indices=None, fmt: str = "NLC", prefix: bool = True, integers: bool = False):
+        """The final-normed token sequence behind the selected blocks -> (tokens, prefix_tokens, scale): for block index i what
+        model.norm returns when called on the pair blocks[i] returns -- for i = D - 1 the reference's own tensor (vit_quant.py:302
+        before its [:, 0]), for i < D - 1 timm's norm=True.  tokens = {i: float32 [B, Gh * Gw, C]} (fmt "NLC") or {i: float32
+        [B, C, Gh, Gw]} ("NCHW"), the patch tokens; prefix_tokens = {i: float32 [B, 1, C]}, the class token (prefix=False: {});
+        scale: float32 [C], the per-channel scaling factor the module returns beside it (the same for every index).
+        indices: block indices (None: the last block); ValueError for one out of range or repeated, before anything is launched.
+        The ordinary eager forward runs -- its logits stay in the workspace as after forward() -- and behind the second residual
+        GEMM of each selected block one launch (engine_common.layernorm_f32: the LayerNorm straight from the integer stream to
+        float32, no float intermediate) writes the tokens, under NCHW one more small one the class rows.  A headless engine stops
+        behind the last selected block.  Not part of taps, of the graph replays or of cls_tail.
+        integers=True (the last block alone: ValueError otherwise): the tensor qact2 gives for the whole normed sequence -- int8
+        tokens and class rows in the same shapes, scale = the float s_feat; the class row is forward_features(integers=True) bit
+        for bit, the rows can go into a knn.FeatureBank."""
+        token_format(fmt)
+        idx = [self.D - 1] if indices is None else intermediate_indices(indices, self.D, "block")
+        if integers and idx != [self.D - 1]:
+            raise ValueError(f"integers=True: qact2 belongs to the last block's norm; indices must be ({self.D - 1},) or None, not {idx}")
+        B, C, T, NP = images.shape[0], self.C, self.T, self.NP
+        tokens, prefixes = {}, {}
+
+        def emit(i, x, st):
+            if integers:
+                q = torch.empty(B * T, C, dtype=torch.int8, device=self.dev)
+                layernorm(self.ln_f, x, C, B * T, C, q, C, st, blocks=False)
+                q = q.view(B, T, C)
+                if prefix:
+                    prefixes[i] = q[:, :1]
+                if fmt == "NLC":
+                    tokens[i] = q[:, 1:]
+                else:
+                    tokens[i] = torch.empty(B, C, *self.grid, dtype=torch.int8, device=self.dev)
+                    tokens_to_nchw(q, C, B, T, 1, NP, C, 1.0, tokens[i], st)
+                return
+            ln = self._ln_tokens(i)
+            if fmt == "NLC":
+                t0 = 0 if prefix else 1
+                full = torch.empty(B, T - t0, C, dtype=torch.float32, device=self.dev)
+                layernorm_f32(ln, x, C, B, T, t0, T - t0, C, full, C, st)
+                tokens[i] = full[:, 1 - t0:]
+                if prefix:
+                    prefixes[i] = full[:, :1]
+                return
+            tokens[i] = torch.empty(B, C, *self.grid, dtype=torch.float32, device=self.dev)
+            layernorm_f32(ln, x, C, B, T, 1, NP, C, tokens[i], NP, st, fmt="NCHW")
+            if prefix:
+                prefixes[i] = torch.empty(B, 1, C, dtype=torch.float32, device=self.dev)
+                layernorm_f32(ln, x, C, B, T, 0, 1, C, prefixes[i], C, st)
+
+        self._forward(images, toks={i: emit for i in idx}, stop=max(idx) if self.head is None else None)
+        return {i: tokens[i] for i in idx}, {i: prefixes[i] for i in idx if prefix}, (self.s_feat if integers else self.ln_f["s"])
+
     def _forward(self, images: torch.Tensor, taps: dict | None = None, topk=None, cls_tail: bool = False, maps: dict | None = None,
-                 feats: dict | None = None, stop=None):
+                 feats: dict | None = None, stop=None, toks: dict | None = None):
         """forward; topk = (k, targets, hits): the classifier launch is the top-k selection (forward_topk).
         stop: None the whole forward; "features": return behind the final LayerNorm (forward_features: no head GEMM, no classifier
         launch); a block index: return behind that block (forward_intermediates_early).  A headless engine needs one.
         cls_tail: the last block through _cls_block (cls_tail_ok engines, no taps).
         maps: {block index: uint8 [B, H, R, T]} to fill with the softmax probabilities of those blocks (attention_maps).
         feats: {block index: [B, C, Gh, Gw]} to fill with the stream behind those blocks, class token dropped (forward_intermediates).
+        toks: {block index: emit(index, stream, hip stream)} called behind those blocks (forward_tokens).
         stream_bits = 4: the 8-bit dataflow; the six stream QuantActs clamp to [-8, 7] (the `_bits` entries), attention is the
         "wide" form with softmax_bits.
         stream_bits = 16: the same dataflow with an int16 residual stream.  The patch GEMM, the embedding assembly and the
@@ -545,6 +612,8 @@ class IntViTEngine(EngineBase):
             tap(p + "qact4", x, (B, T, C))
             if feats is not None and i in feats:
                 tokens_to_nchw(x, C, B, T, 1, T - 1, C, blk["s_out"], feats[i], st)
+            if toks is not None and i in toks:
+                toks[i](i, x, st)
             if stop == i:      # (never "features": block indices are ints)
                 return None
         # final LayerNorm is row-wise and only the cls row is consumed (vit_quant.py:302-304); the int16 kernels want dense rows

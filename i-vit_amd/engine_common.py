@@ -1,6 +1,6 @@
 """Host code shared by the fused engines (engine.IntViTEngine, swin_engine.IntSwinEngine) and the module path
 (quantization_utils/lazy.py), written once per operator: the GEMM weight copies (block_copy, frag_copy); the LayerNorm constants
-and their launcher (ln_spec, layernorm); the ViT attention constants and their launchers (attention_spec, attention,
+and their launchers (ln_spec, layernorm; layernorm_f32: the float32 output of the same kinds, forward_tokens); the ViT attention constants and their launchers (attention_spec, attention,
 attention_probs: the probabilities alone); the GELU
 table of both families (gelu_lut); the feature-map launcher and its index check (tokens_to_nchw, intermediate_indices); the
 embedding's dequantisation (dequant_rows); what the two engines share as classes (EngineBase: the headless refusal and
@@ -108,6 +108,42 @@ def layernorm(ln, x, ldx, rows, C, out, ldo, st, blocks=None, H=0, W=0, ws=0, sh
                   ldo, H, W, ws, shift, st)
     elif kind == "i16":
         _lib.call("ivit_layernorm_i16_i8", p(x), rows, C, bias, s, m, e, p(out), ldo, H, W, ws, shift, st)
+    else:
+        raise ValueError(f"LayerNorm kind {kind!r}")
+
+
+LN_F32_CHANNEL_MAJOR, LN_F32_FAST_DIV = 1, 2     # IVIT_LN_F32_* of include/ivit_hip.h
+TOKEN_FORMATS = ("NLC", "NCHW")
+
+
+def token_format(fmt):
+    """forward_tokens' `fmt`, checked: ValueError for anything but "NLC" / "NCHW" """
+    if fmt not in TOKEN_FORMATS:
+        raise ValueError(f"fmt={fmt!r}: 'NLC' (tokens as rows) or 'NCHW' (channels first, the patch grid)")
+    return fmt
+
+
+def layernorm_f32(ln, x, ldx, B, T_all, t0, T, C, out, ldo, st, fmt="NLC"):
+    """The LayerNorm's own float32 output (the tensor the module returns, y_int * s_ln) for every kind of ln_spec, straight from
+    the integer stream x (element (b, t, c) at (b * T_all + t) * ldx + c), tokens t0 .. t0 + T - 1 of each of the B images.
+    fmt "NLC": out[(b * T + t) * ldo + c]; "NCHW": out[(b * C + c) * ldo + t] (ldo = T: dense [B, C, T]).  One launch
+    (ivit_layernorm_i8_f32 / _i16_f32, ivit_ibert_layernorm_i8_f32 / _i16_f32: csrc/ln_tokens.h)."""
+    kind, p = ln["kind"], _lib.ptr
+    flags = LN_F32_CHANNEL_MAJOR if token_format(fmt) == "NCHW" else 0
+    sel, bias, s = (p(x), ldx, B, T_all, t0, T, C), p(ln["bias"]), p(ln["s"])
+    if kind == "i8":
+        _lib.call("ivit_layernorm_i8_f32", *sel, bias, s, None, None, p(out), ldo, flags, st)
+    elif kind == "i8_compat":
+        _lib.call("ivit_layernorm_i8_f32", *sel, bias, s, p(ln["remap"]), p(ln["phi"]), p(out), ldo, flags, st)
+    elif kind == "i16":
+        _lib.call("ivit_layernorm_i16_f32", *sel, 0.0, bias, s, p(out), ldo, flags, st)
+    elif kind == "i16_compat":
+        _lib.call("ivit_layernorm_i16_f32", *sel, ln["s_in"], bias, s, p(out), ldo, flags | (LN_F32_FAST_DIV if ln["fast_div"] else 0), st)
+    elif kind == "ibert_i8":
+        _lib.call("ivit_ibert_layernorm_i8_f32", *sel, ln["s_in"], bias, s, ln["shift_pow2"], p(out), ldo, flags | ln["flags"], st)
+    elif kind == "ibert_i16":
+        _lib.call("ivit_ibert_layernorm_i16_f32", *sel, ln["s_in"], bias, s, ln["shift_pow2"], p(out), ldo,
+                  flags | ln["flags"] | (LN_F32_FAST_DIV if ln["fast_div"] else 0), st)
     else:
         raise ValueError(f"LayerNorm kind {kind!r}")
 

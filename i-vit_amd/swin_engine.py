@@ -28,7 +28,8 @@ import numpy as np
 import torch
 
 from . import _lib, gemm_forms
-from .engine_common import EngineBase, _np, block_copy, frag_copy, intermediate_indices, layernorm, tokens_to_nchw
+from .engine_common import (EngineBase, _np, block_copy, frag_copy, intermediate_indices, layernorm, layernorm_f32, token_format,
+                            tokens_to_nchw)
 from .prepare import (LayerNormParams, LinearParams, dyadic, dyadic1, f32, ibert_saturated_exp, ibert_window_mask_ok, pad_head,
                       phi_is_identity, phi_table, quant_sym, requant_host, shiftexp_band, sym_scale, window_shiftexp_band)
 from .topk import TOPK_MAX
@@ -603,8 +604,33 @@ class IntSwinEngine(EngineBase):
         self._forward(images, maps=maps, stop="features" if self.head is None else None)      # (a headless engine ends behind the pooling)
         return maps, 2.0 ** -7
 
+    def forward_tokens(self, images: torch.Tensor, fmt: str = "NLC", integers: bool = False):
+        """The final-normed token sequence of the last stage -> (tokens, scale).  Float form: the tensor model.norm returns
+        (swin_quant.py:551), float32 [B, L, C_last] (fmt "NLC") or [B, C_last, H, W] ("NCHW"), with the float32 [C_last] per-channel
+        scaling factor it returns beside it -- one launch (engine_common.layernorm_f32) from the 16-bit stream, both operator
+        families.  integers=True: the int8 tensor qact2 gives (:552), which the engine computes in front of its pooling, in the same
+        shapes, with the float scale of qact2.  The ordinary eager forward runs: pooled features and logits of the same call stay as
+        forward_features / forward leave them (a headless engine stops behind the pooling).  There is no prefix token.  Not part of
+        taps or of the graph replays."""
+        token_format(fmt)
+        B, C, T = images.shape[0], self.C_last, self.T_last
+        hw = (self.stages[-1]["H"], self.stages[-1]["W"])
+        dt = torch.int8 if integers else torch.float32
+        out = torch.empty((B, T, C) if fmt == "NLC" else (B, C, *hw), dtype=dt, device=self.dev)
+
+        def emit(x, q, st):
+            if not integers:
+                layernorm_f32(self.ln_f, x, C, B, T, 0, T, C, out, C if fmt == "NLC" else T, st, fmt=fmt)
+            elif fmt == "NLC":
+                out.copy_(q.view(-1)[: B * T * C].view(B, T, C))
+            else:
+                tokens_to_nchw(q, C, B, T, 0, T, C, 1.0, out, st)
+
+        self._forward(images, toks=emit, stop="features" if self.head is None else None)
+        return out, (self.s_pool if integers else self.ln_f["s"])
+
     def _forward(self, images: torch.Tensor, taps: dict | None = None, topk=None, feats: dict | None = None,
-                 maps: dict | None = None, stop=None):
+                 maps: dict | None = None, stop=None, toks=None):
         """forward; topk = (k, targets, hits): the classifier launch is the top-k selection (forward_topk).
         stop: None the whole forward; "features": return behind the pooling launch (forward_features); a stage index: return behind
         that stage's last block (forward_intermediates_early).  A headless engine needs one.
@@ -754,6 +780,8 @@ class IntSwinEngine(EngineBase):
         C, T = self.C_last, self.T_last
         layernorm(self.ln_f, x, C, B * T, C, ws["hN"], C, st)
         tap("qact2", ws["hN"], B * T, C)
+        if toks is not None:
+            toks(x, ws["hN"], st)
         if self.pool_literal:
             _lib.call("ivit_avgpool_requant_i8_literal", _lib.ptr(ws["hN"]), _lib.ptr(ws["pooled"]), B, T, C, self.s_pool,
                       self.pool_me[0], self.pool_me[1], st)

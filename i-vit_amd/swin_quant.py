@@ -427,6 +427,30 @@ class SwinTransformer(EngineDispatch, ModuleGraph, nn.Module):
                 h.remove()
         return {key: maps[key] for key in sel}, 2.0 ** -7
 
+    def forward_tokens(self, x, fmt="NLC", integers=False, prefix=False):
+        """The final-normed token sequence of the last stage -> (tokens, scale): what self.norm returns in forward_features, float32
+        [B, L, C] (fmt "NLC") or [B, C, H, W] ("NCHW"), with the float32 [C] scaling factor it returns beside it; integers=True: the
+        int8 tensor self.qact2 gives, with its float scale.  Swin has no prefix token: prefix=True is a ValueError.
+        Where takes_engine_for_features(x) holds this is IntSwinEngine.forward_tokens: the eager engine forward plus one launch.
+        Otherwise (an I-BERT model included) the modules are called one by one as the reference's forward calls them, with a forward
+        hook on self.norm / self.qact2: the same tensors bit for bit, at the module path's speed."""
+        from .engine_common import token_format
+        token_format(fmt)
+        if prefix:
+            raise ValueError("prefix=True: Swin has no prefix (class) token")
+        if self.takes_engine_for_features(x):
+            return self.engine(x.shape[0]).forward_tokens(x.contiguous().float(), fmt, integers)
+        y, scale = self._hooked_outputs(x, {0: self.qact2 if integers else self.norm})[0]
+        scale = scale.reshape(-1)
+        if integers:
+            y = torch.round(y / scale).to(torch.int8)
+        if fmt == "NCHW":
+            B, L, C = y.shape
+            h, w = self.patch_embed.grid_size
+            f = 2 ** (self.num_layers - 1)
+            y = y.permute(0, 2, 1).reshape(B, C, h // f, w // f).contiguous()
+        return y, (float(scale[0]) if integers else scale)
+
     def forward_intermediates_early(self, x, indices=None, integers=False):
         """forward_intermediates with an early stop: where the fused engine is taken it launches nothing behind the last selected
         stage (IntSwinEngine.forward_intermediates_early: the same maps and scales; its workspace logits are then stale).  The

@@ -316,6 +316,40 @@ class VisionTransformer(EngineDispatch, ModuleGraph, nn.Module):
                 h.remove()
         return {i: maps[i] for i in layers}, 2.0 ** -7
 
+    def forward_tokens(self, x, indices=None, fmt="NLC", prefix=True, integers=False):
+        """The final-normed token sequence behind the selected blocks -> (tokens, prefix_tokens, scale): for block index i what
+        self.norm returns when called on the pair blocks[i] returns (i = depth - 1: the tensor of forward_features before its
+        [:, 0]; i < depth - 1: timm's norm=True).  tokens = {i: float32 [B, Gh * Gw, C]} (fmt "NLC") or {i: [B, C, Gh, Gw]}
+        ("NCHW"); prefix_tokens = {i: float32 [B, 1, C]}, the class token ({} with prefix=False); scale: the float32 [C] scaling
+        factor self.norm returns.  indices: block indices (None: the last block); ValueError for one out of range or repeated.
+        integers=True (the last block alone): the int8 tensor self.qact2 gives for the whole sequence, with its float scale.
+        Where takes_engine_for_features(x) holds this is IntViTEngine.forward_tokens: the eager engine forward plus one launch per
+        selected block.  Otherwise the modules are called one by one as the reference's forward calls them, with forward hooks on
+        the selected blocks, and self.norm is called on each captured pair: the same tensors bit for bit, at the module path's
+        speed."""
+        from .engine_common import intermediate_indices, token_format
+        token_format(fmt)
+        idx = [self.depth - 1] if indices is None else intermediate_indices(indices, self.depth, "block")
+        if integers and idx != [self.depth - 1]:
+            raise ValueError(f"integers=True: qact2 belongs to the last block's norm; indices must be ({self.depth - 1},) or None, not {idx}")
+        if self.takes_engine_for_features(x):
+            return self.engine(x.shape[0]).forward_tokens(x.contiguous().float(), idx, fmt, prefix, integers)
+        got = self._hooked_outputs(x, {i: self.blocks[i] for i in idx})
+        grid = tuple(self.patch_embed.grid_size)
+        tokens, prefixes, scale = {}, {}, None
+        with torch.no_grad():
+            for i in idx:
+                y, scale = self.norm(*got[i])
+                if integers:
+                    y, scale = self.qact2(y, scale)
+                    y = torch.round(y / scale).to(torch.int8)
+                B, _, C = y.shape
+                tokens[i] = y[:, 1:] if fmt == "NLC" else y[:, 1:].permute(0, 2, 1).reshape(B, C, *grid).contiguous()
+                if prefix:
+                    prefixes[i] = y[:, :1]
+        scale = scale.reshape(-1)
+        return tokens, prefixes, (float(scale[0]) if integers else scale)
+
     def forward_intermediates_early(self, x, indices=None, integers=False):
         """forward_intermediates with an early stop: where the fused engine is taken it launches nothing behind the last selected
         block (IntViTEngine.forward_intermediates_early: the same maps and scales; its workspace logits are then stale).  The

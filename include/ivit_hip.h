@@ -430,6 +430,34 @@ int ivit_layernorm_i8_compat(const int8_t* x, int64_t ldx, int rows, int C, cons
 int ivit_layernorm_i32_f32(const int32_t* x, int64_t ldx, int rows, int C, const float* bias_int,
                            const float* s_ln, float* out, int64_t ldo, ivit_stream_t stream);
 
+/* ---- Token features: the LayerNorm's own float32 output from the integer stream -----------------
+ * The tensor the module returns, out = fl(y_int * s_ln[c]) (ivit_modules.py:63; ibert_modules.py:153 for the I-BERT entries
+ * further down), computed straight from the int8 / int16 rows the engines carry: the statistics and the element chain of the
+ * int8-emitting entries above, without the QuantAct behind them (csrc/ln_tokens.h).  Four entries share the row selection and
+ * the output forms:
+ *   rows     token-major with a leading dimension, as ivit_tokens_to_nchw_* addresses them: row (b, t) of the selection
+ *            (B, T_all, t0, T) is read at (b * T_all + t0 + t) * ldx.  t0 = 1 skips a class token, (t0, T) = (0, 1) takes it alone.
+ *   flags    0: rows, out[(b * T + t) * ldo + c], ldo >= C (NLC).  IVIT_LN_F32_CHANNEL_MAJOR: out[(b * C + c) * ldo + t], ldo >= T;
+ *            ldo == T is the dense [B, C, T] tensor (NCHW for a Gh x Gw grid), written in one launch through LDS in runs of up to
+ *            16 consecutive tokens per channel, no float intermediate in memory.
+ * Preconditions of all four: B, T, C >= 1, 0 <= t0, t0 + T <= T_all, ldx >= C, pointers aligned to their elements
+ * (IVIT_ERR_INVALID, as a NULL operand or an unknown flag); C <= 4096 (IVIT_ERR_UNSUPPORTED).  Nothing is launched on an error.
+ *
+ * ivit_layernorm_i8_f32: int8 rows.  remap == phi == NULL: the integers (ivit_layernorm_i8); both given: the natural-scale form
+ * of ivit_layernorm_i8_compat, tie rows in the inner reduction order.  Preconditions of those entries, IVIT_ERR_UNSUPPORTED:
+ * C % 4 == 0 (with tables: C % 8 == 0, C >= 32), ldx % 4 == 0 and x 4-byte aligned, bias_int and s_ln 16-byte aligned. */
+#define IVIT_LN_F32_CHANNEL_MAJOR 1
+#define IVIT_LN_F32_FAST_DIV 2       /* the 16-bit entries at a scale: the Markstein quotient, as fast_division = 1 of their siblings */
+int ivit_layernorm_i8_f32(const int8_t* x, int64_t ldx, int B, int T_all, int t0, int T, int C, const float* bias_int,
+                          const float* s_ln, const int8_t* remap /* [256] or NULL */, const float* phi /* [256] or NULL */,
+                          float* out, int64_t ldo, int flags, ivit_stream_t stream);
+/* int16 rows (any C <= 4096, rows aligned to 2 bytes).  s_in == 0: the integers (ivit_layernorm_i16_i8: float32 mean in torch's
+ * order from |sum| = 2^24 on, int32 squares that wrap, the ten Newton steps literally).  s_in > 0: the natural-scale form of
+ * ivit_layernorm_i16_i8_compat on phi(q) = fl(fl(q * s_in) / s_in), flags | IVIT_LN_F32_FAST_DIV where the caller has checked the
+ * three-instruction quotient for all 65536 inputs (prepare.markstein_division_ok); with s_in == 0 that flag is IVIT_ERR_INVALID. */
+int ivit_layernorm_i16_f32(const int16_t* x, int64_t ldx, int B, int T_all, int t0, int T, int C, float s_in, const float* bias_int,
+                           const float* s_ln, float* out, int64_t ldo, int flags, ivit_stream_t stream);
+
 /* module-level LITERAL form, any input scale: x is the float view q*s the reference's module receives, s_in its scale
  * (n_s = 1 per tensor, or C per channel).  Every float32 step of ivit_modules.py:36-63 as written, including the mean over
  * x/s in torch's CPU reduction order (decides rows whose mean is an exact .5 tie when s is not a power of two) and the
@@ -926,6 +954,15 @@ int ivit_ibert_layernorm_i16_i8_ex(const int16_t* x, int64_t ldx, int rows, int 
 int ivit_ibert_layernorm_i16_i8_win(const int16_t* x, int64_t ldx, int rows, int C, float s_in, const float* bias_int,
                                     const float* s_out, float shift_pow2, const uint32_t* m, const int32_t* e, int8_t* out, int64_t ldo,
                                     int fast_division, int H, int W, int ws, int shift, ivit_stream_t stream);
+/* Token features with IBERTIntLayerNorm: out = fl(v * s_out[c]) (ibert_modules.py:153), the module's own float32 output, from int8 /
+ * int16 rows at scale s_in -- the literal row of the entries above without their QuantAct.  Row selection (B, T_all, t0, T), output
+ * forms and common preconditions: see ivit_layernorm_i8_f32.  flags = IVIT_LN_F32_CHANNEL_MAJOR | IVIT_IBERT_LN_INT_SQRT, and on the
+ * int16 entry | IVIT_LN_F32_FAST_DIV (as fast_division = 1 above; on the int8 entry IVIT_ERR_INVALID).  Any C <= 4096, rows aligned
+ * to their element; s_in > 0 and shift_pow2 >= 1 (IVIT_ERR_INVALID otherwise). */
+int ivit_ibert_layernorm_i8_f32(const int8_t* x, int64_t ldx, int B, int T_all, int t0, int T, int C, float s_in, const float* bias_int,
+                                const float* s_out, float shift_pow2, float* out, int64_t ldo, int flags, ivit_stream_t stream);
+int ivit_ibert_layernorm_i16_f32(const int16_t* x, int64_t ldx, int B, int T_all, int t0, int T, int C, float s_in, const float* bias_int,
+                                 const float* s_out, float shift_pow2, float* out, int64_t ldo, int flags, ivit_stream_t stream);
 
 /* ---- evaluation transform (the reference's data pipeline in front of the model) ----------------------------------------
  * torchvision Resize([resize_short], BICUBIC) on a PIL image, then CenterCrop(crop) (scripts/inference.py:63-66,
