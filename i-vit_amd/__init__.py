@@ -9,3 +9,4 @@ from .vit_quant import *  # noqa: F401,F403
 from .swin_quant import *  # noqa: F401,F403
 from .model_utils import freeze_model, unfreeze_model  # noqa: F401
 from .knn import FeatureBank, knn_classify  # noqa: F401
+from .probe import BankStats, LinearProbe  # noqa: F401

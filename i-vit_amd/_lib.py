@@ -163,6 +163,10 @@ SIGNATURES = {
     "ivit_knn_topk_i8": [vp, i64, ci, vp, i64, ci, ci, vp, ci, ci, vp, vp, vp, i64, vp],
     "ivit_knn_workspace_bytes": [ci, ci, ci, ci, vp],
     "ivit_knn_vote_f32": [vp, vp, vp, ci, ci, ci, ci, vp, vp, vp],
+    # linear probe on the int8 feature bank (include/ivit_hip.h, end): ivit_gram_workspace_bytes is a host function
+    "ivit_gram_i8_i64": [vp, i64, i64, ci, ci, ci, vp, vp, i64, vp],
+    "ivit_gram_workspace_bytes": [i64, ci, ci, vp],
+    "ivit_group_sums_i8_i64": [vp, i64, i64, ci, vp, vp, ci, ci, vp, vp],
 }
 
 

@@ -12,7 +12,7 @@ change that breaks the budget must fail the build here, on the CPU, not on the G
 wait without spilling.  csrc/check_isa.py checks the emitted instruction stream for exactly that; the bit-exact GEMM tests on the
 GPU remain the proof of the result.
 
-Second use (`check_resources.py <remarks> attention|rowops|swin|calib|features|knn`): the occupancy the launchers of those files assume
+Second use (`check_resources.py <remarks> attention|rowops|swin|calib|features|knn|probe`): the occupancy the launchers of those files assume
 when they size their grids (occupancy_rules below)."""
 import re
 import sys
@@ -128,6 +128,13 @@ def occupancy_rules(path, what):
             if "knn_topk_kernel" in name and r.get("LDS", 0) > 81920:
                 print("FAIL", name, "LDS", r.get("LDS"), "above 80 KiB: two workgroups no longer fit a CU")
                 return 1
+        elif what == "probe":
+            # gram_partial_kernel: two workgroups of four waves per CU (its __launch_bounds__); accumulators, fragments and staged
+            # loads are indexed by constants only: no scratch, no spills.  The reducer and the group sums assume no number of
+            # resident workgroups and keep their per-lane sums in registers: no scratch
+            if not re.search(r"gram_(partial|reduce)_kernel|group_sums_kernel", name):
+                continue
+            occ, need_no_scratch = (2 if "gram_partial_kernel" in name else 1), True
         elif what == "swin":
             if (m := re.search(r"window_attention_kernelILi(\d+)ELb([01])ELi(\d+)E", name)):
                 # window_attention_kernel<SM, RQ32, NKT>: = its __launch_bounds__.  NKT 4 (2..64 tokens): four workgroups per CU;

@@ -29,6 +29,7 @@ from . import swin_quant, topk, vit_quant
 from .knn import FeatureBank, knn_weights
 from .model_utils import freeze_model
 from .parallel import allreduce_hits, shard_bounds
+from .probe import BankStats
 
 FACTORIES = {name: getattr(mod, name) for mod in (vit_quant, swin_quant) for name in mod.__all__ if name.endswith("_224")}
 _BW_KEYS = ("patch_embed_bw", "pos_encoding_bw", "block_input_bw", "attention_out_bw", "softmax_bw", "mlp_out_bw",
@@ -292,6 +293,38 @@ def evaluate_knn(model, bank_loader, query_loader, device, *, k=(10, 20, 100, 20
         classes, _ = bank.vote(idx[:, :kk], w[:, :kk], min(5, kk))
         hit = classes == targets[:, None]
         out[kk] = (100.0 * int(hit[:, 0].sum()) / n, 100.0 * int(hit.any(dim=1).sum()) / n)
+    return out
+
+
+def evaluate_linear_probe(model, bank_loader, query_loader, device, num_classes, *, lam=(1e-4, 1e-3, 1e-2, 1e-1, 1.0), kind: str = "ridge",
+                          transform=None, graph: bool = False):
+    """Linear-probe accuracy of a backbone -> {lam: (top-1 %, top-5 %)}.  Both sets go through extract_features(..., integers=True);
+    the bank stays int8 and its statistics (probe.BankStats: exact Gram matrix, class sums and counts) are computed ONCE; per lam
+    there is one C x C solve on the host (BankStats.ridge) and one int8 head GEMM with the top-5 selection over the queries
+    (LinearProbe.topk).  kind="ncm": the class-mean classifier instead, a single entry under the key None.  The two extractions
+    must carry the same scale (the same frozen model): anything else raises."""
+    if kind not in ("ridge", "ncm"):
+        raise ValueError(f"evaluate_linear_probe: kind={kind!r} is neither 'ridge' nor 'ncm'")
+    lams = (None,) if kind == "ncm" else tuple(float(v) for v in ((lam,) if isinstance(lam, (int, float)) else lam))
+    if not lams:
+        raise ValueError(f"evaluate_linear_probe: lam={lam!r}")
+    rows, labels, s_bank = extract_features(model, bank_loader, device, transform=transform, graph=graph, integers=True)
+    q, targets, s_query = extract_features(model, query_loader, device, transform=transform, graph=graph, integers=True)
+    if s_bank is None or s_query is None:
+        raise ValueError("evaluate_linear_probe: an empty bank or query set")
+    fb, fq = float(torch.as_tensor(s_bank).reshape(-1)[0]), float(torch.as_tensor(s_query).reshape(-1)[0])
+    if fb != fq:
+        raise ValueError(f"evaluate_linear_probe: the bank's rows carry scale {fb!r}, the queries' {fq!r}: not the same frozen model")
+    stats = BankStats(int(rows.shape[1]), num_classes, rows.device).update(rows, labels, s_bank)
+    targets = targets.to(torch.int32).contiguous()
+    k = min(5, int(num_classes))
+    out, n = {}, max(int(q.shape[0]), 1)
+    for v in lams:
+        probe = stats.ncm() if v is None else stats.ridge(v)
+        hits = torch.zeros(k, dtype=torch.int64, device=q.device)
+        probe.topk(q, k, targets, hits)
+        h = hits.cpu()
+        out[v] = (100.0 * int(h[0]) / n, 100.0 * int(h.sum()) / n)
     return out
 
 

@@ -1128,6 +1128,43 @@ int ivit_knn_workspace_bytes(int Q, int N, int k, int splits, int64_t* bytes);
 int ivit_knn_vote_f32(const int32_t* idx, const int32_t* labels, const float* w, int Q, int N, int k, int r, int32_t* classes,
                       float* votes, ivit_stream_t stream);
 
+/* ---- linear probe on an int8 feature bank: the exact integer statistics of a closed-form classifier ---------------------------
+ * Everything least squares onto one-hot targets (or a class-mean classifier) needs from a bank x of `rows` int8 rows of C channels
+ * (row stride ldx >= C in elements) is a sum of integers: the Gram matrix, the per-class row sums and the class counts.  They are
+ * computed exactly, so they are unique for any tiling and additive over batches and ranks (accumulate = 1).  Geometry of both
+ * entries, that of ivit_knn_topk_i8: C % 64 == 0, 64 <= C <= 1024, 0 <= rows < 2^31, x and ldx multiples of 16 bytes; row offsets
+ * are 64-bit products; elements C .. ldx - 1 of a row are not read.  No float anywhere, no atomics on a result.
+ *
+ * ivit_gram_i8_i64: gram[i * C + j] = sum_r x[r][i] * x[r][j], the exact integer, for all 0 <= i, j < C (dense [C][C] int64, both
+ * triangles written; the blocks on or above the diagonal are computed on v_mfma_i32_16x16x64_i8 and mirrored).  accumulate: 0
+ * overwrites, 1 adds to the int64 values already there.  rows == 0 is a sum over nothing: zeros with accumulate = 0, no change
+ * (and no launch) with 1.  splits: the rows are cut into that many segments of ceil(rows / splits) rows rounded up to 64 -- 1 ..
+ * IVIT_GRAM_SPLITS_MAX as given (a segment may be short or empty), 0 = chosen from rows and C for the 256 CUs the other launchers
+ * assume.  Every segment leaves int32 partial Grams in the workspace -- one per 65536 rows, over which no int32 sum of products of
+ * int8 can overflow (65536 * 2^14 = 2^30), so a longer segment widens inside itself -- and a second kernel sums the partials into
+ * int64.  The result does not depend on splits.  workspace: ivit_gram_workspace_bytes(rows, C, splits) bytes aligned to 4 (0
+ * bytes for rows == 0: workspace may then be NULL).
+ * Errors, nothing launched and nothing written: IVIT_ERR_INVALID for a NULL x or gram, rows outside [0, 2^31), splits outside
+ * [0, IVIT_GRAM_SPLITS_MAX], accumulate other than 0 or 1, ldx < C, a misaligned x, ldx or gram, a workspace that is NULL,
+ * misaligned or too small; IVIT_ERR_UNSUPPORTED ("unsupported geometry") for any other C.
+ *
+ * ivit_gram_workspace_bytes: a host function; *bytes for that call (the same checks of rows, C and splits).
+ *
+ * ivit_group_sums_i8_i64: sums[g * C + c] = sum over t in [group_ptr[g], group_ptr[g + 1]) of x[perm[t]][c], exact, for
+ * 0 <= g < groups (int64 [groups][C]; added to the values already there with accumulate = 1).  perm int32 [group_ptr[groups]]: row
+ * indices grouped by class; group_ptr int64 [groups + 1], non-decreasing from 0 -- the CSR form of the labels, which the caller
+ * builds from a stable sort of them.  An empty group gives zeros.  1 <= groups <= IVIT_GROUPS_MAX.  The inverted-index form of a
+ * scatter-add: one workgroup per group, every row read once, 16 bytes per lane.  An entry of perm outside [0, rows) is NOT checked
+ * on the device.  One launch.  Errors, nothing launched: IVIT_ERR_INVALID for a NULL or misaligned operand, rows outside [0, 2^31),
+ * ldx < C, groups outside [1, IVIT_GROUPS_MAX], accumulate other than 0 or 1; IVIT_ERR_UNSUPPORTED for any other C. */
+#define IVIT_GRAM_SPLITS_MAX 64
+#define IVIT_GROUPS_MAX 1048576
+int ivit_gram_i8_i64(const int8_t* x, int64_t ldx, int64_t rows, int C, int splits, int accumulate, int64_t* gram, void* workspace,
+                     int64_t workspace_bytes, ivit_stream_t stream);
+int ivit_gram_workspace_bytes(int64_t rows, int C, int splits, int64_t* bytes);
+int ivit_group_sums_i8_i64(const int8_t* x, int64_t ldx, int64_t rows, int C, const int32_t* perm, const int64_t* group_ptr, int groups,
+                           int accumulate, int64_t* sums, ivit_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
