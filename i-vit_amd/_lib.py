@@ -167,6 +167,9 @@ SIGNATURES = {
     "ivit_gram_i8_i64": [vp, i64, i64, ci, ci, ci, vp, vp, i64, vp],
     "ivit_gram_workspace_bytes": [i64, ci, ci, vp],
     "ivit_group_sums_i8_i64": [vp, i64, i64, ci, vp, vp, ci, ci, vp, vp],
+    # dense linear probe (include/ivit_hip.h, end): acc, s_acc, batch, gh, gw, np, classes, r, labels, target, ignore_index, conf, stream
+    "ivit_dense_argmax_u8": [vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, ci, vp, vp],
+    "ivit_patch_mode_u8": [vp, ci, ci, ci, ci, ci, ci, vp, vp],
 }
 
 

@@ -328,6 +328,73 @@ def evaluate_linear_probe(model, bank_loader, query_loader, device, num_classes,
     return out
 
 
+def _patch_tokens(model, x):
+    """-> (int8 tokens [b, Gh * Gw, C], scale, (Gh, Gw), r): forward_tokens(x, integers=True) as the model returns it -- a ViT's
+    ({block: tokens}, prefixes, scale), a Swin's (tokens, scale) -- and the geometry of its token grid: r = the pixels per token on
+    an axis (the patch size, times 2 per Swin patch merging)"""
+    out = model.forward_tokens(x, integers=True)
+    tok, scale = out[0], out[-1]
+    if isinstance(tok, dict):
+        tok = tok[max(tok)]
+    ph, pw = model.patch_embed.patch_size
+    r = int(ph) * 2 ** (int(getattr(model, "num_layers", 1)) - 1)
+    H, W = int(x.shape[-2]), int(x.shape[-1])
+    if ph != pw or H % r or W % r or tok.dim() != 3 or int(tok.shape[1]) != (H // r) * (W // r):
+        raise ValueError(f"evaluate_dense_probe: {tuple(tok.shape)} tokens for images of {H} x {W} and {r} pixels per token")
+    return tok, scale, (H // r, W // r), r
+
+
+def evaluate_dense_probe(model, train_loader, val_loader, device, num_classes, *, lam=(1e-4, 1e-3, 1e-2, 1e-1, 1.0), ignore_index: int = 255,
+                         transform=None):
+    """Linear segmentation probe of a frozen backbone -> {lam: (mIoU %, pixel accuracy %)}.  The loaders yield (images, uint8 target
+    maps [B, H, W]).  Training side: the int8 patch tokens of model.forward_tokens(x, integers=True) are the rows, dense.patch_labels
+    of the target maps their labels (patches labelled ignore_index are dropped), and probe.BankStats sums them batch by batch; the
+    statistics are computed ONCE.  Per lam there is one C x C solve on the host and one pass over the validation tokens (kept int8
+    on the device): dense.DenseProbe.segment adds every batch's pixels into one int64 confusion matrix -- the upsampled logits
+    never exist -- and dense.miou reads it.  transform: as for extract_features, on the images alone (the targets must already
+    have the transformed geometry).  All tokens must carry the same scale (the same frozen model): anything else raises."""
+    from .dense import DenseProbe, miou, patch_labels
+    lams = tuple(float(v) for v in ((lam,) if isinstance(lam, (int, float)) else lam))
+    if not lams:
+        raise ValueError(f"evaluate_dense_probe: lam={lam!r}")
+    K = int(num_classes)
+
+    def batches(loader):
+        for imgs, targets in loader:
+            b = int(targets.shape[0])
+            if b == 0:
+                continue
+            x = imgs.to(device) if transform is None else transform.to_float(transform(imgs, 0, b, device=device))
+            tok, scale, grid, r = _patch_tokens(model, x)
+            yield tok, float(torch.as_tensor(scale).reshape(-1)[0]), grid, r, targets.to(device=device, dtype=torch.uint8).contiguous()
+
+    stats, s_train = None, None
+    model.eval()
+    with torch.no_grad():
+        for tok, s, grid, r, tgt in batches(train_loader):
+            rows = tok.reshape(-1, tok.shape[-1])
+            lab = patch_labels(tgt, r, K, ignore_index).reshape(-1)
+            keep = lab != ignore_index
+            if stats is None:
+                stats, s_train = BankStats(int(rows.shape[1]), K, rows.device), s
+            stats.update(rows[keep].contiguous(), lab[keep], s)
+        val = [(tok.contiguous(), s, grid, r, tgt) for tok, s, grid, r, tgt in batches(val_loader)]
+    if stats is None or not val:
+        raise ValueError("evaluate_dense_probe: an empty training or validation set")
+    for _, s, _, _, _ in val:
+        if s != s_train:
+            raise ValueError(f"evaluate_dense_probe: the training tokens carry scale {s_train!r}, the validation tokens {s!r}: not the same frozen model")
+    out = {}
+    for v in lams:
+        dp = DenseProbe(stats.ridge(v))
+        conf = torch.zeros(K, K, dtype=torch.int64, device=device)
+        for tok, _, grid, r, tgt in val:
+            dp.segment(tok, grid, r, target=tgt, conf=conf, labels=False, ignore_index=ignore_index)
+        m, pa, _ = miou(conf)
+        out[v] = (100.0 * m, 100.0 * pa)
+    return out
+
+
 def extract_features_parallel(model, data_loader, device, *, transform=None, graph: bool = False, integers: bool = False):
     """extract_features data-parallel over the ranks of the default process group (world 1 without one) -> the same (features [N, C],
     labels int64 [N], scale) on every rank, rows in loader order.

@@ -1165,6 +1165,43 @@ int ivit_gram_workspace_bytes(int64_t rows, int C, int splits, int64_t* bytes);
 int ivit_group_sums_i8_i64(const int8_t* x, int64_t ldx, int64_t rows, int C, const int32_t* perm, const int64_t* group_ptr, int groups,
                            int accumulate, int64_t* sums, ivit_stream_t stream);
 
+/* ---- dense linear probe: bilinear upsample, argmax and confusion matrix of a linear head on the patch tokens -------------------
+ * acc: the int32 accumulators of the head GEMM (ivit_gemm_i8_i32, bias included) on the patch tokens of `batch` images, dense
+ * [batch * gh * gw][np], np >= classes the padded class count; s_acc float32 [np], the head's per-class scale.  The label map
+ * is the argmax over the first `classes` columns of the logits upsampled by the integer factor r (the patch size) to exactly
+ * (gh * r, gw * r), torch's bilinear interpolation with align_corners = False -- computed exactly and never stored.  On an axis with
+ * g patches, for the output coordinate d:
+ *   n = 2d + 1 - r;  n < 0: i0 = 0, f = 0 (the clamp of a negative source coordinate);  else i0 = n div 2r, f = n mod 2r
+ *   i1 = min(i0 + 1, g - 1);  integer weights (2r - f, f) on (i0, i1)
+ * For the pixel (y, x) and the class k:
+ *   I_k     = sum over the four taps of wy * wx * acc[b, iy, ix, k], in int64 (weights sum to 4 r^2 <= 4096: |I_k| < 2^43)
+ *   score_k = fl64(fl64(I_k) * fl64(s_acc[k])): ONE correctly rounded float64 product, everything before it exact
+ *   label   = the smallest k < classes of maximal score (float comparison, -0 == +0)
+ * so the result is unique whatever the tiling.  Columns classes .. np - 1 of acc and s_acc are never read.
+ *
+ * ivit_dense_argmax_u8: labels (uint8 [batch][gh * r][gw * r], or NULL) receives the label map; conf (int64 [classes][classes],
+ * or NULL) is ACCUMULATED: conf[t * classes + p] += 1 for every pixel of label p whose target t (target, uint8 of the labels'
+ * shape) is below classes and not ignore_index -- integer sums, additive over calls, batches and ranks; the caller zeroes it.
+ * At least one of labels and conf is given; conf needs target (target without conf is not read).  All operands are dense.
+ * Geometry: 1 <= classes <= IVIT_DENSE_CLASSES_MAX, classes <= np, 1 <= r <= IVIT_DENSE_R_MAX, batch, gh, gw >= 1, 0 <=
+ * ignore_index <= 255, and fewer than 2^31 pixels: batch * gh * r * gw * r < 2^31 (every offset is nevertheless a 64-bit product).
+ * labels and target may have any alignment (labels aligned to 4 bytes with gw * r % 4 == 0 are written a dword at a time).  One
+ * launch; conf is updated with 64-bit global atomics, one per distinct (t, p) pair of a workgroup's tile.
+ * Errors, nothing launched and nothing written: IVIT_ERR_INVALID for a NULL acc or s_acc, labels and conf both NULL, conf without
+ * target, batch, gh or gw below 1, ignore_index outside [0, 255], np < classes, 2^31 pixels or more, a misaligned acc, s_acc or
+ * conf; IVIT_ERR_UNSUPPORTED ("unsupported geometry") for classes or r outside their range.
+ *
+ * ivit_patch_mode_u8: the patch labels of the training side.  out[b][py][px] (uint8 [batch][gh][gw]) = the most frequent class
+ * among the valid pixels (below classes and not ignore_index) of the r x r patch of target (uint8 [batch][gh * r][gw * r]), equal
+ * counts to the lower class; ignore_index where fewer than half of the patch's pixels are valid.  The same geometry and errors
+ * (NULL target or out: IVIT_ERR_INVALID).  One launch, one wave per patch. */
+#define IVIT_DENSE_CLASSES_MAX 255
+#define IVIT_DENSE_R_MAX 32
+int ivit_dense_argmax_u8(const int32_t* acc, const float* s_acc, int batch, int gh, int gw, int np, int classes, int r, uint8_t* labels,
+                         const uint8_t* target, int ignore_index, int64_t* conf, ivit_stream_t stream);
+int ivit_patch_mode_u8(const uint8_t* target, int batch, int gh, int gw, int r, int classes, int ignore_index, uint8_t* out,
+                       ivit_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
