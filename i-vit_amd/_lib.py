@@ -170,6 +170,14 @@ SIGNATURES = {
     # dense linear probe (include/ivit_hip.h, end): acc, s_acc, batch, gh, gw, np, classes, r, labels, target, ignore_index, conf, stream
     "ivit_dense_argmax_u8": [vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, ci, vp, vp],
     "ivit_patch_mode_u8": [vp, ci, ci, ci, ci, ci, ci, vp, vp],
+    # pooled features (include/ivit_hip.h, end): x, ldx, B, T_all, t0, T, C, <LayerNorm operands>, m, e, sum, out, ldo, col0, flags,
+    # workspace, workspace_bytes, stream; the last two are host functions
+    "ivit_layernorm_pool_i8": [vp, i64, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, ci, vp, i64, vp],
+    "ivit_layernorm_pool_i16": [vp, i64, ci, ci, ci, ci, ci, f32, vp, vp, vp, vp, vp, vp, i64, i64, ci, vp, i64, vp],
+    "ivit_ibert_layernorm_pool_i8": [vp, i64, ci, ci, ci, ci, ci, f32, vp, vp, f32, vp, vp, vp, vp, i64, i64, ci, vp, i64, vp],
+    "ivit_ibert_layernorm_pool_i16": [vp, i64, ci, ci, ci, ci, ci, f32, vp, vp, f32, vp, vp, vp, vp, i64, i64, ci, vp, i64, vp],
+    "ivit_layernorm_pool_slab_rows": [ci, ci, vp],
+    "ivit_layernorm_pool_workspace_bytes": [ci, ci, ci, vp],
 }
 
 

@@ -85,6 +85,14 @@ def occupancy_rules(path, what):
             # count and nothing is indexed at run time, so no form keeps anything in scratch at any C; three workgroups of four
             # waves fit a CU beside their 48 KB token tiles at C = 768 (its launcher assumes no number of resident workgroups)
             occ, need_no_scratch = 3, True
+        elif "ln_pool_kernel" in name or "ln_pool_finish_kernel" in name:
+            # ln_pool_kernel<ROW> (ln_pool.h; the same row types): the per-lane accumulators live in LDS (28 C bytes per workgroup:
+            # five workgroups of four waves per CU at C = 1024), nothing is indexed at run time: no scratch in any form.  Its
+            # launcher sizes the grid by the slab rule (pool.h), which aims at four workgroups per CU: four waves per SIMD.
+            # ln_pool_finish_kernel (pool.hip): four sums per thread, no scratch
+            occ, need_no_scratch = 4, True
+        elif what in ("pool", "ibert"):
+            continue      # nothing else in those files sizes a grid by resident workgroups
         elif what == "attention" and "attention_long_kernel" in name:
             # attention_long_kernel<MODE, RQ32, NKT, NTH, PB>: one workgroup of NTH threads per CU (the launcher's 256 slots), i.e.
             # NTH / 256 waves per SIMD; the packed score rows must stay in registers: no scratch.  PB = 16 (the three probability

@@ -12,6 +12,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "pool.h"
 #include "isqrt.h"
 #include "rowsum.h"
 
@@ -320,6 +321,11 @@ IVIT_DEV void ib_ln_row_literal(const IbLnI8Args& a, int row, int lane, int64_t 
 
 #include "ln_tokens.h"
 
+// ln_chain.h (the QuantAct tail of the pooled entries: ln_cert, ln_literal) packs four results with the including file's pack4
+IVIT_DEV int pack4(int a, int b, int c, int d) { return (a & 0xff) | ((b & 0xff) << 8) | ((c & 0xff) << 16) | ((d & 0xff) << 24); }
+#include "ln_chain.h"
+#include "ln_pool.h"
+
 // one int8 / int16 row of the token-feature kernel: ib_ln_row with the float product (:153) as its tail
 template <typename TX, bool ISQ, bool FASTDIV>
 struct LnTokRowIbert {
@@ -337,7 +343,10 @@ struct LnTokRowIbert {
     {
         const TX* xr = x + xoff;
         ib_ln_row<ISQ>([&](int c) { return ln_tok_phi16<FASTDIV>(xr[c], s_in, r_in); }, C, shift_pow2, bias_int, lane,
-                       [&](int c, float v) { emit(c, v * s_out[c]); });
+                       [&](int c, float v) {
+                           if constexpr (EMIT::RAW) emit(c, v);
+                           else emit(c, v * s_out[c]);
+                       });
     }
 };
 
@@ -894,6 +903,49 @@ IVIT_EXPORT int ivit_ibert_layernorm_i16_f32(const int16_t* x, int64_t ldx, int 
                                              int flags, ivit_stream_t stream)
 {
     return ibert_ln_tokens("ivit_ibert_layernorm_i16_f32", x, ldx, B, T_all, t0, T, C, s_in, bias_int, s_out, shift_pow2, out, ldo, flags, stream);
+}
+
+// pooled features (ln_pool.h, pool.hip): the rows of the two entries above, each through qact2 (m, e), summed over the tokens.
+// flags = IVIT_IBERT_LN_INT_SQRT, and on int16 rows | IVIT_LN_F32_FAST_DIV
+template <typename TX>
+static int ibert_ln_pool(const char* who, const TX* x, int64_t ldx, int B, int T_all, int t0, int T, int C, float s_in, const float* bias_int,
+                         const float* s_out, float shift_pow2, const uint32_t* m, const int32_t* e, int32_t* sum, int8_t* out, int64_t ldo,
+                         int64_t col0, int flags, void* workspace, int64_t workspace_bytes, ivit_stream_t stream)
+{
+    const bool isq = (flags & IVIT_IBERT_LN_INT_SQRT) != 0, fast = (flags & IVIT_LN_F32_FAST_DIV) != 0;
+    LnPool o;
+    IVIT_REQUIRE(s_in > 0.0f && shift_pow2 >= 1.0f, "%s: s_in must be positive and shift_pow2 = 2^shift at least 1", who);
+    IVIT_REQUIRE(!fast || sizeof(TX) == 2, "%s: IVIT_LN_F32_FAST_DIV belongs to the 16-bit entry", who);
+    IVIT_REQUIRE((flags & ~(IVIT_IBERT_LN_INT_SQRT | IVIT_LN_F32_FAST_DIV)) == 0, "%s: unknown flags %d", who, flags);
+    if (const int rc = ln_pool_check(who, x, sizeof(TX), ldx, B, T_all, t0, T, C, bias_int, s_out, m, e, sum, out ? out + col0 : nullptr, ldo,
+                                     col0, workspace, workspace_bytes, 0, &o))
+        return rc;
+    const float r_in = 1.0f / s_in;
+    int8_t* o8 = out + col0;
+    if constexpr (sizeof(TX) == 2) {
+        if (fast && isq) return ln_pool_launch(who, LnTokRowIbert<TX, true, true>{x, C, s_in, r_in, shift_pow2, bias_int, s_out}, o, sum, o8, ldo, stream);
+        if (fast) return ln_pool_launch(who, LnTokRowIbert<TX, false, true>{x, C, s_in, r_in, shift_pow2, bias_int, s_out}, o, sum, o8, ldo, stream);
+    }
+    if (isq) return ln_pool_launch(who, LnTokRowIbert<TX, true, false>{x, C, s_in, r_in, shift_pow2, bias_int, s_out}, o, sum, o8, ldo, stream);
+    return ln_pool_launch(who, LnTokRowIbert<TX, false, false>{x, C, s_in, r_in, shift_pow2, bias_int, s_out}, o, sum, o8, ldo, stream);
+}
+
+IVIT_EXPORT int ivit_ibert_layernorm_pool_i8(const int8_t* x, int64_t ldx, int B, int T_all, int t0, int T, int C, float s_in,
+                                             const float* bias_int, const float* s_out, float shift_pow2, const uint32_t* m,
+                                             const int32_t* e, int32_t* sum, int8_t* out, int64_t ldo, int64_t col0, int flags,
+                                             void* workspace, int64_t workspace_bytes, ivit_stream_t stream)
+{
+    return ibert_ln_pool("ivit_ibert_layernorm_pool_i8", x, ldx, B, T_all, t0, T, C, s_in, bias_int, s_out, shift_pow2, m, e, sum, out, ldo,
+                         col0, flags, workspace, workspace_bytes, stream);
+}
+
+IVIT_EXPORT int ivit_ibert_layernorm_pool_i16(const int16_t* x, int64_t ldx, int B, int T_all, int t0, int T, int C, float s_in,
+                                              const float* bias_int, const float* s_out, float shift_pow2, const uint32_t* m,
+                                              const int32_t* e, int32_t* sum, int8_t* out, int64_t ldo, int64_t col0, int flags,
+                                              void* workspace, int64_t workspace_bytes, ivit_stream_t stream)
+{
+    return ibert_ln_pool("ivit_ibert_layernorm_pool_i16", x, ldx, B, T_all, t0, T, C, s_in, bias_int, s_out, shift_pow2, m, e, sum, out, ldo,
+                         col0, flags, workspace, workspace_bytes, stream);
 }
 
 #if IVIT_LAB

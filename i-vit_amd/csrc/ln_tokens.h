@@ -35,8 +35,10 @@ IVIT_DEV int ln_tok_tile(int c, int i, int tr)
     return c * (tr + 1) + i;
 }
 
-// where a row's elements go: emit(c, v) for one channel, emit.four(c, v4) for channels c .. c + 3 (c % 4 == 0)
+// where a row's elements go: emit(c, v) for one channel, emit.four(c, v4) for channels c .. c + 3 (c % 4 == 0).  RAW = false: v is the
+// module's float output y * s_ln[c]; RAW = true (ln_pool.h): y itself, the chain goes on in the emit
 struct LnTokEmitRow {
+    static constexpr bool RAW = false;
     float* orow;
     bool vec;        // the row admits 16-byte stores
     IVIT_DEV void operator()(int c, float v) const { orow[c] = v; }
@@ -51,6 +53,7 @@ struct LnTokEmitRow {
 };
 
 struct LnTokEmitTile {
+    static constexpr bool RAW = false;
     float* lds;
     int i, tr;
     IVIT_DEV void operator()(int c, float v) const { lds[ln_tok_tile(c, i, tr)] = v; }

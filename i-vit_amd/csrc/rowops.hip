@@ -12,6 +12,7 @@
 #include <limits.h>
 
 #include "common.h"
+#include "pool.h"
 #include "rowsum.h"
 
 // tests / A-B timing: 1 = always the wave-per-row LayerNorm kernel, 2 = the half-wave-per-row one wherever it exists
@@ -813,6 +814,7 @@ __global__ __launch_bounds__(NT) void layernorm_i32_f32_kernel(LnArgs a)
 }
 
 #include "ln_tokens.h"
+#include "ln_pool.h"
 
 // One int8 row of the token-feature kernel (ln_tokens.h), a wave per row, lane d + 64 j on dword d: the statistics of
 // layernorm_i8_kernel (v_dot4 sums, the integer tie test of the natural-scale mean with torch_rowsum_phi behind it) and ln_chain.h's
@@ -890,7 +892,10 @@ struct LnTokRowI8 {
             const float bias[4] = {b4.x, b4.y, b4.z, b4.w}, sl[4] = {s4.x, s4.y, s4.z, s4.w};
             float v[4];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) v[k] = ln_f32(ln_y(sx8(w, k), mean_int, hfactor, bias[k]), sl[k]);
+            for (int k = 0; k < 4; ++k) {
+                const float y = ln_y(sx8(w, k), mean_int, hfactor, bias[k]);
+                v[k] = EMIT::RAW ? y : ln_f32(y, sl[k]);
+            }
             emit.four(4 * d, make_float4(v[0], v[1], v[2], v[3]));
         }
     }
@@ -1839,6 +1844,29 @@ IVIT_EXPORT int ivit_layernorm_i8_f32(const int8_t* x, int64_t ldx, int B, int T
                             "%s: per-channel tables must be 16-byte aligned", who);
     if (compat) return ln_tok_launch(who, LnTokRowI8<true>{x, C, bias_int, s_ln, remap, phi, nullptr, nullptr}, o, lds, stream);
     return ln_tok_launch(who, LnTokRowI8<false>{x, C, bias_int, s_ln, nullptr, nullptr, nullptr, nullptr}, o, lds, stream);
+}
+
+// pooled features (ln_pool.h, pool.hip): the rows of ivit_layernorm_i8_f32, each through qact2 (m, e), summed over the tokens
+IVIT_EXPORT int ivit_layernorm_pool_i8(const int8_t* x, int64_t ldx, int B, int T_all, int t0, int T, int C, const float* bias_int,
+                                       const float* s_ln, const int8_t* remap, const float* phi, const uint32_t* m, const int32_t* e,
+                                       int32_t* sum, int8_t* out, int64_t ldo, int64_t col0, int flags, void* workspace,
+                                       int64_t workspace_bytes, ivit_stream_t stream)
+{
+    const char* who = "ivit_layernorm_pool_i8";
+    const bool compat = remap != nullptr;
+    LnPool o;
+    IVIT_REQUIRE((remap != nullptr) == (phi != nullptr), "%s: remap and phi come together", who);
+    IVIT_REQUIRE(flags == 0, "%s: unknown flags %d", who, flags);
+    if (const int rc = ln_pool_check(who, x, 1, ldx, B, T_all, t0, T, C, bias_int, s_ln, m, e, sum, out ? out + col0 : nullptr, ldo, col0,
+                                     workspace, workspace_bytes, compat ? 256 * 5 : 0, &o))
+        return rc;
+    // the preconditions of ivit_layernorm_i8_f32
+    IVIT_LN_TOK_UNSUPPORTED(!compat || (C >= 32 && C % 8 == 0), "%s: C=%d unsupported", who, C);
+    IVIT_LN_TOK_UNSUPPORTED(ldx % 4 == 0 && (uintptr_t)x % 4 == 0, "%s: rows must be 4-byte aligned", who);
+    IVIT_LN_TOK_UNSUPPORTED((uintptr_t)bias_int % 16 == 0 && (uintptr_t)s_ln % 16 == 0 && (uintptr_t)phi % 4 == 0,
+                            "%s: per-channel tables must be 16-byte aligned", who);
+    if (compat) return ln_pool_launch(who, LnTokRowI8<true>{x, C, bias_int, s_ln, remap, phi, nullptr, nullptr}, o, sum, out + col0, ldo, stream);
+    return ln_pool_launch(who, LnTokRowI8<false>{x, C, bias_int, s_ln, nullptr, nullptr, nullptr, nullptr}, o, sum, out + col0, ldo, stream);
 }
 
 IVIT_EXPORT int ivit_shiftgelu_i8(const int8_t* x, int64_t ldx, int rows, int L, float s, uint32_t m, int32_t e,

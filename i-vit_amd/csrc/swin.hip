@@ -7,6 +7,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "pool.h"
 #include "rowsum.h"
 
 #if IVIT_LAB
@@ -205,6 +206,7 @@ __global__ __launch_bounds__(NT) void layernorm_i16_i8_literal_kernel(Ln16LitArg
 }
 
 #include "ln_tokens.h"
+#include "ln_pool.h"
 
 // one int16 row of the token-feature kernel: ln16_row with the float product as its tail.  s_in == 0: the integers themselves.
 template <bool COMPAT, bool FASTDIV>
@@ -222,7 +224,10 @@ struct LnTokRowI16 {
     IVIT_DEV void row(int64_t xoff, int lane, EMIT emit) const
     {
         const int16_t* xr = x + xoff;
-        auto tail = [&](int c, float y) { emit(c, ln_f32(y, s_ln[c])); };
+        auto tail = [&](int c, float y) {
+            if constexpr (EMIT::RAW) emit(c, y);
+            else emit(c, ln_f32(y, s_ln[c]));
+        };
         if constexpr (COMPAT) ln16_row(xr, C, [&](int c) { return ln_tok_phi16<FASTDIV>(xr[c], s_in, r_in); }, 0, 0, bias_int, lane, tail);
         else ln16_row(xr, C, nullptr, 0, 0, bias_int, lane, tail);
     }
@@ -1316,6 +1321,26 @@ IVIT_EXPORT int ivit_layernorm_i16_f32(const int16_t* x, int64_t ldx, int B, int
     if (s_in == 0.0f) return ln_tok_launch(who, LnTokRowI16<false, false>{x, C, s_in, r_in, bias_int, s_ln}, o, lds, stream);
     if (fast) return ln_tok_launch(who, LnTokRowI16<true, true>{x, C, s_in, r_in, bias_int, s_ln}, o, lds, stream);
     return ln_tok_launch(who, LnTokRowI16<true, false>{x, C, s_in, r_in, bias_int, s_ln}, o, lds, stream);
+}
+
+// pooled features (ln_pool.h, pool.hip): the rows of ivit_layernorm_i16_f32, each through qact2 (m, e), summed over the tokens
+IVIT_EXPORT int ivit_layernorm_pool_i16(const int16_t* x, int64_t ldx, int B, int T_all, int t0, int T, int C, float s_in,
+                                        const float* bias_int, const float* s_ln, const uint32_t* m, const int32_t* e, int32_t* sum,
+                                        int8_t* out, int64_t ldo, int64_t col0, int flags, void* workspace, int64_t workspace_bytes,
+                                        ivit_stream_t stream)
+{
+    const char* who = "ivit_layernorm_pool_i16";
+    const bool fast = (flags & IVIT_LN_F32_FAST_DIV) != 0;
+    LnPool o;
+    IVIT_REQUIRE(s_in >= 0.0f && (s_in > 0.0f || !fast), "%s: s_in is 0 (integers) or a positive scale; IVIT_LN_F32_FAST_DIV needs a scale", who);
+    IVIT_REQUIRE((flags & ~IVIT_LN_F32_FAST_DIV) == 0, "%s: unknown flags %d", who, flags);
+    if (const int rc = ln_pool_check(who, x, 2, ldx, B, T_all, t0, T, C, bias_int, s_ln, m, e, sum, out ? out + col0 : nullptr, ldo, col0,
+                                     workspace, workspace_bytes, 0, &o))
+        return rc;
+    const float r_in = s_in > 0.0f ? 1.0f / s_in : 0.0f;
+    if (s_in == 0.0f) return ln_pool_launch(who, LnTokRowI16<false, false>{x, C, s_in, r_in, bias_int, s_ln}, o, sum, out + col0, ldo, stream);
+    if (fast) return ln_pool_launch(who, LnTokRowI16<true, true>{x, C, s_in, r_in, bias_int, s_ln}, o, sum, out + col0, ldo, stream);
+    return ln_pool_launch(who, LnTokRowI16<true, false>{x, C, s_in, r_in, bias_int, s_ln}, o, sum, out + col0, ldo, stream);
 }
 
 IVIT_EXPORT int ivit_patch_merge_i16(const int16_t* x, int16_t* out, int batch, int H, int W, int C, ivit_stream_t stream)

@@ -28,7 +28,7 @@ import torch
 
 from . import _lib, gemm_forms
 from .engine_common import (EngineBase, _np, attention, attention_probs, attention_spec, block_copy, frag_copy, intermediate_indices,
-                            layernorm, layernorm_f32, ln_spec, token_format, tokens_to_nchw)
+                            layernorm, layernorm_f32, layernorm_pool, layernorm_pool_workspace, ln_spec, token_format, tokens_to_nchw)
 from .prepare import dyadic, dyadic1, f32, pad_head, quant_sym, requant_host
 from .topk import TOPK_MAX
 
@@ -507,6 +507,45 @@ class IntViTEngine(EngineBase):
 
         self._forward(images, toks={i: emit for i in idx}, stop=max(idx) if self.head is None else None)
         return {i: tokens[i] for i in idx}, {i: prefixes[i] for i in idx if prefix}, (self.s_feat if integers else self.ln_f["s"])
+
+    def forward_features_pooled(self, images: torch.Tensor, n_last: int = 1, avgpool: bool = True, out: torch.Tensor | None = None):
+        """The pooled feature of the DINO evaluation protocol -> (int8 [B, W], float32 [W] scale), W = n_last * C (+ C with avgpool):
+        columns [i * C, (i + 1) * C) the class row of block D - n_last + i behind the final norm + qact2 (for the last block
+        forward_features(integers=True) bit for bit; the same two modules on the earlier streams), the last C columns the mean over
+        the last block's patch tokens of that same int8 tensor, halves up (engine_common.round_half_up_div), at qact2's scale.
+        out: [B, W] int8 rows to write into, as forward_features takes them (rows of a wider feature bank).
+        The eager forward runs up to the last block and stops there (the workspace logits are left as they were); behind each
+        selected block one class-row LayerNorm launch on B rows and a copy of its B x C bytes, behind the last one the pool launch
+        pair (engine_common.layernorm_pool): the [B, T, C] normed map is never written.  Not part of the graph replays or cls_tail."""
+        D, C, T = self.D, self.C, self.T
+        if not 1 <= int(n_last) <= D:
+            raise ValueError(f"n_last={n_last}: 1 .. {D} blocks")
+        n_last, B = int(n_last), images.shape[0]
+        W = n_last * C + (C if avgpool else 0)
+        out = self._features_out(B, W, True, out)
+        # the pool kernel stores a dword of four means: rows that do not admit it are filled through a dense tensor
+        direct = out.data_ptr() % 4 == 0 and (B == 1 or out.stride(0) % 4 == 0)
+        dst = out if direct else torch.empty(B, W, dtype=torch.int8, device=self.dev)
+        ldo = dst.stride(0) if B > 1 else W
+        cls = torch.empty(B, C, dtype=torch.int8, device=self.dev)
+        pool_ws = layernorm_pool_workspace(B, T - 1, C, self.dev) if avgpool else None
+
+        def emit(i, x, st):
+            ln = self._ln_tokens(i)
+            if self.stream_bits == 16:      # the int16 kernels want dense rows
+                self.ws["cls16"][:B].copy_(x.view(-1, T, C)[:B, 0])
+                layernorm(ln, self.ws["cls16"], C, B, C, cls, C, st, blocks=False)
+            else:
+                layernorm(ln, x, T * C, B, C, cls, C, st, blocks=False)
+            seg = i - (D - n_last)
+            dst[:, seg * C:(seg + 1) * C].copy_(cls)
+            if avgpool and i == D - 1:
+                layernorm_pool(ln, x, C, B, T, 1, T - 1, C, dst, ldo, n_last * C, pool_ws, st)
+
+        self._forward(images, toks={i: emit for i in range(D - n_last, D)}, stop=D - 1)
+        if dst is not out:
+            out.copy_(dst)
+        return out, torch.full((W,), self.s_feat, dtype=torch.float32, device=self.dev)
 
     def _forward(self, images: torch.Tensor, taps: dict | None = None, topk=None, cls_tail: bool = False, maps: dict | None = None,
                  feats: dict | None = None, stop=None, toks: dict | None = None):

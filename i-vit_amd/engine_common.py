@@ -8,6 +8,8 @@ forward_features' destination among it).  Window attention's pair
 (window_attention_spec, window_attention) lives in swin_engine.py; the scalar dyadic pair is prepare.dyadic1."""
 from __future__ import annotations
 
+import ctypes as C_
+
 import numpy as np
 import torch
 
@@ -144,6 +146,45 @@ def layernorm_f32(ln, x, ldx, B, T_all, t0, T, C, out, ldo, st, fmt="NLC"):
     elif kind == "ibert_i16":
         _lib.call("ivit_ibert_layernorm_i16_f32", *sel, ln["s_in"], bias, s, ln["shift_pow2"], p(out), ldo,
                   flags | ln["flags"] | (LN_F32_FAST_DIV if ln["fast_div"] else 0), st)
+    else:
+        raise ValueError(f"LayerNorm kind {kind!r}")
+
+
+def round_half_up_div(s: int, T: int) -> int:
+    """the pooled mean of the integer sum s over T tokens: floor((2 s + T) / (2 T)), s / T to nearest with halves up -- the rule of
+    csrc/pool.hip in Python integers (// floors)"""
+    return (2 * s + T) // (2 * T)
+
+
+def layernorm_pool_workspace(B, T, C, device):
+    """the workspace of layernorm_pool for that call (ivit_layernorm_pool_workspace_bytes: the slab rule lives in csrc/pool.h)"""
+    n = C_.c_int64()
+    _lib.call("ivit_layernorm_pool_workspace_bytes", B, T, C, C_.byref(n))
+    return torch.empty(n.value // 4, dtype=torch.int32, device=device)
+
+
+def layernorm_pool(ln, x, ldx, B, T_all, t0, T, C, out, ldo, col0, workspace, st, total=None):
+    """The mean over tokens t0 .. t0 + T - 1 of LayerNorm + the QuantAct behind it (ln's m, e), for every kind of ln_spec, straight from
+    the integer stream x (addressed as in layernorm_f32): int8 out[b * ldo + col0 + c] = the per-token int8 values summed exactly and
+    divided by T, halves up; the [B, T, C] map is never written.  total: an int32 [B, C] tensor for the sums themselves.  Two launches
+    (ivit_layernorm_pool_i8 / _i16, ivit_ibert_layernorm_pool_i8 / _i16: csrc/ln_pool.h, csrc/pool.hip)."""
+    kind, p = ln["kind"], _lib.ptr
+    sel, bias, s = (p(x), ldx, B, T_all, t0, T, C), p(ln["bias"]), p(ln["s"])
+    tail = (p(ln["m"]), p(ln["e"]), p(total), p(out), ldo, col0)
+    wsp = (p(workspace), workspace.numel() * workspace.element_size(), st)
+    if kind == "i8":
+        _lib.call("ivit_layernorm_pool_i8", *sel, bias, s, None, None, *tail, 0, *wsp)
+    elif kind == "i8_compat":
+        _lib.call("ivit_layernorm_pool_i8", *sel, bias, s, p(ln["remap"]), p(ln["phi"]), *tail, 0, *wsp)
+    elif kind == "i16":
+        _lib.call("ivit_layernorm_pool_i16", *sel, 0.0, bias, s, *tail, 0, *wsp)
+    elif kind == "i16_compat":
+        _lib.call("ivit_layernorm_pool_i16", *sel, ln["s_in"], bias, s, *tail, LN_F32_FAST_DIV if ln["fast_div"] else 0, *wsp)
+    elif kind == "ibert_i8":
+        _lib.call("ivit_ibert_layernorm_pool_i8", *sel, ln["s_in"], bias, s, ln["shift_pow2"], *tail, ln["flags"], *wsp)
+    elif kind == "ibert_i16":
+        _lib.call("ivit_ibert_layernorm_pool_i16", *sel, ln["s_in"], bias, s, ln["shift_pow2"], *tail,
+                  ln["flags"] | (LN_F32_FAST_DIV if ln["fast_div"] else 0), *wsp)
     else:
         raise ValueError(f"LayerNorm kind {kind!r}")
 

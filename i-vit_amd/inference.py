@@ -221,6 +221,29 @@ def _features_into(model, x, rows, integers, graph, norm=None):
     return scale
 
 
+def pooled_width(model, n_last: int = 1, avgpool: bool = False):
+    """Width W = n_last * C (+ C with avgpool) of model.features_pooled's rows, checked against what the feature-bank kernels take
+    (knn.FeatureBank, probe.BankStats: W % 64 == 0 in 64..1024): ValueError otherwise, before anything is extracted"""
+    C = int(model.num_features)
+    W = int(n_last) * C + (C if avgpool else 0)
+    if int(n_last) < 1 or W % 64 or not 64 <= W <= 1024:
+        raise ValueError(f"pooled features of width W={W} (n_last={n_last}, avgpool={bool(avgpool)}, C={C}): the feature-bank kernels "
+                         "take rows of W % 64 == 0 channels, W in 64..1024")
+    return W
+
+
+def _pooled_into(model, x, rows, n_last, avgpool, norm=None):
+    """model.features_pooled of the image batch x into `rows`, a [b, W] int8 block of rows of a feature bank -> scale (a float: every
+    segment carries qact2's).  uint8 x and norm: as _features_into; a model the fused engine declines raises (no module path)."""
+    takes = getattr(model, "takes_engine_for_features", None)
+    if takes is not None and takes(x) and x.dtype == torch.uint8:
+        eng = model.engine(x.shape[0])
+        if getattr(eng, "input_lut", None) is None or (norm is not None and getattr(eng, "input_norm", None) != norm):
+            eng.set_input_normalisation(*(norm or ()))
+        return eng.forward_features_pooled(x, n_last, avgpool, out=rows)[1][0].item()
+    return model.features_pooled(x, n_last, avgpool, out=rows)[1][0].item()
+
+
 def _sized(data_loader):
     """(loader, number of images): from the loader's dataset where it has one, else by holding its batches"""
     ds = getattr(data_loader, "dataset", None)
@@ -230,7 +253,8 @@ def _sized(data_loader):
     return batches, sum(int(t.shape[0]) for _, t in batches)
 
 
-def extract_features(model, data_loader, device, *, transform=None, graph: bool = False, integers: bool = False):
+def extract_features(model, data_loader, device, *, transform=None, graph: bool = False, integers: bool = False, n_last: int = 1,
+                     avgpool: bool = False):
     """The embeddings of a dataset -> (features [N, C], labels int64 [N], scale), rows in loader order, on `device`: what linear
     probing, a retrieval bank or k-NN evaluation start from.  features: float32, model.features' tensor (integers times scale), or
     with integers=True the int8 integers; scale: the float32 act_scaling_factor they carry (None for an empty loader).
@@ -240,10 +264,16 @@ def extract_features(model, data_loader, device, *, transform=None, graph: bool 
     (forward_features(out=...)): no float copy per batch, no concatenation.  transform, graph: as for evaluate_dataset -- a
     transforms.EvalTransform makes the loader's (PackedImages, targets) batches uint8 crops on the device; graph=True replays the
     fused engine's feature graph (a model the engine declines has no feature graph and runs eagerly) and model.graph_status() is
-    checked once after the loop."""
+    checked once after the loop.
+    n_last, avgpool: anything but the defaults extracts model.features_pooled(x, n_last, avgpool) instead -- the class tokens of the
+    last n_last blocks and, with avgpool, the mean patch token, W = n_last * C (+ C) columns (pooled_width: ValueError, before the
+    loader is touched, for a W the feature-bank kernels do not take) -- on the fused engine, eagerly (graph=True: ValueError)."""
+    pooled = int(n_last) != 1 or bool(avgpool)
+    C = pooled_width(model, n_last, avgpool) if pooled else int(model.num_features)
+    if pooled and graph:
+        raise ValueError("extract_features: features_pooled is not part of the graph replays (graph=False)")
     data_loader, N = _sized(data_loader)
-    C = int(model.num_features)
-    bank = torch.empty(N, C, dtype=torch.int8 if integers else torch.float32, device=device)
+    bank = torch.empty(N, C, dtype=torch.int8 if integers or pooled else torch.float32, device=device)
     labels = torch.empty(N, dtype=torch.int64, device=device)
     n, scale = 0, None
     model.eval()
@@ -253,7 +283,14 @@ def extract_features(model, data_loader, device, *, transform=None, graph: bool 
             if b == 0:
                 continue
             rows = bank[n:n + b]
-            if transform is None:
+            if pooled and transform is None:
+                scale = _pooled_into(model, imgs.to(device), rows, n_last, avgpool)
+            elif pooled:
+                u8 = transform(imgs, 0, b, device=device)
+                takes = getattr(model, "takes_engine_for_features", None)
+                x = u8 if takes is not None and takes(u8) else transform.to_float(u8)
+                scale = _pooled_into(model, x, rows, n_last, avgpool, (transform.mean, transform.std))
+            elif transform is None:
                 scale = _features_into(model, imgs.to(device), rows, integers, graph)
             else:
                 u8 = transform(imgs, 0, b, device=device)
@@ -264,19 +301,24 @@ def extract_features(model, data_loader, device, *, transform=None, graph: bool 
             n += b
     if graph and hasattr(model, "graph_status"):
         model.graph_status()
+    if pooled and not integers and scale is not None:
+        bank = bank.float() * torch.tensor(scale, dtype=torch.float32)      # the integers times scale, one float32 product
     return bank[:n], labels[:n], scale
 
 
-def evaluate_knn(model, bank_loader, query_loader, device, *, k=(10, 20, 100, 200), T: float = 0.07, transform=None, graph: bool = False):
+def evaluate_knn(model, bank_loader, query_loader, device, *, k=(10, 20, 100, 200), T: float = 0.07, transform=None, graph: bool = False,
+                 n_last: int = 1, avgpool: bool = False):
     """Weighted k-NN accuracy of a backbone -> {k: (top-1 %, top-5 %)}.  Both sets go through extract_features(..., integers=True);
     the bank stays int8 (knn.FeatureBank) and ONE search at max(k) serves every k: the neighbour order is total, so the neighbours
     for a smaller k are a prefix.  Per k the neighbours vote with w = exp(cos / T) (knn.knn_weights); top-5 counts a hit among the
-    first min(5, k) voted classes.  The two extractions must carry the same scale (the same frozen model): anything else raises."""
+    first min(5, k) voted classes.  The two extractions must carry the same scale (the same frozen model): anything else raises.
+    n_last, avgpool: the pooled feature of extract_features for both sets."""
     ks = tuple(sorted({int(v) for v in ((k,) if isinstance(k, int) else k)}))
     if not ks or ks[0] < 1:
         raise ValueError(f"evaluate_knn: k={k!r}")
-    rows, labels, s_bank = extract_features(model, bank_loader, device, transform=transform, graph=graph, integers=True)
-    q, targets, s_query = extract_features(model, query_loader, device, transform=transform, graph=graph, integers=True)
+    pooled = {} if int(n_last) == 1 and not avgpool else dict(n_last=n_last, avgpool=avgpool)      # (the defaults: the call as it always was)
+    rows, labels, s_bank = extract_features(model, bank_loader, device, transform=transform, graph=graph, integers=True, **pooled)
+    q, targets, s_query = extract_features(model, query_loader, device, transform=transform, graph=graph, integers=True, **pooled)
     if s_bank is None or s_query is None:
         raise ValueError("evaluate_knn: an empty bank or query set")
     fb, fq = float(torch.as_tensor(s_bank).reshape(-1)[0]), float(torch.as_tensor(s_query).reshape(-1)[0])
@@ -297,19 +339,21 @@ def evaluate_knn(model, bank_loader, query_loader, device, *, k=(10, 20, 100, 20
 
 
 def evaluate_linear_probe(model, bank_loader, query_loader, device, num_classes, *, lam=(1e-4, 1e-3, 1e-2, 1e-1, 1.0), kind: str = "ridge",
-                          transform=None, graph: bool = False):
+                          transform=None, graph: bool = False, n_last: int = 1, avgpool: bool = False):
     """Linear-probe accuracy of a backbone -> {lam: (top-1 %, top-5 %)}.  Both sets go through extract_features(..., integers=True);
     the bank stays int8 and its statistics (probe.BankStats: exact Gram matrix, class sums and counts) are computed ONCE; per lam
     there is one C x C solve on the host (BankStats.ridge) and one int8 head GEMM with the top-5 selection over the queries
     (LinearProbe.topk).  kind="ncm": the class-mean classifier instead, a single entry under the key None.  The two extractions
-    must carry the same scale (the same frozen model): anything else raises."""
+    must carry the same scale (the same frozen model): anything else raises.  n_last, avgpool: the pooled feature of
+    extract_features for both sets."""
     if kind not in ("ridge", "ncm"):
         raise ValueError(f"evaluate_linear_probe: kind={kind!r} is neither 'ridge' nor 'ncm'")
     lams = (None,) if kind == "ncm" else tuple(float(v) for v in ((lam,) if isinstance(lam, (int, float)) else lam))
     if not lams:
         raise ValueError(f"evaluate_linear_probe: lam={lam!r}")
-    rows, labels, s_bank = extract_features(model, bank_loader, device, transform=transform, graph=graph, integers=True)
-    q, targets, s_query = extract_features(model, query_loader, device, transform=transform, graph=graph, integers=True)
+    pooled = {} if int(n_last) == 1 and not avgpool else dict(n_last=n_last, avgpool=avgpool)      # (the defaults: the call as it always was)
+    rows, labels, s_bank = extract_features(model, bank_loader, device, transform=transform, graph=graph, integers=True, **pooled)
+    q, targets, s_query = extract_features(model, query_loader, device, transform=transform, graph=graph, integers=True, **pooled)
     if s_bank is None or s_query is None:
         raise ValueError("evaluate_linear_probe: an empty bank or query set")
     fb, fq = float(torch.as_tensor(s_bank).reshape(-1)[0]), float(torch.as_tensor(s_query).reshape(-1)[0])
@@ -395,7 +439,8 @@ def evaluate_dense_probe(model, train_loader, val_loader, device, num_classes, *
     return out
 
 
-def extract_features_parallel(model, data_loader, device, *, transform=None, graph: bool = False, integers: bool = False):
+def extract_features_parallel(model, data_loader, device, *, transform=None, graph: bool = False, integers: bool = False,
+                              n_last: int = 1, avgpool: bool = False):
     """extract_features data-parallel over the ranks of the default process group (world 1 without one) -> the same (features [N, C],
     labels int64 [N], scale) on every rank, rows in loader order.
 
@@ -403,14 +448,18 @@ def extract_features_parallel(model, data_loader, device, *, transform=None, gra
     evaluate_dataset_parallel does; it collects the int8 integers of its slices with their labels, and ONE
     parallel.gather_feature_rows at the end (one all_gather_into_tensor: uneven shards padded to the largest and trimmed by their
     counts) brings every rank's rows to every rank, where they are put back into loader order.  integers=False: the gathered
-    integers are dequantised once, behind the gather (a quarter of the float32 bytes cross the wire)."""
+    integers are dequantised once, behind the gather (a quarter of the float32 bytes cross the wire).
+    n_last, avgpool: as for extract_features (the pooled rows, checked before the loader is touched)."""
     from .parallel import gather_feature_rows
+    pooled = int(n_last) != 1 or bool(avgpool)
+    C = pooled_width(model, n_last, avgpool) if pooled else int(model.num_features)
+    if pooled and graph:
+        raise ValueError("extract_features_parallel: features_pooled is not part of the graph replays (graph=False)")
     if dist.is_available() and dist.is_initialized():
         world, rank = dist.get_world_size(), dist.get_rank()
     else:
         world, rank = 1, 0
     data_loader, N = _sized(data_loader)
-    C = int(model.num_features)
     # this rank's rows: its slice of a batch is at most one image more than an even share
     cap = N // world + len(data_loader) if hasattr(data_loader, "__len__") else N
     local = torch.empty(min(N, cap), C, dtype=torch.int8, device=device)
@@ -425,7 +474,14 @@ def extract_features_parallel(model, data_loader, device, *, transform=None, gra
             if hi == lo:
                 continue
             rows = local[n:n + hi - lo]
-            if transform is None:
+            if pooled and transform is None:
+                scale = _pooled_into(model, imgs[lo:hi].to(device), rows, n_last, avgpool)
+            elif pooled:
+                u8 = transform(imgs, lo, hi, device=device)
+                takes = getattr(model, "takes_engine_for_features", None)
+                x = u8 if takes is not None and takes(u8) else transform.to_float(u8)
+                scale = _pooled_into(model, x, rows, n_last, avgpool, (transform.mean, transform.std))
+            elif transform is None:
                 scale = _features_into(model, imgs[lo:hi].to(device), rows, True, graph)
             else:
                 u8 = transform(imgs, lo, hi, device=device)

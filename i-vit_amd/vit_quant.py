@@ -350,6 +350,20 @@ class VisionTransformer(EngineDispatch, ModuleGraph, nn.Module):
         scale = scale.reshape(-1)
         return tokens, prefixes, (float(scale[0]) if integers else scale)
 
+    def features_pooled(self, x, n_last=1, avgpool=True, out=None):
+        """The pooled backbone feature of the DINO / DINOv2 linear and k-NN protocol -> (int8 [B, W], float32 [W] scale),
+        W = n_last * C + (C if avgpool else 0): the class tokens of the last n_last blocks, each behind self.norm + self.qact2
+        (columns [i * C, (i + 1) * C): block depth - n_last + i; for the last block features(x, integers=True) bit for bit), then
+        the mean over the last block's patch tokens of the int8 tensor qact2 gives -- the exact integer sum divided by the token
+        count, halves up -- all at qact2's scale.  out: [B, W] int8 rows to write into (rows of a knn.FeatureBank), as features
+        takes them.  IntViTEngine.forward_features_pooled: the eager engine forward plus one small launch per selected block and
+        one pool launch pair; the [B, T, C] normed map is never written.  There is no module path for it: a model the fused
+        engine declines raises NotImplementedError."""
+        if not self.takes_engine_for_features(x):
+            raise NotImplementedError("features_pooled runs on the fused engine only (a frozen model in eval mode on the GPU); "
+                                      f"features_unsupported_reason(): {self.features_unsupported_reason()}")
+        return self.engine(x.shape[0]).forward_features_pooled(x.contiguous().float(), n_last, avgpool, out)
+
     def forward_intermediates_early(self, x, indices=None, integers=False):
         """forward_intermediates with an early stop: where the fused engine is taken it launches nothing behind the last selected
         block (IntViTEngine.forward_intermediates_early: the same maps and scales; its workspace logits are then stale).  The

@@ -1202,6 +1202,39 @@ int ivit_dense_argmax_u8(const int32_t* acc, const float* s_acc, int batch, int 
 int ivit_patch_mode_u8(const uint8_t* target, int batch, int gh, int gw, int r, int classes, int ignore_index, uint8_t* out,
                        ivit_stream_t stream);
 
+/* ---- pooled features: the mean over the patch tokens of the final LayerNorm + qact2, as exact integers ---------------------------
+ * Rows, LayerNorm operands and row preconditions: those of the token-feature entry of the same kind (ivit_layernorm_i8_f32,
+ * ivit_layernorm_i16_f32, ivit_ibert_layernorm_i8_f32 / _i16_f32; flags: IVIT_LN_F32_FAST_DIV and IVIT_IBERT_LN_INT_SQRT where
+ * that entry takes them, no IVIT_LN_F32_CHANNEL_MAJOR).  (m, e) [C]: the QuantAct behind the LayerNorm, as ivit_layernorm_i8 and
+ * its siblings take it: q(b, t, c), the int8 value those entries write for the token, is never stored.
+ *   sum [B][C] int32 (dense, or NULL): sum over t0 <= t < t0 + T of q(b, t, c), exact.
+ *   out: int8, out[b * ldo + col0 + c] = floor((2 * sum + T) / (2 * T)) -- sum / T rounded to nearest, halves up -- at the scale of
+ *        the QuantAct; columns outside [col0, col0 + C) of a row are not touched (a column range of a feature bank row).
+ * Two launches: (image, slab of tokens) workgroups leave int32 partial sums in `workspace`, a second kernel adds the slabs and
+ * rounds.  Integer sums: the result does not depend on the slab length, which ivit_layernorm_pool_slab_rows reports (a host
+ * function, as ivit_layernorm_pool_workspace_bytes: *bytes for a call with that B, T, C).
+ * Errors, nothing launched: IVIT_ERR_INVALID for a NULL operand (sum excepted), B, T or C below 1, t0 < 0, t0 + T > T_all,
+ * ldx < C, col0 < 0, ldo < col0 + C, an unknown flag, out + col0 or (B > 1) ldo not a multiple of 4 bytes, sum or workspace not
+ * 16-byte aligned, a workspace that is too small; IVIT_ERR_UNSUPPORTED for T > 1025, C % 4 != 0, C > 2048 (the kernel keeps 28
+ * bytes of LDS per channel) and for what the token-feature entry of the kind declines. */
+int ivit_layernorm_pool_i8(const int8_t* x, int64_t ldx, int B, int T_all, int t0, int T, int C, const float* bias_int,
+                           const float* s_ln, const int8_t* remap /* [256] or NULL */, const float* phi /* [256] or NULL */,
+                           const uint32_t* m, const int32_t* e, int32_t* sum, int8_t* out, int64_t ldo, int64_t col0, int flags,
+                           void* workspace, int64_t workspace_bytes, ivit_stream_t stream);
+int ivit_layernorm_pool_i16(const int16_t* x, int64_t ldx, int B, int T_all, int t0, int T, int C, float s_in, const float* bias_int,
+                            const float* s_ln, const uint32_t* m, const int32_t* e, int32_t* sum, int8_t* out, int64_t ldo,
+                            int64_t col0, int flags, void* workspace, int64_t workspace_bytes, ivit_stream_t stream);
+int ivit_ibert_layernorm_pool_i8(const int8_t* x, int64_t ldx, int B, int T_all, int t0, int T, int C, float s_in,
+                                 const float* bias_int, const float* s_out, float shift_pow2, const uint32_t* m, const int32_t* e,
+                                 int32_t* sum, int8_t* out, int64_t ldo, int64_t col0, int flags, void* workspace,
+                                 int64_t workspace_bytes, ivit_stream_t stream);
+int ivit_ibert_layernorm_pool_i16(const int16_t* x, int64_t ldx, int B, int T_all, int t0, int T, int C, float s_in,
+                                  const float* bias_int, const float* s_out, float shift_pow2, const uint32_t* m, const int32_t* e,
+                                  int32_t* sum, int8_t* out, int64_t ldo, int64_t col0, int flags, void* workspace,
+                                  int64_t workspace_bytes, ivit_stream_t stream);
+int ivit_layernorm_pool_slab_rows(int B, int T, int* rows);
+int ivit_layernorm_pool_workspace_bytes(int B, int T, int C, int64_t* bytes);
+
 #ifdef __cplusplus
 }
 #endif
