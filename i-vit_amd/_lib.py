@@ -161,12 +161,16 @@ SIGNATURES = {
     # k-NN on the int8 feature bank (include/ivit_hip.h, end): ivit_knn_workspace_bytes is a host function
     "ivit_rows_rnorm_i8_f32": [vp, i64, i64, ci, vp, vp],
     "ivit_knn_topk_i8": [vp, i64, ci, vp, i64, ci, ci, vp, ci, ci, vp, vp, vp, i64, vp],
+    "ivit_knn_topk_i8_wide": [vp, i64, ci, vp, i64, ci, ci, vp, ci, ci, vp, vp, vp, i64, vp],
     "ivit_knn_workspace_bytes": [ci, ci, ci, ci, vp],
     "ivit_knn_vote_f32": [vp, vp, vp, ci, ci, ci, ci, vp, vp, vp],
     # linear probe on the int8 feature bank (include/ivit_hip.h, end): ivit_gram_workspace_bytes is a host function
     "ivit_gram_i8_i64": [vp, i64, i64, ci, ci, ci, vp, vp, i64, vp],
     "ivit_gram_workspace_bytes": [i64, ci, ci, vp],
     "ivit_group_sums_i8_i64": [vp, i64, i64, ci, vp, vp, ci, ci, vp, vp],
+    "ivit_gram_i8_i64_wide": [vp, i64, i64, ci, ci, ci, vp, vp, i64, vp],
+    "ivit_gram_wide_workspace_bytes": [i64, ci, ci, vp],
+    "ivit_group_sums_i8_i64_wide": [vp, i64, i64, ci, vp, vp, ci, ci, vp, vp],
     # dense linear probe (include/ivit_hip.h, end): acc, s_acc, batch, gh, gw, np, classes, r, labels, target, ignore_index, conf, stream
     "ivit_dense_argmax_u8": [vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, ci, vp, vp],
     "ivit_patch_mode_u8": [vp, ci, ci, ci, ci, ci, ci, vp, vp],

@@ -126,6 +126,14 @@ def occupancy_rules(path, what):
             if "tokens_to_nchw_kernel" not in name:
                 continue
             occ, need_no_scratch = 4, True
+        elif what == "knn" and "knn_splitc_kernel" in name:
+            # knn_splitc_kernel<SPW, PF> (the wide search): ONE workgroup of four waves per CU beside its 108.5 KiB of LDS (its
+            # __launch_bounds__; the launcher's segment rule then gives two rounds of the 256 CUs): one wave per SIMD.  The query
+            # fragments and the ring of bank fragments (up to 2 x 16 x 4 + 2 x 16 x 4 registers) are indexed by constants only: no scratch
+            occ, need_no_scratch = 1, True
+            if r.get("LDS", 0) > 163840:
+                print("FAIL", name, "LDS", r.get("LDS"), "above 160 KiB: the workgroup does not fit a CU")
+                return 1
         elif what == "knn":
             # knn_topk_kernel<KSMAX>: two workgroups of four waves per CU (its __launch_bounds__, beside 2 x 76.5 KiB of LDS); the query
             # and bank fragments (up to 192 VGPRs) are indexed by constants only: no scratch.  The merge, rnorm and vote kernels

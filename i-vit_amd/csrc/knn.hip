@@ -2,6 +2,7 @@
 //   ivit_rows_rnorm_i8_f32   rnorm[j] = 1 / sqrt(sum_c b[j][c]^2) in float32 (0 for a zero row), one wave per bank row
 //   ivit_knn_topk_i8         score[i][j] = fl32((float)dot(q_i, b_j) * rnorm[j]) on v_mfma_i32_16x16x64_i8, the k best per query selected
 //                            in the epilogue; a second small kernel merges the lists of the bank segments
+//   ivit_knn_topk_i8_wide    the same search for rows of up to 4096 channels: knn_splitc_kernel splits the channels, not the bank rows, over the waves
 //   ivit_knn_vote_f32        weighted vote among a query's own k neighbours
 //
 // The search kernel.  A workgroup (4 waves) owns KN_QT = 32 queries and one bank segment.  Every wave holds the fragments of all 32
@@ -98,14 +99,105 @@ IVIT_DEV void knn_insert(u64* lists, u64* thr, int* cntl, int* minpos, int q, u6
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// the selection state of a workgroup in LDS (header comment, "Selection") and its three steps, shared by both search kernels
+struct KnnSel {
+    __attribute__((aligned(16))) u64 lists[KN_QT * KN_KCAP];
+    u64 thr[KN_QT];
+    unsigned cskey[KN_CAND];
+    unsigned short cmeta[KN_CAND];      // (row in tile) << 5 | query in tile
+    int cntl[KN_QT], minpos[KN_QT], cnt[2];
+};
+
+IVIT_DEV void knn_sel_init(KnnSel& S, int tid)
+{
+    if (tid < KN_QT) {
+        S.thr[tid] = 0;
+        S.cntl[tid] = 0;
+        S.minpos[tid] = 0;
+    }
+    if (tid < 2) S.cnt[tid] = 0;
+}
+
+// the epilogue of 16 bank rows x 32 queries: acc[qt][r] of lane (g, l15) = dot(row rbase + r, query 16 qt + l15), rt0 = the tile row of
+// rbase.  A key above its query's threshold goes into the tile's candidate buffer (counter cs)
+IVIT_DEV void knn_epilogue(KnnSel& S, const v4i (&acc)[2], const float (&rn)[4], unsigned rbase, int rt0, int q0, int Q, int r_end, int cs, int l15)
+{
+#pragma unroll
+    for (int qt = 0; qt < 2; ++qt) {
+        const int ql = 16 * qt + l15;
+        const u64 th = S.thr[ql];
+        const bool qok = q0 + ql < Q;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const unsigned row = rbase + r;
+            const unsigned sk = knn_skey((float)acc[qt][r] * rn[r]);      // ONE float32 multiplication (-ffp-contract=off)
+            const u64 key = ((u64)sk << 32) | (u64)(0xffffffffu - row);
+            if (qok && row < (unsigned)r_end && key > th) {
+                const int slot = atomicAdd(&S.cnt[cs], 1);                // < KN_CAND: one per (row, query) of the tile
+                S.cskey[slot] = sk;
+                S.cmeta[slot] = (unsigned short)(((rt0 + r) << 5) | ql);
+            }
+        }
+    }
+}
+
+// behind the barrier that ends the epilogues: wave w inserts the candidates of the queries q % 4 == w
+IVIT_DEV void knn_drain(KnnSel& S, unsigned tile_base, int cs, int k, int tid, int lane, int wave)
+{
+    const int n = S.cnt[cs];
+    if (tid == 0) S.cnt[cs ^ 1] = 0;      // next tile's counter: last read before the barrier that ended the previous tile's epilogues
+    for (int e0 = 0; e0 < n; e0 += 64) {
+        const int e = e0 + lane;
+        unsigned sk = 0, me = 0;
+        bool mine = false;
+        if (e < n) {
+            sk = S.cskey[e];
+            me = S.cmeta[e];
+            mine = (int)(me & 3u) == wave;
+        }
+        u64 mask = __builtin_amdgcn_ballot_w64(mine);
+        while (mask) {
+            const int src = __builtin_ctzll(mask);
+            mask &= mask - 1;
+            const unsigned sk1 = (unsigned)__builtin_amdgcn_readlane((int)sk, src), me1 = (unsigned)__builtin_amdgcn_readlane((int)me, src);
+            const u64 key = ((u64)sk1 << 32) | (u64)(0xffffffffu - (tile_base + (me1 >> 5)));
+            knn_insert(S.lists, S.thr, S.cntl, S.minpos, (int)(me1 & 31u), key, k, lane);
+        }
+    }
+}
+
+// rank and write: wave w the queries q % 4 == w (its own lists; with no tile at all the lists are empty)
+IVIT_DEV void knn_finish(const KnnSel& S, const KnnArgs& a, int q0, int s, int lane, int wave)
+{
+    const int k = a.k;
+    for (int ql = wave; ql < KN_QT; ql += 4) {
+        const int q = q0 + ql;
+        if (q >= a.Q) break;
+        const u64* L = S.lists + ql * KN_KCAP;
+        const int c = S.cntl[ql];
+        for (int j = lane; j < k; j += 64) {
+            u64 key = 0;
+            int rank = j;               // positions c .. k - 1: no entry
+            if (j < c) {
+                key = L[j];
+                rank = 0;
+                for (int i = 0; i < c; ++i) rank += L[i] > key ? 1 : 0;
+            }
+            if (a.splits == 1) {        // c == k: k <= N
+                const int64_t o = (int64_t)q * k + rank;
+                a.idx[o] = (int32_t)(0xffffffffu - (unsigned)key);
+                a.score[o] = knn_score_of((unsigned)(key >> 32));
+            } else {
+                a.ws[((int64_t)q * a.splits + s) * k + rank] = key;
+            }
+        }
+    }
+}
+
 template <int KSMAX>
 __global__ __launch_bounds__(KN_NT, 2) void knn_topk_kernel(KnnArgs a)
 {
-    __shared__ __attribute__((aligned(16))) u64 lists[KN_QT * KN_KCAP];
-    __shared__ u64 thr[KN_QT];
-    __shared__ unsigned cskey[KN_CAND];
-    __shared__ unsigned short cmeta[KN_CAND];      // (row in tile) << 5 | query in tile
-    __shared__ int cntl[KN_QT], minpos[KN_QT], cnt[2];
+    __shared__ KnnSel S;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, l15 = lane & 15;
     // consecutive workgroups: the query tiles of one segment, so that the workgroups in flight walk the same bank rows
@@ -115,12 +207,7 @@ __global__ __launch_bounds__(KN_NT, 2) void knn_topk_kernel(KnnArgs a)
     const int r_begin = rb64 < a.N ? (int)rb64 : a.N, r_end = re64 < a.N ? (int)re64 : a.N;
     const int KS = a.KS, k = a.k;
 
-    if (tid < KN_QT) {
-        thr[tid] = 0;
-        cntl[tid] = 0;
-        minpos[tid] = 0;
-    }
-    if (tid < 2) cnt[tid] = 0;
+    knn_sel_init(S, tid);
 
     v4i qf[2][KSMAX];
 #pragma unroll
@@ -162,70 +249,103 @@ __global__ __launch_bounds__(KN_NT, 2) void knn_topk_kernel(KnnArgs a)
             }
         }
         const int cs = t & 1;
+        knn_epilogue(S, acc, rn, rbase, 16 * wave + 4 * g, q0, a.Q, r_end, cs, l15);
+        __syncthreads();
+        knn_drain(S, tile_base, cs, k, tid, lane, wave);
+        __syncthreads();
+    }
+    knn_finish(S, a, q0, s, lane, wave);
+}
+
+// The wide search kernel (C up to IVIT_KNN_C_WIDE_MAX): the CHANNELS are split over the four waves, not the bank rows.  Wave w owns the K
+// steps w, w + 4, ... of the C / 64 (at most SPW = 16 of them) and holds only those of the 32 queries (2 x SPW x 4 VGPRs: today's 128 at
+// C = 4096).  All four waves walk the same bank rows in sub-tiles of 16: a wave's fragments of a sub-tile (SPW x 4 VGPRs) go from
+// global memory straight into MFMA operand registers and are re-issued, PF sub-tiles ahead, right behind the MFMAs that consumed them.
+// The partial accumulators of the four sub-tiles of a 64-row tile (2 x v4i per lane and sub-tile) go to LDS, [sub-tile][wave][query
+// half][lane] in 16-byte pieces (32 KiB); behind one barrier wave w adds the four partials of sub-tile w -- int32, exact, any order --
+// and holds dot(row 16 w + 4 g + r, query l15) in the lane layout of knn_topk_kernel: from there on the code is the shared one.
+// A wave without a K step (C = 64, 128, 192) writes zeros.
+// Barriers: two per tile.  The partials of tile t are last read before the barrier that ends tile t's epilogues, and everything the
+// insertions of tile t write (lists, thresholds, the next counter) is first read behind the barrier that follows tile t + 1's MFMAs,
+// so the insertions of one tile and the MFMAs of the next need no barrier between them.
+// LDS is 108.5 KiB: ONE workgroup per CU (one wave per SIMD, up to 512 registers each), which is why the bank is prefetched deeper.
+template <int SPW, int PF>
+__global__ __launch_bounds__(KN_NT, 1) void knn_splitc_kernel(KnnArgs a)
+{
+    static_assert(PF == 1 || PF == 2 || PF == 4, "the prefetch ring must divide the four sub-tiles of a tile");
+    __shared__ KnnSel S;
+    __shared__ __attribute__((aligned(16))) v4i part[4][4][2][64];
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), g = lane >> 4, l15 = lane & 15;
+    const int qtile = (int)(blockIdx.x % (unsigned)a.qtiles), s = (int)(blockIdx.x / (unsigned)a.qtiles);
+    const int q0 = qtile * KN_QT;
+    const int64_t rb64 = (int64_t)s * a.seg, re64 = rb64 + a.seg;
+    const int r_begin = rb64 < a.N ? (int)rb64 : a.N, r_end = re64 < a.N ? (int)re64 : a.N;
+    const int k = a.k;
+    const int steps = (a.KS - wave + 3) >> 2;      // this wave's K steps: wave + 4 i, i < steps <= SPW (0 for a wave beyond C / 64)
+    const int koff = 64 * wave + 16 * g;           // its 16 bytes of step i: koff + 256 i
+
+    knn_sel_init(S, tid);
+
+    v4i qf[2][SPW];
 #pragma unroll
-        for (int qt = 0; qt < 2; ++qt) {
-            const int ql = 16 * qt + l15;
-            const u64 th = thr[ql];
-            const bool qok = q0 + ql < a.Q;
+    for (int qt = 0; qt < 2; ++qt) {
+        const int8_t* qp = a.q + (int64_t)min(q0 + 16 * qt + l15, a.Q - 1) * a.ldq + koff;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const unsigned row = rbase + r;
-                const unsigned sk = knn_skey((float)acc[qt][r] * rn[r]);      // ONE float32 multiplication (-ffp-contract=off)
-                const u64 key = ((u64)sk << 32) | (u64)(0xffffffffu - row);
-                if (qok && row < (unsigned)r_end && key > th) {
-                    const int slot = atomicAdd(&cnt[cs], 1);                  // < KN_CAND: one per (row, query) of the tile
-                    cskey[slot] = sk;
-                    cmeta[slot] = (unsigned short)(((16 * wave + 4 * g + r) << 5) | ql);
+        for (int i = 0; i < SPW; ++i) {
+            qf[qt][i] = v4i{0, 0, 0, 0};
+            if (i < steps) qf[qt][i] = *reinterpret_cast<const v4i*>(qp + 256 * i);
+        }
+    }
+    __syncthreads();
+
+    const int ntiles = (r_end - r_begin + KN_BT - 1) / KN_BT;
+    // sub-tile j of the segment: rows r_begin + 16 j .. + 15, for every wave (unsigned: N < 2^31; a sub-tile beyond the bank asks for
+    // row N - 1: a row that exists)
+    auto subtile = [&](int j) { return a.bank + (int64_t)min((unsigned)r_begin + (unsigned)(16 * j + l15), (unsigned)(a.N - 1)) * a.ldb + koff; };
+    v4i bf[PF][SPW];
+    if (ntiles > 0) {
+#pragma unroll
+        for (int d = 0; d < PF; ++d) {
+            const int8_t* p = subtile(d);
+#pragma unroll
+            for (int i = 0; i < SPW; ++i) {
+                bf[d][i] = v4i{0, 0, 0, 0};
+                if (i < steps) bf[d][i] = *reinterpret_cast<const v4i*>(p + 256 * i);
+            }
+        }
+    }
+    for (int t = 0; t < ntiles; ++t) {
+        const unsigned tile_base = (unsigned)r_begin + (unsigned)(KN_BT * t);
+        const unsigned rbase = tile_base + (unsigned)(16 * wave + 4 * g);      // the rows whose epilogue is this wave's
+        float rn[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) rn[r] = a.rnorm[min(rbase + r, (unsigned)(a.N - 1))];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int8_t* pn = subtile(4 * t + u + PF);
+            v4i pa[2] = {v4i{0, 0, 0, 0}, v4i{0, 0, 0, 0}};
+#pragma unroll
+            for (int i = 0; i < SPW; ++i) {
+                if (i < steps) {
+                    pa[0] = __builtin_amdgcn_mfma_i32_16x16x64_i8(bf[u % PF][i], qf[0][i], pa[0], 0, 0, 0);
+                    pa[1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(bf[u % PF][i], qf[1][i], pa[1], 0, 0, 0);
+                    bf[u % PF][i] = *reinterpret_cast<const v4i*>(pn + 256 * i);
                 }
             }
+            part[u][wave][0][lane] = pa[0];
+            part[u][wave][1][lane] = pa[1];
         }
         __syncthreads();
-        const int n = cnt[cs];
-        if (tid == 0) cnt[cs ^ 1] = 0;      // next tile's counter: last read before the previous tile's second barrier
-        for (int e0 = 0; e0 < n; e0 += 64) {
-            const int e = e0 + lane;
-            unsigned sk = 0, me = 0;
-            bool mine = false;
-            if (e < n) {
-                sk = cskey[e];
-                me = cmeta[e];
-                mine = (int)(me & 3u) == wave;
-            }
-            u64 mask = __builtin_amdgcn_ballot_w64(mine);
-            while (mask) {
-                const int src = __builtin_ctzll(mask);
-                mask &= mask - 1;
-                const unsigned sk1 = (unsigned)__builtin_amdgcn_readlane((int)sk, src), me1 = (unsigned)__builtin_amdgcn_readlane((int)me, src);
-                const u64 key = ((u64)sk1 << 32) | (u64)(0xffffffffu - (tile_base + (me1 >> 5)));
-                knn_insert(lists, thr, cntl, minpos, (int)(me1 & 31u), key, k, lane);
-            }
-        }
+        v4i acc[2];
+#pragma unroll
+        for (int qt = 0; qt < 2; ++qt) acc[qt] = (part[wave][0][qt][lane] + part[wave][1][qt][lane]) + (part[wave][2][qt][lane] + part[wave][3][qt][lane]);
+        const int cs = t & 1;
+        knn_epilogue(S, acc, rn, rbase, 16 * wave + 4 * g, q0, a.Q, r_end, cs, l15);
         __syncthreads();
+        knn_drain(S, tile_base, cs, k, tid, lane, wave);
     }
-
-    // rank and write: wave w the queries q % 4 == w (its own lists; with no tile at all the lists are empty)
-    for (int ql = wave; ql < KN_QT; ql += 4) {
-        const int q = q0 + ql;
-        if (q >= a.Q) break;
-        const u64* L = lists + ql * KN_KCAP;
-        const int c = cntl[ql];
-        for (int j = lane; j < k; j += 64) {
-            u64 key = 0;
-            int rank = j;               // positions c .. k - 1: no entry
-            if (j < c) {
-                key = L[j];
-                rank = 0;
-                for (int i = 0; i < c; ++i) rank += L[i] > key ? 1 : 0;
-            }
-            if (a.splits == 1) {        // c == k: k <= N
-                const int64_t o = (int64_t)q * k + rank;
-                a.idx[o] = (int32_t)(0xffffffffu - (unsigned)key);
-                a.score[o] = knn_score_of((unsigned)(key >> 32));
-            } else {
-                a.ws[((int64_t)q * a.splits + s) * k + rank] = key;
-            }
-        }
-    }
+    knn_finish(S, a, q0, s, lane, wave);
 }
 
 // the lists of a query's segments (each descending, 0 = no entry, all keys distinct) -> the k largest keys, descending
@@ -379,15 +499,17 @@ IVIT_EXPORT int ivit_knn_workspace_bytes(int Q, int N, int k, int splits, int64_
     return IVIT_OK;
 }
 
-IVIT_EXPORT int ivit_knn_topk_i8(const int8_t* q, int64_t ldq, int Q, const int8_t* bank, int64_t ldb, int N, int C, const float* rnorm, int k,
-                                 int splits, int32_t* idx, float* score, void* workspace, int64_t workspace_bytes, ivit_stream_t stream)
+namespace {
+
+// both search entries: the checks, the segment plan and the merge are shared; cmax picks the kernel family
+int knn_search(const char* who, int cmax, const int8_t* q, int64_t ldq, int Q, const int8_t* bank, int64_t ldb, int N, int C, const float* rnorm, int k,
+               int splits, int32_t* idx, float* score, void* workspace, int64_t workspace_bytes, ivit_stream_t stream)
 {
-    const char* who = "ivit_knn_topk_i8";
     IVIT_REQUIRE(q && bank && rnorm && idx && score, "%s: NULL operand", who);
     const int rc = knn_check_shape(who, Q, N, k, splits);
     if (rc != IVIT_OK) return rc;
-    if (C < 64 || C > 1024 || C % 64 != 0) {
-        ivit_set_error("%s: unsupported geometry (C=%d: multiples of 64 from 64 to 1024)", who, C);
+    if (C < 64 || C > cmax || C % 64 != 0) {
+        ivit_set_error("%s: unsupported geometry (C=%d: multiples of 64 from 64 to %d)", who, C, cmax);
         return IVIT_ERR_UNSUPPORTED;
     }
     IVIT_REQUIRE(ldq >= C && ldb >= C, "%s: ldq=%lld / ldb=%lld below C=%d", who, (long long)ldq, (long long)ldb, C);
@@ -407,13 +529,36 @@ IVIT_EXPORT int ivit_knn_topk_i8(const int8_t* q, int64_t ldq, int Q, const int8
     const int bpq = (sp * k + KN_NT - 1) / KN_NT;
     IVIT_REQUIRE(grid <= 0x7fffffff && (int64_t)Q * bpq <= 0x7fffffff, "%s: Q=%d with %d segments: too many workgroups", who, Q, sp);
     const hipStream_t st = ivit_stream(stream);
-    if (a.KS <= 4) hipLaunchKernelGGL(knn_topk_kernel<4>, dim3((unsigned)grid), dim3(KN_NT), 0, st, a);
-    else if (a.KS <= 8) hipLaunchKernelGGL(knn_topk_kernel<8>, dim3((unsigned)grid), dim3(KN_NT), 0, st, a);
-    else if (a.KS <= 12) hipLaunchKernelGGL(knn_topk_kernel<12>, dim3((unsigned)grid), dim3(KN_NT), 0, st, a);
-    else hipLaunchKernelGGL(knn_topk_kernel<16>, dim3((unsigned)grid), dim3(KN_NT), 0, st, a);
+    const dim3 gd((unsigned)grid), bd(KN_NT);
+    if (cmax == IVIT_KNN_C_WIDE_MAX) {
+        const int spw = (a.KS + 3) / 4;      // K steps of wave 0, the most any wave owns
+        if (spw <= 4) hipLaunchKernelGGL((knn_splitc_kernel<4, 4>), gd, bd, 0, st, a);
+        else if (spw <= 6) hipLaunchKernelGGL((knn_splitc_kernel<6, 4>), gd, bd, 0, st, a);
+        else if (spw <= 8) hipLaunchKernelGGL((knn_splitc_kernel<8, 4>), gd, bd, 0, st, a);
+        else if (spw <= 12) hipLaunchKernelGGL((knn_splitc_kernel<12, 2>), gd, bd, 0, st, a);
+        else hipLaunchKernelGGL((knn_splitc_kernel<16, 2>), gd, bd, 0, st, a);
+    } else if (a.KS <= 4) hipLaunchKernelGGL(knn_topk_kernel<4>, gd, bd, 0, st, a);
+    else if (a.KS <= 8) hipLaunchKernelGGL(knn_topk_kernel<8>, gd, bd, 0, st, a);
+    else if (a.KS <= 12) hipLaunchKernelGGL(knn_topk_kernel<12>, gd, bd, 0, st, a);
+    else hipLaunchKernelGGL(knn_topk_kernel<16>, gd, bd, 0, st, a);
     if (sp > 1)
         hipLaunchKernelGGL(knn_merge_kernel, dim3((unsigned)((int64_t)Q * bpq)), dim3(KN_NT), 0, st, a.ws, sp, k, bpq, idx, score);
     IVIT_CHECK_LAUNCH(who);
+}
+
+}      // namespace
+
+IVIT_EXPORT int ivit_knn_topk_i8(const int8_t* q, int64_t ldq, int Q, const int8_t* bank, int64_t ldb, int N, int C, const float* rnorm, int k,
+                                 int splits, int32_t* idx, float* score, void* workspace, int64_t workspace_bytes, ivit_stream_t stream)
+{
+    return knn_search("ivit_knn_topk_i8", 1024, q, ldq, Q, bank, ldb, N, C, rnorm, k, splits, idx, score, workspace, workspace_bytes, stream);
+}
+
+IVIT_EXPORT int ivit_knn_topk_i8_wide(const int8_t* q, int64_t ldq, int Q, const int8_t* bank, int64_t ldb, int N, int C, const float* rnorm, int k,
+                                      int splits, int32_t* idx, float* score, void* workspace, int64_t workspace_bytes, ivit_stream_t stream)
+{
+    return knn_search("ivit_knn_topk_i8_wide", IVIT_KNN_C_WIDE_MAX, q, ldq, Q, bank, ldb, N, C, rnorm, k, splits, idx, score, workspace,
+                      workspace_bytes, stream);
 }
 
 IVIT_EXPORT int ivit_knn_vote_f32(const int32_t* idx, const int32_t* labels, const float* w, int Q, int N, int k, int r, int32_t* classes,

@@ -214,11 +214,11 @@ __global__ __launch_bounds__(GR_NT) void group_sums_kernel(const int8_t* __restr
     }
 }
 
-// the bank geometry both entries share (knn.FeatureBank's)
-int probe_check_shape(const char* who, int64_t rows, int C)
+// the bank geometry the entries share (knn.FeatureBank's): cmax = 1024, or IVIT_KNN_C_WIDE_MAX for the _wide entries
+int probe_check_shape(const char* who, int64_t rows, int C, int cmax)
 {
-    if (C < 64 || C > 1024 || C % 64 != 0) {
-        ivit_set_error("%s: unsupported geometry (C=%d: multiples of 64 from 64 to 1024)", who, C);
+    if (C < 64 || C > cmax || C % 64 != 0) {
+        ivit_set_error("%s: unsupported geometry (C=%d: multiples of 64 from 64 to %d)", who, C, cmax);
         return IVIT_ERR_UNSUPPORTED;
     }
     IVIT_REQUIRE(rows >= 0 && rows <= 0x7fffffffLL, "%s: rows=%lld outside [0, 2^31)", who, (long long)rows);
@@ -243,9 +243,9 @@ int gram_splits(int64_t rows, int C, int splits)
 }
 
 // -> segment length, slabs per segment and the workspace size for a checked shape
-int gram_plan(const char* who, int64_t rows, int C, int splits, int* sp, int64_t* seg, int* cps, int64_t* bytes)
+int gram_plan(const char* who, int cmax, int64_t rows, int C, int splits, int* sp, int64_t* seg, int* cps, int64_t* bytes)
 {
-    if (const int rc = probe_check_shape(who, rows, C)) return rc;
+    if (const int rc = probe_check_shape(who, rows, C, cmax)) return rc;
     IVIT_REQUIRE(splits >= 0 && splits <= IVIT_GRAM_SPLITS_MAX, "%s: splits=%d outside [0, %d]", who, splits, IVIT_GRAM_SPLITS_MAX);
     *sp = gram_splits(rows, C, splits);
     *seg = ((rows + *sp - 1) / *sp + GR_RT - 1) / GR_RT * GR_RT;
@@ -254,28 +254,25 @@ int gram_plan(const char* who, int64_t rows, int C, int splits, int* sp, int64_t
     return IVIT_OK;
 }
 
-}      // namespace
-
-IVIT_EXPORT int ivit_gram_workspace_bytes(int64_t rows, int C, int splits, int64_t* bytes)
+// the entries and their _wide namesakes: one body each, the kernels do not depend on the width
+int gram_bytes(const char* who, int cmax, int64_t rows, int C, int splits, int64_t* bytes)
 {
-    const char* who = "ivit_gram_workspace_bytes";
     IVIT_REQUIRE(bytes, "%s: NULL pointer", who);
     int sp, cps;
     int64_t seg, need;
-    const int rc = gram_plan(who, rows, C, splits, &sp, &seg, &cps, &need);
+    const int rc = gram_plan(who, cmax, rows, C, splits, &sp, &seg, &cps, &need);
     if (rc != IVIT_OK) return rc;
     *bytes = need;
     return IVIT_OK;
 }
 
-IVIT_EXPORT int ivit_gram_i8_i64(const int8_t* x, int64_t ldx, int64_t rows, int C, int splits, int accumulate, int64_t* gram, void* workspace,
-                                 int64_t workspace_bytes, ivit_stream_t stream)
+int gram_run(const char* who, int cmax, const int8_t* x, int64_t ldx, int64_t rows, int C, int splits, int accumulate, int64_t* gram, void* workspace,
+             int64_t workspace_bytes, ivit_stream_t stream)
 {
-    const char* who = "ivit_gram_i8_i64";
     IVIT_REQUIRE(x && gram, "%s: NULL operand", who);
     int sp, cps;
     int64_t seg, need;
-    int rc = gram_plan(who, rows, C, splits, &sp, &seg, &cps, &need);
+    int rc = gram_plan(who, cmax, rows, C, splits, &sp, &seg, &cps, &need);
     if (rc != IVIT_OK) return rc;
     rc = probe_check_rows(who, x, ldx, C);
     if (rc != IVIT_OK) return rc;
@@ -295,16 +292,52 @@ IVIT_EXPORT int ivit_gram_i8_i64(const int8_t* x, int64_t ldx, int64_t rows, int
     IVIT_CHECK_LAUNCH(who);
 }
 
-IVIT_EXPORT int ivit_group_sums_i8_i64(const int8_t* x, int64_t ldx, int64_t rows, int C, const int32_t* perm, const int64_t* group_ptr, int groups,
-                                       int accumulate, int64_t* sums, ivit_stream_t stream)
+// slots = 256 / (C / 16) rows side by side: 4 at C = 1024, 3, 2 or 1 above (threads beyond slots * C / 16 idle; `part` holds slots * C <= 4096 sums)
+int group_sums_run(const char* who, int cmax, const int8_t* x, int64_t ldx, int64_t rows, int C, const int32_t* perm, const int64_t* group_ptr, int groups,
+                   int accumulate, int64_t* sums, ivit_stream_t stream)
 {
-    const char* who = "ivit_group_sums_i8_i64";
     IVIT_REQUIRE(x && perm && group_ptr && sums, "%s: NULL operand", who);
-    if (const int rc = probe_check_shape(who, rows, C)) return rc;
+    if (const int rc = probe_check_shape(who, rows, C, cmax)) return rc;
     if (const int rc = probe_check_rows(who, x, ldx, C)) return rc;
     IVIT_REQUIRE(groups >= 1 && groups <= IVIT_GROUPS_MAX, "%s: groups=%d outside [1, %d]", who, groups, IVIT_GROUPS_MAX);
     IVIT_REQUIRE(accumulate == 0 || accumulate == 1, "%s: accumulate=%d is neither 0 nor 1", who, accumulate);
     IVIT_REQUIRE((uintptr_t)perm % 4 == 0 && ((uintptr_t)group_ptr | (uintptr_t)sums) % 8 == 0, "%s: perm, group_ptr or sums is not aligned to its element", who);
     hipLaunchKernelGGL(group_sums_kernel, dim3((unsigned)groups), dim3(GR_NT), 0, ivit_stream(stream), x, ldx, C, perm, group_ptr, accumulate, sums);
     IVIT_CHECK_LAUNCH(who);
+}
+
+}      // namespace
+
+IVIT_EXPORT int ivit_gram_workspace_bytes(int64_t rows, int C, int splits, int64_t* bytes)
+{
+    return gram_bytes("ivit_gram_workspace_bytes", 1024, rows, C, splits, bytes);
+}
+
+IVIT_EXPORT int ivit_gram_wide_workspace_bytes(int64_t rows, int C, int splits, int64_t* bytes)
+{
+    return gram_bytes("ivit_gram_wide_workspace_bytes", IVIT_KNN_C_WIDE_MAX, rows, C, splits, bytes);
+}
+
+IVIT_EXPORT int ivit_gram_i8_i64(const int8_t* x, int64_t ldx, int64_t rows, int C, int splits, int accumulate, int64_t* gram, void* workspace,
+                                 int64_t workspace_bytes, ivit_stream_t stream)
+{
+    return gram_run("ivit_gram_i8_i64", 1024, x, ldx, rows, C, splits, accumulate, gram, workspace, workspace_bytes, stream);
+}
+
+IVIT_EXPORT int ivit_gram_i8_i64_wide(const int8_t* x, int64_t ldx, int64_t rows, int C, int splits, int accumulate, int64_t* gram, void* workspace,
+                                      int64_t workspace_bytes, ivit_stream_t stream)
+{
+    return gram_run("ivit_gram_i8_i64_wide", IVIT_KNN_C_WIDE_MAX, x, ldx, rows, C, splits, accumulate, gram, workspace, workspace_bytes, stream);
+}
+
+IVIT_EXPORT int ivit_group_sums_i8_i64(const int8_t* x, int64_t ldx, int64_t rows, int C, const int32_t* perm, const int64_t* group_ptr, int groups,
+                                       int accumulate, int64_t* sums, ivit_stream_t stream)
+{
+    return group_sums_run("ivit_group_sums_i8_i64", 1024, x, ldx, rows, C, perm, group_ptr, groups, accumulate, sums, stream);
+}
+
+IVIT_EXPORT int ivit_group_sums_i8_i64_wide(const int8_t* x, int64_t ldx, int64_t rows, int C, const int32_t* perm, const int64_t* group_ptr,
+                                            int groups, int accumulate, int64_t* sums, ivit_stream_t stream)
+{
+    return group_sums_run("ivit_group_sums_i8_i64_wide", IVIT_KNN_C_WIDE_MAX, x, ldx, rows, C, perm, group_ptr, groups, accumulate, sums, stream);
 }

@@ -221,14 +221,16 @@ def _features_into(model, x, rows, integers, graph, norm=None):
     return scale
 
 
-def pooled_width(model, n_last: int = 1, avgpool: bool = False):
+def pooled_width(model, n_last: int = 1, avgpool: bool = False, wide: bool = False):
     """Width W = n_last * C (+ C with avgpool) of model.features_pooled's rows, checked against what the feature-bank kernels take
-    (knn.FeatureBank, probe.BankStats: W % 64 == 0 in 64..1024): ValueError otherwise, before anything is extracted"""
+    (knn.FeatureBank, probe.BankStats: W % 64 == 0 in 64..1024; with wide=True in 64..4096, the range of the wide kernels -- the
+    protocol's ViT-S n_last=4, ViT-B + avgpool and ViT-L + avgpool): ValueError otherwise, before anything is extracted"""
     C = int(model.num_features)
     W = int(n_last) * C + (C if avgpool else 0)
-    if int(n_last) < 1 or W % 64 or not 64 <= W <= 1024:
+    if int(n_last) < 1 or W % 64 or not 64 <= W <= (4096 if wide else 1024):
         raise ValueError(f"pooled features of width W={W} (n_last={n_last}, avgpool={bool(avgpool)}, C={C}): the feature-bank kernels "
-                         "take rows of W % 64 == 0 channels, W in 64..1024")
+                         + ("take rows of W % 64 == 0 channels, W in 64..4096" if wide else
+                            "take rows of W % 64 == 0 channels, W in 64..1024 (to 4096: pass wide=True)"))
     return W
 
 
@@ -254,7 +256,7 @@ def _sized(data_loader):
 
 
 def extract_features(model, data_loader, device, *, transform=None, graph: bool = False, integers: bool = False, n_last: int = 1,
-                     avgpool: bool = False):
+                     avgpool: bool = False, wide: bool = False):
     """The embeddings of a dataset -> (features [N, C], labels int64 [N], scale), rows in loader order, on `device`: what linear
     probing, a retrieval bank or k-NN evaluation start from.  features: float32, model.features' tensor (integers times scale), or
     with integers=True the int8 integers; scale: the float32 act_scaling_factor they carry (None for an empty loader).
@@ -267,9 +269,10 @@ def extract_features(model, data_loader, device, *, transform=None, graph: bool 
     checked once after the loop.
     n_last, avgpool: anything but the defaults extracts model.features_pooled(x, n_last, avgpool) instead -- the class tokens of the
     last n_last blocks and, with avgpool, the mean patch token, W = n_last * C (+ C) columns (pooled_width: ValueError, before the
-    loader is touched, for a W the feature-bank kernels do not take) -- on the fused engine, eagerly (graph=True: ValueError)."""
+    loader is touched, for a W the feature-bank kernels do not take; wide=True admits W up to 4096) -- on the fused engine, eagerly
+    (graph=True: ValueError)."""
     pooled = int(n_last) != 1 or bool(avgpool)
-    C = pooled_width(model, n_last, avgpool) if pooled else int(model.num_features)
+    C = pooled_width(model, n_last, avgpool, wide) if pooled else int(model.num_features)
     if pooled and graph:
         raise ValueError("extract_features: features_pooled is not part of the graph replays (graph=False)")
     data_loader, N = _sized(data_loader)
@@ -307,16 +310,19 @@ def extract_features(model, data_loader, device, *, transform=None, graph: bool 
 
 
 def evaluate_knn(model, bank_loader, query_loader, device, *, k=(10, 20, 100, 200), T: float = 0.07, transform=None, graph: bool = False,
-                 n_last: int = 1, avgpool: bool = False):
+                 n_last: int = 1, avgpool: bool = False, wide: bool = False):
     """Weighted k-NN accuracy of a backbone -> {k: (top-1 %, top-5 %)}.  Both sets go through extract_features(..., integers=True);
     the bank stays int8 (knn.FeatureBank) and ONE search at max(k) serves every k: the neighbour order is total, so the neighbours
     for a smaller k are a prefix.  Per k the neighbours vote with w = exp(cos / T) (knn.knn_weights); top-5 counts a hit among the
     first min(5, k) voted classes.  The two extractions must carry the same scale (the same frozen model): anything else raises.
-    n_last, avgpool: the pooled feature of extract_features for both sets."""
+    n_last, avgpool, wide: the pooled feature of extract_features for both sets (wide=True: rows of up to 4096 channels, searched
+    by the kernel that splits the channels over the waves)."""
     ks = tuple(sorted({int(v) for v in ((k,) if isinstance(k, int) else k)}))
     if not ks or ks[0] < 1:
         raise ValueError(f"evaluate_knn: k={k!r}")
     pooled = {} if int(n_last) == 1 and not avgpool else dict(n_last=n_last, avgpool=avgpool)      # (the defaults: the call as it always was)
+    if pooled and wide:
+        pooled["wide"] = True
     rows, labels, s_bank = extract_features(model, bank_loader, device, transform=transform, graph=graph, integers=True, **pooled)
     q, targets, s_query = extract_features(model, query_loader, device, transform=transform, graph=graph, integers=True, **pooled)
     if s_bank is None or s_query is None:
@@ -339,19 +345,21 @@ def evaluate_knn(model, bank_loader, query_loader, device, *, k=(10, 20, 100, 20
 
 
 def evaluate_linear_probe(model, bank_loader, query_loader, device, num_classes, *, lam=(1e-4, 1e-3, 1e-2, 1e-1, 1.0), kind: str = "ridge",
-                          transform=None, graph: bool = False, n_last: int = 1, avgpool: bool = False):
+                          transform=None, graph: bool = False, n_last: int = 1, avgpool: bool = False, wide: bool = False):
     """Linear-probe accuracy of a backbone -> {lam: (top-1 %, top-5 %)}.  Both sets go through extract_features(..., integers=True);
     the bank stays int8 and its statistics (probe.BankStats: exact Gram matrix, class sums and counts) are computed ONCE; per lam
     there is one C x C solve on the host (BankStats.ridge) and one int8 head GEMM with the top-5 selection over the queries
     (LinearProbe.topk).  kind="ncm": the class-mean classifier instead, a single entry under the key None.  The two extractions
-    must carry the same scale (the same frozen model): anything else raises.  n_last, avgpool: the pooled feature of
-    extract_features for both sets."""
+    must carry the same scale (the same frozen model): anything else raises.  n_last, avgpool, wide: the pooled feature of
+    extract_features for both sets (wide=True: rows of up to 4096 channels)."""
     if kind not in ("ridge", "ncm"):
         raise ValueError(f"evaluate_linear_probe: kind={kind!r} is neither 'ridge' nor 'ncm'")
     lams = (None,) if kind == "ncm" else tuple(float(v) for v in ((lam,) if isinstance(lam, (int, float)) else lam))
     if not lams:
         raise ValueError(f"evaluate_linear_probe: lam={lam!r}")
     pooled = {} if int(n_last) == 1 and not avgpool else dict(n_last=n_last, avgpool=avgpool)      # (the defaults: the call as it always was)
+    if pooled and wide:
+        pooled["wide"] = True
     rows, labels, s_bank = extract_features(model, bank_loader, device, transform=transform, graph=graph, integers=True, **pooled)
     q, targets, s_query = extract_features(model, query_loader, device, transform=transform, graph=graph, integers=True, **pooled)
     if s_bank is None or s_query is None:
@@ -440,7 +448,7 @@ def evaluate_dense_probe(model, train_loader, val_loader, device, num_classes, *
 
 
 def extract_features_parallel(model, data_loader, device, *, transform=None, graph: bool = False, integers: bool = False,
-                              n_last: int = 1, avgpool: bool = False):
+                              n_last: int = 1, avgpool: bool = False, wide: bool = False):
     """extract_features data-parallel over the ranks of the default process group (world 1 without one) -> the same (features [N, C],
     labels int64 [N], scale) on every rank, rows in loader order.
 
@@ -449,10 +457,10 @@ def extract_features_parallel(model, data_loader, device, *, transform=None, gra
     parallel.gather_feature_rows at the end (one all_gather_into_tensor: uneven shards padded to the largest and trimmed by their
     counts) brings every rank's rows to every rank, where they are put back into loader order.  integers=False: the gathered
     integers are dequantised once, behind the gather (a quarter of the float32 bytes cross the wire).
-    n_last, avgpool: as for extract_features (the pooled rows, checked before the loader is touched)."""
+    n_last, avgpool, wide: as for extract_features (the pooled rows, checked before the loader is touched)."""
     from .parallel import gather_feature_rows
     pooled = int(n_last) != 1 or bool(avgpool)
-    C = pooled_width(model, n_last, avgpool) if pooled else int(model.num_features)
+    C = pooled_width(model, n_last, avgpool, wide) if pooled else int(model.num_features)
     if pooled and graph:
         raise ValueError("extract_features_parallel: features_pooled is not part of the graph replays (graph=False)")
     if dist.is_available() and dist.is_initialized():

@@ -8,7 +8,9 @@
 The bank stays int8 and is never copied; the similarity runs on the int8 MFMA and the selection in the kernel's epilogue, so no
 [Q, N] score matrix exists.  The per-tensor scale of the rows cancels in a cosine: it is kept only so that queries under another
 scale can be told apart by the caller (inference.evaluate_knn refuses them).  There is no fallback: a bank the kernels do not take
-(float rows, C not a multiple of 64, rows not on 16-byte boundaries) raises."""
+(float rows, C not a multiple of 64, rows not on 16-byte boundaries) raises.  Rows of up to 1024 channels take the kernel that
+splits the bank rows over a workgroup's waves, wider ones (to 4096: the pooled features of inference.extract_features(wide=True))
+the one that splits the channels (ivit_knn_topk_i8_wide)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -19,6 +21,8 @@ from . import _lib
 
 K_MAX = 256          # IVIT_KNN_K_MAX
 SPLITS_MAX = 64      # IVIT_KNN_SPLITS_MAX
+C_NARROW_MAX = 1024  # the widest rows of ivit_knn_topk_i8, ivit_gram_i8_i64 and ivit_group_sums_i8_i64
+C_WIDE_MAX = 4096    # IVIT_KNN_C_WIDE_MAX: the widest rows of their _wide namesakes
 
 
 def _rows_ok(t, what):
@@ -28,8 +32,8 @@ def _rows_ok(t, what):
     if t.dim() != 2 or not t.is_cuda:
         raise ValueError(f"{what}: a [rows, C] tensor on the device wanted, got shape {tuple(t.shape)} on {t.device}")
     c = int(t.shape[1])
-    if c % 64 != 0 or not 64 <= c <= 1024:
-        raise ValueError(f"{what}: C={c} is not a multiple of 64 between 64 and 1024")
+    if c % 64 != 0 or not 64 <= c <= C_WIDE_MAX:
+        raise ValueError(f"{what}: C={c} is not a multiple of 64 between 64 and {C_WIDE_MAX}")
 
 
 def _aligned(t):
@@ -84,7 +88,7 @@ class FeatureBank:
             return idx, score
         need = self._workspace(Q, k, splits)
         st = _lib.stream_ptr()
-        _lib.call("ivit_knn_topk_i8", _lib.ptr(q), q.stride(0), Q, _lib.ptr(self.rows), self.rows.stride(0), self.N, self.C, _lib.ptr(self.rnorm),
+        _lib.call("ivit_knn_topk_i8" if self.C <= C_NARROW_MAX else "ivit_knn_topk_i8_wide", _lib.ptr(q), q.stride(0), Q, _lib.ptr(self.rows), self.rows.stride(0), self.N, self.C, _lib.ptr(self.rnorm),
                   k, splits, _lib.ptr(idx), _lib.ptr(score), _lib.ptr(self.workspace) if need else None, need, st)
         _lib.call("ivit_rows_rnorm_i8_f32", _lib.ptr(q), q.stride(0), Q, self.C, _lib.ptr(qnorm), st)
         return idx, score * qnorm[:, None]          # one more float32 product: the cosine

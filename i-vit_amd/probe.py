@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .knn import FeatureBank, _aligned, _rows_ok
+from .knn import C_NARROW_MAX, C_WIDE_MAX, FeatureBank, _aligned, _rows_ok
 from .prepare import LinearParams, pad_head
 from .topk import TOPK_MAX
 
@@ -36,8 +36,8 @@ class BankStats:
 
     def __init__(self, C, num_classes, device):
         C, K = int(C), int(num_classes)
-        if C % 64 != 0 or not 64 <= C <= 1024:
-            raise ValueError(f"BankStats: C={C} is not a multiple of 64 between 64 and 1024")
+        if C % 64 != 0 or not 64 <= C <= C_WIDE_MAX:
+            raise ValueError(f"BankStats: C={C} is not a multiple of 64 between 64 and {C_WIDE_MAX}")
         if not 1 <= K <= GROUPS_MAX:
             raise ValueError(f"BankStats: num_classes={K} outside [1, {GROUPS_MAX}]")
         self.C, self.K, self.device = C, K, torch.device(device)
@@ -79,14 +79,17 @@ class BankStats:
         counts = torch.bincount(labels, minlength=self.K)
         group_ptr = torch.zeros(self.K + 1, dtype=torch.int64, device=rows_int8.device)
         group_ptr[1:] = torch.cumsum(counts, 0)
+        # rows of up to 1024 channels: the calls as they always were; wider ones: the _wide namesakes (the same kernels)
+        gram, gram_ws, group_sums = (("ivit_gram_i8_i64", "ivit_gram_workspace_bytes", "ivit_group_sums_i8_i64") if self.C <= C_NARROW_MAX else
+                                     ("ivit_gram_i8_i64_wide", "ivit_gram_wide_workspace_bytes", "ivit_group_sums_i8_i64_wide"))
         need = C.c_int64(0)
-        _lib.call("ivit_gram_workspace_bytes", n, self.C, 0, C.byref(need))
+        _lib.call(gram_ws, n, self.C, 0, C.byref(need))
         if self.workspace is None or self.workspace.numel() * 4 < need.value:
             self.workspace = torch.empty((need.value + 3) // 4, dtype=torch.int32, device=rows_int8.device)
         st = _lib.stream_ptr()
-        _lib.call("ivit_gram_i8_i64", _lib.ptr(rows_int8), rows_int8.stride(0), n, self.C, 0, 1, _lib.ptr(self.gram), _lib.ptr(self.workspace),
+        _lib.call(gram, _lib.ptr(rows_int8), rows_int8.stride(0), n, self.C, 0, 1, _lib.ptr(self.gram), _lib.ptr(self.workspace),
                   need.value, st)
-        _lib.call("ivit_group_sums_i8_i64", _lib.ptr(rows_int8), rows_int8.stride(0), n, self.C, _lib.ptr(perm), _lib.ptr(group_ptr), self.K, 1,
+        _lib.call(group_sums, _lib.ptr(rows_int8), rows_int8.stride(0), n, self.C, _lib.ptr(perm), _lib.ptr(group_ptr), self.K, 1,
                   _lib.ptr(self.sums), st)
         self.counts += counts
         return self

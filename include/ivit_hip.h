@@ -1110,7 +1110,14 @@ int ivit_dequant_rows_i8_f32(const int8_t* x, int64_t ldx, int64_t rows, int C, 
  * [0, IVIT_KNN_SPLITS_MAX], ldq or ldb below C, a misaligned pointer or leading dimension, a workspace that is NULL, misaligned or
  * too small; IVIT_ERR_UNSUPPORTED ("unsupported geometry") for k > IVIT_KNN_K_MAX and for any other C.
  *
- * ivit_knn_workspace_bytes: a host function; *bytes for that call (the same checks of Q, N, k and splits).
+ * ivit_knn_topk_i8_wide: the same search, argument for argument, for rows of up to IVIT_KNN_C_WIDE_MAX channels: C % 64 == 0,
+ * 64 <= C <= 4096, every other limit and every error as above (IVIT_ERR_UNSUPPORTED for any other C).  |dot| reaches 2^26 and n2
+ * 2^26: above 2^24 (float)dot_ij and (float)n2_j are the round-to-nearest-even conversions of the exact integers (v_cvt_f32_i32;
+ * numpy's astype(float32)), everything else is unchanged, so for C <= 1024 the result equals ivit_knn_topk_i8's bit for bit.  Its
+ * kernel splits the channels, not the bank rows, over the waves of a workgroup.
+ *
+ * ivit_knn_workspace_bytes: a host function; *bytes for that call of either search entry (the same checks of Q, N, k and splits;
+ * the formula has no C in it).
  *
  * ivit_knn_vote_f32: the weighted vote of a query's neighbours.  idx [Q][k] (as above), labels [N] int32, w [Q][k] float32.  The
  * vote of a label is the float32 sum of the w of the neighbours that carry it, added in rank order starting from 0.0f; classes /
@@ -1121,9 +1128,12 @@ int ivit_dequant_rows_i8_f32(const int8_t* x, int64_t ldx, int64_t rows, int C, 
  * outside [1, IVIT_KNN_K_MAX], r outside [1, k]. */
 #define IVIT_KNN_K_MAX 256
 #define IVIT_KNN_SPLITS_MAX 64
+#define IVIT_KNN_C_WIDE_MAX 4096
 int ivit_rows_rnorm_i8_f32(const int8_t* x, int64_t ldx, int64_t rows, int C, float* out, ivit_stream_t stream);
 int ivit_knn_topk_i8(const int8_t* q, int64_t ldq, int Q, const int8_t* bank, int64_t ldb, int N, int C, const float* rnorm, int k,
                      int splits, int32_t* idx, float* score, void* workspace, int64_t workspace_bytes, ivit_stream_t stream);
+int ivit_knn_topk_i8_wide(const int8_t* q, int64_t ldq, int Q, const int8_t* bank, int64_t ldb, int N, int C, const float* rnorm, int k,
+                          int splits, int32_t* idx, float* score, void* workspace, int64_t workspace_bytes, ivit_stream_t stream);
 int ivit_knn_workspace_bytes(int Q, int N, int k, int splits, int64_t* bytes);
 int ivit_knn_vote_f32(const int32_t* idx, const int32_t* labels, const float* w, int Q, int N, int k, int r, int32_t* classes,
                       float* votes, ivit_stream_t stream);
@@ -1156,7 +1166,12 @@ int ivit_knn_vote_f32(const int32_t* idx, const int32_t* labels, const float* w,
  * builds from a stable sort of them.  An empty group gives zeros.  1 <= groups <= IVIT_GROUPS_MAX.  The inverted-index form of a
  * scatter-add: one workgroup per group, every row read once, 16 bytes per lane.  An entry of perm outside [0, rows) is NOT checked
  * on the device.  One launch.  Errors, nothing launched: IVIT_ERR_INVALID for a NULL or misaligned operand, rows outside [0, 2^31),
- * ldx < C, groups outside [1, IVIT_GROUPS_MAX], accumulate other than 0 or 1; IVIT_ERR_UNSUPPORTED for any other C. */
+ * ldx < C, groups outside [1, IVIT_GROUPS_MAX], accumulate other than 0 or 1; IVIT_ERR_UNSUPPORTED for any other C.
+ *
+ * ivit_gram_i8_i64_wide, ivit_gram_wide_workspace_bytes, ivit_group_sums_i8_i64_wide: their namesakes, argument for argument and
+ * error for error, for C % 64 == 0, 64 <= C <= IVIT_KNN_C_WIDE_MAX (the widths of ivit_knn_topk_i8_wide), on the same kernels: the
+ * pair decomposition, the 65536-row int32 slabs (|sum| <= 2^30 whatever C) and the row slots do not depend on C.  A Gram slab is
+ * 4 C^2 bytes: 64 MiB at C = 4096. */
 #define IVIT_GRAM_SPLITS_MAX 64
 #define IVIT_GROUPS_MAX 1048576
 int ivit_gram_i8_i64(const int8_t* x, int64_t ldx, int64_t rows, int C, int splits, int accumulate, int64_t* gram, void* workspace,
@@ -1164,6 +1179,11 @@ int ivit_gram_i8_i64(const int8_t* x, int64_t ldx, int64_t rows, int C, int spli
 int ivit_gram_workspace_bytes(int64_t rows, int C, int splits, int64_t* bytes);
 int ivit_group_sums_i8_i64(const int8_t* x, int64_t ldx, int64_t rows, int C, const int32_t* perm, const int64_t* group_ptr, int groups,
                            int accumulate, int64_t* sums, ivit_stream_t stream);
+int ivit_gram_i8_i64_wide(const int8_t* x, int64_t ldx, int64_t rows, int C, int splits, int accumulate, int64_t* gram, void* workspace,
+                          int64_t workspace_bytes, ivit_stream_t stream);
+int ivit_gram_wide_workspace_bytes(int64_t rows, int C, int splits, int64_t* bytes);
+int ivit_group_sums_i8_i64_wide(const int8_t* x, int64_t ldx, int64_t rows, int C, const int32_t* perm, const int64_t* group_ptr, int groups,
+                                int accumulate, int64_t* sums, ivit_stream_t stream);
 
 /* ---- dense linear probe: bilinear upsample, argmax and confusion matrix of a linear head on the patch tokens -------------------
  * acc: the int32 accumulators of the head GEMM (ivit_gemm_i8_i32, bias included) on the patch tokens of `batch` images, dense

@@ -4,11 +4,13 @@ as float32, torch.matmul over chunks of bank rows, times rnorm, torch.topk per c
 
     python scripts/time_knn.py [--N 1281167 --C 768 --Q 8192 --k 200] [--repeats 5] [--out FILE.json]
     python scripts/time_knn.py --N 100000 --Q 1000 --k 20 --splits-ab        # also: automatic segments against one segment
+    python scripts/time_knn.py --N 100000 --Q 1000 --k 20 --C 1536           # a wide bank (C > 1024: ivit_knn_topk_i8_wide)
+    python scripts/time_knn.py --N 100000 --Q 1000 --k 20 --C 1024 --wide-ab # also: the same search through the wide entry
 
 Same seeded random int8 inputs for both; device events around a synchronised window; the timed shape is warmed up first; the two
 paths alternate inside one process and every repeat is reported.  The indices of the two paths are compared for every query whose
-float32 scores have no tie among its first k + 1 neighbours (there the order is the same by construction: at C <= 1024 the float32
-dot products are exact integers, so both paths form the same score bits).  `share_of_int8_peak`: 2 Q N C operations over the time of
+float32 scores have no tie among its first k + 1 neighbours (there the order is the same by construction: at C <= 1024, and for these
+random rows at any C the script takes, the float32 dot products are exact integers, so both paths form the same score bits).  `share_of_int8_peak`: 2 Q N C operations over the time of
 the search, against 5.0e15 op/s (the dense INT8 MFMA rate: twice the 2.5 PF of BF16) -- the whole search call, query norms and the
 merge of the segments included, so a kernel alone is slightly better than this figure."""
 import argparse
@@ -21,7 +23,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from ivit_amd import _lib, hiptime  # noqa: E402
+from ivit_amd import _lib, hiptime, knn  # noqa: E402
 from ivit_amd.knn import FeatureBank  # noqa: E402
 
 INT8_PEAK = 5.0e15
@@ -55,6 +57,15 @@ def spread(ms):
     return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms), "all_ms": [round(x, 3) for x in ms]}
 
 
+def wide_search(fb, q, k):
+    """FeatureBank.search through ivit_knn_topk_i8_wide whatever C (the class picks the entry by this module constant)"""
+    saved, knn.C_NARROW_MAX = knn.C_NARROW_MAX, 0
+    try:
+        return fb.search(q, k)
+    finally:
+        knn.C_NARROW_MAX = saved
+
+
 def auto_splits(fb, Q, k):
     need = C.c_int64()
     _lib.call("ivit_knn_workspace_bytes", Q, fb.N, k, 0, C.byref(need))
@@ -70,6 +81,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--chunk-bytes", type=float, default=6e9, help="float32 scores of one chunk of the float path")
     ap.add_argument("--splits-ab", action="store_true", help="also time one bank segment against the automatic choice")
+    ap.add_argument("--wide-ab", action="store_true", help="C <= 1024: also time the search through the wide entry (the channel-split kernel)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "a measurement needs the GPU"
@@ -88,14 +100,19 @@ def main():
     same = (fidx[:, :a.k] == idx.long()).all(dim=1)
     assert bool(same[untied].all()), f"{int((~same[untied]).sum())} queries without a tie differ between the two paths"
 
-    fused, base, one = [], [], []
+    if a.wide_ab:
+        widx, wcos = wide_search(fb, q, a.k)
+        assert torch.equal(widx, idx) and torch.equal(wcos.view(torch.int32), cos.view(torch.int32)), "the two entries differ"
+    fused, base, one, wide = [], [], [], []
     for _ in range(a.repeats):
         fused.append(timed(lambda: fb.search(q, a.k))[0])
         base.append(timed(lambda: float_search(bank_f, fb.rnorm, q_f, a.k, chunk))[0])
         if a.splits_ab:
             one.append(timed(lambda: fb.search(q, a.k, splits=1))[0])
+        if a.wide_ab:
+            wide.append(timed(lambda: wide_search(fb, q, a.k))[0])
     ops = 2.0 * a.Q * a.N * a.C
-    res = {"N": a.N, "C": a.C, "Q": a.Q, "k": a.k, "auto_splits": auto_splits(fb, a.Q, a.k), "float_chunk_rows": chunk,
+    res = {"N": a.N, "C": a.C, "Q": a.Q, "k": a.k, "entry": "ivit_knn_topk_i8" if a.C <= knn.C_NARROW_MAX else "ivit_knn_topk_i8_wide", "auto_splits": auto_splits(fb, a.Q, a.k), "float_chunk_rows": chunk,
            "queries_compared": int(untied.sum()), "queries_with_a_float_tie": int((~untied).sum()),
            "fused_search": spread(fused), "float_path": spread(base),
            "speedup_median": statistics.median(base) / statistics.median(fused),
@@ -103,6 +120,8 @@ def main():
            "bank_bytes_int8": a.N * a.C, "bank_bytes_float32": 4 * a.N * a.C}
     if one:
         res["fused_search_one_segment"] = spread(one)
+    if wide:
+        res["fused_search_wide_entry"] = spread(wide)
     line = json.dumps(res)
     print(line)
     if a.out:
