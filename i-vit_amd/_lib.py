@@ -171,6 +171,9 @@ SIGNATURES = {
     "ivit_gram_i8_i64_wide": [vp, i64, i64, ci, ci, ci, vp, vp, i64, vp],
     "ivit_gram_wide_workspace_bytes": [i64, ci, ci, vp],
     "ivit_group_sums_i8_i64_wide": [vp, i64, i64, ci, vp, vp, ci, ci, vp, vp],
+    # logistic linear probe (include/ivit_hip.h, end): x, ldx, C, idx, [y,] B, K, s, ...
+    "ivit_probe_ce_forward_i8": [vp, i64, ci, vp, vp, ci, ci, f32, vp, vp, vp, vp, vp, vp, vp],
+    "ivit_probe_sgd_update_i8": [vp, i64, ci, vp, ci, ci, f32, vp, f32, f32, f32, vp, vp, vp, vp, vp, vp],
     # dense linear probe (include/ivit_hip.h, end): acc, s_acc, batch, gh, gw, np, classes, r, labels, target, ignore_index, conf, stream
     "ivit_dense_argmax_u8": [vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, ci, vp, vp],
     "ivit_patch_mode_u8": [vp, ci, ci, ci, ci, ci, ci, vp, vp],

@@ -12,7 +12,7 @@ change that breaks the budget must fail the build here, on the CPU, not on the G
 wait without spilling.  csrc/check_isa.py checks the emitted instruction stream for exactly that; the bit-exact GEMM tests on the
 GPU remain the proof of the result.
 
-Second use (`check_resources.py <remarks> attention|rowops|swin|calib|features|knn|probe|dense`): the occupancy the launchers of those files assume
+Second use (`check_resources.py <remarks> attention|rowops|swin|calib|features|knn|probe|logistic|dense`): the occupancy the launchers of those files assume
 when they size their grids (occupancy_rules below)."""
 import re
 import sys
@@ -151,6 +151,16 @@ def occupancy_rules(path, what):
             if not re.search(r"gram_(partial|reduce)_kernel|group_sums_kernel", name):
                 continue
             occ, need_no_scratch = (2 if "gram_partial_kernel" in name else 1), True
+        elif what == "logistic":
+            # probe_ce_forward_kernel<NTMAX> / probe_sgd_update_kernel: two workgroups of four waves per CU (their __launch_bounds__:
+            # at most 256 VGPRs) beside at most 18 KiB of LDS each; accumulators and fragments are indexed by constants only
+            # (a tile beyond the class count is skipped by a uniform branch): no scratch, no spills
+            if not re.search(r"probe_ce_forward_kernel|probe_sgd_update_kernel", name):
+                continue
+            occ, need_no_scratch = 2, True
+            if r.get("LDS", 0) > 20480:
+                print("FAIL", name, "LDS", r.get("LDS"), "above 20 KiB")
+                return 1
         elif what == "dense":
             # dense_argmax_kernel: two workgroups of four waves per CU beside its largest LDS (58 KB at 255 classes; the launcher
             # assumes no number of resident workgroups); its per-pixel state is a handful of scalars: no scratch.  patch_mode_kernel:

@@ -29,7 +29,7 @@ from . import swin_quant, topk, vit_quant
 from .knn import FeatureBank, knn_weights
 from .model_utils import freeze_model
 from .parallel import allreduce_hits, shard_bounds
-from .probe import BankStats
+from .probe import CLASSES_MAX, BankStats, fit_logistic
 
 FACTORIES = {name: getattr(mod, name) for mod in (vit_quant, swin_quant) for name in mod.__all__ if name.endswith("_224")}
 _BW_KEYS = ("patch_embed_bw", "pos_encoding_bw", "block_input_bw", "attention_out_bw", "softmax_bw", "mlp_out_bw",
@@ -373,6 +373,45 @@ def evaluate_linear_probe(model, bank_loader, query_loader, device, num_classes,
     out, n = {}, max(int(q.shape[0]), 1)
     for v in lams:
         probe = stats.ncm() if v is None else stats.ridge(v)
+        hits = torch.zeros(k, dtype=torch.int64, device=q.device)
+        probe.topk(q, k, targets, hits)
+        h = hits.cpu()
+        out[v] = (100.0 * int(h[0]) / n, 100.0 * int(h.sum()) / n)
+    return out
+
+
+def evaluate_logistic_probe(model, bank_loader, query_loader, device, num_classes, *, lrs=(1e-3, 1e-2, 1e-1), epochs: int = 10,
+                            batch_size: int = 1024, momentum: float = 0.9, weight_decay: float = 0.0, seed: int = 0, transform=None,
+                            graph: bool = False, n_last: int = 1, avgpool: bool = False, wide: bool = False):
+    """Logistic linear-probe accuracy of a backbone -> {lr: (top-1 %, top-5 %)}: the protocol's softmax classifier trained with
+    minibatch SGD on the frozen features.  Both sets are extracted ONCE (extract_features(..., integers=True)); the bank stays int8
+    and per learning rate there is one probe.fit_logistic on it in place (cosine schedule, `epochs` passes) and one int8 head GEMM
+    with the top-5 selection over the queries (LinearProbe.topk).  The width of the rows (a multiple of 64 up to 4096) and
+    num_classes (up to 1024) are checked before a loader is touched.  n_last, avgpool, wide: as for evaluate_linear_probe."""
+    rates = tuple(float(v) for v in ((lrs,) if isinstance(lrs, (int, float)) else lrs))
+    if not rates:
+        raise ValueError(f"evaluate_logistic_probe: lrs={lrs!r}")
+    pooled = {} if int(n_last) == 1 and not avgpool else dict(n_last=n_last, avgpool=avgpool)
+    if pooled and wide:
+        pooled["wide"] = True
+    C = pooled_width(model, n_last, avgpool, wide) if pooled else int(model.num_features)
+    if C % 64 != 0 or not 64 <= C <= 4096:
+        raise ValueError(f"evaluate_logistic_probe: features of C={C} channels: the logistic probe takes multiples of 64 from 64 to 4096")
+    if not 1 <= int(num_classes) <= CLASSES_MAX:
+        raise ValueError(f"evaluate_logistic_probe: num_classes={num_classes} outside [1, {CLASSES_MAX}]")
+    rows, labels, s_bank = extract_features(model, bank_loader, device, transform=transform, graph=graph, integers=True, **pooled)
+    q, targets, s_query = extract_features(model, query_loader, device, transform=transform, graph=graph, integers=True, **pooled)
+    if s_bank is None or s_query is None:
+        raise ValueError("evaluate_logistic_probe: an empty bank or query set")
+    fb, fq = float(torch.as_tensor(s_bank).reshape(-1)[0]), float(torch.as_tensor(s_query).reshape(-1)[0])
+    if fb != fq:
+        raise ValueError(f"evaluate_logistic_probe: the bank's rows carry scale {fb!r}, the queries' {fq!r}: not the same frozen model")
+    targets = targets.to(torch.int32).contiguous()
+    k = min(5, int(num_classes))
+    out, n = {}, max(int(q.shape[0]), 1)
+    for v in rates:
+        probe = fit_logistic(rows, labels, fb, num_classes, epochs=epochs, batch_size=batch_size, lr=v, momentum=momentum,
+                             weight_decay=weight_decay, seed=seed)
         hits = torch.zeros(k, dtype=torch.int64, device=q.device)
         probe.topk(q, k, targets, hits)
         h = hits.cpu()

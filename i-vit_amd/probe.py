@@ -15,6 +15,7 @@ selection.  There is no fallback: rows the kernels do not take raise, as knn.Fea
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -25,6 +26,8 @@ from .prepare import LinearParams, pad_head
 from .topk import TOPK_MAX
 
 GROUPS_MAX = 1 << 20      # IVIT_GROUPS_MAX
+CLASSES_MAX = 1024        # IVIT_PROBE_CLASSES_MAX: the classes of the logistic probe
+BATCH_MAX = 4096          # IVIT_PROBE_BATCH_MAX: the rows of one of its steps
 
 
 def _scale_of(scale):
@@ -238,3 +241,100 @@ class LinearProbe:
             head.weight.copy_(torch.from_numpy(self.W))
             head.bias.copy_(torch.from_numpy(self.b))
         return model
+
+
+class LogisticTrainer:
+    """A softmax classifier on features f = scale * x trained with minibatch SGD on the int8 bank in place (include/ivit_hip.h,
+    "logistic linear probe"): master W float32 [Kp, C] and b [Kp], their momentum, and the bf16 compute copy Wh, on the device, Kp =
+    num_classes rounded up to 64 (the padded rows are zero and stay zero).  init: a LinearProbe of the same shape and scale to start
+    from (BankStats.ridge's, say); zeros otherwise."""
+
+    def __init__(self, C, num_classes, scale, device, init=None):
+        C, K = int(C), int(num_classes)
+        if C % 64 != 0 or not 64 <= C <= C_WIDE_MAX:
+            raise ValueError(f"LogisticTrainer: C={C} is not a multiple of 64 between 64 and {C_WIDE_MAX}")
+        if not 1 <= K <= CLASSES_MAX:
+            raise ValueError(f"LogisticTrainer: num_classes={K} outside [1, {CLASSES_MAX}]")
+        s = _scale_of(scale)
+        if s is None or not s > 0.0:
+            raise ValueError(f"LogisticTrainer: scale={scale!r} is not a positive number")
+        self.C, self.K, self.Kp, self.scale, self.device = C, K, (K + 63) // 64 * 64, s, torch.device(device)
+        self.W = torch.zeros(self.Kp, C, dtype=torch.float32, device=device)
+        self.b = torch.zeros(self.Kp, dtype=torch.float32, device=device)
+        if init is not None:
+            if (init.K, init.C) != (K, C) or init.scale != s:
+                raise ValueError(f"LogisticTrainer: init of [{init.K}, {init.C}] under scale {init.scale!r} for a probe of [{K}, {C}] under {s!r}")
+            self.W[:K] = torch.from_numpy(init.W).to(device)
+            self.b[:K] = torch.from_numpy(init.b).to(device)
+        self.mW, self.mb = torch.zeros_like(self.W), torch.zeros_like(self.b)
+        self.Wh = self.W.to(torch.bfloat16)      # round to nearest even
+        self.G = None                            # bf16 [Kp, Bp] of the last step, class-major
+
+    def step(self, rows_int8, idx, y, lr, momentum=0.9, weight_decay=0.0):
+        """one SGD step on the bank rows idx (int32 [B], any order, repeats allowed, not checked on the device) with labels y
+        (int32 [B]) -> (loss float32 [B], top1 int32 [B]) of the batch BEFORE the step, on the device, without a synchronisation"""
+        who = "LogisticTrainer.step"
+        _rows_ok(rows_int8, who)
+        if int(rows_int8.shape[1]) != self.C:
+            raise ValueError(f"{who}: rows of {int(rows_int8.shape[1])} channels into a probe of {self.C}")
+        if not _aligned(rows_int8):
+            raise ValueError(f"{who}: rows must be contiguous in C and start on 16-byte boundaries (the rows are used in place)")
+        B = int(idx.shape[0]) if idx.dim() == 1 else -1
+        for t, name in ((idx, "idx"), (y, "y")):
+            if t.dtype != torch.int32 or t.shape != (B,) or not t.is_contiguous() or t.device != rows_int8.device:
+                raise TypeError(f"{who}: {name} must be a contiguous int32 tensor [B] on the rows' device")
+        if not 1 <= B <= BATCH_MAX:
+            raise ValueError(f"{who}: a batch of {B} rows outside [1, {BATCH_MAX}]")
+        Bp = (B + 63) // 64 * 64
+        if self.G is None or self.G.numel() < self.Kp * Bp:
+            self.G = torch.empty(self.Kp * Bp, dtype=torch.bfloat16, device=rows_int8.device)
+        loss = torch.empty(B, dtype=torch.float32, device=rows_int8.device)
+        top1 = torch.empty(B, dtype=torch.int32, device=rows_int8.device)
+        st = _lib.stream_ptr()
+        x, ldx = _lib.ptr(rows_int8), rows_int8.stride(0)
+        _lib.call("ivit_probe_ce_forward_i8", x, ldx, self.C, _lib.ptr(idx), _lib.ptr(y), B, self.K, self.scale, _lib.ptr(self.Wh),
+                  _lib.ptr(self.b), _lib.ptr(self.G), _lib.ptr(loss), _lib.ptr(top1), None, st)
+        _lib.call("ivit_probe_sgd_update_i8", x, ldx, self.C, _lib.ptr(idx), B, self.K, self.scale, _lib.ptr(self.G), float(lr),
+                  float(momentum), float(weight_decay), _lib.ptr(self.W), _lib.ptr(self.b), _lib.ptr(self.mW), _lib.ptr(self.mb),
+                  _lib.ptr(self.Wh), st)
+        return loss, top1
+
+    def probe(self):
+        """-> LinearProbe of the master weights as they are now"""
+        return LinearProbe(self.W[:self.K].cpu().numpy(), self.b[:self.K].cpu().numpy(), self.scale, self.device)
+
+
+def cosine_lr(lr, t, total):
+    """the learning rate of step t of `total`: a half cosine from lr (t = 0) towards 0 (t = total), in float64 on the host"""
+    return 0.5 * float(lr) * (1.0 + math.cos(math.pi * t / total))
+
+
+def fit_logistic(rows_int8, labels, scale, num_classes, *, epochs, batch_size=1024, lr, momentum=0.9, weight_decay=0.0, seed=0, init=None):
+    """-> LinearProbe: softmax regression on the int8 bank [n, C] in place, `epochs` passes of minibatch SGD with momentum and the
+    cosine schedule over all steps.  Every epoch draws one torch.randperm from a CPU generator seeded with seed + epoch; the last,
+    short batch of an epoch is kept."""
+    who = "fit_logistic"
+    _rows_ok(rows_int8, who)
+    n, epochs, bs = int(rows_int8.shape[0]), int(epochs), int(batch_size)
+    if not _aligned(rows_int8):
+        raise ValueError(f"{who}: rows must be contiguous in C and start on 16-byte boundaries (the rows are used in place)")
+    if labels.shape != (n,):
+        raise ValueError(f"{who}: {tuple(labels.shape)} labels for {n} rows")
+    if not 1 <= n < 2 ** 31:
+        raise ValueError(f"{who}: {n} rows outside [1, 2^31)")
+    if epochs < 1 or not 1 <= bs <= BATCH_MAX:
+        raise ValueError(f"{who}: epochs={epochs} below 1 or batch_size={bs} outside [1, {BATCH_MAX}]")
+    trainer = LogisticTrainer(int(rows_int8.shape[1]), num_classes, scale, rows_int8.device, init)
+    labels = labels.to(device=rows_int8.device, dtype=torch.int64)
+    lo, hi = int(labels.min()), int(labels.max())
+    if lo < 0 or hi >= trainer.K:
+        raise ValueError(f"{who}: label {lo if lo < 0 else hi} outside [0, {trainer.K})")
+    total, t = epochs * ((n + bs - 1) // bs), 0
+    for epoch in range(epochs):
+        perm = torch.randperm(n, generator=torch.Generator().manual_seed(int(seed) + epoch)).to(rows_int8.device)
+        y = labels[perm].to(torch.int32)
+        perm = perm.to(torch.int32)
+        for i in range(0, n, bs):
+            trainer.step(rows_int8, perm[i:i + bs], y[i:i + bs], cosine_lr(lr, t, total), momentum, weight_decay)
+            t += 1
+    return trainer.probe()

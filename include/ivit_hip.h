@@ -1185,6 +1185,54 @@ int ivit_gram_wide_workspace_bytes(int64_t rows, int C, int splits, int64_t* byt
 int ivit_group_sums_i8_i64_wide(const int8_t* x, int64_t ldx, int64_t rows, int C, const int32_t* perm, const int64_t* group_ptr, int groups,
                                 int accumulate, int64_t* sums, ivit_stream_t stream);
 
+/* ---- logistic linear probe: one minibatch step of softmax regression with momentum SGD on the int8 feature bank ----------------
+ * The bank x holds int8 rows of C channels (row stride ldx >= C in elements) under the per-tensor scale s: the features are
+ * f = s * x.  Geometry of the bank as for the wide probe entries: C % 64 == 0, 64 <= C <= IVIT_KNN_C_WIDE_MAX, x and ldx multiples
+ * of 16 bytes, row offsets are 64-bit products (a row may start beyond 2^32 bytes), elements C .. ldx - 1 of a row are not read.
+ * Classes 1 <= K <= IVIT_PROBE_CLASSES_MAX, Kp = K rounded up to 64.  A step takes idx int32 [B], the bank rows of the batch in any
+ * order, repeats allowed, NOT checked on the device (as perm of ivit_group_sums_i8_i64), and y int32 [B], their labels in [0, K)
+ * (not checked either: a label outside gives that row an undefined loss and a gradient without its one-hot term);
+ * 1 <= B <= IVIT_PROBE_BATCH_MAX, Bp = B rounded up to 64.
+ * State, all dense and 16-byte aligned: master W float32 [Kp][C] and b float32 [Kp], momentum mW and mb of the same shapes, and the
+ * compute copy Wh bf16 [Kp][C] (uint16_t bit patterns).  Rows K .. Kp - 1 of all five are zero and stay zero (never written).
+ * Mixed precision with stated rounding points: int8 -> bf16 is exact, Wh = bf16_rne(W), G = bf16_rne(p - onehot) (round to
+ * nearest even); everything else is float32, one IEEE operation per step as written (no contraction); the two matrix products
+ * accumulate in float32 inside v_mfma_f32_16x16x32_bf16, 64 reduction indices per step in ascending steps.
+ *
+ * ivit_probe_ce_forward_i8, for 0 <= r < B and 0 <= k < K:
+ *   acc[r][k] = sum_c bf16(x[idx[r]][c]) * Wh[k][c]                      (MFMA, channels in ascending steps of 64)
+ *   z         = fl(fl(acc * s) + b[k]);  m = max_k z;  e_k = expf(z_k - m)
+ *   S         = sum_k e_k: with Kq = Kp / 4, the four quarters q of the classes are summed apart and S = ((S_0 + S_1) + S_2) + S_3;
+ *               inside a quarter S_q = (P_0 + P_1) + (P_2 + P_3), P_g the sum, k ascending from 0.0f, over the classes k with
+ *               (k / 4) % 4 == g;  p_k = e_k / S
+ *   G[k * Bp + r] = bf16_rne(fl(p_k - [k == y[r]]));  every G[k][r] with K <= k < Kp or B <= r < Bp is written as 0
+ *   loss[r]   = fl(logf(S) - fl(z_y - m));  top1[r] = the smallest k of maximal z (float comparison, -0 == +0)
+ *   z_out (or NULL) float32 [B][Kp]: z_out[r * Kp + k] = z, columns K .. Kp - 1 written as 0
+ * expf and logf are the device library's (about 1 ulp).  One launch; a workgroup owns 16 batch rows and all Kp classes, the logits
+ * never reach memory unless z_out is given.
+ *
+ * ivit_probe_sgd_update_i8, for 0 <= k < K and 0 <= c < C, with G as the forward entry left it for the same x, idx, B, K:
+ *   D   = sum_r G[k][r] * bf16(x[idx[r]][c])                             (MFMA, batch rows in ascending steps of 64)
+ *   g   = fl(fl(D * sB) + fl(wd * W)),  sB = fl(s / (float)B) computed once on the host
+ *   mW  = fl(fl(mu * mW) + g);  W = fl(W - fl(lr * mW));  Wh = bf16_rne(W)
+ *   bias: T = sum_r G[k][r] in float32 -- the 16-byte chunks (eight columns) j of the class's row with j % 4 == q are added value
+ *         by value, ascending, from 0.0f into T_q, T = (T_0 + T_1) + (T_2 + T_3) -- gb = fl(T / (float)B);
+ *         mb = fl(fl(mu * mb) + gb);  b = fl(b - fl(lr * mb)): no weight decay
+ * No split over the batch and no float atomics: one workgroup tile (64 classes x 64 channels) owns an element of W, so two runs
+ * give the same bits.  Unlike the integer bank entries the results are NOT independent of the tiling: they are a function of the
+ * inputs and of the step orders stated here.  One launch.
+ *
+ * Errors of both, nothing launched and nothing written: IVIT_ERR_INVALID for a NULL operand (z_out excepted), K < 1, B outside
+ * [1, IVIT_PROBE_BATCH_MAX], ldx < C, a misaligned x, ldx or other operand; IVIT_ERR_UNSUPPORTED ("unsupported geometry") for any
+ * other C and for K > IVIT_PROBE_CLASSES_MAX. */
+#define IVIT_PROBE_CLASSES_MAX 1024
+#define IVIT_PROBE_BATCH_MAX 4096
+int ivit_probe_ce_forward_i8(const int8_t* x, int64_t ldx, int C, const int32_t* idx, const int32_t* y, int B, int K, float s,
+                             const uint16_t* Wh, const float* b, uint16_t* G, float* loss, int32_t* top1, float* z_out,
+                             ivit_stream_t stream);
+int ivit_probe_sgd_update_i8(const int8_t* x, int64_t ldx, int C, const int32_t* idx, int B, int K, float s, const uint16_t* G, float lr,
+                             float mu, float wd, float* W, float* b, float* mW, float* mb, uint16_t* Wh, ivit_stream_t stream);
+
 /* ---- dense linear probe: bilinear upsample, argmax and confusion matrix of a linear head on the patch tokens -------------------
  * acc: the int32 accumulators of the head GEMM (ivit_gemm_i8_i32, bias included) on the patch tokens of `batch` images, dense
  * [batch * gh * gw][np], np >= classes the padded class count; s_acc float32 [np], the head's per-class scale.  The label map
