@@ -8,6 +8,6 @@ from .quantization_utils import *  # noqa: F401,F403
 from .vit_quant import *  # noqa: F401,F403
 from .swin_quant import *  # noqa: F401,F403
 from .model_utils import freeze_model, unfreeze_model  # noqa: F401
-from .knn import FeatureBank, knn_classify  # noqa: F401
+from .knn import FeatureBank, knn_classify, retrieval_ap  # noqa: F401
 from .probe import BankStats, LinearProbe, LogisticTrainer, fit_logistic  # noqa: F401
 from .dense import DenseProbe, miou, patch_labels  # noqa: F401

@@ -164,6 +164,10 @@ SIGNATURES = {
     "ivit_knn_topk_i8_wide": [vp, i64, ci, vp, i64, ci, ci, vp, ci, ci, vp, vp, vp, i64, vp],
     "ivit_knn_workspace_bytes": [ci, ci, ci, ci, vp],
     "ivit_knn_vote_f32": [vp, vp, vp, ci, ci, ci, ci, vp, vp, vp],
+    # retrieval ranks: q, ldq, Q, bank, ldb, N, C, rnorm, tptr, tidx, nnz, splits, rank, score, workspace, workspace_bytes, stream;
+    # ivit_knn_ranks_workspace_bytes is a host function
+    "ivit_knn_ranks_workspace_bytes": [ci, ci, ci, ci, vp],
+    "ivit_knn_ranks_i8": [vp, i64, ci, vp, i64, ci, ci, vp, vp, vp, ci, ci, vp, vp, vp, i64, vp],
     # linear probe on the int8 feature bank (include/ivit_hip.h, end): ivit_gram_workspace_bytes is a host function
     "ivit_gram_i8_i64": [vp, i64, i64, ci, ci, ci, vp, vp, i64, vp],
     "ivit_gram_workspace_bytes": [i64, ci, ci, vp],

@@ -134,6 +134,15 @@ def occupancy_rules(path, what):
             if r.get("LDS", 0) > 163840:
                 print("FAIL", name, "LDS", r.get("LDS"), "above 160 KiB: the workgroup does not fit a CU")
                 return 1
+        elif what == "knn" and "knn_rank_" in name:
+            # knn_rank_count_kernel<KSMAX> (knn_ranks.hip): the search's fragments (indexed by constants only: no scratch) beside
+            # 108.5 KiB of LDS -- 64 KiB sorted keys, 32.1 KiB histogram, 12 KiB candidates, nothing packed -- which is ONE workgroup
+            # of four waves per CU (its __launch_bounds__): one wave per SIMD.  knn_rank_keys_kernel assumes no number of resident
+            # workgroups: no scratch
+            occ, need_no_scratch = 1, True
+            if r.get("LDS", 0) > 163840:
+                print("FAIL", name, "LDS", r.get("LDS"), "above 160 KiB: the workgroup does not fit a CU")
+                return 1
         elif what == "knn":
             # knn_topk_kernel<KSMAX>: two workgroups of four waves per CU (its __launch_bounds__, beside 2 x 76.5 KiB of LDS); the query
             # and bank fragments (up to 192 VGPRs) are indexed by constants only: no scratch.  The merge, rnorm and vote kernels

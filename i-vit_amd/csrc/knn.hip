@@ -20,17 +20,12 @@
 // lanes rescan the list for the new minimum.  After warm-up almost no key passes and the tile costs its two barriers.
 // At the end every list is ranked (rank = number of larger keys) and written in order: to idx / score with one segment, else to the
 // workspace [Q][splits][k] as keys (0 = no entry), which knn_merge_kernel ranks across segments by binary searches.
-#include "common.h"
+// The geometry, the key and the epilogue's threshold test are shared with the rank kernels (knn_ranks.hip): knn_parts.h.
+#include "knn_parts.h"
 
 namespace {
 
-typedef unsigned long long u64;
-
-constexpr int KN_NT = 256;                   // threads per workgroup (four waves)
-constexpr int KN_QT = 32;                    // queries per workgroup
-constexpr int KN_BT = 64;                    // bank rows per tile (16 per wave)
 constexpr int KN_KCAP = IVIT_KNN_K_MAX;      // list capacity
-constexpr int KN_CAND = KN_QT * KN_BT;       // candidates a tile can produce
 
 struct KnnArgs {
     const int8_t* q;
@@ -46,14 +41,6 @@ struct KnnArgs {
     u64* ws;
     int qtiles;
 };
-
-IVIT_DEV unsigned knn_skey(float s)
-{
-    unsigned b = (unsigned)__float_as_int(s);
-    if (b == 0x80000000u) b = 0;                                   // -0 == +0
-    return b ^ ((unsigned)((int)b >> 31) | 0x80000000u);           // monotone: larger float, larger unsigned
-}
-IVIT_DEV float knn_score_of(unsigned k) { return __int_as_float((int)((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k)); }
 
 IVIT_DEV u64 wave_allmin_u64(u64 v) { return ~wave_allmax_u64(~v); }
 
@@ -118,29 +105,6 @@ IVIT_DEV void knn_sel_init(KnnSel& S, int tid)
     if (tid < 2) S.cnt[tid] = 0;
 }
 
-// the epilogue of 16 bank rows x 32 queries: acc[qt][r] of lane (g, l15) = dot(row rbase + r, query 16 qt + l15), rt0 = the tile row of
-// rbase.  A key above its query's threshold goes into the tile's candidate buffer (counter cs)
-IVIT_DEV void knn_epilogue(KnnSel& S, const v4i (&acc)[2], const float (&rn)[4], unsigned rbase, int rt0, int q0, int Q, int r_end, int cs, int l15)
-{
-#pragma unroll
-    for (int qt = 0; qt < 2; ++qt) {
-        const int ql = 16 * qt + l15;
-        const u64 th = S.thr[ql];
-        const bool qok = q0 + ql < Q;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const unsigned row = rbase + r;
-            const unsigned sk = knn_skey((float)acc[qt][r] * rn[r]);      // ONE float32 multiplication (-ffp-contract=off)
-            const u64 key = ((u64)sk << 32) | (u64)(0xffffffffu - row);
-            if (qok && row < (unsigned)r_end && key > th) {
-                const int slot = atomicAdd(&S.cnt[cs], 1);                // < KN_CAND: one per (row, query) of the tile
-                S.cskey[slot] = sk;
-                S.cmeta[slot] = (unsigned short)(((rt0 + r) << 5) | ql);
-            }
-        }
-    }
-}
-
 // behind the barrier that ends the epilogues: wave w inserts the candidates of the queries q % 4 == w
 IVIT_DEV void knn_drain(KnnSel& S, unsigned tile_base, int cs, int k, int tid, int lane, int wave)
 {
@@ -160,7 +124,7 @@ IVIT_DEV void knn_drain(KnnSel& S, unsigned tile_base, int cs, int k, int tid, i
             const int src = __builtin_ctzll(mask);
             mask &= mask - 1;
             const unsigned sk1 = (unsigned)__builtin_amdgcn_readlane((int)sk, src), me1 = (unsigned)__builtin_amdgcn_readlane((int)me, src);
-            const u64 key = ((u64)sk1 << 32) | (u64)(0xffffffffu - (tile_base + (me1 >> 5)));
+            const u64 key = knn_key(sk1, tile_base + (me1 >> 5));
             knn_insert(S.lists, S.thr, S.cntl, S.minpos, (int)(me1 & 31u), key, k, lane);
         }
     }
@@ -449,17 +413,6 @@ __global__ __launch_bounds__(64) void knn_vote_kernel(const int32_t* __restrict_
     }
 }
 
-// bank segments: the caller's count, or (0) enough workgroups for two rounds of the 256 CUs without segments below 2048 rows
-int knn_splits(int Q, int N, int splits)
-{
-    if (splits > 0) return splits;
-    const int64_t qtiles = ((int64_t)Q + KN_QT - 1) / KN_QT;
-    if (qtiles <= 0) return 1;
-    const int64_t want = (512 + qtiles - 1) / qtiles, cap = N / 2048;
-    const int64_t sp = want < cap ? want : cap;
-    return (int)(sp < 1 ? 1 : sp > IVIT_KNN_SPLITS_MAX ? IVIT_KNN_SPLITS_MAX : sp);
-}
-
 int knn_check_shape(const char* who, int Q, int N, int k, int splits)
 {
     IVIT_REQUIRE(Q >= 0 && N >= 1, "%s: Q=%d must be at least 0, N=%d at least 1", who, Q, N);
@@ -522,7 +475,7 @@ int knn_search(const char* who, int cmax, const int8_t* q, int64_t ldq, int Q, c
     if (Q == 0) return IVIT_OK;
     KnnArgs a;
     a.q = q, a.ldq = ldq, a.Q = Q, a.bank = bank, a.ldb = ldb, a.N = N, a.KS = C / 64, a.rnorm = rnorm, a.k = k, a.splits = sp;
-    a.seg = (int)((((int64_t)N + sp - 1) / sp + KN_BT - 1) / KN_BT * KN_BT);
+    a.seg = knn_segment_rows(N, sp);
     a.idx = idx, a.score = score, a.ws = static_cast<u64*>(workspace);
     a.qtiles = (Q + KN_QT - 1) / KN_QT;
     const int64_t grid = (int64_t)a.qtiles * sp;

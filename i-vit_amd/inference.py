@@ -22,11 +22,12 @@ from __future__ import annotations
 import time
 from typing import Iterable, Optional
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
 from . import swin_quant, topk, vit_quant
-from .knn import FeatureBank, knn_weights
+from .knn import C_NARROW_MAX, FeatureBank, knn_weights, retrieval_ap
 from .model_utils import freeze_model
 from .parallel import allreduce_hits, shard_bounds
 from .probe import CLASSES_MAX, BankStats, fit_logistic
@@ -341,6 +342,44 @@ def evaluate_knn(model, bank_loader, query_loader, device, *, k=(10, 20, 100, 20
         classes, _ = bank.vote(idx[:, :kk], w[:, :kk], min(5, kk))
         hit = classes == targets[:, None]
         out[kk] = (100.0 * int(hit[:, 0].sum()) / n, 100.0 * int(hit.any(dim=1).sum()) / n)
+    return out
+
+
+def evaluate_retrieval(model, db_loader, query_loader, device, positives, junk=None, **feature_kw):
+    """Image retrieval scored the revisited-Oxford way -> {"mAP": %, "mP@1": %, "mP@5": %, "mP@10": %}.  positives / junk: per query
+    (in loader order) the database rows (in loader order) that are its positives and the ones to take out of its ranking.  Both
+    sets go through extract_features(..., integers=True, **feature_kw) -- transform, graph, n_last, avgpool -- the database stays
+    int8 (knn.FeatureBank) and ONE counting pass over it (FeatureBank.ranks) gives the exact rank of every listed row in the
+    search's order; knn.retrieval_ap turns the ranks into average precision on the host.  Queries without a positive are left out of
+    the means.  The rank kernel takes rows of at most 1024 channels: a wider feature is refused before a loader is touched, and so
+    is a query scale that is not the database's."""
+    if feature_kw.get("wide"):
+        raise ValueError(f"evaluate_retrieval: wide=True: the rank kernel takes rows of at most {C_NARROW_MAX} channels")
+    pooled = int(feature_kw.get("n_last", 1)) != 1 or bool(feature_kw.get("avgpool", False))
+    W = pooled_width(model, feature_kw.get("n_last", 1), feature_kw.get("avgpool", False)) if pooled else int(model.num_features)
+    if W > C_NARROW_MAX:
+        raise ValueError(f"evaluate_retrieval: features of {W} channels: the rank kernel takes rows of at most {C_NARROW_MAX}")
+    rows, labels, s_db = extract_features(model, db_loader, device, integers=True, **feature_kw)
+    q, _, s_query = extract_features(model, query_loader, device, integers=True, **feature_kw)
+    if s_db is None or s_query is None:
+        raise ValueError("evaluate_retrieval: an empty database or query set")
+    fb, fq = float(torch.as_tensor(s_db).reshape(-1)[0]), float(torch.as_tensor(s_query).reshape(-1)[0])
+    if fb != fq:
+        raise ValueError(f"evaluate_retrieval: the database's rows carry scale {fb!r}, the queries' {fq!r}: not the same frozen model")
+    Q = int(q.shape[0])
+    junk = [()] * Q if junk is None else junk
+    if len(positives) != Q or len(junk) != Q:
+        raise ValueError(f"evaluate_retrieval: {len(positives)} positive and {len(junk)} junk lists for {Q} queries")
+    flat = [[int(v) for v in torch.as_tensor(t).reshape(-1)] for pair in zip(positives, junk) for t in pair]
+    targets = [flat[2 * i] + flat[2 * i + 1] for i in range(Q)]
+    is_pos = [flag for i in range(Q) for flag in [True] * len(flat[2 * i]) + [False] * len(flat[2 * i + 1])]
+    ranks, _, tptr = FeatureBank(rows, labels, s_db).ranks(q, targets)
+    ap, prec = retrieval_ap(ranks, tptr, is_pos)
+    ok = ~np.isnan(ap)
+    if not ok.any():
+        raise ValueError("evaluate_retrieval: no query has a positive")
+    out = {"mAP": 100.0 * float(ap[ok].mean())}
+    out.update({f"mP@{k}": 100.0 * float(prec[ok, c].mean()) for c, k in enumerate((1, 5, 10))})
     return out
 
 

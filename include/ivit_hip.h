@@ -1125,8 +1125,26 @@ int ivit_dequant_rows_i8_f32(const int8_t* x, int64_t ldx, int64_t rows, int C, 
  * label; with fewer than r distinct labels the rest is (-1, 0.0f).  Computed among the query's own k neighbours: no per-class
  * table (any number of classes), no atomics (deterministic).  An index outside [0, N) is NOT checked on the device: idx must be
  * what ivit_knn_topk_i8 wrote for a bank of N rows.  Errors: IVIT_ERR_INVALID for a NULL or misaligned pointer, Q < 0, N < 1, k
- * outside [1, IVIT_KNN_K_MAX], r outside [1, k]. */
+ * outside [1, IVIT_KNN_K_MAX], r outside [1, k].
+ *
+ * ivit_knn_ranks_i8: retrieval ranks -- where listed bank rows ("targets") stand in the FULL ranking of the bank against a query, in
+ * the order above, without a sort and without the [Q][N] scores (mean average precision needs the position of every positive, which
+ * may be anywhere in N).  The lists are CSR: tptr [Q + 1] int32, ascending, tptr[0] = 0, tptr[Q] = nnz; the targets of query i are the
+ * bank rows tidx[tptr[i]] .. tidx[tptr[i + 1] - 1], at most IVIT_KNN_RANK_TARGETS_MAX of them (an empty list is allowed; a row may be
+ * listed twice and gets the same rank twice).  For target p of query i, j = tidx[p]: score[p] = score_ij, the bits ivit_knn_topk_i8
+ * returns for that pair, and rank[p] = the number of bank rows j' in [0, N) with score_ij' > score_ij, or score_ij' == score_ij
+ * (-0 == +0) and j' < j: 0 for the nearest row, never counting a row against itself.  Exact integers: the result does not depend on
+ * splits or on any tiling.  Geometry, alignment, leading dimensions and splits as for ivit_knn_topk_i8 (C % 64 == 0, 64 <= C <= 1024,
+ * N < 2^31; 64-bit row offsets on q and bank; tptr, tidx, rank and score aligned to 4 bytes); workspace:
+ * ivit_knn_ranks_workspace_bytes(Q, N, nnz, splits) bytes aligned to 8 (12 bytes per target: each query's keys sorted once, and each
+ * target's place among them).  Two launches (keys, then the counting pass over the bank); nnz == 0 is IVIT_OK without one.  tptr and
+ * tidx are NOT read back to be checked: a list that is not what this paragraph asks for gives wrong ranks (the kernels clamp what
+ * they take from them for an address, so never an access outside the operands); the caller checks them once on the host.
+ * Errors, nothing launched and nothing written: IVIT_ERR_INVALID as for ivit_knn_topk_i8 and for nnz < 0; IVIT_ERR_UNSUPPORTED
+ * ("unsupported geometry") for any other C and for nnz > Q * IVIT_KNN_RANK_TARGETS_MAX (some list is longer than the limit).
+ * ivit_knn_ranks_workspace_bytes: a host function; *bytes for that call (the same checks of Q, N, nnz and splits). */
 #define IVIT_KNN_K_MAX 256
+#define IVIT_KNN_RANK_TARGETS_MAX 256
 #define IVIT_KNN_SPLITS_MAX 64
 #define IVIT_KNN_C_WIDE_MAX 4096
 int ivit_rows_rnorm_i8_f32(const int8_t* x, int64_t ldx, int64_t rows, int C, float* out, ivit_stream_t stream);
@@ -1137,6 +1155,10 @@ int ivit_knn_topk_i8_wide(const int8_t* q, int64_t ldq, int Q, const int8_t* ban
 int ivit_knn_workspace_bytes(int Q, int N, int k, int splits, int64_t* bytes);
 int ivit_knn_vote_f32(const int32_t* idx, const int32_t* labels, const float* w, int Q, int N, int k, int r, int32_t* classes,
                       float* votes, ivit_stream_t stream);
+int ivit_knn_ranks_workspace_bytes(int Q, int N, int nnz, int splits, int64_t* bytes);
+int ivit_knn_ranks_i8(const int8_t* q, int64_t ldq, int Q, const int8_t* bank, int64_t ldb, int N, int C, const float* rnorm,
+                      const int32_t* tptr /* [Q + 1], ascending, tptr[0] = 0 */, const int32_t* tidx /* [nnz] bank rows */, int nnz, int splits,
+                      int32_t* rank /* [nnz] */, float* score /* [nnz] */, void* workspace, int64_t workspace_bytes, ivit_stream_t stream);
 
 /* ---- linear probe on an int8 feature bank: the exact integer statistics of a closed-form classifier ---------------------------
  * Everything least squares onto one-hot targets (or a class-mean classifier) needs from a bank x of `rows` int8 rows of C channels

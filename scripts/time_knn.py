@@ -6,6 +6,7 @@ as float32, torch.matmul over chunks of bank rows, times rnorm, torch.topk per c
     python scripts/time_knn.py --N 100000 --Q 1000 --k 20 --splits-ab        # also: automatic segments against one segment
     python scripts/time_knn.py --N 100000 --Q 1000 --k 20 --C 1536           # a wide bank (C > 1024: ivit_knn_topk_i8_wide)
     python scripts/time_knn.py --N 100000 --Q 1000 --k 20 --C 1024 --wide-ab # also: the same search through the wide entry
+    python scripts/time_knn.py --N 100000 --Q 64 --ranks 64                  # FeatureBank.ranks: 64 targets per query (below)
 
 Same seeded random int8 inputs for both; device events around a synchronised window; the timed shape is warmed up first; the two
 paths alternate inside one process and every repeat is reported.  The indices of the two paths are compared for every query whose
@@ -72,6 +73,49 @@ def auto_splits(fb, Q, k):
     return max(1, need.value // (Q * k * 8))
 
 
+def float_ranks(bank_f, rnorm, q_f, tidx, step=8):
+    """the float path to a rank: the [Q, N] score matrix, then per target the number of larger scores (equal ones by index)"""
+    s = torch.matmul(q_f, bank_f.T) * rnorm[None, :]
+    ts = torch.gather(s, 1, tidx)
+    j = torch.arange(s.shape[1], device=s.device)[None, None, :]
+    out = []
+    for lo in range(0, tidx.shape[1], step):
+        t, ti = ts[:, lo:lo + step, None], tidx[:, lo:lo + step, None]
+        out.append(((s[:, None, :] > t) | ((s[:, None, :] == t) & (j < ti))).sum(dim=2))
+    return torch.cat(out, dim=1)
+
+
+def ranks_case(a, fb, bank, q):
+    """--ranks T: FeatureBank.ranks with T targets per query, (a) taken from the query's own top 256 -- positives near the top, the
+    threshold test rejects almost every score -- and (b) drawn uniformly from the bank -- every threshold is low and most scores go
+    through the candidate buffer -- against FeatureBank.search at k = 256 (the same main loop) and against the float path."""
+    dev, T = bank.device, a.ranks
+    g = torch.Generator(device=dev).manual_seed(99)
+    top, _ = fb.search(q, 256)
+    pick = torch.stack([torch.randperm(256, generator=g, device=dev)[:T] for _ in range(a.Q)])
+    cases = {"near_top": torch.gather(top.long(), 1, pick), "uniform": torch.randint(0, a.N, (a.Q, T), generator=g, device=dev)}
+    tptr = torch.arange(0, a.Q * T + 1, T)
+    bank_f, q_f = bank.float(), q.float()
+    res = {"case": "ranks", "N": a.N, "C": a.C, "Q": a.Q, "targets_per_query": T, "search_k256": None}
+    times = {name: ([], []) for name in cases}
+    search = []
+    for name, tidx in cases.items():                                  # warm-up at the timed shapes, and the two paths agree
+        r, _, _ = fb.ranks(q, (tptr, tidx.reshape(-1)))
+        assert torch.equal(r.long().reshape(a.Q, T), float_ranks(bank_f, fb.rnorm, q_f, tidx)), f"{name}: the two paths differ"
+    for _ in range(a.repeats):
+        search.append(timed(lambda: fb.search(q, 256))[0])
+        for name, tidx in cases.items():
+            flat = tidx.reshape(-1)
+            times[name][0].append(timed(lambda: fb.ranks(q, (tptr, flat)))[0])
+            times[name][1].append(timed(lambda: float_ranks(bank_f, fb.rnorm, q_f, tidx))[0])
+    res["search_k256"] = spread(search)
+    for name, (fused, base) in times.items():
+        res[name] = {"ranks": spread(fused), "float_path": spread(base), "ranks_over_search_k256": statistics.median(fused) / statistics.median(search),
+                     "float_over_ranks": statistics.median(base) / statistics.median(fused)}
+    res["uniform_over_near_top"] = res["uniform"]["ranks"]["median_ms"] / res["near_top"]["ranks"]["median_ms"]
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--N", type=int, default=1281167)
@@ -82,6 +126,7 @@ def main():
     ap.add_argument("--chunk-bytes", type=float, default=6e9, help="float32 scores of one chunk of the float path")
     ap.add_argument("--splits-ab", action="store_true", help="also time one bank segment against the automatic choice")
     ap.add_argument("--wide-ab", action="store_true", help="C <= 1024: also time the search through the wide entry (the channel-split kernel)")
+    ap.add_argument("--ranks", type=int, default=0, help="time FeatureBank.ranks with this many targets per query instead (ranks_case)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "a measurement needs the GPU"
@@ -90,6 +135,8 @@ def main():
     bank = torch.randint(-128, 128, (a.N, a.C), generator=g, dtype=torch.int8, device=dev)
     q = torch.randint(-128, 128, (a.Q, a.C), generator=g, dtype=torch.int8, device=dev)
     fb = FeatureBank(bank, torch.zeros(a.N, dtype=torch.int64, device=dev), 1.0)
+    if a.ranks:
+        return emit(a, ranks_case(a, fb, bank, q))
     bank_f, q_f = bank.float(), q.float()
     chunk = max(a.k + 1, int(a.chunk_bytes // (4 * a.Q)))
 
@@ -122,6 +169,10 @@ def main():
         res["fused_search_one_segment"] = spread(one)
     if wide:
         res["fused_search_wide_entry"] = spread(wide)
+    emit(a, res)
+
+
+def emit(a, res):
     line = json.dumps(res)
     print(line)
     if a.out:
