@@ -168,6 +168,11 @@ SIGNATURES = {
     # ivit_knn_ranks_workspace_bytes is a host function
     "ivit_knn_ranks_workspace_bytes": [ci, ci, ci, ci, vp],
     "ivit_knn_ranks_i8": [vp, i64, ci, vp, i64, ci, ci, vp, vp, vp, ci, ci, vp, vp, vp, i64, vp],
+    # label propagation (include/ivit_hip.h, end): q, ldq, Gh, Gw, bank, ldb, F, C, rnorm, radius, k, splits, idx, score, workspace,
+    # workspace_bytes, stream; idx, w, T, k, seg, N, K, out, stream; ivit_local_topk_workspace_bytes is a host function
+    "ivit_local_topk_workspace_bytes": [ci, ci, ci, ci, ci, vp],
+    "ivit_local_topk_i8": [vp, i64, ci, ci, vp, i64, ci, ci, vp, ci, ci, ci, vp, vp, vp, i64, vp],
+    "ivit_propagate_labels_f32": [vp, vp, ci, ci, vp, ci, ci, vp, vp],
     # linear probe on the int8 feature bank (include/ivit_hip.h, end): ivit_gram_workspace_bytes is a host function
     "ivit_gram_i8_i64": [vp, i64, i64, ci, ci, ci, vp, vp, i64, vp],
     "ivit_gram_workspace_bytes": [i64, ci, ci, vp],

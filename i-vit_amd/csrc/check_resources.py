@@ -12,7 +12,7 @@ change that breaks the budget must fail the build here, on the CPU, not on the G
 wait without spilling.  csrc/check_isa.py checks the emitted instruction stream for exactly that; the bit-exact GEMM tests on the
 GPU remain the proof of the result.
 
-Second use (`check_resources.py <remarks> attention|rowops|swin|calib|features|knn|probe|logistic|dense`): the occupancy the launchers of those files assume
+Second use (`check_resources.py <remarks> attention|rowops|swin|calib|features|knn|propagate|probe|logistic|dense`): the occupancy the launchers of those files assume
 when they size their grids (occupancy_rules below)."""
 import re
 import sys
@@ -151,6 +151,17 @@ def occupancy_rules(path, what):
                 continue
             occ, need_no_scratch = (2 if "knn_topk_kernel" in name else 1), True
             if "knn_topk_kernel" in name and r.get("LDS", 0) > 81920:
+                print("FAIL", name, "LDS", r.get("LDS"), "above 80 KiB: two workgroups no longer fit a CU")
+                return 1
+        elif what == "propagate":
+            # local_topk_kernel<KSMAX> (propagate.hip): two workgroups of four waves per CU (its __launch_bounds__; the launcher's
+            # segment rule then gives two rounds of the 256 CUs) beside 26.7 KiB of LDS each; the target and context fragments
+            # (up to 192 VGPRs) are indexed by constants only: no scratch.  The label mix and the merge assume no number of resident
+            # workgroups: no scratch
+            if not re.search(r"local_topk_kernel|propagate_labels_kernel|knn_merge_kernel", name):
+                continue
+            occ, need_no_scratch = (2 if "local_topk_kernel" in name else 1), True
+            if "local_topk_kernel" in name and r.get("LDS", 0) > 81920:
                 print("FAIL", name, "LDS", r.get("LDS"), "above 80 KiB: two workgroups no longer fit a CU")
                 return 1
         elif what == "probe":

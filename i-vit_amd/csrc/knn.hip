@@ -21,6 +21,7 @@
 // At the end every list is ranked (rank = number of larger keys) and written in order: to idx / score with one segment, else to the
 // workspace [Q][splits][k] as keys (0 = no entry), which knn_merge_kernel ranks across segments by binary searches.
 // The geometry, the key and the epilogue's threshold test are shared with the rank kernels (knn_ranks.hip): knn_parts.h.
+#define KNN_PARTS_MERGE      // knn_merge_kernel
 #include "knn_parts.h"
 
 namespace {
@@ -41,50 +42,6 @@ struct KnnArgs {
     u64* ws;
     int qtiles;
 };
-
-IVIT_DEV u64 wave_allmin_u64(u64 v) { return ~wave_allmax_u64(~v); }
-
-// one candidate into the list of query q, by the whole wave (the only writer of that list)
-IVIT_DEV void knn_insert(u64* lists, u64* thr, int* cntl, int* minpos, int q, u64 key, int k, int lane)
-{
-    u64* L = lists + q * KN_KCAP;
-    const int c = cntl[q];
-    if (c < k) {
-        if (lane == 0) {
-            L[c] = key;
-            cntl[q] = c + 1;
-        }
-        if (c + 1 < k) {                // the next candidate of this query reads the count lane 0 wrote
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            return;
-        }
-    } else {
-        if (key <= thr[q]) return;      // an earlier candidate of this tile raised the threshold
-        if (lane == 0) L[minpos[q]] = key;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    u64 m = ~0ull;
-    int p = 0;
-    for (int j = lane; j < k; j += 64) {
-        const u64 v = L[j];
-        if (v < m) {
-            m = v;
-            p = j;
-        }
-    }
-    const u64 wm = wave_allmin_u64(m);
-    if (m == wm) {                      // keys are unique: one lane
-        thr[q] = wm;
-        minpos[q] = p;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // the selection state of a workgroup in LDS (header comment, "Selection") and its three steps, shared by both search kernels
 struct KnnSel {
@@ -125,7 +82,7 @@ IVIT_DEV void knn_drain(KnnSel& S, unsigned tile_base, int cs, int k, int tid, i
             mask &= mask - 1;
             const unsigned sk1 = (unsigned)__builtin_amdgcn_readlane((int)sk, src), me1 = (unsigned)__builtin_amdgcn_readlane((int)me, src);
             const u64 key = knn_key(sk1, tile_base + (me1 >> 5));
-            knn_insert(S.lists, S.thr, S.cntl, S.minpos, (int)(me1 & 31u), key, k, lane);
+            knn_insert<KN_KCAP>(S.lists, S.thr, S.cntl, S.minpos, (int)(me1 & 31u), key, k, lane);
         }
     }
 }
@@ -310,35 +267,6 @@ __global__ __launch_bounds__(KN_NT, 1) void knn_splitc_kernel(KnnArgs a)
         knn_drain(S, tile_base, cs, k, tid, lane, wave);
     }
     knn_finish(S, a, q0, s, lane, wave);
-}
-
-// the lists of a query's segments (each descending, 0 = no entry, all keys distinct) -> the k largest keys, descending
-__global__ __launch_bounds__(KN_NT) void knn_merge_kernel(const u64* __restrict__ ws, int splits, int k, int bpq, int32_t* __restrict__ idx,
-                                                          float* __restrict__ score)
-{
-    const int64_t q = blockIdx.x / (unsigned)bpq;
-    const int t = (int)(blockIdx.x % (unsigned)bpq) * KN_NT + threadIdx.x;
-    if (t >= splits * k) return;
-    const int s = t / k, p = t - s * k;
-    const u64* base = ws + q * splits * k;
-    const u64 key = base[t];
-    if (key == 0) return;
-    int rank = p;
-    for (int s2 = 0; s2 < splits && rank < k; ++s2) {
-        if (s2 == s) continue;
-        const u64* L = base + s2 * k;
-        int lo = 0, hi = k;             // number of entries of L above key
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (L[mid] > key) lo = mid + 1;
-            else hi = mid;
-        }
-        rank += lo;
-    }
-    if (rank < k) {
-        idx[q * k + rank] = (int32_t)(0xffffffffu - (unsigned)key);
-        score[q * k + rank] = knn_score_of((unsigned)(key >> 32));
-    }
 }
 
 // ---- rnorm: one wave per row; 16-byte loads where the row starts on a 16-byte boundary, bytes otherwise

@@ -1,7 +1,8 @@
-// knn_parts.h -- the device parts shared by the kernels that stream an int8 bank past 32 resident queries: the search (knn.hip) and the
-// retrieval ranks (knn_ranks.hip).  The geometry of a workgroup, the 64-bit (score, index) key, the main loop on
-// v_mfma_i32_16x16x64_i8 and the threshold test of its epilogue live here once; what a kernel does with the scores that pass the
-// test (insert them into a top-k list, count them against a sorted list of targets) is its own.
+// knn_parts.h -- the device parts shared by the kernels that stream an int8 bank past 32 resident queries: the search (knn.hip), the
+// retrieval ranks (knn_ranks.hip) and the windowed search of the label propagation (propagate.hip).  The geometry of a workgroup, the
+// 64-bit (score, index) key, the main loop on v_mfma_i32_16x16x64_i8 and the threshold test of its epilogue live here once; what a
+// kernel does with the scores that pass the test (insert them into a top-k list, count them against a sorted list of targets) is
+// its own.  The insertion into a top-k list (knn_insert) and the merge of the segments' lists (knn_merge_kernel) serve both searches.
 #pragma once
 #include "common.h"
 
@@ -105,6 +106,83 @@ IVIT_DEV void knn_epilogue(Sel& S, const v4i (&acc)[2], const float (&rn)[4], un
         }
     }
 }
+
+IVIT_DEV u64 wave_allmin_u64(u64 v) { return ~wave_allmax_u64(~v); }
+
+// one candidate into the list of query q (lists of KCAP keys each, k <= KCAP of them in use), by the whole wave (the only writer of that list)
+template <int KCAP>
+IVIT_DEV void knn_insert(u64* lists, u64* thr, int* cntl, int* minpos, int q, u64 key, int k, int lane)
+{
+    u64* L = lists + q * KCAP;
+    const int c = cntl[q];
+    if (c < k) {
+        if (lane == 0) {
+            L[c] = key;
+            cntl[q] = c + 1;
+        }
+        if (c + 1 < k) {                // the next candidate of this query reads the count lane 0 wrote
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            return;
+        }
+    } else {
+        if (key <= thr[q]) return;      // an earlier candidate of this tile raised the threshold
+        if (lane == 0) L[minpos[q]] = key;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    u64 m = ~0ull;
+    int p = 0;
+    for (int j = lane; j < k; j += 64) {
+        const u64 v = L[j];
+        if (v < m) {
+            m = v;
+            p = j;
+        }
+    }
+    const u64 wm = wave_allmin_u64(m);
+    if (m == wm) {                      // keys are unique: one lane
+        thr[q] = wm;
+        minpos[q] = p;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// (only where the including file asks for it with KNN_PARTS_MERGE: a kernel in a header is emitted into every object that sees it)
+#ifdef KNN_PARTS_MERGE
+// the lists of a query's segments (each descending, 0 = no entry, all keys distinct) -> the k largest keys, descending
+__global__ __launch_bounds__(KN_NT) void knn_merge_kernel(const u64* __restrict__ ws, int splits, int k, int bpq, int32_t* __restrict__ idx,
+                                                          float* __restrict__ score)
+{
+    const int64_t q = blockIdx.x / (unsigned)bpq;
+    const int t = (int)(blockIdx.x % (unsigned)bpq) * KN_NT + threadIdx.x;
+    if (t >= splits * k) return;
+    const int s = t / k, p = t - s * k;
+    const u64* base = ws + q * splits * k;
+    const u64 key = base[t];
+    if (key == 0) return;
+    int rank = p;
+    for (int s2 = 0; s2 < splits && rank < k; ++s2) {
+        if (s2 == s) continue;
+        const u64* L = base + s2 * k;
+        int lo = 0, hi = k;             // number of entries of L above key
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (L[mid] > key) lo = mid + 1;
+            else hi = mid;
+        }
+        rank += lo;
+    }
+    if (rank < k) {
+        idx[q * k + rank] = (int32_t)(0xffffffffu - (unsigned)key);
+        score[q * k + rank] = knn_score_of((unsigned)(key >> 32));
+    }
+}
+#endif
 
 // bank segments: the caller's count, or (0) enough workgroups for two rounds of the 256 CUs without segments below 2048 rows
 int knn_splits(int Q, int N, int splits)

@@ -525,6 +525,68 @@ def evaluate_dense_probe(model, train_loader, val_loader, device, num_classes, *
     return out
 
 
+def evaluate_video_segmentation(model, sequences, device, *, n_last: int = 7, radius: int = 12, k: int = 5, T: float = 0.1, transform=None,
+                                batch: int = 8):
+    """Semi-supervised video object segmentation by label propagation (the DAVIS protocol of the DINO evaluation) ->
+    {"J_mean": %, "per_sequence": [%, ...]}: the region similarity J, the mean over a sequence's objects and frames (the first
+    frame, whose mask is given, left out) of the intersection over union of the predicted and the true object mask; a pair whose
+    union is empty counts 1.  sequences yields (frames uint8 / float [L, 3, H, W], first_mask uint8 [H, W], masks uint8 [L, H, W],
+    num_objects): label 0 is the background, 1 .. num_objects the objects.
+    Per sequence the frames go through forward_tokens(integers=True) in batches of `batch`, once; the first frame's patch labels
+    (dense.patch_labels of first_mask) go one-hot into slot 0 of a propagate.TokenMemory, slots 1 .. n_last are a ring of the previous
+    frames with their PROPAGATED soft labels, and every further frame is one TokenMemory.propagate call against the filled slots:
+    the tokens stay int8, no affinity matrix exists.  The frame's [K, Gh, Gw] soft labels are upsampled bilinearly by the pixels per
+    token and the argmax is its prediction: K <= 256 planes of one frame in torch, off the hot path.  transform: as for
+    evaluate_dense_probe, on the frames alone.  Works for ViT and Swin backbones (a Swin's last-stage grid).  A model whose tokens
+    the kernels do not take is refused before a sequence is touched."""
+    from .dense import patch_labels
+    from .propagate import C_MAX, CLASSES_MAX, K_MAX, TokenMemory
+    who = "evaluate_video_segmentation"
+    if not hasattr(model, "forward_tokens"):
+        raise ValueError(f"{who}: {type(model).__name__} has no forward_tokens")
+    Cm, n_last, batch = int(model.num_features), int(n_last), int(batch)
+    if Cm % 64 != 0 or not 64 <= Cm <= C_MAX:
+        raise ValueError(f"{who}: tokens of C={Cm} channels: the windowed search takes C % 64 == 0 in 64..{C_MAX} (there is no float path)")
+    if n_last < 0 or batch < 1 or not 1 <= int(k) <= K_MAX or int(radius) < 0:
+        raise ValueError(f"{who}: n_last={n_last} (at least 0), batch={batch} (at least 1), k={k} (1 .. {K_MAX}), radius={radius} (at least 0)")
+    per_seq = []
+    model.eval()
+    with torch.no_grad():
+        for frames, first_mask, masks, num_objects in sequences:
+            L, K = int(frames.shape[0]), int(num_objects) + 1
+            if L < 2 or not 2 <= K <= CLASSES_MAX:
+                raise ValueError(f"{who}: a sequence of {L} frames with {num_objects} objects (at least 2 frames, 1 .. {CLASSES_MAX - 1} objects)")
+            toks, grid, r = [], None, None
+            for lo in range(0, L, batch):
+                hi = min(lo + batch, L)
+                x = frames[lo:hi].to(device) if transform is None else transform.to_float(transform(frames, lo, hi, device=device))
+                tok, _, grid, r = _patch_tokens(model, x)
+                toks.append(tok)
+            Gh, Gw = grid
+            mem = TokenMemory(Gh, Gw, Cm, K, 1 + min(n_last, L - 1), device)
+            lab0 = patch_labels(first_mask.to(device=device, dtype=torch.uint8).reshape(1, Gh * r, Gw * r).contiguous(), r, K, 255)
+            seg0 = torch.nn.functional.one_hot(lab0.reshape(-1).long().clamp(max=K), K + 1)[:, :K].float()      # an ignored patch: no label at all
+            mem.put(0, toks[0][0], seg0)
+            truth = masks.to(device)
+            inter = torch.zeros(K - 1, dtype=torch.float64, device=device)
+            for t in range(1, L):
+                used = 1 + min(t - 1, n_last)
+                q = toks[t // batch][t % batch]
+                seg = mem.propagate(q, radius, k, T, frames=used)
+                if n_last:
+                    mem.put(1 + (t - 1) % n_last, q, seg)
+                up = torch.nn.functional.interpolate(seg.t().reshape(1, K, Gh, Gw), scale_factor=r, mode="bilinear", align_corners=False)
+                pred = up[0].argmax(dim=0)
+                for o in range(1, K):
+                    p, g = pred == o, truth[t] == o
+                    u = int((p | g).sum())
+                    inter[o - 1] += 1.0 if u == 0 else int((p & g).sum()) / u
+            per_seq.append(100.0 * float(inter.sum()) / ((L - 1) * (K - 1)))
+    if not per_seq:
+        raise ValueError(f"{who}: no sequence")
+    return {"J_mean": sum(per_seq) / len(per_seq), "per_sequence": per_seq}
+
+
 def extract_features_parallel(model, data_loader, device, *, transform=None, graph: bool = False, integers: bool = False,
                               n_last: int = 1, avgpool: bool = False, wide: bool = False):
     """extract_features data-parallel over the ranks of the default process group (world 1 without one) -> the same (features [N, C],

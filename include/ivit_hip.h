@@ -1160,6 +1160,52 @@ int ivit_knn_ranks_i8(const int8_t* q, int64_t ldq, int Q, const int8_t* bank, i
                       const int32_t* tptr /* [Q + 1], ascending, tptr[0] = 0 */, const int32_t* tidx /* [nnz] bank rows */, int nnz, int splits,
                       int32_t* rank /* [nnz] */, float* score /* [nnz] */, void* workspace, int64_t workspace_bytes, ivit_stream_t stream);
 
+/* ---- label propagation on int8 patch tokens: windowed cosine neighbours between the frames of a video ---------------------------
+ * The tokens of a target frame and of F context frames lie on one Gh x Gw grid.  The token (y, x) of the target frame is row
+ * y * Gw + x of q (row stride ldq), the token (f, y, x) of the context row f * Gh * Gw + y * Gw + x of bank (row stride ldb): the
+ * frames follow each other.  rnorm [F * Gh * Gw] is what ivit_rows_rnorm_i8_f32 writes for bank.
+ *
+ * ivit_local_topk_i8: the candidates of target (ty, tx) are the context tokens (f, y, x) with |y - ty| <= radius and
+ * |x - tx| <= radius inside the grid, in all F frames; radius >= max(Gh, Gw) - 1 is the whole frame (no neighbourhood mask).  Score
+ * and order are those of ivit_knn_topk_i8: score = fl32((float)dot * rnorm[row]), ONE float32 multiplication; idx[t * k + n] /
+ * score[t * k + n] = context row and score of the n-th neighbour of target t = ty * Gw + tx: score descending, equal scores (float
+ * comparison, -0 == +0) by ascending context row.  Exactly k entries per target: the float protocol keeps every candidate that ties
+ * with the k-th value, this entry keeps the unique order instead, so the result does not depend on the tiling or on splits, and the
+ * neighbours for a smaller k are a prefix.  idx and score are dense [Gh * Gw][k].  Geometry: C % 64 == 0, 64 <= C <= 1024,
+ * 1 <= k <= IVIT_LOCAL_K_MAX, k at most the smallest candidate set, a corner token's:
+ * F * (min(radius, Gh - 1) + 1) * (min(radius, Gw - 1) + 1); F * Gh * Gw < 2^31; q, bank, ldq and ldb are multiples of 16 bytes; row
+ * offsets are 64-bit products on q and bank; elements C .. ld - 1 of a row are not read.  splits: the context FRAMES are cut into
+ * that many segments of ceil(F / splits) frames, searched by separate workgroups and merged by a second launch -- 1 .. min(F,
+ * IVIT_KNN_SPLITS_MAX) as given (a segment may hold fewer than k candidates, or no frame), 0 = chosen from the grid and F for the 256
+ * CUs the other launchers assume.  workspace: ivit_local_topk_workspace_bytes(Gh, Gw, F, k, splits) bytes aligned to 8 (0 bytes with
+ * one segment: workspace may then be NULL).  No [Gh * Gw][F * Gh * Gw] score matrix, no mask and no float copy of a token reach memory.
+ * Nothing is checked on the device.
+ * Errors, nothing launched and nothing written: IVIT_ERR_INVALID for a NULL operand, Gh, Gw or F < 1, radius < 0,
+ * F * Gh * Gw >= 2^31, k < 1, k above the corner token's candidate set, splits outside [0, min(F, IVIT_KNN_SPLITS_MAX)], ldq or ldb
+ * below C, a misaligned pointer or leading dimension, a workspace that is NULL, misaligned or too small; IVIT_ERR_UNSUPPORTED
+ * ("unsupported geometry") for k > IVIT_LOCAL_K_MAX and for any other C.
+ *
+ * ivit_local_topk_workspace_bytes: a host function; *bytes for that call (the same checks of Gh, Gw, F, k and splits, k against the
+ * window excepted: it has no radius).
+ *
+ * ivit_propagate_labels_f32: the label mix.  idx [T][k] int32 and w [T][k] float32 (the caller's weights of the neighbours, as for
+ * ivit_knn_vote_f32), seg [N][K] float32 the soft labels of the context tokens, out [T][K] float32, all dense:
+ *   out[t][c] = fl32(A / S),  A = sum_j fl32(w[t][j] * seg[idx[t][j]][c]),  S = sum_j w[t][j]
+ * both sums in float32 in rank order j = 0 .. k - 1 starting from 0.0f, every product and every addition rounded on its own (no
+ * fused multiply-add), and one correctly rounded division (S == 0 divides by zero as IEEE 754 says).  1 <= k <= IVIT_LOCAL_K_MAX,
+ * 1 <= K <= IVIT_PROPAGATE_CLASSES_MAX, T >= 0 (T == 0: IVIT_OK, nothing launched).  An index outside [0, N) is NOT checked on the
+ * device: idx must be what ivit_local_topk_i8 wrote for a context of N tokens.  One launch, one wave per target.
+ * Errors: IVIT_ERR_INVALID for a NULL or misaligned pointer, T < 0, N < 1, k outside [1, IVIT_LOCAL_K_MAX], K outside
+ * [1, IVIT_PROPAGATE_CLASSES_MAX]. */
+#define IVIT_LOCAL_K_MAX 32
+#define IVIT_PROPAGATE_CLASSES_MAX 256
+int ivit_local_topk_workspace_bytes(int Gh, int Gw, int F, int k, int splits, int64_t* bytes);
+int ivit_local_topk_i8(const int8_t* q, int64_t ldq, int Gh, int Gw, const int8_t* bank, int64_t ldb, int F, int C, const float* rnorm,
+                       int radius, int k, int splits, int32_t* idx, float* score, void* workspace, int64_t workspace_bytes,
+                       ivit_stream_t stream);
+int ivit_propagate_labels_f32(const int32_t* idx, const float* w, int T, int k, const float* seg, int N, int K, float* out,
+                              ivit_stream_t stream);
+
 /* ---- linear probe on an int8 feature bank: the exact integer statistics of a closed-form classifier ---------------------------
  * Everything least squares onto one-hot targets (or a class-mean classifier) needs from a bank x of `rows` int8 rows of C channels
  * (row stride ldx >= C in elements) is a sum of integers: the Gram matrix, the per-class row sums and the class counts.  They are
