@@ -11,3 +11,4 @@ from .model_utils import freeze_model, unfreeze_model  # noqa: F401
 from .knn import FeatureBank, knn_classify, retrieval_ap  # noqa: F401
 from .probe import BankStats, LinearProbe, LogisticTrainer, fit_logistic  # noqa: F401
 from .dense import DenseProbe, miou, patch_labels  # noqa: F401
+from .propagate import davis_measures, mask_scores, upsample_argmax  # noqa: F401

@@ -173,6 +173,10 @@ SIGNATURES = {
     "ivit_local_topk_workspace_bytes": [ci, ci, ci, ci, ci, vp],
     "ivit_local_topk_i8": [vp, i64, ci, ci, vp, i64, ci, ci, vp, ci, ci, ci, vp, vp, vp, i64, vp],
     "ivit_propagate_labels_f32": [vp, vp, ci, ci, vp, ci, ci, vp, vp],
+    # video segmentation scoring (include/ivit_hip.h, end): seg, Gh, Gw, r, K, pred, stream; pred, truth, n, H, W, num_objects, radius,
+    # counts, stream
+    "ivit_upsample_argmax_u8": [vp, ci, ci, ci, ci, vp, vp],
+    "ivit_mask_scores_u8": [vp, vp, ci, ci, ci, ci, ci, vp, vp],
     # linear probe on the int8 feature bank (include/ivit_hip.h, end): ivit_gram_workspace_bytes is a host function
     "ivit_gram_i8_i64": [vp, i64, i64, ci, ci, ci, vp, vp, i64, vp],
     "ivit_gram_workspace_bytes": [i64, ci, ci, vp],

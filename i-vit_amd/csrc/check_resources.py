@@ -12,7 +12,7 @@ change that breaks the budget must fail the build here, on the CPU, not on the G
 wait without spilling.  csrc/check_isa.py checks the emitted instruction stream for exactly that; the bit-exact GEMM tests on the
 GPU remain the proof of the result.
 
-Second use (`check_resources.py <remarks> attention|rowops|swin|calib|features|knn|propagate|probe|logistic|dense`): the occupancy the launchers of those files assume
+Second use (`check_resources.py <remarks> attention|rowops|swin|calib|features|knn|propagate|davis|probe|logistic|dense`): the occupancy the launchers of those files assume
 when they size their grids (occupancy_rules below)."""
 import re
 import sys
@@ -162,6 +162,17 @@ def occupancy_rules(path, what):
                 continue
             occ, need_no_scratch = (2 if "local_topk_kernel" in name else 1), True
             if "local_topk_kernel" in name and r.get("LDS", 0) > 81920:
+                print("FAIL", name, "LDS", r.get("LDS"), "above 80 KiB: two workgroups no longer fit a CU")
+                return 1
+        elif what == "davis":
+            # mask_scores_kernel (davis.hip): two workgroups of four waves per CU (its __launch_bounds__) beside 41.2 KiB of LDS each;
+            # the row words, the disk's groups and the counters are scalars in registers and the radius table is read from LDS: no
+            # scratch.  upsample_argmax_kernel keeps four running maxima and sixteen weights per thread (constant indices only) and
+            # the zeroing kernel nothing: no scratch; their launchers assume no number of resident workgroups
+            if not re.search(r"mask_scores_kernel|upsample_argmax_kernel|zero_u64_kernel", name):
+                continue
+            occ, need_no_scratch = (2 if "mask_scores_kernel" in name else 1), True
+            if "mask_scores_kernel" in name and r.get("LDS", 0) > 81920:
                 print("FAIL", name, "LDS", r.get("LDS"), "above 80 KiB: two workgroups no longer fit a CU")
                 return 1
         elif what == "probe":

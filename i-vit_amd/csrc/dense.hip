@@ -23,7 +23,7 @@
 // image exactly one), and one lane per distinct pair adds the count into the workgroup's LDS table of DN_SLOTS pairs (open
 // addressing, 8 probes); a pair that finds no slot goes straight to memory.  At the end every occupied slot is one 64-bit global
 // atomic: a workgroup touches conf a handful of times, whatever the class statistics.
-#include "common.h"
+#include "bilinear_tap.h"      // dense_tap: the weights of one axis
 
 namespace {
 
@@ -44,14 +44,6 @@ struct DenseArgs {
     u64* conf;
     int packed;                   // labels rows are dword aligned: W % 4 == 0 and labels % 4 == 0
 };
-
-// weights of one axis for the offset j (0 .. r - 1) inside a cell: source slots (s, s + 1) relative to the cell's predecessor, (2r - f, f)
-IVIT_DEV void dense_tap(int j, int r, int& s, int& f)
-{
-    const int n = 2 * j + 1 - r;
-    s = n < 0 ? 0 : 1;
-    f = n < 0 ? n + 2 * r : n;
-}
 
 IVIT_DEV void dense_pair_add(int* keys, unsigned* cnts, u64* conf, int classes, int key, unsigned n)
 {

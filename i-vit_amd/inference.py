@@ -525,6 +525,48 @@ def evaluate_dense_probe(model, train_loader, val_loader, device, num_classes, *
     return out
 
 
+def _propagated_sequences(who, model, sequences, device, n_last, radius, k, T, transform, batch):
+    """The protocol loop evaluate_video_segmentation and evaluate_davis share.  Checks the model and the knobs before a sequence is
+    touched, then yields per sequence (L, K, (Gh, Gw), r, masks, segs): segs yields (t, seg) for t = 1 .. L - 1, the frame's float32
+    [Gh * Gw, K] soft labels from TokenMemory.propagate, already put into the ring of previous frames."""
+    from .dense import patch_labels
+    from .propagate import C_MAX, CLASSES_MAX, K_MAX, TokenMemory
+    if not hasattr(model, "forward_tokens"):
+        raise ValueError(f"{who}: {type(model).__name__} has no forward_tokens")
+    Cm, n_last, batch = int(model.num_features), int(n_last), int(batch)
+    if Cm % 64 != 0 or not 64 <= Cm <= C_MAX:
+        raise ValueError(f"{who}: tokens of C={Cm} channels: the windowed search takes C % 64 == 0 in 64..{C_MAX} (there is no float path)")
+    if n_last < 0 or batch < 1 or not 1 <= int(k) <= K_MAX or int(radius) < 0:
+        raise ValueError(f"{who}: n_last={n_last} (at least 0), batch={batch} (at least 1), k={k} (1 .. {K_MAX}), radius={radius} (at least 0)")
+
+    def frames_of(mem, toks, L):
+        for t in range(1, L):
+            used = 1 + min(t - 1, n_last)
+            q = toks[t // batch][t % batch]
+            seg = mem.propagate(q, radius, k, T, frames=used)
+            if n_last:
+                mem.put(1 + (t - 1) % n_last, q, seg)
+            yield t, seg
+
+    model.eval()
+    for frames, first_mask, masks, num_objects in sequences:
+        L, K = int(frames.shape[0]), int(num_objects) + 1
+        if L < 2 or not 2 <= K <= CLASSES_MAX:
+            raise ValueError(f"{who}: a sequence of {L} frames with {num_objects} objects (at least 2 frames, 1 .. {CLASSES_MAX - 1} objects)")
+        toks, grid, r = [], None, None
+        for lo in range(0, L, batch):
+            hi = min(lo + batch, L)
+            x = frames[lo:hi].to(device) if transform is None else transform.to_float(transform(frames, lo, hi, device=device))
+            tok, _, grid, r = _patch_tokens(model, x)
+            toks.append(tok)
+        Gh, Gw = grid
+        mem = TokenMemory(Gh, Gw, Cm, K, 1 + min(n_last, L - 1), device)
+        lab0 = patch_labels(first_mask.to(device=device, dtype=torch.uint8).reshape(1, Gh * r, Gw * r).contiguous(), r, K, 255)
+        seg0 = torch.nn.functional.one_hot(lab0.reshape(-1).long().clamp(max=K), K + 1)[:, :K].float()      # an ignored patch: no label at all
+        mem.put(0, toks[0][0], seg0)
+        yield L, K, (Gh, Gw), r, masks, frames_of(mem, toks, L)
+
+
 def evaluate_video_segmentation(model, sequences, device, *, n_last: int = 7, radius: int = 12, k: int = 5, T: float = 0.1, transform=None,
                                 batch: int = 8):
     """Semi-supervised video object segmentation by label propagation (the DAVIS protocol of the DINO evaluation) ->
@@ -536,45 +578,16 @@ def evaluate_video_segmentation(model, sequences, device, *, n_last: int = 7, ra
     (dense.patch_labels of first_mask) go one-hot into slot 0 of a propagate.TokenMemory, slots 1 .. n_last are a ring of the previous
     frames with their PROPAGATED soft labels, and every further frame is one TokenMemory.propagate call against the filled slots:
     the tokens stay int8, no affinity matrix exists.  The frame's [K, Gh, Gw] soft labels are upsampled bilinearly by the pixels per
-    token and the argmax is its prediction: K <= 256 planes of one frame in torch, off the hot path.  transform: as for
-    evaluate_dense_probe, on the frames alone.  Works for ViT and Swin backbones (a Swin's last-stage grid).  A model whose tokens
-    the kernels do not take is refused before a sequence is touched."""
-    from .dense import patch_labels
-    from .propagate import C_MAX, CLASSES_MAX, K_MAX, TokenMemory
-    who = "evaluate_video_segmentation"
-    if not hasattr(model, "forward_tokens"):
-        raise ValueError(f"{who}: {type(model).__name__} has no forward_tokens")
-    Cm, n_last, batch = int(model.num_features), int(n_last), int(batch)
-    if Cm % 64 != 0 or not 64 <= Cm <= C_MAX:
-        raise ValueError(f"{who}: tokens of C={Cm} channels: the windowed search takes C % 64 == 0 in 64..{C_MAX} (there is no float path)")
-    if n_last < 0 or batch < 1 or not 1 <= int(k) <= K_MAX or int(radius) < 0:
-        raise ValueError(f"{who}: n_last={n_last} (at least 0), batch={batch} (at least 1), k={k} (1 .. {K_MAX}), radius={radius} (at least 0)")
+    token and the argmax is its prediction: K <= 256 planes of one frame in torch, off the hot path (evaluate_davis keeps that tail
+    on the device and adds the boundary measure F).  transform: as for evaluate_dense_probe, on the frames alone.  Works for ViT and
+    Swin backbones (a Swin's last-stage grid).  A model whose tokens the kernels do not take is refused before a sequence is touched."""
     per_seq = []
-    model.eval()
     with torch.no_grad():
-        for frames, first_mask, masks, num_objects in sequences:
-            L, K = int(frames.shape[0]), int(num_objects) + 1
-            if L < 2 or not 2 <= K <= CLASSES_MAX:
-                raise ValueError(f"{who}: a sequence of {L} frames with {num_objects} objects (at least 2 frames, 1 .. {CLASSES_MAX - 1} objects)")
-            toks, grid, r = [], None, None
-            for lo in range(0, L, batch):
-                hi = min(lo + batch, L)
-                x = frames[lo:hi].to(device) if transform is None else transform.to_float(transform(frames, lo, hi, device=device))
-                tok, _, grid, r = _patch_tokens(model, x)
-                toks.append(tok)
-            Gh, Gw = grid
-            mem = TokenMemory(Gh, Gw, Cm, K, 1 + min(n_last, L - 1), device)
-            lab0 = patch_labels(first_mask.to(device=device, dtype=torch.uint8).reshape(1, Gh * r, Gw * r).contiguous(), r, K, 255)
-            seg0 = torch.nn.functional.one_hot(lab0.reshape(-1).long().clamp(max=K), K + 1)[:, :K].float()      # an ignored patch: no label at all
-            mem.put(0, toks[0][0], seg0)
+        for L, K, (Gh, Gw), r, masks, segs in _propagated_sequences("evaluate_video_segmentation", model, sequences, device, n_last, radius, k, T,
+                                                                    transform, batch):
             truth = masks.to(device)
             inter = torch.zeros(K - 1, dtype=torch.float64, device=device)
-            for t in range(1, L):
-                used = 1 + min(t - 1, n_last)
-                q = toks[t // batch][t % batch]
-                seg = mem.propagate(q, radius, k, T, frames=used)
-                if n_last:
-                    mem.put(1 + (t - 1) % n_last, q, seg)
+            for t, seg in segs:
                 up = torch.nn.functional.interpolate(seg.t().reshape(1, K, Gh, Gw), scale_factor=r, mode="bilinear", align_corners=False)
                 pred = up[0].argmax(dim=0)
                 for o in range(1, K):
@@ -583,8 +596,40 @@ def evaluate_video_segmentation(model, sequences, device, *, n_last: int = 7, ra
                     inter[o - 1] += 1.0 if u == 0 else int((p & g).sum()) / u
             per_seq.append(100.0 * float(inter.sum()) / ((L - 1) * (K - 1)))
     if not per_seq:
-        raise ValueError(f"{who}: no sequence")
+        raise ValueError("evaluate_video_segmentation: no sequence")
     return {"J_mean": sum(per_seq) / len(per_seq), "per_sequence": per_seq}
+
+
+def evaluate_davis(model, sequences, device, *, n_last: int = 7, radius: int = 12, k: int = 5, T: float = 0.1, bound_th: float = 0.008,
+                   transform=None, batch: int = 8, return_masks: bool = False):
+    """evaluate_video_segmentation's protocol with the scoring on the device -> {"J_mean": %, "F_mean": %, "JF_mean": %,
+    "per_sequence": [(J %, F %), ...]} (and "masks": [uint8 [L, H, W], ...] with return_masks; frame 0 is the given mask): the region
+    similarity J and the boundary measure F of davis2017-evaluation (no void pixels; tolerance propagate.bound_radius(bound_th, H, W)
+    pixels, at most 24), each the mean over a sequence's objects and frames 1 .. L - 1, then over the sequences; JF_mean is the mean of
+    the two.  Every frame's label map is written by propagate.upsample_argmax (the exact float64 bilinear upsample + argmax of
+    csrc/davis.hip) into one [L, H, W] buffer, and the sequence is scored by ONE propagate.mask_scores launch and ONE readback.  J may
+    differ from evaluate_video_segmentation's at pixels where torch's float32 interpolation and the exact one break a near-tie between
+    two classes differently."""
+    from .propagate import davis_measures, mask_scores, upsample_argmax
+    per_seq, kept = [], []
+    with torch.no_grad():
+        for L, K, grid, r, masks, segs in _propagated_sequences("evaluate_davis", model, sequences, device, n_last, radius, k, T, transform, batch):
+            truth = masks.to(device=device, dtype=torch.uint8).contiguous()
+            pred = torch.empty_like(truth)
+            pred[0] = truth[0]
+            for t, seg in segs:
+                upsample_argmax(seg, grid, r, out=pred[t])
+            J, F = davis_measures(mask_scores(pred[1:], truth[1:], K - 1, bound_th))
+            per_seq.append(tuple(100.0 * sum(m.reshape(-1).tolist()) / ((L - 1) * (K - 1)) for m in (J, F)))
+            if return_masks:
+                kept.append(pred)
+    if not per_seq:
+        raise ValueError("evaluate_davis: no sequence")
+    Jm, Fm = (sum(p[i] for p in per_seq) / len(per_seq) for i in (0, 1))
+    out = {"J_mean": Jm, "F_mean": Fm, "JF_mean": (Jm + Fm) / 2, "per_sequence": per_seq}
+    if return_masks:
+        out["masks"] = kept
+    return out
 
 
 def extract_features_parallel(model, data_loader, device, *, transform=None, graph: bool = False, integers: bool = False,

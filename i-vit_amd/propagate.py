@@ -11,10 +11,17 @@ Every token of the target frame looks at the context tokens within `radius` grid
 keeps the k of largest cosine and mixes their soft labels with the weights exp(cos / T).  The tokens stay int8; the similarity
 runs on the int8 MFMA and the selection in the kernel's epilogue, so neither the [hw, F * hw] affinity matrix nor its mask exists.
 The neighbours are exactly k in the unique order of knn.FeatureBank.search (the float protocol keeps every tie with the k-th
-value).  There is no fallback: anything the kernels do not take raises."""
+value).  There is no fallback: anything the kernels do not take raises.
+
+Scoring (include/ivit_hip.h, "video segmentation scoring"; csrc/davis.hip):
+
+    upsample_argmax(seg, (Gh, Gw), r, out=pred[t])                       # the frame's label map, uint8 [Gh * r, Gw * r]
+    counts = mask_scores(pred[1:], truth[1:], num_objects)               # int64 [n, O, 6]: one launch for the sequence
+    J, F = davis_measures(counts)                                        # float64 [n, O] each, on the host"""
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import torch
 
@@ -24,6 +31,9 @@ from .knn import SPLITS_MAX, knn_weights
 K_MAX = 32           # IVIT_LOCAL_K_MAX
 CLASSES_MAX = 256    # IVIT_PROPAGATE_CLASSES_MAX
 C_MAX = 1024         # the widest rows of ivit_local_topk_i8
+R_MAX = 32           # IVIT_UPSAMPLE_R_MAX
+OBJECTS_MAX = 255    # IVIT_SCORES_OBJECTS_MAX
+RADIUS_MAX = 24      # IVIT_SCORES_RADIUS_MAX
 
 
 class TokenMemory:
@@ -120,3 +130,65 @@ class TokenMemory:
         slots with the weights exp(cos / T) (knn.knn_weights), normalised"""
         idx, cos = self.neighbours(q_int8, radius, k, frames)
         return self.mix(idx, knn_weights(cos, T), frames)
+
+
+def upsample_argmax(seg, grid, r, out=None):
+    """-> uint8 [Gh * r, Gw * r]: the argmax over the K classes of seg (float32 [Gh * Gw, K], what TokenMemory.propagate returns)
+    upsampled bilinearly by r with align_corners=False -- the library's exact float64 definition (ivit_upsample_argmax_u8), the
+    lowest class among equals; the upsampled planes never exist.  out: a dense uint8 [Gh * r, Gw * r] tensor to write into."""
+    who = "upsample_argmax"
+    (Gh, Gw), r = (int(v) for v in grid), int(r)
+    if seg.dim() != 2 or not seg.is_cuda or seg.dtype != torch.float32 or int(seg.shape[0]) != Gh * Gw or Gh < 1 or Gw < 1:
+        raise ValueError(f"{who}: float32 soft labels [{Gh} * {Gw}, K] on the device wanted, got {seg.dtype} {tuple(seg.shape)} on {seg.device}")
+    K = int(seg.shape[1])
+    if not 1 <= r <= R_MAX or not 1 <= K <= CLASSES_MAX:
+        raise ValueError(f"{who}: r={r} outside [1, {R_MAX}] or K={K} classes outside [1, {CLASSES_MAX}]")
+    seg = seg.contiguous()
+    if out is None:
+        out = torch.empty(Gh * r, Gw * r, dtype=torch.uint8, device=seg.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (Gh * r, Gw * r) or not out.is_contiguous() or out.device != seg.device:
+        raise ValueError(f"{who}: out must be a dense uint8 [{Gh * r}, {Gw * r}] tensor on {seg.device}, got {out.dtype} {tuple(out.shape)}")
+    _lib.call("ivit_upsample_argmax_u8", _lib.ptr(seg), Gh, Gw, r, K, _lib.ptr(out), _lib.stream_ptr())
+    return out
+
+
+def bound_radius(bound_th, H, W):
+    """the boundary tolerance in pixels of davis2017-evaluation's f_measure: bound_th itself from 1, else ceil(bound_th * |(H, W)|)"""
+    return int(bound_th) if bound_th >= 1 else int(math.ceil(bound_th * math.sqrt(H * H + W * W)))
+
+
+def mask_scores(pred, truth, num_objects, bound_th=0.008):
+    """-> int64 [n, O, 6] on the device: inter, union, n_fg, n_gt, fg_match, gt_match of the object masks (label == o, o = 1 .. O) of two
+    uint8 [n, H, W] stacks of label maps (ivit_mask_scores_u8): the counts of the region similarity J and of the boundary measure F
+    with the tolerance bound_radius(bound_th, H, W).  One launch for all frames and objects, no host synchronisation."""
+    who = "mask_scores"
+    if pred.dim() != 3 or pred.shape != truth.shape or pred.dtype != torch.uint8 or truth.dtype != torch.uint8 or not pred.is_cuda \
+            or truth.device != pred.device:
+        raise ValueError(f"{who}: two uint8 [n, H, W] stacks on one device wanted, got {pred.dtype} {tuple(pred.shape)} on {pred.device} and "
+                         f"{truth.dtype} {tuple(truth.shape)} on {truth.device}")
+    n, H, W = (int(v) for v in pred.shape)
+    O = int(num_objects)
+    if not 1 <= O <= OBJECTS_MAX or H < 2 or W < 2 or H * W >= 2 ** 31:
+        raise ValueError(f"{who}: {O} objects outside [1, {OBJECTS_MAX}] or frames of {H} x {W} pixels (at least 2 each, below 2^31)")
+    R = bound_radius(bound_th, H, W)
+    if not 0 <= R <= RADIUS_MAX:
+        raise ValueError(f"{who}: bound_th={bound_th} is a radius of R={R} pixels at {H} x {W}, outside [0, {RADIUS_MAX}]")
+    counts = torch.empty(n, O, 6, dtype=torch.int64, device=pred.device)
+    _lib.call("ivit_mask_scores_u8", _lib.ptr(pred.contiguous()), _lib.ptr(truth.contiguous()), n, H, W, O, R, _lib.ptr(counts), _lib.stream_ptr())
+    return counts
+
+
+def davis_measures(counts):
+    """counts [n, O, 6] (mask_scores) -> (J, F), float64 [n, O] each, on the host.  J = inter / union, 1 where the union is empty.
+    F = 2 P R / (P + R) (0 where P + R = 0) of the precision P = fg_match / n_fg and the recall R = gt_match / n_gt, with the
+    reference's empty cases: no predicted boundary gives P = 1, R = 0; no true boundary P = 0, R = 1; neither P = R = 1."""
+    c = torch.as_tensor(counts).detach().cpu().to(torch.float64)
+    if c.dim() != 3 or c.shape[2] != 6:
+        raise ValueError(f"davis_measures: counts of shape [n, O, 6] wanted, got {tuple(c.shape)}")
+    inter, union, n_fg, n_gt, fg_match, gt_match = c.unbind(2)
+    one, zero = torch.ones_like(inter), torch.zeros_like(inter)
+    J = torch.where(union == 0, one, inter / union.clamp(min=1))
+    P = torch.where(n_fg == 0, one, torch.where(n_gt == 0, zero, fg_match / n_fg.clamp(min=1)))
+    Rc = torch.where(n_gt == 0, one, torch.where(n_fg == 0, zero, gt_match / n_gt.clamp(min=1)))
+    F = torch.where(P + Rc == 0, zero, 2 * P * Rc / torch.where(P + Rc == 0, one, P + Rc))
+    return J, F

@@ -1206,6 +1206,42 @@ int ivit_local_topk_i8(const int8_t* q, int64_t ldq, int Gh, int Gw, const int8_
 int ivit_propagate_labels_f32(const int32_t* idx, const float* w, int T, int k, const float* seg, int N, int K, float* out,
                               ivit_stream_t stream);
 
+/* ---- video segmentation scoring: the label map of a frame's soft labels, and the J / F counts of label maps (DAVIS) -------------
+ * ivit_upsample_argmax_u8: seg float32 [Gh * Gw][K] dense, what ivit_propagate_labels_f32 writes for a frame; pred uint8
+ * [Gh * r][Gw * r] dense.  The K planes are upsampled bilinearly by the integer factor r (align_corners = False) and the label is the
+ * argmax -- this library's own exact definition, not torch's float32 interpolate, and never stored.  On an axis with G cells, for
+ * the output coordinate y:
+ *   n = max(2y + 1 - r, 0);  y0 = n div 2r, a1 = n mod 2r, a0 = 2r - a1;  y1 = min(y0 + 1, G - 1)
+ * For the pixel (y, x) and the class k, with the integer weights w_ij = ay_i * ax_j and s_ij = seg[(y_i * Gw + x_j) * K + k]:
+ *   v_k = fl64(fl64(w00 * s00 + w01 * s01) + fl64(w10 * s10 + w11 * s11))
+ * every product ONE float64 multiplication (exact: 13 bits times 24), the three additions float64 in that order (no fused
+ * multiply-add); the division by (2r)^2 is omitted.  pred[y][x] = the smallest k of maximal v_k (float comparison, -0 == +0).  A NaN
+ * in seg is outside the contract.  Geometry: 1 <= r <= IVIT_UPSAMPLE_R_MAX, 1 <= K <= IVIT_PROPAGATE_CLASSES_MAX, Gh, Gw >= 1, fewer
+ * than 2^31 pixels and fewer than 2^31 elements of seg.  pred may have any alignment (aligned to 4 bytes with Gw * r % 4 == 0 it is
+ * written a dword at a time).  One launch.
+ * Errors, nothing launched and nothing written: IVIT_ERR_INVALID for a NULL operand, a misaligned seg, Gh or Gw below 1, 2^31 pixels
+ * or elements or more; IVIT_ERR_UNSUPPORTED ("unsupported geometry") for r or K outside their range.
+ *
+ * ivit_mask_scores_u8: pred and truth uint8 [n][H][W] dense label maps (0 the background, o = 1 .. num_objects the objects, larger
+ * labels belong to no object); counts int64 [n][num_objects][6] dense, ZEROED by the entry, then for the frame f and the object o
+ *   counts[f][o - 1] = { inter, union, n_fg, n_gt, fg_match, gt_match }
+ * of the binary masks m = (map == o): inter = |m_pred & m_truth|, union = |m_pred | m_truth|, and the boundary measure of
+ * davis2017-evaluation (f_measure / _seg2bmap at the mask's own size, no void pixels): with E = m[y][x + 1], S = m[y + 1][x],
+ * SE = m[y + 1][x + 1] the boundary map is b = (m ^ E) | (m ^ S) | (m ^ SE) for y < H - 1 and x < W - 1, m ^ E on the last row, m ^ S
+ * on the last column, 0 at the last pixel; dil(b)[y][x] = 1 iff b[y + dy][x + dx] = 1 for some dx^2 + dy^2 <= radius^2 inside the
+ * image (the disk of the reference's dilation); n_fg = |b_pred|, n_gt = |b_truth|, fg_match = |b_pred & dil(b_truth)|, gt_match =
+ * |b_truth & dil(b_pred)|.  Integer sums: one result for any tiling and any order.  Geometry: 1 <= num_objects <=
+ * IVIT_SCORES_OBJECTS_MAX, 0 <= radius <= IVIT_SCORES_RADIUS_MAX, H, W >= 2, H * W < 2^31 per frame, n >= 0 (n == 0: IVIT_OK, nothing
+ * launched).  Two launches (the zeroing, the counts); counts receives one 64-bit atomic per counter, object and workgroup.
+ * Errors, nothing launched and nothing written: IVIT_ERR_INVALID for a NULL operand, a misaligned counts, n < 0, too many
+ * workgroups; IVIT_ERR_UNSUPPORTED ("unsupported geometry") for num_objects, radius, H or W outside their range. */
+#define IVIT_UPSAMPLE_R_MAX 32
+#define IVIT_SCORES_OBJECTS_MAX 255
+#define IVIT_SCORES_RADIUS_MAX 24
+int ivit_upsample_argmax_u8(const float* seg, int Gh, int Gw, int r, int K, uint8_t* pred, ivit_stream_t stream);
+int ivit_mask_scores_u8(const uint8_t* pred, const uint8_t* truth, int n, int H, int W, int num_objects, int radius, int64_t* counts,
+                        ivit_stream_t stream);
+
 /* ---- linear probe on an int8 feature bank: the exact integer statistics of a closed-form classifier ---------------------------
  * Everything least squares onto one-hot targets (or a class-mean classifier) needs from a bank x of `rows` int8 rows of C channels
  * (row stride ldx >= C in elements) is a sum of integers: the Gram matrix, the per-class row sums and the class counts.  They are
