@@ -12,3 +12,4 @@ from .knn import FeatureBank, knn_classify, retrieval_ap  # noqa: F401
 from .probe import BankStats, LinearProbe, LogisticTrainer, fit_logistic  # noqa: F401
 from .dense import DenseProbe, miou, patch_labels  # noqa: F401
 from .propagate import davis_measures, mask_scores, upsample_argmax  # noqa: F401
+from .discover import boxes_to_pixels, corloc, discover_objects, token_degrees  # noqa: F401

@@ -177,6 +177,10 @@ SIGNATURES = {
     # counts, stream
     "ivit_upsample_argmax_u8": [vp, ci, ci, ci, ci, vp, vp],
     "ivit_mask_scores_u8": [vp, vp, ci, ci, ci, ci, ci, vp, vp],
+    # object discovery (include/ivit_hip.h, end): tokens, ld, image_stride, B, Gh, Gw, C, deg, stream; tokens, ld, image_stride, B, Gh,
+    # Gw, C, deg, k, boxes, seed, rows, stream
+    "ivit_token_degrees_i8": [vp, i64, i64, ci, ci, ci, ci, vp, vp],
+    "ivit_discover_boxes_i8": [vp, i64, i64, ci, ci, ci, ci, vp, ci, vp, vp, vp, vp],
     # linear probe on the int8 feature bank (include/ivit_hip.h, end): ivit_gram_workspace_bytes is a host function
     "ivit_gram_i8_i64": [vp, i64, i64, ci, ci, ci, vp, vp, i64, vp],
     "ivit_gram_workspace_bytes": [i64, ci, ci, vp],

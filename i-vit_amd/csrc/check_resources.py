@@ -12,7 +12,7 @@ change that breaks the budget must fail the build here, on the CPU, not on the G
 wait without spilling.  csrc/check_isa.py checks the emitted instruction stream for exactly that; the bit-exact GEMM tests on the
 GPU remain the proof of the result.
 
-Second use (`check_resources.py <remarks> attention|rowops|swin|calib|features|knn|propagate|davis|probe|logistic|dense`): the occupancy the launchers of those files assume
+Second use (`check_resources.py <remarks> attention|rowops|swin|calib|features|knn|propagate|davis|discover|probe|logistic|dense`): the occupancy the launchers of those files assume
 when they size their grids (occupancy_rules below)."""
 import re
 import sys
@@ -173,6 +173,16 @@ def occupancy_rules(path, what):
                 continue
             occ, need_no_scratch = (2 if "mask_scores_kernel" in name else 1), True
             if "mask_scores_kernel" in name and r.get("LDS", 0) > 81920:
+                print("FAIL", name, "LDS", r.get("LDS"), "above 80 KiB: two workgroups no longer fit a CU")
+                return 1
+        elif what == "discover":
+            # token_degrees_kernel<KSMAX> (discover.hip): two workgroups of four waves per CU (its __launch_bounds__) beside 34.3 KiB
+            # of LDS each; the query operands, accumulators and staged pieces are indexed by constants only: no scratch.
+            # discover_boxes_kernel: one workgroup per image, its launcher assumes no number of resident workgroups: no scratch
+            if not re.search(r"token_degrees_kernel|discover_boxes_kernel", name):
+                continue
+            occ, need_no_scratch = (2 if "token_degrees_kernel" in name else 1), True
+            if "token_degrees_kernel" in name and r.get("LDS", 0) > 81920:
                 print("FAIL", name, "LDS", r.get("LDS"), "above 80 KiB: two workgroups no longer fit a CU")
                 return 1
         elif what == "probe":

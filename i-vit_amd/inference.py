@@ -632,6 +632,39 @@ def evaluate_davis(model, sequences, device, *, n_last: int = 7, radius: int = 1
     return out
 
 
+def evaluate_object_discovery(model, loader, device, k: int = 100):
+    """Unsupervised single-object discovery (LOST's seed expansion) scored by CorLoc -> {"CorLoc": %, "per_image": [(hit, IoU), ...]}:
+    the share of images whose discovered box has an intersection over union of at least 0.5 with one of the image's ground-truth
+    boxes.  loader yields (images [B, 3, H, W], a list of B ground-truth box lists, (x0, y0, x1, y1) in pixels).  The int8 patch tokens
+    of model.forward_tokens(x, integers=True) (a ViT's last block, a Swin's last stage) go through discover.discover_objects: two
+    launches and ONE readback (the boxes) per batch; the IoU is float64 on the host (discover.corloc).  A model without the engine
+    path is refused with features_unsupported_reason()'s text before the loader is touched."""
+    from .discover import K_MAX, boxes_to_pixels, corloc, discover_objects
+    who = "evaluate_object_discovery"
+    if not hasattr(model, "forward_tokens") or not hasattr(model, "features_unsupported_reason"):
+        raise ValueError(f"{who}: {type(model).__name__} has no forward_tokens")
+    reason = model.features_unsupported_reason()
+    if reason is not None:
+        raise ValueError(f"{who}: the tokens come from the fused engine, which does not take this model: {reason}")
+    if not 1 <= int(k) <= K_MAX:
+        raise ValueError(f"{who}: k={k} outside [1, {K_MAX}]")
+    per_image = []
+    model.eval()
+    with torch.no_grad():
+        for imgs, gts in loader:
+            if int(imgs.shape[0]) == 0:
+                continue
+            tok, _, grid, r = _patch_tokens(model, imgs.to(device))
+            if tok.stride(2) != 1 or tok.stride(1) % 16 or tok.stride(0) % 16 or tok.data_ptr() % 16:
+                tok = tok.contiguous()
+            boxes = discover_objects(tok, grid, k)[0]
+            hits, iou = corloc(boxes_to_pixels(boxes, r), gts)
+            per_image += list(zip(hits.tolist(), iou.tolist()))
+    if not per_image:
+        raise ValueError(f"{who}: no image")
+    return {"CorLoc": 100.0 * sum(h for h, _ in per_image) / len(per_image), "per_image": per_image}
+
+
 def extract_features_parallel(model, data_loader, device, *, transform=None, graph: bool = False, integers: bool = False,
                               n_last: int = 1, avgpool: bool = False, wide: bool = False):
     """extract_features data-parallel over the ranks of the default process group (world 1 without one) -> the same (features [N, C],

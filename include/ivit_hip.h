@@ -1242,6 +1242,37 @@ int ivit_upsample_argmax_u8(const float* seg, int Gh, int Gw, int r, int K, uint
 int ivit_mask_scores_u8(const uint8_t* pred, const uint8_t* truth, int n, int H, int W, int num_objects, int radius, int64_t* counts,
                         ivit_stream_t stream);
 
+/* ---- object discovery on int8 patch tokens: seed expansion on the token affinities of one image (LOST, scored by CorLoc) --------
+ * tokens: B images of hw = Gh * Gw int8 tokens of C channels; the token (y, x) of image b is the row y * Gw + x at
+ * tokens + b * image_stride + row * ld (both strides in elements; ld >= C; image_stride >= 0, otherwise free: images may overlap or
+ * lie apart).  tokens, ld and image_stride are multiples of 16 bytes; elements C .. ld - 1 of a row and rows from hw on are not
+ * read.  Geometry: B >= 1, 1 <= Gh, Gw <= IVIT_DISCOVER_GRID_MAX, C % 64 == 0, 64 <= C <= 1024.  Within an image let
+ * d(i, j) = sum_c t[i][c] * t[j][c], an exact integer (|d| <= 1024 * 127^2 < 2^24).  Every output is an exact integer statement, so
+ * it does not depend on the tiling:
+ *   1. deg[i] = #{ j != i : d(i, j) > 0 }
+ *   2. the tokens in the order (deg ascending, index ascending); the seed is the first, the potentials the first min(k, hw)
+ *   3. the similars: the seed and every potential p with d(seed, p) > 0
+ *   4. M[j] = sum over the similars s of d(s, j), in int32 (|M| <= 127^2 * 1024 * 128 = 2 114 060 288 < 2^31)
+ *   5. the mask M[j] > 0 on the Gh x Gw grid; the component: the 4-connected component of the mask that holds the seed, the seed's
+ *      cell alone where the mask does not hold it (an all-zero seed row)
+ *   6. the box (x0, y0, x1, y1) in grid cells, inclusive: the smallest and largest column and row of the component
+ *
+ * ivit_token_degrees_i8: step 1.  deg int32 [B][hw] dense.  One launch, (query tile, image) workgroups on
+ * v_mfma_i32_16x16x64_i8; no [hw][hw] matrix and no atomics.
+ *
+ * ivit_discover_boxes_i8: steps 2 - 6 from tokens and the deg of the first entry (a value outside [0, 4095] counts as 4095: nothing
+ * else is checked on the device).  1 <= k <= IVIT_DISCOVER_K_MAX.  boxes int32 [B][4], seed int32 [B]; rows (uint64 [B][Gh], or
+ * NULL): the component, bit x of rows[b][y] set for the cell (y, x).  One launch, one workgroup per image.
+ * Errors of both, nothing launched and nothing written: IVIT_ERR_INVALID for a NULL operand (rows excepted), B, Gh or Gw below 1,
+ * ld < C, image_stride < 0, k outside its range, a misaligned tokens, ld, image_stride or output; IVIT_ERR_UNSUPPORTED
+ * ("unsupported geometry") for Gh or Gw above IVIT_DISCOVER_GRID_MAX and for any other C. */
+#define IVIT_DISCOVER_GRID_MAX 64
+#define IVIT_DISCOVER_K_MAX 128
+int ivit_token_degrees_i8(const int8_t* tokens, int64_t ld, int64_t image_stride, int B, int Gh, int Gw, int C, int32_t* deg,
+                          ivit_stream_t stream);
+int ivit_discover_boxes_i8(const int8_t* tokens, int64_t ld, int64_t image_stride, int B, int Gh, int Gw, int C, const int32_t* deg, int k,
+                           int32_t* boxes, int32_t* seed, uint64_t* rows, ivit_stream_t stream);
+
 /* ---- linear probe on an int8 feature bank: the exact integer statistics of a closed-form classifier ---------------------------
  * Everything least squares onto one-hot targets (or a class-mean classifier) needs from a bank x of `rows` int8 rows of C channels
  * (row stride ldx >= C in elements) is a sum of integers: the Gram matrix, the per-class row sums and the class counts.  They are
