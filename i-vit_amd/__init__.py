@@ -13,3 +13,4 @@ from .probe import BankStats, LinearProbe, LogisticTrainer, fit_logistic  # noqa
 from .dense import DenseProbe, miou, patch_labels  # noqa: F401
 from .propagate import davis_measures, mask_scores, upsample_argmax  # noqa: F401
 from .discover import boxes_to_pixels, corloc, discover_objects, token_degrees  # noqa: F401
+from .cluster import KMeans, partition_scores  # noqa: F401

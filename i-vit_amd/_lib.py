@@ -181,6 +181,10 @@ SIGNATURES = {
     # Gw, C, deg, k, boxes, seed, rows, stream
     "ivit_token_degrees_i8": [vp, i64, i64, ci, ci, ci, ci, vp, vp],
     "ivit_discover_boxes_i8": [vp, i64, i64, ci, ci, ci, ci, vp, ci, vp, vp, vp, vp],
+    # k-means on the int8 feature bank (include/ivit_hip.h, end): x, ldx, rows, C, hi, lo, cnorm, K, label, dist, stream; sums, counts,
+    # K, C, hi, lo, cnorm, changed, stream
+    "ivit_kmeans_assign_i8": [vp, i64, i64, ci, vp, vp, vp, ci, vp, vp, vp],
+    "ivit_kmeans_update_i16": [vp, vp, ci, ci, vp, vp, vp, vp, vp],
     # linear probe on the int8 feature bank (include/ivit_hip.h, end): ivit_gram_workspace_bytes is a host function
     "ivit_gram_i8_i64": [vp, i64, i64, ci, ci, ci, vp, vp, i64, vp],
     "ivit_gram_workspace_bytes": [i64, ci, ci, vp],

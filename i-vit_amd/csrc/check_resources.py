@@ -12,7 +12,7 @@ change that breaks the budget must fail the build here, on the CPU, not on the G
 wait without spilling.  csrc/check_isa.py checks the emitted instruction stream for exactly that; the bit-exact GEMM tests on the
 GPU remain the proof of the result.
 
-Second use (`check_resources.py <remarks> attention|rowops|swin|calib|features|knn|propagate|davis|discover|probe|logistic|dense`): the occupancy the launchers of those files assume
+Second use (`check_resources.py <remarks> attention|rowops|swin|calib|features|knn|propagate|davis|discover|kmeans|probe|logistic|dense`): the occupancy the launchers of those files assume
 when they size their grids (occupancy_rules below)."""
 import re
 import sys
@@ -183,6 +183,16 @@ def occupancy_rules(path, what):
                 continue
             occ, need_no_scratch = (2 if "token_degrees_kernel" in name else 1), True
             if "token_degrees_kernel" in name and r.get("LDS", 0) > 81920:
+                print("FAIL", name, "LDS", r.get("LDS"), "above 80 KiB: two workgroups no longer fit a CU")
+                return 1
+        elif what == "kmeans":
+            # kmeans_assign_kernel<KSMAX> (kmeans.hip): two workgroups of four waves per CU (its __launch_bounds__) beside 37.5 KiB of
+            # LDS each; the row operands, the accumulators of both planes and the staged pieces are indexed by constants only: no
+            # scratch.  kmeans_update_kernel: one wave per centroid, its launcher assumes no number of resident workgroups: no scratch
+            if not re.search(r"kmeans_assign_kernel|kmeans_update_kernel", name):
+                continue
+            occ, need_no_scratch = (2 if "kmeans_assign_kernel" in name else 1), True
+            if "kmeans_assign_kernel" in name and r.get("LDS", 0) > 81920:
                 print("FAIL", name, "LDS", r.get("LDS"), "above 80 KiB: two workgroups no longer fit a CU")
                 return 1
         elif what == "probe":

@@ -665,6 +665,33 @@ def evaluate_object_discovery(model, loader, device, k: int = 100):
     return {"CorLoc": 100.0 * sum(h for h, _ in per_image) / len(per_image), "per_image": per_image}
 
 
+def evaluate_clustering(model, loader, device, num_clusters, iters: int = 20, seed: int = 0, n_last: int = 1, avgpool: bool = False,
+                        wide: bool = False):
+    """Unsupervised classification of a backbone's features -> {"NMI", "ARI", "purity", "inertia", "iterations"}: ONE
+    extract_features(..., integers=True), ONE cluster.KMeans.fit on the int8 bank in place (integer Lloyd iterations on the int8
+    MFMA, csrc/kmeans.hip; the initial centroids are the first num_clusters rows of a CPU randperm seeded with `seed`) and
+    cluster.partition_scores of its labels against the loader's targets, float64 on the host.  n_last, avgpool: the pooled feature
+    of extract_features.  The width (a multiple of 64 from 64 to 1024) and num_clusters are checked before the loader is touched;
+    wide=True is refused: there is no wide assignment kernel.  Patch tokens cluster the same way without this function:
+    forward_tokens(x, integers=True) tokens go into KMeans.fit directly after a reshape to [B * hw, C]."""
+    from .cluster import K_MAX, KMeans, partition_scores
+    who = "evaluate_clustering"
+    if wide:
+        raise ValueError(f"{who}: wide=True: there is no wide assignment kernel (rows of at most {C_NARROW_MAX} channels)")
+    pooled = {} if int(n_last) == 1 and not avgpool else dict(n_last=n_last, avgpool=avgpool)
+    C = pooled_width(model, n_last, avgpool) if pooled else int(model.num_features)
+    if C % 64 != 0 or not 64 <= C <= C_NARROW_MAX:
+        raise ValueError(f"{who}: features of C={C} channels: the assignment kernel takes multiples of 64 from 64 to {C_NARROW_MAX}")
+    if not 1 <= int(num_clusters) <= K_MAX:
+        raise ValueError(f"{who}: num_clusters={num_clusters} outside [1, {K_MAX}]")
+    rows, targets, _ = extract_features(model, loader, device, integers=True, **pooled)
+    km = KMeans(C, num_clusters, rows.device)
+    labels = km.fit(rows, iters=iters, seed=seed)
+    out = partition_scores(labels, targets)
+    out.update(inertia=km.inertia, iterations=len(km.history))
+    return out
+
+
 def extract_features_parallel(model, data_loader, device, *, transform=None, graph: bool = False, integers: bool = False,
                               n_last: int = 1, avgpool: bool = False, wide: bool = False):
     """extract_features data-parallel over the ranks of the default process group (world 1 without one) -> the same (features [N, C],

@@ -1438,6 +1438,41 @@ int ivit_ibert_layernorm_pool_i16(const int16_t* x, int64_t ldx, int B, int T_al
 int ivit_layernorm_pool_slab_rows(int B, int T, int* rows);
 int ivit_layernorm_pool_workspace_bytes(int B, int T, int C, int64_t* bytes);
 
+/* ---- k-means on the int8 feature bank: Lloyd's iteration with fixed-point centroids, an exact integer algorithm -----------------
+ * The bank x holds `rows` int8 rows of C channels, row stride ldx >= C in elements; x and ldx are multiples of 16 bytes, row offsets
+ * are 64-bit products and elements C .. ldx - 1 of a row are not read.  C % 64 == 0, 64 <= C <= 1024; 1 <= K <= IVIT_KMEANS_K_MAX;
+ * 0 <= rows < 2^31 (rows == 0: nothing is launched).  Any int8 value may occur, -128 included.
+ * A centroid is an int16 vector c16[k][c] with 7 fractional bits -- the centroid is c16 / 128 -- in [-16384, 16383], stored as two
+ * dense int8 planes [K][C] so that both go through the int8 MFMA: hi = c16 >> 7 (arithmetic shift, [-128, 127]) and lo = c16 & 127
+ * ([0, 127]), c16 = 128 * hi + lo.  cnorm[k] = sum_c c16[k][c]^2, int64, below 2^38.  A centroid taken from bank row i is
+ * c16 = 128 * x_i: hi = x_i, lo = 0.  One iteration is three integer statements, so a whole trajectory depends on its initial
+ * centroids and on nothing else:
+ *   1. assign: D(r, k) = cnorm[k] - 256 * (128 * dot(x_r, hi_k) + dot(x_r, lo_k)).  The two dots are exact int32 (each at most
+ *      2^24 in magnitude); their combination is 64-bit (at C = 1024, x = -128 and c16 = -16384 the product term is 2^39).
+ *      label[r] = the k of smallest D, equal D to the lower k; dist[r] = D(r, label[r]) + 16384 * sum_c x_r[c]^2 =
+ *      |128 * x_r - c16_label|^2, int64 in [0, 2^40]
+ *   2. sums: S[k][c] = the sum of the rows labelled k, int64, n[k] their count (ivit_group_sums_i8_i64 on the CSR form of label)
+ *   3. update: for n[k] > 0, c16[k][c] = floor((256 * S[k][c] + n[k]) / (2 * n[k])) -- 128 * mean rounded half up, the floor
+ *      towards -inf -- which lies in [-16384, 16256]; for n[k] == 0 the centroid keeps its value.  changed[k] = 1 if any element
+ *      of c16[k] moved, else 0
+ *
+ * ivit_kmeans_assign_i8: step 1.  label int32 [rows], dist int64 [rows], dense.  One launch on v_mfma_i32_16x16x64_i8: a workgroup
+ * keeps 128 bank rows in registers and streams the centroid planes through LDS; every bank row is read once; no [rows][K] matrix, no
+ * atomics, no float.  cnorm is taken as given (a cnorm that is not the planes' gives another, still unique, answer).
+ * Errors, nothing launched and nothing written: IVIT_ERR_INVALID for a NULL operand, rows outside [0, 2^31), K outside its range,
+ * ldx < C, x, ldx, hi or lo not a multiple of 16 bytes, cnorm, dist or label not aligned to its element; IVIT_ERR_UNSUPPORTED
+ * ("unsupported geometry") for any other C.
+ *
+ * ivit_kmeans_update_i16: step 3, in place on the planes, from sums int64 [K][C] and counts int64 [K]; writes cnorm[k] and
+ * changed[k] (int32 [K]) for every k (an empty cluster: changed[k] = 0, planes and cnorm untouched).  One launch, one wave per
+ * centroid.  Errors, nothing launched: IVIT_ERR_INVALID for a NULL or misaligned operand or K outside its range;
+ * IVIT_ERR_UNSUPPORTED for any other C. */
+#define IVIT_KMEANS_K_MAX 65536
+int ivit_kmeans_assign_i8(const int8_t* x, int64_t ldx, int64_t rows, int C, const int8_t* hi, const int8_t* lo, const int64_t* cnorm, int K,
+                          int32_t* label, int64_t* dist, ivit_stream_t stream);
+int ivit_kmeans_update_i16(const int64_t* sums, const int64_t* counts, int K, int C, int8_t* hi, int8_t* lo, int64_t* cnorm,
+                           int32_t* changed, ivit_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
